@@ -94,6 +94,10 @@ def parse_args():
                          'images/s with the letterbox on the compute stream (profiles/r4_bench_pre_stream.txt) -- its '
                          'workgroups keep the 8-wave conv workgroups off their CUs; off by default')
     ap.add_argument('--profile-out', default=None, help='write per-op timings (json) here')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write the formatted detections of the last timed step (what a caller of the '
+                         'hot path receives) and its raw NMS rows as DIR/<name>.npy (dump_outputs); the inputs are seeded, so '
+                         'two builds run with the same arguments can be compared output for output')
     ap.add_argument('--no-extra-configs', action='store_true',
                     help='skip the short legs of the other BASELINE configurations (extra_configs: fp8 batch 64, 1080p video '
                          'frames, 4:3 real shape, fp16 storage); they only run with the default headline workload on one GPU')
@@ -104,7 +108,47 @@ def parse_args():
     ap.add_argument('--rendezvous-check', action='store_true',
                     help='launch-contract check without a GPU: every rank joins a gloo group, rank 0 prints {"n_gpus": world, '
                          '"ranks": [...]} and exits (tests/test_bench_launch.py runs `bench.py --gpus 2 --rendezvous-check`)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, results, nms=None, max_det=300):
+    """What the last timed step returned -- per image (detections, max_conf) of format_detections -- as float64 arrays:
+    num_detections (B,), max_conf (B,), category / conf (B, max_det) and bbox (B, max_det, 4) in the order the caller
+    receives the detections, NaN past num_detections; image_index (B,) names the images.  With `nms` = (det, counts) of
+    that step (mdhip_nms_wait: confidence-descending [x1, y1, x2, y2, conf, cls] rows in letterboxed pixels, before the
+    truncation of the formatting) also nms_det (B, max_det, 6, float32, NaN past the count) and nms_num_detections (B,).
+    Above DUMP_MAX_BYTES a fixed seeded sample of the images is written instead of all of them."""
+    per_image = (3 + 6 * max_det) * 8 + (1 + 6 * max_det // 2) * 8 * (nms is not None)
+    idx = np.arange(len(results))
+    if len(idx) * per_image > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(len(idx), DUMP_MAX_BYTES // per_image, replace=False))
+    n = len(idx)
+    arrays = {'image_index': idx.astype(np.float64), 'num_detections': np.zeros(n), 'max_conf': np.zeros(n),
+              'category': np.full((n, max_det), np.nan), 'conf': np.full((n, max_det), np.nan),
+              'bbox': np.full((n, max_det, 4), np.nan)}
+    for j, i in enumerate(idx):
+        dets, max_conf = results[i]
+        arrays['num_detections'][j] = len(dets)
+        arrays['max_conf'][j] = max_conf
+        for k, d in enumerate(dets):
+            arrays['category'][j, k] = float(d['category'])
+            arrays['conf'][j, k] = d['conf']
+            arrays['bbox'][j, k] = d['bbox']
+    if nms is not None:
+        det, counts = nms
+        arrays['nms_num_detections'] = counts[idx].astype(np.float64)
+        arrays['nms_det'] = np.full((n, max_det, 6), np.nan, dtype=np.float32)
+        for j, i in enumerate(idx):
+            arrays['nms_det'][j, :counts[i]] = det[i, :counts[i]]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def self_launch(args):
@@ -129,28 +173,41 @@ def init_control_plane(torch, rank, world, local_rank, force_gloo, timeout_s=300
     a second group: created, exercised with one all-reduce, and adopted only if EVERY rank got through (agreed over the
     gloo group).  Returns (dist, group, on_host, name, why): `group` carries barriers / reductions (None = the default gloo
     group), `on_host` says where its tensors live, `name` ('rccl' | 'gloo') goes into the JSON line, with `why` when RCCL
-    was not used."""
+    was not used.
+    No rank may wait in an RCCL collective for a rank that has already given up: the group is created without device_id
+    (creating it is then local -- the communicator comes up in the group's first collective), the ranks agree over gloo
+    that every one of them has the group before any of them enters that first all-reduce, and agree again afterwards."""
     import datetime
     import torch.distributed as dist
     os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
     dist.init_process_group('gloo', rank=rank, world_size=world, timeout=datetime.timedelta(seconds=timeout_s))
     if force_gloo:
         return dist, None, True, 'gloo', 'asked for (MDHIP_BENCH_BACKEND=gloo or the one-GPU test hook)'
+
+    def every(ok):                                           # over gloo: every rank or none
+        flag = torch.tensor([ok], dtype=torch.int64)
+        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+        return int(flag.item()) == 1
+
+    def failed(e):
+        return '{}: {}'.format(type(e).__name__, str(e).splitlines()[0][:200] if str(e) else '')
+
     ok, why, group = 1, '', None
     try:
-        group = dist.new_group(backend='nccl', timeout=datetime.timedelta(seconds=nccl_timeout_s),
-                               device_id=torch.device('cuda', local_rank))
-        t = torch.ones(1, device='cuda')
-        dist.all_reduce(t, group=group)
-        torch.cuda.synchronize()
-        if int(t.item()) != world:
-            raise RuntimeError('RCCL all-reduce returned {} for a world of {}'.format(int(t.item()), world))
+        group = dist.new_group(backend='nccl', timeout=datetime.timedelta(seconds=nccl_timeout_s))
+        t = torch.ones(1, device=torch.device('cuda', local_rank))
     except Exception as e:                                   # RCCL missing / refusing this box: the host plane carries on
-        ok, why = 0, '{}: {}'.format(type(e).__name__, str(e).splitlines()[0][:200] if str(e) else '')
-    flag = torch.tensor([ok], dtype=torch.int64)
-    dist.all_reduce(flag, op=dist.ReduceOp.MIN)               # over gloo: every rank or none
-    if int(flag.item()) == 1:
-        return dist, group, False, 'rccl', ''
+        ok, why = 0, failed(e)
+    if every(ok):
+        try:
+            dist.all_reduce(t, group=group)
+            torch.cuda.synchronize()
+            if int(t.item()) != world:
+                raise RuntimeError('RCCL all-reduce returned {} for a world of {}'.format(int(t.item()), world))
+        except Exception as e:
+            ok, why = 0, failed(e)
+        if every(ok):
+            return dist, group, False, 'rccl', ''
     if ok:
         why = 'another rank could not initialise RCCL'
     print('rank {}: RCCL control plane not available ({}): barriers over gloo'.format(rank, why), file=sys.stderr)
@@ -383,6 +440,7 @@ class Workload:
     def collect(self, i):
         from megadetector_amd.postprocess import format_detections
         det, counts = self.ctx.nms_wait(slot=i % 4)
+        self.last_nms = (det, counts)        # views of the pinned slot: valid until step i + 4 is enqueued (--dump-outputs)
         return [format_detections(det[b, :counts[b]], (self.Hn, self.Wn), (self.H0, self.W0, 3), (self.H0, self.W0, 3),
                                   self.threshold) for b in range(self.B)]
 
@@ -621,6 +679,8 @@ def main():
         per_rank = [round(B * args.steps / float(x.item()), 2) for x in allt]
     else:
         per_rank = [round(B * args.steps / my_elapsed, 2)]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, nms=wl.last_nms)
 
     # ---- per-stage and per-kernel timing (outside the timed region) --------------------
     stages = {}

@@ -54,7 +54,8 @@ sys.path.insert(0, {repo!r})
 import torch, bench
 rank, world = int(os.environ['RANK']), int(os.environ['WORLD_SIZE'])
 if os.environ.get('FAIL_ON_RANK') == str(rank):
-    # one rank alone cannot start the device plane: every rank has to end up on the host plane
+    # one rank alone cannot start the device plane, and fails before the group exists: every rank has to end up on
+    # the host plane -- none may be left waiting in an RCCL collective for it
     import torch.distributed as d
     real = d.new_group
     def broken(*a, **k):
@@ -68,7 +69,7 @@ t = torch.tensor([float(rank + 1)], dtype=torch.float64)
 dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
 dist.barrier(group=group)
 allr = [None] * world
-dist.all_gather_object(allr, [name, on_host, bool(why)])
+dist.all_gather_object(allr, [name, on_host, why])
 if rank == 0:
     print(json.dumps({{'planes': allr, 'max': float(t.item())}}))
 dist.destroy_process_group()
@@ -94,6 +95,8 @@ def test_control_plane_falls_back_to_gloo_on_every_rank(tmp_path, mode):
     assert out['max'] == 2.0
     assert [p[0] for p in out['planes']] == ['gloo', 'gloo'] and all(p[1] for p in out['planes'])
     assert all(p[2] for p in out['planes'])                 # each rank says why RCCL is not carrying the barriers
+    if mode == 'one_rank_fails':                             # the injected failure is the one rank 1 reports
+        assert out['planes'][1][2].startswith('RuntimeError: injected'), out['planes']
 
 
 def test_bench_refuses_a_world_size_that_is_not_gpus():
@@ -169,3 +172,99 @@ def test_cpu_baseline_thread_sweep_stops_past_the_optimum_and_inside_the_budget(
     # a small host: its only count
     tried.clear()
     assert list(bench.thread_sweep(4, lambda c: (tried.append(c), 1.0)[1], 30.0, clock=lambda: 0.0)) == [4]
+
+
+def test_dump_outputs_writes_the_formatted_detections_of_a_step(tmp_path, monkeypatch):
+    """bench.py --dump-outputs DIR: the (detections, max_conf) per image of the last timed step as float64 arrays, NaN past
+    each image's count; above the size cap a fixed seeded sample of the images"""
+    import importlib
+    import numpy as np
+    bench = importlib.import_module('bench')
+    from megadetector_amd.postprocess import format_detections
+    rng = np.random.default_rng(3)
+    results = []
+    raw, counts = np.zeros((3, 300, 6), dtype=np.float32), np.zeros(3, dtype=np.int32)
+    for b, k in enumerate((5, 0, 300)):
+        det = np.zeros((k, 6), dtype=np.float32)
+        det[:, :2] = rng.uniform(0, 600, (k, 2))
+        det[:, 2:4] = det[:, :2] + rng.uniform(1, 600, (k, 2))
+        det[:, 4] = np.sort(rng.uniform(1e-5, 1, k))[::-1]
+        det[:, 5] = rng.integers(0, 3, k)
+        results.append(format_detections(det, (1280, 1280), (1280, 1280, 3), (1280, 1280, 3), 1e-5))
+        raw[b, :k], counts[b] = det, k
+    raw[0, 5:] = 7.0                                          # slot contents past the count are not output
+    bench.dump_outputs(str(tmp_path / 'all'), results, nms=(raw, counts))
+    got = {n: np.load(str(tmp_path / 'all' / (n + '.npy')))
+           for n in ('image_index', 'num_detections', 'max_conf', 'category', 'conf', 'bbox', 'nms_det', 'nms_num_detections')}
+    assert all(a.dtype == np.float64 for n, a in got.items() if n != 'nms_det') and got['nms_det'].dtype == np.float32
+    assert got['nms_num_detections'].tolist() == [5, 0, 300] and got['nms_det'].shape == (3, 300, 6)
+    for b, k in enumerate((5, 0, 300)):
+        assert np.array_equal(got['nms_det'][b, :k], raw[b, :k]) and np.isnan(got['nms_det'][b, k:]).all()
+    assert got['image_index'].tolist() == [0, 1, 2]
+    assert got['bbox'].shape == (3, 300, 4) and got['conf'].shape == got['category'].shape == (3, 300)
+    for i, (dets, max_conf) in enumerate(results):
+        n = len(dets)
+        assert got['num_detections'][i] == n and got['max_conf'][i] == max_conf
+        assert got['conf'][i, :n].tolist() == [d['conf'] for d in dets]
+        assert got['category'][i, :n].tolist() == [float(d['category']) for d in dets]
+        assert got['bbox'][i, :n].tolist() == [d['bbox'] for d in dets]
+        assert np.isnan(got['conf'][i, n:]).all() and np.isnan(got['bbox'][i, n:]).all()
+    # the cap: room for two images -> the same two every time
+    monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 2 * (3 + 6 * 300) * 8)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), results)
+    a, b = (np.load(str(tmp_path / d / 'image_index.npy')) for d in ('a', 'b'))
+    assert len(a) == 2 and a.tolist() == b.tolist()
+    i = int(a[0])
+    assert np.array_equal(np.load(str(tmp_path / 'a' / 'conf.npy'))[0], got['conf'][i], equal_nan=True)
+
+
+def test_bench_refuses_zero_timed_steps():
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--steps', '0', '--rendezvous-check'],
+                       env=_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and '--steps' in r.stderr
+
+
+@pytest.mark.gpu
+def test_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """bench.py --steps 3 --dump-outputs: the dump is the NMS output of the batch of the LAST timed step (seeded batch
+    (3 - 1) % 8), recomputed here through the C ABI on a context of its own, and the formatted detections are those rows
+    formatted"""
+    import numpy as np
+    import torch
+    from megadetector_amd import weights_io, yolo_yaml
+    from megadetector_amd.hip_backend import HipContext
+    from megadetector_amd.postprocess import format_detections, letterbox_geometry
+    B, S, steps, thr = 4, 256, 3, 1e-5
+    out = tmp_path / 'dump'
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '1',
+                        '--batch', str(B), '--size', str(S), '--model', 'YOLOV5N6_TEST', '--dtype', 'fp16', '--lean',
+                        '--no-cpu-baseline', '--no-extra-configs', '--dump-outputs', str(out)],
+                       env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1])['steps'] == steps
+    got = {p.stem: np.load(str(p)) for p in out.glob('*.npy')}
+
+    ctx = HipContext(weights_io.synthetic_weights(yolo_yaml.YOLOV5N6_TEST, seed=0), device=0, dtype='fp16', max_batch=B,
+                     max_h=S, max_w=S)
+    try:
+        gen = torch.Generator(device='cuda')
+        gen.manual_seed((steps - 1) % 8)
+        batch = torch.randint(0, 256, (B, S, S, 3), dtype=torch.uint8, device='cuda', generator=gen)
+        lb = letterbox_geometry((S, S), new_shape=S, stride=64, auto=True, scaleup=True)
+        Hn, Wn = lb['out_hw']
+        ctx.preprocess([int(batch[i].data_ptr()) for i in range(B)], [(S, S, lb['new_unpad'][1], lb['new_unpad'][0],
+                                                                       lb['top'], lb['left'])] * B, Hn, Wn)
+        ctx.forward(B, Hn, Wn)
+        det, counts = ctx.nms(B, thr, 0.45, 300)
+        torch.cuda.synchronize()
+    finally:
+        ctx.close()
+    assert got['nms_num_detections'].tolist() == counts.tolist() and counts.sum() > 0
+    for b in range(B):
+        k = int(counts[b])
+        assert np.array_equal(got['nms_det'][b, :k], det[b, :k]), b
+        dets, max_conf = format_detections(det[b, :k], (Hn, Wn), (S, S, 3), (S, S, 3), thr)
+        assert got['num_detections'][b] == len(dets) and got['max_conf'][b] == max_conf
+        assert got['conf'][b, :len(dets)].tolist() == [d['conf'] for d in dets]
+        assert got['bbox'][b, :len(dets)].tolist() == [d['bbox'] for d in dets]
