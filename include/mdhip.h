@@ -47,6 +47,10 @@ extern "C" {
 #define MDHIP_UPSAMPLE  3
 #define MDHIP_CONCAT    4
 #define MDHIP_DETECT    5
+/* module kinds of a YOLO11 model description (ultralytics yolo11.yaml rows, anchor-free; MDv1000-larch / -sorrel) */
+#define MDHIP_C3K2       6
+#define MDHIP_C2PSA      7
+#define MDHIP_DETECT_DFL 8
 
 /* One fused (conv + folded BatchNorm) of the checkpoint: what
  * pytorch_detector.py:957  checkpoint['model'].float().fuse()  leaves in each Conv module. */
@@ -61,7 +65,25 @@ typedef struct {
  * Conv:    convs[first_conv]                        k,s,p as in the module
  * C3:      cv1, cv2, cv3, then (m[j].cv1, m[j].cv2) for j < n        -> 3 + 2n convs
  * SPPF:    cv1, cv2 ; k = pool size
- * Detect:  one 1x1 conv per input level (bias, no activation)        -> n_from convs */
+ * Detect:  one 1x1 conv per input level (bias, no activation)        -> n_from convs
+ * YOLO11 rows (a depthwise 3x3 conv is an mdhip_conv with c_in = 1, weight [c_out][1][3][3]; every conv carries its
+ * folded BatchNorm; "no activation" below = identity, every other conv = SiLU):
+ * Conv:    layer 0 may also be Conv(3->c, k=3, s=2, p=1) (the YOLO11 stem)
+ * C3k2:    n inner blocks, shortcut, k = 0: Bottleneck blocks, k = 1: C3k blocks (c3k = True).  Convs:
+ *          cv1, cv2, then per block j   Bottleneck: m.j.cv1 (3x3), m.j.cv2 (3x3)                          -> 2 + 2n convs
+ *                                       C3k: m.j.cv1, m.j.cv2, m.j.cv3 (1x1), m.j.m.0.cv1, m.j.m.0.cv2,
+ *                                            m.j.m.1.cv1, m.j.m.1.cv2 (3x3)                               -> 2 + 7n convs
+ * C2PSA:   n PSA blocks; cv1, cv2, then per block j: m.j.attn.qkv (1x1, no activation), m.j.attn.proj (1x1, no
+ *          activation), m.j.attn.pe (depthwise 3x3, no activation), m.j.ffn.0 (1x1), m.j.ffn.1 (1x1, no
+ *          activation)                                                                             -> 2 + 5n convs
+ *          (heads = c1 / 128, key_dim 32, head_dim 64: qkv has c1 / 2 + 2 * heads * 32 = c1 outputs)
+ * DetectDFL (anchor-free, reg_max 16; na = 1, anchors_px unused and may be NULL), per input level l:
+ *          cv2.l.0 (3x3), cv2.l.1 (3x3), cv2.l.2 (1x1, 64 box logits, bias, no activation),
+ *          cv3.l.0.0 (depthwise 3x3), cv3.l.0.1 (1x1), cv3.l.1.0 (depthwise 3x3), cv3.l.1.1 (1x1),
+ *          cv3.l.2 (1x1, nc class logits, bias, no activation)                                     -> 8 n_from convs
+ *          Predictions are [cx, cy, w, h, cls0 .. cls(nc-1)] (4 + nc per anchor, no objectness); mdhip_nms* then apply
+ *          the ultralytics rule (conf = largest class score, class offset 7680 in the IoU, 30 000 candidates at most).
+ *          mdhip_forward_tta and MDHIP_DTYPE_FP8 return MDHIP_EUNSUPPORTED for such models. */
 typedef struct {
     int32_t type;
     int32_t n_from;
@@ -122,7 +144,7 @@ int mdhip_preprocess(mdhip_ctx* ctx, const uint8_t* const* images, const mdhip_l
                      int n, int out_h, int out_w, void* hip_stream);
 
 /* Replaces self.model(batch)[0] (pytorch_detector.py:1313): conv stack + Detect decode.
- * Leaves (n, n_anchors, 5+nc) fp32 predictions in a device buffer of the context. */
+ * Leaves (n, n_anchors, 5+nc) fp32 predictions in a device buffer of the context (4+nc for an anchor-free model). */
 int mdhip_forward(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream);
 
 /* Test-time augmentation: replaces mdhip_forward for `model(batch, augment=True)` (reference
@@ -197,9 +219,23 @@ int mdhip_read_input(mdhip_ctx* ctx, int n, int h, int w, float* out, void* hip_
 int mdhip_read_layer(mdhip_ctx* ctx, int layer, int n, float* out, int* c, int* h, int* w,
                      void* hip_stream);
 
+/* the YOLO11 kernels in isolation (tests; host buffers, scratch device memory allocated per call), in the context's
+ * 16-bit storage type (bf16 or fp16 bits):
+ * mdhip_dwconv3x3_on: depthwise 3x3 / s1 / p1 of in [n][h][w][ld_in] -> out [n][h][w][c]; weight fp32 [c][1][3][3],
+ *   bias [c]; output channel o reads input channel (o / grp) * grp_stride + grp_off + o % grp; act 1 = SiLU; res
+ *   ([n][h][w][c] or NULL) is added after the activation
+ * mdhip_attention_on: qkv [n][n_tokens][heads * 128] ([q 32 | k 32 | v 64] per head) -> out [n][n_tokens][heads * 64]
+ * mdhip_dfl_decode_on: box logits fp32 [n][ny][nx][64], class logits fp32 [n][ny][nx][nc] -> pred [n][ny * nx][4 + nc] */
+int mdhip_dwconv3x3_on(mdhip_ctx* ctx, const uint16_t* in, int ld_in, const float* weight, const float* bias, const uint16_t* res,
+                       uint16_t* out, int n, int h, int w, int c, int grp, int grp_stride, int grp_off, int act, void* hip_stream);
+int mdhip_attention_on(mdhip_ctx* ctx, const uint16_t* qkv, uint16_t* out, int n, int n_tokens, int heads, void* hip_stream);
+int mdhip_dfl_decode_on(mdhip_ctx* ctx, const float* box, const float* cls, int nc, int n, int ny, int nx, float stride, float* pred,
+                        void* hip_stream);
+
 typedef struct {
     char    name[48];       /* e.g. "L6.m3.cv2 3x3"                           */
-    int32_t kind;           /* 0 conv (implicit GEMM), 1 pool, 2 upsample, 3 decode, 4 copy */
+    int32_t kind;           /* 0 conv (implicit GEMM), 1 pool, 2 upsample, 3 decode (YOLOv5 Detect decode, or the DFL
+                             * decode of an anchor-free head), 4 copy, 5 depthwise 3x3 conv, 6 C2PSA attention */
     int32_t layer;          /* model layer index                              */
     int32_t m, n, k;        /* GEMM view of a conv (per call, for the last n,h,w) */
     double  flops;          /* algorithmic FLOPs of the op for the last (n,h,w)   */

@@ -17,6 +17,11 @@
 //   * the 6x6/s2 stem runs as a 3x3/s1 conv over the space-to-depth input the letterbox
 //     kernel produces.
 //   * Detect: per level a 1x1 implicit GEMM with fp32 output followed by the decode kernel.
+//   * YOLO11 (anchor-free) models: C3k2 runs on ONE concat buffer (cv1 writes the first 2c channels, inner block j
+//     appends its c channels, cv2 reads all of it); C2PSA as cv1 -> per PSA block qkv 1x1, attention kernel, depthwise
+//     pe(v) added to its output, proj (+x), ffn (+x) -> cv2; Detect as the box / class branches of every level (convs,
+//     depthwise convs, fp32 logits) and the DFL decode kernel.  The 3x3/s2 stem is a 3x3/s1 conv over the
+//     space-to-depth input with the weights of the +1 cell zero.
 
 #include <algorithm>
 #include <cmath>
@@ -61,7 +66,7 @@ struct PackedConv {
     std::vector<float> wscale;
 };
 
-enum OpKind { OP_CONV = 0, OP_POOL = 1, OP_UPSAMPLE = 2, OP_DECODE = 3, OP_COPY = 4 };
+enum OpKind { OP_CONV = 0, OP_POOL = 1, OP_UPSAMPLE = 2, OP_DECODE = 3, OP_COPY = 4, OP_DW = 5, OP_ATTN = 6, OP_DFL = 7 };
 
 struct Op {
     int kind = OP_CONV;
@@ -73,8 +78,12 @@ struct Op {
     int stride = 1, pad = 0, act = 1, out_f32 = 0;
     int pool_k = 5;
     int level = 0;            // decode
-    size_t f32_off = 0;       // decode: logits buffer offset ; conv with out_f32: same
+    size_t f32_off = 0;       // decode: logits buffer offset ; conv with out_f32: same ; DFL decode: box logits
     int f32_ld = 0;
+    size_t cls_off = 0;       // DFL decode: class logits (fp32, pitch cls_ld)
+    int cls_ld = 0;
+    int dw_grp = 0, dw_grp_stride = 0, dw_grp_off = 0;   // depthwise: input channel of output channel o (yolo11_kernels.cpp)
+    int heads = 0;            // attention
     int forced_cfg = -1;
     // fp8 mode: this op writes (f8_out) / reads (f8_in) an e4m3 tensor; f8_peer = the op at the other end of it;
     // act_scale = the tensor's scale (value = e4m3 x act_scale), 0 until calibrated; amax = largest |x| seen
@@ -106,6 +115,7 @@ struct mdhip_ctx {
     int dtype = 0;
     int max_batch = 0, max_h = 0, max_w = 0;
     int nc = 0, na = 0, nl = 0, no = 0;
+    bool anchor_free = false;     // the model ends in MDHIP_DETECT_DFL: predictions [cx, cy, w, h, cls...], ultralytics NMS
     std::vector<float> strides;
     int max_stride = 0;
     std::vector<mdhip_layer> layers;
@@ -277,12 +287,14 @@ struct Planner {
     }
 
     // pack one or more OIHW fp32 convs (stacked along N) to bf16 / fp16 [n_rows][k_pad], k = (r,s,c)
-    int pack(const std::vector<const mdhip_conv*>& cs, bool s2d_stem) {
+    // min_c_out: pad the output channels with zero rows (the class conv of the anchor-free head: 3 -> 8)
+    int pack(const std::vector<const mdhip_conv*>& cs, bool s2d_stem, int min_c_out = 0) {
         PackedConv pc;
         const int f16 = ctx->dtype == MDHIP_DTYPE_FP16;
         const mdhip_conv* c0 = cs[0];
         int c_out = 0;
         for (auto* c : cs) c_out += c->c_out;
+        c_out = std::max(c_out, min_c_out);
         if (s2d_stem) {
             pc.kh = pc.kw = 3;
             pc.cin_pad = 16;
@@ -383,6 +395,75 @@ struct Planner {
         return (int)ctx->packed.size() - 1;
     }
 
+    // a depthwise 3x3 conv (mdhip_conv with c_in = 1): [9][C] 16-bit weights (tap-major: 8 channels per 16-byte load)
+    int pack_dw(const mdhip_conv* c) {
+        PackedConv pc;
+        const int f16 = ctx->dtype == MDHIP_DTYPE_FP16;
+        pc.kh = pc.kw = 3;
+        pc.cin_pad = 1;
+        pc.c_out = pc.n_rows = c->c_out;
+        pc.k_pad = 9;
+        pc.k_real = 9;
+        std::vector<uint16_t> w((size_t)9 * c->c_out);
+        std::vector<float> b(c->c_out);
+        for (int o = 0; o < c->c_out; ++o) {
+            for (int t = 0; t < 9; ++t) w[(size_t)t * c->c_out + o] = f32_to_st(c->weight[(size_t)o * 9 + t], f16);
+            b[o] = c->bias ? c->bias[o] : 0.f;
+        }
+        ctx->packed.push_back(pc);
+        w_host.push_back(std::move(w));
+        w4_host.emplace_back();
+        w4p_host.emplace_back();
+        b_host.push_back(std::move(b));
+        w8_host.emplace_back();
+        return (int)ctx->packed.size() - 1;
+    }
+
+    void add_dw(int layer, const std::string& name, const Tensor& in, const Tensor& out, int pc, bool act, const Tensor* res,
+                int grp, int grp_stride, int grp_off) {
+        Op op;
+        op.kind = OP_DW;
+        op.layer = layer;
+        op.name = name;
+        op.in = in;
+        op.out = out;
+        op.pc = pc;
+        op.act = act ? 1 : 0;
+        if (res) { op.res = *res; op.has_res = true; }
+        op.dw_grp = grp;
+        op.dw_grp_stride = grp_stride;
+        op.dw_grp_off = grp_off;
+        ctx->ops.push_back(op);
+    }
+
+    // a 1x1 conv with fp32 output (Detect logits): `rows` output channels of pitch n_rows in a buffer of its own
+    void add_conv_f32(int layer, const std::string& name, const Tensor& in, int pc, int div) {
+        Op op;
+        op.kind = OP_CONV;
+        op.layer = layer;
+        op.name = name;
+        op.in = in;
+        op.pc = pc;
+        op.act = 0;
+        op.out_f32 = 1;
+        op.f32_ld = ctx->packed[pc].n_rows;
+        const size_t px = (size_t)ctx->max_batch * (ctx->max_h / div) * (ctx->max_w / div);
+        op.f32_off = alloc_bytes(px * op.f32_ld * 4);
+        op.out = in;          // spatial size only
+        op.out.c = ctx->packed[pc].c_out;
+        ctx->ops.push_back(op);
+    }
+
+    bool conv_is(const mdhip_conv& c, int c_in, int c_out, int k) const {
+        return c.c_in == c_in && (c_out < 0 || c.c_out == c_out) && c.kh == k && c.kw == k && c.weight && c.c_out > 0 && c.c_out % 8 == 0;
+    }
+
+    // the 3x3 / stride-2 / pad-1 stem of YOLO11 as the 6x6 / stride-2 / pad-2 stem with zero outer taps: original row
+    // 2y + r - 1 = 2y + (r + 1) - 2, i.e. the 3x3 kernel sits at offset (1, 1) of the 6x6 one (a 3x3 over the
+    // space-to-depth cells whose +1 cell weights are zero)
+    std::vector<float> stem6_w;
+    mdhip_conv stem6;
+
     void add_conv(int layer, const std::string& name, const Tensor& in, const Tensor& out, int pc,
                   int stride, int pad, bool act, const Tensor* res) {
         Op op;
@@ -423,6 +504,8 @@ struct Planner {
                     break;
                 case MDHIP_C3:
                 case MDHIP_SPPF:
+                case MDHIP_C3K2:
+                case MDHIP_C2PSA:
                     layer_c[i] = L.c_out;
                     layer_div[i] = in_div;
                     break;
@@ -444,12 +527,13 @@ struct Planner {
                     break;
                 }
                 case MDHIP_DETECT:
+                case MDHIP_DETECT_DFL:
                     break;
                 default:
                     error = "unknown layer type";
                     return false;
             }
-            if (L.type != MDHIP_DETECT && L.type != MDHIP_CONCAT && (layer_c[i] % 8)) {
+            if (L.type != MDHIP_DETECT && L.type != MDHIP_DETECT_DFL && L.type != MDHIP_CONCAT && (layer_c[i] % 8)) {
                 error = "channel counts must be multiples of 8";
                 return false;
             }
@@ -475,17 +559,36 @@ struct Planner {
             if (f0 < 0 && !(L.type == MDHIP_CONV && i == 0)) { error = "only the stem conv (layer 0) may read the network input"; return false; }
             if (L.type != MDHIP_DETECT && L.type != MDHIP_CONCAT && L.type != MDHIP_UPSAMPLE &&
                 (L.first_conv < 0 || L.first_conv >= model->n_convs)) { error = "first_conv out of range"; return false; }
+            // convs a layer of this kind consumes (the C3 / SPPF / Detect rows are checked where they are read)
+            auto need_convs = [&](int k) {
+                if (L.first_conv + k > model->n_convs) { error = "layer " + std::to_string(i) + ": conv table too short"; return false; }
+                return true;
+            };
             switch (L.type) {
                 case MDHIP_CONV: {
                     const mdhip_conv* c = &model->convs[L.first_conv];
                     Tensor out = out_view(i);
                     if (f0 < 0) {
-                        if (!(c->c_in == 3 && c->kh == 6 && c->kw == 6 && L.s == 2 && L.p == 2)) {
-                            error = "stem must be Conv(3->c, k=6, s=2, p=2)";
+                        const bool stem6x6 = c->c_in == 3 && c->kh == 6 && c->kw == 6 && L.s == 2 && L.p == 2;
+                        const bool stem3x3 = c->c_in == 3 && c->kh == 3 && c->kw == 3 && L.s == 2 && L.p == 1;
+                        if (!stem6x6 && !stem3x3) {
+                            error = "stem must be Conv(3->c, k=6, s=2, p=2) or Conv(3->c, k=3, s=2, p=1)";
                             return false;
                         }
-                        const int pc = pack({c}, true);
-                        snprintf(nm, sizeof(nm), "L%d stem 6x6s2 (3x3 s2d)", i);
+                        if (stem3x3) {
+                            stem6_w.assign((size_t)c->c_out * 3 * 36, 0.f);
+                            for (int o = 0; o < c->c_out; ++o)
+                                for (int ci = 0; ci < 3; ++ci)
+                                    for (int r = 0; r < 3; ++r)
+                                        for (int q = 0; q < 3; ++q)
+                                            stem6_w[(((size_t)o * 3 + ci) * 6 + r + 1) * 6 + q + 1] = c->weight[(((size_t)o * 3 + ci) * 3 + r) * 3 + q];
+                            stem6 = *c;
+                            stem6.weight = stem6_w.data();
+                            stem6.kh = stem6.kw = 6;
+                        }
+                        const int pc = pack({stem3x3 ? &stem6 : c}, true);
+                        if (stem3x3) ctx->packed[pc].k_real = 27;
+                        snprintf(nm, sizeof(nm), stem3x3 ? "L%d stem 3x3s2 (3x3 s2d)" : "L%d stem 6x6s2 (3x3 s2d)", i);
                         add_conv(i, nm, ctx->input, out, pc, 1, 1, true, nullptr);
                     } else {
                         if (c->c_in != layer_c[f0] || c->kh != L.k || c->kw != L.k) { error = "conv shape mismatch"; return false; }
@@ -548,6 +651,190 @@ struct Planner {
                     snprintf(nm, sizeof(nm), "L%d C3.cv3 1x1", i);
                     add_conv(i, nm, Y, out, pc, 1, 0, true, nullptr);
                     ctx->layer_out[i] = out;
+                    break;
+                }
+                case MDHIP_C3K2: {
+                    // cv1, cv2, then per inner block j: Bottleneck  m.j.cv1, m.j.cv2 (3x3, 3x3)            (k == 0)
+                    //                                   C3k         m.j.cv1, m.j.cv2, m.j.cv3, m.j.m.0.cv1, m.j.m.0.cv2,
+                    //                                               m.j.m.1.cv1, m.j.m.1.cv2 (C3 with 3x3 -> 3x3 bottlenecks)
+                    const int per = L.k ? 7 : 2;
+                    if (!need_convs(2 + per * L.n)) return false;
+                    const mdhip_conv* cv = &model->convs[L.first_conv];
+                    const int c = cv[0].c_out / 2;
+                    if (L.n < 1 || c % 8 || !conv_is(cv[0], layer_c[f0], 2 * c, 1) || !conv_is(cv[1], (2 + L.n) * c, L.c_out, 1)) {
+                        error = "C3k2 shape mismatch at layer " + std::to_string(i);
+                        return false;
+                    }
+                    Tensor out = out_view(i);
+                    Tensor Y = alloc((2 + L.n) * c, layer_div[i]);
+                    int pc = pack({&cv[0]}, false);
+                    snprintf(nm, sizeof(nm), "L%d C3k2.cv1 1x1", i);
+                    add_conv(i, nm, ctx->layer_out[f0], slice(Y, 0, 2 * c), pc, 1, 0, true, nullptr);
+                    for (int j = 0; j < L.n; ++j) {
+                        const mdhip_conv* b = &cv[2 + per * j];
+                        const Tensor src = slice(Y, (1 + j) * c, c), dst = slice(Y, (2 + j) * c, c);
+                        if (!L.k) {
+                            const int h = b[0].c_out;
+                            if (!conv_is(b[0], c, h, 3) || !conv_is(b[1], h, c, 3)) { error = "C3k2 bottleneck shape mismatch"; return false; }
+                            Tensor T = alloc(h, layer_div[i]);
+                            pc = pack({&b[0]}, false);
+                            snprintf(nm, sizeof(nm), "L%d C3k2.m%d.cv1 3x3", i, j);
+                            add_conv(i, nm, src, T, pc, 1, 1, true, nullptr);
+                            pc = pack({&b[1]}, false);
+                            snprintf(nm, sizeof(nm), "L%d C3k2.m%d.cv2 3x3", i, j);
+                            add_conv(i, nm, T, dst, pc, 1, 1, true, L.shortcut ? &src : nullptr);
+                        } else {
+                            const int h = b[0].c_out;
+                            if (h % 8 || !conv_is(b[0], c, h, 1) || !conv_is(b[1], c, h, 1) || !conv_is(b[2], 2 * h, c, 1)) {
+                                error = "C3k shape mismatch";
+                                return false;
+                            }
+                            for (int q = 3; q < 7; ++q)
+                                if (!conv_is(b[q], h, h, 3)) { error = "C3k bottleneck must be 3x3 -> 3x3"; return false; }
+                            Tensor YK = alloc(2 * h, layer_div[i]);
+                            Tensor TK = alloc(h, layer_div[i]);
+                            Tensor Y1 = slice(YK, 0, h);
+                            pc = pack({&b[0], &b[1]}, false);
+                            snprintf(nm, sizeof(nm), "L%d C3k2.m%d.cv1|cv2 1x1", i, j);
+                            add_conv(i, nm, src, YK, pc, 1, 0, true, nullptr);
+                            for (int q = 0; q < 2; ++q) {
+                                pc = pack({&b[3 + 2 * q]}, false);
+                                snprintf(nm, sizeof(nm), "L%d C3k2.m%d.m%d.cv1 3x3", i, j, q);
+                                add_conv(i, nm, Y1, TK, pc, 1, 1, true, nullptr);
+                                pc = pack({&b[4 + 2 * q]}, false);
+                                snprintf(nm, sizeof(nm), "L%d C3k2.m%d.m%d.cv2 3x3", i, j, q);
+                                add_conv(i, nm, TK, Y1, pc, 1, 1, true, L.shortcut ? &Y1 : nullptr);
+                            }
+                            pc = pack({&b[2]}, false);
+                            snprintf(nm, sizeof(nm), "L%d C3k2.m%d.cv3 1x1", i, j);
+                            add_conv(i, nm, YK, dst, pc, 1, 0, true, nullptr);
+                        }
+                    }
+                    pc = pack({&cv[1]}, false);
+                    snprintf(nm, sizeof(nm), "L%d C3k2.cv2 1x1", i);
+                    add_conv(i, nm, Y, out, pc, 1, 0, true, nullptr);
+                    ctx->layer_out[i] = out;
+                    break;
+                }
+                case MDHIP_C2PSA: {
+                    // cv1, cv2, then per PSA block j: m.j.attn.qkv, m.j.attn.proj, m.j.attn.pe, m.j.ffn.0, m.j.ffn.1
+                    if (!need_convs(2 + 5 * L.n)) return false;
+                    const mdhip_conv* cv = &model->convs[L.first_conv];
+                    const int c = cv[0].c_out / 2;
+                    const int heads = c / 64;
+                    if (L.n < 1 || c % 64 || !conv_is(cv[0], layer_c[f0], 2 * c, 1) || !conv_is(cv[1], 2 * c, L.c_out, 1)) {
+                        error = "C2PSA shape mismatch at layer " + std::to_string(i) + " (the attention needs c1 / 2 a multiple of 64)";
+                        return false;
+                    }
+                    Tensor out = out_view(i);
+                    Tensor Y = alloc(2 * c, layer_div[i]);
+                    const Tensor B = slice(Y, c, c);
+                    Tensor QKV = alloc(heads * 128, layer_div[i]);
+                    Tensor A = alloc(c, layer_div[i]);
+                    Tensor Fh = alloc(2 * c, layer_div[i]);
+                    int pc = pack({&cv[0]}, false);
+                    snprintf(nm, sizeof(nm), "L%d C2PSA.cv1 1x1", i);
+                    add_conv(i, nm, ctx->layer_out[f0], Y, pc, 1, 0, true, nullptr);
+                    for (int j = 0; j < L.n; ++j) {
+                        const mdhip_conv* b = &cv[2 + 5 * j];
+                        // Attention(dim = c, heads = c / 64, attn_ratio 0.5): key_dim 32, head_dim 64, qkv = c + 2 * heads * 32
+                        if (!conv_is(b[0], c, heads * 128, 1) || !conv_is(b[1], c, c, 1) || !(b[2].c_in == 1 && b[2].c_out == c &&
+                            b[2].kh == 3 && b[2].kw == 3) || !conv_is(b[3], c, 2 * c, 1) || !conv_is(b[4], 2 * c, c, 1)) {
+                            error = "PSABlock shape mismatch at layer " + std::to_string(i) + " (key_dim 32, head_dim 64 expected)";
+                            return false;
+                        }
+                        pc = pack({&b[0]}, false);
+                        snprintf(nm, sizeof(nm), "L%d C2PSA.m%d.attn.qkv 1x1", i, j);
+                        add_conv(i, nm, B, QKV, pc, 1, 0, false, nullptr);
+                        Op at;
+                        at.kind = OP_ATTN;
+                        at.layer = i;
+                        snprintf(nm, sizeof(nm), "L%d C2PSA.m%d.attn", i, j);
+                        at.name = nm;
+                        at.in = QKV;
+                        at.out = A;
+                        at.heads = heads;
+                        ctx->ops.push_back(at);
+                        pc = pack_dw(&b[2]);
+                        snprintf(nm, sizeof(nm), "L%d C2PSA.m%d.attn.pe dw3x3 (+=)", i, j);
+                        add_dw(i, nm, QKV, A, pc, false, &A, 64, 128, 64);
+                        pc = pack({&b[1]}, false);
+                        snprintf(nm, sizeof(nm), "L%d C2PSA.m%d.attn.proj 1x1", i, j);
+                        add_conv(i, nm, A, B, pc, 1, 0, false, &B);
+                        pc = pack({&b[3]}, false);
+                        snprintf(nm, sizeof(nm), "L%d C2PSA.m%d.ffn.0 1x1", i, j);
+                        add_conv(i, nm, B, Fh, pc, 1, 0, true, nullptr);
+                        pc = pack({&b[4]}, false);
+                        snprintf(nm, sizeof(nm), "L%d C2PSA.m%d.ffn.1 1x1", i, j);
+                        add_conv(i, nm, Fh, B, pc, 1, 0, false, &B);
+                    }
+                    pc = pack({&cv[1]}, false);
+                    snprintf(nm, sizeof(nm), "L%d C2PSA.cv2 1x1", i);
+                    add_conv(i, nm, Y, out, pc, 1, 0, true, nullptr);
+                    ctx->layer_out[i] = out;
+                    break;
+                }
+                case MDHIP_DETECT_DFL: {
+                    // per level l: cv2.l.0 (3x3), cv2.l.1 (3x3), cv2.l.2 (1x1, 64 box logits), cv3.l.0.0 (dw 3x3), cv3.l.0.1 (1x1),
+                    // cv3.l.1.0 (dw 3x3), cv3.l.1.1 (1x1), cv3.l.2 (1x1, nc class logits)
+                    if (L.n_from != model->nl) { error = "Detect inputs != nl"; return false; }
+                    if (!need_convs(8 * L.n_from)) return false;
+                    for (int l = 0; l < L.n_from; ++l) {
+                        const mdhip_conv* b = &model->convs[L.first_conv + 8 * l];
+                        const int f = L.from[l];
+                        const int cx = layer_c[f], c2 = b[0].c_out, c3 = b[4].c_out;
+                        if (!conv_is(b[0], cx, c2, 3) || !conv_is(b[1], c2, c2, 3) || !(b[2].c_in == c2 && b[2].c_out == 64 && b[2].kh == 1) ||
+                            !(b[3].c_in == 1 && b[3].c_out == cx && b[3].kh == 3 && b[3].kw == 3) || !conv_is(b[4], cx, c3, 1) ||
+                            !(b[5].c_in == 1 && b[5].c_out == c3 && b[5].kh == 3 && b[5].kw == 3) || !conv_is(b[6], c3, c3, 1) ||
+                            !(b[7].c_in == c3 && b[7].c_out == ctx->nc && b[7].kh == 1)) {
+                            error = "anchor-free Detect level " + std::to_string(l) + ": conv shapes do not match (reg_max 16, "
+                                    "class branch DWConv 3x3 -> Conv 1x1 -> DWConv 3x3 -> Conv 1x1 -> Conv2d 1x1)";
+                            return false;
+                        }
+                        if (std::fabs(ctx->strides[l] - (float)layer_div[f]) > 1e-6f) { error = "Detect stride does not match the graph"; return false; }
+                        const Tensor& x = ctx->layer_out[f];
+                        const int dv = layer_div[f];
+                        Tensor B1 = alloc(c2, dv), B2 = alloc(c2, dv);
+                        Tensor C1 = alloc(cx, dv), C2 = alloc(c3, dv), C3 = alloc(c3, dv), C4 = alloc(c3, dv);
+                        int pc = pack({&b[0]}, false);
+                        snprintf(nm, sizeof(nm), "L%d Detect.cv2.%d.0 3x3", i, l);
+                        add_conv(i, nm, x, B1, pc, 1, 1, true, nullptr);
+                        pc = pack({&b[1]}, false);
+                        snprintf(nm, sizeof(nm), "L%d Detect.cv2.%d.1 3x3", i, l);
+                        add_conv(i, nm, B1, B2, pc, 1, 1, true, nullptr);
+                        pc = pack({&b[2]}, false);
+                        snprintf(nm, sizeof(nm), "L%d Detect.cv2.%d.2 1x1 (box)", i, l);
+                        add_conv_f32(i, nm, B2, pc, dv);
+                        const size_t box_off = ctx->ops.back().f32_off;
+                        const int box_ld = ctx->ops.back().f32_ld;
+                        pc = pack_dw(&b[3]);
+                        snprintf(nm, sizeof(nm), "L%d Detect.cv3.%d.0.0 dw3x3", i, l);
+                        add_dw(i, nm, x, C1, pc, true, nullptr, cx, cx, 0);
+                        pc = pack({&b[4]}, false);
+                        snprintf(nm, sizeof(nm), "L%d Detect.cv3.%d.0.1 1x1", i, l);
+                        add_conv(i, nm, C1, C2, pc, 1, 0, true, nullptr);
+                        pc = pack_dw(&b[5]);
+                        snprintf(nm, sizeof(nm), "L%d Detect.cv3.%d.1.0 dw3x3", i, l);
+                        add_dw(i, nm, C2, C3, pc, true, nullptr, c3, c3, 0);
+                        pc = pack({&b[6]}, false);
+                        snprintf(nm, sizeof(nm), "L%d Detect.cv3.%d.1.1 1x1", i, l);
+                        add_conv(i, nm, C3, C4, pc, 1, 0, true, nullptr);
+                        pc = pack({&b[7]}, false, 8);         // nc class rows padded to 8 (zero weights, zero bias)
+                        snprintf(nm, sizeof(nm), "L%d Detect.cv3.%d.2 1x1 (cls)", i, l);
+                        add_conv_f32(i, nm, C4, pc, dv);
+                        Op dec;
+                        dec.kind = OP_DFL;
+                        dec.layer = i;
+                        snprintf(nm, sizeof(nm), "L%d Detect.dfl_decode%d", i, l);
+                        dec.name = nm;
+                        dec.in = x;
+                        dec.level = l;
+                        dec.f32_off = box_off;
+                        dec.f32_ld = box_ld;
+                        dec.cls_off = ctx->ops.back().f32_off;
+                        dec.cls_ld = ctx->ops.back().f32_ld;
+                        ctx->ops.push_back(dec);
+                    }
                     break;
                 }
                 case MDHIP_SPPF: {
@@ -1087,6 +1374,53 @@ int run_op(mdhip_ctx* ctx, Op& op, int n, int h, int w, hipStream_t s) {
                                           (uint16_t*)(ctx->arena + op.out.off), op.out.ld, op.in.c, px, s));
             break;
         }
+        case OP_DW: {
+            const PackedConv& pc = ctx->packed[op.pc];
+            const int H = h / op.in.div, W = w / op.in.div;
+            const double px = (double)n * H * W;
+            op.gm = n * H * W;
+            op.gn = pc.c_out;
+            op.gk = 9;
+            op.flops = 2.0 * px * pc.c_out * 9;
+            op.bytes = px * pc.c_out * 2.0 * (op.has_res ? 3.0 : 2.0) + (double)pc.c_out * (9 * 2 + 4);
+            op.last_cfg = -1;
+            HIP_TRY(ctx, launch_dwconv3x3((const uint16_t*)(ctx->arena + op.in.off), op.in.ld, (const uint16_t*)(ctx->warena + pc.w_off),
+                                          (const float*)(ctx->warena + pc.b_off), (uint16_t*)(ctx->arena + op.out.off), op.out.ld,
+                                          op.has_res ? (const uint16_t*)(ctx->arena + op.res.off) : nullptr, op.has_res ? op.res.ld : 0,
+                                          n, H, W, pc.c_out, op.dw_grp, op.dw_grp_stride, op.dw_grp_off, op.act,
+                                          ctx->dtype == MDHIP_DTYPE_FP16, s));
+            break;
+        }
+        case OP_ATTN: {
+            const int H = h / op.in.div, W = w / op.in.div;
+            const double N = (double)H * W;
+            // QK^T (32 channels) and PV (64 channels) per head: 2 N^2 (32 + 64) FLOPs
+            op.gm = H * W;
+            op.gn = H * W;
+            op.gk = 32;
+            op.flops = (double)n * op.heads * 2.0 * N * N * (32 + 64);
+            op.bytes = (double)n * N * op.heads * (128 + 64) * 2.0;
+            op.last_cfg = -1;
+            HIP_TRY(ctx, launch_attention((const uint16_t*)(ctx->arena + op.in.off), op.in.ld, (uint16_t*)(ctx->arena + op.out.off),
+                                          op.out.ld, n, H * W, op.heads, ctx->dtype == MDHIP_DTYPE_FP16, s));
+            break;
+        }
+        case OP_DFL: {
+            const int ny = h / op.in.div, nx = w / op.in.div;
+            int level_off = 0;
+            for (int l = 0; l < op.level; ++l) {
+                const int sl = (int)ctx->strides[l];
+                level_off += (h / sl) * (w / sl);
+            }
+            op.gm = n * ny * nx;
+            op.flops = 0;
+            op.bytes = (double)n * ny * nx * (64 + ctx->nc + ctx->no) * 4.0;
+            op.last_cfg = -1;
+            HIP_TRY(ctx, launch_dfl_decode((const float*)(ctx->arena + op.f32_off), op.f32_ld, (const float*)(ctx->arena + op.cls_off),
+                                           op.cls_ld, (float*)(ctx->arena + ctx->pred_off), n, ny, nx, ctx->nc, ctx->cur_A, level_off,
+                                           ctx->strides[op.level], s));
+            break;
+        }
         case OP_DECODE: {
             if (op.dec_done) {                     // decoded in the epilogue of the conv in front (this forward)
                 op.bytes = 0;
@@ -1149,10 +1483,23 @@ int mdhip_create(const mdhip_model* model, int device, int dtype, int max_batch,
     ctx->nl = model->nl;
     ctx->no = model->nc + 5;
     bool has_detect = false;
-    for (int i = 0; i < model->n_layers; ++i) has_detect |= model->layers[i].type == MDHIP_DETECT;
+    for (int i = 0; i < model->n_layers; ++i) {
+        has_detect |= model->layers[i].type == MDHIP_DETECT || model->layers[i].type == MDHIP_DETECT_DFL;
+        ctx->anchor_free |= model->layers[i].type == MDHIP_DETECT_DFL;
+    }
+    if (ctx->anchor_free) {
+        // [cx, cy, w, h, cls0 .. cls(nc-1)]: no objectness, one prediction per cell
+        ctx->no = model->nc + 4;
+        ctx->na = 1;
+        if (dtype == MDHIP_DTYPE_FP8) {
+            delete ctx;
+            return fail(nullptr, MDHIP_EUNSUPPORTED, "MDHIP_DTYPE_FP8 is implemented for the YOLOv5 bottlenecks only, not for "
+                                                     "anchor-free (YOLO11) models: use bf16 or fp16");
+        }
+    }
     ctx->max_stride = 2;
     if (has_detect) {
-        if (model->nl < 1 || !model->strides || !model->anchors_px || model->nc < 1 || model->nc > 250) {
+        if (model->nl < 1 || !model->strides || (!ctx->anchor_free && !model->anchors_px) || model->nc < 1 || model->nc > 250) {
             delete ctx;
             return fail(nullptr, MDHIP_EINVAL, "Detect layer needs nl/strides/anchors/nc");
         }
@@ -1274,7 +1621,7 @@ int mdhip_create(const mdhip_model* model, int device, int dtype, int max_batch,
         const char* pz = getenv("MDHIP_ARENA_POISON");
         CREATE_TRY(hipMemset(ctx->arena, (pz && atoi(pz) != 0) ? 0xff : 0, ctx->arena_bytes));
     }
-    if (has_detect)
+    if (has_detect && !ctx->anchor_free)
         CREATE_TRY(hipMemcpy(ctx->warena + ctx->anchors_off, model->anchors_px, (size_t)ctx->nl * ctx->na * 2 * 4, hipMemcpyHostToDevice));
     for (size_t i = 0; i < ctx->packed.size(); ++i) {
         CREATE_TRY(hipMemcpy(ctx->warena + ctx->packed[i].w_off, P.w_host[i].data(), P.w_host[i].size() * 2, hipMemcpyHostToDevice));
@@ -1475,6 +1822,9 @@ int mdhip_forward(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
 // level of the last pass dropped (_clip_augmented), predictions concatenated along the anchor axis.
 int mdhip_forward_tta(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
     if (!ctx) return MDHIP_EINVAL;
+    if (ctx->anchor_free)
+        return fail(ctx, MDHIP_EUNSUPPORTED, "mdhip_forward_tta: augmented inference is implemented for YOLOv5 (anchor-based) "
+                                             "models only, not for anchor-free (YOLO11) models");
     if (int rc = check_shape(ctx, n, h, w)) return rc;
     if (ctx->last_n < n || ctx->last_h != h || ctx->last_w != w)
         return fail(ctx, MDHIP_EINVAL, "mdhip_forward_tta needs mdhip_preprocess of the same batch first");
@@ -1712,7 +2062,8 @@ static int nms_common(mdhip_ctx* ctx, const float* pred_dev, int n, int n_anchor
     if (n_anchors < 1 || n_anchors > ctx->a_cap) return fail(ctx, MDHIP_EINVAL, "n_anchors %d outside [1,%d]", n_anchors, ctx->a_cap);
     float* out_dev = (float*)(ctx->arena + ctx->nms_out_off);
     int* cnt_dev = (int*)(ctx->arena + ctx->nms_cnt_off);
-    HIP_TRY(ctx, launch_nms(pred_dev, n, n_anchors, ctx->no, conf_thres, iou_thres, max_det, ctx->nms_scr, out_dev, cnt_dev, s));
+    HIP_TRY(ctx, launch_nms(pred_dev, n, n_anchors, ctx->no, conf_thres, iou_thres, max_det, ctx->nms_scr, out_dev, cnt_dev, s,
+                            ctx->anchor_free));
     HIP_TRY(ctx, hipMemcpyAsync(out, out_dev, (size_t)n * max_det * 6 * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipMemcpyAsync(counts, cnt_dev, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -1742,7 +2093,7 @@ int mdhip_nms_enqueue(mdhip_ctx* ctx, int n, float conf_thres, float iou_thres, 
     float* out_dev = (float*)(ctx->arena + ctx->nms_out_off);
     int* cnt_dev = (int*)(ctx->arena + ctx->nms_cnt_off);
     HIP_TRY(ctx, launch_nms((const float*)(ctx->arena + ctx->pred_off), n, A, ctx->no, conf_thres, iou_thres, max_det,
-                            ctx->nms_scr, out_dev, cnt_dev, s));
+                            ctx->nms_scr, out_dev, cnt_dev, s, ctx->anchor_free));
     HIP_TRY(ctx, hipEventRecord(ctx->pred_read[ctx->pred_cur], s));
     ctx->pred_read_valid[ctx->pred_cur] = true;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->nms_host_out[slot], out_dev, (size_t)n * max_det * 6 * 4, hipMemcpyDeviceToHost, s));
@@ -1825,6 +2176,84 @@ int mdhip_read_layer(mdhip_ctx* ctx, int layer, int n, float* out, int* c, int* 
     return MDHIP_OK;
 }
 
+// ---- the YOLO11 kernels in isolation (tests) ----
+// host buffers in / out; scratch device memory is allocated per call (not for the product path)
+namespace {
+struct DevBufs {
+    std::vector<void*> p;
+    ~DevBufs() { for (void* q : p) (void)hipFree(q); }
+    hipError_t get(size_t bytes, void** out) { *out = nullptr; hipError_t e = hipMalloc(out, std::max<size_t>(bytes, 16)); if (e == hipSuccess) p.push_back(*out); return e; }
+};
+}  // namespace
+
+int mdhip_dwconv3x3_on(mdhip_ctx* ctx, const uint16_t* in, int ld_in, const float* weight, const float* bias, const uint16_t* res,
+                       uint16_t* out, int n, int h, int w, int c, int grp, int grp_stride, int grp_off, int act, void* hip_stream) {
+    if (!ctx || !in || !weight || !bias || !out || n < 1 || h < 1 || w < 1 || c < 8 || c % 8 || grp < 8 || ld_in < 8)
+        return MDHIP_EINVAL;
+    if ((c / grp - 1) * grp_stride + grp_off + grp > ld_in || c % grp) return fail(ctx, MDHIP_EINVAL, "channel mapping outside ld_in");
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int f16 = ctx->dtype == MDHIP_DTYPE_FP16;
+    std::vector<uint16_t> wp((size_t)9 * c);
+    for (int o = 0; o < c; ++o)
+        for (int t = 0; t < 9; ++t) wp[(size_t)t * c + o] = f32_to_st(weight[(size_t)o * 9 + t], f16);
+    const size_t px = (size_t)n * h * w;
+    DevBufs d;
+    void *din, *dw, *db, *dout, *dres = nullptr;
+    HIP_TRY(ctx, d.get(px * ld_in * 2, &din));
+    HIP_TRY(ctx, d.get(wp.size() * 2, &dw));
+    HIP_TRY(ctx, d.get((size_t)c * 4, &db));
+    HIP_TRY(ctx, d.get(px * c * 2, &dout));
+    HIP_TRY(ctx, hipMemcpy(din, in, px * ld_in * 2, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(dw, wp.data(), wp.size() * 2, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(db, bias, (size_t)c * 4, hipMemcpyHostToDevice));
+    if (res) {
+        HIP_TRY(ctx, d.get(px * c * 2, &dres));
+        HIP_TRY(ctx, hipMemcpy(dres, res, px * c * 2, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(ctx, launch_dwconv3x3((const uint16_t*)din, ld_in, (const uint16_t*)dw, (const float*)db, (uint16_t*)dout, c,
+                                  (const uint16_t*)dres, c, n, h, w, c, grp, grp_stride, grp_off, act, f16, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipMemcpy(out, dout, px * c * 2, hipMemcpyDeviceToHost));
+    return MDHIP_OK;
+}
+
+int mdhip_attention_on(mdhip_ctx* ctx, const uint16_t* qkv, uint16_t* out, int n, int n_tokens, int heads, void* hip_stream) {
+    if (!ctx || !qkv || !out || n < 1 || n_tokens < 1 || heads < 1) return MDHIP_EINVAL;
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)n * n_tokens;
+    DevBufs d;
+    void *din, *dout;
+    HIP_TRY(ctx, d.get(px * heads * 128 * 2, &din));
+    HIP_TRY(ctx, d.get(px * heads * 64 * 2, &dout));
+    HIP_TRY(ctx, hipMemcpy(din, qkv, px * heads * 128 * 2, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, launch_attention((const uint16_t*)din, heads * 128, (uint16_t*)dout, heads * 64, n, n_tokens, heads,
+                                  ctx->dtype == MDHIP_DTYPE_FP16, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipMemcpy(out, dout, px * heads * 64 * 2, hipMemcpyDeviceToHost));
+    return MDHIP_OK;
+}
+
+int mdhip_dfl_decode_on(mdhip_ctx* ctx, const float* box, const float* cls, int nc, int n, int ny, int nx, float stride, float* pred,
+                        void* hip_stream) {
+    if (!ctx || !box || !cls || !pred || nc < 1 || n < 1 || ny < 1 || nx < 1) return MDHIP_EINVAL;
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)n * ny * nx;
+    DevBufs d;
+    void *db, *dc, *dp;
+    HIP_TRY(ctx, d.get(px * 64 * 4, &db));
+    HIP_TRY(ctx, d.get(px * nc * 4, &dc));
+    HIP_TRY(ctx, d.get(px * (4 + nc) * 4, &dp));
+    HIP_TRY(ctx, hipMemcpy(db, box, px * 64 * 4, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(dc, cls, px * nc * 4, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, launch_dfl_decode((const float*)db, 64, (const float*)dc, nc, (float*)dp, n, ny, nx, nc, ny * nx, 0, stride, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipMemcpy(pred, dp, px * (4 + nc) * 4, hipMemcpyDeviceToHost));
+    return MDHIP_OK;
+}
+
 int mdhip_num_ops(mdhip_ctx* ctx) { return ctx ? (int)ctx->ops.size() : MDHIP_EINVAL; }
 
 int mdhip_get_op_info(mdhip_ctx* ctx, int op, mdhip_op_info* out) {
@@ -1832,7 +2261,7 @@ int mdhip_get_op_info(mdhip_ctx* ctx, int op, mdhip_op_info* out) {
     const Op& o = ctx->ops[op];
     memset(out, 0, sizeof(*out));
     snprintf(out->name, sizeof(out->name), "%s", o.name.c_str());
-    out->kind = o.kind;
+    out->kind = o.kind == OP_DFL ? OP_DECODE : o.kind;       // (the DFL decode is reported as the decode op of its level)
     out->layer = o.layer;
     out->m = o.gm;
     out->n = o.gn;
@@ -1840,7 +2269,7 @@ int mdhip_get_op_info(mdhip_ctx* ctx, int op, mdhip_op_info* out) {
     out->flops = o.flops;
     out->bytes = o.bytes;
     out->cfg = o.last_cfg;
-    if (o.kind == OP_CONV) {
+    if (o.kind == OP_CONV || o.kind == OP_DW) {
         const PackedConv& pc = ctx->packed[o.pc];
         out->ntaps = pc.kh * pc.kw;
         out->stride = o.stride;

@@ -393,9 +393,30 @@ struct NmsScratch {
     int cap;               // candidates capacity per image (= max anchors)
     uint32_t* seg_cnt;     // [n][kNmsScanParts] candidates found by each scan workgroup
 };
+// anchor_free: the ultralytics rule of the YOLO11 models (pred rows [cx, cy, w, h, cls0..], no objectness, conf = the
+// largest class score, IoU on boxes shifted by cls * 7680, only the kNmsMaxNmsAnchorFree highest-ranked candidates)
 hipError_t launch_nms(const float* pred, int n, int n_anchors, int no, float conf_thres,
                       float iou_thres, int max_det, const NmsScratch& scr, float* out /*device [n][max_det][6]*/,
-                      int* counts /*device [n]*/, hipStream_t s);
+                      int* counts /*device [n]*/, hipStream_t s, bool anchor_free = false);
 constexpr int kNmsMaxDet = 1024;
+constexpr int kNmsMaxNmsAnchorFree = 30000;   // ultralytics non_max_suppression max_nms
+
+// ---------------------------------------------------------------------------------------
+// YOLO11 blocks (yolo11_kernels.cpp)
+// ---------------------------------------------------------------------------------------
+// depthwise 3x3 / s1 / p1 over NHWC 16-bit views; wgt [9][C] 16-bit, bias [C] fp32; output channel o reads input channel
+// (o / grp) * grp_stride + grp_off + o % grp; act 1 = SiLU; res (may be nullptr): added after the activation (in place:
+// res == out is allowed).  C, grp, grp_stride, grp_off and every pitch multiples of 8.
+hipError_t launch_dwconv3x3(const uint16_t* in, int ld_in, const uint16_t* wgt, const float* bias, uint16_t* out, int ld_out,
+                            const uint16_t* res, int ld_res, int n, int H, int W, int C, int grp, int grp_stride, int grp_off,
+                            int act, int f16, hipStream_t s);
+// C2PSA attention: qkv [n][N][ld_qkv] with per head [q 32 | k 32 | v 64] channels at head * 128 -> out [n][N][ld_out],
+// channels head * 64 .. + 63 = v softmax(q^T k / sqrt(32))^T
+hipError_t launch_attention(const uint16_t* qkv, int ld_qkv, uint16_t* out, int ld_out, int n, int N, int heads, int f16,
+                            hipStream_t s);
+// DFL decode of one level: box logits fp32 [n*ny*nx][ld_box] (4 sides x 16 bins), class logits fp32 [n*ny*nx][ld_cls]
+// -> pred[n][n_anchors][4 + nc] rows level_off + y * nx + x
+hipError_t launch_dfl_decode(const float* box, int ld_box, const float* cls, int ld_cls, float* pred, int n, int ny, int nx,
+                             int nc, int n_anchors, int level_off, float stride, hipStream_t s);
 
 }  // namespace mdhip

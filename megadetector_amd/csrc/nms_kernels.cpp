@@ -31,6 +31,12 @@
 //   B. 4 x 8-bit stable LSD radix sort (descending confidence) of the band: every wavefront owns a
 //      contiguous segment and a private 256-bin histogram in LDS; ranks inside a 64-key tile
 //      come from an 8-ballot match-any
+//
+// Anchor-free mode (YOLO11 heads; launch_nms(..., anchor_free = true)): ultralytics non_max_suppression [3P] -- rows
+// [cx, cy, w, h, cls...], no objectness, conf = the largest class score (first maximum), conf > conf_thres; only the
+// kNmsMaxNmsAnchorFree highest-ranked candidates take part (max_nms); one NMS over boxes shifted by cls * 7680 (the IoU
+// sees the shifted fp32 coordinates; the output boxes are re-read unshifted).  The greedy-pass argument above carries over.
+// The YOLOv5 instantiation is the code as it was.
 //   C. chunks of 1024 sorted candidates: filter against the kept list, then rounds of up to 64 alive candidates
 //      resolved inside wavefront 0 (lane broadcasts), one barrier round per 64 instead of per kept box; stop at
 //      max_det.  Measured at batch 32 (tools/nms_bench.py, 1 % / 43 % of the anchors passing): scan 0.03 ms,
@@ -51,11 +57,13 @@ struct __attribute__((aligned(16))) NmsLds {
     float4 kept_box[kNmsMaxDet];
     float kept_conf[kNmsMaxDet];
     int kept_cls[kNmsMaxDet];
+    int kept_anchor[kNmsMaxDet];          // anchor-free mode: the output box is re-read from the prediction
     union {
         uint32_t hist[NWV][256];          // stage B
         float4 chunk_box[NT];             // stage C
     } u;
     int chunk_cls[NT];
+    int chunk_anchor[NT];
     float chunk_conf[NT];
     int round_nk;
     unsigned long long alive[2][NWV];
@@ -90,6 +98,7 @@ __device__ __forceinline__ bool iou_gt(const float4 a, const float4 b, float thr
 // stage A: workgroup (part, image) compacts anchors [part * per_part, (part + 1) * per_part) into keys0 / vals0 at
 // offset part * per_part of the image's buffer, and stores the number of candidates it found
 constexpr int NTS = 256;
+template <bool AF>
 __global__ void __launch_bounds__(NTS)
 nms_scan_kernel(const float* __restrict__ pred_all, int n_anchors, int no, float conf_thres, int per_part,
                 uint32_t* __restrict__ keys0, uint32_t* __restrict__ vals0, int cap, uint32_t* __restrict__ seg_cnt) {
@@ -99,7 +108,7 @@ nms_scan_kernel(const float* __restrict__ pred_all, int n_anchors, int no, float
     const float* pred = pred_all + (size_t)img * n_anchors * no;
     uint32_t* kb = keys0 + (size_t)img * cap + (size_t)part * per_part;
     uint32_t* vb = vals0 + (size_t)img * cap + (size_t)part * per_part;
-    const int nc = no - 5;
+    const int nc = no - (AF ? 4 : 5);
     const unsigned long long lt = lanemask_lt(lane);
     const int a_lo = part * per_part, a_hi = min(a_lo + per_part, n_anchors);
     int count = 0;
@@ -109,8 +118,21 @@ nms_scan_kernel(const float* __restrict__ pred_all, int n_anchors, int no, float
         uint32_t key = 0, val = 0;
         if (a < a_hi) {
             const float* p = pred + (size_t)a * no;
-            const float obj = p[4];
-            if (obj > conf_thres) {
+            if (AF) {
+                // ultralytics non_max_suppression (multi_label=False): conf, j = max over the classes; conf > conf_thres
+                float best = p[4];
+                int bi = 0;
+                for (int k = 1; k < nc; ++k) {
+                    const float v = p[4 + k];
+                    if (v > best) { best = v; bi = k; }
+                }
+                if (best > conf_thres) {
+                    pass = true;
+                    key = sort_key_desc(best);
+                    val = (uint32_t)a | ((uint32_t)bi << 24);
+                }
+            } else if (p[4] > conf_thres) {
+                const float obj = p[4];
                 float best = p[5] * obj;
                 int bi = 0;
                 for (int k = 1; k < nc; ++k) {
@@ -145,9 +167,10 @@ nms_scan_kernel(const float* __restrict__ pred_all, int n_anchors, int no, float
     if (tid == 0) seg_cnt[(size_t)img * kNmsScanParts + part] = (uint32_t)count;
 }
 
+template <bool AF>
 __global__ void __launch_bounds__(NT)
 nms_image_kernel(const float* __restrict__ pred_all, int n_anchors, int no, float conf_thres,
-                 float iou_thres, int max_det, uint32_t* keys0, uint32_t* vals0, uint32_t* keys1,
+                 float iou_thres, int max_det, int max_rank, uint32_t* keys0, uint32_t* vals0, uint32_t* keys1,
                  uint32_t* vals1, uint32_t* keys2, uint32_t* vals2, int cap, int per_part,
                  const uint32_t* __restrict__ seg_cnt, float* __restrict__ out, int* __restrict__ counts) {
     __shared__ NmsLds L;
@@ -213,7 +236,10 @@ nms_image_kernel(const float* __restrict__ pred_all, int n_anchors, int no, floa
     if (max_det > kNmsMaxDet) max_det = kNmsMaxDet;
     int done = 0, b_start = 0;                                      // candidates / bins consumed by earlier bands
     uint32_t want = kBandFirst;
-    while (done < count && nk < max_det) {
+    // anchor-free mode: only the max_rank highest-ranked candidates take part (ultralytics max_nms); the YOLOv5 mode
+    // passes max_rank >= count
+    const int ranked = min(count, max_rank);
+    while (done < ranked && nk < max_det) {
         // ---- this band: bins [b_start, b_end], b_end = the first bin that brings the band to `want` candidates ----
         if (tid == 0) L.band_end = kBandBins - 1;
         __syncthreads();
@@ -226,6 +252,7 @@ nms_image_kernel(const float* __restrict__ pred_all, int n_anchors, int no, floa
         __syncthreads();
         const int b_end = L.band_end;
         const int bcount = (int)L.band[b_end] - done;
+        const int bused = min(bcount, ranked - done);         // sorted candidates of this band inside the rank cut
         // ---- compaction of the band out of buffer 1 (anchor order: the sort below stays stable), wavefront ranges ----
         {
             int mine = 0;
@@ -329,15 +356,16 @@ nms_image_kernel(const float* __restrict__ pred_all, int n_anchors, int no, floa
     const uint32_t* sorted_v = vbuf[0];              // four passes: back in buffer 0 (also when bcount <= 1)
 
     // ---------------- stage C: greedy suppression over the band's sorted candidates ----------------
-    for (int c0 = 0; c0 < bcount && nk < max_det; c0 += NT) {
+    for (int c0 = 0; c0 < bused && nk < max_det; c0 += NT) {
         const int i = c0 + tid;
-        const bool valid = i < bcount;
+        const bool valid = i < bused;
         float4 box = make_float4(0.f, 0.f, 0.f, 0.f);
-        int cls = -1;
+        int cls = -1, anchor = -1;
         float conf = 0.f;
         if (valid) {
             const uint32_t v = sorted_v[i];
             const int a = (int)(v & 0xffffffu);
+            anchor = a;
             cls = (int)(v >> 24);
             const float* p = pred + (size_t)a * no;
             const float cx = p[0], cy = p[1], w = p[2], h = p[3];
@@ -345,7 +373,14 @@ nms_image_kernel(const float* __restrict__ pred_all, int n_anchors, int no, floa
             box.y = cy - h / 2.0f;
             box.z = cx + w / 2.0f;
             box.w = cy + h / 2.0f;
-            conf = p[5 + cls] * p[4];
+            if (AF) {
+                // ultralytics: one torchvision nms over boxes + cls * max_wh (7680): the IoU sees the shifted fp32 coordinates
+                const float off = (float)cls * 7680.0f;
+                box.x = box.x + off; box.y = box.y + off; box.z = box.z + off; box.w = box.w + off;
+                conf = p[4 + cls];
+            } else {
+                conf = p[5 + cls] * p[4];
+            }
         }
         bool alive = valid;
         for (int k = 0; k < nk; ++k) {
@@ -354,6 +389,7 @@ nms_image_kernel(const float* __restrict__ pred_all, int n_anchors, int no, floa
         L.u.chunk_box[tid] = box;
         L.chunk_cls[tid] = cls;
         L.chunk_conf[tid] = conf;
+        L.chunk_anchor[tid] = anchor;
         {
             const unsigned long long bal = __ballot(alive);
             if (lane == 0) L.alive[0][wave] = bal;
@@ -393,9 +429,9 @@ nms_image_kernel(const float* __restrict__ pred_all, int n_anchors, int no, floa
                     }
                 }
                 float4 gb = make_float4(0.f, 0.f, 0.f, 0.f);
-                int gc = -2;
+                int gc = -2, ga = -1;
                 float gconf = 0.f;
-                if (idx >= 0) { gb = L.u.chunk_box[idx]; gc = L.chunk_cls[idx]; gconf = L.chunk_conf[idx]; }
+                if (idx >= 0) { gb = L.u.chunk_box[idx]; gc = L.chunk_cls[idx]; gconf = L.chunk_conf[idx]; ga = L.chunk_anchor[idx]; }
                 bool galive = idx >= 0;
                 for (int k = 0; k < group; ++k) {
                     const unsigned long long am = __ballot(galive);
@@ -411,6 +447,7 @@ nms_image_kernel(const float* __restrict__ pred_all, int n_anchors, int no, floa
                     L.kept_box[nk + rank] = gb;
                     L.kept_conf[nk + rank] = gconf;
                     L.kept_cls[nk + rank] = gc;
+                    L.kept_anchor[nk + rank] = ga;
                 }
                 // the candidates of this round leave the alive set (kept or suppressed)
                 if (idx >= 0) atomicAnd(&L.alive[0][idx >> 6], ~(1ull << (idx & 63)));
@@ -445,7 +482,12 @@ nms_image_kernel(const float* __restrict__ pred_all, int n_anchors, int no, floa
     __syncthreads();
     float* o = out + (size_t)img * max_det * 6;
     for (int k = tid; k < nk; k += NT) {
-        const float4 b = L.kept_box[k];
+        float4 b = L.kept_box[k];
+        if (AF) {                                  // the unshifted box, recomputed with the same statements
+            const float* p = pred + (size_t)L.kept_anchor[k] * no;
+            const float cx = p[0], cy = p[1], w = p[2], h = p[3];
+            b = make_float4(cx - w / 2.0f, cy - h / 2.0f, cx + w / 2.0f, cy + h / 2.0f);
+        }
         o[k * 6 + 0] = b.x;
         o[k * 6 + 1] = b.y;
         o[k * 6 + 2] = b.z;
@@ -460,16 +502,25 @@ nms_image_kernel(const float* __restrict__ pred_all, int n_anchors, int no, floa
 
 hipError_t launch_nms(const float* pred, int n, int n_anchors, int no, float conf_thres,
                       float iou_thres, int max_det, const NmsScratch& scr, float* out, int* counts,
-                      hipStream_t s) {
+                      hipStream_t s, bool anchor_free) {
     if (n_anchors > scr.cap || max_det > kNmsMaxDet || max_det < 1 || !scr.seg_cnt || !scr.keys[2] || !scr.vals[2]) return hipErrorInvalidValue;
     const int per_part = (n_anchors + kNmsScanParts - 1) / kNmsScanParts;
-    hipLaunchKernelGGL(nms_scan_kernel, dim3(kNmsScanParts, n), dim3(NTS), 0, s, pred, n_anchors, no, conf_thres, per_part,
-                       scr.keys[0], scr.vals[0], scr.cap, scr.seg_cnt);
+    if (anchor_free)
+        hipLaunchKernelGGL(nms_scan_kernel<true>, dim3(kNmsScanParts, n), dim3(NTS), 0, s, pred, n_anchors, no, conf_thres, per_part,
+                           scr.keys[0], scr.vals[0], scr.cap, scr.seg_cnt);
+    else
+        hipLaunchKernelGGL(nms_scan_kernel<false>, dim3(kNmsScanParts, n), dim3(NTS), 0, s, pred, n_anchors, no, conf_thres, per_part,
+                           scr.keys[0], scr.vals[0], scr.cap, scr.seg_cnt);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(nms_image_kernel, dim3(n), dim3(NT), 0, s, pred, n_anchors, no, conf_thres,
-                       iou_thres, max_det, scr.keys[0], scr.vals[0], scr.keys[1], scr.vals[1], scr.keys[2], scr.vals[2],
-                       scr.cap, per_part, scr.seg_cnt, out, counts);
+    if (anchor_free)
+        hipLaunchKernelGGL(nms_image_kernel<true>, dim3(n), dim3(NT), 0, s, pred, n_anchors, no, conf_thres,
+                           iou_thres, max_det, kNmsMaxNmsAnchorFree, scr.keys[0], scr.vals[0], scr.keys[1], scr.vals[1], scr.keys[2],
+                           scr.vals[2], scr.cap, per_part, scr.seg_cnt, out, counts);
+    else
+        hipLaunchKernelGGL(nms_image_kernel<false>, dim3(n), dim3(NT), 0, s, pred, n_anchors, no, conf_thres,
+                           iou_thres, max_det, 0x7fffffff, scr.keys[0], scr.vals[0], scr.keys[1], scr.vals[1], scr.keys[2],
+                           scr.vals[2], scr.cap, per_part, scr.seg_cnt, out, counts);
     return hipGetLastError();
 }
 

@@ -131,6 +131,11 @@ class HIPDetector:
         else:
             weights = model_path
         self.weights = weights
+        # YOLO11 (MDv1000-larch / -sorrel): the reference runs them through the ultralytics package -- its NMS and its
+        # scale_boxes (pytorch_detector.py:395-402, :1327-1344); the library picks the NMS from the model's head
+        self.anchor_free = bool(getattr(weights, 'anchor_free', False))
+        if self.anchor_free and str(opts.get('dtype') or DEFAULT_DTYPE).lower() == 'fp8':
+            raise ValueError("dtype 'fp8' is implemented for YOLOv5 models only; use 'fp16' or 'bf16' for a YOLO11 model")
         if weights.max_stride != self.letterbox_stride and verbose:
             print('*** Warning: model stride is {}, letterbox stride is {} ***'.format(
                 weights.max_stride, self.letterbox_stride))
@@ -245,6 +250,7 @@ class HIPDetector:
             detection_threshold = 0.0
         if self._ctx is None:
             raise RuntimeError('this HIPDetector was created with preprocess_only')
+        self._check_augment(augment)
         results, shape_groups = self._prepare_batch(img_original, image_id, image_size, verbose)
         for shape, items in shape_groups.items():
             try:
@@ -280,6 +286,10 @@ class HIPDetector:
             shape_groups.setdefault(tuple(item[1]['img_processed'].shape), []).append(item)
         return results, shape_groups
 
+    def _check_augment(self, augment):
+        if augment and getattr(self, 'anchor_free', False):
+            raise ValueError('augment=True (test-time augmentation) is implemented for YOLOv5 models only, not for YOLO11')
+
     def _nms_iou(self):
         return 0.45 if 'classic' in self.compatibility_mode else 0.6        # reference :1318-1321
 
@@ -305,7 +315,7 @@ class HIPDetector:
                 det, (h, w), info.get('resized_shape', info['img_original'].shape) if modern else info['img_original'].shape,
                 info['scaling_shape'], detection_threshold,
                 use_model_native_classes=self.use_model_native_classes, modern=modern,
-                letterbox_pad=info.get('letterbox_pad'))
+                letterbox_pad=info.get('letterbox_pad'), round_pad=getattr(self, 'anchor_free', False))
             results[original_idx] = {'file': current_id, 'detections': detections,
                                      'max_detection_conf': max_conf}
 
@@ -433,6 +443,7 @@ class HIPDetector:
         Same arguments as generate_detections_one_batch (augment = yolov5's three-pass augmented inference)."""
         if self._ctx is None:
             raise RuntimeError('this HIPDetector was created with preprocess_only')
+        self._check_augment(augment)
         if detection_threshold is None:
             detection_threshold = 0.0
         results, shape_groups = self._prepare_batch(img_original, image_id, image_size, verbose)

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import HipError
-from .yolo_model import MDHIP_DETECT
+from .yolo_model import DETECT_TYPES
 
 
 class HipContext:
@@ -69,8 +69,9 @@ class HipContext:
             raise HipError('mdhip_create failed ({}): {}'.format(
                 rc, self.lib.mdhip_last_error(None).decode()))
         self.h = handle
-        self.no = weights.nc + 5
-        self.has_detect = specs[-1].type == MDHIP_DETECT
+        self.anchor_free = bool(getattr(weights, 'anchor_free', False))
+        self.no = weights.nc + (4 if self.anchor_free else 5)      # anchor-free rows: [cx, cy, w, h, cls...]
+        self.has_detect = specs[-1].type in DETECT_TYPES
         self.max_stride = self.lib.mdhip_max_stride(self.h)
         self.load_tuned()
 
@@ -82,6 +83,10 @@ class HipContext:
         entries.  Shapes without an entry use the built-in heuristic, so a missing or stale file only
         costs speed.
         """
+        if path is None and getattr(self, 'anchor_free', False):
+            # the tables hold YOLOv5 layers; the YOLO11 layers take the built-in heuristic (an entry matched by geometry
+            # from another model would pick a kernel family for them that nobody measured)
+            return 0
         if path is None:
             # a table measured for this storage type, if there is one (tuned_cfgs_fp16.json), else the bf16 table
             path = self.TUNED_PATH

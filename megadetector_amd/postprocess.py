@@ -66,7 +66,7 @@ def modern_geometry(shape_hw, image_size=1280, stride=64, use_ceil=False):
 
 
 def format_detections(det, batch_hw, img_original_shape, scaling_shape, detection_threshold,
-                      use_model_native_classes=False, modern=False, letterbox_pad=None):
+                      use_model_native_classes=False, modern=False, letterbox_pad=None, round_pad=False):
     """
     det: (k,6) float32 [x1,y1,x2,y2,conf,cls] in letterboxed pixels, confidence-descending
     (what mdhip_nms returns).  Returns (detections, max_conf) exactly as the reference builds
@@ -74,6 +74,9 @@ def format_detections(det, batch_hw, img_original_shape, scaling_shape, detectio
     modern=True (reference :1369-1381,:1396-1397): `img_original_shape` is the shape of the RESIZED image,
     scale_coords gets ratio_pad = ((resized / original per axis), letterbox_pad) -- gain = the first ratio --
     and coordinates / confidences are rounded instead of truncated.
+    round_pad=True: the ultralytics scale_boxes the reference imports for YOLO11 models (pytorch_detector.py:402, [3P])
+    -- in the classic mode the padding is rounded, pad = round((w1 - w0 * gain) / 2 - 0.1) per axis (Python round:
+    half to even); the modern mode is the same as YOLOv5's.
     """
     det = np.asarray(det, dtype=_F)
     k = det.shape[0]
@@ -89,6 +92,8 @@ def format_detections(det, batch_hw, img_original_shape, scaling_shape, detectio
         # scale_coords (ratio_pad=None) -- gain/pad are Python floats, tensor math is fp32
         gain = min(h1 / h0, w1 / w0)
         pad = ((w1 - w0 * gain) / 2, (h1 - h0 * gain) / 2)
+        if round_pad:
+            pad = (round(pad[0] - 0.1), round(pad[1] - 0.1))
     xyxy = det[:, :4].copy()
     xyxy[:, [0, 2]] -= _F(pad[0])
     xyxy[:, [1, 3]] -= _F(pad[1])

@@ -17,7 +17,7 @@ import zipfile
 import numpy as np
 
 from . import yolo_yaml
-from .yolo_model import YoloWeights, resolve_yaml, MDHIP_DETECT
+from .yolo_model import YoloWeights, resolve_yaml, MDHIP_DETECT, MDHIP_DETECT_DFL
 
 
 # --------------------------------------------------------------------------------------
@@ -40,6 +40,8 @@ def synthetic_weights(yaml=None, seed=0, gain=1.75, res_gain=0.6, bias_std=0.1,
     """
     from .yolo_model import model_strides
     yaml = yaml or yolo_yaml.YOLOV5X6_MD
+    if yolo_yaml.is_yolo11(yaml):
+        return synthetic_weights_yolo11(yaml, seed=seed)
     specs = resolve_yaml(yaml)
     rng = np.random.Generator(np.random.PCG64(seed))
     w = {}
@@ -75,6 +77,77 @@ def synthetic_weights(yaml=None, seed=0, gain=1.75, res_gain=0.6, bias_std=0.1,
             wt *= np.float32(g / np.sqrt(c1 * k * k))
             w[name + '.weight'] = wt
             w[name + '.bias'] = rng.standard_normal(c2, dtype=np.float32) * np.float32(bias_std)
+    return YoloWeights(yaml, w, source='synthetic(seed={})'.format(seed))
+
+
+def yolo11_conv_shapes(s, specs):
+    """(name, (c_out, c_in, k)) of every conv of a YOLO11 layer, in the order of include/mdhip.h (c_in 1 = depthwise)"""
+    from .yolo_model import MDHIP_C3K2, MDHIP_C2PSA
+    names = s.conv_names
+    if s.type == MDHIP_C3K2:
+        c = s.hidden
+        shapes = [(2 * c, s.c_in, 1), (s.c_out, (2 + s.n) * c, 1)]
+        for _ in range(s.n):
+            if s.k:
+                h = c // 2
+                shapes += [(h, c, 1), (h, c, 1), (c, 2 * h, 1)] + [(h, h, 3)] * 4
+            else:
+                shapes += [(c // 2, c, 3), (c, c // 2, 3)]
+    elif s.type == MDHIP_C2PSA:
+        c = s.hidden
+        shapes = [(2 * c, s.c_in, 1), (s.c_out, 2 * c, 1)]
+        for _ in range(s.n):
+            shapes += [(2 * c, c, 1), (c, c, 1), (c, 1, 3), (2 * c, c, 1), (c, 2 * c, 1)]
+    elif s.type == MDHIP_DETECT_DFL:
+        c2, c3 = s.hidden
+        nc = s.c_out - 4
+        shapes = []
+        for f in s.frm:
+            cx = specs[f].c_out
+            shapes += [(c2, cx, 3), (c2, c2, 3), (64, c2, 1), (cx, 1, 3), (c3, cx, 1), (c3, 1, 3), (c3, c3, 1), (nc, c3, 1)]
+    else:
+        shapes = _conv_shapes(s)
+    assert len(shapes) == len(names), (s.index, len(shapes), len(names))
+    return list(zip(names, shapes))
+
+
+def synthetic_weights_yolo11(yaml, seed=0, gain=1.6, res_gain=0.5, bias_std=0.1, cls_bias=-12.0, cls_gain=1.5,
+                             box_gain=0.5):
+    """
+    Seeded weights on a YOLO11 topology, built like the YOLOv5 set: zero-mean N(0, gain^2 / fan_in) kernels, the
+    convs that end a residual branch (bottleneck cv2, attention proj, ffn.1) at res_gain, the ones without activation
+    at gain 1.  Class biases of -12 with logits of std ~1.5 let about one anchor in six clear the 1e-5 batch-mode
+    threshold (sigmoid(-11.5) = 1e-5), as the YOLOv5 set does; box logits stay small (boxes of a
+    few cells).
+    """
+    specs = resolve_yaml(yaml)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    w = {}
+    for s in specs:
+        for name, (c2, c1, k) in yolo11_conv_shapes(s, specs):
+            wt = rng.standard_normal((c2, c1, k, k), dtype=np.float32)
+            fan = c1 * k * k
+            if c1 > 1:
+                wt -= wt.mean(axis=(1, 2, 3), keepdims=True)
+            g = gain
+            if name.endswith(('.attn.proj.conv', '.ffn.1.conv')) or (s.type != MDHIP_DETECT_DFL and name.endswith('.cv2.conv')
+                                                                      and '.m.' in name):
+                g = res_gain
+            elif name.endswith(('.attn.qkv.conv', '.attn.pe.conv')):
+                g = 1.0
+            b = rng.standard_normal(c2, dtype=np.float32) * np.float32(bias_std)
+            if s.type == MDHIP_DETECT_DFL and name.split('.')[-1] == '2':
+                if name.split('.')[2] == 'cv2':       # box logits
+                    g = box_gain * np.sqrt(fan)
+                    b = rng.standard_normal(c2, dtype=np.float32) * np.float32(0.5)
+                else:                                 # class logits
+                    g = cls_gain * np.sqrt(fan)
+                    b = np.float32(cls_bias) + rng.standard_normal(c2, dtype=np.float32) * np.float32(0.5)
+            wt *= np.float32(g / np.sqrt(fan))
+            w[name + '.weight'] = wt.astype(np.float32)
+            w[name + '.bias'] = b.astype(np.float32)
+    det = specs[-1]
+    w['model.{}.dfl.conv.weight'.format(det.index)] = np.arange(16, dtype=np.float32).reshape(1, 16, 1, 1)
     return YoloWeights(yaml, w, source='synthetic(seed={})'.format(seed))
 
 
@@ -255,6 +328,8 @@ def load_checkpoint(path):
     if isinstance(ckpt, dict) and ckpt.get('ema') is not None and not hasattr(model, 'yaml'):
         model = ckpt['ema']
     yaml = dict(model.__dict__['yaml'])
+    if yolo_yaml.is_yolo11(yaml) or type(model).__module__.split('.')[0] == 'ultralytics':
+        return _load_ultralytics(model, yaml, path)
     if 'anchors' in yaml and not isinstance(yaml['anchors'], (list, tuple)):
         raise ValueError('checkpoint yaml has no explicit anchor list')
     seq = _modules(model)['model']
@@ -277,6 +352,59 @@ def load_checkpoint(path):
             wf, bf = _fold(sub)
             w[name + '.weight'] = wf
             w[name + '.bias'] = bf
+    names = model.__dict__.get('names')
+    if isinstance(names, (list, tuple)):
+        names = {i: n for i, n in enumerate(names)}
+    return YoloWeights(yaml, w, names=names, source=path)
+
+
+def _load_ultralytics(model, yaml, path):
+    """
+    An ultralytics checkpoint (MDv1000-larch / -sorrel: {'model': DetectionModel}, model.yaml = the yolo11 yaml dict with
+    'scale').  What the reference runs is model.float().fuse() (pytorch_detector.py:957): every Conv / DWConv -- the
+    Attention's qkv / proj / pe included -- with its BatchNorm folded; the Detect head's final Conv2d layers and the DFL
+    conv have no BatchNorm.  The head must be the current one (class branch DWConv -> Conv -> DWConv -> Conv -> Conv2d):
+    the older 'legacy' head (Conv 3x3 -> Conv 3x3 -> Conv2d) is refused.
+    """
+    if not yolo_yaml.is_yolo11(yaml):
+        raise ValueError('{}: ultralytics checkpoint without a YOLO11 model description'.format(path))
+    specs = resolve_yaml(yaml)           # refuses other ultralytics modules (cedar = YOLOv9c) by name
+    layers = _modules(_modules(model)['model'])
+    det = specs[-1]
+    if det.type != MDHIP_DETECT_DFL:
+        raise ValueError('{}: the last layer is not an anchor-free Detect head'.format(path))
+    dmod = layers[str(det.index)]
+    dm = _modules(dmod)
+    if 'cv3' not in dm or 'dfl' not in dm:
+        raise ValueError('{}: Detect head without cv3 / dfl'.format(path))
+    for l in range(len(det.frm)):
+        branch = _modules(_modules(dm['cv3'])[str(l)])
+        first = branch.get('0')
+        if first is None or 'conv' in _modules(first) or '0' not in _modules(first):
+            raise ValueError('{}: legacy YOLO11 Detect head (class branch without DWConv) is not supported; only the '
+                             'current head (DWConv 3x3 -> Conv 1x1 -> DWConv 3x3 -> Conv 1x1 -> Conv2d) is'.format(path))
+    if getattr(dmod, 'end2end', False):
+        raise ValueError('{}: end-to-end (one-to-one) Detect heads are not supported'.format(path))
+    reg_max = int(getattr(dmod, 'reg_max', 16))
+    dfl_w = _np32(_param(_modules(dm['dfl'])['conv'], 'weight')).reshape(-1)
+    if reg_max != 16 or dfl_w.shape != (16,) or not np.array_equal(dfl_w, np.arange(16, dtype=np.float32)):
+        raise ValueError('{}: DFL conv weight must be arange(16) (reg_max 16)'.format(path))
+    w = {}
+    for s in specs:
+        mod = layers[str(s.index)]
+        for name in s.conv_names:
+            sub = mod
+            parts = name.split('.')[2:]
+            for part in (parts[:-1] if parts[-1] == 'conv' else parts):
+                sub = _modules(sub)[part]
+            if parts[-1] == 'conv':
+                wf, bf = _fold(sub)
+            else:                                         # a plain Conv2d of the Detect head (bias, no BatchNorm)
+                wf = _np32(_param(sub, 'weight'))
+                bf = _np32(_param(sub, 'bias'))
+            w[name + '.weight'] = wf
+            w[name + '.bias'] = bf
+    w['model.{}.dfl.conv.weight'.format(det.index)] = dfl_w.reshape(1, 16, 1, 1)
     names = model.__dict__.get('names')
     if isinstance(names, (list, tuple)):
         names = {i: n for i, n in enumerate(names)}

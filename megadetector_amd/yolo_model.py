@@ -14,6 +14,12 @@ import numpy as np
 
 # module kinds of include/mdhip.h
 MDHIP_CONV, MDHIP_C3, MDHIP_SPPF, MDHIP_UPSAMPLE, MDHIP_CONCAT, MDHIP_DETECT = range(6)
+MDHIP_C3K2, MDHIP_C2PSA, MDHIP_DETECT_DFL = 6, 7, 8
+
+DETECT_TYPES = (MDHIP_DETECT, MDHIP_DETECT_DFL)
+#: ultralytics modules of other MDv1000 architectures (cedar = YOLOv9c) that this package does not run
+_OTHER_ULTRALYTICS = ('RepNCSPELAN4', 'ADown', 'SPPELAN', 'CBLinear', 'CBFuse', 'DDetect', 'DualDDetect', 'Silence',
+                      'C2f', 'RepC3', 'AConv', 'ELAN1', 'Segment', 'Pose', 'OBB', 'v10Detect')
 
 
 def _make_divisible(x, divisor):
@@ -33,8 +39,10 @@ def resolve_yaml(yaml, ch=3):
     """
     yaml dict -> list[LayerSpec]; every 'from' is an absolute layer index (-1 = network input);
     conv_names lists the state_dict prefixes ('model.2.cv1.conv', ...) of the layer's convs in
-    the order include/mdhip.h prescribes.
+    the order include/mdhip.h prescribes.  YOLOv5 and YOLO11 (ultralytics, anchor-free) yamls.
     """
+    if 'anchors' not in yaml:
+        return resolve_yolo11_yaml(yaml, ch)
     anchors, nc = yaml['anchors'], yaml['nc']
     gd, gw = yaml['depth_multiple'], yaml['width_multiple']
     na = (len(anchors[0]) // 2) if isinstance(anchors, (list, tuple)) else int(anchors)
@@ -91,6 +99,100 @@ def resolve_yaml(yaml, ch=3):
     return specs
 
 
+def resolve_yolo11_yaml(yaml, ch=3):
+    """
+    ultralytics yolo11.yaml dict -> list[LayerSpec] ([3P] ultralytics nn/tasks.py parse_model, restated):
+    channels make_divisible(min(c, max_channels) * width, 8), repeats max(round(n * depth), 1) for n > 1, c3k forced on
+    every C3k2 at the m / l / x scales, Detect hidden widths c2 = max(16, ch0 / 4, 64), c3 = max(ch0, min(nc, 100)).
+    """
+    nc = int(yaml['nc'])
+    scale = yaml.get('scale')
+    scales = yaml.get('scales') or {}
+    if not scale or scale not in scales:
+        raise ValueError('YOLO11 model description without a usable "scale" (got {!r}; scales {})'.format(
+            scale, sorted(scales)))
+    gd, gw, max_ch = scales[scale]
+    out_ch, specs = [], []
+    rows = list(yaml['backbone']) + list(yaml['head'])
+    for i, (f, n, m, args) in enumerate(rows):
+        args = list(args)
+        m = m.split('.')[-1] if m.startswith('torch.nn.') else m
+        n_rep = max(round(n * gd), 1) if n > 1 else n
+        frm = [f] if isinstance(f, int) else list(f)
+        frm = [(i - 1 if x == -1 else (x if x >= 0 else i + x)) for x in frm]
+        c_in = ch if frm[0] < 0 else out_ch[frm[0]]
+        pre = 'model.{}'.format(i)
+        div = lambda c: _make_divisible(min(c, max_ch) * gw, 8)
+        if m == 'Conv':
+            c2 = div(args[0])
+            k = args[1] if len(args) > 1 else 1
+            s = args[2] if len(args) > 2 else 1
+            p = args[3] if len(args) > 3 and args[3] is not None else k // 2
+            spec = LayerSpec(index=i, type=MDHIP_CONV, frm=frm, c_in=c_in, c_out=c2, k=k, s=s, p=p,
+                             n=1, shortcut=0, conv_names=[pre + '.conv'])
+        elif m == 'C3k2':
+            c2 = div(args[0])
+            c3k = bool(args[1]) if len(args) > 1 else False
+            e = args[2] if len(args) > 2 else 0.5
+            if scale in 'mlx':
+                c3k = True
+            c = int(c2 * e)
+            names = [pre + '.cv1.conv', pre + '.cv2.conv']
+            for j in range(n_rep):
+                b = '{}.m.{}'.format(pre, j)
+                if c3k:
+                    names += [b + '.cv1.conv', b + '.cv2.conv', b + '.cv3.conv']
+                    names += ['{}.m.{}.cv{}.conv'.format(b, q, r) for q in range(2) for r in (1, 2)]
+                else:
+                    names += [b + '.cv1.conv', b + '.cv2.conv']
+            spec = LayerSpec(index=i, type=MDHIP_C3K2, frm=frm, c_in=c_in, c_out=c2, k=int(c3k), s=1, p=0,
+                             n=n_rep, shortcut=1, hidden=c, conv_names=names)
+        elif m == 'C2PSA':
+            c2 = div(args[0])
+            if c2 != c_in:
+                raise ValueError('C2PSA at layer {}: c1 {} != c2 {}'.format(i, c_in, c2))
+            names = [pre + '.cv1.conv', pre + '.cv2.conv']
+            for j in range(n_rep):
+                b = '{}.m.{}'.format(pre, j)
+                names += [b + '.attn.qkv.conv', b + '.attn.proj.conv', b + '.attn.pe.conv', b + '.ffn.0.conv',
+                          b + '.ffn.1.conv']
+            spec = LayerSpec(index=i, type=MDHIP_C2PSA, frm=frm, c_in=c_in, c_out=c2, k=0, s=1, p=0,
+                             n=n_rep, shortcut=1, hidden=c2 // 2, conv_names=names)
+        elif m == 'SPPF':
+            c2 = div(args[0])
+            k = args[1] if len(args) > 1 else 5
+            spec = LayerSpec(index=i, type=MDHIP_SPPF, frm=frm, c_in=c_in, c_out=c2, k=k, s=1,
+                             p=k // 2, n=1, shortcut=0, hidden=c_in // 2,
+                             conv_names=[pre + '.cv1.conv', pre + '.cv2.conv'])
+        elif m in ('nn.Upsample', 'Upsample'):
+            if args[1] != 2 or (len(args) > 2 and args[2] != 'nearest'):
+                raise ValueError('only nearest x2 upsampling is supported')
+            spec = LayerSpec(index=i, type=MDHIP_UPSAMPLE, frm=frm, c_in=c_in, c_out=c_in, k=0, s=1,
+                             p=0, n=1, shortcut=0, conv_names=[])
+        elif m == 'Concat':
+            c2 = sum(out_ch[x] for x in frm)
+            spec = LayerSpec(index=i, type=MDHIP_CONCAT, frm=frm, c_in=c_in, c_out=c2, k=0, s=1, p=0,
+                             n=1, shortcut=0, conv_names=[])
+        elif m == 'Detect':
+            names = []
+            for l in range(len(frm)):
+                names += ['{}.cv2.{}.0.conv'.format(pre, l), '{}.cv2.{}.1.conv'.format(pre, l), '{}.cv2.{}.2'.format(pre, l),
+                          '{}.cv3.{}.0.0.conv'.format(pre, l), '{}.cv3.{}.0.1.conv'.format(pre, l),
+                          '{}.cv3.{}.1.0.conv'.format(pre, l), '{}.cv3.{}.1.1.conv'.format(pre, l),
+                          '{}.cv3.{}.2'.format(pre, l)]
+            ch0 = out_ch[frm[0]]
+            spec = LayerSpec(index=i, type=MDHIP_DETECT_DFL, frm=frm, c_in=c_in, c_out=4 + nc, k=1, s=1, p=0,
+                             n=1, shortcut=0, hidden=(max(16, ch0 // 4, 64), max(ch0, min(nc, 100))), conv_names=names)
+        elif m in _OTHER_ULTRALYTICS:
+            raise ValueError('unsupported ultralytics module "{}" at layer {}: of the ultralytics MDv1000 models only the '
+                             'YOLO11 ones (larch, sorrel) run on the HIP path; cedar (YOLOv9c) does not'.format(m, i))
+        else:
+            raise ValueError('unsupported YOLO11 module "{}" at layer {}'.format(m, i))
+        specs.append(spec)
+        out_ch.append(spec.c_out if spec.type != MDHIP_DETECT_DFL else None)
+    return specs
+
+
 def model_strides(specs):
     """Stride of every Detect input level, derived from the graph (== model.stride)."""
     div = []
@@ -102,7 +204,7 @@ def model_strides(specs):
             d //= 2
         div.append(d)
     det = specs[-1]
-    if det.type != MDHIP_DETECT:
+    if det.type not in DETECT_TYPES:
         return []
     return [float(div[f]) for f in det.frm]
 
@@ -124,7 +226,12 @@ class YoloWeights:
         self.strides = model_strides(self.specs)
         self.nl = len(self.strides)
         det = self.specs[-1]
-        if det.type == MDHIP_DETECT:
+        #: anchor-free (YOLO11) head: predictions [cx, cy, w, h, cls...], the ultralytics NMS and box rescale
+        self.anchor_free = det.type == MDHIP_DETECT_DFL
+        if self.anchor_free:
+            self.na = 1
+            self.anchors_px = np.zeros((0, 0, 2), dtype=np.float32)
+        elif det.type == MDHIP_DETECT:
             a = self.weights['model.{}.anchors'.format(det.index)].reshape(self.nl, -1, 2)
             self.na = a.shape[1]
             self.anchors_px = np.ascontiguousarray(

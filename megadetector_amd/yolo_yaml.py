@@ -130,3 +130,81 @@ YOLOV5S6_TEST = make_yaml(0.33, 0.50, nc=3, p6=True)
 #: small P5 (3 heads, stride 32) network with 5 classes: the non-P6 family members (MDv1000-spruce is a
 #: YOLOv5s) and a class count other than 3, in the tests
 YOLOV5N_P5_TEST = make_yaml(0.33, 0.25, nc=5, p6=False)
+
+
+# --------------------------------------------------------------------------------------
+# YOLO11 (anchor-free) descriptions: MDv1000-larch (YOLO11-L, 640 px) and MDv1000-sorrel (YOLO11-s, 960 px)
+# (reference docs/release-notes/mdv1000-release.md:278-284, :317).  The reference loads them through the third-party
+# ultralytics package (8.3.x); its published yolo11.yaml is restated here in the ultralytics yaml format [3P]:
+# 'scales' maps a scale to [depth, width, max_channels], 'scale' names the one in use (the checkpoint's model.yaml
+# carries both).
+# --------------------------------------------------------------------------------------
+
+YOLO11_SCALES = {
+    'n': [0.50, 0.25, 1024],
+    's': [0.50, 0.50, 1024],
+    'm': [0.50, 1.00, 512],
+    'l': [1.00, 1.00, 512],
+    'x': [1.00, 1.50, 512],
+}
+
+_BACKBONE_YOLO11 = [
+    [-1, 1, 'Conv', [64, 3, 2]],               # 0-P1/2
+    [-1, 1, 'Conv', [128, 3, 2]],              # 1-P2/4
+    [-1, 2, 'C3k2', [256, False, 0.25]],
+    [-1, 1, 'Conv', [256, 3, 2]],              # 3-P3/8
+    [-1, 2, 'C3k2', [512, False, 0.25]],
+    [-1, 1, 'Conv', [512, 3, 2]],              # 5-P4/16
+    [-1, 2, 'C3k2', [512, True]],
+    [-1, 1, 'Conv', [1024, 3, 2]],             # 7-P5/32
+    [-1, 2, 'C3k2', [1024, True]],
+    [-1, 1, 'SPPF', [1024, 5]],                # 9
+    [-1, 2, 'C2PSA', [1024]],                  # 10
+]
+
+_HEAD_YOLO11 = [
+    [-1, 1, 'nn.Upsample', [None, 2, 'nearest']],
+    [[-1, 6], 1, 'Concat', [1]],               # cat backbone P4
+    [-1, 2, 'C3k2', [512, False]],             # 13
+    [-1, 1, 'nn.Upsample', [None, 2, 'nearest']],
+    [[-1, 4], 1, 'Concat', [1]],               # cat backbone P3
+    [-1, 2, 'C3k2', [256, False]],             # 16 (P3/8-small)
+    [-1, 1, 'Conv', [256, 3, 2]],
+    [[-1, 13], 1, 'Concat', [1]],              # cat head P4
+    [-1, 2, 'C3k2', [512, False]],             # 19 (P4/16-medium)
+    [-1, 1, 'Conv', [512, 3, 2]],
+    [[-1, 10], 1, 'Concat', [1]],              # cat head P5
+    [-1, 2, 'C3k2', [1024, True]],             # 22 (P5/32-large)
+    [[16, 19, 22], 1, 'Detect', ['nc']],       # 23 Detect(P3, P4, P5)
+]
+
+
+def make_yolo11_yaml(scale, nc=3):
+    """A YOLO11 yaml dict (the keys ultralytics pickles as model.yaml) at one scale."""
+    return {
+        'nc': nc,
+        'scales': {k: list(v) for k, v in YOLO11_SCALES.items()},
+        'scale': scale,
+        'backbone': [list(r) for r in _BACKBONE_YOLO11],
+        'head': [list(r) for r in _HEAD_YOLO11],
+    }
+
+
+#: MDv1000-larch: YOLO11-L, nc = 3, 640 px
+YOLO11L_MD = make_yolo11_yaml('l', nc=3)
+
+#: MDv1000-sorrel: YOLO11-s, nc = 3, 960 px
+YOLO11S_MD = make_yolo11_yaml('s', nc=3)
+
+#: small YOLO11 for fast tests (scale n: the same module mix, C3k2 without C3k blocks, 2 attention heads)
+YOLO11N_TEST = make_yolo11_yaml('n', nc=3)
+
+#: the upstream COCO models, only to cross-check the work / parameter counts against the published figures
+YOLO11N_COCO = make_yolo11_yaml('n', nc=80)
+YOLO11S_COCO = make_yolo11_yaml('s', nc=80)
+YOLO11L_COCO = make_yolo11_yaml('l', nc=80)
+
+
+def is_yolo11(yaml):
+    """True for an ultralytics (anchor-free) yaml dict, False for a YOLOv5 one."""
+    return 'anchors' not in yaml and ('scales' in yaml or 'scale' in yaml)

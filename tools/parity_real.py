@@ -8,6 +8,12 @@ first person with the files gets the reference's own verdict:
     MDV5A=/path/to/md_v5a.0.0.pt python tools/parity_real.py /path/to/md-test-images \
         [--expected /path/to/mdv5a-image-gpu-pt2.x.json] [--dtypes fp16 bf16] [--batch_size 8]
 
+Any other model the same way, by path or by name: MDV1000_LARCH=/path/to/md_v1000.0.0-larch.pt (or
+--model MDV1000-larch with that variable set, or --model /path/to/md_v1000.0.0-sorrel.pt).  For the YOLO11 models
+(larch, sorrel) the expected-results file comes from the reference with the ultralytics package installed
+(pytorch_detector.py:371-458); this is how the restated ultralytics decode / NMS / rescale (tests/yolo11_ref.py, [3P])
+get pinned.
+
 What it does, per storage type (fp16 = the detector default, bf16 = the benchmarked throughput mode):
   1. runs megadetector_amd.run_detector_batch over the folder (recursive, relative filenames, the reference's
      batch-mode defaults: detection threshold 1e-5 in the detector, output threshold 0.005) and writes
@@ -39,6 +45,21 @@ MAX_COORD_ERROR = 0.001       # md_tests.py:96
 CI_CONF_ERROR = 0.01          # md_tests.py:1779
 IOU_MATCH = 0.85              # md_tests.py:124
 KNOWN_MD5 = {'md_v5a.0.0.pt': None, 'md_v5a.0.1.pt': None, 'md_v5b.0.0.pt': None, 'md_v5b.0.1.pt': None}
+# environment variables that may name a checkpoint, in the order they are tried when --model is not given
+MODEL_ENV = ('MDV5A', 'MDV5B', 'MDV1000_REDWOOD', 'MDV1000_SPRUCE', 'MDV1000_LARCH', 'MDV1000_SORREL')
+
+
+def resolve_model(model):
+    """--model as given (a file, or a name such as MDV1000-larch / mdv1000_sorrel naming an environment variable), or
+    the first of MODEL_ENV that is set; returns a path or None"""
+    if model and os.path.isfile(model):
+        return model
+    if model:
+        return os.environ.get(model.upper().replace('-', '_').replace('.', '_'))
+    for var in MODEL_ENV:
+        if os.environ.get(var):
+            return os.environ[var]
+    return None
 
 
 def get_iou(bb1, bb2):
@@ -120,7 +141,9 @@ def verdict(label, res):
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
     ap.add_argument('image_folder')
-    ap.add_argument('--model', default=os.environ.get('MDV5A'), help='checkpoint (default: $MDV5A, as run_detector.py:1083-1087)')
+    ap.add_argument('--model', default=None,
+                    help='checkpoint path, or a model name whose environment variable holds the path (MDV1000-larch -> '
+                         '$MDV1000_LARCH); default: the first of ${} that is set'.format(', $'.join(MODEL_ENV)))
     ap.add_argument('--expected', default=None, help='expected-results .json of the reference (md_tests.py:155-218)')
     ap.add_argument('--dtypes', nargs='+', default=['fp16', 'bf16'], choices=['fp16', 'bf16', 'fp8'])
     ap.add_argument('--batch_size', type=int, default=8)
@@ -128,8 +151,9 @@ def main(argv=None):
     ap.add_argument('--threshold', type=float, default=0.005)
     ap.add_argument('--compatibility_mode', default='classic-test', help='md_tests.py:124 uses classic-test')
     args = ap.parse_args(argv)
+    args.model = resolve_model(args.model)
     if not args.model or not os.path.isfile(args.model):
-        print('no checkpoint: set MDV5A=/path/to/md_v5a.0.0.pt or pass --model', file=sys.stderr)
+        print('no checkpoint: set MDV5A=/path/to/md_v5a.0.0.pt (or MDV1000_LARCH=..., ...) or pass --model', file=sys.stderr)
         return 2
     if not os.path.isdir(args.image_folder):
         print('not a folder: {}'.format(args.image_folder), file=sys.stderr)
