@@ -51,6 +51,13 @@ extern "C" {
 #define MDHIP_C3K2       6
 #define MDHIP_C2PSA      7
 #define MDHIP_DETECT_DFL 8
+/* module kinds of a YOLOv9-C model description (WongKinYiu yolov9 yaml rows, anchor-free; MDv1000-cedar) */
+#define MDHIP_ELAN4       9     /* RepNCSPELAN4                                                                 */
+#define MDHIP_ADOWN      10
+#define MDHIP_CBLINEAR   11
+#define MDHIP_CBFUSE     12
+#define MDHIP_DETECT_DDFL 13    /* DDetect / DualDDetect                                                        */
+#define MDHIP_SILENCE    14     /* identity (an alias of its input; yolov9 Silence)                             */
 
 /* One fused (conv + folded BatchNorm) of the checkpoint: what
  * pytorch_detector.py:957  checkpoint['model'].float().fuse()  leaves in each Conv module. */
@@ -83,7 +90,32 @@ typedef struct {
  *          cv3.l.2 (1x1, nc class logits, bias, no activation)                                     -> 8 n_from convs
  *          Predictions are [cx, cy, w, h, cls0 .. cls(nc-1)] (4 + nc per anchor, no objectness); mdhip_nms* then apply
  *          the ultralytics rule (conf = largest class score, class offset 7680 in the IoU, 30 000 candidates at most).
- *          mdhip_forward_tta and MDHIP_DTYPE_FP8 return MDHIP_EUNSUPPORTED for such models. */
+ *          mdhip_forward_tta and MDHIP_DTYPE_FP8 return MDHIP_EUNSUPPORTED for such models.
+ * YOLOv9-C rows (every Conv carries its folded BatchNorm and SiLU unless noted; SPPELAN is an MDHIP_SPPF row whose cv1
+ * has the hidden width c3, convs cv1, cv5):
+ * Silence: n_from 1, no convs; the layer's output IS its input.  A Conv whose input is the network input, directly or
+ *          through Silence, is a stem (the 3x3 / s2 / p1 form above); a model may have several (yolov9-c.yaml's second
+ *          stem, layer 26, reads layer 0).
+ * ELAN4:   RepNCSPELAN4(c1, c2, c3, c4, n): cv1 (1x1 -> c3), then RepNCSP(c3 / 2 -> c4) cv2.0.cv1, cv2.0.cv2 (1x1 -> h),
+ *          cv2.0.cv3 (1x1 2h -> c4), per j < n cv2.0.m.j.cv1 (3x3: RepConvN folded, the 1x1 branch at the centre tap),
+ *          cv2.0.m.j.cv2 (3x3, + residual); cv2.1 (3x3 c4 -> c4); the same for cv3.0 (RepNCSP c4 -> c4) and cv3.1;
+ *          cv4 (1x1 c3 + 2 c4 -> c2)                                                                  -> 10 + 4n convs
+ *          (h = c4 / 2; lowered on ONE buffer [cv1 | cv2 | cv3] that cv4 reads)
+ * ADown:   cv1 (3x3 / s2 / p1, c1 / 2 -> c2 / 2) over avg_pool2d(2, s1) of the first input half, cv2 (1x1, c1 / 2 ->
+ *          c2 / 2) over max_pool2d(3, 2, 1) of avg_pool2d(2, s1) of the second half; output [cv1 | cv2] at half size
+ *                                                                                                            -> 2 convs
+ * CBLinear: one 1x1 conv (bias, NO activation) to the sum of the splits; c_out = that sum                  -> 1 conv
+ * CBFuse:  from[0 .. n_from-2] CBLinear layers (1 to 3), from[n_from-1] the tensor they are added to; k, s, p = the
+ *          channel offset of the chosen split in from[0], from[1], from[2] (the split has the channels of the last
+ *          input); each split is nearest-resized to the last input's size (integer factors) and the sum is
+ *          ((s0 + s1) + s2) + last in fp32, rounded once                                                 -> 0 convs
+ * DetectDDFL (DDetect, reg_max 16; na = 1, anchors_px unused): n = heads in the conv table (1 DDetect, 2 DualDDetect),
+ *          k = the head that runs (0 = cv2 / cv3 over the first nl inputs; yolov9's NMS keeps DualDDetect's first
+ *          output), from[] = that head's nl inputs; per head h, per level l (head 1: cv4 / cv5):
+ *          cv2.l.0 (3x3 -> c2), cv2.l.1 (3x3, GROUPED g = 4: weight [c2][c2 / 4][3][3]), cv2.l.2 (1x1, 64 box logits,
+ *          bias, no activation), cv3.l.0 (3x3 -> c3), cv3.l.1 (3x3), cv3.l.2 (1x1, nc class logits, bias, no
+ *          activation)                                                                          -> 6 nl n convs
+ *          Predictions and NMS as for DetectDFL. */
 typedef struct {
     int32_t type;
     int32_t n_from;
@@ -232,10 +264,20 @@ int mdhip_attention_on(mdhip_ctx* ctx, const uint16_t* qkv, uint16_t* out, int n
 int mdhip_dfl_decode_on(mdhip_ctx* ctx, const float* box, const float* cls, int nc, int n, int ny, int nx, float stride, float* pred,
                         void* hip_stream);
 
+/* the YOLOv9 kernels in isolation (tests; host buffers, 16-bit storage of the context):
+ * mdhip_adown_pool_on: in [n][h][w][c_in] -> a [n][h][w][c_in / 2] (2x2 / s1 average of the first half, last row and
+ *   column zero), b [n][h / 2][w / 2][c_in / 2] (3x3 / s2 / p1 max of the 2x2 / s1 average of the second half)
+ * mdhip_cbfuse_on: n_src sources src[k] [n][h / factor[k]][w / factor[k]][c] and last [n][h][w][c] -> out [n][h][w][c] */
+int mdhip_adown_pool_on(mdhip_ctx* ctx, const uint16_t* in, uint16_t* a, uint16_t* b, int n, int h, int w, int c_in,
+                        void* hip_stream);
+int mdhip_cbfuse_on(mdhip_ctx* ctx, const uint16_t* const* src, const int32_t* factor, int n_src, const uint16_t* last,
+                    uint16_t* out, int n, int h, int w, int c, void* hip_stream);
+
 typedef struct {
     char    name[48];       /* e.g. "L6.m3.cv2 3x3"                           */
     int32_t kind;           /* 0 conv (implicit GEMM), 1 pool, 2 upsample, 3 decode (YOLOv5 Detect decode, or the DFL
-                             * decode of an anchor-free head), 4 copy, 5 depthwise 3x3 conv, 6 C2PSA attention */
+                             * decode of an anchor-free head), 4 copy, 5 depthwise 3x3 conv, 6 C2PSA attention,
+                             * 7 ADown pools, 8 CBFuse */
     int32_t layer;          /* model layer index                              */
     int32_t m, n, k;        /* GEMM view of a conv (per call, for the last n,h,w) */
     double  flops;          /* algorithmic FLOPs of the op for the last (n,h,w)   */

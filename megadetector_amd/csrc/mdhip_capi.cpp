@@ -22,6 +22,12 @@
 //     pe(v) added to its output, proj (+x), ffn (+x) -> cv2; Detect as the box / class branches of every level (convs,
 //     depthwise convs, fp32 logits) and the DFL decode kernel.  The 3x3/s2 stem is a 3x3/s1 conv over the
 //     space-to-depth input with the weights of the +1 cell zero.
+//   * YOLOv9-C (anchor-free) models: RepNCSPELAN4 on ONE concat buffer (cv1 writes c3 channels, each branch -- RepNCSP, i.e.
+//     the C3k lowering with n bottlenecks, then a 3x3 -- appends its c4 channels, cv4 reads all of it); ADown as one pool
+//     launch (yolov9_kernels.cpp) feeding the existing stride-2 3x3 and a 1x1; SPPELAN as SPPF; CBLinear as a 1x1 without
+//     activation; CBFuse as one kernel; DDetect as the box / class branches of every level (the grouped box conv expanded
+//     block-diagonally) and the DFL decode kernel.  Silence is an alias; every Conv that reads the network input (through
+//     Silence or not) is a stem.  Under a DualDDetect only the layers that reach the head that runs are lowered.
 
 #include <algorithm>
 #include <cmath>
@@ -66,7 +72,8 @@ struct PackedConv {
     std::vector<float> wscale;
 };
 
-enum OpKind { OP_CONV = 0, OP_POOL = 1, OP_UPSAMPLE = 2, OP_DECODE = 3, OP_COPY = 4, OP_DW = 5, OP_ATTN = 6, OP_DFL = 7 };
+enum OpKind { OP_CONV = 0, OP_POOL = 1, OP_UPSAMPLE = 2, OP_DECODE = 3, OP_COPY = 4, OP_DW = 5, OP_ATTN = 6, OP_DFL = 7,
+              OP_ADOWN = 8, OP_CBFUSE = 9 };
 
 struct Op {
     int kind = OP_CONV;
@@ -84,6 +91,10 @@ struct Op {
     int cls_ld = 0;
     int dw_grp = 0, dw_grp_stride = 0, dw_grp_off = 0;   // depthwise: input channel of output channel o (yolo11_kernels.cpp)
     int heads = 0;            // attention
+    Tensor out2;              // ADown pools: the max-pooled half (out = the averaged half)
+    Tensor fsrc[3];           // CBFuse: the CBLinear splits added to `in`, their nearest-resize factors
+    int ffac[3] = {1, 1, 1};
+    int n_fsrc = 0;
     int forced_cfg = -1;
     // fp8 mode: this op writes (f8_out) / reads (f8_in) an e4m3 tensor; f8_peer = the op at the other end of it;
     // act_scale = the tensor's scale (value = e4m3 x act_scale), 0 until calibrated; amax = largest |x| seen
@@ -181,11 +192,12 @@ struct mdhip_ctx {
     std::map<std::tuple<int, int, int, int>, GraphSlot> graphs;
     static constexpr int kMaxGraphs = 32;                 // cached executables (letterbox shapes x batch sizes x 2 buffers)
     long long graph_clock = 0;
-    // recorded on the forward's stream behind the last op that reads the network input (the stem, op 0): a following
+    // recorded on the forward's stream behind the last op that reads the network input (last_input_op): a following
     // mdhip_preprocess -- possibly on ANOTHER stream, next to the rest of this forward -- waits for it before it overwrites
     // the input tensor
     hipEvent_t input_free = nullptr;
     bool input_free_valid = false;
+    int last_input_op = 0;        // the last op that reads the network input (a model may have several stems)
     // the NMS that reads prediction buffer k (possibly on another stream: mdhip_nms_enqueue) records pred_read[k]; the
     // forward that is about to overwrite buffer k waits for it -- the ordering is the library's, not the caller's
     hipEvent_t pred_read[2] = {nullptr, nullptr};
@@ -259,6 +271,7 @@ struct Planner {
     std::vector<int> layer_c, layer_div;
     std::vector<int> concat_target, concat_choff;   // per producer layer
     std::vector<Tensor> concat_buf;                  // per concat layer
+    std::vector<char> reach;                         // per layer: lowered (feeds the Detect head that runs)
     std::string error;
 
     // ld >= c: pixel pitch in elements (a pitch that is a multiple of 64 keeps every 128-byte K-slab row of
@@ -480,6 +493,34 @@ struct Planner {
         ctx->ops.push_back(op);
     }
 
+    // RepNCSP (yolov9; the C3k lowering with n bottlenecks): b = cv1, cv2 (1x1 -> h), cv3 (1x1 2h -> dst.c), then per
+    // bottleneck j m.j.cv1 (3x3, RepConvN folded), m.j.cv2 (3x3, + residual).  YK (2h channels) and TK (h) are scratch.
+    bool repncsp(int i, const char* tag, const mdhip_conv* b, int n, const Tensor& src, const Tensor& dst, const Tensor& YK,
+                 const Tensor& TK) {
+        char nm[96];
+        const int h = b[0].c_out;
+        bool ok = h % 8 == 0 && 2 * h == YK.c && h == TK.c && conv_is(b[0], src.c, h, 1) && conv_is(b[1], src.c, h, 1) &&
+                  conv_is(b[2], 2 * h, dst.c, 1);
+        for (int j = 0; j < n; ++j) ok = ok && conv_is(b[3 + 2 * j], h, h, 3) && conv_is(b[4 + 2 * j], h, h, 3);
+        if (!ok) { error = "RepNCSP shape mismatch at layer " + std::to_string(i) + " (" + tag + ")"; return false; }
+        const Tensor Y1 = slice(YK, 0, h);
+        int pc = pack({&b[0], &b[1]}, false);
+        snprintf(nm, sizeof(nm), "L%d ELAN.%s.cv1|cv2 1x1", i, tag);
+        add_conv(i, nm, src, YK, pc, 1, 0, true, nullptr);
+        for (int j = 0; j < n; ++j) {
+            pc = pack({&b[3 + 2 * j]}, false);
+            snprintf(nm, sizeof(nm), "L%d ELAN.%s.m%d.cv1 3x3", i, tag, j);
+            add_conv(i, nm, Y1, TK, pc, 1, 1, true, nullptr);
+            pc = pack({&b[4 + 2 * j]}, false);
+            snprintf(nm, sizeof(nm), "L%d ELAN.%s.m%d.cv2 3x3", i, tag, j);
+            add_conv(i, nm, TK, Y1, pc, 1, 1, true, &Y1);
+        }
+        pc = pack({&b[2]}, false);
+        snprintf(nm, sizeof(nm), "L%d ELAN.%s.cv3 1x1", i, tag);
+        add_conv(i, nm, YK, dst, pc, 1, 0, true, nullptr);
+        return true;
+    }
+
     bool plan() {
         const int nL = model->n_layers;
         layer_c.assign(nL, 0);
@@ -490,9 +531,24 @@ struct Planner {
         ctx->layer_out.assign(nL, Tensor());
         char nm[96];
 
+        // pass 0: a model ending in a YOLOv9 head lowers only the layers that reach the head that runs (its from[]): under
+        // DualDDetect the branch that feeds the other head is skipped.  Every other model lowers every layer.
+        reach.assign(nL, 1);
+        if (model->layers[nL - 1].type == MDHIP_DETECT_DDFL) {
+            reach.assign(nL, 0);
+            reach[nL - 1] = 1;
+            for (int i = nL - 1; i >= 0; --i) {
+                const mdhip_layer& L = model->layers[i];
+                if (L.n_from < 0 || L.n_from > 4) { error = "n_from outside [0, 4]"; return false; }
+                for (int j = 0; j < L.n_from && reach[i]; ++j)
+                    if (L.from[j] >= 0 && L.from[j] < i) reach[L.from[j]] = 1;
+            }
+        }
+
         // pass 1: channels / divisors / concat targets
         for (int i = 0; i < nL; ++i) {
             const mdhip_layer& L = model->layers[i];
+            if (L.n_from < 0 || L.n_from > 4) { error = "n_from outside [0, 4]"; return false; }
             for (int j = 0; j < L.n_from; ++j)
                 if (L.from[j] >= i || L.from[j] < -1) { error = "layer 'from' index out of order"; return false; }
             const int f0 = L.n_from > 0 ? L.from[0] : -1;
@@ -506,7 +562,27 @@ struct Planner {
                 case MDHIP_SPPF:
                 case MDHIP_C3K2:
                 case MDHIP_C2PSA:
+                case MDHIP_ELAN4:
+                case MDHIP_CBLINEAR:
                     layer_c[i] = L.c_out;
+                    layer_div[i] = in_div;
+                    break;
+                case MDHIP_ADOWN:
+                    if (f0 < 0) { error = "ADown cannot read the network input"; return false; }
+                    layer_c[i] = L.c_out;
+                    layer_div[i] = in_div * 2;
+                    break;
+                case MDHIP_CBFUSE: {
+                    if (L.n_from < 2) { error = "CBFuse needs a CBLinear input and a target"; return false; }
+                    const int last = L.from[L.n_from - 1];
+                    if (last < 0) { error = "CBFuse target cannot be the network input"; return false; }
+                    layer_c[i] = layer_c[last];
+                    layer_div[i] = layer_div[last];
+                    break;
+                }
+                case MDHIP_SILENCE:
+                    if (L.n_from != 1) { error = "Silence has one input"; return false; }
+                    layer_c[i] = f0 < 0 ? 3 : layer_c[f0];
                     layer_div[i] = in_div;
                     break;
                 case MDHIP_UPSAMPLE:
@@ -519,7 +595,8 @@ struct Planner {
                     for (int j = 0; j < L.n_from; ++j) {
                         const int f = L.from[j];
                         if (f < 0 || layer_div[f] != in_div) { error = "concat inputs differ in size"; return false; }
-                        if (concat_target[f] < 0) { concat_target[f] = i; concat_choff[f] = c; }
+                        if (model->layers[f].type == MDHIP_SILENCE) { error = "a Silence output cannot be concatenated"; return false; }
+                        if (concat_target[f] < 0 && reach[i]) { concat_target[f] = i; concat_choff[f] = c; }
                         c += layer_c[f];
                     }
                     layer_c[i] = c;
@@ -528,12 +605,14 @@ struct Planner {
                 }
                 case MDHIP_DETECT:
                 case MDHIP_DETECT_DFL:
+                case MDHIP_DETECT_DDFL:
                     break;
                 default:
                     error = "unknown layer type";
                     return false;
             }
-            if (L.type != MDHIP_DETECT && L.type != MDHIP_DETECT_DFL && L.type != MDHIP_CONCAT && (layer_c[i] % 8)) {
+            if (L.type != MDHIP_DETECT && L.type != MDHIP_DETECT_DFL && L.type != MDHIP_DETECT_DDFL && L.type != MDHIP_CONCAT &&
+                L.type != MDHIP_SILENCE && (layer_c[i] % 8)) {
                 error = "channel counts must be multiples of 8";
                 return false;
             }
@@ -553,11 +632,25 @@ struct Planner {
         };
 
         // pass 2: ops
+        // the network input, directly or through Silence layers
+        auto reads_input = [&](int f) {
+            while (f >= 0 && model->layers[f].type == MDHIP_SILENCE) f = model->layers[f].n_from > 0 ? model->layers[f].from[0] : -1;
+            return f < 0;
+        };
         for (int i = 0; i < nL; ++i) {
             const mdhip_layer& L = model->layers[i];
             const int f0 = L.n_from > 0 ? L.from[0] : -1;
-            if (f0 < 0 && !(L.type == MDHIP_CONV && i == 0)) { error = "only the stem conv (layer 0) may read the network input"; return false; }
-            if (L.type != MDHIP_DETECT && L.type != MDHIP_CONCAT && L.type != MDHIP_UPSAMPLE &&
+            if (!reach[i]) continue;
+            const bool from_input = L.type != MDHIP_CBFUSE && reads_input(f0);
+            if (from_input && L.type != MDHIP_CONV && L.type != MDHIP_SILENCE) {
+                error = "layer " + std::to_string(i) + ": only a stem conv (or Silence) may read the network input";
+                return false;
+            }
+            if (L.type == MDHIP_SILENCE) {
+                if (!from_input) ctx->layer_out[i] = ctx->layer_out[f0];   // (the network input has no layer view)
+                continue;
+            }
+            if (L.type != MDHIP_DETECT && L.type != MDHIP_CONCAT && L.type != MDHIP_UPSAMPLE && L.type != MDHIP_CBFUSE &&
                 (L.first_conv < 0 || L.first_conv >= model->n_convs)) { error = "first_conv out of range"; return false; }
             // convs a layer of this kind consumes (the C3 / SPPF / Detect rows are checked where they are read)
             auto need_convs = [&](int k) {
@@ -568,7 +661,7 @@ struct Planner {
                 case MDHIP_CONV: {
                     const mdhip_conv* c = &model->convs[L.first_conv];
                     Tensor out = out_view(i);
-                    if (f0 < 0) {
+                    if (from_input) {
                         const bool stem6x6 = c->c_in == 3 && c->kh == 6 && c->kw == 6 && L.s == 2 && L.p == 2;
                         const bool stem3x3 = c->c_in == 3 && c->kh == 3 && c->kw == 3 && L.s == 2 && L.p == 1;
                         if (!stem6x6 && !stem3x3) {
@@ -826,6 +919,187 @@ struct Planner {
                         dec.kind = OP_DFL;
                         dec.layer = i;
                         snprintf(nm, sizeof(nm), "L%d Detect.dfl_decode%d", i, l);
+                        dec.name = nm;
+                        dec.in = x;
+                        dec.level = l;
+                        dec.f32_off = box_off;
+                        dec.f32_ld = box_ld;
+                        dec.cls_off = ctx->ops.back().f32_off;
+                        dec.cls_ld = ctx->ops.back().f32_ld;
+                        ctx->ops.push_back(dec);
+                    }
+                    break;
+                }
+                case MDHIP_ELAN4: {
+                    // cv1, RepNCSP cv2.0 (3 + 2n), cv2.1, RepNCSP cv3.0 (3 + 2n), cv3.1, cv4: one buffer [cv1 | cv2 | cv3]
+                    const int rn = L.n;
+                    if (rn < 1 || !need_convs(10 + 4 * rn)) { if (error.empty()) error = "RepNCSPELAN4 needs n >= 1"; return false; }
+                    const mdhip_conv* cv = &model->convs[L.first_conv];
+                    const mdhip_conv* ra = cv + 1;
+                    const mdhip_conv* ca = cv + 4 + 2 * rn;
+                    const mdhip_conv* rb = cv + 5 + 2 * rn;
+                    const mdhip_conv* cb = cv + 8 + 4 * rn;
+                    const mdhip_conv* c4v = cv + 9 + 4 * rn;
+                    const int c3 = cv[0].c_out, c4 = ca->c_out;
+                    if (c3 % 16 || c4 % 16 || !conv_is(cv[0], layer_c[f0], c3, 1) || !conv_is(*ca, c4, c4, 3) || !conv_is(*cb, c4, c4, 3) ||
+                        !conv_is(*c4v, c3 + 2 * c4, L.c_out, 1)) {
+                        error = "RepNCSPELAN4 shape mismatch at layer " + std::to_string(i);
+                        return false;
+                    }
+                    Tensor out = out_view(i);
+                    Tensor Y = alloc(c3 + 2 * c4, layer_div[i]);
+                    Tensor T = alloc(c4, layer_div[i]);
+                    Tensor YK = alloc(c4, layer_div[i]), TK = alloc(c4 / 2, layer_div[i]);
+                    int pc = pack({&cv[0]}, false);
+                    snprintf(nm, sizeof(nm), "L%d ELAN.cv1 1x1", i);
+                    add_conv(i, nm, ctx->layer_out[f0], slice(Y, 0, c3), pc, 1, 0, true, nullptr);
+                    if (!repncsp(i, "cv2.0", ra, rn, slice(Y, c3 / 2, c3 / 2), T, YK, TK)) return false;
+                    pc = pack({ca}, false);
+                    snprintf(nm, sizeof(nm), "L%d ELAN.cv2.1 3x3", i);
+                    add_conv(i, nm, T, slice(Y, c3, c4), pc, 1, 1, true, nullptr);
+                    if (!repncsp(i, "cv3.0", rb, rn, slice(Y, c3, c4), T, YK, TK)) return false;
+                    pc = pack({cb}, false);
+                    snprintf(nm, sizeof(nm), "L%d ELAN.cv3.1 3x3", i);
+                    add_conv(i, nm, T, slice(Y, c3 + c4, c4), pc, 1, 1, true, nullptr);
+                    pc = pack({c4v}, false);
+                    snprintf(nm, sizeof(nm), "L%d ELAN.cv4 1x1", i);
+                    add_conv(i, nm, Y, out, pc, 1, 0, true, nullptr);
+                    ctx->layer_out[i] = out;
+                    break;
+                }
+                case MDHIP_ADOWN: {
+                    // cv1 (3x3 / s2 / p1 over the averaged first half), cv2 (1x1 over the max-pooled second half)
+                    if (!need_convs(2)) return false;
+                    const mdhip_conv* cv = &model->convs[L.first_conv];
+                    const int c1 = layer_c[f0], c = cv[0].c_out;
+                    if (c1 % 16 || !conv_is(cv[0], c1 / 2, c, 3) || !conv_is(cv[1], c1 / 2, c, 1) || L.c_out != 2 * c) {
+                        error = "ADown shape mismatch at layer " + std::to_string(i);
+                        return false;
+                    }
+                    Tensor out = out_view(i);
+                    Tensor A = alloc(c1 / 2, layer_div[f0]);
+                    Tensor B = alloc(c1 / 2, layer_div[i]);
+                    Op pool;
+                    pool.kind = OP_ADOWN;
+                    pool.layer = i;
+                    snprintf(nm, sizeof(nm), "L%d ADown.pool avg2|max3s2", i);
+                    pool.name = nm;
+                    pool.in = ctx->layer_out[f0];
+                    pool.out = A;
+                    pool.out2 = B;
+                    ctx->ops.push_back(pool);
+                    int pc = pack({&cv[0]}, false);
+                    snprintf(nm, sizeof(nm), "L%d ADown.cv1 3x3s2", i);
+                    add_conv(i, nm, A, slice(out, 0, c), pc, 2, 1, true, nullptr);
+                    pc = pack({&cv[1]}, false);
+                    snprintf(nm, sizeof(nm), "L%d ADown.cv2 1x1", i);
+                    add_conv(i, nm, B, slice(out, c, c), pc, 1, 0, true, nullptr);
+                    ctx->layer_out[i] = out;
+                    break;
+                }
+                case MDHIP_CBLINEAR: {
+                    if (!need_convs(1)) return false;
+                    const mdhip_conv* c = &model->convs[L.first_conv];
+                    if (!conv_is(*c, layer_c[f0], L.c_out, 1)) { error = "CBLinear shape mismatch at layer " + std::to_string(i); return false; }
+                    Tensor out = out_view(i);
+                    const int pc = pack({c}, false);
+                    snprintf(nm, sizeof(nm), "L%d CBLinear 1x1", i);
+                    add_conv(i, nm, ctx->layer_out[f0], out, pc, 1, 0, false, nullptr);
+                    ctx->layer_out[i] = out;
+                    break;
+                }
+                case MDHIP_CBFUSE: {
+                    const int nsrc = L.n_from - 1;
+                    const int last = L.from[nsrc];
+                    const int C = layer_c[last];
+                    const int offs[3] = {L.k, L.s, L.p};
+                    if (nsrc < 1 || nsrc > 3) { error = "CBFuse takes 1 to 3 CBLinear inputs"; return false; }
+                    Op op;
+                    op.kind = OP_CBFUSE;
+                    op.layer = i;
+                    snprintf(nm, sizeof(nm), "L%d CBFuse x%d", i, nsrc);
+                    op.name = nm;
+                    op.in = ctx->layer_out[last];
+                    op.n_fsrc = nsrc;
+                    for (int j = 0; j < nsrc; ++j) {
+                        const int f = L.from[j];
+                        const int ratio = f >= 0 ? layer_div[f] / layer_div[last] : 0;
+                        if (f < 0 || model->layers[f].type != MDHIP_CBLINEAR || offs[j] < 0 || offs[j] % 8 || offs[j] + C > layer_c[f] ||
+                            layer_div[f] % layer_div[last] || (ratio != 1 && ratio != 2 && ratio != 4)) {
+                            error = "CBFuse input " + std::to_string(j) + " at layer " + std::to_string(i) +
+                                    " must be a CBLinear split (channel offset a multiple of 8) at 1x, 1/2 or 1/4 the size";
+                            return false;
+                        }
+                        op.fsrc[j] = slice(ctx->layer_out[f], offs[j], C);
+                        op.ffac[j] = ratio;
+                    }
+                    Tensor out = out_view(i);
+                    op.out = out;
+                    ctx->ops.push_back(op);
+                    ctx->layer_out[i] = out;
+                    break;
+                }
+                case MDHIP_DETECT_DDFL: {
+                    // n heads of 6 nl convs each; head k runs: per level cv2.l.0 (3x3), cv2.l.1 (3x3, g = 4), cv2.l.2 (1x1, 64 box
+                    // logits), cv3.l.0 (3x3), cv3.l.1 (3x3), cv3.l.2 (1x1, nc class logits)
+                    const int nh = L.n, hsel = L.k, nl = model->nl;
+                    if (nh < 1 || nh > 2 || hsel < 0 || hsel >= nh) { error = "DDetect: n (heads) must be 1 or 2 and k < n"; return false; }
+                    if (L.n_from != nl) { error = "Detect inputs != nl"; return false; }
+                    if (!need_convs(6 * nl * nh)) return false;
+                    for (int l = 0; l < nl; ++l) {
+                        const mdhip_conv* b = &model->convs[L.first_conv + (hsel * nl + l) * 6];
+                        const int f = L.from[l];
+                        const int cx = layer_c[f], c2 = b[0].c_out, c3 = b[3].c_out;
+                        const bool grouped = b[1].c_in * 4 == c2 && b[1].c_out == c2 && b[1].kh == 3 && b[1].kw == 3 && b[1].weight;
+                        if (!conv_is(b[0], cx, c2, 3) || c2 % 32 || !(grouped || conv_is(b[1], c2, c2, 3)) ||
+                            !(b[2].c_in == c2 && b[2].c_out == 64 && b[2].kh == 1 && b[2].kw == 1) || !conv_is(b[3], cx, c3, 3) ||
+                            !conv_is(b[4], c3, c3, 3) || !(b[5].c_in == c3 && b[5].c_out == ctx->nc && b[5].kh == 1 && b[5].kw == 1)) {
+                            error = "DDetect level " + std::to_string(l) + ": conv shapes do not match (reg_max 16; box branch Conv 3x3 "
+                                    "-> Conv 3x3 (g = 4) -> Conv2d 1x1, class branch Conv 3x3 -> Conv 3x3 -> Conv2d 1x1)";
+                            return false;
+                        }
+                        if (std::fabs(ctx->strides[l] - (float)layer_div[f]) > 1e-6f) { error = "Detect stride does not match the graph"; return false; }
+                        // the grouped conv as a dense one: output channel o reads the c2 / 4 inputs of its group, every other
+                        // weight is an exact zero
+                        std::vector<float> dense;
+                        mdhip_conv b1 = b[1];
+                        if (grouped) {
+                            const int gi = c2 / 4;
+                            dense.assign((size_t)c2 * c2 * 9, 0.f);
+                            for (int o = 0; o < c2; ++o)
+                                for (int ci = 0; ci < gi; ++ci)
+                                    for (int t = 0; t < 9; ++t)
+                                        dense[((size_t)o * c2 + (o / gi) * gi + ci) * 9 + t] = b[1].weight[((size_t)o * gi + ci) * 9 + t];
+                            b1.weight = dense.data();
+                            b1.c_in = c2;
+                        }
+                        const Tensor& x = ctx->layer_out[f];
+                        const int dv = layer_div[f];
+                        Tensor B1 = alloc(c2, dv), B2 = alloc(c2, dv), C1 = alloc(c3, dv), C2 = alloc(c3, dv);
+                        int pc = pack({&b[0]}, false);
+                        snprintf(nm, sizeof(nm), "L%d DDetect.cv2.%d.0 3x3", i, l);
+                        add_conv(i, nm, x, B1, pc, 1, 1, true, nullptr);
+                        pc = pack({&b1}, false);
+                        snprintf(nm, sizeof(nm), "L%d DDetect.cv2.%d.1 3x3 g4", i, l);
+                        add_conv(i, nm, B1, B2, pc, 1, 1, true, nullptr);
+                        pc = pack({&b[2]}, false);
+                        snprintf(nm, sizeof(nm), "L%d DDetect.cv2.%d.2 1x1 (box)", i, l);
+                        add_conv_f32(i, nm, B2, pc, dv);
+                        const size_t box_off = ctx->ops.back().f32_off;
+                        const int box_ld = ctx->ops.back().f32_ld;
+                        pc = pack({&b[3]}, false);
+                        snprintf(nm, sizeof(nm), "L%d DDetect.cv3.%d.0 3x3", i, l);
+                        add_conv(i, nm, x, C1, pc, 1, 1, true, nullptr);
+                        pc = pack({&b[4]}, false);
+                        snprintf(nm, sizeof(nm), "L%d DDetect.cv3.%d.1 3x3", i, l);
+                        add_conv(i, nm, C1, C2, pc, 1, 1, true, nullptr);
+                        pc = pack({&b[5]}, false, 8);         // nc class rows padded to 8 (zero weights, zero bias)
+                        snprintf(nm, sizeof(nm), "L%d DDetect.cv3.%d.2 1x1 (cls)", i, l);
+                        add_conv_f32(i, nm, C2, pc, dv);
+                        Op dec;
+                        dec.kind = OP_DFL;
+                        dec.layer = i;
+                        snprintf(nm, sizeof(nm), "L%d DDetect.dfl_decode%d", i, l);
                         dec.name = nm;
                         dec.in = x;
                         dec.level = l;
@@ -1421,6 +1695,44 @@ int run_op(mdhip_ctx* ctx, Op& op, int n, int h, int w, hipStream_t s) {
                                            ctx->strides[op.level], s));
             break;
         }
+        case OP_ADOWN: {
+            const int H = h / op.in.div, W = w / op.in.div;
+            const double half = op.out.c;
+            // input read once, the averaged half written at H x W, the max-pooled half at H/2 x W/2
+            op.gm = n * H * W;
+            op.flops = 0;
+            op.bytes = (double)n * H * W * half * 2.0 * 2.0 + (double)n * H * W * half * 2.0 + (double)n * (H / 2) * (W / 2) * half * 2.0;
+            op.last_cfg = -1;
+            HIP_TRY(ctx, launch_adown_pool((const uint16_t*)(ctx->arena + op.in.off), op.in.ld, (uint16_t*)(ctx->arena + op.out.off),
+                                           op.out.ld, (uint16_t*)(ctx->arena + op.out2.off), op.out2.ld, n, H, W, op.in.c,
+                                           ctx->dtype == MDHIP_DTYPE_FP16, s));
+            break;
+        }
+        case OP_CBFUSE: {
+            CbfuseArgs a{};
+            a.n = n;
+            a.H = h / op.in.div;
+            a.W = w / op.in.div;
+            a.C = op.in.c;
+            a.n_src = op.n_fsrc;
+            double bytes = 2.0 * n * a.H * a.W * a.C * 2.0;
+            for (int k = 0; k < op.n_fsrc; ++k) {
+                a.src[k] = (const uint16_t*)(ctx->arena + op.fsrc[k].off);
+                a.ld_src[k] = op.fsrc[k].ld;
+                a.factor[k] = op.ffac[k];
+                bytes += (double)n * (a.H / op.ffac[k]) * (a.W / op.ffac[k]) * a.C * 2.0;
+            }
+            a.last = (const uint16_t*)(ctx->arena + op.in.off);
+            a.ld_last = op.in.ld;
+            a.out = (uint16_t*)(ctx->arena + op.out.off);
+            a.ld_out = op.out.ld;
+            op.gm = n * a.H * a.W;
+            op.flops = 0;
+            op.bytes = bytes;
+            op.last_cfg = -1;
+            HIP_TRY(ctx, launch_cbfuse(a, ctx->dtype == MDHIP_DTYPE_FP16, s));
+            break;
+        }
         case OP_DECODE: {
             if (op.dec_done) {                     // decoded in the epilogue of the conv in front (this forward)
                 op.bytes = 0;
@@ -1484,8 +1796,9 @@ int mdhip_create(const mdhip_model* model, int device, int dtype, int max_batch,
     ctx->no = model->nc + 5;
     bool has_detect = false;
     for (int i = 0; i < model->n_layers; ++i) {
-        has_detect |= model->layers[i].type == MDHIP_DETECT || model->layers[i].type == MDHIP_DETECT_DFL;
-        ctx->anchor_free |= model->layers[i].type == MDHIP_DETECT_DFL;
+        const int t = model->layers[i].type;
+        has_detect |= t == MDHIP_DETECT || t == MDHIP_DETECT_DFL || t == MDHIP_DETECT_DDFL;
+        ctx->anchor_free |= t == MDHIP_DETECT_DFL || t == MDHIP_DETECT_DDFL;
     }
     if (ctx->anchor_free) {
         // [cx, cy, w, h, cls0 .. cls(nc-1)]: no objectness, one prediction per cell
@@ -1494,7 +1807,7 @@ int mdhip_create(const mdhip_model* model, int device, int dtype, int max_batch,
         if (dtype == MDHIP_DTYPE_FP8) {
             delete ctx;
             return fail(nullptr, MDHIP_EUNSUPPORTED, "MDHIP_DTYPE_FP8 is implemented for the YOLOv5 bottlenecks only, not for "
-                                                     "anchor-free (YOLO11) models: use bf16 or fp16");
+                                                     "anchor-free (YOLO11, YOLOv9) models: use bf16 or fp16");
         }
     }
     ctx->max_stride = 2;
@@ -1510,9 +1823,11 @@ int mdhip_create(const mdhip_model* model, int device, int dtype, int max_batch,
         std::vector<int> div(model->n_layers, 1);
         for (int i = 0; i < model->n_layers; ++i) {
             const mdhip_layer& L = model->layers[i];
-            const int f0 = L.n_from > 0 ? L.from[0] : -1;
+            const int nf = std::min(std::max(L.n_from, 0), 4);
+            const int f0 = nf > 0 ? L.from[L.type == MDHIP_CBFUSE ? nf - 1 : 0] : -1;
             const int d = (f0 < 0 || f0 >= i) ? 1 : div[f0];
-            div[i] = L.type == MDHIP_CONV ? d * std::max(1, L.s) : (L.type == MDHIP_UPSAMPLE ? std::max(1, d / 2) : d);
+            div[i] = L.type == MDHIP_CONV ? d * std::max(1, L.s) : (L.type == MDHIP_UPSAMPLE ? std::max(1, d / 2) :
+                                                                     L.type == MDHIP_ADOWN ? d * 2 : d);
             ctx->max_stride = std::max(ctx->max_stride, div[i]);
         }
     }
@@ -1594,14 +1909,17 @@ int mdhip_create(const mdhip_model* model, int device, int dtype, int max_batch,
         }                                                                                       \
     } while (0)
 
-    // mdhip_forward records `input_free` right behind op 0: nothing after it may read the network input
-    for (size_t oi = 1; oi < ctx->ops.size(); ++oi)
-        if ((ctx->ops[oi].in.valid && ctx->ops[oi].in.off == ctx->input.off) ||
-            (ctx->ops[oi].has_res && ctx->ops[oi].res.off == ctx->input.off)) {
-            const std::string m = "op " + std::to_string(oi) + " (" + ctx->ops[oi].name + ") reads the network input: only layer 0 may";
+    // mdhip_forward records `input_free` right behind the last op that reads the network input (only stem convs do)
+    for (size_t oi = 0; oi < ctx->ops.size(); ++oi) {
+        const Op& o = ctx->ops[oi];
+        const bool reads = (o.in.valid && o.in.off == ctx->input.off) || (o.has_res && o.res.off == ctx->input.off);
+        if (reads && o.kind != OP_CONV) {
+            const std::string m = "op " + std::to_string(oi) + " (" + o.name + ") reads the network input: only a stem conv may";
             mdhip_destroy(ctx);
             return fail(nullptr, MDHIP_EINVAL, "%s", m.c_str());
         }
+        if (reads) ctx->last_input_op = (int)oi;
+    }
     CREATE_TRY(hipMalloc((void**)&ctx->arena, ctx->arena_bytes));
     CREATE_TRY(hipMalloc((void**)&ctx->warena, ctx->warena_bytes));
     CREATE_TRY(hipMemset(ctx->warena, 0, 256));
@@ -1796,7 +2114,7 @@ int mdhip_forward(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
     if (!launched) {
         for (size_t oi = 0; oi < ctx->ops.size(); ++oi) {
             if (int rc = run_op(ctx, ctx->ops[oi], n, h, w, s)) return rc;
-            if (oi == 0) {                                   // (the planner lets only layer 0 read the network input)
+            if ((int)oi == ctx->last_input_op) {             // (nothing behind it reads the network input)
                 HIP_TRY(ctx, hipEventRecord(ctx->input_free, s));
                 ctx->input_free_valid = true;
             }
@@ -2254,6 +2572,65 @@ int mdhip_dfl_decode_on(mdhip_ctx* ctx, const float* box, const float* cls, int 
     return MDHIP_OK;
 }
 
+int mdhip_adown_pool_on(mdhip_ctx* ctx, const uint16_t* in, uint16_t* a, uint16_t* b, int n, int h, int w, int c_in,
+                        void* hip_stream) {
+    if (!ctx || !in || !a || !b || n < 1 || h < 2 || w < 2 || h % 2 || w % 2 || c_in < 16 || c_in % 16) return MDHIP_EINVAL;
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)n * h * w, half = (size_t)c_in / 2;
+    DevBufs d;
+    void *din, *da, *db;
+    HIP_TRY(ctx, d.get(px * c_in * 2, &din));
+    HIP_TRY(ctx, d.get(px * half * 2, &da));
+    HIP_TRY(ctx, d.get(px / 4 * half * 2, &db));
+    HIP_TRY(ctx, hipMemcpy(din, in, px * c_in * 2, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, launch_adown_pool((const uint16_t*)din, c_in, (uint16_t*)da, (int)half, (uint16_t*)db, (int)half, n, h, w, c_in,
+                                   ctx->dtype == MDHIP_DTYPE_FP16, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipMemcpy(a, da, px * half * 2, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(b, db, px / 4 * half * 2, hipMemcpyDeviceToHost));
+    return MDHIP_OK;
+}
+
+int mdhip_cbfuse_on(mdhip_ctx* ctx, const uint16_t* const* src, const int32_t* factor, int n_src, const uint16_t* last,
+                    uint16_t* out, int n, int h, int w, int c, void* hip_stream) {
+    if (!ctx || !src || !factor || !last || !out || n_src < 1 || n_src > 3 || n < 1 || h < 1 || w < 1 || c < 8 || c % 8)
+        return MDHIP_EINVAL;
+    for (int k = 0; k < n_src; ++k)
+        if (!src[k] || factor[k] < 1 || h % factor[k] || w % factor[k]) return fail(ctx, MDHIP_EINVAL, "bad CBFuse source %d", k);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)n * h * w;
+    DevBufs d;
+    CbfuseArgs a{};
+    void *dl, *dout;
+    for (int k = 0; k < n_src; ++k) {
+        const size_t bytes = (size_t)n * (h / factor[k]) * (w / factor[k]) * c * 2;
+        void* p;
+        HIP_TRY(ctx, d.get(bytes, &p));
+        HIP_TRY(ctx, hipMemcpy(p, src[k], bytes, hipMemcpyHostToDevice));
+        a.src[k] = (const uint16_t*)p;
+        a.ld_src[k] = c;
+        a.factor[k] = factor[k];
+    }
+    HIP_TRY(ctx, d.get(px * c * 2, &dl));
+    HIP_TRY(ctx, d.get(px * c * 2, &dout));
+    HIP_TRY(ctx, hipMemcpy(dl, last, px * c * 2, hipMemcpyHostToDevice));
+    a.n_src = n_src;
+    a.last = (const uint16_t*)dl;
+    a.ld_last = c;
+    a.out = (uint16_t*)dout;
+    a.ld_out = c;
+    a.n = n;
+    a.H = h;
+    a.W = w;
+    a.C = c;
+    HIP_TRY(ctx, launch_cbfuse(a, ctx->dtype == MDHIP_DTYPE_FP16, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipMemcpy(out, dout, px * c * 2, hipMemcpyDeviceToHost));
+    return MDHIP_OK;
+}
+
 int mdhip_num_ops(mdhip_ctx* ctx) { return ctx ? (int)ctx->ops.size() : MDHIP_EINVAL; }
 
 int mdhip_get_op_info(mdhip_ctx* ctx, int op, mdhip_op_info* out) {
@@ -2262,6 +2639,7 @@ int mdhip_get_op_info(mdhip_ctx* ctx, int op, mdhip_op_info* out) {
     memset(out, 0, sizeof(*out));
     snprintf(out->name, sizeof(out->name), "%s", o.name.c_str());
     out->kind = o.kind == OP_DFL ? OP_DECODE : o.kind;       // (the DFL decode is reported as the decode op of its level)
+    if (o.kind == OP_ADOWN || o.kind == OP_CBFUSE) out->kind = o.kind - 1;                  // 7 ADown pools, 8 CBFuse
     out->layer = o.layer;
     out->m = o.gm;
     out->n = o.gn;

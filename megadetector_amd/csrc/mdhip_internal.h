@@ -419,4 +419,27 @@ hipError_t launch_attention(const uint16_t* qkv, int ld_qkv, uint16_t* out, int 
 hipError_t launch_dfl_decode(const float* box, int ld_box, const float* cls, int ld_cls, float* pred, int n, int ny, int nx,
                              int nc, int n_anchors, int level_off, float stride, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------
+// YOLOv9-C blocks (yolov9_kernels.cpp)
+// ---------------------------------------------------------------------------------------
+// ADown pools of in [n][H][W][c_in] (H, W even): A [n][H][W][c_in / 2] = avg_pool2d(2, s1) of the first half, zero in the
+// last row and column; B [n][H/2][W/2][c_in / 2] = max_pool2d(3, 2, 1) of avg_pool2d(2, s1) of the second half (windows
+// clipped to the (H-1) x (W-1) extent).  Averages: ((a + b) + c) + d in fp32, times 1/4, rounded once to storage.
+hipError_t launch_adown_pool(const uint16_t* in, int ld_in, uint16_t* A, int ld_a, uint16_t* B, int ld_b, int n, int H, int W,
+                             int c_in, int f16, hipStream_t s);
+// CBFuse: out [n][H][W][C] = round(((up(src0) + up(src1)) + up(src2)) + last), sums in fp32, up = nearest resize of
+// source k ([n][H / factor_k][W / factor_k], pitch ld_src_k) by its integer factor
+struct CbfuseArgs {
+    const uint16_t* src[3];
+    int ld_src[3];
+    int factor[3];
+    int n_src;
+    const uint16_t* last;
+    int ld_last;
+    uint16_t* out;
+    int ld_out;
+    int n, H, W, C;
+};
+hipError_t launch_cbfuse(const CbfuseArgs& a, int f16, hipStream_t s);
+
 }  // namespace mdhip

@@ -134,8 +134,12 @@ class HIPDetector:
         # YOLO11 (MDv1000-larch / -sorrel): the reference runs them through the ultralytics package -- its NMS and its
         # scale_boxes (pytorch_detector.py:395-402, :1327-1344); the library picks the NMS from the model's head
         self.anchor_free = bool(getattr(weights, 'anchor_free', False))
+        # YOLOv9-C (MDv1000-cedar): the reference runs it through the yolov9 package -- its NMS (the same rule; the library's
+        # anchor-free NMS) and its YOLOv5-style scale_boxes, which does NOT round the padding
+        self.yolov9 = bool(getattr(weights, 'yolov9', False))
         if self.anchor_free and str(opts.get('dtype') or DEFAULT_DTYPE).lower() == 'fp8':
-            raise ValueError("dtype 'fp8' is implemented for YOLOv5 models only; use 'fp16' or 'bf16' for a YOLO11 model")
+            raise ValueError("dtype 'fp8' is implemented for YOLOv5 models only; use 'fp16' or 'bf16' for a {} model".format(
+                'YOLOv9' if self.yolov9 else 'YOLO11'))
         if weights.max_stride != self.letterbox_stride and verbose:
             print('*** Warning: model stride is {}, letterbox stride is {} ***'.format(
                 weights.max_stride, self.letterbox_stride))
@@ -288,7 +292,8 @@ class HIPDetector:
 
     def _check_augment(self, augment):
         if augment and getattr(self, 'anchor_free', False):
-            raise ValueError('augment=True (test-time augmentation) is implemented for YOLOv5 models only, not for YOLO11')
+            raise ValueError('augment=True (test-time augmentation) is implemented for YOLOv5 models only, not for {}'.format(
+                'YOLOv9' if getattr(self, 'yolov9', False) else 'YOLO11'))
 
     def _nms_iou(self):
         return 0.45 if 'classic' in self.compatibility_mode else 0.6        # reference :1318-1321
@@ -315,7 +320,8 @@ class HIPDetector:
                 det, (h, w), info.get('resized_shape', info['img_original'].shape) if modern else info['img_original'].shape,
                 info['scaling_shape'], detection_threshold,
                 use_model_native_classes=self.use_model_native_classes, modern=modern,
-                letterbox_pad=info.get('letterbox_pad'), round_pad=getattr(self, 'anchor_free', False))
+                letterbox_pad=info.get('letterbox_pad'),
+                round_pad=getattr(self, 'anchor_free', False) and not getattr(self, 'yolov9', False))
             results[original_idx] = {'file': current_id, 'detections': detections,
                                      'max_detection_conf': max_conf}
 

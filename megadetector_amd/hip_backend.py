@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import HipError
-from .yolo_model import DETECT_TYPES
+from .yolo_model import DETECT_TYPES, MDHIP_CBFUSE, MDHIP_DETECT_DDFL, detect_inputs
 
 
 class HipContext:
@@ -29,11 +29,14 @@ class HipContext:
         for i, s in enumerate(specs):
             L = layers[i]
             L.type = s.type
-            L.n_from = len(s.frm)
-            for j, f in enumerate(s.frm):
+            frm = detect_inputs(s)                  # (DualDDetect: the inputs of the head that runs)
+            L.n_from = len(frm)
+            for j, f in enumerate(frm):
                 L.from_[j] = f
             L.c_out = s.c_out if s.c_out is not None else 0
             L.k, L.s, L.p = s.k or 0, s.s or 1, s.p or 0
+            if s.type == MDHIP_CBFUSE:              # channel offsets of the chosen splits (0 is an offset, not a default)
+                L.k, L.s, L.p = s.k, s.s, s.p
             L.n = s.n or 1
             L.shortcut = s.shortcut or 0
             L.first_conv = len(convs)

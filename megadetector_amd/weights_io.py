@@ -17,7 +17,7 @@ import zipfile
 import numpy as np
 
 from . import yolo_yaml
-from .yolo_model import YoloWeights, resolve_yaml, MDHIP_DETECT, MDHIP_DETECT_DFL
+from .yolo_model import YoloWeights, resolve_yaml, MDHIP_DETECT, MDHIP_DETECT_DFL, MDHIP_DETECT_DDFL
 
 
 # --------------------------------------------------------------------------------------
@@ -42,6 +42,8 @@ def synthetic_weights(yaml=None, seed=0, gain=1.75, res_gain=0.6, bias_std=0.1,
     yaml = yaml or yolo_yaml.YOLOV5X6_MD
     if yolo_yaml.is_yolo11(yaml):
         return synthetic_weights_yolo11(yaml, seed=seed)
+    if yolo_yaml.is_yolov9(yaml):
+        return synthetic_weights_yolov9(yaml, seed=seed)
     specs = resolve_yaml(yaml)
     rng = np.random.Generator(np.random.PCG64(seed))
     w = {}
@@ -151,6 +153,79 @@ def synthetic_weights_yolo11(yaml, seed=0, gain=1.6, res_gain=0.5, bias_std=0.1,
     return YoloWeights(yaml, w, source='synthetic(seed={})'.format(seed))
 
 
+def yolov9_conv_shapes(s, specs):
+    """(name, (c_out, c_in, k)) of every conv of a YOLOv9 layer, in the order of include/mdhip.h (the grouped box conv of
+    the Detect head: c_in = c2 / 4, its checkpoint shape)"""
+    from .yolo_model import MDHIP_ELAN4, MDHIP_ADOWN, MDHIP_CBLINEAR
+    names = s.conv_names
+    if s.type == MDHIP_ELAN4:
+        c3, c4 = s.hidden
+
+        def rep(c1, c2):
+            h = c2 // 2
+            return [(h, c1, 1), (h, c1, 1), (c2, 2 * h, 1)] + [(h, h, 3), (h, h, 3)] * s.n
+        shapes = [(c3, s.c_in, 1)] + rep(c3 // 2, c4) + [(c4, c4, 3)] + rep(c4, c4) + [(c4, c4, 3), (s.c_out, c3 + 2 * c4, 1)]
+    elif s.type == MDHIP_ADOWN:
+        c = s.c_out // 2
+        shapes = [(c, s.c_in // 2, 3), (c, s.c_in // 2, 1)]
+    elif s.type == MDHIP_CBLINEAR:
+        shapes = [(s.c_out, s.c_in, 1)]
+    elif s.type == MDHIP_DETECT_DDFL:
+        nc = s.c_out - 4
+        nl = len(s.frm) // s.n
+        shapes = []
+        for h in range(s.n):
+            c2, c3 = s.hidden[h]
+            for f in s.frm[h * nl:(h + 1) * nl]:
+                cx = specs[f].c_out
+                shapes += [(c2, cx, 3), (c2, c2 // 4, 3), (64, c2, 1), (c3, cx, 3), (c3, c3, 3), (nc, c3, 1)]
+    else:
+        shapes = _conv_shapes(s)
+    assert len(shapes) == len(names), (s.index, len(shapes), len(names))
+    return list(zip(names, shapes))
+
+
+def synthetic_weights_yolov9(yaml, seed=0, gain=1.5, res_gain=0.5, bias_std=0.1, cls_bias=-13.5, cls_gain=12.0,
+                             box_gain=1.5):
+    """
+    Seeded weights on a YOLOv9 topology, built like the YOLO11 set: zero-mean N(0, gain^2 / fan_in) kernels, the second
+    conv of every RepNBottleneck (the end of a residual branch) at res_gain, CBLinear (no activation) at gain 1.  The
+    head's features have a standard deviation of ~0.1 whatever their width, so the final convs take gains of 12 (class)
+    and 1.5 (box) over 1 / sqrt(fan_in): class logits of std ~1.5 around a bias of -13.5 (a minority of anchors clears the
+    1e-5 batch-mode threshold), box logits of a few units.
+    """
+    from .yolo_model import MDHIP_CBLINEAR
+    specs = resolve_yaml(yaml)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    w = {}
+    for s in specs:
+        for name, (c2, c1, k) in yolov9_conv_shapes(s, specs):
+            wt = rng.standard_normal((c2, c1, k, k), dtype=np.float32)
+            fan = c1 * k * k
+            wt -= wt.mean(axis=(1, 2, 3), keepdims=True)
+            g = gain
+            if '.m.' in name and name.endswith('.cv2.conv'):
+                g = res_gain
+            elif s.type == MDHIP_CBLINEAR:
+                g = 1.0
+            b = rng.standard_normal(c2, dtype=np.float32) * np.float32(bias_std)
+            if s.type == MDHIP_DETECT_DDFL and name.split('.')[-1] == '2':
+                if name.split('.')[2] in ('cv2', 'cv4'):       # box logits
+                    g = box_gain
+                    b = rng.standard_normal(c2, dtype=np.float32) * np.float32(0.5)
+                else:                                          # class logits
+                    g = cls_gain
+                    b = np.float32(cls_bias) + rng.standard_normal(c2, dtype=np.float32) * np.float32(0.5)
+            wt *= np.float32(g / np.sqrt(fan))
+            w[name + '.weight'] = wt.astype(np.float32)
+            w[name + '.bias'] = b.astype(np.float32)
+    det = specs[-1]
+    for h in range(det.n):
+        w['model.{}.dfl{}.conv.weight'.format(det.index, '' if h == 0 else h + 1)] = \
+            np.arange(16, dtype=np.float32).reshape(1, 16, 1, 1)
+    return YoloWeights(yaml, w, source='synthetic(seed={})'.format(seed))
+
+
 def _channels_of(specs, idx):
     return specs[idx].c_out
 
@@ -256,7 +331,7 @@ class _CheckpointUnpickler(pickle.Unpickler):
             if isinstance(cls, type) and issubclass(cls, torch.nn.Module):
                 return cls
             raise pickle.UnpicklingError('refusing to unpickle {}.{}'.format(module, name))
-        if module.split('.')[0] in ('models', 'utils', 'yolov5', 'ultralytics', '__main__'):
+        if module.split('.')[0] in ('models', 'utils', 'yolov5', 'yolov9', 'ultralytics', '__main__'):
             return _stub_class(module, name)
         raise pickle.UnpicklingError('refusing to unpickle {}.{}'.format(module, name))
 
@@ -330,6 +405,8 @@ def load_checkpoint(path):
     yaml = dict(model.__dict__['yaml'])
     if yolo_yaml.is_yolo11(yaml) or type(model).__module__.split('.')[0] == 'ultralytics':
         return _load_ultralytics(model, yaml, path)
+    if yolo_yaml.is_yolov9(yaml):
+        return _load_yolov9(model, yaml, path)
     if 'anchors' in yaml and not isinstance(yaml['anchors'], (list, tuple)):
         raise ValueError('checkpoint yaml has no explicit anchor list')
     seq = _modules(model)['model']
@@ -405,6 +482,77 @@ def _load_ultralytics(model, yaml, path):
             w[name + '.weight'] = wf
             w[name + '.bias'] = bf
     w['model.{}.dfl.conv.weight'.format(det.index)] = dfl_w.reshape(1, 16, 1, 1)
+    names = model.__dict__.get('names')
+    if isinstance(names, (list, tuple)):
+        names = {i: n for i, n in enumerate(names)}
+    return YoloWeights(yaml, w, names=names, source=path)
+
+
+def _fold_repconvn(mod):
+    """
+    yolov9 RepConvN (conv1: Conv 3x3 + BN, conv2: Conv 1x1 + BN, no identity branch, then SiLU) -> one 3x3 (w, b) fp32,
+    as its fuse_convs() does: both branches BN-folded, the 1x1 kernel added at the centre tap, the biases summed.
+    A module that is already fused (a plain `conv`) is read as it is.
+    """
+    mods = _modules(mod)
+    if 'conv1' not in mods:
+        return _fold(mod)
+    if mods.get('bn') is not None:
+        raise ValueError('RepConvN with an identity BatchNorm branch is not supported')
+    w3, b3 = _fold(mods['conv1'])
+    w1, b1 = _fold(mods['conv2'])
+    if w3.shape[2:] != (3, 3) or w1.shape[2:] != (1, 1):
+        raise ValueError('RepConvN: 3x3 and 1x1 branches expected, got {} / {}'.format(w3.shape, w1.shape))
+    w = w3.copy()
+    w[:, :, 1, 1] += w1[:, :, 0, 0]
+    return w.astype(np.float32), (b3 + b1).astype(np.float32)
+
+
+def _load_yolov9(model, yaml, path):
+    """
+    A yolov9-package checkpoint (MDv1000-cedar: {'model': models.yolo.DetectionModel} -- or the same under `yolov9.` --
+    with model.yaml in the YOLOv5 format).  What the reference runs is model.float().fuse() (pytorch_detector.py:957):
+    every Conv with its BatchNorm folded, every RepConvN folded into one 3x3 conv, the Detect head's grouped box conv as
+    it is ([c2][c2 / 4][3][3]), its final Conv2d layers and CBLinear as plain convs with bias (no BatchNorm, no
+    activation).  Both head forms load: DDetect (converted, GELAN-C) and DualDDetect (training form).
+    """
+    root = type(model).__module__.split('.')[0]
+    if root not in ('models', 'yolov9'):
+        raise ValueError('{}: yolov9 model description in a checkpoint of package "{}" (models.* or yolov9.* expected)'.format(
+            path, type(model).__module__))
+    specs = resolve_yaml(yaml)           # refuses unknown modules by name
+    layers = _modules(_modules(model)['model'])
+    det = specs[-1]
+    dmod = layers[str(det.index)]
+    dm = _modules(dmod)
+    reg_max = int(getattr(dmod, 'reg_max', 16))
+    dfl = {}
+    for h in range(det.n):
+        key = 'dfl' if h == 0 else 'dfl{}'.format(h + 1)
+        if key not in dm:
+            raise ValueError('{}: Detect head without {}'.format(path, key))
+        dfl_w = _np32(_param(_modules(dm[key])['conv'], 'weight')).reshape(-1)
+        if reg_max != 16 or dfl_w.shape != (16,) or not np.array_equal(dfl_w, np.arange(16, dtype=np.float32)):
+            raise ValueError('{}: DFL conv weight must be arange(16) (reg_max 16)'.format(path))
+        dfl['model.{}.{}.conv.weight'.format(det.index, key)] = dfl_w.reshape(1, 16, 1, 1)
+    w = {}
+    for s in specs:
+        if not s.conv_names:
+            continue
+        mod = layers[str(s.index)]
+        for name in s.conv_names:
+            sub = mod
+            parts = name.split('.')[2:]
+            for part in (parts[:-1] if parts[-1] == 'conv' else parts):
+                sub = _modules(sub)[part]
+            if parts[-1] == 'conv':
+                wf, bf = _fold_repconvn(sub)
+            else:                                         # a plain Conv2d of the Detect head (bias, no BatchNorm)
+                wf = _np32(_param(sub, 'weight'))
+                bf = _np32(_param(sub, 'bias'))
+            w[name + '.weight'] = wf
+            w[name + '.bias'] = bf
+    w.update(dfl)
     names = model.__dict__.get('names')
     if isinstance(names, (list, tuple)):
         names = {i: n for i, n in enumerate(names)}

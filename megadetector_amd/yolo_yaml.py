@@ -208,3 +208,118 @@ YOLO11L_COCO = make_yolo11_yaml('l', nc=80)
 def is_yolo11(yaml):
     """True for an ultralytics (anchor-free) yaml dict, False for a YOLOv5 one."""
     return 'anchors' not in yaml and ('scales' in yaml or 'scale' in yaml)
+
+
+# --------------------------------------------------------------------------------------
+# YOLOv9-C descriptions: MDv1000-cedar (YOLOv9c, 640 px; reference docs/release-notes/mdv1000-release.md:280, :319).
+# The reference runs it through the third-party yolov9pip package (WongKinYiu's YOLOv9 code, pytorch_detector.py:348-368),
+# whose yaml format is the YOLOv5 one ('depth_multiple', 'width_multiple', 'anchors' an int).  Restated [3P] from the
+# published yolov9-c.yaml; a leading Silence keeps the layer numbers of that file in both forms:
+#   converted (GELAN-C): layers 0-22 and DDetect over (16, 19, 22) -- 25.3 M parameters, 102.1 GFLOPs at nc = 80;
+#   training (yolov9-c.yaml): adds the reversible auxiliary branch (CBLinear 23-25, a second stem 26 reading layer 0,
+#   CBFuse 30 / 33 / 36) and DualDDetect over (31, 34, 37, 16, 19, 22).
+# --------------------------------------------------------------------------------------
+
+_BACKBONE_YOLOV9C = [
+    [-1, 1, 'Silence', []],                              # 0
+    [-1, 1, 'Conv', [64, 3, 2]],                         # 1-P1/2
+    [-1, 1, 'Conv', [128, 3, 2]],                        # 2-P2/4
+    [-1, 1, 'RepNCSPELAN4', [256, 128, 64, 1]],          # 3
+    [-1, 1, 'ADown', [256]],                             # 4-P3/8
+    [-1, 1, 'RepNCSPELAN4', [512, 256, 128, 1]],         # 5
+    [-1, 1, 'ADown', [512]],                             # 6-P4/16
+    [-1, 1, 'RepNCSPELAN4', [512, 512, 256, 1]],         # 7
+    [-1, 1, 'ADown', [512]],                             # 8-P5/32
+    [-1, 1, 'RepNCSPELAN4', [512, 512, 256, 1]],         # 9
+]
+
+_HEAD_YOLOV9C = [
+    [-1, 1, 'SPPELAN', [512, 256]],                      # 10
+    [-1, 1, 'nn.Upsample', [None, 2, 'nearest']],
+    [[-1, 7], 1, 'Concat', [1]],                         # cat backbone P4
+    [-1, 1, 'RepNCSPELAN4', [512, 512, 256, 1]],         # 13
+    [-1, 1, 'nn.Upsample', [None, 2, 'nearest']],
+    [[-1, 5], 1, 'Concat', [1]],                         # cat backbone P3
+    [-1, 1, 'RepNCSPELAN4', [256, 256, 128, 1]],         # 16 (P3/8-small)
+    [-1, 1, 'ADown', [256]],
+    [[-1, 13], 1, 'Concat', [1]],                        # cat head P4
+    [-1, 1, 'RepNCSPELAN4', [512, 512, 256, 1]],         # 19 (P4/16-medium)
+    [-1, 1, 'ADown', [512]],
+    [[-1, 10], 1, 'Concat', [1]],                        # cat head P5
+    [-1, 1, 'RepNCSPELAN4', [512, 512, 256, 1]],         # 22 (P5/32-large)
+]
+
+_AUX_YOLOV9C = [
+    [5, 1, 'CBLinear', [[256]]],                         # 23
+    [7, 1, 'CBLinear', [[256, 512]]],                    # 24
+    [9, 1, 'CBLinear', [[256, 512, 512]]],               # 25
+    [0, 1, 'Conv', [64, 3, 2]],                          # 26-P1/2
+    [-1, 1, 'Conv', [128, 3, 2]],                        # 27-P2/4
+    [-1, 1, 'RepNCSPELAN4', [256, 128, 64, 1]],          # 28
+    [-1, 1, 'ADown', [256]],                             # 29-P3/8
+    [[23, 24, 25, -1], 1, 'CBFuse', [[0, 0, 0]]],        # 30
+    [-1, 1, 'RepNCSPELAN4', [512, 256, 128, 1]],         # 31
+    [-1, 1, 'ADown', [512]],                             # 32-P4/16
+    [[24, 25, -1], 1, 'CBFuse', [[1, 1]]],               # 33
+    [-1, 1, 'RepNCSPELAN4', [512, 512, 256, 1]],         # 34
+    [-1, 1, 'ADown', [512]],                             # 35-P5/32
+    [[25, -1], 1, 'CBFuse', [[2]]],                      # 36
+    [-1, 1, 'RepNCSPELAN4', [512, 512, 256, 1]],         # 37
+]
+
+
+def _scaled_rows(rows, div):
+    """channel arguments divided by `div` (small test networks with the same module mix)"""
+    if div == 1:
+        return [list(r) for r in rows]
+    out = []
+    for f, n, m, args in rows:
+        if m in ('Conv', 'ADown'):
+            args = [args[0] // div] + list(args[1:])
+        elif m in ('RepNCSPELAN4', 'SPPELAN'):
+            args = [a // div for a in args[:3]] + list(args[3:])
+        elif m == 'CBLinear':
+            args = [[c // div for c in args[0]]]
+        out.append([f, n, m, list(args)])
+    return out
+
+
+def make_yolov9_yaml(nc=3, dual=False, div=1):
+    """A YOLOv9-C yaml dict (the keys the yolov9 package pickles as model.yaml): converted (DDetect) or training
+    (dual, DualDDetect) form; div > 1 divides every channel argument (test networks)."""
+    head = _scaled_rows(_HEAD_YOLOV9C, div)
+    if dual:
+        head += _scaled_rows(_AUX_YOLOV9C, div) + [[[31, 34, 37, 16, 19, 22], 1, 'DualDDetect', ['nc']]]
+    else:
+        head += [[[16, 19, 22], 1, 'DDetect', ['nc']]]
+    return {
+        'nc': nc,
+        'depth_multiple': 1.0,
+        'width_multiple': 1.0,
+        'anchors': 3,
+        'backbone': _scaled_rows(_BACKBONE_YOLOV9C, div),
+        'head': head,
+    }
+
+
+#: MDv1000-cedar, converted (GELAN-C) form: nc = 3, 640 px
+GELAN_C_MD = make_yolov9_yaml(nc=3)
+#: MDv1000-cedar, training (yolov9-c.yaml) form with the auxiliary branch and DualDDetect
+YOLOV9C_MD = make_yolov9_yaml(nc=3, dual=True)
+#: small networks of the same module mix for fast tests (channel arguments / 4)
+GELAN_TEST = make_yolov9_yaml(nc=3, div=4)
+YOLOV9_DUAL_TEST = make_yolov9_yaml(nc=3, dual=True, div=4)
+#: the upstream COCO models, only to cross-check the work / parameter counts against the published figures
+GELAN_C_COCO = make_yolov9_yaml(nc=80)
+YOLOV9C_COCO = make_yolov9_yaml(nc=80, dual=True)
+
+#: module names that only the yolov9 package's yaml format uses: they select the yolov9 resolver
+YOLOV9_MODULES = ('RepNCSPELAN4', 'ADown', 'SPPELAN', 'CBLinear', 'CBFuse', 'DDetect', 'DualDDetect', 'Silence')
+
+
+def is_yolov9(yaml):
+    """True for a yolov9-package yaml dict: the YOLOv5 format (no 'scales') with at least one yolov9 module."""
+    if 'scales' in yaml or 'scale' in yaml:
+        return False
+    rows = list(yaml.get('backbone') or []) + list(yaml.get('head') or [])
+    return any(len(r) > 2 and r[2] in YOLOV9_MODULES for r in rows)

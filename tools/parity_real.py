@@ -46,7 +46,7 @@ CI_CONF_ERROR = 0.01          # md_tests.py:1779
 IOU_MATCH = 0.85              # md_tests.py:124
 KNOWN_MD5 = {'md_v5a.0.0.pt': None, 'md_v5a.0.1.pt': None, 'md_v5b.0.0.pt': None, 'md_v5b.0.1.pt': None}
 # environment variables that may name a checkpoint, in the order they are tried when --model is not given
-MODEL_ENV = ('MDV5A', 'MDV5B', 'MDV1000_REDWOOD', 'MDV1000_SPRUCE', 'MDV1000_LARCH', 'MDV1000_SORREL')
+MODEL_ENV = ('MDV5A', 'MDV5B', 'MDV1000_REDWOOD', 'MDV1000_SPRUCE', 'MDV1000_LARCH', 'MDV1000_SORREL', 'MDV1000_CEDAR')
 
 
 def resolve_model(model):
