@@ -12,6 +12,11 @@ its own GPU (the image queue shards embarrassingly, no collectives: SURVEY.md se
 
 Launch (N > 1):  python -m torch.distributed.run --nnodes=1 --nproc-per-node N
                  --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what its headline figure needs and nothing else: set-up, warm-up, the timed steps, --dump-outputs and the
+JSON line (with the roofline of the timed steps' own HIP events).  --full adds what takes runs of its own after the timed
+region: the per-stage and per-op timings (stages, the per-op and dominant-kernel rows of roofline, --profile-out), the
+short legs of the other BASELINE configurations (extra_configs) and the CPU baseline (cpu_baseline).
 """
 
 import argparse
@@ -71,21 +76,25 @@ def parse_args():
                          'the letterbox kernel resizes to the --size long side; not the headline configuration')
     ap.add_argument('--threshold', type=float, default=1e-5,
                     help='detection threshold handed to NMS (batch mode default of the reference)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no cpu_baseline (a plain run has none)')
     ap.add_argument('--host-fed', action='store_true',
                     help='inputs start in pinned host memory and cross PCIe inside the timed region (H2D on a copy '
                          'stream, overlapped with the previous step); reported as the PCIe-inclusive rate, NOT the headline value')
     ap.add_argument('--graph', default='off', choices=['auto', 'on', 'off'],
                     help="graph replay of the forward (mdhip_set_graph; 'auto' = batches <= 8).  Off like the detector's default: "
                          "measured, no gain (profiles/r3_graph_replay.txt)")
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region also measure what takes runs of its own: per-stage and per-op timings, the '
+                         'extra_configs legs and the CPU baseline (--lean, --no-extra-configs and --no-cpu-baseline leave parts '
+                         'out again).  Off: the run ends with the headline line')
     ap.add_argument('--lean', action='store_true',
-                    help='only warm-up + timed steps (no per-stage / per-op extras): for rocprofv3 runs')
+                    help='with --full: no per-stage / per-op timings and no extra_configs legs (a plain run has neither)')
     ap.add_argument('--cpu-seconds', type=float, default=24.0)
     ap.add_argument('--no-cpu-single-thread', action='store_true', help='skip the one-thread CPU row (one image, ~1 min)')
     ap.add_argument('--nms-inline', action='store_true',
                     help='NMS + D2H of step i on the compute stream behind the forward (rounds 2-3 default).  Default since '
                          'round 4: on their own stream next to the forward of step i+1 -- with the banded NMS sort the 32 '
-                         'workgroups are gone before the next forward reaches its 8-wave kernels (+0.4 .. 0.7 %, '
+                         'workgroups are gone before the next forward reaches its 8-wave kernels (+0.4 .. 0.7 %%, '
                          'profiles/r4_bench_nms_stream.txt)')
     ap.add_argument('--nms-own-stream', action='store_true', help='(the default now; kept so that older command lines still parse)')
     ap.add_argument('--pre-own-stream', action='store_true',
@@ -93,14 +102,15 @@ def parse_args():
                          '(mdhip_preprocess waits for it inside the library).  Measured in round 4: 1015.5 against 1021.5 '
                          'images/s with the letterbox on the compute stream (profiles/r4_bench_pre_stream.txt) -- its '
                          'workgroups keep the 8-wave conv workgroups off their CUs; off by default')
-    ap.add_argument('--profile-out', default=None, help='write per-op timings (json) here')
+    ap.add_argument('--profile-out', default=None, help='write per-op timings (json) here (needs --full)')
     ap.add_argument('--dump-outputs', default=None, metavar='DIR',
                     help='after the timed steps, write the formatted detections of the last timed step (what a caller of the '
                          'hot path receives) and its raw NMS rows as DIR/<name>.npy (dump_outputs); the inputs are seeded, so '
                          'two builds run with the same arguments can be compared output for output')
     ap.add_argument('--no-extra-configs', action='store_true',
-                    help='skip the short legs of the other BASELINE configurations (extra_configs: fp8 batch 64, 1080p video '
-                         'frames, 4:3 real shape, fp16 storage); they only run with the default headline workload on one GPU')
+                    help='with --full: skip the short legs of the other BASELINE configurations (extra_configs: fp8 batch 64, '
+                         '1080p video frames, 4:3 real shape, fp16 storage); they only run with the default headline workload '
+                         'on one GPU')
     ap.add_argument('--extra-steps', type=int, default=10)
     ap.add_argument('--pin-cpus', action='store_true',
                     help='N = 1: pin this process to the CPUs of the GPU\'s NUMA node anyway (placement.pin_worker(force=True); '
@@ -111,6 +121,8 @@ def parse_args():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if args.profile_out and not args.full:
+        ap.error('--profile-out needs --full (the per-op timings are a pass of their own after the timed region)')
     return args
 
 
@@ -476,7 +488,7 @@ class Workload:
         self.batches = None
 
 
-# bench.py's default invocation also measures, after the timed region of the headline workload (BASELINE configs[1]),
+# bench.py --full also measures, after the timed region of the headline workload (BASELINE configs[1]),
 # every other BASELINE configuration that fits one GPU -- short legs, reported under "extra_configs", never `value`
 EXTRA_LEGS = [
     # key,            dtype,  batch, source HxW,  what
@@ -628,6 +640,8 @@ def main():
     from megadetector_amd.postprocess import format_detections
 
     B, S = args.batch, args.size
+    # the per-stage / per-op pass after the timed region: --full only (the module docstring)
+    per_op = args.full and not args.lean
     yaml = getattr(yolo_yaml, args.model)
     weights = weights_io.synthetic_weights(yaml, seed=0)
     wl = Workload(torch, weights, args.dtype, B, S, args.src, args.threshold, local_rank, seed_base=1000 * rank,
@@ -694,7 +708,7 @@ def main():
             torch.cuda.synchronize()
             return (time.perf_counter() - t) / reps * 1e3
         ms = np.zeros(ctx.num_ops(), dtype=np.float64)
-        if not args.lean:
+        if per_op:
             stages['preprocess_ms'] = timed(lambda: ctx.preprocess(dev_ptrs[0] if args.host_fed else ptr_lists[0], geoms, Hn, Wn))
             stages['forward_ms'] = timed(lambda: ctx.forward(B, Hn, Wn))
             stages['nms_d2h_ms'] = timed(lambda: ctx.nms(B, args.threshold, 0.45, 300))
@@ -756,10 +770,10 @@ def main():
                           'conv_v5_kernel / conv_v5s_kernel / conv_stem_kernel / conv_f8_kernel instantiations), HIP events on the launch stream around '
                           'mdhip_forward in the timed region, mean of {} steps'.format(len(conv), len(fwd_ms_live)),
                 'flops_per_step': conv_flops, 'kernel_ms_per_step': round(fwd_ms, 3),
-                'per_op_conv_ms_per_step': None if args.lean else round(conv_ms, 3),
-                'per_op_conv_tflops': None if args.lean else round(conv_flops / (conv_ms * 1e-3) / 1e12, 2),
-                'other_kernels_ms_per_step': None if args.lean else round(other_ms, 3)}
-        if not args.lean:
+                'per_op_conv_ms_per_step': round(conv_ms, 3) if per_op else None,
+                'per_op_conv_tflops': round(conv_flops / (conv_ms * 1e-3) / 1e12, 2) if per_op else None,
+                'other_kernels_ms_per_step': round(other_ms, 3) if per_op else None}
+        if per_op:
             # the dominant kernel instantiation (by time) and its own rate, from the per-op events
             by_cfg = {}
             for o, t in conv:
@@ -806,7 +820,7 @@ def main():
                          'nms kernels + D2H of the results, live events on the NMS stream, {} steps'.format(len(live_nms))),
             'decode': None,
         }
-        if not args.lean:
+        if per_op:
             dec_ops = [o for o in infos if o['kind'] == 3]
             folded = [o for o in dec_ops if o['cfg'] == -2]          # decoded in the epilogue of the conv in front (mdhip.h)
             if folded and len(folded) == len(dec_ops):
@@ -824,7 +838,7 @@ def main():
                         sum(1 for o in dec_ops if o['cfg'] != -2)))
         if args.model == 'YOLOV5X6_MD' and (Hn, Wn) == (1280, 1280):
             assert abs(conv_flops / B / 1e9 - GFLOP_PER_IMAGE_1280) < 0.05, conv_flops / B / 1e9
-        if args.profile_out and not args.lean:
+        if args.profile_out and per_op:
             os.makedirs(os.path.dirname(os.path.abspath(args.profile_out)), exist_ok=True)
             with open(args.profile_out, 'w') as f:
                 json.dump([dict(o, ms=float(ms[o['op']]),
@@ -835,7 +849,7 @@ def main():
     extra = None
     default_workload = (args.dtype == 'bf16' and B == 32 and not args.src and not args.host_fed and args.model == 'YOLOV5X6_MD'
                         and S == 1280 and not args.no_table)
-    if rank == 0 and world == 1 and default_workload and not args.lean and not args.no_extra_configs:
+    if rank == 0 and world == 1 and default_workload and per_op and not args.no_extra_configs:
         wl.close()                                   # the headline context's arena goes back before the legs allocate theirs
         extra = {}
         for key, dt, b, src, what in EXTRA_LEGS:
@@ -854,7 +868,7 @@ def main():
         dist = None
     wl.close()
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         if world > 1 and hasattr(os, 'sched_setaffinity'):
             # the rank was pinned to its GPU's share of the host; the baseline is the HOST's best, as in the N = 1 line
             try:
@@ -902,6 +916,7 @@ def main():
             'per_rank_images_per_s': per_rank,
             'pinned_cpus': len(pinned_cpus) if (world > 1 or args.pin_cpus) else None,
             'control_plane': control_plane,
+            'full': args.full,
         }
         if control_why:
             line['control_plane_note'] = control_why

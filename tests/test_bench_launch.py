@@ -268,3 +268,53 @@ def test_dump_outputs_holds_the_last_timed_step(tmp_path):
         assert got['num_detections'][b] == len(dets) and got['max_conf'][b] == max_conf
         assert got['conf'][b, :len(dets)].tolist() == [d['conf'] for d in dets]
         assert got['bbox'][b, :len(dets)].tolist() == [d['bbox'] for d in dets]
+
+
+def test_bench_help_lists_full():
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--help'], env=_env(), capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0 and '--full' in r.stdout, r.stderr[-2000:]
+
+
+def test_bench_profile_out_needs_full(tmp_path):
+    """the per-op timings --profile-out writes come from a pass of their own that only a --full run makes: asked for in a
+    plain run, the run is refused before it starts, not left without its file"""
+    ops = str(tmp_path / 'ops.json')
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--profile-out', ops, '--rendezvous-check'],
+                       env=_env(), capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and '--profile-out needs --full' in r.stderr
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--full', '--profile-out', ops,
+                        '--rendezvous-check'], env=_env(), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and json.loads(r.stdout.strip())['n_gpus'] == 1
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone_and_full_adds_the_rest(tmp_path):
+    """a plain run: set-up, warm-up, timed steps, the line -- with the roofline of the timed steps' own events and none of
+    the passes after the timed region; --full: the per-stage and per-op timings, --profile-out and the CPU baseline as
+    before (extra_configs only belong to the default headline workload, not to this small one)"""
+    args = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '4',
+            '--size', '256', '--model', 'YOLOV5N6_TEST', '--dtype', 'fp16']
+
+    def line(extra):
+        r = subprocess.run(args + extra, env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads(r.stdout.strip().splitlines()[-1])
+        assert out['unit'] == 'images/s' and out['higher_is_better'] is True and out['dtype'] == 'fp16'
+        assert out['value'] > 0 and out['ms_per_step'] > 0 and out['steps'] == 3 and out['warmup'] == 1
+        assert out['metric'].startswith('images/sec (whole node)')
+        assert out['roofline']['kernel_ms_per_step'] > 0 and out['extra_configs'] is None
+        return out
+
+    plain = line([])
+    assert plain['full'] is False and plain['stages'] == {} and plain['cpu_baseline'] is None
+    assert plain['roofline']['per_op_conv_ms_per_step'] is None and 'dominant_kernel' not in plain['roofline']
+    assert plain['roofline']['stages']['decode'] is None
+
+    ops = tmp_path / 'ops.json'
+    full = line(['--full', '--cpu-seconds', '2', '--no-cpu-single-thread', '--profile-out', str(ops)])
+    assert full['full'] is True and full['stages']['forward_ms'] > 0 and full['cpu_baseline']['value'] > 0
+    assert full['roofline']['per_op_conv_ms_per_step'] > 0 and 'dominant_kernel' in full['roofline']
+    assert full['roofline']['stages']['decode'] is not None
+    rows = json.loads(ops.read_text())
+    assert rows and all('ms' in o for o in rows)

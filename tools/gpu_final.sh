@@ -22,11 +22,11 @@ grep -E "^\.|passed|failed|pytest exit|x6 checkpoint|sparse x6|worst|predictions
 timeout 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1; echo "smoke exit $?" >> $O/smoke.log
 stamp "tests"
 # ---- bench lines ----
-timeout 600 python bench.py --steps 100 --warmup 10 --profile-out $O/ops_b32.json > $O/bench.log 2>&1
-timeout 300 python bench.py --dtype fp8 --batch 64 --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs --profile-out $O/ops_fp8_b64.json > $O/bench_fp8_b64.log 2>&1
-timeout 300 python bench.py --dtype fp16 --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs > $O/bench_fp16.log 2>&1
-timeout 300 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs --nms-inline > $O/bench_nms_inline.log 2>&1
-timeout 300 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs > $O/bench_nms_own.log 2>&1
+timeout 600 python bench.py --full --steps 100 --warmup 10 --profile-out $O/ops_b32.json > $O/bench.log 2>&1
+timeout 300 python bench.py --full --dtype fp8 --batch 64 --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs --profile-out $O/ops_fp8_b64.json > $O/bench_fp8_b64.log 2>&1
+timeout 300 python bench.py --full --dtype fp16 --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs > $O/bench_fp16.log 2>&1
+timeout 300 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs --nms-inline > $O/bench_nms_inline.log 2>&1
+timeout 300 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs > $O/bench_nms_own.log 2>&1
 stamp "main benches"
 # ---- rocprofv3: kernel trace of the bench command, then the counter passes ----
 (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$O/prof" -o r$R -- \
@@ -59,28 +59,28 @@ find $O/tcc -type f -size +1M -delete 2>/dev/null
 stamp "trace + traffic + L2 hit rate"
 left && { bash tools/pmc_bench.sh final$R > $O/pmc_bench.log 2>&1; cp gpurun_out/pmc_final$R.txt gpurun_out/pmc_final$R.json $O/ 2>/dev/null; }
 stamp "pmc"
-left && timeout 300 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs --src 1536x2048 > $O/bench_real43.log 2>&1
-left && timeout 300 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs --src 1080x1920 > $O/bench_video_1080p.log 2>&1
-left && timeout 300 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs --src 1600x2400 > $O/bench_real32.log 2>&1
+left && timeout 300 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs --src 1536x2048 > $O/bench_real43.log 2>&1
+left && timeout 300 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs --src 1080x1920 > $O/bench_video_1080p.log 2>&1
+left && timeout 300 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs --src 1600x2400 > $O/bench_real32.log 2>&1
 for s in 1080x1920 1536x2048 1600x2400; do
   left && timeout 200 python bench.py --dtype fp16 --src $s --steps 30 --warmup 5 --no-cpu-baseline --no-extra-configs --lean > $O/bench_fp16_$s.log 2>&1
 done
 for b in 1 2 4 8 16; do
   left && timeout 200 python bench.py --batch $b --steps 60 --warmup 10 --no-cpu-baseline --lean > $O/bench_b$b.log 2>&1
 done
-left && timeout 300 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs --host-fed > $O/bench_hostfed.log 2>&1
+left && timeout 300 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs --host-fed > $O/bench_hostfed.log 2>&1
 left && timeout 300 python tests/accuracy_report.py --x6 > $O/accuracy_x6.txt 2>&1
 stamp "all done"
 ls -laR $O > $O/ls.log
 # ---- the multi-rank code path of bench.py on this one GPU (gloo test hook), the end-to-end feed on JPEG files ----
 left && MDHIP_BENCH_ONE_GPU=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 \
-    bench.py --gpus 2 --batch 8 --steps 30 --warmup 5 > $O/bench_2rank_one_gpu_gloo.log 2>&1
+    bench.py --full --gpus 2 --batch 8 --steps 30 --warmup 5 > $O/bench_2rank_one_gpu_gloo.log 2>&1
 # the self-launching form (`python bench.py --gpus 2`, no launcher) and a pinned single-GPU run (placement.pin_worker(force))
-left && MDHIP_BENCH_ONE_GPU=1 timeout 300 python bench.py --gpus 2 --batch 8 --steps 30 --warmup 5 > $O/bench_selflaunch_2rank.log 2> $O/bench_selflaunch_2rank.err
-left && timeout 300 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs --pin-cpus > $O/bench_pinned.log 2> $O/bench_pinned.err
-left && MDHIP_BENCH_ONE_GPU=1 timeout 400 python bench.py --gpus 8 --batch 2 --steps 20 --warmup 3 > $O/bench_8rank_one_gpu_gloo.log 2> $O/bench_8rank_one_gpu_gloo.err
+left && MDHIP_BENCH_ONE_GPU=1 timeout 300 python bench.py --full --gpus 2 --batch 8 --steps 30 --warmup 5 > $O/bench_selflaunch_2rank.log 2> $O/bench_selflaunch_2rank.err
+left && timeout 300 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs --pin-cpus > $O/bench_pinned.log 2> $O/bench_pinned.err
+left && MDHIP_BENCH_ONE_GPU=1 timeout 400 python bench.py --full --gpus 8 --batch 2 --steps 20 --warmup 3 > $O/bench_8rank_one_gpu_gloo.log 2> $O/bench_8rank_one_gpu_gloo.err
 # a REAL RCCL failure: both ranks on device 0 with the RCCL attempt made (RCCL refuses the duplicate device) -> the line must come out over gloo, with the reason
-left && MDHIP_BENCH_ONE_GPU=try timeout 300 python bench.py --gpus 2 --batch 8 --steps 30 --warmup 5 > $O/bench_2rank_rccl_refused.log 2> $O/bench_2rank_rccl_refused.err
+left && MDHIP_BENCH_ONE_GPU=try timeout 300 python bench.py --full --gpus 2 --batch 8 --steps 30 --warmup 5 > $O/bench_2rank_rccl_refused.log 2> $O/bench_2rank_rccl_refused.err
 left && timeout 200 python tools/letterbox_bench.py > $O/letterbox_bench.txt 2>&1
 left && timeout 400 python tools/e2e_feed_bench.py --n 4096 --workers 16,24 --out $O/e2e_feed.json > $O/e2e_feed.log 2>&1
 # the NUMA placement code on this box's topology (8 GPUs asked for: what the planner does with the GPUs it cannot see)

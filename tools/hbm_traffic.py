@@ -6,7 +6,7 @@ MI355X_MICROARCH.md 'rocprofv3 PMC slots').
 
 usage: hbm_traffic.py <fetch_pass_dir> <write_pass_dir> <key> <out.json> [<ops.json> [<table.txt>]]
 
-With <ops.json> (bench.py --profile-out of the same build: one row per op of the forward, the library's own accounting of
+With <ops.json> (bench.py --full --profile-out of the same build: one row per op of the forward, the library's own accounting of
 every op's algorithmic bytes, mdhip_get_op_info) the dispatches of a step are aligned with the ops in launch order and the
 output gains `per_op` and `per_instantiation`: counter bytes next to ALGORITHMIC read / write bytes and their ratio --
 read amplification per kernel instantiation (halo re-reads across tiles and XCDs, operands that miss L2) instead of one

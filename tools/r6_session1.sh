@@ -22,6 +22,6 @@ for sh in l26_cv3 l23_cv12; do
   echo "== $sh" >> $O/pf_ablation.txt
   timeout 200 $CB $sh 20 p6 p7 p8 p9 p10 p11 p12 >> $O/pf_ablation.txt 2>&1
 done
-timeout 600 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs --profile-out $O/ops_b32.json > $O/bench.log 2>&1
+timeout 600 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extra-configs --profile-out $O/ops_b32.json > $O/bench.log 2>&1
 echo "bench exit $?" >> $O/bench.log
 ls -la $O > $O/ls.log

@@ -7,5 +7,5 @@ mkdir -p $O
 export TMPDIR=/tmp
 python -c "import torch" > /dev/null 2>&1
 T0=$(date +%s)
-MDHIP_BENCH_DUMP_AFTER=200 MDHIP_BENCH_ONE_GPU=try timeout 280 python bench.py --gpus 2 --batch 8 --steps 30 --warmup 5 > $O/bench_2rank_rccl_refused.log 2> $O/bench_2rank_rccl_refused.err; echo "exit $? at $(( $(date +%s) - T0 )) s" >> $O/bench_2rank_rccl_refused.log
+MDHIP_BENCH_DUMP_AFTER=200 MDHIP_BENCH_ONE_GPU=try timeout 280 python bench.py --full --gpus 2 --batch 8 --steps 30 --warmup 5 > $O/bench_2rank_rccl_refused.log 2> $O/bench_2rank_rccl_refused.err; echo "exit $? at $(( $(date +%s) - T0 )) s" >> $O/bench_2rank_rccl_refused.log
 ls -la $O > $O/ls.log

@@ -22,10 +22,10 @@ timeout 900 python -m pytest tests/test_gpu_headline.py tests/test_gpu_parity.py
 for b in 1 2 4 8 16; do
   timeout 200 python bench.py --batch $b --steps 60 --warmup 10 --no-cpu-baseline --lean > $O/bench_b$b.log 2>&1
 done
-timeout 300 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --src 1536x2048 > $O/bench_real43.log 2>&1
-timeout 300 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --src 1080x1920 > $O/bench_video_1080p.log 2>&1
-timeout 300 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --src 1600x2400 > $O/bench_real32.log 2>&1
-timeout 300 python bench.py --dtype fp16 --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_fp16.log 2>&1
+timeout 300 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --src 1536x2048 > $O/bench_real43.log 2>&1
+timeout 300 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --src 1080x1920 > $O/bench_video_1080p.log 2>&1
+timeout 300 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --src 1600x2400 > $O/bench_real32.log 2>&1
+timeout 300 python bench.py --full --dtype fp16 --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_fp16.log 2>&1
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/retune/bench_*.log')):
