@@ -175,6 +175,20 @@ const char* mdhip_last_error(mdhip_ctx* ctx);
 int mdhip_preprocess(mdhip_ctx* ctx, const uint8_t* const* images, const mdhip_letterbox* geom,
                      int n, int out_h, int out_w, void* hip_stream);
 
+/* mdhip_preprocess for sources that are WINDOWS of larger device images (tiles of an aerial image, ...): the parent image is
+ * uploaded once and every tile of it is cut, resampled and normalised on the device.
+ *   windows[i]   device pointer to the window's first pixel (parent + y0 * pitch + x0 * 3); a host pointer is MDHIP_EINVAL
+ *   geom[i]      src_h / src_w = the WINDOW's size: geometry, and the clamping of the interpolation at the window's edge,
+ *                are those of a dense image of that size (crop first, resize afterwards)
+ *   pitches[i]   bytes between two rows of the parent (>= src_w * 3)
+ *   readable[i]  bytes readable from windows[i] to the end of the parent allocation (>= (src_h - 1) * pitch + src_w * 3).
+ *                The streaming kernels read whole aligned dwords around what they use; inside the parent that only touches
+ *                neighbouring pixels, and no read reaches behind the aligned dword that holds byte readable[i] - 1.
+ * Streams, the wait for the previous forward's stem and the bookkeeping for mdhip_forward are those of mdhip_preprocess;
+ * the network input it leaves is the same, bit for bit, as mdhip_preprocess leaves for the contiguous copy of each window. */
+int mdhip_preprocess_windows(mdhip_ctx* ctx, const uint8_t* const* windows, const mdhip_letterbox* geom,
+                             const int64_t* pitches, const int64_t* readable, int n, int out_h, int out_w, void* hip_stream);
+
 /* Replaces self.model(batch)[0] (pytorch_detector.py:1313): conv stack + Detect decode.
  * Leaves (n, n_anchors, 5+nc) fp32 predictions in a device buffer of the context (4+nc for an anchor-free model). */
 int mdhip_forward(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream);

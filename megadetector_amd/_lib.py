@@ -61,6 +61,8 @@ SYMBOLS = {
     'mdhip_destroy': (None, [_P]),
     'mdhip_last_error': (C.c_char_p, [_P]),
     'mdhip_preprocess': (C.c_int, [_P, C.POINTER(_P), C.POINTER(mdhip_letterbox), C.c_int, C.c_int, C.c_int, _P]),
+    'mdhip_preprocess_windows': (C.c_int, [_P, C.POINTER(_P), C.POINTER(mdhip_letterbox), C.POINTER(C.c_int64),
+                                           C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_forward': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_forward_tta': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_last_num_anchors': (C.c_int, [_P]),

@@ -175,7 +175,7 @@ struct mdhip_ctx {
     hipEvent_t fwd_ev[kFwdRing][2] = {};
     long long fwd_count = 0;
     // pinned host staging: letterbox geometry ring + asynchronous NMS result slots
-    LetterboxDev* geom_host = nullptr;
+    uint8_t* geom_host = nullptr;      // 4 slots of max_batch * sizeof(LetterboxWin) (the larger of the two geometry records)
     int geom_slot = 0;
     hipEvent_t geom_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float* nms_host_out[MDHIP_NMS_SLOTS] = {};
@@ -1862,7 +1862,7 @@ int mdhip_create(const mdhip_model* model, int device, int dtype, int max_batch,
     const size_t nms_seg = P.alloc_bytes((size_t)max_batch * kNmsScanParts * 4);
     ctx->nms_out_off = P.alloc_bytes((size_t)max_batch * kNmsMaxDet * 6 * 4);
     ctx->nms_cnt_off = P.alloc_bytes((size_t)max_batch * 4);
-    ctx->geom_off = P.alloc_bytes((size_t)max_batch * sizeof(LetterboxDev));
+    ctx->geom_off = P.alloc_bytes((size_t)max_batch * sizeof(LetterboxWin));
     {   // fp8 calibration: one range word per e4m3 tensor
         const size_t base = P.alloc_bytes((size_t)std::max(1, ctx->n_f8) * 4);
         size_t k = 0;
@@ -1923,7 +1923,7 @@ int mdhip_create(const mdhip_model* model, int device, int dtype, int max_batch,
     CREATE_TRY(hipMalloc((void**)&ctx->arena, ctx->arena_bytes));
     CREATE_TRY(hipMalloc((void**)&ctx->warena, ctx->warena_bytes));
     CREATE_TRY(hipMemset(ctx->warena, 0, 256));
-    CREATE_TRY(hipHostMalloc((void**)&ctx->geom_host, (size_t)4 * max_batch * sizeof(LetterboxDev), hipHostMallocDefault));
+    CREATE_TRY(hipHostMalloc((void**)&ctx->geom_host, (size_t)4 * max_batch * sizeof(LetterboxWin), hipHostMallocDefault));
     for (int i = 0; i < 4; ++i) CREATE_TRY(hipEventCreateWithFlags(&ctx->geom_ev[i], hipEventDisableTiming));
     CREATE_TRY(hipEventCreateWithFlags(&ctx->input_free, hipEventDisableTiming));
     for (int i = 0; i < 2; ++i) CREATE_TRY(hipEventCreateWithFlags(&ctx->pred_read[i], hipEventDisableTiming));
@@ -1997,6 +1997,31 @@ int mdhip_num_anchors(mdhip_ctx* ctx, int h, int w) {
     return num_anchors_for(ctx, h, w);
 }
 
+// the common end of mdhip_preprocess / mdhip_preprocess_windows: G = LetterboxDev (dense images) or LetterboxWin (windows)
+extern "C++" {
+template <class G>
+static int enqueue_letterbox(mdhip_ctx* ctx, const std::vector<G>& g, int n, int out_h, int out_w, hipStream_t s) {
+    // the forward that still reads the input tensor (its stem) comes first, whatever stream it runs on
+    if (ctx->input_free_valid) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->input_free, 0));
+    if (!letterbox_geometry_travels_inline(g.data(), n, out_w, ctx->letterbox_general)) {
+        // geometry goes through a 4-deep pinned ring so that the call never blocks on the stream
+        const int slot = ctx->geom_slot;
+        ctx->geom_slot = (slot + 1) & 3;
+        HIP_TRY(ctx, hipEventSynchronize(ctx->geom_ev[slot]));          // slot's previous copy has completed
+        uint8_t* gh = ctx->geom_host + (size_t)slot * ctx->max_batch * sizeof(LetterboxWin);
+        memcpy(gh, g.data(), n * sizeof(G));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->arena + ctx->geom_off, gh, n * sizeof(G), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipEventRecord(ctx->geom_ev[slot], s));
+    }
+    HIP_TRY(ctx, launch_letterbox_s2d((const G*)(ctx->arena + ctx->geom_off), g.data(), n, out_h, out_w,
+                                      (uint16_t*)(ctx->arena + ctx->input.off), ctx->dtype == MDHIP_DTYPE_FP16, ctx->letterbox_general, s));
+    ctx->last_n = n;
+    ctx->last_h = out_h;
+    ctx->last_w = out_w;
+    return MDHIP_OK;
+}
+}   // extern "C++"
+
 int mdhip_preprocess(mdhip_ctx* ctx, const uint8_t* const* images, const mdhip_letterbox* geom,
                      int n, int out_h, int out_w, void* hip_stream) {
     if (!ctx) return MDHIP_EINVAL;
@@ -2041,24 +2066,45 @@ int mdhip_preprocess(mdhip_ctx* ctx, const uint8_t* const* images, const mdhip_l
         g[i].src = (const uint8_t*)(ctx->stage + cur);
         cur += align_up(bytes, 256);
     }
-    // the forward that still reads the input tensor (its stem) comes first, whatever stream it runs on
-    if (ctx->input_free_valid) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->input_free, 0));
-    if (!letterbox_geometry_travels_inline(g.data(), n, out_w, ctx->letterbox_general)) {
-        // geometry goes through a 4-deep pinned ring so that the call never blocks on the stream
-        const int slot = ctx->geom_slot;
-        ctx->geom_slot = (slot + 1) & 3;
-        HIP_TRY(ctx, hipEventSynchronize(ctx->geom_ev[slot]));          // slot's previous copy has completed
-        LetterboxDev* gh = ctx->geom_host + (size_t)slot * ctx->max_batch;
-        memcpy(gh, g.data(), n * sizeof(LetterboxDev));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->arena + ctx->geom_off, gh, n * sizeof(LetterboxDev), hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipEventRecord(ctx->geom_ev[slot], s));
+    return enqueue_letterbox(ctx, g, n, out_h, out_w, s);
+}
+
+int mdhip_preprocess_windows(mdhip_ctx* ctx, const uint8_t* const* windows, const mdhip_letterbox* geom,
+                             const int64_t* pitches, const int64_t* readable, int n, int out_h, int out_w, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!windows || !geom || !pitches || !readable) return fail(ctx, MDHIP_EINVAL, "windows/geom/pitches/readable is NULL");
+    if (int rc = check_shape(ctx, n, out_h, out_w)) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<LetterboxWin> g(n);
+    for (int i = 0; i < n; ++i) {
+        const mdhip_letterbox& q = geom[i];
+        if (!windows[i] || q.src_h < 1 || q.src_w < 1 || q.resized_h < 1 || q.resized_w < 1 || q.top < 0 || q.left < 0 ||
+            q.top + q.resized_h > out_h || q.left + q.resized_w > out_w)
+            return fail(ctx, MDHIP_EINVAL, "window %d: letterbox geometry does not fit %dx%d", i, out_h, out_w);
+        hipPointerAttribute_t attr;
+        const hipError_t e = hipPointerGetAttributes(&attr, windows[i]);
+        if (e != hipSuccess) (void)hipGetLastError();
+        if (e != hipSuccess || !(attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged))
+            return fail(ctx, MDHIP_EINVAL, "window %d: host pointer -- a window must point into a device image (upload the parent image "
+                        "once and pass pointers into it)", i);
+        if (q.interp != 0 && q.interp != 1) return fail(ctx, MDHIP_EINVAL, "window %d: interp %d (0 = linear, 1 = area)", i, q.interp);
+        if (q.interp == 1 && (q.resized_h > q.src_h || q.resized_w > q.src_w))
+            return fail(ctx, MDHIP_EINVAL, "window %d: INTER_AREA is implemented for shrinking only", i);
+        // bytes from the window's first pixel to the end of its last row: all of them must be readable
+        const long long need = (long long)(q.src_h - 1) * pitches[i] + (long long)q.src_w * 3;
+        if (pitches[i] < (long long)q.src_w * 3 || need > 0x7fff0000LL)
+            return fail(ctx, MDHIP_EINVAL, "window %d: pitch %lld for %d pixels per row (or a window above 2 GB)", i, (long long)pitches[i], q.src_w);
+        if (readable[i] < need)
+            return fail(ctx, MDHIP_EINVAL, "window %d: %lld readable bytes, the window spans %lld", i, (long long)readable[i], need);
+        g[i].d = LetterboxDev{windows[i], q.src_h, q.src_w, q.resized_h, q.resized_w, q.top, q.left, q.interp,
+                              1.0 / ((double)q.resized_w / (double)q.src_w), 1.0 / ((double)q.resized_h / (double)q.src_h)};
+        // (the kernels look at most 16 bytes behind what they use: a larger figure says nothing more, and this one fits 32 bits)
+        g[i].readable = std::min<long long>(readable[i], need + 64);
+        g[i].pitch = (int)pitches[i];
+        g[i].reserved = 0;
     }
-    HIP_TRY(ctx, launch_letterbox_s2d((const LetterboxDev*)(ctx->arena + ctx->geom_off), g.data(), n, out_h, out_w,
-                                      (uint16_t*)(ctx->arena + ctx->input.off), ctx->dtype == MDHIP_DTYPE_FP16, ctx->letterbox_general, s));
-    ctx->last_n = n;
-    ctx->last_h = out_h;
-    ctx->last_w = out_w;
-    return MDHIP_OK;
+    return enqueue_letterbox(ctx, g, n, out_h, out_w, s);
 }
 
 int mdhip_forward(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {

@@ -344,6 +344,15 @@ struct LetterboxDev {     // device copy of mdhip_letterbox + source pointer
     // double on both sides: the bits the kernels' own linear_scale() produces); read by letterbox_linear_s2d_kernel
     double sx, sy;
 };
+// A window of a larger device image with a row pitch (a tile): d.src is the window's first pixel, d.src_h x d.src_w the
+// window.  The streaming kernels read whole aligned dwords; inside the parent that is harmless, behind its end it is not:
+// `readable` bounds every read.
+struct LetterboxWin {
+    LetterboxDev d;
+    long long readable;   // bytes from d.src to the end of the parent allocation (the host clamps it below 2^31)
+    int pitch;            // bytes between two rows of the parent
+    int reserved;
+};
 // u8 HWC -> space-to-depth bf16 [n][out_h/2][out_w/2][16] (12 real channels: (dy,dx,c)), /255
 // Three kernels, chosen per batch from the geometry: a streaming copy (no image resampled), a streaming bilinear kernel
 // (cv2.INTER_LINEAR, every real camera image) and the general one (INTER_AREA, very wide sources); force_general = the last
@@ -352,6 +361,10 @@ struct LetterboxDev {     // device copy of mdhip_letterbox + source pointer
 // the upload)
 bool letterbox_geometry_travels_inline(const LetterboxDev* geom_host, int n, int out_w, bool force_general);
 hipError_t launch_letterbox_s2d(const LetterboxDev* geom_dev, const LetterboxDev* geom_host, int n, int out_h, int out_w,
+                                uint16_t* out, int f16, bool force_general, hipStream_t s);
+// the same for windows of pitched images (sibling kernels built from the same bodies; the dense kernels do not change)
+bool letterbox_geometry_travels_inline(const LetterboxWin* geom_host, int n, int out_w, bool force_general);
+hipError_t launch_letterbox_s2d(const LetterboxWin* geom_dev, const LetterboxWin* geom_host, int n, int out_h, int out_w,
                                 uint16_t* out, int f16, bool force_general, hipStream_t s);
 // SPPF: three chained 5x5/s1/p2 max pools of slice 0 written to slices 1..3 of the same buffer
 hipError_t launch_sppf_pool(uint16_t* buf, int ld, int c, int n, int h, int w, int k, int f16, hipStream_t s);

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "mdhip_internal.h"
 
@@ -77,15 +78,33 @@ __device__ __forceinline__ AreaAxis area_axis(int d, int dst_len, int src_len) {
     return t;
 }
 
-__global__ void __launch_bounds__(256)
-letterbox_s2d_kernel(const LetterboxDev* __restrict__ geom, int out_h, int out_w,
-                     uint16_t* __restrict__ out, int f16) {
+// The three kernels below exist in two forms built from one body: dense sources (G = LetterboxDev: rows src_w * 3 bytes apart,
+// the image ends with its last row) and windows of a larger pitched image (G = LetterboxWin: rows `pitch` bytes apart, reads
+// allowed up to `readable` bytes from the window's first pixel).  Everything that differs is selected with `if constexpr`,
+// so the dense instantiations are the kernels they were before the windowed form existed.
+__host__ __device__ __forceinline__ const LetterboxDev& lb_dev(const LetterboxDev& g) { return g; }
+__host__ __device__ __forceinline__ const LetterboxDev& lb_dev(const LetterboxWin& g) { return g.d; }
+template <class G> constexpr bool kLbPitched = std::is_same<G, LetterboxWin>::value;
+__device__ __forceinline__ int lb_pitch(const LetterboxDev& g) { return g.src_w * 3; }
+__device__ __forceinline__ int lb_pitch(const LetterboxWin& g) { return g.pitch; }
+__device__ __forceinline__ long long lb_readable(const LetterboxDev& g) { return (long long)g.src_h * (g.src_w * 3); }
+__device__ __forceinline__ long long lb_readable(const LetterboxWin& g) { return g.readable; }
+
+template <class G>
+__device__ __forceinline__ void letterbox_s2d_body(const G* __restrict__ geom, int out_h, int out_w,
+                                                   uint16_t* __restrict__ out, int f16) {
     const int img = blockIdx.z;
     const int X = blockIdx.x * blockDim.x + threadIdx.x;     // s2d column
     const int Y = blockIdx.y;                                // s2d row
     const int W2 = out_w >> 1, H2 = out_h >> 1;
     if (X >= W2) return;
-    const LetterboxDev g = geom[img];
+    const G gw = geom[img];
+    const LetterboxDev& g = lb_dev(gw);
+    // address of source pixel (yy, xx)
+    auto pix = [&](size_t yy, size_t xx) __attribute__((always_inline)) -> const uint8_t* {
+        if constexpr (kLbPitched<G>) return g.src + yy * (size_t)gw.pitch + xx * 3;
+        else return g.src + (yy * g.src_w + xx) * 3;
+    };
     const bool resize = (g.resized_h != g.src_h) || (g.resized_w != g.src_w);
     // INTER_AREA (compatibility_mode 'modern', shrinking): integer factors in both directions take OpenCV's
     // integer path, everything else the float table path
@@ -113,13 +132,13 @@ letterbox_s2d_kernel(const LetterboxDev* __restrict__ geom, int out_h, int out_w
             int v[3] = {114, 114, 114};
             if (y_in && (unsigned)x < (unsigned)g.resized_w) {
                 if (!resize) {
-                    const uint8_t* s = g.src + ((size_t)y * g.src_w + x) * 3;
+                    const uint8_t* s = pix((size_t)y, (size_t)x);
                     v[0] = s[0]; v[1] = s[1]; v[2] = s[2];
                 } else if (area && isx > 0) {
                     // resizeAreaFast_: block sum; 2x2 as (s + 2) >> 2, else saturate_cast<uchar>(sum * (1.f / area))
                     int sum[3] = {0, 0, 0};
                     for (int yy = 0; yy < isy; ++yy) {
-                        const uint8_t* r = g.src + ((size_t)(y * isy + yy) * g.src_w + (size_t)x * isx) * 3;
+                        const uint8_t* r = pix((size_t)(y * isy + yy), (size_t)x * isx);
                         for (int xx = 0; xx < isx; ++xx) { sum[0] += r[xx * 3]; sum[1] += r[xx * 3 + 1]; sum[2] += r[xx * 3 + 2]; }
                     }
                     if (isx == 2 && isy == 2) {
@@ -138,7 +157,7 @@ letterbox_s2d_kernel(const LetterboxDev* __restrict__ geom, int out_h, int out_w
                     for (int j = 0; j < nyy; ++j) {
                         int sy; float beta;
                         ay.entry(j, sy, beta);
-                        const uint8_t* r = g.src + (size_t)sy * g.src_w * 3;
+                        const uint8_t* r = pix((size_t)sy, 0);
                         float buf[3] = {0.f, 0.f, 0.f};
                         for (int k = 0; k < nx; ++k) {
                             int sxk; float a;
@@ -155,8 +174,8 @@ letterbox_s2d_kernel(const LetterboxDev* __restrict__ geom, int out_h, int out_w
                 } else {
                     int x0, x1, a0, a1;
                     linear_coef(x, g.resized_w, g.src_w, x0, x1, a0, a1);
-                    const uint8_t* r0 = g.src + (size_t)y0 * g.src_w * 3;
-                    const uint8_t* r1 = g.src + (size_t)y1 * g.src_w * 3;
+                    const uint8_t* r0 = pix((size_t)y0, 0);
+                    const uint8_t* r1 = pix((size_t)y1, 0);
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
                         const int t0 = r0[x0 * 3 + c] * a0 + r0[x1 * 3 + c] * a1;
@@ -179,6 +198,16 @@ letterbox_s2d_kernel(const LetterboxDev* __restrict__ geom, int out_h, int out_w
     hi.z = px[12] | ((uint32_t)px[13] << 16); hi.w = px[14] | ((uint32_t)px[15] << 16);
     dst[0] = lo;
     dst[1] = hi;
+}
+__global__ void __launch_bounds__(256)
+letterbox_s2d_kernel(const LetterboxDev* __restrict__ geom, int out_h, int out_w,
+                     uint16_t* __restrict__ out, int f16) {
+    letterbox_s2d_body(geom, out_h, out_w, out, f16);
+}
+__global__ void __launch_bounds__(256)
+letterbox_win_s2d_kernel(const LetterboxWin* __restrict__ geom, int out_h, int out_w,
+                         uint16_t* __restrict__ out, int f16) {
+    letterbox_s2d_body(geom, out_h, out_w, out, f16);
 }
 
 // [r5] The same transform for batches in which NO image is resampled (resized == source size: the synthetic 1280x1280
@@ -203,33 +232,51 @@ struct LetterboxGeom {
     const LetterboxDev* ptr;
     LetterboxDev inl[kLbInline];
 };
-__global__ void __launch_bounds__(256)
-letterbox_copy_s2d_kernel(const LetterboxGeom geom, int out_h, int out_w,
-                          uint16_t* __restrict__ out, int f16) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lb_lds[];
+struct LetterboxWinGeom {
+    const LetterboxWin* ptr;
+    LetterboxWin inl[kLbInline];
+};
+template <class G> struct LbGeomOf { typedef LetterboxGeom type; };
+template <> struct LbGeomOf<LetterboxWin> { typedef LetterboxWinGeom type; };
+// (a dispatch carries at most 4 KiB of kernel arguments: 32 windows of 72 bytes fit next to the other arguments)
+static_assert(sizeof(LetterboxWinGeom) + 64 <= 4096, "windowed letterbox geometry does not fit the kernel arguments");
+// Windows: a row's aligned dwords may reach into the neighbouring parent pixels (harmless), but not past the parent's last dword
+// -- a group whose dwords would is read byte by byte, like the groups at an image edge.
+template <class G>
+__device__ __forceinline__ void letterbox_copy_s2d_body(const typename LbGeomOf<G>::type& geom, uint32_t* lb_lds, int out_h, int out_w,
+                                                        uint16_t* __restrict__ out, int f16) {
     uint16_t* lut = (uint16_t*)lb_lds;                          // 256 entries
     uint32_t* rows = lb_lds + 128;                              // 2 rows x (out_w * 3 / 2) dwords of 16-bit pairs
     const int img = blockIdx.y, Y = blockIdx.x, t = threadIdx.x;
     const int W2 = out_w >> 1, H2 = out_h >> 1;
     const int row_dw = (out_w * 3) >> 1;                        // dwords per staged row (out_w is a multiple of 4)
-    const LetterboxDev g = geom.ptr ? geom.ptr[img] : geom.inl[img];
+    const G gw = geom.ptr ? geom.ptr[img] : geom.inl[img];
+    const LetterboxDev& g = lb_dev(gw);
     lut[t] = f32_to_st((float)t / 255.0f, f16);
     __syncthreads();
     const uint32_t pad1 = lut[114], pad2 = pad1 | (pad1 << 16);
     const int row_bytes = g.src_w * 3, left3 = g.left * 3;
+    const int row_pitch = lb_pitch(gw);                         // distance of two rows
+    // (windows) end of the dword that holds the last readable byte
+    const uintptr_t lim = ((uintptr_t)g.src + (uintptr_t)lb_readable(gw) + 3) & ~(uintptr_t)3;
     const int groups = (out_w * 3) >> 2;                        // groups of 4 output bytes per row
 #pragma unroll
     for (int dy = 0; dy < 2; ++dy) {
         const int y = 2 * Y + dy - g.top;
         const bool y_in = (unsigned)y < (unsigned)g.src_h;
-        const uint8_t* rb = g.src + (size_t)(y_in ? y : 0) * row_bytes;
+        const uint8_t* rb = g.src + (size_t)(y_in ? y : 0) * row_pitch;
         uint32_t* dst = rows + dy * row_dw;
         for (int gi = t; gi < groups; gi += 256) {
             const int o = 4 * gi - left3;                       // source byte offset of this group's first byte
             uint32_t lo16 = pad2, hi16 = pad2;
             if (y_in && o + 3 >= 0 && o < row_bytes) {
                 uint32_t v;
-                if (o >= 0 && o + 3 < row_bytes) {
+                bool whole = o >= 0 && o + 3 < row_bytes;
+                if constexpr (kLbPitched<G>) {
+                    const uintptr_t a = (uintptr_t)(rb + o);
+                    whole = whole && (a & ~(uintptr_t)3) + ((a & 3) ? 8 : 4) <= lim;
+                }
+                if (whole) {
                     const uintptr_t a = (uintptr_t)(rb + o);
                     const uint32_t* al = (const uint32_t*)(a & ~(uintptr_t)3);
                     const uint32_t sh = (uint32_t)(a & 3);
@@ -262,6 +309,18 @@ letterbox_copy_s2d_kernel(const LetterboxGeom geom, int out_h, int out_w,
         orow[q] = v;
     }
 }
+__global__ void __launch_bounds__(256)
+letterbox_copy_s2d_kernel(const LetterboxGeom geom, int out_h, int out_w,
+                          uint16_t* __restrict__ out, int f16) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lb_lds[];
+    letterbox_copy_s2d_body<LetterboxDev>(geom, lb_lds, out_h, out_w, out, f16);
+}
+__global__ void __launch_bounds__(256)
+letterbox_win_copy_s2d_kernel(const LetterboxWinGeom geom, int out_h, int out_w,
+                              uint16_t* __restrict__ out, int f16) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lb_lds[];
+    letterbox_copy_s2d_body<LetterboxWin>(geom, lb_lds, out_h, out_w, out, f16);
+}
 
 
 // [r6] The bilinear path (cv2.INTER_LINEAR, what yolov5's letterbox() runs for every real camera image: reference
@@ -284,21 +343,21 @@ letterbox_copy_s2d_kernel(const LetterboxGeom geom, int out_h, int out_w,
 // no window reaches past its row; a window whose 12-byte load would reach past the dword of the image's last byte (the last
 // pixels of the last row) is read byte by byte.
 constexpr int kLbRows = 2;
-__global__ void __launch_bounds__(256)
-letterbox_linear_s2d_kernel(const LetterboxGeom geom, int out_h, int out_w, uint16_t* __restrict__ out, int f16) {
-    __shared__ uint16_t lut[256];
-    __shared__ uint4 stage[4 * 128];                            // 2 KiB per wave (the store transpose below)
+// Windows: src_w / src_h stay the WINDOW's size, so the interpolation clamps at the window's edge (the reference crops, then
+// resizes); rows are `pitch` apart and "the image's last byte" is the parent's last readable byte.
+template <class G>
+__device__ __forceinline__ void letterbox_linear_s2d_body(const G& gw, uint16_t* lut, uint4* stage, int out_h, int out_w, uint16_t* __restrict__ out, int f16) {
     const int img = blockIdx.z, t = threadIdx.x;
     const int X = blockIdx.x * 256 + t;                         // s2d column
     const int Y = blockIdx.y;                                   // s2d rows Y * kLbRows ..
     const int W2 = out_w >> 1, H2 = out_h >> 1;
-    const LetterboxDev g = geom.ptr ? geom.ptr[img] : geom.inl[img];
+    const LetterboxDev& g = lb_dev(gw);
     lut[t] = f32_to_st((float)t / 255.0f, f16);
     __syncthreads();
-    const int row_bytes = g.src_w * 3;
+    const int row_bytes = lb_pitch(gw);                         // distance of two rows
     typedef const __attribute__((address_space(1))) uint8_t* gptr_t;
     const uintptr_t src = (uintptr_t)g.src;
-    const long long image_bytes = (long long)g.src_h * row_bytes;
+    const long long image_bytes = lb_readable(gw);              // bytes readable from src on
     // columns: window start (byte offset in a row) and the packed weights of its two pixels
     int wo[2];
     uint32_t aw[2];
@@ -414,18 +473,36 @@ letterbox_linear_s2d_kernel(const LetterboxGeom geom, int out_h, int out_w, uint
         if (X0 + 32 + (lane >> 1) < W2) dst[64 + lane] = c1;
     }
 }
+__global__ void __launch_bounds__(256)
+letterbox_linear_s2d_kernel(const LetterboxGeom geom, int out_h, int out_w, uint16_t* __restrict__ out, int f16) {
+    const int img = blockIdx.z;
+    const LetterboxDev g = geom.ptr ? geom.ptr[img] : geom.inl[img];
+    __shared__ uint16_t lut[256];
+    __shared__ uint4 stage[4 * 128];                            // 2 KiB per wave (the store transpose)
+    letterbox_linear_s2d_body<LetterboxDev>(g, lut, stage, out_h, out_w, out, f16);
+}
+__global__ void __launch_bounds__(256)
+letterbox_win_linear_s2d_kernel(const LetterboxWinGeom geom, int out_h, int out_w, uint16_t* __restrict__ out, int f16) {
+    const int img = blockIdx.z;
+    const LetterboxWin g = geom.ptr ? geom.ptr[img] : geom.inl[img];
+    __shared__ uint16_t lut[256];
+    __shared__ uint4 stage[4 * 128];                            // 2 KiB per wave (the store transpose)
+    letterbox_linear_s2d_body<LetterboxWin>(g, lut, stage, out_h, out_w, out, f16);
+}
 
 // which kernel a batch takes: 1 = streaming copy (no image is resampled), 2 = streaming bilinear (every resampled image with
 // cv2.INTER_LINEAR, source rows short enough for the LDS), 0 = the general kernel (INTER_AREA, very wide sources, odd widths)
 struct LbPlan { int kind; size_t lds; };
-static LbPlan lb_plan(const LetterboxDev* g, int n, int out_w, bool force_general) {
+template <class G>
+static LbPlan lb_plan(const G* gs, int n, int out_w, bool force_general) {
     LbPlan p{0, 0};
     if (force_general) return p;
     bool no_resampling = true, linear = true;
     for (int i = 0; i < n; ++i) {
-        const bool rs = g[i].resized_h != g[i].src_h || g[i].resized_w != g[i].src_w;
+        const LetterboxDev& g = lb_dev(gs[i]);
+        const bool rs = g.resized_h != g.src_h || g.resized_w != g.src_w;
         no_resampling = no_resampling && !rs;
-        linear = linear && (!rs || g[i].interp == 0);
+        linear = linear && (!rs || g.interp == 0);
     }
     if (no_resampling) {
         p.lds = 512 + (size_t)out_w * 12;
@@ -439,26 +516,53 @@ static LbPlan lb_plan(const LetterboxDev* g, int n, int out_w, bool force_genera
 bool letterbox_geometry_travels_inline(const LetterboxDev* geom_host, int n, int out_w, bool force_general) {
     return lb_plan(geom_host, n, out_w, force_general).kind != 0 && n <= kLbInline;
 }
+bool letterbox_geometry_travels_inline(const LetterboxWin* geom_host, int n, int out_w, bool force_general) {
+    return lb_plan(geom_host, n, out_w, force_general).kind != 0 && n <= kLbInline;
+}
 
-hipError_t launch_letterbox_s2d(const LetterboxDev* geom_dev, const LetterboxDev* geom_host, int n, int out_h, int out_w,
-                                uint16_t* out, int f16, bool force_general, hipStream_t s) {
+static LetterboxDev lb_unused(const LetterboxDev*) { return LetterboxDev{nullptr, 0, 0, 0, 0, 0, 0, 0, 1.0, 1.0}; }
+static LetterboxWin lb_unused(const LetterboxWin*) { return LetterboxWin{lb_unused((const LetterboxDev*)nullptr), 0, 0, 0}; }
+static void lb_launch(const LbPlan& plan, dim3 grid, hipStream_t s, const LetterboxGeom& geom, int out_h, int out_w, uint16_t* out, int f16) {
+    if (plan.kind == 1) hipLaunchKernelGGL(letterbox_copy_s2d_kernel, grid, dim3(256), plan.lds, s, geom, out_h, out_w, out, f16);
+    else hipLaunchKernelGGL(letterbox_linear_s2d_kernel, grid, dim3(256), 0, s, geom, out_h, out_w, out, f16);
+}
+static void lb_launch(const LbPlan& plan, dim3 grid, hipStream_t s, const LetterboxWinGeom& geom, int out_h, int out_w, uint16_t* out, int f16) {
+    if (plan.kind == 1) hipLaunchKernelGGL(letterbox_win_copy_s2d_kernel, grid, dim3(256), plan.lds, s, geom, out_h, out_w, out, f16);
+    else hipLaunchKernelGGL(letterbox_win_linear_s2d_kernel, grid, dim3(256), 0, s, geom, out_h, out_w, out, f16);
+}
+static void lb_launch_general(dim3 grid, hipStream_t s, const LetterboxDev* geom, int out_h, int out_w, uint16_t* out, int f16) {
+    hipLaunchKernelGGL(letterbox_s2d_kernel, grid, dim3(256), 0, s, geom, out_h, out_w, out, f16);
+}
+static void lb_launch_general(dim3 grid, hipStream_t s, const LetterboxWin* geom, int out_h, int out_w, uint16_t* out, int f16) {
+    hipLaunchKernelGGL(letterbox_win_s2d_kernel, grid, dim3(256), 0, s, geom, out_h, out_w, out, f16);
+}
+
+template <class G>
+static hipError_t launch_letterbox_s2d_t(const G* geom_dev, const G* geom_host, int n, int out_h, int out_w,
+                                         uint16_t* out, int f16, bool force_general, hipStream_t s) {
     const int W2 = out_w / 2, H2 = out_h / 2;
     const LbPlan plan = lb_plan(geom_host, n, out_w, force_general);
     if (plan.kind != 0) {
-        LetterboxGeom geom;
+        typename LbGeomOf<G>::type geom;
         geom.ptr = geom_dev;
         if (n <= kLbInline) {
             geom.ptr = nullptr;
             for (int i = 0; i < n; ++i) geom.inl[i] = geom_host[i];
-            for (int i = n; i < kLbInline; ++i) geom.inl[i] = LetterboxDev{nullptr, 0, 0, 0, 0, 0, 0, 0, 1.0, 1.0};
+            for (int i = n; i < kLbInline; ++i) geom.inl[i] = lb_unused(geom_host);
         }
-        if (plan.kind == 1) hipLaunchKernelGGL(letterbox_copy_s2d_kernel, dim3(H2, n), dim3(256), plan.lds, s, geom, out_h, out_w, out, f16);
-        else hipLaunchKernelGGL(letterbox_linear_s2d_kernel, dim3((W2 + 255) / 256, (H2 + kLbRows - 1) / kLbRows, n), dim3(256), 0, s, geom, out_h, out_w, out, f16);
+        lb_launch(plan, plan.kind == 1 ? dim3(H2, n) : dim3((W2 + 255) / 256, (H2 + kLbRows - 1) / kLbRows, n), s, geom, out_h, out_w, out, f16);
         return hipGetLastError();
     }
-    dim3 grid((W2 + 255) / 256, H2, n);
-    hipLaunchKernelGGL(letterbox_s2d_kernel, grid, dim3(256), 0, s, geom_dev, out_h, out_w, out, f16);
+    lb_launch_general(dim3((W2 + 255) / 256, H2, n), s, geom_dev, out_h, out_w, out, f16);
     return hipGetLastError();
+}
+hipError_t launch_letterbox_s2d(const LetterboxDev* geom_dev, const LetterboxDev* geom_host, int n, int out_h, int out_w,
+                                uint16_t* out, int f16, bool force_general, hipStream_t s) {
+    return launch_letterbox_s2d_t(geom_dev, geom_host, n, out_h, out_w, out, f16, force_general, s);
+}
+hipError_t launch_letterbox_s2d(const LetterboxWin* geom_dev, const LetterboxWin* geom_host, int n, int out_h, int out_w,
+                                uint16_t* out, int f16, bool force_general, hipStream_t s) {
+    return launch_letterbox_s2d_t(geom_dev, geom_host, n, out_h, out_w, out, f16, force_general, s);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -353,6 +353,86 @@ class HIPDetector:
         self._format_group(group_items, det_all, counts, h, w, results, detection_threshold)
 
     # -----------------------------------------------------------------------------------
+    def generate_detections_for_tiles(self, img_original, tile_origins, tile_size, tile_ids=None,
+                                      detection_threshold=0.00001, image_size=None, augment=False, verbose=False):
+        """
+        Tiled inference on one large image (the device half of run_tiled_inference.py): the image is uploaded ONCE and
+        every tile is cut out of it, letterboxed and normalised by the windowed letterbox kernels
+        (mdhip_preprocess_windows) -- no tile is ever materialised on the host.
+
+        img_original: PIL image or HWC uint8 array.  tile_origins: [(x, y)] upper-left corners.  tile_size: (w, h).
+        tile_ids: the 'file' of each result (default '<x>_<y>', zero-padded to four digits).
+        Returns one result dict per tile, the very dicts generate_detections_one_batch returns for the list of crops
+        img[y:y + h, x:x + w]: a tile counts as an image of size (h, w).  Tiles are processed in chunks of max_batch; an
+        exception in a chunk marks that chunk's tiles 'inference failure'.
+        """
+        if detection_threshold is None:
+            detection_threshold = 0.0
+        if self._ctx is None:
+            raise RuntimeError('this HIPDetector was created with preprocess_only')
+        self._check_augment(augment)
+        img = img_original if isinstance(img_original, np.ndarray) else np.asarray(img_original)
+        if img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
+            raise ValueError('expected an HxWx3 uint8 RGB image, got {} {}'.format(img.shape, img.dtype))
+        img = np.ascontiguousarray(img)
+        H, W = img.shape[:2]
+        tw, th = int(tile_size[0]), int(tile_size[1])
+        origins = [(int(x), int(y)) for x, y in tile_origins]
+        for x, y in origins:
+            if x < 0 or y < 0 or tw < 1 or th < 1 or x + tw > W or y + th > H:
+                raise ValueError('tile ({}, {}) of size {}x{} does not lie inside the {}x{} image'.format(x, y, tw, th, W, H))
+        if tile_ids is None:
+            tile_ids = ['{}_{}'.format(str(x).zfill(4), str(y).zfill(4)) for x, y in origins]
+        if len(tile_ids) != len(origins):
+            raise ValueError('Length mismatch: {} tile origins, {} tile ids'.format(len(origins), len(tile_ids)))
+        if len(origins) == 0:
+            return []
+        # geometry of a tile = geometry of an image of the tile's size (the views share the parent's pixels: nothing is copied)
+        views = [img[y:y + th, x:x + tw] for x, y in origins]
+        results, shape_groups = self._prepare_batch(views, list(tile_ids), image_size, verbose)
+        if not shape_groups:
+            return results
+        import torch
+        dev = torch.device('cuda', _device_ordinal(self.device))
+        pitch, total = W * 3, H * W * 3
+        with torch.cuda.device(dev):
+            parent = torch.empty(total, dtype=torch.uint8, device=dev)      # exactly the image: `readable` is exact
+            parent.copy_(torch.from_numpy(img.reshape(-1)))
+            torch.cuda.synchronize(dev)
+            base = parent.data_ptr()
+            try:
+                for shape, items in shape_groups.items():                   # (one group: all tiles have one size)
+                    for start in range(0, len(items), self.max_batch):
+                        chunk = items[start:start + self.max_batch]
+                        try:
+                            self._process_tile_chunk(chunk, origins, base, pitch, total, results, detection_threshold, augment)
+                        except Exception as e:
+                            print('Warning: tile inference failed for shape {}: {}'.format(shape, str(e)))
+                            for original_idx, _, current_id in chunk:
+                                results[original_idx] = {'file': current_id, 'detections': None, 'failure': FAILURE_INFER}
+            finally:
+                torch.cuda.synchronize(dev)                                 # nothing reads `parent` once it is released
+        return results
+
+    def _process_tile_chunk(self, chunk, origins, base, pitch, total, results, detection_threshold, augment):
+        """_process_batch_group for windows of the device image at `base` (row pitch `pitch`, `total` bytes)"""
+        h, w = chunk[0][1]['img_processed'].shape[:2]
+        n = len(chunk)
+        offs = [origins[idx][1] * pitch + origins[idx][0] * 3 for idx, _, _ in chunk]
+        ctx = self._ctx
+        ctx.preprocess_windows([base + o for o in offs], [info['img_processed'].geometry for _, info, _ in chunk],
+                               [pitch] * n, [total - o for o in offs], h, w)
+        if self._fp8_pending:
+            ctx.calibrate(n, h, w)
+            self._fp8_calibrated()
+        if augment:
+            ctx.forward_tta(n, h, w)
+        else:
+            ctx.forward(n, h, w)
+        det_all, counts = ctx.nms(n, detection_threshold, self._nms_iou(), max_det=300)
+        self._format_group(chunk, det_all, counts, h, w, results, detection_threshold)
+
+    # -----------------------------------------------------------------------------------
     # Pipelined variant of generate_detections_one_batch for the batch driver (feed.py): the device work
     # of a batch is enqueued on a private stream and the call returns; finish_batch() waits for it and
     # formats.  Host images are copied to the device on a copy stream into one of two staging buffers

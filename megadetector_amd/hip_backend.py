@@ -166,6 +166,27 @@ class HipContext:
         self._check(self.lib.mdhip_preprocess(self.h, C.cast(ptrs, C.POINTER(C.c_void_p)), g, n, int(out_h), int(out_w),
                                               C.c_void_p(stream)), 'mdhip_preprocess')
 
+    def preprocess_windows(self, ptrs, geoms, pitches, readable, out_h, out_w, stream=0):
+        """
+        preprocess() for windows of larger device images (tiles): nothing is copied, the kernels read the parent in place.
+        ptrs:     integer device pointers to each window's first pixel
+        geoms:    as for preprocess(); src_h / src_w are the window's size
+        pitches:  bytes between two rows of each window's parent image
+        readable: bytes readable from each pointer to the end of its parent allocation
+        """
+        n = len(ptrs)
+        if not (len(geoms) == len(pitches) == len(readable) == n):
+            raise ValueError('ptrs, geoms, pitches and readable must have one entry per window')
+        p = (C.c_void_p * n)(*[int(v) for v in ptrs])
+        g = (_lib.mdhip_letterbox * n)()
+        for i, q in enumerate(geoms):
+            g[i].src_h, g[i].src_w, g[i].resized_h, g[i].resized_w, g[i].top, g[i].left = [int(v) for v in q[:6]]
+            g[i].interp = int(q[6]) if len(q) > 6 else 0
+        pt = (C.c_int64 * n)(*[int(v) for v in pitches])
+        rd = (C.c_int64 * n)(*[int(v) for v in readable])
+        self._check(self.lib.mdhip_preprocess_windows(self.h, C.cast(p, C.POINTER(C.c_void_p)), g, pt, rd, n, int(out_h), int(out_w),
+                                                      C.c_void_p(stream)), 'mdhip_preprocess_windows')
+
     def forward(self, n, h, w, stream=0):
         self._check(self.lib.mdhip_forward(self.h, int(n), int(h), int(w), C.c_void_p(stream)), 'mdhip_forward')
 
