@@ -193,6 +193,30 @@ int mdhip_preprocess_windows(mdhip_ctx* ctx, const uint8_t* const* windows, cons
  * Leaves (n, n_anchors, 5+nc) fp32 predictions in a device buffer of the context (4+nc for an anchor-free model). */
 int mdhip_forward(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream);
 
+/* GPU half of JPEG decoding (the reference decodes with PIL on the host, visualization_utils.py:103-175; the host half here is
+ * libmdjpeg.so, include/mdjpeg.h): rebuilds from the QUANTISED DCT coefficients of a baseline JPEG the RGB pixels that
+ * Pillow / libjpeg-turbo produce, bit for bit -- de-quantisation, the "islow" integer inverse DCT, "fancy" chroma
+ * upsampling, fixed-point YCbCr -> RGB, and the EXIF rotation -- into device memory that mdhip_preprocess then reads.
+ *   coef        DEVICE pointer, 16-byte aligned: the planes of Y[, Cb, Cr] one behind the other exactly as mdjpeg_decode
+ *               writes them (plane c: [blocks_h[c]][blocks_w[c]][64], natural order within a block)
+ *   width, height   of the image before rotation;  components 1 (grayscale: R = G = B = Y) or 3
+ *   h_samp, v_samp  luma sampling factors: (1, 1) 4:4:4 and grayscale, (2, 1) 4:2:2, (2, 2) 4:2:0; chroma is 1 x 1
+ *   blocks_w / blocks_h   plane sizes in 8x8 blocks (whole MCUs: mdjpeg_info says them)
+ *   quant       quantisation table of each component, natural order
+ *   rotation    0 / 90 / 180 / 270 counter-clockwise, as PIL's rotate(angle, expand = True) turns
+ * out_rgb[i]: device memory for the rotated image, H x W x 3 bytes (W x H x 3 for 90 / 270), written completely.
+ * The u8 component planes between the two kernels live in scratch memory of the context that grows on demand (the device
+ * is synchronised when it does): keep all mdhip_jpeg_reconstruct calls of one context on ONE stream. */
+typedef struct {
+    const int16_t* coef;
+    int32_t  width, height, components;
+    int32_t  h_samp, v_samp;
+    int32_t  blocks_w[3], blocks_h[3];
+    int32_t  rotation;
+    uint16_t quant[3][64];
+} mdhip_jpeg_image;
+int mdhip_jpeg_reconstruct(mdhip_ctx* ctx, const mdhip_jpeg_image* images, int n, uint8_t* const* out_rgb, void* hip_stream);
+
 /* Test-time augmentation: replaces mdhip_forward for `model(batch, augment=True)` (reference
  * pytorch_detector.py:1313 -> yolov5 _forward_augment): three passes over the batch that mdhip_preprocess
  * left in the context -- scale 1, scale 0.83 left-right flipped, scale 0.67 (bilinear, padded with 0.447 to

@@ -1,0 +1,66 @@
+/*
+ * mdjpeg.h -- C ABI of libmdjpeg.so: the host half of the GPU JPEG feed ("GPU JPEG reconstruction").
+ *
+ * A loader process parses a baseline JPEG and Huffman-decodes its scan to QUANTISED DCT coefficients; everything after
+ * that (de-quantisation, inverse DCT, chroma upsampling, colour conversion, EXIF rotation) runs on the GPU
+ * (mdhip_jpeg_reconstruct, include/mdhip.h).  This library is plain C++ and links nothing of HIP: the loader processes
+ * never open the GPU.
+ *
+ * The decoder never guesses.  Whatever is not a clean stream of a supported kind is an error code, and the caller decodes
+ * that file with its ordinary decoder, so every warning, failure string and partial image stays that decoder's.
+ */
+#ifndef MDJPEG_H
+#define MDJPEG_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define MDJPEG_OK            0
+#define MDJPEG_EINVAL       -1   /* bad argument                                                              */
+#define MDJPEG_EUNSUPPORTED -2   /* a JPEG (or not) of a kind this decoder leaves to the caller: info.reason  */
+#define MDJPEG_ECORRUPT     -3   /* the stream is not clean (see mdjpeg_decode): info.reason                  */
+#define MDJPEG_ECAPACITY    -4   /* the coefficient planes do not fit `capacity`                              */
+
+typedef struct {
+    int32_t  width, height;          /* image size in pixels (before any EXIF rotation)                          */
+    int32_t  components;             /* 1 (grayscale) or 3 (YCbCr)                                               */
+    int32_t  h_samp[3], v_samp[3];   /* sampling factors; (1, 1) for grayscale whatever the file says            */
+    int32_t  restart_interval;       /* MCUs between restart markers, 0 = none                                   */
+    int32_t  mcus_x, mcus_y;         /* MCUs per row / column                                                    */
+    int32_t  blocks_w[3], blocks_h[3]; /* size of each component's plane in 8x8 blocks (whole MCUs)              */
+    int64_t  plane_offset[3];        /* first coefficient of each plane, in int16 units from the buffer's start  */
+    int64_t  coef_count;             /* int16 values mdjpeg_decode writes: sum of blocks_w * blocks_h * 64       */
+    uint16_t quant[3][64];           /* quantisation table of each COMPONENT, natural (row-major) order          */
+    int32_t  supported;              /* 1: mdjpeg_decode takes this file                                         */
+    char     reason[100];            /* why not (supported == 0), or what the decoder met (MDJPEG_ECORRUPT)      */
+} mdjpeg_info;
+
+/* Walks the markers up to the first SOS.  Returns MDJPEG_OK with info->supported = 1, or MDJPEG_EUNSUPPORTED with
+ * info->supported = 0 and info->reason set (width / height / components are filled in as far as they were read).
+ * Supported: 8-bit sequential Huffman (SOF0, SOF1 with 8-bit samples), ONE interleaved scan, grayscale or three
+ * components YCbCr with chroma 1x1 and luma 1x1 / 2x1 / 2x2 (4:4:4, 4:2:2, 4:2:0), with or without restart intervals,
+ * any size.  Not supported: progressive, lossless and hierarchical frames, arithmetic coding, 12-bit samples, four
+ * components (CMYK / YCCK), an Adobe marker with transform 0 (RGB stored as such), any other sampling (4:4:0, 4:1:1 ...),
+ * several scans, anything that does not parse. */
+int mdjpeg_parse(const uint8_t* data, size_t size, mdjpeg_info* info);
+
+/* Huffman-decodes the scan into coef[0 .. info->coef_count): one plane per component, blocks in raster order, the 64
+ * values of a block in natural (row-major) order, still quantised.  `capacity` counts int16 values; nothing is written at
+ * or beyond coef[capacity].  Parses the file itself and fills *info as mdjpeg_parse does.
+ * MDJPEG_ECORRUPT, never a guess, for: an undefined Huffman code, a DC / AC magnitude category a baseline file cannot
+ * hold, a coefficient index past 63, a zero run that leaves the block, a block whose de-quantised coefficients carry
+ * more energy than 64 samples of 8 bits can have (plus the quantisation error), data that end early or bytes left
+ * over in front of a marker, a restart marker that is missing or out of sequence, a scan not followed by EOI at once.
+ * On any error the contents of coef are unspecified. */
+int mdjpeg_decode(const uint8_t* data, size_t size, mdjpeg_info* info, int16_t* coef, size_t capacity);
+
+const char* mdjpeg_version(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* MDJPEG_H */

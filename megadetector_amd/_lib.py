@@ -42,6 +42,12 @@ class mdhip_letterbox(C.Structure):
                 ('resized_w', C.c_int32), ('top', C.c_int32), ('left', C.c_int32), ('interp', C.c_int32)]
 
 
+class mdhip_jpeg_image(C.Structure):
+    _fields_ = [('coef', C.c_void_p), ('width', C.c_int32), ('height', C.c_int32), ('components', C.c_int32),
+                ('h_samp', C.c_int32), ('v_samp', C.c_int32), ('blocks_w', C.c_int32 * 3), ('blocks_h', C.c_int32 * 3),
+                ('rotation', C.c_int32), ('quant', (C.c_uint16 * 64) * 3)]
+
+
 class mdhip_op_info(C.Structure):
     _fields_ = [('name', C.c_char * 48), ('kind', C.c_int32), ('layer', C.c_int32),
                 ('m', C.c_int32), ('n', C.c_int32), ('k', C.c_int32),
@@ -64,6 +70,7 @@ SYMBOLS = {
     'mdhip_preprocess_windows': (C.c_int, [_P, C.POINTER(_P), C.POINTER(mdhip_letterbox), C.POINTER(C.c_int64),
                                            C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_forward': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
+    'mdhip_jpeg_reconstruct': (C.c_int, [_P, C.POINTER(mdhip_jpeg_image), C.c_int, C.POINTER(_P), _P]),
     'mdhip_forward_tta': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_last_num_anchors': (C.c_int, [_P]),
     'mdhip_calibrate': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),

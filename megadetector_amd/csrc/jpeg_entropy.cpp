@@ -1,0 +1,436 @@
+// libmdjpeg.so: JPEG marker parser and Huffman entropy decoder of the loader processes (C ABI: include/mdjpeg.h).
+//
+// Plain C++17, host compiler, no HIP: a loader process that maps this library does not open the GPU.  The output is the
+// scan's QUANTISED coefficients; de-quantisation, IDCT, upsampling, colour conversion and rotation are
+// mdhip_jpeg_reconstruct (jpeg_kernels.cpp).  Every irregularity is an error code -- the caller then decodes the file
+// with PIL, so that no behaviour of the ordinary path (warnings, partial images, failure strings) is restated here.
+//
+// Decoder: 64-bit left-aligned bit buffer refilled eight bytes at a time while no 0xFF is in sight; one 11-bit look-ahead
+// per symbol that yields code length and run/size together; the canonical maxcode walk for the rare longer codes.
+
+#include "../../include/mdjpeg.h"
+
+#include <cstdio>
+#include <cstring>
+
+namespace {
+
+constexpr int LOOK = 11;
+
+const uint8_t ZIGZAG[64] = {
+    0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+    41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+    30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+struct Huff {
+    bool     defined = false;
+    uint16_t look[1 << LOOK];      // (length << 8) | symbol, 0 = longer than LOOK bits or undefined
+    int32_t  maxcode[18];          // largest code of each length, -1 = none
+    int32_t  valoff[17];           // index of the first symbol of a length minus its first code
+    uint8_t  vals[256];
+};
+
+struct Parsed {
+    Huff     dc[4], ac[4];
+    uint16_t qt[4][64];            // natural order
+    bool     qt_defined[4] = {false, false, false, false};
+    int      comp_id[4], comp_tq[4], comp_td[4], comp_ta[4];
+    size_t   scan_begin = 0;       // first byte of entropy-coded data
+};
+
+int fail(mdjpeg_info* info, int code, const char* why) {
+    snprintf(info->reason, sizeof(info->reason), "%s", why);
+    info->supported = 0;
+    return code;
+}
+
+// Builds the decoding tables of one DHT entry; false when the counts do not describe a prefix code.
+bool build_huff(Huff& h, const uint8_t* counts, const uint8_t* vals, int nvals) {
+    memset(h.look, 0, sizeof(h.look));
+    memcpy(h.vals, vals, nvals);
+    int code = 0, k = 0;
+    for (int len = 1; len <= 16; ++len) {
+        int n = counts[len - 1];
+        h.valoff[len] = k - code;
+        if (n) {
+            if (code + n > (1 << len)) return false;
+            if (len <= LOOK) {
+                for (int i = 0; i < n; ++i) {
+                    int first = (code + i) << (LOOK - len);
+                    for (int j = 0; j < (1 << (LOOK - len)); ++j) h.look[first + j] = uint16_t((len << 8) | vals[k + i]);
+                }
+            }
+            k += n;
+            code += n;
+            h.maxcode[len] = code - 1;
+        } else {
+            h.maxcode[len] = -1;
+        }
+        code <<= 1;
+    }
+    h.maxcode[17] = 0x7fffffff;
+    h.defined = true;
+    return true;
+}
+
+inline unsigned be16(const uint8_t* p) { return (unsigned(p[0]) << 8) | p[1]; }
+
+int parse_headers(const uint8_t* d, size_t size, mdjpeg_info* info, Parsed& P) {
+    memset(info, 0, sizeof(*info));
+    if (size < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail(info, MDJPEG_EUNSUPPORTED, "not a JPEG file (no SOI marker)");
+    size_t p = 2;
+    bool have_sof = false, jfif = false, adobe = false;
+    int adobe_transform = -1;
+    for (;;) {
+        if (p + 4 > size) return fail(info, MDJPEG_EUNSUPPORTED, "file ends inside the headers");
+        if (d[p] != 0xFF) return fail(info, MDJPEG_EUNSUPPORTED, "bytes between marker segments");
+        while (p < size && d[p] == 0xFF) ++p;                        // fill bytes in front of a marker are legal here
+        if (p + 3 > size) return fail(info, MDJPEG_EUNSUPPORTED, "file ends inside the headers");
+        int m = d[p++];
+        if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;        // parameterless
+        if (m == 0xD9) return fail(info, MDJPEG_EUNSUPPORTED, "EOI before any scan");
+        if (m == 0x00) return fail(info, MDJPEG_EUNSUPPORTED, "bytes between marker segments");
+        size_t len = be16(d + p);
+        if (len < 2 || p + len > size) return fail(info, MDJPEG_EUNSUPPORTED, "marker segment runs past the end of the file");
+        const uint8_t* s = d + p + 2;
+        size_t n = len - 2;
+        switch (m) {
+        case 0xC0: case 0xC1: {
+            if (have_sof) return fail(info, MDJPEG_EUNSUPPORTED, "more than one frame header");
+            if (n < 6) return fail(info, MDJPEG_EUNSUPPORTED, "short frame header");
+            int prec = s[0];
+            info->height = int(be16(s + 1));
+            info->width = int(be16(s + 3));
+            info->components = s[5];
+            if (prec != 8) return fail(info, MDJPEG_EUNSUPPORTED, "sample precision is not 8 bits");
+            if (info->width < 1 || info->height < 1) return fail(info, MDJPEG_EUNSUPPORTED, "frame header without a size (DNL)");
+            if (info->components == 4) return fail(info, MDJPEG_EUNSUPPORTED, "four components (CMYK / YCCK)");
+            if (info->components != 1 && info->components != 3) return fail(info, MDJPEG_EUNSUPPORTED, "neither one nor three components");
+            if (n != size_t(6 + 3 * info->components)) return fail(info, MDJPEG_EUNSUPPORTED, "frame header of the wrong length");
+            for (int c = 0; c < info->components; ++c) {
+                P.comp_id[c] = s[6 + 3 * c];
+                info->h_samp[c] = s[7 + 3 * c] >> 4;
+                info->v_samp[c] = s[7 + 3 * c] & 15;
+                P.comp_tq[c] = s[8 + 3 * c];
+                if (P.comp_tq[c] > 3 || info->h_samp[c] < 1 || info->h_samp[c] > 4 || info->v_samp[c] < 1 || info->v_samp[c] > 4)
+                    return fail(info, MDJPEG_EUNSUPPORTED, "bad component specification");
+            }
+            have_sof = true;
+            break;
+        }
+        case 0xC2: return fail(info, MDJPEG_EUNSUPPORTED, "progressive JPEG (SOF2)");
+        case 0xC3: case 0xC5: case 0xC6: case 0xC7:
+            return fail(info, MDJPEG_EUNSUPPORTED, "lossless or hierarchical JPEG");
+        case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF: case 0xCC:
+            return fail(info, MDJPEG_EUNSUPPORTED, "arithmetic coding");
+        case 0xC4: {                                                                 // DHT
+            while (n > 0) {
+                if (n < 17) return fail(info, MDJPEG_EUNSUPPORTED, "short Huffman table");
+                int tc = s[0] >> 4, th = s[0] & 15, total = 0;
+                for (int i = 0; i < 16; ++i) total += s[1 + i];
+                if (tc > 1 || th > 3 || total > 256 || n < size_t(17 + total)) return fail(info, MDJPEG_EUNSUPPORTED, "bad Huffman table");
+                if (!build_huff(tc ? P.ac[th] : P.dc[th], s + 1, s + 17, total))
+                    return fail(info, MDJPEG_EUNSUPPORTED, "Huffman table is not a prefix code");
+                s += 17 + total;
+                n -= 17 + total;
+            }
+            break;
+        }
+        case 0xDB: {                                                                 // DQT
+            while (n > 0) {
+                int pq = s[0] >> 4, tq = s[0] & 15;
+                size_t need = 1 + (pq ? 128 : 64);
+                if (pq > 1 || tq > 3 || n < need) return fail(info, MDJPEG_EUNSUPPORTED, "bad quantisation table");
+                for (int i = 0; i < 64; ++i)
+                    P.qt[tq][ZIGZAG[i]] = pq ? uint16_t(be16(s + 1 + 2 * i)) : uint16_t(s[1 + i]);
+                P.qt_defined[tq] = true;
+                s += need;
+                n -= need;
+            }
+            break;
+        }
+        case 0xDD:
+            if (n != 2) return fail(info, MDJPEG_EUNSUPPORTED, "bad restart interval segment");
+            info->restart_interval = int(be16(s));
+            break;
+        case 0xE0:
+            if (n >= 5 && memcmp(s, "JFIF\0", 5) == 0) jfif = true;
+            break;
+        case 0xEE:
+            if (n >= 12 && memcmp(s, "Adobe", 5) == 0) { adobe = true; adobe_transform = s[11]; }
+            break;
+        case 0xDA: {                                                                 // SOS
+            if (!have_sof) return fail(info, MDJPEG_EUNSUPPORTED, "scan before the frame header");
+            int ns = n >= 1 ? s[0] : 0;
+            if (ns != info->components) return fail(info, MDJPEG_EUNSUPPORTED, "several scans (scan does not hold every component)");
+            if (n != size_t(4 + 2 * ns)) return fail(info, MDJPEG_EUNSUPPORTED, "scan header of the wrong length");
+            for (int c = 0; c < ns; ++c) {
+                if (s[1 + 2 * c] != P.comp_id[c]) return fail(info, MDJPEG_EUNSUPPORTED, "scan components not in frame order");
+                P.comp_td[c] = s[2 + 2 * c] >> 4;
+                P.comp_ta[c] = s[2 + 2 * c] & 15;
+                if (P.comp_td[c] > 3 || P.comp_ta[c] > 3 || !P.dc[P.comp_td[c]].defined || !P.ac[P.comp_ta[c]].defined)
+                    return fail(info, MDJPEG_EUNSUPPORTED, "scan names a Huffman table that was not defined");
+                if (!P.qt_defined[P.comp_tq[c]]) return fail(info, MDJPEG_EUNSUPPORTED, "component names a quantisation table that was not defined");
+            }
+            if (s[1 + 2 * ns] != 0 || s[2 + 2 * ns] != 63 || s[3 + 2 * ns] != 0)
+                return fail(info, MDJPEG_EUNSUPPORTED, "scan is not a full sequential scan");
+            if (ns == 3) {
+                if (adobe && adobe_transform != 1) return fail(info, MDJPEG_EUNSUPPORTED, "Adobe marker with transform 0 (not YCbCr)");
+                if (!adobe && !jfif && P.comp_id[0] == 'R' && P.comp_id[1] == 'G' && P.comp_id[2] == 'B')
+                    return fail(info, MDJPEG_EUNSUPPORTED, "components named R, G, B (not YCbCr)");
+                bool ok = info->h_samp[1] == 1 && info->v_samp[1] == 1 && info->h_samp[2] == 1 && info->v_samp[2] == 1 &&
+                          ((info->h_samp[0] == 1 && info->v_samp[0] == 1) || (info->h_samp[0] == 2 && info->v_samp[0] == 1) ||
+                           (info->h_samp[0] == 2 && info->v_samp[0] == 2));
+                if (!ok) return fail(info, MDJPEG_EUNSUPPORTED, "chroma sampling other than 4:4:4, 4:2:2 and 4:2:0");
+            } else {
+                info->h_samp[0] = info->v_samp[0] = 1;             // a one-component scan is never interleaved
+            }
+            int mh = info->h_samp[0], mv = info->v_samp[0];
+            info->mcus_x = (info->width + 8 * mh - 1) / (8 * mh);
+            info->mcus_y = (info->height + 8 * mv - 1) / (8 * mv);
+            int64_t off = 0;
+            for (int c = 0; c < ns; ++c) {
+                info->blocks_w[c] = info->mcus_x * info->h_samp[c];
+                info->blocks_h[c] = info->mcus_y * info->v_samp[c];
+                info->plane_offset[c] = off;
+                off += int64_t(info->blocks_w[c]) * info->blocks_h[c] * 64;
+                memcpy(info->quant[c], P.qt[P.comp_tq[c]], sizeof(info->quant[c]));
+            }
+            info->coef_count = off;
+            P.scan_begin = p + len;
+            info->supported = 1;
+            return MDJPEG_OK;
+        }
+        default:
+            break;                                                                   // APPn, COM, ...: skipped
+        }
+        p += len;
+    }
+}
+
+// ---- bit reader over entropy-coded data ---------------------------------------------------------------------------
+struct Bits {
+    const uint8_t* p;
+    const uint8_t* end;
+    uint64_t acc = 0;        // next bit = bit 63
+    int      n = 0;          // valid bits in acc
+    bool     stopped = false;   // a marker or the end of the data is next: nothing more to read
+
+    inline void fill() {
+        if (n > 56 || stopped) return;
+        if (end - p >= 8) {
+            uint64_t w;
+            memcpy(&w, p, 8);
+            w = __builtin_bswap64(w);
+            uint64_t t = ~w;                                  // a 0xFF byte is a zero byte of t
+            if (!((t - 0x0101010101010101ull) & ~t & 0x8080808080808080ull)) {
+                int k = (64 - n) >> 3;
+                acc |= (w >> (64 - 8 * k)) << (64 - n - 8 * k);
+                p += k;
+                n += 8 * k;
+                return;
+            }
+        }
+        while (n <= 56) {
+            if (p >= end) { stopped = true; return; }
+            unsigned b = *p;
+            if (b == 0xFF) {
+                if (p + 1 >= end) { stopped = true; return; }
+                if (p[1] != 0) { stopped = true; return; }     // a marker: stay in front of it
+                p += 2;
+            } else {
+                ++p;
+            }
+            acc |= uint64_t(b) << (56 - n);
+            n += 8;
+        }
+    }
+    inline unsigned peek(int k) const { return unsigned(acc >> (64 - k)); }
+    inline void skip(int k) { acc <<= k; n -= k; }
+};
+
+struct Corrupt { const char* why; };
+
+// one Huffman symbol; returns -1 when the code is undefined or the data end inside it
+inline int decode_symbol(Bits& b, const Huff& h) {
+    unsigned e = h.look[b.peek(LOOK)];
+    if (e) {
+        int len = int(e >> 8);
+        if (len > b.n) return -1;
+        b.skip(len);
+        return int(e & 255);
+    }
+    unsigned v = b.peek(16);
+    for (int len = LOOK + 1; len <= 16; ++len) {
+        int code = int(v >> (16 - len));
+        if (code <= h.maxcode[len]) {
+            if (len > b.n) return -1;
+            b.skip(len);
+            return h.vals[(code + h.valoff[len]) & 255];
+        }
+    }
+    return -1;
+}
+
+inline int receive_extend(Bits& b, int s) {
+    int v = int(b.peek(s));
+    b.skip(s);
+    return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
+}
+
+const char* decode_block(Bits& b, const Huff& dc, const Huff& ac, const uint16_t* q, int64_t emax, int& pred, int16_t* blk) {
+    memset(blk, 0, 64 * sizeof(int16_t));
+    if (b.n < 32) b.fill();                          // a code (<= 16 bits) and its magnitude bits (<= 11) fit 32 bits
+    int s = decode_symbol(b, dc);
+    if (s < 0) return "undefined DC code or data end early";
+    if (s > 11) return "DC magnitude category above 11";
+    if (s) {
+        if (s > b.n) return "data end early";
+        pred += receive_extend(b, s);
+    }
+    if (pred < -32768 || pred > 32767) return "DC value out of range";
+    blk[0] = int16_t(pred);
+    int64_t v0 = int64_t(pred) * q[0];
+    int64_t energy = v0 * v0;
+    for (int k = 1; k < 64;) {
+        if (b.n < 32) b.fill();
+        int rs = decode_symbol(b, ac);
+        if (rs < 0) return "undefined AC code or data end early";
+        int r = rs >> 4;
+        s = rs & 15;
+        if (s) {
+            k += r;
+            if (k > 63) return "coefficient index past 63";
+            if (s > 10) return "AC magnitude category above 10";
+            if (s > b.n) return "data end early";
+            int v = receive_extend(b, s);
+            int nat = ZIGZAG[k];
+            blk[nat] = int16_t(v);
+            int64_t dv = int64_t(v) * q[nat];
+            energy += dv * dv;
+            ++k;
+        } else if (r == 15) {
+            k += 16;
+            if (k > 63) return "zero run leaves the block";
+        } else if (r == 0) {
+            break;
+        } else {
+            return "end-of-band code in a sequential scan";
+        }
+    }
+    if (energy > emax) return "block energy beyond what 8-bit samples can hold";
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mdjpeg_parse(const uint8_t* data, size_t size, mdjpeg_info* info) {
+    if (!data || !info) return MDJPEG_EINVAL;
+    Parsed P;
+    return parse_headers(data, size, info, P);
+}
+
+int mdjpeg_decode(const uint8_t* data, size_t size, mdjpeg_info* info, int16_t* coef, size_t capacity) {
+    if (!data || !info || !coef) return MDJPEG_EINVAL;
+    Parsed P;
+    int rc = parse_headers(data, size, info, P);
+    if (rc != MDJPEG_OK) return rc;
+    if (uint64_t(info->coef_count) > uint64_t(capacity)) {
+        snprintf(info->reason, sizeof(info->reason), "coefficient planes need %lld values, capacity is %llu",
+                 (long long)info->coef_count, (unsigned long long)capacity);
+        return MDJPEG_ECAPACITY;
+    }
+    const int nc = info->components;
+    // Parseval: the coefficients of 64 samples in [-128, 127] have a 2-norm of at most 8 * 128; quantisation moves every
+    // coefficient by at most half its step.  A block beyond that was not made from 8-bit samples; it is also the bound
+    // that keeps 16-bit and 32-bit implementations of the inverse DCT in agreement.
+    int64_t emax[3];
+    for (int c = 0; c < nc; ++c) {
+        double qn = 0;
+        for (int i = 0; i < 64; ++i) qn += double(info->quant[c][i]) * info->quant[c][i];
+        double lim = 1024.0 + 0.5 * __builtin_sqrt(qn) + 1.0;
+        if (lim > 2800.0) lim = 2800.0;
+        emax[c] = int64_t(lim * lim);
+    }
+    Bits b;
+    b.p = data + P.scan_begin;
+    b.end = data + size;
+    int pred[3] = {0, 0, 0};
+    const int interval = info->restart_interval;
+    int to_go = interval, next_rst = 0;
+    const int64_t total_mcus = int64_t(info->mcus_x) * info->mcus_y;
+    int64_t done = 0;
+    const char* why = nullptr;
+    for (int my = 0; my < info->mcus_y && !why; ++my) {
+        for (int mx = 0; mx < info->mcus_x && !why; ++mx) {
+            for (int c = 0; c < nc && !why; ++c) {
+                const Huff& hd = P.dc[P.comp_td[c]];
+                const Huff& ha = P.ac[P.comp_ta[c]];
+                const int hs = info->h_samp[c], vs = info->v_samp[c];
+                for (int v = 0; v < vs && !why; ++v)
+                    for (int h = 0; h < hs && !why; ++h) {
+                        int64_t blk = int64_t(my * vs + v) * info->blocks_w[c] + (mx * hs + h);
+                        why = decode_block(b, hd, ha, info->quant[c], emax[c], pred[c], coef + info->plane_offset[c] + blk * 64);
+                    }
+            }
+            if (why) break;
+            ++done;
+            if (interval && --to_go == 0 && done < total_mcus) {
+                // end of a restart interval: only padding bits may be left in front of RSTn
+                b.fill();
+                if (b.n >= 8 || !b.stopped) { why = "bytes left over in front of a restart marker"; break; }
+                if (b.end - b.p < 2 || b.p[0] != 0xFF || b.p[1] != 0xD0 + next_rst) { why = "restart marker missing or out of sequence"; break; }
+                b.p += 2;
+                b.acc = 0; b.n = 0; b.stopped = false;
+                next_rst = (next_rst + 1) & 7;
+                to_go = interval;
+                pred[0] = pred[1] = pred[2] = 0;
+            }
+        }
+    }
+    if (!why) {
+        b.fill();
+        if (b.n >= 8 || !b.stopped) why = "bytes left over behind the last MCU";
+        else if (b.end - b.p < 2 || b.p[0] != 0xFF || b.p[1] != 0xD9) why = "scan is not followed by EOI";
+    }
+    if (why) {
+        snprintf(info->reason, sizeof(info->reason), "%s", why);
+        return MDJPEG_ECORRUPT;
+    }
+    return MDJPEG_OK;
+}
+
+const char* mdjpeg_version(void) { return "mdjpeg 1"; }
+
+}  // extern "C"
+
+#ifdef MDJPEG_ASAN_MAIN
+// `make asan-jpeg`: decodes every file named on the command line into a heap buffer of exactly coef_count values, so that
+// the sanitizers see any access outside it.  Prints one line per file; the exit status is 0 unless a sanitizer fires.
+#include <vector>
+int main(int argc, char** argv) {
+    for (int i = 1; i < argc; ++i) {
+        FILE* f = fopen(argv[i], "rb");
+        if (!f) { printf("%s: cannot open\n", argv[i]); continue; }
+        std::vector<uint8_t> bytes;
+        uint8_t chunk[65536];
+        size_t got;
+        while ((got = fread(chunk, 1, sizeof(chunk), f)) > 0) bytes.insert(bytes.end(), chunk, chunk + got);
+        fclose(f);
+        uint8_t* exact = new uint8_t[bytes.size() ? bytes.size() : 1];          // exact extent: reads past the file are seen
+        memcpy(exact, bytes.data(), bytes.size());
+        mdjpeg_info info;
+        int rc = mdjpeg_parse(exact, bytes.size(), &info);
+        if (rc == MDJPEG_OK) {
+            int16_t* coef = new int16_t[size_t(info.coef_count)];
+            rc = mdjpeg_decode(exact, bytes.size(), &info, coef, size_t(info.coef_count));
+            delete[] coef;
+        }
+        printf("%s: rc %d %s\n", argv[i], rc, info.reason);
+        delete[] exact;
+    }
+    return 0;
+}
+#endif

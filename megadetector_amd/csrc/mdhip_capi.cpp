@@ -155,6 +155,8 @@ struct mdhip_ctx {
     size_t geom_off = 0;
     char* stage = nullptr;        // device staging for host images
     size_t stage_bytes = 0;
+    char* jpeg_planes = nullptr;  // mdhip_jpeg_reconstruct: u8 component planes between the IDCT and the colour kernel
+    size_t jpeg_planes_bytes = 0;
     int last_n = 0, last_h = 0, last_w = 0;
     std::string err;
     // fp8 mode: until every e4m3 tensor has a scale (mdhip_calibrate / mdhip_fp8_set_scales) the forward refuses
@@ -1977,6 +1979,7 @@ void mdhip_destroy(mdhip_ctx* ctx) {
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->warena) (void)hipFree(ctx->warena);
     if (ctx->stage) (void)hipFree(ctx->stage);
+    if (ctx->jpeg_planes) (void)hipFree(ctx->jpeg_planes);
     if (ctx->geom_host) (void)hipHostFree(ctx->geom_host);
     for (int i = 0; i < 4; ++i) if (ctx->geom_ev[i]) (void)hipEventDestroy(ctx->geom_ev[i]);
     if (ctx->input_free) (void)hipEventDestroy(ctx->input_free);
@@ -2105,6 +2108,76 @@ int mdhip_preprocess_windows(mdhip_ctx* ctx, const uint8_t* const* windows, cons
         g[i].reserved = 0;
     }
     return enqueue_letterbox(ctx, g, n, out_h, out_w, s);
+}
+
+int mdhip_jpeg_reconstruct(mdhip_ctx* ctx, const mdhip_jpeg_image* images, int n, uint8_t* const* out_rgb, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!images || !out_rgb) return fail(ctx, MDHIP_EINVAL, "images/out_rgb is NULL");
+    if (n < 1) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<JpegDev> devs(n);
+    size_t planes_bytes = 0;
+    for (int i = 0; i < n; ++i) {
+        const mdhip_jpeg_image& q = images[i];
+        JpegDev& d = devs[i];
+        if (q.width < 1 || q.height < 1 || q.width > 65535 || q.height > 65535 || (q.components != 1 && q.components != 3))
+            return fail(ctx, MDHIP_EINVAL, "jpeg image %d: %dx%d with %d components", i, q.width, q.height, q.components);
+        const bool samp_ok = q.components == 1 ? (q.h_samp == 1 && q.v_samp == 1)
+                                               : ((q.h_samp == 1 && q.v_samp == 1) || (q.h_samp == 2 && q.v_samp == 1) ||
+                                                  (q.h_samp == 2 && q.v_samp == 2));
+        if (!samp_ok) return fail(ctx, MDHIP_EUNSUPPORTED, "jpeg image %d: luma sampling %dx%d", i, q.h_samp, q.v_samp);
+        if (q.rotation != 0 && q.rotation != 90 && q.rotation != 180 && q.rotation != 270)
+            return fail(ctx, MDHIP_EINVAL, "jpeg image %d: rotation %d", i, q.rotation);
+        // the planes must cover what the kernels read: the luma plane the image, a chroma plane its downsampled size
+        long long coef_off = 0;
+        for (int c = 0; c < q.components; ++c) {
+            const int hs = c == 0 ? 1 : q.h_samp, vs = c == 0 ? 1 : q.v_samp;
+            const int need_w = ((q.width + hs - 1) / hs + 7) / 8, need_h = ((q.height + vs - 1) / vs + 7) / 8;
+            if (q.blocks_w[c] < need_w || q.blocks_h[c] < need_h || q.blocks_w[c] > 16384 || q.blocks_h[c] > 16384)
+                return fail(ctx, MDHIP_EINVAL, "jpeg image %d: plane %d of %dx%d blocks for a %dx%d image", i, c, q.blocks_w[c],
+                            q.blocks_h[c], q.width, q.height);
+            d.blocks_w[c] = q.blocks_w[c];
+            d.blocks_h[c] = q.blocks_h[c];
+            d.coef_off[c] = coef_off;
+            d.plane_off[c] = (long long)planes_bytes;
+            coef_off += (long long)q.blocks_w[c] * q.blocks_h[c] * 64;
+            planes_bytes += (size_t)q.blocks_w[c] * q.blocks_h[c] * 64;
+        }
+        for (int c = q.components; c < 3; ++c) d.blocks_w[c] = d.blocks_h[c] = 0, d.coef_off[c] = d.plane_off[c] = 0;
+        planes_bytes = align_up(planes_bytes, 256);
+        if (!q.coef || !out_rgb[i] || ((uintptr_t)q.coef & 15))
+            return fail(ctx, MDHIP_EINVAL, "jpeg image %d: coef / out_rgb is NULL or coef is not 16-byte aligned", i);
+        for (const void* p : {(const void*)q.coef, (const void*)out_rgb[i]}) {
+            hipPointerAttribute_t attr;
+            const hipError_t e = hipPointerGetAttributes(&attr, p);
+            if (e != hipSuccess) (void)hipGetLastError();
+            if (e != hipSuccess || !(attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged))
+                return fail(ctx, MDHIP_EINVAL, "jpeg image %d: coef and out_rgb must be device memory", i);
+        }
+        d.coef = q.coef;
+        d.out = out_rgb[i];
+        d.width = q.width;
+        d.height = q.height;
+        d.components = q.components;
+        d.h_samp = q.h_samp;
+        d.v_samp = q.v_samp;
+        d.rotation = q.rotation;
+        memcpy(d.quant, q.quant, sizeof(d.quant));
+    }
+    if (planes_bytes > ctx->jpeg_planes_bytes) {
+        HIP_TRY(ctx, hipDeviceSynchronize());                  // an earlier call's kernels may still use the old planes
+        if (ctx->jpeg_planes) HIP_TRY(ctx, hipFree(ctx->jpeg_planes));
+        ctx->jpeg_planes = nullptr;
+        ctx->jpeg_planes_bytes = 0;
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->jpeg_planes, planes_bytes));
+        ctx->jpeg_planes_bytes = planes_bytes;
+    }
+    for (int i = 0; i < n; ++i) {
+        devs[i].planes = (uint8_t*)ctx->jpeg_planes;
+        HIP_TRY(ctx, launch_jpeg_reconstruct(devs[i], s));
+    }
+    return MDHIP_OK;
 }
 
 int mdhip_forward(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {

@@ -455,4 +455,22 @@ struct CbfuseArgs {
 };
 hipError_t launch_cbfuse(const CbfuseArgs& a, int f16, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------
+// JPEG reconstruction (jpeg_kernels.cpp): one image, passed to the kernels by value
+// ---------------------------------------------------------------------------------------
+struct JpegDev {
+    const int16_t* coef;          // quantised coefficients, 16-byte aligned; plane c at coef + coef_off[c]: [blocks_h][blocks_w][64]
+    uint8_t* planes;              // scratch: u8 component planes, plane c at planes + plane_off[c], (blocks_h * 8) x (blocks_w * 8)
+    uint8_t* out;                 // the rotated H x W x 3 RGB image
+    long long coef_off[3];
+    long long plane_off[3];
+    int blocks_w[3], blocks_h[3];
+    int width, height, components;
+    int h_samp, v_samp;           // luma sampling factors (chroma 1 x 1)
+    int rotation;                 // 0 / 90 / 180 / 270, counter-clockwise
+    uint16_t quant[3][64];        // natural order
+};
+// de-quantisation + inverse DCT into the planes, then upsampling + colour conversion + rotation into `out`
+hipError_t launch_jpeg_reconstruct(const JpegDev& d, hipStream_t s);
+
 }  // namespace mdhip

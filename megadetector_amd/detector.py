@@ -18,6 +18,9 @@ Differences, all deliberate and documented in DESIGN.md:
     the GPU as well; 'img_original' stays the caller's array and 'resized_shape' carries the resized size.
 augment=True runs yolov5's augmented inference (three scaled / flipped passes) on the device
 (mdhip_forward_tta).
+An image may also arrive as a jpeg_host.CoefficientImage (the quantised DCT coefficients of a baseline JPEG, feed.py
+decode='coefficients'): its pixels are rebuilt on the device (mdhip_jpeg_reconstruct), bit for bit what PIL decodes, and
+never exist on the host; `jpeg_images_reconstructed` counts them.
 """
 
 import json
@@ -27,6 +30,7 @@ import numpy as np
 
 from . import weights_io
 from .constants import (FAILURE_IMAGE_OPEN, FAILURE_INFER, DEFAULT_COMPATIBILITY_MODE)
+from .jpeg_host import CoefficientImage
 from .postprocess import letterbox_geometry, modern_geometry, format_detections
 
 
@@ -109,6 +113,7 @@ class HIPDetector:
         self.half_precision = False
         self.model = None
         self._ctx = None
+        self.jpeg_images_reconstructed = 0      # images whose pixels were rebuilt on the device from JPEG coefficients
         if preprocess_only:
             return                      # never touches HIP: safe in forked producer processes
 
@@ -186,7 +191,9 @@ class HIPDetector:
         """reference pytorch_detector.py:964-1119 ('classic'): geometry only, pixels stay put."""
         result = {'file': image_id}
         img_original_pil = None
-        if not isinstance(img_original, np.ndarray):
+        if isinstance(img_original, CoefficientImage):
+            pass                                # .shape is the decoded, rotated image's; the pixels are made on the device
+        elif not isinstance(img_original, np.ndarray):
             img_original_pil = img_original
             img_original = np.asarray(img_original)
         if img_original.ndim != 3 or img_original.shape[2] != 3 or img_original.dtype != np.uint8:
@@ -304,7 +311,8 @@ class HIPDetector:
         for _, info, _ in group_items:
             ip = info['img_processed']
             if isinstance(ip, LetterboxSpec):
-                images.append(np.ascontiguousarray(info['img_original']))
+                io = info['img_original']
+                images.append(io if isinstance(io, CoefficientImage) else np.ascontiguousarray(io))
                 geoms.append(ip.geometry)
             else:                      # an already letterboxed HWC u8 array
                 ip = np.ascontiguousarray(ip)
@@ -325,6 +333,31 @@ class HIPDetector:
             results[original_idx] = {'file': current_id, 'detections': detections,
                                      'max_detection_conf': max_conf}
 
+    def _reconstruct_jpegs(self, images):
+        """synchronous path: coefficient images -> device RGB images (integer pointers); returns (images, tensors to keep)"""
+        idx = [i for i, im in enumerate(images) if isinstance(im, CoefficientImage)]
+        if not idx:
+            return images, None
+        import torch
+        dev = torch.device('cuda', _device_ordinal(self.device))
+        images = list(images)
+        hold = []
+        with torch.cuda.device(dev):
+            coefs, outs = [], []
+            for i in idx:
+                im = images[i]
+                c = torch.from_numpy(np.array(im.coef, dtype=np.int16)).to(dev)
+                o = torch.empty(int(np.prod(im.shape)), dtype=torch.uint8, device=dev)
+                coefs.append(c)
+                outs.append(o)
+            hold = coefs + outs
+            torch.cuda.synchronize(dev)
+            self._ctx.jpeg_reconstruct([images[i] for i in idx], [c.data_ptr() for c in coefs], [o.data_ptr() for o in outs])
+            for i, o in zip(idx, outs):
+                images[i] = o.data_ptr()
+        self.jpeg_images_reconstructed += len(idx)
+        return images, hold
+
     def _fp8_calibrated(self):
         self._fp8_pending = False
         if self._fp8_scales_file:
@@ -341,6 +374,7 @@ class HIPDetector:
         images, geoms = self._group_inputs(group_items)
         n = len(group_items)
         ctx = self._ctx
+        images, hold = self._reconstruct_jpegs(images)       # (`hold` keeps the device images alive until the NMS has returned)
         ctx.preprocess(images, geoms, h, w)
         if self._fp8_pending:               # fp8 mode, explicit opt-in: this batch calibrates the scales
             ctx.calibrate(n, h, w)
@@ -463,6 +497,12 @@ class HIPDetector:
         for im in images:
             offs.append(total)
             total += (im.nbytes + 255) // 256 * 256
+        # coefficient images: their pixels are rebuilt on the device, behind the copies, into the same staging buffer
+        jpeg_idx = [i for i, im in enumerate(images) if isinstance(im, CoefficientImage)]
+        rgb_offs = {}
+        for i in jpeg_idx:
+            rgb_offs[i] = total
+            total += (int(np.prod(images[i].shape)) + 255) // 256 * 256
         with torch.cuda.device(pl['dev']):
             if pl['stage'][k] is None or pl['stage'][k].numel() < total:
                 if pl['consumed'][k] is not None:
@@ -473,7 +513,7 @@ class HIPDetector:
                 if pl['consumed'][k] is not None:
                     pl['copy_s'].wait_event(pl['consumed'][k])      # the letterbox kernel that read this buffer is done
                 for im, off in zip(images, offs):
-                    flat = im.reshape(-1)
+                    flat = im.coef.view(np.uint8) if isinstance(im, CoefficientImage) else im.reshape(-1)
                     if not flat.flags.writeable:          # torch warns on read-only arrays; the copy only reads
                         flat = flat.view()
                         try:
@@ -486,10 +526,17 @@ class HIPDetector:
             base = stage.data_ptr()
             ctx = self._ctx
             comp.wait_event(pl['copied'][k])
+            srcs = [base + off for off in offs]
+            if jpeg_idx:
+                ctx.jpeg_reconstruct([images[i] for i in jpeg_idx], [base + offs[i] for i in jpeg_idx],
+                                     [base + rgb_offs[i] for i in jpeg_idx], stream=comp.cuda_stream)
+                for i in jpeg_idx:
+                    srcs[i] = base + rgb_offs[i]
+                self.jpeg_images_reconstructed += len(jpeg_idx)
             # (the letterbox on the copy stream next to the previous batch's forward -- mdhip_preprocess waits for that
             # forward's stem inside the library -- was measured with bench.py --pre-own-stream: 0.6 % slower, its workgroups
             # keep the 8-wave conv workgroups off their CUs; it stays on the compute stream)
-            ctx.preprocess([base + off for off in offs], geoms, h, w, stream=comp.cuda_stream)
+            ctx.preprocess(srcs, geoms, h, w, stream=comp.cuda_stream)
             if self._fp8_pending:
                 ctx.calibrate(n, h, w, stream=comp.cuda_stream)
                 self._fp8_calibrated()

@@ -14,9 +14,14 @@ takes ~1 ms per image).  Here:
   * the ring is page-locked in the GPU process (hipHostRegister), so the host-to-device copy of a batch
     is an asynchronous DMA at PCIe rate on a copy stream, overlapped with the previous batch's kernels
     (detector.HIPDetector.start_batch / finish_batch);
-  * an image that does not fit a slot falls back to travelling through the queue as an array.
+  * an image that does not fit a slot falls back to travelling through the queue as an array;
+  * decode='coefficients' (opt-in, run_detector_batch --gpu_jpeg): for a baseline JPEG the loader only Huffman-decodes
+    (jpeg_host / libmdjpeg.so) and the slot carries quantised DCT coefficients; the GPU rebuilds the pixels PIL would
+    have produced, bit for bit (mdhip_jpeg_reconstruct).  Any file the entropy decoder does not take cleanly goes the
+    PIL way above, per file.
 
-This module must stay import-light (numpy + PIL only): it is what the spawned loader processes import.
+This module must stay import-light (numpy + PIL, and jpeg_host's ctypes): it is what the spawned loader processes import,
+and they never open the GPU.
 """
 
 import multiprocessing as mp
@@ -71,6 +76,12 @@ class ImageMeta:
         return {36867: self._dt} if self._dt is not None else {}
 
 
+def coefficient_image(ring, slot, shape):
+    """the jpeg_host.CoefficientImage a loader left in `slot` (views of the ring: nothing is copied)"""
+    from . import jpeg_host
+    return jpeg_host.CoefficientImage.from_slot(ring.slot(slot), shape)
+
+
 class SharedImageRing:
     """n_slots x slot_bytes of shared memory + the queue of free slot numbers."""
 
@@ -92,6 +103,11 @@ class SharedImageRing:
         n = int(np.prod(shape))
         off = slot * self.slot_bytes
         return self._all[off:off + n].reshape(shape)
+
+    def slot(self, slot):
+        """the whole slot as a flat uint8 view"""
+        off = slot * self.slot_bytes
+        return self._all[off:off + self.slot_bytes]
 
     def pin(self):
         """Page-locks the ring for asynchronous H2D copies (no-op without a HIP device).  Returns bool."""
@@ -124,7 +140,83 @@ class SharedImageRing:
             pass
 
 
-def _loader_process_main(shm_name, slot_bytes, file_q, free_q, ready_q, want_meta, worker_id):
+def _pixels_to_ring(im_file, buf, slot_bytes, free_q, ready_q, want_meta, worker_id):
+    """PIL decode of one file into a ring slot (or, too large for one, through the queue)"""
+    image = load_image(im_file)
+    meta = image_metadata(image) if want_meta else None
+    arr = np.asarray(image)
+    if arr.ndim != 3 or arr.shape[2] != 3 or arr.dtype != np.uint8:
+        raise ValueError('unexpected decoded layout {} {}'.format(arr.shape, arr.dtype))
+    if arr.nbytes <= slot_bytes:
+        slot = free_q.get()
+        off = slot * slot_bytes
+        np.copyto(buf[off:off + arr.nbytes].reshape(arr.shape), arr)
+        ready_q.put(('slot', im_file, slot, arr.shape, meta, worker_id))
+    else:
+        ready_q.put(('array', im_file, np.ascontiguousarray(arr), arr.shape, meta, worker_id))
+
+
+def open_for_coefficients(input_file):
+    """
+    The header half of load_image: opens the file (no pixel is decoded), applies load_image's mode check and reads the
+    EXIF orientation with load_image's own statements.  Returns (image, rotation): the angle load_image would turn the
+    decoded image by (0 when it would not turn it: no tag, orientation 1, a mirrored orientation whose assert fails
+    inside the try, an EXIF block that raises, ignore).
+    """
+    from PIL import Image
+    image = Image.open(input_file)
+    if image.mode not in ('RGBA', 'RGB', 'L', 'I;16'):
+        raise AttributeError('Image {} uses unsupported mode {}'.format(input_file, image.mode))
+    rotation = 0
+    try:
+        # load_image converts 'RGBA' / 'L' first; what convert() returns is a plain Image, and where that has no
+        # _getexif the lookup raises inside the try: such an image is never rotated
+        exif = (image if image.mode not in ('RGBA', 'L') else Image.Image())._getexif()
+        orientation = exif.get(274, None)
+        if orientation is not None and orientation != 1:
+            assert orientation in EXIF_IMAGE_ROTATIONS, 'Mirrored rotations are not supported'
+            rotation = EXIF_IMAGE_ROTATIONS[orientation]
+    except Exception:
+        pass
+    return image, rotation
+
+
+def _coefficients_to_ring(im_file, buf, slot_bytes, free_q, ready_q, want_meta, worker_id):
+    """
+    Entropy decode of one baseline JPEG into a ring slot.  Returns False -- having put nothing on the queue -- when the
+    file has to go the PIL way: not a JPEG, a kind mdjpeg_parse does not support, planes larger than a slot, or a stream
+    the decoder reports as not clean.  Exceptions of the header half are load_image's own and propagate.
+    """
+    from . import jpeg_host
+    image, rotation = open_for_coefficients(im_file)
+    if image.format != 'JPEG':
+        return False
+    with open(im_file, 'rb') as f:
+        data = f.read()
+    header = jpeg_host.parse(data)
+    if not header.supported or jpeg_host.SLOT_HEADER_BYTES + 2 * header.coef_count > slot_bytes:
+        return False
+    meta = None
+    if want_meta:
+        meta = image_metadata(image)
+        if rotation in (90, 270):
+            meta['width'], meta['height'] = meta['height'], meta['width']
+    slot = free_q.get()
+    try:
+        off = slot * slot_bytes
+        rc = jpeg_host.decode_into_slot(data, buf[off:off + slot_bytes], rotation)
+    except BaseException:
+        free_q.put(slot)
+        raise
+    if rc != jpeg_host.MDJPEG_OK:
+        free_q.put(slot)
+        return False
+    h, w = (header.width, header.height) if rotation in (90, 270) else (header.height, header.width)
+    ready_q.put(('jpeg', im_file, slot, (h, w, 3), meta, worker_id))
+    return True
+
+
+def _loader_process_main(shm_name, slot_bytes, file_q, free_q, ready_q, want_meta, worker_id, decode='pixels'):
     """Body of a loader process: file names in, (file, slot, shape) out."""
     from multiprocessing import shared_memory
     shm = shared_memory.SharedMemory(name=shm_name)
@@ -135,18 +227,9 @@ def _loader_process_main(shm_name, slot_bytes, file_q, free_q, ready_q, want_met
             if im_file is None:
                 break
             try:
-                image = load_image(im_file)
-                meta = image_metadata(image) if want_meta else None
-                arr = np.asarray(image)
-                if arr.ndim != 3 or arr.shape[2] != 3 or arr.dtype != np.uint8:
-                    raise ValueError('unexpected decoded layout {} {}'.format(arr.shape, arr.dtype))
-                if arr.nbytes <= slot_bytes:
-                    slot = free_q.get()
-                    off = slot * slot_bytes
-                    np.copyto(buf[off:off + arr.nbytes].reshape(arr.shape), arr)
-                    ready_q.put(('slot', im_file, slot, arr.shape, meta, worker_id))
-                else:
-                    ready_q.put(('array', im_file, np.ascontiguousarray(arr), arr.shape, meta, worker_id))
+                if decode != 'coefficients' or not _coefficients_to_ring(im_file, buf, slot_bytes, free_q, ready_q,
+                                                                        want_meta, worker_id):
+                    _pixels_to_ring(im_file, buf, slot_bytes, free_q, ready_q, want_meta, worker_id)
             except Exception as e:
                 print('Producer process: image {} cannot be loaded:\n{}'.format(im_file, str(e)))
                 ready_q.put(('fail', im_file, None, None, None, worker_id))
@@ -160,11 +243,16 @@ def _loader_process_main(shm_name, slot_bytes, file_q, free_q, ready_q, want_met
 
 class ProcessLoader:
     """
-    Spawns the loader processes and yields ('slot'|'array'|'fail', file, payload, shape, meta) in
+    Spawns the loader processes and yields ('slot'|'array'|'fail'|'jpeg', file, payload, shape, meta) in
     completion order.  `payload` is the slot number (pixels: ring.view(slot, shape)) or the array.
+    decode='coefficients': baseline JPEGs arrive as 'jpeg' -- the slot holds quantised DCT coefficients
+    (jpeg_host.CoefficientImage.from_slot(ring.slot(slot), shape)), `shape` is that of the rotated RGB image; every
+    other file arrives exactly as with decode='pixels' (the default).
     """
 
-    def __init__(self, image_files, n_workers, n_slots, slot_bytes, want_meta=False):
+    def __init__(self, image_files, n_workers, n_slots, slot_bytes, want_meta=False, decode='pixels'):
+        if decode not in ('pixels', 'coefficients'):
+            raise ValueError("decode must be 'pixels' or 'coefficients', got {!r}".format(decode))
         self.ctx = mp.get_context('spawn')
         self.ring = SharedImageRing(n_slots, slot_bytes, self.ctx)
         self.file_q = self.ctx.Queue()
@@ -176,7 +264,7 @@ class ProcessLoader:
             self.file_q.put(None)
         self.procs = [self.ctx.Process(target=_loader_process_main,
                                        args=(self.ring.name, self.ring.slot_bytes, self.file_q, self.ring.free_q,
-                                             self.ready_q, bool(want_meta), i), daemon=True)
+                                             self.ready_q, bool(want_meta), i, decode), daemon=True)
                       for i in range(self.n_workers)]
         for p in self.procs:
             p.start()

@@ -187,6 +187,30 @@ class HipContext:
         self._check(self.lib.mdhip_preprocess_windows(self.h, C.cast(p, C.POINTER(C.c_void_p)), g, pt, rd, n, int(out_h), int(out_w),
                                                       C.c_void_p(stream)), 'mdhip_preprocess_windows')
 
+    def jpeg_reconstruct(self, images, coef_ptrs, out_ptrs, stream=0):
+        """
+        Rebuilds RGB images from quantised JPEG coefficients on the device (include/mdhip.h: mdhip_jpeg_reconstruct).
+        images:    jpeg_host.CoefficientImage objects (geometry, sampling, tables, rotation)
+        coef_ptrs: integer device pointers to each image's coefficient planes (16-byte aligned)
+        out_ptrs:  integer device pointers to room for each rotated H x W x 3 image (image.shape)
+        """
+        n = len(images)
+        if not (len(coef_ptrs) == len(out_ptrs) == n):
+            raise ValueError('images, coef_ptrs and out_ptrs must have one entry per image')
+        arr = (_lib.mdhip_jpeg_image * n)()
+        for i, im in enumerate(images):
+            a = arr[i]
+            a.coef = int(coef_ptrs[i])
+            a.width, a.height, a.components = im.width, im.height, im.components
+            a.h_samp, a.v_samp, a.rotation = im.h_samp, im.v_samp, im.rotation
+            for c in range(im.components):
+                a.blocks_w[c], a.blocks_h[c] = im.blocks_w[c], im.blocks_h[c]
+            q = np.ascontiguousarray(im.quant, dtype=np.uint16).reshape(3, 64)
+            C.memmove(C.addressof(a.quant), q.ctypes.data, 384)
+        outs = (C.c_void_p * n)(*[int(v) for v in out_ptrs])
+        self._check(self.lib.mdhip_jpeg_reconstruct(self.h, arr, n, C.cast(outs, C.POINTER(C.c_void_p)), C.c_void_p(stream)),
+                    'mdhip_jpeg_reconstruct')
+
     def forward(self, n, h, w, stream=0):
         self._check(self.lib.mdhip_forward(self.h, int(n), int(h), int(w), C.c_void_p(stream)), 'mdhip_forward')
 

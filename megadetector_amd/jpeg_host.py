@@ -1,0 +1,188 @@
+"""
+ctypes binding of libmdjpeg.so (C ABI: include/mdjpeg.h): the host half of the GPU JPEG feed.
+
+parse() / decode() turn the bytes of a baseline JPEG into quantised DCT coefficients; the GPU rebuilds the pixels
+(hip_backend.HipContext.jpeg_reconstruct).  Whatever the decoder does not take cleanly is reported, never guessed at: the
+caller then decodes that file with PIL.
+
+This module must stay import-light (ctypes + numpy only, like feed.py): the spawned loader processes import it, and
+they may never open the GPU -- libmdjpeg.so links nothing of HIP.
+"""
+
+import ctypes as C
+import os
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, 'libmdjpeg.so')
+
+MDJPEG_OK = 0
+MDJPEG_EINVAL = -1
+MDJPEG_EUNSUPPORTED = -2
+MDJPEG_ECORRUPT = -3
+MDJPEG_ECAPACITY = -4
+
+
+class mdjpeg_info(C.Structure):
+    _fields_ = [('width', C.c_int32), ('height', C.c_int32), ('components', C.c_int32),
+                ('h_samp', C.c_int32 * 3), ('v_samp', C.c_int32 * 3), ('restart_interval', C.c_int32),
+                ('mcus_x', C.c_int32), ('mcus_y', C.c_int32), ('blocks_w', C.c_int32 * 3), ('blocks_h', C.c_int32 * 3),
+                ('plane_offset', C.c_int64 * 3), ('coef_count', C.c_int64), ('quant', (C.c_uint16 * 64) * 3),
+                ('supported', C.c_int32), ('reason', C.c_char * 100)]
+
+
+#: every symbol include/mdjpeg.h declares: name -> (restype, argtypes)
+SYMBOLS = {
+    'mdjpeg_parse': (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(mdjpeg_info)]),
+    'mdjpeg_decode': (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(mdjpeg_info), C.c_void_p, C.c_size_t]),
+    'mdjpeg_version': (C.c_char_p, []),
+}
+
+_lib = None
+
+
+def load():
+    """Loads libmdjpeg.so (once).  Raises RuntimeError when the library is not built."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise RuntimeError('libmdjpeg.so not found at {}: build it with `make -C megadetector_amd/csrc`'.format(LIB_PATH))
+    lib = C.CDLL(LIB_PATH)
+    for name, (res, args) in SYMBOLS.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _lib = lib
+    return lib
+
+
+class JpegHeader:
+    """What mdjpeg_parse reports, as plain Python data."""
+
+    def __init__(self, info, rc):
+        nc = info.components if info.components in (1, 3) else 0
+        self.rc = int(rc)
+        self.width, self.height, self.components = info.width, info.height, info.components
+        self.supported = bool(info.supported)
+        self.reason = info.reason.decode('ascii', 'replace')
+        self.h_samp = tuple(info.h_samp[:nc])
+        self.v_samp = tuple(info.v_samp[:nc])
+        self.restart_interval = info.restart_interval
+        self.mcus_x, self.mcus_y = info.mcus_x, info.mcus_y
+        self.blocks_w = tuple(info.blocks_w[:nc])
+        self.blocks_h = tuple(info.blocks_h[:nc])
+        self.plane_offset = tuple(info.plane_offset[:nc])
+        self.coef_count = int(info.coef_count)
+        self.quant = np.ctypeslib.as_array(info.quant).reshape(3, 64).copy()      # uint16, natural order
+
+    def planes(self, coef):
+        """views of the flat int16 coefficient buffer: one [blocks_h][blocks_w][64] array per component"""
+        return [coef[o:o + bh * bw * 64].reshape(bh, bw, 64)
+                for o, bh, bw in zip(self.plane_offset, self.blocks_h, self.blocks_w)]
+
+
+def _as_buffer(data):
+    if isinstance(data, np.ndarray):
+        if data.dtype != np.uint8 or not data.flags.c_contiguous:
+            raise ValueError('file bytes must be a contiguous uint8 array')
+        return data, data.ctypes.data, data.size
+    arr = np.frombuffer(data, dtype=np.uint8)
+    return arr, arr.ctypes.data, arr.size
+
+
+def parse(data):
+    """data: the file's bytes (bytes or uint8 array).  Returns a JpegHeader; .supported says whether decode() takes it."""
+    hold, ptr, n = _as_buffer(data)
+    info = mdjpeg_info()
+    rc = load().mdjpeg_parse(ptr, n, C.byref(info))
+    return JpegHeader(info, rc)
+
+
+def decode(data, out=None):
+    """
+    Entropy-decodes the scan.  out: a contiguous int16 array to decode into (e.g. a view of a shared-memory slot); it is
+    allocated when None.  Returns (rc, header, out): rc == MDJPEG_OK and the first header.coef_count values of `out`
+    hold the planes, or rc < 0 (header.reason says why) and `out` holds nothing of use.
+    """
+    hold, ptr, n = _as_buffer(data)
+    lib = load()
+    info = mdjpeg_info()
+    if out is None:
+        rc = lib.mdjpeg_parse(ptr, n, C.byref(info))
+        if rc != MDJPEG_OK:
+            return rc, JpegHeader(info, rc), None
+        out = np.empty((int(info.coef_count),), dtype=np.int16)
+    if out.dtype != np.int16 or not out.flags.c_contiguous or not out.flags.writeable:
+        raise ValueError('out must be a writeable contiguous int16 array')
+    rc = lib.mdjpeg_decode(ptr, n, C.byref(info), out.ctypes.data, out.size)
+    return rc, JpegHeader(info, rc), out
+
+
+# ---- a coefficient image in a ring slot (feed.py decode='coefficients') ------------------------------------------------
+# slot = [16 x int32 header][3 x 64 uint16 quantisation tables][int16 planes]
+SLOT_MAGIC = 0x4D444A31
+SLOT_HEADER_BYTES = 512              # 64 + 384, rounded up: the planes start 256-byte aligned within the slot
+_SLOT_QUANT_OFF = 64
+
+
+def decode_into_slot(data, slot_view, rotation):
+    """Entropy-decodes `data` into the flat uint8 view of a slot.  Returns the code of mdjpeg_decode."""
+    coef = slot_view[SLOT_HEADER_BYTES:SLOT_HEADER_BYTES + (slot_view.size - SLOT_HEADER_BYTES) // 2 * 2].view(np.int16)
+    rc, h, _ = decode(data, out=coef)
+    if rc != MDJPEG_OK:
+        return rc
+    head = slot_view[:64].view(np.int32)
+    head[:] = 0
+    head[0:8] = (SLOT_MAGIC, h.width, h.height, h.components, h.h_samp[0], h.v_samp[0], int(rotation), h.coef_count)
+    head[8:8 + h.components] = h.blocks_w
+    head[11:11 + h.components] = h.blocks_h
+    slot_view[_SLOT_QUANT_OFF:_SLOT_QUANT_OFF + 384].view(np.uint16)[:] = h.quant.reshape(-1)
+    return rc
+
+
+class CoefficientImage:
+    """
+    A JPEG as the GPU takes it: quantised coefficient planes plus what reconstruction needs.  `.shape` is that of the
+    RGB image mdhip_jpeg_reconstruct writes (rotated H x W x 3), which is all the letterbox geometry reads.
+    coef: flat int16 (planes of Y[, Cb, Cr], each [blocks_h][blocks_w][64]); quant: [3][64] uint16, natural order.
+    """
+
+    ndim = 3
+    dtype = np.dtype(np.uint8)
+
+    def __init__(self, width, height, components, h_samp, v_samp, rotation, blocks_w, blocks_h, quant, coef):
+        self.width, self.height, self.components = int(width), int(height), int(components)
+        self.h_samp, self.v_samp, self.rotation = int(h_samp), int(v_samp), int(rotation)
+        self.blocks_w = tuple(int(v) for v in blocks_w)
+        self.blocks_h = tuple(int(v) for v in blocks_h)
+        self.quant, self.coef = quant, coef
+        if self.rotation in (90, 270):
+            self.shape = (self.width, self.height, 3)
+        else:
+            self.shape = (self.height, self.width, 3)
+
+    @property
+    def nbytes(self):
+        return self.coef.nbytes
+
+    @classmethod
+    def from_header(cls, header, coef, rotation=0):
+        """from the results of decode()"""
+        return cls(header.width, header.height, header.components, header.h_samp[0], header.v_samp[0], rotation,
+                   header.blocks_w, header.blocks_h, header.quant, coef[:header.coef_count])
+
+    @classmethod
+    def from_slot(cls, slot_view, shape=None):
+        """from the flat uint8 view of a ring slot written by decode_into_slot (views, nothing is copied)"""
+        head = slot_view[:64].view(np.int32)
+        if int(head[0]) != SLOT_MAGIC:
+            raise ValueError('ring slot does not hold a coefficient image')
+        nc = int(head[3])
+        quant = slot_view[_SLOT_QUANT_OFF:_SLOT_QUANT_OFF + 384].view(np.uint16).reshape(3, 64)
+        coef = slot_view[SLOT_HEADER_BYTES:SLOT_HEADER_BYTES + 2 * int(head[7])].view(np.int16)
+        im = cls(head[1], head[2], nc, head[4], head[5], head[6], head[8:8 + nc], head[11:11 + nc], quant, coef)
+        if shape is not None and tuple(shape) != im.shape:
+            raise ValueError('slot holds a {} image, the queue announced {}'.format(im.shape, tuple(shape)))
+        return im

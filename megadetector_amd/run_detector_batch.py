@@ -381,19 +381,32 @@ ring_slot_bytes = 48 * 1024 * 1024              # a 16-megapixel RGB frame; larg
 ring_slots_per_batch_image = 3                  # one batch being filled, two in flight
 
 
+#: how the files of the most recent shared-ring run reached the detector: 'jpeg' = as DCT coefficients (gpu_jpeg), 'slot' /
+#: 'array' = as PIL pixels, 'fail' = could not be opened
+last_feed_counts = {}
+
+
 def _run_detector_with_shared_ring(image_files, detector, confidence_threshold, quiet, image_size,
                                    include_image_size, include_image_timestamp, augment, loader_workers,
-                                   batch_size, on_results):
+                                   batch_size, on_results, gpu_jpeg=False):
     """
     SURVEY.md 8(f) N1 (feed.py): spawned loader processes decode into a page-locked shared-memory ring,
     the batches go through the detector's pipelined interface.  Same results as every other mode.
+    gpu_jpeg: the loaders only entropy-decode baseline JPEGs and the detector rebuilds their pixels on the GPU
+    (feed.py decode='coefficients'); needs a detector that takes coefficient images (HIPDetector).
     """
+    global last_feed_counts
+    last_feed_counts = {'jpeg': 0, 'slot': 0, 'array': 0, 'fail': 0}
+    if gpu_jpeg and not hasattr(detector, 'jpeg_images_reconstructed'):
+        print('Warning: gpu_jpeg is ignored: this detector does not take JPEG coefficients')
+        gpu_jpeg = False
     bs = max(1, batch_size)
     n_workers = max(1, min(loader_workers, len(image_files)))
     n_slots = ring_slots_per_batch_image * bs + n_workers
     try:
         loader = feed.ProcessLoader(image_files, n_workers, n_slots, ring_slot_bytes,
-                                    want_meta=include_image_size or include_image_timestamp)
+                                    want_meta=include_image_size or include_image_timestamp,
+                                    decode='coefficients' if gpu_jpeg else 'pixels')
     except (OSError, MemoryError) as e:
         # e.g. a container whose /dev/shm is smaller than the ring: the thread queue needs no shared memory
         print('Warning: cannot create the shared-memory ring ({} slots of {} MB: {}); using loader threads'.format(
@@ -426,6 +439,7 @@ def _run_detector_with_shared_ring(image_files, detector, confidence_threshold, 
             pending.clear()
 
         for kind, im_file, payload, shape, meta in loader:
+            last_feed_counts[kind] = last_feed_counts.get(kind, 0) + 1
             if kind == 'fail':
                 on_results([{'file': im_file, 'failure': FAILURE_IMAGE_OPEN}])
                 continue
@@ -433,6 +447,10 @@ def _run_detector_with_shared_ring(image_files, detector, confidence_threshold, 
             if kind == 'slot':
                 slot = payload
                 pending.append((im_file, ring.view(slot, shape), meta_img, (lambda s=slot: ring.release(s))))
+            elif kind == 'jpeg':
+                slot = payload
+                pending.append((im_file, feed.coefficient_image(ring, slot, shape), meta_img,
+                                (lambda s=slot: ring.release(s))))
             else:
                 pending.append((im_file, payload, meta_img, None))
             if len(pending) >= bs:
@@ -472,10 +490,13 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
                                 include_exif_tags=None, augment=False, force_model_download=False,
                                 detector_options=None, loader_workers=default_loaders,
                                 preprocess_on_image_queue=default_preprocess_on_image_queue, batch_size=1,
-                                verbose_output=False, use_threads_for_queue=True, detector=None):
+                                verbose_output=False, use_threads_for_queue=True, detector=None, gpu_jpeg=False):
     """
     reference :1062-1439.  `detector` (extra, optional) injects an already constructed detector
     object -- used by run_sharded and by the CPU tests of the loop with a stub detector.
+    `gpu_jpeg` (extra, default off): in the shared-ring mode (use_image_queue with loader processes) baseline JPEGs travel
+    as DCT coefficients and are rebuilt on the GPU, bit for bit what PIL decodes; every other file, and every other mode,
+    runs as without it.
     Returns the list of per-image result dicts.
     """
     global verbose
@@ -541,10 +562,12 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
             write_checkpoint(checkpoint_path, results)
             counts['last_checkpoint'] = counts['images']
 
+    if gpu_jpeg and not (use_image_queue and not use_threads_for_queue):
+        print('gpu_jpeg is ignored: it takes effect with --use_image_queue and loader processes only')
     if use_image_queue and not use_threads_for_queue and len(image_files) > 0:
         _run_detector_with_shared_ring(image_files, detector, confidence_threshold, quiet, image_size,
                                        include_image_size, include_image_timestamp, augment, loader_workers,
-                                       batch_size, on_results)
+                                       batch_size, on_results, gpu_jpeg=bool(gpu_jpeg))
     elif use_image_queue:
         _run_detector_with_image_queue(image_files, detector, confidence_threshold, quiet, image_size,
                                        include_image_size, include_image_timestamp, augment, loader_workers,
@@ -810,6 +833,9 @@ def main(argv=None):
                          'are merged into the output (needs a folder and --output_relative_filenames; reference :1894)')
     ap.add_argument('--overwrite_handling', type=str, default='overwrite', choices=['skip', 'overwrite', 'error'])
     ap.add_argument('--n_gpus', type=int, default=1, help='shard the image list over this many GPUs')
+    ap.add_argument('--gpu_jpeg', action='store_true',
+                    help='with --use_image_queue and loader processes: the loaders only entropy-decode baseline JPEGs, the GPU '
+                         'rebuilds the pixels PIL would have decoded (bit for bit); other files are decoded with PIL as usual')
     ap.add_argument('--verbose', action='store_true')
     args = ap.parse_args(argv)
 
@@ -854,7 +880,7 @@ def main(argv=None):
                   include_image_timestamp=args.include_image_timestamp, augment=args.augment,
                   detector_options=parse_kvp_list(args.detector_options), loader_workers=args.loader_workers,
                   preprocess_on_image_queue=args.preprocess_on_image_queue, batch_size=args.batch_size,
-                  verbose_output=args.verbose, use_threads_for_queue=args.use_threads_for_queue)
+                  verbose_output=args.verbose, use_threads_for_queue=args.use_threads_for_queue, gpu_jpeg=args.gpu_jpeg)
     t0 = time.time()
     if args.n_gpus > 1:
         results = run_sharded(args.detector_file, files, args.n_gpus, results=results, **kwargs)
