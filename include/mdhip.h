@@ -217,6 +217,25 @@ typedef struct {
 } mdhip_jpeg_image;
 int mdhip_jpeg_reconstruct(mdhip_ctx* ctx, const mdhip_jpeg_image* images, int n, uint8_t* const* out_rgb, void* hip_stream);
 
+/* JPEG recompression of windows of device images (the reference writes every tile of run_tiled_inference.py as a quality-95
+ * JPEG and detects on the decoded file, run_tiled_inference.py:54,262): out_rgb[i] receives the pixels that Pillow /
+ * libjpeg-turbo give for Image.save(<window i>, quality = q) followed by Image.open, bit for bit, without a file, a host
+ * copy or an entropy coder.  The encoder's lossy half in libjpeg's integer arithmetic -- fixed-point RGB -> YCbCr, edges
+ * replicated to whole blocks, h2v2 chroma down-sampling (three components, 4:2:0: what Pillow writes for RGB input with
+ * default settings), the "islow" forward DCT, quantisation rounding half away from zero -- then mdhip_jpeg_reconstruct's
+ * de-quantisation, inverse DCT, fancy upsampling and colour conversion.
+ *   windows[i]   device pointer to the window's first pixel (parent + y0 * pitch + x0 * 3), as for mdhip_preprocess_windows;
+ *                a host pointer is MDHIP_EINVAL.  Only bytes of the window are read: no aligned over-read, no `readable`.
+ *   widths[i], heights[i]   the window's size in pixels, 1 .. 65535 each, any value (no multiple of 8 or 16 is needed)
+ *   pitches[i]   bytes between two rows of the parent (>= widths[i] * 3)
+ *   quant_luma, quant_chroma   HOST pointers: the encoder's tables, natural order, entries 1 .. 255 (for a Pillow quality:
+ *                the standard's tables under libjpeg's quality scaling; megadetector_amd/jpeg_host.py quant_tables)
+ *   out_rgb[i]   device memory of heights[i] x widths[i] x 3 bytes, written completely; it must not overlap the window
+ * Scratch and streams are those of mdhip_jpeg_reconstruct (the two calls share the scratch): one stream per context. */
+int mdhip_jpeg_recompress(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
+                          const int64_t* pitches, int n, const uint16_t quant_luma[64], const uint16_t quant_chroma[64],
+                          uint8_t* const* out_rgb, void* hip_stream);
+
 /* Test-time augmentation: replaces mdhip_forward for `model(batch, augment=True)` (reference
  * pytorch_detector.py:1313 -> yolov5 _forward_augment): three passes over the batch that mdhip_preprocess
  * left in the context -- scale 1, scale 0.83 left-right flipped, scale 0.67 (bilinear, padded with 0.447 to

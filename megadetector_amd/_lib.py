@@ -71,6 +71,8 @@ SYMBOLS = {
                                            C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_forward': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_jpeg_reconstruct': (C.c_int, [_P, C.POINTER(mdhip_jpeg_image), C.c_int, C.POINTER(_P), _P]),
+    'mdhip_jpeg_recompress': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                        C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(_P), _P]),
     'mdhip_forward_tta': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_last_num_anchors': (C.c_int, [_P]),
     'mdhip_calibrate': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),

@@ -8,6 +8,17 @@
 //
 // One launch of each per image: an image's description travels by value in the kernel arguments, so nothing of a call
 // lives in device memory except the component planes (scratch of the context).
+//
+// JPEG recompression of a window (mdhip_jpeg_recompress): the pixels Image.save(quality=q) + Image.open give, without a file.
+// The encoder's lossy half in libjpeg's integer arithmetic (restates tests/jpeg_enc_ref.py, pinned against Pillow), then
+// the kernels above from the planes on:
+//
+//   jpeg_enc_planes_kernel   16-bit fixed-point RGB -> YCbCr, edges replicated to whole blocks, h2v2 chroma down-sampling with
+//                            the alternating 1 / 2 bias -> u8 component planes; one thread = 4 x 2 luma samples + 2 of each chroma
+//   jpeg_requant_kernel      per 8x8 block of a plane, in place: samples - 128, "islow" forward DCT (jfdctint: rows then
+//                            columns, PASS1_BITS 2), division by 8 * table entry rounded half away from zero, times the table
+//                            entry, and the inverse DCT of jpeg_idct_kernel.  The quantised coefficients live in registers only.
+//   jpeg_colour_kernel       as above, rotation 0
 
 #include <hip/hip_runtime.h>
 
@@ -188,7 +199,170 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(const JpegDev d) {
     }
 }
 
+// ---- recompression: the encoder's lossy half ---------------------------------------------------------------------------
+
+// one pixel of the window (clamped coordinates: the callers replicate edges) -> Y, Cb, Cr of jccolor.c
+__device__ __forceinline__ void load_ycc(const uint8_t* src, long long pitch, int sx, int sy, int& y, int& cb, int& cr) {
+    const uint8_t* p = src + (long long)sy * pitch + (long long)sx * 3;
+    const int r = p[0], g = p[1], b = p[2];
+    y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
+    cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
+    cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+}
+
+__global__ __launch_bounds__(256) void jpeg_enc_planes_kernel(const JpegDev d, const uint8_t* __restrict__ src, const long long pitch) {
+    const int tx = blockIdx.x * 32 + (threadIdx.x & 31);              // two chroma columns, four luma columns
+    const int cy = blockIdx.y * 8 + (threadIdx.x >> 5);               // one chroma row, two luma rows
+    const int cpw = d.blocks_w[1] * 8, cph = d.blocks_h[1] * 8;       // chroma plane
+    if (tx * 2 >= cpw || cy >= cph) return;
+    const int W = d.width, H = d.height;
+    const int ypw = d.blocks_w[0] * 8, yph = d.blocks_h[0] * 8;       // luma plane: multiples of 8, so four columns are in or out together
+    const int ch = (H + 1) >> 1;
+    int yv[2][4], cbv[2][4], crv[2][4];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int sy = min(2 * cy + j, H - 1);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) load_ycc(src, pitch, min(4 * tx + k, W - 1), sy, yv[j][k], cbv[j][k], crv[j][k]);
+    }
+    if (4 * tx < ypw) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (2 * cy + j < yph) {
+                uint8_t* row = d.planes + d.plane_off[0] + (long long)(2 * cy + j) * ypw + 4 * tx;
+                *reinterpret_cast<unsigned*>(row) = unsigned(yv[j][0]) | (unsigned(yv[j][1]) << 8) | (unsigned(yv[j][2]) << 16) |
+                                                    (unsigned(yv[j][3]) << 24);
+            }
+        }
+    }
+    if (cy >= ch) {                                                   // below the image chroma repeats its last down-sampled row
+        int unused;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int sy = min(2 * (ch - 1) + j, H - 1);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) load_ycc(src, pitch, min(4 * tx + k, W - 1), sy, unused, cbv[j][k], crv[j][k]);
+        }
+    }
+    // h2v2_downsample: the bias is 1 in even output columns and 2 in odd ones
+    const unsigned cb0 = unsigned(cbv[0][0] + cbv[0][1] + cbv[1][0] + cbv[1][1] + 1) >> 2;
+    const unsigned cb1 = unsigned(cbv[0][2] + cbv[0][3] + cbv[1][2] + cbv[1][3] + 2) >> 2;
+    const unsigned cr0 = unsigned(crv[0][0] + crv[0][1] + crv[1][0] + crv[1][1] + 1) >> 2;
+    const unsigned cr1 = unsigned(crv[0][2] + crv[0][3] + crv[1][2] + crv[1][3] + 2) >> 2;
+    const long long co = (long long)cy * cpw + 2 * tx;
+    *reinterpret_cast<unsigned short*>(d.planes + d.plane_off[1] + co) = (unsigned short)(cb0 | (cb1 << 8));
+    *reinterpret_cast<unsigned short*>(d.planes + d.plane_off[2] + co) = (unsigned short)(cr0 | (cr1 << 8));
+}
+
+// one 1-D pass of jpeg_fdct_islow; pass 1 (rows) scales up by PASS1_BITS, pass 2 (columns) takes it out again
+template <bool FIRST>
+__device__ __forceinline__ void fdct_1d(const int* d, int* o) {
+    constexpr int n = FIRST ? 11 : 15;
+    int tmp0 = d[0] + d[7], tmp7 = d[0] - d[7];
+    int tmp1 = d[1] + d[6], tmp6 = d[1] - d[6];
+    int tmp2 = d[2] + d[5], tmp5 = d[2] - d[5];
+    int tmp3 = d[3] + d[4], tmp4 = d[3] - d[4];
+    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    if (FIRST) {
+        o[0] = (tmp10 + tmp11) * 4;
+        o[4] = (tmp10 - tmp11) * 4;
+    } else {
+        o[0] = descale(tmp10 + tmp11, 2);
+        o[4] = descale(tmp10 - tmp11, 2);
+    }
+    int z1 = (tmp12 + tmp13) * 4433;
+    o[2] = descale(z1 + tmp13 * 6270, n);
+    o[6] = descale(z1 + tmp12 * (-15137), n);
+    z1 = tmp4 + tmp7;
+    int z2 = tmp5 + tmp6;
+    int z3 = tmp4 + tmp6;
+    int z4 = tmp5 + tmp7;
+    const int z5 = (z3 + z4) * 9633;
+    tmp4 *= 2446;
+    tmp5 *= 16819;
+    tmp6 *= 25172;
+    tmp7 *= 12299;
+    z1 *= -7373;
+    z2 *= -20995;
+    z3 = z3 * (-16069) + z5;
+    z4 = z4 * (-3196) + z5;
+    o[7] = descale(tmp4 + z1 + z3, n);
+    o[5] = descale(tmp5 + z2 + z4, n);
+    o[3] = descale(tmp6 + z2 + z3, n);
+    o[1] = descale(tmp7 + z1 + z4, n);
+}
+
+__global__ __launch_bounds__(IDCT_BLOCKS * 8) void jpeg_requant_kernel(const JpegDev d) {
+    __shared__ int lds[IDCT_BLOCKS][8][9];
+    const int t = threadIdx.x;
+    const int lb = t >> 3, r = t & 7;
+    const long long g = (long long)blockIdx.x * IDCT_BLOCKS + lb;         // block number within the image, all planes
+    int c = 0;
+    long long b = g;
+    bool active = false;
+    for (int k = 0; k < 3; ++k) {
+        const long long nb = (long long)d.blocks_w[k] * d.blocks_h[k];
+        if (b < nb) { c = k; active = true; break; }
+        b -= nb;
+    }
+    uint8_t* row = nullptr;
+    int v[8], ws[8];
+    if (active) {
+        const int bw = d.blocks_w[c];
+        const int by = (int)(b / bw), bx = (int)(b % bw);
+        row = d.planes + d.plane_off[c] + ((long long)by * 8 + r) * ((long long)bw * 8) + bx * 8;
+        const uint2 in = *reinterpret_cast<const uint2*>(row);           // row r of the block
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[i] = int((in.x >> (8 * i)) & 255u) - 128;
+            v[4 + i] = int((in.y >> (8 * i)) & 255u) - 128;
+        }
+        fdct_1d<true>(v, ws);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) lds[lb][r][i] = ws[i];
+    }
+    __syncthreads();
+    if (active) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = lds[lb][i][r];                 // column r of the workspace
+        fdct_1d<false>(v, ws);                                            // coefficients (i, r), scaled by 8
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const unsigned q = d.quant[c][i * 8 + r];
+            const unsigned div = q * 8u;
+            const unsigned mag = (unsigned(ws[i] < 0 ? -ws[i] : ws[i]) + (div >> 1)) / div;
+            v[i] = ws[i] < 0 ? -int(mag * q) : int(mag * q);              // quantised, and de-quantised again
+        }
+        idct_1d(v, ws, 11);                                               // the inverse starts with the columns
+    }
+    __syncthreads();
+    if (active) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) lds[lb][i][r] = ws[i];
+    }
+    __syncthreads();
+    if (active) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = lds[lb][r][i];                 // row r of the workspace
+        idct_1d(v, ws, 18);
+        uint2 o;
+        o.x = range_limit(ws[0]) | (range_limit(ws[1]) << 8) | (range_limit(ws[2]) << 16) | (range_limit(ws[3]) << 24);
+        o.y = range_limit(ws[4]) | (range_limit(ws[5]) << 8) | (range_limit(ws[6]) << 16) | (range_limit(ws[7]) << 24);
+        *reinterpret_cast<uint2*>(row) = o;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_jpeg_recompress(const JpegDev& d, const uint8_t* src, long long pitch, hipStream_t s) {
+    const int cpw = d.blocks_w[1] * 8, cph = d.blocks_h[1] * 8;
+    hipLaunchKernelGGL(jpeg_enc_planes_kernel, dim3((cpw / 2 + 31) / 32, (cph + 7) / 8), dim3(256), 0, s, d, src, pitch);
+    long long blocks = 0;
+    for (int c = 0; c < 3; ++c) blocks += (long long)d.blocks_w[c] * d.blocks_h[c];
+    hipLaunchKernelGGL(jpeg_requant_kernel, dim3((unsigned)((blocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS)), dim3(IDCT_BLOCKS * 8), 0, s, d);
+    hipLaunchKernelGGL(jpeg_colour_kernel, dim3((d.width + 63) / 64, (d.height + 15) / 16), dim3(256), 0, s, d);
+    return hipGetLastError();
+}
 
 hipError_t launch_jpeg_reconstruct(const JpegDev& d, hipStream_t s) {
     long long blocks = 0;

@@ -2180,6 +2180,67 @@ int mdhip_jpeg_reconstruct(mdhip_ctx* ctx, const mdhip_jpeg_image* images, int n
     return MDHIP_OK;
 }
 
+int mdhip_jpeg_recompress(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
+                          const int64_t* pitches, int n, const uint16_t quant_luma[64], const uint16_t quant_chroma[64],
+                          uint8_t* const* out_rgb, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!windows || !widths || !heights || !pitches || !quant_luma || !quant_chroma || !out_rgb)
+        return fail(ctx, MDHIP_EINVAL, "windows/widths/heights/pitches/quant_luma/quant_chroma/out_rgb is NULL");
+    if (n < 1) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
+    for (int k = 0; k < 64; ++k)
+        if (quant_luma[k] < 1 || quant_luma[k] > 255 || quant_chroma[k] < 1 || quant_chroma[k] > 255)
+            return fail(ctx, MDHIP_EINVAL, "quantisation table entry %d outside 1 .. 255 (baseline JPEG)", k);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<JpegDev> devs(n);
+    size_t planes_bytes = 0;
+    for (int i = 0; i < n; ++i) {
+        JpegDev& d = devs[i];
+        const int w = widths[i], h = heights[i];
+        if (w < 1 || h < 1 || w > 65535 || h > 65535) return fail(ctx, MDHIP_EINVAL, "window %d: %dx%d", i, w, h);
+        if (pitches[i] < (long long)w * 3 || (long long)(h - 1) * pitches[i] + (long long)w * 3 > 0x7fff0000LL)
+            return fail(ctx, MDHIP_EINVAL, "window %d: pitch %lld for %d pixels per row (or a window above 2 GB)", i, (long long)pitches[i], w);
+        if (!windows[i] || !out_rgb[i]) return fail(ctx, MDHIP_EINVAL, "window %d: windows / out_rgb is NULL", i);
+        for (const void* p : {(const void*)windows[i], (const void*)out_rgb[i]}) {
+            hipPointerAttribute_t attr;
+            const hipError_t e = hipPointerGetAttributes(&attr, p);
+            if (e != hipSuccess) (void)hipGetLastError();
+            if (e != hipSuccess || !(attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged))
+                return fail(ctx, MDHIP_EINVAL, "window %d: host pointer -- windows and out_rgb must be device memory", i);
+        }
+        d.coef = nullptr;
+        d.out = out_rgb[i];
+        d.width = w;
+        d.height = h;
+        d.components = 3;
+        d.h_samp = d.v_samp = 2;
+        d.rotation = 0;
+        for (int c = 0; c < 3; ++c) {                                   // each component's own whole blocks (4:2:0)
+            const int cw = c == 0 ? w : (w + 1) / 2, ch = c == 0 ? h : (h + 1) / 2;
+            d.blocks_w[c] = (cw + 7) / 8;
+            d.blocks_h[c] = (ch + 7) / 8;
+            d.coef_off[c] = 0;
+            d.plane_off[c] = (long long)planes_bytes;
+            planes_bytes += (size_t)d.blocks_w[c] * d.blocks_h[c] * 64;
+            memcpy(d.quant[c], c == 0 ? quant_luma : quant_chroma, sizeof(d.quant[c]));
+        }
+        planes_bytes = align_up(planes_bytes, 256);
+    }
+    if (planes_bytes > ctx->jpeg_planes_bytes) {
+        HIP_TRY(ctx, hipDeviceSynchronize());                  // an earlier call's kernels may still use the old planes
+        if (ctx->jpeg_planes) HIP_TRY(ctx, hipFree(ctx->jpeg_planes));
+        ctx->jpeg_planes = nullptr;
+        ctx->jpeg_planes_bytes = 0;
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->jpeg_planes, planes_bytes));
+        ctx->jpeg_planes_bytes = planes_bytes;
+    }
+    for (int i = 0; i < n; ++i) {
+        devs[i].planes = (uint8_t*)ctx->jpeg_planes;
+        HIP_TRY(ctx, launch_jpeg_recompress(devs[i], windows[i], pitches[i], s));
+    }
+    return MDHIP_OK;
+}
+
 int mdhip_forward(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
     if (!ctx) return MDHIP_EINVAL;
     if (int rc = check_shape(ctx, n, h, w)) return rc;

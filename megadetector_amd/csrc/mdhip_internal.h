@@ -472,5 +472,9 @@ struct JpegDev {
 };
 // de-quantisation + inverse DCT into the planes, then upsampling + colour conversion + rotation into `out`
 hipError_t launch_jpeg_reconstruct(const JpegDev& d, hipStream_t s);
+// JPEG recompression of a window (mdhip_jpeg_recompress): the encoder's lossy half on the width x height window at `src`
+// (rows `pitch` bytes apart), then the reconstruction above from the planes on.  d: three components, 2 x 2 luma sampling,
+// rotation 0, blocks_w / blocks_h each component's own whole blocks, quant = {luma, chroma, chroma}; d.coef is not read.
+hipError_t launch_jpeg_recompress(const JpegDev& d, const uint8_t* src, long long pitch, hipStream_t s);
 
 }  // namespace mdhip

@@ -30,7 +30,7 @@ import numpy as np
 
 from . import weights_io
 from .constants import (FAILURE_IMAGE_OPEN, FAILURE_INFER, DEFAULT_COMPATIBILITY_MODE)
-from .jpeg_host import CoefficientImage
+from .jpeg_host import CoefficientImage, check_quality
 from .postprocess import letterbox_geometry, modern_geometry, format_detections
 
 
@@ -388,7 +388,8 @@ class HIPDetector:
 
     # -----------------------------------------------------------------------------------
     def generate_detections_for_tiles(self, img_original, tile_origins, tile_size, tile_ids=None,
-                                      detection_threshold=0.00001, image_size=None, augment=False, verbose=False):
+                                      detection_threshold=0.00001, image_size=None, augment=False, verbose=False,
+                                      jpeg_quality=None):
         """
         Tiled inference on one large image (the device half of run_tiled_inference.py): the image is uploaded ONCE and
         every tile is cut out of it, letterboxed and normalised by the windowed letterbox kernels
@@ -399,7 +400,14 @@ class HIPDetector:
         Returns one result dict per tile, the very dicts generate_detections_one_batch returns for the list of crops
         img[y:y + h, x:x + w]: a tile counts as an image of size (h, w).  Tiles are processed in chunks of max_batch; an
         exception in a chunk marks that chunk's tiles 'inference failure'.
+
+        jpeg_quality (1 .. 100, default None = off): every tile first goes through a JPEG round trip on the device
+        (mdhip_jpeg_recompress) and the detector sees what it would read from the tile FILE the reference writes with
+        PIL at that quality (95 there) -- the results are those of generate_detections_one_batch for the crops after
+        Image.save(quality=jpeg_quality) / Image.open, bit for bit.  No file, no host copy.
         """
+        if jpeg_quality is not None:
+            jpeg_quality = check_quality(jpeg_quality)
         if detection_threshold is None:
             detection_threshold = 0.0
         if self._ctx is None:
@@ -439,7 +447,11 @@ class HIPDetector:
                     for start in range(0, len(items), self.max_batch):
                         chunk = items[start:start + self.max_batch]
                         try:
-                            self._process_tile_chunk(chunk, origins, base, pitch, total, results, detection_threshold, augment)
+                            if jpeg_quality is None:
+                                self._process_tile_chunk(chunk, origins, base, pitch, total, results, detection_threshold, augment)
+                            else:
+                                self._process_tile_chunk(*self._recompress_tile_chunk(chunk, origins, base, pitch, (tw, th), jpeg_quality),
+                                                         results, detection_threshold, augment)
                         except Exception as e:
                             print('Warning: tile inference failed for shape {}: {}'.format(shape, str(e)))
                             for original_idx, _, current_id in chunk:
@@ -447,6 +459,27 @@ class HIPDetector:
             finally:
                 torch.cuda.synchronize(dev)                                 # nothing reads `parent` once it is released
         return results
+
+    def _recompress_tile_chunk(self, chunk, origins, base, pitch, tile_size, quality):
+        """
+        The chunk's windows of the device image at `base`, after a JPEG round trip at `quality`, as tile-sized device images
+        in a buffer this detector owns.  Returns the (chunk, origins, base, pitch, total) that make _process_tile_chunk
+        read them: each a window that covers a whole image, one behind the other like the rows of a tw-wide strip.
+        """
+        import torch
+        tw, th = tile_size
+        n = len(chunk)
+        tile_bytes = th * tw * 3
+        buf = getattr(self, '_tile_jpeg_buf', None)
+        if buf is None or buf.numel() < n * tile_bytes:
+            torch.cuda.synchronize()                                        # (earlier kernels may still read the old buffer)
+            self._tile_jpeg_buf = buf = torch.empty(n * tile_bytes, dtype=torch.uint8,
+                                                    device=torch.device('cuda', _device_ordinal(self.device)))
+        out = buf.data_ptr()
+        self._ctx.jpeg_recompress([base + origins[idx][1] * pitch + origins[idx][0] * 3 for idx, _, _ in chunk], [(tw, th)] * n,
+                                  [pitch] * n, quality, [out + i * tile_bytes for i in range(n)])
+        strip = {idx: (0, i * th) for i, (idx, _, _) in enumerate(chunk)}
+        return chunk, strip, out, tw * 3, n * tile_bytes
 
     def _process_tile_chunk(self, chunk, origins, base, pitch, total, results, detection_threshold, augment):
         """_process_batch_group for windows of the device image at `base` (row pitch `pitch`, `total` bytes)"""

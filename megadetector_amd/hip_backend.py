@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import HipError
+from .jpeg_host import quant_tables
 from .yolo_model import DETECT_TYPES, MDHIP_CBFUSE, MDHIP_DETECT_DDFL, detect_inputs
 
 
@@ -210,6 +211,29 @@ class HipContext:
         outs = (C.c_void_p * n)(*[int(v) for v in out_ptrs])
         self._check(self.lib.mdhip_jpeg_reconstruct(self.h, arr, n, C.cast(outs, C.POINTER(C.c_void_p)), C.c_void_p(stream)),
                     'mdhip_jpeg_reconstruct')
+
+    def jpeg_recompress(self, ptrs, sizes, pitches, quality, out_ptrs, stream=0):
+        """
+        Gives windows of device images the pixels of Image.save(quality=quality) + Image.open, bit for bit, on the device
+        (include/mdhip.h: mdhip_jpeg_recompress).
+        ptrs:     integer device pointers to each window's first pixel
+        sizes:    (width, height) of each window
+        pitches:  bytes between two rows of each window's parent image
+        quality:  Pillow's `quality`, 1 .. 100 (jpeg_host.quant_tables)
+        out_ptrs: integer device pointers to room for each height x width x 3 result
+        """
+        n = len(ptrs)
+        if not (len(sizes) == len(pitches) == len(out_ptrs) == n):
+            raise ValueError('ptrs, sizes, pitches and out_ptrs must have one entry per window')
+        ql, qc = quant_tables(quality)
+        p = (C.c_void_p * n)(*[int(v) for v in ptrs])
+        o = (C.c_void_p * n)(*[int(v) for v in out_ptrs])
+        ws = (C.c_int32 * n)(*[int(v[0]) for v in sizes])
+        hs = (C.c_int32 * n)(*[int(v[1]) for v in sizes])
+        pt = (C.c_int64 * n)(*[int(v) for v in pitches])
+        self._check(self.lib.mdhip_jpeg_recompress(self.h, C.cast(p, C.POINTER(C.c_void_p)), ws, hs, pt, n,
+                                                   ql.ctypes.data_as(C.POINTER(C.c_uint16)), qc.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                   C.cast(o, C.POINTER(C.c_void_p)), C.c_void_p(stream)), 'mdhip_jpeg_recompress')
 
     def forward(self, n, h, w, stream=0):
         self._check(self.lib.mdhip_forward(self.h, int(n), int(h), int(w), C.c_void_p(stream)), 'mdhip_forward')

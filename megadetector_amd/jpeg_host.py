@@ -120,6 +120,33 @@ def decode(data, out=None):
     return rc, JpegHeader(info, rc), out
 
 
+# ---- quantisation tables of an encoder quality (mdhip_jpeg_recompress) --------------------------------------------------
+# the example tables of the JPEG standard (ITU-T T.81, Annex K.1), natural order
+_STD_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+             14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+             49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+_STD_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+               47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+
+
+def check_quality(quality):
+    """a Pillow / libjpeg `quality`: an integer from 1 to 100; anything else is a ValueError"""
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
+        raise ValueError('JPEG quality must be an integer from 1 to 100, got {!r}'.format(quality))
+    return int(quality)
+
+
+def quant_tables(quality):
+    """
+    The (luminance, chrominance) quantisation tables Image.save(quality=quality) writes: the standard's tables under
+    libjpeg's quality scaling (jpeg_quality_scaling, jpeg_add_quant_table with force_baseline).  uint16 [64], natural order.
+    """
+    quality = check_quality(quality)
+    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+    return tuple(np.clip((np.array(base, dtype=np.int64) * scale + 50) // 100, 1, 255).astype(np.uint16)
+                 for base in (_STD_LUMA, _STD_CHROMA))
+
+
 # ---- a coefficient image in a ring slot (feed.py decode='coefficients') ------------------------------------------------
 # slot = [16 x int32 header][3 x 64 uint16 quantisation tables][int16 planes]
 SLOT_MAGIC = 0x4D444A31

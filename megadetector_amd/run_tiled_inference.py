@@ -6,12 +6,16 @@ Every image is split into tiles of tile_size_x x tile_size_y pixels with a fract
 tiles, tile detections are mapped back to the image and de-duplicated across overlapping tiles (class-agnostic NMS at
 IoU 0.45).  Parameter names, defaults, output JSON and the intermediate JSON files are the reference's.
 
-What differs, deliberately: the reference crops every tile with PIL, writes it as a quality-95 JPEG into the tiling
-folder and runs the batch driver on that folder.  Here an image is decoded and uploaded to the GPU once; every tile is
-cut out of the device image by the windowed letterbox kernels (HIPDetector.generate_detections_for_tiles).  No tile
-file is ever written, so
-  * the detector sees the SOURCE pixels, not pixels that went through a JPEG encode / decode: results differ from the
-    reference's by whatever that re-compression changes.  NOT PINNED: it cannot be quantified without real weights;
+What differs: the reference crops every tile with PIL, writes it as a quality-95 JPEG into the tiling folder and runs the
+batch driver on that folder.  Here an image is decoded and uploaded to the GPU once; every tile is cut out of the device
+image by the windowed letterbox kernels (HIPDetector.generate_detections_for_tiles).  No tile file is ever written, so
+  * BY DEFAULT the detector sees the SOURCE pixels, not pixels that went through a JPEG encode / decode;
+  * with tile_jpeg_quality=95 (--tile_jpeg_quality 95; extra, off by default) every tile goes through that JPEG round
+    trip on the GPU (mdhip_jpeg_recompress: libjpeg's integer arithmetic, no file, no entropy coder) and the detector
+    sees the reference's tile pixels, bit for bit what PIL reads back from the tile file it would have written.  PINNED:
+    tests/test_tile_jpeg_cpu.py (the arithmetic against Pillow, coefficient by coefficient) and
+    tests/test_gpu_tile_jpeg.py (the kernels, the network input, and a run against tile files written with PIL);
+  * what the default's difference does to detections of the real weights remains NOT PINNED (no real weights here);
   * `patch_fn` in <folder>_patch_info.json is the path the tile WOULD have.
 
 Parameters of the reference that have no meaning without tile files:
@@ -39,6 +43,7 @@ import numpy as np
 from . import run_detector
 from .constants import CONF_DIGITS, COORD_DIGITS, DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD
 from .feed import load_image
+from .jpeg_host import check_quality
 from .run_detector_batch import (default_loaders, find_images, load_checkpoint, parse_kvp_list, write_checkpoint,
                                  write_json, write_results_to_file)
 
@@ -213,14 +218,15 @@ def _resolve_image_files(image_folder, image_list):
     return files
 
 
-def _tile_level_results(detector, image, patches, confidence_threshold, inference_size, augment):
+def _tile_level_results(detector, image, patches, confidence_threshold, inference_size, augment, tile_jpeg_quality=None):
     """runs the detector on the tiles of one image; returns the per-tile result dicts (file = the tile's would-be path)"""
     names = [p['patch_fn'] for p in patches]
     origins = [(p['xmin'], p['ymin']) for p in patches]
     size = (patches[0]['xmax'] - patches[0]['xmin'] + 1, patches[0]['ymax'] - patches[0]['ymin'] + 1)
+    extra = {} if tile_jpeg_quality is None else {'jpeg_quality': tile_jpeg_quality}
     try:
         results = detector.generate_detections_for_tiles(image, origins, size, tile_ids=names, image_size=inference_size,
-                                                         augment=augment)
+                                                         augment=augment, **extra)
     except Exception as e:
         print('Warning: tile inference failed for an image: {}'.format(str(e)))
         return [{'file': n, 'failure': run_detector.FAILURE_INFER} for n in names]
@@ -241,11 +247,14 @@ def run_tiled_inference(model_file, image_folder, tiling_folder, output_file, ti
                         overwrite_tiles=True, image_list=None, augment=False, detector_options=None,
                         use_image_queue=True, preprocess_on_image_queue=True, loader_workers=default_loaders,
                         inference_size=None, verbose=False, pool_type=None, load_cached_tiles_if_available=False,
-                        create_tiles_only=False, detector=None):
+                        create_tiles_only=False, detector=None, tile_jpeg_quality=None):
     """
     See the module docstring.  `detector` (extra, optional) injects an already constructed detector object.
+    `tile_jpeg_quality` (extra, 1 .. 100, default None = off): tiles go through a JPEG round trip at that quality on the
+    GPU before the detector sees them; 95 is the reference's patch_jpeg_quality.
     Checkpoints hold one record per finished IMAGE ({'file', 'size', 'tiles': tile-level results, files relative to
-    the tiling folder}).
+    the tiling folder}, and 'tile_jpeg_quality' when that switch is on); a checkpoint made with another setting of the
+    switch is refused.
     Returns the image-level results dict that is written to output_file.
     """
     assert 0 <= tile_overlap < 1, 'Illegal tile overlap value {}'.format(tile_overlap)
@@ -253,6 +262,8 @@ def run_tiled_inference(model_file, image_folder, tiling_folder, output_file, ti
         raise ValueError('yolo_inference_options: run_inference_with_yolov5_val is not part of this package')
     if create_tiles_only:
         raise ValueError('create_tiles_only: tiles are cut on the GPU and never written, there is nothing to create')
+    if tile_jpeg_quality is not None:
+        tile_jpeg_quality = check_quality(tile_jpeg_quality)
     if tile_size_x == -1:
         tile_size_x = default_tile_size[0]
     if tile_size_y == -1:
@@ -286,6 +297,10 @@ def run_tiled_inference(model_file, image_folder, tiling_folder, output_file, ti
     done = {}
     if checkpoint_path is not None and os.path.isfile(checkpoint_path):
         done = {r['file']: r for r in load_checkpoint(checkpoint_path)}
+        other = sorted({str(r.get('tile_jpeg_quality')) for r in done.values() if r.get('tile_jpeg_quality') != tile_jpeg_quality})
+        if other:
+            raise ValueError('checkpoint {} holds records made with tile_jpeg_quality {}, this run uses {}: results of two '
+                             'settings are not mixed'.format(checkpoint_path, ', '.join(other), tile_jpeg_quality))
     records = []                                   # per image, in input order: {'file', 'size', 'tiles' | 'load_failure'}
 
     def load(fn_relative):
@@ -310,6 +325,8 @@ def run_tiled_inference(model_file, image_folder, tiling_folder, output_file, ti
             if pool is not None:
                 pending = pool.submit(load, todo[i_todo]) if i_todo < len(todo) else None
             rec = {'file': fn_relative}
+            if tile_jpeg_quality is not None:
+                rec['tile_jpeg_quality'] = tile_jpeg_quality
             if image is None:
                 rec['size'] = None
                 rec['load_failure'] = load_error
@@ -317,7 +334,8 @@ def run_tiled_inference(model_file, image_folder, tiling_folder, output_file, ti
                 rec['size'] = [image.width, image.height]
                 info = tiles_for_image(fn_relative, rec['size'], tiling_folder, patch_size, patch_stride)
                 rec['tiles'] = [] if info['error'] is not None else _tile_level_results(
-                    detector, image, info['patches'], DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD, inference_size, augment)
+                    detector, image, info['patches'], DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD, inference_size, augment,
+                    tile_jpeg_quality)
                 for t in rec['tiles']:              # (a checkpoint may be resumed with another tiling folder)
                     t['file'] = os.path.relpath(t['file'], tiling_folder)
             records.append(rec)
@@ -395,6 +413,9 @@ def main(argv=None):
     parser.add_argument('--inference_size', type=int, default=None, help='Run inference at a non-default size')
     parser.add_argument('--n_patch_extraction_workers', type=int, default=1, help='Accepted for compatibility (tiles are cut on the GPU)')
     parser.add_argument('--loader_workers', type=int, default=default_loaders, help='0 disables decoding the next image while the current one is on the GPU')
+    parser.add_argument('--tile_jpeg_quality', type=int, default=None, metavar='Q',
+                        help='Pass every tile through a JPEG round trip at quality Q (1-100) on the GPU before detection: the pixels of '
+                             'the tile files the reference writes.  The reference\'s value is 95.  Default: off, detect on the source pixels')
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) == 0:
         parser.print_help()
@@ -416,7 +437,8 @@ def main(argv=None):
                         remove_tiles=not args.no_remove_tiles, image_list=args.image_list, augment=args.augment,
                         detector_options=parse_kvp_list(args.detector_options), inference_size=args.inference_size,
                         verbose=args.verbose, n_patch_extraction_workers=args.n_patch_extraction_workers,
-                        loader_workers=args.loader_workers, use_image_queue=args.loader_workers > 0)
+                        loader_workers=args.loader_workers, use_image_queue=args.loader_workers > 0,
+                        tile_jpeg_quality=args.tile_jpeg_quality)
 
 
 if __name__ == '__main__':
