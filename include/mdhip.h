@@ -23,6 +23,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mdjpeg.h"      /* mdjpeg_scan_info: the descriptor mdhip_jpeg_entropy_decode takes */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -216,6 +218,39 @@ typedef struct {
     uint16_t quant[3][64];
 } mdhip_jpeg_image;
 int mdhip_jpeg_reconstruct(mdhip_ctx* ctx, const mdhip_jpeg_image* images, int n, uint8_t* const* out_rgb, void* hip_stream);
+
+/* Entropy decoding of baseline JPEG scans on the GPU: from the compressed scan of each of n files to the quantised
+ * coefficient planes mdhip_jpeg_reconstruct takes, in the layout of mdjpeg_decode (include/mdjpeg.h), so that the loaders
+ * decode no Huffman symbol at all.  Self-synchronising decoding: every restart segment (or the whole scan) is cut into
+ * subsequences of subseq_bits bits (0 = 1024; a multiple of 8, at least 64) that are decoded in parallel, speculatively
+ * first and again until each starts where its left neighbour ended; one launch grid per pass holds the whole batch.
+ *   scan         DEVICE pointer: the file's bytes [desc->scan_begin, desc->scan_end)
+ *   desc         host: what mdjpeg_scan returned for the file
+ *   seg_offsets  host: the desc->n_segments offsets mdjpeg_scan wrote
+ *   coef         DEVICE pointer, 16-byte aligned: receives desc->info.coef_count values
+ *   status[i]    host: 0, and coef holds exactly what mdjpeg_decode writes; or a mask of MDHIP_JPEG_* bits for exactly the
+ *                files mdjpeg_decode answers with MDJPEG_ECORRUPT, and coef holds nothing of use (decode that file with
+ *                the ordinary decoder).  Only lanes that start from verified states flag.
+ * No byte outside a scan's range is read and no value outside coef_count written, whatever the bytes say.  A descriptor
+ * whose ranges contradict each other, a host pointer or n < 1 is MDHIP_EINVAL.  The call returns when the planes are
+ * written (it reads the statuses back).  Scratch grows on demand; stream rule as mdhip_jpeg_reconstruct. */
+#define MDHIP_JPEG_ECODE      1     /* undefined Huffman code                                           */
+#define MDHIP_JPEG_ECATEGORY  2     /* DC / AC magnitude category a baseline file cannot hold           */
+#define MDHIP_JPEG_EINDEX     4     /* coefficient index past 63, zero run leaving the block            */
+#define MDHIP_JPEG_EEARLY     8     /* data end early                                                   */
+#define MDHIP_JPEG_ELEFTOVER  16    /* bytes left over in front of a marker                             */
+#define MDHIP_JPEG_ECOUNT     32    /* a segment does not hold exactly its MCUs                         */
+#define MDHIP_JPEG_EENERGY    64    /* block energy beyond what 8-bit samples can hold                  */
+#define MDHIP_JPEG_EDC        128   /* DC value out of range                                            */
+typedef struct {
+    const uint8_t*          scan;
+    const mdjpeg_scan_info* desc;
+    const uint32_t*         seg_offsets;
+    int16_t*                coef;
+} mdhip_jpeg_scan;
+int mdhip_jpeg_entropy_decode(mdhip_ctx* ctx, const mdhip_jpeg_scan* scans, int n, int subseq_bits, int32_t* status, void* hip_stream);
+/* of the last mdhip_jpeg_entropy_decode: subsequences, subsequences decoded again in pass 2, pass-2 launches, images */
+int mdhip_jpeg_entropy_stats(mdhip_ctx* ctx, int64_t out[4]);
 
 /* JPEG recompression of windows of device images (the reference writes every tile of run_tiled_inference.py as a quality-95
  * JPEG and detects on the decoded file, run_tiled_inference.py:54,262): out_rgb[i] receives the pixels that Pillow /

@@ -58,6 +58,33 @@ int mdjpeg_parse(const uint8_t* data, size_t size, mdjpeg_info* info);
  * On any error the contents of coef are unspecified. */
 int mdjpeg_decode(const uint8_t* data, size_t size, mdjpeg_info* info, int16_t* coef, size_t capacity);
 
+/* ---- the scan as a decoder that starts anywhere needs it (GPU entropy decoding: mdhip_jpeg_entropy_decode) ------------- */
+#define MDJPEG_MAX_TABLES 6          /* a scan of three components names at most three DC and three AC tables           */
+
+typedef struct {
+    mdjpeg_info info;                        /* exactly what mdjpeg_parse fills in                                         */
+    int32_t  n_tables;                       /* distinct Huffman tables the scan's components name, in order of first use  */
+    int32_t  dc_table[3], ac_table[3];       /* which of them each component uses                                          */
+    uint8_t  huff_counts[MDJPEG_MAX_TABLES][16];   /* as the file's DHT segments write them: codes of each length ...      */
+    uint8_t  huff_vals[MDJPEG_MAX_TABLES][256];    /* ... and their values                                                 */
+    int64_t  scan_begin, scan_end;           /* file offsets: first byte of entropy-coded data; the FF of the EOI marker   */
+    int32_t  n_segments;                     /* restart segments (1 without a restart interval)                            */
+    int32_t  reserved;
+} mdjpeg_scan_info;
+
+/* mdjpeg_parse's acceptance rule and info, plus the tables and the byte ranges.  Decodes no Huffman symbol: the restart
+ * segments are found by a plain search for FF bytes that are not followed by 00.  seg_offsets[k] receives the offset of
+ * segment k's first byte from scan_begin; segment k ends two bytes (its RSTn marker) in front of segment k + 1, the last
+ * one at scan_end.  Applies the checks of mdjpeg_decode that need no symbol: MDJPEG_ECORRUPT when a restart marker is
+ * missing or out of sequence, when the scan is not followed by EOI at once or when the file ends first;
+ * MDJPEG_ECAPACITY (with n_segments set) when there are more segments than seg_capacity.  Never reads beyond `size`. */
+int mdjpeg_scan(const uint8_t* data, size_t size, mdjpeg_scan_info* scan, uint32_t* seg_offsets, size_t seg_capacity);
+
+/* The host model of the GPU entropy decoder, for tests: the same passes over subsequences of `subseq_bits` bits (a multiple
+ * of 8 from 64 to 65536, or longer than every restart segment; anything else is MDJPEG_EINVAL), as loops over "lanes", with the per-lane decoder the kernels are compiled from (csrc/jpeg_subseq.h).  Arguments,
+ * results and return codes are those of mdjpeg_decode; info->reason differs.  The loaders do not call it. */
+int mdjpeg_decode_subsequences(const uint8_t* data, size_t size, int subseq_bits, mdjpeg_info* info, int16_t* coef, size_t capacity);
+
 const char* mdjpeg_version(void);
 
 #ifdef __cplusplus

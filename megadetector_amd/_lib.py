@@ -48,6 +48,10 @@ class mdhip_jpeg_image(C.Structure):
                 ('rotation', C.c_int32), ('quant', (C.c_uint16 * 64) * 3)]
 
 
+class mdhip_jpeg_scan(C.Structure):
+    _fields_ = [('scan', C.c_void_p), ('desc', C.c_void_p), ('seg_offsets', C.c_void_p), ('coef', C.c_void_p)]
+
+
 class mdhip_op_info(C.Structure):
     _fields_ = [('name', C.c_char * 48), ('kind', C.c_int32), ('layer', C.c_int32),
                 ('m', C.c_int32), ('n', C.c_int32), ('k', C.c_int32),
@@ -71,6 +75,8 @@ SYMBOLS = {
                                            C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_forward': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_jpeg_reconstruct': (C.c_int, [_P, C.POINTER(mdhip_jpeg_image), C.c_int, C.POINTER(_P), _P]),
+    'mdhip_jpeg_entropy_decode': (C.c_int, [_P, C.POINTER(mdhip_jpeg_scan), C.c_int, C.c_int, C.POINTER(C.c_int32), _P]),
+    'mdhip_jpeg_entropy_stats': (C.c_int, [_P, C.POINTER(C.c_int64)]),
     'mdhip_jpeg_recompress': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                         C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(_P), _P]),
     'mdhip_forward_tta': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),

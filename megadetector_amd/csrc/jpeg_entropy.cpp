@@ -9,9 +9,11 @@
 // per symbol that yields code length and run/size together; the canonical maxcode walk for the rare longer codes.
 
 #include "../../include/mdjpeg.h"
+#include "jpeg_subseq.h"
 
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 namespace {
 
@@ -28,6 +30,7 @@ struct Huff {
     int32_t  maxcode[18];          // largest code of each length, -1 = none
     int32_t  valoff[17];           // index of the first symbol of a length minus its first code
     uint8_t  vals[256];
+    uint8_t  counts[16];           // as the file writes them (mdjpeg_scan hands them on)
 };
 
 struct Parsed {
@@ -47,7 +50,9 @@ int fail(mdjpeg_info* info, int code, const char* why) {
 // Builds the decoding tables of one DHT entry; false when the counts do not describe a prefix code.
 bool build_huff(Huff& h, const uint8_t* counts, const uint8_t* vals, int nvals) {
     memset(h.look, 0, sizeof(h.look));
+    memset(h.vals, 0, sizeof(h.vals));
     memcpy(h.vals, vals, nvals);
+    memcpy(h.counts, counts, 16);
     int code = 0, k = 0;
     for (int len = 1; len <= 16; ++len) {
         int n = counts[len - 1];
@@ -322,6 +327,71 @@ const char* decode_block(Bits& b, const Huff& dc, const Huff& ac, const uint16_t
     return nullptr;
 }
 
+
+// ---- the scan for a decoder that starts anywhere ----------------------------------------------------------------------
+// the first FF at or behind p that is not followed by 00 (a marker, or an FF the file ends on); `size` when there is none
+size_t next_marker(const uint8_t* d, size_t size, size_t p) {
+    while (p < size) {
+        const uint8_t* f = (const uint8_t*)memchr(d + p, 0xFF, size - p);
+        if (!f) return size;
+        p = size_t(f - d);
+        if (p + 1 >= size || d[p + 1] != 0) return p;
+        p += 2;
+    }
+    return size;
+}
+
+int scan_file(const uint8_t* d, size_t size, mdjpeg_scan_info* sc, Parsed& P, uint32_t* seg_offsets, size_t seg_capacity) {
+    mdjpeg_info* info = &sc->info;
+    int rc = parse_headers(d, size, info, P);
+    mdjpeg_info keep = *info;
+    memset(sc, 0, sizeof(*sc));
+    *info = keep;
+    if (rc != MDJPEG_OK) return rc;
+    int used_class[MDJPEG_MAX_TABLES], used_id[MDJPEG_MAX_TABLES];
+    for (int c = 0; c < info->components; ++c)
+        for (int cls = 0; cls < 2; ++cls) {
+            const int id = cls ? P.comp_ta[c] : P.comp_td[c];
+            int t = 0;
+            while (t < sc->n_tables && !(used_class[t] == cls && used_id[t] == id)) ++t;
+            if (t == sc->n_tables) {
+                const Huff& h = cls ? P.ac[id] : P.dc[id];
+                used_class[t] = cls;
+                used_id[t] = id;
+                memcpy(sc->huff_counts[t], h.counts, 16);
+                memcpy(sc->huff_vals[t], h.vals, 256);
+                ++sc->n_tables;
+            }
+            (cls ? sc->ac_table : sc->dc_table)[c] = t;
+        }
+    const int64_t total_mcus = int64_t(info->mcus_x) * info->mcus_y;
+    const int64_t interval = info->restart_interval;
+    const int64_t nseg = interval ? (total_mcus + interval - 1) / interval : 1;
+    sc->scan_begin = int64_t(P.scan_begin);
+    sc->n_segments = int32_t(nseg > 0x7fffffff ? 0x7fffffff : nseg);
+    if (uint64_t(nseg) > uint64_t(seg_capacity)) {
+        snprintf(info->reason, sizeof(info->reason), "%lld restart segments, capacity is %llu", (long long)nseg, (unsigned long long)seg_capacity);
+        return MDJPEG_ECAPACITY;
+    }
+    size_t p = P.scan_begin;
+    for (int64_t k = 0; k < nseg; ++k) {
+        if (p - P.scan_begin > 0xffffffffull) {                       // (an offset that 32 bits do not hold: left to the caller's decoder)
+            snprintf(info->reason, sizeof(info->reason), "scan of 4 GB or more");
+            return MDJPEG_ECAPACITY;
+        }
+        seg_offsets[k] = uint32_t(p - P.scan_begin);
+        const size_t m = next_marker(d, size, p);
+        const int want = k + 1 < nseg ? 0xD0 + int(k & 7) : 0xD9;
+        if (m + 2 > size || d[m + 1] != want) {
+            snprintf(info->reason, sizeof(info->reason), "%s", k + 1 < nseg ? "restart marker missing or out of sequence" : "scan is not followed by EOI");
+            return MDJPEG_ECORRUPT;
+        }
+        if (k + 1 == nseg) sc->scan_end = int64_t(m);
+        p = m + 2;
+    }
+    return MDJPEG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -402,7 +472,120 @@ int mdjpeg_decode(const uint8_t* data, size_t size, mdjpeg_info* info, int16_t* 
     return MDJPEG_OK;
 }
 
-const char* mdjpeg_version(void) { return "mdjpeg 1"; }
+int mdjpeg_scan(const uint8_t* data, size_t size, mdjpeg_scan_info* scan, uint32_t* seg_offsets, size_t seg_capacity) {
+    if (!data || !scan || (!seg_offsets && seg_capacity)) return MDJPEG_EINVAL;
+    Parsed P;
+    return scan_file(data, size, scan, P, seg_offsets, seg_capacity);
+}
+
+int mdjpeg_decode_subsequences(const uint8_t* data, size_t size, int subseq_bits, mdjpeg_info* info, int16_t* coef, size_t capacity) {
+    if (!data || !info || !coef || subseq_bits < MDJ_MIN_SUBSEQ_BITS || subseq_bits % 8) return MDJPEG_EINVAL;
+    Parsed P;
+    mdjpeg_scan_info sc;
+    int rc = parse_headers(data, size, info, P);
+    if (rc != MDJPEG_OK) return rc;
+    if (uint64_t(info->coef_count) > uint64_t(capacity)) {
+        snprintf(info->reason, sizeof(info->reason), "coefficient planes need %lld values, capacity is %llu",
+                 (long long)info->coef_count, (unsigned long long)capacity);
+        return MDJPEG_ECAPACITY;
+    }
+    const int64_t total_mcus = int64_t(info->mcus_x) * info->mcus_y;
+    const int64_t nseg = info->restart_interval ? (total_mcus + info->restart_interval - 1) / info->restart_interval : 1;
+    std::vector<uint32_t> seg(size_t(nseg) + 1);
+    rc = scan_file(data, size, &sc, P, seg.data(), size_t(nseg));
+    *info = sc.info;
+    if (rc != MDJPEG_OK) return rc;
+    if (sc.scan_end - sc.scan_begin >= MDJ_MAX_SCAN_BYTES) {
+        snprintf(info->reason, sizeof(info->reason), "scan too long for 32-bit bit positions");
+        return MDJPEG_ECAPACITY;
+    }
+    seg[size_t(nseg)] = uint32_t(sc.scan_end - sc.scan_begin + 2);
+    std::vector<MdjImage> imv(1);
+    MdjImage& im = imv[0];
+    if (!mdj_fill_image(sc, subseq_bits, im)) return fail(info, MDJPEG_EUNSUPPORTED, "Huffman table is not a prefix code");
+    const uint8_t* base = data + sc.scan_begin;
+    // a lane's block count is 16 bits: subsequences longer than MDJ_MAX_SUBSEQ_BITS are taken only where they give every
+    // segment ONE lane, whose count nothing reads
+    if (subseq_bits > MDJ_MAX_SUBSEQ_BITS)
+        for (int64_t k = 0; k < nseg; ++k)
+            if (uint64_t(seg[size_t(k) + 1] - 2 - seg[size_t(k)]) * 8 > uint64_t(subseq_bits)) return MDJPEG_EINVAL;
+    // lanes: every segment is cut into subsequences
+    struct Lane { int64_t seg; uint32_t sub; };
+    std::vector<Lane> lanes;
+    std::vector<size_t> first_lane(size_t(nseg) + 1);
+    for (int64_t k = 0; k < nseg; ++k) {
+        first_lane[size_t(k)] = lanes.size();
+        const uint32_t nb = seg[size_t(k) + 1] - 2 - seg[size_t(k)];
+        const uint32_t n = mdj_lanes_of(nb, uint32_t(subseq_bits));
+        for (uint32_t i = 0; i < n; ++i) lanes.push_back(Lane{k, i});
+    }
+    first_lane[size_t(nseg)] = lanes.size();
+    const size_t L = lanes.size();
+    std::vector<uint64_t> end(L), start(L);
+    auto seg_ptr = [&](int64_t k) { return base + seg[size_t(k)]; };
+    auto seg_len = [&](int64_t k) { return uint32_t(seg[size_t(k) + 1] - 2 - seg[size_t(k)]); };
+    // pass 1: every lane from its own first bit
+    for (size_t l = 0; l < L; ++l) {
+        const Lane& ln = lanes[l];
+        const MdjState s0 = mdj_blind_start(seg_ptr(ln.seg), seg_len(ln.seg), ln.sub, uint32_t(subseq_bits));
+        start[l] = mdj_start_key(mdj_pack(s0));
+        end[l] = mdj_pack(mdj_decode_lane(im, im.tables, seg_ptr(ln.seg), seg_len(ln.seg), s0, mdj_lane_limit(ln.sub, uint32_t(subseq_bits)), nullptr));
+    }
+    // pass 2: carry every lane's end into its right neighbour until nothing changes
+    for (bool changed = true; changed;) {
+        changed = false;
+        std::vector<uint64_t> prev = end;                    // the lanes of a round all see the round before (as the worst GPU schedule would)
+        for (size_t l = 0; l < L; ++l) {
+            const Lane& ln = lanes[l];
+            if (ln.sub == 0) continue;
+            const uint64_t key = mdj_start_key(prev[l - 1]);
+            if (key == start[l]) continue;
+            start[l] = key;
+            end[l] = mdj_pack(mdj_decode_lane(im, im.tables, seg_ptr(ln.seg), seg_len(ln.seg), mdj_unpack(key),
+                                              mdj_lane_limit(ln.sub, uint32_t(subseq_bits)), nullptr));
+            changed = true;
+        }
+    }
+    // pass 3 + 4: output positions, then the final decode
+    memset(coef, 0, size_t(info->coef_count) * sizeof(int16_t));
+    std::vector<uint32_t> energy(size_t(info->coef_count / 64), 0);
+    uint32_t err = 0;
+    for (int64_t k = 0; k < nseg; ++k) {
+        int64_t block = 0;
+        const int64_t first_mcu = k * im.interval;
+        const int64_t mcus = total_mcus - first_mcu < im.interval ? total_mcus - first_mcu : im.interval;
+        for (size_t l = first_lane[size_t(k)]; l < first_lane[size_t(k) + 1]; ++l) {
+            MdjSink sink{coef, energy.data(), first_mcu, block, mcus * im.blocks_per_mcu, 0};
+            const MdjState s = mdj_unpack(start[l]);
+            mdj_decode_lane(im, im.tables, seg_ptr(k), seg_len(k), s, mdj_lane_limit(lanes[l].sub, uint32_t(subseq_bits)), &sink);
+            err |= sink.err;
+            if (l + 1 == first_lane[size_t(k) + 1] && sink.block < sink.blocks) err |= MDJ_ERR_COUNT;
+            block += mdj_unpack(end[l]).n;
+        }
+        if (first_lane[size_t(k)] == first_lane[size_t(k) + 1]) err |= MDJ_ERR_COUNT;
+    }
+    // pass 5: the DC differences become values, per component, anew in every segment
+    if (!err)
+        for (int c = 0; c < im.components; ++c) {
+            const int64_t per_mcu = int64_t(im.h_samp[c]) * im.v_samp[c];
+            const int64_t nblocks = total_mcus * per_mcu;
+            int64_t dc = 0;
+            for (int64_t j = 0; j < nblocks; ++j) {
+                if (j % (im.interval * per_mcu) == 0) dc = 0;
+                const int64_t off = mdj_dc_block_offset(im, c, j);
+                dc += coef[off * 64];
+                err |= mdj_check_block(im, c, dc, energy[size_t(off)]);
+                coef[off * 64] = int16_t(dc);
+            }
+        }
+    if (err) {
+        snprintf(info->reason, sizeof(info->reason), "the final lanes flagged 0x%x", err);
+        return MDJPEG_ECORRUPT;
+    }
+    return MDJPEG_OK;
+}
+
+const char* mdjpeg_version(void) { return "mdjpeg 2"; }
 
 }  // extern "C"
 
@@ -427,6 +610,22 @@ int main(int argc, char** argv) {
             int16_t* coef = new int16_t[size_t(info.coef_count)];
             rc = mdjpeg_decode(exact, bytes.size(), &info, coef, size_t(info.coef_count));
             delete[] coef;
+            // the descriptor and the host model of the GPU decoder, at two subsequence lengths, into exact buffers too
+            mdjpeg_scan_info sc;
+            std::vector<uint32_t> seg(1);
+            int rs = mdjpeg_scan(exact, bytes.size(), &sc, seg.data(), seg.size());
+            if (rs == MDJPEG_ECAPACITY && sc.n_segments > 0) {
+                uint32_t* segs = new uint32_t[size_t(sc.n_segments)];
+                rs = mdjpeg_scan(exact, bytes.size(), &sc, segs, size_t(sc.n_segments));
+                delete[] segs;
+            }
+            for (int bits : {64, 1024}) {
+                mdjpeg_info info2;
+                int16_t* coef2 = new int16_t[size_t(info.coef_count)];
+                const int r2 = mdjpeg_decode_subsequences(exact, bytes.size(), bits, &info2, coef2, size_t(info.coef_count));
+                delete[] coef2;
+                if (r2 != rc) { printf("%s: subsequences of %d bits give %d, mdjpeg_decode %d\n", argv[i], bits, r2, rc); return 3; }
+            }
         }
         printf("%s: rc %d %s\n", argv[i], rc, info.reason);
         delete[] exact;

@@ -42,6 +42,7 @@
 
 #include "../../include/mdhip.h"
 #include "mdhip_internal.h"
+#include "jpeg_subseq.h"
 
 using namespace mdhip;
 
@@ -157,6 +158,9 @@ struct mdhip_ctx {
     size_t stage_bytes = 0;
     char* jpeg_planes = nullptr;  // mdhip_jpeg_reconstruct: u8 component planes between the IDCT and the colour kernel
     size_t jpeg_planes_bytes = 0;
+    char* jpeg_entropy = nullptr; // mdhip_jpeg_entropy_decode: descriptors, lane records, block energies (grows on demand)
+    size_t jpeg_entropy_bytes = 0;
+    long long jpeg_entropy_stats[4] = {0, 0, 0, 0};   // of the last call: lanes, lanes decoded again, pass-2 launches, images
     int last_n = 0, last_h = 0, last_w = 0;
     std::string err;
     // fp8 mode: until every e4m3 tensor has a scale (mdhip_calibrate / mdhip_fp8_set_scales) the forward refuses
@@ -1980,6 +1984,7 @@ void mdhip_destroy(mdhip_ctx* ctx) {
     if (ctx->warena) (void)hipFree(ctx->warena);
     if (ctx->stage) (void)hipFree(ctx->stage);
     if (ctx->jpeg_planes) (void)hipFree(ctx->jpeg_planes);
+    if (ctx->jpeg_entropy) (void)hipFree(ctx->jpeg_entropy);
     if (ctx->geom_host) (void)hipHostFree(ctx->geom_host);
     for (int i = 0; i < 4; ++i) if (ctx->geom_ev[i]) (void)hipEventDestroy(ctx->geom_ev[i]);
     if (ctx->input_free) (void)hipEventDestroy(ctx->input_free);
@@ -2177,6 +2182,176 @@ int mdhip_jpeg_reconstruct(mdhip_ctx* ctx, const mdhip_jpeg_image* images, int n
         devs[i].planes = (uint8_t*)ctx->jpeg_planes;
         HIP_TRY(ctx, launch_jpeg_reconstruct(devs[i], s));
     }
+    return MDHIP_OK;
+}
+
+int mdhip_jpeg_entropy_decode(mdhip_ctx* ctx, const mdhip_jpeg_scan* scans, int n, int subseq_bits, int32_t* status, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!scans || !status) return fail(ctx, MDHIP_EINVAL, "scans/status is NULL");
+    if (n < 1) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
+    if (subseq_bits == 0) subseq_bits = 1024;
+    if (subseq_bits < MDJ_MIN_SUBSEQ_BITS || subseq_bits > MDJ_MAX_SUBSEQ_BITS || subseq_bits % 8)
+        return fail(ctx, MDHIP_EINVAL, "subseq_bits = %d (a multiple of 8 from %d to 65536)", subseq_bits, MDJ_MIN_SUBSEQ_BITS);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int chunk = jpeg_entropy_dc_chunk();
+    // host image of the scratch: [JpegScanDev x n][status x n][counters][per image: MdjImage, seg_off, seg_lane0 | lane records, energy, dc]
+    std::vector<JpegScanDev> devs(n);
+    std::vector<MdjImage> ims(n);
+    std::vector<std::vector<uint32_t>> seg_off(n), seg_lane0(n);
+    struct Off { size_t im, seg_off, seg_lane0, lane_end, lane_start, lane_seg, lane_block, energy, dc_sum, dc_reset; };
+    std::vector<Off> offs(n);
+    size_t cur = align_up(sizeof(JpegScanDev) * n, 256);
+    const size_t status_off = cur;
+    cur = align_up(cur + 4 * (size_t)n, 256);
+    const size_t counters_off = cur;
+    cur = align_up(cur + 16, 256);
+    unsigned max_lanes = 1;
+    long long max_chunks = 1, total_lanes = 0;
+    for (int i = 0; i < n; ++i) {
+        const mdhip_jpeg_scan& q = scans[i];
+        if (!q.desc || !q.seg_offsets || !q.scan || !q.coef || ((uintptr_t)q.coef & 15))
+            return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: desc / seg_offsets / scan / coef is NULL or coef is not 16-byte aligned", i);
+        const mdjpeg_scan_info& sc = *q.desc;
+        const mdjpeg_info& in = sc.info;
+        const long long bytes = sc.scan_end - sc.scan_begin;
+        if (!in.supported || sc.scan_begin < 0 || bytes < 0 || bytes >= MDJ_MAX_SCAN_BYTES)
+            return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: scan range %lld .. %lld of a file that is %ssupported", i, (long long)sc.scan_begin,
+                        (long long)sc.scan_end, in.supported ? "" : "not ");
+        if (!mdj_fill_image(sc, subseq_bits, ims[i]))
+            return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: components, sampling or Huffman tables of the descriptor are not valid", i);
+        const MdjImage& im = ims[i];
+        // the geometry must be the one mdjpeg_parse derives: the kernels' bounds rest on it
+        long long count = 0;
+        bool ok = in.width >= 1 && in.height >= 1 && in.width <= 65535 && in.height <= 65535 && in.restart_interval >= 0 &&
+                  in.mcus_x == (in.width + 8 * in.h_samp[0] - 1) / (8 * in.h_samp[0]) &&
+                  in.mcus_y == (in.height + 8 * in.v_samp[0] - 1) / (8 * in.v_samp[0]);
+        for (int c = 0; ok && c < in.components; ++c) {
+            ok = in.blocks_w[c] == in.mcus_x * in.h_samp[c] && in.blocks_h[c] == in.mcus_y * in.v_samp[c] && in.plane_offset[c] == count;
+            count += (long long)in.blocks_w[c] * in.blocks_h[c] * 64;
+        }
+        if (!ok || count != in.coef_count)
+            return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: plane sizes and offsets contradict the image size and sampling", i);
+        const long long nseg = (im.total_mcus + im.interval - 1) / im.interval;
+        if (nseg != sc.n_segments) return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: %d segments for %lld MCUs at interval %lld", i, sc.n_segments,
+                                               (long long)im.total_mcus, (long long)im.interval);
+        seg_off[i].resize((size_t)nseg + 1);
+        seg_lane0[i].resize((size_t)nseg + 1);
+        long long lanes = 0;
+        for (long long k = 0; k <= nseg; ++k) {
+            const long long o = k < nseg ? (long long)q.seg_offsets[k] : bytes + 2;
+            const long long prev = k ? (long long)seg_off[i][(size_t)k - 1] + 2 : 0;
+            if (o < prev || o > bytes + 2) return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: segment offset %lld outside the scan or out of order", i, o);
+            if (k == 0 && o != 0) return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: the first segment does not begin the scan", i);
+            seg_off[i][(size_t)k] = (uint32_t)o;
+            if (k) lanes += mdj_lanes_of((uint32_t)(o - 2 - seg_off[i][(size_t)k - 1]), (uint32_t)subseq_bits);
+            seg_lane0[i][(size_t)k] = (uint32_t)lanes;
+        }
+        if (lanes > 0x7fffffffLL) return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: too many subsequences", i);
+        for (const void* p : {(const void*)q.scan, (const void*)q.coef}) {
+            hipPointerAttribute_t attr;
+            const hipError_t e = hipPointerGetAttributes(&attr, p);
+            if (e != hipSuccess) (void)hipGetLastError();
+            if (e != hipSuccess || !(attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged))
+                return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: scan and coef must be device memory", i);
+        }
+        JpegScanDev& d = devs[i];
+        d.scan = q.scan;
+        d.coef = q.coef;
+        d.coef_count = in.coef_count;
+        d.n_segments = (uint32_t)nseg;
+        d.n_lanes = (uint32_t)lanes;
+        long long chunks = 0;
+        for (int c = 0; c < 3; ++c) {
+            d.dc_blocks[c] = c < in.components ? (long long)in.blocks_w[c] * in.blocks_h[c] : 0;
+            d.dc_chunks[c] = (d.dc_blocks[c] + chunk - 1) / chunk;
+            chunks += d.dc_chunks[c];
+        }
+        max_lanes = std::max(max_lanes, d.n_lanes);
+        max_chunks = std::max(max_chunks, chunks);
+        total_lanes += lanes;
+        Off& o = offs[i];
+        o.im = cur;          cur = align_up(cur + sizeof(MdjImage), 256);
+        o.seg_off = cur;     cur = align_up(cur + 4 * ((size_t)nseg + 1), 256);
+        o.seg_lane0 = cur;   cur = align_up(cur + 4 * ((size_t)nseg + 1), 256);
+    }
+    const size_t upload_bytes = cur;
+    for (int i = 0; i < n; ++i) {
+        Off& o = offs[i];
+        const size_t lanes = devs[i].n_lanes, blocks = (size_t)(devs[i].coef_count / 64);
+        const size_t chunks = (size_t)(devs[i].dc_chunks[0] + devs[i].dc_chunks[1] + devs[i].dc_chunks[2]);
+        o.lane_end = cur;    cur = align_up(cur + 8 * lanes, 256);
+        o.lane_start = cur;  cur = align_up(cur + 8 * lanes, 256);
+        o.lane_seg = cur;    cur = align_up(cur + 4 * lanes, 256);
+        o.lane_block = cur;  cur = align_up(cur + 4 * lanes, 256);
+        o.energy = cur;      cur = align_up(cur + 4 * blocks, 256);
+        o.dc_sum = cur;      cur = align_up(cur + 8 * chunks, 256);
+        o.dc_reset = cur;    cur = align_up(cur + 4 * chunks, 256);
+    }
+    if (cur > ctx->jpeg_entropy_bytes) {
+        HIP_TRY(ctx, hipDeviceSynchronize());                  // an earlier call's kernels may still use the old scratch
+        if (ctx->jpeg_entropy) HIP_TRY(ctx, hipFree(ctx->jpeg_entropy));
+        ctx->jpeg_entropy = nullptr;
+        ctx->jpeg_entropy_bytes = 0;
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->jpeg_entropy, cur));
+        ctx->jpeg_entropy_bytes = cur;
+    }
+    char* base = ctx->jpeg_entropy;
+    std::vector<char> up(upload_bytes, 0);
+    for (int i = 0; i < n; ++i) {
+        const Off& o = offs[i];
+        JpegScanDev& d = devs[i];
+        d.im = (const MdjImage*)(base + o.im);
+        d.seg_off = (const uint32_t*)(base + o.seg_off);
+        d.seg_lane0 = (const uint32_t*)(base + o.seg_lane0);
+        d.lane_end = (uint64_t*)(base + o.lane_end);
+        d.lane_start = (uint64_t*)(base + o.lane_start);
+        d.lane_seg = (uint32_t*)(base + o.lane_seg);
+        d.lane_block = (uint32_t*)(base + o.lane_block);
+        d.energy = (uint32_t*)(base + o.energy);
+        d.dc_sum = (long long*)(base + o.dc_sum);
+        d.dc_reset = (uint32_t*)(base + o.dc_reset);
+        memcpy(up.data() + o.im, &ims[i], sizeof(MdjImage));
+        memcpy(up.data() + o.seg_off, seg_off[i].data(), 4 * seg_off[i].size());
+        memcpy(up.data() + o.seg_lane0, seg_lane0[i].data(), 4 * seg_lane0[i].size());
+    }
+    memcpy(up.data(), devs.data(), sizeof(JpegScanDev) * n);
+    // (the upload is from pageable memory: the copy has left `up` when the call returns; status and counters arrive zeroed)
+    HIP_TRY(ctx, hipMemcpyAsync(base, up.data(), upload_bytes, hipMemcpyHostToDevice, s));
+    const JpegScanDev* ddevs = (const JpegScanDev*)base;
+    uint32_t* dstatus = (uint32_t*)(base + status_off);
+    unsigned long long* dcounters = (unsigned long long*)(base + counters_off);
+    launch_jpeg_entropy_front(ddevs, n, max_lanes, s);
+    HIP_TRY(ctx, hipGetLastError());
+    // pass 2: until a launch moves no lane.  Every launch settles whole workgroups, so this is two launches unless a change
+    // has to cross workgroups; a chain of lanes that never meet is bounded by the number of lanes.
+    long long launches = 0;
+    unsigned long long counters[2] = {0, 0};
+    for (;;) {
+        launch_jpeg_entropy_sync(ddevs, n, max_lanes, dcounters, s);
+        HIP_TRY(ctx, hipGetLastError());
+        ++launches;
+        HIP_TRY(ctx, hipMemcpyAsync(counters, dcounters, sizeof(counters), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipMemsetAsync(dcounters + 1, 0, 8, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        if (!counters[1]) break;
+        if (launches > (long long)max_lanes + 2) return fail(ctx, MDHIP_EHIP, "the subsequences did not synchronise in %lld launches", launches);
+    }
+    launch_jpeg_entropy_back(ddevs, n, max_lanes, max_chunks, dstatus, s);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(status, dstatus, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    ctx->jpeg_entropy_stats[0] = total_lanes;
+    ctx->jpeg_entropy_stats[1] = (long long)counters[0];
+    ctx->jpeg_entropy_stats[2] = launches;
+    ctx->jpeg_entropy_stats[3] = n;
+    return MDHIP_OK;
+}
+
+int mdhip_jpeg_entropy_stats(mdhip_ctx* ctx, int64_t out[4]) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!out) return fail(ctx, MDHIP_EINVAL, "out is NULL");
+    for (int i = 0; i < 4; ++i) out[i] = ctx->jpeg_entropy_stats[i];
     return MDHIP_OK;
 }
 

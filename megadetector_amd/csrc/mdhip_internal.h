@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct MdjImage;
+
 namespace mdhip {
 
 // ---------------------------------------------------------------------------------------
@@ -476,5 +478,30 @@ hipError_t launch_jpeg_reconstruct(const JpegDev& d, hipStream_t s);
 // (rows `pitch` bytes apart), then the reconstruction above from the planes on.  d: three components, 2 x 2 luma sampling,
 // rotation 0, blocks_w / blocks_h each component's own whole blocks, quant = {luma, chroma, chroma}; d.coef is not read.
 hipError_t launch_jpeg_recompress(const JpegDev& d, const uint8_t* src, long long pitch, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------
+// JPEG entropy decoding (jpeg_huffman.cpp): one record per image of the batch, in device memory
+// ---------------------------------------------------------------------------------------
+struct JpegScanDev {
+    const uint8_t*  scan;         // the entropy-coded bytes of the file
+    int16_t*        coef;         // coef_count values, 16-byte aligned
+    const ::MdjImage* im;
+    const uint32_t* seg_off;      // [n_segments + 1] first byte of each segment; a segment ends 2 bytes in front of the next
+    const uint32_t* seg_lane0;    // [n_segments + 1] first lane of each segment
+    uint64_t*       lane_end;     // [n_lanes] packed MdjState: where the lane's decode ended
+    uint64_t*       lane_start;   // [n_lanes] packed start it decoded from
+    uint32_t*       lane_seg;     // [n_lanes]
+    uint32_t*       lane_block;   // [n_lanes] blocks closed in front of the lane within its segment
+    uint32_t*       energy;       // [coef_count / 64] AC energy of each block
+    long long*      dc_sum;       // [sum of dc_chunks]
+    uint32_t*       dc_reset;
+    long long       coef_count;
+    long long       dc_blocks[3], dc_chunks[3];
+    uint32_t        n_segments, n_lanes;
+};
+void launch_jpeg_entropy_front(const JpegScanDev* devs, int n, unsigned max_lanes, hipStream_t s);
+void launch_jpeg_entropy_sync(const JpegScanDev* devs, int n, unsigned max_lanes, unsigned long long* counters, hipStream_t s);
+void launch_jpeg_entropy_back(const JpegScanDev* devs, int n, unsigned max_lanes, long long max_chunks, uint32_t* status, hipStream_t s);
+int jpeg_entropy_dc_chunk();
 
 }  // namespace mdhip

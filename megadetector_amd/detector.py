@@ -20,7 +20,10 @@ augment=True runs yolov5's augmented inference (three scaled / flipped passes) o
 (mdhip_forward_tta).
 An image may also arrive as a jpeg_host.CoefficientImage (the quantised DCT coefficients of a baseline JPEG, feed.py
 decode='coefficients'): its pixels are rebuilt on the device (mdhip_jpeg_reconstruct), bit for bit what PIL decodes, and
-never exist on the host; `jpeg_images_reconstructed` counts them.
+never exist on the host; `jpeg_images_reconstructed` counts them.  Or as a jpeg_host.ScanImage (the compressed file and the
+descriptor of its scan, feed.py decode='scan'): decode_scans() Huffman-decodes those on the device first
+(mdhip_jpeg_entropy_decode; `jpeg_images_entropy_decoded` counts them) and decodes a file the GPU flags with PIL from the
+bytes it holds (`jpeg_entropy_fallbacks`).
 """
 
 import json
@@ -30,7 +33,7 @@ import numpy as np
 
 from . import weights_io
 from .constants import (FAILURE_IMAGE_OPEN, FAILURE_INFER, DEFAULT_COMPATIBILITY_MODE)
-from .jpeg_host import CoefficientImage, check_quality
+from .jpeg_host import CoefficientImage, DeviceCoefficientImage, ScanFailure, ScanImage, check_quality
 from .postprocess import letterbox_geometry, modern_geometry, format_detections
 
 
@@ -114,6 +117,8 @@ class HIPDetector:
         self.model = None
         self._ctx = None
         self.jpeg_images_reconstructed = 0      # images whose pixels were rebuilt on the device from JPEG coefficients
+        self.jpeg_images_entropy_decoded = 0    # of those: images whose scan was Huffman-decoded on the device too
+        self.jpeg_entropy_fallbacks = 0         # scans the device flagged: decoded with PIL from the file's bytes instead
         if preprocess_only:
             return                      # never touches HIP: safe in forked producer processes
 
@@ -262,6 +267,7 @@ class HIPDetector:
         if self._ctx is None:
             raise RuntimeError('this HIPDetector was created with preprocess_only')
         self._check_augment(augment)
+        img_original = self.decode_scans(img_original)
         results, shape_groups = self._prepare_batch(img_original, image_id, image_size, verbose)
         for shape, items in shape_groups.items():
             try:
@@ -286,6 +292,8 @@ class HIPDetector:
                     current_id = info['file']
                 else:
                     current_id = image_id[i_img]
+                    if isinstance(img, ScanFailure):
+                        raise img.error
                     info = self.preprocess_image(img, image_id=current_id, image_size=image_size, verbose=verbose)
                 preprocessed.append((i_img, info, current_id))
             except Exception as e:
@@ -333,6 +341,53 @@ class HIPDetector:
             results[original_idx] = {'file': current_id, 'detections': detections,
                                      'max_detection_conf': max_conf}
 
+    def decode_scans(self, images):
+        """
+        Replaces every jpeg_host.ScanImage of `images`: one upload of the compressed scans and one mdhip_jpeg_entropy_decode
+        for all of them on the compute stream, the statuses read back once.  A clean file becomes a DeviceCoefficientImage
+        (its planes stay on the device and go through mdhip_jpeg_reconstruct like a CoefficientImage's).  A file the
+        decoder flags is decoded here from the bytes the ScanImage holds, by load_image's own statements (mode handling,
+        EXIF rotation): it becomes the RGB array PIL gives or, when PIL fails too, a ScanFailure carrying that error.
+        Every other entry is returned as it is.
+        """
+        idx = [i for i, im in enumerate(images) if isinstance(im, ScanImage)]
+        if not idx:
+            return images
+        if self._ctx is None:
+            raise RuntimeError('this HIPDetector was created with preprocess_only')
+        import io
+        from .feed import load_image
+        pl = self._pipeline()
+        torch = pl['torch']
+        images = list(images)
+        scan_offs, coef_offs, nbytes, nvals = [], [], 0, 0
+        for i in idx:
+            scan_offs.append(nbytes)
+            nbytes += (images[i].nbytes + 255) // 256 * 256 + 256
+            coef_offs.append(nvals)
+            nvals += (images[i].coef_count + 127) // 128 * 128
+        host = np.zeros(nbytes, dtype=np.uint8)
+        for i, off in zip(idx, scan_offs):
+            host[off:off + images[i].nbytes] = images[i].scan_bytes
+        comp = pl['comp_s']
+        with torch.cuda.device(pl['dev']), torch.cuda.stream(comp):
+            scans = torch.from_numpy(host).to(pl['dev'])
+            coefs = torch.empty(max(nvals, 1), dtype=torch.int16, device=pl['dev'])
+            status = self._ctx.jpeg_entropy_decode([images[i] for i in idx], [scans.data_ptr() + o for o in scan_offs],
+                                                   [coefs.data_ptr() + 2 * o for o in coef_offs], stream=comp.cuda_stream)
+        for i, off, st in zip(idx, coef_offs, status):
+            im = images[i]
+            if st == 0:
+                images[i] = im.coefficient_image(DeviceCoefficientImage.Planes(coefs, off, im.coef_count))
+                self.jpeg_images_entropy_decoded += 1
+                continue
+            self.jpeg_entropy_fallbacks += 1
+            try:
+                images[i] = np.asarray(load_image(io.BytesIO(im.file.tobytes())))
+            except Exception as e:
+                images[i] = ScanFailure(e)
+        return images
+
     def _reconstruct_jpegs(self, images):
         """synchronous path: coefficient images -> device RGB images (integer pointers); returns (images, tensors to keep)"""
         idx = [i for i, im in enumerate(images) if isinstance(im, CoefficientImage)]
@@ -346,7 +401,7 @@ class HIPDetector:
             coefs, outs = [], []
             for i in idx:
                 im = images[i]
-                c = torch.from_numpy(np.array(im.coef, dtype=np.int16)).to(dev)
+                c = im.coef.tensor() if isinstance(im, DeviceCoefficientImage) else torch.from_numpy(np.array(im.coef, dtype=np.int16)).to(dev)
                 o = torch.empty(int(np.prod(im.shape)), dtype=torch.uint8, device=dev)
                 coefs.append(c)
                 outs.append(o)
@@ -546,6 +601,8 @@ class HIPDetector:
                 if pl['consumed'][k] is not None:
                     pl['copy_s'].wait_event(pl['consumed'][k])      # the letterbox kernel that read this buffer is done
                 for im, off in zip(images, offs):
+                    if isinstance(im, DeviceCoefficientImage):
+                        continue                          # its planes are on the device already (decode_scans)
                     flat = im.coef.view(np.uint8) if isinstance(im, CoefficientImage) else im.reshape(-1)
                     if not flat.flags.writeable:          # torch warns on read-only arrays; the copy only reads
                         flat = flat.view()
@@ -561,7 +618,9 @@ class HIPDetector:
             comp.wait_event(pl['copied'][k])
             srcs = [base + off for off in offs]
             if jpeg_idx:
-                ctx.jpeg_reconstruct([images[i] for i in jpeg_idx], [base + offs[i] for i in jpeg_idx],
+                ctx.jpeg_reconstruct([images[i] for i in jpeg_idx],
+                                     [images[i].coef.data_ptr() if isinstance(images[i], DeviceCoefficientImage) else base + offs[i]
+                                      for i in jpeg_idx],
                                      [base + rgb_offs[i] for i in jpeg_idx], stream=comp.cuda_stream)
                 for i in jpeg_idx:
                     srcs[i] = base + rgb_offs[i]
@@ -612,6 +671,7 @@ class HIPDetector:
         self._check_augment(augment)
         if detection_threshold is None:
             detection_threshold = 0.0
+        img_original = self.decode_scans(img_original)
         results, shape_groups = self._prepare_batch(img_original, image_id, image_size, verbose)
         chunks = []
         for shape, items in shape_groups.items():

@@ -17,7 +17,9 @@ takes ~1 ms per image).  Here:
   * an image that does not fit a slot falls back to travelling through the queue as an array;
   * decode='coefficients' (opt-in, run_detector_batch --gpu_jpeg): for a baseline JPEG the loader only Huffman-decodes
     (jpeg_host / libmdjpeg.so) and the slot carries quantised DCT coefficients; the GPU rebuilds the pixels PIL would
-    have produced, bit for bit (mdhip_jpeg_reconstruct).  Any file the entropy decoder does not take cleanly goes the
+    have produced, bit for bit (mdhip_jpeg_reconstruct).  decode='scan' (run_detector_batch --gpu_jpeg_entropy) goes one
+    step further: the loader only parses the headers and the slot carries the compressed file; the GPU also Huffman-decodes
+    (mdhip_jpeg_entropy_decode).  Any file the entropy decoder does not take cleanly goes the
     PIL way above, per file.
 
 This module must stay import-light (numpy + PIL, and jpeg_host's ctypes): it is what the spawned loader processes import,
@@ -80,6 +82,12 @@ def coefficient_image(ring, slot, shape):
     """the jpeg_host.CoefficientImage a loader left in `slot` (views of the ring: nothing is copied)"""
     from . import jpeg_host
     return jpeg_host.CoefficientImage.from_slot(ring.slot(slot), shape)
+
+
+def scan_image(ring, slot, shape):
+    """the jpeg_host.ScanImage a loader left in `slot` (the file's bytes stay views of the ring)"""
+    from . import jpeg_host
+    return jpeg_host.ScanImage.from_slot(ring.slot(slot), shape)
 
 
 class SharedImageRing:
@@ -216,6 +224,44 @@ def _coefficients_to_ring(im_file, buf, slot_bytes, free_q, ready_q, want_meta, 
     return True
 
 
+def _scan_to_ring(im_file, buf, slot_bytes, free_q, ready_q, want_meta, worker_id):
+    """
+    The compressed scan of one baseline JPEG into a ring slot, with its descriptor (jpeg_host.scan_into_slot): no Huffman
+    symbol is decoded here.  Returns False -- having put nothing on the queue -- exactly where _coefficients_to_ring
+    does, except that damage only symbol decoding can see is left for the GPU to flag.
+    """
+    from . import jpeg_host
+    image, rotation = open_for_coefficients(im_file)
+    if image.format != 'JPEG':
+        return False
+    with open(im_file, 'rb') as f:
+        data = f.read()
+    header = jpeg_host.parse(data)
+    if not header.supported or jpeg_host.SLOT_HEADER_BYTES + 2 * header.coef_count > slot_bytes:
+        return False
+    meta = None
+    if want_meta:
+        meta = image_metadata(image)
+        if rotation in (90, 270):
+            meta['width'], meta['height'] = meta['height'], meta['width']
+    slot = free_q.get()
+    try:
+        off = slot * slot_bytes
+        rc = jpeg_host.scan_into_slot(data, buf[off:off + slot_bytes], rotation)
+    except BaseException:
+        free_q.put(slot)
+        raise
+    if rc != jpeg_host.MDJPEG_OK:
+        free_q.put(slot)
+        return False
+    h, w = (header.width, header.height) if rotation in (90, 270) else (header.height, header.width)
+    ready_q.put(('scan', im_file, slot, (h, w, 3), meta, worker_id))
+    return True
+
+
+_FAST_PATHS = {'coefficients': _coefficients_to_ring, 'scan': _scan_to_ring}
+
+
 def _loader_process_main(shm_name, slot_bytes, file_q, free_q, ready_q, want_meta, worker_id, decode='pixels'):
     """Body of a loader process: file names in, (file, slot, shape) out."""
     from multiprocessing import shared_memory
@@ -227,8 +273,8 @@ def _loader_process_main(shm_name, slot_bytes, file_q, free_q, ready_q, want_met
             if im_file is None:
                 break
             try:
-                if decode != 'coefficients' or not _coefficients_to_ring(im_file, buf, slot_bytes, free_q, ready_q,
-                                                                        want_meta, worker_id):
+                fast = _FAST_PATHS.get(decode)
+                if fast is None or not fast(im_file, buf, slot_bytes, free_q, ready_q, want_meta, worker_id):
                     _pixels_to_ring(im_file, buf, slot_bytes, free_q, ready_q, want_meta, worker_id)
             except Exception as e:
                 print('Producer process: image {} cannot be loaded:\n{}'.format(im_file, str(e)))
@@ -248,11 +294,14 @@ class ProcessLoader:
     decode='coefficients': baseline JPEGs arrive as 'jpeg' -- the slot holds quantised DCT coefficients
     (jpeg_host.CoefficientImage.from_slot(ring.slot(slot), shape)), `shape` is that of the rotated RGB image; every
     other file arrives exactly as with decode='pixels' (the default).
+    decode='scan': baseline JPEGs arrive as 'scan' -- the slot holds the file's bytes and the descriptor of its scan
+    (jpeg_host.ScanImage.from_slot), no Huffman symbol decoded; the same files as with 'coefficients', plus those whose
+    damage only symbol decoding can see.
     """
 
     def __init__(self, image_files, n_workers, n_slots, slot_bytes, want_meta=False, decode='pixels'):
-        if decode not in ('pixels', 'coefficients'):
-            raise ValueError("decode must be 'pixels' or 'coefficients', got {!r}".format(decode))
+        if decode not in ('pixels', 'coefficients', 'scan'):
+            raise ValueError("decode must be 'pixels', 'coefficients' or 'scan', got {!r}".format(decode))
         self.ctx = mp.get_context('spawn')
         self.ring = SharedImageRing(n_slots, slot_bytes, self.ctx)
         self.file_q = self.ctx.Queue()

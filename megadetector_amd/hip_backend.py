@@ -212,6 +212,33 @@ class HipContext:
         self._check(self.lib.mdhip_jpeg_reconstruct(self.h, arr, n, C.cast(outs, C.POINTER(C.c_void_p)), C.c_void_p(stream)),
                     'mdhip_jpeg_reconstruct')
 
+    def jpeg_entropy_decode(self, images, scan_ptrs, coef_ptrs, subseq_bits=0, stream=0):
+        """
+        Huffman-decodes the scans of baseline JPEGs on the device (include/mdhip.h: mdhip_jpeg_entropy_decode).
+        images:    jpeg_host.ScanImage objects (descriptor and segment offsets of mdjpeg_scan)
+        scan_ptrs: integer device pointers to each file's entropy-coded bytes [scan_begin, scan_end)
+        coef_ptrs: integer device pointers to room for each image's coefficient planes (16-byte aligned, coef_count int16)
+        Returns the status words (int32 array): 0, or a mask of MDHIP_JPEG_* bits for a file the decoder refuses.
+        """
+        n = len(images)
+        if not (len(scan_ptrs) == len(coef_ptrs) == n):
+            raise ValueError('images, scan_ptrs and coef_ptrs must have one entry per image')
+        arr = (_lib.mdhip_jpeg_scan * max(n, 1))()
+        for i, im in enumerate(images):
+            arr[i].scan, arr[i].coef = int(scan_ptrs[i]), int(coef_ptrs[i])
+            arr[i].desc = C.addressof(im.desc)
+            arr[i].seg_offsets = im.seg_offsets.ctypes.data
+        status = (C.c_int32 * max(n, 1))()
+        self._check(self.lib.mdhip_jpeg_entropy_decode(self.h, arr, n, int(subseq_bits), status, C.c_void_p(stream)),
+                    'mdhip_jpeg_entropy_decode')
+        return np.array(status[:n], dtype=np.int32)
+
+    def jpeg_entropy_stats(self):
+        """of the last jpeg_entropy_decode: {'subsequences', 'decoded_again', 'sync_launches', 'images'}"""
+        out = (C.c_int64 * 4)()
+        self._check(self.lib.mdhip_jpeg_entropy_stats(self.h, out), 'mdhip_jpeg_entropy_stats')
+        return dict(zip(('subsequences', 'decoded_again', 'sync_launches', 'images'), [int(v) for v in out]))
+
     def jpeg_recompress(self, ptrs, sizes, pitches, quality, out_ptrs, stream=0):
         """
         Gives windows of device images the pixels of Image.save(quality=quality) + Image.open, bit for bit, on the device

@@ -32,10 +32,21 @@ class mdjpeg_info(C.Structure):
                 ('supported', C.c_int32), ('reason', C.c_char * 100)]
 
 
+MAX_TABLES = 6
+
+
+class mdjpeg_scan_info(C.Structure):
+    _fields_ = [('info', mdjpeg_info), ('n_tables', C.c_int32), ('dc_table', C.c_int32 * 3), ('ac_table', C.c_int32 * 3),
+                ('huff_counts', (C.c_uint8 * 16) * MAX_TABLES), ('huff_vals', (C.c_uint8 * 256) * MAX_TABLES),
+                ('scan_begin', C.c_int64), ('scan_end', C.c_int64), ('n_segments', C.c_int32), ('reserved', C.c_int32)]
+
+
 #: every symbol include/mdjpeg.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     'mdjpeg_parse': (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(mdjpeg_info)]),
     'mdjpeg_decode': (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(mdjpeg_info), C.c_void_p, C.c_size_t]),
+    'mdjpeg_scan': (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(mdjpeg_scan_info), C.c_void_p, C.c_size_t]),
+    'mdjpeg_decode_subsequences': (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(mdjpeg_info), C.c_void_p, C.c_size_t]),
     'mdjpeg_version': (C.c_char_p, []),
 }
 
@@ -117,6 +128,42 @@ def decode(data, out=None):
     if out.dtype != np.int16 or not out.flags.c_contiguous or not out.flags.writeable:
         raise ValueError('out must be a writeable contiguous int16 array')
     rc = lib.mdjpeg_decode(ptr, n, C.byref(info), out.ctypes.data, out.size)
+    return rc, JpegHeader(info, rc), out
+
+
+def scan(data, seg_out=None):
+    """
+    The descriptor of the scan for the GPU's entropy decoder (mdjpeg_scan): no Huffman symbol is decoded.  seg_out: a
+    contiguous uint32 array for the segment offsets (allocated when None).  Returns (rc, mdjpeg_scan_info, offsets): with
+    rc == MDJPEG_OK the first n_segments values of `offsets` are each restart segment's first byte, counted from
+    scan_begin; otherwise info.reason says why the file is left to the caller's decoder.
+    """
+    hold, ptr, n = _as_buffer(data)
+    lib = load()
+    sc = mdjpeg_scan_info()
+    if seg_out is None:
+        seg_out = np.empty((64,), dtype=np.uint32)
+        rc = lib.mdjpeg_scan(ptr, n, C.byref(sc), seg_out.ctypes.data, seg_out.size)
+        if rc != MDJPEG_ECAPACITY or sc.n_segments <= seg_out.size:
+            return rc, sc, seg_out
+        seg_out = np.empty((sc.n_segments,), dtype=np.uint32)
+    if seg_out.dtype != np.uint32 or not seg_out.flags.c_contiguous or not seg_out.flags.writeable:
+        raise ValueError('seg_out must be a writeable contiguous uint32 array')
+    rc = lib.mdjpeg_scan(ptr, n, C.byref(sc), seg_out.ctypes.data, seg_out.size)
+    return rc, sc, seg_out
+
+
+def decode_subsequences(data, subseq_bits, out=None):
+    """The host model of the GPU entropy decoder (mdjpeg_decode_subsequences): results as decode().  For tests."""
+    hold, ptr, n = _as_buffer(data)
+    lib = load()
+    info = mdjpeg_info()
+    if out is None:
+        rc = lib.mdjpeg_parse(ptr, n, C.byref(info))
+        if rc != MDJPEG_OK:
+            return rc, JpegHeader(info, rc), None
+        out = np.empty((int(info.coef_count),), dtype=np.int16)
+    rc = lib.mdjpeg_decode_subsequences(ptr, n, int(subseq_bits), C.byref(info), out.ctypes.data, out.size)
     return rc, JpegHeader(info, rc), out
 
 
@@ -210,6 +257,118 @@ class CoefficientImage:
         quant = slot_view[_SLOT_QUANT_OFF:_SLOT_QUANT_OFF + 384].view(np.uint16).reshape(3, 64)
         coef = slot_view[SLOT_HEADER_BYTES:SLOT_HEADER_BYTES + 2 * int(head[7])].view(np.int16)
         im = cls(head[1], head[2], nc, head[4], head[5], head[6], head[8:8 + nc], head[11:11 + nc], quant, coef)
+        if shape is not None and tuple(shape) != im.shape:
+            raise ValueError('slot holds a {} image, the queue announced {}'.format(im.shape, tuple(shape)))
+        return im
+
+
+class DeviceCoefficientImage(CoefficientImage):
+    """A CoefficientImage whose planes are in device memory already (the GPU's entropy decoder wrote them): `.coef` is a
+    Planes record instead of a host array, and nothing of it is copied."""
+
+    class Planes:
+        """count int16 values at element `offset` of a device tensor (kept alive by this record)"""
+
+        def __init__(self, tensor, offset, count):
+            self.base, self.offset, self.count = tensor, int(offset), int(count)
+            self.nbytes = 0                   # bytes a host-to-device copy has to move
+
+        def data_ptr(self):
+            return self.base.data_ptr() + 2 * self.offset
+
+        def tensor(self):
+            return self.base[self.offset:self.offset + self.count]
+
+
+class ScanFailure:
+    """stands for a file the GPU's entropy decoder flagged and PIL could not decode either; .error is PIL's exception"""
+
+    def __init__(self, error):
+        self.error = error
+
+
+# ---- a JPEG as its compressed scan in a ring slot (feed.py decode='scan') ---------------------------------------------
+# slot = [16 x int32 header][mdjpeg_scan_info][uint32 segment offsets][the file's bytes]: the loader decodes no Huffman
+# symbol, and the detector holds the whole file, so that it can decode a file the GPU flags with PIL itself
+SCAN_SLOT_MAGIC = 0x4D444A32
+_SCAN_DESC_OFF = 64
+_SCAN_SEG_OFF = (_SCAN_DESC_OFF + C.sizeof(mdjpeg_scan_info) + 255) // 256 * 256
+
+
+def scan_into_slot(data, slot_view, rotation):
+    """Writes the descriptor of `data` (the file's bytes) and the bytes themselves into the flat uint8 view of a slot.
+    Returns the code of mdjpeg_scan; MDJPEG_ECAPACITY also when the slot is too small for the file."""
+    arr, _, n = _as_buffer(data)
+    room = slot_view.size - _SCAN_SEG_OFF - n
+    if room < 4:
+        return MDJPEG_ECAPACITY
+    seg = slot_view[_SCAN_SEG_OFF:_SCAN_SEG_OFF + room // 4 * 4].view(np.uint32)
+    rc, sc, _ = scan(arr, seg_out=seg)
+    if rc != MDJPEG_OK:
+        return rc
+    file_off = (_SCAN_SEG_OFF + 4 * sc.n_segments + 255) // 256 * 256
+    if file_off + n > slot_view.size:
+        return MDJPEG_ECAPACITY
+    head = slot_view[:64].view(np.int32)
+    head[:] = 0
+    head[0:5] = (SCAN_SLOT_MAGIC, int(rotation), sc.n_segments, file_off, n)
+    C.memmove(slot_view[_SCAN_DESC_OFF:].ctypes.data, C.addressof(sc), C.sizeof(sc))
+    slot_view[file_off:file_off + n] = arr
+    return rc
+
+
+class ScanImage:
+    """
+    A JPEG as the GPU's entropy decoder takes it: the descriptor of mdjpeg_scan, the segment offsets and the file's bytes.
+    `.shape` is that of the RGB image mdhip_jpeg_reconstruct writes in the end (rotated H x W x 3).
+    """
+
+    ndim = 3
+    dtype = np.dtype(np.uint8)
+
+    def __init__(self, desc, seg_offsets, file_bytes, rotation):
+        self.desc, self.seg_offsets, self.file, self.rotation = desc, seg_offsets, file_bytes, int(rotation)
+        info = desc.info
+        self.width, self.height, self.components = int(info.width), int(info.height), int(info.components)
+        self.coef_count = int(info.coef_count)
+        self.shape = (self.width, self.height, 3) if self.rotation in (90, 270) else (self.height, self.width, 3)
+
+    @property
+    def scan_bytes(self):
+        """view of the entropy-coded bytes [scan_begin, scan_end)"""
+        return self.file[int(self.desc.scan_begin):int(self.desc.scan_end)]
+
+    @property
+    def nbytes(self):
+        return int(self.desc.scan_end - self.desc.scan_begin)
+
+    def coefficient_image(self, coef=None):
+        """the CoefficientImage of this file once its planes are decoded (coef: what holds them, may stay None)"""
+        i = self.desc.info
+        nc = self.components
+        quant = np.ctypeslib.as_array(i.quant).reshape(3, 64).copy()
+        kind = DeviceCoefficientImage if isinstance(coef, DeviceCoefficientImage.Planes) else CoefficientImage
+        return kind(i.width, i.height, nc, i.h_samp[0], i.v_samp[0], self.rotation, i.blocks_w[:nc], i.blocks_h[:nc], quant, coef)
+
+    @classmethod
+    def from_bytes(cls, data, rotation=0):
+        """-> (rc, ScanImage or None, reason) from a file's bytes"""
+        arr, _, _ = _as_buffer(data)
+        rc, sc, seg = scan(arr)
+        if rc != MDJPEG_OK:
+            return rc, None, sc.info.reason.decode('ascii', 'replace')
+        return rc, cls(sc, seg[:sc.n_segments].copy(), arr, rotation), ''
+
+    @classmethod
+    def from_slot(cls, slot_view, shape=None):
+        """from the flat uint8 view of a ring slot written by scan_into_slot (the descriptor is copied, the bytes are views)"""
+        head = slot_view[:64].view(np.int32)
+        if int(head[0]) != SCAN_SLOT_MAGIC:
+            raise ValueError('ring slot does not hold a JPEG scan')
+        sc = mdjpeg_scan_info()
+        C.memmove(C.addressof(sc), slot_view[_SCAN_DESC_OFF:].ctypes.data, C.sizeof(sc))
+        seg = slot_view[_SCAN_SEG_OFF:_SCAN_SEG_OFF + 4 * int(head[2])].view(np.uint32)
+        im = cls(sc, seg, slot_view[int(head[3]):int(head[3]) + int(head[4])], int(head[1]))
         if shape is not None and tuple(shape) != im.shape:
             raise ValueError('slot holds a {} image, the queue announced {}'.format(im.shape, tuple(shape)))
         return im

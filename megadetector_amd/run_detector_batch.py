@@ -34,10 +34,13 @@ import threading
 import time
 from datetime import datetime
 
+import numpy as np
+
 from . import feed, placement, run_detector
 from .feed import load_image, EXIF_IMAGE_ROTATIONS          # noqa: F401  (re-exported)
 from .constants import FAILURE_IMAGE_OPEN, FAILURE_INFER, DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD
 from .constants import DEFAULT_DETECTOR_LABEL_MAP
+from .jpeg_host import ScanFailure
 
 # reference run_detector_batch.py:86-119
 default_loaders = 4
@@ -382,7 +385,7 @@ ring_slots_per_batch_image = 3                  # one batch being filled, two in
 
 
 #: how the files of the most recent shared-ring run reached the detector: 'jpeg' = as DCT coefficients (gpu_jpeg), 'slot' /
-#: 'array' = as PIL pixels, 'fail' = could not be opened
+#: 'array' = as PIL pixels, 'fail' = could not be opened; with gpu_jpeg='entropy' also 'scan' = as the compressed scan
 last_feed_counts = {}
 
 
@@ -394,19 +397,27 @@ def _run_detector_with_shared_ring(image_files, detector, confidence_threshold, 
     the batches go through the detector's pipelined interface.  Same results as every other mode.
     gpu_jpeg: the loaders only entropy-decode baseline JPEGs and the detector rebuilds their pixels on the GPU
     (feed.py decode='coefficients'); needs a detector that takes coefficient images (HIPDetector).
+    gpu_jpeg='entropy': the loaders only parse the headers and the GPU Huffman-decodes too (feed.py decode='scan',
+    HIPDetector.decode_scans); a file the GPU flags is decoded with PIL in this process from the bytes it holds.
     """
     global last_feed_counts
     last_feed_counts = {'jpeg': 0, 'slot': 0, 'array': 0, 'fail': 0}
     if gpu_jpeg and not hasattr(detector, 'jpeg_images_reconstructed'):
         print('Warning: gpu_jpeg is ignored: this detector does not take JPEG coefficients')
         gpu_jpeg = False
+    if gpu_jpeg == 'entropy' and not hasattr(detector, 'decode_scans'):
+        print('Warning: gpu_jpeg="entropy" is ignored: this detector does not take JPEG scans')
+        gpu_jpeg = False
+    entropy = gpu_jpeg == 'entropy'
+    if entropy:
+        last_feed_counts['scan'] = 0
     bs = max(1, batch_size)
     n_workers = max(1, min(loader_workers, len(image_files)))
     n_slots = ring_slots_per_batch_image * bs + n_workers
     try:
         loader = feed.ProcessLoader(image_files, n_workers, n_slots, ring_slot_bytes,
                                     want_meta=include_image_size or include_image_timestamp,
-                                    decode='coefficients' if gpu_jpeg else 'pixels')
+                                    decode='scan' if entropy else 'coefficients' if gpu_jpeg else 'pixels')
     except (OSError, MemoryError) as e:
         # e.g. a container whose /dev/shm is smaller than the ring: the thread queue needs no shared memory
         print('Warning: cannot create the shared-memory ring ({} slots of {} MB: {}); using loader threads'.format(
@@ -421,7 +432,27 @@ def _run_detector_with_shared_ring(image_files, detector, confidence_threshold, 
         pipe = _BatchPipeline(detector, confidence_threshold, include_image_size, include_image_timestamp, on_results)
         pending = []
 
+        def decode_scans():
+            """gpu_jpeg='entropy': the batch's scans become device coefficient images, or what PIL makes of a flagged file --
+            pixels, or the failure the loader would have reported"""
+            images = detector.decode_scans([it[1] for it in pending])
+            kept = []
+            for (f, _, meta_img, release), im in zip(pending, images):
+                if isinstance(im, ScanFailure):
+                    print('Image {} cannot be loaded:\n{}'.format(f, str(im.error)))
+                    if release is not None:
+                        release()
+                    on_results([{'file': f, 'failure': FAILURE_IMAGE_OPEN}])
+                elif isinstance(im, np.ndarray) and release is not None:
+                    release()                                # PIL's pixels are an array of this process: the slot is free
+                    kept.append((f, im, meta_img, None))
+                else:
+                    kept.append((f, im, meta_img, release))
+            pending[:] = kept
+
         def flush():
+            if pending and entropy:
+                decode_scans()
             if not pending:
                 return
             if bs > 1:
@@ -451,6 +482,9 @@ def _run_detector_with_shared_ring(image_files, detector, confidence_threshold, 
                 slot = payload
                 pending.append((im_file, feed.coefficient_image(ring, slot, shape), meta_img,
                                 (lambda s=slot: ring.release(s))))
+            elif kind == 'scan':
+                slot = payload
+                pending.append((im_file, feed.scan_image(ring, slot, shape), meta_img, (lambda s=slot: ring.release(s))))
             else:
                 pending.append((im_file, payload, meta_img, None))
             if len(pending) >= bs:
@@ -496,7 +530,8 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
     object -- used by run_sharded and by the CPU tests of the loop with a stub detector.
     `gpu_jpeg` (extra, default off): in the shared-ring mode (use_image_queue with loader processes) baseline JPEGs travel
     as DCT coefficients and are rebuilt on the GPU, bit for bit what PIL decodes; every other file, and every other mode,
-    runs as without it.
+    runs as without it.  gpu_jpeg='entropy' (--gpu_jpeg_entropy): they travel as their compressed scan and the GPU
+    Huffman-decodes them too; a file the GPU flags is decoded with PIL here from its bytes.  Same results either way.
     Returns the list of per-image result dicts.
     """
     global verbose
@@ -567,7 +602,7 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
     if use_image_queue and not use_threads_for_queue and len(image_files) > 0:
         _run_detector_with_shared_ring(image_files, detector, confidence_threshold, quiet, image_size,
                                        include_image_size, include_image_timestamp, augment, loader_workers,
-                                       batch_size, on_results, gpu_jpeg=bool(gpu_jpeg))
+                                       batch_size, on_results, gpu_jpeg='entropy' if gpu_jpeg == 'entropy' else bool(gpu_jpeg))
     elif use_image_queue:
         _run_detector_with_image_queue(image_files, detector, confidence_threshold, quiet, image_size,
                                        include_image_size, include_image_timestamp, augment, loader_workers,
@@ -836,6 +871,9 @@ def main(argv=None):
     ap.add_argument('--gpu_jpeg', action='store_true',
                     help='with --use_image_queue and loader processes: the loaders only entropy-decode baseline JPEGs, the GPU '
                          'rebuilds the pixels PIL would have decoded (bit for bit); other files are decoded with PIL as usual')
+    ap.add_argument('--gpu_jpeg_entropy', action='store_true',
+                    help='as --gpu_jpeg, and the GPU Huffman-decodes too: the loaders only parse the headers and ship the '
+                         'compressed scan; a file the GPU flags is decoded with PIL in the detector process')
     ap.add_argument('--verbose', action='store_true')
     args = ap.parse_args(argv)
 
@@ -880,7 +918,8 @@ def main(argv=None):
                   include_image_timestamp=args.include_image_timestamp, augment=args.augment,
                   detector_options=parse_kvp_list(args.detector_options), loader_workers=args.loader_workers,
                   preprocess_on_image_queue=args.preprocess_on_image_queue, batch_size=args.batch_size,
-                  verbose_output=args.verbose, use_threads_for_queue=args.use_threads_for_queue, gpu_jpeg=args.gpu_jpeg)
+                  verbose_output=args.verbose, use_threads_for_queue=args.use_threads_for_queue,
+                  gpu_jpeg='entropy' if args.gpu_jpeg_entropy else args.gpu_jpeg)
     t0 = time.time()
     if args.n_gpus > 1:
         results = run_sharded(args.detector_file, files, args.n_gpus, results=results, **kwargs)

@@ -1,12 +1,18 @@
 """
-Measures the GPU JPEG feed (run_detector_batch --gpu_jpeg), each figure next to its baseline from the same run.
+Measures the GPU JPEG feed (run_detector_batch --gpu_jpeg / --gpu_jpeg_entropy), each figure next to its baseline from
+the same run.
 
-  host (no GPU needed)   per file, single thread, same process: mdjpeg_parse + mdjpeg_decode (entropy decode only)
-                         against np.asarray(load_image(f)) (PIL's full decode), median of >= 20 repeats, on JPEGs
-                         written here with Pillow from seeded images at 3 MP (4:2:0 and 4:2:2, quality 75 / 90 / 95)
-  --gpu                  the reconstruction kernels alone (events around mdhip_jpeg_reconstruct, batch 32), and the
-                         end-to-end run_detector_batch rate with and without gpu_jpeg on the same files with the same
-                         number of loader processes
+  host (no GPU needed)   per file, single thread, same process, the loader's work in its three modes: np.asarray(load_image(f))
+                         (PIL's full decode), mdjpeg_parse + mdjpeg_decode (entropy decode only, --gpu_jpeg), and
+                         mdjpeg_parse + mdjpeg_scan + the copy of the file into a slot (no symbol decoded,
+                         --gpu_jpeg_entropy); median and quartiles of >= 20 repeats, the three modes interleaved repeat by
+                         repeat, on JPEGs written here with Pillow from seeded images at 3 MP (4:2:0 and 4:2:2, quality
+                         75 / 90 / 95, with and without restart markers)
+  --gpu                  the kernels alone, batch 32: mdhip_jpeg_entropy_decode (whole call, it returns when the planes are
+                         written; with the subsequences, repeated decodes and pass-2 launches it needed) and
+                         mdhip_jpeg_reconstruct (events on the stream); and the end-to-end run_detector_batch rate without
+                         a switch, with gpu_jpeg and with gpu_jpeg='entropy' on the same files with the same number of
+                         loader processes, interleaved
 
     python tools/jpeg_feed_bench.py [--gpu] [--out profiles/jpeg_feed.txt] [--files 64] [--loader_workers 12]
 """
@@ -42,12 +48,15 @@ def seeded_image(seed, w=W3MP, h=H3MP):
 
 
 def write_files(folder, n, variants):
+    """variants: (subsampling, quality) or (subsampling, quality, restart_marker_rows)"""
     from PIL import Image
     out = []
     for i in range(n):
-        sub, q = variants[i % len(variants)]
-        p = os.path.join(folder, 'f{:03d}_{}_q{}.jpg'.format(i, '420' if sub == 2 else '422', q))
-        Image.fromarray(seeded_image(i % 8)).save(p, 'JPEG', quality=q, subsampling=sub)
+        sub, q = variants[i % len(variants)][:2]
+        rst = variants[i % len(variants)][2] if len(variants[i % len(variants)]) > 2 else 0
+        p = os.path.join(folder, 'f{:03d}_{}_q{}{}.jpg'.format(i, '420' if sub == 2 else '422', q, '_rst' if rst else ''))
+        kw = {'restart_marker_rows': rst} if rst else {}
+        Image.fromarray(seeded_image(i % 8)).save(p, 'JPEG', quality=q, subsampling=sub, **kw)
         out.append(p)
     return out
 
@@ -61,28 +70,52 @@ def median_ms(fn, repeats):
     return float(np.median(ts))
 
 
+def interleaved_ms(fns, repeats):
+    """times the callables in turn, repeat by repeat; -> per callable (median, lower quartile, upper quartile) in ms"""
+    ts = [[] for _ in fns]
+    for _ in range(repeats):
+        for k, fn in enumerate(fns):
+            t0 = time.perf_counter()
+            fn()
+            ts[k].append((time.perf_counter() - t0) * 1e3)
+    return [tuple(float(np.percentile(t, q)) for q in (50, 25, 75)) for t in ts]
+
+
 def host_part(folder, repeats, say):
     from megadetector_amd import jpeg_host
     from megadetector_amd.feed import load_image
-    say('host, one thread, median of {} repeats per file, {} x {} pixels'.format(repeats, W3MP, H3MP))
-    say('{:<10} {:>8} {:>12} {:>18} {:>18} {:>8}'.format('sampling', 'quality', 'file bytes', 'entropy only ms', 'PIL full decode ms', 'ratio'))
+    say('host, one thread, {} repeats per file with the three modes interleaved, {} x {} pixels; median [quartiles] in ms'.format(
+        repeats, W3MP, H3MP))
+    say('{:<8} {:>4} {:>4} {:>10}  {:>22} {:>22} {:>22} {:>10} {:>12}'.format(
+        'sampling', 'q', 'rst', 'file bytes', 'PIL full decode', 'coefficients (--gpu_jpeg)', 'scan (--gpu_jpeg_entropy)', 'coef/scan',
+        'margin ms'))
     rows = []
-    for sub, q in [(2, 75), (2, 90), (2, 95), (1, 75), (1, 90), (1, 95)]:
-        p = write_files(folder, 1, [(sub, q)])[0]
+    for sub, q, rst in [(2, 75, 0), (2, 90, 0), (2, 95, 0), (1, 75, 0), (1, 90, 0), (1, 95, 0), (2, 75, 1), (2, 90, 1), (2, 95, 1), (1, 90, 1)]:
+        p = write_files(folder, 1, [(sub, q, rst)])[0]
         data = open(p, 'rb').read()
         hd = jpeg_host.parse(data)
         buf = np.empty(hd.coef_count, dtype=np.int16)
+        slot = np.empty(jpeg_host.SLOT_HEADER_BYTES + 2 * hd.coef_count, dtype=np.uint8)
 
-        def ours():
+        def coefficients():
             assert jpeg_host.parse(data).supported
             rc, _, _ = jpeg_host.decode(data, out=buf)
             assert rc == 0
 
-        t_ours = median_ms(ours, repeats)
-        t_pil = median_ms(lambda: np.asarray(load_image(p)), repeats)
-        rows.append((sub, q, t_ours, t_pil))
-        say('{:<10} {:>8} {:>12} {:>18.2f} {:>18.2f} {:>8.2f}'.format('4:2:0' if sub == 2 else '4:2:2', q, len(data), t_ours, t_pil,
-                                                                     t_pil / t_ours))
+        def scan():
+            assert jpeg_host.parse(data).supported
+            assert jpeg_host.scan_into_slot(data, slot, 0) == 0
+
+        t_pil, t_coef, t_scan = interleaved_ms([lambda: np.asarray(load_image(p)), coefficients, scan], repeats)
+        # the margin: the slower quartile of the scan leg against the faster quartile of the coefficient leg
+        margin = t_coef[1] - t_scan[2]
+        rows.append((sub, q, rst, t_pil, t_coef, t_scan, margin))
+        fmt = lambda t: '{:8.2f} [{:6.2f} {:6.2f}]'.format(*t)
+        say('{:<8} {:>4} {:>4} {:>10}  {:>22} {:>22} {:>22} {:>10.1f} {:>12.2f}'.format(
+            '4:2:0' if sub == 2 else '4:2:2', q, 'rows' if rst else '-', len(data), fmt(t_pil), fmt(t_coef), fmt(t_scan),
+            t_coef[0] / t_scan[0], margin))
+    say('margin = lower quartile of the coefficient leg minus upper quartile of the scan leg: positive means the scan mode is '
+        'faster by more than the spread of both')
     return rows
 
 
@@ -90,7 +123,7 @@ def gpu_part(folder, n_files, loader_workers, say):
     import torch
     from megadetector_amd import feed, jpeg_host, run_detector, run_detector_batch as RDB
     from megadetector_amd.jpeg_host import CoefficientImage
-    files = write_files(folder, n_files, [(2, 90), (1, 90), (2, 75), (2, 95)])
+    files = write_files(folder, n_files, [(2, 90), (1, 90), (2, 75), (2, 95), (2, 90, 1), (1, 75), (2, 75, 1), (1, 95)])
     det = run_detector.load_detector('synthetic', detector_options={'batch_size': 32})
     ctx = det._ctx
     # --- the kernels alone: 32 images resident on the device
@@ -120,17 +153,44 @@ def gpu_part(folder, n_files, loader_workers, say):
         '(20 calls, events on the stream)'.format(len(images), px / 1e6, float(np.median(ts)), min(ts)))
     want = np.asarray(feed.load_image(files[0]))
     assert np.array_equal(outs[0].cpu().numpy().reshape(want.shape), want), 'reconstruction differs from PIL'
-    del coefs, outs
+    # --- the entropy kernels alone: the same 32 files as compressed scans resident on the device
+    scans = []
+    for f in files[:32]:
+        rc, si, why = jpeg_host.ScanImage.from_bytes(open(f, 'rb').read())
+        assert rc == 0, why
+        scans.append(si)
+    dscan = [torch.from_numpy(np.array(si.scan_bytes)).cuda() for si in scans]
+    sp = [t.data_ptr() for t in dscan]
+    torch.cuda.synchronize()
+    for bits in (1024, 512, 2048):
+        for _ in range(2):
+            status = ctx.jpeg_entropy_decode(scans, sp, cp, bits, stream=s.cuda_stream)
+        assert (status == 0).all()
+        ts = []
+        for _ in range(10):
+            t0 = time.perf_counter()
+            ctx.jpeg_entropy_decode(scans, sp, cp, bits, stream=s.cuda_stream)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        st = ctx.jpeg_entropy_stats()
+        say('kernels alone: mdhip_jpeg_entropy_decode of {} images, {} scan bytes, subsequences of {} bits: median {:.3f} ms, min '
+            '{:.3f} ms per call (10 calls, host clock around the synchronous call: upload of the descriptors, all passes, '
+            'status read-back); {} subsequences, {:.2f} decodes per subsequence in pass 2, {} pass-2 launches'.format(
+                len(scans), sum(si.nbytes for si in scans), bits, float(np.median(ts)), min(ts), st['subsequences'],
+                st['decoded_again'] / max(st['subsequences'], 1), st['sync_launches']))
+    ctx.jpeg_entropy_decode(scans, sp, cp, 0, stream=s.cuda_stream)
+    for c, im, f in list(zip(coefs, images, files))[:4]:
+        assert np.array_equal(c.cpu().numpy(), np.asarray(im.coef)), 'entropy decode differs from mdjpeg_decode: ' + f
+    del coefs, outs, dscan
     # --- end to end
     say('')
     say('end to end: run_detector_batch, {} files of 3 MP, batch 32, {} loader processes, shared ring'.format(len(files), loader_workers))
-    for gpu_jpeg in (False, True, False, True):
+    for gpu_jpeg in (False, True, 'entropy', False, True, 'entropy'):
         t0 = time.perf_counter()
         res = RDB.load_and_run_detector_batch('synthetic', files, quiet=True, detector=det, batch_size=32, use_image_queue=True,
                                               use_threads_for_queue=False, loader_workers=loader_workers, gpu_jpeg=gpu_jpeg)
         dt = time.perf_counter() - t0
         assert len(res) == len(files) and not any('failure' in r for r in res)
-        say('  gpu_jpeg={!s:<5}  {:.2f} s  {:.1f} images/s (includes starting the loader processes)  feed {}'.format(
+        say('  gpu_jpeg={!s:<8}  {:.2f} s  {:.1f} images/s (includes starting the loader processes)  feed {}'.format(
             gpu_jpeg, dt, len(files) / dt, dict(RDB.last_feed_counts)))
 
 
