@@ -34,6 +34,7 @@ extern "C" {
 #define MDHIP_EHIP         -2   /* a HIP runtime call failed                     */
 #define MDHIP_ENOMEM       -3   /* device arena too small for the request        */
 #define MDHIP_EUNSUPPORTED -4   /* valid request this build does not implement   */
+#define MDHIP_ECAPACITY    -5   /* mdhip_jpeg_encode: the output buffer is too small */
 
 /* arithmetic type of the conv stack */
 #define MDHIP_DTYPE_BF16 0
@@ -270,6 +271,32 @@ int mdhip_jpeg_entropy_stats(mdhip_ctx* ctx, int64_t out[4]);
 int mdhip_jpeg_recompress(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
                           const int64_t* pitches, int n, const uint16_t quant_luma[64], const uint16_t quant_chroma[64],
                           uint8_t* const* out_rgb, void* hip_stream);
+
+/* Entropy ENCODING of windows of device images (the reference cuts every detection out of a second PIL decode of the file and
+ * saves it as a quality-95 JPEG, postprocessing/create_crop_folder.py): for each of n windows the entropy-coded scan of the
+ * file Image.fromarray(window).save(f, 'JPEG', quality = q) writes, byte for byte -- every byte between the SOS header and
+ * the EOI marker.  mdhip_jpeg_recompress's lossy half (same arithmetic, same statements), then a baseline Huffman encoder:
+ * three components, 4:2:0, one interleaved scan without restart markers, the standard's four tables (what Pillow emits
+ * without `optimize`), DC differences along the MCU order, FF bytes stuffed with 00, the last byte padded with 1-bits (and
+ * stuffed when that makes it FF).  The bytes in front of and behind the scan depend on size and quality only
+ * (megadetector_amd/jpeg_host.py jfif_file).  One launch grid per pass for the whole batch.
+ *   windows, widths, heights, pitches, quant_luma, quant_chroma   as for mdhip_jpeg_recompress; at most 2^21 blocks a window
+ *   out, capacity   ONE caller-owned DEVICE buffer of `capacity` bytes (out may be NULL when capacity is 0)
+ *   offsets, sizes  HOST arrays of n values: window i's scan lies at out[offsets[i]], sizes[i] bytes; the scans lie one behind
+ *                   the other in the order of the windows
+ *   needed          HOST: the capacity this call needs
+ * MDHIP_ECAPACITY when *needed > capacity: nothing is written at or beyond out[capacity], offsets / sizes / *needed are valid,
+ * and the same call with a buffer of *needed bytes succeeds -- so a caller retries once.  mdhip_jpeg_encode_bound(w, h) is
+ * a capacity that always suffices for one window, derived from the worst code lengths of the standard tables and not from
+ * a trial: a block costs at most 11 + 11 bits of DC and 63 x (16 + 10) bits of AC = 1660 bits, a window pads at most 7
+ * bits, and stuffing at most doubles the bytes: 8 x (52 x blocks + 1) bytes, blocks = 6 x ((w + 15) / 16) x ((h + 15) / 16);
+ * -1 for a size outside 1 .. 65535.  Typical scans take a few per cent of it.
+ * The call returns when the scans are written (it reads sizes and statuses back, once).  Scratch grows on demand (the
+ * device is synchronised when it does): keep all mdhip_jpeg_encode calls of one context on ONE stream. */
+int mdhip_jpeg_encode(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
+                      const int64_t* pitches, int n, const uint16_t quant_luma[64], const uint16_t quant_chroma[64], uint8_t* out,
+                      int64_t capacity, int64_t* offsets, int64_t* sizes, int64_t* needed, void* hip_stream);
+long long mdhip_jpeg_encode_bound(int width, int height);
 
 /* Test-time augmentation: replaces mdhip_forward for `model(batch, augment=True)` (reference
  * pytorch_detector.py:1313 -> yolov5 _forward_augment): three passes over the batch that mdhip_preprocess

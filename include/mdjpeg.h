@@ -85,6 +85,27 @@ int mdjpeg_scan(const uint8_t* data, size_t size, mdjpeg_scan_info* scan, uint32
  * results and return codes are those of mdjpeg_decode; info->reason differs.  The loaders do not call it. */
 int mdjpeg_decode_subsequences(const uint8_t* data, size_t size, int subseq_bits, mdjpeg_info* info, int16_t* coef, size_t capacity);
 
+/* ---- entropy ENCODING (GPU: mdhip_jpeg_encode, include/mdhip.h) ------------------------------------------------------- */
+/* The host model of the GPU entropy encoder, for tests: the same passes -- bit length of every block, prefix sum, bit
+ * writing at the offsets, stuffing in chunks of `chunk_bytes` unstuffed bytes (any size from 1 up; the device uses 64) --
+ * as loops over "lanes", with the per-block encoder, the offset arithmetic and the stuffing chunk the kernels are compiled
+ * from (csrc/jpeg_encode.h).  n crops in one call, as one batch of the device.
+ *   coefs[i]   crop i's quantised coefficients in the layout of mdjpeg_decode for three components, 4:2:0: the planes of
+ *              Y, Cb, Cr one behind the other, whole MCUs ((w + 15) / 16 x (h + 15) / 16 MCUs, Y 2 x 2 blocks each), natural
+ *              order within a block.  Luma blocks that only fill up an MCU are not read: libjpeg's rule stands in for them.
+ *   out        receives the crops' scans one behind the other: crop i's at out[offsets[i]], sizes[i] bytes -- every byte
+ *              between the SOS header and the EOI marker of the file Pillow / libjpeg-turbo write for these coefficients
+ *              (interleaved scan, no restart markers, the standard's four Huffman tables, FF bytes stuffed, the last byte
+ *              padded with 1-bits).
+ * *needed is the capacity the call needs.  MDJPEG_ECAPACITY when it is more than `capacity`: nothing is written at or beyond
+ * out[capacity], offsets / sizes / *needed are valid, and a second call with *needed bytes succeeds.  MDJPEG_ECORRUPT for a
+ * DC difference or an AC coefficient no baseline file can hold.  mdjpeg_encode_bound: what one crop's scan can take at the
+ * very most, from the worst code lengths of the tables (1660 bits a block, every byte stuffed); -1 for a size outside
+ * 1 .. 65535. */
+int mdjpeg_encode_subsequences(const int16_t* const* coefs, const int32_t* widths, const int32_t* heights, int n, int chunk_bytes,
+                               uint8_t* out, size_t capacity, int64_t* offsets, int64_t* sizes, size_t* needed);
+int64_t mdjpeg_encode_bound(int32_t width, int32_t height);
+
 const char* mdjpeg_version(void);
 
 #ifdef __cplusplus

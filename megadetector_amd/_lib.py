@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libmdhip.so')
 
 MDHIP_OK = 0
+MDHIP_ECAPACITY = -5
 MDHIP_DTYPE_BF16 = 0
 MDHIP_DTYPE_FP8 = 1
 MDHIP_DTYPE_FP16 = 2
@@ -79,6 +80,10 @@ SYMBOLS = {
     'mdhip_jpeg_entropy_stats': (C.c_int, [_P, C.POINTER(C.c_int64)]),
     'mdhip_jpeg_recompress': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                         C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(_P), _P]),
+    'mdhip_jpeg_encode': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int,
+                                    C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), _P, C.c_int64, C.POINTER(C.c_int64),
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
+    'mdhip_jpeg_encode_bound': (C.c_longlong, [C.c_int, C.c_int]),
     'mdhip_forward_tta': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_last_num_anchors': (C.c_int, [_P]),
     'mdhip_calibrate': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),

@@ -10,6 +10,7 @@
 
 #include "../../include/mdjpeg.h"
 #include "jpeg_subseq.h"
+#include "jpeg_encode.h"
 
 #include <cstdio>
 #include <cstring>
@@ -585,7 +586,83 @@ int mdjpeg_decode_subsequences(const uint8_t* data, size_t size, int subseq_bits
     return MDJPEG_OK;
 }
 
-const char* mdjpeg_version(void) { return "mdjpeg 2"; }
+int mdjpeg_encode_subsequences(const int16_t* const* coefs, const int32_t* widths, const int32_t* heights, int n, int chunk_bytes,
+                               uint8_t* out, size_t capacity, int64_t* offsets, int64_t* sizes, size_t* needed) {
+    if (!coefs || !widths || !heights || !offsets || !sizes || !needed || n < 1 || chunk_bytes < MDJ_ENC_MIN_CHUNK || (!out && capacity))
+        return MDJPEG_EINVAL;
+    // the batch as the device lays it out: crops one behind the other in block order, bit buffer regions and chunks at their bounds
+    std::vector<MdjEncCrop> crops(size_t(n) + 1);
+    int64_t blocks = 0, words = 0, chunks = 0;
+    for (int i = 0; i <= n; ++i) {
+        MdjEncCrop& c = crops[size_t(i)];
+        memset(&c, 0, sizeof(c));
+        c.block0 = blocks;
+        c.word0 = words;
+        c.chunk0 = chunks;
+        if (i == n) break;
+        if (!coefs[i] || widths[i] < 1 || heights[i] < 1 || widths[i] > 65535 || heights[i] > 65535) return MDJPEG_EINVAL;
+        c.width = widths[i];
+        c.height = heights[i];
+        c.mcus_x = (widths[i] + 15) / 16;
+        c.mcus_y = (heights[i] + 15) / 16;
+        const int64_t nb = mdj_enc_blocks(widths[i], heights[i]);
+        if (nb > MDJ_ENC_MAX_BLOCKS) return MDJPEG_EINVAL;
+        blocks += nb;
+        words += mdj_enc_region_words(nb);
+        chunks += mdj_enc_region_chunks(nb, chunk_bytes);
+    }
+    // planes in natural order -> MCU order, blocks transposed
+    std::vector<int16_t> coef((size_t)blocks * 64);
+    for (int i = 0; i < n; ++i) {
+        const MdjEncCrop& c = crops[size_t(i)];
+        const int64_t mcus = int64_t(c.mcus_x) * c.mcus_y;
+        const int16_t* plane[3] = {coefs[i], coefs[i] + mcus * 4 * 64, coefs[i] + mcus * 5 * 64};
+        for (int64_t m = 0; m < mcus; ++m) {
+            const int mx = int(m % c.mcus_x), my = int(m / c.mcus_x);
+            for (int k = 0; k < 6; ++k) {
+                const int16_t* src = k < 4 ? plane[0] + ((int64_t(my) * 2 + (k >> 1)) * (c.mcus_x * 2) + mx * 2 + (k & 1)) * 64
+                                           : plane[k - 3] + m * 64;
+                int16_t* dst = coef.data() + (c.block0 + m * 6 + k) * 64;
+                for (int j = 0; j < 64; ++j) dst[((j & 7) << 3) | (j >> 3)] = src[j];
+            }
+        }
+    }
+    MdjEncTables tables;
+    mdj_enc_build_tables(tables);
+    std::vector<uint32_t> len((size_t)blocks), bitbuf((size_t)words, 0u), count((size_t)chunks);
+    std::vector<uint64_t> off((size_t)blocks + 1), start((size_t)chunks + 1);
+    uint32_t errors = 0;
+    for (int64_t g = 0; g < blocks; ++g) {                               // pass "bits"
+        int c;
+        uint32_t e;
+        len[size_t(g)] = mdj_enc_lane_bits(crops.data(), n, coef.data(), tables, g, &c, &e);
+        errors |= e;
+    }
+    if (errors) return MDJPEG_ECORRUPT;
+    off[0] = 0;
+    for (int64_t g = 0; g < blocks; ++g) off[size_t(g) + 1] = off[size_t(g)] + len[size_t(g)];
+    for (int64_t g = 0; g < blocks; ++g)                                  // pass "write"
+        mdj_enc_lane_write(crops.data(), n, coef.data(), tables, off.data(), bitbuf.data(), g);
+    for (int64_t q = 0; q < chunks; ++q)                                  // pass "count"
+        count[size_t(q)] = mdj_enc_lane_count(crops.data(), n, off.data(), bitbuf.data(), chunk_bytes, q);
+    start[0] = 0;
+    for (int64_t q = 0; q < chunks; ++q) start[size_t(q) + 1] = start[size_t(q)] + count[size_t(q)];
+    for (int i = 0; i < n; ++i) {
+        offsets[i] = int64_t(start[size_t(crops[size_t(i)].chunk0)]);
+        sizes[i] = int64_t(start[size_t(crops[size_t(i) + 1].chunk0)]) - offsets[i];
+    }
+    *needed = size_t(start[size_t(chunks)]);
+    for (int64_t q = 0; q < chunks; ++q)                                  // pass "stuff"
+        mdj_enc_lane_stuff(crops.data(), n, off.data(), bitbuf.data(), chunk_bytes, start.data(), out, int64_t(capacity), q);
+    return *needed > capacity ? MDJPEG_ECAPACITY : MDJPEG_OK;
+}
+
+int64_t mdjpeg_encode_bound(int32_t width, int32_t height) {
+    if (width < 1 || height < 1 || width > 65535 || height > 65535) return -1;
+    return mdj_enc_bound_bytes(width, height);
+}
+
+const char* mdjpeg_version(void) { return "mdjpeg 3"; }
 
 }  // extern "C"
 
@@ -609,6 +686,21 @@ int main(int argc, char** argv) {
         if (rc == MDJPEG_OK) {
             int16_t* coef = new int16_t[size_t(info.coef_count)];
             rc = mdjpeg_decode(exact, bytes.size(), &info, coef, size_t(info.coef_count));
+            if (rc == MDJPEG_OK && info.components == 3 && info.h_samp[0] == 2 && info.v_samp[0] == 2) {
+                // and back: the host model of the GPU entropy ENCODER on these coefficients, output buffers of the exact size
+                const int16_t* planes = coef;
+                for (int chunk : {1, 3, 64}) {
+                    int64_t off, size;
+                    size_t need = 0;
+                    int re = mdjpeg_encode_subsequences(&planes, &info.width, &info.height, 1, chunk, nullptr, 0, &off, &size, &need);
+                    if (re == MDJPEG_ECAPACITY) {
+                        uint8_t* scan = new uint8_t[need];
+                        re = mdjpeg_encode_subsequences(&planes, &info.width, &info.height, 1, chunk, scan, need, &off, &size, &need);
+                        delete[] scan;
+                    }
+                    if (re != MDJPEG_OK && re != MDJPEG_ECORRUPT) { printf("%s: encoding at chunk %d gives %d\n", argv[i], chunk, re); return 4; }
+                }
+            }
             delete[] coef;
             // the descriptor and the host model of the GPU decoder, at two subsequence lengths, into exact buffers too
             mdjpeg_scan_info sc;

@@ -23,14 +23,16 @@
 #include <hip/hip_runtime.h>
 
 #include "mdhip_internal.h"
+#include "jpeg_dct.h"
 
 namespace mdhip {
 
 namespace {
 
+using namespace jpeg_dct;
+
 constexpr int IDCT_BLOCKS = 32;          // 8x8 blocks per workgroup: 256 threads, thread = (block, row / column)
 
-__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 
 // one 1-D pass of jpeg_idct_islow
 __device__ __forceinline__ void idct_1d(const int* d, int* o, int shift) {
@@ -201,15 +203,6 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(const JpegDev d) {
 
 // ---- recompression: the encoder's lossy half ---------------------------------------------------------------------------
 
-// one pixel of the window (clamped coordinates: the callers replicate edges) -> Y, Cb, Cr of jccolor.c
-__device__ __forceinline__ void load_ycc(const uint8_t* src, long long pitch, int sx, int sy, int& y, int& cb, int& cr) {
-    const uint8_t* p = src + (long long)sy * pitch + (long long)sx * 3;
-    const int r = p[0], g = p[1], b = p[2];
-    y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
-    cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
-    cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
-}
-
 __global__ __launch_bounds__(256) void jpeg_enc_planes_kernel(const JpegDev d, const uint8_t* __restrict__ src, const long long pitch) {
     const int tx = blockIdx.x * 32 + (threadIdx.x & 31);              // two chroma columns, four luma columns
     const int cy = blockIdx.y * 8 + (threadIdx.x >> 5);               // one chroma row, two luma rows
@@ -254,44 +247,6 @@ __global__ __launch_bounds__(256) void jpeg_enc_planes_kernel(const JpegDev d, c
     *reinterpret_cast<unsigned short*>(d.planes + d.plane_off[2] + co) = (unsigned short)(cr0 | (cr1 << 8));
 }
 
-// one 1-D pass of jpeg_fdct_islow; pass 1 (rows) scales up by PASS1_BITS, pass 2 (columns) takes it out again
-template <bool FIRST>
-__device__ __forceinline__ void fdct_1d(const int* d, int* o) {
-    constexpr int n = FIRST ? 11 : 15;
-    int tmp0 = d[0] + d[7], tmp7 = d[0] - d[7];
-    int tmp1 = d[1] + d[6], tmp6 = d[1] - d[6];
-    int tmp2 = d[2] + d[5], tmp5 = d[2] - d[5];
-    int tmp3 = d[3] + d[4], tmp4 = d[3] - d[4];
-    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-    if (FIRST) {
-        o[0] = (tmp10 + tmp11) * 4;
-        o[4] = (tmp10 - tmp11) * 4;
-    } else {
-        o[0] = descale(tmp10 + tmp11, 2);
-        o[4] = descale(tmp10 - tmp11, 2);
-    }
-    int z1 = (tmp12 + tmp13) * 4433;
-    o[2] = descale(z1 + tmp13 * 6270, n);
-    o[6] = descale(z1 + tmp12 * (-15137), n);
-    z1 = tmp4 + tmp7;
-    int z2 = tmp5 + tmp6;
-    int z3 = tmp4 + tmp6;
-    int z4 = tmp5 + tmp7;
-    const int z5 = (z3 + z4) * 9633;
-    tmp4 *= 2446;
-    tmp5 *= 16819;
-    tmp6 *= 25172;
-    tmp7 *= 12299;
-    z1 *= -7373;
-    z2 *= -20995;
-    z3 = z3 * (-16069) + z5;
-    z4 = z4 * (-3196) + z5;
-    o[7] = descale(tmp4 + z1 + z3, n);
-    o[5] = descale(tmp5 + z2 + z4, n);
-    o[3] = descale(tmp6 + z2 + z3, n);
-    o[1] = descale(tmp7 + z1 + z4, n);
-}
-
 __global__ __launch_bounds__(IDCT_BLOCKS * 8) void jpeg_requant_kernel(const JpegDev d) {
     __shared__ int lds[IDCT_BLOCKS][8][9];
     const int t = threadIdx.x;
@@ -329,8 +284,7 @@ __global__ __launch_bounds__(IDCT_BLOCKS * 8) void jpeg_requant_kernel(const Jpe
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const unsigned q = d.quant[c][i * 8 + r];
-            const unsigned div = q * 8u;
-            const unsigned mag = (unsigned(ws[i] < 0 ? -ws[i] : ws[i]) + (div >> 1)) / div;
+            const unsigned mag = quant_magnitude(ws[i], q);
             v[i] = ws[i] < 0 ? -int(mag * q) : int(mag * q);              // quantised, and de-quantised again
         }
         idct_1d(v, ws, 11);                                               // the inverse starts with the columns

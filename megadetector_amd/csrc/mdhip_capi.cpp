@@ -43,6 +43,7 @@
 #include "../../include/mdhip.h"
 #include "mdhip_internal.h"
 #include "jpeg_subseq.h"
+#include "jpeg_encode.h"
 
 using namespace mdhip;
 
@@ -160,6 +161,8 @@ struct mdhip_ctx {
     size_t jpeg_planes_bytes = 0;
     char* jpeg_entropy = nullptr; // mdhip_jpeg_entropy_decode: descriptors, lane records, block energies (grows on demand)
     size_t jpeg_entropy_bytes = 0;
+    char* jpeg_encode = nullptr;  // mdhip_jpeg_encode: crops, tables, coefficients, lengths, offsets, bit buffer (grows on demand)
+    size_t jpeg_encode_bytes = 0;
     long long jpeg_entropy_stats[4] = {0, 0, 0, 0};   // of the last call: lanes, lanes decoded again, pass-2 launches, images
     int last_n = 0, last_h = 0, last_w = 0;
     std::string err;
@@ -1985,6 +1988,7 @@ void mdhip_destroy(mdhip_ctx* ctx) {
     if (ctx->stage) (void)hipFree(ctx->stage);
     if (ctx->jpeg_planes) (void)hipFree(ctx->jpeg_planes);
     if (ctx->jpeg_entropy) (void)hipFree(ctx->jpeg_entropy);
+    if (ctx->jpeg_encode) (void)hipFree(ctx->jpeg_encode);
     if (ctx->geom_host) (void)hipHostFree(ctx->geom_host);
     for (int i = 0; i < 4; ++i) if (ctx->geom_ev[i]) (void)hipEventDestroy(ctx->geom_ev[i]);
     if (ctx->input_free) (void)hipEventDestroy(ctx->input_free);
@@ -2413,6 +2417,131 @@ int mdhip_jpeg_recompress(mdhip_ctx* ctx, const uint8_t* const* windows, const i
         devs[i].planes = (uint8_t*)ctx->jpeg_planes;
         HIP_TRY(ctx, launch_jpeg_recompress(devs[i], windows[i], pitches[i], s));
     }
+    return MDHIP_OK;
+}
+
+long long mdhip_jpeg_encode_bound(int width, int height) {
+    if (width < 1 || height < 1 || width > 65535 || height > 65535) return -1;
+    return mdj_enc_bound_bytes(width, height);
+}
+
+int mdhip_jpeg_encode(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
+                      const int64_t* pitches, int n, const uint16_t quant_luma[64], const uint16_t quant_chroma[64], uint8_t* out,
+                      int64_t capacity, int64_t* offsets, int64_t* sizes, int64_t* needed, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!windows || !widths || !heights || !pitches || !quant_luma || !quant_chroma || !offsets || !sizes || !needed)
+        return fail(ctx, MDHIP_EINVAL, "windows/widths/heights/pitches/quant_luma/quant_chroma/offsets/sizes/needed is NULL");
+    if (n < 1) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
+    if (capacity < 0 || (capacity > 0 && !out)) return fail(ctx, MDHIP_EINVAL, "capacity %lld with out %p", (long long)capacity, (void*)out);
+    for (int k = 0; k < 64; ++k)
+        if (quant_luma[k] < 1 || quant_luma[k] > 255 || quant_chroma[k] < 1 || quant_chroma[k] > 255)
+            return fail(ctx, MDHIP_EINVAL, "quantisation table entry %d outside 1 .. 255 (baseline JPEG)", k);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto is_device = [](const void* p) {
+        hipPointerAttribute_t attr;
+        const hipError_t e = hipPointerGetAttributes(&attr, p);
+        if (e != hipSuccess) (void)hipGetLastError();
+        return e == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged);
+    };
+    if (capacity > 0 && !is_device(out)) return fail(ctx, MDHIP_EINVAL, "host pointer -- out must be device memory");
+    const int chunk_bytes = 64;
+    std::vector<MdjEncCrop> crops((size_t)n + 1);
+    long long blocks = 0, words = 0, chunks = 0;
+    for (int i = 0; i <= n; ++i) {
+        MdjEncCrop& c = crops[i];
+        memset(&c, 0, sizeof(c));
+        c.block0 = blocks;
+        c.word0 = words;
+        c.chunk0 = chunks;
+        if (i == n) break;
+        const int w = widths[i], h = heights[i];
+        if (w < 1 || h < 1 || w > 65535 || h > 65535) return fail(ctx, MDHIP_EINVAL, "window %d: %dx%d", i, w, h);
+        if (pitches[i] < (long long)w * 3 || (long long)(h - 1) * pitches[i] + (long long)w * 3 > 0x7fff0000LL)
+            return fail(ctx, MDHIP_EINVAL, "window %d: pitch %lld for %d pixels per row (or a window above 2 GB)", i, (long long)pitches[i], w);
+        if (!windows[i] || !is_device(windows[i])) return fail(ctx, MDHIP_EINVAL, "window %d: NULL or a host pointer -- windows must be device memory", i);
+        const long long nb = mdj_enc_blocks(w, h);
+        if (nb > MDJ_ENC_MAX_BLOCKS) return fail(ctx, MDHIP_EINVAL, "window %d: %dx%d is more than %lld blocks", i, w, h, (long long)MDJ_ENC_MAX_BLOCKS);
+        c.src = windows[i];
+        c.pitch = pitches[i];
+        c.width = w;
+        c.height = h;
+        c.mcus_x = (w + 15) / 16;
+        c.mcus_y = (h + 15) / 16;
+        blocks += nb;
+        words += mdj_enc_region_words(nb);
+        chunks += mdj_enc_region_chunks(nb, chunk_bytes);
+    }
+    // the scratch: [crops][tables][quant] uploaded; [status][bit buffer] zeroed; the rest written before it is read
+    size_t cur = 0;
+    auto take = [&cur](size_t bytes) { const size_t o = cur; cur = align_up(cur + bytes, 256); return o; };
+    const size_t o_crops = take(sizeof(MdjEncCrop) * ((size_t)n + 1));
+    const size_t o_tables = take(sizeof(MdjEncTables));
+    const size_t o_quant = take(256);
+    const size_t upload_bytes = cur;
+    const size_t o_status = take(4 * (size_t)n);
+    const size_t o_bitbuf = take(4 * (size_t)words);
+    const size_t zero_bytes = cur - o_status;
+    const size_t o_coef = take(128 * (size_t)blocks);
+    const size_t o_len = take(4 * (size_t)blocks);
+    const size_t o_off = take(8 * ((size_t)blocks + 1));
+    const size_t o_partial = take(8 * (size_t)std::max(jpeg_encode_scan_tiles(blocks), jpeg_encode_scan_tiles(chunks)));
+    const size_t o_count = take(4 * (size_t)chunks);
+    const size_t o_start = take(8 * ((size_t)chunks + 1));
+    const size_t o_result = take(8 * (2 * (size_t)n + 1));
+    if (cur > ctx->jpeg_encode_bytes) {
+        HIP_TRY(ctx, hipDeviceSynchronize());                  // an earlier call's kernels may still use the old scratch
+        if (ctx->jpeg_encode) HIP_TRY(ctx, hipFree(ctx->jpeg_encode));
+        ctx->jpeg_encode = nullptr;
+        ctx->jpeg_encode_bytes = 0;
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->jpeg_encode, cur));
+        ctx->jpeg_encode_bytes = cur;
+    }
+    char* base = ctx->jpeg_encode;
+    std::vector<char> up(upload_bytes, 0);
+    memcpy(up.data() + o_crops, crops.data(), sizeof(MdjEncCrop) * ((size_t)n + 1));
+    MdjEncTables tables;
+    mdj_enc_build_tables(tables);
+    memcpy(up.data() + o_tables, &tables, sizeof(tables));
+    memcpy(up.data() + o_quant, quant_luma, 128);
+    memcpy(up.data() + o_quant + 128, quant_chroma, 128);
+    // (the upload is from pageable memory: the copy has left `up` when the call returns)
+    HIP_TRY(ctx, hipMemcpyAsync(base, up.data(), upload_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(base + o_status, 0, zero_bytes, s));
+    JpegEncDev d;
+    d.crops = (const MdjEncCrop*)(base + o_crops);
+    d.tables = (const MdjEncTables*)(base + o_tables);
+    d.quant = (const uint16_t*)(base + o_quant);
+    d.coef = (int16_t*)(base + o_coef);
+    d.len = (uint32_t*)(base + o_len);
+    d.off = (uint64_t*)(base + o_off);
+    d.partial = (uint64_t*)(base + o_partial);
+    d.bitbuf = (uint32_t*)(base + o_bitbuf);
+    d.count = (uint32_t*)(base + o_count);
+    d.start = (uint64_t*)(base + o_start);
+    d.status = (uint32_t*)(base + o_status);
+    d.result = (long long*)(base + o_result);
+    d.out = out;
+    d.capacity = capacity;
+    d.blocks = blocks;
+    d.chunks = chunks;
+    d.n = n;
+    d.chunk_bytes = chunk_bytes;
+    HIP_TRY(ctx, launch_jpeg_encode(d, s));
+    std::vector<long long> result(2 * (size_t)n + 1);
+    std::vector<uint32_t> status((size_t)n);
+    HIP_TRY(ctx, hipMemcpyAsync(result.data(), d.result, 8 * result.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(status.data(), d.status, 4 * status.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    for (int i = 0; i < n; ++i) {
+        offsets[i] = result[i];
+        sizes[i] = result[(size_t)n + i];
+    }
+    *needed = result[2 * (size_t)n];
+    for (int i = 0; i < n; ++i)
+        if (status[i]) return fail(ctx, MDHIP_EINVAL, "window %d: a coefficient no baseline JPEG can hold (status %u)", i, status[i]);
+    if (*needed > capacity)
+        return fail(ctx, MDHIP_ECAPACITY, "the scans take %lld bytes, the output buffer has %lld", (long long)*needed, (long long)capacity);
     return MDHIP_OK;
 }
 

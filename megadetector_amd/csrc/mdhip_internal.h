@@ -6,6 +6,8 @@
 #include <stdint.h>
 
 struct MdjImage;
+struct MdjEncCrop;
+struct MdjEncTables;
 
 namespace mdhip {
 
@@ -503,5 +505,29 @@ void launch_jpeg_entropy_front(const JpegScanDev* devs, int n, unsigned max_lane
 void launch_jpeg_entropy_sync(const JpegScanDev* devs, int n, unsigned max_lanes, unsigned long long* counters, hipStream_t s);
 void launch_jpeg_entropy_back(const JpegScanDev* devs, int n, unsigned max_lanes, long long max_chunks, uint32_t* status, hipStream_t s);
 int jpeg_entropy_dc_chunk();
+
+// ---------------------------------------------------------------------------------------
+// JPEG entropy encoding (jpeg_encode.cpp): one record for the whole batch, passed to the kernels by value
+// ---------------------------------------------------------------------------------------
+struct JpegEncDev {
+    const ::MdjEncCrop*   crops;  // [n + 1] the crops (jpeg_encode.h); the last entry carries the totals
+    const ::MdjEncTables* tables; // the standard's four tables as codes and lengths
+    const uint16_t* quant;        // [2][64] luma, chroma; natural order
+    int16_t*  coef;               // [blocks][64] quantised coefficients, MCU order, blocks transposed; 16-byte aligned
+    uint32_t* len;                // [blocks] bit length of each block
+    uint64_t* off;                // [blocks + 1] exclusive prefix sum of len
+    uint64_t* partial;            // scratch of the prefix sums: one value per 1024 items
+    uint32_t* bitbuf;             // the unstuffed bits: every crop's region at its bound, zeroed before the call
+    uint32_t* count;              // [chunks] bytes each stuffing chunk writes
+    uint64_t* start;              // [chunks + 1] exclusive prefix sum of count: where each chunk's output begins
+    uint32_t* status;             // [n] MDJ_ENC_ERR_* bits of each crop, zeroed before the call
+    long long* result;            // [2 n + 1] offsets, sizes, capacity needed
+    uint8_t*  out;
+    long long capacity;
+    long long blocks, chunks;
+    int n, chunk_bytes;
+};
+hipError_t launch_jpeg_encode(const JpegEncDev& d, hipStream_t s);
+long long jpeg_encode_scan_tiles(long long n);
 
 }  // namespace mdhip

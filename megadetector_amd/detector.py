@@ -118,6 +118,7 @@ class HIPDetector:
         self._ctx = None
         self.jpeg_images_reconstructed = 0      # images whose pixels were rebuilt on the device from JPEG coefficients
         self.jpeg_images_entropy_decoded = 0    # of those: images whose scan was Huffman-decoded on the device too
+        self.crop_counts = {'gpu': 0, 'host': 0, 'skipped': 0}      # crops= : encoded on the device / saved by PIL / without area
         self.jpeg_entropy_fallbacks = 0         # scans the device flagged: decoded with PIL from the file's bytes instead
         if preprocess_only:
             return                      # never touches HIP: safe in forked producer processes
@@ -240,9 +241,13 @@ class HIPDetector:
         return result
 
     # -----------------------------------------------------------------------------------
+    supports_crops = True
+
     def generate_detections_one_batch(self, img_original, image_id=None, detection_threshold=0.00001,
-                                      image_size=None, augment=False, verbose=False):
-        """reference pytorch_detector.py:1124-1252"""
+                                      image_size=None, augment=False, verbose=False, crops=None):
+        """reference pytorch_detector.py:1124-1252.  crops (a crops.CropOptions, default None = off): every result dict gains
+        'crops', a list of (crop_id, crop_filename_relative, bytes) -- the files create_crop_folder.py writes for the
+        image's detections, encoded on the device from the pixels that are resident there (mdhip_jpeg_encode)."""
         if not isinstance(img_original, list):
             raise ValueError('img_original must be a list for batch processing')
         if len(img_original) == 0:
@@ -273,12 +278,41 @@ class HIPDetector:
             try:
                 for start in range(0, len(items), self.max_batch):
                     self._process_batch_group(items[start:start + self.max_batch], results,
-                                              detection_threshold, augment, verbose)
+                                              detection_threshold, augment, verbose, crops)
             except Exception as e:
                 print('Warning: batch inference failed for shape {}: {}'.format(shape, str(e)))
                 for original_idx, _, current_id in items:
                     results[original_idx] = {'file': current_id, 'detections': None, 'failure': FAILURE_INFER}
+        return self._crops_everywhere(results, crops)
+
+    @staticmethod
+    def _crops_everywhere(results, crops):
+        """an image that failed has no crops, as the reference's second pass gives it none"""
+        if crops is not None:
+            for r in results:
+                if r is not None:
+                    r.setdefault('crops', [])
         return results
+
+    def _add_crops(self, group_items, tensors, results, crops, stream=0):
+        """'crops' of the results of one group: tensors[i] holds the pixels of group_items[i] on the device.  One encoder
+        call and one read-back for the group."""
+        from . import crops as K
+        entries, where = [], []
+        for (original_idx, info, current_id), t in zip(group_items, tensors):
+            r = results[original_idx]
+            if r is None or r.get('detections') is None:
+                continue
+            hh, ww = info['img_original'].shape[:2] if isinstance(info['img_processed'], LetterboxSpec) else info['img_processed'].shape[:2]
+            entries.append((t, ww, hh, current_id, r['detections']))
+            where.append(original_idx)
+        if not entries:
+            return
+        out, counts = K.crops_of_device_images(self._ctx, entries, crops, crops.category_ids(), stream=stream)
+        for original_idx, c in zip(where, out):
+            results[original_idx]['crops'] = c
+        for key, v in counts.items():
+            self.crop_counts[key] += v
 
     def _prepare_batch(self, img_original, image_id, image_size, verbose):
         """per-image preprocessing with failure capture (reference :1194-1222) and grouping by processed
@@ -421,7 +455,7 @@ class HIPDetector:
                 json.dump({'fp8_scales': [float(sc) for sc, _, _ in self._ctx.fp8_scales()]}, f)
             os.replace(tmp, self._fp8_scales_file)
 
-    def _process_batch_group(self, group_items, results, detection_threshold, augment, verbose):
+    def _process_batch_group(self, group_items, results, detection_threshold, augment, verbose, crops=None):
         """reference pytorch_detector.py:1257-1426 with the device work in libmdhip.so"""
         if len(group_items) == 0:
             return
@@ -430,6 +464,25 @@ class HIPDetector:
         n = len(group_items)
         ctx = self._ctx
         images, hold = self._reconstruct_jpegs(images)       # (`hold` keeps the device images alive until the NMS has returned)
+        tensors = None
+        if crops is not None:
+            # every source image on the device exactly once, where the encoder can still address it: host arrays that
+            # mdhip_preprocess would stage internally are uploaded here and passed as device pointers
+            import torch
+            dev = torch.device('cuda', _device_ordinal(self.device))
+            rebuilt = {o.data_ptr(): o for o in (hold or [])}
+            tensors = []
+            for i, im in enumerate(images):
+                if isinstance(im, np.ndarray):
+                    flat = im.reshape(-1)
+                    if not flat.flags.writeable:
+                        flat = np.array(flat)
+                    t = torch.from_numpy(flat).to(dev)
+                    images[i] = t.data_ptr()
+                else:
+                    t = rebuilt[im]
+                tensors.append(t)
+            torch.cuda.synchronize(dev)
         ctx.preprocess(images, geoms, h, w)
         if self._fp8_pending:               # fp8 mode, explicit opt-in: this batch calibrates the scales
             ctx.calibrate(n, h, w)
@@ -440,6 +493,8 @@ class HIPDetector:
             ctx.forward(n, h, w)
         det_all, counts = ctx.nms(n, detection_threshold, self._nms_iou(), max_det=300)
         self._format_group(group_items, det_all, counts, h, w, results, detection_threshold)
+        if crops is not None:
+            self._add_crops(group_items, tensors, results, crops)
 
     # -----------------------------------------------------------------------------------
     def generate_detections_for_tiles(self, img_original, tile_origins, tile_size, tile_ids=None,
@@ -569,10 +624,10 @@ class HIPDetector:
                 self._pl = {'torch': torch, 'dev': dev, 'copy_s': torch.cuda.Stream(), 'comp_s': torch.cuda.Stream(),
                             'nms_s': torch.cuda.Stream(), 'nms_done': [None] * 4,
                             'stage': [None, None], 'copied': [torch.cuda.Event(), torch.cuda.Event()],
-                            'consumed': [None, None], 'count': 0}
+                            'consumed': [None, None], 'count': 0, 'crop_owner': [None, None]}
         return self._pl
 
-    def _submit_group(self, group_items, detection_threshold, augment=False):
+    def _submit_group(self, group_items, detection_threshold, augment=False, crops=None):
         pl = self._pipeline()
         torch = pl['torch']
         h, w = group_items[0][1]['img_processed'].shape[:2]
@@ -592,6 +647,12 @@ class HIPDetector:
             rgb_offs[i] = total
             total += (int(np.prod(images[i].shape)) + 255) // 256 * 256
         with torch.cuda.device(pl['dev']):
+            if pl['crop_owner'][k] is not None:
+                # a group whose crops are not encoded yet (a ticket that is still outstanding) keeps its pixels in this
+                # buffer, and `consumed` stands behind its letterbox only: that group keeps the storage (its views hold
+                # it) and this one gets a tensor of its own
+                pl['stage'][k] = None
+                pl['crop_owner'][k] = None
             if pl['stage'][k] is None or pl['stage'][k].numel() < total:
                 if pl['consumed'][k] is not None:
                     pl['consumed'][k].synchronize()
@@ -656,14 +717,42 @@ class HIPDetector:
             done = torch.cuda.Event()
             done.record(nms_s)
             pl['nms_done'][nms_slot] = done
-        return {'items': group_items, 'h': h, 'w': w, 'slot': nms_slot, 'copied': pl['copied'][k], 'images': images}
+        handle = {'items': group_items, 'h': h, 'w': w, 'slot': nms_slot, 'copied': pl['copied'][k], 'images': images}
+        if crops is not None:
+            # the pixels stay in staging buffer k until the crops are encoded (_collect_group): views of it, per image
+            handle['crops'] = crops
+            handle['k'], handle['consumed'] = k, ev
+            pl['crop_owner'][k] = handle
+            handle['tensors'] = [stage[rgb_offs[i]:rgb_offs[i] + int(np.prod(im.shape))] if i in rgb_offs
+                                 else stage[offs[i]:offs[i] + im.nbytes] for i, im in enumerate(images)]
+        return handle
 
     def _collect_group(self, handle, results, detection_threshold):
         det_all, counts = self._ctx.nms_wait(slot=handle['slot'])
         self._format_group(handle['items'], det_all, counts, handle['h'], handle['w'], results, detection_threshold)
+        if handle.get('crops') is not None:
+            pl = self._pipeline()
+            torch = pl['torch']
+            with torch.cuda.device(pl['dev']):
+                if pl.get('crop_s') is None:
+                    pl['crop_s'] = torch.cuda.Stream()
+                crop_s = pl['crop_s']
+                crop_s.wait_event(handle['consumed'])            # copies, reconstruction and letterbox of this batch are done
+                try:
+                    self._add_crops(handle['items'], handle['tensors'], results, handle['crops'], stream=crop_s.cuda_stream)
+                finally:
+                    # While this group owned staging buffer k no other group could take it (_submit_group gives a later one a
+                    # tensor of its own).  From here on the buffer may be reused: its `consumed` event moves behind the
+                    # encoder's kernels, so the copy stream overwrites it only behind this group's encode.
+                    if pl['crop_owner'][handle['k']] is handle:
+                        pl['crop_owner'][handle['k']] = None
+                        if pl['consumed'][handle['k']] is handle['consumed']:
+                            ev = torch.cuda.Event()
+                            ev.record(crop_s)
+                            pl['consumed'][handle['k']] = ev
 
     def start_batch(self, img_original, image_id, detection_threshold=0.00001, image_size=None, augment=False,
-                    verbose=False):
+                    verbose=False, crops=None):
         """Enqueues a batch; returns a ticket for finish_batch().  At most two tickets may be outstanding.
         Same arguments as generate_detections_one_batch (augment = yolov5's three-pass augmented inference)."""
         if self._ctx is None:
@@ -680,7 +769,7 @@ class HIPDetector:
         pending = None
         for ci, chunk in enumerate(chunks):
             try:
-                handle = self._submit_group(chunk, detection_threshold, augment)
+                handle = self._submit_group(chunk, detection_threshold, augment, crops)
                 if ci == len(chunks) - 1:
                     pending = handle                     # the last group stays in flight
                 else:
@@ -689,7 +778,7 @@ class HIPDetector:
                 print('Warning: batch inference failed for shape {}: {}'.format(chunk[0][1]['img_processed'].shape, str(e)))
                 for original_idx, _, current_id in chunk:
                     results[original_idx] = {'file': current_id, 'detections': None, 'failure': FAILURE_INFER}
-        return {'results': results, 'pending': pending, 'threshold': detection_threshold}
+        return {'results': results, 'pending': pending, 'threshold': detection_threshold, 'crops': crops}
 
     def batch_inputs_consumed(self, ticket):
         """Blocks until the host images of the ticket's in-flight group have been copied to the device
@@ -708,16 +797,16 @@ class HIPDetector:
                 for original_idx, _, current_id in handle['items']:
                     results[original_idx] = {'file': current_id, 'detections': None, 'failure': FAILURE_INFER}
             ticket['pending'] = None
-        return results
+        return self._crops_everywhere(results, ticket.get('crops'))
 
     # -----------------------------------------------------------------------------------
     def generate_detections_one_image(self, img_original, image_id='unknown', detection_threshold=0.00001,
-                                      image_size=None, augment=False, verbose=False):
+                                      image_size=None, augment=False, verbose=False, crops=None):
         """reference pytorch_detector.py:1428-1478"""
         if isinstance(img_original, dict):
             res = self.generate_detections_one_batch([img_original], None, detection_threshold,
-                                                     image_size, augment, verbose)
+                                                     image_size, augment, verbose, crops=crops)
         else:
             res = self.generate_detections_one_batch([img_original], [image_id], detection_threshold,
-                                                     image_size, augment, verbose)
+                                                     image_size, augment, verbose, crops=crops)
         return res[0]

@@ -262,6 +262,37 @@ class HipContext:
                                                    ql.ctypes.data_as(C.POINTER(C.c_uint16)), qc.ctypes.data_as(C.POINTER(C.c_uint16)),
                                                    C.cast(o, C.POINTER(C.c_void_p)), C.c_void_p(stream)), 'mdhip_jpeg_recompress')
 
+    def jpeg_encode(self, ptrs, sizes, pitches, quality, out_ptr, capacity, stream=0):
+        """
+        Entropy-coded JPEG scans of windows of device images, byte for byte those of Image.save(quality=quality)
+        (include/mdhip.h: mdhip_jpeg_encode); jpeg_host.jfif_file puts the file around a scan.
+        ptrs, sizes, pitches, quality: as for jpeg_recompress
+        out_ptr, capacity: ONE device buffer for all scans, and its size in bytes
+        Returns (fits, offsets, sizes, needed): int64 arrays of each window's scan within the buffer, and the capacity the
+        call needs.  fits False (MDHIP_ECAPACITY): nothing was written beyond the capacity; call again with `needed` bytes.
+        """
+        n = len(ptrs)
+        if not (len(sizes) == len(pitches) == n):
+            raise ValueError('ptrs, sizes and pitches must have one entry per window')
+        ql, qc = quant_tables(quality)
+        p = (C.c_void_p * n)(*[int(v) for v in ptrs])
+        ws = (C.c_int32 * n)(*[int(v[0]) for v in sizes])
+        hs = (C.c_int32 * n)(*[int(v[1]) for v in sizes])
+        pt = (C.c_int64 * n)(*[int(v) for v in pitches])
+        offs, lens, need = (C.c_int64 * max(n, 1))(), (C.c_int64 * max(n, 1))(), C.c_int64(0)
+        rc = self.lib.mdhip_jpeg_encode(self.h, C.cast(p, C.POINTER(C.c_void_p)), ws, hs, pt, n,
+                                        ql.ctypes.data_as(C.POINTER(C.c_uint16)), qc.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                        C.c_void_p(int(out_ptr) if capacity else 0), int(capacity), offs, lens, C.byref(need),
+                                        C.c_void_p(stream))
+        if rc != _lib.MDHIP_ECAPACITY:
+            self._check(rc, 'mdhip_jpeg_encode')
+        return rc == 0, np.array(offs[:n], dtype=np.int64), np.array(lens[:n], dtype=np.int64), int(need.value)
+
+    @staticmethod
+    def jpeg_encode_bound(width, height):
+        """bytes the scan of a width x height window can take at the very most (mdhip_jpeg_encode_bound)"""
+        return int(_lib.load().mdhip_jpeg_encode_bound(int(width), int(height)))
+
     def forward(self, n, h, w, stream=0):
         self._check(self.lib.mdhip_forward(self.h, int(n), int(h), int(w), C.c_void_p(stream)), 'mdhip_forward')
 

@@ -47,6 +47,10 @@ SYMBOLS = {
     'mdjpeg_decode': (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(mdjpeg_info), C.c_void_p, C.c_size_t]),
     'mdjpeg_scan': (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(mdjpeg_scan_info), C.c_void_p, C.c_size_t]),
     'mdjpeg_decode_subsequences': (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(mdjpeg_info), C.c_void_p, C.c_size_t]),
+    'mdjpeg_encode_subsequences': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                             C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_size_t)]),
+    'mdjpeg_encode_bound': (C.c_int64, [C.c_int32, C.c_int32]),
     'mdjpeg_version': (C.c_char_p, []),
 }
 
@@ -192,6 +196,96 @@ def quant_tables(quality):
     scale = 5000 // quality if quality < 50 else 200 - 2 * quality
     return tuple(np.clip((np.array(base, dtype=np.int64) * scale + 50) // 100, 1, 255).astype(np.uint16)
                  for base in (_STD_LUMA, _STD_CHROMA))
+
+
+# ---- a JPEG file around an entropy-coded scan (mdhip_jpeg_encode) ------------------------------------------------------
+_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+           35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+# the example Huffman tables of the standard (ITU-T T.81, K.3 - K.6) as DHT segments carry them: (class << 4 | id, codes of
+# each length, symbols), in the order libjpeg writes them
+_STD_HUFFMAN = (
+    (0x00, (0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), tuple(range(12))),
+    (0x10, (0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125),
+     (0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+      0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
+      0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+      0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
+      0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+      0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+      0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
+      0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa)),
+    (0x01, (0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), tuple(range(12))),
+    (0x11, (0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119),
+     (0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
+      0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
+      0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
+      0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
+      0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+      0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+      0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
+      0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa)),
+)
+_HEADERS = {}
+
+
+def _segment(marker, payload):
+    return bytes((0xFF, marker)) + (len(payload) + 2).to_bytes(2, 'big') + payload
+
+
+def jfif_file(width, height, quality, scan_bytes):
+    """
+    The file Image.fromarray(rgb).save(f, 'JPEG', quality=quality) writes for a width x height RGB image whose entropy-coded
+    scan is `scan_bytes` (mdhip_jpeg_encode; mdjpeg_encode_subsequences): SOI, APP0 (JFIF 1.01, no density unit, 1 x 1), the
+    two DQT segments, SOF0 (three components, 4:2:0), the standard's four DHT segments, SOS, the scan, EOI.  Pillow also
+    copies a COM segment of the SOURCE file (info['comment']) into what it saves; the files built here carry none.
+    """
+    width, height = int(width), int(height)
+    if not (1 <= width <= 65535 and 1 <= height <= 65535):
+        raise ValueError('a JPEG is 1 .. 65535 pixels wide and high, got {} x {}'.format(width, height))
+    quality = check_quality(quality)
+    if quality not in _HEADERS:
+        ql, qc = quant_tables(quality)
+        zz = np.array(_ZIGZAG)
+        front = b'\xff\xd8' + _segment(0xE0, b'JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00')
+        front += _segment(0xDB, b'\x00' + ql[zz].astype(np.uint8).tobytes()) + _segment(0xDB, b'\x01' + qc[zz].astype(np.uint8).tobytes())
+        back = b''.join(_segment(0xC4, bytes((tc_th,)) + bytes(counts) + bytes(vals)) for tc_th, counts, vals in _STD_HUFFMAN)
+        back += _segment(0xDA, b'\x03\x01\x00\x02\x11\x03\x11\x00\x3f\x00')
+        _HEADERS[quality] = (front, back)
+    front, back = _HEADERS[quality]
+    sof = _segment(0xC0, b'\x08' + height.to_bytes(2, 'big') + width.to_bytes(2, 'big') + b'\x03\x01\x22\x00\x02\x11\x01\x03\x11\x01')
+    return b''.join((front, sof, back, bytes(scan_bytes), b'\xff\xd9'))
+
+
+def encode_bound(width, height):
+    """bytes the scan of a width x height crop can take at the very most (mdjpeg_encode_bound)"""
+    return int(load().mdjpeg_encode_bound(int(width), int(height)))
+
+
+def encode_subsequences(coefs, sizes, chunk_bytes=64, capacity=None):
+    """
+    The host model of the GPU entropy encoder (mdjpeg_encode_subsequences), for tests.  coefs: per crop a flat int16 array in
+    the layout of decode() for 4:2:0; sizes: (width, height) per crop.  Returns (rc, scans, needed, buffer): the scans as
+    bytes objects when rc == MDJPEG_OK.  capacity None: as much as the call needs (asked for first).
+    """
+    lib = load()
+    n = len(coefs)
+    hold = [np.ascontiguousarray(c, dtype=np.int16) for c in coefs]
+    ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in hold])
+    ws = (C.c_int32 * n)(*[int(s[0]) for s in sizes])
+    hs = (C.c_int32 * n)(*[int(s[1]) for s in sizes])
+    offs, lens, need = (C.c_int64 * n)(), (C.c_int64 * n)(), C.c_size_t(0)
+    if capacity is None:
+        rc = lib.mdjpeg_encode_subsequences(ptrs, ws, hs, n, int(chunk_bytes), None, 0, offs, lens, C.byref(need))
+        if rc != MDJPEG_ECAPACITY:
+            return rc, None, int(need.value), None
+        capacity = int(need.value)
+    guard = 64
+    buf = np.full(capacity + guard, 0xA5, dtype=np.uint8)
+    rc = lib.mdjpeg_encode_subsequences(ptrs, ws, hs, n, int(chunk_bytes), buf.ctypes.data, capacity, offs, lens, C.byref(need))
+    if not (buf[capacity:] == 0xA5).all():
+        raise AssertionError('mdjpeg_encode_subsequences wrote beyond its capacity')
+    scans = [buf[offs[i]:offs[i] + lens[i]].tobytes() for i in range(n)] if rc == MDJPEG_OK else None
+    return rc, scans, int(need.value), buf[:capacity]
 
 
 # ---- a coefficient image in a ring slot (feed.py decode='coefficients') ------------------------------------------------

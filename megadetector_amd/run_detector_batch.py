@@ -40,6 +40,7 @@ from . import feed, placement, run_detector
 from .feed import load_image, EXIF_IMAGE_ROTATIONS          # noqa: F401  (re-exported)
 from .constants import FAILURE_IMAGE_OPEN, FAILURE_INFER, DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD
 from .constants import DEFAULT_DETECTOR_LABEL_MAP
+from . import crops as crops_mod
 from .jpeg_host import ScanFailure
 
 # reference run_detector_batch.py:86-119
@@ -143,6 +144,89 @@ def _filter_batch_output(dets, names, images, confidence_threshold, include_imag
     return out
 
 
+# --------------------------------------------------------------------------------------------
+# detection crops (reference postprocessing/create_crop_folder.py, written while the images are at hand)
+# --------------------------------------------------------------------------------------------
+#: crops of the most recent run in this process: 'files' written, of them 'gpu' = JPEG names encoded by the detector on
+#: the device, 'host_jpeg' = JPEG names saved by PIL here (a detector without crops=), 'host_other' = other extensions,
+#: saved by PIL as the reference does; 'skipped' = rectangles without area
+last_crop_counts = {}
+
+
+def _crop_relative_name(file, base):
+    """the name an image's crops are derived from: relative to the image folder (a lone file: its base name)"""
+    if os.path.isabs(file):
+        file = os.path.relpath(file, start=base) if base else os.path.basename(file)
+    return file.replace('\\', '/')
+
+
+class _CropWriter:
+    """writes an image's crops below the crop folder BEFORE its result is handed on, so that a result a checkpoint holds
+    has its crops on disk and a resumed run leaves no gaps"""
+
+    def __init__(self, folder, options, base):
+        self.folder, self.options, self.base = folder, options, base
+        self.category_ids = options.category_ids()
+        self.counts = {'files': 0, 'gpu': 0, 'host_jpeg': 0, 'host_other': 0, 'skipped': 0}
+
+    def detector_kw(self, detector):
+        return {'crops': self.options} if getattr(detector, 'supports_crops', False) else {}
+
+    def _pixels(self, image, file):
+        if isinstance(image, dict):
+            image = image.get('img_original')
+        a = None if image is None or hasattr(image, 'coef') or hasattr(image, 'desc') else np.asarray(image)
+        if a is None or a.ndim != 3 or a.dtype != np.uint8:
+            a = np.asarray(load_image(file))                 # the reference's second pass: the file once more
+        return a
+
+    def write(self, results, images):
+        for i, r in enumerate(results):
+            crops = r.pop('crops', None)
+            if r.get('detections') is None:
+                continue
+            if crops is None:                                # a detector without crops=: PIL on the host, as the reference
+                skipped = 0
+                if crops_mod.select_crops(crops_mod.output_order(r['detections'], self.options.output_threshold),
+                                          self.options, self.category_ids):
+                    crops, skipped = crops_mod.crops_of_host_image(self._pixels(images[i] if images else None, r['file']),
+                                                                   r['file'], r['detections'], self.options, self.category_ids)
+                self.counts['skipped'] += skipped
+                kinds = ('host_jpeg', 'host_other')
+            else:
+                kinds = ('gpu', 'host_other')
+            rel = _crop_relative_name(r['file'], self.base)
+            named = [(cid, crops_mod.crop_filename(rel, cid), data) for cid, _, data in crops or []]
+            crops_mod.write_crops(self.folder, named)
+            for _, name, _ in named:
+                self.counts['files'] += 1
+                self.counts[kinds[0] if crops_mod.is_jpeg_name(name) else kinds[1]] += 1
+
+
+def _crop_kw(crop_writer, detector):
+    return crop_writer.detector_kw(detector) if crop_writer is not None else {}
+
+
+def _write_crops(crop_writer, results, images):
+    """outside the callers' try blocks: a crop folder that cannot be written ends the run, it is no inference failure"""
+    if crop_writer is not None:
+        crop_writer.write(results, images)
+
+
+def write_crop_result_files(final_output, options, base, crop_results_file=None, crops_output_file=None):
+    """the two files create_crop_folder writes next to the crops: the results with 'crop_id' and 'crop_filename_relative'
+    added (its output_file), and one entry per crop (its crops_output_file, create_crop_folder.py:485-521)"""
+    annotated = copy.deepcopy(final_output)
+    records = crops_mod.annotate_results(annotated['images'], options, options.category_ids(),
+                                         name_of=lambda f: _crop_relative_name(f, base))
+    if crop_results_file is not None:
+        write_json(crop_results_file, annotated)
+    if crops_output_file is not None:
+        per_crop = dict(annotated)
+        per_crop['images'] = records
+        write_json(crops_output_file, per_crop)
+
+
 class _BatchPipeline:
     """
     Feeds batches of (file, image, meta_image, release) to the detector.  With a detector that has
@@ -151,7 +235,8 @@ class _BatchPipeline:
     """
 
     def __init__(self, detector, confidence_threshold, include_image_size, include_image_timestamp, on_results,
-                 depth=2):
+                 depth=2, crop_writer=None):
+        self.crops = crop_writer
         self.det = detector
         self.thr = confidence_threshold
         self.inc_size, self.inc_time = include_image_size, include_image_timestamp
@@ -169,35 +254,37 @@ class _BatchPipeline:
         releases = [it[3] for it in items if it[3] is not None]
         if not self.async_ok:
             try:
-                dets = self.det.generate_detections_one_batch(images, names, verbose=verbose)
+                dets = self.det.generate_detections_one_batch(images, names, verbose=verbose, **_crop_kw(self.crops, self.det))
                 res = _filter_batch_output(dets, names, metas, self.thr, self.inc_size, self.inc_time)
             except Exception as e:
                 print('Batch processing failure for {} images: {}'.format(len(images), str(e)))
                 res = [{'file': n, 'failure': FAILURE_INFER} for n in names]
+            _write_crops(self.crops, res, images)
             for r in releases:
                 r()
             self.on_results(res)
             return
         try:
-            ticket = self.det.start_batch(images, names, verbose=verbose)
+            ticket = self.det.start_batch(images, names, verbose=verbose, **_crop_kw(self.crops, self.det))
         except Exception as e:
             print('Batch processing failure for {} images: {}'.format(len(images), str(e)))
             for r in releases:
                 r()
             self.on_results([{'file': n, 'failure': FAILURE_INFER} for n in names])
             return
-        self.inflight.append((ticket, names, metas, releases))
+        self.inflight.append((ticket, names, metas, releases, images))
         while len(self.inflight) >= self.depth:
             self._finish_oldest()
 
     def _finish_oldest(self):
-        ticket, names, metas, releases = self.inflight.pop(0)
+        ticket, names, metas, releases, images = self.inflight.pop(0)
         try:
             dets = self.det.finish_batch(ticket)
             res = _filter_batch_output(dets, names, metas, self.thr, self.inc_size, self.inc_time)
         except Exception as e:
             print('Batch processing failure for {} images: {}'.format(len(names), str(e)))
             res = [{'file': n, 'failure': FAILURE_INFER} for n in names]
+        _write_crops(self.crops, res, images)
         for r in releases:
             r()
         self.on_results(res)
@@ -209,7 +296,7 @@ class _BatchPipeline:
 
 def _process_batch(image_items_batch, detector, confidence_threshold, quiet=False, image_size=None,
                    include_image_size=False, include_image_timestamp=False, include_exif_tags=None,
-                   augment=False):
+                   augment=False, crop_writer=None):
     """
     reference :680-831.  Items are file names or (file, image, producer_id) tuples.  As in the
     reference, the batched detector call receives neither the threshold nor image_size/augment
@@ -234,19 +321,21 @@ def _process_batch(image_items_batch, detector, confidence_threshold, quiet=Fals
     valid_results = []
     if valid_images:
         try:
-            dets = detector.generate_detections_one_batch(valid_images, valid_names, verbose=verbose)
+            dets = detector.generate_detections_one_batch(valid_images, valid_names, verbose=verbose,
+                                                          **_crop_kw(crop_writer, detector))
             valid_results = _filter_batch_output(dets, valid_names, valid_images, confidence_threshold,
                                                  include_image_size, include_image_timestamp)
         except Exception as e:
             print('Batch processing failure for {} images: {}'.format(len(valid_images), str(e)))
             valid_results = [{'file': n, 'failure': FAILURE_INFER} for n in valid_names]
+        _write_crops(crop_writer, valid_results, valid_images)
     batch_results.extend(valid_results)
     return batch_results
 
 
 def _process_image(im_file, detector, confidence_threshold, image=None, quiet=False, image_size=None,
                    include_image_size=False, include_image_timestamp=False, include_exif_tags=None,
-                   augment=False):
+                   augment=False, crop_writer=None):
     """reference :937-1056 (the un-batched path: threshold, image_size and augment ARE forwarded)"""
     if not quiet:
         print('Processing image {}'.format(im_file))
@@ -259,11 +348,13 @@ def _process_image(im_file, detector, confidence_threshold, image=None, quiet=Fa
             return {'file': im_file, 'failure': FAILURE_IMAGE_OPEN}
     try:
         result = detector.generate_detections_one_image(image, im_file, detection_threshold=confidence_threshold,
-                                                        image_size=image_size, augment=augment, verbose=verbose)
+                                                        image_size=image_size, augment=augment, verbose=verbose,
+                                                        **_crop_kw(crop_writer, detector))
     except Exception as e:
         if not quiet:
             print('Image {} cannot be processed: {}'.format(im_file, str(e)))
         return {'file': im_file, 'failure': FAILURE_INFER}
+    _write_crops(crop_writer, [result], [image])
     if 'failure' not in result or result.get('failure') is None:
         _add_image_metadata(result, image, include_image_size, include_image_timestamp)
     return result
@@ -332,7 +423,8 @@ def _make_preprocessor(detector, detector_options):
 
 def _run_detector_with_image_queue(image_files, detector, confidence_threshold, quiet, image_size,
                                    include_image_size, include_image_timestamp, augment, loader_workers,
-                                   preprocess_on_image_queue, batch_size, on_results, detector_options=None):
+                                   preprocess_on_image_queue, batch_size, on_results, detector_options=None,
+                                   crop_writer=None):
     q = queue.Queue(max_queue_size)
     file_q = queue.Queue()
     for f in image_files:
@@ -349,7 +441,8 @@ def _run_detector_with_image_queue(image_files, detector, confidence_threshold, 
         t.start()
     finished = 0
     pending = []
-    pipe = _BatchPipeline(detector, confidence_threshold, include_image_size, include_image_timestamp, on_results)
+    pipe = _BatchPipeline(detector, confidence_threshold, include_image_size, include_image_timestamp, on_results,
+                          crop_writer=crop_writer)
 
     def flush():
         if pending:
@@ -358,7 +451,8 @@ def _run_detector_with_image_queue(image_files, detector, confidence_threshold, 
             else:
                 on_results([_process_image(f, detector, confidence_threshold, image=im, quiet=quiet,
                                            image_size=image_size, include_image_size=include_image_size,
-                                           include_image_timestamp=include_image_timestamp, augment=augment)
+                                           include_image_timestamp=include_image_timestamp, augment=augment,
+                                           crop_writer=crop_writer)
                             for f, im, _ in pending])
             pending.clear()
 
@@ -391,7 +485,7 @@ last_feed_counts = {}
 
 def _run_detector_with_shared_ring(image_files, detector, confidence_threshold, quiet, image_size,
                                    include_image_size, include_image_timestamp, augment, loader_workers,
-                                   batch_size, on_results, gpu_jpeg=False):
+                                   batch_size, on_results, gpu_jpeg=False, crop_writer=None):
     """
     SURVEY.md 8(f) N1 (feed.py): spawned loader processes decode into a page-locked shared-memory ring,
     the batches go through the detector's pipelined interface.  Same results as every other mode.
@@ -424,12 +518,13 @@ def _run_detector_with_shared_ring(image_files, detector, confidence_threshold, 
             n_slots, ring_slot_bytes >> 20, str(e)))
         return _run_detector_with_image_queue(image_files, detector, confidence_threshold, quiet, image_size,
                                               include_image_size, include_image_timestamp, augment, loader_workers,
-                                              False, batch_size, on_results)
+                                              False, batch_size, on_results, crop_writer=crop_writer)
     ring = loader.ring
     try:
         if hasattr(detector, 'start_batch'):
             ring.pin()
-        pipe = _BatchPipeline(detector, confidence_threshold, include_image_size, include_image_timestamp, on_results)
+        pipe = _BatchPipeline(detector, confidence_threshold, include_image_size, include_image_timestamp, on_results,
+                              crop_writer=crop_writer)
         pending = []
 
         def decode_scans():
@@ -461,7 +556,7 @@ def _run_detector_with_shared_ring(image_files, detector, confidence_threshold, 
                 for f, im, meta_img, release in pending:
                     r = _process_image(f, detector, confidence_threshold, image=im, quiet=quiet,
                                        image_size=image_size, include_image_size=False,
-                                       include_image_timestamp=False, augment=augment)
+                                       include_image_timestamp=False, augment=augment, crop_writer=crop_writer)
                     if r.get('failure') is None and meta_img is not None:
                         _add_image_metadata(r, meta_img, include_image_size, include_image_timestamp)
                     if release is not None:
@@ -524,7 +619,9 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
                                 include_exif_tags=None, augment=False, force_model_download=False,
                                 detector_options=None, loader_workers=default_loaders,
                                 preprocess_on_image_queue=default_preprocess_on_image_queue, batch_size=1,
-                                verbose_output=False, use_threads_for_queue=True, detector=None, gpu_jpeg=False):
+                                verbose_output=False, use_threads_for_queue=True, detector=None, gpu_jpeg=False,
+                                crop_folder=None, crop_confidence_threshold=0.1, crop_expansion=0, crop_quality=95,
+                                crop_categories=None, crop_base=None):
     """
     reference :1062-1439.  `detector` (extra, optional) injects an already constructed detector
     object -- used by run_sharded and by the CPU tests of the loop with a stub detector.
@@ -532,10 +629,24 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
     as DCT coefficients and are rebuilt on the GPU, bit for bit what PIL decodes; every other file, and every other mode,
     runs as without it.  gpu_jpeg='entropy' (--gpu_jpeg_entropy): they travel as their compressed scan and the GPU
     Huffman-decodes them too; a file the GPU flags is decoded with PIL here from its bytes.  Same results either way.
+    `crop_folder` (extra, default None = off): every detection at or above crop_confidence_threshold (of the categories
+    named in crop_categories, if any) is written below it as create_crop_folder.py names and cuts it, at crop_quality,
+    crop_expansion pixels on every side; names are relative to crop_base (the image folder).  A detector with crops=
+    (HIPDetector) encodes JPEG crops on the GPU from the resident image; other extensions, and other detectors, go through
+    PIL here.  An image's crops are on disk before its result can reach a checkpoint.  The results are the same objects
+    as without it.
     Returns the list of per-image result dicts.
     """
-    global verbose
+    global verbose, last_crop_counts
     verbose = bool(verbose_output)
+    crop_writer = None
+    if crop_folder is not None:
+        names = [v for v in crop_categories.replace(',', ' ').split() if v] if isinstance(crop_categories, str) else crop_categories
+        crop_writer = _CropWriter(crop_folder, crops_mod.CropOptions(
+            confidence_threshold=crop_confidence_threshold, expansion=crop_expansion, quality=crop_quality,
+            category_names_to_include=names or None,
+            output_threshold=DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD if confidence_threshold is None else confidence_threshold), crop_base)
+        last_crop_counts = crop_writer.counts         # (of the most recent call, for reporting; the writer itself is local)
     if detector_options is None:
         detector_options = {}
     elif isinstance(detector_options, (list, str)):
@@ -602,21 +713,24 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
     if use_image_queue and not use_threads_for_queue and len(image_files) > 0:
         _run_detector_with_shared_ring(image_files, detector, confidence_threshold, quiet, image_size,
                                        include_image_size, include_image_timestamp, augment, loader_workers,
-                                       batch_size, on_results, gpu_jpeg='entropy' if gpu_jpeg == 'entropy' else bool(gpu_jpeg))
+                                       batch_size, on_results, gpu_jpeg='entropy' if gpu_jpeg == 'entropy' else bool(gpu_jpeg),
+                                       crop_writer=crop_writer)
     elif use_image_queue:
         _run_detector_with_image_queue(image_files, detector, confidence_threshold, quiet, image_size,
                                        include_image_size, include_image_timestamp, augment, loader_workers,
                                        preprocess_on_image_queue, batch_size, on_results,
-                                       detector_options=detector_options)
+                                       detector_options=detector_options, crop_writer=crop_writer)
     elif batch_size > 1:
         for batch in _group_into_batches(image_files, batch_size):
             on_results(_process_batch(batch, detector, confidence_threshold, quiet, image_size,
-                                      include_image_size, include_image_timestamp, None, augment), len(batch))
+                                      include_image_size, include_image_timestamp, None, augment, crop_writer=crop_writer),
+                       len(batch))
     else:
         for im_file in image_files:
             on_results([_process_image(im_file, detector, confidence_threshold, quiet=quiet, image_size=image_size,
                                        include_image_size=include_image_size,
-                                       include_image_timestamp=include_image_timestamp, augment=augment)])
+                                       include_image_timestamp=include_image_timestamp, augment=augment,
+                                       crop_writer=crop_writer)])
     # a loader process that died mid-list, or a result dropped anywhere above, must not pass silently
     have = set(r['file'] for r in results)
     missing = [f for f in image_files if f not in have]
@@ -874,8 +988,22 @@ def main(argv=None):
     ap.add_argument('--gpu_jpeg_entropy', action='store_true',
                     help='as --gpu_jpeg, and the GPU Huffman-decodes too: the loaders only parse the headers and ship the '
                          'compressed scan; a file the GPU flags is decoded with PIL in the detector process')
+    ap.add_argument('--crop_folder', type=str, default=None,
+                    help='write every detection at or above --crop_confidence_threshold below this folder, named and cut as '
+                         'create_crop_folder.py does; JPEG crops are encoded on the GPU from the image that is resident there')
+    ap.add_argument('--crop_confidence_threshold', type=float, default=0.1)
+    ap.add_argument('--crop_expansion', type=int, default=0, help='pixels added on every side of a crop')
+    ap.add_argument('--crop_quality', type=int, default=95)
+    ap.add_argument('--crop_categories', type=str, default=None, help='comma-separated category names; default: all')
+    ap.add_argument('--crop_results_file', type=str, default=None,
+                    help='the results with crop_id and crop_filename_relative added (create_crop_folder output_file)')
+    ap.add_argument('--crops_output_file', type=str, default=None,
+                    help='one entry per crop (create_crop_folder crops_output_file)')
     ap.add_argument('--verbose', action='store_true')
     args = ap.parse_args(argv)
+    if args.crop_folder is None:
+        assert args.crop_results_file is None and args.crops_output_file is None, \
+            '--crop_results_file / --crops_output_file need --crop_folder'
 
     assert 0.0 <= args.threshold <= 1.0, 'Confidence threshold needs to be between 0 and 1'
     assert args.output_file.endswith('.json'), 'output_file specified needs to end with .json'
@@ -920,6 +1048,11 @@ def main(argv=None):
                   preprocess_on_image_queue=args.preprocess_on_image_queue, batch_size=args.batch_size,
                   verbose_output=args.verbose, use_threads_for_queue=args.use_threads_for_queue,
                   gpu_jpeg='entropy' if args.gpu_jpeg_entropy else args.gpu_jpeg)
+    crop_base = os.path.abspath(args.image_file) if os.path.isdir(args.image_file) else None
+    if args.crop_folder is not None:
+        kwargs.update(crop_folder=args.crop_folder, crop_confidence_threshold=args.crop_confidence_threshold,
+                      crop_expansion=args.crop_expansion, crop_quality=args.crop_quality, crop_categories=args.crop_categories,
+                      crop_base=crop_base)
     t0 = time.time()
     if args.n_gpus > 1:
         results = run_sharded(args.detector_file, files, args.n_gpus, results=results, **kwargs)
@@ -934,8 +1067,13 @@ def main(argv=None):
         assert not previous_set.intersection(r['file'] for r in results), \
             'Previous results handling error: redundant image filenames'
         results.extend(previous_images)
-    write_results_to_file(results, args.output_file, relative_path_base=base, detector_file=args.detector_file,
-                          include_max_conf=args.include_max_conf)
+    final_output = write_results_to_file(results, args.output_file, relative_path_base=base, detector_file=args.detector_file,
+                                         include_max_conf=args.include_max_conf)
+    if args.crop_folder is not None and (args.crop_results_file or args.crops_output_file):
+        names = [v for v in (args.crop_categories or '').replace(',', ' ').split() if v]
+        write_crop_result_files(final_output, crops_mod.CropOptions(
+            confidence_threshold=args.crop_confidence_threshold, expansion=args.crop_expansion, quality=args.crop_quality,
+            category_names_to_include=names or None), crop_base, args.crop_results_file, args.crops_output_file)
     for cp in [checkpoint_path] + [shard_checkpoint_path(checkpoint_path, g) for g in range(max(1, args.n_gpus))]:
         if cp and os.path.isfile(cp):
             os.remove(cp)
