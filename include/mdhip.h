@@ -298,6 +298,29 @@ int mdhip_jpeg_encode(mdhip_ctx* ctx, const uint8_t* const* windows, const int32
                       int64_t capacity, int64_t* offsets, int64_t* sizes, int64_t* needed, void* hip_stream);
 long long mdhip_jpeg_encode_bound(int width, int height);
 
+/* Gaussian blur of rectangles of device images, IN PLACE (the reference blurs people in the image copies it writes:
+ * postprocessing/separate_detections_into_folders.py --category_names_to_blur, visualization_utils.blur_detections: per box
+ * crop -> ImageFilter.GaussianBlur(40) -> paste): every rectangle becomes, bit for bit, what Pillow's GaussianBlur(radius)
+ * makes of it -- three passes of an extended box filter along x, then three along y, 32-bit integers with an 8-bit
+ * rounding behind every pass, the RECTANGLE's edges replicated (csrc/blur_box.h, shared with the host model
+ * mdjpeg_blur_regions).  Running sums: the cost follows the pixels, not pixels x box length.
+ *   images, widths, heights, pitches   n_images DEVICE images, 8 bits a sample, R G B interleaved, pitches[i] bytes a row
+ *                                      (>= 3 * widths[i], any value: 3 * width is fine); every access is a single byte, so
+ *                                      nothing beside a rectangle is read or written; sizes 1 .. 65535, below 2 GB
+ *   rect_image, rects, n_rects         rectangle i lies in image rect_image[i] and is rects[4 i .. 4 i + 3] = left, top,
+ *                                      right, bottom in pixels, right and bottom exclusive.  The rectangles of ONE image
+ *                                      are applied in the order of the list, each to what the earlier ones left (so
+ *                                      overlapping rectangles interact as they do in the reference); rectangles of
+ *                                      different images run side by side: launch round k takes the k-th rectangle of
+ *                                      every image.  A rectangle without area (right <= left or bottom <= top) is
+ *                                      skipped, as Pillow pastes nothing for it; any other that leaves its image is
+ *                                      MDHIP_EINVAL, and then nothing has been launched.
+ *   radius                             of the Gaussian, 0 .. 512 (0 changes nothing); 40 in the reference
+ * The call only enqueues (two launches per round).  Scratch -- two planes per rectangle of the largest round -- grows on
+ * demand (the device is synchronised when it does): keep all mdhip_blur_regions calls of one context on ONE stream. */
+int mdhip_blur_regions(mdhip_ctx* ctx, uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
+                       int n_images, const int32_t* rect_image, const int32_t* rects, int n_rects, float radius, void* hip_stream);
+
 /* Test-time augmentation: replaces mdhip_forward for `model(batch, augment=True)` (reference
  * pytorch_detector.py:1313 -> yolov5 _forward_augment): three passes over the batch that mdhip_preprocess
  * left in the context -- scale 1, scale 0.83 left-right flipped, scale 0.67 (bilinear, padded with 0.447 to

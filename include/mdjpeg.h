@@ -106,6 +106,25 @@ int mdjpeg_encode_subsequences(const int16_t* const* coefs, const int32_t* width
                                uint8_t* out, size_t capacity, int64_t* offsets, int64_t* sizes, size_t* needed);
 int64_t mdjpeg_encode_bound(int32_t width, int32_t height);
 
+/* ---- Gaussian blur of rectangles (GPU: mdhip_blur_regions, include/mdhip.h) -------------------------------------------- */
+/* The host model of the GPU blur and the host leg of HIPDetector(blur=): Pillow's ImageFilter.GaussianBlur(radius) of
+ * rectangles of an RGB image, bit for bit -- three passes of an extended box filter along x, then three along y, in 32-bit
+ * integers with an 8-bit rounding behind every pass, the rectangle's own edges replicated -- with the weights, the line pass
+ * and the chunk arithmetic the kernels are compiled from (csrc/blur_box.h).
+ *   rgb, width, height, pitch   the image, 8 bits a sample, R G B interleaved, `pitch` bytes a row (>= 3 * width); changed in place
+ *   rects, n_rects              n_rects x 4 values: left, top, right, bottom in pixels, right and bottom exclusive.  They are
+ *                               applied in the order of the list, each to what the ones before it left (what
+ *                               visualization_utils.blur_detections does: crop, blur, paste), so overlapping rectangles interact.
+ *                               A rectangle without area (right <= left or bottom <= top) is skipped, as Pillow pastes
+ *                               nothing for it; any other that leaves the image is MDJPEG_EINVAL, and nothing is changed.
+ *   radius                      of the Gaussian, 0 .. 512 (0 changes nothing)
+ * mdjpeg_blur_regions_chunked cuts the rows into the chunks (with their halo) a device with lds_bytes of on-chip memory
+ * would cut them into (the device has 49152); same result.  mdjpeg_blur_weights: r, ww, fw of a radius. */
+int mdjpeg_blur_regions(uint8_t* rgb, int32_t width, int32_t height, int64_t pitch, const int32_t* rects, int n_rects, float radius);
+int mdjpeg_blur_regions_chunked(uint8_t* rgb, int32_t width, int32_t height, int64_t pitch, const int32_t* rects, int n_rects,
+                                float radius, int lds_bytes);
+int mdjpeg_blur_weights(float radius, int32_t* r, uint32_t* ww, uint32_t* fw);
+
 const char* mdjpeg_version(void);
 
 #ifdef __cplusplus

@@ -11,6 +11,7 @@
 #include "../../include/mdjpeg.h"
 #include "jpeg_subseq.h"
 #include "jpeg_encode.h"
+#include "blur_box.h"
 
 #include <cstdio>
 #include <cstring>
@@ -662,7 +663,73 @@ int64_t mdjpeg_encode_bound(int32_t width, int32_t height) {
     return mdj_enc_bound_bytes(width, height);
 }
 
-const char* mdjpeg_version(void) { return "mdjpeg 3"; }
+// the rectangles of mdjpeg_blur_regions / mdjpeg_blur_regions_chunked, one after the other; lds_bytes 0: every row in one piece
+static int blur_regions(uint8_t* rgb, int32_t width, int32_t height, int64_t pitch, const int32_t* rects, int n_rects, float radius,
+                        int lds_bytes) {
+    if (!rgb || width < 1 || height < 1 || pitch < int64_t(width) * 3 || n_rects < 0 || (n_rects && !rects)) return MDJPEG_EINVAL;
+    if (!(radius >= 0.0f) || radius > MD_BLUR_MAX_RADIUS) return MDJPEG_EINVAL;
+    for (int i = 0; i < n_rects; ++i) {
+        const int32_t* q = rects + 4 * i;
+        if (q[2] <= q[0] || q[3] <= q[1]) continue;
+        if (q[0] < 0 || q[1] < 0 || q[2] > width || q[3] > height) return MDJPEG_EINVAL;
+    }
+    const MdBlurWeights wt = md_blur_weights(radius);
+    std::vector<uint8_t> s0, s1, la, lb;
+    for (int i = 0; i < n_rects; ++i) {
+        const int32_t* q = rects + 4 * i;
+        const int w = q[2] - q[0], h = q[3] - q[1];
+        if (w <= 0 || h <= 0) continue;                                  // without area: nothing is pasted
+        uint8_t* img = rgb + int64_t(q[1]) * pitch + int64_t(q[0]) * 3;
+        const int64_t sp = int64_t(w) * 3;
+        s0.assign(size_t(sp) * h, 0);
+        s1.assign(size_t(sp) * h, 0);
+        MdBlurXPlan plan;
+        if (lds_bytes > 0) {
+            if (!md_blur_plan_x(w, wt.r, lds_bytes, &plan)) return MDJPEG_EINVAL;
+        } else {
+            plan.rows = 1, plan.stride = md_blur_row_stride(w), plan.chunks = 1, plan.step = w, plan.halo = 0;
+        }
+        la.assign(size_t(plan.stride), 0);
+        lb.assign(size_t(plan.stride), 0);
+        // the row stage, as a workgroup runs it: load a chunk with its halo, three passes per channel, keep the middle
+        for (int y = 0; y < h; ++y)
+            for (int k = 0; k < plan.chunks; ++k) {
+                int o0, o1, a, b;
+                md_blur_chunk(plan, w, k, &o0, &o1, &a, &b);
+                const int n = b - a;
+                if (size_t(n) * 3 > la.size()) return MDJPEG_EINVAL;
+                memcpy(la.data(), img + int64_t(y) * pitch + int64_t(a) * 3, size_t(n) * 3);
+                for (int c = 0; c < 3; ++c) md_blur_line3(la.data() + c, lb.data() + c, 3, n, wt);
+                memcpy(s0.data() + int64_t(y) * sp + int64_t(o0) * 3, lb.data() + size_t(o0 - a) * 3, size_t(o1 - o0) * 3);
+            }
+        // the column stage, as a lane runs it: one byte column through the three passes, the last one into the image
+        for (int64_t t = 0; t < sp; ++t) {
+            md_blur_line(s0.data() + t, sp, s1.data() + t, sp, h, wt.r, wt.ww, wt.fw);
+            md_blur_line(s1.data() + t, sp, s0.data() + t, sp, h, wt.r, wt.ww, wt.fw);
+            md_blur_line(s0.data() + t, sp, img + t, pitch, h, wt.r, wt.ww, wt.fw);
+        }
+    }
+    return MDJPEG_OK;
+}
+
+int mdjpeg_blur_regions(uint8_t* rgb, int32_t width, int32_t height, int64_t pitch, const int32_t* rects, int n_rects, float radius) {
+    return blur_regions(rgb, width, height, pitch, rects, n_rects, radius, 0);
+}
+
+int mdjpeg_blur_regions_chunked(uint8_t* rgb, int32_t width, int32_t height, int64_t pitch, const int32_t* rects, int n_rects,
+                                float radius, int lds_bytes) {
+    if (lds_bytes < 1) return MDJPEG_EINVAL;
+    return blur_regions(rgb, width, height, pitch, rects, n_rects, radius, lds_bytes);
+}
+
+int mdjpeg_blur_weights(float radius, int32_t* r, uint32_t* ww, uint32_t* fw) {
+    if (!(radius >= 0.0f) || radius > MD_BLUR_MAX_RADIUS || !r || !ww || !fw) return MDJPEG_EINVAL;
+    const MdBlurWeights wt = md_blur_weights(radius);
+    *r = wt.r, *ww = wt.ww, *fw = wt.fw;
+    return MDJPEG_OK;
+}
+
+const char* mdjpeg_version(void) { return "mdjpeg 4"; }
 
 }  // extern "C"
 
@@ -670,7 +737,48 @@ const char* mdjpeg_version(void) { return "mdjpeg 3"; }
 // `make asan-jpeg`: decodes every file named on the command line into a heap buffer of exactly coef_count values, so that
 // the sanitizers see any access outside it.  Prints one line per file; the exit status is 0 unless a sanitizer fires.
 #include <vector>
+// `--blur`: mdjpeg_blur_regions and its chunked form on heap images of exactly pitch x height bytes -- the whole image, single
+// rows and columns, rectangles on every border and the sizes around the box radius -- so that the sanitizers see any
+// access outside an image; the two forms must agree.
+static int blur_matrix() {
+    const int W = 97, H = 131;
+    const int64_t pitch = 393;
+    std::vector<int32_t> rects = {0, 0, W, H, 50, 60, 51, 61, 0, 70, W, 71, 33, 0, 34, H, 0, 0, 30, 20, W - 30, 0, W, 25, 0, H - 20, 41, H,
+                                  W - 17, H - 33, W, H, 5, 5, 5, 9, 9, 5, 5, 9};
+    for (int n : {5, 39, 40, 41, 79, 80, 81}) {
+        rects.insert(rects.end(), {1, 3, 1 + n, 50});
+        rects.insert(rects.end(), {3, 1, 26, 1 + n});
+        rects.insert(rects.end(), {2, 4, 2 + n, 4 + n});
+    }
+    const int n_rects = int(rects.size() / 4);
+    for (float radius : {40.0f, 2.0f, 7.5f, 100.0f, 0.0f, 512.0f})
+        for (int k = 0; k < n_rects; ++k) {
+            const size_t bytes = size_t(pitch) * (H - 1) + size_t(W) * 3;           // the last row ends with its last pixel
+            uint8_t* a = new uint8_t[bytes];
+            uint8_t* b = new uint8_t[bytes];
+            uint32_t seed = 12345u + uint32_t(k);
+            for (size_t i = 0; i < bytes; ++i) a[i] = b[i] = uint8_t((seed = seed * 1664525u + 1013904223u) >> 24);
+            const int ra = mdjpeg_blur_regions(a, W, H, pitch, rects.data() + 4 * k, 1, radius);
+            int32_t r;
+            uint32_t ww, fw;
+            mdjpeg_blur_weights(radius, &r, &ww, &fw);
+            const int rb = mdjpeg_blur_regions_chunked(b, W, H, pitch, rects.data() + 4 * k, 1, radius, 2 * (18 * (r + 1) + 20));
+            const bool same = memcmp(a, b, bytes) == 0;
+            delete[] a;
+            delete[] b;
+            if (ra != MDJPEG_OK || rb != MDJPEG_OK || !same) { printf("blur: rectangle %d at radius %g: %d %d %d\n", k, double(radius), ra, rb, int(same)); return 5; }
+        }
+    // all rectangles one after the other in one image, and rectangles that leave it
+    std::vector<uint8_t> img(size_t(pitch) * H, 77);
+    if (mdjpeg_blur_regions(img.data(), W, H, pitch, rects.data(), n_rects, 40.0f) != MDJPEG_OK) return 5;
+    const int32_t outside[8] = {0, 0, 5, 5, 90, 100, 98, 131};
+    if (mdjpeg_blur_regions(img.data(), W, H, pitch, outside, 2, 40.0f) != MDJPEG_EINVAL) return 5;
+    printf("blur: %d rectangles x 6 radii\n", n_rects);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc == 2 && !strcmp(argv[1], "--blur")) return blur_matrix();
     for (int i = 1; i < argc; ++i) {
         FILE* f = fopen(argv[i], "rb");
         if (!f) { printf("%s: cannot open\n", argv[i]); continue; }

@@ -44,6 +44,7 @@
 #include "mdhip_internal.h"
 #include "jpeg_subseq.h"
 #include "jpeg_encode.h"
+#include "blur_box.h"
 
 using namespace mdhip;
 
@@ -163,6 +164,8 @@ struct mdhip_ctx {
     size_t jpeg_entropy_bytes = 0;
     char* jpeg_encode = nullptr;  // mdhip_jpeg_encode: crops, tables, coefficients, lengths, offsets, bit buffer (grows on demand)
     size_t jpeg_encode_bytes = 0;
+    char* blur = nullptr;         // mdhip_blur_regions: the rectangles' records and their two planes (grows on demand)
+    size_t blur_bytes = 0;
     long long jpeg_entropy_stats[4] = {0, 0, 0, 0};   // of the last call: lanes, lanes decoded again, pass-2 launches, images
     int last_n = 0, last_h = 0, last_w = 0;
     std::string err;
@@ -1989,6 +1992,7 @@ void mdhip_destroy(mdhip_ctx* ctx) {
     if (ctx->jpeg_planes) (void)hipFree(ctx->jpeg_planes);
     if (ctx->jpeg_entropy) (void)hipFree(ctx->jpeg_entropy);
     if (ctx->jpeg_encode) (void)hipFree(ctx->jpeg_encode);
+    if (ctx->blur) (void)hipFree(ctx->blur);
     if (ctx->geom_host) (void)hipHostFree(ctx->geom_host);
     for (int i = 0; i < 4; ++i) if (ctx->geom_ev[i]) (void)hipEventDestroy(ctx->geom_ev[i]);
     if (ctx->input_free) (void)hipEventDestroy(ctx->input_free);
@@ -2542,6 +2546,98 @@ int mdhip_jpeg_encode(mdhip_ctx* ctx, const uint8_t* const* windows, const int32
         if (status[i]) return fail(ctx, MDHIP_EINVAL, "window %d: a coefficient no baseline JPEG can hold (status %u)", i, status[i]);
     if (*needed > capacity)
         return fail(ctx, MDHIP_ECAPACITY, "the scans take %lld bytes, the output buffer has %lld", (long long)*needed, (long long)capacity);
+    return MDHIP_OK;
+}
+
+int mdhip_blur_regions(mdhip_ctx* ctx, uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
+                       int n_images, const int32_t* rect_image, const int32_t* rects, int n_rects, float radius, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (n_rects == 0) return MDHIP_OK;
+    if (!images || !widths || !heights || !pitches || !rect_image || !rects)
+        return fail(ctx, MDHIP_EINVAL, "images/widths/heights/pitches/rect_image/rects is NULL");
+    if (n_images < 1 || n_images > 65535 || n_rects < 0) return fail(ctx, MDHIP_EINVAL, "n_images = %d, n_rects = %d", n_images, n_rects);
+    if (!(radius >= 0.0f) || radius > MD_BLUR_MAX_RADIUS) return fail(ctx, MDHIP_EINVAL, "radius %g outside 0 .. %g", (double)radius, (double)MD_BLUR_MAX_RADIUS);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const MdBlurWeights wt = md_blur_weights(radius);
+    // every rectangle is checked before anything is launched; round k holds the k-th rectangle with area of every image
+    std::vector<int> seen((size_t)n_images, -1), count((size_t)n_images, 0);
+    std::vector<std::vector<BlurRect>> rounds;
+    for (int i = 0; i < n_rects; ++i) {
+        const int m = rect_image[i];
+        if (m < 0 || m >= n_images) return fail(ctx, MDHIP_EINVAL, "rectangle %d: image %d of %d", i, m, n_images);
+        const int32_t* q = rects + 4 * (size_t)i;
+        if (q[2] <= q[0] || q[3] <= q[1]) continue;                     // without area: Pillow pastes nothing
+        if (seen[m] < 0) {
+            const int W = widths[m], H = heights[m];
+            if (W < 1 || H < 1 || W > 65535 || H > 65535) return fail(ctx, MDHIP_EINVAL, "image %d: %dx%d", m, W, H);
+            if (pitches[m] < (long long)W * 3 || (long long)(H - 1) * pitches[m] + (long long)W * 3 > 0x7fff0000LL)
+                return fail(ctx, MDHIP_EINVAL, "image %d: pitch %lld for %d pixels per row (or an image above 2 GB)", m, (long long)pitches[m], W);
+            hipPointerAttribute_t attr;
+            const hipError_t e = images[m] ? hipPointerGetAttributes(&attr, images[m]) : hipErrorInvalidValue;
+            if (e != hipSuccess) (void)hipGetLastError();
+            if (e != hipSuccess || !(attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged))
+                return fail(ctx, MDHIP_EINVAL, "image %d: NULL or a host pointer -- images must be device memory", m);
+            seen[m] = 1;
+        }
+        if (q[0] < 0 || q[1] < 0 || q[2] > widths[m] || q[3] > heights[m])
+            return fail(ctx, MDHIP_EINVAL, "rectangle %d: (%d, %d, %d, %d) leaves its %dx%d image", i, q[0], q[1], q[2], q[3], widths[m], heights[m]);
+        BlurRect d;
+        memset(&d, 0, sizeof(d));
+        d.img = images[m] + (long long)q[1] * pitches[m] + (long long)q[0] * 3;
+        d.pitch = pitches[m];
+        d.w = q[2] - q[0];
+        d.h = q[3] - q[1];
+        d.sp = (int)align_up((size_t)d.w * 3, 64);
+        MdBlurXPlan plan;
+        if (!md_blur_plan_x(d.w, wt.r, BLUR_LDS_BYTES, &plan) || (long long)plan.rows * plan.stride * 2 > BLUR_LDS_BYTES)
+            return fail(ctx, MDHIP_EUNSUPPORTED, "rectangle %d: no row plan for %d pixels at box radius %d", i, d.w, wt.r);
+        d.rows = plan.rows, d.stride = plan.stride, d.chunks = plan.chunks, d.step = plan.step, d.halo = plan.halo;
+        d.row_groups = (d.h + d.rows - 1) / d.rows;
+        const size_t k = (size_t)count[m]++;
+        if (rounds.size() <= k) rounds.resize(k + 1);
+        rounds[k].push_back(d);
+    }
+    if (rounds.empty()) return MDHIP_OK;
+    // the scratch: [records of all rounds][planes of one round]; the rounds run one after the other and share the planes
+    size_t n_records = 0, plane_bytes = 0;
+    for (auto& round : rounds) {
+        size_t cur = 0;
+        for (BlurRect& d : round) {
+            const size_t one = align_up((size_t)d.sp * (size_t)d.h, 256);
+            d.s0 = (long long)cur;
+            d.s1 = (long long)(cur + one);
+            cur += 2 * one;
+        }
+        plane_bytes = std::max(plane_bytes, cur);
+        n_records += round.size();
+    }
+    const size_t o_planes = align_up(sizeof(BlurRect) * n_records, 256);
+    const size_t total = o_planes + plane_bytes;
+    if (total > ctx->blur_bytes) {
+        HIP_TRY(ctx, hipDeviceSynchronize());                  // an earlier call's kernels may still use the old scratch
+        if (ctx->blur) HIP_TRY(ctx, hipFree(ctx->blur));
+        ctx->blur = nullptr;
+        ctx->blur_bytes = 0;
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->blur, total));
+        ctx->blur_bytes = total;
+    }
+    std::vector<BlurRect> up;
+    up.reserve(n_records);
+    for (auto& round : rounds) up.insert(up.end(), round.begin(), round.end());
+    // (the upload is from pageable memory: the copy has left `up` when the call returns)
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->blur, up.data(), sizeof(BlurRect) * n_records, hipMemcpyHostToDevice, s));
+    size_t first = 0;
+    for (auto& round : rounds) {
+        int max_blocks = 1, max_width = 1;
+        for (const BlurRect& d : round) {
+            max_blocks = std::max(max_blocks, d.row_groups * d.chunks);
+            max_width = std::max(max_width, d.w);
+        }
+        HIP_TRY(ctx, launch_blur_round((const BlurRect*)ctx->blur + first, (int)round.size(), max_blocks, max_width,
+                                       (uint8_t*)ctx->blur + o_planes, wt.r, wt.ww, wt.fw, s));
+        first += round.size();
+    }
     return MDHIP_OK;
 }
 

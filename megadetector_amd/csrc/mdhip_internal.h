@@ -530,4 +530,23 @@ struct JpegEncDev {
 hipError_t launch_jpeg_encode(const JpegEncDev& d, hipStream_t s);
 long long jpeg_encode_scan_tiles(long long n);
 
+// ---------------------------------------------------------------------------------------
+// Gaussian blur of rectangles (blur_kernels.cpp): one record per rectangle, read by the workgroups of a launch (blockIdx.y)
+// ---------------------------------------------------------------------------------------
+constexpr int BLUR_LDS_BYTES = 49152;  // the two row buffers of a workgroup of the row stage (blur_box.h md_blur_plan_x)
+struct BlurRect {
+    uint8_t*  img;                     // the rectangle's first byte in its image
+    long long pitch;                   // bytes from row to row of the image
+    long long s0, s1;                  // the rectangle's two planes in the scratch buffer: byte offsets, sp bytes a row
+    int w, h;                          // pixels
+    int sp;                            // bytes a row of a plane: >= 3 w
+    int rows, stride, chunks, step, halo;  // blur_box.h MdBlurXPlan
+    int row_groups;                    // (h + rows - 1) / rows: the row stage runs row_groups * chunks workgroups
+    int pad;
+};
+// one rectangle of each of n images: rows -> scratch, columns -> image.  max_row_blocks / max_width: the largest
+// row_groups * chunks and w among the n records
+hipError_t launch_blur_round(const BlurRect* rects, int n, int max_row_blocks, int max_width, uint8_t* scratch, int r, uint32_t ww,
+                             uint32_t fw, hipStream_t s);
+
 }  // namespace mdhip

@@ -293,6 +293,28 @@ class HipContext:
         """bytes the scan of a width x height window can take at the very most (mdhip_jpeg_encode_bound)"""
         return int(_lib.load().mdhip_jpeg_encode_bound(int(width), int(height)))
 
+    def blur_regions(self, ptrs, sizes, pitches, rect_image, rects, radius=40, stream=0):
+        """
+        Pillow's ImageFilter.GaussianBlur(radius) of rectangles of device images, in place and bit for bit
+        (include/mdhip.h: mdhip_blur_regions).
+        ptrs, sizes, pitches: per image the device address of an RGB uint8 image, its (width, height) and its bytes a row
+        rect_image, rects: per rectangle the index of its image and (left, top, right, bottom), right / bottom exclusive.
+        The rectangles of one image are applied in list order; a rectangle without area is skipped.  Only enqueues.
+        """
+        n, m = len(ptrs), len(rects)
+        if not (len(sizes) == len(pitches) == n) or len(rect_image) != m:
+            raise ValueError('ptrs, sizes and pitches must have one entry per image, rect_image and rects one per rectangle')
+        if m == 0:
+            return
+        p = (C.c_void_p * n)(*[int(v) for v in ptrs])
+        ws = (C.c_int32 * n)(*[int(v[0]) for v in sizes])
+        hs = (C.c_int32 * n)(*[int(v[1]) for v in sizes])
+        pt = (C.c_int64 * n)(*[int(v) for v in pitches])
+        ri = (C.c_int32 * m)(*[int(v) for v in rect_image])
+        rc4 = (C.c_int32 * (4 * m))(*[int(v) for q in rects for v in q])
+        self._check(self.lib.mdhip_blur_regions(self.h, C.cast(p, C.POINTER(C.c_void_p)), ws, hs, pt, n, ri, rc4, m,
+                                                C.c_float(float(radius)), C.c_void_p(stream)), 'mdhip_blur_regions')
+
     def forward(self, n, h, w, stream=0):
         self._check(self.lib.mdhip_forward(self.h, int(n), int(h), int(w), C.c_void_p(stream)), 'mdhip_forward')
 

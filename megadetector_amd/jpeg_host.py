@@ -51,6 +51,10 @@ SYMBOLS = {
                                              C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                              C.POINTER(C.c_size_t)]),
     'mdjpeg_encode_bound': (C.c_int64, [C.c_int32, C.c_int32]),
+    'mdjpeg_blur_regions': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_float]),
+    'mdjpeg_blur_regions_chunked': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int,
+                                              C.c_float, C.c_int]),
+    'mdjpeg_blur_weights': (C.c_int, [C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     'mdjpeg_version': (C.c_char_p, []),
 }
 
@@ -286,6 +290,34 @@ def encode_subsequences(coefs, sizes, chunk_bytes=64, capacity=None):
         raise AssertionError('mdjpeg_encode_subsequences wrote beyond its capacity')
     scans = [buf[offs[i]:offs[i] + lens[i]].tobytes() for i in range(n)] if rc == MDJPEG_OK else None
     return rc, scans, int(need.value), buf[:capacity]
+
+
+def blur_regions(rgb, rects, radius, lds_bytes=None):
+    """
+    Pillow's GaussianBlur(radius) of rectangles of an H x W x 3 uint8 array, IN PLACE and in the order of the list
+    (mdjpeg_blur_regions: the host model of the GPU blur and the host leg of blur=).  rects: (left, top, right, bottom),
+    right / bottom exclusive; rows may be strided (a view of a wider array).  lds_bytes: cut the rows into the chunks a
+    device with that much on-chip memory would (mdjpeg_blur_regions_chunked; same result).  Returns the library's code.
+    """
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.strides[1:] != (3, 1) or not rgb.flags.writeable:
+        raise ValueError('rgb must be a writeable H x W x 3 uint8 array with contiguous rows')
+    n = len(rects)
+    flat = (C.c_int32 * max(4 * n, 1))(*[int(v) for q in rects for v in q])
+    h, w = rgb.shape[:2]
+    pitch = rgb.strides[0] if h > 1 else w * 3
+    lib = load()
+    if lds_bytes is None:
+        return lib.mdjpeg_blur_regions(rgb.ctypes.data, w, h, pitch, flat, n, float(radius))
+    return lib.mdjpeg_blur_regions_chunked(rgb.ctypes.data, w, h, pitch, flat, n, float(radius), int(lds_bytes))
+
+
+def blur_weights(radius):
+    """(r, ww, fw) of Pillow's extended box filter for a Gaussian radius (mdjpeg_blur_weights)"""
+    r, ww, fw = C.c_int32(0), C.c_uint32(0), C.c_uint32(0)
+    rc = load().mdjpeg_blur_weights(float(radius), C.byref(r), C.byref(ww), C.byref(fw))
+    if rc != MDJPEG_OK:
+        raise ValueError('radius {!r} is outside 0 .. 512'.format(radius))
+    return int(r.value), int(ww.value), int(fw.value)
 
 
 # ---- a coefficient image in a ring slot (feed.py decode='coefficients') ------------------------------------------------

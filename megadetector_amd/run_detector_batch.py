@@ -41,6 +41,7 @@ from .feed import load_image, EXIF_IMAGE_ROTATIONS          # noqa: F401  (re-ex
 from .constants import FAILURE_IMAGE_OPEN, FAILURE_INFER, DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD
 from .constants import DEFAULT_DETECTOR_LABEL_MAP
 from . import crops as crops_mod
+from . import blur as blur_mod
 from .jpeg_host import ScanFailure
 
 # reference run_detector_batch.py:86-119
@@ -201,6 +202,64 @@ class _CropWriter:
             for _, name, _ in named:
                 self.counts['files'] += 1
                 self.counts[kinds[0] if crops_mod.is_jpeg_name(name) else kinds[1]] += 1
+
+
+# --------------------------------------------------------------------------------------------
+# blurred copies (reference postprocessing/separate_detections_into_folders.py --category_names_to_blur, written while
+# the images are at hand)
+# --------------------------------------------------------------------------------------------
+#: blurred copies of the most recent run in this process: 'files' written, of them 'gpu' = made by the detector from the
+#: image in device memory (blur=), 'host' = blurred and saved here (a detector without blur=)
+last_blur_counts = {}
+
+
+class _BlurWriter:
+    """writes the blurred copy of an image that has something to blur to <blur folder>/<relative path>, BEFORE its result
+    is handed on (as _CropWriter does, and for the same reason); no other image is written"""
+
+    def __init__(self, folder, options, base):
+        self.folder, self.options, self.base = folder, options, base
+        self.category_ids = options.category_ids()
+        self.counts = {'files': 0, 'gpu': 0, 'host': 0}
+
+    def detector_kw(self, detector):
+        return {'blur': self.options} if getattr(detector, 'supports_blur', False) else {}
+
+    _pixels = _CropWriter._pixels
+
+    def write(self, results, images):
+        for i, r in enumerate(results):
+            from_detector = 'blurred' in r
+            data = r.pop('blurred', None)
+            if r.get('detections') is None:
+                continue
+            rel = _crop_relative_name(r['file'], self.base)
+            if not from_detector and blur_mod.select_detections(r['detections'], self.options, self.category_ids):
+                # a detector without blur=, or pixels that never were in device memory: the host leg
+                data = blur_mod.blurred_file_of_host_image(self._pixels(images[i] if images else None, r['file']), rel,
+                                                           r['detections'], self.options, self.category_ids)
+            if data is None:
+                continue
+            blur_mod.write_blurred(self.folder, rel, data)
+            self.counts['files'] += 1
+            self.counts['gpu' if from_detector else 'host'] += 1
+
+
+class _Writers:
+    """several writers behind the one hook of the loops (detector_kw / write)"""
+
+    def __init__(self, writers):
+        self.writers = writers
+
+    def detector_kw(self, detector):
+        kw = {}
+        for w in self.writers:
+            kw.update(w.detector_kw(detector))
+        return kw
+
+    def write(self, results, images):
+        for w in self.writers:
+            w.write(results, images)
 
 
 def _crop_kw(crop_writer, detector):
@@ -621,7 +680,9 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
                                 preprocess_on_image_queue=default_preprocess_on_image_queue, batch_size=1,
                                 verbose_output=False, use_threads_for_queue=True, detector=None, gpu_jpeg=False,
                                 crop_folder=None, crop_confidence_threshold=0.1, crop_expansion=0, crop_quality=95,
-                                crop_categories=None, crop_base=None):
+                                crop_categories=None, crop_base=None,
+                                blur_folder=None, blur_categories=('person',), blur_confidence_threshold=None, blur_radius=40,
+                                blur_quality=85, blur_base=None):
     """
     reference :1062-1439.  `detector` (extra, optional) injects an already constructed detector
     object -- used by run_sharded and by the CPU tests of the loop with a stub detector.
@@ -635,9 +696,15 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
     (HIPDetector) encodes JPEG crops on the GPU from the resident image; other extensions, and other detectors, go through
     PIL here.  An image's crops are on disk before its result can reach a checkpoint.  The results are the same objects
     as without it.
+    `blur_folder` (extra, default None = off): every image with a detection of blur_categories at or above
+    blur_confidence_threshold (None: blur.DEFAULT_BLUR_CONFIDENCE_THRESHOLD, the reference script's default) is written to
+    <blur_folder>/<path relative to blur_base> with those boxes blurred as visualization_utils.blur_detections blurs them
+    (Gaussian, blur_radius) and saved at blur_quality; no other image is written.  A detector with blur= (HIPDetector)
+    blurs and encodes a copy of the image on the GPU; other detectors, and pixels that are not in device memory, go
+    through libmdjpeg.so and PIL here.  The results are the same objects as without it.
     Returns the list of per-image result dicts.
     """
-    global verbose, last_crop_counts
+    global verbose, last_crop_counts, last_blur_counts
     verbose = bool(verbose_output)
     crop_writer = None
     if crop_folder is not None:
@@ -647,6 +714,14 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
             category_names_to_include=names or None,
             output_threshold=DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD if confidence_threshold is None else confidence_threshold), crop_base)
         last_crop_counts = crop_writer.counts         # (of the most recent call, for reporting; the writer itself is local)
+    if blur_folder is not None:
+        blur_writer = _BlurWriter(blur_folder, blur_mod.BlurOptions(
+            category_names=blur_categories,
+            confidence_threshold=blur_mod.DEFAULT_BLUR_CONFIDENCE_THRESHOLD if blur_confidence_threshold is None else blur_confidence_threshold,
+            radius=blur_radius, quality=blur_quality,
+            output_threshold=DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD if confidence_threshold is None else confidence_threshold), blur_base)
+        last_blur_counts = blur_writer.counts
+        crop_writer = blur_writer if crop_writer is None else _Writers([crop_writer, blur_writer])
     if detector_options is None:
         detector_options = {}
     elif isinstance(detector_options, (list, str)):
@@ -999,8 +1074,22 @@ def main(argv=None):
                     help='the results with crop_id and crop_filename_relative added (create_crop_folder output_file)')
     ap.add_argument('--crops_output_file', type=str, default=None,
                     help='one entry per crop (create_crop_folder crops_output_file)')
+    ap.add_argument('--blur_folder', type=str, default=None,
+                    help='write a copy of every image with a detection of --blur_categories at or above '
+                         '--blur_confidence_threshold to this folder (same relative path), those boxes blurred as '
+                         'separate_detections_into_folders.py --category_names_to_blur blurs them; the copy is blurred and '
+                         'encoded on the GPU from the image that is resident there.  No other image is written')
+    ap.add_argument('--blur_categories', type=str, default=None, help='comma-separated category names; default: person')
+    ap.add_argument('--blur_confidence_threshold', type=float, default=None,
+                    help='default: {} (the typical detection threshold the reference script falls back to)'.format(
+                        blur_mod.DEFAULT_BLUR_CONFIDENCE_THRESHOLD))
+    ap.add_argument('--blur_radius', type=float, default=None, help='radius of the Gaussian; default 40, as the reference')
+    ap.add_argument('--blur_quality', type=int, default=None, help='JPEG quality of the copies; default 85, as the reference')
     ap.add_argument('--verbose', action='store_true')
     args = ap.parse_args(argv)
+    if args.blur_folder is None:
+        assert args.blur_categories is None and args.blur_confidence_threshold is None and args.blur_radius is None \
+            and args.blur_quality is None, '--blur_categories / --blur_confidence_threshold / --blur_radius / --blur_quality need --blur_folder'
     if args.crop_folder is None:
         assert args.crop_results_file is None and args.crops_output_file is None, \
             '--crop_results_file / --crops_output_file need --crop_folder'
@@ -1053,6 +1142,12 @@ def main(argv=None):
         kwargs.update(crop_folder=args.crop_folder, crop_confidence_threshold=args.crop_confidence_threshold,
                       crop_expansion=args.crop_expansion, crop_quality=args.crop_quality, crop_categories=args.crop_categories,
                       crop_base=crop_base)
+    if args.blur_folder is not None:
+        kwargs.update(blur_folder=args.blur_folder, blur_categories=args.blur_categories or 'person',
+                      blur_confidence_threshold=args.blur_confidence_threshold,
+                      blur_radius=blur_mod.DEFAULT_BLUR_RADIUS if args.blur_radius is None else args.blur_radius,
+                      blur_quality=blur_mod.DEFAULT_BLUR_QUALITY if args.blur_quality is None else args.blur_quality,
+                      blur_base=crop_base)
     t0 = time.time()
     if args.n_gpus > 1:
         results = run_sharded(args.detector_file, files, args.n_gpus, results=results, **kwargs)
