@@ -1,11 +1,13 @@
-// C-ABI layer (include/mdhip.h): model planning, weight packing, buffer arena, executor.
+// C-ABI layer (include/mdhip.h): model planning, weight packing, buffer arena, executor, NMS, fp8 calibration and the setters.
 //
 // This is the native runtime under the Python detector seam
 // (reference megadetector/detection/pytorch_detector.py:739 PTDetector):
 //   mdhip_create      <- PTDetector.__init__/_load_model            (:745-959)
-//   mdhip_preprocess  <- letterbox + tensor prep                    (:1104-1109, :1283-1310)
 //   mdhip_forward     <- self.model(batch)[0]                       (:1313)
 //   mdhip_nms         <- nms()                                      (:502-610, :1342)
+// The context and what the host files share are in mdhip_ctx.h.  The image entry points (mdhip_preprocess <- letterbox +
+// tensor prep :1104-1109, :1283-1310; the windows, JPEG and blur calls) are in mdhip_image_api.cpp, the single-kernel test
+// hooks (mdhip_*_on) in mdhip_kernel_hooks.cpp.
 //
 // Planning turns the YOLOv5 module list into a flat list of ops over channel-strided NHWC
 // bf16 views of one device arena:
@@ -35,190 +37,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <string>
-#include <tuple>
-#include <vector>
 
-#include "../../include/mdhip.h"
-#include "mdhip_internal.h"
-#include "jpeg_subseq.h"
-#include "jpeg_encode.h"
-#include "blur_box.h"
+#include "mdhip_ctx.h"
 
-using namespace mdhip;
+static thread_local std::string g_create_error;   // of the last failed mdhip_create of this thread (there is no context yet)
 
-namespace {
-
-thread_local std::string g_create_error;
-
-struct Tensor {
-    size_t off = 0;   // byte offset into the arena
-    int ld = 0;       // elements between consecutive pixels
-    int c = 0;        // channels of the view
-    int div = 1;      // spatial size = network input / div
-    bool valid = false;
-};
-
-struct PackedConv {
-    size_t w_off = 0, b_off = 0;     // byte offsets into the weight arena
-    size_t w4_off = 0;               // second packing for the row-patch kernel (0 = none)
-    int k_pad4 = 0, groups = 0;
-    size_t w4p_off = 0;              // the same with the half-full last group's taps paired (conv_v5.cpp; 0 = none)
-    int k_pad4p = 0;
-    int n_rows = 0, k_pad = 0, cin_pad = 0, kh = 0, kw = 0, c_out = 0, k_real = 0;
-    // fp8 form (MDHIP_DTYPE_FP8, 3x3 / stride-1 bottleneck convs): e4m3 weights [n_rows][groups8*9*128], quantised per
-    // output channel (wscale[n] = max_k |w[n][k]| / 448); scale_off = device array of n_rows floats holding
-    // activation scale x wscale[n], written by mdhip_calibrate / mdhip_fp8_set_scales
-    size_t w8_off = 0, scale_off = 0;
-    int k_pad8 = 0, groups8 = 0;
-    std::vector<float> wscale;
-};
-
-enum OpKind { OP_CONV = 0, OP_POOL = 1, OP_UPSAMPLE = 2, OP_DECODE = 3, OP_COPY = 4, OP_DW = 5, OP_ATTN = 6, OP_DFL = 7,
-              OP_ADOWN = 8, OP_CBFUSE = 9 };
-
-struct Op {
-    int kind = OP_CONV;
-    int layer = -1;
-    std::string name;
-    Tensor in, out, res;
-    bool has_res = false;
-    int pc = -1;
-    int stride = 1, pad = 0, act = 1, out_f32 = 0;
-    int pool_k = 5;
-    int level = 0;            // decode
-    size_t f32_off = 0;       // decode: logits buffer offset ; conv with out_f32: same ; DFL decode: box logits
-    int f32_ld = 0;
-    size_t cls_off = 0;       // DFL decode: class logits (fp32, pitch cls_ld)
-    int cls_ld = 0;
-    int dw_grp = 0, dw_grp_stride = 0, dw_grp_off = 0;   // depthwise: input channel of output channel o (yolo11_kernels.cpp)
-    int heads = 0;            // attention
-    Tensor out2;              // ADown pools: the max-pooled half (out = the averaged half)
-    Tensor fsrc[3];           // CBFuse: the CBLinear splits added to `in`, their nearest-resize factors
-    int ffac[3] = {1, 1, 1};
-    int n_fsrc = 0;
-    int forced_cfg = -1;
-    // fp8 mode: this op writes (f8_out) / reads (f8_in) an e4m3 tensor; f8_peer = the op at the other end of it;
-    // act_scale = the tensor's scale (value = e4m3 x act_scale), 0 until calibrated; amax = largest |x| seen
-    bool f8_out = false, f8_in = false;
-    int f8_peer = -1;
-    float act_scale = 0.f, amax = 0.f;
-    // fused bottleneck (conv_v5c.cpp): fuse_role 1 = the 1x1 of bottleneck fuse_idx of C3 block fuse_group, 2 = its 3x3
-    int fuse_group = -1, fuse_idx = -1, fuse_role = 0;
-    double pre_flops = 0;
-    // upsample read in place (conv_v2.cpp): an OP_UPSAMPLE whose only reader is the 1x1 conv `up_peer` (and vice versa)
-    int up_peer = -1;
-    // Detect: the 1x1 conv of a level and its OP_DECODE (the next op); dec_done = the conv of THIS forward decoded in its
-    // epilogue, the decode op has nothing left to launch
-    bool dec_done = false;
-    size_t amax_off = 0;
-    // the configuration chosen for the last (n, h, w): the table walk is not repeated on every launch
-    int memo_n = 0, memo_h = 0, memo_w = 0, memo_cfg = -1;
-    bool memo_from_table = false;
-    int last_cfg = -1;
-    // stats for the last (n,h,w)
-    int gm = 0, gn = 0, gk = 0;
-    double flops = 0, bytes = 0;
-};
-
-}  // namespace
-
-struct mdhip_ctx {
-    int device = 0;
-    int dtype = 0;
-    int max_batch = 0, max_h = 0, max_w = 0;
-    int nc = 0, na = 0, nl = 0, no = 0;
-    bool anchor_free = false;     // the model ends in MDHIP_DETECT_DFL: predictions [cx, cy, w, h, cls...], ultralytics NMS
-    std::vector<float> strides;
-    int max_stride = 0;
-    std::vector<mdhip_layer> layers;
-    std::vector<Tensor> layer_out;
-    std::vector<PackedConv> packed;
-    std::vector<Op> ops;
-    Tensor input;                 // space-to-depth network input (16 channels, div 2)
-    Tensor input_orig;            // copy of it during test-time augmentation (the scaled passes overwrite `input`)
-    DecodeTta cur_tta;            // how the Detect decode of the running pass places its anchors
-    int cur_A = 0;                // anchors per image of the prediction being written (row pitch of `pred`)
-    int last_A = 0;               // anchors per image of the last forward (plain or augmented)
-    int a_cap = 0;                // capacity of `pred` and of the NMS scratch, anchors per image
-    size_t arena_bytes = 0;
-    char* arena = nullptr;
-    char* warena = nullptr;       // packed weights + biases + zero page + anchors
-    size_t warena_bytes = 0;
-    size_t zero_off = 0, anchors_off = 0;
-    // fp32 predictions [max_batch][a_cap][no], two of them: every forward writes the other one, so that the NMS of
-    // batch i (on its own stream) may still read its predictions while the forward of batch i+1 runs
-    size_t pred_offs[2] = {0, 0};
-    int pred_cur = 0;
-    size_t pred_off = 0;          // = pred_offs[pred_cur]: the prediction of the last forward
-    int a_max = 0;
-    NmsScratch nms_scr{};
-    size_t nms_out_off = 0, nms_cnt_off = 0;
-    size_t geom_off = 0;
-    char* stage = nullptr;        // device staging for host images
-    size_t stage_bytes = 0;
-    char* jpeg_planes = nullptr;  // mdhip_jpeg_reconstruct: u8 component planes between the IDCT and the colour kernel
-    size_t jpeg_planes_bytes = 0;
-    char* jpeg_entropy = nullptr; // mdhip_jpeg_entropy_decode: descriptors, lane records, block energies (grows on demand)
-    size_t jpeg_entropy_bytes = 0;
-    char* jpeg_encode = nullptr;  // mdhip_jpeg_encode: crops, tables, coefficients, lengths, offsets, bit buffer (grows on demand)
-    size_t jpeg_encode_bytes = 0;
-    char* blur = nullptr;         // mdhip_blur_regions: the rectangles' records and their two planes (grows on demand)
-    size_t blur_bytes = 0;
-    long long jpeg_entropy_stats[4] = {0, 0, 0, 0};   // of the last call: lanes, lanes decoded again, pass-2 launches, images
-    int last_n = 0, last_h = 0, last_w = 0;
-    std::string err;
-    // fp8 mode: until every e4m3 tensor has a scale (mdhip_calibrate / mdhip_fp8_set_scales) the forward refuses
-    // to run; `calibrating` makes run_op execute every op in 16 bits and record the range of the tensors
-    bool calibrated = false, calibrating = false;
-    int n_f8 = 0;
-    // C3 blocks whose bottlenecks can run as one launch each (1x1 -> LDS -> 3x3): op indices of the 3x3s per block
-    std::vector<std::vector<int>> fuse_groups;
-    bool fuse_enabled = true, fuse_suspended = false;
-    bool pair_enabled = true;         // paired taps of a half-full last channel group (conv_v5.cpp); MDHIP_PAIR=0 at create: off
-    bool fuse_decode = true;          // Detect decode in the epilogue of the Detect 1x1 convs (mdhip_set_option "fuse_decode")
-    bool letterbox_general = false;   // MDHIP_LETTERBOX_GENERAL at create: never take the streaming-copy letterbox (A/B, tests)
-    std::vector<hipEvent_t> events;
-    std::vector<mdhip_tuned> tuned;   // measured tile choices (tools/autotune.py)
-    // optional event pair around every mdhip_forward (bench.py's live roofline measurement)
-    static constexpr int kFwdRing = 64;
-    bool time_forward = false;
-    hipEvent_t fwd_ev[kFwdRing][2] = {};
-    long long fwd_count = 0;
-    // pinned host staging: letterbox geometry ring + asynchronous NMS result slots
-    uint8_t* geom_host = nullptr;      // 4 slots of max_batch * sizeof(LetterboxWin) (the larger of the two geometry records)
-    int geom_slot = 0;
-    hipEvent_t geom_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    float* nms_host_out[MDHIP_NMS_SLOTS] = {};
-    int32_t* nms_host_cnt[MDHIP_NMS_SLOTS] = {};
-    hipEvent_t nms_ev[MDHIP_NMS_SLOTS] = {};
-    int nms_slot_n[MDHIP_NMS_SLOTS] = {};
-    // mdhip_set_graph: the op sequence of a forward captured once per (batch, height, width, prediction buffer) and
-    // replayed with one hipGraphLaunch (small batches are bound by ~160 launches of a few microseconds of work each)
-    int graph_mode = 0;                                   // 0 = off, 1 = on, 2 = on for batches <= graph_max_n
-    int graph_max_n = 8;
-    hipStream_t capture_stream = nullptr;
-    // `disabled`: capture or instantiation failed once for this shape -- it runs eagerly from then on; `last_use`: LRU stamp
-    struct GraphSlot { hipGraphExec_t exec = nullptr; int seen = 0; bool disabled = false; long long last_use = 0; };
-    std::map<std::tuple<int, int, int, int>, GraphSlot> graphs;
-    static constexpr int kMaxGraphs = 32;                 // cached executables (letterbox shapes x batch sizes x 2 buffers)
-    long long graph_clock = 0;
-    // recorded on the forward's stream behind the last op that reads the network input (last_input_op): a following
-    // mdhip_preprocess -- possibly on ANOTHER stream, next to the rest of this forward -- waits for it before it overwrites
-    // the input tensor
-    hipEvent_t input_free = nullptr;
-    bool input_free_valid = false;
-    int last_input_op = 0;        // the last op that reads the network input (a model may have several stems)
-    // the NMS that reads prediction buffer k (possibly on another stream: mdhip_nms_enqueue) records pred_read[k]; the
-    // forward that is about to overwrite buffer k waits for it -- the ordering is the library's, not the caller's
-    hipEvent_t pred_read[2] = {nullptr, nullptr};
-    bool pred_read_valid[2] = {false, false};
-};
-
-namespace {
-
-int fail(mdhip_ctx* ctx, int code, const char* fmt, ...) {
+int mdhip::fail(mdhip_ctx* ctx, int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -227,6 +51,17 @@ int fail(mdhip_ctx* ctx, int code, const char* fmt, ...) {
     if (ctx) ctx->err = buf; else g_create_error = buf;
     return code;
 }
+
+int mdhip::check_shape(mdhip_ctx* ctx, int n, int h, int w) {
+    if (n < 1 || n > ctx->max_batch) return fail(ctx, MDHIP_EINVAL, "batch %d outside [1,%d]", n, ctx->max_batch);
+    if (h < ctx->max_stride || w < ctx->max_stride || h % ctx->max_stride || w % ctx->max_stride)
+        return fail(ctx, MDHIP_EINVAL, "input %dx%d must be a positive multiple of the model stride %d", h, w, ctx->max_stride);
+    if ((size_t)h * w > (size_t)ctx->max_h * ctx->max_w)
+        return fail(ctx, MDHIP_ENOMEM, "input %dx%d exceeds the planned %dx%d", h, w, ctx->max_h, ctx->max_w);
+    return MDHIP_OK;
+}
+
+namespace {
 
 // every call that changes what a forward launches drops the captured graphs (after the device has finished with them: an
 // executable may still be in flight on the caller's stream)
@@ -256,17 +91,6 @@ void evict_graph_if_full(mdhip_ctx* ctx) {
     (void)hipGraphExecDestroy(victim->second.exec);
     ctx->graphs.erase(victim);
 }
-
-#define HIP_TRY(ctx, expr)                                                                   \
-    do {                                                                                     \
-        hipError_t e__ = (expr);                                                             \
-        if (e__ != hipSuccess)                                                               \
-            return fail(ctx, MDHIP_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), \
-                        __FILE__, __LINE__);                                                 \
-    } while (0)
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-inline int round_up(int x, int a) { return (x + a - 1) / a * a; }
 
 // ---------------------------------------------------------------------------------------
 // planner
@@ -1286,15 +1110,6 @@ int apply_fp8_scale(mdhip_ctx* ctx, Op& producer, float act_scale) {
     return MDHIP_OK;
 }
 
-int check_shape(mdhip_ctx* ctx, int n, int h, int w) {
-    if (n < 1 || n > ctx->max_batch) return fail(ctx, MDHIP_EINVAL, "batch %d outside [1,%d]", n, ctx->max_batch);
-    if (h < ctx->max_stride || w < ctx->max_stride || h % ctx->max_stride || w % ctx->max_stride)
-        return fail(ctx, MDHIP_EINVAL, "input %dx%d must be a positive multiple of the model stride %d", h, w, ctx->max_stride);
-    if ((size_t)h * w > (size_t)ctx->max_h * ctx->max_w)
-        return fail(ctx, MDHIP_ENOMEM, "input %dx%d exceeds the planned %dx%d", h, w, ctx->max_h, ctx->max_w);
-    return MDHIP_OK;
-}
-
 // the conv API of the context's storage type (the kernels are compiled once per type, mdhip_internal.h)
 struct ConvApi {
     int (*num_cfgs)();
@@ -1988,11 +1803,7 @@ void mdhip_destroy(mdhip_ctx* ctx) {
             if (ctx->fwd_ev[i][k]) (void)hipEventDestroy(ctx->fwd_ev[i][k]);
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->warena) (void)hipFree(ctx->warena);
-    if (ctx->stage) (void)hipFree(ctx->stage);
-    if (ctx->jpeg_planes) (void)hipFree(ctx->jpeg_planes);
-    if (ctx->jpeg_entropy) (void)hipFree(ctx->jpeg_entropy);
-    if (ctx->jpeg_encode) (void)hipFree(ctx->jpeg_encode);
-    if (ctx->blur) (void)hipFree(ctx->blur);
+    for (DevBuffer* b : {&ctx->stage, &ctx->jpeg_planes, &ctx->jpeg_entropy, &ctx->jpeg_encode, &ctx->blur}) b->release();
     if (ctx->geom_host) (void)hipHostFree(ctx->geom_host);
     for (int i = 0; i < 4; ++i) if (ctx->geom_ev[i]) (void)hipEventDestroy(ctx->geom_ev[i]);
     if (ctx->input_free) (void)hipEventDestroy(ctx->input_free);
@@ -2011,634 +1822,6 @@ int mdhip_max_stride(mdhip_ctx* ctx) { return ctx ? ctx->max_stride : MDHIP_EINV
 int mdhip_num_anchors(mdhip_ctx* ctx, int h, int w) {
     if (!ctx) return MDHIP_EINVAL;
     return num_anchors_for(ctx, h, w);
-}
-
-// the common end of mdhip_preprocess / mdhip_preprocess_windows: G = LetterboxDev (dense images) or LetterboxWin (windows)
-extern "C++" {
-template <class G>
-static int enqueue_letterbox(mdhip_ctx* ctx, const std::vector<G>& g, int n, int out_h, int out_w, hipStream_t s) {
-    // the forward that still reads the input tensor (its stem) comes first, whatever stream it runs on
-    if (ctx->input_free_valid) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->input_free, 0));
-    if (!letterbox_geometry_travels_inline(g.data(), n, out_w, ctx->letterbox_general)) {
-        // geometry goes through a 4-deep pinned ring so that the call never blocks on the stream
-        const int slot = ctx->geom_slot;
-        ctx->geom_slot = (slot + 1) & 3;
-        HIP_TRY(ctx, hipEventSynchronize(ctx->geom_ev[slot]));          // slot's previous copy has completed
-        uint8_t* gh = ctx->geom_host + (size_t)slot * ctx->max_batch * sizeof(LetterboxWin);
-        memcpy(gh, g.data(), n * sizeof(G));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->arena + ctx->geom_off, gh, n * sizeof(G), hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipEventRecord(ctx->geom_ev[slot], s));
-    }
-    HIP_TRY(ctx, launch_letterbox_s2d((const G*)(ctx->arena + ctx->geom_off), g.data(), n, out_h, out_w,
-                                      (uint16_t*)(ctx->arena + ctx->input.off), ctx->dtype == MDHIP_DTYPE_FP16, ctx->letterbox_general, s));
-    ctx->last_n = n;
-    ctx->last_h = out_h;
-    ctx->last_w = out_w;
-    return MDHIP_OK;
-}
-}   // extern "C++"
-
-int mdhip_preprocess(mdhip_ctx* ctx, const uint8_t* const* images, const mdhip_letterbox* geom,
-                     int n, int out_h, int out_w, void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
-    if (!images || !geom) return fail(ctx, MDHIP_EINVAL, "images/geom is NULL");
-    if (int rc = check_shape(ctx, n, out_h, out_w)) return rc;
-    hipStream_t s = (hipStream_t)hip_stream;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::vector<LetterboxDev> g(n);
-    std::vector<bool> on_host(n);
-    size_t host_bytes = 0;
-    for (int i = 0; i < n; ++i) {
-        const mdhip_letterbox& q = geom[i];
-        if (!images[i] || q.src_h < 1 || q.src_w < 1 || q.resized_h < 1 || q.resized_w < 1 || q.top < 0 || q.left < 0 ||
-            q.top + q.resized_h > out_h || q.left + q.resized_w > out_w)
-            return fail(ctx, MDHIP_EINVAL, "image %d: letterbox geometry does not fit %dx%d", i, out_h, out_w);
-        hipPointerAttribute_t attr;
-        const hipError_t e = hipPointerGetAttributes(&attr, images[i]);
-        bool host = true;
-        if (e == hipSuccess) host = !(attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged);
-        else (void)hipGetLastError();
-        on_host[i] = host;
-        if (host) host_bytes += align_up((size_t)q.src_h * q.src_w * 3, 256);
-        if (q.interp != 0 && q.interp != 1) return fail(ctx, MDHIP_EINVAL, "image %d: interp %d (0 = linear, 1 = area)", i, q.interp);
-        if (q.interp == 1 && (q.resized_h > q.src_h || q.resized_w > q.src_w))
-            return fail(ctx, MDHIP_EINVAL, "image %d: INTER_AREA is implemented for shrinking only", i);
-        g[i] = LetterboxDev{images[i], q.src_h, q.src_w, q.resized_h, q.resized_w, q.top, q.left, q.interp,
-                            1.0 / ((double)q.resized_w / (double)q.src_w), 1.0 / ((double)q.resized_h / (double)q.src_h)};
-    }
-    if (host_bytes > ctx->stage_bytes) {
-        HIP_TRY(ctx, hipStreamSynchronize(s));
-        if (ctx->stage) HIP_TRY(ctx, hipFree(ctx->stage));
-        ctx->stage = nullptr;
-        ctx->stage_bytes = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->stage, host_bytes));
-        ctx->stage_bytes = host_bytes;
-    }
-    size_t cur = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!on_host[i]) continue;
-        const size_t bytes = (size_t)g[i].src_h * g[i].src_w * 3;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->stage + cur, images[i], bytes, hipMemcpyHostToDevice, s));
-        g[i].src = (const uint8_t*)(ctx->stage + cur);
-        cur += align_up(bytes, 256);
-    }
-    return enqueue_letterbox(ctx, g, n, out_h, out_w, s);
-}
-
-int mdhip_preprocess_windows(mdhip_ctx* ctx, const uint8_t* const* windows, const mdhip_letterbox* geom,
-                             const int64_t* pitches, const int64_t* readable, int n, int out_h, int out_w, void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
-    if (!windows || !geom || !pitches || !readable) return fail(ctx, MDHIP_EINVAL, "windows/geom/pitches/readable is NULL");
-    if (int rc = check_shape(ctx, n, out_h, out_w)) return rc;
-    hipStream_t s = (hipStream_t)hip_stream;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::vector<LetterboxWin> g(n);
-    for (int i = 0; i < n; ++i) {
-        const mdhip_letterbox& q = geom[i];
-        if (!windows[i] || q.src_h < 1 || q.src_w < 1 || q.resized_h < 1 || q.resized_w < 1 || q.top < 0 || q.left < 0 ||
-            q.top + q.resized_h > out_h || q.left + q.resized_w > out_w)
-            return fail(ctx, MDHIP_EINVAL, "window %d: letterbox geometry does not fit %dx%d", i, out_h, out_w);
-        hipPointerAttribute_t attr;
-        const hipError_t e = hipPointerGetAttributes(&attr, windows[i]);
-        if (e != hipSuccess) (void)hipGetLastError();
-        if (e != hipSuccess || !(attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged))
-            return fail(ctx, MDHIP_EINVAL, "window %d: host pointer -- a window must point into a device image (upload the parent image "
-                        "once and pass pointers into it)", i);
-        if (q.interp != 0 && q.interp != 1) return fail(ctx, MDHIP_EINVAL, "window %d: interp %d (0 = linear, 1 = area)", i, q.interp);
-        if (q.interp == 1 && (q.resized_h > q.src_h || q.resized_w > q.src_w))
-            return fail(ctx, MDHIP_EINVAL, "window %d: INTER_AREA is implemented for shrinking only", i);
-        // bytes from the window's first pixel to the end of its last row: all of them must be readable
-        const long long need = (long long)(q.src_h - 1) * pitches[i] + (long long)q.src_w * 3;
-        if (pitches[i] < (long long)q.src_w * 3 || need > 0x7fff0000LL)
-            return fail(ctx, MDHIP_EINVAL, "window %d: pitch %lld for %d pixels per row (or a window above 2 GB)", i, (long long)pitches[i], q.src_w);
-        if (readable[i] < need)
-            return fail(ctx, MDHIP_EINVAL, "window %d: %lld readable bytes, the window spans %lld", i, (long long)readable[i], need);
-        g[i].d = LetterboxDev{windows[i], q.src_h, q.src_w, q.resized_h, q.resized_w, q.top, q.left, q.interp,
-                              1.0 / ((double)q.resized_w / (double)q.src_w), 1.0 / ((double)q.resized_h / (double)q.src_h)};
-        // (the kernels look at most 16 bytes behind what they use: a larger figure says nothing more, and this one fits 32 bits)
-        g[i].readable = std::min<long long>(readable[i], need + 64);
-        g[i].pitch = (int)pitches[i];
-        g[i].reserved = 0;
-    }
-    return enqueue_letterbox(ctx, g, n, out_h, out_w, s);
-}
-
-int mdhip_jpeg_reconstruct(mdhip_ctx* ctx, const mdhip_jpeg_image* images, int n, uint8_t* const* out_rgb, void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
-    if (!images || !out_rgb) return fail(ctx, MDHIP_EINVAL, "images/out_rgb is NULL");
-    if (n < 1) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
-    hipStream_t s = (hipStream_t)hip_stream;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::vector<JpegDev> devs(n);
-    size_t planes_bytes = 0;
-    for (int i = 0; i < n; ++i) {
-        const mdhip_jpeg_image& q = images[i];
-        JpegDev& d = devs[i];
-        if (q.width < 1 || q.height < 1 || q.width > 65535 || q.height > 65535 || (q.components != 1 && q.components != 3))
-            return fail(ctx, MDHIP_EINVAL, "jpeg image %d: %dx%d with %d components", i, q.width, q.height, q.components);
-        const bool samp_ok = q.components == 1 ? (q.h_samp == 1 && q.v_samp == 1)
-                                               : ((q.h_samp == 1 && q.v_samp == 1) || (q.h_samp == 2 && q.v_samp == 1) ||
-                                                  (q.h_samp == 2 && q.v_samp == 2));
-        if (!samp_ok) return fail(ctx, MDHIP_EUNSUPPORTED, "jpeg image %d: luma sampling %dx%d", i, q.h_samp, q.v_samp);
-        if (q.rotation != 0 && q.rotation != 90 && q.rotation != 180 && q.rotation != 270)
-            return fail(ctx, MDHIP_EINVAL, "jpeg image %d: rotation %d", i, q.rotation);
-        // the planes must cover what the kernels read: the luma plane the image, a chroma plane its downsampled size
-        long long coef_off = 0;
-        for (int c = 0; c < q.components; ++c) {
-            const int hs = c == 0 ? 1 : q.h_samp, vs = c == 0 ? 1 : q.v_samp;
-            const int need_w = ((q.width + hs - 1) / hs + 7) / 8, need_h = ((q.height + vs - 1) / vs + 7) / 8;
-            if (q.blocks_w[c] < need_w || q.blocks_h[c] < need_h || q.blocks_w[c] > 16384 || q.blocks_h[c] > 16384)
-                return fail(ctx, MDHIP_EINVAL, "jpeg image %d: plane %d of %dx%d blocks for a %dx%d image", i, c, q.blocks_w[c],
-                            q.blocks_h[c], q.width, q.height);
-            d.blocks_w[c] = q.blocks_w[c];
-            d.blocks_h[c] = q.blocks_h[c];
-            d.coef_off[c] = coef_off;
-            d.plane_off[c] = (long long)planes_bytes;
-            coef_off += (long long)q.blocks_w[c] * q.blocks_h[c] * 64;
-            planes_bytes += (size_t)q.blocks_w[c] * q.blocks_h[c] * 64;
-        }
-        for (int c = q.components; c < 3; ++c) d.blocks_w[c] = d.blocks_h[c] = 0, d.coef_off[c] = d.plane_off[c] = 0;
-        planes_bytes = align_up(planes_bytes, 256);
-        if (!q.coef || !out_rgb[i] || ((uintptr_t)q.coef & 15))
-            return fail(ctx, MDHIP_EINVAL, "jpeg image %d: coef / out_rgb is NULL or coef is not 16-byte aligned", i);
-        for (const void* p : {(const void*)q.coef, (const void*)out_rgb[i]}) {
-            hipPointerAttribute_t attr;
-            const hipError_t e = hipPointerGetAttributes(&attr, p);
-            if (e != hipSuccess) (void)hipGetLastError();
-            if (e != hipSuccess || !(attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged))
-                return fail(ctx, MDHIP_EINVAL, "jpeg image %d: coef and out_rgb must be device memory", i);
-        }
-        d.coef = q.coef;
-        d.out = out_rgb[i];
-        d.width = q.width;
-        d.height = q.height;
-        d.components = q.components;
-        d.h_samp = q.h_samp;
-        d.v_samp = q.v_samp;
-        d.rotation = q.rotation;
-        memcpy(d.quant, q.quant, sizeof(d.quant));
-    }
-    if (planes_bytes > ctx->jpeg_planes_bytes) {
-        HIP_TRY(ctx, hipDeviceSynchronize());                  // an earlier call's kernels may still use the old planes
-        if (ctx->jpeg_planes) HIP_TRY(ctx, hipFree(ctx->jpeg_planes));
-        ctx->jpeg_planes = nullptr;
-        ctx->jpeg_planes_bytes = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->jpeg_planes, planes_bytes));
-        ctx->jpeg_planes_bytes = planes_bytes;
-    }
-    for (int i = 0; i < n; ++i) {
-        devs[i].planes = (uint8_t*)ctx->jpeg_planes;
-        HIP_TRY(ctx, launch_jpeg_reconstruct(devs[i], s));
-    }
-    return MDHIP_OK;
-}
-
-int mdhip_jpeg_entropy_decode(mdhip_ctx* ctx, const mdhip_jpeg_scan* scans, int n, int subseq_bits, int32_t* status, void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
-    if (!scans || !status) return fail(ctx, MDHIP_EINVAL, "scans/status is NULL");
-    if (n < 1) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
-    if (subseq_bits == 0) subseq_bits = 1024;
-    if (subseq_bits < MDJ_MIN_SUBSEQ_BITS || subseq_bits > MDJ_MAX_SUBSEQ_BITS || subseq_bits % 8)
-        return fail(ctx, MDHIP_EINVAL, "subseq_bits = %d (a multiple of 8 from %d to 65536)", subseq_bits, MDJ_MIN_SUBSEQ_BITS);
-    hipStream_t s = (hipStream_t)hip_stream;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int chunk = jpeg_entropy_dc_chunk();
-    // host image of the scratch: [JpegScanDev x n][status x n][counters][per image: MdjImage, seg_off, seg_lane0 | lane records, energy, dc]
-    std::vector<JpegScanDev> devs(n);
-    std::vector<MdjImage> ims(n);
-    std::vector<std::vector<uint32_t>> seg_off(n), seg_lane0(n);
-    struct Off { size_t im, seg_off, seg_lane0, lane_end, lane_start, lane_seg, lane_block, energy, dc_sum, dc_reset; };
-    std::vector<Off> offs(n);
-    size_t cur = align_up(sizeof(JpegScanDev) * n, 256);
-    const size_t status_off = cur;
-    cur = align_up(cur + 4 * (size_t)n, 256);
-    const size_t counters_off = cur;
-    cur = align_up(cur + 16, 256);
-    unsigned max_lanes = 1;
-    long long max_chunks = 1, total_lanes = 0;
-    for (int i = 0; i < n; ++i) {
-        const mdhip_jpeg_scan& q = scans[i];
-        if (!q.desc || !q.seg_offsets || !q.scan || !q.coef || ((uintptr_t)q.coef & 15))
-            return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: desc / seg_offsets / scan / coef is NULL or coef is not 16-byte aligned", i);
-        const mdjpeg_scan_info& sc = *q.desc;
-        const mdjpeg_info& in = sc.info;
-        const long long bytes = sc.scan_end - sc.scan_begin;
-        if (!in.supported || sc.scan_begin < 0 || bytes < 0 || bytes >= MDJ_MAX_SCAN_BYTES)
-            return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: scan range %lld .. %lld of a file that is %ssupported", i, (long long)sc.scan_begin,
-                        (long long)sc.scan_end, in.supported ? "" : "not ");
-        if (!mdj_fill_image(sc, subseq_bits, ims[i]))
-            return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: components, sampling or Huffman tables of the descriptor are not valid", i);
-        const MdjImage& im = ims[i];
-        // the geometry must be the one mdjpeg_parse derives: the kernels' bounds rest on it
-        long long count = 0;
-        bool ok = in.width >= 1 && in.height >= 1 && in.width <= 65535 && in.height <= 65535 && in.restart_interval >= 0 &&
-                  in.mcus_x == (in.width + 8 * in.h_samp[0] - 1) / (8 * in.h_samp[0]) &&
-                  in.mcus_y == (in.height + 8 * in.v_samp[0] - 1) / (8 * in.v_samp[0]);
-        for (int c = 0; ok && c < in.components; ++c) {
-            ok = in.blocks_w[c] == in.mcus_x * in.h_samp[c] && in.blocks_h[c] == in.mcus_y * in.v_samp[c] && in.plane_offset[c] == count;
-            count += (long long)in.blocks_w[c] * in.blocks_h[c] * 64;
-        }
-        if (!ok || count != in.coef_count)
-            return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: plane sizes and offsets contradict the image size and sampling", i);
-        const long long nseg = (im.total_mcus + im.interval - 1) / im.interval;
-        if (nseg != sc.n_segments) return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: %d segments for %lld MCUs at interval %lld", i, sc.n_segments,
-                                               (long long)im.total_mcus, (long long)im.interval);
-        seg_off[i].resize((size_t)nseg + 1);
-        seg_lane0[i].resize((size_t)nseg + 1);
-        long long lanes = 0;
-        for (long long k = 0; k <= nseg; ++k) {
-            const long long o = k < nseg ? (long long)q.seg_offsets[k] : bytes + 2;
-            const long long prev = k ? (long long)seg_off[i][(size_t)k - 1] + 2 : 0;
-            if (o < prev || o > bytes + 2) return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: segment offset %lld outside the scan or out of order", i, o);
-            if (k == 0 && o != 0) return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: the first segment does not begin the scan", i);
-            seg_off[i][(size_t)k] = (uint32_t)o;
-            if (k) lanes += mdj_lanes_of((uint32_t)(o - 2 - seg_off[i][(size_t)k - 1]), (uint32_t)subseq_bits);
-            seg_lane0[i][(size_t)k] = (uint32_t)lanes;
-        }
-        if (lanes > 0x7fffffffLL) return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: too many subsequences", i);
-        for (const void* p : {(const void*)q.scan, (const void*)q.coef}) {
-            hipPointerAttribute_t attr;
-            const hipError_t e = hipPointerGetAttributes(&attr, p);
-            if (e != hipSuccess) (void)hipGetLastError();
-            if (e != hipSuccess || !(attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged))
-                return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: scan and coef must be device memory", i);
-        }
-        JpegScanDev& d = devs[i];
-        d.scan = q.scan;
-        d.coef = q.coef;
-        d.coef_count = in.coef_count;
-        d.n_segments = (uint32_t)nseg;
-        d.n_lanes = (uint32_t)lanes;
-        long long chunks = 0;
-        for (int c = 0; c < 3; ++c) {
-            d.dc_blocks[c] = c < in.components ? (long long)in.blocks_w[c] * in.blocks_h[c] : 0;
-            d.dc_chunks[c] = (d.dc_blocks[c] + chunk - 1) / chunk;
-            chunks += d.dc_chunks[c];
-        }
-        max_lanes = std::max(max_lanes, d.n_lanes);
-        max_chunks = std::max(max_chunks, chunks);
-        total_lanes += lanes;
-        Off& o = offs[i];
-        o.im = cur;          cur = align_up(cur + sizeof(MdjImage), 256);
-        o.seg_off = cur;     cur = align_up(cur + 4 * ((size_t)nseg + 1), 256);
-        o.seg_lane0 = cur;   cur = align_up(cur + 4 * ((size_t)nseg + 1), 256);
-    }
-    const size_t upload_bytes = cur;
-    for (int i = 0; i < n; ++i) {
-        Off& o = offs[i];
-        const size_t lanes = devs[i].n_lanes, blocks = (size_t)(devs[i].coef_count / 64);
-        const size_t chunks = (size_t)(devs[i].dc_chunks[0] + devs[i].dc_chunks[1] + devs[i].dc_chunks[2]);
-        o.lane_end = cur;    cur = align_up(cur + 8 * lanes, 256);
-        o.lane_start = cur;  cur = align_up(cur + 8 * lanes, 256);
-        o.lane_seg = cur;    cur = align_up(cur + 4 * lanes, 256);
-        o.lane_block = cur;  cur = align_up(cur + 4 * lanes, 256);
-        o.energy = cur;      cur = align_up(cur + 4 * blocks, 256);
-        o.dc_sum = cur;      cur = align_up(cur + 8 * chunks, 256);
-        o.dc_reset = cur;    cur = align_up(cur + 4 * chunks, 256);
-    }
-    if (cur > ctx->jpeg_entropy_bytes) {
-        HIP_TRY(ctx, hipDeviceSynchronize());                  // an earlier call's kernels may still use the old scratch
-        if (ctx->jpeg_entropy) HIP_TRY(ctx, hipFree(ctx->jpeg_entropy));
-        ctx->jpeg_entropy = nullptr;
-        ctx->jpeg_entropy_bytes = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->jpeg_entropy, cur));
-        ctx->jpeg_entropy_bytes = cur;
-    }
-    char* base = ctx->jpeg_entropy;
-    std::vector<char> up(upload_bytes, 0);
-    for (int i = 0; i < n; ++i) {
-        const Off& o = offs[i];
-        JpegScanDev& d = devs[i];
-        d.im = (const MdjImage*)(base + o.im);
-        d.seg_off = (const uint32_t*)(base + o.seg_off);
-        d.seg_lane0 = (const uint32_t*)(base + o.seg_lane0);
-        d.lane_end = (uint64_t*)(base + o.lane_end);
-        d.lane_start = (uint64_t*)(base + o.lane_start);
-        d.lane_seg = (uint32_t*)(base + o.lane_seg);
-        d.lane_block = (uint32_t*)(base + o.lane_block);
-        d.energy = (uint32_t*)(base + o.energy);
-        d.dc_sum = (long long*)(base + o.dc_sum);
-        d.dc_reset = (uint32_t*)(base + o.dc_reset);
-        memcpy(up.data() + o.im, &ims[i], sizeof(MdjImage));
-        memcpy(up.data() + o.seg_off, seg_off[i].data(), 4 * seg_off[i].size());
-        memcpy(up.data() + o.seg_lane0, seg_lane0[i].data(), 4 * seg_lane0[i].size());
-    }
-    memcpy(up.data(), devs.data(), sizeof(JpegScanDev) * n);
-    // (the upload is from pageable memory: the copy has left `up` when the call returns; status and counters arrive zeroed)
-    HIP_TRY(ctx, hipMemcpyAsync(base, up.data(), upload_bytes, hipMemcpyHostToDevice, s));
-    const JpegScanDev* ddevs = (const JpegScanDev*)base;
-    uint32_t* dstatus = (uint32_t*)(base + status_off);
-    unsigned long long* dcounters = (unsigned long long*)(base + counters_off);
-    launch_jpeg_entropy_front(ddevs, n, max_lanes, s);
-    HIP_TRY(ctx, hipGetLastError());
-    // pass 2: until a launch moves no lane.  Every launch settles whole workgroups, so this is two launches unless a change
-    // has to cross workgroups; a chain of lanes that never meet is bounded by the number of lanes.
-    long long launches = 0;
-    unsigned long long counters[2] = {0, 0};
-    for (;;) {
-        launch_jpeg_entropy_sync(ddevs, n, max_lanes, dcounters, s);
-        HIP_TRY(ctx, hipGetLastError());
-        ++launches;
-        HIP_TRY(ctx, hipMemcpyAsync(counters, dcounters, sizeof(counters), hipMemcpyDeviceToHost, s));
-        HIP_TRY(ctx, hipMemsetAsync(dcounters + 1, 0, 8, s));
-        HIP_TRY(ctx, hipStreamSynchronize(s));
-        if (!counters[1]) break;
-        if (launches > (long long)max_lanes + 2) return fail(ctx, MDHIP_EHIP, "the subsequences did not synchronise in %lld launches", launches);
-    }
-    launch_jpeg_entropy_back(ddevs, n, max_lanes, max_chunks, dstatus, s);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(status, dstatus, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    ctx->jpeg_entropy_stats[0] = total_lanes;
-    ctx->jpeg_entropy_stats[1] = (long long)counters[0];
-    ctx->jpeg_entropy_stats[2] = launches;
-    ctx->jpeg_entropy_stats[3] = n;
-    return MDHIP_OK;
-}
-
-int mdhip_jpeg_entropy_stats(mdhip_ctx* ctx, int64_t out[4]) {
-    if (!ctx) return MDHIP_EINVAL;
-    if (!out) return fail(ctx, MDHIP_EINVAL, "out is NULL");
-    for (int i = 0; i < 4; ++i) out[i] = ctx->jpeg_entropy_stats[i];
-    return MDHIP_OK;
-}
-
-int mdhip_jpeg_recompress(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
-                          const int64_t* pitches, int n, const uint16_t quant_luma[64], const uint16_t quant_chroma[64],
-                          uint8_t* const* out_rgb, void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
-    if (!windows || !widths || !heights || !pitches || !quant_luma || !quant_chroma || !out_rgb)
-        return fail(ctx, MDHIP_EINVAL, "windows/widths/heights/pitches/quant_luma/quant_chroma/out_rgb is NULL");
-    if (n < 1) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
-    for (int k = 0; k < 64; ++k)
-        if (quant_luma[k] < 1 || quant_luma[k] > 255 || quant_chroma[k] < 1 || quant_chroma[k] > 255)
-            return fail(ctx, MDHIP_EINVAL, "quantisation table entry %d outside 1 .. 255 (baseline JPEG)", k);
-    hipStream_t s = (hipStream_t)hip_stream;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::vector<JpegDev> devs(n);
-    size_t planes_bytes = 0;
-    for (int i = 0; i < n; ++i) {
-        JpegDev& d = devs[i];
-        const int w = widths[i], h = heights[i];
-        if (w < 1 || h < 1 || w > 65535 || h > 65535) return fail(ctx, MDHIP_EINVAL, "window %d: %dx%d", i, w, h);
-        if (pitches[i] < (long long)w * 3 || (long long)(h - 1) * pitches[i] + (long long)w * 3 > 0x7fff0000LL)
-            return fail(ctx, MDHIP_EINVAL, "window %d: pitch %lld for %d pixels per row (or a window above 2 GB)", i, (long long)pitches[i], w);
-        if (!windows[i] || !out_rgb[i]) return fail(ctx, MDHIP_EINVAL, "window %d: windows / out_rgb is NULL", i);
-        for (const void* p : {(const void*)windows[i], (const void*)out_rgb[i]}) {
-            hipPointerAttribute_t attr;
-            const hipError_t e = hipPointerGetAttributes(&attr, p);
-            if (e != hipSuccess) (void)hipGetLastError();
-            if (e != hipSuccess || !(attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged))
-                return fail(ctx, MDHIP_EINVAL, "window %d: host pointer -- windows and out_rgb must be device memory", i);
-        }
-        d.coef = nullptr;
-        d.out = out_rgb[i];
-        d.width = w;
-        d.height = h;
-        d.components = 3;
-        d.h_samp = d.v_samp = 2;
-        d.rotation = 0;
-        for (int c = 0; c < 3; ++c) {                                   // each component's own whole blocks (4:2:0)
-            const int cw = c == 0 ? w : (w + 1) / 2, ch = c == 0 ? h : (h + 1) / 2;
-            d.blocks_w[c] = (cw + 7) / 8;
-            d.blocks_h[c] = (ch + 7) / 8;
-            d.coef_off[c] = 0;
-            d.plane_off[c] = (long long)planes_bytes;
-            planes_bytes += (size_t)d.blocks_w[c] * d.blocks_h[c] * 64;
-            memcpy(d.quant[c], c == 0 ? quant_luma : quant_chroma, sizeof(d.quant[c]));
-        }
-        planes_bytes = align_up(planes_bytes, 256);
-    }
-    if (planes_bytes > ctx->jpeg_planes_bytes) {
-        HIP_TRY(ctx, hipDeviceSynchronize());                  // an earlier call's kernels may still use the old planes
-        if (ctx->jpeg_planes) HIP_TRY(ctx, hipFree(ctx->jpeg_planes));
-        ctx->jpeg_planes = nullptr;
-        ctx->jpeg_planes_bytes = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->jpeg_planes, planes_bytes));
-        ctx->jpeg_planes_bytes = planes_bytes;
-    }
-    for (int i = 0; i < n; ++i) {
-        devs[i].planes = (uint8_t*)ctx->jpeg_planes;
-        HIP_TRY(ctx, launch_jpeg_recompress(devs[i], windows[i], pitches[i], s));
-    }
-    return MDHIP_OK;
-}
-
-long long mdhip_jpeg_encode_bound(int width, int height) {
-    if (width < 1 || height < 1 || width > 65535 || height > 65535) return -1;
-    return mdj_enc_bound_bytes(width, height);
-}
-
-int mdhip_jpeg_encode(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
-                      const int64_t* pitches, int n, const uint16_t quant_luma[64], const uint16_t quant_chroma[64], uint8_t* out,
-                      int64_t capacity, int64_t* offsets, int64_t* sizes, int64_t* needed, void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
-    if (!windows || !widths || !heights || !pitches || !quant_luma || !quant_chroma || !offsets || !sizes || !needed)
-        return fail(ctx, MDHIP_EINVAL, "windows/widths/heights/pitches/quant_luma/quant_chroma/offsets/sizes/needed is NULL");
-    if (n < 1) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
-    if (capacity < 0 || (capacity > 0 && !out)) return fail(ctx, MDHIP_EINVAL, "capacity %lld with out %p", (long long)capacity, (void*)out);
-    for (int k = 0; k < 64; ++k)
-        if (quant_luma[k] < 1 || quant_luma[k] > 255 || quant_chroma[k] < 1 || quant_chroma[k] > 255)
-            return fail(ctx, MDHIP_EINVAL, "quantisation table entry %d outside 1 .. 255 (baseline JPEG)", k);
-    hipStream_t s = (hipStream_t)hip_stream;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto is_device = [](const void* p) {
-        hipPointerAttribute_t attr;
-        const hipError_t e = hipPointerGetAttributes(&attr, p);
-        if (e != hipSuccess) (void)hipGetLastError();
-        return e == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged);
-    };
-    if (capacity > 0 && !is_device(out)) return fail(ctx, MDHIP_EINVAL, "host pointer -- out must be device memory");
-    const int chunk_bytes = 64;
-    std::vector<MdjEncCrop> crops((size_t)n + 1);
-    long long blocks = 0, words = 0, chunks = 0;
-    for (int i = 0; i <= n; ++i) {
-        MdjEncCrop& c = crops[i];
-        memset(&c, 0, sizeof(c));
-        c.block0 = blocks;
-        c.word0 = words;
-        c.chunk0 = chunks;
-        if (i == n) break;
-        const int w = widths[i], h = heights[i];
-        if (w < 1 || h < 1 || w > 65535 || h > 65535) return fail(ctx, MDHIP_EINVAL, "window %d: %dx%d", i, w, h);
-        if (pitches[i] < (long long)w * 3 || (long long)(h - 1) * pitches[i] + (long long)w * 3 > 0x7fff0000LL)
-            return fail(ctx, MDHIP_EINVAL, "window %d: pitch %lld for %d pixels per row (or a window above 2 GB)", i, (long long)pitches[i], w);
-        if (!windows[i] || !is_device(windows[i])) return fail(ctx, MDHIP_EINVAL, "window %d: NULL or a host pointer -- windows must be device memory", i);
-        const long long nb = mdj_enc_blocks(w, h);
-        if (nb > MDJ_ENC_MAX_BLOCKS) return fail(ctx, MDHIP_EINVAL, "window %d: %dx%d is more than %lld blocks", i, w, h, (long long)MDJ_ENC_MAX_BLOCKS);
-        c.src = windows[i];
-        c.pitch = pitches[i];
-        c.width = w;
-        c.height = h;
-        c.mcus_x = (w + 15) / 16;
-        c.mcus_y = (h + 15) / 16;
-        blocks += nb;
-        words += mdj_enc_region_words(nb);
-        chunks += mdj_enc_region_chunks(nb, chunk_bytes);
-    }
-    // the scratch: [crops][tables][quant] uploaded; [status][bit buffer] zeroed; the rest written before it is read
-    size_t cur = 0;
-    auto take = [&cur](size_t bytes) { const size_t o = cur; cur = align_up(cur + bytes, 256); return o; };
-    const size_t o_crops = take(sizeof(MdjEncCrop) * ((size_t)n + 1));
-    const size_t o_tables = take(sizeof(MdjEncTables));
-    const size_t o_quant = take(256);
-    const size_t upload_bytes = cur;
-    const size_t o_status = take(4 * (size_t)n);
-    const size_t o_bitbuf = take(4 * (size_t)words);
-    const size_t zero_bytes = cur - o_status;
-    const size_t o_coef = take(128 * (size_t)blocks);
-    const size_t o_len = take(4 * (size_t)blocks);
-    const size_t o_off = take(8 * ((size_t)blocks + 1));
-    const size_t o_partial = take(8 * (size_t)std::max(jpeg_encode_scan_tiles(blocks), jpeg_encode_scan_tiles(chunks)));
-    const size_t o_count = take(4 * (size_t)chunks);
-    const size_t o_start = take(8 * ((size_t)chunks + 1));
-    const size_t o_result = take(8 * (2 * (size_t)n + 1));
-    if (cur > ctx->jpeg_encode_bytes) {
-        HIP_TRY(ctx, hipDeviceSynchronize());                  // an earlier call's kernels may still use the old scratch
-        if (ctx->jpeg_encode) HIP_TRY(ctx, hipFree(ctx->jpeg_encode));
-        ctx->jpeg_encode = nullptr;
-        ctx->jpeg_encode_bytes = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->jpeg_encode, cur));
-        ctx->jpeg_encode_bytes = cur;
-    }
-    char* base = ctx->jpeg_encode;
-    std::vector<char> up(upload_bytes, 0);
-    memcpy(up.data() + o_crops, crops.data(), sizeof(MdjEncCrop) * ((size_t)n + 1));
-    MdjEncTables tables;
-    mdj_enc_build_tables(tables);
-    memcpy(up.data() + o_tables, &tables, sizeof(tables));
-    memcpy(up.data() + o_quant, quant_luma, 128);
-    memcpy(up.data() + o_quant + 128, quant_chroma, 128);
-    // (the upload is from pageable memory: the copy has left `up` when the call returns)
-    HIP_TRY(ctx, hipMemcpyAsync(base, up.data(), upload_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemsetAsync(base + o_status, 0, zero_bytes, s));
-    JpegEncDev d;
-    d.crops = (const MdjEncCrop*)(base + o_crops);
-    d.tables = (const MdjEncTables*)(base + o_tables);
-    d.quant = (const uint16_t*)(base + o_quant);
-    d.coef = (int16_t*)(base + o_coef);
-    d.len = (uint32_t*)(base + o_len);
-    d.off = (uint64_t*)(base + o_off);
-    d.partial = (uint64_t*)(base + o_partial);
-    d.bitbuf = (uint32_t*)(base + o_bitbuf);
-    d.count = (uint32_t*)(base + o_count);
-    d.start = (uint64_t*)(base + o_start);
-    d.status = (uint32_t*)(base + o_status);
-    d.result = (long long*)(base + o_result);
-    d.out = out;
-    d.capacity = capacity;
-    d.blocks = blocks;
-    d.chunks = chunks;
-    d.n = n;
-    d.chunk_bytes = chunk_bytes;
-    HIP_TRY(ctx, launch_jpeg_encode(d, s));
-    std::vector<long long> result(2 * (size_t)n + 1);
-    std::vector<uint32_t> status((size_t)n);
-    HIP_TRY(ctx, hipMemcpyAsync(result.data(), d.result, 8 * result.size(), hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipMemcpyAsync(status.data(), d.status, 4 * status.size(), hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    for (int i = 0; i < n; ++i) {
-        offsets[i] = result[i];
-        sizes[i] = result[(size_t)n + i];
-    }
-    *needed = result[2 * (size_t)n];
-    for (int i = 0; i < n; ++i)
-        if (status[i]) return fail(ctx, MDHIP_EINVAL, "window %d: a coefficient no baseline JPEG can hold (status %u)", i, status[i]);
-    if (*needed > capacity)
-        return fail(ctx, MDHIP_ECAPACITY, "the scans take %lld bytes, the output buffer has %lld", (long long)*needed, (long long)capacity);
-    return MDHIP_OK;
-}
-
-int mdhip_blur_regions(mdhip_ctx* ctx, uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
-                       int n_images, const int32_t* rect_image, const int32_t* rects, int n_rects, float radius, void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
-    if (n_rects == 0) return MDHIP_OK;
-    if (!images || !widths || !heights || !pitches || !rect_image || !rects)
-        return fail(ctx, MDHIP_EINVAL, "images/widths/heights/pitches/rect_image/rects is NULL");
-    if (n_images < 1 || n_images > 65535 || n_rects < 0) return fail(ctx, MDHIP_EINVAL, "n_images = %d, n_rects = %d", n_images, n_rects);
-    if (!(radius >= 0.0f) || radius > MD_BLUR_MAX_RADIUS) return fail(ctx, MDHIP_EINVAL, "radius %g outside 0 .. %g", (double)radius, (double)MD_BLUR_MAX_RADIUS);
-    hipStream_t s = (hipStream_t)hip_stream;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const MdBlurWeights wt = md_blur_weights(radius);
-    // every rectangle is checked before anything is launched; round k holds the k-th rectangle with area of every image
-    std::vector<int> seen((size_t)n_images, -1), count((size_t)n_images, 0);
-    std::vector<std::vector<BlurRect>> rounds;
-    for (int i = 0; i < n_rects; ++i) {
-        const int m = rect_image[i];
-        if (m < 0 || m >= n_images) return fail(ctx, MDHIP_EINVAL, "rectangle %d: image %d of %d", i, m, n_images);
-        const int32_t* q = rects + 4 * (size_t)i;
-        if (q[2] <= q[0] || q[3] <= q[1]) continue;                     // without area: Pillow pastes nothing
-        if (seen[m] < 0) {
-            const int W = widths[m], H = heights[m];
-            if (W < 1 || H < 1 || W > 65535 || H > 65535) return fail(ctx, MDHIP_EINVAL, "image %d: %dx%d", m, W, H);
-            if (pitches[m] < (long long)W * 3 || (long long)(H - 1) * pitches[m] + (long long)W * 3 > 0x7fff0000LL)
-                return fail(ctx, MDHIP_EINVAL, "image %d: pitch %lld for %d pixels per row (or an image above 2 GB)", m, (long long)pitches[m], W);
-            hipPointerAttribute_t attr;
-            const hipError_t e = images[m] ? hipPointerGetAttributes(&attr, images[m]) : hipErrorInvalidValue;
-            if (e != hipSuccess) (void)hipGetLastError();
-            if (e != hipSuccess || !(attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged))
-                return fail(ctx, MDHIP_EINVAL, "image %d: NULL or a host pointer -- images must be device memory", m);
-            seen[m] = 1;
-        }
-        if (q[0] < 0 || q[1] < 0 || q[2] > widths[m] || q[3] > heights[m])
-            return fail(ctx, MDHIP_EINVAL, "rectangle %d: (%d, %d, %d, %d) leaves its %dx%d image", i, q[0], q[1], q[2], q[3], widths[m], heights[m]);
-        BlurRect d;
-        memset(&d, 0, sizeof(d));
-        d.img = images[m] + (long long)q[1] * pitches[m] + (long long)q[0] * 3;
-        d.pitch = pitches[m];
-        d.w = q[2] - q[0];
-        d.h = q[3] - q[1];
-        d.sp = (int)align_up((size_t)d.w * 3, 64);
-        MdBlurXPlan plan;
-        if (!md_blur_plan_x(d.w, wt.r, BLUR_LDS_BYTES, &plan) || (long long)plan.rows * plan.stride * 2 > BLUR_LDS_BYTES)
-            return fail(ctx, MDHIP_EUNSUPPORTED, "rectangle %d: no row plan for %d pixels at box radius %d", i, d.w, wt.r);
-        d.rows = plan.rows, d.stride = plan.stride, d.chunks = plan.chunks, d.step = plan.step, d.halo = plan.halo;
-        d.row_groups = (d.h + d.rows - 1) / d.rows;
-        const size_t k = (size_t)count[m]++;
-        if (rounds.size() <= k) rounds.resize(k + 1);
-        rounds[k].push_back(d);
-    }
-    if (rounds.empty()) return MDHIP_OK;
-    // the scratch: [records of all rounds][planes of one round]; the rounds run one after the other and share the planes
-    size_t n_records = 0, plane_bytes = 0;
-    for (auto& round : rounds) {
-        size_t cur = 0;
-        for (BlurRect& d : round) {
-            const size_t one = align_up((size_t)d.sp * (size_t)d.h, 256);
-            d.s0 = (long long)cur;
-            d.s1 = (long long)(cur + one);
-            cur += 2 * one;
-        }
-        plane_bytes = std::max(plane_bytes, cur);
-        n_records += round.size();
-    }
-    const size_t o_planes = align_up(sizeof(BlurRect) * n_records, 256);
-    const size_t total = o_planes + plane_bytes;
-    if (total > ctx->blur_bytes) {
-        HIP_TRY(ctx, hipDeviceSynchronize());                  // an earlier call's kernels may still use the old scratch
-        if (ctx->blur) HIP_TRY(ctx, hipFree(ctx->blur));
-        ctx->blur = nullptr;
-        ctx->blur_bytes = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->blur, total));
-        ctx->blur_bytes = total;
-    }
-    std::vector<BlurRect> up;
-    up.reserve(n_records);
-    for (auto& round : rounds) up.insert(up.end(), round.begin(), round.end());
-    // (the upload is from pageable memory: the copy has left `up` when the call returns)
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->blur, up.data(), sizeof(BlurRect) * n_records, hipMemcpyHostToDevice, s));
-    size_t first = 0;
-    for (auto& round : rounds) {
-        int max_blocks = 1, max_width = 1;
-        for (const BlurRect& d : round) {
-            max_blocks = std::max(max_blocks, d.row_groups * d.chunks);
-            max_width = std::max(max_width, d.w);
-        }
-        HIP_TRY(ctx, launch_blur_round((const BlurRect*)ctx->blur + first, (int)round.size(), max_blocks, max_width,
-                                       (uint8_t*)ctx->blur + o_planes, wt.r, wt.ww, wt.fw, s));
-        first += round.size();
-    }
-    return MDHIP_OK;
 }
 
 int mdhip_forward(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
@@ -3071,143 +2254,6 @@ int mdhip_read_layer(mdhip_ctx* ctx, int layer, int n, float* out, int* c, int* 
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(tmp);
     HIP_TRY(ctx, e);
-    return MDHIP_OK;
-}
-
-// ---- the YOLO11 kernels in isolation (tests) ----
-// host buffers in / out; scratch device memory is allocated per call (not for the product path)
-namespace {
-struct DevBufs {
-    std::vector<void*> p;
-    ~DevBufs() { for (void* q : p) (void)hipFree(q); }
-    hipError_t get(size_t bytes, void** out) { *out = nullptr; hipError_t e = hipMalloc(out, std::max<size_t>(bytes, 16)); if (e == hipSuccess) p.push_back(*out); return e; }
-};
-}  // namespace
-
-int mdhip_dwconv3x3_on(mdhip_ctx* ctx, const uint16_t* in, int ld_in, const float* weight, const float* bias, const uint16_t* res,
-                       uint16_t* out, int n, int h, int w, int c, int grp, int grp_stride, int grp_off, int act, void* hip_stream) {
-    if (!ctx || !in || !weight || !bias || !out || n < 1 || h < 1 || w < 1 || c < 8 || c % 8 || grp < 8 || ld_in < 8)
-        return MDHIP_EINVAL;
-    if ((c / grp - 1) * grp_stride + grp_off + grp > ld_in || c % grp) return fail(ctx, MDHIP_EINVAL, "channel mapping outside ld_in");
-    hipStream_t s = (hipStream_t)hip_stream;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int f16 = ctx->dtype == MDHIP_DTYPE_FP16;
-    std::vector<uint16_t> wp((size_t)9 * c);
-    for (int o = 0; o < c; ++o)
-        for (int t = 0; t < 9; ++t) wp[(size_t)t * c + o] = f32_to_st(weight[(size_t)o * 9 + t], f16);
-    const size_t px = (size_t)n * h * w;
-    DevBufs d;
-    void *din, *dw, *db, *dout, *dres = nullptr;
-    HIP_TRY(ctx, d.get(px * ld_in * 2, &din));
-    HIP_TRY(ctx, d.get(wp.size() * 2, &dw));
-    HIP_TRY(ctx, d.get((size_t)c * 4, &db));
-    HIP_TRY(ctx, d.get(px * c * 2, &dout));
-    HIP_TRY(ctx, hipMemcpy(din, in, px * ld_in * 2, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(dw, wp.data(), wp.size() * 2, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(db, bias, (size_t)c * 4, hipMemcpyHostToDevice));
-    if (res) {
-        HIP_TRY(ctx, d.get(px * c * 2, &dres));
-        HIP_TRY(ctx, hipMemcpy(dres, res, px * c * 2, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(ctx, launch_dwconv3x3((const uint16_t*)din, ld_in, (const uint16_t*)dw, (const float*)db, (uint16_t*)dout, c,
-                                  (const uint16_t*)dres, c, n, h, w, c, grp, grp_stride, grp_off, act, f16, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    HIP_TRY(ctx, hipMemcpy(out, dout, px * c * 2, hipMemcpyDeviceToHost));
-    return MDHIP_OK;
-}
-
-int mdhip_attention_on(mdhip_ctx* ctx, const uint16_t* qkv, uint16_t* out, int n, int n_tokens, int heads, void* hip_stream) {
-    if (!ctx || !qkv || !out || n < 1 || n_tokens < 1 || heads < 1) return MDHIP_EINVAL;
-    hipStream_t s = (hipStream_t)hip_stream;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t px = (size_t)n * n_tokens;
-    DevBufs d;
-    void *din, *dout;
-    HIP_TRY(ctx, d.get(px * heads * 128 * 2, &din));
-    HIP_TRY(ctx, d.get(px * heads * 64 * 2, &dout));
-    HIP_TRY(ctx, hipMemcpy(din, qkv, px * heads * 128 * 2, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, launch_attention((const uint16_t*)din, heads * 128, (uint16_t*)dout, heads * 64, n, n_tokens, heads,
-                                  ctx->dtype == MDHIP_DTYPE_FP16, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    HIP_TRY(ctx, hipMemcpy(out, dout, px * heads * 64 * 2, hipMemcpyDeviceToHost));
-    return MDHIP_OK;
-}
-
-int mdhip_dfl_decode_on(mdhip_ctx* ctx, const float* box, const float* cls, int nc, int n, int ny, int nx, float stride, float* pred,
-                        void* hip_stream) {
-    if (!ctx || !box || !cls || !pred || nc < 1 || n < 1 || ny < 1 || nx < 1) return MDHIP_EINVAL;
-    hipStream_t s = (hipStream_t)hip_stream;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t px = (size_t)n * ny * nx;
-    DevBufs d;
-    void *db, *dc, *dp;
-    HIP_TRY(ctx, d.get(px * 64 * 4, &db));
-    HIP_TRY(ctx, d.get(px * nc * 4, &dc));
-    HIP_TRY(ctx, d.get(px * (4 + nc) * 4, &dp));
-    HIP_TRY(ctx, hipMemcpy(db, box, px * 64 * 4, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(dc, cls, px * nc * 4, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, launch_dfl_decode((const float*)db, 64, (const float*)dc, nc, (float*)dp, n, ny, nx, nc, ny * nx, 0, stride, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    HIP_TRY(ctx, hipMemcpy(pred, dp, px * (4 + nc) * 4, hipMemcpyDeviceToHost));
-    return MDHIP_OK;
-}
-
-int mdhip_adown_pool_on(mdhip_ctx* ctx, const uint16_t* in, uint16_t* a, uint16_t* b, int n, int h, int w, int c_in,
-                        void* hip_stream) {
-    if (!ctx || !in || !a || !b || n < 1 || h < 2 || w < 2 || h % 2 || w % 2 || c_in < 16 || c_in % 16) return MDHIP_EINVAL;
-    hipStream_t s = (hipStream_t)hip_stream;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t px = (size_t)n * h * w, half = (size_t)c_in / 2;
-    DevBufs d;
-    void *din, *da, *db;
-    HIP_TRY(ctx, d.get(px * c_in * 2, &din));
-    HIP_TRY(ctx, d.get(px * half * 2, &da));
-    HIP_TRY(ctx, d.get(px / 4 * half * 2, &db));
-    HIP_TRY(ctx, hipMemcpy(din, in, px * c_in * 2, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, launch_adown_pool((const uint16_t*)din, c_in, (uint16_t*)da, (int)half, (uint16_t*)db, (int)half, n, h, w, c_in,
-                                   ctx->dtype == MDHIP_DTYPE_FP16, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    HIP_TRY(ctx, hipMemcpy(a, da, px * half * 2, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(b, db, px / 4 * half * 2, hipMemcpyDeviceToHost));
-    return MDHIP_OK;
-}
-
-int mdhip_cbfuse_on(mdhip_ctx* ctx, const uint16_t* const* src, const int32_t* factor, int n_src, const uint16_t* last,
-                    uint16_t* out, int n, int h, int w, int c, void* hip_stream) {
-    if (!ctx || !src || !factor || !last || !out || n_src < 1 || n_src > 3 || n < 1 || h < 1 || w < 1 || c < 8 || c % 8)
-        return MDHIP_EINVAL;
-    for (int k = 0; k < n_src; ++k)
-        if (!src[k] || factor[k] < 1 || h % factor[k] || w % factor[k]) return fail(ctx, MDHIP_EINVAL, "bad CBFuse source %d", k);
-    hipStream_t s = (hipStream_t)hip_stream;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t px = (size_t)n * h * w;
-    DevBufs d;
-    CbfuseArgs a{};
-    void *dl, *dout;
-    for (int k = 0; k < n_src; ++k) {
-        const size_t bytes = (size_t)n * (h / factor[k]) * (w / factor[k]) * c * 2;
-        void* p;
-        HIP_TRY(ctx, d.get(bytes, &p));
-        HIP_TRY(ctx, hipMemcpy(p, src[k], bytes, hipMemcpyHostToDevice));
-        a.src[k] = (const uint16_t*)p;
-        a.ld_src[k] = c;
-        a.factor[k] = factor[k];
-    }
-    HIP_TRY(ctx, d.get(px * c * 2, &dl));
-    HIP_TRY(ctx, d.get(px * c * 2, &dout));
-    HIP_TRY(ctx, hipMemcpy(dl, last, px * c * 2, hipMemcpyHostToDevice));
-    a.n_src = n_src;
-    a.last = (const uint16_t*)dl;
-    a.ld_last = c;
-    a.out = (uint16_t*)dout;
-    a.ld_out = c;
-    a.n = n;
-    a.H = h;
-    a.W = w;
-    a.C = c;
-    HIP_TRY(ctx, launch_cbfuse(a, ctx->dtype == MDHIP_DTYPE_FP16, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    HIP_TRY(ctx, hipMemcpy(out, dout, px * c * 2, hipMemcpyDeviceToHost));
     return MDHIP_OK;
 }
 

@@ -1,0 +1,595 @@
+// The image entry points of the C ABI (include/mdhip.h): letterbox (mdhip_preprocess*), JPEG (mdhip_jpeg_*), mdhip_blur_regions.
+// None of them looks at the model: they check their arguments, lay out scratch in one of the context's growable buffers
+// (mdhip_ctx.h DevBuffer) and launch.  What their checks have in common is written once, below; where two entry points
+// apply the same checks in a different order, each keeps its own order (the first failing check is what a caller sees).
+
+#include <algorithm>
+#include <climits>
+#include <cstring>
+#include <vector>
+
+#include "mdhip_ctx.h"
+#include "jpeg_subseq.h"
+#include "jpeg_encode.h"
+#include "blur_box.h"
+
+namespace {
+
+// device (or managed) memory?  (a pointer the runtime does not know is an error: cleared, or a later hipGetLastError reports it)
+bool is_device_ptr(const void* p) {
+    hipPointerAttribute_t attr;
+    const hipError_t e = hipPointerGetAttributes(&attr, p);
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged);
+}
+
+// A pitched RGB window of `noun` i ("window", "image"): sides of 1 .. max_side pixels, rows that do not overlap, and no more
+// bytes from its first pixel to the end of its last row (*extent) than the kernels' 32-bit offsets reach.
+int check_window(mdhip_ctx* ctx, const char* noun, int i, int w, int h, long long pitch, int max_side = 65535, long long* extent = nullptr) {
+    if (w < 1 || h < 1 || w > max_side || h > max_side) return fail(ctx, MDHIP_EINVAL, "%s %d: %dx%d", noun, i, w, h);
+    const long long need = (long long)(h - 1) * pitch + (long long)w * 3;
+    if (pitch < (long long)w * 3 || need > 0x7fff0000LL)
+        return fail(ctx, MDHIP_EINVAL, "%s %d: pitch %lld for %d pixels per row (or %s %s above 2 GB)", noun, i, pitch, w,
+                    strchr("aeiou", noun[0]) ? "an" : "a", noun);
+    if (extent) *extent = need;
+    return MDHIP_OK;
+}
+
+int check_quant_tables(mdhip_ctx* ctx, const uint16_t quant_luma[64], const uint16_t quant_chroma[64]) {
+    for (int k = 0; k < 64; ++k)
+        if (quant_luma[k] < 1 || quant_luma[k] > 255 || quant_chroma[k] < 1 || quant_chroma[k] > 255)
+            return fail(ctx, MDHIP_EINVAL, "quantisation table entry %d outside 1 .. 255 (baseline JPEG)", k);
+    return MDHIP_OK;
+}
+
+// The letterbox of `noun` i in two steps, because mdhip_preprocess_windows refuses a host pointer between them:
+// the source exists and the resized image lies inside the out_h x out_w network input ...
+int check_letterbox_fits(mdhip_ctx* ctx, const char* noun, int i, const uint8_t* src, const mdhip_letterbox& q, int out_h, int out_w) {
+    if (!src || q.src_h < 1 || q.src_w < 1 || q.resized_h < 1 || q.resized_w < 1 || q.top < 0 || q.left < 0 ||
+        q.top + q.resized_h > out_h || q.left + q.resized_w > out_w)
+        return fail(ctx, MDHIP_EINVAL, "%s %d: letterbox geometry does not fit %dx%d", noun, i, out_h, out_w);
+    return MDHIP_OK;
+}
+
+// ... and the interpolation is one the kernels have: the device record, with the two source steps per output pixel
+int build_letterbox(mdhip_ctx* ctx, const char* noun, int i, const uint8_t* src, const mdhip_letterbox& q, LetterboxDev* d) {
+    if (q.interp != 0 && q.interp != 1) return fail(ctx, MDHIP_EINVAL, "%s %d: interp %d (0 = linear, 1 = area)", noun, i, q.interp);
+    if (q.interp == 1 && (q.resized_h > q.src_h || q.resized_w > q.src_w))
+        return fail(ctx, MDHIP_EINVAL, "%s %d: INTER_AREA is implemented for shrinking only", noun, i);
+    *d = LetterboxDev{src, q.src_h, q.src_w, q.resized_h, q.resized_w, q.top, q.left, q.interp,
+                      1.0 / ((double)q.resized_w / (double)q.src_w), 1.0 / ((double)q.resized_h / (double)q.src_h)};
+    return MDHIP_OK;
+}
+
+// a scratch layout: parts taken one after the other, each starting on a multiple of 256 bytes
+struct ScratchLayout {
+    size_t size = 0;
+    size_t take(size_t bytes) { const size_t off = size; size = align_up(size + bytes, 256); return off; }
+};
+
+// the common end of mdhip_preprocess / mdhip_preprocess_windows: G = LetterboxDev (dense images) or LetterboxWin (windows)
+template <class G>
+int enqueue_letterbox(mdhip_ctx* ctx, const std::vector<G>& g, int n, int out_h, int out_w, hipStream_t s) {
+    // the forward that still reads the input tensor (its stem) comes first, whatever stream it runs on
+    if (ctx->input_free_valid) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->input_free, 0));
+    if (!letterbox_geometry_travels_inline(g.data(), n, out_w, ctx->letterbox_general)) {
+        // geometry goes through a 4-deep pinned ring so that the call never blocks on the stream
+        const int slot = ctx->geom_slot;
+        ctx->geom_slot = (slot + 1) & 3;
+        HIP_TRY(ctx, hipEventSynchronize(ctx->geom_ev[slot]));          // slot's previous copy has completed
+        uint8_t* gh = ctx->geom_host + (size_t)slot * ctx->max_batch * sizeof(LetterboxWin);
+        memcpy(gh, g.data(), n * sizeof(G));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->arena + ctx->geom_off, gh, n * sizeof(G), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipEventRecord(ctx->geom_ev[slot], s));
+    }
+    HIP_TRY(ctx, launch_letterbox_s2d((const G*)(ctx->arena + ctx->geom_off), g.data(), n, out_h, out_w,
+                                      (uint16_t*)(ctx->arena + ctx->input.off), ctx->dtype == MDHIP_DTYPE_FP16, ctx->letterbox_general, s));
+    ctx->last_n = n;
+    ctx->last_h = out_h;
+    ctx->last_w = out_w;
+    return MDHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mdhip_preprocess(mdhip_ctx* ctx, const uint8_t* const* images, const mdhip_letterbox* geom,
+                     int n, int out_h, int out_w, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!images || !geom) return fail(ctx, MDHIP_EINVAL, "images/geom is NULL");
+    if (int rc = check_shape(ctx, n, out_h, out_w)) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<LetterboxDev> g(n);
+    std::vector<long long> stage_off(n, -1);                    // of an image in host memory: where its copy is staged
+    ScratchLayout stage;
+    for (int i = 0; i < n; ++i) {
+        const mdhip_letterbox& q = geom[i];
+        if (int rc = check_letterbox_fits(ctx, "image", i, images[i], q, out_h, out_w)) return rc;
+        if (!is_device_ptr(images[i])) stage_off[i] = (long long)stage.take((size_t)q.src_h * q.src_w * 3);
+        if (int rc = build_letterbox(ctx, "image", i, images[i], q, &g[i])) return rc;
+    }
+    if (int rc = ctx->stage.reserve(ctx, stage.size, &s)) return rc;
+    for (int i = 0; i < n; ++i) {
+        if (stage_off[i] < 0) continue;
+        g[i].src = (const uint8_t*)(ctx->stage.p + stage_off[i]);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->stage.p + stage_off[i], images[i], (size_t)g[i].src_h * g[i].src_w * 3, hipMemcpyHostToDevice, s));
+    }
+    return enqueue_letterbox(ctx, g, n, out_h, out_w, s);
+}
+
+int mdhip_preprocess_windows(mdhip_ctx* ctx, const uint8_t* const* windows, const mdhip_letterbox* geom,
+                             const int64_t* pitches, const int64_t* readable, int n, int out_h, int out_w, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!windows || !geom || !pitches || !readable) return fail(ctx, MDHIP_EINVAL, "windows/geom/pitches/readable is NULL");
+    if (int rc = check_shape(ctx, n, out_h, out_w)) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<LetterboxWin> g(n);
+    for (int i = 0; i < n; ++i) {
+        const mdhip_letterbox& q = geom[i];
+        if (int rc = check_letterbox_fits(ctx, "window", i, windows[i], q, out_h, out_w)) return rc;
+        if (!is_device_ptr(windows[i]))
+            return fail(ctx, MDHIP_EINVAL, "window %d: host pointer -- a window must point into a device image (upload the parent image "
+                        "once and pass pointers into it)", i);
+        if (int rc = build_letterbox(ctx, "window", i, windows[i], q, &g[i].d)) return rc;
+        // bytes from the window's first pixel to the end of its last row: all must be readable (no limit on a source's sides)
+        long long need = 0;
+        if (int rc = check_window(ctx, "window", i, q.src_w, q.src_h, pitches[i], INT_MAX, &need)) return rc;
+        if (readable[i] < need)
+            return fail(ctx, MDHIP_EINVAL, "window %d: %lld readable bytes, the window spans %lld", i, (long long)readable[i], need);
+        // (the kernels look at most 16 bytes behind what they use: a larger figure says nothing more, and this one fits 32 bits)
+        g[i].readable = std::min<long long>(readable[i], need + 64);
+        g[i].pitch = (int)pitches[i];
+        g[i].reserved = 0;
+    }
+    return enqueue_letterbox(ctx, g, n, out_h, out_w, s);
+}
+
+int mdhip_jpeg_reconstruct(mdhip_ctx* ctx, const mdhip_jpeg_image* images, int n, uint8_t* const* out_rgb, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!images || !out_rgb) return fail(ctx, MDHIP_EINVAL, "images/out_rgb is NULL");
+    if (n < 1) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<JpegDev> devs(n);
+    size_t planes_bytes = 0;
+    for (int i = 0; i < n; ++i) {
+        const mdhip_jpeg_image& q = images[i];
+        JpegDev& d = devs[i];
+        if (q.width < 1 || q.height < 1 || q.width > 65535 || q.height > 65535 || (q.components != 1 && q.components != 3))
+            return fail(ctx, MDHIP_EINVAL, "jpeg image %d: %dx%d with %d components", i, q.width, q.height, q.components);
+        const bool samp_ok = q.components == 1 ? (q.h_samp == 1 && q.v_samp == 1)
+                                               : ((q.h_samp == 1 && q.v_samp == 1) || (q.h_samp == 2 && q.v_samp == 1) ||
+                                                  (q.h_samp == 2 && q.v_samp == 2));
+        if (!samp_ok) return fail(ctx, MDHIP_EUNSUPPORTED, "jpeg image %d: luma sampling %dx%d", i, q.h_samp, q.v_samp);
+        if (q.rotation != 0 && q.rotation != 90 && q.rotation != 180 && q.rotation != 270)
+            return fail(ctx, MDHIP_EINVAL, "jpeg image %d: rotation %d", i, q.rotation);
+        // the planes must cover what the kernels read: the luma plane the image, a chroma plane its downsampled size
+        long long coef_off = 0;
+        for (int c = 0; c < q.components; ++c) {
+            const int hs = c == 0 ? 1 : q.h_samp, vs = c == 0 ? 1 : q.v_samp;
+            const int need_w = ((q.width + hs - 1) / hs + 7) / 8, need_h = ((q.height + vs - 1) / vs + 7) / 8;
+            if (q.blocks_w[c] < need_w || q.blocks_h[c] < need_h || q.blocks_w[c] > 16384 || q.blocks_h[c] > 16384)
+                return fail(ctx, MDHIP_EINVAL, "jpeg image %d: plane %d of %dx%d blocks for a %dx%d image", i, c, q.blocks_w[c],
+                            q.blocks_h[c], q.width, q.height);
+            d.blocks_w[c] = q.blocks_w[c];
+            d.blocks_h[c] = q.blocks_h[c];
+            d.coef_off[c] = coef_off;
+            d.plane_off[c] = (long long)planes_bytes;
+            coef_off += (long long)q.blocks_w[c] * q.blocks_h[c] * 64;
+            planes_bytes += (size_t)q.blocks_w[c] * q.blocks_h[c] * 64;
+        }
+        for (int c = q.components; c < 3; ++c) d.blocks_w[c] = d.blocks_h[c] = 0, d.coef_off[c] = d.plane_off[c] = 0;
+        planes_bytes = align_up(planes_bytes, 256);
+        if (!q.coef || !out_rgb[i] || ((uintptr_t)q.coef & 15))
+            return fail(ctx, MDHIP_EINVAL, "jpeg image %d: coef / out_rgb is NULL or coef is not 16-byte aligned", i);
+        if (!is_device_ptr(q.coef) || !is_device_ptr(out_rgb[i]))
+            return fail(ctx, MDHIP_EINVAL, "jpeg image %d: coef and out_rgb must be device memory", i);
+        d.coef = q.coef;
+        d.out = out_rgb[i];
+        d.width = q.width;
+        d.height = q.height;
+        d.components = q.components;
+        d.h_samp = q.h_samp;
+        d.v_samp = q.v_samp;
+        d.rotation = q.rotation;
+        memcpy(d.quant, q.quant, sizeof(d.quant));
+    }
+    if (int rc = ctx->jpeg_planes.reserve(ctx, planes_bytes)) return rc;
+    for (int i = 0; i < n; ++i) {
+        devs[i].planes = (uint8_t*)ctx->jpeg_planes.p;
+        HIP_TRY(ctx, launch_jpeg_reconstruct(devs[i], s));
+    }
+    return MDHIP_OK;
+}
+
+int mdhip_jpeg_entropy_decode(mdhip_ctx* ctx, const mdhip_jpeg_scan* scans, int n, int subseq_bits, int32_t* status, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!scans || !status) return fail(ctx, MDHIP_EINVAL, "scans/status is NULL");
+    if (n < 1) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
+    if (subseq_bits == 0) subseq_bits = 1024;
+    if (subseq_bits < MDJ_MIN_SUBSEQ_BITS || subseq_bits > MDJ_MAX_SUBSEQ_BITS || subseq_bits % 8)
+        return fail(ctx, MDHIP_EINVAL, "subseq_bits = %d (a multiple of 8 from %d to 65536)", subseq_bits, MDJ_MIN_SUBSEQ_BITS);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int chunk = jpeg_entropy_dc_chunk();
+    // host image of the scratch: [JpegScanDev x n][status x n][counters][per image: MdjImage, seg_off, seg_lane0 | lane records, energy, dc]
+    std::vector<JpegScanDev> devs(n);
+    std::vector<MdjImage> ims(n);
+    std::vector<std::vector<uint32_t>> seg_off(n), seg_lane0(n);
+    struct Off { size_t im, seg_off, seg_lane0, lane_end, lane_start, lane_seg, lane_block, energy, dc_sum, dc_reset; };
+    std::vector<Off> offs(n);
+    ScratchLayout lay;
+    lay.take(sizeof(JpegScanDev) * n);                          // (at offset 0)
+    const size_t status_off = lay.take(4 * (size_t)n);
+    const size_t counters_off = lay.take(16);
+    unsigned max_lanes = 1;
+    long long max_chunks = 1, total_lanes = 0;
+    for (int i = 0; i < n; ++i) {
+        const mdhip_jpeg_scan& q = scans[i];
+        if (!q.desc || !q.seg_offsets || !q.scan || !q.coef || ((uintptr_t)q.coef & 15))
+            return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: desc / seg_offsets / scan / coef is NULL or coef is not 16-byte aligned", i);
+        const mdjpeg_scan_info& sc = *q.desc;
+        const mdjpeg_info& in = sc.info;
+        const long long bytes = sc.scan_end - sc.scan_begin;
+        if (!in.supported || sc.scan_begin < 0 || bytes < 0 || bytes >= MDJ_MAX_SCAN_BYTES)
+            return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: scan range %lld .. %lld of a file that is %ssupported", i, (long long)sc.scan_begin,
+                        (long long)sc.scan_end, in.supported ? "" : "not ");
+        if (!mdj_fill_image(sc, subseq_bits, ims[i]))
+            return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: components, sampling or Huffman tables of the descriptor are not valid", i);
+        const MdjImage& im = ims[i];
+        // the geometry must be the one mdjpeg_parse derives: the kernels' bounds rest on it
+        long long count = 0;
+        bool ok = in.width >= 1 && in.height >= 1 && in.width <= 65535 && in.height <= 65535 && in.restart_interval >= 0 &&
+                  in.mcus_x == (in.width + 8 * in.h_samp[0] - 1) / (8 * in.h_samp[0]) &&
+                  in.mcus_y == (in.height + 8 * in.v_samp[0] - 1) / (8 * in.v_samp[0]);
+        for (int c = 0; ok && c < in.components; ++c) {
+            ok = in.blocks_w[c] == in.mcus_x * in.h_samp[c] && in.blocks_h[c] == in.mcus_y * in.v_samp[c] && in.plane_offset[c] == count;
+            count += (long long)in.blocks_w[c] * in.blocks_h[c] * 64;
+        }
+        if (!ok || count != in.coef_count)
+            return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: plane sizes and offsets contradict the image size and sampling", i);
+        const long long nseg = (im.total_mcus + im.interval - 1) / im.interval;
+        if (nseg != sc.n_segments) return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: %d segments for %lld MCUs at interval %lld", i, sc.n_segments,
+                                               (long long)im.total_mcus, (long long)im.interval);
+        seg_off[i].resize((size_t)nseg + 1);
+        seg_lane0[i].resize((size_t)nseg + 1);
+        long long lanes = 0;
+        for (long long k = 0; k <= nseg; ++k) {
+            const long long o = k < nseg ? (long long)q.seg_offsets[k] : bytes + 2;
+            const long long prev = k ? (long long)seg_off[i][(size_t)k - 1] + 2 : 0;
+            if (o < prev || o > bytes + 2) return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: segment offset %lld outside the scan or out of order", i, o);
+            if (k == 0 && o != 0) return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: the first segment does not begin the scan", i);
+            seg_off[i][(size_t)k] = (uint32_t)o;
+            if (k) lanes += mdj_lanes_of((uint32_t)(o - 2 - seg_off[i][(size_t)k - 1]), (uint32_t)subseq_bits);
+            seg_lane0[i][(size_t)k] = (uint32_t)lanes;
+        }
+        if (lanes > 0x7fffffffLL) return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: too many subsequences", i);
+        if (!is_device_ptr(q.scan) || !is_device_ptr(q.coef))
+            return fail(ctx, MDHIP_EINVAL, "jpeg scan %d: scan and coef must be device memory", i);
+        JpegScanDev& d = devs[i];
+        d.scan = q.scan;
+        d.coef = q.coef;
+        d.coef_count = in.coef_count;
+        d.n_segments = (uint32_t)nseg;
+        d.n_lanes = (uint32_t)lanes;
+        long long chunks = 0;
+        for (int c = 0; c < 3; ++c) {
+            d.dc_blocks[c] = c < in.components ? (long long)in.blocks_w[c] * in.blocks_h[c] : 0;
+            d.dc_chunks[c] = (d.dc_blocks[c] + chunk - 1) / chunk;
+            chunks += d.dc_chunks[c];
+        }
+        max_lanes = std::max(max_lanes, d.n_lanes);
+        max_chunks = std::max(max_chunks, chunks);
+        total_lanes += lanes;
+        Off& o = offs[i];
+        o.im = lay.take(sizeof(MdjImage));
+        o.seg_off = lay.take(4 * ((size_t)nseg + 1));
+        o.seg_lane0 = lay.take(4 * ((size_t)nseg + 1));
+    }
+    const size_t upload_bytes = lay.size;                       // what follows is written on the device before it is read
+    for (int i = 0; i < n; ++i) {
+        Off& o = offs[i];
+        const size_t lanes = devs[i].n_lanes, blocks = (size_t)(devs[i].coef_count / 64);
+        const size_t chunks = (size_t)(devs[i].dc_chunks[0] + devs[i].dc_chunks[1] + devs[i].dc_chunks[2]);
+        o.lane_end = lay.take(8 * lanes);
+        o.lane_start = lay.take(8 * lanes);
+        o.lane_seg = lay.take(4 * lanes);
+        o.lane_block = lay.take(4 * lanes);
+        o.energy = lay.take(4 * blocks);
+        o.dc_sum = lay.take(8 * chunks);
+        o.dc_reset = lay.take(4 * chunks);
+    }
+    if (int rc = ctx->jpeg_entropy.reserve(ctx, lay.size)) return rc;
+    char* base = ctx->jpeg_entropy.p;
+    std::vector<char> up(upload_bytes, 0);
+    for (int i = 0; i < n; ++i) {
+        const Off& o = offs[i];
+        JpegScanDev& d = devs[i];
+        d.im = (const MdjImage*)(base + o.im);
+        d.seg_off = (const uint32_t*)(base + o.seg_off);
+        d.seg_lane0 = (const uint32_t*)(base + o.seg_lane0);
+        d.lane_end = (uint64_t*)(base + o.lane_end);
+        d.lane_start = (uint64_t*)(base + o.lane_start);
+        d.lane_seg = (uint32_t*)(base + o.lane_seg);
+        d.lane_block = (uint32_t*)(base + o.lane_block);
+        d.energy = (uint32_t*)(base + o.energy);
+        d.dc_sum = (long long*)(base + o.dc_sum);
+        d.dc_reset = (uint32_t*)(base + o.dc_reset);
+        memcpy(up.data() + o.im, &ims[i], sizeof(MdjImage));
+        memcpy(up.data() + o.seg_off, seg_off[i].data(), 4 * seg_off[i].size());
+        memcpy(up.data() + o.seg_lane0, seg_lane0[i].data(), 4 * seg_lane0[i].size());
+    }
+    memcpy(up.data(), devs.data(), sizeof(JpegScanDev) * n);
+    // (the upload is from pageable memory: the copy has left `up` when the call returns; status and counters arrive zeroed)
+    HIP_TRY(ctx, hipMemcpyAsync(base, up.data(), upload_bytes, hipMemcpyHostToDevice, s));
+    const JpegScanDev* ddevs = (const JpegScanDev*)base;
+    uint32_t* dstatus = (uint32_t*)(base + status_off);
+    unsigned long long* dcounters = (unsigned long long*)(base + counters_off);
+    launch_jpeg_entropy_front(ddevs, n, max_lanes, s);
+    HIP_TRY(ctx, hipGetLastError());
+    // pass 2: until a launch moves no lane.  Every launch settles whole workgroups, so this is two launches unless a change
+    // has to cross workgroups; a chain of lanes that never meet is bounded by the number of lanes.
+    long long launches = 0;
+    unsigned long long counters[2] = {0, 0};
+    for (;;) {
+        launch_jpeg_entropy_sync(ddevs, n, max_lanes, dcounters, s);
+        HIP_TRY(ctx, hipGetLastError());
+        ++launches;
+        HIP_TRY(ctx, hipMemcpyAsync(counters, dcounters, sizeof(counters), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipMemsetAsync(dcounters + 1, 0, 8, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        if (!counters[1]) break;
+        if (launches > (long long)max_lanes + 2) return fail(ctx, MDHIP_EHIP, "the subsequences did not synchronise in %lld launches", launches);
+    }
+    launch_jpeg_entropy_back(ddevs, n, max_lanes, max_chunks, dstatus, s);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(status, dstatus, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    ctx->jpeg_entropy_stats[0] = total_lanes;
+    ctx->jpeg_entropy_stats[1] = (long long)counters[0];
+    ctx->jpeg_entropy_stats[2] = launches;
+    ctx->jpeg_entropy_stats[3] = n;
+    return MDHIP_OK;
+}
+
+int mdhip_jpeg_entropy_stats(mdhip_ctx* ctx, int64_t out[4]) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!out) return fail(ctx, MDHIP_EINVAL, "out is NULL");
+    for (int i = 0; i < 4; ++i) out[i] = ctx->jpeg_entropy_stats[i];
+    return MDHIP_OK;
+}
+
+int mdhip_jpeg_recompress(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
+                          const int64_t* pitches, int n, const uint16_t quant_luma[64], const uint16_t quant_chroma[64],
+                          uint8_t* const* out_rgb, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!windows || !widths || !heights || !pitches || !quant_luma || !quant_chroma || !out_rgb)
+        return fail(ctx, MDHIP_EINVAL, "windows/widths/heights/pitches/quant_luma/quant_chroma/out_rgb is NULL");
+    if (n < 1) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
+    if (int rc = check_quant_tables(ctx, quant_luma, quant_chroma)) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<JpegDev> devs(n);
+    size_t planes_bytes = 0;
+    for (int i = 0; i < n; ++i) {
+        JpegDev& d = devs[i];
+        const int w = widths[i], h = heights[i];
+        if (int rc = check_window(ctx, "window", i, w, h, pitches[i])) return rc;
+        if (!windows[i] || !out_rgb[i]) return fail(ctx, MDHIP_EINVAL, "window %d: windows / out_rgb is NULL", i);
+        if (!is_device_ptr(windows[i]) || !is_device_ptr(out_rgb[i]))
+            return fail(ctx, MDHIP_EINVAL, "window %d: host pointer -- windows and out_rgb must be device memory", i);
+        d.coef = nullptr;
+        d.out = out_rgb[i];
+        d.width = w;
+        d.height = h;
+        d.components = 3;
+        d.h_samp = d.v_samp = 2;
+        d.rotation = 0;
+        for (int c = 0; c < 3; ++c) {                                   // each component's own whole blocks (4:2:0)
+            const int cw = c == 0 ? w : (w + 1) / 2, ch = c == 0 ? h : (h + 1) / 2;
+            d.blocks_w[c] = (cw + 7) / 8;
+            d.blocks_h[c] = (ch + 7) / 8;
+            d.coef_off[c] = 0;
+            d.plane_off[c] = (long long)planes_bytes;
+            planes_bytes += (size_t)d.blocks_w[c] * d.blocks_h[c] * 64;
+            memcpy(d.quant[c], c == 0 ? quant_luma : quant_chroma, sizeof(d.quant[c]));
+        }
+        planes_bytes = align_up(planes_bytes, 256);
+    }
+    if (int rc = ctx->jpeg_planes.reserve(ctx, planes_bytes)) return rc;
+    for (int i = 0; i < n; ++i) {
+        devs[i].planes = (uint8_t*)ctx->jpeg_planes.p;
+        HIP_TRY(ctx, launch_jpeg_recompress(devs[i], windows[i], pitches[i], s));
+    }
+    return MDHIP_OK;
+}
+
+long long mdhip_jpeg_encode_bound(int width, int height) {
+    if (width < 1 || height < 1 || width > 65535 || height > 65535) return -1;
+    return mdj_enc_bound_bytes(width, height);
+}
+
+int mdhip_jpeg_encode(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
+                      const int64_t* pitches, int n, const uint16_t quant_luma[64], const uint16_t quant_chroma[64], uint8_t* out,
+                      int64_t capacity, int64_t* offsets, int64_t* sizes, int64_t* needed, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!windows || !widths || !heights || !pitches || !quant_luma || !quant_chroma || !offsets || !sizes || !needed)
+        return fail(ctx, MDHIP_EINVAL, "windows/widths/heights/pitches/quant_luma/quant_chroma/offsets/sizes/needed is NULL");
+    if (n < 1) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
+    if (capacity < 0 || (capacity > 0 && !out)) return fail(ctx, MDHIP_EINVAL, "capacity %lld with out %p", (long long)capacity, (void*)out);
+    if (int rc = check_quant_tables(ctx, quant_luma, quant_chroma)) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (capacity > 0 && !is_device_ptr(out)) return fail(ctx, MDHIP_EINVAL, "host pointer -- out must be device memory");
+    const int chunk_bytes = 64;
+    std::vector<MdjEncCrop> crops((size_t)n + 1);
+    long long blocks = 0, words = 0, chunks = 0;
+    for (int i = 0; i <= n; ++i) {
+        MdjEncCrop& c = crops[i];
+        memset(&c, 0, sizeof(c));
+        c.block0 = blocks;
+        c.word0 = words;
+        c.chunk0 = chunks;
+        if (i == n) break;
+        const int w = widths[i], h = heights[i];
+        if (int rc = check_window(ctx, "window", i, w, h, pitches[i])) return rc;
+        if (!windows[i] || !is_device_ptr(windows[i])) return fail(ctx, MDHIP_EINVAL, "window %d: NULL or a host pointer -- windows must be device memory", i);
+        const long long nb = mdj_enc_blocks(w, h);
+        if (nb > MDJ_ENC_MAX_BLOCKS) return fail(ctx, MDHIP_EINVAL, "window %d: %dx%d is more than %lld blocks", i, w, h, (long long)MDJ_ENC_MAX_BLOCKS);
+        c.src = windows[i];
+        c.pitch = pitches[i];
+        c.width = w;
+        c.height = h;
+        c.mcus_x = (w + 15) / 16;
+        c.mcus_y = (h + 15) / 16;
+        blocks += nb;
+        words += mdj_enc_region_words(nb);
+        chunks += mdj_enc_region_chunks(nb, chunk_bytes);
+    }
+    // the scratch: [crops][tables][quant] uploaded; [status][bit buffer] zeroed; the rest written before it is read
+    ScratchLayout lay;
+    const size_t o_crops = lay.take(sizeof(MdjEncCrop) * ((size_t)n + 1));
+    const size_t o_tables = lay.take(sizeof(MdjEncTables));
+    const size_t o_quant = lay.take(256);
+    const size_t upload_bytes = lay.size;
+    const size_t o_status = lay.take(4 * (size_t)n);
+    const size_t o_bitbuf = lay.take(4 * (size_t)words);
+    const size_t zero_bytes = lay.size - o_status;
+    const size_t o_coef = lay.take(128 * (size_t)blocks);
+    const size_t o_len = lay.take(4 * (size_t)blocks);
+    const size_t o_off = lay.take(8 * ((size_t)blocks + 1));
+    const size_t o_partial = lay.take(8 * (size_t)std::max(jpeg_encode_scan_tiles(blocks), jpeg_encode_scan_tiles(chunks)));
+    const size_t o_count = lay.take(4 * (size_t)chunks);
+    const size_t o_start = lay.take(8 * ((size_t)chunks + 1));
+    const size_t o_result = lay.take(8 * (2 * (size_t)n + 1));
+    if (int rc = ctx->jpeg_encode.reserve(ctx, lay.size)) return rc;
+    char* base = ctx->jpeg_encode.p;
+    std::vector<char> up(upload_bytes, 0);
+    memcpy(up.data() + o_crops, crops.data(), sizeof(MdjEncCrop) * ((size_t)n + 1));
+    MdjEncTables tables;
+    mdj_enc_build_tables(tables);
+    memcpy(up.data() + o_tables, &tables, sizeof(tables));
+    memcpy(up.data() + o_quant, quant_luma, 128);
+    memcpy(up.data() + o_quant + 128, quant_chroma, 128);
+    // (the upload is from pageable memory: the copy has left `up` when the call returns)
+    HIP_TRY(ctx, hipMemcpyAsync(base, up.data(), upload_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(base + o_status, 0, zero_bytes, s));
+    JpegEncDev d;
+    d.crops = (const MdjEncCrop*)(base + o_crops);
+    d.tables = (const MdjEncTables*)(base + o_tables);
+    d.quant = (const uint16_t*)(base + o_quant);
+    d.coef = (int16_t*)(base + o_coef);
+    d.len = (uint32_t*)(base + o_len);
+    d.off = (uint64_t*)(base + o_off);
+    d.partial = (uint64_t*)(base + o_partial);
+    d.bitbuf = (uint32_t*)(base + o_bitbuf);
+    d.count = (uint32_t*)(base + o_count);
+    d.start = (uint64_t*)(base + o_start);
+    d.status = (uint32_t*)(base + o_status);
+    d.result = (long long*)(base + o_result);
+    d.out = out;
+    d.capacity = capacity;
+    d.blocks = blocks;
+    d.chunks = chunks;
+    d.n = n;
+    d.chunk_bytes = chunk_bytes;
+    HIP_TRY(ctx, launch_jpeg_encode(d, s));
+    std::vector<long long> result(2 * (size_t)n + 1);
+    std::vector<uint32_t> status((size_t)n);
+    HIP_TRY(ctx, hipMemcpyAsync(result.data(), d.result, 8 * result.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(status.data(), d.status, 4 * status.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    for (int i = 0; i < n; ++i) {
+        offsets[i] = result[i];
+        sizes[i] = result[(size_t)n + i];
+    }
+    *needed = result[2 * (size_t)n];
+    for (int i = 0; i < n; ++i)
+        if (status[i]) return fail(ctx, MDHIP_EINVAL, "window %d: a coefficient no baseline JPEG can hold (status %u)", i, status[i]);
+    if (*needed > capacity)
+        return fail(ctx, MDHIP_ECAPACITY, "the scans take %lld bytes, the output buffer has %lld", (long long)*needed, (long long)capacity);
+    return MDHIP_OK;
+}
+
+int mdhip_blur_regions(mdhip_ctx* ctx, uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
+                       int n_images, const int32_t* rect_image, const int32_t* rects, int n_rects, float radius, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (n_rects == 0) return MDHIP_OK;
+    if (!images || !widths || !heights || !pitches || !rect_image || !rects)
+        return fail(ctx, MDHIP_EINVAL, "images/widths/heights/pitches/rect_image/rects is NULL");
+    if (n_images < 1 || n_images > 65535 || n_rects < 0) return fail(ctx, MDHIP_EINVAL, "n_images = %d, n_rects = %d", n_images, n_rects);
+    if (!(radius >= 0.0f) || radius > MD_BLUR_MAX_RADIUS) return fail(ctx, MDHIP_EINVAL, "radius %g outside 0 .. %g", (double)radius, (double)MD_BLUR_MAX_RADIUS);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const MdBlurWeights wt = md_blur_weights(radius);
+    // every rectangle is checked before anything is launched; round k holds the k-th rectangle with area of every image
+    std::vector<int> seen((size_t)n_images, -1), count((size_t)n_images, 0);
+    std::vector<std::vector<BlurRect>> rounds;
+    for (int i = 0; i < n_rects; ++i) {
+        const int m = rect_image[i];
+        if (m < 0 || m >= n_images) return fail(ctx, MDHIP_EINVAL, "rectangle %d: image %d of %d", i, m, n_images);
+        const int32_t* q = rects + 4 * (size_t)i;
+        if (q[2] <= q[0] || q[3] <= q[1]) continue;                     // without area: Pillow pastes nothing
+        if (seen[m] < 0) {
+            const int W = widths[m], H = heights[m];
+            if (int rc = check_window(ctx, "image", m, W, H, pitches[m])) return rc;
+            if (!images[m] || !is_device_ptr(images[m]))
+                return fail(ctx, MDHIP_EINVAL, "image %d: NULL or a host pointer -- images must be device memory", m);
+            seen[m] = 1;
+        }
+        if (q[0] < 0 || q[1] < 0 || q[2] > widths[m] || q[3] > heights[m])
+            return fail(ctx, MDHIP_EINVAL, "rectangle %d: (%d, %d, %d, %d) leaves its %dx%d image", i, q[0], q[1], q[2], q[3], widths[m], heights[m]);
+        BlurRect d;
+        memset(&d, 0, sizeof(d));
+        d.img = images[m] + (long long)q[1] * pitches[m] + (long long)q[0] * 3;
+        d.pitch = pitches[m];
+        d.w = q[2] - q[0];
+        d.h = q[3] - q[1];
+        d.sp = (int)align_up((size_t)d.w * 3, 64);
+        MdBlurXPlan plan;
+        if (!md_blur_plan_x(d.w, wt.r, BLUR_LDS_BYTES, &plan) || (long long)plan.rows * plan.stride * 2 > BLUR_LDS_BYTES)
+            return fail(ctx, MDHIP_EUNSUPPORTED, "rectangle %d: no row plan for %d pixels at box radius %d", i, d.w, wt.r);
+        d.rows = plan.rows, d.stride = plan.stride, d.chunks = plan.chunks, d.step = plan.step, d.halo = plan.halo;
+        d.row_groups = (d.h + d.rows - 1) / d.rows;
+        const size_t k = (size_t)count[m]++;
+        if (rounds.size() <= k) rounds.resize(k + 1);
+        rounds[k].push_back(d);
+    }
+    if (rounds.empty()) return MDHIP_OK;
+    // the scratch: [records of all rounds][planes of one round]; the rounds run one after the other and share the planes
+    size_t n_records = 0, plane_bytes = 0;
+    for (auto& round : rounds) {
+        ScratchLayout planes;
+        for (BlurRect& d : round) {
+            d.s0 = (long long)planes.take((size_t)d.sp * (size_t)d.h);
+            d.s1 = (long long)planes.take((size_t)d.sp * (size_t)d.h);
+        }
+        plane_bytes = std::max(plane_bytes, planes.size);
+        n_records += round.size();
+    }
+    const size_t o_planes = align_up(sizeof(BlurRect) * n_records, 256);
+    const size_t total = o_planes + plane_bytes;
+    if (int rc = ctx->blur.reserve(ctx, total)) return rc;
+    std::vector<BlurRect> up;
+    up.reserve(n_records);
+    for (auto& round : rounds) up.insert(up.end(), round.begin(), round.end());
+    // (the upload is from pageable memory: the copy has left `up` when the call returns)
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->blur.p, up.data(), sizeof(BlurRect) * n_records, hipMemcpyHostToDevice, s));
+    size_t first = 0;
+    for (auto& round : rounds) {
+        int max_blocks = 1, max_width = 1;
+        for (const BlurRect& d : round) {
+            max_blocks = std::max(max_blocks, d.row_groups * d.chunks);
+            max_width = std::max(max_width, d.w);
+        }
+        HIP_TRY(ctx, launch_blur_round((const BlurRect*)ctx->blur.p + first, (int)round.size(), max_blocks, max_width,
+                                       (uint8_t*)ctx->blur.p + o_planes, wt.r, wt.ww, wt.fw, s));
+        first += round.size();
+    }
+    return MDHIP_OK;
+}
+
+}  // extern "C"

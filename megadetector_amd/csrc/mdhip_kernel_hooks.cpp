@@ -1,0 +1,146 @@
+// The YOLO11 / YOLOv9 kernels in isolation (tests): the mdhip_*_on hooks of include/mdhip.h.
+// host buffers in / out; scratch device memory is allocated per call (not for the product path)
+
+#include <algorithm>
+#include <vector>
+
+#include "mdhip_ctx.h"
+
+namespace {
+struct DevBufs {
+    std::vector<void*> p;
+    ~DevBufs() { for (void* q : p) (void)hipFree(q); }
+    hipError_t get(size_t bytes, void** out) { *out = nullptr; hipError_t e = hipMalloc(out, std::max<size_t>(bytes, 16)); if (e == hipSuccess) p.push_back(*out); return e; }
+};
+}  // namespace
+
+extern "C" {
+
+int mdhip_dwconv3x3_on(mdhip_ctx* ctx, const uint16_t* in, int ld_in, const float* weight, const float* bias, const uint16_t* res,
+                       uint16_t* out, int n, int h, int w, int c, int grp, int grp_stride, int grp_off, int act, void* hip_stream) {
+    if (!ctx || !in || !weight || !bias || !out || n < 1 || h < 1 || w < 1 || c < 8 || c % 8 || grp < 8 || ld_in < 8)
+        return MDHIP_EINVAL;
+    if ((c / grp - 1) * grp_stride + grp_off + grp > ld_in || c % grp) return fail(ctx, MDHIP_EINVAL, "channel mapping outside ld_in");
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int f16 = ctx->dtype == MDHIP_DTYPE_FP16;
+    std::vector<uint16_t> wp((size_t)9 * c);
+    for (int o = 0; o < c; ++o)
+        for (int t = 0; t < 9; ++t) wp[(size_t)t * c + o] = f32_to_st(weight[(size_t)o * 9 + t], f16);
+    const size_t px = (size_t)n * h * w;
+    DevBufs d;
+    void *din, *dw, *db, *dout, *dres = nullptr;
+    HIP_TRY(ctx, d.get(px * ld_in * 2, &din));
+    HIP_TRY(ctx, d.get(wp.size() * 2, &dw));
+    HIP_TRY(ctx, d.get((size_t)c * 4, &db));
+    HIP_TRY(ctx, d.get(px * c * 2, &dout));
+    HIP_TRY(ctx, hipMemcpy(din, in, px * ld_in * 2, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(dw, wp.data(), wp.size() * 2, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(db, bias, (size_t)c * 4, hipMemcpyHostToDevice));
+    if (res) {
+        HIP_TRY(ctx, d.get(px * c * 2, &dres));
+        HIP_TRY(ctx, hipMemcpy(dres, res, px * c * 2, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(ctx, launch_dwconv3x3((const uint16_t*)din, ld_in, (const uint16_t*)dw, (const float*)db, (uint16_t*)dout, c,
+                                  (const uint16_t*)dres, c, n, h, w, c, grp, grp_stride, grp_off, act, f16, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipMemcpy(out, dout, px * c * 2, hipMemcpyDeviceToHost));
+    return MDHIP_OK;
+}
+
+int mdhip_attention_on(mdhip_ctx* ctx, const uint16_t* qkv, uint16_t* out, int n, int n_tokens, int heads, void* hip_stream) {
+    if (!ctx || !qkv || !out || n < 1 || n_tokens < 1 || heads < 1) return MDHIP_EINVAL;
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)n * n_tokens;
+    DevBufs d;
+    void *din, *dout;
+    HIP_TRY(ctx, d.get(px * heads * 128 * 2, &din));
+    HIP_TRY(ctx, d.get(px * heads * 64 * 2, &dout));
+    HIP_TRY(ctx, hipMemcpy(din, qkv, px * heads * 128 * 2, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, launch_attention((const uint16_t*)din, heads * 128, (uint16_t*)dout, heads * 64, n, n_tokens, heads,
+                                  ctx->dtype == MDHIP_DTYPE_FP16, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipMemcpy(out, dout, px * heads * 64 * 2, hipMemcpyDeviceToHost));
+    return MDHIP_OK;
+}
+
+int mdhip_dfl_decode_on(mdhip_ctx* ctx, const float* box, const float* cls, int nc, int n, int ny, int nx, float stride, float* pred,
+                        void* hip_stream) {
+    if (!ctx || !box || !cls || !pred || nc < 1 || n < 1 || ny < 1 || nx < 1) return MDHIP_EINVAL;
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)n * ny * nx;
+    DevBufs d;
+    void *db, *dc, *dp;
+    HIP_TRY(ctx, d.get(px * 64 * 4, &db));
+    HIP_TRY(ctx, d.get(px * nc * 4, &dc));
+    HIP_TRY(ctx, d.get(px * (4 + nc) * 4, &dp));
+    HIP_TRY(ctx, hipMemcpy(db, box, px * 64 * 4, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(dc, cls, px * nc * 4, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, launch_dfl_decode((const float*)db, 64, (const float*)dc, nc, (float*)dp, n, ny, nx, nc, ny * nx, 0, stride, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipMemcpy(pred, dp, px * (4 + nc) * 4, hipMemcpyDeviceToHost));
+    return MDHIP_OK;
+}
+
+int mdhip_adown_pool_on(mdhip_ctx* ctx, const uint16_t* in, uint16_t* a, uint16_t* b, int n, int h, int w, int c_in,
+                        void* hip_stream) {
+    if (!ctx || !in || !a || !b || n < 1 || h < 2 || w < 2 || h % 2 || w % 2 || c_in < 16 || c_in % 16) return MDHIP_EINVAL;
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)n * h * w, half = (size_t)c_in / 2;
+    DevBufs d;
+    void *din, *da, *db;
+    HIP_TRY(ctx, d.get(px * c_in * 2, &din));
+    HIP_TRY(ctx, d.get(px * half * 2, &da));
+    HIP_TRY(ctx, d.get(px / 4 * half * 2, &db));
+    HIP_TRY(ctx, hipMemcpy(din, in, px * c_in * 2, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, launch_adown_pool((const uint16_t*)din, c_in, (uint16_t*)da, (int)half, (uint16_t*)db, (int)half, n, h, w, c_in,
+                                   ctx->dtype == MDHIP_DTYPE_FP16, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipMemcpy(a, da, px * half * 2, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(b, db, px / 4 * half * 2, hipMemcpyDeviceToHost));
+    return MDHIP_OK;
+}
+
+int mdhip_cbfuse_on(mdhip_ctx* ctx, const uint16_t* const* src, const int32_t* factor, int n_src, const uint16_t* last,
+                    uint16_t* out, int n, int h, int w, int c, void* hip_stream) {
+    if (!ctx || !src || !factor || !last || !out || n_src < 1 || n_src > 3 || n < 1 || h < 1 || w < 1 || c < 8 || c % 8)
+        return MDHIP_EINVAL;
+    for (int k = 0; k < n_src; ++k)
+        if (!src[k] || factor[k] < 1 || h % factor[k] || w % factor[k]) return fail(ctx, MDHIP_EINVAL, "bad CBFuse source %d", k);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)n * h * w;
+    DevBufs d;
+    CbfuseArgs a{};
+    void *dl, *dout;
+    for (int k = 0; k < n_src; ++k) {
+        const size_t bytes = (size_t)n * (h / factor[k]) * (w / factor[k]) * c * 2;
+        void* p;
+        HIP_TRY(ctx, d.get(bytes, &p));
+        HIP_TRY(ctx, hipMemcpy(p, src[k], bytes, hipMemcpyHostToDevice));
+        a.src[k] = (const uint16_t*)p;
+        a.ld_src[k] = c;
+        a.factor[k] = factor[k];
+    }
+    HIP_TRY(ctx, d.get(px * c * 2, &dl));
+    HIP_TRY(ctx, d.get(px * c * 2, &dout));
+    HIP_TRY(ctx, hipMemcpy(dl, last, px * c * 2, hipMemcpyHostToDevice));
+    a.n_src = n_src;
+    a.last = (const uint16_t*)dl;
+    a.ld_last = c;
+    a.out = (uint16_t*)dout;
+    a.ld_out = c;
+    a.n = n;
+    a.H = h;
+    a.W = w;
+    a.C = c;
+    HIP_TRY(ctx, launch_cbfuse(a, ctx->dtype == MDHIP_DTYPE_FP16, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipMemcpy(out, dout, px * c * 2, hipMemcpyDeviceToHost));
+    return MDHIP_OK;
+}
+
+}  // extern "C"
