@@ -321,6 +321,46 @@ long long mdhip_jpeg_encode_bound(int width, int height);
 int mdhip_blur_regions(mdhip_ctx* ctx, uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
                        int n_images, const int32_t* rect_image, const int32_t* rects, int n_rects, float radius, void* hip_stream);
 
+/* Annotated previews of device images (the reference's visualization/visualize_detector_output.py: resize to 1000 pixels
+ * wide with Pillow's LANCZOS filter, then render_detection_bounding_boxes), from the image that is in device memory already.
+ *
+ * mdhip_resample_lanczos makes of every source what Pillow's Image.resize((dst_width, dst_height), LANCZOS) makes of it,
+ * bit for bit (csrc/resample.h, shared with the host model mdjpeg_resample): per axis whose size changes, the horizontal one
+ * first, a weighted sum of the taps within 3 max(scale, 1) samples of the output sample's centre; weights in double,
+ * normalised, rounded to 22 fractional bits; 32-bit integer sums, rounded and clipped to 8 bits behind each pass.  An axis
+ * whose size stays is not resampled; an image whose size stays is copied.
+ *   src, widths, heights, pitches               n DEVICE images, 8 bits a sample, R G B interleaved, pitches[i] bytes a row
+ *                                               (>= 3 * widths[i], any value); sizes 1 .. 65535, below 2 GB
+ *   dst, dst_widths, dst_heights, dst_pitches   the n destinations, likewise; they must not overlap the sources.  Nothing
+ *                                               beside the 3 * dst_widths[i] bytes of each of their rows is written.
+ * One launch per pass for the whole batch.  The coefficient tables are computed here, once per distinct (in, out) pair of the
+ * batch.  MDHIP_EUNSUPPORTED when the taps of one output pixel of a row do not fit on chip (a row reduced more than about
+ * 1800 times); nothing has been enqueued then.  The call only enqueues.  Scratch -- tables and the 8-bit images between the
+ * passes (heights[i] x dst_widths[i]) -- belongs to the context and grows on demand (the device is synchronised when it
+ * does): keep all mdhip_resample_lanczos and mdhip_draw_ops calls of one context on ONE stream. */
+int mdhip_resample_lanczos(mdhip_ctx* ctx, const uint8_t* const* src, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
+                           int n, uint8_t* const* dst, const int32_t* dst_widths, const int32_t* dst_heights, const int64_t* dst_pitches,
+                           void* hip_stream);
+
+/* mdhip_draw_ops applies to each image its ordered list of drawing operations, IN PLACE and in one launch: a pixel takes
+ * the value of the LAST operation of its image's list that covers it (the host model: mdjpeg_draw).
+ *   images, widths, heights, pitches   n_images DEVICE images as above
+ *   op_image, ops, n_ops               operation i belongs to image op_image[i] and is the 8 int32 ops[8 i .. 8 i + 7]:
+ *                                        [0, x0, y0, x1, y1, colour, 0, 0]  a solid rectangle, x0 .. x1 and y0 .. y1 INCLUSIVE,
+ *                                                                           colour = R | G << 8 | B << 16
+ *                                        [1, x, y, w, h, offset, 0, 0]      the paste of w x h pixels (R G B, 3 w bytes a row)
+ *                                                                           that begin at byte `offset` of `patches`, their
+ *                                                                           top left corner at (x, y); w, h <= 32767
+ *                                      Both are clipped to the image (coordinates may be negative or beyond it).  The
+ *                                      operations of one image keep the order of the list; those of different images may
+ *                                      be interleaved.
+ *   patches, patch_bytes               ONE packed DEVICE buffer with the pixels of all patches, and its size
+ * MDHIP_EINVAL, with nothing launched and no image changed, for an operation that names an image outside 0 .. n_images - 1,
+ * an unknown kind, or a patch that is not wholly inside `patches`.  The call only enqueues; see above for the stream. */
+int mdhip_draw_ops(mdhip_ctx* ctx, uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
+                   int n_images, const int32_t* op_image, const int32_t* ops, int n_ops, const uint8_t* patches, int64_t patch_bytes,
+                   void* hip_stream);
+
 /* Test-time augmentation: replaces mdhip_forward for `model(batch, augment=True)` (reference
  * pytorch_detector.py:1313 -> yolov5 _forward_augment): three passes over the batch that mdhip_preprocess
  * left in the context -- scale 1, scale 0.83 left-right flipped, scale 0.67 (bilinear, padded with 0.447 to

@@ -125,6 +125,18 @@ int mdjpeg_blur_regions_chunked(uint8_t* rgb, int32_t width, int32_t height, int
                                 float radius, int lds_bytes);
 int mdjpeg_blur_weights(float radius, int32_t* r, uint32_t* ww, uint32_t* fw);
 
+/* ---- annotated previews (GPU: mdhip_resample_lanczos, mdhip_draw_ops, include/mdhip.h) ---------------------------------- */
+/* The host models of the two GPU calls, compiled from the header the kernels are compiled from (csrc/resample.h).
+ * mdjpeg_resample: Pillow's Image.resize((dst_width, dst_height), LANCZOS) of an 8-bit RGB image, bit for bit; `pitch` and
+ * `dst_pitch` are bytes a row (>= 3 * width); sizes 1 .. 65535; the images must not overlap.
+ * mdjpeg_draw: applies n_ops drawing operations of 8 int32 each (see mdhip_draw_ops) to an image in place -- a pixel takes
+ * the value of the last operation that covers it; `patches` holds the pixels of the patch operations, patch_bytes bytes.
+ * MDJPEG_EINVAL, and nothing is changed, for an unknown kind or a patch outside `patches`. */
+int mdjpeg_resample(const uint8_t* src, int32_t width, int32_t height, int64_t pitch, uint8_t* dst, int32_t dst_width, int32_t dst_height,
+                    int64_t dst_pitch);
+int mdjpeg_draw(uint8_t* rgb, int32_t width, int32_t height, int64_t pitch, const int32_t* ops, int n_ops, const uint8_t* patches,
+                int64_t patch_bytes);
+
 const char* mdjpeg_version(void);
 
 #ifdef __cplusplus

@@ -86,6 +86,10 @@ SYMBOLS = {
     'mdhip_jpeg_encode_bound': (C.c_longlong, [C.c_int, C.c_int]),
     'mdhip_blur_regions': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_float, _P]),
+    'mdhip_resample_lanczos': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int,
+                                         C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), _P]),
+    'mdhip_draw_ops': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int,
+                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, _P, C.c_int64, _P]),
     'mdhip_forward_tta': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_last_num_anchors': (C.c_int, [_P]),
     'mdhip_calibrate': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),

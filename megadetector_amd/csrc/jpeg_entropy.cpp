@@ -12,6 +12,7 @@
 #include "jpeg_subseq.h"
 #include "jpeg_encode.h"
 #include "blur_box.h"
+#include "resample.h"
 
 #include <cstdio>
 #include <cstring>
@@ -729,7 +730,88 @@ int mdjpeg_blur_weights(float radius, int32_t* r, uint32_t* ww, uint32_t* fw) {
     return MDJPEG_OK;
 }
 
-const char* mdjpeg_version(void) { return "mdjpeg 4"; }
+// The host model of mdhip_resample_lanczos for one image: the passes as the workgroups run them -- the horizontal one strip
+// by strip out of a copy of the strip's source run (placed as the on-chip copy is), the vertical one byte column by byte column.
+int mdjpeg_resample(const uint8_t* src, int32_t width, int32_t height, int64_t pitch, uint8_t* dst, int32_t dst_width, int32_t dst_height,
+                    int64_t dst_pitch) {
+    if (!src || !dst || width < 1 || height < 1 || dst_width < 1 || dst_height < 1 || width > 65535 || height > 65535 ||
+        dst_width > 65535 || dst_height > 65535 || pitch < int64_t(width) * 3 || dst_pitch < int64_t(dst_width) * 3)
+        return MDJPEG_EINVAL;
+    const bool horizontal = dst_width != width, vertical = dst_height != height;
+    if (!horizontal && !vertical) {
+        for (int y = 0; y < height; ++y) memcpy(dst + int64_t(y) * dst_pitch, src + int64_t(y) * pitch, size_t(width) * 3);
+        return MDJPEG_OK;
+    }
+    std::vector<int32_t> bounds, kk;
+    std::vector<double> work;
+    std::vector<uint8_t> between;
+    const uint8_t* in = src;
+    int64_t in_pitch = pitch;
+    if (horizontal) {
+        const int ksize = md_resample_ksize(width, dst_width);
+        bounds.assign(size_t(dst_width) * 2, 0);
+        kk.assign(size_t(dst_width) * ksize, 0);
+        work.assign(size_t(ksize), 0.0);
+        md_resample_coeffs(width, dst_width, ksize, bounds.data(), kk.data(), work.data());
+        MdResampleStrips plan;
+        if (!md_resample_plan_strips(bounds.data(), dst_width, MD_RESAMPLE_LDS_BYTES, &plan)) return MDJPEG_EUNSUPPORTED;
+        uint8_t* out = dst;
+        int64_t out_pitch = dst_pitch;
+        if (vertical) {
+            between.assign(size_t(dst_width) * 3 * height, 0);
+            out = between.data(), out_pitch = int64_t(dst_width) * 3;
+        }
+        std::vector<uint8_t> run(size_t(plan.run_bytes), 0);
+        for (int y = 0; y < height; ++y)
+            for (int o0 = 0; o0 < dst_width; o0 += plan.strip) {
+                const int o1 = o0 + plan.strip < dst_width ? o0 + plan.strip : dst_width;
+                const int first = bounds[2 * o0];
+                const int nb = (bounds[2 * (o1 - 1)] + bounds[2 * (o1 - 1) + 1] - first) * 3;
+                const uint8_t* line = src + int64_t(y) * pitch + int64_t(first) * 3;
+                const int sh = int(uintptr_t(line) & 3);
+                if (sh + nb > plan.run_bytes) return MDJPEG_EINVAL;
+                memcpy(run.data() + sh, line, size_t(nb));
+                for (int o = o0; o < o1; ++o)
+                    for (int c = 0; c < 3; ++c)
+                        out[int64_t(y) * out_pitch + int64_t(o) * 3 + c] =
+                            md_resample_dot(run.data() + sh + (bounds[2 * o] - first) * 3 + c, 3, kk.data() + size_t(o) * ksize, bounds[2 * o + 1]);
+            }
+        in = out, in_pitch = out_pitch;
+    }
+    if (vertical) {
+        const int ksize = md_resample_ksize(height, dst_height);
+        bounds.assign(size_t(dst_height) * 2, 0);
+        kk.assign(size_t(dst_height) * ksize, 0);
+        work.assign(size_t(ksize), 0.0);
+        md_resample_coeffs(height, dst_height, ksize, bounds.data(), kk.data(), work.data());
+        for (int y = 0; y < dst_height; ++y)
+            for (int x = 0; x < dst_width * 3; ++x)
+                dst[int64_t(y) * dst_pitch + x] =
+                    md_resample_dot(in + int64_t(bounds[2 * y]) * in_pitch + x, in_pitch, kk.data() + size_t(y) * ksize, bounds[2 * y + 1]);
+    }
+    return MDJPEG_OK;
+}
+
+// the host model of mdhip_draw_ops for one image: every pixel takes the value of the last operation that covers it
+int mdjpeg_draw(uint8_t* rgb, int32_t width, int32_t height, int64_t pitch, const int32_t* ops, int n_ops, const uint8_t* patches,
+                int64_t patch_bytes) {
+    if (!rgb || width < 1 || height < 1 || pitch < int64_t(width) * 3 || n_ops < 0 || (n_ops && !ops) || patch_bytes < 0) return MDJPEG_EINVAL;
+    for (int i = 0; i < n_ops; ++i) {
+        const int32_t* op = ops + size_t(i) * MD_DRAW_OP_WORDS;
+        if (md_draw_op_bad(op, patch_bytes)) return MDJPEG_EINVAL;
+        if (op[0] == MD_DRAW_PATCH && op[3] > 0 && op[4] > 0 && !patches) return MDJPEG_EINVAL;
+    }
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+            uint8_t v[3];
+            if (!md_draw_pixel(ops, n_ops, patches, x, y, v)) continue;
+            uint8_t* p = rgb + int64_t(y) * pitch + int64_t(x) * 3;
+            p[0] = v[0], p[1] = v[1], p[2] = v[2];
+        }
+    return MDJPEG_OK;
+}
+
+const char* mdjpeg_version(void) { return "mdjpeg 5"; }
 
 }  // extern "C"
 
@@ -777,7 +859,54 @@ static int blur_matrix() {
     return 0;
 }
 
+// `--preview`: mdjpeg_resample and mdjpeg_draw on heap images of exactly pitch x (height - 1) + 3 x width bytes -- reducing,
+// enlarging, one axis unchanged, a single pixel, a pitch above 3 x width, runs longer than a strip -- and operations that
+// leave the image on every side, so that the sanitizers see any access outside an image.
+static int preview_matrix() {
+    const int shapes[][6] = {{97, 61, 40, 25, 0, 0}, {333, 500, 166, 249, 0, 0}, {50, 40, 120, 96, 0, 0}, {1000, 37, 70, 2, 0, 0}, {1, 1, 5, 5, 0, 0},
+                             {640, 480, 640, 479, 0, 0}, {17, 9, 8, 4, 64, 29}, {1300, 40, 100, 3, 3907, 301}, {17, 9, 17, 9, 64, 64}, {3, 2000, 2, 1, 0, 0}};
+    for (const auto& q : shapes) {
+        const int w = q[0], h = q[1], dw = q[2], dh = q[3];
+        const int64_t pitch = q[4] ? q[4] : int64_t(w) * 3, dpitch = q[5] ? q[5] : int64_t(dw) * 3;
+        const size_t bytes = size_t(pitch) * (h - 1) + size_t(w) * 3, dbytes = size_t(dpitch) * (dh - 1) + size_t(dw) * 3;
+        for (int shift = 0; shift < 4; ++shift) {                        // every alignment of the first byte
+            uint8_t* a = new uint8_t[bytes + shift];
+            uint8_t* b = new uint8_t[dbytes];
+            uint32_t seed = 777u + uint32_t(w);
+            for (size_t i = 0; i < bytes + shift; ++i) a[i] = uint8_t((seed = seed * 1664525u + 1013904223u) >> 24);
+            const int rc = mdjpeg_resample(a + shift, w, h, pitch, b, dw, dh, dpitch);
+            delete[] a;
+            delete[] b;
+            if (rc != MDJPEG_OK) { printf("preview: %dx%d -> %dx%d: %d\n", w, h, dw, dh, rc); return 6; }
+        }
+    }
+    const int W = 53, H = 31;
+    const int64_t pitch = 170;
+    const size_t bytes = size_t(pitch) * (H - 1) + size_t(W) * 3;
+    const int pw = 20, ph = 9;
+    uint8_t* patch = new uint8_t[size_t(pw) * ph * 3 + 5];
+    for (size_t i = 0; i < size_t(pw) * ph * 3 + 5; ++i) patch[i] = uint8_t(i);
+    const int32_t ops[] = {0, 5, 5, 20, 12, 0x0000ff, 0, 0,   0, -7, -3, 2, 200, 0x00ff00, 0, 0,   0, 40, 25, 1000, 30, 0xff0000, 0, 0,
+                           0, 10, 10, 9, 20, 0x123456, 0, 0,   0, -2147483647, -2147483647, 2147483647, 0, 0x654321, 0, 0,
+                           1, -5, -4, pw, ph, 5, 0, 0,   1, W - 3, H - 2, pw, ph, 0, 0, 0,   1, 7, 11, pw, ph, 0, 0, 0,
+                           1, 2147483000, 2147483000, pw, ph, 0, 0, 0,   1, -2147483647, 3, pw, ph, 0, 0, 0,   1, 30, 3, 0, 0, 0, 0, 0};
+    const int n_ops = int(sizeof(ops) / sizeof(ops[0]) / MD_DRAW_OP_WORDS);
+    uint8_t* img = new uint8_t[bytes];
+    memset(img, 9, bytes);
+    int rc = mdjpeg_draw(img, W, H, pitch, ops, n_ops, patch, int64_t(pw) * ph * 3 + 5);
+    const int32_t outside[] = {1, 0, 0, pw, ph, 6, 0, 0};
+    const int rb = mdjpeg_draw(img, W, H, pitch, outside, 1, patch, int64_t(pw) * ph * 3 + 5);
+    const int32_t unknown[] = {2, 0, 0, 1, 1, 0, 0, 0};
+    const int ru = mdjpeg_draw(img, W, H, pitch, unknown, 1, patch, 0);
+    delete[] img;
+    delete[] patch;
+    if (rc != MDJPEG_OK || rb != MDJPEG_EINVAL || ru != MDJPEG_EINVAL) { printf("preview: draw %d %d %d\n", rc, rb, ru); return 6; }
+    printf("preview: %d shapes x 4 alignments, %d operations\n", int(sizeof(shapes) / sizeof(shapes[0])), n_ops);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc == 2 && !strcmp(argv[1], "--preview")) return preview_matrix();
     if (argc == 2 && !strcmp(argv[1], "--blur")) return blur_matrix();
     for (int i = 1; i < argc; ++i) {
         FILE* f = fopen(argv[i], "rb");

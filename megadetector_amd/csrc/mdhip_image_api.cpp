@@ -1,4 +1,5 @@
-// The image entry points of the C ABI (include/mdhip.h): letterbox (mdhip_preprocess*), JPEG (mdhip_jpeg_*), mdhip_blur_regions.
+// The image entry points of the C ABI (include/mdhip.h): letterbox (mdhip_preprocess*), JPEG (mdhip_jpeg_*), mdhip_blur_regions,
+// the previews (mdhip_resample_lanczos, mdhip_draw_ops).
 // None of them looks at the model: they check their arguments, lay out scratch in one of the context's growable buffers
 // (mdhip_ctx.h DevBuffer) and launch.  What their checks have in common is written once, below; where two entry points
 // apply the same checks in a different order, each keeps its own order (the first failing check is what a caller sees).
@@ -6,12 +7,15 @@
 #include <algorithm>
 #include <climits>
 #include <cstring>
+#include <map>
+#include <utility>
 #include <vector>
 
 #include "mdhip_ctx.h"
 #include "jpeg_subseq.h"
 #include "jpeg_encode.h"
 #include "blur_box.h"
+#include "resample.h"
 
 namespace {
 
@@ -589,6 +593,195 @@ int mdhip_blur_regions(mdhip_ctx* ctx, uint8_t* const* images, const int32_t* wi
                                        (uint8_t*)ctx->blur.p + o_planes, wt.r, wt.ww, wt.fw, s));
         first += round.size();
     }
+    return MDHIP_OK;
+}
+
+int mdhip_resample_lanczos(mdhip_ctx* ctx, const uint8_t* const* src, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
+                           int n, uint8_t* const* dst, const int32_t* dst_widths, const int32_t* dst_heights, const int64_t* dst_pitches,
+                           void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (n == 0) return MDHIP_OK;
+    if (!src || !widths || !heights || !pitches || !dst || !dst_widths || !dst_heights || !dst_pitches)
+        return fail(ctx, MDHIP_EINVAL, "src/widths/heights/pitches/dst/dst_widths/dst_heights/dst_pitches is NULL");
+    if (n < 1 || n > 65535) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // every image is checked and planned before anything is enqueued; one coefficient table per distinct (in, out) pair
+    struct Coeffs { int ksize, bounds_off, kk_off; };
+    std::map<std::pair<int, int>, Coeffs> pairs;
+    std::vector<int32_t> table;
+    std::vector<double> work;
+    auto coeffs = [&](int in, int out) -> Coeffs {
+        auto it = pairs.find({in, out});
+        if (it != pairs.end()) return it->second;
+        Coeffs c;
+        c.ksize = md_resample_ksize(in, out);
+        c.bounds_off = (int)table.size();
+        c.kk_off = c.bounds_off + 2 * out;
+        table.resize(table.size() + 2 * (size_t)out + (size_t)out * c.ksize);
+        work.resize((size_t)c.ksize);
+        md_resample_coeffs(in, out, c.ksize, table.data() + c.bounds_off, table.data() + c.kk_off, work.data());
+        pairs[{in, out}] = c;
+        return c;
+    };
+    std::vector<ResampleRows> rows;
+    std::vector<ResampleColumns> columns;
+    std::vector<int> copies;
+    std::vector<long long> between((size_t)n, -1);                      // of an image that takes both passes: its 8-bit image between them
+    ScratchLayout planes;
+    for (int i = 0; i < n; ++i) {
+        const int sw = widths[i], sh = heights[i], dw = dst_widths[i], dh = dst_heights[i];
+        if (int rc = check_window(ctx, "source", i, sw, sh, pitches[i])) return rc;
+        if (int rc = check_window(ctx, "destination", i, dw, dh, dst_pitches[i])) return rc;
+        if (!src[i] || !dst[i] || !is_device_ptr(src[i]) || !is_device_ptr(dst[i]))
+            return fail(ctx, MDHIP_EINVAL, "image %d: NULL or a host pointer -- sources and destinations must be device memory", i);
+        const bool horizontal = dw != sw, vertical = dh != sh;
+        if (!horizontal && !vertical) { copies.push_back(i); continue; }
+        const int tmp_pitch = (int)align_up((size_t)dw * 3, 16);
+        if (horizontal && vertical) between[i] = (long long)planes.take((size_t)tmp_pitch * (size_t)sh);
+        if (horizontal) {
+            const Coeffs c = coeffs(sw, dw);
+            MdResampleStrips plan;
+            if (!md_resample_plan_strips(table.data() + c.bounds_off, dw, MD_RESAMPLE_LDS_BYTES, &plan))
+                return fail(ctx, MDHIP_EUNSUPPORTED, "image %d: the taps of one pixel of %d -> %d pixels do not fit on chip", i, sw, dw);
+            ResampleRows d;
+            memset(&d, 0, sizeof(d));
+            d.src = src[i], d.src_pitch = pitches[i];
+            d.dst = vertical ? nullptr : dst[i], d.dst_pitch = vertical ? tmp_pitch : dst_pitches[i];
+            d.rows = sh, d.out_w = dw, d.ksize = c.ksize, d.bounds_off = c.bounds_off, d.kk_off = c.kk_off;
+            d.strip = plan.strip, d.wg_rows = plan.rows, d.run_bytes = plan.run_bytes;
+            d.strips = (dw + plan.strip - 1) / plan.strip;
+            d.row_groups = (sh + plan.rows - 1) / plan.rows;
+            if ((long long)d.strips * d.row_groups > 0x7fffffffLL) return fail(ctx, MDHIP_EUNSUPPORTED, "image %d: too many strips", i);
+            rows.push_back(d);
+        }
+        if (vertical) {
+            const Coeffs c = coeffs(sh, dh);
+            ResampleColumns d;
+            memset(&d, 0, sizeof(d));
+            d.src = horizontal ? nullptr : src[i], d.src_pitch = horizontal ? tmp_pitch : pitches[i];
+            d.dst = dst[i], d.dst_pitch = dst_pitches[i];
+            d.row_bytes = dw * 3, d.out_h = dh, d.ksize = c.ksize, d.bounds_off = c.bounds_off, d.kk_off = c.kk_off;
+            d.pad = i;                                                  // (the image, until the scratch is laid out)
+            columns.push_back(d);
+        }
+    }
+    for (int i : copies)
+        HIP_TRY(ctx, hipMemcpy2DAsync(dst[i], (size_t)dst_pitches[i], src[i], (size_t)pitches[i], (size_t)widths[i] * 3, (size_t)heights[i],
+                                      hipMemcpyDeviceToDevice, s));
+    if (rows.empty() && columns.empty()) return MDHIP_OK;
+    // the scratch: [coefficient tables][records of the rows pass][records of the columns pass][images between the passes]
+    ScratchLayout lay;
+    const size_t o_table = lay.take(table.size() * sizeof(int32_t));
+    const size_t o_rows = lay.take(rows.size() * sizeof(ResampleRows));
+    const size_t o_columns = lay.take(columns.size() * sizeof(ResampleColumns));
+    const size_t o_planes = lay.take(planes.size);
+    if (int rc = ctx->resample.reserve(ctx, lay.size)) return rc;
+    uint8_t* base = (uint8_t*)ctx->resample.p;
+    {
+        size_t r = 0;
+        for (int i = 0, c = 0; i < n; ++i) {
+            const bool horizontal = dst_widths[i] != widths[i], vertical = dst_heights[i] != heights[i];
+            if (horizontal && vertical) rows[r].dst = base + o_planes + between[i];
+            if (horizontal) ++r;
+            if (vertical) {
+                if (horizontal) columns[c].src = base + o_planes + between[i];
+                columns[c].pad = 0;
+                ++c;
+            }
+        }
+    }
+    // (the uploads are from pageable memory: the copies have left the vectors when the call returns)
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_table, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (!rows.empty()) {
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_rows, rows.data(), rows.size() * sizeof(ResampleRows), hipMemcpyHostToDevice, s));
+        int max_blocks = 1;
+        for (const ResampleRows& d : rows) max_blocks = std::max(max_blocks, d.strips * d.row_groups);
+        HIP_TRY(ctx, launch_resample_rows((const ResampleRows*)(base + o_rows), (int)rows.size(), max_blocks, (const int32_t*)(base + o_table), s));
+    }
+    if (!columns.empty()) {
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_columns, columns.data(), columns.size() * sizeof(ResampleColumns), hipMemcpyHostToDevice, s));
+        int max_row_bytes = 1, max_out_h = 1;
+        for (const ResampleColumns& d : columns) {
+            max_row_bytes = std::max(max_row_bytes, d.row_bytes);
+            max_out_h = std::max(max_out_h, d.out_h);
+        }
+        HIP_TRY(ctx, launch_resample_columns((const ResampleColumns*)(base + o_columns), (int)columns.size(), max_row_bytes, max_out_h,
+                                             (const int32_t*)(base + o_table), s));
+    }
+    return MDHIP_OK;
+}
+
+int mdhip_draw_ops(mdhip_ctx* ctx, uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
+                   int n_images, const int32_t* op_image, const int32_t* ops, int n_ops, const uint8_t* patches, int64_t patch_bytes,
+                   void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (n_ops == 0) return MDHIP_OK;
+    if (!images || !widths || !heights || !pitches || !op_image || !ops)
+        return fail(ctx, MDHIP_EINVAL, "images/widths/heights/pitches/op_image/ops is NULL");
+    if (n_images < 1 || n_images > 65535 || n_ops < 0 || patch_bytes < 0 || patch_bytes > 0x7fff0000LL)
+        return fail(ctx, MDHIP_EINVAL, "n_images = %d, n_ops = %d, patch_bytes = %lld", n_images, n_ops, (long long)patch_bytes);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // every operation is checked before anything is launched; an image's operations keep the order of the list
+    std::vector<int> count((size_t)n_images, 0);
+    bool any_patch = false;
+    for (int i = 0; i < n_ops; ++i) {
+        const int m = op_image[i];
+        if (m < 0 || m >= n_images) return fail(ctx, MDHIP_EINVAL, "operation %d: image %d of %d", i, m, n_images);
+        const int32_t* op = ops + (size_t)i * MD_DRAW_OP_WORDS;
+        if (md_draw_op_bad(op, patch_bytes))
+            return fail(ctx, MDHIP_EINVAL, "operation %d: kind %d, or a patch of %dx%d pixels at byte %d of %lld", i, op[0], op[3], op[4], op[5],
+                        (long long)patch_bytes);
+        any_patch |= op[0] == MD_DRAW_PATCH && op[3] > 0 && op[4] > 0;
+        ++count[m];
+    }
+    if (any_patch && (!patches || !is_device_ptr(patches))) return fail(ctx, MDHIP_EINVAL, "patches: NULL or a host pointer");
+    std::vector<DrawImage> recs;
+    std::vector<int> rec_of((size_t)n_images, -1), fill((size_t)n_images, 0);
+    int first = 0;
+    for (int m = 0; m < n_images; ++m) {
+        if (!count[m]) continue;
+        if (int rc = check_window(ctx, "image", m, widths[m], heights[m], pitches[m])) return rc;
+        if (!images[m] || !is_device_ptr(images[m]))
+            return fail(ctx, MDHIP_EINVAL, "image %d: NULL or a host pointer -- images must be device memory", m);
+        DrawImage d;
+        memset(&d, 0, sizeof(d));
+        d.img = images[m], d.pitch = pitches[m];
+        d.x0 = widths[m], d.y0 = heights[m], d.x1 = -1, d.y1 = -1;
+        d.op_first = first, d.op_count = count[m];
+        first += count[m];
+        rec_of[m] = (int)recs.size();
+        recs.push_back(d);
+    }
+    std::vector<int32_t> sorted((size_t)n_ops * MD_DRAW_OP_WORDS);
+    for (int i = 0; i < n_ops; ++i) {
+        const int m = op_image[i];
+        DrawImage& d = recs[(size_t)rec_of[m]];
+        const int32_t* op = ops + (size_t)i * MD_DRAW_OP_WORDS;
+        memcpy(sorted.data() + (size_t)(d.op_first + fill[m]++) * MD_DRAW_OP_WORDS, op, sizeof(int32_t) * MD_DRAW_OP_WORDS);
+        // what the operation covers, clipped to the image (64-bit: a corner plus a size may pass 2^31)
+        long long a = op[1], b = op[2], c = op[3], e = op[4];
+        if (op[0] == MD_DRAW_PATCH) c = a + c - 1, e = b + e - 1;
+        a = std::max(a, 0LL), b = std::max(b, 0LL);
+        c = std::min(c, (long long)widths[m] - 1), e = std::min(e, (long long)heights[m] - 1);
+        if (c < a || e < b) continue;
+        d.x0 = std::min(d.x0, (int)a), d.y0 = std::min(d.y0, (int)b), d.x1 = std::max(d.x1, (int)c), d.y1 = std::max(d.y1, (int)e);
+    }
+    int max_w = 0, max_h = 0;
+    for (const DrawImage& d : recs) {
+        max_w = std::max(max_w, d.x1 - d.x0 + 1);
+        max_h = std::max(max_h, d.y1 - d.y0 + 1);
+    }
+    if (max_w < 1 || max_h < 1) return MDHIP_OK;                         // nothing of any operation lies in its image
+    ScratchLayout lay;
+    const size_t o_recs = lay.take(recs.size() * sizeof(DrawImage));
+    const size_t o_ops = lay.take(sorted.size() * sizeof(int32_t));
+    if (int rc = ctx->draw.reserve(ctx, lay.size)) return rc;
+    uint8_t* base = (uint8_t*)ctx->draw.p;
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_recs, recs.data(), recs.size() * sizeof(DrawImage), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_ops, sorted.data(), sorted.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, launch_draw_ops((const DrawImage*)(base + o_recs), (int)recs.size(), max_w, max_h, (const int32_t*)(base + o_ops), patches, s));
     return MDHIP_OK;
 }
 

@@ -549,4 +549,35 @@ struct BlurRect {
 hipError_t launch_blur_round(const BlurRect* rects, int n, int max_row_blocks, int max_width, uint8_t* scratch, int r, uint32_t ww,
                              uint32_t fw, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------
+// Annotated previews (preview_kernels.cpp): LANCZOS resize and drawing, one record per image and pass (blockIdx.y / .z)
+// ---------------------------------------------------------------------------------------
+struct ResampleRows {                  // the horizontal pass of one image
+    const uint8_t* src;
+    uint8_t*  dst;                     // the image between the passes, or the destination when the height stays
+    long long src_pitch, dst_pitch;    // bytes from row to row
+    int rows, out_w;                   // rows of both images, pixels of an output row
+    int ksize;                         // taps a line of the coefficient table has room for
+    int strip, wg_rows, run_bytes;     // resample.h MdResampleStrips
+    int strips, row_groups;            // the pass runs strips * row_groups workgroups
+    int bounds_off, kk_off;            // of this (in, out) pair in the coefficient table, in int32 words
+};
+struct ResampleColumns {               // the vertical pass of one image
+    const uint8_t* src;                // the image between the passes, or the source when the width stays
+    uint8_t*  dst;
+    long long src_pitch, dst_pitch;
+    int row_bytes, out_h;              // bytes of a row that hold pixels (3 x width), output rows
+    int ksize, bounds_off, kk_off;
+    int pad;
+};
+struct DrawImage {
+    uint8_t*  img;
+    long long pitch;
+    int x0, y0, x1, y1;                // what the image's operations cover, clipped to the image; inclusive
+    int op_first, op_count;            // its operations in the list, in order
+};
+hipError_t launch_resample_rows(const ResampleRows* descs, int n, int max_blocks, const int32_t* table, hipStream_t s);
+hipError_t launch_resample_columns(const ResampleColumns* descs, int n, int max_row_bytes, int max_out_h, const int32_t* table, hipStream_t s);
+hipError_t launch_draw_ops(const DrawImage* images, int n, int max_w, int max_h, const int32_t* ops, const uint8_t* patches, hipStream_t s);
+
 }  // namespace mdhip

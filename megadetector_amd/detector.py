@@ -120,6 +120,7 @@ class HIPDetector:
         self.jpeg_images_entropy_decoded = 0    # of those: images whose scan was Huffman-decoded on the device too
         self.crop_counts = {'gpu': 0, 'host': 0, 'skipped': 0}      # crops= : encoded on the device / saved by PIL / without area
         self.blur_counts = {'gpu': 0, 'host': 0}                    # blur= : copies encoded on the device / saved by PIL
+        self.preview_counts = {'gpu': 0, 'host': 0, 'skipped': 0}   # preview= : encoded on the device / rendered or saved by PIL / no file
         self.jpeg_entropy_fallbacks = 0         # scans the device flagged: decoded with PIL from the file's bytes instead
         if preprocess_only:
             return                      # never touches HIP: safe in forked producer processes
@@ -244,16 +245,22 @@ class HIPDetector:
     # -----------------------------------------------------------------------------------
     supports_crops = True
     supports_blur = True
+    supports_preview = True
 
     def generate_detections_one_batch(self, img_original, image_id=None, detection_threshold=0.00001,
-                                      image_size=None, augment=False, verbose=False, crops=None, blur=None):
+                                      image_size=None, augment=False, verbose=False, crops=None, blur=None, preview=None):
         """reference pytorch_detector.py:1124-1252.  crops (a crops.CropOptions, default None = off): every result dict gains
         'crops', a list of (crop_id, crop_filename_relative, bytes) -- the files create_crop_folder.py writes for the
         image's detections, encoded on the device from the pixels that are resident there (mdhip_jpeg_encode).
         blur (a blur.BlurOptions, default None = off): every result dict gains 'blurred' -- None when nothing in the image is
         to be blurred, otherwise the bytes of the file separate_detections_into_folders.py --category_names_to_blur writes
         for it: a COPY of the resident image is blurred (mdhip_blur_regions) and encoded whole on the device; the pixels
-        detection and crops= read are not changed, and crops are cut from the unblurred image."""
+        detection and crops= read are not changed, and crops are cut from the unblurred image.
+        preview (a preview.PreviewOptions, default None = off): every result dict gains 'preview', a pair (bytes or None,
+        leg) -- the file visualize_detector_output.py writes for the image (blurred if asked, resized with Pillow's LANCZOS
+        filter, boxes and labels drawn), made on the device from the resident pixels (mdhip_blur_regions on a copy,
+        mdhip_resample_lanczos, mdhip_draw_ops, mdhip_jpeg_encode); leg is 'gpu', 'host' (PIL saved or rendered it) or
+        'skipped' (no file).  The resident pixels are not changed."""
         if not isinstance(img_original, list):
             raise ValueError('img_original must be a list for batch processing')
         if len(img_original) == 0:
@@ -284,15 +291,15 @@ class HIPDetector:
             try:
                 for start in range(0, len(items), self.max_batch):
                     self._process_batch_group(items[start:start + self.max_batch], results,
-                                              detection_threshold, augment, verbose, crops, blur)
+                                              detection_threshold, augment, verbose, crops, blur, preview)
             except Exception as e:
                 print('Warning: batch inference failed for shape {}: {}'.format(shape, str(e)))
                 for original_idx, _, current_id in items:
                     results[original_idx] = {'file': current_id, 'detections': None, 'failure': FAILURE_INFER}
-        return self._crops_everywhere(results, crops, blur)
+        return self._crops_everywhere(results, crops, blur, preview)
 
     @staticmethod
-    def _crops_everywhere(results, crops, blur=None):
+    def _crops_everywhere(results, crops, blur=None, preview=None):
         """an image that failed has no crops and no blurred copy, as the reference's second pass gives it none"""
         if crops is not None:
             for r in results:
@@ -302,7 +309,40 @@ class HIPDetector:
             for r in results:
                 if r is not None:
                     r.setdefault('blurred', None)
+        if preview is not None:
+            for r in results:
+                if r is not None:
+                    r.setdefault('preview', (None, 'skipped'))
         return results
+
+    def _add_preview(self, group_items, tensors, results, preview, stream=0):
+        """'preview' of the results of one group: tensors[i] holds the pixels of group_items[i] on the device.  One blur,
+        one resample, one drawing and one encoder call and one read-back for the group.  An image that came already
+        letterboxed has its source pixels on the host only: PIL renders it there (preview.preview_file_of_host_image)."""
+        from . import preview as V
+        entries, where = [], []
+        for (original_idx, info, current_id), t in zip(group_items, tensors):
+            r = results[original_idx]
+            if r is None or not V.is_rendered(r, preview):
+                if r is not None:
+                    r['preview'] = (None, 'skipped')
+                    self.preview_counts['skipped'] += 1
+                continue
+            if isinstance(info['img_processed'], LetterboxSpec):
+                hh, ww = info['img_original'].shape[:2]
+                entries.append((t, ww, hh, current_id, r['detections']))
+                where.append(original_idx)
+            else:
+                data = V.preview_file_of_host_image(np.asarray(info['img_original']), current_id, r['detections'], preview)
+                r['preview'] = (data, 'host' if data is not None else 'skipped')
+                self.preview_counts[r['preview'][1]] += 1
+        if not entries:
+            return
+        out, counts = V.previews_of_device_images(self._ctx, entries, preview, stream=stream)
+        for original_idx, pair in zip(where, out):
+            results[original_idx]['preview'] = pair
+        for key, v in counts.items():
+            self.preview_counts[key] += v
 
     def _add_blur(self, group_items, tensors, results, blur, stream=0):
         """'blurred' of the results of one group: tensors[i] holds the pixels of group_items[i] on the device.  One blur call,
@@ -491,7 +531,7 @@ class HIPDetector:
                 json.dump({'fp8_scales': [float(sc) for sc, _, _ in self._ctx.fp8_scales()]}, f)
             os.replace(tmp, self._fp8_scales_file)
 
-    def _process_batch_group(self, group_items, results, detection_threshold, augment, verbose, crops=None, blur=None):
+    def _process_batch_group(self, group_items, results, detection_threshold, augment, verbose, crops=None, blur=None, preview=None):
         """reference pytorch_detector.py:1257-1426 with the device work in libmdhip.so"""
         if len(group_items) == 0:
             return
@@ -501,7 +541,7 @@ class HIPDetector:
         ctx = self._ctx
         images, hold = self._reconstruct_jpegs(images)       # (`hold` keeps the device images alive until the NMS has returned)
         tensors = None
-        if crops is not None or blur is not None:
+        if crops is not None or blur is not None or preview is not None:
             # every source image on the device exactly once, where the encoder can still address it: host arrays that
             # mdhip_preprocess would stage internally are uploaded here and passed as device pointers
             import torch
@@ -533,6 +573,8 @@ class HIPDetector:
             self._add_crops(group_items, tensors, results, crops)
         if blur is not None:
             self._add_blur(group_items, tensors, results, blur)
+        if preview is not None:
+            self._add_preview(group_items, tensors, results, preview)
 
     # -----------------------------------------------------------------------------------
     def generate_detections_for_tiles(self, img_original, tile_origins, tile_size, tile_ids=None,
@@ -665,7 +707,7 @@ class HIPDetector:
                             'consumed': [None, None], 'count': 0, 'crop_owner': [None, None]}
         return self._pl
 
-    def _submit_group(self, group_items, detection_threshold, augment=False, crops=None, blur=None):
+    def _submit_group(self, group_items, detection_threshold, augment=False, crops=None, blur=None, preview=None):
         pl = self._pipeline()
         torch = pl['torch']
         h, w = group_items[0][1]['img_processed'].shape[:2]
@@ -756,9 +798,9 @@ class HIPDetector:
             done.record(nms_s)
             pl['nms_done'][nms_slot] = done
         handle = {'items': group_items, 'h': h, 'w': w, 'slot': nms_slot, 'copied': pl['copied'][k], 'images': images}
-        if crops is not None or blur is not None:
+        if crops is not None or blur is not None or preview is not None:
             # the pixels stay in staging buffer k until the crops are encoded (_collect_group): views of it, per image
-            handle['crops'], handle['blur'] = crops, blur
+            handle['crops'], handle['blur'], handle['preview'] = crops, blur, preview
             handle['k'], handle['consumed'] = k, ev
             pl['crop_owner'][k] = handle
             handle['tensors'] = [stage[rgb_offs[i]:rgb_offs[i] + int(np.prod(im.shape))] if i in rgb_offs
@@ -781,6 +823,8 @@ class HIPDetector:
                         self._add_crops(handle['items'], handle['tensors'], results, handle['crops'], stream=crop_s.cuda_stream)
                     if handle['blur'] is not None:
                         self._add_blur(handle['items'], handle['tensors'], results, handle['blur'], stream=crop_s.cuda_stream)
+                    if handle['preview'] is not None:
+                        self._add_preview(handle['items'], handle['tensors'], results, handle['preview'], stream=crop_s.cuda_stream)
                 finally:
                     # While this group owned staging buffer k no other group could take it (_submit_group gives a later one a
                     # tensor of its own).  From here on the buffer may be reused: its `consumed` event moves behind the
@@ -793,7 +837,7 @@ class HIPDetector:
                             pl['consumed'][handle['k']] = ev
 
     def start_batch(self, img_original, image_id, detection_threshold=0.00001, image_size=None, augment=False,
-                    verbose=False, crops=None, blur=None):
+                    verbose=False, crops=None, blur=None, preview=None):
         """Enqueues a batch; returns a ticket for finish_batch().  At most two tickets may be outstanding.
         Same arguments as generate_detections_one_batch (augment = yolov5's three-pass augmented inference)."""
         if self._ctx is None:
@@ -810,7 +854,7 @@ class HIPDetector:
         pending = None
         for ci, chunk in enumerate(chunks):
             try:
-                handle = self._submit_group(chunk, detection_threshold, augment, crops, blur)
+                handle = self._submit_group(chunk, detection_threshold, augment, crops, blur, preview)
                 if ci == len(chunks) - 1:
                     pending = handle                     # the last group stays in flight
                 else:
@@ -819,7 +863,7 @@ class HIPDetector:
                 print('Warning: batch inference failed for shape {}: {}'.format(chunk[0][1]['img_processed'].shape, str(e)))
                 for original_idx, _, current_id in chunk:
                     results[original_idx] = {'file': current_id, 'detections': None, 'failure': FAILURE_INFER}
-        return {'results': results, 'pending': pending, 'threshold': detection_threshold, 'crops': crops, 'blur': blur}
+        return {'results': results, 'pending': pending, 'threshold': detection_threshold, 'crops': crops, 'blur': blur, 'preview': preview}
 
     def batch_inputs_consumed(self, ticket):
         """Blocks until the host images of the ticket's in-flight group have been copied to the device
@@ -838,16 +882,16 @@ class HIPDetector:
                 for original_idx, _, current_id in handle['items']:
                     results[original_idx] = {'file': current_id, 'detections': None, 'failure': FAILURE_INFER}
             ticket['pending'] = None
-        return self._crops_everywhere(results, ticket.get('crops'), ticket.get('blur'))
+        return self._crops_everywhere(results, ticket.get('crops'), ticket.get('blur'), ticket.get('preview'))
 
     # -----------------------------------------------------------------------------------
     def generate_detections_one_image(self, img_original, image_id='unknown', detection_threshold=0.00001,
-                                      image_size=None, augment=False, verbose=False, crops=None, blur=None):
+                                      image_size=None, augment=False, verbose=False, crops=None, blur=None, preview=None):
         """reference pytorch_detector.py:1428-1478"""
         if isinstance(img_original, dict):
             res = self.generate_detections_one_batch([img_original], None, detection_threshold,
-                                                     image_size, augment, verbose, crops=crops, blur=blur)
+                                                     image_size, augment, verbose, crops=crops, blur=blur, preview=preview)
         else:
             res = self.generate_detections_one_batch([img_original], [image_id], detection_threshold,
-                                                     image_size, augment, verbose, crops=crops, blur=blur)
+                                                     image_size, augment, verbose, crops=crops, blur=blur, preview=preview)
         return res[0]

@@ -315,6 +315,47 @@ class HipContext:
         self._check(self.lib.mdhip_blur_regions(self.h, C.cast(p, C.POINTER(C.c_void_p)), ws, hs, pt, n, ri, rc4, m,
                                                 C.c_float(float(radius)), C.c_void_p(stream)), 'mdhip_blur_regions')
 
+    def resample_lanczos(self, src_ptrs, src_sizes, src_pitches, dst_ptrs, dst_sizes, dst_pitches, stream=0):
+        """
+        Pillow's Image.resize(size, LANCZOS) of device images into device images, bit for bit (include/mdhip.h:
+        mdhip_resample_lanczos).  Per image the device address of an RGB uint8 image, its (width, height) and its bytes a
+        row, for sources and destinations.  One launch per pass for all images.  Only enqueues.
+        """
+        n = len(src_ptrs)
+        if not (len(src_sizes) == len(src_pitches) == len(dst_ptrs) == len(dst_sizes) == len(dst_pitches) == n):
+            raise ValueError('one entry per image is needed in every list')
+        if n == 0:
+            return
+
+        def arrays(ptrs, sizes, pitches):
+            return ((C.c_void_p * n)(*[int(v) for v in ptrs]), (C.c_int32 * n)(*[int(v[0]) for v in sizes]),
+                    (C.c_int32 * n)(*[int(v[1]) for v in sizes]), (C.c_int64 * n)(*[int(v) for v in pitches]))
+        sp, sw, sh, st = arrays(src_ptrs, src_sizes, src_pitches)
+        dp, dw, dh, dt = arrays(dst_ptrs, dst_sizes, dst_pitches)
+        self._check(self.lib.mdhip_resample_lanczos(self.h, C.cast(sp, C.POINTER(C.c_void_p)), sw, sh, st, n,
+                                                    C.cast(dp, C.POINTER(C.c_void_p)), dw, dh, dt, C.c_void_p(stream)),
+                    'mdhip_resample_lanczos')
+
+    def draw_ops(self, ptrs, sizes, pitches, op_image, ops, patches_ptr=0, patch_bytes=0, stream=0):
+        """
+        Applies each device image's ordered list of drawing operations in place, in one launch (include/mdhip.h:
+        mdhip_draw_ops).  op_image: per operation the index of its image; ops: rows of 8 int32 (a solid rectangle or the
+        paste of a patch); patches_ptr / patch_bytes: the packed DEVICE buffer the patch operations point into.  Only enqueues.
+        """
+        n, m = len(ptrs), len(ops)
+        if not (len(sizes) == len(pitches) == n) or len(op_image) != m:
+            raise ValueError('ptrs, sizes and pitches must have one entry per image, op_image and ops one per operation')
+        if m == 0:
+            return
+        p = (C.c_void_p * n)(*[int(v) for v in ptrs])
+        ws = (C.c_int32 * n)(*[int(v[0]) for v in sizes])
+        hs = (C.c_int32 * n)(*[int(v[1]) for v in sizes])
+        pt = (C.c_int64 * n)(*[int(v) for v in pitches])
+        oi = (C.c_int32 * m)(*[int(v) for v in op_image])
+        flat = (C.c_int32 * (8 * m))(*[int(v) for q in ops for v in q])
+        self._check(self.lib.mdhip_draw_ops(self.h, C.cast(p, C.POINTER(C.c_void_p)), ws, hs, pt, n, oi, flat, m,
+                                            C.c_void_p(int(patches_ptr) or None), int(patch_bytes), C.c_void_p(stream)), 'mdhip_draw_ops')
+
     def forward(self, n, h, w, stream=0):
         self._check(self.lib.mdhip_forward(self.h, int(n), int(h), int(w), C.c_void_p(stream)), 'mdhip_forward')
 

@@ -55,6 +55,8 @@ SYMBOLS = {
     'mdjpeg_blur_regions_chunked': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int,
                                               C.c_float, C.c_int]),
     'mdjpeg_blur_weights': (C.c_int, [C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    'mdjpeg_resample': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64]),
+    'mdjpeg_draw': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int64]),
     'mdjpeg_version': (C.c_char_p, []),
 }
 
@@ -309,6 +311,44 @@ def blur_regions(rgb, rects, radius, lds_bytes=None):
     if lds_bytes is None:
         return lib.mdjpeg_blur_regions(rgb.ctypes.data, w, h, pitch, flat, n, float(radius))
     return lib.mdjpeg_blur_regions_chunked(rgb.ctypes.data, w, h, pitch, flat, n, float(radius), int(lds_bytes))
+
+
+def _rgb_rows(rgb, writeable):
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.strides[1:] != (3, 1) or (writeable and not rgb.flags.writeable):
+        raise ValueError('an H x W x 3 uint8 array with contiguous rows is needed{}'.format(' (writeable)' if writeable else ''))
+    h, w = rgb.shape[:2]
+    return w, h, rgb.strides[0] if h > 1 else w * 3
+
+
+def resample_lanczos(rgb, size, out=None):
+    """
+    Pillow's Image.resize(size, LANCZOS) of an H x W x 3 uint8 array, bit for bit (mdjpeg_resample: the host model of the GPU
+    resize).  size: (width, height); rows of `rgb` and of `out` may be strided (views of wider arrays).  Returns the new array.
+    """
+    w, h, pitch = _rgb_rows(rgb, False)
+    dw, dh = int(size[0]), int(size[1])
+    if out is None:
+        out = np.empty((dh, dw, 3), np.uint8)
+    ow, oh, opitch = _rgb_rows(out, True)
+    if (ow, oh) != (dw, dh):
+        raise ValueError('out is {} x {}, not {} x {}'.format(ow, oh, dw, dh))
+    rc = load().mdjpeg_resample(rgb.ctypes.data, w, h, pitch, out.ctypes.data, dw, dh, opitch)
+    if rc != MDJPEG_OK:
+        raise ValueError('mdjpeg_resample returned {} for {} x {} -> {} x {}'.format(rc, w, h, dw, dh))
+    return out
+
+
+def draw_ops(rgb, ops, patches=b''):
+    """
+    Applies drawing operations (rows of 8 int32: include/mdhip.h mdhip_draw_ops) to an H x W x 3 uint8 array IN PLACE
+    (mdjpeg_draw: the host model of the GPU drawing).  patches: the bytes the patch operations point into.  Returns the
+    library's code.
+    """
+    w, h, pitch = _rgb_rows(rgb, True)
+    flat = np.ascontiguousarray(np.asarray(ops, dtype=np.int32).reshape(-1, 8))
+    pbuf = np.frombuffer(bytes(patches), np.uint8) if not isinstance(patches, np.ndarray) else np.ascontiguousarray(patches, np.uint8)
+    return load().mdjpeg_draw(rgb.ctypes.data, w, h, pitch, flat.ctypes.data_as(C.POINTER(C.c_int32)), len(flat),
+                              pbuf.ctypes.data if pbuf.size else None, pbuf.size)
 
 
 def blur_weights(radius):

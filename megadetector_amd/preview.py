@@ -1,0 +1,539 @@
+"""
+Annotated preview copies, as the reference writes them (visualization/visualize_detector_output.py _render_image: open the
+file again, optionally blur_detections, visualization_utils.resize_image to 1000 pixels wide with Pillow's LANCZOS filter,
+render_detection_bounding_boxes, Image.save to anno_<name>), from an image that is in device memory already: the GPU blurs a
+copy (HipContext.blur_regions), resamples it (HipContext.resample_lanczos, Pillow's arithmetic bit for bit), draws the boxes
+and their labels (HipContext.draw_ops) and encodes the result (HipContext.jpeg_encode); the host puts the file around the
+scan (jpeg_host.jfif_file).  No second read or decode of the source file, no resample and no encode on the host.
+
+What the reference draws is restated here as a PLAN (render_plan): an ordered list of solid rectangles and of small label
+patches that PIL rasterises on the host, once per distinct label.  Whatever the plan does not restate -- a box thinner than
+its own outline, ink that may leave a label's patch, a confidence of None -- sends the image to the HOST LEG
+(preview_file_of_host_image), which draws with PIL's own calls in the reference's order, so a run writes the same files
+either way.
+
+Two deliberate differences from the reference script: the HTML index is not written, and an image whose resize target is not
+positive is skipped and counted (the reference asserts, which its caller reports as a rendering failure of that image: no
+file either).  Image.save(path) copies no EXIF block, and neither do these files; what Pillow does carry from the opened
+file into the saved one through Image.info -- a JPEG's COM segment, a PNG's ICC profile -- is not written, as for the crops.
+"""
+
+import os
+
+from . import jpeg_host
+from .crops import is_jpeg_name, output_order, _pil_file
+
+DEFAULT_PREVIEW_CONFIDENCE_THRESHOLD = 0.15     # visualize_detector_output.py:177 confidence_threshold=0.15
+DEFAULT_PREVIEW_WIDTH = 1000                    # visualize_detector_output.py:179 output_image_width=1000
+DEFAULT_BOX_THICKNESS = 4                       # visualization_utils.py:64
+DEFAULT_LABEL_FONT_SIZE = 16                    # visualization_utils.py:65
+DEFAULT_LABEL_FONT = 'arial.ttf'                # visualization_utils.py:66
+DEFAULT_PREVIEW_QUALITY = 75                    # visualize_detector_output.py:159 image.save(path): Pillow's JPEG default
+
+# visualization_utils.py:72-96 DEFAULT_COLORS: the colour of a box is entry int(category) % 126, so the order is behaviour
+PREVIEW_COLORS = (
+    'AliceBlue Red RoyalBlue Gold Chartreuse Aqua Azure Beige Bisque BlanchedAlmond BlueViolet BurlyWood CadetBlue AntiqueWhite '
+    'Chocolate Coral CornflowerBlue Cornsilk Crimson Cyan DarkCyan DarkGoldenRod DarkGrey DarkKhaki DarkOrange DarkOrchid '
+    'DarkSalmon DarkSeaGreen DarkTurquoise DarkViolet DeepPink DeepSkyBlue DodgerBlue FireBrick FloralWhite ForestGreen Fuchsia '
+    'Gainsboro GhostWhite GoldenRod Salmon Tan HoneyDew HotPink IndianRed Ivory Khaki Lavender LavenderBlush LawnGreen '
+    'LemonChiffon LightBlue LightCoral LightCyan LightGoldenRodYellow LightGray LightGrey LightGreen LightPink LightSalmon '
+    'LightSeaGreen LightSkyBlue LightSlateGray LightSlateGrey LightSteelBlue LightYellow Lime LimeGreen Linen Magenta '
+    'MediumAquaMarine MediumOrchid MediumPurple MediumSeaGreen MediumSlateBlue MediumSpringGreen MediumTurquoise '
+    'MediumVioletRed MintCream MistyRose Moccasin NavajoWhite OldLace Olive OliveDrab Orange OrangeRed Orchid PaleGoldenRod '
+    'PaleGreen PaleTurquoise PaleVioletRed PapayaWhip PeachPuff Peru Pink Plum PowderBlue Purple RosyBrown Aquamarine '
+    'SaddleBrown Green SandyBrown SeaGreen SeaShell Sienna Silver SkyBlue SlateBlue SlateGray SlateGrey Snow SpringGreen '
+    'SteelBlue GreenYellow Teal Thistle Tomato Turquoise Violet Wheat White WhiteSmoke Yellow YellowGreen').split()
+
+OP_RECT, OP_PATCH = 0, 1                        # csrc/resample.h MD_DRAW_RECT / MD_DRAW_PATCH
+_COORD_LIMIT = 1 << 30                          # operations carry int32 coordinates
+
+
+class PreviewOptions:
+    """which images are rendered and how (defaults: visualize_detector_output's own)"""
+
+    def __init__(self, confidence_threshold=DEFAULT_PREVIEW_CONFIDENCE_THRESHOLD, output_image_width=DEFAULT_PREVIEW_WIDTH,
+                 detections_only=False, preserve_path_structure=False, box_thickness=DEFAULT_BOX_THICKNESS, box_expansion=0,
+                 label_font_size=DEFAULT_LABEL_FONT_SIZE, label_font=DEFAULT_LABEL_FONT, box_sort_order='confidence',
+                 blur_categories=None, quality=DEFAULT_PREVIEW_QUALITY, output_threshold=None):
+        # visualize_detector_output.py:279-280
+        if not 0 <= confidence_threshold <= 1:
+            raise ValueError('confidence threshold {!r} is outside 0 .. 1'.format(confidence_threshold))
+        self.confidence_threshold = confidence_threshold
+        self.output_image_width = -1 if output_image_width is None else int(output_image_width)
+        self.detections_only = bool(detections_only)
+        self.preserve_path_structure = bool(preserve_path_structure)
+        label_font_size = DEFAULT_LABEL_FONT_SIZE if label_font_size is None else label_font_size      # visualization_utils.py:645-646
+        # visualization_utils.py:996-997
+        if box_thickness == 0 or label_font_size == 0:
+            raise ValueError('box thickness and label font size cannot be zero')
+        if box_thickness < 0 or box_expansion < 0 or label_font_size < 0:
+            raise ValueError('box thickness, box expansion and label font size cannot be negative')
+        self.box_thickness, self.box_expansion = box_thickness, box_expansion
+        self.label_font_size = label_font_size
+        self.label_font = DEFAULT_LABEL_FONT if label_font is None else label_font
+        if box_sort_order not in (None, 'confidence', 'reverse_confidence'):
+            raise ValueError('Unrecognized sorting scheme {}'.format(box_sort_order))    # visualization_utils.py:671
+        self.box_sort_order = box_sort_order
+        if isinstance(blur_categories, str):
+            blur_categories = [s.strip() for s in blur_categories.split(',') if s.strip()]
+        self.blur_categories = tuple(blur_categories) if blur_categories else None
+        self.quality = jpeg_host.check_quality(quality)
+        # the confidence threshold of the results file, as for blur.BlurOptions: the reference renders what that file holds
+        self.output_threshold = output_threshold
+
+    def blur_category_ids(self, label_map=None):
+        """visualize_detector_output.py:118-124: the ids whose NAME is one to blur (a name no category has selects nothing)"""
+        if self.blur_categories is None:
+            return set()
+        return {k for k, v in _label_map(label_map).items() if v in self.blur_categories}
+
+
+def _label_map(label_map):
+    if label_map is None:
+        from .constants import DEFAULT_DETECTOR_LABEL_MAP
+        return DEFAULT_DETECTOR_LABEL_MAP
+    return label_map
+
+
+NO_LABELS = 'no_detection_labels'               # visualize_detector_output.py:282-285: boxes without labels
+
+
+# ---- which images, which size, which name ----------------------------------------------------------------------------------
+
+def target_size(width, height, target_width):
+    """
+    visualization_utils.resize_image(image, target_width) (:367-417): the size the image is resized to, (width, height) itself
+    when there is nothing to resize, None for a target that is not positive (the reference asserts).
+    """
+    if target_width is None or target_width == -1:
+        return width, height
+    aspect_ratio = width / height                                   # :385
+    target_height = int(target_width / aspect_ratio)                # :389
+    if target_width == width and target_height == height:           # :403
+        return width, height
+    if not (target_width > 0 and target_height > 0):                # :416
+        return None
+    return target_width, target_height
+
+
+def output_name(image_file, options):
+    """visualize_detector_output.py:150-156: the path below the output folder; image_file is relative to the image folder"""
+    if options.preserve_path_structure:
+        if os.path.isabs(image_file):
+            raise ValueError("Can't preserve paths when operating on absolute paths")
+        return image_file
+    for char in ['/', '\\', ':']:
+        image_file = image_file.replace(char, '~')
+    return 'anno_' + image_file
+
+
+def file_detections(detections, options):
+    """the detections as the results file holds them (crops.output_order): what the reference script reads"""
+    return output_order(detections, options.output_threshold)
+
+
+def is_rendered(result, options):
+    """visualize_detector_output.py:79-90: not an image that failed, and not one below the threshold with detections_only"""
+    if result.get('failure') is not None or result.get('detections') is None:
+        return False
+    confs = [d['conf'] for d in file_detections(result['detections'], options)]
+    max_conf = max(confs) if confs else 0.0                          # ct_utils.get_max_conf
+    return not (max_conf < options.confidence_threshold and options.detections_only)
+
+
+def rectangles_to_blur(detections, width, height, options, label_map=None):
+    """visualize_detector_output.py:126-131: blur_detections' rectangles for the boxes of the categories to blur at or above
+    the threshold, in the order of the file"""
+    from .blur import blur_rectangle
+    ids = options.blur_category_ids(label_map)
+    rects = [blur_rectangle(d['bbox'], width, height) for d in file_detections(detections, options)
+             if d['conf'] >= options.confidence_threshold and d['category'] in ids]
+    return [r for r in rects if r is not None]
+
+
+# ---- what is drawn ---------------------------------------------------------------------------------------------------------
+
+def resolve_sizes(options, im_width):
+    """visualization_utils.py:1002-1013: thickness, expansion and font size in pixels; a value in (0, 1) is a fraction of the
+    image width"""
+    thickness, expansion, font_size = options.box_thickness, options.box_expansion, options.label_font_size
+    if 0 < thickness < 1:
+        thickness = max(1, round(thickness * im_width))
+    if 0 < expansion < 1:
+        expansion = round(expansion * im_width)
+    if 0 < font_size < 1:
+        font_size = max(1, round(font_size * im_width))
+    return int(thickness), int(expansion), int(font_size)
+
+
+_FONTS = {}
+
+
+def load_font(label_font, label_font_size):
+    """visualization_utils._load_font (:895-915): the named font, else Pillow's default at that size, else its default"""
+    key = (label_font, label_font_size)
+    if key not in _FONTS:
+        from PIL import ImageFont
+        font = None
+        try:
+            font = ImageFont.truetype(label_font, label_font_size)
+        except Exception:
+            font = None
+        if font is None:
+            try:
+                font = ImageFont.load_default(label_font_size)
+            except Exception:
+                font = None
+        if font is None:
+            font = ImageFont.load_default()
+        _FONTS[key] = font
+    return _FONTS[key]
+
+
+def text_size(font, s):
+    """visualization_utils.get_text_size (:865-892): right and bottom of the text's box, NOT its width and height"""
+    try:
+        _, _, w, h = font.getbbox(s)
+    except Exception:
+        w, h = font.getsize(s)
+    return w, h
+
+
+def box_color(category):
+    """visualization_utils.py:984-988 (name, (r, g, b))"""
+    from PIL import ImageColor
+    name = PREVIEW_COLORS[1] if category is None else PREVIEW_COLORS[int(category) % len(PREVIEW_COLORS)]
+    return name, ImageColor.getrgb(name)[:3]
+
+
+def drawn_detections(detections, options):
+    """render_detection_bounding_boxes :664-684: the order the boxes are drawn in -- ascending confidence, so that the most
+    confident box lands on top (a stable sort: equal confidences keep the file's order) -- and only those at or above the
+    threshold (a confidence of None is always drawn)"""
+    dets = list(file_detections(detections, options))
+    if options.box_sort_order is not None:
+        dets = sorted(dets, key=lambda d: (d['conf'] is not None, d['conf']), reverse=options.box_sort_order == 'reverse_confidence')
+    return [d for d in dets if d['conf'] is None or d['conf'] >= options.confidence_threshold]
+
+
+def label_string(det, label_map):
+    """render_detection_bounding_boxes :696-703; label_map None: no label"""
+    if label_map is None:
+        return ''
+    label = label_map[det['category']] if det['category'] in label_map else det['category']
+    if det['conf'] is None:
+        return '{}'.format(label)
+    return '{}: {}%'.format(label, round(100 * det['conf']))
+
+
+def box_edges(bbox, width, height, expansion):
+    """draw_bounding_box_on_image :1015-1042: (left, top, right, bottom) of a normalised [x, y, w, h] box as floats, expanded
+    and, only then, clamped to the image"""
+    x1, y1, w_box, h_box = bbox
+    ymin, xmin, ymax, xmax = y1, x1, y1 + h_box, x1 + w_box          # render_detection_bounding_boxes :686-687
+    left, right, top, bottom = xmin * width, xmax * width, ymin * height, ymax * height
+    if expansion > 0:
+        left -= expansion
+        right += expansion
+        top -= expansion
+        bottom += expansion
+        left, right, top, bottom = max(left, 0), max(right, 0), max(top, 0), max(bottom, 0)
+        left, right = min(left, width - 1), min(right, width - 1)
+        top, bottom = min(top, height - 1), min(bottom, height - 1)
+    return left, top, right, bottom
+
+
+def label_box(font, s, left, top, bottom, im_height):
+    """
+    draw_bounding_box_on_image :1052-1131 for ONE label, left- and top-aligned: the padded string, its margin and the filled
+    rectangle (x0, y0, x1, y1 inclusive) the text is drawn into at (x0 + margin, y0 + margin).  Above the box; below it when
+    that leaves the image at the top; inside it when below leaves the image too.
+    """
+    import numpy as np
+    total_height = (1 + 2 * 0.05) * text_size(font, s)[1]           # :1055 (of the string WITHOUT its padding)
+    padded = ' ' + s + ' '
+    text_width, text_height = text_size(font, padded)
+    margin = int(np.ceil(0.05 * text_height))
+    text_bottom = top
+    if (text_bottom - total_height) < 0:
+        text_bottom = bottom + total_height
+        if text_bottom > im_height:
+            text_bottom = top + total_height
+    text_bottom = int(text_bottom)
+    text_left = int(left)
+    return padded, margin, (text_left, (text_bottom - text_height) - (2 * margin), text_left + text_width, text_bottom)
+
+
+class HostLeg(Exception):
+    """the plan does not restate what the reference draws for this image: PIL draws it (preview_file_of_host_image)"""
+
+
+class RenderFailure(Exception):
+    """the reference's own drawing raises for this image: it gets no file (visualize_detector_output.py:162-165)"""
+
+
+def _check_rectangle(left, top, right, bottom):
+    # ImageDraw.rectangle refuses reversed corners (Pillow's _draw_rectangle, on the floats)
+    if right < left:
+        raise RenderFailure('x1 must be greater than or equal to x0')
+    if bottom < top:
+        raise RenderFailure('y1 must be greater than or equal to y0')
+    if not all(abs(v) < _COORD_LIMIT for v in (left, top, right, bottom)):
+        raise HostLeg('a box edge beyond 2^30 pixels')
+
+
+def outline_ops(left, top, right, bottom, thickness, rgb):
+    """
+    ImageDraw.rectangle([(left, top), (right, bottom)], outline=color, width=thickness) as four solid rectangles, inward from
+    int(left), int(top), int(right), int(bottom) inclusive: the top and bottom bars over the whole width, the side bars
+    between them.  Pinned against Pillow for thicknesses 1 .. 5 (tests/test_preview_cpu.py): equal for every box at least
+    2 * thickness pixels wide and high, in and out of the image; a thinner box Pillow draws otherwise -> HostLeg.
+    """
+    _check_rectangle(left, top, right, bottom)
+    x0, y0, x1, y1 = int(left), int(top), int(right), int(bottom)
+    t = thickness
+    if x1 - x0 + 1 < 2 * t or y1 - y0 + 1 < 2 * t:
+        raise HostLeg('a box of {} x {} pixels with an outline of {}'.format(x1 - x0 + 1, y1 - y0 + 1, t))
+    c = rgb[0] | rgb[1] << 8 | rgb[2] << 16
+    return [[OP_RECT, x0, y0, x1, y0 + t - 1, c, 0, 0], [OP_RECT, x0, y1 - t + 1, x1, y1, c, 0, 0],
+            [OP_RECT, x0, y0 + t, x0 + t - 1, y1 - t, c, 0, 0], [OP_RECT, x1 - t + 1, y0 + t, x1, y1 - t, c, 0, 0]]
+
+
+_PATCHES = {}
+
+
+def label_patch(font, font_key, padded, margin, size, color_name):
+    """the label as pixels: an RGB image of `size` filled with the colour, the text in black at (margin, margin) -- what the
+    reference's filled rectangle and draw.text leave in the image.  -> bytes (R G B, 3 * width a row)"""
+    key = (font_key, padded, margin, size, color_name)
+    if key not in _PATCHES:
+        from PIL import Image, ImageDraw
+        if len(_PATCHES) > 4096:
+            _PATCHES.clear()
+        patch = Image.new('RGB', size, color_name)
+        ImageDraw.Draw(patch).text((margin, margin), padded, fill='black', font=font)
+        _PATCHES[key] = patch.tobytes()
+    return _PATCHES[key]
+
+
+class RenderPlan:
+    """ops: rows of 8 int32 in drawing order (include/mdhip.h mdhip_draw_ops), patch offsets into `patches`; labels and
+    order: the label string and the index in the file's list of every drawn detection, in drawing order"""
+
+    def __init__(self):
+        self.ops, self.patches, self.labels, self.order = [], bytearray(), [], []
+        self._offsets = {}
+
+    def add_patch(self, data):
+        if data not in self._offsets:
+            self._offsets[data] = len(self.patches)
+            self.patches += data
+        return self._offsets[data]
+
+
+def render_plan(detections, width, height, options, label_map=None, labels=True):
+    """
+    render_detection_bounding_boxes(detections, image, label_map=..., confidence_threshold, thickness, expansion,
+    label_font_size, label_font, box_sort_order) for an image of width x height (the RESIZED size) as a RenderPlan.
+    labels False: label_map=None of the reference (boxes only).  Raises HostLeg or RenderFailure.
+    """
+    thickness, expansion, font_size = resolve_sizes(options, width)
+    label_map = _label_map(label_map) if labels else None
+    font = None
+    plan = RenderPlan()
+    listed = file_detections(detections, options)
+    for det in drawn_detections(detections, options):
+        if det['conf'] is None:
+            raise HostLeg('a detection without a confidence')
+        if 'classifications' in det and len(det['classifications']) > 0:
+            raise HostLeg('classification labels')
+        try:
+            color_name, rgb = box_color(det['category'])
+        except (TypeError, ValueError) as e:
+            raise RenderFailure(str(e))
+        left, top, right, bottom = box_edges(det['bbox'], width, height, expansion)
+        plan.ops += outline_ops(left, top, right, bottom, thickness, rgb)
+        s = label_string(det, label_map)
+        plan.labels.append(s)
+        plan.order.append(next(i for i, d in enumerate(listed) if d is det))
+        if len(s) == 0:                                                          # :1061
+            continue
+        if font is None:
+            font = load_font(options.label_font, font_size)
+        padded, margin, (x0, y0, x1, y1) = label_box(font, s, left, top, bottom, height)
+        bbox = font.getbbox(padded)
+        if bbox[0] < 0 or bbox[1] < 0:
+            raise HostLeg('ink of {!r} may leave its label'.format(padded))
+        if not all(isinstance(v, int) or float(v).is_integer() for v in (x0, y0, x1, y1)):
+            raise HostLeg('a label of a fractional size')
+        x0, y0, x1, y1 = int(x0), int(y0), int(x1), int(y1)
+        w, h = x1 - x0 + 1, y1 - y0 + 1
+        if w < 1 or h < 1 or w > 32767 or h > 32767:
+            raise HostLeg('a label of {} x {} pixels'.format(w, h))
+        data = label_patch(font, (options.label_font, font_size), padded, margin, (w, h), color_name)
+        plan.ops.append([OP_PATCH, x0, y0, w, h, plan.add_patch(data), 0, 0])
+    return plan
+
+
+def render_with_pil(image, detections, options, label_map=None, labels=True):
+    """the same drawing by PIL's own calls in the reference's order (draw_bounding_box_on_image :990-1137), IN PLACE on a
+    PIL image of the resized size: the host leg.  Raises what PIL raises."""
+    from PIL import ImageDraw
+    width, height = image.size
+    thickness, expansion, font_size = resolve_sizes(options, width)
+    label_map = _label_map(label_map) if labels else None
+    for det in drawn_detections(detections, options):
+        if 'classifications' in det and len(det['classifications']) > 0:
+            raise NotImplementedError('classification labels are not rendered')
+        color_name, _ = box_color(det['category'])
+        draw = ImageDraw.Draw(image)
+        left, top, right, bottom = box_edges(det['bbox'], width, height, expansion)
+        draw.rectangle([(left, top), (right, bottom)], outline=color_name, width=thickness)
+        font = load_font(options.label_font, font_size)
+        s = label_string(det, label_map)
+        if len(s) == 0:
+            continue
+        padded, margin, (x0, y0, x1, y1) = label_box(font, s, left, top, bottom, height)
+        draw.rectangle([(x0, y0), (x1, y1)], fill=color_name)
+        draw.text((x0 + margin, y0 + margin), padded, fill='black', font=font)
+    return image
+
+
+# ---- the two legs -----------------------------------------------------------------------------------------------------------
+
+def preview_file_of_host_image(pixels, name, detections, options, label_map=None):
+    """
+    The host leg, for an image whose pixels are not in device memory or whose drawing the plan does not restate: the
+    reference's steps on a copy of the H x W x 3 uint8 array -- blur (libmdjpeg.so: Pillow's blur), Image.resize(LANCZOS),
+    PIL's drawing -- saved by PIL in the format of `name` at options.quality.  None for an image that gets no file: a resize
+    target that is not positive, or drawing that raises.
+    """
+    import numpy as np
+    from PIL import Image
+    height, width = pixels.shape[:2]
+    size = target_size(width, height, options.output_image_width)
+    if size is None:
+        return None
+    labels = label_map != NO_LABELS
+    label_map = None if not labels else label_map
+    copy = np.array(pixels, dtype=np.uint8, order='C')
+    rects = rectangles_to_blur(detections, width, height, options, label_map)
+    if rects:
+        rc = jpeg_host.blur_regions(copy, rects, 40)                 # visualization_utils.py:497 blur_radius=40
+        if rc != jpeg_host.MDJPEG_OK:
+            raise RuntimeError('mdjpeg_blur_regions returned {}'.format(rc))
+    image = Image.fromarray(copy)
+    if size != (width, height):
+        image = image.resize(size, Image.LANCZOS)
+    try:
+        render_with_pil(image, detections, options, label_map, labels)
+    except Exception as e:
+        print('Warning: error rendering {}: {}'.format(name, str(e)))
+        return None
+    return _pil_file(np.asarray(image), name, options.quality)
+
+
+def previews_of_device_images(ctx, entries, options, label_map=None, stream=0):
+    """
+    The previews of a batch of images that lie in device memory.  entries: [(tensor, width, height, name, detections)],
+    tensor a flat uint8 torch tensor of height * width * 3 bytes, which is NOT changed; name the output name (its extension
+    picks the format).  Returns ([(bytes or None, leg) per entry], counts), leg 'gpu', 'host' or 'skipped': for all images
+    together at most ONE blur call (on copies of the images with something to blur), ONE resample call, ONE drawing call and,
+    for the names Pillow maps to JPEG, ONE encoder call (counts['gpu']); for any other extension the rendered pixels are
+    copied back and PIL saves them (counts['host']).  An image the plan hands to the host leg is copied back as it is and
+    PIL renders it (counts['host'] too); one without a file counts as 'skipped'.
+    """
+    import numpy as np
+    import torch
+    counts = {'gpu': 0, 'host': 0, 'skipped': 0}
+    out = [(None, 'skipped')] * len(entries)
+    labels = label_map != NO_LABELS
+    plan_map = None if not labels else label_map
+    jobs, host = [], []                                              # (entry, size, plan, rectangles to blur)
+    for e, (tensor, width, height, name, detections) in enumerate(entries):
+        size = target_size(width, height, options.output_image_width)
+        if size is None:
+            continue
+        try:
+            plan = render_plan(detections, size[0], size[1], options, plan_map, labels)
+        except RenderFailure as err:
+            print('Warning: error rendering {}: {}'.format(name, str(err)))
+            continue
+        except HostLeg:
+            host.append(e)
+            continue
+        jobs.append((e, size, plan, rectangles_to_blur(detections, width, height, options, plan_map)))
+    if not entries:
+        return out, counts
+    device = entries[0][0].device
+    ext = torch.cuda.ExternalStream(stream, device=device) if stream else torch.cuda.current_stream(device)
+    for e in host:
+        tensor, width, height, name, detections = entries[e]
+        with torch.cuda.stream(ext):
+            pixels = tensor.cpu().numpy().reshape(height, width, 3)
+        data = preview_file_of_host_image(pixels, name, detections, options, label_map)
+        out[e] = (data, 'host' if data is not None else 'skipped')
+    if jobs:
+        sizes = [(entries[e][1], entries[e][2]) for e, _, _, _ in jobs]
+        with torch.cuda.stream(ext):
+            # a copy only where the source would be changed: something to blur, or nothing to resize (drawn in place)
+            sources = [entries[e][0].clone() if rects or size == sizes[k] else entries[e][0] for k, (e, size, _, rects) in enumerate(jobs)]
+        blurred = [k for k, job in enumerate(jobs) if job[3]]
+        if blurred:
+            ctx.blur_regions([sources[k].data_ptr() for k in blurred], [sizes[k] for k in blurred], [sizes[k][0] * 3 for k in blurred],
+                             [i for i, k in enumerate(blurred) for _ in jobs[k][3]], [r for k in blurred for r in jobs[k][3]], 40,
+                             stream=ext.cuda_stream)
+        with torch.cuda.stream(ext):
+            rendered = [sources[k] if size == sizes[k] else torch.empty(size[0] * size[1] * 3, dtype=torch.uint8, device=device)
+                        for k, (_, size, _, _) in enumerate(jobs)]
+        resized = [k for k, job in enumerate(jobs) if job[1] != sizes[k]]
+        if resized:
+            ctx.resample_lanczos([sources[k].data_ptr() for k in resized], [sizes[k] for k in resized], [sizes[k][0] * 3 for k in resized],
+                                 [rendered[k].data_ptr() for k in resized], [jobs[k][1] for k in resized], [jobs[k][1][0] * 3 for k in resized],
+                                 stream=ext.cuda_stream)
+        # all patches of the batch in one buffer, a patch once
+        packed, where, op_image, ops = bytearray(), {}, [], []
+        for k, (_, _, plan, _) in enumerate(jobs):
+            for op in plan.ops:
+                if op[0] == OP_PATCH:
+                    data = bytes(plan.patches[op[5]:op[5] + op[3] * op[4] * 3])
+                    if data not in where:
+                        where[data] = len(packed)
+                        packed += data
+                    op = op[:5] + [where[data]] + op[6:]
+                op_image.append(k)
+                ops.append(op)
+        if ops:
+            with torch.cuda.stream(ext):
+                patches = torch.from_numpy(np.frombuffer(bytes(packed) or b'\0', np.uint8).copy()).to(device)
+            ctx.draw_ops([t.data_ptr() for t in rendered], [job[1] for job in jobs], [job[1][0] * 3 for job in jobs], op_image, ops,
+                         patches.data_ptr(), len(packed), stream=ext.cuda_stream)
+        jpeg = [k for k, (e, _, _, _) in enumerate(jobs) if is_jpeg_name(entries[e][3])]
+        if jpeg:
+            from .crops import encode_windows
+            files = encode_windows(ctx, [rendered[k].data_ptr() for k in jpeg], [jobs[k][1][0] * 3 for k in jpeg],
+                                   [(0, 0) + tuple(jobs[k][1]) for k in jpeg], options.quality, ext.cuda_stream)
+            for k, data in zip(jpeg, files):
+                out[jobs[k][0]] = (data, 'gpu')
+        for k, (e, size, _, _) in enumerate(jobs):
+            if out[e][0] is None:
+                with torch.cuda.stream(ext):
+                    pixels = rendered[k].cpu().numpy().reshape(size[1], size[0], 3)
+                out[e] = (_pil_file(pixels, entries[e][3], options.quality), 'host')
+    for _, leg in out:
+        counts[leg] += 1
+    return out, counts
+
+
+def write_preview(preview_folder, relative_name, data):
+    """writes one preview below preview_folder; returns the path"""
+    path = os.path.join(preview_folder, relative_name).replace('\\', '/')
+    os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    with open(path, 'wb') as f:
+        f.write(data)
+    return path
+
+
+__all__ = ['HostLeg', 'NO_LABELS', 'PreviewOptions', 'RenderFailure', 'RenderPlan', 'box_edges', 'drawn_detections', 'is_rendered',
+           'label_box', 'label_string', 'output_name', 'outline_ops', 'preview_file_of_host_image', 'previews_of_device_images',
+           'rectangles_to_blur', 'render_plan', 'render_with_pil', 'resolve_sizes', 'target_size', 'write_preview']

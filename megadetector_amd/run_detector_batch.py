@@ -42,6 +42,7 @@ from .constants import FAILURE_IMAGE_OPEN, FAILURE_INFER, DEFAULT_OUTPUT_CONFIDE
 from .constants import DEFAULT_DETECTOR_LABEL_MAP
 from . import crops as crops_mod
 from . import blur as blur_mod
+from . import preview as preview_mod
 from .jpeg_host import ScanFailure
 
 # reference run_detector_batch.py:86-119
@@ -243,6 +244,46 @@ class _BlurWriter:
             blur_mod.write_blurred(self.folder, rel, data)
             self.counts['files'] += 1
             self.counts['gpu' if from_detector else 'host'] += 1
+
+
+# --------------------------------------------------------------------------------------------
+# annotated previews (reference visualization/visualize_detector_output.py, written while the images are at hand)
+# --------------------------------------------------------------------------------------------
+#: previews of the most recent run in this process: 'files' written, of them 'gpu' = made by the detector from the image in
+#: device memory (preview=), 'host' = rendered or saved by PIL (a detector without preview=, pixels that never were in device
+#: memory, an extension that is not JPEG, drawing the plan does not restate); 'skipped' = images without a file (failed,
+#: below the threshold with detections_only, a resize target that is not positive, drawing that raises)
+last_preview_counts = {}
+
+
+class _PreviewWriter:
+    """writes the annotated preview of an image to <preview folder>/anno_<name> (or <relative path>), BEFORE its result is
+    handed on (as _CropWriter does, and for the same reason)"""
+
+    def __init__(self, folder, options, base):
+        self.folder, self.options, self.base = folder, options, base
+        self.counts = {'files': 0, 'gpu': 0, 'host': 0, 'skipped': 0}
+
+    def detector_kw(self, detector):
+        return {'preview': self.options} if getattr(detector, 'supports_preview', False) else {}
+
+    _pixels = _CropWriter._pixels
+
+    def write(self, results, images):
+        for i, r in enumerate(results):
+            data, leg = r.pop('preview', (None, None))
+            rel = _crop_relative_name(r['file'], self.base)
+            if leg is None and preview_mod.is_rendered(r, self.options):
+                # a detector without preview=: the host leg
+                data = preview_mod.preview_file_of_host_image(self._pixels(images[i] if images else None, r['file']), rel,
+                                                              r['detections'], self.options)
+                leg = 'host'
+            if data is None:
+                self.counts['skipped'] += 1
+                continue
+            preview_mod.write_preview(self.folder, preview_mod.output_name(rel, self.options), data)
+            self.counts['files'] += 1
+            self.counts[leg] += 1
 
 
 class _Writers:
@@ -682,7 +723,11 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
                                 crop_folder=None, crop_confidence_threshold=0.1, crop_expansion=0, crop_quality=95,
                                 crop_categories=None, crop_base=None,
                                 blur_folder=None, blur_categories=('person',), blur_confidence_threshold=None, blur_radius=40,
-                                blur_quality=85, blur_base=None):
+                                blur_quality=85, blur_base=None,
+                                preview_folder=None, preview_width=1000, preview_confidence_threshold=0.15,
+                                preview_detections_only=False, preview_preserve_paths=False, preview_box_thickness=4,
+                                preview_box_expansion=0, preview_label_font_size=16, preview_label_font='arial.ttf',
+                                preview_blur_categories=None, preview_quality=75, preview_base=None):
     """
     reference :1062-1439.  `detector` (extra, optional) injects an already constructed detector
     object -- used by run_sharded and by the CPU tests of the loop with a stub detector.
@@ -702,9 +747,15 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
     (Gaussian, blur_radius) and saved at blur_quality; no other image is written.  A detector with blur= (HIPDetector)
     blurs and encodes a copy of the image on the GPU; other detectors, and pixels that are not in device memory, go
     through libmdjpeg.so and PIL here.  The results are the same objects as without it.
+    `preview_folder` (extra, default None = off): every image is written to <preview_folder>/anno_<name> as
+    visualization/visualize_detector_output.py writes it -- resized to preview_width with Pillow's LANCZOS filter, the boxes at
+    or above preview_confidence_threshold drawn with their labels, people blurred first with preview_blur_categories -- the
+    name relative to preview_base with slashes, backslashes and colons replaced by ~ (preview_preserve_paths: the relative path itself).  A detector
+    with preview= (HIPDetector) does all of it on the GPU from the resident image; other detectors, and pixels that are not in
+    device memory, go through PIL here.  The results are the same objects as without it.
     Returns the list of per-image result dicts.
     """
-    global verbose, last_crop_counts, last_blur_counts
+    global verbose, last_crop_counts, last_blur_counts, last_preview_counts
     verbose = bool(verbose_output)
     crop_writer = None
     if crop_folder is not None:
@@ -722,6 +773,16 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
             output_threshold=DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD if confidence_threshold is None else confidence_threshold), blur_base)
         last_blur_counts = blur_writer.counts
         crop_writer = blur_writer if crop_writer is None else _Writers([crop_writer, blur_writer])
+    if preview_folder is not None:
+        preview_writer = _PreviewWriter(preview_folder, preview_mod.PreviewOptions(
+            confidence_threshold=preview_confidence_threshold, output_image_width=preview_width,
+            detections_only=preview_detections_only, preserve_path_structure=preview_preserve_paths,
+            box_thickness=preview_box_thickness, box_expansion=preview_box_expansion, label_font_size=preview_label_font_size,
+            label_font=preview_label_font, blur_categories=preview_blur_categories, quality=preview_quality,
+            output_threshold=DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD if confidence_threshold is None else confidence_threshold), preview_base)
+        last_preview_counts = preview_writer.counts
+        crop_writer = preview_writer if crop_writer is None else _Writers(
+            (crop_writer.writers if isinstance(crop_writer, _Writers) else [crop_writer]) + [preview_writer])
     if detector_options is None:
         detector_options = {}
     elif isinstance(detector_options, (list, str)):
@@ -1085,8 +1146,30 @@ def main(argv=None):
                         blur_mod.DEFAULT_BLUR_CONFIDENCE_THRESHOLD))
     ap.add_argument('--blur_radius', type=float, default=None, help='radius of the Gaussian; default 40, as the reference')
     ap.add_argument('--blur_quality', type=int, default=None, help='JPEG quality of the copies; default 85, as the reference')
+    ap.add_argument('--preview_folder', type=str, default=None,
+                    help='write an annotated copy of every image to this folder as anno_<name>, as '
+                         'visualize_detector_output.py does: resized to --preview_width with the LANCZOS filter, boxes and '
+                         'labels drawn; resized, drawn and encoded on the GPU from the image that is resident there')
+    ap.add_argument('--preview_width', type=int, default=None, help='width of the previews; default 1000, -1: no resize')
+    ap.add_argument('--preview_confidence_threshold', type=float, default=None, help='boxes at or above it are drawn; default 0.15')
+    ap.add_argument('--preview_detections_only', action='store_true', help='no preview of an image without such a box')
+    ap.add_argument('--preview_preserve_paths', action='store_true', help='<folder>/<relative path> instead of anno_<name>')
+    ap.add_argument('--preview_box_thickness', type=float, default=None, help='default 4; below 1: a fraction of the width')
+    ap.add_argument('--preview_box_expansion', type=float, default=None, help='default 0; below 1: a fraction of the width')
+    ap.add_argument('--preview_label_font_size', type=float, default=None, help='default 16; below 1: a fraction of the width')
+    ap.add_argument('--preview_label_font', type=str, default=None, help="default arial.ttf; Pillow's default font if not found")
+    ap.add_argument('--preview_blur_categories', type=str, default=None, help='comma-separated category names blurred before drawing')
+    ap.add_argument('--preview_quality', type=int, default=None, help="JPEG quality; default 75, Pillow's own, as the reference")
     ap.add_argument('--verbose', action='store_true')
     args = ap.parse_args(argv)
+    preview_sub = {k: getattr(args, k) for k in ('preview_width', 'preview_confidence_threshold', 'preview_box_thickness',
+                                                 'preview_box_expansion', 'preview_label_font_size', 'preview_label_font',
+                                                 'preview_blur_categories', 'preview_quality')}
+    if args.preview_folder is None:
+        assert all(v is None for v in preview_sub.values()) and not args.preview_detections_only and not args.preview_preserve_paths, \
+            '--preview_width / --preview_confidence_threshold / --preview_detections_only / --preview_preserve_paths / ' \
+            '--preview_box_thickness / --preview_box_expansion / --preview_label_font_size / --preview_label_font / ' \
+            '--preview_blur_categories / --preview_quality need --preview_folder'
     if args.blur_folder is None:
         assert args.blur_categories is None and args.blur_confidence_threshold is None and args.blur_radius is None \
             and args.blur_quality is None, '--blur_categories / --blur_confidence_threshold / --blur_radius / --blur_quality need --blur_folder'
@@ -1148,6 +1231,14 @@ def main(argv=None):
                       blur_radius=blur_mod.DEFAULT_BLUR_RADIUS if args.blur_radius is None else args.blur_radius,
                       blur_quality=blur_mod.DEFAULT_BLUR_QUALITY if args.blur_quality is None else args.blur_quality,
                       blur_base=crop_base)
+    if args.preview_folder is not None:
+        whole = lambda v: int(v) if v is not None and v >= 1 else v     # (pixels are whole numbers; a fraction stays one)
+        kwargs.update(preview_folder=args.preview_folder, preview_detections_only=args.preview_detections_only,
+                      preview_preserve_paths=args.preview_preserve_paths, preview_base=crop_base,
+                      **{k: v for k, v in preview_sub.items() if v is not None})
+        for k in ('preview_box_thickness', 'preview_box_expansion', 'preview_label_font_size'):
+            if k in kwargs:
+                kwargs[k] = whole(kwargs[k])
     t0 = time.time()
     if args.n_gpus > 1:
         results = run_sharded(args.detector_file, files, args.n_gpus, results=results, **kwargs)
