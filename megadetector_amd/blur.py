@@ -11,10 +11,8 @@ The files equal, byte for byte, what Image.save(name, quality=q) writes for Pill
 difference: the EXIF block exif_preserving_save copies from the source file is not written.
 """
 
-import os
-
 from . import jpeg_host
-from .crops import is_jpeg_name, output_order, _pil_file
+from .crops import Product, device_stream, files_of_device_images, output_order, write_file, _pil_file
 
 #: the reference script's own default: its --threshold is None (separate_detections_into_folders.py:708), so it takes
 #: get_typical_confidence_threshold_from_results (separate_detections_into_folders.py:557-560), which is
@@ -123,37 +121,38 @@ def blurred_of_device_images(ctx, entries, options, category_ids, stream=0):
             jobs.append((e, rects))
     if not jobs:
         return out, counts
-    ext = torch.cuda.ExternalStream(stream, device=entries[0][0].device) if stream else torch.cuda.current_stream(entries[0][0].device)
+    ext = device_stream(stream, entries[0][0].device)
     with torch.cuda.stream(ext):
         copies = [entries[e][0].clone() for e, _ in jobs]
     sizes = [(entries[e][1], entries[e][2]) for e, _ in jobs]
-    pitches = [w * 3 for w, _ in sizes]
-    ctx.blur_regions([c.data_ptr() for c in copies], sizes, pitches, [k for k, (_, rects) in enumerate(jobs) for _ in rects],
+    ctx.blur_regions([c.data_ptr() for c in copies], sizes, [w * 3 for w, _ in sizes], [k for k, (_, rects) in enumerate(jobs) for _ in rects],
                      [r for _, rects in jobs for r in rects], options.radius, stream=ext.cuda_stream)
-    jpeg = [k for k, (e, _) in enumerate(jobs) if is_jpeg_name(entries[e][3])]
-    if jpeg:
-        from .crops import encode_windows
-        files = encode_windows(ctx, [copies[k].data_ptr() for k in jpeg], [pitches[k] for k in jpeg],
-                               [(0, 0) + sizes[k] for k in jpeg], options.quality, ext.cuda_stream)
-        for k, data in zip(jpeg, files):
-            out[jobs[k][0]] = data
-        counts['gpu'] = len(jpeg)
-    for k, (e, _) in enumerate(jobs):
-        if out[e] is None:
-            with torch.cuda.stream(ext):
-                pixels = copies[k].cpu().numpy().reshape(sizes[k][1], sizes[k][0], 3)
-            out[e] = _pil_file(pixels, entries[e][3], options.quality)
-            counts['host'] += 1
+    files = files_of_device_images(ctx, [(c, w, h, entries[e][3]) for c, (w, h), (e, _) in zip(copies, sizes, jobs)], options.quality, ext)
+    for (e, _), (data, leg) in zip(jobs, files):
+        out[e] = data
+        counts[leg] += 1
     return out, counts
 
 
 def write_blurred(blur_folder, relative_name, data):
     """writes one blurred copy below blur_folder; returns the path"""
-    path = os.path.join(blur_folder, relative_name).replace('\\', '/')
-    os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
-    with open(path, 'wb') as f:
-        f.write(data)
-    return path
+    return write_file(blur_folder, relative_name, data)
+
+
+class BlurProduct(Product):
+    """blur=: result['blurred'] = bytes, or None when nothing in the image is to be blurred; counted in HIPDetector.blur_counts"""
+
+    key = 'blurred'
+
+    def nothing(self):
+        return None
+
+    def _host(self, pixels, name, detections):
+        data = blurred_file_of_host_image(pixels, name, detections, self.options, self.options.category_ids())
+        return data, None if data is None else 'host'
+
+    def _device(self, ctx, entries, stream):
+        return blurred_of_device_images(ctx, entries, self.options, self.options.category_ids(), stream=stream)
 
 
 __all__ = ['BlurOptions', 'DEFAULT_BLUR_CONFIDENCE_THRESHOLD', 'blur_rectangle', 'blurred_file_of_host_image',

@@ -155,6 +155,34 @@ def _pil_file(pixels, name, quality):
     return bio.getvalue()
 
 
+def device_stream(stream, device):
+    """the torch stream work for a raw stream handle goes on: an ExternalStream around the handle, the current stream for 0"""
+    import torch
+    return torch.cuda.ExternalStream(stream, device=device) if stream else torch.cuda.current_stream(device)
+
+
+def files_of_device_images(ctx, images, quality, ext):
+    """
+    Whole images in device memory saved under names.  images: [(tensor, width, height, name)], ext the torch stream they were
+    made on.  Returns [(bytes, leg)]: the names Pillow maps to JPEG are encoded on the device, all in ONE encoder call
+    ('gpu'); for any other extension the pixels are copied back and PIL saves them in the format of the name ('host').
+    """
+    import torch
+    out = [None] * len(images)
+    jpeg = [k for k, image in enumerate(images) if is_jpeg_name(image[3])]
+    if jpeg:
+        files = encode_windows(ctx, [images[k][0].data_ptr() for k in jpeg], [images[k][1] * 3 for k in jpeg],
+                               [(0, 0, images[k][1], images[k][2]) for k in jpeg], quality, ext.cuda_stream)
+        for k, data in zip(jpeg, files):
+            out[k] = (data, 'gpu')
+    for k, (tensor, width, height, name) in enumerate(images):
+        if out[k] is None:
+            with torch.cuda.stream(ext):
+                pixels = tensor.cpu().numpy().reshape(height, width, 3)
+            out[k] = (_pil_file(pixels, name, quality), 'host')
+    return out
+
+
 def crops_of_host_image(pixels, image_file, detections, options, category_ids=None, warn=print):
     """the reference's way, from an H x W x 3 uint8 array on the host: PIL saves every crop.  -> (crops, skipped)"""
     picked, skipped = _pick(image_file, pixels.shape[1], pixels.shape[0], detections, options, category_ids, warn)
@@ -201,16 +229,62 @@ def crops_of_device_image(ctx, tensor, width, height, image_file, detections, op
     return out[0], counts['skipped']
 
 
+def write_file(folder, relative_name, data):
+    """writes the bytes of one file below folder under its relative name; returns the path"""
+    path = os.path.join(folder, relative_name).replace('\\', '/')
+    os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    with open(path, 'wb') as f:
+        f.write(data)
+    return path
+
+
 def write_crops(crop_folder, crops):
     """writes [(crop_id, crop_filename_relative, bytes)] below crop_folder; returns the paths"""
-    paths = []
-    for _, name, data in crops:
-        path = os.path.join(crop_folder, name).replace('\\', '/')
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        with open(path, 'wb') as f:
-            f.write(data)
-        paths.append(path)
-    return paths
+    return [write_file(crop_folder, name, data) for _, name, data in crops]
+
+
+class Product:
+    """
+    What HIPDetector needs to know about a product it makes from the image in device memory (crops=, blur=, preview=): `key`
+    of the result dict, nothing() for an image that has none, the dict `counts` feeds, selects(result), and how the product
+    is made -- _device(ctx, entries, stream) -> (values, counts) for a batch of [(tensor, width, height, name, detections)]
+    and, unless `letterboxed_on_device`, _host(pixels, name, detections) -> (value, the count it adds to or None).
+    """
+
+    #: an input that came already letterboxed: True = the product is made on the device from the letterboxed pixels, False =
+    #: by the host leg from 'img_original', which for such an input is on the host only
+    letterboxed_on_device = False
+
+    def __init__(self, options, counts):
+        self.options, self.counts = options, counts
+
+    def selects(self, result):
+        return result.get('detections') is not None
+
+    def of_host_image(self, pixels, name, detections):
+        value, leg = self._host(pixels, name, detections)
+        if leg is not None:
+            self.counts[leg] += 1
+        return value
+
+    def of_device_images(self, ctx, entries, stream=0):
+        out, counts = self._device(ctx, entries, stream)
+        for key, n in counts.items():
+            self.counts[key] += n
+        return out
+
+
+class CropProduct(Product):
+    """crops=: result['crops'] = [(crop_id, crop_filename_relative, bytes)], counted in HIPDetector.crop_counts"""
+
+    key = 'crops'
+    letterboxed_on_device = True
+
+    def nothing(self):
+        return []
+
+    def _device(self, ctx, entries, stream):
+        return crops_of_device_images(ctx, entries, self.options, self.options.category_ids(), stream=stream)
 
 
 def annotate_results(images, options, category_ids=None, name_of=None):

@@ -32,6 +32,9 @@ import os
 import numpy as np
 
 from . import weights_io
+from .blur import BlurProduct
+from .crops import CropProduct
+from .preview import PreviewProduct
 from .constants import (FAILURE_IMAGE_OPEN, FAILURE_INFER, DEFAULT_COMPATIBILITY_MODE)
 from .jpeg_host import CoefficientImage, DeviceCoefficientImage, ScanFailure, ScanImage, check_quality
 from .postprocess import letterbox_geometry, modern_geometry, format_detections
@@ -285,110 +288,57 @@ class HIPDetector:
         if self._ctx is None:
             raise RuntimeError('this HIPDetector was created with preprocess_only')
         self._check_augment(augment)
+        products = self._products(crops, blur, preview)
         img_original = self.decode_scans(img_original)
         results, shape_groups = self._prepare_batch(img_original, image_id, image_size, verbose)
         for shape, items in shape_groups.items():
             try:
                 for start in range(0, len(items), self.max_batch):
                     self._process_batch_group(items[start:start + self.max_batch], results,
-                                              detection_threshold, augment, verbose, crops, blur, preview)
+                                              detection_threshold, augment, verbose, products)
             except Exception as e:
                 print('Warning: batch inference failed for shape {}: {}'.format(shape, str(e)))
                 for original_idx, _, current_id in items:
                     results[original_idx] = {'file': current_id, 'detections': None, 'failure': FAILURE_INFER}
-        return self._crops_everywhere(results, crops, blur, preview)
+        return self._products_everywhere(results, products)
+
+    def _products(self, crops, blur, preview):
+        """the products asked for (crops.Product), in the order their kernels are enqueued"""
+        asked = ((CropProduct, crops, self.crop_counts), (BlurProduct, blur, self.blur_counts), (PreviewProduct, preview, self.preview_counts))
+        return [product(options, counts) for product, options, counts in asked if options is not None]
 
     @staticmethod
-    def _crops_everywhere(results, crops, blur=None, preview=None):
-        """an image that failed has no crops and no blurred copy, as the reference's second pass gives it none"""
-        if crops is not None:
+    def _products_everywhere(results, products):
+        """an image that failed has no crops, no blurred copy and no preview, as the reference's second passes give it none"""
+        for product in products:
             for r in results:
                 if r is not None:
-                    r.setdefault('crops', [])
-        if blur is not None:
-            for r in results:
-                if r is not None:
-                    r.setdefault('blurred', None)
-        if preview is not None:
-            for r in results:
-                if r is not None:
-                    r.setdefault('preview', (None, 'skipped'))
+                    r.setdefault(product.key, product.nothing())
         return results
 
-    def _add_preview(self, group_items, tensors, results, preview, stream=0):
-        """'preview' of the results of one group: tensors[i] holds the pixels of group_items[i] on the device.  One blur,
-        one resample, one drawing and one encoder call and one read-back for the group.  An image that came already
-        letterboxed has its source pixels on the host only: PIL renders it there (preview.preview_file_of_host_image)."""
-        from . import preview as V
-        entries, where = [], []
-        for (original_idx, info, current_id), t in zip(group_items, tensors):
-            r = results[original_idx]
-            if r is None or not V.is_rendered(r, preview):
-                if r is not None:
-                    r['preview'] = (None, 'skipped')
-                    self.preview_counts['skipped'] += 1
-                continue
-            if isinstance(info['img_processed'], LetterboxSpec):
-                hh, ww = info['img_original'].shape[:2]
+    def _add_products(self, group_items, tensors, results, products, stream=0):
+        """the products of the results of one group: tensors[i] holds the pixels of group_items[i] on the device.  For each
+        product one round of device calls and one read-back for the group.  An image that came already letterboxed has its
+        source pixels on the host only: crops are cut from the letterboxed pixels on the device, every other product is made
+        from 'img_original' by its host leg."""
+        for product in products:
+            entries, where = [], []
+            for (original_idx, info, current_id), t in zip(group_items, tensors):
+                r = results[original_idx]
+                if not product.selects(r):
+                    continue
+                if isinstance(info['img_processed'], LetterboxSpec):
+                    hh, ww = info['img_original'].shape[:2]
+                elif product.letterboxed_on_device:
+                    hh, ww = info['img_processed'].shape[:2]
+                else:
+                    r[product.key] = product.of_host_image(np.asarray(info['img_original']), current_id, r['detections'])
+                    continue
                 entries.append((t, ww, hh, current_id, r['detections']))
                 where.append(original_idx)
-            else:
-                data = V.preview_file_of_host_image(np.asarray(info['img_original']), current_id, r['detections'], preview)
-                r['preview'] = (data, 'host' if data is not None else 'skipped')
-                self.preview_counts[r['preview'][1]] += 1
-        if not entries:
-            return
-        out, counts = V.previews_of_device_images(self._ctx, entries, preview, stream=stream)
-        for original_idx, pair in zip(where, out):
-            results[original_idx]['preview'] = pair
-        for key, v in counts.items():
-            self.preview_counts[key] += v
-
-    def _add_blur(self, group_items, tensors, results, blur, stream=0):
-        """'blurred' of the results of one group: tensors[i] holds the pixels of group_items[i] on the device.  One blur call,
-        one encoder call and one read-back for the group.  An image that came already letterboxed has its source pixels on
-        the host only: libmdjpeg.so blurs a copy there and PIL saves it."""
-        from . import blur as B
-        ids = blur.category_ids()
-        entries, where = [], []
-        for (original_idx, info, current_id), t in zip(group_items, tensors):
-            r = results[original_idx]
-            if r is None or r.get('detections') is None:
-                continue
-            if isinstance(info['img_processed'], LetterboxSpec):
-                hh, ww = info['img_original'].shape[:2]
-                entries.append((t, ww, hh, current_id, r['detections']))
-                where.append(original_idx)
-            else:
-                r['blurred'] = B.blurred_file_of_host_image(np.asarray(info['img_original']), current_id, r['detections'], blur, ids)
-                self.blur_counts['host'] += r['blurred'] is not None
-        if not entries:
-            return
-        out, counts = B.blurred_of_device_images(self._ctx, entries, blur, ids, stream=stream)
-        for original_idx, data in zip(where, out):
-            results[original_idx]['blurred'] = data
-        for key, v in counts.items():
-            self.blur_counts[key] += v
-
-    def _add_crops(self, group_items, tensors, results, crops, stream=0):
-        """'crops' of the results of one group: tensors[i] holds the pixels of group_items[i] on the device.  One encoder
-        call and one read-back for the group."""
-        from . import crops as K
-        entries, where = [], []
-        for (original_idx, info, current_id), t in zip(group_items, tensors):
-            r = results[original_idx]
-            if r is None or r.get('detections') is None:
-                continue
-            hh, ww = info['img_original'].shape[:2] if isinstance(info['img_processed'], LetterboxSpec) else info['img_processed'].shape[:2]
-            entries.append((t, ww, hh, current_id, r['detections']))
-            where.append(original_idx)
-        if not entries:
-            return
-        out, counts = K.crops_of_device_images(self._ctx, entries, crops, crops.category_ids(), stream=stream)
-        for original_idx, c in zip(where, out):
-            results[original_idx]['crops'] = c
-        for key, v in counts.items():
-            self.crop_counts[key] += v
+            if entries:
+                for original_idx, value in zip(where, product.of_device_images(self._ctx, entries, stream)):
+                    results[original_idx][product.key] = value
 
     def _prepare_batch(self, img_original, image_id, image_size, verbose):
         """per-image preprocessing with failure capture (reference :1194-1222) and grouping by processed
@@ -531,7 +481,7 @@ class HIPDetector:
                 json.dump({'fp8_scales': [float(sc) for sc, _, _ in self._ctx.fp8_scales()]}, f)
             os.replace(tmp, self._fp8_scales_file)
 
-    def _process_batch_group(self, group_items, results, detection_threshold, augment, verbose, crops=None, blur=None, preview=None):
+    def _process_batch_group(self, group_items, results, detection_threshold, augment, verbose, products=()):
         """reference pytorch_detector.py:1257-1426 with the device work in libmdhip.so"""
         if len(group_items) == 0:
             return
@@ -541,7 +491,7 @@ class HIPDetector:
         ctx = self._ctx
         images, hold = self._reconstruct_jpegs(images)       # (`hold` keeps the device images alive until the NMS has returned)
         tensors = None
-        if crops is not None or blur is not None or preview is not None:
+        if products:
             # every source image on the device exactly once, where the encoder can still address it: host arrays that
             # mdhip_preprocess would stage internally are uploaded here and passed as device pointers
             import torch
@@ -569,12 +519,8 @@ class HIPDetector:
             ctx.forward(n, h, w)
         det_all, counts = ctx.nms(n, detection_threshold, self._nms_iou(), max_det=300)
         self._format_group(group_items, det_all, counts, h, w, results, detection_threshold)
-        if crops is not None:
-            self._add_crops(group_items, tensors, results, crops)
-        if blur is not None:
-            self._add_blur(group_items, tensors, results, blur)
-        if preview is not None:
-            self._add_preview(group_items, tensors, results, preview)
+        if products:
+            self._add_products(group_items, tensors, results, products)
 
     # -----------------------------------------------------------------------------------
     def generate_detections_for_tiles(self, img_original, tile_origins, tile_size, tile_ids=None,
@@ -704,10 +650,10 @@ class HIPDetector:
                 self._pl = {'torch': torch, 'dev': dev, 'copy_s': torch.cuda.Stream(), 'comp_s': torch.cuda.Stream(),
                             'nms_s': torch.cuda.Stream(), 'nms_done': [None] * 4,
                             'stage': [None, None], 'copied': [torch.cuda.Event(), torch.cuda.Event()],
-                            'consumed': [None, None], 'count': 0, 'crop_owner': [None, None]}
+                            'consumed': [None, None], 'count': 0, 'owes_products': [None, None]}
         return self._pl
 
-    def _submit_group(self, group_items, detection_threshold, augment=False, crops=None, blur=None, preview=None):
+    def _submit_group(self, group_items, detection_threshold, augment=False, products=()):
         pl = self._pipeline()
         torch = pl['torch']
         h, w = group_items[0][1]['img_processed'].shape[:2]
@@ -727,12 +673,12 @@ class HIPDetector:
             rgb_offs[i] = total
             total += (int(np.prod(images[i].shape)) + 255) // 256 * 256
         with torch.cuda.device(pl['dev']):
-            if pl['crop_owner'][k] is not None:
-                # a group whose crops are not encoded yet (a ticket that is still outstanding) keeps its pixels in this
+            if pl['owes_products'][k] is not None:
+                # a group whose products are not made yet (a ticket that is still outstanding) keeps its pixels in this
                 # buffer, and `consumed` stands behind its letterbox only: that group keeps the storage (its views hold
                 # it) and this one gets a tensor of its own
                 pl['stage'][k] = None
-                pl['crop_owner'][k] = None
+                pl['owes_products'][k] = None
             if pl['stage'][k] is None or pl['stage'][k].numel() < total:
                 if pl['consumed'][k] is not None:
                     pl['consumed'][k].synchronize()
@@ -798,11 +744,10 @@ class HIPDetector:
             done.record(nms_s)
             pl['nms_done'][nms_slot] = done
         handle = {'items': group_items, 'h': h, 'w': w, 'slot': nms_slot, 'copied': pl['copied'][k], 'images': images}
-        if crops is not None or blur is not None or preview is not None:
-            # the pixels stay in staging buffer k until the crops are encoded (_collect_group): views of it, per image
-            handle['crops'], handle['blur'], handle['preview'] = crops, blur, preview
-            handle['k'], handle['consumed'] = k, ev
-            pl['crop_owner'][k] = handle
+        if products:
+            # the pixels stay in staging buffer k until the products are made (_collect_group): views of it, per image
+            handle['products'], handle['k'], handle['consumed'] = products, k, ev
+            pl['owes_products'][k] = handle
             handle['tensors'] = [stage[rgb_offs[i]:rgb_offs[i] + int(np.prod(im.shape))] if i in rgb_offs
                                  else stage[offs[i]:offs[i] + im.nbytes] for i, im in enumerate(images)]
         return handle
@@ -814,26 +759,21 @@ class HIPDetector:
             pl = self._pipeline()
             torch = pl['torch']
             with torch.cuda.device(pl['dev']):
-                if pl.get('crop_s') is None:
-                    pl['crop_s'] = torch.cuda.Stream()
-                crop_s = pl['crop_s']
-                crop_s.wait_event(handle['consumed'])            # copies, reconstruction and letterbox of this batch are done
+                if pl.get('product_s') is None:
+                    pl['product_s'] = torch.cuda.Stream()
+                product_s = pl['product_s']
+                product_s.wait_event(handle['consumed'])         # copies, reconstruction and letterbox of this batch are done
                 try:
-                    if handle['crops'] is not None:
-                        self._add_crops(handle['items'], handle['tensors'], results, handle['crops'], stream=crop_s.cuda_stream)
-                    if handle['blur'] is not None:
-                        self._add_blur(handle['items'], handle['tensors'], results, handle['blur'], stream=crop_s.cuda_stream)
-                    if handle['preview'] is not None:
-                        self._add_preview(handle['items'], handle['tensors'], results, handle['preview'], stream=crop_s.cuda_stream)
+                    self._add_products(handle['items'], handle['tensors'], results, handle['products'], stream=product_s.cuda_stream)
                 finally:
                     # While this group owned staging buffer k no other group could take it (_submit_group gives a later one a
                     # tensor of its own).  From here on the buffer may be reused: its `consumed` event moves behind the
-                    # encoder's kernels, so the copy stream overwrites it only behind this group's encode.
-                    if pl['crop_owner'][handle['k']] is handle:
-                        pl['crop_owner'][handle['k']] = None
+                    # products' kernels, so the copy stream overwrites it only behind this group's last encode.
+                    if pl['owes_products'][handle['k']] is handle:
+                        pl['owes_products'][handle['k']] = None
                         if pl['consumed'][handle['k']] is handle['consumed']:
                             ev = torch.cuda.Event()
-                            ev.record(crop_s)
+                            ev.record(product_s)
                             pl['consumed'][handle['k']] = ev
 
     def start_batch(self, img_original, image_id, detection_threshold=0.00001, image_size=None, augment=False,
@@ -845,6 +785,7 @@ class HIPDetector:
         self._check_augment(augment)
         if detection_threshold is None:
             detection_threshold = 0.0
+        products = self._products(crops, blur, preview)
         img_original = self.decode_scans(img_original)
         results, shape_groups = self._prepare_batch(img_original, image_id, image_size, verbose)
         chunks = []
@@ -854,7 +795,7 @@ class HIPDetector:
         pending = None
         for ci, chunk in enumerate(chunks):
             try:
-                handle = self._submit_group(chunk, detection_threshold, augment, crops, blur, preview)
+                handle = self._submit_group(chunk, detection_threshold, augment, products)
                 if ci == len(chunks) - 1:
                     pending = handle                     # the last group stays in flight
                 else:
@@ -863,7 +804,7 @@ class HIPDetector:
                 print('Warning: batch inference failed for shape {}: {}'.format(chunk[0][1]['img_processed'].shape, str(e)))
                 for original_idx, _, current_id in chunk:
                     results[original_idx] = {'file': current_id, 'detections': None, 'failure': FAILURE_INFER}
-        return {'results': results, 'pending': pending, 'threshold': detection_threshold, 'crops': crops, 'blur': blur, 'preview': preview}
+        return {'results': results, 'pending': pending, 'threshold': detection_threshold, 'products': products}
 
     def batch_inputs_consumed(self, ticket):
         """Blocks until the host images of the ticket's in-flight group have been copied to the device
@@ -882,7 +823,7 @@ class HIPDetector:
                 for original_idx, _, current_id in handle['items']:
                     results[original_idx] = {'file': current_id, 'detections': None, 'failure': FAILURE_INFER}
             ticket['pending'] = None
-        return self._crops_everywhere(results, ticket.get('crops'), ticket.get('blur'), ticket.get('preview'))
+        return self._products_everywhere(results, ticket['products'])
 
     # -----------------------------------------------------------------------------------
     def generate_detections_one_image(self, img_original, image_id='unknown', detection_threshold=0.00001,

@@ -21,7 +21,7 @@ file into the saved one through Image.info -- a JPEG's COM segment, a PNG's ICC 
 import os
 
 from . import jpeg_host
-from .crops import is_jpeg_name, output_order, _pil_file
+from .crops import Product, device_stream, files_of_device_images, output_order, write_file, _pil_file
 
 DEFAULT_PREVIEW_CONFIDENCE_THRESHOLD = 0.15     # visualize_detector_output.py:177 confidence_threshold=0.15
 DEFAULT_PREVIEW_WIDTH = 1000                    # visualize_detector_output.py:179 output_image_width=1000
@@ -466,7 +466,7 @@ def previews_of_device_images(ctx, entries, options, label_map=None, stream=0):
     if not entries:
         return out, counts
     device = entries[0][0].device
-    ext = torch.cuda.ExternalStream(stream, device=device) if stream else torch.cuda.current_stream(device)
+    ext = device_stream(stream, device)
     for e in host:
         tensor, width, height, name, detections = entries[e]
         with torch.cuda.stream(ext):
@@ -508,18 +508,10 @@ def previews_of_device_images(ctx, entries, options, label_map=None, stream=0):
                 patches = torch.from_numpy(np.frombuffer(bytes(packed) or b'\0', np.uint8).copy()).to(device)
             ctx.draw_ops([t.data_ptr() for t in rendered], [job[1] for job in jobs], [job[1][0] * 3 for job in jobs], op_image, ops,
                          patches.data_ptr(), len(packed), stream=ext.cuda_stream)
-        jpeg = [k for k, (e, _, _, _) in enumerate(jobs) if is_jpeg_name(entries[e][3])]
-        if jpeg:
-            from .crops import encode_windows
-            files = encode_windows(ctx, [rendered[k].data_ptr() for k in jpeg], [jobs[k][1][0] * 3 for k in jpeg],
-                                   [(0, 0) + tuple(jobs[k][1]) for k in jpeg], options.quality, ext.cuda_stream)
-            for k, data in zip(jpeg, files):
-                out[jobs[k][0]] = (data, 'gpu')
-        for k, (e, size, _, _) in enumerate(jobs):
-            if out[e][0] is None:
-                with torch.cuda.stream(ext):
-                    pixels = rendered[k].cpu().numpy().reshape(size[1], size[0], 3)
-                out[e] = (_pil_file(pixels, entries[e][3], options.quality), 'host')
+        files = files_of_device_images(ctx, [(t, size[0], size[1], entries[e][3]) for t, (e, size, _, _) in zip(rendered, jobs)],
+                                       options.quality, ext)
+        for (e, _, _, _), pair in zip(jobs, files):
+            out[e] = pair
     for _, leg in out:
         counts[leg] += 1
     return out, counts
@@ -527,11 +519,32 @@ def previews_of_device_images(ctx, entries, options, label_map=None, stream=0):
 
 def write_preview(preview_folder, relative_name, data):
     """writes one preview below preview_folder; returns the path"""
-    path = os.path.join(preview_folder, relative_name).replace('\\', '/')
-    os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
-    with open(path, 'wb') as f:
-        f.write(data)
-    return path
+    return write_file(preview_folder, relative_name, data)
+
+
+class PreviewProduct(Product):
+    """preview=: result['preview'] = (bytes or None, leg); counted in HIPDetector.preview_counts, the images that are not
+    rendered (is_rendered) as 'skipped'"""
+
+    key = 'preview'
+
+    def nothing(self):
+        return None, 'skipped'
+
+    def selects(self, result):
+        if is_rendered(result, self.options):
+            return True
+        result[self.key] = self.nothing()
+        self.counts['skipped'] += 1
+        return False
+
+    def _host(self, pixels, name, detections):
+        data = preview_file_of_host_image(pixels, name, detections, self.options)
+        leg = 'host' if data is not None else 'skipped'
+        return (data, leg), leg
+
+    def _device(self, ctx, entries, stream):
+        return previews_of_device_images(ctx, entries, self.options, stream=stream)
 
 
 __all__ = ['HostLeg', 'NO_LABELS', 'PreviewOptions', 'RenderFailure', 'RenderPlan', 'box_edges', 'drawn_detections', 'is_rendered',

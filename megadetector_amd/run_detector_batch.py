@@ -147,34 +147,50 @@ def _filter_batch_output(dets, names, images, confidence_threshold, include_imag
 
 
 # --------------------------------------------------------------------------------------------
-# detection crops (reference postprocessing/create_crop_folder.py, written while the images are at hand)
+# written products, made while the images are at hand: detection crops (reference postprocessing/create_crop_folder.py),
+# blurred copies (postprocessing/separate_detections_into_folders.py --category_names_to_blur) and annotated previews
+# (visualization/visualize_detector_output.py)
 # --------------------------------------------------------------------------------------------
 #: crops of the most recent run in this process: 'files' written, of them 'gpu' = JPEG names encoded by the detector on
 #: the device, 'host_jpeg' = JPEG names saved by PIL here (a detector without crops=), 'host_other' = other extensions,
 #: saved by PIL as the reference does; 'skipped' = rectangles without area
 last_crop_counts = {}
 
+#: blurred copies of the most recent run in this process: 'files' written, of them 'gpu' = made by the detector from the
+#: image in device memory (blur=), 'host' = blurred and saved here (a detector without blur=)
+last_blur_counts = {}
 
-def _crop_relative_name(file, base):
-    """the name an image's crops are derived from: relative to the image folder (a lone file: its base name)"""
+#: previews of the most recent run in this process: 'files' written, of them 'gpu' = made by the detector from the image in
+#: device memory (preview=), 'host' = rendered or saved by PIL (a detector without preview=, pixels that never were in device
+#: memory, an extension that is not JPEG, drawing the plan does not restate); 'skipped' = images without a file (failed,
+#: below the threshold with detections_only, a resize target that is not positive, drawing that raises)
+last_preview_counts = {}
+
+
+def _relative_name(file, base):
+    """the name an image's products are derived from: relative to the image folder (a lone file: its base name)"""
     if os.path.isabs(file):
         file = os.path.relpath(file, start=base) if base else os.path.basename(file)
     return file.replace('\\', '/')
 
 
-class _CropWriter:
-    """writes an image's crops below the crop folder BEFORE its result is handed on, so that a result a checkpoint holds
-    has its crops on disk and a resumed run leaves no gaps"""
+class _Writer:
+    """writes an image's product below the product's folder BEFORE its result is handed on, so that a result a checkpoint
+    holds has its files on disk and a resumed run leaves no gaps.  A detector that has the product's keyword makes it and
+    the result carries it; for any other detector the host leg makes it here.  The per-product part: `keyword`, `count_keys`
+    and files(result, relative name, pixels) -> [(name below the folder, bytes, the count it adds to)]."""
 
     def __init__(self, folder, options, base):
         self.folder, self.options, self.base = folder, options, base
-        self.category_ids = options.category_ids()
-        self.counts = {'files': 0, 'gpu': 0, 'host_jpeg': 0, 'host_other': 0, 'skipped': 0}
+        # (a category name the label map does not hold ends the run here)
+        self.category_ids = options.category_ids() if hasattr(options, 'category_ids') else None
+        self.counts = dict.fromkeys(('files',) + self.count_keys, 0)
 
     def detector_kw(self, detector):
-        return {'crops': self.options} if getattr(detector, 'supports_crops', False) else {}
+        return {self.keyword: self.options} if getattr(detector, 'supports_' + self.keyword, False) else {}
 
-    def _pixels(self, image, file):
+    @staticmethod
+    def _pixels(image, file):
         if isinstance(image, dict):
             image = image.get('img_original')
         a = None if image is None or hasattr(image, 'coef') or hasattr(image, 'desc') else np.asarray(image)
@@ -184,133 +200,84 @@ class _CropWriter:
 
     def write(self, results, images):
         for i, r in enumerate(results):
-            crops = r.pop('crops', None)
-            if r.get('detections') is None:
-                continue
-            if crops is None:                                # a detector without crops=: PIL on the host, as the reference
-                skipped = 0
-                if crops_mod.select_crops(crops_mod.output_order(r['detections'], self.options.output_threshold),
-                                          self.options, self.category_ids):
-                    crops, skipped = crops_mod.crops_of_host_image(self._pixels(images[i] if images else None, r['file']),
-                                                                   r['file'], r['detections'], self.options, self.category_ids)
-                self.counts['skipped'] += skipped
-                kinds = ('host_jpeg', 'host_other')
-            else:
-                kinds = ('gpu', 'host_other')
-            rel = _crop_relative_name(r['file'], self.base)
-            named = [(cid, crops_mod.crop_filename(rel, cid), data) for cid, _, data in crops or []]
-            crops_mod.write_crops(self.folder, named)
-            for _, name, _ in named:
+            pixels = lambda: self._pixels(images[i] if images else None, r['file'])
+            for name, data, kind in self.files(r, _relative_name(r['file'], self.base), pixels):
+                crops_mod.write_file(self.folder, name, data)
                 self.counts['files'] += 1
-                self.counts[kinds[0] if crops_mod.is_jpeg_name(name) else kinds[1]] += 1
+                self.counts[kind] += 1
 
 
-# --------------------------------------------------------------------------------------------
-# blurred copies (reference postprocessing/separate_detections_into_folders.py --category_names_to_blur, written while
-# the images are at hand)
-# --------------------------------------------------------------------------------------------
-#: blurred copies of the most recent run in this process: 'files' written, of them 'gpu' = made by the detector from the
-#: image in device memory (blur=), 'host' = blurred and saved here (a detector without blur=)
-last_blur_counts = {}
+class _CropWriter(_Writer):
+    """<crop folder>/<crop_filename of the relative path>, one file for every detection that is cropped"""
+
+    keyword, count_keys = 'crops', ('gpu', 'host_jpeg', 'host_other', 'skipped')
+
+    def files(self, r, rel, pixels):
+        crops, jpeg_kind = r.pop('crops', None), 'gpu'
+        if r.get('detections') is None:
+            return []
+        if crops is None:                                    # a detector without crops=: PIL on the host, as the reference
+            jpeg_kind = 'host_jpeg'
+            if crops_mod.select_crops(crops_mod.output_order(r['detections'], self.options.output_threshold), self.options, self.category_ids):
+                crops, skipped = crops_mod.crops_of_host_image(pixels(), r['file'], r['detections'], self.options, self.category_ids)
+                self.counts['skipped'] += skipped
+        named = [(crops_mod.crop_filename(rel, cid), data) for cid, _, data in crops or []]
+        return [(name, data, jpeg_kind if crops_mod.is_jpeg_name(name) else 'host_other') for name, data in named]
 
 
-class _BlurWriter:
-    """writes the blurred copy of an image that has something to blur to <blur folder>/<relative path>, BEFORE its result
-    is handed on (as _CropWriter does, and for the same reason); no other image is written"""
+class _BlurWriter(_Writer):
+    """<blur folder>/<relative path>, for an image that has something to blur; no other image is written"""
 
-    def __init__(self, folder, options, base):
-        self.folder, self.options, self.base = folder, options, base
-        self.category_ids = options.category_ids()
-        self.counts = {'files': 0, 'gpu': 0, 'host': 0}
+    keyword, count_keys = 'blur', ('gpu', 'host')
 
-    def detector_kw(self, detector):
-        return {'blur': self.options} if getattr(detector, 'supports_blur', False) else {}
-
-    _pixels = _CropWriter._pixels
-
-    def write(self, results, images):
-        for i, r in enumerate(results):
-            from_detector = 'blurred' in r
-            data = r.pop('blurred', None)
-            if r.get('detections') is None:
-                continue
-            rel = _crop_relative_name(r['file'], self.base)
-            if not from_detector and blur_mod.select_detections(r['detections'], self.options, self.category_ids):
-                # a detector without blur=, or pixels that never were in device memory: the host leg
-                data = blur_mod.blurred_file_of_host_image(self._pixels(images[i] if images else None, r['file']), rel,
-                                                           r['detections'], self.options, self.category_ids)
-            if data is None:
-                continue
-            blur_mod.write_blurred(self.folder, rel, data)
-            self.counts['files'] += 1
-            self.counts['gpu' if from_detector else 'host'] += 1
+    def files(self, r, rel, pixels):
+        from_detector = 'blurred' in r
+        data = r.pop('blurred', None)
+        if r.get('detections') is None:
+            return []
+        if not from_detector and blur_mod.select_detections(r['detections'], self.options, self.category_ids):
+            # a detector without blur=, or pixels that never were in device memory: the host leg
+            data = blur_mod.blurred_file_of_host_image(pixels(), rel, r['detections'], self.options, self.category_ids)
+        return [] if data is None else [(rel, data, 'gpu' if from_detector else 'host')]
 
 
-# --------------------------------------------------------------------------------------------
-# annotated previews (reference visualization/visualize_detector_output.py, written while the images are at hand)
-# --------------------------------------------------------------------------------------------
-#: previews of the most recent run in this process: 'files' written, of them 'gpu' = made by the detector from the image in
-#: device memory (preview=), 'host' = rendered or saved by PIL (a detector without preview=, pixels that never were in device
-#: memory, an extension that is not JPEG, drawing the plan does not restate); 'skipped' = images without a file (failed,
-#: below the threshold with detections_only, a resize target that is not positive, drawing that raises)
-last_preview_counts = {}
+class _PreviewWriter(_Writer):
+    """<preview folder>/anno_<name> (or <relative path>); an image without a file counts as 'skipped'"""
+
+    keyword, count_keys = 'preview', ('gpu', 'host', 'skipped')
+
+    def files(self, r, rel, pixels):
+        data, leg = r.pop('preview', (None, None))
+        if leg is None and preview_mod.is_rendered(r, self.options):
+            # a detector without preview=: the host leg
+            data, leg = preview_mod.preview_file_of_host_image(pixels(), rel, r['detections'], self.options), 'host'
+        if data is None:
+            self.counts['skipped'] += 1
+            return []
+        return [(preview_mod.output_name(rel, self.options), data, leg)]
 
 
-class _PreviewWriter:
-    """writes the annotated preview of an image to <preview folder>/anno_<name> (or <relative path>), BEFORE its result is
-    handed on (as _CropWriter does, and for the same reason)"""
-
-    def __init__(self, folder, options, base):
-        self.folder, self.options, self.base = folder, options, base
-        self.counts = {'files': 0, 'gpu': 0, 'host': 0, 'skipped': 0}
-
-    def detector_kw(self, detector):
-        return {'preview': self.options} if getattr(detector, 'supports_preview', False) else {}
-
-    _pixels = _CropWriter._pixels
-
-    def write(self, results, images):
-        for i, r in enumerate(results):
-            data, leg = r.pop('preview', (None, None))
-            rel = _crop_relative_name(r['file'], self.base)
-            if leg is None and preview_mod.is_rendered(r, self.options):
-                # a detector without preview=: the host leg
-                data = preview_mod.preview_file_of_host_image(self._pixels(images[i] if images else None, r['file']), rel,
-                                                              r['detections'], self.options)
-                leg = 'host'
-            if data is None:
-                self.counts['skipped'] += 1
-                continue
-            preview_mod.write_preview(self.folder, preview_mod.output_name(rel, self.options), data)
-            self.counts['files'] += 1
-            self.counts[leg] += 1
+def _detector_kw(writers, detector):
+    """the product keywords this detector takes; a duck-typed detector without the flag never receives the keyword"""
+    kw = {}
+    for w in writers:
+        kw.update(w.detector_kw(detector))
+    return kw
 
 
-class _Writers:
-    """several writers behind the one hook of the loops (detector_kw / write)"""
-
-    def __init__(self, writers):
-        self.writers = writers
-
-    def detector_kw(self, detector):
-        kw = {}
-        for w in self.writers:
-            kw.update(w.detector_kw(detector))
-        return kw
-
-    def write(self, results, images):
-        for w in self.writers:
-            w.write(results, images)
+def _write_products(writers, results, images):
+    """outside the callers' try blocks: a folder that cannot be written ends the run, it is no inference failure"""
+    for w in writers:
+        w.write(results, images)
 
 
-def _crop_kw(crop_writer, detector):
-    return crop_writer.detector_kw(detector) if crop_writer is not None else {}
-
-
-def _write_crops(crop_writer, results, images):
-    """outside the callers' try blocks: a crop folder that cannot be written ends the run, it is no inference failure"""
-    if crop_writer is not None:
-        crop_writer.write(results, images)
+def _crop_options(confidence_threshold, expansion, quality, categories, output_threshold=None):
+    """crops.CropOptions from the crop arguments of load_and_run_detector_batch and of the command line; categories: a list of
+    names, or a string of names separated by commas or blanks"""
+    if isinstance(categories, str):
+        categories = [v for v in categories.replace(',', ' ').split() if v]
+    return crops_mod.CropOptions(confidence_threshold=confidence_threshold, expansion=expansion, quality=quality,
+                                 category_names_to_include=categories or None, output_threshold=output_threshold)
 
 
 def write_crop_result_files(final_output, options, base, crop_results_file=None, crops_output_file=None):
@@ -318,7 +285,7 @@ def write_crop_result_files(final_output, options, base, crop_results_file=None,
     added (its output_file), and one entry per crop (its crops_output_file, create_crop_folder.py:485-521)"""
     annotated = copy.deepcopy(final_output)
     records = crops_mod.annotate_results(annotated['images'], options, options.category_ids(),
-                                         name_of=lambda f: _crop_relative_name(f, base))
+                                         name_of=lambda f: _relative_name(f, base))
     if crop_results_file is not None:
         write_json(crop_results_file, annotated)
     if crops_output_file is not None:
@@ -335,8 +302,8 @@ class _BatchPipeline:
     """
 
     def __init__(self, detector, confidence_threshold, include_image_size, include_image_timestamp, on_results,
-                 depth=2, crop_writer=None):
-        self.crops = crop_writer
+                 depth=2, writers=()):
+        self.writers = writers
         self.det = detector
         self.thr = confidence_threshold
         self.inc_size, self.inc_time = include_image_size, include_image_timestamp
@@ -354,18 +321,18 @@ class _BatchPipeline:
         releases = [it[3] for it in items if it[3] is not None]
         if not self.async_ok:
             try:
-                dets = self.det.generate_detections_one_batch(images, names, verbose=verbose, **_crop_kw(self.crops, self.det))
+                dets = self.det.generate_detections_one_batch(images, names, verbose=verbose, **_detector_kw(self.writers, self.det))
                 res = _filter_batch_output(dets, names, metas, self.thr, self.inc_size, self.inc_time)
             except Exception as e:
                 print('Batch processing failure for {} images: {}'.format(len(images), str(e)))
                 res = [{'file': n, 'failure': FAILURE_INFER} for n in names]
-            _write_crops(self.crops, res, images)
+            _write_products(self.writers, res, images)
             for r in releases:
                 r()
             self.on_results(res)
             return
         try:
-            ticket = self.det.start_batch(images, names, verbose=verbose, **_crop_kw(self.crops, self.det))
+            ticket = self.det.start_batch(images, names, verbose=verbose, **_detector_kw(self.writers, self.det))
         except Exception as e:
             print('Batch processing failure for {} images: {}'.format(len(images), str(e)))
             for r in releases:
@@ -384,7 +351,7 @@ class _BatchPipeline:
         except Exception as e:
             print('Batch processing failure for {} images: {}'.format(len(names), str(e)))
             res = [{'file': n, 'failure': FAILURE_INFER} for n in names]
-        _write_crops(self.crops, res, images)
+        _write_products(self.writers, res, images)
         for r in releases:
             r()
         self.on_results(res)
@@ -396,7 +363,7 @@ class _BatchPipeline:
 
 def _process_batch(image_items_batch, detector, confidence_threshold, quiet=False, image_size=None,
                    include_image_size=False, include_image_timestamp=False, include_exif_tags=None,
-                   augment=False, crop_writer=None):
+                   augment=False, writers=()):
     """
     reference :680-831.  Items are file names or (file, image, producer_id) tuples.  As in the
     reference, the batched detector call receives neither the threshold nor image_size/augment
@@ -422,20 +389,20 @@ def _process_batch(image_items_batch, detector, confidence_threshold, quiet=Fals
     if valid_images:
         try:
             dets = detector.generate_detections_one_batch(valid_images, valid_names, verbose=verbose,
-                                                          **_crop_kw(crop_writer, detector))
+                                                          **_detector_kw(writers, detector))
             valid_results = _filter_batch_output(dets, valid_names, valid_images, confidence_threshold,
                                                  include_image_size, include_image_timestamp)
         except Exception as e:
             print('Batch processing failure for {} images: {}'.format(len(valid_images), str(e)))
             valid_results = [{'file': n, 'failure': FAILURE_INFER} for n in valid_names]
-        _write_crops(crop_writer, valid_results, valid_images)
+        _write_products(writers, valid_results, valid_images)
     batch_results.extend(valid_results)
     return batch_results
 
 
 def _process_image(im_file, detector, confidence_threshold, image=None, quiet=False, image_size=None,
                    include_image_size=False, include_image_timestamp=False, include_exif_tags=None,
-                   augment=False, crop_writer=None):
+                   augment=False, writers=()):
     """reference :937-1056 (the un-batched path: threshold, image_size and augment ARE forwarded)"""
     if not quiet:
         print('Processing image {}'.format(im_file))
@@ -449,12 +416,12 @@ def _process_image(im_file, detector, confidence_threshold, image=None, quiet=Fa
     try:
         result = detector.generate_detections_one_image(image, im_file, detection_threshold=confidence_threshold,
                                                         image_size=image_size, augment=augment, verbose=verbose,
-                                                        **_crop_kw(crop_writer, detector))
+                                                        **_detector_kw(writers, detector))
     except Exception as e:
         if not quiet:
             print('Image {} cannot be processed: {}'.format(im_file, str(e)))
         return {'file': im_file, 'failure': FAILURE_INFER}
-    _write_crops(crop_writer, [result], [image])
+    _write_products(writers, [result], [image])
     if 'failure' not in result or result.get('failure') is None:
         _add_image_metadata(result, image, include_image_size, include_image_timestamp)
     return result
@@ -524,7 +491,7 @@ def _make_preprocessor(detector, detector_options):
 def _run_detector_with_image_queue(image_files, detector, confidence_threshold, quiet, image_size,
                                    include_image_size, include_image_timestamp, augment, loader_workers,
                                    preprocess_on_image_queue, batch_size, on_results, detector_options=None,
-                                   crop_writer=None):
+                                   writers=()):
     q = queue.Queue(max_queue_size)
     file_q = queue.Queue()
     for f in image_files:
@@ -542,7 +509,7 @@ def _run_detector_with_image_queue(image_files, detector, confidence_threshold, 
     finished = 0
     pending = []
     pipe = _BatchPipeline(detector, confidence_threshold, include_image_size, include_image_timestamp, on_results,
-                          crop_writer=crop_writer)
+                          writers=writers)
 
     def flush():
         if pending:
@@ -552,7 +519,7 @@ def _run_detector_with_image_queue(image_files, detector, confidence_threshold, 
                 on_results([_process_image(f, detector, confidence_threshold, image=im, quiet=quiet,
                                            image_size=image_size, include_image_size=include_image_size,
                                            include_image_timestamp=include_image_timestamp, augment=augment,
-                                           crop_writer=crop_writer)
+                                           writers=writers)
                             for f, im, _ in pending])
             pending.clear()
 
@@ -585,7 +552,7 @@ last_feed_counts = {}
 
 def _run_detector_with_shared_ring(image_files, detector, confidence_threshold, quiet, image_size,
                                    include_image_size, include_image_timestamp, augment, loader_workers,
-                                   batch_size, on_results, gpu_jpeg=False, crop_writer=None):
+                                   batch_size, on_results, gpu_jpeg=False, writers=()):
     """
     SURVEY.md 8(f) N1 (feed.py): spawned loader processes decode into a page-locked shared-memory ring,
     the batches go through the detector's pipelined interface.  Same results as every other mode.
@@ -618,13 +585,13 @@ def _run_detector_with_shared_ring(image_files, detector, confidence_threshold, 
             n_slots, ring_slot_bytes >> 20, str(e)))
         return _run_detector_with_image_queue(image_files, detector, confidence_threshold, quiet, image_size,
                                               include_image_size, include_image_timestamp, augment, loader_workers,
-                                              False, batch_size, on_results, crop_writer=crop_writer)
+                                              False, batch_size, on_results, writers=writers)
     ring = loader.ring
     try:
         if hasattr(detector, 'start_batch'):
             ring.pin()
         pipe = _BatchPipeline(detector, confidence_threshold, include_image_size, include_image_timestamp, on_results,
-                              crop_writer=crop_writer)
+                              writers=writers)
         pending = []
 
         def decode_scans():
@@ -656,7 +623,7 @@ def _run_detector_with_shared_ring(image_files, detector, confidence_threshold, 
                 for f, im, meta_img, release in pending:
                     r = _process_image(f, detector, confidence_threshold, image=im, quiet=quiet,
                                        image_size=image_size, include_image_size=False,
-                                       include_image_timestamp=False, augment=augment, crop_writer=crop_writer)
+                                       include_image_timestamp=False, augment=augment, writers=writers)
                     if r.get('failure') is None and meta_img is not None:
                         _add_image_metadata(r, meta_img, include_image_size, include_image_timestamp)
                     if release is not None:
@@ -757,32 +724,26 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
     """
     global verbose, last_crop_counts, last_blur_counts, last_preview_counts
     verbose = bool(verbose_output)
-    crop_writer = None
+    output_threshold = DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD if confidence_threshold is None else confidence_threshold
+    writers = []
     if crop_folder is not None:
-        names = [v for v in crop_categories.replace(',', ' ').split() if v] if isinstance(crop_categories, str) else crop_categories
-        crop_writer = _CropWriter(crop_folder, crops_mod.CropOptions(
-            confidence_threshold=crop_confidence_threshold, expansion=crop_expansion, quality=crop_quality,
-            category_names_to_include=names or None,
-            output_threshold=DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD if confidence_threshold is None else confidence_threshold), crop_base)
-        last_crop_counts = crop_writer.counts         # (of the most recent call, for reporting; the writer itself is local)
+        writers.append(_CropWriter(crop_folder, _crop_options(crop_confidence_threshold, crop_expansion, crop_quality, crop_categories,
+                                                              output_threshold), crop_base))
+        last_crop_counts = writers[-1].counts         # (of the most recent call, for reporting; the writer itself is local)
     if blur_folder is not None:
-        blur_writer = _BlurWriter(blur_folder, blur_mod.BlurOptions(
+        writers.append(_BlurWriter(blur_folder, blur_mod.BlurOptions(
             category_names=blur_categories,
             confidence_threshold=blur_mod.DEFAULT_BLUR_CONFIDENCE_THRESHOLD if blur_confidence_threshold is None else blur_confidence_threshold,
-            radius=blur_radius, quality=blur_quality,
-            output_threshold=DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD if confidence_threshold is None else confidence_threshold), blur_base)
-        last_blur_counts = blur_writer.counts
-        crop_writer = blur_writer if crop_writer is None else _Writers([crop_writer, blur_writer])
+            radius=blur_radius, quality=blur_quality, output_threshold=output_threshold), blur_base))
+        last_blur_counts = writers[-1].counts
     if preview_folder is not None:
-        preview_writer = _PreviewWriter(preview_folder, preview_mod.PreviewOptions(
+        writers.append(_PreviewWriter(preview_folder, preview_mod.PreviewOptions(
             confidence_threshold=preview_confidence_threshold, output_image_width=preview_width,
             detections_only=preview_detections_only, preserve_path_structure=preview_preserve_paths,
             box_thickness=preview_box_thickness, box_expansion=preview_box_expansion, label_font_size=preview_label_font_size,
             label_font=preview_label_font, blur_categories=preview_blur_categories, quality=preview_quality,
-            output_threshold=DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD if confidence_threshold is None else confidence_threshold), preview_base)
-        last_preview_counts = preview_writer.counts
-        crop_writer = preview_writer if crop_writer is None else _Writers(
-            (crop_writer.writers if isinstance(crop_writer, _Writers) else [crop_writer]) + [preview_writer])
+            output_threshold=output_threshold), preview_base))
+        last_preview_counts = writers[-1].counts
     if detector_options is None:
         detector_options = {}
     elif isinstance(detector_options, (list, str)):
@@ -850,23 +811,23 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
         _run_detector_with_shared_ring(image_files, detector, confidence_threshold, quiet, image_size,
                                        include_image_size, include_image_timestamp, augment, loader_workers,
                                        batch_size, on_results, gpu_jpeg='entropy' if gpu_jpeg == 'entropy' else bool(gpu_jpeg),
-                                       crop_writer=crop_writer)
+                                       writers=writers)
     elif use_image_queue:
         _run_detector_with_image_queue(image_files, detector, confidence_threshold, quiet, image_size,
                                        include_image_size, include_image_timestamp, augment, loader_workers,
                                        preprocess_on_image_queue, batch_size, on_results,
-                                       detector_options=detector_options, crop_writer=crop_writer)
+                                       detector_options=detector_options, writers=writers)
     elif batch_size > 1:
         for batch in _group_into_batches(image_files, batch_size):
             on_results(_process_batch(batch, detector, confidence_threshold, quiet, image_size,
-                                      include_image_size, include_image_timestamp, None, augment, crop_writer=crop_writer),
+                                      include_image_size, include_image_timestamp, None, augment, writers=writers),
                        len(batch))
     else:
         for im_file in image_files:
             on_results([_process_image(im_file, detector, confidence_threshold, quiet=quiet, image_size=image_size,
                                        include_image_size=include_image_size,
                                        include_image_timestamp=include_image_timestamp, augment=augment,
-                                       crop_writer=crop_writer)])
+                                       writers=writers)])
     # a loader process that died mid-list, or a result dropped anywhere above, must not pass silently
     have = set(r['file'] for r in results)
     missing = [f for f in image_files if f not in have]
@@ -1256,10 +1217,8 @@ def main(argv=None):
     final_output = write_results_to_file(results, args.output_file, relative_path_base=base, detector_file=args.detector_file,
                                          include_max_conf=args.include_max_conf)
     if args.crop_folder is not None and (args.crop_results_file or args.crops_output_file):
-        names = [v for v in (args.crop_categories or '').replace(',', ' ').split() if v]
-        write_crop_result_files(final_output, crops_mod.CropOptions(
-            confidence_threshold=args.crop_confidence_threshold, expansion=args.crop_expansion, quality=args.crop_quality,
-            category_names_to_include=names or None), crop_base, args.crop_results_file, args.crops_output_file)
+        write_crop_result_files(final_output, _crop_options(args.crop_confidence_threshold, args.crop_expansion, args.crop_quality,
+                                                            args.crop_categories), crop_base, args.crop_results_file, args.crops_output_file)
     for cp in [checkpoint_path] + [shard_checkpoint_path(checkpoint_path, g) for g in range(max(1, args.n_gpus))]:
         if cp and os.path.isfile(cp):
             os.remove(cp)

@@ -2,7 +2,8 @@
 Annotated previews on the device: mdhip_resample_lanczos (HipContext.resample_lanczos) against Pillow's
 Image.resize(LANCZOS), bit for bit and with nothing written beside the destinations' rows; mdhip_draw_ops
 (HipContext.draw_ops) against its host model, byte for byte; HIPDetector(preview=) against the host leg on the same pixels
-and detections.  The shapes, scenes and the restated renderer are those of test_preview_cpu.py.
+and detections.  The shapes, scenes and the restated renderer are those of test_preview_cpu.py.  At the end crops=, blur= and
+preview= in one call against each alone, and already letterboxed inputs, where the products read different pixels.
 """
 
 import numpy as np
@@ -217,3 +218,133 @@ def test_detector_preview_synchronous_and_pipelined_equal_the_host_leg(blur):
     from megadetector_amd import blur as B
     both = det.generate_detections_one_batch(imgs, names, detection_threshold=1e-5, preview=opt, blur=B.BlurOptions(confidence_threshold=1.1))
     assert [r['preview'] for r in both] == [r['preview'] for r in sync]
+
+
+# ---- crops=, blur= and preview= in one call -------------------------------------------------------------------------------
+
+def _all_products():
+    from megadetector_amd import blur as B, crops as K
+    return dict(crops=K.CropOptions(confidence_threshold=0.0),
+                blur=B.BlurOptions(category_names=('animal', 'person', 'vehicle'), confidence_threshold=0.0),
+                preview=P.PreviewOptions(confidence_threshold=0.0, output_image_width=160))
+
+
+def _threshold_with_every_product(results, size_of, products):
+    """a detection threshold, taken from the detections themselves (the k-th highest confidence for the largest k up to 12), at
+    which there is a crop and a rectangle to blur with area and at least one JPEG name whose preview the plan restates, so that
+    it is made on the device.  Every product's own threshold is 0.0: what the detector returns is what they see"""
+    from megadetector_amd import blur as B, crops as K
+    confs = sorted((d['conf'] for r in results for d in r['detections']), reverse=True)
+    for k in range(min(12, len(confs)), 0, -1):
+        kept = {r['file']: [d for d in r['detections'] if d['conf'] >= confs[k - 1]] for r in results}
+        on_device = 0
+        for name, dets in kept.items():
+            try:
+                P.render_plan(dets, *P.target_size(*size_of[name], products['preview'].output_image_width), products['preview'])
+                on_device += K.is_jpeg_name(name)
+            except (P.HostLeg, P.RenderFailure):
+                pass
+        boxes = [(d['bbox'],) + size_of[name] for name, dets in kept.items() for d in dets]
+        if on_device and any(K.crop_rectangle(*b) for b in boxes) and any(B.blur_rectangle(*b) for b in boxes):
+            return confs[k - 1], k
+    raise AssertionError('no choice of boxes gives every product: {}'.format(confs[:12]))
+
+
+_PRODUCT_KEYS = ('crops', 'blurred', 'preview')
+_COUNTS = ('crop_counts', 'blur_counts', 'preview_counts')
+
+
+def _without_products(results):
+    return [{k: v for k, v in r.items() if k not in _PRODUCT_KEYS} for r in results]
+
+
+def _counts(det):
+    return {name: dict(getattr(det, name)) for name in _COUNTS}
+
+
+def _increase(det, before):
+    return {name: {k: v - before[name][k] for k, v in getattr(det, name).items()} for name in _COUNTS}
+
+
+def test_crops_blur_and_preview_together_equal_each_alone_synchronous_and_pipelined():
+    """two tickets outstanding, the second with two shape groups, and once more so that staging buffers handed out while
+    products were owed are themselves reused (as test_two_tickets_outstanding_and_the_second_holds_three_shape_groups)"""
+    from test_gpu_tile_jpeg import _image
+    det = _yolo_detector(4)
+    cuts = [(0, 0, 400, 300), (1500, 100, 333, 257), (100, 400, 640, 480), (500, 0, 300, 400), (0, 1100, 600, 400), (900, 900, 301, 199)]
+    imgs = [np.ascontiguousarray(_image()[y:y + h, x:x + w]) for x, y, w, h in cuts]
+    names = ['a.jpg', 'd/b.jpeg', 'c.JPG', 'e.png', 'f.jpg', 'g.jpg']
+    sources = [a.copy() for a in imgs]
+    shape = lambda a: tuple(det.preprocess_image(a)['img_processed'].shape)
+    assert len({shape(a) for a in imgs[:3]}) == 1 and len({shape(a) for a in imgs[3:]}) == 2
+    products = _all_products()
+    size_of = {n: (a.shape[1], a.shape[0]) for n, a in zip(names, imgs)}
+    threshold, k = _threshold_with_every_product(det.generate_detections_one_batch(imgs, names, detection_threshold=1e-5), size_of, products)
+    print('detection threshold {} keeps {} boxes'.format(threshold, k))
+    plain = det.generate_detections_one_batch(imgs, names, detection_threshold=threshold)
+    assert all(r.get('failure') is None for r in plain) and not any(key in r for r in plain for key in _PRODUCT_KEYS)
+    alone = {}
+    for (kw, options), key in zip(products.items(), _PRODUCT_KEYS):
+        res = det.generate_detections_one_batch(imgs, names, detection_threshold=threshold, **{kw: options})
+        assert _without_products(res) == plain and all(set(r) - set(p) == {key} for r, p in zip(res, plain))
+        alone[key] = [r[key] for r in res]
+
+    def check(results):
+        assert _without_products(results) == plain
+        for key in _PRODUCT_KEYS:
+            assert [r[key] for r in results] == alone[key], key
+
+    before = _counts(det)
+    check(det.generate_detections_one_batch(imgs, names, detection_threshold=threshold, **products))
+    synchronous = _increase(det, before)
+    for _ in range(2):
+        before = _counts(det)
+        tickets = [det.start_batch(imgs[:3], names[:3], detection_threshold=threshold, **products),
+                   det.start_batch(imgs[3:], names[3:], detection_threshold=threshold, **products)]
+        check(det.finish_batch(tickets[0]) + det.finish_batch(tickets[1]))
+        assert _increase(det, before) == synchronous
+    assert all(np.array_equal(a, b) for a, b in zip(imgs, sources))
+    print('increase of the counts in one run:', synchronous)
+    assert sum(len(c) for c in alone['crops']) >= 1 and sum(b is not None for b in alone['blurred']) >= 1
+    assert sum(leg == 'gpu' for _, leg in alone['preview']) >= 1
+    assert alone['preview'][3][1] in ('host', 'skipped')                              # the .png name: PIL saves it
+
+
+def test_already_letterboxed_inputs_crops_read_the_letterbox_blur_and_preview_the_original():
+    """the one branch where the products read different pixels: 'img_processed' is an array, so crops= cuts the letterboxed
+    pixels on the device, while blur= and preview= go to their host legs with 'img_original'"""
+    from megadetector_amd import blur as B
+    from test_blur_cpu import reference_blurred_file
+    from test_gpu_crop_encode import _host_crops
+    from test_gpu_tile_jpeg import _image
+    det = _yolo_detector(4)
+    products = _all_products()
+    batch = []
+    for i, (name, (x, y, w, h)) in enumerate([('a.jpg', (0, 0, 400, 300)), ('d/b.jpg', (500, 0, 300, 400))]):
+        info = det.preprocess_image(np.ascontiguousarray(_image()[y:y + h, x:x + w]), image_id=name)
+        info['file'] = name
+        hh, ww = info['img_processed'].shape[:2]
+        info['img_processed'] = np.ascontiguousarray(_image()[700 + 40 * i:700 + 40 * i + hh, 1000:1000 + ww])
+        assert info['img_processed'].shape == (hh, ww, 3) and info['img_processed'].dtype == np.uint8 and info['img_processed'].std() > 1
+        batch.append(info)
+    letterboxed = [info['img_processed'].copy() for info in batch]
+    originals = [info['img_original'].copy() for info in batch]
+    first = det.generate_detections_one_batch(batch, detection_threshold=1e-5)
+    confs = sorted((d['conf'] for r in first for d in r['detections']), reverse=True)
+    assert confs, 'the test has no detection'
+    threshold = confs[min(8, len(confs)) - 1]
+    plain = det.generate_detections_one_batch(batch, detection_threshold=threshold)
+    before = _counts(det)
+    got = det.generate_detections_one_batch(batch, detection_threshold=threshold, **products)
+    assert _without_products(got) == plain and all(r.get('failure') is None for r in got)
+    for r, info, lb, original in zip(got, batch, letterboxed, originals):
+        assert np.array_equal(info['img_processed'], lb) and np.array_equal(info['img_original'], original)
+        assert r['crops'] == _host_crops(lb, r['file'], r['detections'], products['crops'])
+        assert r['blurred'] == reference_blurred_file(original, r['file'], r['detections'], products['blur'])
+        data, leg = r['preview']
+        assert leg == 'host' and data == P.preview_file_of_host_image(original, r['file'], r['detections'], products['preview'])
+    n_crops, n_blurred = sum(len(r['crops']) for r in got), sum(r['blurred'] is not None for r in got)
+    print('crops:', n_crops, 'blurred:', n_blurred)
+    assert n_crops >= 1 and n_blurred >= 1
+    assert _increase(det, before) == {'crop_counts': {'gpu': n_crops, 'host': 0, 'skipped': sum(len(r['detections']) for r in got) - n_crops},
+                                      'blur_counts': {'gpu': 0, 'host': n_blurred}, 'preview_counts': {'gpu': 0, 'host': 2, 'skipped': 0}}
