@@ -361,6 +361,39 @@ int mdhip_draw_ops(mdhip_ctx* ctx, uint8_t* const* images, const int32_t* widths
                    int n_images, const int32_t* op_image, const int32_t* ops, int n_ops, const uint8_t* patches, int64_t patch_bytes,
                    void* hip_stream);
 
+/* The input of a species classifier for n detections of a batch, from the images that are in device memory already (the
+ * reference: classification/crop_detections.py save_crop writes a crop file per detection, classification/run_classifier.py
+ * reads it back and applies Resize(size, BICUBIC), CenterCrop(size), ToTensor, Normalize): ONE launch takes every crop from
+ * its image to out[i] = fp32 [3][size][size], bit for bit what those steps give for the same pixels (csrc/resample.h, shared
+ * with the host model mdjpeg_classifier_input).
+ * A crop is a CANVAS of canvas_w x canvas_h pixels: the rectangle src_w x src_h at (off_x, off_y) holds image pixels, the
+ * rest is 0 (a box that leaves its image, or one padded to a square).  The canvas is resized with Pillow's arithmetic --
+ * the shorter side to `size`, the longer to int(size * longer / shorter); integer weights of 22 bits, 8 bits between the
+ * horizontal and the vertical pass, an axis whose size stays is not resampled -- the size x size centre is kept (offsets
+ * int(round((n - size) / 2)), a half to the even neighbour), and a byte v of channel c becomes
+ * ((float)v / 255 - mean[c]) / std[c], from a table computed on the host in fp32.  Only that centre is computed, and the
+ * canvas is never built: a tap outside the rectangle contributes 0.
+ *   crops, n     n records (HOST memory), 0 .. 65535; the pixels they name are DEVICE memory, R G B interleaved
+ *   size         1 .. 4096
+ *   filter       0 bicubic (the reference), 1 bilinear, 2 LANCZOS: Pillow's filters of those names
+ *   mean, std    per channel; std != 0
+ *   out          DEVICE, n * 3 * size * size floats; nothing else is written, no source is changed
+ * MDHIP_EINVAL, with nothing enqueued, for a host pointer, a rectangle that leaves its canvas, sizes outside the ranges, an
+ * unknown filter or a std of 0.  MDHIP_EUNSUPPORTED, with nothing enqueued, when the canvas rows one output row needs do not
+ * fit on chip even for a single column (a canvas reduced more than about 1800 times with LANCZOS, 2700 with bicubic); the
+ * caller makes that crop on the host.  The call only enqueues.  Scratch -- the float table, the records and the
+ * coefficient tables -- belongs to the context and grows on demand (the device is synchronised when it does): keep all
+ * mdhip_classifier_input calls of one context on ONE stream. */
+typedef struct {
+    const uint8_t* src;          /* DEVICE: first image pixel that lies in the canvas           */
+    int64_t  pitch;              /* bytes a row of the image (>= 3 * src_w, any value)          */
+    int32_t  src_w, src_h;       /* the part of the canvas that holds image pixels, >= 1        */
+    int32_t  canvas_w, canvas_h; /* 1 .. 65535                                                  */
+    int32_t  off_x, off_y;       /* where that part lies in the canvas; the rest of it is 0     */
+} mdhip_classifier_crop;
+int mdhip_classifier_input(mdhip_ctx* ctx, const mdhip_classifier_crop* crops, int n, int size, int filter, const float mean[3],
+                           const float std[3], float* out, void* hip_stream);
+
 /* Test-time augmentation: replaces mdhip_forward for `model(batch, augment=True)` (reference
  * pytorch_detector.py:1313 -> yolov5 _forward_augment): three passes over the batch that mdhip_preprocess
  * left in the context -- scale 1, scale 0.83 left-right flipped, scale 0.67 (bilinear, padded with 0.447 to

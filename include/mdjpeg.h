@@ -137,6 +137,18 @@ int mdjpeg_resample(const uint8_t* src, int32_t width, int32_t height, int64_t p
 int mdjpeg_draw(uint8_t* rgb, int32_t width, int32_t height, int64_t pitch, const int32_t* ops, int n_ops, const uint8_t* patches,
                 int64_t patch_bytes);
 
+/* ---- classifier input (GPU: mdhip_classifier_input, include/mdhip.h) ---------------------------------------------------- */
+/* The host model of the GPU call for ONE crop, compiled from the header the kernel is compiled from (csrc/resample.h): the
+ * canvas_w x canvas_h canvas whose rectangle src_w x src_h at (off_x, off_y) holds the pixels at `src` (`pitch` bytes a row)
+ * and is 0 elsewhere, resized with Pillow's filter (0 bicubic, 1 bilinear, 2 LANCZOS) so that its shorter side is `size`,
+ * the size x size centre, (v / 255 - mean) / std: out = fp32 [3][size][size], bit for bit what PIL and torchvision give.
+ * mdjpeg_classifier_plan: plan[0] output columns and plan[1] output rows a workgroup takes of a crop of that canvas with
+ * lds_bytes of on-chip memory (0: what the device has); MDJPEG_EUNSUPPORTED when nothing fits -- the sizes the GPU call
+ * refuses. */
+int mdjpeg_classifier_input(const uint8_t* src, int64_t pitch, int32_t src_w, int32_t src_h, int32_t canvas_w, int32_t canvas_h,
+                            int32_t off_x, int32_t off_y, int32_t size, int32_t filter, const float mean[3], const float std[3], float* out);
+int mdjpeg_classifier_plan(int32_t canvas_w, int32_t canvas_h, int32_t size, int32_t filter, int32_t lds_bytes, int32_t plan[2]);
+
 const char* mdjpeg_version(void);
 
 #ifdef __cplusplus

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, 'libmdhip.so')
 
 MDHIP_OK = 0
 MDHIP_ECAPACITY = -5
+MDHIP_EUNSUPPORTED = -4
 MDHIP_DTYPE_BF16 = 0
 MDHIP_DTYPE_FP8 = 1
 MDHIP_DTYPE_FP16 = 2
@@ -51,6 +52,11 @@ class mdhip_jpeg_image(C.Structure):
 
 class mdhip_jpeg_scan(C.Structure):
     _fields_ = [('scan', C.c_void_p), ('desc', C.c_void_p), ('seg_offsets', C.c_void_p), ('coef', C.c_void_p)]
+
+
+class mdhip_classifier_crop(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('pitch', C.c_int64), ('src_w', C.c_int32), ('src_h', C.c_int32),
+                ('canvas_w', C.c_int32), ('canvas_h', C.c_int32), ('off_x', C.c_int32), ('off_y', C.c_int32)]
 
 
 class mdhip_op_info(C.Structure):
@@ -90,6 +96,8 @@ SYMBOLS = {
                                          C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), _P]),
     'mdhip_draw_ops': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int,
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, _P, C.c_int64, _P]),
+    'mdhip_classifier_input': (C.c_int, [_P, C.POINTER(mdhip_classifier_crop), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                         C.POINTER(C.c_float), _P, _P]),
     'mdhip_forward_tta': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_last_num_anchors': (C.c_int, [_P]),
     'mdhip_calibrate': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),

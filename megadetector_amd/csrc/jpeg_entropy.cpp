@@ -14,6 +14,8 @@
 #include "blur_box.h"
 #include "resample.h"
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -811,7 +813,63 @@ int mdjpeg_draw(uint8_t* rgb, int32_t width, int32_t height, int64_t pitch, cons
     return MDJPEG_OK;
 }
 
-const char* mdjpeg_version(void) { return "mdjpeg 5"; }
+// The host model of mdhip_classifier_input for one crop: tile by tile as the workgroups run it -- the horizontal pass of the
+// canvas rows a tile's vertical taps cover into an 8-bit tile of exactly that size, then the vertical pass and the lookup.
+int mdjpeg_classifier_input(const uint8_t* src, int64_t pitch, int32_t src_w, int32_t src_h, int32_t canvas_w, int32_t canvas_h,
+                            int32_t off_x, int32_t off_y, int32_t size, int32_t filter, const float mean[3], const float std[3], float* out) {
+    if (!src || !mean || !std || !out || src_w < 1 || src_h < 1 || canvas_w < 1 || canvas_h < 1 || canvas_w > 65535 || canvas_h > 65535 ||
+        pitch < int64_t(src_w) * 3 || off_x < 0 || off_y < 0 || off_x > canvas_w - src_w || off_y > canvas_h - src_h || size < 1 ||
+        size > MD_CLASSIFY_MAX_SIZE || filter < MD_FILTER_BICUBIC || filter > MD_FILTER_LANCZOS)
+        return MDJPEG_EINVAL;
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(mean[c]) || !std::isfinite(std[c]) || std[c] == 0.0f) return MDJPEG_EINVAL;
+    std::vector<int32_t> table;
+    std::vector<double> work;
+    MdClassifyCrop d;
+    memset(&d, 0, sizeof(d));
+    if (!md_classify_build(filter, canvas_w, canvas_h, size, MD_CLASSIFY_LDS_BYTES, table, work, &d)) return MDJPEG_EUNSUPPORTED;
+    d.src = src, d.pitch = pitch, d.src_w = src_w, d.src_h = src_h, d.off_x = off_x, d.off_y = off_y;
+    std::vector<float> lut(3 * 256);
+    md_classify_lut(mean, std, lut.data());
+    for (int g = 0; g < d.row_tiles; ++g)
+        for (int k = 0; k < d.strips; ++k) {
+            const int x0 = k * d.strip, nx = std::min(d.strip, size - x0);
+            const int r0 = g * d.rows, nr = std::min(d.rows, size - r0);
+            const int tile_pitch = nx * 3;
+            int first, count;
+            md_classify_rows(d, table.data(), r0, r0 + nr, &first, &count);
+            if (int64_t(count) * tile_pitch > MD_CLASSIFY_LDS_BYTES) return MDJPEG_EINVAL;
+            std::vector<uint8_t> tile(size_t(count) * tile_pitch);       // (exact: the sanitizers see an access outside it)
+            for (int i = 0; i < count * tile_pitch; ++i) {
+                const int j = i / tile_pitch, b = i - j * tile_pitch;
+                tile[size_t(i)] = md_classify_hsample(d, table.data(), first + j, x0 + b / 3, b % 3);
+            }
+            for (int i = 0; i < 3 * nr * nx; ++i) {
+                const int q = i / nx, px = i - q * nx;
+                const int c = q / nr, y = r0 + (q - c * nr);
+                const uint8_t v = md_classify_vsample(d, table.data(), tile.data(), tile_pitch, first, y, px * 3 + c);
+                out[(size_t(c) * size + y) * size + x0 + px] = lut[size_t(c) * 256 + v];
+            }
+        }
+    return MDJPEG_OK;
+}
+
+// the tile a workgroup takes of a crop of this canvas: plan[0] output columns, plan[1] output rows; MDJPEG_EUNSUPPORTED when
+// none fits lds_bytes (0: what the device has)
+int mdjpeg_classifier_plan(int32_t canvas_w, int32_t canvas_h, int32_t size, int32_t filter, int32_t lds_bytes, int32_t plan[2]) {
+    if (!plan || canvas_w < 1 || canvas_h < 1 || canvas_w > 65535 || canvas_h > 65535 || size < 1 || size > MD_CLASSIFY_MAX_SIZE ||
+        filter < MD_FILTER_BICUBIC || filter > MD_FILTER_LANCZOS || lds_bytes < 0)
+        return MDJPEG_EINVAL;
+    std::vector<int32_t> table;
+    std::vector<double> work;
+    MdClassifyCrop d;
+    memset(&d, 0, sizeof(d));
+    if (!md_classify_build(filter, canvas_w, canvas_h, size, lds_bytes ? lds_bytes : MD_CLASSIFY_LDS_BYTES, table, work, &d)) return MDJPEG_EUNSUPPORTED;
+    plan[0] = d.strip, plan[1] = d.rows;
+    return MDJPEG_OK;
+}
+
+const char* mdjpeg_version(void) { return "mdjpeg 6"; }
 
 }  // extern "C"
 
@@ -905,7 +963,49 @@ static int preview_matrix() {
     return 0;
 }
 
+// `--classify`: mdjpeg_classifier_input on heap images of exactly pitch x (src_h - 1) + 3 x src_w bytes and an output of
+// exactly 3 x size x size floats -- reducing, enlarging, a single column, an unchanged size, more than one strip, canvases
+// with zeros on every side, the three filters -- so that the sanitizers see any access outside a rectangle or the tensor.
+static int classify_matrix() {
+    // src_w, src_h, canvas_w, canvas_h, off_x, off_y, size, pitch (0: 3 x src_w)
+    const int shapes[][8] = {{97, 61, 97, 61, 0, 0, 32, 0},     {5, 7, 5, 7, 0, 0, 32, 0},         {1, 9, 1, 9, 0, 0, 32, 0},
+                             {301, 187, 301, 187, 0, 0, 32, 908}, {333, 500, 333, 500, 0, 0, 80, 0}, {80, 200, 80, 200, 0, 0, 80, 245},
+                             {640, 480, 640, 480, 0, 0, 224, 0}, {1300, 40, 1300, 40, 0, 0, 32, 0}, {40, 30, 50, 50, 10, 0, 32, 0},
+                             {40, 30, 50, 50, 0, 20, 32, 0},     {40, 30, 50, 50, 0, 0, 32, 121},   {21, 17, 60, 60, 20, 30, 32, 0},
+                             {13, 20, 20, 20, 4, 0, 32, 0},      {2, 2, 3000, 3000, 1500, 1500, 8, 0}};
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+    int runs = 0;
+    for (const auto& q : shapes)
+        for (int filter = 0; filter < 3; ++filter) {
+            const int64_t pitch = q[7] ? q[7] : int64_t(q[0]) * 3;
+            const size_t bytes = size_t(pitch) * (q[1] - 1) + size_t(q[0]) * 3;
+            const int shift = runs & 3;                                  // every alignment of the first byte
+            uint8_t* a = new uint8_t[bytes + shift];
+            float* o = new float[size_t(3) * q[6] * q[6]];
+            uint32_t seed = 99u + uint32_t(runs);
+            for (size_t i = 0; i < bytes + shift; ++i) a[i] = uint8_t((seed = seed * 1664525u + 1013904223u) >> 24);
+            const int rc = mdjpeg_classifier_input(a + shift, pitch, q[0], q[1], q[2], q[3], q[4], q[5], q[6], filter, mean, stdv, o);
+            delete[] a;
+            delete[] o;
+            if (rc != MDJPEG_OK) { printf("classify: %dx%d in %dx%d at %d, filter %d: %d\n", q[0], q[1], q[2], q[3], q[6], filter, rc); return 7; }
+            ++runs;
+        }
+    uint8_t px[3] = {1, 2, 3};
+    float o1[3];
+    const float zero[3] = {0.229f, 0.0f, 0.225f};
+    int32_t plan[2];
+    const int bad[] = {mdjpeg_classifier_input(px, 3, 1, 1, 1, 1, 0, 0, 1, 3, mean, stdv, o1), mdjpeg_classifier_input(px, 3, 1, 1, 1, 1, 0, 0, 1, 0, mean, zero, o1),
+                       mdjpeg_classifier_input(px, 3, 1, 1, 4, 4, 4, 0, 1, 0, mean, stdv, o1), mdjpeg_classifier_input(px, 3, 1, 1, 1, 1, 0, 0, 0, 0, mean, stdv, o1)};
+    for (int rc : bad)
+        if (rc != MDJPEG_EINVAL) { printf("classify: a bad argument gives %d\n", rc); return 7; }
+    if (mdjpeg_classifier_input(px, 3, 1, 1, 1, 1, 0, 0, 1, 0, mean, stdv, o1) != MDJPEG_OK) return 7;
+    if (mdjpeg_classifier_plan(65535, 65535, 8, MD_FILTER_LANCZOS, 0, plan) != MDJPEG_EUNSUPPORTED) { printf("classify: plan\n"); return 7; }
+    printf("classify: %d runs\n", runs);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc == 2 && !strcmp(argv[1], "--classify")) return classify_matrix();
     if (argc == 2 && !strcmp(argv[1], "--preview")) return preview_matrix();
     if (argc == 2 && !strcmp(argv[1], "--blur")) return blur_matrix();
     for (int i = 1; i < argc; ++i) {

@@ -1,11 +1,12 @@
 // The image entry points of the C ABI (include/mdhip.h): letterbox (mdhip_preprocess*), JPEG (mdhip_jpeg_*), mdhip_blur_regions,
-// the previews (mdhip_resample_lanczos, mdhip_draw_ops).
+// the previews (mdhip_resample_lanczos, mdhip_draw_ops), the classifier input (mdhip_classifier_input).
 // None of them looks at the model: they check their arguments, lay out scratch in one of the context's growable buffers
 // (mdhip_ctx.h DevBuffer) and launch.  What their checks have in common is written once, below; where two entry points
 // apply the same checks in a different order, each keeps its own order (the first failing check is what a caller sees).
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <utility>
@@ -782,6 +783,70 @@ int mdhip_draw_ops(mdhip_ctx* ctx, uint8_t* const* images, const int32_t* widths
     HIP_TRY(ctx, hipMemcpyAsync(base + o_recs, recs.data(), recs.size() * sizeof(DrawImage), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemcpyAsync(base + o_ops, sorted.data(), sorted.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, launch_draw_ops((const DrawImage*)(base + o_recs), (int)recs.size(), max_w, max_h, (const int32_t*)(base + o_ops), patches, s));
+    return MDHIP_OK;
+}
+
+int mdhip_classifier_input(mdhip_ctx* ctx, const mdhip_classifier_crop* crops, int n, int size, int filter, const float mean[3],
+                           const float std[3], float* out, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (n == 0) return MDHIP_OK;
+    if (!crops || !mean || !std || !out) return fail(ctx, MDHIP_EINVAL, "crops/mean/std/out is NULL");
+    if (n < 1 || n > 65535) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
+    if (size < 1 || size > MD_CLASSIFY_MAX_SIZE) return fail(ctx, MDHIP_EINVAL, "size = %d (1 .. %d)", size, MD_CLASSIFY_MAX_SIZE);
+    if (filter != MD_FILTER_BICUBIC && filter != MD_FILTER_BILINEAR && filter != MD_FILTER_LANCZOS)
+        return fail(ctx, MDHIP_EINVAL, "filter %d (0 = bicubic, 1 = bilinear, 2 = lanczos)", filter);
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(mean[c]) || !std::isfinite(std[c]) || std[c] == 0.0f)
+            return fail(ctx, MDHIP_EINVAL, "channel %d: mean %g, std %g", c, (double)mean[c], (double)std[c]);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!is_device_ptr(out)) return fail(ctx, MDHIP_EINVAL, "host pointer -- out must be device memory");
+    // every crop is checked and planned before anything is enqueued; crops of one canvas size share their tables
+    std::map<std::pair<int, int>, MdClassifyCrop> planned;
+    std::vector<MdClassifyCrop> recs((size_t)n);
+    std::vector<int32_t> table;
+    std::vector<double> work;
+    int max_blocks = 1;
+    for (int i = 0; i < n; ++i) {
+        const mdhip_classifier_crop& q = crops[i];
+        if (q.canvas_w < 1 || q.canvas_h < 1 || q.canvas_w > 65535 || q.canvas_h > 65535)
+            return fail(ctx, MDHIP_EINVAL, "crop %d: a canvas of %dx%d", i, q.canvas_w, q.canvas_h);
+        if (int rc = check_window(ctx, "crop", i, q.src_w, q.src_h, q.pitch)) return rc;
+        if (q.off_x < 0 || q.off_y < 0 || q.off_x > q.canvas_w - q.src_w || q.off_y > q.canvas_h - q.src_h)
+            return fail(ctx, MDHIP_EINVAL, "crop %d: %dx%d pixels at (%d, %d) leave the %dx%d canvas", i, q.src_w, q.src_h, q.off_x, q.off_y,
+                        q.canvas_w, q.canvas_h);
+        if (!q.src || !is_device_ptr(q.src)) return fail(ctx, MDHIP_EINVAL, "crop %d: NULL or a host pointer -- the pixels must be device memory", i);
+        auto it = planned.find({q.canvas_w, q.canvas_h});
+        if (it == planned.end()) {
+            MdClassifyCrop d;
+            memset(&d, 0, sizeof(d));
+            if (!md_classify_build(filter, q.canvas_w, q.canvas_h, size, MD_CLASSIFY_LDS_BYTES, table, work, &d))
+                return fail(ctx, MDHIP_EUNSUPPORTED, "crop %d: the rows one output row of a %dx%d canvas at size %d needs do not fit on chip", i,
+                            q.canvas_w, q.canvas_h, size);
+            if (table.size() > 0x7fff0000u / sizeof(int32_t)) return fail(ctx, MDHIP_EUNSUPPORTED, "crop %d: the coefficient tables pass 2 GB", i);
+            it = planned.emplace(std::make_pair(q.canvas_w, q.canvas_h), d).first;
+        }
+        MdClassifyCrop& d = recs[(size_t)i];
+        d = it->second;
+        d.src = q.src, d.pitch = q.pitch, d.src_w = q.src_w, d.src_h = q.src_h, d.off_x = q.off_x, d.off_y = q.off_y;
+        if ((long long)d.strips * d.row_tiles > 0x7fffffffLL) return fail(ctx, MDHIP_EUNSUPPORTED, "crop %d: too many tiles", i);
+        max_blocks = std::max(max_blocks, d.strips * d.row_tiles);
+    }
+    // the scratch: [float table][records][coefficient tables]
+    ScratchLayout lay;
+    const size_t o_lut = lay.take(3 * 256 * sizeof(float));
+    const size_t o_recs = lay.take(recs.size() * sizeof(MdClassifyCrop));
+    const size_t o_table = lay.take(std::max<size_t>(table.size(), 1) * sizeof(int32_t));
+    if (int rc = ctx->classify.reserve(ctx, lay.size)) return rc;
+    uint8_t* base = (uint8_t*)ctx->classify.p;
+    float lut[3 * 256];
+    md_classify_lut(mean, std, lut);
+    // (the uploads are from pageable memory: the copies have left the buffers when the call returns)
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_lut, lut, sizeof(lut), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_recs, recs.data(), recs.size() * sizeof(MdClassifyCrop), hipMemcpyHostToDevice, s));
+    if (!table.empty()) HIP_TRY(ctx, hipMemcpyAsync(base + o_table, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, launch_classifier_input((const MdClassifyCrop*)(base + o_recs), n, max_blocks, (const int32_t*)(base + o_table),
+                                         (const float*)(base + o_lut), out, s));
     return MDHIP_OK;
 }
 

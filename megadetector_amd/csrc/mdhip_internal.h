@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct MdClassifyCrop;             // resample.h: the record of a crop of mdhip_classifier_input
+
 struct MdjImage;
 struct MdjEncCrop;
 struct MdjEncTables;
@@ -579,5 +581,12 @@ struct DrawImage {
 hipError_t launch_resample_rows(const ResampleRows* descs, int n, int max_blocks, const int32_t* table, hipStream_t s);
 hipError_t launch_resample_columns(const ResampleColumns* descs, int n, int max_row_bytes, int max_out_h, const int32_t* table, hipStream_t s);
 hipError_t launch_draw_ops(const DrawImage* images, int n, int max_w, int max_h, const int32_t* ops, const uint8_t* patches, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------
+// Classifier input (classify_kernels.cpp): n crops -> fp32 [n][3][S][S], one record per crop (blockIdx.y), one launch.
+// The record (MdClassifyCrop) is resample.h's; max_blocks: the largest strips * row_tiles among the n records
+// ---------------------------------------------------------------------------------------
+hipError_t launch_classifier_input(const MdClassifyCrop* crops, int n, int max_blocks, const int32_t* table, const float* lut, float* out,
+                                   hipStream_t s);
 
 }  // namespace mdhip

@@ -1,5 +1,6 @@
-// Pillow's LANCZOS resize and the drawing of annotated previews, shared by the GPU kernels (preview_kernels.cpp) and their
-// host models (mdjpeg_resample, mdjpeg_draw in jpeg_entropy.cpp): ONE computation of the coefficient tables, ONE weighted
+// Pillow's resize (LANCZOS for the annotated previews; bicubic, bilinear and LANCZOS for the classifier input, at the end of
+// this file), and the drawing of the previews, shared by the GPU kernels (preview_kernels.cpp, classify_kernels.cpp) and their
+// host models (mdjpeg_resample, mdjpeg_draw, mdjpeg_classifier_input in jpeg_entropy.cpp): ONE computation of the coefficient tables, ONE weighted
 // sum of a run of samples, ONE walk of a pixel through its image's drawing operations, compiled by both, so that the CPU
 // suite and the host sanitizers exercise the very statements the lanes run (the arrangement of blur_box.h).
 //
@@ -23,6 +24,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <vector>
+
 #if defined(__HIPCC__)
 #define MDR_HD __host__ __device__
 #else
@@ -44,21 +47,50 @@ static inline double md_lanczos3(double x) {
     return (sin(a) / a) * (x / 3.0 == 0.0 ? 1.0 : sin(b) / b);
 }
 
-// taps a line of the table has room for (Resample.c precompute_coeffs: ksize)
-static inline int md_resample_ksize(int in_size, int out_size) {
-    double filterscale = (double)in_size / out_size;
-    if (filterscale < 1.0) filterscale = 1.0;
-    return (int)ceil(3.0 * filterscale) * 2 + 1;
+// Pillow's other filters (Resample.c bicubic_filter with a = -0.5, bilinear_filter), for the classifier input
+#define MD_FILTER_BICUBIC 0
+#define MD_FILTER_BILINEAR 1
+#define MD_FILTER_LANCZOS 2
+
+static inline double md_bicubic(double x) {
+    const double a = -0.5;
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
 }
 
-// precompute_coeffs + normalize_coeffs_8bpc: bounds[2 i] = first tap, bounds[2 i + 1] = count, kk[i ksize ..] the integer
-// weights of output index i (zero behind the count); `work` holds ksize doubles
-static inline void md_resample_coeffs(int in_size, int out_size, int ksize, int32_t* bounds, int32_t* kk, double* work) {
+static inline double md_bilinear(double x) {
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return 1.0 - x;
+    return 0.0;
+}
+
+static inline double md_filter_support(int filter) { return filter == MD_FILTER_BICUBIC ? 2.0 : filter == MD_FILTER_BILINEAR ? 1.0 : 3.0; }
+
+static inline double md_filter_value(int filter, double x) {
+    return filter == MD_FILTER_BICUBIC ? md_bicubic(x) : filter == MD_FILTER_BILINEAR ? md_bilinear(x) : md_lanczos3(x);
+}
+
+// taps a line of the table has room for (Resample.c precompute_coeffs: ksize)
+static inline int md_resample_ksize_filter(int filter, int in_size, int out_size) {
+    double filterscale = (double)in_size / out_size;
+    if (filterscale < 1.0) filterscale = 1.0;
+    return (int)ceil(md_filter_support(filter) * filterscale) * 2 + 1;
+}
+
+static inline int md_resample_ksize(int in_size, int out_size) { return md_resample_ksize_filter(MD_FILTER_LANCZOS, in_size, out_size); }
+
+// precompute_coeffs + normalize_coeffs_8bpc for the output indices o0 .. o1 - 1 of an axis resampled in_size -> out_size
+// with `filter`: bounds[2 i] = first tap, bounds[2 i + 1] = count, kk[i ksize ..] the integer weights of output index
+// o0 + i (zero behind the count); `work` holds ksize doubles
+static inline void md_resample_coeffs_filter(int filter, int in_size, int out_size, int o0, int o1, int ksize, int32_t* bounds,
+                                             int32_t* kk, double* work) {
     const double scale = (double)in_size / out_size;
     const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 3.0 * filterscale;
+    const double support = md_filter_support(filter) * filterscale;
     const double ss = 1.0 / filterscale;
-    for (int xx = 0; xx < out_size; ++xx) {
+    for (int xx = o0; xx < o1; ++xx) {
         const double center = (xx + 0.5) * scale;
         double ww = 0.0;
         int xmin = (int)(center - support + 0.5);
@@ -68,19 +100,24 @@ static inline void md_resample_coeffs(int in_size, int out_size, int ksize, int3
         xmax -= xmin;
         if (xmax > ksize) xmax = ksize;                                  // (never: ksize bounds the run)
         for (int x = 0; x < xmax; ++x) {
-            const double w = md_lanczos3((x + xmin - center + 0.5) * ss);
+            const double w = md_filter_value(filter, (x + xmin - center + 0.5) * ss);
             work[x] = w;
             ww += w;
         }
-        int32_t* k = kk + (size_t)xx * ksize;
+        int32_t* k = kk + (size_t)(xx - o0) * ksize;
         for (int x = 0; x < xmax; ++x) {
             const double w = ww != 0.0 ? work[x] / ww : work[x];
             k[x] = w < 0 ? (int32_t)(-0.5 + w * (1 << MD_RESAMPLE_PRECISION_BITS)) : (int32_t)(0.5 + w * (1 << MD_RESAMPLE_PRECISION_BITS));
         }
         for (int x = xmax; x < ksize; ++x) k[x] = 0;
-        bounds[2 * xx] = xmin;
-        bounds[2 * xx + 1] = xmax;
+        bounds[2 * (xx - o0)] = xmin;
+        bounds[2 * (xx - o0) + 1] = xmax;
     }
+}
+
+// the whole table of the LANCZOS filter (the previews): output indices 0 .. out_size - 1
+static inline void md_resample_coeffs(int in_size, int out_size, int ksize, int32_t* bounds, int32_t* kk, double* work) {
+    md_resample_coeffs_filter(MD_FILTER_LANCZOS, in_size, out_size, 0, out_size, ksize, bounds, kk, work);
 }
 
 // ---- one output sample --------------------------------------------------------------------------------------------------
@@ -159,6 +196,136 @@ MDR_HD static inline int md_draw_pixel(const int32_t* ops, int n, const uint8_t*
         return 1;
     }
     return 0;
+}
+
+// ---- classifier input ---------------------------------------------------------------------------------------------------
+//
+// What the reference feeds a classifier for one detection (classification/crop_detections.py save_crop, then
+// run_classifier.py: Resize(S, BICUBIC), CenterCrop(S), ToTensor, Normalize [3P: torchvision]): the crop is a CANVAS of
+// canvas_w x canvas_h pixels of which the rectangle src_w x src_h at (off_x, off_y) holds image pixels and the rest is 0;
+// the canvas is resized so that its shorter side is S (the longer int(S long / short)), the S x S centre is kept, and every
+// byte v of channel c becomes (v / 255 - mean[c]) / std[c] in fp32, planar.  Only the S x S window is computed and the
+// canvas is never built: a tap outside the rectangle contributes 0, but bounds and weights are those of the canvas.
+//
+// A workgroup takes `strip` output columns and `rows` output rows of a crop: the horizontal pass of the canvas rows its
+// vertical taps cover goes into an 8-bit tile on chip (md_classify_hsample), the vertical pass reads the tile
+// (md_classify_vsample).  Both are compiled by classify_kernels.cpp and by the host model mdjpeg_classifier_input.
+
+#define MD_CLASSIFY_LDS_BYTES 32768              // the 8-bit tile of a workgroup
+#define MD_CLASSIFY_STRIP 64                     // output columns of a workgroup at the most
+#define MD_CLASSIFY_MAX_ROWS 32                  // output rows of a workgroup at the most
+#define MD_CLASSIFY_MAX_SIZE 4096                // S at the most
+
+struct MdClassifyCrop {
+    const uint8_t* src;                  // the first image pixel that lies in the canvas
+    long long pitch;                     // bytes a row of the image
+    int32_t src_w, src_h, off_x, off_y;  // the part of the canvas that holds image pixels
+    int32_t size;                        // S
+    int32_t hb_off, hk_off, hks;         // horizontal table of output columns 0 .. S - 1 (int32 words into the table: bounds,
+                                         // weights; taps a line); hks 0 = the width stays: column x is canvas column hb_off + x
+    int32_t vb_off, vk_off, vks;         // vertical table of output rows 0 .. S - 1, likewise (vks 0: row y is canvas row vb_off + y)
+    int32_t strip, rows;                 // output columns and rows of a workgroup
+    int32_t strips, row_tiles;           // the crop runs strips * row_tiles workgroups
+};
+
+// the resized size of the canvas and where the S x S window lies in it [3P: torchvision Resize(int) and CenterCrop]
+static inline void md_classify_geometry(int canvas_w, int canvas_h, int size, int* resized_w, int* resized_h, int* left, int* top) {
+    const int lo = canvas_w <= canvas_h ? canvas_w : canvas_h, hi = canvas_w <= canvas_h ? canvas_h : canvas_w;
+    const int longer = (int)((double)((long long)size * hi) / (double)lo);
+    *resized_w = canvas_w <= canvas_h ? size : longer;
+    *resized_h = canvas_w <= canvas_h ? longer : size;
+    // int(round((n - S) / 2.0)), Python's round: a half goes to the even neighbour
+    const int dx = *resized_w - size, dy = *resized_h - size;
+    *left = dx / 2 + ((dx & 1) && ((dx / 2) & 1));
+    *top = dy / 2 + ((dy & 1) && ((dy / 2) & 1));
+}
+
+// canvas rows the output rows [r0, r1) of the window need: their first, and how many
+MDR_HD static inline void md_classify_rows(const MdClassifyCrop& d, const int32_t* table, int r0, int r1, int* first, int* count) {
+    if (!d.vks) { *first = d.vb_off + r0, *count = r1 - r0; return; }
+    const int32_t* vb = table + d.vb_off;
+    *first = vb[2 * r0];
+    *count = vb[2 * (r1 - 1)] + vb[2 * (r1 - 1) + 1] - *first;
+}
+
+// the plan of a crop: the widest strip, then the most rows, whose tile fits lds_bytes.  vbounds: the vertical bounds of the
+// window's rows, NULL when the height stays.  Returns 0 when the taps of one output row do not fit even for one column.
+static inline int md_classify_plan(const int32_t* vbounds, int size, int lds_bytes, int32_t* strip_out, int32_t* rows_out) {
+    for (int strip = MD_CLASSIFY_STRIP; strip >= 1; strip >>= 1)
+        for (int rows = MD_CLASSIFY_MAX_ROWS; rows >= 1; rows >>= 1) {
+            long long longest = 0;
+            for (int r0 = 0; r0 < size; r0 += rows) {
+                const int r1 = r0 + rows < size ? r0 + rows : size;
+                const long long n = vbounds ? (long long)vbounds[2 * (r1 - 1)] + vbounds[2 * (r1 - 1) + 1] - vbounds[2 * r0] : r1 - r0;
+                if (n > longest) longest = n;
+            }
+            if (longest * strip * 3 > lds_bytes) continue;
+            *strip_out = strip, *rows_out = rows;
+            return 1;
+        }
+    return 0;
+}
+
+// byte c of output column x (of the window) in canvas row yy: the horizontal pass, or the canvas byte when the width stays
+MDR_HD static inline uint8_t md_classify_hsample(const MdClassifyCrop& d, const int32_t* table, int yy, int x, int c) {
+    const int sy = yy - d.off_y;
+    if (sy < 0 || sy >= d.src_h) return 0;
+    const uint8_t* row = d.src + (long long)sy * d.pitch + c;
+    if (!d.hks) {
+        const int sx = d.hb_off + x - d.off_x;
+        return sx < 0 || sx >= d.src_w ? 0 : row[(long long)sx * 3];
+    }
+    const int32_t* hb = table + d.hb_off;
+    const int32_t* k = table + d.hk_off + (long long)x * d.hks;
+    const int first = hb[2 * x] - d.off_x;                               // of the run, in pixels of the rectangle
+    const int i0 = first < 0 ? -first : 0;
+    const int i1 = hb[2 * x + 1] < d.src_w - first ? hb[2 * x + 1] : d.src_w - first;
+    if (i1 <= i0) return md_resample_clip8(1 << (MD_RESAMPLE_PRECISION_BITS - 1));
+    return md_resample_dot(row + (long long)(first + i0) * 3, 3, k + i0, i1 - i0);
+}
+
+// byte b (3 x + c within the strip) of output row y (of the window) from the tile whose row 0 is canvas row `first`
+MDR_HD static inline uint8_t md_classify_vsample(const MdClassifyCrop& d, const int32_t* table, const uint8_t* tile, int tile_pitch,
+                                                 int first, int y, int b) {
+    if (!d.vks) return tile[(long long)(d.vb_off + y - first) * tile_pitch + b];
+    const int32_t* vb = table + d.vb_off;
+    return md_resample_dot(tile + (long long)(vb[2 * y] - first) * tile_pitch + b, tile_pitch, table + d.vk_off + (long long)y * d.vks,
+                           vb[2 * y + 1]);
+}
+
+// the 3 x 256 floats a byte of channel c becomes: ToTensor (v / 255) and Normalize ((x - mean) / std) in fp32, on the host
+static inline void md_classify_lut(const float mean[3], const float std[3], float* lut) {
+    for (int c = 0; c < 3; ++c)
+        for (int v = 0; v < 256; ++v) {
+            volatile float x = (float)v / 255.0f;                        // (volatile: each step rounds to fp32, no contraction)
+            volatile float y = x - mean[c];
+            lut[c * 256 + v] = y / std[c];
+        }
+}
+
+// Tables and plan of one crop, appended to `table` (int32 words); fills everything of `d` but src / pitch / the rectangle.
+// Returns 0 when no plan fits lds_bytes.  `work` is scratch.
+static inline int md_classify_build(int filter, int canvas_w, int canvas_h, int size, int lds_bytes, std::vector<int32_t>& table,
+                                    std::vector<double>& work, MdClassifyCrop* d) {
+    int rw, rh, left, top;
+    md_classify_geometry(canvas_w, canvas_h, size, &rw, &rh, &left, &top);
+    d->size = size;
+    auto axis = [&](int in, int out, int o0, int32_t* b_off, int32_t* k_off, int32_t* ks) {
+        if (in == out) { *b_off = o0, *k_off = 0, *ks = 0; return; }
+        const int ksize = md_resample_ksize_filter(filter, in, out);
+        *ks = ksize;
+        *b_off = (int32_t)table.size();
+        *k_off = *b_off + 2 * size;
+        table.resize(table.size() + 2 * (size_t)size + (size_t)size * ksize);
+        work.resize((size_t)ksize);
+        md_resample_coeffs_filter(filter, in, out, o0, o0 + size, ksize, table.data() + *b_off, table.data() + *k_off, work.data());
+    };
+    axis(canvas_w, rw, left, &d->hb_off, &d->hk_off, &d->hks);
+    axis(canvas_h, rh, top, &d->vb_off, &d->vk_off, &d->vks);
+    if (!md_classify_plan(d->vks ? table.data() + d->vb_off : nullptr, size, lds_bytes, &d->strip, &d->rows)) return 0;
+    d->strips = (size + d->strip - 1) / d->strip;
+    d->row_tiles = (size + d->rows - 1) / d->rows;
+    return 1;
 }
 
 #endif  // MD_RESAMPLE_H

@@ -33,6 +33,7 @@ import numpy as np
 
 from . import weights_io
 from .blur import BlurProduct
+from .classify import ClassifyProduct
 from .crops import CropProduct
 from .preview import PreviewProduct
 from .constants import (FAILURE_IMAGE_OPEN, FAILURE_INFER, DEFAULT_COMPATIBILITY_MODE)
@@ -124,6 +125,7 @@ class HIPDetector:
         self.crop_counts = {'gpu': 0, 'host': 0, 'skipped': 0}      # crops= : encoded on the device / saved by PIL / without area
         self.blur_counts = {'gpu': 0, 'host': 0}                    # blur= : copies encoded on the device / saved by PIL
         self.preview_counts = {'gpu': 0, 'host': 0, 'skipped': 0}   # preview= : encoded on the device / rendered or saved by PIL / no file
+        self.classify_counts = {'gpu': 0, 'host': 0, 'skipped': 0}  # classify= : crops made by the kernel / by PIL / without a crop
         self.jpeg_entropy_fallbacks = 0         # scans the device flagged: decoded with PIL from the file's bytes instead
         if preprocess_only:
             return                      # never touches HIP: safe in forked producer processes
@@ -249,9 +251,11 @@ class HIPDetector:
     supports_crops = True
     supports_blur = True
     supports_preview = True
+    supports_classify = True
 
     def generate_detections_one_batch(self, img_original, image_id=None, detection_threshold=0.00001,
-                                      image_size=None, augment=False, verbose=False, crops=None, blur=None, preview=None):
+                                      image_size=None, augment=False, verbose=False, crops=None, blur=None, preview=None,
+                                      classify=None):
         """reference pytorch_detector.py:1124-1252.  crops (a crops.CropOptions, default None = off): every result dict gains
         'crops', a list of (crop_id, crop_filename_relative, bytes) -- the files create_crop_folder.py writes for the
         image's detections, encoded on the device from the pixels that are resident there (mdhip_jpeg_encode).
@@ -263,7 +267,12 @@ class HIPDetector:
         leg) -- the file visualize_detector_output.py writes for the image (blurred if asked, resized with Pillow's LANCZOS
         filter, boxes and labels drawn), made on the device from the resident pixels (mdhip_blur_regions on a copy,
         mdhip_resample_lanczos, mdhip_draw_ops, mdhip_jpeg_encode); leg is 'gpu', 'host' (PIL saved or rendered it) or
-        'skipped' (no file).  The resident pixels are not changed."""
+        'skipped' (no file).  The resident pixels are not changed.
+        classify (a classify.ClassifyOptions, default None = off): every result dict gains 'classifications', a list of
+        (detection_index, [[class_id, conf], ...]) -- what classification/run_classifier.py and
+        merge_classification_detection_output.py give the image's detections: the crops of a group go from the resident,
+        unblurred pixels to the model's input tensor in one launch per chunk (mdhip_classifier_input), the model runs on
+        the same stream, and the probabilities come back in one copy."""
         if not isinstance(img_original, list):
             raise ValueError('img_original must be a list for batch processing')
         if len(img_original) == 0:
@@ -288,7 +297,7 @@ class HIPDetector:
         if self._ctx is None:
             raise RuntimeError('this HIPDetector was created with preprocess_only')
         self._check_augment(augment)
-        products = self._products(crops, blur, preview)
+        products = self._products(crops, blur, preview, classify)
         img_original = self.decode_scans(img_original)
         results, shape_groups = self._prepare_batch(img_original, image_id, image_size, verbose)
         for shape, items in shape_groups.items():
@@ -302,9 +311,10 @@ class HIPDetector:
                     results[original_idx] = {'file': current_id, 'detections': None, 'failure': FAILURE_INFER}
         return self._products_everywhere(results, products)
 
-    def _products(self, crops, blur, preview):
+    def _products(self, crops, blur, preview, classify=None):
         """the products asked for (crops.Product), in the order their kernels are enqueued"""
-        asked = ((CropProduct, crops, self.crop_counts), (BlurProduct, blur, self.blur_counts), (PreviewProduct, preview, self.preview_counts))
+        asked = ((CropProduct, crops, self.crop_counts), (ClassifyProduct, classify, self.classify_counts),
+                 (BlurProduct, blur, self.blur_counts), (PreviewProduct, preview, self.preview_counts))
         return [product(options, counts) for product, options, counts in asked if options is not None]
 
     @staticmethod
@@ -777,7 +787,7 @@ class HIPDetector:
                             pl['consumed'][handle['k']] = ev
 
     def start_batch(self, img_original, image_id, detection_threshold=0.00001, image_size=None, augment=False,
-                    verbose=False, crops=None, blur=None, preview=None):
+                    verbose=False, crops=None, blur=None, preview=None, classify=None):
         """Enqueues a batch; returns a ticket for finish_batch().  At most two tickets may be outstanding.
         Same arguments as generate_detections_one_batch (augment = yolov5's three-pass augmented inference)."""
         if self._ctx is None:
@@ -785,7 +795,7 @@ class HIPDetector:
         self._check_augment(augment)
         if detection_threshold is None:
             detection_threshold = 0.0
-        products = self._products(crops, blur, preview)
+        products = self._products(crops, blur, preview, classify)
         img_original = self.decode_scans(img_original)
         results, shape_groups = self._prepare_batch(img_original, image_id, image_size, verbose)
         chunks = []
@@ -827,12 +837,13 @@ class HIPDetector:
 
     # -----------------------------------------------------------------------------------
     def generate_detections_one_image(self, img_original, image_id='unknown', detection_threshold=0.00001,
-                                      image_size=None, augment=False, verbose=False, crops=None, blur=None, preview=None):
+                                      image_size=None, augment=False, verbose=False, crops=None, blur=None, preview=None,
+                                      classify=None):
         """reference pytorch_detector.py:1428-1478"""
         if isinstance(img_original, dict):
             res = self.generate_detections_one_batch([img_original], None, detection_threshold,
-                                                     image_size, augment, verbose, crops=crops, blur=blur, preview=preview)
+                                                     image_size, augment, verbose, crops=crops, blur=blur, preview=preview, classify=classify)
         else:
             res = self.generate_detections_one_batch([img_original], [image_id], detection_threshold,
-                                                     image_size, augment, verbose, crops=crops, blur=blur, preview=preview)
+                                                     image_size, augment, verbose, crops=crops, blur=blur, preview=preview, classify=classify)
         return res[0]

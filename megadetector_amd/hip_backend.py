@@ -356,6 +356,26 @@ class HipContext:
         self._check(self.lib.mdhip_draw_ops(self.h, C.cast(p, C.POINTER(C.c_void_p)), ws, hs, pt, n, oi, flat, m,
                                             C.c_void_p(int(patches_ptr) or None), int(patch_bytes), C.c_void_p(stream)), 'mdhip_draw_ops')
 
+    def classifier_input(self, crops, size, out_ptr, filter=0, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), stream=0):
+        """
+        The input tensor of a classifier for crops of device images, in one launch (include/mdhip.h: mdhip_classifier_input).
+        crops:   per crop (ptr, pitch, src_w, src_h, canvas_w, canvas_h, off_x, off_y): the device address of the first image
+                 pixel that lies in the canvas, the image's bytes a row, the part of the canvas that holds pixels, the canvas,
+                 where the part lies in it
+        size, filter, mean, std: the side of the tensor, 0 bicubic / 1 bilinear / 2 lanczos, the normalisation
+        out_ptr: device address of len(crops) x 3 x size x size floats
+        Returns True; False (MDHIP_EUNSUPPORTED, nothing enqueued) when a crop is reduced more than fits on chip.  Only enqueues.
+        """
+        n = len(crops)
+        if n == 0:
+            return True
+        recs = (_lib.mdhip_classifier_crop * n)(*[_lib.mdhip_classifier_crop(*[int(v) for v in q]) for q in crops])
+        rc = self.lib.mdhip_classifier_input(self.h, recs, n, int(size), int(filter), (C.c_float * 3)(*mean), (C.c_float * 3)(*std),
+                                             C.c_void_p(int(out_ptr)), C.c_void_p(stream))
+        if rc != _lib.MDHIP_EUNSUPPORTED:
+            self._check(rc, 'mdhip_classifier_input')
+        return rc == 0
+
     def forward(self, n, h, w, stream=0):
         self._check(self.lib.mdhip_forward(self.h, int(n), int(h), int(w), C.c_void_p(stream)), 'mdhip_forward')
 

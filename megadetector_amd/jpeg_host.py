@@ -57,6 +57,9 @@ SYMBOLS = {
     'mdjpeg_blur_weights': (C.c_int, [C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     'mdjpeg_resample': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64]),
     'mdjpeg_draw': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int64]),
+    'mdjpeg_classifier_input': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p]),
+    'mdjpeg_classifier_plan': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     'mdjpeg_version': (C.c_char_p, []),
 }
 
@@ -349,6 +352,34 @@ def draw_ops(rgb, ops, patches=b''):
     pbuf = np.frombuffer(bytes(patches), np.uint8) if not isinstance(patches, np.ndarray) else np.ascontiguousarray(patches, np.uint8)
     return load().mdjpeg_draw(rgb.ctypes.data, w, h, pitch, flat.ctypes.data_as(C.POINTER(C.c_int32)), len(flat),
                               pbuf.ctypes.data if pbuf.size else None, pbuf.size)
+
+
+def classifier_input(rgb, canvas, size, filter=0, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+    """
+    The classifier input of one crop (mdjpeg_classifier_input: the host model of the GPU call): rgb, an H x W x 3 uint8 array
+    whose rows may be strided, is the part of a canvas (canvas_w, canvas_h, off_x, off_y) that holds pixels; the rest of the
+    canvas is 0.  Returns float32 [3][size][size], or raises ValueError with the library's code.
+    """
+    w, h, pitch = _rgb_rows(rgb, False)
+    cw, ch, ox, oy = (int(v) for v in canvas)
+    out = np.empty((3, int(size), int(size)), np.float32)
+    rc = load().mdjpeg_classifier_input(rgb.ctypes.data, pitch, w, h, cw, ch, ox, oy, int(size), int(filter),
+                                        (C.c_float * 3)(*mean), (C.c_float * 3)(*std), out.ctypes.data)
+    if rc != MDJPEG_OK:
+        raise ValueError('mdjpeg_classifier_input returned {} for {} x {} in a canvas of {} x {} at size {}'.format(rc, w, h, cw, ch, size))
+    return out
+
+
+def classifier_plan(canvas_w, canvas_h, size, filter=0, lds_bytes=0):
+    """(output columns, output rows) a workgroup of the GPU call takes of a crop of this canvas, or None when the call
+    refuses it with MDHIP_EUNSUPPORTED (mdjpeg_classifier_plan; lds_bytes 0: what the device has)"""
+    plan = (C.c_int32 * 2)()
+    rc = load().mdjpeg_classifier_plan(int(canvas_w), int(canvas_h), int(size), int(filter), int(lds_bytes), plan)
+    if rc == MDJPEG_EUNSUPPORTED:
+        return None
+    if rc != MDJPEG_OK:
+        raise ValueError('mdjpeg_classifier_plan returned {}'.format(rc))
+    return plan[0], plan[1]
 
 
 def blur_weights(radius):

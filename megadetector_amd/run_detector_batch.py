@@ -40,6 +40,7 @@ from . import feed, placement, run_detector
 from .feed import load_image, EXIF_IMAGE_ROTATIONS          # noqa: F401  (re-exported)
 from .constants import FAILURE_IMAGE_OPEN, FAILURE_INFER, DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD
 from .constants import DEFAULT_DETECTOR_LABEL_MAP
+from . import classify as classify_mod
 from . import crops as crops_mod
 from . import blur as blur_mod
 from . import preview as preview_mod
@@ -166,6 +167,13 @@ last_blur_counts = {}
 #: below the threshold with detections_only, a resize target that is not positive, drawing that raises)
 last_preview_counts = {}
 
+#: classifications of the most recent run in this process (--classifier): {image file: [(detection index, [[class id,
+#: conf], ...])]}, the index counting the detections as the results file holds them; and the crops counted: 'gpu' = by a
+#: detector with classify= (its own classify_counts tell its kernel and its host leg apart), 'host' = made by PIL here (a
+#: detector without classify=), 'skipped' = detections without a crop
+last_classifications = {}
+last_classify_counts = {}
+
 
 def _relative_name(file, base):
     """the name an image's products are derived from: relative to the image folder (a lone file: its base name)"""
@@ -255,6 +263,48 @@ class _PreviewWriter(_Writer):
             self.counts['skipped'] += 1
             return []
         return [(preview_mod.output_name(rel, self.options), data, leg)]
+
+
+class _ClassifyWriter(_Writer):
+    """no folder and no files: takes an image's classifications off its result, so that the results and the checkpoints are
+    what they are without the classifier, and keeps them for the classified results file"""
+
+    keyword, count_keys = 'classify', ('gpu', 'host', 'skipped')
+
+    def __init__(self, options):
+        super().__init__(None, options, None)
+        self.collected = {}
+
+    def files(self, r, rel, pixels):
+        from_detector = 'classifications' in r
+        value = r.pop('classifications', None)
+        if r.get('detections') is None:
+            return []
+        if from_detector:
+            self.counts['gpu'] += len(value)
+        elif crops_mod.select_crops(crops_mod.output_order(r['detections'], self.options.output_threshold), self.options, self.category_ids):
+            # a detector without classify=: the host leg
+            value, skipped = classify_mod.classifications_of_host_image(pixels(), r['file'], r['detections'], self.options, self.category_ids)
+            self.counts['host'] += len(value)
+            self.counts['skipped'] += skipped
+        if value:
+            self.collected[r['file']] = value
+        return []
+
+
+def write_classified_results(final_output, classifications, options, path, relative_path_base=None):
+    """the results with 'classifications' on every classified detection, 'classification_categories' and the classifier in
+    'info' (merge_classification_detection_output.py:307-335), as a copy: the results themselves are not changed"""
+    def name(f):
+        if relative_path_base is not None:
+            f = os.path.relpath(f, start=relative_path_base)
+        return f.replace('\\', '/')
+    classified = copy.deepcopy(final_output)
+    classify_mod.annotate_results(classified, {name(f): v for f, v in classifications.items()}, options,
+                                  datetime.now().strftime('%Y-%m-%d %H:%M:%S'))
+    write_json(path, classified)
+    print('Classified results saved at {}'.format(path))
+    return classified
 
 
 def _detector_kw(writers, detector):
@@ -694,7 +744,7 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
                                 preview_folder=None, preview_width=1000, preview_confidence_threshold=0.15,
                                 preview_detections_only=False, preview_preserve_paths=False, preview_box_thickness=4,
                                 preview_box_expansion=0, preview_label_font_size=16, preview_label_font='arial.ttf',
-                                preview_blur_categories=None, preview_quality=75, preview_base=None):
+                                preview_blur_categories=None, preview_quality=75, preview_base=None, classify_options=None):
     """
     reference :1062-1439.  `detector` (extra, optional) injects an already constructed detector
     object -- used by run_sharded and by the CPU tests of the loop with a stub detector.
@@ -720,9 +770,14 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
     name relative to preview_base with slashes, backslashes and colons replaced by ~ (preview_preserve_paths: the relative path itself).  A detector
     with preview= (HIPDetector) does all of it on the GPU from the resident image; other detectors, and pixels that are not in
     device memory, go through PIL here.  The results are the same objects as without it.
+    `classify_options` (extra, default None = off; a classify.ClassifyOptions): every detection at or above its confidence
+    threshold is classified as classification/run_classifier.py classifies the reference's crop files.  A detector with
+    classify= (HIPDetector) makes the classifier's input on the GPU from the resident image and runs the model there; other
+    detectors go through PIL here.  The classifications are kept in last_classifications (write_classified_results writes
+    them); the results, and the checkpoints, are what they are without it.
     Returns the list of per-image result dicts.
     """
-    global verbose, last_crop_counts, last_blur_counts, last_preview_counts
+    global verbose, last_crop_counts, last_blur_counts, last_preview_counts, last_classifications, last_classify_counts
     verbose = bool(verbose_output)
     output_threshold = DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD if confidence_threshold is None else confidence_threshold
     writers = []
@@ -744,6 +799,10 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
             label_font=preview_label_font, blur_categories=preview_blur_categories, quality=preview_quality,
             output_threshold=output_threshold), preview_base))
         last_preview_counts = writers[-1].counts
+    if classify_options is not None:
+        classify_options.output_threshold = output_threshold
+        writers.append(_ClassifyWriter(classify_options))
+        last_classifications, last_classify_counts = writers[-1].collected, writers[-1].counts
     if detector_options is None:
         detector_options = {}
     elif isinstance(detector_options, (list, str)):
@@ -1121,8 +1180,33 @@ def main(argv=None):
     ap.add_argument('--preview_label_font', type=str, default=None, help="default arial.ttf; Pillow's default font if not found")
     ap.add_argument('--preview_blur_categories', type=str, default=None, help='comma-separated category names blurred before drawing')
     ap.add_argument('--preview_quality', type=int, default=None, help="JPEG quality; default 75, Pillow's own, as the reference")
+    ap.add_argument('--classifier', type=str, default=None, metavar='MODEL',
+                    help='a TorchScript classifier (torch.jit.load): every detection at or above --classify_confidence_threshold is '
+                         'classified as classification/run_classifier.py classifies crop files; the crops go from the image that is '
+                         'resident on the GPU to the model in one kernel.  Results go to --classification_results_file')
+    ap.add_argument('--classifier_categories', type=str, default=None, metavar='FILE', help='JSON {"0": name, ...}; default: the index')
+    ap.add_argument('--classifier_image_size', type=int, default=None, help='default 224')
+    ap.add_argument('--classifier_no_square_crops', action='store_true', help='crop the box itself, not the square around it')
+    ap.add_argument('--classifier_interpolation', type=str, default=None, choices=sorted(classify_mod.FILTERS), help='default bicubic')
+    ap.add_argument('--classify_confidence_threshold', type=float, default=None, help='detections at or above it are classified; default 0.1')
+    ap.add_argument('--classify_categories', type=str, default=None, help='comma-separated detection category names; default: all')
+    ap.add_argument('--classification_threshold', type=float, default=None, help='classes at or above it are written; default 0.1')
+    ap.add_argument('--classifier_batch_size', type=int, default=None, help='crops per run of the model; default 64')
+    ap.add_argument('--classifier_jpeg_quality', type=int, default=None, metavar='Q',
+                    help='give every crop the JPEG file round trip of the reference (75 there) on the GPU; default: the source pixels')
+    ap.add_argument('--classification_results_file', type=str, default=None, metavar='F',
+                    help='the results with classifications; default <output>.classified.json')
     ap.add_argument('--verbose', action='store_true')
     args = ap.parse_args(argv)
+    classify_sub = {k: getattr(args, k) for k in ('classifier_categories', 'classifier_image_size', 'classifier_interpolation',
+                                                  'classify_confidence_threshold', 'classify_categories', 'classification_threshold',
+                                                  'classifier_batch_size', 'classifier_jpeg_quality', 'classification_results_file')}
+    if args.classifier is None:
+        assert all(v is None for v in classify_sub.values()) and not args.classifier_no_square_crops, \
+            '--classifier_* / --classify_* / --classification_* need --classifier'
+    else:
+        # the classifications live in this process until the run ends: neither a checkpoint nor a shard carries them
+        assert args.n_gpus <= 1 and not args.resume_from_checkpoint, '--classifier runs on one GPU and does not resume from a checkpoint'
     preview_sub = {k: getattr(args, k) for k in ('preview_width', 'preview_confidence_threshold', 'preview_box_thickness',
                                                  'preview_box_expansion', 'preview_label_font_size', 'preview_label_font',
                                                  'preview_blur_categories', 'preview_quality')}
@@ -1200,6 +1284,18 @@ def main(argv=None):
         for k in ('preview_box_thickness', 'preview_box_expansion', 'preview_label_font_size'):
             if k in kwargs:
                 kwargs[k] = whole(kwargs[k])
+    classify_options = None
+    if args.classifier is not None:
+        names = [v for v in (args.classify_categories or '').replace(',', ' ').split() if v]
+        given = {'categories': args.classifier_categories, 'image_size': args.classifier_image_size,
+                 'interpolation': args.classifier_interpolation, 'confidence_threshold': args.classify_confidence_threshold,
+                 'classification_threshold': args.classification_threshold, 'batch_size': args.classifier_batch_size,
+                 'jpeg_quality': args.classifier_jpeg_quality}
+        classify_options = classify_mod.ClassifyOptions(args.classifier, square_crops=not args.classifier_no_square_crops,
+                                                        category_names_to_include=names or None,
+                                                        **{k: v for k, v in given.items() if v is not None})
+        classify_options.category_ids()                      # (a category name the label map does not hold ends the run here)
+        kwargs.update(classify_options=classify_options)
     t0 = time.time()
     if args.n_gpus > 1:
         results = run_sharded(args.detector_file, files, args.n_gpus, results=results, **kwargs)
@@ -1219,6 +1315,11 @@ def main(argv=None):
     if args.crop_folder is not None and (args.crop_results_file or args.crops_output_file):
         write_crop_result_files(final_output, _crop_options(args.crop_confidence_threshold, args.crop_expansion, args.crop_quality,
                                                             args.crop_categories), crop_base, args.crop_results_file, args.crops_output_file)
+    if classify_options is not None:
+        write_classified_results(final_output, last_classifications, classify_options,
+                                 args.classification_results_file or os.path.splitext(args.output_file)[0] + '.classified.json', base)
+        print('Classified {} detections ({} skipped)'.format(last_classify_counts['gpu'] + last_classify_counts['host'],
+                                                             last_classify_counts['skipped']))
     for cp in [checkpoint_path] + [shard_checkpoint_path(checkpoint_path, g) for g in range(max(1, args.n_gpus))]:
         if cp and os.path.isfile(cp):
             os.remove(cp)
