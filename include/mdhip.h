@@ -502,6 +502,13 @@ typedef struct {
     int32_t ntaps, stride, has_res;   /* conv: kh*kw of the packed kernel, stride, residual added */
 } mdhip_op_info;
 
+/* What mdhip_create would plan for this model, dtype and capacity, as text, without touching a device: the context's sizes and
+ * arena offsets, every layer view, every packed conv (shape, weight-arena offsets, element count and 64-bit FNV-1a hash of each of
+ * its arrays) and every op (name, tensors, parameters), one record per line in a fixed field order.  Writes at most cap - 1
+ * characters and a terminating 0 to buf (buf may be NULL with cap 0) and returns the length of the whole text; on failure the
+ * negative code mdhip_create would return for the model, its text in mdhip_last_error(NULL).  tests/test_plan_cpu.py pins plans
+ * with it. */
+long long mdhip_plan_describe(const mdhip_model* model, int dtype, int max_batch, int max_h, int max_w, char* buf, size_t cap);
 int mdhip_num_ops(mdhip_ctx* ctx);
 int mdhip_get_op_info(mdhip_ctx* ctx, int op, mdhip_op_info* out);
 /* run the forward with a hipEvent pair around every op; ms[op] = duration in milliseconds */

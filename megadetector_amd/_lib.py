@@ -120,6 +120,7 @@ SYMBOLS = {
     'mdhip_dfl_decode_on': (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P]),
     'mdhip_adown_pool_on': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_cbfuse_on': (C.c_int, [_P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    'mdhip_plan_describe': (C.c_longlong, [C.POINTER(mdhip_model), C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     'mdhip_num_ops': (C.c_int, [_P]),
     'mdhip_get_op_info': (C.c_int, [_P, C.c_int, C.POINTER(mdhip_op_info)]),
     'mdhip_forward_timed': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),

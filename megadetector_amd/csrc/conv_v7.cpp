@@ -32,7 +32,7 @@
 // ring (conv_v4's packing, walked in the order (group, kernel row, tap 0 / 2 / 1)), the lane-local epilogue with packed
 // SiLU and 16-byte buffer stores -- is conv_v5's 8-wave tile.  K order (group, r, tap 0 / 2 / 1, channel): a summation
 // order of its own, so the layer's results equal the implicit-GEMM kernels' to fp32 rounding only (tolerance test), and
-// a layer that takes this kernel at batch 32 takes it at every batch size (bitwise batch invariance, mdhip_capi.cpp).
+// a layer that takes this kernel at batch 32 takes it at every batch size (bitwise batch invariance, select_cfg in mdhip_exec.cpp).
 
 #include <algorithm>
 #include <type_traits>

@@ -1,5 +1,6 @@
 // The context behind the C ABI (include/mdhip.h) and what the host files that implement it share: mdhip_capi.cpp,
-// mdhip_image_api.cpp, mdhip_kernel_hooks.cpp.  Private to these three: kernels and launchers see mdhip_internal.h alone.
+// mdhip_plan.cpp, mdhip_exec.cpp, mdhip_image_api.cpp, mdhip_kernel_hooks.cpp.  Private to these five: kernels and launchers see
+// mdhip_internal.h alone.
 #pragma once
 
 #include <map>
@@ -122,6 +123,52 @@ struct Op {
     double flops = 0, bytes = 0;
 };
 
+// ---- mdhip_plan.cpp: everything mdhip_create does before its first device call ----
+
+// the host copies of one packed conv's arrays, in the order they lie in the weight arena (an empty one has no place there)
+struct PackedBlobs {
+    std::vector<uint16_t> w;      // 16-bit weights [n_rows][k_pad]
+    std::vector<float> b;         // bias [n_rows]
+    std::vector<uint16_t> w4;     // row-patch packing
+    std::vector<uint16_t> w4p;    // ... with the last group's taps paired
+    std::vector<uint8_t> w8;      // e4m3 packing (its scales follow it in the arena: PackedConv::scale_off, zero until calibrated)
+    struct Ref { const void* data; size_t bytes; size_t PackedConv::*off; };
+    std::vector<Ref> refs() const {
+        return {{w.data(), w.size() * 2, &PackedConv::w_off},    {b.data(), b.size() * 4, &PackedConv::b_off},
+                {w4.data(), w4.size() * 2, &PackedConv::w4_off}, {w4p.data(), w4p.size() * 2, &PackedConv::w4p_off},
+                {w8.data(), w8.size(), &PackedConv::w8_off}};
+    }
+};
+struct PlannedWeights { std::vector<PackedBlobs> convs; };   // one per mdhip_ctx::packed entry
+
+// Fills a fresh context from the model: sizes and strides, ops, layer views, packed convs (their host bytes go to `pw`), every
+// arena and weight-arena offset.  Touches no device.  Returns MDHIP_OK, or the code mdhip_create fails with and its text in `err`.
+int plan_context(mdhip_ctx* ctx, const mdhip_model* model, int dtype, int max_batch, int max_h, int max_w, PlannedWeights* pw,
+                 std::string* err);
+// the planned context as text (mdhip_plan_describe)
+std::string describe_plan(const mdhip_ctx* ctx, const PlannedWeights& pw);
+int num_anchors_for(const mdhip_ctx* ctx, int h, int w);
+
+// ---- mdhip_exec.cpp ----
+
+// the conv API of the context's storage type (the kernels are compiled once per type, mdhip_internal.h)
+struct ConvApi {
+    int (*num_cfgs)();
+    const ConvCfg& (*cfg)(int);
+    hipError_t (*launch)(int, const ConvArgs&, hipStream_t);
+    hipError_t (*init)();
+    bool (*supports)(int, const ConvArgs&);
+    bool (*is_bitwise_family)(int);
+    int (*num_v1_cfgs)();
+    bool (*cfg_decodes)(int);
+};
+const ConvApi& conv_api(const mdhip_ctx* ctx);
+int conv_num_cfgs();
+const ConvCfg& conv_cfg(int i);
+bool conv_cfg_is_bitwise_family(int c);
+void fill_conv_args(mdhip_ctx* ctx, Op& op, int n, int h, int w, ConvArgs& a);
+int run_op(mdhip_ctx* ctx, Op& op, int n, int h, int w, hipStream_t s);
+
 }  // namespace mdhip
 
 struct mdhip_ctx {
@@ -154,6 +201,7 @@ struct mdhip_ctx {
     size_t pred_off = 0;          // = pred_offs[pred_cur]: the prediction of the last forward
     int a_max = 0;
     NmsScratch nms_scr{};
+    size_t nms_kv_off[6] = {}, nms_seg_off = 0;   // what nms_scr's keys / vals / seg_cnt point at once the arena exists
     size_t nms_out_off = 0, nms_cnt_off = 0;
     size_t geom_off = 0;
     DevBuffer stage;              // device staging for host images

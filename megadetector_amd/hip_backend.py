@@ -16,6 +16,75 @@ from .jpeg_host import quant_tables
 from .yolo_model import DETECT_TYPES, MDHIP_CBFUSE, MDHIP_DETECT_DDFL, detect_inputs
 
 
+_DTYPES = {'bf16': _lib.MDHIP_DTYPE_BF16, 'fp8': _lib.MDHIP_DTYPE_FP8, 'fp16': _lib.MDHIP_DTYPE_FP16}
+
+
+def model_description(weights):
+    """YoloWeights -> (mdhip_model, the objects its pointers lead into: keep them for as long as the description is used)"""
+    keep = []
+    specs = weights.specs
+    convs = []
+    layers = (_lib.mdhip_layer * len(specs))()
+    for i, s in enumerate(specs):
+        L = layers[i]
+        L.type = s.type
+        frm = detect_inputs(s)                  # (DualDDetect: the inputs of the head that runs)
+        L.n_from = len(frm)
+        for j, f in enumerate(frm):
+            L.from_[j] = f
+        L.c_out = s.c_out if s.c_out is not None else 0
+        L.k, L.s, L.p = s.k or 0, s.s or 1, s.p or 0
+        if s.type == MDHIP_CBFUSE:              # channel offsets of the chosen splits (0 is an offset, not a default)
+            L.k, L.s, L.p = s.k, s.s, s.p
+        L.n = s.n or 1
+        L.shortcut = s.shortcut or 0
+        L.first_conv = len(convs)
+        for name in s.conv_names:
+            w = weights.weights[name + '.weight']
+            b = weights.weights[name + '.bias']
+            keep += [w, b]
+            cv = _lib.mdhip_conv()
+            cv.weight = w.ctypes.data_as(C.POINTER(C.c_float))
+            cv.bias = b.ctypes.data_as(C.POINTER(C.c_float))
+            cv.c_out, cv.c_in, cv.kh, cv.kw = w.shape
+            convs.append(cv)
+    conv_arr = (_lib.mdhip_conv * max(1, len(convs)))(*convs)
+    m = _lib.mdhip_model()
+    m.n_layers = len(specs)
+    m.layers = layers
+    m.n_convs = len(convs)
+    m.convs = conv_arr
+    m.nc = weights.nc
+    m.na = weights.na
+    m.nl = weights.nl
+    anchors = np.ascontiguousarray(weights.anchors_px.reshape(-1), dtype=np.float32)
+    strides = np.ascontiguousarray(np.asarray(weights.strides, dtype=np.float32))
+    keep += [anchors, strides, layers, conv_arr]
+    m.anchors_px = anchors.ctypes.data_as(C.POINTER(C.c_float)) if anchors.size else None
+    m.strides = strides.ctypes.data_as(C.POINTER(C.c_float)) if strides.size else None
+    return m, keep
+
+
+def describe_plan(weights, dtype='bf16', max_batch=32, max_h=1280, max_w=1280):
+    """
+    What mdhip_create would plan for these weights, as text (mdhip_plan_describe): the ops, every tensor's place in the
+    arena, the packed convs with a hash of their bytes.  Needs no GPU.  HipError (with .code) for a model the planner refuses.
+    """
+    lib = _lib.load()
+    m, keep = model_description(weights)
+    args = (C.byref(m), _DTYPES[dtype], int(max_batch), int(max_h), int(max_w))
+    need = lib.mdhip_plan_describe(*args, None, 0)
+    if need >= 0:
+        buf = C.create_string_buffer(need + 1)
+        need = lib.mdhip_plan_describe(*args, buf, need + 1)
+    if need < 0:
+        err = HipError('mdhip_plan_describe failed ({}): {}'.format(need, lib.mdhip_last_error(None).decode()))
+        err.code = int(need)
+        raise err
+    del keep
+    return buf.value.decode()
+
+
 class HipContext:
 
     def __init__(self, weights, device=0, dtype='bf16', max_batch=32, max_h=1280, max_w=1280):
@@ -23,48 +92,8 @@ class HipContext:
         self.weights = weights
         self.device = int(device)
         self.max_batch = int(max_batch)
-        self._keep = []
-        specs = weights.specs
-        convs = []
-        layers = (_lib.mdhip_layer * len(specs))()
-        for i, s in enumerate(specs):
-            L = layers[i]
-            L.type = s.type
-            frm = detect_inputs(s)                  # (DualDDetect: the inputs of the head that runs)
-            L.n_from = len(frm)
-            for j, f in enumerate(frm):
-                L.from_[j] = f
-            L.c_out = s.c_out if s.c_out is not None else 0
-            L.k, L.s, L.p = s.k or 0, s.s or 1, s.p or 0
-            if s.type == MDHIP_CBFUSE:              # channel offsets of the chosen splits (0 is an offset, not a default)
-                L.k, L.s, L.p = s.k, s.s, s.p
-            L.n = s.n or 1
-            L.shortcut = s.shortcut or 0
-            L.first_conv = len(convs)
-            for name in s.conv_names:
-                w = weights.weights[name + '.weight']
-                b = weights.weights[name + '.bias']
-                self._keep += [w, b]
-                cv = _lib.mdhip_conv()
-                cv.weight = w.ctypes.data_as(C.POINTER(C.c_float))
-                cv.bias = b.ctypes.data_as(C.POINTER(C.c_float))
-                cv.c_out, cv.c_in, cv.kh, cv.kw = w.shape
-                convs.append(cv)
-        conv_arr = (_lib.mdhip_conv * max(1, len(convs)))(*convs)
-        m = _lib.mdhip_model()
-        m.n_layers = len(specs)
-        m.layers = layers
-        m.n_convs = len(convs)
-        m.convs = conv_arr
-        m.nc = weights.nc
-        m.na = weights.na
-        m.nl = weights.nl
-        anchors = np.ascontiguousarray(weights.anchors_px.reshape(-1), dtype=np.float32)
-        strides = np.ascontiguousarray(np.asarray(weights.strides, dtype=np.float32))
-        self._keep += [anchors, strides, layers, conv_arr]
-        m.anchors_px = anchors.ctypes.data_as(C.POINTER(C.c_float)) if anchors.size else None
-        m.strides = strides.ctypes.data_as(C.POINTER(C.c_float)) if strides.size else None
-        dt = {'bf16': _lib.MDHIP_DTYPE_BF16, 'fp8': _lib.MDHIP_DTYPE_FP8, 'fp16': _lib.MDHIP_DTYPE_FP16}[dtype]
+        m, self._keep = model_description(weights)
+        dt = _DTYPES[dtype]
         self.dtype = dtype
         handle = C.c_void_p()
         rc = self.lib.mdhip_create(C.byref(m), self.device, dt, int(max_batch), int(max_h), int(max_w),
@@ -75,7 +104,7 @@ class HipContext:
         self.h = handle
         self.anchor_free = bool(getattr(weights, 'anchor_free', False))
         self.no = weights.nc + (4 if self.anchor_free else 5)      # anchor-free rows: [cx, cy, w, h, cls...]
-        self.has_detect = specs[-1].type in DETECT_TYPES
+        self.has_detect = weights.specs[-1].type in DETECT_TYPES
         self.max_stride = self.lib.mdhip_max_stride(self.h)
         self.load_tuned()
 

@@ -109,7 +109,7 @@ def test_detector_input_validation_without_gpu():
 
 
 def test_host_e4m3_quantiser_matches_torch():
-    """fp8 mode: the library quantises the 3x3 weights on the host (mdhip_capi.cpp pack(), mdhip_internal.h
+    """fp8 mode: the library quantises the 3x3 weights on the host (mdhip_plan.cpp pack(), mdhip_internal.h
     f32_to_e4m3); the oracle uses torch.float8_e4m3fn after a clamp to +-448.  Every e4m3 value, every midpoint
     between neighbours (ties to even), the subnormal range, saturation, signs, and random values must agree."""
     import ctypes as C
