@@ -572,6 +572,25 @@ int mdhip_set_option(mdhip_ctx* ctx, const char* name, int value);
 /* time one op in isolation: `iters` back-to-back launches bracketed by events */
 int mdhip_time_op(mdhip_ctx* ctx, int op, int n, int h, int w, int iters, float* ms_avg,
                   void* hip_stream);
+/* What a forward of n images of h x w would launch on such a context, as text, without touching a device: one line per op, in op
+ * order -- index, name, what the op does (`launch` with the name of its tile configuration, `in_next` = runs inside the next
+ * launch, `in_place` = read in place by its consumer, `in_front` = decoded in the conv in front, `plain` = its own launch
+ * without a tile), whether the tile came from the table `tuned` (as mdhip_set_tuned takes it), whether the conv decodes in its
+ * epilogue, and the statistics mdhip_get_op_info reports (m n k, flops and bytes as %.17g).  `flags`: the settings and the kind
+ * of pass below; `forced`: n_forced pairs (op, cfg) as mdhip_set_op_cfg takes them.  Buffer, return value and errors as
+ * mdhip_plan_describe.  A tile the launcher would refuse at launch (a stale table entry) is not predicted.
+ * tests/test_launches_cpu.py pins launches with it. */
+#define MDHIP_LAUNCHES_NO_FUSE 1          /* mdhip_set_fuse(ctx, 0) */
+#define MDHIP_LAUNCHES_NO_FUSE_DECODE 2   /* mdhip_set_option(ctx, "fuse_decode", 0) */
+#define MDHIP_LAUNCHES_NO_PAIR 4          /* MDHIP_PAIR=0 at mdhip_create */
+#define MDHIP_LAUNCHES_ISOLATED 8         /* one op on its own, as mdhip_time_op runs it */
+#define MDHIP_LAUNCHES_CALIBRATING 16     /* the 16-bit forward of mdhip_calibrate (fp8 contexts) */
+#define MDHIP_LAUNCHES_AUGMENTED 32       /* a pass of mdhip_forward_tta, h x w being the size of that pass */
+#define MDHIP_LAUNCHES_AFTER_OTHERS 64    /* test hook: other shapes, passes and settings are resolved on the context first and
+                                             every setting is flipped and flipped back; the text must not depend on it */
+long long mdhip_launches_describe(const mdhip_model* model, int dtype, int max_batch, int max_h, int max_w, const mdhip_tuned* tuned,
+                                  int n_tuned, int n, int h, int w, unsigned flags, const int32_t* forced, int n_forced, char* buf,
+                                  size_t cap);
 
 const char* mdhip_version(void);
 

@@ -19,6 +19,9 @@ MDHIP_EUNSUPPORTED = -4
 MDHIP_DTYPE_BF16 = 0
 MDHIP_DTYPE_FP8 = 1
 MDHIP_DTYPE_FP16 = 2
+#: flags of mdhip_launches_describe
+MDHIP_LAUNCHES_NO_FUSE, MDHIP_LAUNCHES_NO_FUSE_DECODE, MDHIP_LAUNCHES_NO_PAIR, MDHIP_LAUNCHES_ISOLATED = 1, 2, 4, 8
+MDHIP_LAUNCHES_CALIBRATING, MDHIP_LAUNCHES_AUGMENTED, MDHIP_LAUNCHES_AFTER_OTHERS = 16, 32, 64
 
 
 class mdhip_conv(C.Structure):
@@ -121,6 +124,9 @@ SYMBOLS = {
     'mdhip_adown_pool_on': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_cbfuse_on': (C.c_int, [_P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_plan_describe': (C.c_longlong, [C.POINTER(mdhip_model), C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    'mdhip_launches_describe': (C.c_longlong, [C.POINTER(mdhip_model), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(mdhip_tuned),
+                                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_int32), C.c_int,
+                                               C.c_char_p, C.c_size_t]),
     'mdhip_num_ops': (C.c_int, [_P]),
     'mdhip_get_op_info': (C.c_int, [_P, C.c_int, C.POINTER(mdhip_op_info)]),
     'mdhip_forward_timed': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),

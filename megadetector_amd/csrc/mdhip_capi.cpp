@@ -8,9 +8,10 @@
 // The context and what the host files share are in mdhip_ctx.h.  The image entry points (mdhip_preprocess <- letterbox +
 // tensor prep :1104-1109, :1283-1310; the windows, JPEG and blur calls) are in mdhip_image_api.cpp, the single-kernel test
 // hooks (mdhip_*_on) in mdhip_kernel_hooks.cpp.  The planner (model -> ops, arena, packed weights: all that mdhip_create does on
-// the host) is mdhip_plan.cpp, the executor (tile choice, run_op) mdhip_exec.cpp.
+// the host) is mdhip_plan.cpp, the executor (what a pass launches: resolved once, then launched) mdhip_exec.cpp.
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -42,8 +43,7 @@ int mdhip::check_shape(mdhip_ctx* ctx, int n, int h, int w) {
 
 namespace {
 
-// every call that changes what a forward launches drops the captured graphs (after the device has finished with them: an
-// executable may still be in flight on the caller's stream)
+// the captured graphs go (after the device has finished with them: an executable may still be in flight on the caller's stream)
 void drop_graphs(mdhip_ctx* ctx) {
     bool any = false;
     for (auto& kv : ctx->graphs) any |= kv.second.exec != nullptr;
@@ -71,6 +71,51 @@ void evict_graph_if_full(mdhip_ctx* ctx) {
     ctx->graphs.erase(victim);
 }
 
+// every call that changes what a forward launches: the resolved passes are void (mdhip_ctx::generation), the graphs dropped
+void launches_changed(mdhip_ctx* ctx) {
+    ++ctx->generation;
+    drop_graphs(ctx);
+}
+
+// One pass over the ops, as mdhip_forward and its kin make it: the state the ops read while it lasts (the kind of pass, the
+// anchor pitch of the prediction it writes; an augmented pass sets mdhip_ctx::cur_tta itself), and what it leaves to later calls.
+struct Pass {
+    mdhip_ctx* ctx;
+    hipStream_t s;
+    std::shared_ptr<Resolved> ran;
+    Pass(mdhip_ctx* c, hipStream_t stream, int n_anchors, bool isolated = false, bool calibrating = false) : ctx(c), s(stream) {
+        ctx->cur_tta = DecodeTta();
+        ctx->cur_A = n_anchors;
+        ctx->fuse_suspended = isolated;
+        ctx->calibrating = calibrating;
+    }
+    ~Pass() { ctx->cur_tta = DecodeTta(); ctx->fuse_suspended = ctx->calibrating = false; }
+    // the pass writes the other prediction buffer, once an NMS that may still read it on another stream is done
+    int flip_prediction() {
+        ctx->pred_cur ^= 1;
+        ctx->pred_off = ctx->pred_offs[ctx->pred_cur];
+        if (ctx->pred_read_valid[ctx->pred_cur]) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->pred_read[ctx->pred_cur], 0));
+        return MDHIP_OK;
+    }
+    // launches ops [first, first + count) for n images of h x w on stream `on`
+    int run(int n, int h, int w, hipStream_t on, size_t first = 0, size_t count = INT_MAX) {
+        ran = resolved_for(ctx, n, h, w);
+        return launch_ops(ctx, *ran, first, count, on);
+    }
+    // nothing behind this point reads the network input (mdhip_ctx::input_free); idle: the stream has been waited for
+    int input_done(bool idle) {
+        if (!idle) HIP_TRY(ctx, hipEventRecord(ctx->input_free, s));
+        ctx->input_free_valid = !idle;
+        return MDHIP_OK;
+    }
+    // the context's last forward is this pass of n images, h x w being the input's size
+    void finish(int n, int h, int w) {
+        ctx->last_n = n; ctx->last_h = h; ctx->last_w = w;
+        ctx->last_A = ctx->cur_A;
+        ctx->last_ran = ran;
+    }
+};
+
 int check_calibrated(mdhip_ctx* ctx) {
     if (ctx->dtype == MDHIP_DTYPE_FP8 && ctx->n_f8 > 0 && !ctx->calibrated)
         return fail(ctx, MDHIP_EINVAL, "fp8 context without activation scales: call mdhip_calibrate (or mdhip_fp8_set_scales) first");
@@ -79,7 +124,7 @@ int check_calibrated(mdhip_ctx* ctx) {
 
 // new range -> scale of an e4m3 tensor and the combined per-channel factors of the conv that reads it
 int apply_fp8_scale(mdhip_ctx* ctx, Op& producer, float act_scale) {
-    drop_graphs(ctx);                               // (the quantisation scale is a launch argument)
+    launches_changed(ctx);                          // (the quantisation scale is a launch argument)
     producer.act_scale = act_scale;
     Op& consumer = ctx->ops[producer.f8_peer];
     consumer.act_scale = act_scale;
@@ -200,6 +245,47 @@ long long mdhip_plan_describe(const mdhip_model* model, int dtype, int max_batch
     return (long long)text.size();
 }
 
+long long mdhip_launches_describe(const mdhip_model* model, int dtype, int max_batch, int max_h, int max_w, const mdhip_tuned* tuned,
+                                  int n_tuned, int n, int h, int w, unsigned flags, const int32_t* forced, int n_forced, char* buf,
+                                  size_t cap) {
+    if (int rc = check_create_args(model, dtype, max_batch, max_h, max_w)) return rc;
+    if (n_tuned < 0 || (n_tuned > 0 && !tuned) || n_forced < 0 || (n_forced > 0 && !forced))
+        return fail(nullptr, MDHIP_EINVAL, "mdhip_launches_describe: bad table or forced list");
+    mdhip_ctx ctx;                                      // thrown away: no device is touched, nothing to destroy
+    ctx.pair_enabled = !(flags & MDHIP_LAUNCHES_NO_PAIR);
+    PlannedWeights pw;
+    std::string err;
+    if (int rc = plan_context(&ctx, model, dtype, max_batch, max_h, max_w, &pw, &err)) return fail(nullptr, rc, "%s", err.c_str());
+    // the decisions read which pointers are null and which are equal and follow none of them: any two bases do
+    ctx.arena = (char*)(uintptr_t)(1ull << 40);
+    ctx.warena = (char*)(uintptr_t)(2ull << 40);
+    int rc = check_shape(&ctx, n, h, w);
+    if (!rc) rc = mdhip_set_tuned(&ctx, tuned, n_tuned);
+    for (int i = 0; i < n_forced && !rc; ++i) rc = mdhip_set_op_cfg(&ctx, forced[2 * i], forced[2 * i + 1]);
+    if (rc) return fail(nullptr, rc, "%s", ctx.err.empty() ? "mdhip_launches_describe: bad forced list" : ctx.err.c_str());
+    const bool fuse = !(flags & MDHIP_LAUNCHES_NO_FUSE), fuse_decode = !(flags & MDHIP_LAUNCHES_NO_FUSE_DECODE);
+    (void)mdhip_set_fuse(&ctx, fuse);
+    (void)mdhip_set_option(&ctx, "fuse_decode", fuse_decode);
+    // the pass as one of the forward-like calls would set it up (an augmented pass: any placement but the plain one)
+    auto resolve_as = [&](unsigned kind, int rn, int rh, int rw) {
+        Pass pass(&ctx, nullptr, num_anchors_for(&ctx, rh, rw), (kind & MDHIP_LAUNCHES_ISOLATED) != 0, (kind & MDHIP_LAUNCHES_CALIBRATING) != 0);
+        if (kind & MDHIP_LAUNCHES_AUGMENTED) ctx.cur_tta.scale = 0.83f;
+        return resolved_for(&ctx, rn, rh, rw);
+    };
+    if (flags & MDHIP_LAUNCHES_AFTER_OTHERS)
+        for (int round = 0; round < 4; ++round) {       // as set, fuse flipped, fuse_decode flipped, back as set
+            (void)mdhip_set_fuse(&ctx, round == 1 ? !fuse : fuse);
+            (void)mdhip_set_option(&ctx, "fuse_decode", round == 2 ? !fuse_decode : fuse_decode);
+            for (unsigned kind : {0u, (unsigned)MDHIP_LAUNCHES_ISOLATED, (unsigned)MDHIP_LAUNCHES_CALIBRATING, (unsigned)MDHIP_LAUNCHES_AUGMENTED}) {
+                (void)resolve_as(kind, n, h, w);
+                (void)resolve_as(kind, 1, ctx.max_stride * 2, ctx.max_stride * 3);
+            }
+        }
+    const std::string text = describe_launches(&ctx, *resolve_as(flags, n, h, w));
+    if (buf && cap) snprintf(buf, cap, "%s", text.c_str());
+    return (long long)text.size();
+}
+
 void mdhip_destroy(mdhip_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
@@ -240,12 +326,8 @@ int mdhip_forward(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int slot = (int)(ctx->fwd_count % mdhip_ctx::kFwdRing);
     if (ctx->time_forward) HIP_TRY(ctx, hipEventRecord(ctx->fwd_ev[slot][0], s));
-    ctx->cur_tta = DecodeTta();
-    ctx->cur_A = num_anchors_for(ctx, h, w);
-    ctx->pred_cur ^= 1;
-    ctx->pred_off = ctx->pred_offs[ctx->pred_cur];
-    if (ctx->pred_read_valid[ctx->pred_cur])            // an NMS on another stream may still read the buffer this forward overwrites
-        HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->pred_read[ctx->pred_cur], 0));
+    Pass pass(ctx, s, num_anchors_for(ctx, h, w));
+    if (int rc = pass.flip_prediction()) return rc;
     const bool use_graph = (ctx->graph_mode == 1 || (ctx->graph_mode == 2 && n <= ctx->graph_max_n)) && !ctx->calibrating;
     bool launched = false;
     if (use_graph) {
@@ -263,8 +345,7 @@ int mdhip_forward(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
             hipGraphExec_t exec = nullptr;
             bool ok = hipStreamBeginCapture(ctx->capture_stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
             if (ok) {
-                for (Op& op : ctx->ops)
-                    if (run_op(ctx, op, n, h, w, ctx->capture_stream) != MDHIP_OK) { ok = false; break; }
+                ok = pass.run(n, h, w, ctx->capture_stream) == MDHIP_OK;
                 ok = (hipStreamEndCapture(ctx->capture_stream, &graph) == hipSuccess) && ok && graph != nullptr;
             }
             if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess && exec != nullptr;
@@ -282,26 +363,16 @@ int mdhip_forward(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
             }
         }
     }
-    if (!launched) {
-        for (size_t oi = 0; oi < ctx->ops.size(); ++oi) {
-            if (int rc = run_op(ctx, ctx->ops[oi], n, h, w, s)) return rc;
-            if ((int)oi == ctx->last_input_op) {             // (nothing behind it reads the network input)
-                HIP_TRY(ctx, hipEventRecord(ctx->input_free, s));
-                ctx->input_free_valid = true;
-            }
-        }
-    } else {
-        HIP_TRY(ctx, hipEventRecord(ctx->input_free, s));
-        ctx->input_free_valid = true;
-    }
+    // eager: the ops up to the last one that reads the network input, then the rest; behind a replayed graph: none
+    const size_t head = launched ? 0 : (size_t)ctx->last_input_op + 1, rest = launched ? 0 : ctx->ops.size();
+    if (int rc = pass.run(n, h, w, s, 0, head)) return rc;
+    if (int rc = pass.input_done(false)) return rc;
+    if (int rc = pass.run(n, h, w, s, head, rest)) return rc;
     if (ctx->time_forward) {
         HIP_TRY(ctx, hipEventRecord(ctx->fwd_ev[slot][1], s));
         ++ctx->fwd_count;
     }
-    ctx->last_n = n;
-    ctx->last_h = h;
-    ctx->last_w = w;
-    ctx->last_A = ctx->cur_A;
+    pass.finish(n, h, w);
     return MDHIP_OK;
 }
 
@@ -343,11 +414,8 @@ int mdhip_forward_tta(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
     uint16_t* orig = (uint16_t*)(ctx->arena + ctx->input_orig.off);
     HIP_TRY(ctx, hipMemcpyAsync(orig, in, in_bytes, hipMemcpyDeviceToDevice, s));
     const int f16 = ctx->dtype == MDHIP_DTYPE_FP16;
-    ctx->cur_A = total;
-    ctx->pred_cur ^= 1;
-    ctx->pred_off = ctx->pred_offs[ctx->pred_cur];
-    if (ctx->pred_read_valid[ctx->pred_cur])            // an NMS on another stream may still read the buffer this forward overwrites
-        HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->pred_read[ctx->pred_cur], 0));
+    Pass pass(ctx, s, total);
+    if (int rc = pass.flip_prediction()) return rc;
     int out_off = 0;
     for (int k = 0; k < 3; ++k) {
         if (k) HIP_TRY(ctx, launch_tta_scale(orig, in, n, h, w, sh[k], sw[k], oh[k], ow[k], flips[k], f16, s));
@@ -359,18 +427,12 @@ int mdhip_forward_tta(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
         t.flip_lr = flips[k];
         t.img_w = (float)w;
         ctx->cur_tta = t;
-        for (Op& op : ctx->ops)
-            if (int rc = run_op(ctx, op, n, oh[k], ow[k], s)) return rc;
+        if (int rc = pass.run(n, oh[k], ow[k], s)) return rc;
         out_off += t.keep_to - t.keep_from;
     }
     HIP_TRY(ctx, hipMemcpyAsync(in, orig, in_bytes, hipMemcpyDeviceToDevice, s));       // `input` holds the batch again
-    HIP_TRY(ctx, hipEventRecord(ctx->input_free, s));
-    ctx->input_free_valid = true;
-    ctx->cur_tta = DecodeTta();
-    ctx->last_n = n;
-    ctx->last_h = h;
-    ctx->last_w = w;
-    ctx->last_A = total;
+    if (int rc = pass.input_done(false)) return rc;
+    pass.finish(n, h, w);
     return MDHIP_OK;
 }
 
@@ -391,18 +453,10 @@ int mdhip_calibrate(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
     for (Op& op : ctx->ops)
         if (op.f8_out) HIP_TRY(ctx, hipMemsetAsync(ctx->arena + op.amax_off, 0, 4, s));
     // one forward in 16 bits (every op, the 3x3 convs through their bf16 weights), ranges recorded on the way
-    ctx->calibrating = true;
-    for (Op& op : ctx->ops) op.memo_cfg = -1;
-    ctx->cur_tta = DecodeTta();
-    ctx->cur_A = num_anchors_for(ctx, h, w);
-    int rc = MDHIP_OK;
-    for (Op& op : ctx->ops)
-        if ((rc = run_op(ctx, op, n, h, w, s)) != MDHIP_OK) break;
-    ctx->calibrating = false;
-    for (Op& op : ctx->ops) op.memo_cfg = -1;
-    if (rc) return rc;
+    Pass pass(ctx, s, num_anchors_for(ctx, h, w), false, true);
+    if (int rc = pass.run(n, h, w, s)) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(s));
-    ctx->input_free_valid = false;                      // (the stream is idle: nothing to wait for)
+    (void)pass.input_done(true);
     for (Op& op : ctx->ops) {
         if (!op.f8_out) continue;
         float m = 0.f;
@@ -413,7 +467,7 @@ int mdhip_calibrate(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
         if (int r2 = apply_fp8_scale(ctx, op, scale)) return r2;
     }
     ctx->calibrated = true;
-    ctx->last_A = ctx->cur_A;
+    pass.finish(ctx->last_n, h, w);                     // (the batch mdhip_preprocess wrote stays the context's)
     return MDHIP_OK;
 }
 
@@ -455,7 +509,6 @@ int mdhip_fp8_set_scales(mdhip_ctx* ctx, const float* scales, int n) {
         if (int rc = apply_fp8_scale(ctx, op, sc)) return rc;
     }
     ctx->calibrated = true;
-    for (Op& op : ctx->ops) op.memo_cfg = -1;
     return MDHIP_OK;
 }
 
@@ -498,20 +551,16 @@ int mdhip_forward_timed(mdhip_ctx* ctx, int n, int h, int w, float* ms, void* hi
         ctx->events.push_back(ev);
     }
     HIP_TRY(ctx, hipEventRecord(ctx->events[0], s));
-    ctx->cur_tta = DecodeTta();
-    ctx->cur_A = num_anchors_for(ctx, h, w);
+    Pass pass(ctx, s, num_anchors_for(ctx, h, w));
     for (size_t i = 0; i < ctx->ops.size(); ++i) {
-        if (int rc = run_op(ctx, ctx->ops[i], n, h, w, s)) return rc;
+        if (int rc = pass.run(n, h, w, s, i, 1)) return rc;
         HIP_TRY(ctx, hipEventRecord(ctx->events[i + 1], s));
     }
     HIP_TRY(ctx, hipStreamSynchronize(s));
-    ctx->input_free_valid = false;
+    (void)pass.input_done(true);
     for (size_t i = 0; i < ctx->ops.size(); ++i)
         HIP_TRY(ctx, hipEventElapsedTime(&ms[i], ctx->events[i], ctx->events[i + 1]));
-    ctx->last_n = n;
-    ctx->last_h = h;
-    ctx->last_w = w;
-    ctx->last_A = ctx->cur_A;
+    pass.finish(n, h, w);
     return MDHIP_OK;
 }
 
@@ -526,15 +575,12 @@ int mdhip_time_op(mdhip_ctx* ctx, int op, int n, int h, int w, int iters, float*
         HIP_TRY(ctx, hipEventCreate(&ev));
         ctx->events.push_back(ev);
     }
-    ctx->cur_tta = DecodeTta();
-    ctx->cur_A = num_anchors_for(ctx, h, w);
-    // one op in isolation: a bottleneck's two convs as the two launches they are (no fusion)
-    struct Suspend { mdhip_ctx* c; Suspend(mdhip_ctx* c_) : c(c_) { c->fuse_suspended = true; } ~Suspend() { c->fuse_suspended = false; } } suspend(ctx);
-    ctx->ops[op].dec_done = false;                                     // (a decode op on its own: launched, whatever the last forward did)
-    if (int rc = run_op(ctx, ctx->ops[op], n, h, w, s)) return rc;    // warm
+    // one op in isolation: a bottleneck's two convs as the two launches they are, an upsample and a decode op as their own
+    Pass pass(ctx, s, num_anchors_for(ctx, h, w), true);
+    if (int rc = pass.run(n, h, w, s, op, 1)) return rc;              // warm
     HIP_TRY(ctx, hipEventRecord(ctx->events[0], s));
     for (int i = 0; i < iters; ++i)
-        if (int rc = run_op(ctx, ctx->ops[op], n, h, w, s)) return rc;
+        if (int rc = pass.run(n, h, w, s, op, 1)) return rc;
     HIP_TRY(ctx, hipEventRecord(ctx->events[1], s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     float ms = 0.f;
@@ -675,12 +721,14 @@ int mdhip_get_op_info(mdhip_ctx* ctx, int op, mdhip_op_info* out) {
     out->kind = o.kind == OP_DFL ? OP_DECODE : o.kind;       // (the DFL decode is reported as the decode op of its level)
     if (o.kind == OP_ADOWN || o.kind == OP_CBFUSE) out->kind = o.kind - 1;                  // 7 ADown pools, 8 CBFuse
     out->layer = o.layer;
-    out->m = o.gm;
-    out->n = o.gn;
-    out->k = o.gk;
-    out->flops = o.flops;
-    out->bytes = o.bytes;
-    out->cfg = o.last_cfg;
+    const Launch L = ctx->last_ran ? ctx->last_ran->ops[op] : Launch();      // (of the last forward; none yet: zeros)
+    out->m = L.gm;
+    out->n = L.gn;
+    out->k = L.gk;
+    out->flops = L.flops;
+    out->bytes = L.bytes;
+    // a conv with its own launch: its tile; -2 = a decode folded into the conv in front; -1 = anything else
+    out->cfg = L.how == RUN_IN_FRONT ? -2 : (o.kind == OP_CONV && L.how == RUN_LAUNCH) ? L.cfg : -1;
     if (o.kind == OP_CONV || o.kind == OP_DW) {
         const PackedConv& pc = ctx->packed[o.pc];
         out->ntaps = pc.kh * pc.kw;
@@ -697,7 +745,7 @@ int mdhip_op_supports_cfg(mdhip_ctx* ctx, int op, int cfg) {
     if (ctx->ops[op].kind != OP_CONV || cfg < 0 || cfg >= conv_num_cfgs()) return 0;
     ConvArgs a{};
     const int h = ctx->last_h ? ctx->last_h : ctx->max_stride, w = ctx->last_w ? ctx->last_w : ctx->max_stride;
-    fill_conv_args(ctx, ctx->ops[op], ctx->last_n ? ctx->last_n : 1, h, w, a);
+    conv_args(ctx, ctx->ops[op], ctx->last_n ? ctx->last_n : 1, h, w, a);
     return conv_api(ctx).supports(cfg, a) ? 1 : 0;
 }
 
@@ -711,15 +759,14 @@ int mdhip_set_tuned(mdhip_ctx* ctx, const mdhip_tuned* entries, int n) {
         if (entries[i].cfg < 0 || entries[i].cfg >= conv_num_cfgs())
             return fail(ctx, MDHIP_EINVAL, "tuned entry %d: cfg %d outside [0,%d)", i, entries[i].cfg, conv_num_cfgs());
     ctx->tuned.assign(entries, entries + n);
-    for (Op& op : ctx->ops) op.memo_cfg = -1;
-    drop_graphs(ctx);
+    launches_changed(ctx);
     return MDHIP_OK;
 }
 
 int mdhip_set_fuse(mdhip_ctx* ctx, int on) {
     if (!ctx) return MDHIP_EINVAL;
     ctx->fuse_enabled = on != 0;
-    drop_graphs(ctx);
+    launches_changed(ctx);
     return MDHIP_OK;
 }
 
@@ -728,7 +775,7 @@ int mdhip_set_option(mdhip_ctx* ctx, const char* name, int value) {
     if (!strcmp(name, "letterbox_general")) ctx->letterbox_general = value != 0;
     else if (!strcmp(name, "fuse_decode")) ctx->fuse_decode = value != 0;
     else return fail(ctx, MDHIP_EINVAL, "unknown option '%s'", name);
-    drop_graphs(ctx);
+    launches_changed(ctx);
     return MDHIP_OK;
 }
 
@@ -745,7 +792,7 @@ int mdhip_set_op_cfg(mdhip_ctx* ctx, int op, int cfg) {
     if (ctx->ops[op].kind != OP_CONV) return fail(ctx, MDHIP_EINVAL, "op %d is not a conv", op);
     if (cfg < -1 || cfg >= conv_num_cfgs()) return fail(ctx, MDHIP_EINVAL, "cfg %d outside [-1,%d)", cfg, conv_num_cfgs());
     ctx->ops[op].forced_cfg = cfg;
-    drop_graphs(ctx);
+    launches_changed(ctx);
     return MDHIP_OK;
 }
 

@@ -4,6 +4,7 @@
 #pragma once
 
 #include <map>
+#include <memory>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -107,20 +108,9 @@ struct Op {
     float act_scale = 0.f, amax = 0.f;
     // fused bottleneck (conv_v5c.cpp): fuse_role 1 = the 1x1 of bottleneck fuse_idx of C3 block fuse_group, 2 = its 3x3
     int fuse_group = -1, fuse_idx = -1, fuse_role = 0;
-    double pre_flops = 0;
     // upsample read in place (conv_v2.cpp): an OP_UPSAMPLE whose only reader is the 1x1 conv `up_peer` (and vice versa)
     int up_peer = -1;
-    // Detect: the 1x1 conv of a level and its OP_DECODE (the next op); dec_done = the conv of THIS forward decoded in its
-    // epilogue, the decode op has nothing left to launch
-    bool dec_done = false;
     size_t amax_off = 0;
-    // the configuration chosen for the last (n, h, w): the table walk is not repeated on every launch
-    int memo_n = 0, memo_h = 0, memo_w = 0, memo_cfg = -1;
-    bool memo_from_table = false;
-    int last_cfg = -1;
-    // stats for the last (n,h,w)
-    int gm = 0, gn = 0, gk = 0;
-    double flops = 0, bytes = 0;
 };
 
 // ---- mdhip_plan.cpp: everything mdhip_create does before its first device call ----
@@ -166,8 +156,30 @@ const ConvApi& conv_api(const mdhip_ctx* ctx);
 int conv_num_cfgs();
 const ConvCfg& conv_cfg(int i);
 bool conv_cfg_is_bitwise_family(int c);
-void fill_conv_args(mdhip_ctx* ctx, Op& op, int n, int h, int w, ConvArgs& a);
-int run_op(mdhip_ctx* ctx, Op& op, int n, int h, int w, hipStream_t s);
+void conv_args(const mdhip_ctx* ctx, const Op& op, int n, int h, int w, ConvArgs& a);
+
+// What one op does in a pass, resolved for a shape and a kind of pass: its own launch (a conv: with tile `cfg`), inside the
+// next op's launch (the 1x1 of a fused bottleneck), read in place by its consumer (an absorbed upsample), or decoded in the
+// epilogue of the conv in front (a Detect decode).
+enum RunHow { RUN_LAUNCH = 0, RUN_IN_NEXT = 1, RUN_IN_PLACE = 2, RUN_IN_FRONT = 3 };
+struct Launch {
+    int how = RUN_LAUNCH;
+    int cfg = -1;
+    bool from_table = false;      // the tile is a table entry: replaced by the heuristic if the launcher refuses it ...
+    bool as_planned = true;       // ... and the op is neither fused nor reads an upsample in place
+    bool decodes = false;         // this conv decodes its Detect level in its epilogue
+    ConvArgs a{};                 // conv: the launch arguments that do not change between calls
+    int gm = 0, gn = 0, gk = 0;   // statistics (mdhip_get_op_info)
+    double flops = 0, bytes = 0;
+};
+struct Resolved {
+    long long generation = 0;     // mdhip_ctx::generation it was resolved at
+    int n = 0, h = 0, w = 0;
+    std::vector<Launch> ops;      // one per mdhip_ctx::ops entry
+};
+std::shared_ptr<Resolved> resolved_for(mdhip_ctx* ctx, int n, int h, int w);
+int launch_ops(mdhip_ctx* ctx, Resolved& r, size_t first, size_t count, hipStream_t s);
+std::string describe_launches(const mdhip_ctx* ctx, const Resolved& r);
 
 }  // namespace mdhip
 
@@ -216,7 +228,7 @@ struct mdhip_ctx {
     int last_n = 0, last_h = 0, last_w = 0;
     std::string err;
     // fp8 mode: until every e4m3 tensor has a scale (mdhip_calibrate / mdhip_fp8_set_scales) the forward refuses
-    // to run; `calibrating` makes run_op execute every op in 16 bits and record the range of the tensors
+    // to run; `calibrating` (the pass of mdhip_calibrate) runs every op in 16 bits and records the range of the tensors
     bool calibrated = false, calibrating = false;
     int n_f8 = 0;
     // C3 blocks whose bottlenecks can run as one launch each (1x1 -> LDS -> 3x3): op indices of the 3x3s per block
@@ -250,6 +262,13 @@ struct mdhip_ctx {
     std::map<std::tuple<int, int, int, int>, GraphSlot> graphs;
     static constexpr int kMaxGraphs = 32;                 // cached executables (letterbox shapes x batch sizes x 2 buffers)
     long long graph_clock = 0;
+    // What a pass launches, resolved once (mdhip_exec.cpp resolve) per (batch, height, width, kind of pass: plain / isolated /
+    // calibrating) and `generation`, which every call that changes what a forward launches bumps (launches_changed in
+    // mdhip_capi.cpp).  last_ran: the list of the last pass, whose statistics mdhip_get_op_info reports.
+    std::map<std::tuple<int, int, int, int>, std::shared_ptr<Resolved>> resolved;
+    static constexpr int kMaxResolved = 64;
+    long long generation = 0;
+    std::shared_ptr<Resolved> last_ran;
     // recorded on the forward's stream behind the last op that reads the network input (last_input_op): a following
     // mdhip_preprocess -- possibly on ANOTHER stream, next to the rest of this forward -- waits for it before it overwrites
     // the input tensor

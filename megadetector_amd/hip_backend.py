@@ -65,6 +65,43 @@ def model_description(weights):
     return m, keep
 
 
+def tuned_array(lib, entries):
+    """table entries (the dicts of tuned_cfgs*.json) -> (mdhip_tuned array, count) as mdhip_set_tuned takes them"""
+    ncfg = lib.mdhip_num_conv_cfgs()
+    # an entry names its configuration; the id is looked up in THIS build (ids shift when a kernel family is
+    # added or removed), entries without a name keep their id, entries naming an unknown configuration are dropped
+    by_name = {lib.mdhip_conv_cfg_name(i).decode(): i for i in range(ncfg)}
+    resolved = []
+    for e in entries:
+        if e.get('name'):
+            if e['name'] not in by_name:
+                continue
+            e = dict(e, cfg=by_name[e['name']])
+        if 0 <= int(e['cfg']) < ncfg:
+            resolved.append(e)
+    arr = (_lib.mdhip_tuned * max(1, len(resolved)))()
+    for i, e in enumerate(resolved):
+        arr[i].m, arr[i].n, arr[i].k = int(e['m']), int(e['n']), int(e['k'])
+        arr[i].ntaps, arr[i].stride = int(e['ntaps']), int(e['stride'])
+        arr[i].has_res, arr[i].cfg = int(e['has_res']), int(e['cfg'])
+        arr[i].batch = int(e.get('batch', 32))
+    return arr, len(resolved)
+
+
+def _described(call, what):
+    """the text of one of the describe calls: asked for its length first, then written"""
+    lib = _lib.load()
+    need = call(None, 0)
+    if need >= 0:
+        buf = C.create_string_buffer(need + 1)
+        need = call(buf, need + 1)
+    if need < 0:
+        err = HipError('{} failed ({}): {}'.format(what, need, lib.mdhip_last_error(None).decode()))
+        err.code = int(need)
+        raise err
+    return buf.value.decode()
+
+
 def describe_plan(weights, dtype='bf16', max_batch=32, max_h=1280, max_w=1280):
     """
     What mdhip_create would plan for these weights, as text (mdhip_plan_describe): the ops, every tensor's place in the
@@ -73,16 +110,37 @@ def describe_plan(weights, dtype='bf16', max_batch=32, max_h=1280, max_w=1280):
     lib = _lib.load()
     m, keep = model_description(weights)
     args = (C.byref(m), _DTYPES[dtype], int(max_batch), int(max_h), int(max_w))
-    need = lib.mdhip_plan_describe(*args, None, 0)
-    if need >= 0:
-        buf = C.create_string_buffer(need + 1)
-        need = lib.mdhip_plan_describe(*args, buf, need + 1)
-    if need < 0:
-        err = HipError('mdhip_plan_describe failed ({}): {}'.format(need, lib.mdhip_last_error(None).decode()))
-        err.code = int(need)
-        raise err
-    del keep
-    return buf.value.decode()
+    return _described(lambda buf, cap: lib.mdhip_plan_describe(*args, buf, cap), 'mdhip_plan_describe')
+
+
+def describe_launches(weights, dtype, capacity, tuned_entries, n, h, w, fuse=True, fuse_decode=True, pair=True, isolated=False,
+                      calibrating=False, augmented=False, forced=None, after_others=False):
+    """
+    What a forward of n images of h x w launches on a context of these weights, storage type and capacity (max_batch, max_h,
+    max_w) with this tile table (the entries of tuned_cfgs*.json; None = none) and these settings, as text
+    (mdhip_launches_describe): one line per op.  `forced`: {op index: configuration id or name}.  Needs no GPU.
+    """
+    lib = _lib.load()
+    m, keep = model_description(weights)
+    arr, n_tuned = tuned_array(lib, tuned_entries or [])
+    flags = ((not fuse) * _lib.MDHIP_LAUNCHES_NO_FUSE | (not fuse_decode) * _lib.MDHIP_LAUNCHES_NO_FUSE_DECODE |
+             (not pair) * _lib.MDHIP_LAUNCHES_NO_PAIR | bool(isolated) * _lib.MDHIP_LAUNCHES_ISOLATED |
+             bool(calibrating) * _lib.MDHIP_LAUNCHES_CALIBRATING | bool(augmented) * _lib.MDHIP_LAUNCHES_AUGMENTED |
+             bool(after_others) * _lib.MDHIP_LAUNCHES_AFTER_OTHERS)
+    by_name = {lib.mdhip_conv_cfg_name(i).decode(): i for i in range(lib.mdhip_num_conv_cfgs())}
+    pairs = [v for op, cfg in sorted((forced or {}).items()) for v in (int(op), by_name[cfg] if isinstance(cfg, str) else int(cfg))]
+    farr = (C.c_int32 * max(1, len(pairs)))(*pairs)
+    args = (C.byref(m), _DTYPES[dtype], *[int(v) for v in capacity], arr, n_tuned, int(n), int(h), int(w), flags, farr, len(pairs) // 2)
+    return _described(lambda buf, cap: lib.mdhip_launches_describe(*args, buf, cap), 'mdhip_launches_describe')
+
+
+def table_entries(dtype='bf16'):
+    """the entries of the shipped tile table a context of this storage type loads (HipContext.load_tuned)"""
+    path = HipContext.TUNED_PATH
+    alt = path.replace('.json', '_{}.json'.format(dtype))
+    if dtype != 'bf16' and os.path.exists(alt):
+        path = alt
+    return json.load(open(path)).get('entries', [])
 
 
 class HipContext:
@@ -132,27 +190,9 @@ class HipContext:
             entries = json.load(open(path)).get('entries', [])
         except Exception:
             return 0
-        ncfg = self.lib.mdhip_num_conv_cfgs()
-        # an entry names its configuration; the id is looked up in THIS build (ids shift when a kernel family is
-        # added or removed), entries without a name keep their id, entries naming an unknown configuration are dropped
-        by_name = {self.lib.mdhip_conv_cfg_name(i).decode(): i for i in range(ncfg)}
-        resolved = []
-        for e in entries:
-            if e.get('name'):
-                if e['name'] not in by_name:
-                    continue
-                e = dict(e, cfg=by_name[e['name']])
-            if 0 <= int(e['cfg']) < ncfg:
-                resolved.append(e)
-        entries = resolved
-        arr = (_lib.mdhip_tuned * max(1, len(entries)))()
-        for i, e in enumerate(entries):
-            arr[i].m, arr[i].n, arr[i].k = int(e['m']), int(e['n']), int(e['k'])
-            arr[i].ntaps, arr[i].stride = int(e['ntaps']), int(e['stride'])
-            arr[i].has_res, arr[i].cfg = int(e['has_res']), int(e['cfg'])
-            arr[i].batch = int(e.get('batch', 32))
-        self._check(self.lib.mdhip_set_tuned(self.h, arr, len(entries)), 'mdhip_set_tuned')
-        return len(entries)
+        arr, n = tuned_array(self.lib, entries)
+        self._check(self.lib.mdhip_set_tuned(self.h, arr, n), 'mdhip_set_tuned')
+        return n
 
     # -- plumbing ---------------------------------------------------------------------
     def _check(self, rc, what):

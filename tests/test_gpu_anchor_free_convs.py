@@ -200,7 +200,7 @@ def test_every_conv_configuration(name, dtype):
 
 def _up_readers(ctx, W):
     """[(upsample op, its reader conv op, whether the in-place read is admitted)].  The reader is the cv1 of the
-    C3k2 / RepNCSPELAN4 behind the Concat; up_is_absorbed (mdhip_exec.cpp) admits the pair when the upsample's input
+    C3k2 / RepNCSPELAN4 behind the Concat; absorb_upsample (mdhip_exec.cpp) admits the pair when the upsample's input
     has whole 64-channel slabs (the conv's map is twice the upsample input's, so even)"""
     infos = ctx.op_infos()
     out = []
@@ -259,7 +259,7 @@ def test_upsample_read_in_place_on_the_heads(name, dtype):
             if rd in forced:
                 assert infos[rd]['cfg'] == cfg, (infos[rd]['name'], infos[rd]['cfg'])
             admitted = admitted and rd in forced
-            # mdhip_exec.cpp run_op: an upsample read in place by its consumer is not launched and reports no bytes
+            # mdhip_exec.cpp resolve: an upsample read in place by its consumer is not launched and reports no bytes
             assert (infos[u]['bytes'] == 0) == admitted, (infos[u]['name'], infos[rd]['name'], admitted, infos[u]['bytes'])
             if admitted:
                 absorbed.append(infos[rd]['name'])
