@@ -24,6 +24,9 @@ never exist on the host; `jpeg_images_reconstructed` counts them.  Or as a jpeg_
 descriptor of its scan, feed.py decode='scan'): decode_scans() Huffman-decodes those on the device first
 (mdhip_jpeg_entropy_decode; `jpeg_images_entropy_decoded` counts them) and decodes a file the GPU flags with PIL from the
 bytes it holds (`jpeg_entropy_fallbacks`).
+The device is driven in one way: start_batch() enqueues the groups of a batch on the detector's streams and finish_batch()
+collects them; generate_detections_one_batch is the two in one call and generate_detections_for_tiles runs its chunks through
+the same runner (_run_group / _collect_group), behind the windowed letterbox.
 """
 
 import json
@@ -292,24 +295,9 @@ class HIPDetector:
             for i_img, img in enumerate(img_original):
                 if isinstance(img, dict):
                     raise ValueError('Mixed input types in batch: item {} is a dict, but item 0 is not a dict'.format(i_img))
-        if detection_threshold is None:
-            detection_threshold = 0.0
-        if self._ctx is None:
-            raise RuntimeError('this HIPDetector was created with preprocess_only')
-        self._check_augment(augment)
-        products = self._products(crops, blur, preview, classify)
-        img_original = self.decode_scans(img_original)
-        results, shape_groups = self._prepare_batch(img_original, image_id, image_size, verbose)
-        for shape, items in shape_groups.items():
-            try:
-                for start in range(0, len(items), self.max_batch):
-                    self._process_batch_group(items[start:start + self.max_batch], results,
-                                              detection_threshold, augment, verbose, products)
-            except Exception as e:
-                print('Warning: batch inference failed for shape {}: {}'.format(shape, str(e)))
-                for original_idx, _, current_id in items:
-                    results[original_idx] = {'file': current_id, 'detections': None, 'failure': FAILURE_INFER}
-        return self._products_everywhere(results, products)
+        # one group in flight at a time: each chunk is collected before the next is enqueued, the last one here
+        return self.finish_batch(self.start_batch(img_original, image_id, detection_threshold, image_size, augment, verbose,
+                                                  crops=crops, blur=blur, preview=preview, classify=classify))
 
     def _products(self, crops, blur, preview, classify=None):
         """the products asked for (crops.Product), in the order their kernels are enqueued"""
@@ -428,7 +416,7 @@ class HIPDetector:
         import io
         from .feed import load_image
         pl = self._pipeline()
-        torch = pl['torch']
+        torch = pl.torch
         images = list(images)
         scan_offs, coef_offs, nbytes, nvals = [], [], 0, 0
         for i in idx:
@@ -439,10 +427,10 @@ class HIPDetector:
         host = np.zeros(nbytes, dtype=np.uint8)
         for i, off in zip(idx, scan_offs):
             host[off:off + images[i].nbytes] = images[i].scan_bytes
-        comp = pl['comp_s']
-        with torch.cuda.device(pl['dev']), torch.cuda.stream(comp):
-            scans = torch.from_numpy(host).to(pl['dev'])
-            coefs = torch.empty(max(nvals, 1), dtype=torch.int16, device=pl['dev'])
+        comp = pl.comp_s
+        with torch.cuda.device(pl.dev), torch.cuda.stream(comp):
+            scans = torch.from_numpy(host).to(pl.dev)
+            coefs = torch.empty(max(nvals, 1), dtype=torch.int16, device=pl.dev)
             status = self._ctx.jpeg_entropy_decode([images[i] for i in idx], [scans.data_ptr() + o for o in scan_offs],
                                                    [coefs.data_ptr() + 2 * o for o in coef_offs], stream=comp.cuda_stream)
         for i, off, st in zip(idx, coef_offs, status):
@@ -458,31 +446,6 @@ class HIPDetector:
                 images[i] = ScanFailure(e)
         return images
 
-    def _reconstruct_jpegs(self, images):
-        """synchronous path: coefficient images -> device RGB images (integer pointers); returns (images, tensors to keep)"""
-        idx = [i for i, im in enumerate(images) if isinstance(im, CoefficientImage)]
-        if not idx:
-            return images, None
-        import torch
-        dev = torch.device('cuda', _device_ordinal(self.device))
-        images = list(images)
-        hold = []
-        with torch.cuda.device(dev):
-            coefs, outs = [], []
-            for i in idx:
-                im = images[i]
-                c = im.coef.tensor() if isinstance(im, DeviceCoefficientImage) else torch.from_numpy(np.array(im.coef, dtype=np.int16)).to(dev)
-                o = torch.empty(int(np.prod(im.shape)), dtype=torch.uint8, device=dev)
-                coefs.append(c)
-                outs.append(o)
-            hold = coefs + outs
-            torch.cuda.synchronize(dev)
-            self._ctx.jpeg_reconstruct([images[i] for i in idx], [c.data_ptr() for c in coefs], [o.data_ptr() for o in outs])
-            for i, o in zip(idx, outs):
-                images[i] = o.data_ptr()
-        self.jpeg_images_reconstructed += len(idx)
-        return images, hold
-
     def _fp8_calibrated(self):
         self._fp8_pending = False
         if self._fp8_scales_file:
@@ -490,47 +453,6 @@ class HIPDetector:
             with open(tmp, 'w') as f:
                 json.dump({'fp8_scales': [float(sc) for sc, _, _ in self._ctx.fp8_scales()]}, f)
             os.replace(tmp, self._fp8_scales_file)
-
-    def _process_batch_group(self, group_items, results, detection_threshold, augment, verbose, products=()):
-        """reference pytorch_detector.py:1257-1426 with the device work in libmdhip.so"""
-        if len(group_items) == 0:
-            return
-        h, w = group_items[0][1]['img_processed'].shape[:2]
-        images, geoms = self._group_inputs(group_items)
-        n = len(group_items)
-        ctx = self._ctx
-        images, hold = self._reconstruct_jpegs(images)       # (`hold` keeps the device images alive until the NMS has returned)
-        tensors = None
-        if products:
-            # every source image on the device exactly once, where the encoder can still address it: host arrays that
-            # mdhip_preprocess would stage internally are uploaded here and passed as device pointers
-            import torch
-            dev = torch.device('cuda', _device_ordinal(self.device))
-            rebuilt = {o.data_ptr(): o for o in (hold or [])}
-            tensors = []
-            for i, im in enumerate(images):
-                if isinstance(im, np.ndarray):
-                    flat = im.reshape(-1)
-                    if not flat.flags.writeable:
-                        flat = np.array(flat)
-                    t = torch.from_numpy(flat).to(dev)
-                    images[i] = t.data_ptr()
-                else:
-                    t = rebuilt[im]
-                tensors.append(t)
-            torch.cuda.synchronize(dev)
-        ctx.preprocess(images, geoms, h, w)
-        if self._fp8_pending:               # fp8 mode, explicit opt-in: this batch calibrates the scales
-            ctx.calibrate(n, h, w)
-            self._fp8_calibrated()
-        if augment:
-            ctx.forward_tta(n, h, w)        # yolov5 _forward_augment: 3 passes, concatenated predictions
-        else:
-            ctx.forward(n, h, w)
-        det_all, counts = ctx.nms(n, detection_threshold, self._nms_iou(), max_det=300)
-        self._format_group(group_items, det_all, counts, h, w, results, detection_threshold)
-        if products:
-            self._add_products(group_items, tensors, results, products)
 
     # -----------------------------------------------------------------------------------
     def generate_detections_for_tiles(self, img_original, tile_origins, tile_size, tile_ids=None,
@@ -546,6 +468,8 @@ class HIPDetector:
         Returns one result dict per tile, the very dicts generate_detections_one_batch returns for the list of crops
         img[y:y + h, x:x + w]: a tile counts as an image of size (h, w).  Tiles are processed in chunks of max_batch; an
         exception in a chunk marks that chunk's tiles 'inference failure'.
+        Every chunk takes one of the four NMS result slots in turn, like the groups of start_batch(): with two tickets
+        outstanding a call of more than two chunks reaches a slot a ticket holds, and that chunk fails.
 
         jpeg_quality (1 .. 100, default None = off): every tile first goes through a JPEG round trip on the device
         (mdhip_jpeg_recompress) and the detector sees what it would read from the tile FILE the reference writes with
@@ -580,8 +504,7 @@ class HIPDetector:
         results, shape_groups = self._prepare_batch(views, list(tile_ids), image_size, verbose)
         if not shape_groups:
             return results
-        import torch
-        dev = torch.device('cuda', _device_ordinal(self.device))
+        torch, dev = self._pipeline().torch, self._pipeline().dev
         pitch, total = W * 3, H * W * 3
         with torch.cuda.device(dev):
             parent = torch.empty(total, dtype=torch.uint8, device=dev)      # exactly the image: `readable` is exact
@@ -612,66 +535,54 @@ class HIPDetector:
         in a buffer this detector owns.  Returns the (chunk, origins, base, pitch, total) that make _process_tile_chunk
         read them: each a window that covers a whole image, one behind the other like the rows of a tw-wide strip.
         """
-        import torch
+        pl = self._pipeline()
         tw, th = tile_size
         n = len(chunk)
         tile_bytes = th * tw * 3
         buf = getattr(self, '_tile_jpeg_buf', None)
         if buf is None or buf.numel() < n * tile_bytes:
-            torch.cuda.synchronize()                                        # (earlier kernels may still read the old buffer)
-            self._tile_jpeg_buf = buf = torch.empty(n * tile_bytes, dtype=torch.uint8,
-                                                    device=torch.device('cuda', _device_ordinal(self.device)))
+            pl.torch.cuda.synchronize()                                     # (earlier kernels may still read the old buffer)
+            self._tile_jpeg_buf = buf = pl.torch.empty(n * tile_bytes, dtype=pl.torch.uint8, device=pl.dev)
         out = buf.data_ptr()
+        # on the compute stream: behind the letterbox that read `out` last and in front of the one that reads it next
         self._ctx.jpeg_recompress([base + origins[idx][1] * pitch + origins[idx][0] * 3 for idx, _, _ in chunk], [(tw, th)] * n,
-                                  [pitch] * n, quality, [out + i * tile_bytes for i in range(n)])
+                                  [pitch] * n, quality, [out + i * tile_bytes for i in range(n)], stream=pl.comp_s.cuda_stream)
         strip = {idx: (0, i * th) for i, (idx, _, _) in enumerate(chunk)}
         return chunk, strip, out, tw * 3, n * tile_bytes
 
     def _process_tile_chunk(self, chunk, origins, base, pitch, total, results, detection_threshold, augment):
-        """_process_batch_group for windows of the device image at `base` (row pitch `pitch`, `total` bytes)"""
+        """the chunk's windows of the device image at `base` (row pitch `pitch`, `total` bytes): letterboxed in place on the
+        compute stream, run like a dense group (_run_group) and collected at once -- tile chunks do not overlap"""
         h, w = chunk[0][1]['img_processed'].shape[:2]
         n = len(chunk)
         offs = [origins[idx][1] * pitch + origins[idx][0] * 3 for idx, _, _ in chunk]
-        ctx = self._ctx
-        ctx.preprocess_windows([base + o for o in offs], [info['img_processed'].geometry for _, info, _ in chunk],
-                               [pitch] * n, [total - o for o in offs], h, w)
-        if self._fp8_pending:
-            ctx.calibrate(n, h, w)
-            self._fp8_calibrated()
-        if augment:
-            ctx.forward_tta(n, h, w)
-        else:
-            ctx.forward(n, h, w)
-        det_all, counts = ctx.nms(n, detection_threshold, self._nms_iou(), max_det=300)
-        self._format_group(chunk, det_all, counts, h, w, results, detection_threshold)
+        self._ctx.preprocess_windows([base + o for o in offs], [info['img_processed'].geometry for _, info, _ in chunk],
+                                     [pitch] * n, [total - o for o in offs], h, w, stream=self._pipeline().comp_s.cuda_stream)
+        self._collect_group(self._run_group(chunk, detection_threshold, augment), results, detection_threshold)
 
     # -----------------------------------------------------------------------------------
-    # Pipelined variant of generate_detections_one_batch for the batch driver (feed.py): the device work
-    # of a batch is enqueued on a private stream and the call returns; finish_batch() waits for it and
-    # formats.  Host images are copied to the device on a copy stream into one of two staging buffers
-    # (asynchronously when they live in page-locked memory, e.g. feed.SharedImageRing), so the copy of
-    # batch i+1 overlaps the kernels of batch i.  Same kernels, same results as the synchronous call.
+    # The one device path.  The device work of a group (the images of one letterboxed shape, at most max_batch of them, or a
+    # chunk of tiles) is enqueued on private streams (_submit_group, _run_group) and collected later (_collect_group):
+    # start_batch() returns with its last group in flight and finish_batch() waits for it and formats, so a caller that keeps
+    # two tickets outstanding (the batch driver, feed.py) overlaps the copy of batch i+1 with the kernels of batch i;
+    # generate_detections_one_batch is start_batch + finish_batch, one group in flight at a time.  Host images are copied
+    # to the device on a copy stream into one of two staging buffers (asynchronously when they live in page-locked memory,
+    # e.g. feed.SharedImageRing).  _Pipeline and _StagingSlot (below the class) hold the streams and the buffers' rules.
     # -----------------------------------------------------------------------------------
     def _pipeline(self):
         if getattr(self, '_pl', None) is None:
-            import torch
-            dev = torch.device('cuda', _device_ordinal(self.device))
-            with torch.cuda.device(dev):
-                self._pl = {'torch': torch, 'dev': dev, 'copy_s': torch.cuda.Stream(), 'comp_s': torch.cuda.Stream(),
-                            'nms_s': torch.cuda.Stream(), 'nms_done': [None] * 4,
-                            'stage': [None, None], 'copied': [torch.cuda.Event(), torch.cuda.Event()],
-                            'consumed': [None, None], 'count': 0, 'owes_products': [None, None]}
+            self._pl = _Pipeline(self.device)
         return self._pl
 
     def _submit_group(self, group_items, detection_threshold, augment=False, products=()):
+        """a dense group: its host images into a staging buffer, coefficient images rebuilt behind them, the letterbox, then
+        _run_group; returns the handle for _collect_group"""
         pl = self._pipeline()
-        torch = pl['torch']
+        torch = pl.torch
         h, w = group_items[0][1]['img_processed'].shape[:2]
         images, geoms = self._group_inputs(group_items)
-        n = len(group_items)
-        k = pl['count'] % 2
-        nms_slot = pl['count'] % 4
-        pl['count'] += 1
+        slot = pl.slots[pl.staged % 2]
+        pl.staged += 1
         offs, total = [], 0
         for im in images:
             offs.append(total)
@@ -682,21 +593,9 @@ class HIPDetector:
         for i in jpeg_idx:
             rgb_offs[i] = total
             total += (int(np.prod(images[i].shape)) + 255) // 256 * 256
-        with torch.cuda.device(pl['dev']):
-            if pl['owes_products'][k] is not None:
-                # a group whose products are not made yet (a ticket that is still outstanding) keeps its pixels in this
-                # buffer, and `consumed` stands behind its letterbox only: that group keeps the storage (its views hold
-                # it) and this one gets a tensor of its own
-                pl['stage'][k] = None
-                pl['owes_products'][k] = None
-            if pl['stage'][k] is None or pl['stage'][k].numel() < total:
-                if pl['consumed'][k] is not None:
-                    pl['consumed'][k].synchronize()
-                pl['stage'][k] = torch.empty(max(total, 1), dtype=torch.uint8, device=pl['dev'])
-            stage = pl['stage'][k]
-            with torch.cuda.stream(pl['copy_s']):
-                if pl['consumed'][k] is not None:
-                    pl['copy_s'].wait_event(pl['consumed'][k])      # the letterbox kernel that read this buffer is done
+        with torch.cuda.device(pl.dev):
+            stage = slot.take(total, pl.copy_s)
+            with torch.cuda.stream(pl.copy_s):
                 for im, off in zip(images, offs):
                     if isinstance(im, DeviceCoefficientImage):
                         continue                          # its planes are on the device already (decode_scans)
@@ -708,87 +607,98 @@ class HIPDetector:
                         except ValueError:
                             flat = np.array(flat)
                     stage[off:off + im.nbytes].copy_(torch.from_numpy(flat), non_blocking=True)
-                pl['copied'][k].record(pl['copy_s'])
-            comp = pl['comp_s']
+                slot.copied.record(pl.copy_s)
+            comp = pl.comp_s
             base = stage.data_ptr()
-            ctx = self._ctx
-            comp.wait_event(pl['copied'][k])
+            comp.wait_event(slot.copied)
             srcs = [base + off for off in offs]
             if jpeg_idx:
-                ctx.jpeg_reconstruct([images[i] for i in jpeg_idx],
-                                     [images[i].coef.data_ptr() if isinstance(images[i], DeviceCoefficientImage) else base + offs[i]
-                                      for i in jpeg_idx],
-                                     [base + rgb_offs[i] for i in jpeg_idx], stream=comp.cuda_stream)
+                self._ctx.jpeg_reconstruct([images[i] for i in jpeg_idx],
+                                           [images[i].coef.data_ptr() if isinstance(images[i], DeviceCoefficientImage) else base + offs[i]
+                                            for i in jpeg_idx],
+                                           [base + rgb_offs[i] for i in jpeg_idx], stream=comp.cuda_stream)
                 for i in jpeg_idx:
                     srcs[i] = base + rgb_offs[i]
                 self.jpeg_images_reconstructed += len(jpeg_idx)
             # (the letterbox on the copy stream next to the previous batch's forward -- mdhip_preprocess waits for that
             # forward's stem inside the library -- was measured with bench.py --pre-own-stream: 0.6 % slower, its workgroups
             # keep the 8-wave conv workgroups off their CUs; it stays on the compute stream)
-            ctx.preprocess(srcs, geoms, h, w, stream=comp.cuda_stream)
-            if self._fp8_pending:
+            self._ctx.preprocess(srcs, geoms, h, w, stream=comp.cuda_stream)
+            slot.consumed = consumed = torch.cuda.Event()
+            consumed.record(comp)
+            handle = self._run_group(group_items, detection_threshold, augment)
+        handle['copied'], handle['images'] = slot.copied, images      # (the host arrays live until the ticket is done)
+        if products:
+            # the pixels stay in the staging buffer until the products are made (_collect_group): views of it, per image
+            handle['products'], handle['staged'], handle['consumed'] = products, slot, consumed
+            slot.owed = handle
+            handle['tensors'] = [stage[rgb_offs[i]:rgb_offs[i] + int(np.prod(im.shape))] if i in rgb_offs
+                                 else stage[offs[i]:offs[i] + im.nbytes] for i, im in enumerate(images)]
+        return handle
+
+    def _run_group(self, group_items, detection_threshold, augment):
+        """What follows the letterbox, for a dense group and for a chunk of tiles alike: calibration if it is due, the forward on
+        the compute stream, the NMS on its own stream into the next of the four result slots.  Returns the handle
+        _collect_group takes."""
+        pl = self._pipeline()
+        torch, ctx, comp = pl.torch, self._ctx, pl.comp_s
+        h, w = group_items[0][1]['img_processed'].shape[:2]
+        n = len(group_items)
+        nms_slot = pl.count % 4
+        if pl.uncollected[nms_slot]:
+            raise RuntimeError('NMS result slot {} holds a group that has not been collected: finish the outstanding tickets '
+                               'before enqueueing more groups'.format(nms_slot))
+        pl.count += 1
+        with torch.cuda.device(pl.dev):
+            if self._fp8_pending:               # fp8 mode, explicit opt-in: this batch calibrates the scales
                 ctx.calibrate(n, h, w, stream=comp.cuda_stream)
                 self._fp8_calibrated()
-            ev = torch.cuda.Event()
-            ev.record(comp)
-            pl['consumed'][k] = ev
             # NMS + D2H on their own stream, next to the following batch's letterbox and first layers (the library
             # alternates between two prediction buffers; the forward that reuses a buffer waits for the NMS that read it).
             # History: own stream in round 1; in line behind the forward in rounds 2-3 (the 1024-thread NMS workgroups kept
             # the persistent conv workgroups off their CUs: 37.6 vs 37.2 ms / step); since round 4 the NMS sorts only the
             # confidence band it needs and is gone before the next forward reaches its 8-wave kernels: own stream again
             # (+0.4 .. 0.7 % at batch 32, profiles/r4_bench_nms_stream.txt).
-            prev = pl['nms_done'][(pl['count'] - 3) % 4]             # (count was incremented above: the batch two before this one)
+            prev = pl.nms_done[(nms_slot - 2) % 4]                   # the group two before this one
             if prev is not None:
                 comp.wait_event(prev)
             if augment:
-                ctx.forward_tta(n, h, w, stream=comp.cuda_stream)
+                ctx.forward_tta(n, h, w, stream=comp.cuda_stream)    # yolov5 _forward_augment: 3 passes, concatenated predictions
             else:
                 ctx.forward(n, h, w, stream=comp.cuda_stream)
             fwd_done = torch.cuda.Event()
             fwd_done.record(comp)
-            nms_s = pl['nms_s']
-            nms_s.wait_event(fwd_done)
-            ctx.nms_enqueue(n, detection_threshold, self._nms_iou(), 300, slot=nms_slot, stream=nms_s.cuda_stream)
+            pl.nms_s.wait_event(fwd_done)
+            ctx.nms_enqueue(n, detection_threshold, self._nms_iou(), 300, slot=nms_slot, stream=pl.nms_s.cuda_stream)
             done = torch.cuda.Event()
-            done.record(nms_s)
-            pl['nms_done'][nms_slot] = done
-        handle = {'items': group_items, 'h': h, 'w': w, 'slot': nms_slot, 'copied': pl['copied'][k], 'images': images}
-        if products:
-            # the pixels stay in staging buffer k until the products are made (_collect_group): views of it, per image
-            handle['products'], handle['k'], handle['consumed'] = products, k, ev
-            pl['owes_products'][k] = handle
-            handle['tensors'] = [stage[rgb_offs[i]:rgb_offs[i] + int(np.prod(im.shape))] if i in rgb_offs
-                                 else stage[offs[i]:offs[i] + im.nbytes] for i, im in enumerate(images)]
-        return handle
+            done.record(pl.nms_s)
+            pl.nms_done[nms_slot], pl.uncollected[nms_slot] = done, True
+        return {'items': group_items, 'h': h, 'w': w, 'slot': nms_slot}
 
     def _collect_group(self, handle, results, detection_threshold):
-        det_all, counts = self._ctx.nms_wait(slot=handle['slot'])
+        """waits for a group's NMS, formats its results and makes the products it owes"""
+        try:
+            det_all, counts = self._ctx.nms_wait(slot=handle['slot'])
+        finally:
+            self._pipeline().uncollected[handle['slot']] = False
         self._format_group(handle['items'], det_all, counts, handle['h'], handle['w'], results, detection_threshold)
         if handle.get('tensors') is not None:
             pl = self._pipeline()
-            torch = pl['torch']
-            with torch.cuda.device(pl['dev']):
-                if pl.get('product_s') is None:
-                    pl['product_s'] = torch.cuda.Stream()
-                product_s = pl['product_s']
-                product_s.wait_event(handle['consumed'])         # copies, reconstruction and letterbox of this batch are done
+            with pl.torch.cuda.device(pl.dev):
+                product_s = pl.product_stream()
+                product_s.wait_event(handle['consumed'])      # copies, reconstruction and letterbox of this batch are done
                 try:
                     self._add_products(handle['items'], handle['tensors'], results, handle['products'], stream=product_s.cuda_stream)
                 finally:
-                    # While this group owned staging buffer k no other group could take it (_submit_group gives a later one a
-                    # tensor of its own).  From here on the buffer may be reused: its `consumed` event moves behind the
-                    # products' kernels, so the copy stream overwrites it only behind this group's last encode.
-                    if pl['owes_products'][handle['k']] is handle:
-                        pl['owes_products'][handle['k']] = None
-                        if pl['consumed'][handle['k']] is handle['consumed']:
-                            ev = torch.cuda.Event()
-                            ev.record(product_s)
-                            pl['consumed'][handle['k']] = ev
+                    handle['staged'].products_made(handle, product_s)
 
     def start_batch(self, img_original, image_id, detection_threshold=0.00001, image_size=None, augment=False,
                     verbose=False, crops=None, blur=None, preview=None, classify=None):
-        """Enqueues a batch; returns a ticket for finish_batch().  At most two tickets may be outstanding.
+        """Enqueues a batch; returns a ticket for finish_batch(), and every ticket must be finished.  At most two tickets may
+        be outstanding, and at most four groups can be in flight: every shape group of at most max_batch images takes one of
+        the four NMS result slots until it is collected, and so does every chunk of the other calls.  All groups of a batch
+        but the last are collected here.  The slots are taken in turn: a group whose slot is still held by an
+        uncollected group fails ('inference failure').
         Same arguments as generate_detections_one_batch (augment = yolov5's three-pass augmented inference)."""
         if self._ctx is None:
             raise RuntimeError('this HIPDetector was created with preprocess_only')
@@ -847,3 +757,69 @@ class HIPDetector:
             res = self.generate_detections_one_batch([img_original], [image_id], detection_threshold,
                                                      image_size, augment, verbose, crops=crops, blur=blur, preview=preview, classify=classify)
         return res[0]
+
+
+class _StagingSlot:
+    """
+    One of the pipeline's two staging buffers: a group's host images are copied into `tensor` on the copy stream (`copied`
+    stands behind the copies), coefficient images are rebuilt behind them, and the letterbox reads it (`consumed` stands
+    behind the last kernel that read the buffer).  `owed` is the group whose products are not made yet.
+    """
+
+    def __init__(self, torch, dev):
+        self.torch, self.dev = torch, dev
+        self.tensor = None
+        self.copied = torch.cuda.Event()
+        self.consumed = None
+        self.owed = None
+
+    def take(self, total, copy_s):
+        """the buffer with room for `total` bytes, for the next group, whose copies go onto the stream `copy_s`"""
+        if self.owed is not None:
+            # a group whose products are not made yet (a ticket that is still outstanding) keeps its pixels in this
+            # buffer, and `consumed` stands behind its letterbox only: that group keeps the storage (its views hold
+            # it) and this one gets a tensor of its own
+            self.tensor = None
+            self.owed = None
+        if self.tensor is None or self.tensor.numel() < total:
+            if self.consumed is not None:
+                self.consumed.synchronize()
+            self.tensor = self.torch.empty(max(total, 1), dtype=self.torch.uint8, device=self.dev)
+        if self.consumed is not None:
+            copy_s.wait_event(self.consumed)        # the letterbox kernel that read this buffer is done
+        return self.tensor
+
+    def products_made(self, handle, product_s):
+        """While `handle`'s group owned the buffer no other group could take it (take() gives a later one a tensor of its
+        own).  From here on the buffer may be reused: its `consumed` event moves behind the products' kernels, so the copy
+        stream overwrites it only behind this group's last encode."""
+        if self.owed is handle:
+            self.owed = None
+            if self.consumed is handle['consumed']:
+                self.consumed = self.torch.cuda.Event()
+                self.consumed.record(product_s)
+
+
+class _Pipeline:
+    """The streams, the two staging buffers and the four NMS result slots of a HIPDetector, made on first use.  `count` numbers
+    the groups enqueued, dense groups and tile chunks alike: nms_done[count % 4] is the event behind a group's NMS and
+    uncollected[count % 4] says that its results have not been fetched, so the slot must not be written.  `staged` numbers
+    the dense groups alone, which alternate between the two staging buffers."""
+
+    def __init__(self, device):
+        import torch
+        self.torch = torch
+        self.dev = torch.device('cuda', _device_ordinal(device))
+        with torch.cuda.device(self.dev):
+            self.copy_s, self.comp_s, self.nms_s = torch.cuda.Stream(), torch.cuda.Stream(), torch.cuda.Stream()
+            self.slots = [_StagingSlot(torch, self.dev), _StagingSlot(torch, self.dev)]
+        self.product_s = None               # made when the first product is asked for
+        self.count = self.staged = 0
+        self.uncollected = [False] * 4
+        self.nms_done = [None] * 4
+
+    def product_stream(self):
+        if self.product_s is None:
+            with self.torch.cuda.device(self.dev):
+                self.product_s = self.torch.cuda.Stream()
+        return self.product_s

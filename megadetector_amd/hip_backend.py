@@ -143,6 +143,23 @@ def table_entries(dtype='bf16'):
     return json.load(open(path)).get('entries', [])
 
 
+def _window_arrays(ptrs, sizes, pitches):
+    """per image or window its device address, (width, height) and bytes a row -> the pointer, width, height and pitch arrays
+    the image entry points take"""
+    n = len(ptrs)
+    return (C.cast((C.c_void_p * n)(*[int(v) for v in ptrs]), C.POINTER(C.c_void_p)), (C.c_int32 * n)(*[int(v[0]) for v in sizes]),
+            (C.c_int32 * n)(*[int(v[1]) for v in sizes]), (C.c_int64 * n)(*[int(v) for v in pitches]))
+
+
+def _letterbox_array(geoms):
+    """[(src_h, src_w, resized_h, resized_w, top, left[, interp])] -> mdhip_letterbox array"""
+    g = (_lib.mdhip_letterbox * len(geoms))()
+    for i, q in enumerate(geoms):
+        g[i].src_h, g[i].src_w, g[i].resized_h, g[i].resized_w, g[i].top, g[i].left = [int(v) for v in q[:6]]
+        g[i].interp = int(q[6]) if len(q) > 6 else 0
+    return g
+
+
 class HipContext:
 
     def __init__(self, weights, device=0, dtype='bf16', max_batch=32, max_h=1280, max_w=1280):
@@ -229,12 +246,8 @@ class HipContext:
                 ptrs[i] = im.ctypes.data
             else:
                 ptrs[i] = int(im)
-        g = (_lib.mdhip_letterbox * n)()
-        for i, q in enumerate(geoms):
-            g[i].src_h, g[i].src_w, g[i].resized_h, g[i].resized_w, g[i].top, g[i].left = [int(v) for v in q[:6]]
-            g[i].interp = int(q[6]) if len(q) > 6 else 0
-        self._check(self.lib.mdhip_preprocess(self.h, C.cast(ptrs, C.POINTER(C.c_void_p)), g, n, int(out_h), int(out_w),
-                                              C.c_void_p(stream)), 'mdhip_preprocess')
+        self._check(self.lib.mdhip_preprocess(self.h, C.cast(ptrs, C.POINTER(C.c_void_p)), _letterbox_array(geoms), n,
+                                              int(out_h), int(out_w), C.c_void_p(stream)), 'mdhip_preprocess')
 
     def preprocess_windows(self, ptrs, geoms, pitches, readable, out_h, out_w, stream=0):
         """
@@ -248,14 +261,10 @@ class HipContext:
         if not (len(geoms) == len(pitches) == len(readable) == n):
             raise ValueError('ptrs, geoms, pitches and readable must have one entry per window')
         p = (C.c_void_p * n)(*[int(v) for v in ptrs])
-        g = (_lib.mdhip_letterbox * n)()
-        for i, q in enumerate(geoms):
-            g[i].src_h, g[i].src_w, g[i].resized_h, g[i].resized_w, g[i].top, g[i].left = [int(v) for v in q[:6]]
-            g[i].interp = int(q[6]) if len(q) > 6 else 0
         pt = (C.c_int64 * n)(*[int(v) for v in pitches])
         rd = (C.c_int64 * n)(*[int(v) for v in readable])
-        self._check(self.lib.mdhip_preprocess_windows(self.h, C.cast(p, C.POINTER(C.c_void_p)), g, pt, rd, n, int(out_h), int(out_w),
-                                                      C.c_void_p(stream)), 'mdhip_preprocess_windows')
+        self._check(self.lib.mdhip_preprocess_windows(self.h, C.cast(p, C.POINTER(C.c_void_p)), _letterbox_array(geoms), pt, rd, n,
+                                                      int(out_h), int(out_w), C.c_void_p(stream)), 'mdhip_preprocess_windows')
 
     def jpeg_reconstruct(self, images, coef_ptrs, out_ptrs, stream=0):
         """
@@ -322,12 +331,9 @@ class HipContext:
         if not (len(sizes) == len(pitches) == len(out_ptrs) == n):
             raise ValueError('ptrs, sizes, pitches and out_ptrs must have one entry per window')
         ql, qc = quant_tables(quality)
-        p = (C.c_void_p * n)(*[int(v) for v in ptrs])
+        p, ws, hs, pt = _window_arrays(ptrs, sizes, pitches)
         o = (C.c_void_p * n)(*[int(v) for v in out_ptrs])
-        ws = (C.c_int32 * n)(*[int(v[0]) for v in sizes])
-        hs = (C.c_int32 * n)(*[int(v[1]) for v in sizes])
-        pt = (C.c_int64 * n)(*[int(v) for v in pitches])
-        self._check(self.lib.mdhip_jpeg_recompress(self.h, C.cast(p, C.POINTER(C.c_void_p)), ws, hs, pt, n,
+        self._check(self.lib.mdhip_jpeg_recompress(self.h, p, ws, hs, pt, n,
                                                    ql.ctypes.data_as(C.POINTER(C.c_uint16)), qc.ctypes.data_as(C.POINTER(C.c_uint16)),
                                                    C.cast(o, C.POINTER(C.c_void_p)), C.c_void_p(stream)), 'mdhip_jpeg_recompress')
 
@@ -344,12 +350,9 @@ class HipContext:
         if not (len(sizes) == len(pitches) == n):
             raise ValueError('ptrs, sizes and pitches must have one entry per window')
         ql, qc = quant_tables(quality)
-        p = (C.c_void_p * n)(*[int(v) for v in ptrs])
-        ws = (C.c_int32 * n)(*[int(v[0]) for v in sizes])
-        hs = (C.c_int32 * n)(*[int(v[1]) for v in sizes])
-        pt = (C.c_int64 * n)(*[int(v) for v in pitches])
+        p, ws, hs, pt = _window_arrays(ptrs, sizes, pitches)
         offs, lens, need = (C.c_int64 * max(n, 1))(), (C.c_int64 * max(n, 1))(), C.c_int64(0)
-        rc = self.lib.mdhip_jpeg_encode(self.h, C.cast(p, C.POINTER(C.c_void_p)), ws, hs, pt, n,
+        rc = self.lib.mdhip_jpeg_encode(self.h, p, ws, hs, pt, n,
                                         ql.ctypes.data_as(C.POINTER(C.c_uint16)), qc.ctypes.data_as(C.POINTER(C.c_uint16)),
                                         C.c_void_p(int(out_ptr) if capacity else 0), int(capacity), offs, lens, C.byref(need),
                                         C.c_void_p(stream))
@@ -375,13 +378,10 @@ class HipContext:
             raise ValueError('ptrs, sizes and pitches must have one entry per image, rect_image and rects one per rectangle')
         if m == 0:
             return
-        p = (C.c_void_p * n)(*[int(v) for v in ptrs])
-        ws = (C.c_int32 * n)(*[int(v[0]) for v in sizes])
-        hs = (C.c_int32 * n)(*[int(v[1]) for v in sizes])
-        pt = (C.c_int64 * n)(*[int(v) for v in pitches])
+        p, ws, hs, pt = _window_arrays(ptrs, sizes, pitches)
         ri = (C.c_int32 * m)(*[int(v) for v in rect_image])
         rc4 = (C.c_int32 * (4 * m))(*[int(v) for q in rects for v in q])
-        self._check(self.lib.mdhip_blur_regions(self.h, C.cast(p, C.POINTER(C.c_void_p)), ws, hs, pt, n, ri, rc4, m,
+        self._check(self.lib.mdhip_blur_regions(self.h, p, ws, hs, pt, n, ri, rc4, m,
                                                 C.c_float(float(radius)), C.c_void_p(stream)), 'mdhip_blur_regions')
 
     def resample_lanczos(self, src_ptrs, src_sizes, src_pitches, dst_ptrs, dst_sizes, dst_pitches, stream=0):
@@ -395,14 +395,8 @@ class HipContext:
             raise ValueError('one entry per image is needed in every list')
         if n == 0:
             return
-
-        def arrays(ptrs, sizes, pitches):
-            return ((C.c_void_p * n)(*[int(v) for v in ptrs]), (C.c_int32 * n)(*[int(v[0]) for v in sizes]),
-                    (C.c_int32 * n)(*[int(v[1]) for v in sizes]), (C.c_int64 * n)(*[int(v) for v in pitches]))
-        sp, sw, sh, st = arrays(src_ptrs, src_sizes, src_pitches)
-        dp, dw, dh, dt = arrays(dst_ptrs, dst_sizes, dst_pitches)
-        self._check(self.lib.mdhip_resample_lanczos(self.h, C.cast(sp, C.POINTER(C.c_void_p)), sw, sh, st, n,
-                                                    C.cast(dp, C.POINTER(C.c_void_p)), dw, dh, dt, C.c_void_p(stream)),
+        self._check(self.lib.mdhip_resample_lanczos(self.h, *_window_arrays(src_ptrs, src_sizes, src_pitches), n,
+                                                    *_window_arrays(dst_ptrs, dst_sizes, dst_pitches), C.c_void_p(stream)),
                     'mdhip_resample_lanczos')
 
     def draw_ops(self, ptrs, sizes, pitches, op_image, ops, patches_ptr=0, patch_bytes=0, stream=0):
@@ -416,13 +410,10 @@ class HipContext:
             raise ValueError('ptrs, sizes and pitches must have one entry per image, op_image and ops one per operation')
         if m == 0:
             return
-        p = (C.c_void_p * n)(*[int(v) for v in ptrs])
-        ws = (C.c_int32 * n)(*[int(v[0]) for v in sizes])
-        hs = (C.c_int32 * n)(*[int(v[1]) for v in sizes])
-        pt = (C.c_int64 * n)(*[int(v) for v in pitches])
+        p, ws, hs, pt = _window_arrays(ptrs, sizes, pitches)
         oi = (C.c_int32 * m)(*[int(v) for v in op_image])
         flat = (C.c_int32 * (8 * m))(*[int(v) for q in ops for v in q])
-        self._check(self.lib.mdhip_draw_ops(self.h, C.cast(p, C.POINTER(C.c_void_p)), ws, hs, pt, n, oi, flat, m,
+        self._check(self.lib.mdhip_draw_ops(self.h, p, ws, hs, pt, n, oi, flat, m,
                                             C.c_void_p(int(patches_ptr) or None), int(patch_bytes), C.c_void_p(stream)), 'mdhip_draw_ops')
 
     def classifier_input(self, crops, size, out_ptr, filter=0, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), stream=0):

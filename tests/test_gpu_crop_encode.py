@@ -268,6 +268,133 @@ def test_two_tickets_outstanding_and_the_second_holds_three_shape_groups():
     assert det.finish_batch(ta) == want1 and det.finish_batch(tb) == want2
 
 
+def _cut(x, y, w, h):
+    return np.ascontiguousarray(_image()[y:y + h, x:x + w])
+
+
+def _three_one_shape_batches():
+    """three batches of one letterboxed shape each, with names: for calls that are in flight together"""
+    batches = [[_cut(0, 0, 400, 300), _cut(1500, 100, 400, 300), _cut(100, 400, 400, 300)],
+               [_cut(500, 0, 300, 400), _cut(1600, 200, 300, 400)],
+               [_cut(0, 1100, 400, 400), _cut(300, 300, 400, 400), _cut(900, 900, 333, 333)]]
+    det = _yolo_detector(4)
+    for b in batches:
+        assert len({tuple(det.preprocess_image(a)['img_processed'].shape) for a in b}) == 1
+    return batches, [['{}{}.jpg'.format(c, i) for i in range(len(b))] for c, b in zip('abc', batches)]
+
+
+def _crops_equal_the_host_leg(results, images, opt):
+    total = 0
+    for r, a in zip(results, images):
+        assert r.get('failure') is None and r['crops'] == _host_crops(a, r['file'], r['detections'], opt)
+        total += len(r['crops'])
+    return total
+
+
+def test_a_synchronous_call_between_two_outstanding_tickets():
+    """generate_detections_one_batch shares the NMS slots and the staging buffers with the tickets: three groups in flight
+    (of four slots), the tickets' crops still owed while the call in the middle takes a staging buffer and makes its own"""
+    from megadetector_amd import crops as K
+    det = _yolo_detector(4)
+    (first, second, third), (n1, n2, n3) = _three_one_shape_batches()
+    opt = K.CropOptions(confidence_threshold=0.0)
+    kw = dict(detection_threshold=0.0005, crops=opt)
+    want1 = det.finish_batch(det.start_batch(first, n1, **kw))
+    want2 = det.finish_batch(det.start_batch(second, n2, **kw))
+    want3 = det.generate_detections_one_batch(third, n3, **kw)
+    for _ in range(2):          # (the second time the buffers handed out while crops were owed are themselves reused)
+        ta = det.start_batch(first, n1, **kw)
+        tb = det.start_batch(second, n2, **kw)
+        got3 = det.generate_detections_one_batch(third, n3, **kw)
+        got1, got2 = det.finish_batch(ta), det.finish_batch(tb)
+        assert got1 == want1 and got2 == want2 and got3 == want3
+    total = _crops_equal_the_host_leg(got1 + got2 + got3, first + second + third, opt)
+    print('crops:', [sum(len(r['crops']) for r in g) for g in (got1, got2, got3)])
+    assert all(sum(len(r['crops']) for r in g) >= 1 for g in (got1, got2, got3)) and total >= 3, 'a call produced no crop'
+
+
+@pytest.mark.parametrize('jpeg_quality', [None, 90])
+def test_a_tiled_call_between_two_outstanding_tickets(jpeg_quality):
+    """generate_detections_for_tiles runs on the streams and in the NMS slots of the tickets"""
+    from megadetector_amd import crops as K
+    det = _yolo_detector(4)
+    (first, second, _), (n1, n2, _) = _three_one_shape_batches()
+    opt = K.CropOptions(confidence_threshold=0.0)
+    kw = dict(detection_threshold=0.0005, crops=opt)
+    big = _cut(200, 300, 700, 900)
+    origins = [(0, 0), (300, 600), (151, 299)]
+    tiled = lambda: det.generate_detections_for_tiles(big, origins, (400, 300), detection_threshold=0.0005, jpeg_quality=jpeg_quality)
+    want1 = det.finish_batch(det.start_batch(first, n1, **kw))
+    want2 = det.finish_batch(det.start_batch(second, n2, **kw))
+    want_tiles = tiled()
+    assert len(want_tiles) == 3 and all(r.get('failure') is None for r in want_tiles)
+    assert sum(len(r['detections']) for r in want_tiles) >= 1, 'the tiles gave no detection'
+    ta = det.start_batch(first, n1, **kw)
+    tb = det.start_batch(second, n2, **kw)
+    got_tiles = tiled()
+    got1, got2 = det.finish_batch(ta), det.finish_batch(tb)
+    assert got_tiles == want_tiles and got1 == want1 and got2 == want2
+    assert _crops_equal_the_host_leg(got1 + got2, first + second, opt) >= 2
+
+
+@pytest.mark.parametrize('entry', ['one_batch', 'tickets'])
+def test_a_failing_chunk_is_marked_alone_and_the_detector_recovers(entry):
+    """nine images of one shape at max_batch 4 are three chunks; the forward of the second raises (a Python exception on the
+    host, nothing is done to the device): its images fail, the chunks around it and the next call are undisturbed"""
+    from megadetector_amd import crops as K
+    from megadetector_amd._lib import HipError
+    from megadetector_amd.constants import FAILURE_INFER
+    det = _yolo_detector(4)
+    imgs = [_cut(37 * i, 53 * i, 400, 300) for i in range(9)]
+    names = ['f{}.jpg'.format(i) for i in range(9)]
+    opt = K.CropOptions(confidence_threshold=0.0)
+    if entry == 'one_batch':
+        call = lambda: det.generate_detections_one_batch(imgs, names, detection_threshold=0.0005, crops=opt)
+    else:
+        call = lambda: det.finish_batch(det.start_batch(imgs, names, detection_threshold=0.0005, crops=opt))
+    want = call()
+    assert _crops_equal_the_host_leg(want, imgs, opt) >= 1
+    forward, calls = det._ctx.forward, []
+
+    def second_call_raises(*args, **kwargs):
+        calls.append(args)
+        if len(calls) == 2:
+            raise HipError('mdhip_forward failed (test): raised by the test on the host')
+        return forward(*args, **kwargs)
+    det._ctx.forward = second_call_raises
+    try:
+        got = call()
+    finally:
+        del det._ctx.forward
+    assert len(calls) == 3
+    assert got[:4] == want[:4] and got[8:] == want[8:]
+    for r, name in zip(got[4:8], names[4:8]):
+        assert r == {'file': name, 'detections': None, 'failure': FAILURE_INFER, 'crops': []}
+    assert call() == want
+
+
+def test_a_group_whose_nms_slot_a_ticket_holds_is_refused():
+    """the four NMS result slots are taken in turn: with two tickets outstanding the third chunk of a call in between would
+    write into the first ticket's slot.  It fails instead, the tickets keep their results, and the detector goes on"""
+    from megadetector_amd import crops as K
+    from megadetector_amd.constants import FAILURE_INFER
+    det = _yolo_detector(4)
+    (first, second, _), (n1, n2, _) = _three_one_shape_batches()
+    imgs = [_cut(37 * i, 53 * i, 400, 300) for i in range(9)]
+    names = ['f{}.jpg'.format(i) for i in range(9)]
+    kw = dict(detection_threshold=0.0005, crops=K.CropOptions(confidence_threshold=0.0))
+    want1 = det.finish_batch(det.start_batch(first, n1, **kw))
+    want2 = det.finish_batch(det.start_batch(second, n2, **kw))
+    want = det.generate_detections_one_batch(imgs, names, **kw)
+    ta = det.start_batch(first, n1, **kw)
+    tb = det.start_batch(second, n2, **kw)
+    got = det.generate_detections_one_batch(imgs, names, **kw)
+    assert got[:8] == want[:8]
+    assert got[8] == {'file': names[8], 'detections': None, 'failure': FAILURE_INFER, 'crops': []}
+    assert det.finish_batch(ta) == want1 and det.finish_batch(tb) == want2
+    assert det.generate_detections_one_batch(imgs, names, **kw) == want
+
+
 def test_driver_three_feeds_write_the_second_pass(tmp_path):
     """a folder of Pillow-written .jpg files and one .png through run_detector_batch with a crop folder: the PIL feed, gpu_jpeg
     and gpu_jpeg='entropy' write identical folders, equal to the reference's second pass over the results; no .jpg crop
