@@ -497,11 +497,10 @@ static const ConvCfg g_cfgs8[] = {
     MDHIP_CONV8_CFGS(X) MDHIP_CONV8_PROF(X)
 #undef X
 };
-constexpr int kNumProf8 = 9;
+constexpr int kNumCfgs8 = 0 MDHIP_CONV8_CFGS(MDHIP_COUNT_ROW);
+constexpr int kNumProf8 = 0 MDHIP_CONV8_PROF(MDHIP_COUNT_ROW);          // developer variants, behind the configurations
 
-int conv8_num_cfgs() { return (int)(sizeof(g_cfgs8) / sizeof(g_cfgs8[0])) - kNumProf8; }
-const ConvCfg& conv8_cfg(int i) { return g_cfgs8[i]; }
-
+namespace {
 hipError_t conv8_init() {
     hipError_t e = hipSuccess;
 #define X(id, bm, bn, wm, wn, prof)                                                              \
@@ -514,21 +513,17 @@ hipError_t conv8_init() {
 }
 
 bool conv8_supports(int cfg, const ConvArgs& a) {
-    if (cfg < 0 || cfg >= conv8_num_cfgs() + kNumProf8) return false;
+    if (cfg < 0 || cfg >= kNumCfgs8 + kNumProf8) return false;
     return a.in_f8 && !a.out_f8 && !a.out_f32 && a.wgt8 != nullptr && a.scale != nullptr && a.ntaps == 9 && a.kw == 3 &&
            a.stride == 1 && a.pad == 1 && a.Ho == a.H && a.Wo == a.W && a.C8 >= 1 && (a.N % 8) == 0 &&
-           ((long long)a.M + 2 * a.W + g_cfgs8[cfg < conv8_num_cfgs() ? cfg : 0].bm + 16) * a.ld_in < 0x7fffffffLL;   // one descriptor over the tensor
+           ((long long)a.M + 2 * a.W + g_cfgs8[cfg < kNumCfgs8 ? cfg : 0].bm + 16) * a.ld_in < 0x7fffffffLL;   // one descriptor over the tensor
 }
 
 hipError_t conv8_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     if (!conv8_supports(cfg, a)) return hipErrorInvalidValue;
     const ConvCfg& c = g_cfgs8[cfg];
     ConvArgs p = a;
-    p.tiles_n = (a.n_rows + c.bn - 1) / c.bn;
-    p.tiles_m = (a.M + c.bm - 1) / c.bm;
-    p.tiles_per_xcd = (p.tiles_m + 7) / 8;
-    p.m_streams = std::max(1, std::min(p.tiles_per_xcd, (32 * c.blocks_per_cu) / p.tiles_n));
-    const dim3 grid((unsigned)(8 * p.tiles_n * p.m_streams));
+    const dim3 grid = conv_tile_grid(p, c);
     switch (cfg) {
 #define X(id, bm, bn, wm, wn, prof)                                                               \
     case id:                                                                                    \
@@ -539,6 +534,9 @@ hipError_t conv8_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     }
     return hipGetLastError();
 }
+}  // namespace
+
+MDHIP_CONV_FAMILY(conv_f8, CONV_F8, g_cfgs8, kNumCfgs8, kNumProf8, false, true, false, conv8_supports, conv8_launch, conv8_init, nullptr)
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

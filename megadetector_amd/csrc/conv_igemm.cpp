@@ -439,51 +439,49 @@ conv_igemm_kernel(const ConvArgs p) {
 // ---------------------------------------------------------------------------------------
 // configuration table
 // ---------------------------------------------------------------------------------------
-// id, BM, BN, waves along M, waves along N, LDS stages, fragment prefetch
-#define MDHIP_CONV_CFGS(X)     \
-    X(0, 256, 160, 4, 2, 2, 0) \
-    X(1, 128, 160, 2, 2, 2, 0) \
-    X(2, 256, 80, 4, 1, 2, 0)  \
-    X(3, 128, 80, 4, 1, 2, 0)  \
-    X(4, 256, 32, 4, 1, 2, 0)  \
-    X(5, 128, 64, 2, 2, 2, 0)  \
-    X(6, 128, 128, 2, 2, 2, 0) \
-    X(7, 256, 128, 4, 2, 2, 0) \
-    X(8, 128, 320, 2, 4, 2, 0) \
-    X(9, 64, 160, 1, 2, 2, 0)  \
-    X(10, 64, 64, 1, 2, 2, 0)  \
-    X(11, 256, 64, 4, 1, 2, 0) \
-    X(12, 256, 160, 4, 2, 3, 0) \
-    X(13, 128, 160, 2, 2, 3, 1) \
-    X(14, 256, 160, 4, 2, 3, 1) \
-    X(15, 128, 80, 4, 1, 3, 0)  \
-    X(16, 128, 80, 4, 1, 3, 1)  \
-    X(17, 256, 80, 4, 1, 3, 1)  \
-    X(18, 256, 128, 4, 2, 3, 0) \
-    X(19, 128, 128, 2, 2, 3, 1) \
-    X(20, 256, 128, 4, 2, 3, 1) \
-    X(21, 64, 160, 1, 2, 4, 0)  \
-    X(22, 128, 64, 2, 2, 4, 1)  \
-    X(23, 256, 32, 4, 1, 4, 0)  \
-    X(24, 256, 320, 2, 4, 2, 0) \
-    X(25, 128, 80, 2, 1, 3, 1)  \
-    X(26, 256, 320, 4, 4, 2, 0) \
-    X(27, 128, 160, 4, 2, 3, 1)
+// id, BM, BN, waves along M, waves along N, LDS stages, fragment prefetch, prior of the heuristic tile choice (choose_cfg,
+// mdhip_exec.cpp: from measurements on MI355X, profiles/autotune_r1.txt; tools/autotune.py refines the choice)
+#define MDHIP_CONV_CFGS(X) \
+    X(0, 256, 160, 4, 2, 2, 0, 0.92f)  \
+    X(1, 128, 160, 2, 2, 2, 0, 1.00f)  \
+    X(2, 256, 80, 4, 1, 2, 0, 0.55f)   \
+    X(3, 128, 80, 4, 1, 2, 0, 0.95f)   \
+    X(4, 256, 32, 4, 1, 2, 0, 0.45f)   \
+    X(5, 128, 64, 2, 2, 2, 0, 0.70f)   \
+    X(6, 128, 128, 2, 2, 2, 0, 0.85f)  \
+    X(7, 256, 128, 4, 2, 2, 0, 0.85f)  \
+    X(8, 128, 320, 2, 4, 2, 0, 0.95f)  \
+    X(9, 64, 160, 1, 2, 2, 0, 0.55f)   \
+    X(10, 64, 64, 1, 2, 2, 0, 0.45f)   \
+    X(11, 256, 64, 4, 1, 2, 0, 0.65f)  \
+    X(12, 256, 160, 4, 2, 3, 0, 0.95f) \
+    X(13, 128, 160, 2, 2, 3, 1, 1.00f) \
+    X(14, 256, 160, 4, 2, 3, 1, 1.00f) \
+    X(15, 128, 80, 4, 1, 3, 0, 0.95f)  \
+    X(16, 128, 80, 4, 1, 3, 1, 0.95f)  \
+    X(17, 256, 80, 4, 1, 3, 1, 0.60f)  \
+    X(18, 256, 128, 4, 2, 3, 0, 0.90f) \
+    X(19, 128, 128, 2, 2, 3, 1, 0.88f) \
+    X(20, 256, 128, 4, 2, 3, 1, 0.88f) \
+    X(21, 64, 160, 1, 2, 4, 0, 0.55f)  \
+    X(22, 128, 64, 2, 2, 4, 1, 0.70f)  \
+    X(23, 256, 32, 4, 1, 4, 0, 0.45f)  \
+    X(24, 256, 320, 2, 4, 2, 0, 0.50f) \
+    X(25, 128, 80, 2, 1, 3, 1, 0.50f)  \
+    X(26, 256, 320, 4, 4, 2, 0, 0.50f) \
+    X(27, 128, 160, 4, 2, 3, 1, 0.50f)
 
 static const ConvCfg g_cfgs[] = {
-#define X(id, bm, bn, wm, wn, ns, fp)                                                                 \
+#define X(id, bm, bn, wm, wn, ns, fp, prior)                                                          \
     {bm, bn, (wm) * (wn) * 64, (size_t)conv_lds_bytes(bm, bn, ns),                                  \
-     conv_blocks_per_cu(bm, bn, (wm) * (wn), ns), #bm "x" #bn "/" #wm "x" #wn "/s" #ns "/p" #fp},
+     conv_blocks_per_cu(bm, bn, (wm) * (wn), ns), #bm "x" #bn "/" #wm "x" #wn "/s" #ns "/p" #fp, prior},
     MDHIP_CONV_CFGS(X)
 #undef X
 };
-
-// configuration ids: [0, kNumV1) = this file's kernel, then the other families in the order of g_fams
 constexpr int kNumV1 = (int)(sizeof(g_cfgs) / sizeof(g_cfgs[0]));
-int conv_num_v1_cfgs() { return kNumV1; }
 
 namespace {
-// the first-generation configurations that exist in a decoding instantiation (DEC): the narrow tiles a 24-channel op is given
+// the configurations that exist in a decoding instantiation (DEC): the narrow tiles a 24-channel op is given
 constexpr bool v1_decodes(int bn) { return bn <= 80; }
 template <int BM, int BN, int WM, int WN, int NS, int FP>
 hipError_t v1_set_lds(int lds) {
@@ -506,126 +504,37 @@ hipError_t v1_launch(const ConvArgs& p, dim3 grid, size_t lds, hipStream_t s) {
     hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, NS, FP>), grid, dim3(WM * WN * 64), lds, s, p);
     return hipGetLastError();
 }
-bool conv2_supports_l(int cfg, const ConvArgs& a) {
-    if (conv2_cfg_is_ring(cfg) && !(conv2_is_pointwise(a) && a.k_pad >= 3 * 64)) return false;
-    return conv2_supports(a) && (a.in_up == nullptr || cfg == 0);                    // in_up: 160x160 only
-}
-// one row per kernel family after the first: local configuration ids [0, num()), developer variants
-// (tools/convbench.cpp) behind them at the negative ids  dev_base - k
-struct Family {
-    int (*num)();
-    const ConvCfg& (*cfg)(int);
-    bool (*supports)(int, const ConvArgs&);
-    hipError_t (*launch)(int, const ConvArgs&, hipStream_t);
-    hipError_t (*init)();
-    bool bitwise;        // false: equals the implicit-GEMM kernels up to fp32 summation order only (other K order)
-    int dev_base;        // developer variant k (0, 1, ...) is addressed as  dev_base - k
-    bool f8_in;          // takes e4m3 activations (and nothing else)
-    bool f8_out;         // its epilogue can write e4m3 (ConvArgs::out_f8)
-};
-const Family g_fams[] = {
-    {conv2_num_cfgs, conv2_cfg, conv2_supports_l, conv2_launch, conv2_init, true, -1, false, true},
-    // (conv_v4.cpp -- the row-patch direct convolution of round 1, conv_v5's predecessor and the origin of the (group, r, s, c)
-    // weight packing -- left the build in round 5: no table entry had selected it since round 3)
-    {conv5_num_cfgs, conv5_cfg, conv5_supports, conv5_launch, conv5_init, false, -301, false, false},
-    {conv6_num_cfgs, conv6_cfg, conv6_supports, conv6_launch, conv6_init, true, -401, false, false},     // the stem kernel: same K order
-    {conv8_num_cfgs, conv8_cfg, conv8_supports, conv8_launch, conv8_init, false, -801, true, false},
-    {conv7_num_cfgs, conv7_cfg, conv7_supports, conv7_launch, conv7_init, false, -901, false, false},    // stride-2 row runs: a K order of its own
-};
-constexpr int kNumFams = (int)(sizeof(g_fams) / sizeof(g_fams[0]));
-// family and local id of a global id >= kNumV1
-const Family* find_family(int cfg, int* local) {
-    int i = cfg - kNumV1;
-    for (int f = 0; f < kNumFams; ++f) {
-        const int n = g_fams[f].num();
-        if (i < n) { *local = i; return &g_fams[f]; }
-        i -= n;
-    }
-    return nullptr;
-}
-}  // namespace
 
-int conv_num_cfgs() {
-    int n = kNumV1;
-    for (int f = 0; f < kNumFams; ++f) n += g_fams[f].num();
-    return n;
-}
-const ConvCfg& conv_cfg(int i) {
-    if (i < kNumV1) return g_cfgs[i];
-    int l = 0;
-    const Family* f = find_family(i, &l);
-    return f ? f->cfg(l) : g_cfgs[0];
-}
-bool conv_cfg_is_bitwise_family(int cfg) {
-    if (cfg < kNumV1) return true;
-    int l = 0;
-    const Family* f = find_family(cfg, &l);
-    return f ? f->bitwise : true;
-}
+bool igemm_decodes(int cfg) { return v1_decodes(g_cfgs[cfg].bn); }
+bool igemm_supports(int, const ConvArgs&) { return true; }             // this kernel takes every 16-bit op
 
-// (a.dec_pred: the op decodes in its epilogue -- only the configurations with such an instantiation take it)
-bool conv_cfg_decodes(int cfg) {
-    if (cfg < 0 || cfg >= conv_num_cfgs()) return false;
-    if (cfg < kNumV1) return v1_decodes(g_cfgs[cfg].bn);
-    int l = 0;
-    const Family* f = find_family(cfg, &l);
-    return f == &g_fams[0] && conv2_cfg_decodes(l);
-}
-
-bool conv_supports(int cfg, const ConvArgs& a) {
-    if (cfg < 0 || cfg >= conv_num_cfgs()) return false;
-    if (a.dec_pred && !(conv_cfg_decodes(cfg) && a.out_f32 && (a.N % 8) == 0)) return false;
-    if (cfg < kNumV1) return !a.in_f8;                              // the first-generation kernel takes every 16-bit op
-    int l = 0;
-    const Family* f = find_family(cfg, &l);
-    if (!f || f->f8_in != (a.in_f8 != 0) || (a.out_f8 && !f->f8_out)) return false;
-    return f->supports(l, a);
-}
-
-hipError_t conv_init() {
+hipError_t igemm_init() {
     hipError_t e = hipSuccess;
-#define X(id, bm, bn, wm, wn, ns, fp) \
+#define X(id, bm, bn, wm, wn, ns, fp, prior) \
     if (e == hipSuccess) e = v1_set_lds<bm, bn, wm, wn, ns, fp>((int)g_cfgs[id].lds_bytes);
     MDHIP_CONV_CFGS(X)
 #undef X
-    for (int f = 0; f < kNumFams && e == hipSuccess; ++f) e = g_fams[f].init();
     return e;
 }
 
-hipError_t conv_launch(int cfg, const ConvArgs& a, hipStream_t s) {
-    // negative ids address the developer variants (tools/convbench.cpp): family f's k-th variant is dev_base - k
-    if (cfg >= conv_num_cfgs()) return hipErrorInvalidValue;
-    if (cfg < 0) {
-        for (int f = kNumFams - 1; f >= 0; --f)
-            if (cfg <= g_fams[f].dev_base) return g_fams[f].launch(g_fams[f].num() + (g_fams[f].dev_base - cfg), a, s);
-        return hipErrorInvalidValue;
-    }
-    if (cfg >= kNumV1) {
-        int l = 0;
-        const Family* f = find_family(cfg, &l);
-        if (!f || f->f8_in != (a.in_f8 != 0) || (a.out_f8 && !f->f8_out)) return hipErrorInvalidValue;
-        return f->launch(l, a, s);
-    }
-    if (a.in_f8) return hipErrorInvalidValue;
+hipError_t igemm_launch(int cfg, const ConvArgs& a, hipStream_t s) {
+    if (cfg < 0 || cfg >= kNumV1 || a.in_f8) return hipErrorInvalidValue;
     const ConvCfg& c = g_cfgs[cfg];
     ConvArgs p = a;
     conv_set_rcp(p);
-    p.tiles_n = (a.n_rows + c.bn - 1) / c.bn;
-    p.tiles_m = (a.M + c.bm - 1) / c.bm;
-    // persistent streams: about as many workgroups as fit on the chip at once (32 CUs per XCD);
-    // the load pipeline of a stream runs across its tile boundaries
-    p.tiles_per_xcd = (p.tiles_m + 7) / 8;
-    p.m_streams = std::max(1, std::min(p.tiles_per_xcd, (32 * c.blocks_per_cu) / p.tiles_n));
-    const dim3 grid((unsigned)(8 * p.tiles_n * p.m_streams));
-    if (p.dec_pred && !conv_supports(cfg, p)) return hipErrorInvalidValue;
+    const dim3 grid = conv_tile_grid(p, c);
+    if (!conv_decode_ok(igemm_decodes(cfg), p)) return hipErrorInvalidValue;
     switch (cfg) {
-#define X(id, bm, bn, wm, wn, ns, fp) \
+#define X(id, bm, bn, wm, wn, ns, fp, prior) \
     case id: return v1_launch<bm, bn, wm, wn, ns, fp>(p, grid, c.lds_bytes, s);
         MDHIP_CONV_CFGS(X)
 #undef X
     }
     return hipErrorInvalidValue;
 }
+}  // namespace
+
+MDHIP_CONV_FAMILY(conv_igemm, CONV_IGEMM, g_cfgs, kNumV1, 0, true, false, true, igemm_supports, igemm_launch, igemm_init, igemm_decodes)
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

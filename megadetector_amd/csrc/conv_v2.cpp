@@ -692,11 +692,11 @@ static const ConvCfg g_cfgs2[] = {
     MDHIP_CONV2_PROFRING(X)
 #undef X
 };
-constexpr int kNumProf = 10;   // trailing instrumented entries: reachable through conv2_launch only
+constexpr int kNumPlain2 = 0 MDHIP_CONV2_CFGS(MDHIP_COUNT_ROW);        // local ids [kNumPlain2, kNumCfgs2): the ring configurations
+constexpr int kNumCfgs2 = kNumPlain2 MDHIP_CONV2_RING(MDHIP_COUNT_ROW);
+constexpr int kNumProf = 0 MDHIP_CONV2_PROF(MDHIP_COUNT_ROW) MDHIP_CONV2_PROFRING(MDHIP_COUNT_ROW);   // trailing instrumented entries: developer variants
 
-int conv2_num_cfgs() { return (int)(sizeof(g_cfgs2) / sizeof(g_cfgs2[0])) - kNumProf; }
-const ConvCfg& conv2_cfg(int i) { return g_cfgs2[i]; }
-
+namespace {
 hipError_t conv2_init() {
     hipError_t e = hipSuccess;
 #define X(id, bm, bn, wm, wn)                                                                        \
@@ -745,32 +745,33 @@ hipError_t conv2_init() {
 }
 
 // (the configurations with a three-stage activation ring: 1x1 / stride 1 / unpadded launches only, at least three K slabs)
-bool conv2_cfg_is_ring(int cfg) { return cfg >= 9 && cfg < conv2_num_cfgs(); }
+bool conv2_cfg_is_ring(int cfg) { return cfg >= kNumPlain2 && cfg < kNumCfgs2; }
 // the configurations with a decoding instantiation (pointwise, channel count a multiple of 64): the tiles the tables give the
 // 24-channel Detect convs
 bool conv2_cfg_decodes(int cfg) { return cfg == 0 || cfg == 2 || cfg == 3 || cfg == 8; }
 bool conv2_is_pointwise(const ConvArgs& a) {
     return a.ntaps == 1 && a.stride == 1 && a.pad == 0 && a.H == a.Ho && a.W == a.Wo && a.in_up == nullptr;
 }
-bool conv2_supports(const ConvArgs& a) {
+// what every launch needs of an op (conv2_launch checks no more than this)
+bool conv2_shape_ok(const ConvArgs& a) {
     // the branch-free K walk needs at least one whole slab per tap; the epilogue stores 4 channels
-    // (in_up goes with configuration 0 only: the family table in conv_igemm.cpp checks the id)
     if (a.in_up && !(a.ntaps == 1 && a.stride == 1 && (a.H % 2) == 0 && (a.W % 2) == 0 && a.up_slabs > 0 &&
                      a.up_slabs * 8 <= a.C8 && !a.in_f8))
         return false;
     return a.C8 >= 8 && a.kw <= 3 && a.ntaps <= 9 && (a.k_pad % 64) == 0;
 }
+bool conv2_supports(int cfg, const ConvArgs& a) {
+    if (cfg < 0 || cfg >= kNumCfgs2 + kNumProf) return false;
+    if (conv2_cfg_is_ring(cfg) && !(conv2_is_pointwise(a) && a.k_pad >= 3 * 64)) return false;
+    return conv2_shape_ok(a) && (a.in_up == nullptr || cfg == 0);                   // in_up: 160x160 only
+}
 
 hipError_t conv2_launch(int cfg, const ConvArgs& a, hipStream_t s) {
-    if (cfg < 0 || cfg >= conv2_num_cfgs() + kNumProf || !conv2_supports(a)) return hipErrorInvalidValue;
+    if (cfg < 0 || cfg >= kNumCfgs2 + kNumProf || !conv2_shape_ok(a)) return hipErrorInvalidValue;
     const ConvCfg& c = g_cfgs2[cfg];
     ConvArgs p = a;
     conv_set_rcp(p);
-    p.tiles_n = (a.n_rows + c.bn - 1) / c.bn;
-    p.tiles_m = (a.M + c.bm - 1) / c.bm;
-    p.tiles_per_xcd = (p.tiles_m + 7) / 8;
-    p.m_streams = std::max(1, std::min(p.tiles_per_xcd, (32 * c.blocks_per_cu) / p.tiles_n));
-    const dim3 grid((unsigned)(8 * p.tiles_n * p.m_streams));
+    const dim3 grid = conv_tile_grid(p, c);
     if (a.in_up) {                                     // upsample read in place: configuration 0 (160x160) only
         hipLaunchKernelGGL((conv_v2_kernel<160, 160, 2, 2, 0, true>), grid, dim3(256), c.lds_bytes, s, p);
         return hipGetLastError();
@@ -822,6 +823,9 @@ hipError_t conv2_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     }
     return hipGetLastError();
 }
+}  // namespace
+
+MDHIP_CONV_FAMILY(conv_v2, CONV_V2, g_cfgs2, kNumCfgs2, kNumProf, true, false, true, conv2_supports, conv2_launch, conv2_init, conv2_cfg_decodes)
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

@@ -771,24 +771,12 @@ static const ConvCfg g_cfgs5[] = {
     MDHIP_CONV5_CFGS(X) MDHIP_CONV5_PROF(X)
 #undef X
 };
-constexpr int kNumProf5 = 19;
+constexpr int kNumMain5 = 0 MDHIP_CONV5_CFGS(MDHIP_COUNT_ROW);
+constexpr int kNumProf5 = 0 MDHIP_CONV5_PROF(MDHIP_COUNT_ROW);          // developer variants, behind the configurations
 
-// ids: [0, kNumMain5) the configurations above, then the small-launch configurations of conv_v5s.cpp and the C = 80
-// strip kernel of conv_v5c.cpp (same K order, same results), then the developer variants
-constexpr int kNumMain5 = (int)(sizeof(g_cfgs5) / sizeof(g_cfgs5[0])) - kNumProf5;
-static int first5c() { return kNumMain5 + conv5s_num_cfgs(); }
-
-int conv5_num_cfgs() { return first5c() + conv5c_num_cfgs(); }
-const ConvCfg& conv5_cfg(int i) {
-    if (i < kNumMain5) return g_cfgs5[i];
-    if (i < first5c()) return conv5s_cfg(i - kNumMain5);
-    if (i < conv5_num_cfgs()) return conv5c_cfg(i - first5c());
-    return g_cfgs5[i - conv5_num_cfgs() + kNumMain5];
-}
-
+namespace {
 hipError_t conv5_init() {
-    hipError_t e = conv5s_init();
-    if (e == hipSuccess) e = conv5c_init();
+    hipError_t e = hipSuccess;
 #define X(id, bm, bn, wm, wn, prof)                                                              \
     if (e == hipSuccess)                                                                       \
         e = hipFuncSetAttribute((const void*)conv_v5_kernel<bm, bn, wm, wn, prof>,                \
@@ -817,37 +805,24 @@ hipError_t conv5_init() {
 }
 
 bool conv5_supports(int cfg, const ConvArgs& a) {
-    if (cfg < 0 || cfg >= conv5_num_cfgs() + kNumProf5) return false;
-    const bool ok = a.wgt4 != nullptr && a.ntaps == 9 && a.kw == 3 && a.stride == 1 && a.pad == 1 && a.Ho == a.H &&
-                    a.Wo == a.W && a.C8 >= 8 && (a.N % 8) == 0 &&
-                    (long long)(2 * a.W + conv5_cfg(cfg).bm + 16) * a.ld_in * 2 + 4096 < 0x7fffffffLL;
+    if (cfg < 0 || cfg >= kNumMain5 + kNumProf5) return false;
+    const ConvCfg& c = g_cfgs5[cfg];
+    if (!conv5_shape_ok(a, c.bm)) return false;
     // the run loader addresses the whole tensor through one descriptor (dma_run_piece)
-    if (ok && (cfg < kNumMain5 || cfg >= conv5_num_cfgs()) && ((long long)a.M + 320 + 2 * a.W + 16) * a.ld_in * 2 >= 0xffffff00LL)
-        return false;
+    if (((long long)a.M + 320 + 2 * a.W + 16) * a.ld_in * 2 >= 0xffffff00LL) return false;
     // the 80x80-wave-tile configurations (LEAN; the developer variants of that tile shape too): no channel test on stores
     // or weight rows, so every channel of every N tile must exist (N a multiple of BN, not merely of 8), activated 16-bit
     // outputs, 32-channel granularity of the input
-    const int local = cfg < kNumMain5 ? cfg : (cfg >= conv5_num_cfgs() ? cfg - conv5_num_cfgs() + kNumMain5 : -1);
-    if (ok && local >= 0 && g_cfgs5[local].threads >= 512 && g_cfgs5[local].bm * g_cfgs5[local].bn == 160 * 320 &&
-        ((a.N % g_cfgs5[local].bn) != 0 || a.N != a.n_rows || !a.act || a.out_f32 || (a.C8 % 4) != 0))
+    if (c.threads >= 512 && c.bm * c.bn == 160 * 320 && ((a.N % c.bn) != 0 || a.N != a.n_rows || !a.act || a.out_f32 || (a.C8 % 4) != 0))
         return false;
-    if (ok && cfg >= kNumMain5 && cfg < first5c()) return conv5s_supports(cfg - kNumMain5, a);
-    if (ok && cfg >= first5c() && cfg < conv5_num_cfgs()) return conv5c_supports(cfg - first5c(), a);
-    return ok;
+    return true;
 }
 
 hipError_t conv5_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     if (!conv5_supports(cfg, a)) return hipErrorInvalidValue;
-    if (cfg >= kNumMain5 && cfg < first5c()) return conv5s_launch(cfg - kNumMain5, a, s);
-    if (cfg >= first5c() && cfg < conv5_num_cfgs()) return conv5c_launch(cfg - first5c(), a, s);
-    if (cfg >= conv5_num_cfgs()) cfg -= conv5_num_cfgs() - kNumMain5;        // developer variants
     const ConvCfg& c = g_cfgs5[cfg];
     ConvArgs p = a;
-    p.tiles_n = (a.n_rows + c.bn - 1) / c.bn;
-    p.tiles_m = (a.M + c.bm - 1) / c.bm;
-    p.tiles_per_xcd = (p.tiles_m + 7) / 8;
-    p.m_streams = std::max(1, std::min(p.tiles_per_xcd, (32 * c.blocks_per_cu) / p.tiles_n));
-    const dim3 grid((unsigned)(8 * p.tiles_n * p.m_streams));
+    const dim3 grid = conv_tile_grid(p, c);
     // the last channel group (see TAIL): at most half full -> its k 32..63 MFMAs are skipped; with the paired packing two taps a step
     const bool tail_short = (a.C8 & 7) != 0 && (a.C8 & 7) <= 4;
     const int tail = !tail_short ? 0 : (a.wgt4p != nullptr ? 2 : 1);
@@ -878,6 +853,9 @@ hipError_t conv5_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     }
     return hipGetLastError();
 }
+}  // namespace
+
+MDHIP_CONV_FAMILY(conv_v5, CONV_V5_RUN, g_cfgs5, kNumMain5, kNumProf5, false, false, false, conv5_supports, conv5_launch, conv5_init, nullptr)
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

@@ -851,7 +851,7 @@ conv_c80d_kernel(const ConvArgs p) {
 // latency at its occupancy, not by LDS bandwidth.)
 // ---------------------------------------------------------------------------------------
 // ---------------------------------------------------------------------------------------
-// configuration table (ids local to this file; conv_v5.cpp appends them to its own)
+// configuration table (the dev:strip entries are public configurations: they have global ids)
 // ---------------------------------------------------------------------------------------
 // id, BM (pixels of an image row per tile), pixel groups (x 5 channel fragments = waves)
 #define MDHIP_CONV5C_CFGS(X) \
@@ -872,11 +872,9 @@ static const ConvCfg g_cfgs5c[] = {
     {kD_BM, 80, 640, (size_t)kD_LDS, 1, "dev:strip64x80/2x5/r4/nb3rl3"},
     {kD_BM, 80, 640, (size_t)kD_LDS, 1, "dev:strip64x80/2x5/r4/nb4rl3"},
 };
+constexpr int kNumCfgs5c = (int)(sizeof(g_cfgs5c) / sizeof(g_cfgs5c[0]));
 
-
-int conv5c_num_cfgs() { return (int)(sizeof(g_cfgs5c) / sizeof(g_cfgs5c[0])); }
-const ConvCfg& conv5c_cfg(int i) { return g_cfgs5c[i]; }
-
+namespace {
 hipError_t conv5c_init() {
     hipError_t e = hipSuccess;
 #define X(id, bm, wm)                                                                            \
@@ -898,18 +896,19 @@ hipError_t conv5c_init() {
     return e;
 }
 
-// the caller (conv5_supports) has checked the shape conditions common to the family
 // (a.wgt_pre != nullptr: the fused bottleneck -- in and out must be different tensors, the 1x1 has 80 input channels)
 bool conv5c_supports(int cfg, const ConvArgs& a) {
+    if (cfg < 0 || cfg >= kNumCfgs5c || !conv5_shape_ok(a, g_cfgs5c[cfg].bm)) return false;
     if (a.wgt_pre != nullptr && (a.bias_pre == nullptr || a.k_pad_pre < 96 || (const void*)a.in == (const void*)a.out || a.act != 1))
         return false;
     if (cfg > kCfgR4 && (a.dbg == nullptr || a.wgt_pre == nullptr)) return false;            // developer variants
-    return cfg >= 0 && cfg < conv5c_num_cfgs() && !a.out_f32 && !a.out_f8 && !a.in_f8 && a.C8 == 10 && a.groups == 2 &&
+    return !a.out_f32 && !a.out_f8 && !a.in_f8 && a.C8 == 10 && a.groups == 2 &&
            a.N == 80 && a.n_rows == 80 && (long long)a.HoWo * a.ld_in * 2 < 0x3fffffffLL &&
            (long long)a.HoWo * a.ld_out * 2 < 0x3fffffffLL && (a.res == nullptr || (long long)a.HoWo * a.ld_res * 2 < 0x3fffffffLL);
 }
 
 hipError_t conv5c_launch(int cfg, const ConvArgs& a, hipStream_t s) {
+    if (!conv5c_supports(cfg, a)) return hipErrorInvalidValue;
     const int dev = cfg > kCfgR4 ? cfg - kCfgR4 - 1 : -1;
     if (dev >= 0) cfg = kCfgR4;
     if (cfg == kCfgR4 && !a.wgt_pre) cfg = 0;                   // (not fused: the strip kernel, same family)
@@ -965,6 +964,9 @@ hipError_t conv5c_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     }
     return hipGetLastError();
 }
+}  // namespace
+
+MDHIP_CONV_FAMILY(conv_v5c, CONV_V5_STRIP, g_cfgs5c, kNumCfgs5c, 0, false, false, false, conv5c_supports, conv5c_launch, conv5c_init, nullptr)
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

@@ -363,7 +363,7 @@ conv_v5s_kernel(const ConvArgs p) {
 }
 
 // ---------------------------------------------------------------------------------------
-// configuration table (ids local to this file; conv_v5.cpp appends them to its own)
+// configuration table
 // ---------------------------------------------------------------------------------------
 // id, BM, BN, waves along M, waves along N, run stages, fragment prefetch distance (half steps)
 #define MDHIP_CONV5S_CFGS(X)   \
@@ -378,9 +378,9 @@ static const ConvCfg g_cfgs5s[] = {
 #undef X
 };
 
-int conv5s_num_cfgs() { return (int)(sizeof(g_cfgs5s) / sizeof(g_cfgs5s[0])); }
-const ConvCfg& conv5s_cfg(int i) { return g_cfgs5s[i]; }
+constexpr int kNumCfgs5s = (int)(sizeof(g_cfgs5s) / sizeof(g_cfgs5s[0]));
 
+namespace {
 hipError_t conv5s_init() {
     hipError_t e = hipSuccess;
 #define X(id, bm, bn, wm, wn, ns, pd)                                                          \
@@ -392,19 +392,15 @@ hipError_t conv5s_init() {
     return e;
 }
 
-// the caller (conv5_supports) has checked the shape conditions common to the family
 bool conv5s_supports(int cfg, const ConvArgs& a) {
-    return cfg >= 0 && cfg < conv5s_num_cfgs() && !a.out_f32;
+    return cfg >= 0 && cfg < kNumCfgs5s && conv5_shape_ok(a, g_cfgs5s[cfg].bm) && !a.out_f32;
 }
 
 hipError_t conv5s_launch(int cfg, const ConvArgs& a, hipStream_t s) {
+    if (!conv5s_supports(cfg, a)) return hipErrorInvalidValue;
     const ConvCfg& c = g_cfgs5s[cfg];
     ConvArgs p = a;
-    p.tiles_n = (a.n_rows + c.bn - 1) / c.bn;
-    p.tiles_m = (a.M + c.bm - 1) / c.bm;
-    p.tiles_per_xcd = (p.tiles_m + 7) / 8;
-    p.m_streams = std::max(1, std::min(p.tiles_per_xcd, (32 * c.blocks_per_cu) / p.tiles_n));
-    const dim3 grid((unsigned)(8 * p.tiles_n * p.m_streams));
+    const dim3 grid = conv_tile_grid(p, c);
     switch (cfg) {
 #define X(id, bm, bn, wm, wn, ns, pd)                                                              \
     case id:                                                                                    \
@@ -415,6 +411,9 @@ hipError_t conv5s_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     }
     return hipGetLastError();
 }
+}  // namespace
+
+MDHIP_CONV_FAMILY(conv_v5s, CONV_V5_SMALL, g_cfgs5s, kNumCfgs5s, 0, false, false, false, conv5s_supports, conv5s_launch, conv5s_init, nullptr)
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

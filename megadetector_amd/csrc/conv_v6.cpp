@@ -189,11 +189,9 @@ conv_stem_kernel(const ConvArgs p) {
 // ---------------------------------------------------------------------------------------
 // configuration table: one configuration
 // ---------------------------------------------------------------------------------------
-static const ConvCfg g_cfg6 = {kBM, 80, kNW * 64, (size_t)kStemLds, 2, "stem:row128x80/4x1"};
+[[maybe_unused]] static const ConvCfg g_cfg6 = {kBM, 80, kNW * 64, (size_t)kStemLds, 2, "stem:row128x80/4x1"};
 
-int conv6_num_cfgs() { return 1; }
-const ConvCfg& conv6_cfg(int) { return g_cfg6; }
-
+namespace {
 hipError_t conv6_init() {
     return hipFuncSetAttribute((const void*)conv_stem_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kStemLds);
 }
@@ -215,6 +213,9 @@ hipError_t conv6_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(conv_stem_kernel, dim3((unsigned)(8 * slots)), dim3(kNW * 64), kStemLds, s, a);
     return hipGetLastError();
 }
+}  // namespace
+
+MDHIP_CONV_FAMILY(conv_v6, CONV_STEM, &g_cfg6, 1, 0, true, false, false, conv6_supports, conv6_launch, conv6_init, nullptr)   // same K order as the implicit GEMM
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

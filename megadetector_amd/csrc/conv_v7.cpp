@@ -498,11 +498,9 @@ conv_v7_kernel(const ConvArgs p) {
 // ---------------------------------------------------------------------------------------
 // configuration table: one configuration
 // ---------------------------------------------------------------------------------------
-static const ConvCfg g_cfg7 = {kBM7, kBN7, kNW7 * 64, (size_t)kLds7, 1, "v7:s2run320x160/4x2"};
+[[maybe_unused]] static const ConvCfg g_cfg7 = {kBM7, kBN7, kNW7 * 64, (size_t)kLds7, 1, "v7:s2run320x160/4x2"};
 
-int conv7_num_cfgs() { return 1; }
-const ConvCfg& conv7_cfg(int) { return g_cfg7; }
-
+namespace {
 hipError_t conv7_init() {
     hipError_t e = hipFuncSetAttribute((const void*)conv_v7_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds7);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv_v7_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds7);
@@ -544,6 +542,9 @@ hipError_t conv7_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     }
     return hipGetLastError();
 }
+}  // namespace
+
+MDHIP_CONV_FAMILY(conv_v7, CONV_V7, &g_cfg7, 1, 0, false, false, false, conv7_supports, conv7_launch, conv7_init, nullptr)   // a K order of its own
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

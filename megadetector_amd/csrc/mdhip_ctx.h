@@ -141,18 +141,9 @@ int num_anchors_for(const mdhip_ctx* ctx, int h, int w);
 
 // ---- mdhip_exec.cpp ----
 
-// the conv API of the context's storage type (the kernels are compiled once per type, mdhip_internal.h)
-struct ConvApi {
-    int (*num_cfgs)();
-    const ConvCfg& (*cfg)(int);
-    hipError_t (*launch)(int, const ConvArgs&, hipStream_t);
-    hipError_t (*init)();
-    bool (*supports)(int, const ConvArgs&);
-    bool (*is_bitwise_family)(int);
-    int (*num_v1_cfgs)();
-    bool (*cfg_decodes)(int);
-};
-const ConvApi& conv_api(const mdhip_ctx* ctx);
+// the conv kernel registry of the context's storage type (the kernels are compiled once per type, mdhip_internal.h)
+const ConvRegistry& conv_api(const mdhip_ctx* ctx);
+// tile configurations (count, names, families) are the same for both storage types
 int conv_num_cfgs();
 const ConvCfg& conv_cfg(int i);
 bool conv_cfg_is_bitwise_family(int c);

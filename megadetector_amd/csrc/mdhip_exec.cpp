@@ -11,33 +11,23 @@
 
 namespace mdhip {
 
-// the conv API of the context's storage type (the kernels are compiled once per type, mdhip_internal.h)
-const ConvApi g_conv_bf16 = {st_bf16::conv_num_cfgs, st_bf16::conv_cfg, st_bf16::conv_launch, st_bf16::conv_init,
-                             st_bf16::conv_supports, st_bf16::conv_cfg_is_bitwise_family, st_bf16::conv_num_v1_cfgs, st_bf16::conv_cfg_decodes};
-const ConvApi g_conv_f16 = {st_f16::conv_num_cfgs, st_f16::conv_cfg, st_f16::conv_launch, st_f16::conv_init,
-                            st_f16::conv_supports, st_f16::conv_cfg_is_bitwise_family, st_f16::conv_num_v1_cfgs, st_f16::conv_cfg_decodes};
-const ConvApi& conv_api(const mdhip_ctx* ctx) { return ctx->dtype == MDHIP_DTYPE_FP16 ? g_conv_f16 : g_conv_bf16; }
-// tile configurations (count, names, families) are the same for both storage types
-int conv_num_cfgs() { return g_conv_bf16.num_cfgs(); }
-const ConvCfg& conv_cfg(int i) { return g_conv_bf16.cfg(i); }
-bool conv_cfg_is_bitwise_family(int c) { return g_conv_bf16.is_bitwise_family(c); }
-inline int conv_num_v1_cfgs() { return g_conv_bf16.num_v1_cfgs(); }
+const ConvRegistry& conv_api(const mdhip_ctx* ctx) { return ctx->dtype == MDHIP_DTYPE_FP16 ? st_f16::conv_registry : st_bf16::conv_registry; }
+int conv_num_cfgs() { return st_bf16::conv_registry.num_cfgs(); }
+const ConvCfg& conv_cfg(int i) { return st_bf16::conv_registry.cfg(i); }
+bool conv_cfg_is_bitwise_family(int c) { return st_bf16::conv_registry.is_bitwise_family(c); }
 
-// heuristic tile choice; measured overrides arrive through mdhip_set_op_cfg
+// heuristic tile choice over the first-generation configurations (each with its measured prior, conv_igemm.cpp); measured
+// overrides arrive through mdhip_set_op_cfg
 int choose_cfg(int M, int n_rows) {
-    // prior from measurements on MI355X (profiles/autotune_r1.txt); tools/autotune.py refines it
-    static const float quality[] = {0.92f, 1.00f, 0.55f, 0.95f, 0.45f, 0.70f, 0.85f, 0.85f, 0.95f, 0.55f, 0.45f, 0.65f,
-                                    0.95f, 1.00f, 1.00f, 0.95f, 0.95f, 0.60f, 0.90f, 0.88f, 0.88f, 0.55f, 0.70f, 0.45f,
-                                    0.50f, 0.50f, 0.50f, 0.50f};
-    static_assert(sizeof(quality) / sizeof(quality[0]) == 28, "one prior per tile configuration");
+    const ConvFamily& v1 = *st_bf16::conv_registry.fam[CONV_IGEMM];
     int best = 0;
     float best_score = -1.f;
-    for (int i = 0; i < conv_num_v1_cfgs(); ++i) {
-        const ConvCfg& c = conv_cfg(i);
+    for (int i = 0; i < v1.n_cfgs; ++i) {
+        const ConvCfg& c = v1.cfgs[i];
         const int tn = (n_rows + c.bn - 1) / c.bn, tm = (M + c.bm - 1) / c.bm;
         const float useful = ((float)n_rows / (tn * c.bn)) * ((float)M / ((float)tm * c.bm));
         const float fill = std::min(1.0f, (float)tm * tn / 512.0f);
-        const float score = useful * (0.35f + 0.65f * fill) * quality[i];
+        const float score = useful * (0.35f + 0.65f * fill) * c.prior;
         if (score > best_score) { best_score = score; best = i; }
     }
     return best;
@@ -209,10 +199,10 @@ void fused_args(const mdhip_ctx* ctx, const Op& op, const Op& pre, ConvArgs& a) 
 }
 
 // `op` resolves (with its plain arguments `a`) to a tile of the kernel family `family`, and that tile takes the arguments `with`
-bool resolves_to(const mdhip_ctx* ctx, const Op& op, const ConvArgs& a, int n, const char* family, const ConvArgs& with) {
+bool resolves_to(const mdhip_ctx* ctx, const Op& op, const ConvArgs& a, int n, ConvFamilyId family, const ConvArgs& with) {
     bool from_table = false;
     const int cfg = pick_cfg(ctx, op, a, n, &from_table);
-    return strncmp(conv_cfg(cfg).name, family, strlen(family)) == 0 && conv_api(ctx).supports(cfg, with);
+    return conv_api(ctx).family(cfg) == family && conv_api(ctx).supports(cfg, with);
 }
 
 bool group_is_fused(const mdhip_ctx* ctx, const std::vector<int>& group, int n, int h, int w) {
@@ -221,7 +211,7 @@ bool group_is_fused(const mdhip_ctx* ctx, const std::vector<int>& group, int n, 
         conv_args(ctx, ctx->ops[oi], n, h, w, a);
         ConvArgs f = a;
         fused_args(ctx, ctx->ops[oi], ctx->ops[oi - 1], f);
-        if (!resolves_to(ctx, ctx->ops[oi], a, n, "v5:strip", f)) return false;
+        if (!resolves_to(ctx, ctx->ops[oi], a, n, CONV_V5_STRIP, f)) return false;
     }
     return true;
 }
@@ -234,7 +224,7 @@ bool absorb_upsample(const mdhip_ctx* ctx, const Op& conv, int n, ConvArgs& a) {
     b.in_up = (const uint16_t*)(ctx->arena + up.in.off);
     b.ld_up = up.in.ld;
     b.up_slabs = up.in.c / 64;
-    if (up.in.c % 64 || !resolves_to(ctx, conv, a, n, "v2:", b)) return false;
+    if (up.in.c % 64 || !resolves_to(ctx, conv, a, n, CONV_V2, b)) return false;
     a = b;
     return true;
 }
@@ -261,7 +251,7 @@ void resolve_decode(const mdhip_ctx* ctx, Resolved& r, size_t conv) {
     Launch& L = r.ops[conv];
     const Op& dec = ctx->ops[conv + 1];
     L.decodes = ctx->fuse_decode && !ctx->fuse_suspended && ctx->no == 8 && plain_pass(ctx->cur_tta) && !ctx->calibrating &&
-                conv_api(ctx).cfg_decodes(L.cfg) && (L.cfg < conv_num_v1_cfgs() || (L.a.C8 & 7) == 0);
+                conv_api(ctx).cfg_decodes(L.cfg) && (conv_api(ctx).family(L.cfg) == CONV_IGEMM || (L.a.C8 & 7) == 0);
     L.a.dec_anchors = (const float*)(ctx->warena + ctx->anchors_off) + dec.level * ctx->na * 2;
     L.a.dec_stride = ctx->strides[dec.level];
     L.a.dec_level_off = level_offset(ctx, dec.level, r.h, r.w, ctx->na);

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 struct MdClassifyCrop;             // resample.h: the record of a crop of mdhip_classifier_input
 
 struct MdjImage;
@@ -155,7 +157,7 @@ struct ConvArgs {
     int stride, pad;
     int act;                // 1 = SiLU
     int out_f32;            // 1 = fp32 output, no rounding (Detect logits)
-    int tiles_n, tiles_m, tiles_per_xcd, m_streams;   // filled by conv_launch
+    int tiles_n, tiles_m, tiles_per_xcd, m_streams;   // filled by the launch function of the kernel family
     // second packing (introduced by the row-patch kernel of round 1; read by conv_v5 / conv_v5s / conv_v5c / conv_v7 / conv_f8): weights packed [n_rows][groups*9*64], k = (cg, r, s, c % 64)
     const uint16_t* wgt4;   // nullptr when the op has no such packing
     int k_pad4, groups;
@@ -196,7 +198,7 @@ struct ConvArgs {
     int dec_level_off, dec_n_anchors;
     // floor(2^32 / HoWo), floor(2^32 / Wo) (0xffffffff for a divisor of 1): the tile set-up of the implicit-GEMM kernels
     // splits an output pixel index into (image, row, column) with conv_udiv() instead of two run-time integer
-    // divisions per row; filled by conv_launch / conv2_launch (conv_set_rcp), callers leave them alone
+    // divisions per row; filled by the launch functions that need them (conv_set_rcp), callers leave them alone
     unsigned rcp_howo, rcp_wo;
 };
 inline unsigned conv_rcp32(int d) { return d <= 1 ? 0xffffffffu : (unsigned)(0x100000000ull / (unsigned)d); }
@@ -270,74 +272,136 @@ struct ConvCfg {
     size_t lds_bytes;
     int blocks_per_cu;      // residency the kernel is compiled for (LDS- and wave-limited)
     const char* name;
+    float prior;            // first-generation tiles: the heuristic's measured prior (choose_cfg, mdhip_exec.cpp); else unused
 };
 
-// The conv API exists once per storage type (see MDHIP_ST above):
-//   conv_*  : dispatch over all kernels (conv_igemm.cpp); ids [0, conv_num_v1_cfgs()) run conv_igemm.cpp's
-//             kernel (every shape), then conv_v2.cpp's, conv_v5.cpp's, conv_v6.cpp's
-//   conv2_* : second-generation main loop (conv_v2.cpp); local ids, reached through conv_launch
-//   conv5_* : 3x3 / stride 1 with row-segment reuse across the taps of a kernel row (conv_v5.cpp); its configurations
-//             for small launches (conv5s_*, conv_v5s.cpp) are listed behind its own
-//   conv6_* : the stem (3x3 over 16-channel space-to-depth pixels, N = 80) with its weights in registers (conv_v6.cpp)
-//   conv8_* : conv_v5's structure on e4m3 operands with the block-scaled K = 128 MFMA (conv_f8.cpp)
-//   conv7_* : 3x3 / STRIDE 2 with row-run reuse (odd / even input columns in two sub-buffers; conv_v7.cpp); listed last
-// conv_launch returns hipSuccess or the launch error; conv_init raises the dynamic-LDS limits (one-off);
-// conv_cfg_is_bitwise_family is false for kernels whose result equals the others' up to fp32 summation
-// order only.
-#define MDHIP_CONV_API \
-    int conv_num_cfgs(); \
-    const ConvCfg& conv_cfg(int i); \
-    hipError_t conv_launch(int cfg, const ConvArgs& a, hipStream_t s); \
-    hipError_t conv_init(); \
-    bool conv_supports(int cfg, const ConvArgs& a); \
-    bool conv_cfg_is_bitwise_family(int cfg); \
-    bool conv_cfg_decodes(int cfg); \
-    bool conv2_cfg_decodes(int cfg); \
-    int conv_num_v1_cfgs(); \
-    int conv2_num_cfgs(); \
-    const ConvCfg& conv2_cfg(int i); \
-    bool conv2_supports(const ConvArgs& a); \
-    bool conv2_cfg_is_ring(int cfg); \
-    bool conv2_is_pointwise(const ConvArgs& a); \
-    hipError_t conv2_launch(int cfg, const ConvArgs& a, hipStream_t s); \
-    hipError_t conv2_init(); \
-    int conv5_num_cfgs(); \
-    const ConvCfg& conv5_cfg(int i); \
-    bool conv5_supports(int cfg, const ConvArgs& a); \
-    hipError_t conv5_launch(int cfg, const ConvArgs& a, hipStream_t s); \
-    hipError_t conv5_init(); \
-    int conv5s_num_cfgs(); \
-    const ConvCfg& conv5s_cfg(int i); \
-    bool conv5s_supports(int cfg, const ConvArgs& a); \
-    hipError_t conv5s_launch(int cfg, const ConvArgs& a, hipStream_t s); \
-    hipError_t conv5s_init(); \
-    int conv5c_num_cfgs(); \
-    const ConvCfg& conv5c_cfg(int i); \
-    bool conv5c_supports(int cfg, const ConvArgs& a); \
-    hipError_t conv5c_launch(int cfg, const ConvArgs& a, hipStream_t s); \
-    hipError_t conv5c_init(); \
-    int conv6_num_cfgs(); \
-    const ConvCfg& conv6_cfg(int i); \
-    bool conv6_supports(int cfg, const ConvArgs& a); \
-    hipError_t conv6_launch(int cfg, const ConvArgs& a, hipStream_t s); \
-    hipError_t conv6_init(); \
-    int conv8_num_cfgs(); \
-    const ConvCfg& conv8_cfg(int i); \
-    bool conv8_supports(int cfg, const ConvArgs& a); \
-    hipError_t conv8_launch(int cfg, const ConvArgs& a, hipStream_t s); \
-    hipError_t conv8_init(); \
-    int conv7_num_cfgs(); \
-    const ConvCfg& conv7_cfg(int i); \
-    bool conv7_supports(int cfg, const ConvArgs& a); \
-    hipError_t conv7_launch(int cfg, const ConvArgs& a, hipStream_t s); \
-    hipError_t conv7_init();
+// rows of a configuration list (an X-macro):  constexpr int n = 0 LIST(MDHIP_COUNT_ROW);
+#define MDHIP_COUNT_ROW(...) +1
+
+// the tile grid of the persistent kernels (conv_igemm / conv_v2 / conv_v5 / conv_v5s / conv_f8): about as many workgroups as
+// fit on the chip at once (8 XCDs of 32 CUs), each a stream of M tiles whose load pipeline runs across its tile boundaries
+inline dim3 conv_tile_grid(ConvArgs& p, const ConvCfg& c) {
+    p.tiles_n = (p.n_rows + c.bn - 1) / c.bn;
+    p.tiles_m = (p.M + c.bm - 1) / c.bm;
+    p.tiles_per_xcd = (p.tiles_m + 7) / 8;
+    p.m_streams = std::max(1, std::min(p.tiles_per_xcd, (32 * c.blocks_per_cu) / p.tiles_n));
+    return dim3((unsigned)(8 * p.tiles_n * p.m_streams));
+}
+
+// A kernel family: what one conv translation unit exports, once per storage type (see MDHIP_ST above) and nothing else.
+// A configuration is addressed by its family and a local id; the registry below numbers them globally, in this order:
+//   CONV_IGEMM    : the first-generation implicit-GEMM kernel, every 16-bit shape (conv_igemm.cpp)
+//   CONV_V2       : second-generation main loop; 1x1 configurations with an activation ring, upsample read in place, Detect
+//                   decode in the epilogue (conv_v2.cpp)
+//   CONV_V5_RUN   : 3x3 / stride 1 with row-segment reuse across the taps of a kernel row (conv_v5.cpp; its predecessor
+//                   conv_v4.cpp, the row-patch direct convolution of round 1 and the origin of the (group, r, s, c) weight
+//                   packing, left the build in round 5: no table entry had selected it since round 3)
+//   CONV_V5_SMALL : the same for small launches (conv_v5s.cpp)
+//   CONV_V5_STRIP : the same for 80 channels, alone or fused with the 1x1 in front (conv_v5c.cpp)
+//   CONV_STEM     : the stem (3x3 over 16-channel space-to-depth pixels, N = 80) with its weights in registers (conv_v6.cpp)
+//   CONV_F8       : conv_v5's structure on e4m3 operands with the block-scaled K = 128 MFMA (conv_f8.cpp)
+//   CONV_V7       : 3x3 / STRIDE 2 with row-run reuse (odd / even input columns in two sub-buffers; conv_v7.cpp)
+enum ConvFamilyId { CONV_IGEMM = 0, CONV_V2, CONV_V5_RUN, CONV_V5_SMALL, CONV_V5_STRIP, CONV_STEM, CONV_F8, CONV_V7, CONV_NUM_FAMILIES };
+struct ConvFamily {
+    ConvFamilyId id;
+    const ConvCfg* cfgs;    // n_cfgs public configurations, then n_dev developer variants (tools/convbench.cpp: launch_dev)
+    int n_cfgs, n_dev;
+    bool bitwise;           // false: equals the implicit-GEMM kernels up to fp32 summation order only (other K order)
+    bool f8_in;             // takes e4m3 activations (and nothing else)
+    bool f8_out;            // its epilogue can write e4m3 (ConvArgs::out_f8)
+    bool (*supports)(int local, const ConvArgs& a);
+    hipError_t (*launch)(int local, const ConvArgs& a, hipStream_t s);   // hipSuccess or the launch error
+    hipError_t (*init)();                                                // raises the dynamic-LDS limits (one-off)
+    bool (*decodes)(int local);   // the configuration has an instantiation that decodes in its epilogue; nullptr: none has
+};
+// MDHIP_CONV_FAMILY(name, id, cfgs, n_cfgs, n_dev, bitwise, f8_in, f8_out, supports, launch, init, decodes) defines a translation
+// unit's family object.  It is host data: the device pass must not emit a copy into the code object
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MDHIP_CONV_FAMILY(name, ...)
+#else
+#define MDHIP_CONV_FAMILY(name, ...) extern const ConvFamily name = {__VA_ARGS__};
+#endif
+inline bool conv_family_takes(const ConvFamily& f, const ConvArgs& a) { return f.f8_in == (a.in_f8 != 0) && (!a.out_f8 || f.f8_out); }
+// (a.dec_pred: the op decodes in its epilogue -- only the configurations with such an instantiation take it)
+inline bool conv_decode_ok(bool cfg_decodes, const ConvArgs& a) { return !a.dec_pred || (cfg_decodes && a.out_f32 && (a.N % 8) == 0); }
+// what conv_v5.cpp, conv_v5s.cpp and conv_v5c.cpp all need of an op: 3x3 / stride 1 / pad 1 on the (group, r, s, c) packing,
+// the rows a tile of bm pixels touches inside the 31-bit offset range
+inline bool conv5_shape_ok(const ConvArgs& a, int bm) {
+    return a.wgt4 != nullptr && a.ntaps == 9 && a.kw == 3 && a.stride == 1 && a.pad == 1 && a.Ho == a.H && a.Wo == a.W && a.C8 >= 8 &&
+           (a.N % 8) == 0 && (long long)(2 * a.W + bm + 16) * a.ld_in * 2 + 4096 < 0x7fffffffLL;
+}
+
+// The registry: the families in id order.  Global configuration ids count through their public configurations in that order
+// (tuned tables and mdhip_set_op_cfg name them); developer variants have no global id.
+struct ConvRegistry {
+    const ConvFamily* fam[CONV_NUM_FAMILIES];
+
+    int num_cfgs() const {
+        int n = 0;
+        for (const ConvFamily* f : fam) n += f->n_cfgs;
+        return n;
+    }
+    // family and local id of a global id; nullptr outside [0, num_cfgs())
+    const ConvFamily* find(int cfg, int* local) const {
+        if (cfg < 0) return nullptr;
+        for (const ConvFamily* f : fam) {
+            if (cfg < f->n_cfgs) { *local = cfg; return f; }
+            cfg -= f->n_cfgs;
+        }
+        return nullptr;
+    }
+    ConvFamilyId family(int cfg) const {
+        int l = 0;
+        const ConvFamily* f = find(cfg, &l);
+        return f ? f->id : CONV_NUM_FAMILIES;
+    }
+    const ConvCfg& cfg(int i) const {
+        int l = 0;
+        const ConvFamily* f = find(i, &l);
+        return f ? f->cfgs[l] : fam[0]->cfgs[0];
+    }
+    const ConvCfg& dev_cfg(ConvFamilyId family, int k) const { return fam[family]->cfgs[fam[family]->n_cfgs + k]; }
+    bool is_bitwise_family(int cfg) const {
+        int l = 0;
+        const ConvFamily* f = find(cfg, &l);
+        return f ? f->bitwise : true;
+    }
+    bool cfg_decodes(int cfg) const {
+        int l = 0;
+        const ConvFamily* f = find(cfg, &l);
+        return f && f->decodes && f->decodes(l);
+    }
+    bool supports(int cfg, const ConvArgs& a) const {
+        int l = 0;
+        const ConvFamily* f = find(cfg, &l);
+        return f && conv_decode_ok(f->decodes && f->decodes(l), a) && conv_family_takes(*f, a) && f->supports(l, a);
+    }
+    hipError_t launch(int cfg, const ConvArgs& a, hipStream_t s) const {
+        int l = 0;
+        const ConvFamily* f = find(cfg, &l);
+        return f && conv_family_takes(*f, a) ? f->launch(l, a, s) : hipErrorInvalidValue;
+    }
+    // developer variant k of a family (tools/convbench.cpp)
+    hipError_t launch_dev(ConvFamilyId family, int k, const ConvArgs& a, hipStream_t s) const {
+        const ConvFamily* f = fam[family];
+        return k >= 0 && k < f->n_dev ? f->launch(f->n_cfgs + k, a, s) : hipErrorInvalidValue;
+    }
+    hipError_t init() const {
+        hipError_t e = hipSuccess;
+        for (const ConvFamily* f : fam)
+            if (e == hipSuccess) e = f->init();
+        return e;
+    }
+};
+#define MDHIP_CONV_FAMILIES extern const ConvFamily conv_igemm, conv_v2, conv_v5, conv_v5s, conv_v5c, conv_v6, conv_f8, conv_v7; \
+                            extern const ConvRegistry conv_registry;   /* conv_registry.cpp */
 namespace st_bf16 {
-MDHIP_CONV_API
+MDHIP_CONV_FAMILIES
 }
 namespace st_f16 {
-MDHIP_CONV_API
+MDHIP_CONV_FAMILIES
 }
-#undef MDHIP_CONV_API
+#undef MDHIP_CONV_FAMILIES
 
 // ---------------------------------------------------------------------------------------
 // memory-bound helpers (misc_kernels.cpp)

@@ -165,3 +165,14 @@ def test_shipped_tile_tables_name_configurations_of_this_build(table):
     assert not mixed, mixed
     strip = [e for e in entries if e['n'] == 80 and e['k'] == 720 and e['ntaps'] == 9 and e['has_res'] == 1 and e.get('batch') == 32]
     assert strip and all(e['name'].startswith('v5:strip') for e in strip), strip
+
+
+def test_configuration_ids_names_and_families_are_pinned():
+    """every configuration id keeps its name and its bitwise-family flag (tests/golden/conv_cfgs.json: [id, name, bitwise] of all
+    67): tuned tables, mdhip_set_op_cfg callers and recorded profiles name configurations by these ids"""
+    import json
+    from megadetector_amd import _lib
+    lib = _lib.load()
+    want = json.load(open(os.path.join(REPO, 'tests', 'golden', 'conv_cfgs.json')))
+    got = [[i, lib.mdhip_conv_cfg_name(i).decode(), int(lib.mdhip_cfg_is_bitwise(i))] for i in range(lib.mdhip_num_conv_cfgs())]
+    assert got == want

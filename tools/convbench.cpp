@@ -20,7 +20,25 @@
 #include "../megadetector_amd/csrc/mdhip_internal.h"
 
 using namespace mdhip;
-using namespace mdhip::st_bf16;
+static const ConvRegistry& R = st_bf16::conv_registry;
+
+// a configuration to run: global id `cfg` (fam = CONV_NUM_FAMILIES), or developer variant `cfg` of family `fam` (argument
+// <letter><k>).  `label`: the number the output shows for it -- the id; for a developer variant  base - k, as every recorded
+// profile has it
+struct Run { int cfg; ConvFamilyId fam; int label; };
+static const struct { char letter; ConvFamilyId fam; int base; } kDev[] = {
+    {'p', CONV_V2, -1},        // p0, p1: instrumented v2 variants
+    {'t', CONV_V5_RUN, -301},  // t0..: v5 developer variants
+    {'f', CONV_F8, -801},      // f0..: fp8 developer variants
+};
+static Run run_of(const char* arg) {
+    for (const auto& d : kDev)
+        if (arg[0] == d.letter) return {atoi(arg + 1), d.fam, d.base - atoi(arg + 1)};
+    return {atoi(arg), CONV_NUM_FAMILIES, atoi(arg)};
+}
+static hipError_t launch(const Run& r, const ConvArgs& a) {
+    return r.fam != CONV_NUM_FAMILIES ? R.launch_dev(r.fam, r.cfg, a, 0) : R.launch(r.cfg, a, 0);
+}
 
 #define CK(x)                                                                         \
     do {                                                                              \
@@ -141,20 +159,16 @@ int main(int argc, char** argv) {
     Shape sh_b;                                                   // CONVBENCH_B=<n>: the same layer at another batch
     if (const char* eb = getenv("CONVBENCH_B")) { sh_b = *sh; sh_b.b = atoi(eb); sh = &sh_b; }
     const int iters = atoi(argv[2]);
-    std::vector<int> cfgs;
+    std::vector<Run> cfgs;
     for (int i = 3; i < argc; ++i) {
-        if (!strcmp(argv[i], "all")) { for (int j = 0; j < conv_num_cfgs(); ++j) cfgs.push_back(j); continue; }
-        if (argv[i][0] == 'p') { cfgs.push_back(-1 - atoi(argv[i] + 1)); continue; }   // p0, p1: instrumented v2 variants
-        if (argv[i][0] == 't') { cfgs.push_back(-301 - atoi(argv[i] + 1)); continue; } // t0..: v5 developer variants
-        if (argv[i][0] == 'u') { cfgs.push_back(-401 - atoi(argv[i] + 1)); continue; } // u0..: v6 developer variants
-        if (argv[i][0] == 'f') { cfgs.push_back(-801 - atoi(argv[i] + 1)); continue; } // f0..: fp8 developer variants
+        if (!strcmp(argv[i], "all")) { for (int j = 0; j < R.num_cfgs(); ++j) cfgs.push_back({j, CONV_NUM_FAMILIES, j}); continue; }
         if (argv[i][0] == 'n') {                                                        // n<prefix>: every configuration whose name starts with prefix
-            for (int j = 0; j < conv_num_cfgs(); ++j) if (!strncmp(conv_cfg(j).name, argv[i] + 1, strlen(argv[i] + 1))) cfgs.push_back(j);
+            for (int j = 0; j < R.num_cfgs(); ++j) if (!strncmp(R.cfg(j).name, argv[i] + 1, strlen(argv[i] + 1))) cfgs.push_back({j, CONV_NUM_FAMILIES, j});
             continue;
         }
-        cfgs.push_back(atoi(argv[i]));
+        cfgs.push_back(run_of(argv[i]));
     }
-    CK(conv_init());
+    CK(R.init());
     const int pad = sh->k / 2;
     const int Ho = sh->h / sh->s, Wo = sh->w / sh->s;
     const long long M = (long long)sh->b * Ho * Wo;
@@ -337,13 +351,17 @@ int main(int argc, char** argv) {
     ConvArgs af8 = a;
     af8.in = (const uint16_t*)d_in8; af8.in_f8 = 1; af8.wgt8 = d_w8; af8.scale = d_scale; af8.k_pad8 = k_pad8; af8.groups8 = groups8;
     af8.C8 = (sh->cin + 15) / 16; af8.wgt4 = nullptr; af8.wgt4p = nullptr;
-    for (int cfg : cfgs) {
-        const bool is_f8 = cfg <= -801 || (cfg >= 0 && !strncmp(conv_cfg(cfg).name, "f8:", 3));
+    for (const Run& run : cfgs) {
+        const int cfg = run.label;
+        const bool dev = run.fam != CONV_NUM_FAMILIES;
+        const ConvFamilyId fam = dev ? run.fam : R.family(run.cfg);
+        const char* name = !dev ? R.cfg(run.cfg).name : (run.cfg >= 0 && run.cfg < R.fam[fam]->n_dev) ? R.dev_cfg(fam, run.cfg).name : "";
+        const bool is_f8 = fam == CONV_F8;
         if (is_f8 && !want_f8) { printf("  cfg %2d: no fp8 form of this shape\n", cfg); continue; }
         a = is_f8 ? af8 : a16;
         const std::vector<uint16_t>& h_ref = is_f8 ? h_ref8 : h_ref16;
         CK(hipMemset(d_out, 0xff, out_elems * 2));
-        hipError_t e = conv_launch(cfg, a, 0);
+        hipError_t e = launch(run, a);
         if (e != hipSuccess) { printf("  cfg %2d launch failed: %s\n", cfg, hipGetErrorString(e)); (void)hipGetLastError(); continue; }
         CK(hipDeviceSynchronize());
         CK(hipMemcpy(h_out.data(), d_out, out_elems * 2, hipMemcpyDeviceToHost));
@@ -360,7 +378,7 @@ int main(int argc, char** argv) {
         const int reps = 3;
         for (int r = 0; r < reps; ++r) {
             CK(hipEventRecord(e0, 0));
-            for (int i = 0; i < iters; ++i) (void)conv_launch(cfg, a, 0);
+            for (int i = 0; i < iters; ++i) (void)launch(run, a);
             CK(hipEventRecord(e1, 0));
             CK(hipEventSynchronize(e1));
             float ms;
@@ -370,9 +388,9 @@ int main(int argc, char** argv) {
             if (ms < best) best = ms;
         }
         printf("  cfg %2d %-22s %8.4f ms (best %8.4f)  %7.1f TF/s   max|err| %.3g (max|ref| %.3g) bad %zu%s\n", cfg,
-               cfg <= -801 ? conv8_cfg(conv8_num_cfgs() - 801 - cfg).name : cfg <= -401 ? conv6_cfg(conv6_num_cfgs() - 401 - cfg).name : cfg <= -301 ? conv5_cfg(conv5_num_cfgs() - 301 - cfg).name : cfg < 0 ? conv2_cfg(conv2_num_cfgs() - 1 - cfg).name : conv_cfg(cfg).name, tot / reps, best, flops / (tot / reps * 1e-3) / 1e12, max_err, max_ref, bad,
+               name, tot / reps, best, flops / (tot / reps * 1e-3) / 1e12, max_err, max_ref, bad,
                bad ? "  <-- MISMATCH" : "");
-        if (cfg >= 0 && !strncmp(conv_cfg(cfg).name, "dev:strip", 9)) {
+        if (!dev && !strncmp(name, "dev:strip", 9)) {
             // the stamped four-row fused bottleneck: cycles per tile and wave by phase
             std::vector<unsigned long long> h(dbg_words);
             CK(hipMemcpy(h.data(), d_dbg, dbg_words * 8, hipMemcpyDeviceToHost));
@@ -409,7 +427,7 @@ int main(int argc, char** argv) {
             for (int k = 0; k < 6; ++k) printf("      %-36s %8.1f  (%4.1f%%)\n", nm[k], sum[k] / std::max(1.0, tiles), 100 * sum[k] / std::max(1.0, tot));
             CK(hipMemset(d_dbg, 0, dbg_words * 8));
         }
-        if (cfg < 0) {
+        if (dev) {
             // per-wave phase sums of the last launch: cycles per step, averaged over all waves that ran
             std::vector<unsigned long long> h(dbg_words);
             CK(hipMemcpy(h.data(), d_dbg, dbg_words * 8, hipMemcpyDeviceToHost));
@@ -438,7 +456,7 @@ int main(int argc, char** argv) {
                                          "first step after an epilogue: wait + barrier", "epilogue (amortised)"};
             static const char* nm_epi[6] = {"epilogue pixel row 0", "epilogue pixel row 1", "epilogue pixel row 2", "epilogue pixel row 3",
                                             "epilogue pixel row 4", "everything else (main loop, waits, barriers)"};
-            const char* cname = cfg <= -301 && cfg > -401 ? conv5_cfg(conv5_num_cfgs() - 301 - cfg).name : "";
+            const char* cname = fam == CONV_V5_RUN ? name : "";
             const int prof_bits = strrchr(cname, '/') ? atoi(strrchr(cname, '/') + 1) : 0;
             const char* const* nm = (prof_bits & 128) ? nm_epi : nm5;
             double tot = 0;
