@@ -265,6 +265,61 @@ def jfif_file(width, height, quality, scan_bytes):
     return b''.join((front, sof, back, bytes(scan_bytes), b'\xff\xd9'))
 
 
+def with_standard_tables(data):
+    """
+    The file for an abbreviated stream: Motion-JPEG frames usually carry no DHT segment, because the standard's example
+    tables are implied.  Returns `data` itself when every Huffman table its first scan header names is defined in front of
+    that header; otherwise bytes with ONE DHT segment inserted in front of SOS that defines the named tables which are
+    missing -- id 0: the standard's luminance pair, id 1: its chrominance pair (the tables jfif_file writes).  This is
+    libjpeg's rule, hence Pillow's (jinit_huff_decoder fills each of DC 0, AC 0, DC 1, AC 1 that is not defined, one by
+    one, and nothing else): a scan that names a missing table 2 or 3, and bytes whose segments cannot be walked up to a
+    scan header, come back unchanged and stay refused by everything that refused them.
+    """
+    buf = data if isinstance(data, bytes) else data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
+    n = len(buf)
+    if n < 4 or buf[0] != 0xFF or buf[1] != 0xD8:
+        return data
+    defined, p = set(), 2
+    while True:
+        if p + 4 > n or buf[p] != 0xFF:
+            return data
+        m = buf[p + 1]
+        if m == 0xFF:                                   # fill byte
+            p += 1
+            continue
+        if m == 0x01 or 0xD0 <= m <= 0xD8:              # TEM, RSTn, SOI: no length
+            p += 2
+            continue
+        if m == 0xD9:
+            return data
+        ln = (buf[p + 2] << 8) | buf[p + 3]
+        if ln < 2 or p + 2 + ln > n:
+            return data
+        if m == 0xC4:
+            q, end = p + 4, p + 2 + ln
+            while q + 17 <= end:
+                defined.add(buf[q])
+                q += 17 + sum(buf[q + 1:q + 17])
+            if q != end:
+                return data
+        elif m == 0xDA:
+            ns = buf[p + 4] if ln >= 3 else 0
+            if not 1 <= ns <= 4 or ln < 6 + 2 * ns:
+                return data
+            named = set()
+            for k in range(ns):
+                sel = buf[p + 6 + 2 * k]
+                named.update((sel >> 4, 0x10 | (sel & 15)))
+            missing = named - defined
+            if not missing:
+                return data
+            if any((t & 15) > 1 for t in missing):
+                return data
+            dht = b''.join(bytes((tc_th,)) + bytes(counts) + bytes(vals) for tc_th, counts, vals in _STD_HUFFMAN if tc_th in missing)
+            return buf[:p] + _segment(0xC4, dht) + buf[p:]
+        p += 2 + ln
+
+
 def encode_bound(width, height):
     """bytes the scan of a width x height crop can take at the very most (mdjpeg_encode_bound)"""
     return int(load().mdjpeg_encode_bound(int(width), int(height)))

@@ -15,11 +15,18 @@ are the reference's.
 Decoding is behind a small frame-source interface (`frame_rate`, `n_frames`, iteration over RGB HxWx3
 uint8 frames in order): `OpenCVFrameSource` is the reference's decoder (cv2.VideoCapture + BGR->RGB)
 and needs `opencv-python`, which this image does not have; `ArrayFrameSource` serves in-memory frames
-(tests, or frames decoded elsewhere).
+(tests, or frames decoded elsewhere); `MJPEGAVIFrameSource` reads Motion-JPEG AVI files with this package's own container
+reader (avi.py) and hands each sampled frame's JPEG to the device's decoder (`mjpeg='gpu'`) or to Pillow (`mjpeg='host'`).
+A source may yield lazy frame handles (objects with `materialise()`): only a frame that is sampled is materialised.
+
+Command line: python -m megadetector_amd.process_video MODEL INPUT [options]; see main().
 """
 
+import functools
+import io
 import os
 import re
+import sys
 
 import numpy as np
 
@@ -94,6 +101,84 @@ class OpenCVFrameSource:
             self.cap.release()
         except Exception:
             pass
+
+
+class LazyFrame:
+    """a frame that is read and decoded only when the driver samples it (run_detector_on_frames calls materialise())"""
+
+    def __init__(self, source, index):
+        self.source, self.index = source, index
+
+    def materialise(self):
+        return self.source.frame(self.index)
+
+
+class MJPEGAVIFrameSource:
+    """
+    A Motion-JPEG AVI file (avi.AviFile: every frame is a complete baseline JPEG, found by walking the chunk headers).
+    Iteration yields LazyFrame handles in frame order; `frames_read` counts the chunks that were read from the file, which
+    in a sampled run are the sampled frames only.  A frame is pinned to Pillow's decode of its stored JPEG on both legs:
+
+    device=True   the chunk, with the standard's Huffman tables written in where the frame leaves them implied
+                  (jpeg_host.with_standard_tables), becomes a jpeg_host.ScanImage: HIPDetector.decode_scans Huffman-decodes
+                  a batch of them in one launch grid and mdhip_jpeg_reconstruct makes the pixels, on the device.  A frame
+                  mdjpeg_scan does not take (progressive, another sampling, ...) becomes the RGB array feed.load_image
+                  gives for the same bytes.  Needs a detector with decode_scans (HIPDetector).
+    device=False  every frame is decoded by feed.load_image on the host; works with any detector object.
+
+    On either leg a frame Pillow cannot decode becomes a jpeg_host.ScanFailure, which the detector turns into a failure
+    record for that frame: the video goes on.  Raises avi.AviError for a file that is not an MJPG AVI.
+    """
+
+    def __init__(self, path, device=True):
+        from . import avi
+        self.avi = avi.AviFile(path)
+        self.device = bool(device)
+        self.frame_rate = float(self.avi.frame_rate)
+        self.n_frames = self.avi.n_frames
+        self.frames_read = 0
+
+    def __iter__(self):
+        return (LazyFrame(self, i) for i in range(self.n_frames))
+
+    def frame(self, i):
+        from . import feed, jpeg_host
+        data = jpeg_host.with_standard_tables(self.avi.read_frame(i))
+        self.frames_read += 1
+        try:
+            if self.device:
+                # the header half of load_image: its mode check and the EXIF rotation it would apply; no pixel is decoded
+                image, rotation = feed.open_for_coefficients(io.BytesIO(data))
+                if image.format == 'JPEG':
+                    rc, scan_image, _ = jpeg_host.ScanImage.from_bytes(data, rotation)
+                    if rc == jpeg_host.MDJPEG_OK:
+                        return scan_image
+            return np.asarray(feed.load_image(io.BytesIO(data)))
+        except Exception as e:
+            return jpeg_host.ScanFailure(e)
+
+    def close(self):
+        self.avi.close()
+
+
+def open_video_source(path, mjpeg='off'):
+    """The frame source of a video file.  mjpeg 'host' / 'gpu': a file that is an AVI with an MJPG stream is read by
+    MJPEGAVIFrameSource (a damaged one fails as that video's failure); every other file, and every file with 'off', goes to
+    OpenCVFrameSource.  A top-level function, so that functools.partial(open_video_source, mjpeg=...) can be pickled for
+    the shard processes of n_gpus > 1."""
+    if mjpeg != 'off':
+        from .avi import AviError
+        try:
+            return MJPEGAVIFrameSource(path, device=(mjpeg == 'gpu'))
+        except AviError as e:
+            if e.mjpeg:
+                raise
+        except OSError:
+            pass                          # OpenCVFrameSource reports a file that cannot be opened in its own words
+    return OpenCVFrameSource(path)
+
+
+MJPEG_MODES = ('off', 'host', 'gpu')
 
 
 def find_videos(folder, recursive=True):
@@ -178,7 +263,7 @@ def run_detector_on_frames(detector, source, every_n_frames=None, frames_to_proc
                 continue
         name = frame_number_to_filename(frame_number)
         frame_filenames.append(name)
-        frames.append(np.ascontiguousarray(image))
+        frames.append(image.materialise() if hasattr(image, 'materialise') else np.ascontiguousarray(image))
         ids.append(name)
         if len(frames) >= batch_size:
             flush(frames, ids)
@@ -341,13 +426,21 @@ def run_detector_on_videos_sharded(model_file, videos, n_gpus, detector_options=
 def process_videos(model_file, input_video_file, output_json_file=None, frame_sample=None, time_sample=None,
                    json_confidence_threshold=DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD, image_size=None, recursive=True,
                    batch_size=8, detector_options=None, detector=None, exit_on_empty_video=False, verbose=False,
-                   n_gpus=1, videos=None, open_source=None, shard_worker=None):
+                   n_gpus=1, videos=None, open_source=None, shard_worker=None, mjpeg='off'):
     """
     reference process_video.py:123-272 (the options that touch this path).  n_gpus > 1 (BASELINE.json configs[3],
     reference notebooks/manage_video_batch.py:51-67,201-218 does it out of process): the video list is sharded over
     the GPUs of the node, the per-video JSON is the one-process one.  `videos` ([(relative name, source argument)]) and
     `open_source` replace the folder scan and the cv2 decoder (tests, frames decoded elsewhere).
+    mjpeg: 'off' | 'host' | 'gpu' (open_video_source): with 'host' or 'gpu' Motion-JPEG AVI files are read without cv2, and
+    with 'gpu' their sampled frames are decoded on the device -- the same pixels, hence the same JSON.
     """
+    if mjpeg not in MJPEG_MODES:
+        raise ValueError('mjpeg must be one of {}, got {!r}'.format(MJPEG_MODES, mjpeg))
+    if mjpeg != 'off' and open_source is not None:
+        raise ValueError('mjpeg= chooses the frame source: it cannot be combined with open_source')
+    if mjpeg == 'gpu' and detector is not None and not hasattr(detector, 'decode_scans'):
+        raise ValueError("mjpeg='gpu' needs a detector that decodes JPEG scans on the device (HIPDetector.decode_scans)")
     if frame_sample is not None and time_sample is not None:
         raise ValueError('frame_sample and time_sample are mutually exclusive')
     if output_json_file is None:
@@ -370,6 +463,8 @@ def process_videos(model_file, input_video_file, output_json_file=None, frame_sa
             videos = [(os.path.relpath(f, folder).replace('\\', '/'), f) for f in find_videos(folder, recursive=recursive)]
     run_kwargs = dict(every_n_frames=every, batch_size=batch_size, detection_threshold=json_confidence_threshold,
                       image_size=image_size, error_on_empty_video=exit_on_empty_video, verbose=verbose)
+    if mjpeg != 'off':
+        open_source = functools.partial(open_video_source, mjpeg=mjpeg)
     if open_source is not None:
         run_kwargs['open_source'] = open_source
     if n_gpus > 1 and len(videos) > 1:
@@ -387,3 +482,50 @@ def process_videos(model_file, input_video_file, output_json_file=None, frame_sa
     images = video_results_to_md_format(md)
     run_detector_batch.write_results_to_file(images, output_json_file, relative_path_base=None, detector_file=model_file)
     return images
+
+
+# --------------------------------------------------------------------------------------------
+# command line (reference process_video.py:375-480, the arguments this path implements)
+# --------------------------------------------------------------------------------------------
+def main(argv=None, detector=None):
+    """python -m megadetector_amd.process_video MODEL INPUT ...; `detector` replaces the model file's detector (tests)"""
+    import argparse
+    ap = argparse.ArgumentParser(description='Run MegaDetector on the sampled frames of a video file or a folder of videos')
+    ap.add_argument('model_file', type=str, help='MegaDetector model file or model name')
+    ap.add_argument('input_video_file', type=str, help='video file (or folder) to process')
+    ap.add_argument('--recursive', action='store_true', help='recurse into [input_video_file] if it is a folder')
+    ap.add_argument('--output_json_file', type=str, default=None, help='.json output file, defaults to [video file].json')
+    ap.add_argument('--json_confidence_threshold', type=float, default=DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD,
+                    help="don't include boxes in the .json file with confidence below this threshold (default {})".format(
+                        DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD))
+    ap.add_argument('--frame_sample', type=int, default=None,
+                    help='process every Nth frame (defaults to every frame), mutually exclusive with --time_sample')
+    ap.add_argument('--time_sample', type=float, default=None,
+                    help='process frames every N seconds (converted to a frame interval), mutually exclusive with --frame_sample')
+    ap.add_argument('--image_size', type=int, default=None, help='force image resizing to this size on the long axis')
+    ap.add_argument('--exit_on_empty_video', action='store_true',
+                    help='halt on a video with no retrievable frames instead of storing it as a failure')
+    ap.add_argument('--verbose', action='store_true', help='enable additional debug output')
+    ap.add_argument('--detector_options', nargs='*', metavar='KEY=VALUE', default='',
+                    help='detector-specific options, as a space-separated list of key-value pairs')
+    ap.add_argument('--batch_size', type=int, default=8, help='sampled frames per detector batch (default 8)')
+    ap.add_argument('--n_gpus', type=int, default=1, help='shard the video list over this many GPUs')
+    ap.add_argument('--mjpeg', choices=MJPEG_MODES, default='off',
+                    help="read Motion-JPEG AVI files without OpenCV: 'host' decodes their frames with Pillow, 'gpu' on the "
+                         "device (same pixels); every other file goes to OpenCV as with 'off' (default)")
+    args = ap.parse_args(argv)
+    if args.frame_sample is not None and args.time_sample is not None:
+        ap.error('--frame_sample and --time_sample are mutually exclusive')
+    if not os.path.exists(args.input_video_file):
+        ap.error('{} does not exist'.format(args.input_video_file))
+    process_videos(args.model_file, args.input_video_file, output_json_file=args.output_json_file,
+                   frame_sample=args.frame_sample, time_sample=args.time_sample,
+                   json_confidence_threshold=args.json_confidence_threshold, image_size=args.image_size,
+                   recursive=args.recursive, batch_size=args.batch_size,
+                   detector_options=run_detector_batch.parse_kvp_list(args.detector_options), detector=detector,
+                   exit_on_empty_video=args.exit_on_empty_video, verbose=args.verbose, n_gpus=args.n_gpus, mjpeg=args.mjpeg)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
