@@ -13,7 +13,7 @@
  * Conventions: plain pointers and sizes only; every function returns 0 on success or a
  * negative MDHIP_E* code, never throws, never exits.  mdhip_last_error() returns a
  * human-readable message for the most recent failure on that context (or, with ctx == NULL,
- * the most recent mdhip_create failure on the calling thread).  A context is bound to one GPU
+ * the most recent failure of mdhip_create or of a context-free call on the calling thread).  A context is bound to one GPU
  * and is not thread-safe; use one context per (process, GPU).  The library owns all device
  * buffers and packed weights; the caller owns every pointer it passes in.
  */
@@ -34,7 +34,7 @@ extern "C" {
 #define MDHIP_EHIP         -2   /* a HIP runtime call failed                     */
 #define MDHIP_ENOMEM       -3   /* device arena too small for the request        */
 #define MDHIP_EUNSUPPORTED -4   /* valid request this build does not implement   */
-#define MDHIP_ECAPACITY    -5   /* mdhip_jpeg_encode: the output buffer is too small */
+#define MDHIP_ECAPACITY    -5   /* mdhip_jpeg_encode, mdhip_repeat_detections: the output buffer is too small */
 
 /* arithmetic type of the conv stack */
 #define MDHIP_DTYPE_BF16 0
@@ -393,6 +393,43 @@ typedef struct {
 } mdhip_classifier_crop;
 int mdhip_classifier_input(mdhip_ctx* ctx, const mdhip_classifier_crop* crops, int n, int size, int filter, const float mean[3],
                            const float std[3], float* out, void* hip_stream);
+
+/* Repeat-detection elimination (the reference: postprocessing/repeat_detection_elimination/repeat_detections_core.py
+ * _find_matches_in_directory and the "Mark suspicious locations" block of find_repeat_detections): which detections of a camera
+ * sit where the same camera was boxed again and again.  CONTEXT-FREE: marking a results file needs no model, so the call takes
+ * a device index, not a context; its errors are in mdhip_last_error(NULL).
+ *   boxes, n     HOST: the detections that take part, of ALL locations, in processing order (images in file order, detections
+ *                in list order); `group` is the index of the location, non-decreasing.  0 <= n <= 2^30
+ * Boxes are taken in order.  A box MATCHES a candidate of its group when the categories are equal (or category_agnostic is
+ * set) and ct_utils.get_iou(box, candidate) >= iou_threshold -- in doubles, operation for operation, the division included
+ * (csrc/rde_match.h, shared with the host model mdjpeg_repeat_detections).  It becomes an instance of EVERY candidate it
+ * matches; when it matches none it opens a new candidate whose first instance is itself.  Only boxes that matched nothing are
+ * ever candidates.  A box get_iou raises for (x + w <= x or y + h <= y, or a NaN) matches nothing and nothing matches it.
+ * A candidate with at least occurrence_threshold instances is suspicious.
+ *   is_candidate[i]   HOST, n: 1 when box i opened a candidate
+ *   n_instances[i]    HOST, n: the instances of the candidate box i opened (itself included), 0 for any other box
+ *   pairs, capacity   HOST, capacity x 2: the instance lists of the suspicious candidates, one behind the other, each entry
+ *                     (instance, candidate) as indices into boxes; sorted by candidate, then by instance -- the order of the
+ *                     reference's lists.  May be NULL when capacity is 0
+ *   needed            HOST: the entries this call needs
+ *   chunk             boxes resolved per step, 1 .. 16384; 0 = 1024.  No result depends on it (tests put chunk edges into small
+ *                     inputs with it)
+ * MDHIP_ECAPACITY when *needed > capacity: is_candidate, n_instances and *needed are valid, nothing is written to pairs, and
+ * the same call with room for *needed entries succeeds -- so a caller retries once.  MDHIP_EINVAL for n < 0, a group that
+ * decreases, a NaN threshold, a chunk or a device outside its range; MDHIP_EHIP "no HIP device" where there is none.
+ * Candidates are resolved chunk by chunk in stream order -- per chunk: its rows against the candidates so far, its rows
+ * against each other (64-bit match words), one wave that walks them in order -- with no host synchronisation between chunks;
+ * then the instances are counted, and written by rank.  The n x n matches are never stored: device memory is
+ * O(n + chunk^2 / 8 + pairs), allocated by the call and released before it returns.  The call returns when the results are
+ * in host memory. */
+typedef mdjpeg_rde_box mdhip_rde_box;      /* { double x, y, w, h; int32_t group, category; } */
+int mdhip_repeat_detections(int device, const mdhip_rde_box* boxes, int64_t n, double iou_threshold, int category_agnostic,
+                            int32_t occurrence_threshold, int32_t chunk, uint8_t* is_candidate, int32_t* n_instances,
+                            int64_t* pairs, int64_t capacity, int64_t* needed);
+/* device time of this thread's last mdhip_repeat_detections, from events on its stream, in milliseconds: ms[0] resolving the
+ * candidates (all chunks), ms[1] counting the instances, ms[2] writing the pairs (0 when none were written); uploads and
+ * read-backs are in none of them (tools/rde_bench.py) */
+int mdhip_repeat_detections_times(float ms[3]);
 
 /* Test-time augmentation: replaces mdhip_forward for `model(batch, augment=True)` (reference
  * pytorch_detector.py:1313 -> yolov5 _forward_augment): three passes over the batch that mdhip_preprocess

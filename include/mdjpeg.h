@@ -149,6 +149,22 @@ int mdjpeg_classifier_input(const uint8_t* src, int64_t pitch, int32_t src_w, in
                             int32_t off_x, int32_t off_y, int32_t size, int32_t filter, const float mean[3], const float std[3], float* out);
 int mdjpeg_classifier_plan(int32_t canvas_w, int32_t canvas_h, int32_t size, int32_t filter, int32_t lds_bytes, int32_t plan[2]);
 
+/* ---- repeat-detection elimination (GPU: mdhip_repeat_detections, include/mdhip.h) --------------------------------------- */
+/* The host model of the GPU call, compiled from the header the kernels are compiled from (csrc/rde_match.h): a plain
+ * sequential restatement of the reference's rule (repeat_detections_core.py _find_matches_in_directory) -- a box is appended
+ * to every earlier candidate of its group that it matches, and opens a new candidate when it matches none.  Arguments and
+ * results are those of mdhip_repeat_detections without `device`; `chunk` is checked (>= 0) and otherwise has no meaning here.
+ * MDJPEG_EINVAL for n < 0, a decreasing group, a NaN threshold, a negative chunk or capacity; MDJPEG_ECAPACITY when
+ * *needed > capacity: is_candidate, n_instances and *needed are valid and `pairs` is untouched. */
+typedef struct {
+    double  x, y, w, h;      /* the detection's bbox as the results file has it                       */
+    int32_t group;           /* index of its location; non-decreasing along the array                 */
+    int32_t category;
+} mdjpeg_rde_box;
+int mdjpeg_repeat_detections(const mdjpeg_rde_box* boxes, int64_t n, double iou_threshold, int category_agnostic,
+                             int32_t occurrence_threshold, int32_t chunk, uint8_t* is_candidate, int32_t* n_instances,
+                             int64_t* pairs, int64_t capacity, int64_t* needed);
+
 const char* mdjpeg_version(void);
 
 #ifdef __cplusplus

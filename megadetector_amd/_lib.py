@@ -62,6 +62,11 @@ class mdhip_classifier_crop(C.Structure):
                 ('canvas_w', C.c_int32), ('canvas_h', C.c_int32), ('off_x', C.c_int32), ('off_y', C.c_int32)]
 
 
+class mdhip_rde_box(C.Structure):
+    _fields_ = [('x', C.c_double), ('y', C.c_double), ('w', C.c_double), ('h', C.c_double),
+                ('group', C.c_int32), ('category', C.c_int32)]
+
+
 class mdhip_op_info(C.Structure):
     _fields_ = [('name', C.c_char * 48), ('kind', C.c_int32), ('layer', C.c_int32),
                 ('m', C.c_int32), ('n', C.c_int32), ('k', C.c_int32),
@@ -101,6 +106,9 @@ SYMBOLS = {
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, _P, C.c_int64, _P]),
     'mdhip_classifier_input': (C.c_int, [_P, C.POINTER(mdhip_classifier_crop), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
                                          C.POINTER(C.c_float), _P, _P]),
+    'mdhip_repeat_detections': (C.c_int, [C.c_int, _P, C.c_int64, C.c_double, C.c_int, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64,
+                                          C.POINTER(C.c_int64)]),
+    'mdhip_repeat_detections_times': (C.c_int, [C.POINTER(C.c_float)]),
     'mdhip_forward_tta': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_last_num_anchors': (C.c_int, [_P]),
     'mdhip_calibrate': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),

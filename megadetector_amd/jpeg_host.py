@@ -60,6 +60,8 @@ SYMBOLS = {
     'mdjpeg_classifier_input': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p]),
     'mdjpeg_classifier_plan': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    'mdjpeg_repeat_detections': (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     'mdjpeg_version': (C.c_char_p, []),
 }
 

@@ -1196,8 +1196,19 @@ def main(argv=None):
                     help='give every crop the JPEG file round trip of the reference (75 there) on the GPU; default: the source pixels')
     ap.add_argument('--classification_results_file', type=str, default=None, metavar='F',
                     help='the results with classifications; default <output>.classified.json')
+    ap.add_argument('--rde_results_file', type=str, default=None, metavar='F',
+                    help='after the run, mark the repeat detections of the results (repeat_detections.find_repeat_detections: a box a '
+                         'camera was given --rde_occurrence_threshold times gets a negative confidence) and write them to F and '
+                         'F.rde_index.json; the output file and the checkpoints are what they are without it')
+    ap.add_argument('--rde_occurrence_threshold', type=int, default=None, help='default 20, as the reference')
+    ap.add_argument('--rde_iou_threshold', type=float, default=None, help='default 0.9, as the reference')
+    ap.add_argument('--rde_backend', type=str, default=None, choices=('gpu', 'host'),
+                    help="default gpu; 'host': the host model of the kernels")
     ap.add_argument('--verbose', action='store_true')
     args = ap.parse_args(argv)
+    if args.rde_results_file is None:
+        assert args.rde_occurrence_threshold is None and args.rde_iou_threshold is None and args.rde_backend is None, \
+            '--rde_occurrence_threshold / --rde_iou_threshold / --rde_backend need --rde_results_file'
     classify_sub = {k: getattr(args, k) for k in ('classifier_categories', 'classifier_image_size', 'classifier_interpolation',
                                                   'classify_confidence_threshold', 'classify_categories', 'classification_threshold',
                                                   'classifier_batch_size', 'classifier_jpeg_quality', 'classification_results_file')}
@@ -1320,6 +1331,16 @@ def main(argv=None):
                                  args.classification_results_file or os.path.splitext(args.output_file)[0] + '.classified.json', base)
         print('Classified {} detections ({} skipped)'.format(last_classify_counts['gpu'] + last_classify_counts['host'],
                                                              last_classify_counts['skipped']))
+    if args.rde_results_file is not None:
+        from megadetector_amd import repeat_detections as rde_mod
+        rde_options = rde_mod.RepeatDetectionOptions()
+        if args.rde_occurrence_threshold is not None:
+            rde_options.occurrenceThreshold = args.rde_occurrence_threshold
+        if args.rde_iou_threshold is not None:
+            rde_options.iouThreshold = args.rde_iou_threshold
+        marked = rde_mod.mark_repeat_detections(copy.deepcopy(final_output), rde_options, backend=args.rde_backend or 'gpu')
+        rde_mod.write_outputs(marked, rde_options, args.rde_results_file)
+        print('Marked {} repeat detections; results saved at {}'.format(marked.n_bbox_changes, args.rde_results_file))
     for cp in [checkpoint_path] + [shard_checkpoint_path(checkpoint_path, g) for g in range(max(1, args.n_gpus))]:
         if cp and os.path.isfile(cp):
             os.remove(cp)
