@@ -159,6 +159,13 @@ typedef struct mdhip_ctx mdhip_ctx;
  * max_batch images of max_h x max_w letterboxed pixels on GPU `device`. */
 int mdhip_create(const mdhip_model* model, int device, int dtype,
                  int max_batch, int max_h, int max_w, mdhip_ctx** out);
+/* A context WITHOUT a model, for work that only touches images (marking a results file and writing its review folder load no
+ * detector): every image entry point works on it -- mdhip_jpeg_*, mdhip_blur_regions, mdhip_resample_lanczos, mdhip_draw_ops,
+ * mdhip_classifier_input, mdhip_thumbnails -- and every entry point that needs the plan or the weights (mdhip_preprocess*,
+ * the forwards, mdhip_nms*, mdhip_read_*, mdhip_calibrate and the fp8 calls, the op / cfg / tuned / fuse / option / graph /
+ * timing calls, the mdhip_*_on kernel hooks) returns MDHIP_EINVAL with a text in mdhip_last_error.  It owns nothing on the
+ * device until a call needs scratch.  mdhip_destroy frees it. */
+int mdhip_create_images(int device, mdhip_ctx** out);
 void mdhip_destroy(mdhip_ctx* ctx);
 const char* mdhip_last_error(mdhip_ctx* ctx);
 
@@ -393,6 +400,39 @@ typedef struct {
 } mdhip_classifier_crop;
 int mdhip_classifier_input(mdhip_ctx* ctx, const mdhip_classifier_crop* crops, int n, int size, int filter, const float mean[3],
                            const float std[3], float* out, void* hip_stream);
+
+/* Thumbnails: n tiles go from images in device memory to their places in sheets in device memory, in ONE launch (the
+ * reference: visualization_utils.render_images_with_thumbnails, which for every tile opens a file, crops, resizes and
+ * pastes -- the grid of a sample of the repeat-detection review folder).  Tile i is, bit for bit, what Pillow gives for
+ * image.crop(box).resize((out_w, out_h), filter) followed by sheet.paste(tile, (x, y)): the crop is a CANVAS as for
+ * mdhip_classifier_input (the rectangle src_w x src_h at (off_x, off_y) holds image pixels, the rest is 0, as Image.crop fills
+ * where the box leaves the image), the canvas is resized to out_w x out_h with Pillow's arithmetic (the horizontal pass
+ * first, weights normalised and rounded to 22 bits, 32-bit sums clipped to 8 bits behind each pass, an axis whose size stays
+ * is not resampled, a tile whose size stays is a copy), and its bytes are stored R G B interleaved at dst, dst_pitch bytes a
+ * row.  The canvas is never built: a tap outside the rectangle contributes 0, but bounds and weights are the canvas's
+ * (csrc/resample.h, shared with the host model mdjpeg_thumbnails).
+ *   tiles, n     n records (HOST memory), 0 .. 65535; the pixels they name are DEVICE memory
+ *   filter       0 bicubic (Image.resize's default for RGB), 1 bilinear, 2 LANCZOS
+ * Only the 3 * out_w bytes of each of a tile's out_h rows are written; no source is changed.  The tiles of one call must not
+ * overlap each other or a source (the caller's guarantee).
+ * MDHIP_EINVAL, with nothing enqueued, for a host or NULL pixel pointer, a rectangle that leaves its canvas, a canvas or
+ * output size outside 1 .. 65535, a dst_pitch below 3 * out_w or an unknown filter.  MDHIP_EUNSUPPORTED, with nothing
+ * enqueued, when the canvas rows one output row needs do not fit on chip even for a single column (a canvas reduced more than
+ * about 2700 times with bicubic); the caller makes that tile on the host.  The call only enqueues.  Scratch -- the records
+ * and the coefficient tables -- belongs to the context (it shares mdhip_classifier_input's) and grows on demand (the device is
+ * synchronised when it does): keep these calls of one context on ONE stream. */
+typedef struct {
+    const uint8_t* src;          /* DEVICE: first image pixel that lies in the canvas           */
+    int64_t  pitch;              /* bytes a row of the image (>= 3 * src_w, any value)          */
+    int32_t  src_w, src_h;       /* the part of the canvas that holds image pixels; either 0:   */
+                                 /* none (a box wholly outside its image), src is not read      */
+    int32_t  canvas_w, canvas_h; /* 1 .. 65535                                                  */
+    int32_t  off_x, off_y;       /* where that part lies in the canvas; the rest of it is 0     */
+    int32_t  out_w, out_h;       /* the tile, 1 .. 65535                                        */
+    uint8_t* dst;                /* DEVICE: the tile's first pixel in its sheet                 */
+    int64_t  dst_pitch;          /* bytes a row of the sheet (>= 3 * out_w)                     */
+} mdhip_thumbnail;
+int mdhip_thumbnails(mdhip_ctx* ctx, const mdhip_thumbnail* tiles, int n, int filter, void* hip_stream);
 
 /* Repeat-detection elimination (the reference: postprocessing/repeat_detection_elimination/repeat_detections_core.py
  * _find_matches_in_directory and the "Mark suspicious locations" block of find_repeat_detections): which detections of a camera

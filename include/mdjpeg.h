@@ -149,6 +149,27 @@ int mdjpeg_classifier_input(const uint8_t* src, int64_t pitch, int32_t src_w, in
                             int32_t off_x, int32_t off_y, int32_t size, int32_t filter, const float mean[3], const float std[3], float* out);
 int mdjpeg_classifier_plan(int32_t canvas_w, int32_t canvas_h, int32_t size, int32_t filter, int32_t lds_bytes, int32_t plan[2]);
 
+/* ---- thumbnails (GPU: mdhip_thumbnails, include/mdhip.h) ---------------------------------------------------------------- */
+/* The host model of the GPU call, compiled from the header the kernel is compiled from (csrc/resample.h), and of the same
+ * record with every pointer in HOST memory: tile i is Pillow's image.crop(box).resize((out_w, out_h), filter) -- the box as a
+ * canvas_w x canvas_h canvas whose rectangle src_w x src_h at (off_x, off_y) holds the pixels at `src` and is 0 elsewhere --
+ * written R G B interleaved at dst, dst_pitch bytes a row, bit for bit; only the 3 * out_w bytes of its out_h rows are
+ * written.  src_w or src_h of 0: the canvas holds no image pixel and src is not read.  filter: 0 bicubic, 1 bilinear,
+ * 2 LANCZOS.  MDJPEG_EINVAL for a NULL pointer, a rectangle that leaves its canvas,
+ * a size outside 1 .. 65535, a pitch below its row or an unknown filter, MDJPEG_EUNSUPPORTED for the sizes the GPU call
+ * refuses; nothing is written in either case. */
+typedef struct {
+    const uint8_t* src;
+    int64_t  pitch;
+    int32_t  src_w, src_h;
+    int32_t  canvas_w, canvas_h;
+    int32_t  off_x, off_y;
+    int32_t  out_w, out_h;
+    uint8_t* dst;
+    int64_t  dst_pitch;
+} mdjpeg_thumbnail;
+int mdjpeg_thumbnails(const mdjpeg_thumbnail* tiles, int n, int32_t filter);
+
 /* ---- repeat-detection elimination (GPU: mdhip_repeat_detections, include/mdhip.h) --------------------------------------- */
 /* The host model of the GPU call, compiled from the header the kernels are compiled from (csrc/rde_match.h): a plain
  * sequential restatement of the reference's rule (repeat_detections_core.py _find_matches_in_directory) -- a box is appended

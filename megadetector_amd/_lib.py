@@ -62,6 +62,12 @@ class mdhip_classifier_crop(C.Structure):
                 ('canvas_w', C.c_int32), ('canvas_h', C.c_int32), ('off_x', C.c_int32), ('off_y', C.c_int32)]
 
 
+class mdhip_thumbnail(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('pitch', C.c_int64), ('src_w', C.c_int32), ('src_h', C.c_int32),
+                ('canvas_w', C.c_int32), ('canvas_h', C.c_int32), ('off_x', C.c_int32), ('off_y', C.c_int32),
+                ('out_w', C.c_int32), ('out_h', C.c_int32), ('dst', C.c_void_p), ('dst_pitch', C.c_int64)]
+
+
 class mdhip_rde_box(C.Structure):
     _fields_ = [('x', C.c_double), ('y', C.c_double), ('w', C.c_double), ('h', C.c_double),
                 ('group', C.c_int32), ('category', C.c_int32)]
@@ -83,6 +89,7 @@ class mdhip_tuned(C.Structure):
 _P = C.c_void_p
 SYMBOLS = {
     'mdhip_create': (C.c_int, [C.POINTER(mdhip_model), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    'mdhip_create_images': (C.c_int, [C.c_int, C.POINTER(_P)]),
     'mdhip_destroy': (None, [_P]),
     'mdhip_last_error': (C.c_char_p, [_P]),
     'mdhip_preprocess': (C.c_int, [_P, C.POINTER(_P), C.POINTER(mdhip_letterbox), C.c_int, C.c_int, C.c_int, _P]),
@@ -106,6 +113,7 @@ SYMBOLS = {
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, _P, C.c_int64, _P]),
     'mdhip_classifier_input': (C.c_int, [_P, C.POINTER(mdhip_classifier_crop), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
                                          C.POINTER(C.c_float), _P, _P]),
+    'mdhip_thumbnails': (C.c_int, [_P, C.POINTER(mdhip_thumbnail), C.c_int, C.c_int, _P]),
     'mdhip_repeat_detections': (C.c_int, [C.c_int, _P, C.c_int64, C.c_double, C.c_int, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64,
                                           C.POINTER(C.c_int64)]),
     'mdhip_repeat_detections_times': (C.c_int, [C.POINTER(C.c_float)]),

@@ -831,26 +831,49 @@ int mdjpeg_classifier_input(const uint8_t* src, int64_t pitch, int32_t src_w, in
     d.src = src, d.pitch = pitch, d.src_w = src_w, d.src_h = src_h, d.off_x = off_x, d.off_y = off_y;
     std::vector<float> lut(3 * 256);
     md_classify_lut(mean, std, lut.data());
+    std::vector<uint8_t> tile;
     for (int g = 0; g < d.row_tiles; ++g)
-        for (int k = 0; k < d.strips; ++k) {
-            const int x0 = k * d.strip, nx = std::min(d.strip, size - x0);
-            const int r0 = g * d.rows, nr = std::min(d.rows, size - r0);
-            const int tile_pitch = nx * 3;
-            int first, count;
-            md_classify_rows(d, table.data(), r0, r0 + nr, &first, &count);
-            if (int64_t(count) * tile_pitch > MD_CLASSIFY_LDS_BYTES) return MDJPEG_EINVAL;
-            std::vector<uint8_t> tile(size_t(count) * tile_pitch);       // (exact: the sanitizers see an access outside it)
-            for (int i = 0; i < count * tile_pitch; ++i) {
-                const int j = i / tile_pitch, b = i - j * tile_pitch;
-                tile[size_t(i)] = md_classify_hsample(d, table.data(), first + j, x0 + b / 3, b % 3);
-            }
-            for (int i = 0; i < 3 * nr * nx; ++i) {
-                const int q = i / nx, px = i - q * nx;
-                const int c = q / nr, y = r0 + (q - c * nr);
-                const uint8_t v = md_classify_vsample(d, table.data(), tile.data(), tile_pitch, first, y, px * 3 + c);
-                out[(size_t(c) * size + y) * size + x0 + px] = lut[size_t(c) * 256 + v];
-            }
-        }
+        for (int k = 0; k < d.strips; ++k)
+            if (!md_classify_run_tile(d, table.data(), k, g, MD_CLASSIFY_LDS_BYTES, tile, [&](int x, int y, int c, uint8_t v) {
+                    out[(size_t(c) * size + y) * size + x] = lut[size_t(c) * 256 + v];
+                }))
+                return MDJPEG_EINVAL;
+    return MDJPEG_OK;
+}
+
+// The host model of mdhip_thumbnails: every tile is checked and planned before any is made, then made workgroup by workgroup
+// with the statements the lanes run; the bytes go interleaved to their place in the sheet.
+int mdjpeg_thumbnails(const mdjpeg_thumbnail* tiles, int n, int32_t filter) {
+    if (n == 0) return MDJPEG_OK;
+    if (!tiles || n < 0 || n > 65535 || filter < MD_FILTER_BICUBIC || filter > MD_FILTER_LANCZOS) return MDJPEG_EINVAL;
+    std::vector<MdClassifyCrop> recs((size_t)n);
+    std::vector<std::vector<int32_t>> tables((size_t)n);
+    std::vector<double> work;
+    for (int i = 0; i < n; ++i) {
+        const mdjpeg_thumbnail& q = tiles[i];
+        const bool empty = (q.src_w == 0 && q.src_h >= 0) || (q.src_h == 0 && q.src_w >= 0);      // no image pixel in the canvas: src is not read
+        if (!q.dst || q.canvas_w < 1 || q.canvas_h < 1 || q.canvas_w > 65535 || q.canvas_h > 65535 ||
+            (!empty && (!q.src || q.src_w < 1 || q.src_h < 1 || q.pitch < int64_t(q.src_w) * 3 || q.off_x < 0 || q.off_y < 0 ||
+                        q.off_x > q.canvas_w - q.src_w || q.off_y > q.canvas_h - q.src_h)) ||
+            q.out_w < 1 || q.out_h < 1 || q.out_w > 65535 || q.out_h > 65535 || q.dst_pitch < int64_t(q.out_w) * 3)
+            return MDJPEG_EINVAL;
+        MdClassifyCrop& d = recs[size_t(i)];
+        memset(&d, 0, sizeof(d));
+        if (!md_thumbnail_build(filter, q.canvas_w, q.canvas_h, q.out_w, q.out_h, MD_CLASSIFY_LDS_BYTES, tables[size_t(i)], work, &d))
+            return MDJPEG_EUNSUPPORTED;
+        if (!empty) d.src = q.src, d.pitch = q.pitch, d.src_w = q.src_w, d.src_h = q.src_h, d.off_x = q.off_x, d.off_y = q.off_y;
+        d.dst = q.dst, d.dst_pitch = q.dst_pitch;
+    }
+    std::vector<uint8_t> tile;
+    for (int i = 0; i < n; ++i) {
+        const MdClassifyCrop& d = recs[size_t(i)];
+        for (int g = 0; g < d.row_tiles; ++g)
+            for (int k = 0; k < d.strips; ++k)
+                if (!md_classify_run_tile(d, tables[size_t(i)].data(), k, g, MD_CLASSIFY_LDS_BYTES, tile, [&](int x, int y, int c, uint8_t v) {
+                        d.dst[int64_t(y) * d.dst_pitch + int64_t(x) * 3 + c] = v;
+                    }))
+                    return MDJPEG_EINVAL;
+    }
     return MDJPEG_OK;
 }
 
@@ -869,7 +892,7 @@ int mdjpeg_classifier_plan(int32_t canvas_w, int32_t canvas_h, int32_t size, int
     return MDJPEG_OK;
 }
 
-const char* mdjpeg_version(void) { return "mdjpeg 6"; }
+const char* mdjpeg_version(void) { return "mdjpeg 7"; }
 
 }  // extern "C"
 
@@ -1004,7 +1027,48 @@ static int classify_matrix() {
     return 0;
 }
 
+// `--thumbnails`: mdjpeg_thumbnails on heap images of exactly pitch x (src_h - 1) + 3 x src_w bytes and sheets of exactly
+// dst_pitch x (out_h - 1) + 3 x out_w bytes -- reducing, enlarging, one axis unchanged, a copy, a single pixel either way,
+// canvases with zeros on every side and wholly of zeros, a tap run longer than a strip, the three filters -- so that the
+// sanitizers see any access outside a rectangle or a tile.
+static int thumbnails_matrix() {
+    // src_w, src_h, canvas_w, canvas_h, off_x, off_y, out_w, out_h, pitch (0: 3 x src_w), dst_pitch (0: 3 x out_w)
+    const int shapes[][10] = {{97, 61, 97, 61, 0, 0, 13, 9, 0, 0},    {9, 7, 9, 7, 0, 0, 40, 31, 0, 121},  {40, 30, 40, 30, 0, 0, 40, 11, 0, 0},
+                              {40, 30, 40, 30, 0, 0, 17, 30, 127, 0}, {31, 20, 31, 20, 0, 0, 31, 20, 0, 100}, {50, 40, 50, 40, 0, 0, 1, 1, 0, 0},
+                              {1, 1, 1, 1, 0, 0, 5, 5, 0, 0},         {40, 30, 50, 30, 10, 0, 20, 12, 0, 0}, {40, 30, 50, 30, 0, 0, 20, 12, 0, 0},
+                              {40, 30, 40, 41, 0, 11, 20, 12, 0, 0},  {40, 30, 40, 41, 0, 0, 20, 12, 0, 67}, {1, 1, 30, 30, 29, 29, 7, 7, 0, 0},
+                              {1300, 40, 1300, 40, 0, 0, 20, 3, 0, 0}, {0, 0, 12, 9, 0, 0, 5, 4, 3, 0}, {0, 5, 12, 9, 0, 0, 12, 9, 3, 0}, {8, 8, 8, 60000, 0, 29000, 3, 40, 0, 0}};
+    int runs = 0;
+    for (const auto& q : shapes)
+        for (int filter = 0; filter < 3; ++filter) {
+            const int64_t pitch = q[8] ? q[8] : int64_t(q[0]) * 3, dpitch = q[9] ? q[9] : int64_t(q[6]) * 3;
+            const size_t bytes = q[0] && q[1] ? size_t(pitch) * (q[1] - 1) + size_t(q[0]) * 3 : 0, dbytes =size_t(dpitch) * (q[7] - 1) + size_t(q[6]) * 3;
+            const int shift = runs & 3;                                  // every alignment of the first byte
+            uint8_t* a = new uint8_t[bytes + shift];
+            uint8_t* o = new uint8_t[dbytes];
+            uint32_t seed = 4242u + uint32_t(runs);
+            for (size_t i = 0; i < bytes + shift; ++i) a[i] = uint8_t((seed = seed * 1664525u + 1013904223u) >> 24);
+            const mdjpeg_thumbnail t = {a + shift, pitch, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], o, dpitch};
+            const int rc = mdjpeg_thumbnails(&t, 1, filter);
+            delete[] a;
+            delete[] o;
+            if (rc != MDJPEG_OK) { printf("thumbnails: %dx%d in %dx%d to %dx%d, filter %d: %d\n", q[0], q[1], q[2], q[3], q[6], q[7], filter, rc); return 8; }
+            ++runs;
+        }
+    uint8_t px[3] = {1, 2, 3}, o1[3];
+    const mdjpeg_thumbnail bad[] = {{px, 3, 1, 1, 4, 4, 4, 0, 1, 1, o1, 3}, {px, 3, 1, 1, 1, 1, 0, 0, 0, 1, o1, 3}, {px, 3, 1, 1, 1, 1, 0, 0, 1, 1, o1, 2},
+                                    {nullptr, 3, 1, 1, 1, 1, 0, 0, 1, 1, o1, 3}, {px, 3, 1, 1, 1, 1, 0, 0, 1, 1, nullptr, 3}};
+    for (const mdjpeg_thumbnail& t : bad)
+        if (mdjpeg_thumbnails(&t, 1, 0) != MDJPEG_EINVAL) { printf("thumbnails: a bad argument is accepted\n"); return 8; }
+    const mdjpeg_thumbnail good = {px, 3, 1, 1, 1, 1, 0, 0, 1, 1, o1, 3}, tall = {px, 3, 1, 1, 1, 60000, 0, 0, 1, 1, o1, 3};
+    if (mdjpeg_thumbnails(&good, 1, 3) != MDJPEG_EINVAL || mdjpeg_thumbnails(&good, 1, 0) != MDJPEG_OK || o1[0] != 1 || o1[2] != 3) return 8;
+    if (mdjpeg_thumbnails(&tall, 1, 0) != MDJPEG_EUNSUPPORTED) { printf("thumbnails: plan\n"); return 8; }
+    printf("thumbnails: %d runs\n", runs);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc == 2 && !strcmp(argv[1], "--thumbnails")) return thumbnails_matrix();
     if (argc == 2 && !strcmp(argv[1], "--classify")) return classify_matrix();
     if (argc == 2 && !strcmp(argv[1], "--preview")) return preview_matrix();
     if (argc == 2 && !strcmp(argv[1], "--blur")) return blur_matrix();

@@ -41,6 +41,11 @@ int mdhip::check_shape(mdhip_ctx* ctx, int n, int h, int w) {
     return MDHIP_OK;
 }
 
+int mdhip::need_model(mdhip_ctx* ctx, const char* call) {
+    if (!ctx->images_only) return MDHIP_OK;
+    return fail(ctx, MDHIP_EINVAL, "%s: this context has no model (mdhip_create_images): only the image entry points work on it", call);
+}
+
 namespace {
 
 // the captured graphs go (after the device has finished with them: an executable may still be in flight on the caller's stream)
@@ -234,6 +239,22 @@ int mdhip_create(const mdhip_model* model, int device, int dtype, int max_batch,
     return MDHIP_OK;
 }
 
+int mdhip_create_images(int device, mdhip_ctx** out) {
+    if (!out) return fail(nullptr, MDHIP_EINVAL, "out is NULL");
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(nullptr, MDHIP_EHIP, "no HIP device visible (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(nullptr, MDHIP_EINVAL, "device %d outside [0,%d)", device, ndev);
+    const hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail(nullptr, MDHIP_EHIP, "device init failed: %s", hipGetErrorString(e));
+    mdhip_ctx* ctx = new mdhip_ctx();
+    ctx->device = device;
+    ctx->images_only = true;
+    *out = ctx;
+    return MDHIP_OK;
+}
+
 long long mdhip_plan_describe(const mdhip_model* model, int dtype, int max_batch, int max_h, int max_w, char* buf, size_t cap) {
     if (int rc = check_create_args(model, dtype, max_batch, max_h, max_w)) return rc;
     mdhip_ctx ctx;                                      // thrown away: no device is touched, nothing to destroy
@@ -314,12 +335,12 @@ void mdhip_destroy(mdhip_ctx* ctx) {
 int mdhip_max_stride(mdhip_ctx* ctx) { return ctx ? ctx->max_stride : MDHIP_EINVAL; }
 
 int mdhip_num_anchors(mdhip_ctx* ctx, int h, int w) {
-    if (!ctx) return MDHIP_EINVAL;
+    NEED_MODEL(ctx);
     return num_anchors_for(ctx, h, w);
 }
 
 int mdhip_forward(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
+    NEED_MODEL(ctx);
     if (int rc = check_shape(ctx, n, h, w)) return rc;
     if (int rc = check_calibrated(ctx)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
@@ -381,7 +402,7 @@ int mdhip_forward(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
 // batch, boxes de-scaled and un-flipped, the largest-stride level of the first pass and the smallest-stride
 // level of the last pass dropped (_clip_augmented), predictions concatenated along the anchor axis.
 int mdhip_forward_tta(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
+    NEED_MODEL(ctx);
     if (ctx->anchor_free)
         return fail(ctx, MDHIP_EUNSUPPORTED, "mdhip_forward_tta: augmented inference is implemented for YOLOv5 (anchor-based) "
                                              "models only, not for anchor-free (YOLO11) models");
@@ -443,7 +464,7 @@ int mdhip_forward_tta(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
 static constexpr float kFp8RangeMargin = 2.0f;
 
 int mdhip_calibrate(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
+    NEED_MODEL(ctx);
     if (ctx->dtype != MDHIP_DTYPE_FP8) return fail(ctx, MDHIP_EINVAL, "mdhip_calibrate: not an fp8 context");
     if (int rc = check_shape(ctx, n, h, w)) return rc;
     if (ctx->last_n < n || ctx->last_h != h || ctx->last_w != w)
@@ -480,6 +501,7 @@ int mdhip_f32_to_e4m3(const float* in, uint8_t* out, int n) {
 }
 
 int mdhip_fp8_get_scales(mdhip_ctx* ctx, float* scales, int32_t* layers, int32_t* ops, int max_n) {
+    NEED_MODEL(ctx);
     if (!ctx || max_n < 0) return MDHIP_EINVAL;
     int k = 0;
     for (size_t i = 0; i < ctx->ops.size(); ++i) {
@@ -496,6 +518,7 @@ int mdhip_fp8_get_scales(mdhip_ctx* ctx, float* scales, int32_t* layers, int32_t
 }
 
 int mdhip_fp8_set_scales(mdhip_ctx* ctx, const float* scales, int n) {
+    NEED_MODEL(ctx);
     if (!ctx || !scales) return MDHIP_EINVAL;
     if (ctx->dtype != MDHIP_DTYPE_FP8) return fail(ctx, MDHIP_EINVAL, "mdhip_fp8_set_scales: not an fp8 context");
     if (n != ctx->n_f8) return fail(ctx, MDHIP_EINVAL, "%d scales for %d fp8 tensors", n, ctx->n_f8);
@@ -515,7 +538,7 @@ int mdhip_fp8_set_scales(mdhip_ctx* ctx, const float* scales, int n) {
 int mdhip_last_num_anchors(mdhip_ctx* ctx) { return ctx ? ctx->last_A : 0; }
 
 int mdhip_time_forwards(mdhip_ctx* ctx, int enable) {
-    if (!ctx) return MDHIP_EINVAL;
+    NEED_MODEL(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (enable && !ctx->fwd_ev[0][0])
         for (int i = 0; i < mdhip_ctx::kFwdRing; ++i)
@@ -526,6 +549,7 @@ int mdhip_time_forwards(mdhip_ctx* ctx, int enable) {
 }
 
 int mdhip_forward_times(mdhip_ctx* ctx, float* ms, int max_n) {
+    NEED_MODEL(ctx);
     if (!ctx || !ms || max_n < 0) return MDHIP_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const long long have = std::min<long long>(ctx->fwd_count, mdhip_ctx::kFwdRing);
@@ -539,6 +563,7 @@ int mdhip_forward_times(mdhip_ctx* ctx, float* ms, int max_n) {
 }
 
 int mdhip_forward_timed(mdhip_ctx* ctx, int n, int h, int w, float* ms, void* hip_stream) {
+    NEED_MODEL(ctx);
     if (!ctx || !ms) return MDHIP_EINVAL;
     if (int rc = check_shape(ctx, n, h, w)) return rc;
     if (int rc = check_calibrated(ctx)) return rc;
@@ -565,6 +590,7 @@ int mdhip_forward_timed(mdhip_ctx* ctx, int n, int h, int w, float* ms, void* hi
 }
 
 int mdhip_time_op(mdhip_ctx* ctx, int op, int n, int h, int w, int iters, float* ms_avg, void* hip_stream) {
+    NEED_MODEL(ctx);
     if (!ctx || !ms_avg || op < 0 || op >= (int)ctx->ops.size() || iters < 1) return MDHIP_EINVAL;
     if (int rc = check_shape(ctx, n, h, w)) return rc;
     if (int rc = check_calibrated(ctx)) return rc;
@@ -607,7 +633,7 @@ static int nms_common(mdhip_ctx* ctx, const float* pred_dev, int n, int n_anchor
 
 int mdhip_nms(mdhip_ctx* ctx, int n, float conf_thres, float iou_thres, int max_det, float* out,
               int32_t* counts, void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
+    NEED_MODEL(ctx);
     if (ctx->last_h == 0) return fail(ctx, MDHIP_EINVAL, "mdhip_nms before mdhip_forward");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int A = ctx->last_A;
@@ -617,7 +643,7 @@ int mdhip_nms(mdhip_ctx* ctx, int n, float conf_thres, float iou_thres, int max_
 
 int mdhip_nms_enqueue(mdhip_ctx* ctx, int n, float conf_thres, float iou_thres, int max_det, int slot,
                       void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
+    NEED_MODEL(ctx);
     if (ctx->last_h == 0) return fail(ctx, MDHIP_EINVAL, "mdhip_nms_enqueue before mdhip_forward");
     if (slot < 0 || slot >= MDHIP_NMS_SLOTS) return fail(ctx, MDHIP_EINVAL, "slot %d outside [0,%d)", slot, MDHIP_NMS_SLOTS);
     if (n < 1 || n > ctx->max_batch) return fail(ctx, MDHIP_EINVAL, "batch %d outside [1,%d]", n, ctx->max_batch);
@@ -639,6 +665,7 @@ int mdhip_nms_enqueue(mdhip_ctx* ctx, int n, float conf_thres, float iou_thres, 
 }
 
 int mdhip_nms_wait(mdhip_ctx* ctx, int slot, const float** out, const int32_t** counts) {
+    NEED_MODEL(ctx);
     if (!ctx || !out || !counts) return MDHIP_EINVAL;
     if (slot < 0 || slot >= MDHIP_NMS_SLOTS || ctx->nms_slot_n[slot] == 0)
         return fail(ctx, MDHIP_EINVAL, "nothing enqueued in slot %d", slot);
@@ -650,7 +677,7 @@ int mdhip_nms_wait(mdhip_ctx* ctx, int slot, const float** out, const int32_t** 
 
 int mdhip_nms_on(mdhip_ctx* ctx, const float* pred, int n, int n_anchors, float conf_thres,
                  float iou_thres, int max_det, float* out, int32_t* counts, void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
+    NEED_MODEL(ctx);
     if (!pred) return fail(ctx, MDHIP_EINVAL, "pred is NULL");
     if (n < 1 || n > ctx->max_batch || n_anchors < 1 || n_anchors > ctx->a_cap)
         return fail(ctx, MDHIP_EINVAL, "n=%d n_anchors=%d outside the context capacity (%d x %d)", n, n_anchors, ctx->max_batch, ctx->a_cap);
@@ -663,6 +690,7 @@ int mdhip_nms_on(mdhip_ctx* ctx, const float* pred, int n, int n_anchors, float 
 }
 
 int mdhip_read_predictions(mdhip_ctx* ctx, int n, float* out, void* hip_stream) {
+    NEED_MODEL(ctx);
     if (!ctx || !out) return MDHIP_EINVAL;
     if (ctx->last_h == 0 || n < 1 || n > ctx->last_n) return fail(ctx, MDHIP_EINVAL, "no forward result for n=%d", n);
     hipStream_t s = (hipStream_t)hip_stream;
@@ -673,6 +701,7 @@ int mdhip_read_predictions(mdhip_ctx* ctx, int n, float* out, void* hip_stream) 
 }
 
 int mdhip_read_input(mdhip_ctx* ctx, int n, int h, int w, float* out, void* hip_stream) {
+    NEED_MODEL(ctx);
     if (!ctx || !out) return MDHIP_EINVAL;
     if (int rc = check_shape(ctx, n, h, w)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
@@ -688,7 +717,7 @@ int mdhip_read_input(mdhip_ctx* ctx, int n, int h, int w, float* out, void* hip_
 }
 
 int mdhip_read_layer(mdhip_ctx* ctx, int layer, int n, float* out, int* c, int* h, int* w, void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
+    NEED_MODEL(ctx);
     if (layer < 0 || layer >= (int)ctx->layer_out.size() || !ctx->layer_out[layer].valid)
         return fail(ctx, MDHIP_EINVAL, "layer %d has no readable output", layer);
     if (ctx->last_h == 0) return fail(ctx, MDHIP_EINVAL, "mdhip_read_layer before mdhip_forward");
@@ -714,6 +743,7 @@ int mdhip_read_layer(mdhip_ctx* ctx, int layer, int n, float* out, int* c, int* 
 int mdhip_num_ops(mdhip_ctx* ctx) { return ctx ? (int)ctx->ops.size() : MDHIP_EINVAL; }
 
 int mdhip_get_op_info(mdhip_ctx* ctx, int op, mdhip_op_info* out) {
+    NEED_MODEL(ctx);
     if (!ctx || !out || op < 0 || op >= (int)ctx->ops.size()) return MDHIP_EINVAL;
     const Op& o = ctx->ops[op];
     memset(out, 0, sizeof(*out));
@@ -741,6 +771,7 @@ int mdhip_get_op_info(mdhip_ctx* ctx, int op, mdhip_op_info* out) {
 int mdhip_num_conv_cfgs(void) { return conv_num_cfgs(); }
 
 int mdhip_op_supports_cfg(mdhip_ctx* ctx, int op, int cfg) {
+    NEED_MODEL(ctx);
     if (!ctx || op < 0 || op >= (int)ctx->ops.size()) return MDHIP_EINVAL;
     if (ctx->ops[op].kind != OP_CONV || cfg < 0 || cfg >= conv_num_cfgs()) return 0;
     ConvArgs a{};
@@ -754,6 +785,7 @@ const char* mdhip_conv_cfg_name(int cfg) { return (cfg >= 0 && cfg < conv_num_cf
 int mdhip_cfg_is_bitwise(int cfg) { return (cfg >= 0 && cfg < conv_num_cfgs() && conv_cfg_is_bitwise_family(cfg)) ? 1 : 0; }
 
 int mdhip_set_tuned(mdhip_ctx* ctx, const mdhip_tuned* entries, int n) {
+    NEED_MODEL(ctx);
     if (!ctx || n < 0 || (n > 0 && !entries)) return MDHIP_EINVAL;
     for (int i = 0; i < n; ++i)
         if (entries[i].cfg < 0 || entries[i].cfg >= conv_num_cfgs())
@@ -764,13 +796,14 @@ int mdhip_set_tuned(mdhip_ctx* ctx, const mdhip_tuned* entries, int n) {
 }
 
 int mdhip_set_fuse(mdhip_ctx* ctx, int on) {
-    if (!ctx) return MDHIP_EINVAL;
+    NEED_MODEL(ctx);
     ctx->fuse_enabled = on != 0;
     launches_changed(ctx);
     return MDHIP_OK;
 }
 
 int mdhip_set_option(mdhip_ctx* ctx, const char* name, int value) {
+    NEED_MODEL(ctx);
     if (!ctx || !name) return MDHIP_EINVAL;
     if (!strcmp(name, "letterbox_general")) ctx->letterbox_general = value != 0;
     else if (!strcmp(name, "fuse_decode")) ctx->fuse_decode = value != 0;
@@ -780,6 +813,7 @@ int mdhip_set_option(mdhip_ctx* ctx, const char* name, int value) {
 }
 
 int mdhip_set_graph(mdhip_ctx* ctx, int mode, int max_n) {
+    NEED_MODEL(ctx);
     if (!ctx || mode < 0 || mode > 2) return MDHIP_EINVAL;
     ctx->graph_mode = mode;
     if (max_n > 0) ctx->graph_max_n = max_n;
@@ -788,6 +822,7 @@ int mdhip_set_graph(mdhip_ctx* ctx, int mode, int max_n) {
 }
 
 int mdhip_set_op_cfg(mdhip_ctx* ctx, int op, int cfg) {
+    NEED_MODEL(ctx);
     if (!ctx || op < 0 || op >= (int)ctx->ops.size()) return MDHIP_EINVAL;
     if (ctx->ops[op].kind != OP_CONV) return fail(ctx, MDHIP_EINVAL, "op %d is not a conv", op);
     if (cfg < -1 || cfg >= conv_num_cfgs()) return fail(ctx, MDHIP_EINVAL, "cfg %d outside [-1,%d)", cfg, conv_num_cfgs());

@@ -33,6 +33,15 @@ inline int round_up(int x, int a) { return (x + a - 1) / a * a; }
 // batch and input size against what the context was planned for
 int check_shape(mdhip_ctx* ctx, int n, int h, int w);
 
+// A context of mdhip_create_images has no plan, no weights and no arena: every entry point that reads one of them starts with
+// NEED_MODEL, which refuses such a context (MDHIP_EINVAL, the call's name in mdhip_last_error) -- and a NULL one
+int need_model(mdhip_ctx* ctx, const char* call);
+#define NEED_MODEL(ctx)                                                   \
+    do {                                                                  \
+        if (!(ctx)) return MDHIP_EINVAL;                                  \
+        if (int rc__ = need_model((ctx), __func__)) return rc__;          \
+    } while (0)
+
 // device scratch that a context keeps between calls: it grows to the largest request and never shrinks
 struct DevBuffer {
     char* p = nullptr;
@@ -176,6 +185,7 @@ std::string describe_launches(const mdhip_ctx* ctx, const Resolved& r);
 
 struct mdhip_ctx {
     int device = 0;
+    bool images_only = false;     // made by mdhip_create_images: nothing below but the DevBuffers, err and the device is in use
     int dtype = 0;
     int max_batch = 0, max_h = 0, max_w = 0;
     int nc = 0, na = 0, nl = 0, no = 0;

@@ -1,5 +1,6 @@
 // The image entry points of the C ABI (include/mdhip.h): letterbox (mdhip_preprocess*), JPEG (mdhip_jpeg_*), mdhip_blur_regions,
-// the previews (mdhip_resample_lanczos, mdhip_draw_ops), the classifier input (mdhip_classifier_input).
+// the previews (mdhip_resample_lanczos, mdhip_draw_ops), the classifier input (mdhip_classifier_input), the thumbnails
+// (mdhip_thumbnails).
 // None of them looks at the model: they check their arguments, lay out scratch in one of the context's growable buffers
 // (mdhip_ctx.h DevBuffer) and launch.  What their checks have in common is written once, below; where two entry points
 // apply the same checks in a different order, each keeps its own order (the first failing check is what a caller sees).
@@ -9,6 +10,7 @@
 #include <cmath>
 #include <cstring>
 #include <map>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -37,6 +39,20 @@ int check_window(mdhip_ctx* ctx, const char* noun, int i, int w, int h, long lon
         return fail(ctx, MDHIP_EINVAL, "%s %d: pitch %lld for %d pixels per row (or %s %s above 2 GB)", noun, i, pitch, w,
                     strchr("aeiou", noun[0]) ? "an" : "a", noun);
     if (extent) *extent = need;
+    return MDHIP_OK;
+}
+
+// The canvas of crop / tile i (mdhip_classifier_input, mdhip_thumbnails): its size, the rectangle of image pixels inside it,
+// and that those pixels are device memory
+int check_canvas(mdhip_ctx* ctx, const char* noun, int i, const uint8_t* src, long long pitch, int src_w, int src_h, int canvas_w, int canvas_h,
+                 int off_x, int off_y) {
+    if (canvas_w < 1 || canvas_h < 1 || canvas_w > 65535 || canvas_h > 65535)
+        return fail(ctx, MDHIP_EINVAL, "%s %d: a canvas of %dx%d", noun, i, canvas_w, canvas_h);
+    if (int rc = check_window(ctx, noun, i, src_w, src_h, pitch)) return rc;
+    if (off_x < 0 || off_y < 0 || off_x > canvas_w - src_w || off_y > canvas_h - src_h)
+        return fail(ctx, MDHIP_EINVAL, "%s %d: %dx%d pixels at (%d, %d) leave the %dx%d canvas", noun, i, src_w, src_h, off_x, off_y, canvas_w,
+                    canvas_h);
+    if (!src || !is_device_ptr(src)) return fail(ctx, MDHIP_EINVAL, "%s %d: NULL or a host pointer -- the pixels must be device memory", noun, i);
     return MDHIP_OK;
 }
 
@@ -101,7 +117,7 @@ extern "C" {
 
 int mdhip_preprocess(mdhip_ctx* ctx, const uint8_t* const* images, const mdhip_letterbox* geom,
                      int n, int out_h, int out_w, void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
+    NEED_MODEL(ctx);
     if (!images || !geom) return fail(ctx, MDHIP_EINVAL, "images/geom is NULL");
     if (int rc = check_shape(ctx, n, out_h, out_w)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
@@ -126,7 +142,7 @@ int mdhip_preprocess(mdhip_ctx* ctx, const uint8_t* const* images, const mdhip_l
 
 int mdhip_preprocess_windows(mdhip_ctx* ctx, const uint8_t* const* windows, const mdhip_letterbox* geom,
                              const int64_t* pitches, const int64_t* readable, int n, int out_h, int out_w, void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
+    NEED_MODEL(ctx);
     if (!windows || !geom || !pitches || !readable) return fail(ctx, MDHIP_EINVAL, "windows/geom/pitches/readable is NULL");
     if (int rc = check_shape(ctx, n, out_h, out_w)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
@@ -809,13 +825,7 @@ int mdhip_classifier_input(mdhip_ctx* ctx, const mdhip_classifier_crop* crops, i
     int max_blocks = 1;
     for (int i = 0; i < n; ++i) {
         const mdhip_classifier_crop& q = crops[i];
-        if (q.canvas_w < 1 || q.canvas_h < 1 || q.canvas_w > 65535 || q.canvas_h > 65535)
-            return fail(ctx, MDHIP_EINVAL, "crop %d: a canvas of %dx%d", i, q.canvas_w, q.canvas_h);
-        if (int rc = check_window(ctx, "crop", i, q.src_w, q.src_h, q.pitch)) return rc;
-        if (q.off_x < 0 || q.off_y < 0 || q.off_x > q.canvas_w - q.src_w || q.off_y > q.canvas_h - q.src_h)
-            return fail(ctx, MDHIP_EINVAL, "crop %d: %dx%d pixels at (%d, %d) leave the %dx%d canvas", i, q.src_w, q.src_h, q.off_x, q.off_y,
-                        q.canvas_w, q.canvas_h);
-        if (!q.src || !is_device_ptr(q.src)) return fail(ctx, MDHIP_EINVAL, "crop %d: NULL or a host pointer -- the pixels must be device memory", i);
+        if (int rc = check_canvas(ctx, "crop", i, q.src, q.pitch, q.src_w, q.src_h, q.canvas_w, q.canvas_h, q.off_x, q.off_y)) return rc;
         auto it = planned.find({q.canvas_w, q.canvas_h});
         if (it == planned.end()) {
             MdClassifyCrop d;
@@ -847,6 +857,63 @@ int mdhip_classifier_input(mdhip_ctx* ctx, const mdhip_classifier_crop* crops, i
     if (!table.empty()) HIP_TRY(ctx, hipMemcpyAsync(base + o_table, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, launch_classifier_input((const MdClassifyCrop*)(base + o_recs), n, max_blocks, (const int32_t*)(base + o_table),
                                          (const float*)(base + o_lut), out, s));
+    return MDHIP_OK;
+}
+
+int mdhip_thumbnails(mdhip_ctx* ctx, const mdhip_thumbnail* tiles, int n, int filter, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (n == 0) return MDHIP_OK;
+    if (!tiles) return fail(ctx, MDHIP_EINVAL, "tiles is NULL");
+    if (n < 1 || n > 65535) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
+    if (filter != MD_FILTER_BICUBIC && filter != MD_FILTER_BILINEAR && filter != MD_FILTER_LANCZOS)
+        return fail(ctx, MDHIP_EINVAL, "filter %d (0 = bicubic, 1 = bilinear, 2 = lanczos)", filter);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // every tile is checked and planned before anything is enqueued; tiles of one canvas and output size share their tables
+    std::map<std::tuple<int, int, int, int>, MdClassifyCrop> planned;
+    std::vector<MdClassifyCrop> recs((size_t)n);
+    std::vector<int32_t> table;
+    std::vector<double> work;
+    int max_blocks = 1;
+    for (int i = 0; i < n; ++i) {
+        const mdhip_thumbnail& q = tiles[i];
+        // (a canvas without image pixels -- a box wholly outside its image -- has a rectangle of no width or height: src is not read)
+        const bool empty = (q.src_w == 0 && q.src_h >= 0) || (q.src_h == 0 && q.src_w >= 0);
+        if (empty) {
+            if (q.canvas_w < 1 || q.canvas_h < 1 || q.canvas_w > 65535 || q.canvas_h > 65535)
+                return fail(ctx, MDHIP_EINVAL, "tile %d: a canvas of %dx%d", i, q.canvas_w, q.canvas_h);
+        } else if (int rc = check_canvas(ctx, "tile", i, q.src, q.pitch, q.src_w, q.src_h, q.canvas_w, q.canvas_h, q.off_x, q.off_y)) {
+            return rc;
+        }
+        if (int rc = check_window(ctx, "tile (output)", i, q.out_w, q.out_h, q.dst_pitch)) return rc;
+        if (!q.dst || !is_device_ptr(q.dst)) return fail(ctx, MDHIP_EINVAL, "tile %d: NULL or a host pointer -- dst must be device memory", i);
+        auto it = planned.find(std::make_tuple(q.canvas_w, q.canvas_h, q.out_w, q.out_h));
+        if (it == planned.end()) {
+            MdClassifyCrop d;
+            memset(&d, 0, sizeof(d));
+            if (!md_thumbnail_build(filter, q.canvas_w, q.canvas_h, q.out_w, q.out_h, MD_CLASSIFY_LDS_BYTES, table, work, &d))
+                return fail(ctx, MDHIP_EUNSUPPORTED, "tile %d: the rows one output row of a %dx%d canvas reduced to %dx%d needs do not fit on chip",
+                            i, q.canvas_w, q.canvas_h, q.out_w, q.out_h);
+            if (table.size() > 0x7fff0000u / sizeof(int32_t)) return fail(ctx, MDHIP_EUNSUPPORTED, "tile %d: the coefficient tables pass 2 GB", i);
+            it = planned.emplace(std::make_tuple(q.canvas_w, q.canvas_h, q.out_w, q.out_h), d).first;
+        }
+        MdClassifyCrop& d = recs[(size_t)i];
+        d = it->second;
+        if (!empty) d.src = q.src, d.pitch = q.pitch, d.src_w = q.src_w, d.src_h = q.src_h, d.off_x = q.off_x, d.off_y = q.off_y;
+        d.dst = q.dst, d.dst_pitch = q.dst_pitch;
+        if ((long long)d.strips * d.row_tiles > 0x7fffffffLL) return fail(ctx, MDHIP_EUNSUPPORTED, "tile %d: too many workgroups", i);
+        max_blocks = std::max(max_blocks, d.strips * d.row_tiles);
+    }
+    // the scratch: [records][coefficient tables]
+    ScratchLayout lay;
+    const size_t o_recs = lay.take(recs.size() * sizeof(MdClassifyCrop));
+    const size_t o_table = lay.take(std::max<size_t>(table.size(), 1) * sizeof(int32_t));
+    if (int rc = ctx->classify.reserve(ctx, lay.size)) return rc;
+    uint8_t* base = (uint8_t*)ctx->classify.p;
+    // (the uploads are from pageable memory: the copies have left the buffers when the call returns)
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_recs, recs.data(), recs.size() * sizeof(MdClassifyCrop), hipMemcpyHostToDevice, s));
+    if (!table.empty()) HIP_TRY(ctx, hipMemcpyAsync(base + o_table, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, launch_thumbnails((const MdClassifyCrop*)(base + o_recs), n, max_blocks, (const int32_t*)(base + o_table), s));
     return MDHIP_OK;
 }
 

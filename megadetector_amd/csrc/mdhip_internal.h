@@ -652,5 +652,7 @@ hipError_t launch_draw_ops(const DrawImage* images, int n, int max_w, int max_h,
 // ---------------------------------------------------------------------------------------
 hipError_t launch_classifier_input(const MdClassifyCrop* crops, int n, int max_blocks, const int32_t* table, const float* lut, float* out,
                                    hipStream_t s);
+// Thumbnails (the same kernel body, bytes stored interleaved at each record's dst): n tiles, one launch
+hipError_t launch_thumbnails(const MdClassifyCrop* tiles, int n, int max_blocks, const int32_t* table, hipStream_t s);
 
 }  // namespace mdhip

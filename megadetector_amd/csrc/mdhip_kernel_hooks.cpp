@@ -18,6 +18,7 @@ extern "C" {
 
 int mdhip_dwconv3x3_on(mdhip_ctx* ctx, const uint16_t* in, int ld_in, const float* weight, const float* bias, const uint16_t* res,
                        uint16_t* out, int n, int h, int w, int c, int grp, int grp_stride, int grp_off, int act, void* hip_stream) {
+    NEED_MODEL(ctx);
     if (!ctx || !in || !weight || !bias || !out || n < 1 || h < 1 || w < 1 || c < 8 || c % 8 || grp < 8 || ld_in < 8)
         return MDHIP_EINVAL;
     if ((c / grp - 1) * grp_stride + grp_off + grp > ld_in || c % grp) return fail(ctx, MDHIP_EINVAL, "channel mapping outside ld_in");
@@ -49,6 +50,7 @@ int mdhip_dwconv3x3_on(mdhip_ctx* ctx, const uint16_t* in, int ld_in, const floa
 }
 
 int mdhip_attention_on(mdhip_ctx* ctx, const uint16_t* qkv, uint16_t* out, int n, int n_tokens, int heads, void* hip_stream) {
+    NEED_MODEL(ctx);
     if (!ctx || !qkv || !out || n < 1 || n_tokens < 1 || heads < 1) return MDHIP_EINVAL;
     hipStream_t s = (hipStream_t)hip_stream;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -67,6 +69,7 @@ int mdhip_attention_on(mdhip_ctx* ctx, const uint16_t* qkv, uint16_t* out, int n
 
 int mdhip_dfl_decode_on(mdhip_ctx* ctx, const float* box, const float* cls, int nc, int n, int ny, int nx, float stride, float* pred,
                         void* hip_stream) {
+    NEED_MODEL(ctx);
     if (!ctx || !box || !cls || !pred || nc < 1 || n < 1 || ny < 1 || nx < 1) return MDHIP_EINVAL;
     hipStream_t s = (hipStream_t)hip_stream;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -86,6 +89,7 @@ int mdhip_dfl_decode_on(mdhip_ctx* ctx, const float* box, const float* cls, int 
 
 int mdhip_adown_pool_on(mdhip_ctx* ctx, const uint16_t* in, uint16_t* a, uint16_t* b, int n, int h, int w, int c_in,
                         void* hip_stream) {
+    NEED_MODEL(ctx);
     if (!ctx || !in || !a || !b || n < 1 || h < 2 || w < 2 || h % 2 || w % 2 || c_in < 16 || c_in % 16) return MDHIP_EINVAL;
     hipStream_t s = (hipStream_t)hip_stream;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -106,6 +110,7 @@ int mdhip_adown_pool_on(mdhip_ctx* ctx, const uint16_t* in, uint16_t* a, uint16_
 
 int mdhip_cbfuse_on(mdhip_ctx* ctx, const uint16_t* const* src, const int32_t* factor, int n_src, const uint16_t* last,
                     uint16_t* out, int n, int h, int w, int c, void* hip_stream) {
+    NEED_MODEL(ctx);
     if (!ctx || !src || !factor || !last || !out || n_src < 1 || n_src > 3 || n < 1 || h < 1 || w < 1 || c < 8 || c % 8)
         return MDHIP_EINVAL;
     for (int k = 0; k < n_src; ++k)

@@ -1,6 +1,7 @@
-// Pillow's resize (LANCZOS for the annotated previews; bicubic, bilinear and LANCZOS for the classifier input, at the end of
-// this file), and the drawing of the previews, shared by the GPU kernels (preview_kernels.cpp, classify_kernels.cpp) and their
-// host models (mdjpeg_resample, mdjpeg_draw, mdjpeg_classifier_input in jpeg_entropy.cpp): ONE computation of the coefficient tables, ONE weighted
+// Pillow's resize (LANCZOS for the annotated previews; bicubic, bilinear and LANCZOS for the classifier input and the
+// thumbnails of the RDE review folder, at the end of this file), and the drawing of the previews, shared by the GPU kernels
+// (preview_kernels.cpp, classify_kernels.cpp) and their host models (mdjpeg_resample, mdjpeg_draw, mdjpeg_classifier_input,
+// mdjpeg_thumbnails in jpeg_entropy.cpp): ONE computation of the coefficient tables, ONE weighted
 // sum of a run of samples, ONE walk of a pixel through its image's drawing operations, compiled by both, so that the CPU
 // suite and the host sanitizers exercise the very statements the lanes run (the arrangement of blur_box.h).
 //
@@ -210,6 +211,10 @@ MDR_HD static inline int md_draw_pixel(const int32_t* ops, int n, const uint8_t*
 // A workgroup takes `strip` output columns and `rows` output rows of a crop: the horizontal pass of the canvas rows its
 // vertical taps cover goes into an 8-bit tile on chip (md_classify_hsample), the vertical pass reads the tile
 // (md_classify_vsample).  Both are compiled by classify_kernels.cpp and by the host model mdjpeg_classifier_input.
+//
+// The same record and the same two functions make a THUMBNAIL (mdhip_thumbnails, mdjpeg_thumbnails; the tiles of the RDE
+// review folder: Image.crop(box).resize((out_w, out_h)) pasted into a sheet): there the window is the whole resized canvas,
+// out_w x out_h of any shape, and the bytes are stored interleaved at `dst` instead of going through the float table.
 
 #define MD_CLASSIFY_LDS_BYTES 32768              // the 8-bit tile of a workgroup
 #define MD_CLASSIFY_STRIP 64                     // output columns of a workgroup at the most
@@ -220,12 +225,14 @@ struct MdClassifyCrop {
     const uint8_t* src;                  // the first image pixel that lies in the canvas
     long long pitch;                     // bytes a row of the image
     int32_t src_w, src_h, off_x, off_y;  // the part of the canvas that holds image pixels
-    int32_t size;                        // S
-    int32_t hb_off, hk_off, hks;         // horizontal table of output columns 0 .. S - 1 (int32 words into the table: bounds,
+    int32_t out_w, out_h;                // the window: S x S for a classifier, the whole resized canvas for a thumbnail
+    int32_t hb_off, hk_off, hks;         // horizontal table of output columns 0 .. out_w - 1 (int32 words into the table: bounds,
                                          // weights; taps a line); hks 0 = the width stays: column x is canvas column hb_off + x
-    int32_t vb_off, vk_off, vks;         // vertical table of output rows 0 .. S - 1, likewise (vks 0: row y is canvas row vb_off + y)
+    int32_t vb_off, vk_off, vks;         // vertical table of output rows 0 .. out_h - 1, likewise (vks 0: row y is canvas row vb_off + y)
     int32_t strip, rows;                 // output columns and rows of a workgroup
     int32_t strips, row_tiles;           // the crop runs strips * row_tiles workgroups
+    uint8_t* dst;                        // a thumbnail: where pixel (0, 0) of the window goes, R G B interleaved (a classifier: unused)
+    long long dst_pitch;                 // bytes a row of the sheet it lies in
 };
 
 // the resized size of the canvas and where the S x S window lies in it [3P: torchvision Resize(int) and CenterCrop]
@@ -249,7 +256,8 @@ MDR_HD static inline void md_classify_rows(const MdClassifyCrop& d, const int32_
 }
 
 // the plan of a crop: the widest strip, then the most rows, whose tile fits lds_bytes.  vbounds: the vertical bounds of the
-// window's rows, NULL when the height stays.  Returns 0 when the taps of one output row do not fit even for one column.
+// window's rows, NULL when the height stays; size: the rows of the window.  Returns 0 when the taps of one output row do not
+// fit even for one column.
 static inline int md_classify_plan(const int32_t* vbounds, int size, int lds_bytes, int32_t* strip_out, int32_t* rows_out) {
     for (int strip = MD_CLASSIFY_STRIP; strip >= 1; strip >>= 1)
         for (int rows = MD_CLASSIFY_MAX_ROWS; rows >= 1; rows >>= 1) {
@@ -303,28 +311,64 @@ static inline void md_classify_lut(const float mean[3], const float std[3], floa
         }
 }
 
-// Tables and plan of one crop, appended to `table` (int32 words); fills everything of `d` but src / pitch / the rectangle.
-// Returns 0 when no plan fits lds_bytes.  `work` is scratch.
-static inline int md_classify_build(int filter, int canvas_w, int canvas_h, int size, int lds_bytes, std::vector<int32_t>& table,
-                                    std::vector<double>& work, MdClassifyCrop* d) {
-    int rw, rh, left, top;
-    md_classify_geometry(canvas_w, canvas_h, size, &rw, &rh, &left, &top);
-    d->size = size;
-    auto axis = [&](int in, int out, int o0, int32_t* b_off, int32_t* k_off, int32_t* ks) {
+// Tables and plan of the window out_w x out_h at (left, top) of a canvas resized to rw x rh, appended to `table` (int32
+// words); fills everything of `d` but src / pitch / the rectangle / dst.  Returns 0 when no plan fits lds_bytes.  `work` is
+// scratch.
+static inline int md_classify_build_window(int filter, int canvas_w, int canvas_h, int rw, int rh, int left, int top, int out_w, int out_h,
+                                           int lds_bytes, std::vector<int32_t>& table, std::vector<double>& work, MdClassifyCrop* d) {
+    d->out_w = out_w, d->out_h = out_h;
+    auto axis = [&](int in, int out, int o0, int n, int32_t* b_off, int32_t* k_off, int32_t* ks) {
         if (in == out) { *b_off = o0, *k_off = 0, *ks = 0; return; }
         const int ksize = md_resample_ksize_filter(filter, in, out);
         *ks = ksize;
         *b_off = (int32_t)table.size();
-        *k_off = *b_off + 2 * size;
-        table.resize(table.size() + 2 * (size_t)size + (size_t)size * ksize);
+        *k_off = *b_off + 2 * n;
+        table.resize(table.size() + 2 * (size_t)n + (size_t)n * ksize);
         work.resize((size_t)ksize);
-        md_resample_coeffs_filter(filter, in, out, o0, o0 + size, ksize, table.data() + *b_off, table.data() + *k_off, work.data());
+        md_resample_coeffs_filter(filter, in, out, o0, o0 + n, ksize, table.data() + *b_off, table.data() + *k_off, work.data());
     };
-    axis(canvas_w, rw, left, &d->hb_off, &d->hk_off, &d->hks);
-    axis(canvas_h, rh, top, &d->vb_off, &d->vk_off, &d->vks);
-    if (!md_classify_plan(d->vks ? table.data() + d->vb_off : nullptr, size, lds_bytes, &d->strip, &d->rows)) return 0;
-    d->strips = (size + d->strip - 1) / d->strip;
-    d->row_tiles = (size + d->rows - 1) / d->rows;
+    axis(canvas_w, rw, left, out_w, &d->hb_off, &d->hk_off, &d->hks);
+    axis(canvas_h, rh, top, out_h, &d->vb_off, &d->vk_off, &d->vks);
+    if (!md_classify_plan(d->vks ? table.data() + d->vb_off : nullptr, out_h, lds_bytes, &d->strip, &d->rows)) return 0;
+    d->strips = (out_w + d->strip - 1) / d->strip;
+    d->row_tiles = (out_h + d->rows - 1) / d->rows;
+    return 1;
+}
+
+// a classifier's crop: the S x S centre of the canvas resized so that its shorter side is S
+static inline int md_classify_build(int filter, int canvas_w, int canvas_h, int size, int lds_bytes, std::vector<int32_t>& table,
+                                    std::vector<double>& work, MdClassifyCrop* d) {
+    int rw, rh, left, top;
+    md_classify_geometry(canvas_w, canvas_h, size, &rw, &rh, &left, &top);
+    return md_classify_build_window(filter, canvas_w, canvas_h, rw, rh, left, top, size, size, lds_bytes, table, work, d);
+}
+
+// a thumbnail: the whole canvas resized to out_w x out_h (Image.crop(box).resize((out_w, out_h), filter))
+static inline int md_thumbnail_build(int filter, int canvas_w, int canvas_h, int out_w, int out_h, int lds_bytes,
+                                     std::vector<int32_t>& table, std::vector<double>& work, MdClassifyCrop* d) {
+    return md_classify_build_window(filter, canvas_w, canvas_h, out_w, out_h, 0, 0, out_w, out_h, lds_bytes, table, work, d);
+}
+
+// one tile of a record on the host, as a workgroup runs it: strip k, row tile g.  `store(x, y, c, v)` takes byte v of channel
+// c of window pixel (x, y).  Returns 0 when the tile does not fit lds_bytes (a plan that md_classify_plan did not make).
+template <class Store>
+static inline int md_classify_run_tile(const MdClassifyCrop& d, const int32_t* table, int k, int g, int lds_bytes, std::vector<uint8_t>& tile,
+                                       Store store) {
+    const int x0 = k * d.strip, nx = d.strip < d.out_w - x0 ? d.strip : d.out_w - x0;
+    const int r0 = g * d.rows, nr = d.rows < d.out_h - r0 ? d.rows : d.out_h - r0;
+    const int tile_pitch = nx * 3;
+    int first, count;
+    md_classify_rows(d, table, r0, r0 + nr, &first, &count);
+    if ((long long)count * tile_pitch > lds_bytes) return 0;
+    tile.assign((size_t)count * tile_pitch, 0);                          // (exact: the sanitizers see an access outside it)
+    for (int i = 0; i < count * tile_pitch; ++i) {
+        const int j = i / tile_pitch, b = i - j * tile_pitch;
+        tile[(size_t)i] = md_classify_hsample(d, table, first + j, x0 + b / 3, b % 3);
+    }
+    for (int i = 0; i < nr * tile_pitch; ++i) {
+        const int j = i / tile_pitch, b = i - j * tile_pitch;
+        store(x0 + b / 3, r0 + j, b % 3, md_classify_vsample(d, table, tile.data(), tile_pitch, first, r0 + j, b));
+    }
     return 1;
 }
 

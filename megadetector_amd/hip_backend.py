@@ -183,6 +183,31 @@ class HipContext:
         self.max_stride = self.lib.mdhip_max_stride(self.h)
         self.load_tuned()
 
+    @classmethod
+    def for_images(cls, device=0):
+        """
+        A context without a model (include/mdhip.h: mdhip_create_images): the image calls work on it -- jpeg_*, blur_regions,
+        resample_lanczos, draw_ops, classifier_input, thumbnails -- and every call that needs the plan or the weights
+        (preprocess, forward, nms, read_*, ...) raises HipError (MDHIP_EINVAL).
+        """
+        self = cls.__new__(cls)
+        self.lib = _lib.load()
+        self.weights = None
+        self.device = int(device)
+        self.max_batch = 0
+        self._keep = None
+        self.dtype = None
+        handle = C.c_void_p()
+        rc = self.lib.mdhip_create_images(self.device, C.byref(handle))
+        if rc != 0:
+            raise HipError('mdhip_create_images failed ({}): {}'.format(rc, self.lib.mdhip_last_error(None).decode()))
+        self.h = handle
+        self.anchor_free = False
+        self.no = 0
+        self.has_detect = False
+        self.max_stride = 0
+        return self
+
     TUNED_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tuned_cfgs.json')
 
     def load_tuned(self, path=None):
@@ -434,6 +459,25 @@ class HipContext:
                                              C.c_void_p(int(out_ptr)), C.c_void_p(stream))
         if rc != _lib.MDHIP_EUNSUPPORTED:
             self._check(rc, 'mdhip_classifier_input')
+        return rc == 0
+
+    def thumbnails(self, tiles, filter=0, stream=0):
+        """
+        Tiles of device images into device sheets, in one launch (include/mdhip.h: mdhip_thumbnails): tile i is Pillow's
+        image.crop(box).resize((out_w, out_h)) pasted at dst, bit for bit.
+        tiles:   per tile (ptr, pitch, src_w, src_h, canvas_w, canvas_h, off_x, off_y, out_w, out_h, dst, dst_pitch): the
+                 canvas as for classifier_input, the tile's size, the device address of its first pixel in its sheet and the
+                 sheet's bytes a row.  The tiles of one call must not overlap.
+        filter:  0 bicubic (Image.resize's default for RGB) / 1 bilinear / 2 lanczos
+        Returns True; False (MDHIP_EUNSUPPORTED, nothing enqueued) when a tile is reduced more than fits on chip.  Only enqueues.
+        """
+        n = len(tiles)
+        if n == 0:
+            return True
+        recs = (_lib.mdhip_thumbnail * n)(*[_lib.mdhip_thumbnail(*[int(v) for v in q]) for q in tiles])
+        rc = self.lib.mdhip_thumbnails(self.h, recs, n, int(filter), C.c_void_p(stream))
+        if rc != _lib.MDHIP_EUNSUPPORTED:
+            self._check(rc, 'mdhip_thumbnails')
         return rc == 0
 
     def forward(self, n, h, w, stream=0):

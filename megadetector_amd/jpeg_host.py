@@ -41,6 +41,12 @@ class mdjpeg_scan_info(C.Structure):
                 ('scan_begin', C.c_int64), ('scan_end', C.c_int64), ('n_segments', C.c_int32), ('reserved', C.c_int32)]
 
 
+class mdjpeg_thumbnail(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('pitch', C.c_int64), ('src_w', C.c_int32), ('src_h', C.c_int32),
+                ('canvas_w', C.c_int32), ('canvas_h', C.c_int32), ('off_x', C.c_int32), ('off_y', C.c_int32),
+                ('out_w', C.c_int32), ('out_h', C.c_int32), ('dst', C.c_void_p), ('dst_pitch', C.c_int64)]
+
+
 #: every symbol include/mdjpeg.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     'mdjpeg_parse': (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(mdjpeg_info)]),
@@ -60,6 +66,7 @@ SYMBOLS = {
     'mdjpeg_classifier_input': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p]),
     'mdjpeg_classifier_plan': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    'mdjpeg_thumbnails': (C.c_int, [C.POINTER(mdjpeg_thumbnail), C.c_int, C.c_int32]),
     'mdjpeg_repeat_detections': (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     'mdjpeg_version': (C.c_char_p, []),
@@ -425,6 +432,35 @@ def classifier_input(rgb, canvas, size, filter=0, mean=(0.485, 0.456, 0.406), st
     if rc != MDJPEG_OK:
         raise ValueError('mdjpeg_classifier_input returned {} for {} x {} in a canvas of {} x {} at size {}'.format(rc, w, h, cw, ch, size))
     return out
+
+
+def thumbnails(tiles, filter=0):
+    """
+    Tiles into sheets (mdjpeg_thumbnails: the host model of HipContext.thumbnails): Pillow's image.crop(box).resize((out_w,
+    out_h)) + sheet.paste(tile, (x, y)), bit for bit.  tiles: (rgb, canvas, sheet, x, y, out_w, out_h) each -- rgb, an H x W x 3
+    uint8 array whose rows may be strided, is the part of the canvas (canvas_w, canvas_h, off_x, off_y) that holds pixels;
+    sheet, a writeable H x W x 3 uint8 array, gets the tile at (x, y), which must lie inside it.  All or nothing: raises
+    ValueError for an argument the library refuses, returns False when it answers MDJPEG_EUNSUPPORTED (the sizes the GPU call
+    refuses), else True.
+    """
+    recs = (mdjpeg_thumbnail * max(len(tiles), 1))()
+    for r, (rgb, canvas, sheet, x, y, out_w, out_h) in zip(recs, tiles):
+        # (rgb None or without pixels: the canvas holds no image pixel -- a box wholly outside its image)
+        src, (w, h, pitch) = (0, (0, 0, 0)) if rgb is None or rgb.size == 0 else (rgb.ctypes.data, _rgb_rows(rgb, False))
+        sw, sh, spitch = _rgb_rows(sheet, True)
+        x, y, out_w, out_h = int(x), int(y), int(out_w), int(out_h)
+        if x < 0 or y < 0 or out_w < 1 or out_h < 1 or x + out_w > sw or y + out_h > sh:
+            raise ValueError('a tile of {} x {} at ({}, {}) leaves its sheet of {} x {}'.format(out_w, out_h, x, y, sw, sh))
+        cw, ch, ox, oy = (int(v) for v in canvas)
+        r.src, r.pitch, r.src_w, r.src_h = src, pitch, w, h
+        r.canvas_w, r.canvas_h, r.off_x, r.off_y = cw, ch, ox, oy
+        r.out_w, r.out_h, r.dst, r.dst_pitch = out_w, out_h, sheet.ctypes.data + y * spitch + x * 3, spitch
+    rc = load().mdjpeg_thumbnails(recs, len(tiles), int(filter))
+    if rc == MDJPEG_EUNSUPPORTED:
+        return False
+    if rc != MDJPEG_OK:
+        raise ValueError('mdjpeg_thumbnails returned {}'.format(rc))
+    return True
 
 
 def classifier_plan(canvas_w, canvas_h, size, filter=0, lds_bytes=0):

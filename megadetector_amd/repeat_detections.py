@@ -11,15 +11,17 @@ the marking.  The comparison of every detection with the candidates before it --
 camera)^2 -- runs on the GPU (mdhip_repeat_detections, csrc/rde_kernels.cpp) or, with backend='host', in its host model
 (mdjpeg_repeat_detections); both decide a pair with the same doubles, operation for operation, as ct_utils.get_iou.
 
-What is not: the review folder (sample images, the HTML page, remove_repeat_detections after a manual review,
-filterFileToLoad), smartSort='clustersort', the CSV and intermediate-file paths.  They raise NotImplementedError.  So
-bWriteFilteringFolder defaults to False HERE (True in the reference).
+What is not, in THIS module: the review folder (sample images, remove_repeat_detections after a manual review,
+filterFileToLoad) -- it has entry points of its own in rde_review.py (write_review_folder, find_and_write,
+remove_repeat_detections), which take what find_repeat_detections returns -- and, anywhere, the HTML page,
+smartSort='clustersort', the CSV and intermediate-file paths.  Here they raise NotImplementedError.  So bWriteFilteringFolder
+defaults to False HERE (True in the reference).
 
 The output file differs from the reference's write_api_results in two deliberate ways: values are NOT rounded (the reference's
 writer rounds every float of the file to 3 decimals, a side effect of DataFrame.to_json(double_precision=3)), and images do
 not gain keys they did not have (the reference's table gives a failed image "detections": null).  A second file,
-<output>.rde_index.json, lists the suspicious candidates with their instances in a plain layout of our own, from which a later
-change can build the review folder.
+<output>.rde_index.json, lists the suspicious candidates with their instances in a plain layout of our own; the review folder's
+detectionIndex.json extends it.
 
 No pandas on this path.
 
@@ -51,7 +53,7 @@ REVIEW_FOLDER_OPTIONS = ('imageBase', 'outputBase', 'filteredFileListToLoad', 'b
 
 class RepeatDetectionOptions:
     """The reference's RepeatDetectionOptions, under its attribute names and with its defaults -- except bWriteFilteringFolder,
-    which is False here: the review folder is not built (see the module text)."""
+    which is False here: the review folder is written by rde_review.write_review_folder, not by this function."""
 
     def __init__(self):
         self.confidenceMin = 0.1                 #: detections below it are not considered
@@ -69,7 +71,7 @@ class RepeatDetectionOptions:
         self.excludeFolders = None
         self.filenameReplacements = {}
         self.smartSort = 'xsort'                 #: 'xsort': suspicious candidates from left to right; None: in order of creation
-        self.bWriteFilteringFolder = False       #: the reference's default is True; True is NotImplementedError here
+        self.bWriteFilteringFolder = False       #: the reference's default is True; True is NotImplementedError here (rde_review.py)
         self.filterFileToLoad = ''
 
 
@@ -111,13 +113,13 @@ def check_options(options):
     if options.smartSort not in (None, 'xsort'):
         raise ValueError('Unrecognized sort method {}'.format(options.smartSort))
     if getattr(options, 'bWriteFilteringFolder', False):
-        raise NotImplementedError('the review folder is not built here: bWriteFilteringFolder must stay False '
-                                  '(<output>.rde_index.json holds the candidates and their instances)')
+        raise NotImplementedError('the review folder is not written by find_repeat_detections: bWriteFilteringFolder must stay False '
+                                  '(rde_review.write_review_folder takes what this function returns)')
     if getattr(options, 'filterFileToLoad', ''):
-        raise NotImplementedError('filterFileToLoad belongs to the review folder, which is not built here')
+        raise NotImplementedError('filterFileToLoad belongs to the review folder: rde_review.remove_repeat_detections loads its index')
     given = [k for k in REVIEW_FOLDER_OPTIONS if k in vars(options) and vars(options)[k] not in (None, '', False)]
     if given:
-        raise NotImplementedError('{} belong(s) to the review folder, which is not built here'.format(', '.join(given)))
+        raise NotImplementedError('{} belong(s) to the review folder: see rde_review.ReviewFolderOptions'.format(', '.join(given)))
     if options.customDirNameFunction is not None and options.nDirLevelsFromLeaf != 0:
         raise ValueError('Cannot mix custom dir name functions with nDirLevelsFromLeaf')
     if options.includeFolders is not None and options.excludeFolders is not None:

@@ -173,6 +173,7 @@ last_preview_counts = {}
 #: detector without classify=), 'skipped' = detections without a crop
 last_classifications = {}
 last_classify_counts = {}
+last_detector = None        # the detector of the last load_and_run_detector_batch of this process (--rde_review_folder works on its context)
 
 
 def _relative_name(file, base):
@@ -777,7 +778,7 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
     them); the results, and the checkpoints, are what they are without it.
     Returns the list of per-image result dicts.
     """
-    global verbose, last_crop_counts, last_blur_counts, last_preview_counts, last_classifications, last_classify_counts
+    global verbose, last_crop_counts, last_blur_counts, last_preview_counts, last_classifications, last_classify_counts, last_detector
     verbose = bool(verbose_output)
     output_threshold = DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD if confidence_threshold is None else confidence_threshold
     writers = []
@@ -835,6 +836,7 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
         detector = run_detector.load_detector(model_file, force_model_download=force_model_download,
                                               detector_options=detector_options, verbose=verbose)
         print('Loaded model in {:.2f} seconds'.format(time.time() - t0))
+    last_detector = detector
     # Building the per-image result dicts allocates tens of thousands of containers per batch; every full pass of
     # the cyclic collector they trigger walks the start-up heap (torch, numpy, the model).  Freezing that heap once
     # (the collector stays on) is worth ~7 % of the loop at MI355X speeds.
@@ -1200,6 +1202,10 @@ def main(argv=None):
                     help='after the run, mark the repeat detections of the results (repeat_detections.find_repeat_detections: a box a '
                          'camera was given --rde_occurrence_threshold times gets a negative confidence) and write them to F and '
                          'F.rde_index.json; the output file and the checkpoints are what they are without it')
+    ap.add_argument('--rde_review_folder', type=str, default=None, metavar='DIR',
+                    help='with --rde_results_file: also write the review folder DIR/filtering_<date>/ (rde_review.write_review_folder: one '
+                         'sample image per suspicious candidate; after a review, python -m megadetector_amd.rde_review remove un-marks '
+                         'the candidates whose samples were deleted); the images are read from the image folder of the run')
     ap.add_argument('--rde_occurrence_threshold', type=int, default=None, help='default 20, as the reference')
     ap.add_argument('--rde_iou_threshold', type=float, default=None, help='default 0.9, as the reference')
     ap.add_argument('--rde_backend', type=str, default=None, choices=('gpu', 'host'),
@@ -1209,6 +1215,9 @@ def main(argv=None):
     if args.rde_results_file is None:
         assert args.rde_occurrence_threshold is None and args.rde_iou_threshold is None and args.rde_backend is None, \
             '--rde_occurrence_threshold / --rde_iou_threshold / --rde_backend need --rde_results_file'
+        assert args.rde_review_folder is None, '--rde_review_folder needs --rde_results_file'
+    if args.rde_review_folder is not None:
+        assert os.path.isdir(args.image_file), '--rde_review_folder needs a folder of images as the input'
     classify_sub = {k: getattr(args, k) for k in ('classifier_categories', 'classifier_image_size', 'classifier_interpolation',
                                                   'classify_confidence_threshold', 'classify_categories', 'classification_threshold',
                                                   'classifier_batch_size', 'classifier_jpeg_quality', 'classification_results_file')}
@@ -1341,6 +1350,14 @@ def main(argv=None):
         marked = rde_mod.mark_repeat_detections(copy.deepcopy(final_output), rde_options, backend=args.rde_backend or 'gpu')
         rde_mod.write_outputs(marked, rde_options, args.rde_results_file)
         print('Marked {} repeat detections; results saved at {}'.format(marked.n_bbox_changes, args.rde_results_file))
+        if args.rde_review_folder is not None:
+            from megadetector_amd import rde_review
+            review_options = rde_review.ReviewFolderOptions()
+            review_options.imageBase, review_options.outputBase = os.path.abspath(args.image_file), args.rde_review_folder
+            # on the detector's own context where this process has one (a sharded run has none here: a context without a model)
+            counts = rde_review.write_review_folder(marked, review_options, backend=args.rde_backend or 'gpu',
+                                                    ctx=getattr(last_detector, '_ctx', None), rde_options=rde_options)
+            print('Wrote {} review samples to {} ({} on the GPU, {} by PIL)'.format(counts['sheets'], counts['folder'], counts['gpu'], counts['host']))
     for cp in [checkpoint_path] + [shard_checkpoint_path(checkpoint_path, g) for g in range(max(1, args.n_gpus))]:
         if cp and os.path.isfile(cp):
             os.remove(cp)
