@@ -305,6 +305,34 @@ int mdhip_jpeg_encode(mdhip_ctx* ctx, const uint8_t* const* windows, const int32
                       int64_t capacity, int64_t* offsets, int64_t* sizes, int64_t* needed, void* hip_stream);
 long long mdhip_jpeg_encode_bound(int width, int height);
 
+/* mdhip_jpeg_encode with the chroma sampling and the quantisation tables of EACH window (the reference's
+ * exif_preserving_save(quality = 'keep') makes Pillow re-encode an RGB JPEG with the source file's own tables and its own
+ * sampling, postprocessing/separate_detections_into_folders.py): window i's scan is, byte for byte, the scan of
+ * Image.fromarray(window).save(f, 'JPEG', qtables = [luma, chroma], subsampling = samplings[i]).  The same kernels, the same
+ * passes and the same contract as mdhip_jpeg_encode, which is this call with MDHIP_JPEG_H2V2 and one pair for all windows.
+ *   samplings   HOST array of n values, numbered as Pillow's `subsampling`:
+ *                 MDHIP_JPEG_H1V1 (4:4:4)  MCU  8 x 8,   3 blocks  Y Cb Cr;          chroma as it is (fullsize_downsample)
+ *                 MDHIP_JPEG_H2V1 (4:2:2)  MCU 16 x 8,   4 blocks  Y0 Y1 Cb Cr;      pairs along a row, bias 0, 1, 0, 1 ...
+ *                                          (h2v1_downsample), the right edge replicated before
+ *                 MDHIP_JPEG_H2V2 (4:2:0)  MCU 16 x 16,  6 blocks  Y00 Y01 Y10 Y11 Cb Cr, as mdhip_jpeg_encode
+ *               (libjpeg's jcsample.c, statement for statement); dummy blocks at the right and bottom edge and the DC
+ *               prediction along the MCU order follow the window's own layout
+ *   quant       HOST array of n pairs of tables, [n][2][64]: window i's luma table, then its chroma table, natural order,
+ *               every entry 1 .. 255
+ * A sampling outside 0 .. 2 or a table entry outside 1 .. 255 is MDHIP_EINVAL, and nothing is launched.
+ * mdhip_jpeg_encode_sampled_bound(w, h, sampling) is a capacity that always suffices for one window, derived as
+ * mdhip_jpeg_encode_bound is: 1660 bits a block at most whatever the sampling (the code lengths are the tables', not the
+ * layout's), 7 bits of padding, every byte stuffed: 8 x (52 x blocks + 1) bytes with
+ * blocks = (hs x vs + 2) x ((w + 8 hs - 1) / (8 hs)) x ((h + 8 vs - 1) / (8 vs)), (hs, vs) = (1, 1), (2, 1), (2, 2);
+ * -1 for a size outside 1 .. 65535 or a sampling outside 0 .. 2.  For h2v2 it is mdhip_jpeg_encode_bound(w, h). */
+#define MDHIP_JPEG_H1V1 0
+#define MDHIP_JPEG_H2V1 1
+#define MDHIP_JPEG_H2V2 2
+int mdhip_jpeg_encode_sampled(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
+                              const int64_t* pitches, const int32_t* samplings, int n, const uint16_t* quant, uint8_t* out,
+                              int64_t capacity, int64_t* offsets, int64_t* sizes, int64_t* needed, void* hip_stream);
+long long mdhip_jpeg_encode_sampled_bound(int width, int height, int sampling);
+
 /* Gaussian blur of rectangles of device images, IN PLACE (the reference blurs people in the image copies it writes:
  * postprocessing/separate_detections_into_folders.py --category_names_to_blur, visualization_utils.blur_detections: per box
  * crop -> ImageFilter.GaussianBlur(40) -> paste): every rectangle becomes, bit for bit, what Pillow's GaussianBlur(radius)

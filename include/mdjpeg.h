@@ -105,6 +105,15 @@ int mdjpeg_decode_subsequences(const uint8_t* data, size_t size, int subseq_bits
 int mdjpeg_encode_subsequences(const int16_t* const* coefs, const int32_t* widths, const int32_t* heights, int n, int chunk_bytes,
                                uint8_t* out, size_t capacity, int64_t* offsets, int64_t* sizes, size_t* needed);
 int64_t mdjpeg_encode_bound(int32_t width, int32_t height);
+/* The same with a chroma sampling per crop (GPU: mdhip_jpeg_encode_sampled): samplings[i] 0 = h1v1 (4:4:4, MCU of 3 blocks),
+ * 1 = h2v1 (4:2:2, 4 blocks), 2 = h2v2 (4:2:0, 6 blocks), numbered as Pillow's `subsampling`; anything else is
+ * MDJPEG_EINVAL.  coefs[i] in the layout of mdjpeg_decode for that sampling: Y in whole MCUs ((w + 8 hs - 1) / (8 hs) x
+ * (h + 8 vs - 1) / (8 vs) MCUs of hs x vs luma blocks), then Cb, then Cr, one block an MCU each.
+ * mdjpeg_encode_subsequences is this call with 2 for every crop: one encoder, not two. */
+int mdjpeg_encode_subsequences_sampled(const int16_t* const* coefs, const int32_t* widths, const int32_t* heights,
+                                       const int32_t* samplings, int n, int chunk_bytes, uint8_t* out, size_t capacity,
+                                       int64_t* offsets, int64_t* sizes, size_t* needed);
+int64_t mdjpeg_encode_sampled_bound(int32_t width, int32_t height, int32_t sampling);
 
 /* ---- Gaussian blur of rectangles (GPU: mdhip_blur_regions, include/mdhip.h) -------------------------------------------- */
 /* The host model of the GPU blur and the host leg of HIPDetector(blur=): Pillow's ImageFilter.GaussianBlur(radius) of

@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libmdhip.so')
 
 MDHIP_OK = 0
+MDHIP_EINVAL = -1
 MDHIP_ECAPACITY = -5
 MDHIP_EUNSUPPORTED = -4
 MDHIP_DTYPE_BF16 = 0
@@ -105,6 +106,10 @@ SYMBOLS = {
                                     C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), _P, C.c_int64, C.POINTER(C.c_int64),
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
     'mdhip_jpeg_encode_bound': (C.c_longlong, [C.c_int, C.c_int]),
+    'mdhip_jpeg_encode_sampled': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_uint16), _P, C.c_int64, C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
+    'mdhip_jpeg_encode_sampled_bound': (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     'mdhip_blur_regions': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_float, _P]),
     'mdhip_resample_lanczos': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int,

@@ -1,14 +1,18 @@
 """
 Privacy blurring of detections in written image copies, as the reference does it
 (postprocessing/separate_detections_into_folders.py --category_names_to_blur person: vis_utils.load_image, then
-visualization_utils.blur_detections -- per box crop, ImageFilter.GaussianBlur(40), paste -- then exif_preserving_save, which
-for an image that went through load_image's convert('RGB') is save(quality=85)), from an image that is in device memory
-already: the GPU blurs a copy of it (HipContext.blur_regions, Pillow's arithmetic bit for bit), encodes the whole copy
-(HipContext.jpeg_encode) and the host puts the file around the scan (jpeg_host.jfif_file).  No second read or decode of
-the source file, no blur and no encode on the host.
+visualization_utils.blur_detections -- per box crop, ImageFilter.GaussianBlur(40), paste -- then exif_preserving_save),
+from an image that is in device memory already: the GPU blurs a copy of it (HipContext.blur_regions, Pillow's arithmetic
+bit for bit), encodes the whole copy (HipContext.jpeg_encode) and the host puts the file around the scan
+(jpeg_host.jfif_file).  No second read or decode of the source file, no blur and no encode on the host.
 
-The files equal, byte for byte, what Image.save(name, quality=q) writes for Pillow's blurred pixels, with one stated
-difference: the EXIF block exif_preserving_save copies from the source file is not written.
+The files equal, byte for byte, what Image.save(name, quality=q) writes for Pillow's blurred pixels.  That is what the
+reference's exif_preserving_save(quality='keep') writes only where open_image made a NEW image -- an 'L' or 'RGBA' file, a
+file with an EXIF rotation -- and then with the source's EXIF block and COM segment, which are not written here.  For a plain
+RGB JPEG, which is what a camera trap writes, the opened image is still a JPEG to Pillow, and quality='keep' re-encodes with
+the source file's own quantisation tables and its own chroma sampling (4:4:4, 4:2:2 or 4:2:0), again with an EXIF APP1 segment
+and the source's COM segment: these files do NOT equal the reference's.  separate_detections.py reproduces them, on the
+device too (HipContext.jpeg_encode_sampled, jpeg_host.sampled_file); blur= keeps its behaviour.
 """
 
 from . import jpeg_host

@@ -4,11 +4,14 @@
 // jpeg_kernels.cpp (jpeg_dct.h).  Plain C++ and vector memory operations only.
 //
 // One launch grid per pass for the WHOLE batch; work is mapped by block (or chunk) number across all crops, the crop found
-// by a binary search over the crops' first blocks, so a 1 x 1 crop is six lanes of a workgroup it shares with its
-// neighbours and a 700 x 500 crop is 8448 lanes over 33 workgroups:
+// by a binary search over the crops' first blocks, so a 1 x 1 crop at 4:2:0 is six lanes of a workgroup it shares with its
+// neighbours and a 700 x 500 crop is 8448 lanes over 33 workgroups.  The blocks of an MCU and what each of them is are the
+// crop's own (MdjEncCrop::hs, vs, per_mcu), and so is its pair of quantisation tables (MdjEncCrop::table):
 //
 //   jpeg_enc_coef_kernel    8 lanes per 8x8 block, 32 blocks per workgroup: colour conversion of the block's pixels (edges
-//                           replicated, chroma down-sampled h2v2), "islow" forward DCT rows -> LDS -> columns, quantisation;
+//                           replicated, chroma down-sampled as the crop's sampling says: jcsample.c fullsize_downsample,
+//                           h2v1_downsample or h2v2_downsample), "islow" forward DCT rows -> LDS -> columns, quantisation
+//                           by the crop's own pair of tables;
 //                           int16 coefficients in MCU order, a lane stores its column with one 16-byte store
 //   jpeg_enc_bits_kernel    lane = block: DC difference (a local read), zig-zag walk -> the block's bit length
 //   scan (three kernels)    exclusive prefix sum over all blocks; a crop's own offsets are differences to its first block's
@@ -36,7 +39,8 @@ constexpr int LANES = 256;               // workgroup of the lane-per-block / la
 constexpr int SCAN_ITEMS = 4;            // values a thread of the scan kernels takes
 constexpr int SCAN_TILE = LANES * SCAN_ITEMS;
 
-__global__ __launch_bounds__(COEF_BLOCKS * 8) void jpeg_enc_coef_kernel(const JpegEncDev d) {
+// (8 waves a SIMD, as before the sampling became data: the three chroma branches must not cost the kernel a wave)
+__global__ __launch_bounds__(COEF_BLOCKS * 8) __attribute__((amdgpu_waves_per_eu(8, 8))) void jpeg_enc_coef_kernel(const JpegEncDev d) {
     __shared__ int lds[COEF_BLOCKS][8][9];
     const int t = threadIdx.x;
     const int lb = t >> 3, r = t & 7;
@@ -44,19 +48,23 @@ __global__ __launch_bounds__(COEF_BLOCKS * 8) void jpeg_enc_coef_kernel(const Jp
     const bool active = g < d.blocks;
     bool real = false;
     int chroma = 0;
+    const uint16_t* quant = d.quant;                                      // the crop's pair of tables
     int v[8], ws[8];
     if (active) {
         const MdjEncCrop& c = d.crops[mdj_enc_locate<&MdjEncCrop::block0>(d.crops, d.n, g)];
         const long long local = g - c.block0;
-        const long long m = local / 6;
-        const int k = int(local % 6);
-        const int mx = int(m % c.mcus_x), my = int(m / c.mcus_x);
+        const int hs = c.hs, vs = c.vs, per_mcu = c.per_mcu, luma = hs * vs;
+        const unsigned m = unsigned(local) / unsigned(per_mcu);           // (a crop has at most 2^21 blocks)
+        const int k = int(unsigned(local) - m * unsigned(per_mcu));
+        const int my = int(m / unsigned(c.mcus_x)), mx = int(m - unsigned(my) * unsigned(c.mcus_x));
         const int W = c.width, H = c.height;
+        quant = d.quant + c.table * 128;
         real = mdj_enc_block_real(c, m, k);
-        if (k < 4) {
+        if (k < luma) {
             if (real) {                                                   // row r of a luma block
-                const int sy = min((my * 2 + (k >> 1)) * 8 + r, H - 1);
-                const int x0 = (mx * 2 + (k & 1)) * 8;
+                const int kx = hs == 2 ? k & 1 : 0, ky = hs == 2 ? k >> 1 : k;
+                const int sy = min((my * vs + ky) * 8 + r, H - 1);
+                const int x0 = (mx * hs + kx) * 8;
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     int y, cb, cr;
@@ -64,7 +72,29 @@ __global__ __launch_bounds__(COEF_BLOCKS * 8) void jpeg_enc_coef_kernel(const Jp
                     v[i] = y - 128;
                 }
             }
-        } else {                                                          // row r of a chroma block: 2 x 16 pixels
+        } else if (hs == 1) {                                             // row r of a chroma block, h1v1: 1 x 8 pixels
+            chroma = 1;
+            const int sy = min(my * 8 + r, H - 1);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {                                 // fullsize_downsample: the samples as they are
+                int y, cb, cr;
+                load_ycc(c.src, c.pitch, min(mx * 8 + i, W - 1), sy, y, cb, cr);
+                v[i] = (k == luma ? cb : cr) - 128;
+            }
+        } else if (vs == 1) {                                             // h2v1: 1 x 16 pixels
+            chroma = 1;
+            const int sy = min(my * 8 + r, H - 1);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int sx0 = min((mx * 8 + i) * 2, W - 1), sx1 = min((mx * 8 + i) * 2 + 1, W - 1);
+                int y, cb[2], cr[2];
+                load_ycc(c.src, c.pitch, sx0, sy, y, cb[0], cr[0]);
+                load_ycc(c.src, c.pitch, sx1, sy, y, cb[1], cr[1]);
+                const int bias = i & 1;                                   // h2v1_downsample: 0 in even output columns, 1 in odd ones
+                const int s = k == luma ? cb[0] + cb[1] : cr[0] + cr[1];
+                v[i] = int(unsigned(s + bias) >> 1) - 128;
+            }
+        } else {                                                          // h2v2: 2 x 16 pixels
             chroma = 1;
             const int ch = (H + 1) >> 1;
             const int cy = min(my * 8 + r, ch - 1);                       // below the image chroma repeats its last down-sampled row
@@ -78,7 +108,7 @@ __global__ __launch_bounds__(COEF_BLOCKS * 8) void jpeg_enc_coef_kernel(const Jp
                 load_ycc(c.src, c.pitch, sx0, sy1, y, cb[2], cr[2]);
                 load_ycc(c.src, c.pitch, sx1, sy1, y, cb[3], cr[3]);
                 const int bias = 1 + (i & 1);                             // h2v2_downsample: 1 in even output columns, 2 in odd ones
-                const int s = k == 4 ? cb[0] + cb[1] + cb[2] + cb[3] : cr[0] + cr[1] + cr[2] + cr[3];
+                const int s = k == luma ? cb[0] + cb[1] + cb[2] + cb[3] : cr[0] + cr[1] + cr[2] + cr[3];
                 v[i] = int(unsigned(s + bias) >> 2) - 128;
             }
         }
@@ -98,7 +128,7 @@ __global__ __launch_bounds__(COEF_BLOCKS * 8) void jpeg_enc_coef_kernel(const Jp
         unsigned h[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const unsigned q = d.quant[chroma * 64 + i * 8 + r];
+            const unsigned q = quant[chroma * 64 + i * 8 + r];
             const unsigned mag = quant_magnitude(ws[i], q);
             h[i] = unsigned(ws[i] < 0 ? -int(mag) : int(mag)) & 0xffffu;
         }

@@ -3,17 +3,24 @@
 // stuffing chunk, compiled by both, so that the CPU suite and the host sanitizers exercise the very code the lanes run
 // (the arrangement of jpeg_subseq.h for the decoder).
 //
-// What is encoded: three components, 4:2:0, one interleaved scan without restart markers, the four example tables of the
-// standard (ITU-T T.81, K.3 - K.6) -- the scan Pillow / libjpeg-turbo write for Image.save(quality = q) of an RGB image.
+// What is encoded: three components, one interleaved scan without restart markers, the four example tables of the
+// standard (ITU-T T.81, K.3 - K.6) -- the scan Pillow / libjpeg-turbo write for Image.save(quality = q) of an RGB image, or
+// for save(qtables = ..., subsampling = ...).  The chroma sampling is a crop's own (MdjEncCrop::hs, vs: the luma sampling
+// factors; chroma has 1 x 1):
+//   h1v1  4:4:4  MCU  8 x 8   3 blocks  Y Cb Cr
+//   h2v1  4:2:2  MCU 16 x 8   4 blocks  Y0 Y1 Cb Cr
+//   h2v2  4:2:0  MCU 16 x 16  6 blocks  Y00 Y01 Y10 Y11 Cb Cr
+// Block k of an MCU is luma block (k % hs, k / hs) of the MCU for k < hs * vs, then Cb, then Cr.
 //
-// Coefficients: the blocks of a crop in MCU ORDER (Y00 Y01 Y10 Y11 Cb Cr of MCU 0, then MCU 1 ...), each block TRANSPOSED
+// Coefficients: the blocks of a crop in MCU ORDER (the blocks of MCU 0, then MCU 1 ...), each block TRANSPOSED
 // (value (v, u) of the natural order at u * 8 + v: the column pass of the forward DCT leaves a lane one column, which it
 // stores with one 16-byte store).  A luma block right of or below the component's own blocks only fills up its MCU: libjpeg
 // gives it the DC of the block in front of it and no AC, so its DC difference is 0 and it costs an all-zero block's bits;
 // what is stored for it is never read.
 //
 // Passes (each a loop over "lanes" in the host model, a launch grid over the whole batch on the device):
-//   bits     lane = block: DC difference to the previous block of the component (chroma: 6 blocks back; luma: 1 to 6), zig-zag walk, run/size symbols with ZRL
+//   bits     lane = block: DC difference to the previous block of the component (chroma: one MCU back; luma: the last of
+//            the component's own blocks in front of it), zig-zag walk, run/size symbols with ZRL
 //            and EOB -> the block's bit length                                                       (mdj_enc_block, counting)
 //   scan     exclusive prefix sum of the lengths; a block's offset within its crop is the difference to the crop's first
 //   write    lane = block: the same walk, now writing at the offset into a zeroed buffer of 32-bit words; words a block
@@ -48,6 +55,11 @@
 #define MDJ_ENC_ERR_DC 1u                // a DC difference beyond category 11
 #define MDJ_ENC_ERR_AC 2u                // an AC coefficient beyond category 10 (8-bit samples cannot give one)
 
+// chroma sampling of a crop, numbered as Pillow's `subsampling`
+#define MDJ_ENC_H1V1 0
+#define MDJ_ENC_H2V1 1
+#define MDJ_ENC_H2V2 2
+
 // code and length of every symbol: table 0 DC luma, 1 AC luma, 2 DC chroma, 3 AC chroma; length 0 = not a symbol
 struct MdjEncTables {
     uint16_t code[4][256];
@@ -63,16 +75,36 @@ struct MdjEncCrop {
     int64_t chunk0;                      // its first stuffing chunk
     int32_t width, height;
     int32_t mcus_x, mcus_y;
+    int32_t hs, vs;                      // luma blocks of an MCU across and down: 1 1, 2 1 or 2 2
+    int32_t per_mcu;                     // blocks of an MCU: hs * vs + 2
+    int32_t table;                       // its pair of quantisation tables: quant[table][2][64] (the device's)
 };
 
-MDJ_HD int64_t mdj_enc_blocks(int width, int height) { return int64_t((width + 15) / 16) * ((height + 15) / 16) * 6; }
+MDJ_HD bool mdj_enc_sampling_ok(int sampling) { return sampling >= MDJ_ENC_H1V1 && sampling <= MDJ_ENC_H2V2; }
+// width, height, sampling -> mcus_x, mcus_y, hs, vs, per_mcu of the crop
+MDJ_HD void mdj_enc_set_layout(MdjEncCrop& c, int width, int height, int sampling) {
+    c.width = width;
+    c.height = height;
+    c.hs = sampling == MDJ_ENC_H1V1 ? 1 : 2;
+    c.vs = sampling == MDJ_ENC_H2V2 ? 2 : 1;
+    c.per_mcu = c.hs * c.vs + 2;
+    c.mcus_x = (width + 8 * c.hs - 1) / (8 * c.hs);
+    c.mcus_y = (height + 8 * c.vs - 1) / (8 * c.vs);
+}
+MDJ_HD int64_t mdj_enc_blocks(int width, int height, int sampling = MDJ_ENC_H2V2) {
+    MdjEncCrop c;
+    mdj_enc_set_layout(c, width, height, sampling);
+    return int64_t(c.mcus_x) * c.mcus_y * c.per_mcu;
+}
 // 32-bit words of a crop's region of the bit buffer: every block at its bound, and the padding bits
 MDJ_HD int64_t mdj_enc_region_words(int64_t blocks) { return blocks * MDJ_ENC_BLOCK_WORDS + 1; }
 MDJ_HD int64_t mdj_enc_region_chunks(int64_t blocks, int chunk_bytes) {
     return (mdj_enc_region_words(blocks) * 4 + chunk_bytes - 1) / chunk_bytes;
 }
 // what a crop's scan can take at most: every byte of the region an FF
-MDJ_HD int64_t mdj_enc_bound_bytes(int width, int height) { return mdj_enc_region_words(mdj_enc_blocks(width, height)) * 8; }
+MDJ_HD int64_t mdj_enc_bound_bytes(int width, int height, int sampling = MDJ_ENC_H2V2) {
+    return mdj_enc_region_words(mdj_enc_blocks(width, height, sampling)) * 8;
+}
 
 // the standard's tables as DHT segments carry them: codes of each length, then the symbols
 static const uint8_t MDJ_ENC_STD_BITS[4][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0},
@@ -130,28 +162,30 @@ MDJ_HD int mdj_enc_locate(const MdjEncCrop* crops, int n, int64_t g) {
 
 // block k of MCU m is one of the component's own (chroma blocks always are)
 MDJ_HD bool mdj_enc_block_real(const MdjEncCrop& c, int64_t m, int k) {
-    if (k >= 4) return true;
-    const int bx = int(m % c.mcus_x) * 2 + (k & 1), by = int(m / c.mcus_x) * 2 + (k >> 1);
+    if (k >= c.hs * c.vs) return true;
+    const int kx = c.hs == 2 ? k & 1 : 0, ky = c.hs == 2 ? k >> 1 : k;
+    const uint32_t my = uint32_t(m) / uint32_t(c.mcus_x), mx = uint32_t(m) - my * uint32_t(c.mcus_x);    // (at most 2^21 blocks a crop)
+    const int bx = int(mx) * c.hs + kx, by = int(my) * c.vs + ky;
     return bx < (c.width + 7) / 8 && by < (c.height + 7) / 8;
 }
 
 // DC difference of block `lb` of the crop (coef: the crop's first block)
 MDJ_HD int mdj_enc_dc_diff(const int16_t* coef, const MdjEncCrop& c, int64_t lb) {
-    const int64_t m = lb / 6;
-    const int k = int(lb % 6);
+    const int64_t m = int64_t(uint32_t(lb) / uint32_t(c.per_mcu));
+    const int k = int(lb - m * c.per_mcu);
     if (!mdj_enc_block_real(c, m, k)) return 0;
     const int cur = coef[lb * 64];
-    if (k >= 4) return m == 0 ? cur : cur - coef[(lb - 6) * 64];
+    if (k >= c.hs * c.vs) return m == 0 ? cur : cur - coef[(lb - c.per_mcu) * 64];
     // luma: the last block of the component's own in front of this one (block 0 of an MCU always is one)
     int64_t pm = m;
     int pk = k - 1;
     if (pk < 0) {
         if (m == 0) return cur;
         pm = m - 1;
-        pk = 3;
+        pk = c.hs * c.vs - 1;
     }
     while (!mdj_enc_block_real(c, pm, pk)) --pk;
-    return cur - coef[(pm * 6 + pk) * 64];
+    return cur - coef[(pm * c.per_mcu + pk) * 64];
 }
 
 MDJ_HD int mdj_enc_bit_length(unsigned v) { return v == 0 ? 0 : 32 - __builtin_clz(v); }
@@ -262,7 +296,9 @@ MDJ_HD uint32_t mdj_enc_lane_bits(const MdjEncCrop* crops, int n, const int16_t*
     const int64_t lb = g - cr.block0;
     const int16_t* base = coef + cr.block0 * 64;
     MdjEncCount count;
-    *err = mdj_enc_block(base + lb * 64, mdj_enc_dc_diff(base, cr, lb), mdj_enc_block_real(cr, lb / 6, int(lb % 6)), t, lb % 6 >= 4, count);
+    const int64_t m = int64_t(uint32_t(lb) / uint32_t(cr.per_mcu));
+    const int k = int(lb - m * cr.per_mcu);
+    *err = mdj_enc_block(base + lb * 64, mdj_enc_dc_diff(base, cr, lb), mdj_enc_block_real(cr, m, k), t, k >= cr.hs * cr.vs, count);
     *crop = c;
     return count.bits;
 }
@@ -283,7 +319,9 @@ MDJ_HD void mdj_enc_lane_write(const MdjEncCrop* crops, int n, const int16_t* co
     const int64_t lb = g - cr.block0;
     const int16_t* base = coef + cr.block0 * 64;
     MdjEncWriter w(bitbuf + cr.word0, int64_t(offsets[g] - offsets[cr.block0]));
-    mdj_enc_block(base + lb * 64, mdj_enc_dc_diff(base, cr, lb), mdj_enc_block_real(cr, lb / 6, int(lb % 6)), t, lb % 6 >= 4, w);
+    const int64_t m = int64_t(uint32_t(lb) / uint32_t(cr.per_mcu));
+    const int k = int(lb - m * cr.per_mcu);
+    mdj_enc_block(base + lb * 64, mdj_enc_dc_diff(base, cr, lb), mdj_enc_block_real(cr, m, k), t, k >= cr.hs * cr.vs, w);
     if (g + 1 == crops[c + 1].block0) {                              // the crop's last block fills the last byte with 1-bits
         const int pad = int((8 - (mdj_enc_crop_bits(crops, c, offsets) & 7)) & 7);
         if (pad) w.put((1u << pad) - 1u, pad);

@@ -590,10 +590,14 @@ int mdjpeg_decode_subsequences(const uint8_t* data, size_t size, int subseq_bits
     return MDJPEG_OK;
 }
 
-int mdjpeg_encode_subsequences(const int16_t* const* coefs, const int32_t* widths, const int32_t* heights, int n, int chunk_bytes,
-                               uint8_t* out, size_t capacity, int64_t* offsets, int64_t* sizes, size_t* needed) {
+// mdjpeg_encode_subsequences (samplings NULL: h2v2 for every crop) and mdjpeg_encode_subsequences_sampled
+static int encode_subsequences(const int16_t* const* coefs, const int32_t* widths, const int32_t* heights, const int32_t* samplings, int n,
+                               int chunk_bytes, uint8_t* out, size_t capacity, int64_t* offsets, int64_t* sizes, size_t* needed) {
     if (!coefs || !widths || !heights || !offsets || !sizes || !needed || n < 1 || chunk_bytes < MDJ_ENC_MIN_CHUNK || (!out && capacity))
         return MDJPEG_EINVAL;
+    if (samplings)
+        for (int i = 0; i < n; ++i)
+            if (!mdj_enc_sampling_ok(samplings[i])) return MDJPEG_EINVAL;
     // the batch as the device lays it out: crops one behind the other in block order, bit buffer regions and chunks at their bounds
     std::vector<MdjEncCrop> crops(size_t(n) + 1);
     int64_t blocks = 0, words = 0, chunks = 0;
@@ -605,11 +609,9 @@ int mdjpeg_encode_subsequences(const int16_t* const* coefs, const int32_t* width
         c.chunk0 = chunks;
         if (i == n) break;
         if (!coefs[i] || widths[i] < 1 || heights[i] < 1 || widths[i] > 65535 || heights[i] > 65535) return MDJPEG_EINVAL;
-        c.width = widths[i];
-        c.height = heights[i];
-        c.mcus_x = (widths[i] + 15) / 16;
-        c.mcus_y = (heights[i] + 15) / 16;
-        const int64_t nb = mdj_enc_blocks(widths[i], heights[i]);
+        const int sampling = samplings ? samplings[i] : MDJ_ENC_H2V2;
+        mdj_enc_set_layout(c, widths[i], heights[i], sampling);
+        const int64_t nb = mdj_enc_blocks(widths[i], heights[i], sampling);
         if (nb > MDJ_ENC_MAX_BLOCKS) return MDJPEG_EINVAL;
         blocks += nb;
         words += mdj_enc_region_words(nb);
@@ -620,13 +622,14 @@ int mdjpeg_encode_subsequences(const int16_t* const* coefs, const int32_t* width
     for (int i = 0; i < n; ++i) {
         const MdjEncCrop& c = crops[size_t(i)];
         const int64_t mcus = int64_t(c.mcus_x) * c.mcus_y;
-        const int16_t* plane[3] = {coefs[i], coefs[i] + mcus * 4 * 64, coefs[i] + mcus * 5 * 64};
+        const int luma = c.hs * c.vs;
+        const int16_t* plane[3] = {coefs[i], coefs[i] + mcus * luma * 64, coefs[i] + mcus * (luma + 1) * 64};
         for (int64_t m = 0; m < mcus; ++m) {
             const int mx = int(m % c.mcus_x), my = int(m / c.mcus_x);
-            for (int k = 0; k < 6; ++k) {
-                const int16_t* src = k < 4 ? plane[0] + ((int64_t(my) * 2 + (k >> 1)) * (c.mcus_x * 2) + mx * 2 + (k & 1)) * 64
-                                           : plane[k - 3] + m * 64;
-                int16_t* dst = coef.data() + (c.block0 + m * 6 + k) * 64;
+            for (int k = 0; k < c.per_mcu; ++k) {
+                const int16_t* src = k < luma ? plane[0] + ((int64_t(my) * c.vs + k / c.hs) * (c.mcus_x * c.hs) + mx * c.hs + k % c.hs) * 64
+                                              : plane[k - luma + 1] + m * 64;
+                int16_t* dst = coef.data() + (c.block0 + m * c.per_mcu + k) * 64;
                 for (int j = 0; j < 64; ++j) dst[((j & 7) << 3) | (j >> 3)] = src[j];
             }
         }
@@ -661,9 +664,26 @@ int mdjpeg_encode_subsequences(const int16_t* const* coefs, const int32_t* width
     return *needed > capacity ? MDJPEG_ECAPACITY : MDJPEG_OK;
 }
 
+int mdjpeg_encode_subsequences(const int16_t* const* coefs, const int32_t* widths, const int32_t* heights, int n, int chunk_bytes,
+                               uint8_t* out, size_t capacity, int64_t* offsets, int64_t* sizes, size_t* needed) {
+    return encode_subsequences(coefs, widths, heights, nullptr, n, chunk_bytes, out, capacity, offsets, sizes, needed);
+}
+
+int mdjpeg_encode_subsequences_sampled(const int16_t* const* coefs, const int32_t* widths, const int32_t* heights,
+                                       const int32_t* samplings, int n, int chunk_bytes, uint8_t* out, size_t capacity,
+                                       int64_t* offsets, int64_t* sizes, size_t* needed) {
+    if (!samplings) return MDJPEG_EINVAL;
+    return encode_subsequences(coefs, widths, heights, samplings, n, chunk_bytes, out, capacity, offsets, sizes, needed);
+}
+
 int64_t mdjpeg_encode_bound(int32_t width, int32_t height) {
     if (width < 1 || height < 1 || width > 65535 || height > 65535) return -1;
     return mdj_enc_bound_bytes(width, height);
+}
+
+int64_t mdjpeg_encode_sampled_bound(int32_t width, int32_t height, int32_t sampling) {
+    if (width < 1 || height < 1 || width > 65535 || height > 65535 || !mdj_enc_sampling_ok(sampling)) return -1;
+    return mdj_enc_bound_bytes(width, height, sampling);
 }
 
 // the rectangles of mdjpeg_blur_regions / mdjpeg_blur_regions_chunked, one after the other; lds_bytes 0: every row in one piece
@@ -1087,16 +1107,18 @@ int main(int argc, char** argv) {
         if (rc == MDJPEG_OK) {
             int16_t* coef = new int16_t[size_t(info.coef_count)];
             rc = mdjpeg_decode(exact, bytes.size(), &info, coef, size_t(info.coef_count));
-            if (rc == MDJPEG_OK && info.components == 3 && info.h_samp[0] == 2 && info.v_samp[0] == 2) {
+            const int sampling = info.h_samp[0] == 1 && info.v_samp[0] == 1 ? 0 : info.h_samp[0] == 2 && info.v_samp[0] == 1 ? 1
+                                 : info.h_samp[0] == 2 && info.v_samp[0] == 2 ? 2 : -1;
+            if (rc == MDJPEG_OK && info.components == 3 && sampling >= 0) {
                 // and back: the host model of the GPU entropy ENCODER on these coefficients, output buffers of the exact size
                 const int16_t* planes = coef;
                 for (int chunk : {1, 3, 64}) {
                     int64_t off, size;
                     size_t need = 0;
-                    int re = mdjpeg_encode_subsequences(&planes, &info.width, &info.height, 1, chunk, nullptr, 0, &off, &size, &need);
+                    int re = mdjpeg_encode_subsequences_sampled(&planes, &info.width, &info.height, &sampling, 1, chunk, nullptr, 0, &off, &size, &need);
                     if (re == MDJPEG_ECAPACITY) {
                         uint8_t* scan = new uint8_t[need];
-                        re = mdjpeg_encode_subsequences(&planes, &info.width, &info.height, 1, chunk, scan, need, &off, &size, &need);
+                        re = mdjpeg_encode_subsequences_sampled(&planes, &info.width, &info.height, &sampling, 1, chunk, scan, need, &off, &size, &need);
                         delete[] scan;
                     }
                     if (re != MDJPEG_OK && re != MDJPEG_ECORRUPT) { printf("%s: encoding at chunk %d gives %d\n", argv[i], chunk, re); return 4; }

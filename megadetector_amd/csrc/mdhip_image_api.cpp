@@ -433,15 +433,26 @@ long long mdhip_jpeg_encode_bound(int width, int height) {
     return mdj_enc_bound_bytes(width, height);
 }
 
-int mdhip_jpeg_encode(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
-                      const int64_t* pitches, int n, const uint16_t quant_luma[64], const uint16_t quant_chroma[64], uint8_t* out,
-                      int64_t capacity, int64_t* offsets, int64_t* sizes, int64_t* needed, void* hip_stream) {
-    if (!ctx) return MDHIP_EINVAL;
-    if (!windows || !widths || !heights || !pitches || !quant_luma || !quant_chroma || !offsets || !sizes || !needed)
-        return fail(ctx, MDHIP_EINVAL, "windows/widths/heights/pitches/quant_luma/quant_chroma/offsets/sizes/needed is NULL");
+long long mdhip_jpeg_encode_sampled_bound(int width, int height, int sampling) {
+    if (width < 1 || height < 1 || width > 65535 || height > 65535 || !mdj_enc_sampling_ok(sampling)) return -1;
+    return mdj_enc_bound_bytes(width, height, sampling);
+}
+
+namespace {
+
+// mdhip_jpeg_encode and mdhip_jpeg_encode_sampled.  samplings NULL: h2v2 for every window; quant: n_tables pairs
+// [luma 64][chroma 64], window i takes pair i when there are n of them and pair 0 when there is one.
+int jpeg_encode_windows(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
+                        const int64_t* pitches, const int32_t* samplings, int n, const uint16_t* quant, int n_tables, uint8_t* out,
+                        int64_t capacity, int64_t* offsets, int64_t* sizes, int64_t* needed, void* hip_stream) {
     if (n < 1) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
     if (capacity < 0 || (capacity > 0 && !out)) return fail(ctx, MDHIP_EINVAL, "capacity %lld with out %p", (long long)capacity, (void*)out);
-    if (int rc = check_quant_tables(ctx, quant_luma, quant_chroma)) return rc;
+    for (int t = 0; t < n_tables; ++t)
+        if (int rc = check_quant_tables(ctx, quant + 128 * (size_t)t, quant + 128 * (size_t)t + 64)) return rc;
+    if (samplings)
+        for (int i = 0; i < n; ++i)
+            if (!mdj_enc_sampling_ok(samplings[i]))
+                return fail(ctx, MDHIP_EINVAL, "window %d: sampling %d is none of h1v1 (0), h2v1 (1), h2v2 (2)", i, samplings[i]);
     hipStream_t s = (hipStream_t)hip_stream;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (capacity > 0 && !is_device_ptr(out)) return fail(ctx, MDHIP_EINVAL, "host pointer -- out must be device memory");
@@ -458,14 +469,13 @@ int mdhip_jpeg_encode(mdhip_ctx* ctx, const uint8_t* const* windows, const int32
         const int w = widths[i], h = heights[i];
         if (int rc = check_window(ctx, "window", i, w, h, pitches[i])) return rc;
         if (!windows[i] || !is_device_ptr(windows[i])) return fail(ctx, MDHIP_EINVAL, "window %d: NULL or a host pointer -- windows must be device memory", i);
-        const long long nb = mdj_enc_blocks(w, h);
+        const int sampling = samplings ? samplings[i] : MDJ_ENC_H2V2;
+        const long long nb = mdj_enc_blocks(w, h, sampling);
         if (nb > MDJ_ENC_MAX_BLOCKS) return fail(ctx, MDHIP_EINVAL, "window %d: %dx%d is more than %lld blocks", i, w, h, (long long)MDJ_ENC_MAX_BLOCKS);
         c.src = windows[i];
         c.pitch = pitches[i];
-        c.width = w;
-        c.height = h;
-        c.mcus_x = (w + 15) / 16;
-        c.mcus_y = (h + 15) / 16;
+        mdj_enc_set_layout(c, w, h, sampling);
+        c.table = n_tables == 1 ? 0 : i;
         blocks += nb;
         words += mdj_enc_region_words(nb);
         chunks += mdj_enc_region_chunks(nb, chunk_bytes);
@@ -474,7 +484,7 @@ int mdhip_jpeg_encode(mdhip_ctx* ctx, const uint8_t* const* windows, const int32
     ScratchLayout lay;
     const size_t o_crops = lay.take(sizeof(MdjEncCrop) * ((size_t)n + 1));
     const size_t o_tables = lay.take(sizeof(MdjEncTables));
-    const size_t o_quant = lay.take(256);
+    const size_t o_quant = lay.take(256 * (size_t)n_tables);
     const size_t upload_bytes = lay.size;
     const size_t o_status = lay.take(4 * (size_t)n);
     const size_t o_bitbuf = lay.take(4 * (size_t)words);
@@ -493,8 +503,7 @@ int mdhip_jpeg_encode(mdhip_ctx* ctx, const uint8_t* const* windows, const int32
     MdjEncTables tables;
     mdj_enc_build_tables(tables);
     memcpy(up.data() + o_tables, &tables, sizeof(tables));
-    memcpy(up.data() + o_quant, quant_luma, 128);
-    memcpy(up.data() + o_quant + 128, quant_chroma, 128);
+    memcpy(up.data() + o_quant, quant, 256 * (size_t)n_tables);
     // (the upload is from pageable memory: the copy has left `up` when the call returns)
     HIP_TRY(ctx, hipMemcpyAsync(base, up.data(), upload_bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemsetAsync(base + o_status, 0, zero_bytes, s));
@@ -533,6 +542,29 @@ int mdhip_jpeg_encode(mdhip_ctx* ctx, const uint8_t* const* windows, const int32
     if (*needed > capacity)
         return fail(ctx, MDHIP_ECAPACITY, "the scans take %lld bytes, the output buffer has %lld", (long long)*needed, (long long)capacity);
     return MDHIP_OK;
+}
+
+}  // namespace
+
+int mdhip_jpeg_encode(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
+                      const int64_t* pitches, int n, const uint16_t quant_luma[64], const uint16_t quant_chroma[64], uint8_t* out,
+                      int64_t capacity, int64_t* offsets, int64_t* sizes, int64_t* needed, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!windows || !widths || !heights || !pitches || !quant_luma || !quant_chroma || !offsets || !sizes || !needed)
+        return fail(ctx, MDHIP_EINVAL, "windows/widths/heights/pitches/quant_luma/quant_chroma/offsets/sizes/needed is NULL");
+    uint16_t pair[128];
+    memcpy(pair, quant_luma, 128);
+    memcpy(pair + 64, quant_chroma, 128);
+    return jpeg_encode_windows(ctx, windows, widths, heights, pitches, nullptr, n, pair, 1, out, capacity, offsets, sizes, needed, hip_stream);
+}
+
+int mdhip_jpeg_encode_sampled(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
+                              const int64_t* pitches, const int32_t* samplings, int n, const uint16_t* quant, uint8_t* out,
+                              int64_t capacity, int64_t* offsets, int64_t* sizes, int64_t* needed, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!windows || !widths || !heights || !pitches || !samplings || !quant || !offsets || !sizes || !needed)
+        return fail(ctx, MDHIP_EINVAL, "windows/widths/heights/pitches/samplings/quant/offsets/sizes/needed is NULL");
+    return jpeg_encode_windows(ctx, windows, widths, heights, pitches, samplings, n, quant, n, out, capacity, offsets, sizes, needed, hip_stream);
 }
 
 int mdhip_blur_regions(mdhip_ctx* ctx, uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches,

@@ -578,7 +578,7 @@ int jpeg_entropy_dc_chunk();
 struct JpegEncDev {
     const ::MdjEncCrop*   crops;  // [n + 1] the crops (jpeg_encode.h); the last entry carries the totals
     const ::MdjEncTables* tables; // the standard's four tables as codes and lengths
-    const uint16_t* quant;        // [2][64] luma, chroma; natural order
+    const uint16_t* quant;        // [pairs][2][64] luma, chroma; natural order; crop c takes pair crops[c].table
     int16_t*  coef;               // [blocks][64] quantised coefficients, MCU order, blocks transposed; 16-byte aligned
     uint32_t* len;                // [blocks] bit length of each block
     uint64_t* off;                // [blocks + 1] exclusive prefix sum of len

@@ -1,0 +1,77 @@
+"""
+Files of a folder as RGB pixels in device memory, each decoded once: what the tools that work on written results files share
+(rde_review.py, separate_detections.py).  A baseline JPEG the GPU's decoder takes goes through mdhip_jpeg_entropy_decode and
+mdhip_jpeg_reconstruct on a context that needs no model -- one call each for a whole chunk of files -- and comes out as the
+pixels the reference's load_image gives, EXIF rotation included; every other file, and a JPEG the decoder flags, is decoded
+by PIL and uploaded.
+"""
+
+import os
+
+
+def probe(path, keep_data=False):
+    """What the device leg needs of a file before any pixel is decoded: {'size': (width, height) as open_image gives them,
+    'scan': a jpeg_host.ScanImage when the GPU's decoder takes the file, else None}; with keep_data also 'data', the bytes of
+    a file Pillow calls a JPEG (else None).  Raises what opening it raises."""
+    from . import jpeg_host
+    from .feed import open_for_coefficients
+    image, rotation = open_for_coefficients(path)
+    size = (image.size[1], image.size[0]) if rotation in (90, 270) else image.size
+    scan = data = None
+    if image.format == 'JPEG':
+        with open(path, 'rb') as f:
+            data = f.read()
+        if jpeg_host.parse(data).supported:
+            rc, scan, _ = jpeg_host.ScanImage.from_bytes(data, rotation)
+            if rc != jpeg_host.MDJPEG_OK:
+                scan = None
+    out = {'size': tuple(size), 'scan': scan}
+    if keep_data:
+        out['data'] = data
+    return out
+
+
+def decode_chunk(ctx, torch, device, image_base, files, probes, counts, via_pil=None):
+    """file -> flat uint8 device tensor of its RGB pixels, each file decoded once: the JPEGs the decoder takes through
+    mdhip_jpeg_entropy_decode and mdhip_jpeg_reconstruct (one call each for the chunk), every other file -- and a JPEG the
+    decoder flags -- through PIL and an upload.  files are relative to image_base; probes: file -> probe(); counts gets
+    'files_decoded_gpu' and 'files_decoded_pil' added to; via_pil: a set that receives the files PIL decoded.
+    -> (pixels, the files PIL could not decode either)"""
+    import numpy as np
+    from .feed import load_image
+    pixels, failed = {}, set()
+    scans = [f for f in files if probes[f]['scan'] is not None]
+    if scans:
+        images = [probes[f]['scan'] for f in scans]
+        scan_offs, coef_offs, nbytes, nvals = [], [], 0, 0
+        for im in images:
+            scan_offs.append(nbytes)
+            nbytes += (im.nbytes + 255) // 256 * 256 + 256
+            coef_offs.append(nvals)
+            nvals += (im.coef_count + 127) // 128 * 128
+        host = np.zeros(nbytes, dtype=np.uint8)
+        for im, off in zip(images, scan_offs):
+            host[off:off + im.nbytes] = im.scan_bytes
+        compressed = torch.from_numpy(host).to(device)
+        coefs = torch.empty(max(nvals, 1), dtype=torch.int16, device=device)
+        status = ctx.jpeg_entropy_decode(images, [compressed.data_ptr() + o for o in scan_offs], [coefs.data_ptr() + 2 * o for o in coef_offs])
+        clean = [k for k, st in enumerate(status) if st == 0]
+        if clean:
+            outs = [torch.empty(int(np.prod(images[k].shape)), dtype=torch.uint8, device=device) for k in clean]
+            ctx.jpeg_reconstruct([images[k].coefficient_image() for k in clean], [coefs.data_ptr() + 2 * coef_offs[k] for k in clean],
+                                 [t.data_ptr() for t in outs])
+            for k, t in zip(clean, outs):
+                pixels[scans[k]] = t
+            counts['files_decoded_gpu'] += len(clean)
+    for f in files:
+        if f not in pixels:
+            try:
+                array = np.ascontiguousarray(np.asarray(load_image(os.path.join(image_base, f))))
+            except Exception:
+                failed.add(f)                                           # what needs it goes to the caller's host leg, which fails as PIL does
+                continue
+            pixels[f] = torch.from_numpy(array.reshape(-1).copy()).to(device)
+            counts['files_decoded_pil'] += 1
+            if via_pil is not None:
+                via_pil.add(f)
+    return pixels, failed

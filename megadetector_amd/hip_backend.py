@@ -385,6 +385,40 @@ class HipContext:
             self._check(rc, 'mdhip_jpeg_encode')
         return rc == 0, np.array(offs[:n], dtype=np.int64), np.array(lens[:n], dtype=np.int64), int(need.value)
 
+    def jpeg_encode_sampled(self, ptrs, sizes, pitches, samplings, quants, out_ptr, capacity, stream=0):
+        """
+        jpeg_encode with each window's own chroma sampling and quantisation tables (include/mdhip.h:
+        mdhip_jpeg_encode_sampled): byte for byte the scans of Image.save(qtables=[luma, chroma], subsampling=sampling);
+        jpeg_host.sampled_file puts the file around a scan.
+        samplings: per window 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0), as Pillow's `subsampling`
+        quants: per window (luma, chroma), 64 entries of 1 .. 255 each, natural order
+        Everything else, and what is returned, as for jpeg_encode.
+        """
+        n = len(ptrs)
+        if not (len(sizes) == len(pitches) == len(samplings) == len(quants) == n):
+            raise ValueError('ptrs, sizes, pitches, samplings and quants must have one entry per window')
+        p, ws, hs, pt = _window_arrays(ptrs, sizes, pitches)
+        ss = (C.c_int32 * max(n, 1))(*[int(v) for v in samplings])
+        packed = np.zeros((max(n, 1), 2, 64), dtype=np.uint16)
+        for i, pair in enumerate(quants):
+            for k in (0, 1):
+                table = np.asarray(pair[k]).reshape(-1)
+                if table.size != 64 or table.min() < 0 or table.max() > 65535:
+                    raise ValueError('window {}: a quantisation table has 64 entries'.format(i))
+                packed[i, k] = table
+        offs, lens, need = (C.c_int64 * max(n, 1))(), (C.c_int64 * max(n, 1))(), C.c_int64(0)
+        rc = self.lib.mdhip_jpeg_encode_sampled(self.h, p, ws, hs, pt, ss, n, packed.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                C.c_void_p(int(out_ptr) if capacity else 0), int(capacity), offs, lens, C.byref(need),
+                                                C.c_void_p(stream))
+        if rc != _lib.MDHIP_ECAPACITY:
+            self._check(rc, 'mdhip_jpeg_encode_sampled')
+        return rc == 0, np.array(offs[:n], dtype=np.int64), np.array(lens[:n], dtype=np.int64), int(need.value)
+
+    @staticmethod
+    def jpeg_encode_sampled_bound(width, height, sampling):
+        """bytes the scan of a width x height window can take at the very most at that sampling (mdhip_jpeg_encode_sampled_bound)"""
+        return int(_lib.load().mdhip_jpeg_encode_sampled_bound(int(width), int(height), int(sampling)))
+
     @staticmethod
     def jpeg_encode_bound(width, height):
         """bytes the scan of a width x height window can take at the very most (mdhip_jpeg_encode_bound)"""

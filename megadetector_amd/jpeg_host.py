@@ -57,6 +57,10 @@ SYMBOLS = {
                                              C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                              C.POINTER(C.c_size_t)]),
     'mdjpeg_encode_bound': (C.c_int64, [C.c_int32, C.c_int32]),
+    'mdjpeg_encode_subsequences_sampled': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                     C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]),
+    'mdjpeg_encode_sampled_bound': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     'mdjpeg_blur_regions': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_float]),
     'mdjpeg_blur_regions_chunked': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int,
                                               C.c_float, C.c_int]),
@@ -274,6 +278,90 @@ def jfif_file(width, height, quality, scan_bytes):
     return b''.join((front, sof, back, bytes(scan_bytes), b'\xff\xd9'))
 
 
+#: chroma sampling numbered as Pillow's `subsampling` (include/mdhip.h MDHIP_JPEG_H1V1 ...) -> the luma sampling factors
+SAMPLING_FACTORS = {0: (1, 1), 1: (2, 1), 2: (2, 2)}
+
+
+def sampling_of(header):
+    """the sampling number of a JpegHeader (parse()), or None when it is none of 4:4:4, 4:2:2 and 4:2:0 of three components"""
+    if header.components != 3 or tuple(header.h_samp[1:]) != (1, 1) or tuple(header.v_samp[1:]) != (1, 1):
+        return None
+    for number, factors in SAMPLING_FACTORS.items():
+        if (header.h_samp[0], header.v_samp[0]) == factors:
+            return number
+    return None
+
+
+def sampled_file(width, height, quant_luma, quant_chroma, sampling, scan_bytes, exif=b'', comment=None):
+    """
+    The file Pillow writes around the scan `scan_bytes` (mdhip_jpeg_encode_sampled; mdjpeg_encode_subsequences_sampled) of a
+    width x height RGB image for save(f, 'JPEG', qtables=[quant_luma, quant_chroma], subsampling=sampling, exif=exif) -- and so
+    for save(f, exif=exif, quality='keep') of an image opened from a JPEG with these two tables and this sampling, which is
+    what the reference's exif_preserving_save does: SOI, APP0 (JFIF 1.01, no density unit, 1 x 1), APP1 with `exif` (the bytes
+    of Exif.tobytes(); none when empty), the COM segment Pillow copies from info['comment'] (none when empty or None), one DQT
+    segment per table with 8-bit entries in zig-zag order, SOF0 with the sampling factors, the standard's four DHT segments,
+    SOS, the scan, EOI.  The tables: 64 entries of 1 .. 255, natural order.
+    """
+    width, height = int(width), int(height)
+    if not (1 <= width <= 65535 and 1 <= height <= 65535):
+        raise ValueError('a JPEG is 1 .. 65535 pixels wide and high, got {} x {}'.format(width, height))
+    if sampling not in SAMPLING_FACTORS:
+        raise ValueError('sampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0), got {!r}'.format(sampling))
+    tables = [np.asarray(t, dtype=np.int64).reshape(-1) for t in (quant_luma, quant_chroma)]
+    if any(t.size != 64 or t.min() < 1 or t.max() > 255 for t in tables):
+        raise ValueError('a quantisation table has 64 entries of 1 .. 255')
+    exif, comment = bytes(exif or b''), bytes(comment or b'')
+    if len(exif) > 65533 or len(comment) > 65533:
+        raise ValueError('EXIF data or comment is too long for one segment')
+    zz = np.array(_ZIGZAG)
+    parts = [b'\xff\xd8', _segment(0xE0, b'JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00')]
+    if exif:
+        parts.append(_segment(0xE1, exif))
+    if comment:
+        parts.append(_segment(0xFE, comment))
+    parts += [_segment(0xDB, bytes((k,)) + t[zz].astype(np.uint8).tobytes()) for k, t in enumerate(tables)]
+    hs, vs = SAMPLING_FACTORS[sampling]
+    parts.append(_segment(0xC0, b'\x08' + height.to_bytes(2, 'big') + width.to_bytes(2, 'big') + b'\x03\x01' + bytes((hs << 4 | vs,))
+                          + b'\x00\x02\x11\x01\x03\x11\x01'))
+    parts += [_segment(0xC4, bytes((tc_th,)) + bytes(counts) + bytes(vals)) for tc_th, counts, vals in _STD_HUFFMAN]
+    parts += [_segment(0xDA, b'\x03\x01\x00\x02\x11\x03\x11\x00\x3f\x00'), bytes(scan_bytes), b'\xff\xd9']
+    return b''.join(parts)
+
+
+def keep_source(path, data=None):
+    """
+    What exif_preserving_save(image, target, quality='keep') takes from the source file of `image`, the image the reference's
+    open_image makes of `path`, read from the LAZILY opened file (Image.open parses headers and decodes no pixel): a dict with
+      'size', 'rotation'  of the image open_image gives, and the angle it turned the file's pixels by
+      'exif'              the bytes of getexif().tobytes() (Pillow writes them as APP1; never empty)
+      'comment'           info['comment'], the source's COM segment, or None
+      'format'            what Pillow calls the file
+      'keep'              True when open_image returns the opened image itself, so that Pillow still calls it a JPEG and
+                          re-encodes with the file's own tables and sampling; False when it made a new image (an 'L' or 'RGBA'
+                          file, an EXIF rotation) or Pillow calls the file something else ('MPO'): that one is saved with the
+                          quality-85 tables and 4:2:0
+      'quant', 'sampling' with keep and `data` (the file's bytes): [luma, chroma] and the sampling number for sampled_file,
+                          from mdjpeg_parse; None when the saved form is not one sampled_file writes -- not exactly two tables
+                          of 8-bit entries, table 0 for Y and table 1 for Cb and Cr, or a sampling other than 4:4:4, 4:2:2, 4:2:0.
+    Raises what opening the file raises.
+    """
+    from .feed import open_for_coefficients
+    image, rotation = open_for_coefficients(path)
+    out = {'size': (image.size[1], image.size[0]) if rotation in (90, 270) else tuple(image.size), 'rotation': rotation,
+           'exif': image.getexif().tobytes(), 'comment': image.info.get('comment'), 'format': image.format,
+           'keep': image.format == 'JPEG' and image.mode not in ('RGBA', 'L') and rotation == 0, 'quant': None, 'sampling': None}
+    if out['keep'] and data is not None:
+        header = parse(data)
+        tables = getattr(image, 'quantization', None) or {}
+        if header.rc == MDJPEG_OK and sorted(tables) == [0, 1] and all(len(tables[k]) == 64 and 1 <= min(tables[k]) and max(tables[k]) <= 255
+                                                                        for k in (0, 1)):
+            ql, qc = (np.array(tables[k], dtype=np.uint16) for k in (0, 1))          # natural order, as JpegHeader.quant
+            if header.components == 3 and (header.quant[0] == ql).all() and (header.quant[1] == qc).all() and (header.quant[2] == qc).all():
+                out['sampling'] = sampling_of(header)
+                out['quant'] = [ql, qc] if out['sampling'] is not None else None
+    return out
+
+
 def with_standard_tables(data):
     """
     The file for an abbreviated stream: Motion-JPEG frames usually carry no DHT segment, because the standard's example
@@ -334,11 +422,17 @@ def encode_bound(width, height):
     return int(load().mdjpeg_encode_bound(int(width), int(height)))
 
 
-def encode_subsequences(coefs, sizes, chunk_bytes=64, capacity=None):
+def encode_bound_sampled(width, height, sampling):
+    """the same for a chroma sampling (mdjpeg_encode_sampled_bound): 0 = h1v1, 1 = h2v1, 2 = h2v2, as Pillow's `subsampling`"""
+    return int(load().mdjpeg_encode_sampled_bound(int(width), int(height), int(sampling)))
+
+
+def encode_subsequences(coefs, sizes, chunk_bytes=64, capacity=None, samplings=None):
     """
     The host model of the GPU entropy encoder (mdjpeg_encode_subsequences), for tests.  coefs: per crop a flat int16 array in
     the layout of decode() for 4:2:0; sizes: (width, height) per crop.  Returns (rc, scans, needed, buffer): the scans as
     bytes objects when rc == MDJPEG_OK.  capacity None: as much as the call needs (asked for first).
+    samplings: per crop 0 = h1v1, 1 = h2v1, 2 = h2v2 (mdjpeg_encode_subsequences_sampled), coefs in that sampling's layout.
     """
     lib = load()
     n = len(coefs)
@@ -347,14 +441,22 @@ def encode_subsequences(coefs, sizes, chunk_bytes=64, capacity=None):
     ws = (C.c_int32 * n)(*[int(s[0]) for s in sizes])
     hs = (C.c_int32 * n)(*[int(s[1]) for s in sizes])
     offs, lens, need = (C.c_int64 * n)(), (C.c_int64 * n)(), C.c_size_t(0)
+    if samplings is None:
+        call = lambda out, cap: lib.mdjpeg_encode_subsequences(ptrs, ws, hs, n, int(chunk_bytes), out, cap, offs, lens, C.byref(need))
+    else:
+        if len(samplings) != n:
+            raise ValueError('one sampling per crop is needed')
+        ss = (C.c_int32 * n)(*[int(v) for v in samplings])
+        call = lambda out, cap: lib.mdjpeg_encode_subsequences_sampled(ptrs, ws, hs, ss, n, int(chunk_bytes), out, cap, offs, lens,
+                                                                        C.byref(need))
     if capacity is None:
-        rc = lib.mdjpeg_encode_subsequences(ptrs, ws, hs, n, int(chunk_bytes), None, 0, offs, lens, C.byref(need))
+        rc = call(None, 0)
         if rc != MDJPEG_ECAPACITY:
             return rc, None, int(need.value), None
         capacity = int(need.value)
     guard = 64
     buf = np.full(capacity + guard, 0xA5, dtype=np.uint8)
-    rc = lib.mdjpeg_encode_subsequences(ptrs, ws, hs, n, int(chunk_bytes), buf.ctypes.data, capacity, offs, lens, C.byref(need))
+    rc = call(buf.ctypes.data, capacity)
     if not (buf[capacity:] == 0xA5).all():
         raise AssertionError('mdjpeg_encode_subsequences wrote beyond its capacity')
     scans = [buf[offs[i]:offs[i] + lens[i]].tobytes() for i in range(n)] if rc == MDJPEG_OK else None

@@ -37,6 +37,7 @@ import traceback
 
 from . import preview as PV
 from . import repeat_detections as RD
+from .device_decode import decode_chunk, probe
 
 INDEX_NAME = 'detectionIndex.json'           # reference detection_index_file_name_base
 
@@ -274,66 +275,6 @@ def render_sample_host(location, filtering_dir, options):
 
 # ---- the device leg ----------------------------------------------------------------------------------------------------------
 
-def _probe(path):
-    """What the device leg needs of a file before any pixel is decoded: {'size': (width, height) as open_image gives them,
-    'scan': a jpeg_host.ScanImage when the GPU's decoder takes the file, else None}.  Raises what opening it raises."""
-    from . import jpeg_host
-    from .feed import open_for_coefficients
-    image, rotation = open_for_coefficients(path)
-    size = (image.size[1], image.size[0]) if rotation in (90, 270) else image.size
-    scan = None
-    if image.format == 'JPEG':
-        with open(path, 'rb') as f:
-            data = f.read()
-        if jpeg_host.parse(data).supported:
-            rc, scan, _ = jpeg_host.ScanImage.from_bytes(data, rotation)
-            if rc != jpeg_host.MDJPEG_OK:
-                scan = None
-    return {'size': tuple(size), 'scan': scan}
-
-
-def _decode_chunk(ctx, torch, device, options, files, probes, counts):
-    """file -> flat uint8 device tensor of its RGB pixels, each file decoded once: the JPEGs the decoder takes through
-    mdhip_jpeg_entropy_decode and mdhip_jpeg_reconstruct (one call each for the chunk), every other file -- and a JPEG the
-    decoder flags -- through PIL and an upload.  -> (pixels, the files PIL could not decode either)"""
-    import numpy as np
-    from .feed import load_image
-    pixels, failed = {}, set()
-    scans = [f for f in files if probes[f]['scan'] is not None]
-    if scans:
-        images = [probes[f]['scan'] for f in scans]
-        scan_offs, coef_offs, nbytes, nvals = [], [], 0, 0
-        for im in images:
-            scan_offs.append(nbytes)
-            nbytes += (im.nbytes + 255) // 256 * 256 + 256
-            coef_offs.append(nvals)
-            nvals += (im.coef_count + 127) // 128 * 128
-        host = np.zeros(nbytes, dtype=np.uint8)
-        for im, off in zip(images, scan_offs):
-            host[off:off + im.nbytes] = im.scan_bytes
-        compressed = torch.from_numpy(host).to(device)
-        coefs = torch.empty(max(nvals, 1), dtype=torch.int16, device=device)
-        status = ctx.jpeg_entropy_decode(images, [compressed.data_ptr() + o for o in scan_offs], [coefs.data_ptr() + 2 * o for o in coef_offs])
-        clean = [k for k, st in enumerate(status) if st == 0]
-        if clean:
-            outs = [torch.empty(int(np.prod(images[k].shape)), dtype=torch.uint8, device=device) for k in clean]
-            ctx.jpeg_reconstruct([images[k].coefficient_image() for k in clean], [coefs.data_ptr() + 2 * coef_offs[k] for k in clean],
-                                 [t.data_ptr() for t in outs])
-            for k, t in zip(clean, outs):
-                pixels[scans[k]] = t
-            counts['files_decoded_gpu'] += len(clean)
-    for f in files:
-        if f not in pixels:
-            try:
-                array = np.ascontiguousarray(np.asarray(load_image(os.path.join(options.imageBase, f))))
-            except Exception:
-                failed.add(f)                                           # the sheets that need it go to the host leg, which fails as PIL does
-                continue
-            pixels[f] = torch.from_numpy(array.reshape(-1).copy()).to(device)
-            counts['files_decoded_pil'] += 1
-    return pixels, failed
-
-
 class _Clock:
     """milliseconds per kind of call into counts['ms'], when write_review_folder(profile=True) put that dict there: the device
     is waited for before and after the timed calls, so a profiled run is slower than a plain one"""
@@ -382,7 +323,7 @@ def _render_group_device(ctx, torch, device, group, probes, filtering_dir, optio
     for files in chunks:
         counts['decode_chunks'] += 1
         with _Clock(torch, device, counts, 'decode'):
-            pixels, failed = _decode_chunk(ctx, torch, device, options, files, probes, counts)
+            pixels, failed = decode_chunk(ctx, torch, device, options.imageBase, files, probes, counts)
         refused.update(p['name'] for p in group if p['file'] in failed or any(t[0] in failed for t in p['tiles']))
         tiles = []
         for p in group:
@@ -483,7 +424,7 @@ def _render_device(flat, filtering_dir, options, ctx, device, counts):
 
     def size_of(f):
         if f not in probes:
-            probes[f] = _probe(os.path.join(options.imageBase, f))
+            probes[f] = probe(os.path.join(options.imageBase, f))
         return probes[f]['size']
 
     draw = draw_options(options)
