@@ -333,6 +333,42 @@ int mdhip_jpeg_encode_sampled(mdhip_ctx* ctx, const uint8_t* const* windows, con
                               int64_t capacity, int64_t* offsets, int64_t* sizes, int64_t* needed, void* hip_stream);
 long long mdhip_jpeg_encode_sampled_bound(int width, int height, int sampling);
 
+/* mdhip_jpeg_encode_sampled for copies in which only rectangles changed (boxes drawn, people blurred): the blocks of every
+ * MCU that no changed rectangle touches are the SOURCE file's own quantised coefficients, so outside the rectangles the copy
+ * is the source and not a re-encode of its decoded pixels.  No reference behaviour: the reference re-encodes the whole copy.
+ *   sources[i]   window i's source: coef, a DEVICE pointer, 16-byte aligned, to its quantised planes in the layout of
+ *                mdjpeg_decode (what mdhip_jpeg_entropy_decode leaves behind): plane c is [blocks_h[c]][blocks_w[c]][64],
+ *                natural order, Y then Cb then Cr one behind the other; blocks_w / blocks_h must be the window's whole MCUs for
+ *                its sampling: Y mcus_x * hs x mcus_y * vs, Cb and Cr mcus_x x mcus_y
+ *   rect_image, rects, n_rects   the changed rectangles: rectangle i lies in window rect_image[i] and is rects[4 i .. 4 i + 3] =
+ *                left, top, right, bottom in pixels, right and bottom exclusive (mdhip_blur_regions' convention)
+ *   status       HOST array of n values: 0, or 1 for a window whose merged blocks no baseline scan holds (below)
+ * Rules:
+ *   clipping     a rectangle is clipped to its window; one without area after that is dropped
+ *   changed MCU  the MCU is 8 hs x 8 vs pixels, (hs, vs) from the window's sampling; MCU (mx, my) is CHANGED iff some rectangle
+ *                of its window has left < (mx + 1) * 8 hs, right > mx * 8 hs, top < (my + 1) * 8 vs and bottom > my * 8 vs
+ *   blocks       of a changed MCU: exactly those mdhip_jpeg_encode_sampled computes from the window's pixels; of every other
+ *                MCU: the source's -- Y block (my * vs + dy, mx * hs + dx), Cb and Cr block (my, mx) -- value for value, the
+ *                dummy blocks of edge MCUs included (the scan codes a dummy luma block as libjpeg does whatever it holds)
+ *   entropy      the passes of mdhip_jpeg_encode_sampled over the merged blocks: DC differences run along the merged planes
+ * A source DC beside a recomputed one can differ by more than the 11 bits a baseline DC code holds: the decoder lets a
+ * source DC d through when (d * q0)^2 stays below its energy bound, which is at least 1029^2, a black block re-encodes to
+ * -1024 / q0, so with q0 = 1 a difference of 2053 > 2047 is legal input.  Such a window -- and one whose source planes hold
+ * an AC value beyond 10 bits, which no decoded file does -- gets status 1 and a scan of size 0; the scans of the other
+ * windows are what they are without it and lie one behind the other as always.  The caller re-encodes that copy whole.
+ * MDHIP_EINVAL, and nothing is launched: a host pointer or a misaligned one for the planes, plane sizes that are not the
+ * window's whole MCUs, a rectangle naming a window outside 0 .. n - 1, and everything mdhip_jpeg_encode_sampled refuses.
+ * Capacity, *needed, MDHIP_ECAPACITY (status is valid then too), streams and scratch as mdhip_jpeg_encode_sampled;
+ * mdhip_jpeg_encode_sampled_bound still bounds a window: a block's worst case does not depend on where its values came from. */
+typedef struct {
+    const int16_t* coef;
+    int32_t blocks_w[3], blocks_h[3];
+} mdhip_jpeg_source;
+int mdhip_jpeg_encode_kept(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
+                           const int64_t* pitches, const int32_t* samplings, int n, const uint16_t* quant,
+                           const mdhip_jpeg_source* sources, const int32_t* rect_image, const int32_t* rects, int n_rects, uint8_t* out,
+                           int64_t capacity, int64_t* offsets, int64_t* sizes, int64_t* needed, int32_t* status, void* hip_stream);
+
 /* Gaussian blur of rectangles of device images, IN PLACE (the reference blurs people in the image copies it writes:
  * postprocessing/separate_detections_into_folders.py --category_names_to_blur, visualization_utils.blur_detections: per box
  * crop -> ImageFilter.GaussianBlur(40) -> paste): every rectangle becomes, bit for bit, what Pillow's GaussianBlur(radius)

@@ -114,6 +114,16 @@ int mdjpeg_encode_subsequences_sampled(const int16_t* const* coefs, const int32_
                                        const int32_t* samplings, int n, int chunk_bytes, uint8_t* out, size_t capacity,
                                        int64_t* offsets, int64_t* sizes, size_t* needed);
 int64_t mdjpeg_encode_sampled_bound(int32_t width, int32_t height, int32_t sampling);
+/* The host model of mdhip_jpeg_encode_kept's merge, for ONE window, compiled from the header the kernel is compiled from
+ * (csrc/jpeg_keep.h): `planes` holds the window's re-encoded coefficients (the layout of mdjpeg_decode for `sampling`: whole
+ * MCUs, Y then Cb then Cr) and `source` the source file's in the same layout; every block of an MCU that none of the
+ * n_rects rectangles touches (rects: left, top, right, bottom in pixels, right and bottom exclusive; each is clipped to the
+ * window and dropped when nothing is left) is overwritten with the source's, dummy blocks included.  *status: 1 when the merged
+ * planes hold a DC difference beyond category 11 or an AC value beyond category 10 -- mdjpeg_encode_subsequences_sampled
+ * answers MDJPEG_ECORRUPT for them, the device gives that window a scan of size 0 -- else 0.  MDJPEG_EINVAL for a NULL
+ * pointer, a size outside 1 .. 65535, a sampling outside 0 .. 2 or n_rects < 0. */
+int mdjpeg_keep_merge(int16_t* planes, const int16_t* source, int32_t width, int32_t height, int32_t sampling, const int32_t* rects,
+                      int n_rects, int32_t* status);
 
 /* ---- Gaussian blur of rectangles (GPU: mdhip_blur_regions, include/mdhip.h) -------------------------------------------- */
 /* The host model of the GPU blur and the host leg of HIPDetector(blur=): Pillow's ImageFilter.GaussianBlur(radius) of

@@ -54,6 +54,10 @@ class mdhip_jpeg_image(C.Structure):
                 ('rotation', C.c_int32), ('quant', (C.c_uint16 * 64) * 3)]
 
 
+class mdhip_jpeg_source(C.Structure):
+    _fields_ = [('coef', C.c_void_p), ('blocks_w', C.c_int32 * 3), ('blocks_h', C.c_int32 * 3)]
+
+
 class mdhip_jpeg_scan(C.Structure):
     _fields_ = [('scan', C.c_void_p), ('desc', C.c_void_p), ('seg_offsets', C.c_void_p), ('coef', C.c_void_p)]
 
@@ -110,6 +114,10 @@ SYMBOLS = {
                                             C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_uint16), _P, C.c_int64, C.POINTER(C.c_int64),
                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
     'mdhip_jpeg_encode_sampled_bound': (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    'mdhip_jpeg_encode_kept': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_uint16), C.POINTER(mdhip_jpeg_source),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, _P, C.c_int64, C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P]),
     'mdhip_blur_regions': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_float, _P]),
     'mdhip_resample_lanczos': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int,

@@ -12,7 +12,10 @@
 //                           replicated, chroma down-sampled as the crop's sampling says: jcsample.c fullsize_downsample,
 //                           h2v1_downsample or h2v2_downsample), "islow" forward DCT rows -> LDS -> columns, quantisation
 //                           by the crop's own pair of tables;
-//                           int16 coefficients in MCU order, a lane stores its column with one 16-byte store
+//                           int16 coefficients in MCU order, a lane stores its column with one 16-byte store.
+//                           mdhip_jpeg_encode_kept: a block of an MCU that no changed rectangle touches (jpeg_keep.h)
+//                           skips all of that -- a lane loads row r of the SOURCE's block with one 16-byte load and the
+//                           rows go through the same LDS tile to the lanes that store the columns
 //   jpeg_enc_bits_kernel    lane = block: DC difference (a local read), zig-zag walk -> the block's bit length
 //   scan (three kernels)    exclusive prefix sum over all blocks; a crop's own offsets are differences to its first block's
 //   jpeg_enc_write_kernel   lane = block: the same walk, bits into the crop's region of the zeroed bit buffer; interior
@@ -27,6 +30,7 @@
 #include "mdhip_internal.h"
 #include "jpeg_dct.h"
 #include "jpeg_encode.h"
+#include "jpeg_keep.h"
 
 namespace mdhip {
 
@@ -39,19 +43,22 @@ constexpr int LANES = 256;               // workgroup of the lane-per-block / la
 constexpr int SCAN_ITEMS = 4;            // values a thread of the scan kernels takes
 constexpr int SCAN_TILE = LANES * SCAN_ITEMS;
 
-// (8 waves a SIMD, as before the sampling became data: the three chroma branches must not cost the kernel a wave)
+// (8 waves a SIMD, as before the sampling became data: the three chroma branches must not cost the kernel a wave, and
+// neither does the kept branch: its rectangle loop depends on the MCU alone and ends before a pixel is loaded, and a kept
+// block holds 4 registers of source values where a recomputed one holds 16 of samples -- 57 VGPRs and no scratch with it as without it; 8 waves need <= 64)
 __global__ __launch_bounds__(COEF_BLOCKS * 8) __attribute__((amdgpu_waves_per_eu(8, 8))) void jpeg_enc_coef_kernel(const JpegEncDev d) {
     __shared__ int lds[COEF_BLOCKS][8][9];
     const int t = threadIdx.x;
     const int lb = t >> 3, r = t & 7;
     const long long g = (long long)blockIdx.x * COEF_BLOCKS + lb;         // block number within the batch
     const bool active = g < d.blocks;
-    bool real = false;
+    bool real = false, keep = false;
     int chroma = 0;
     const uint16_t* quant = d.quant;                                      // the crop's pair of tables
     int v[8], ws[8];
     if (active) {
-        const MdjEncCrop& c = d.crops[mdj_enc_locate<&MdjEncCrop::block0>(d.crops, d.n, g)];
+        const int ci = mdj_enc_locate<&MdjEncCrop::block0>(d.crops, d.n, g);
+        const MdjEncCrop& c = d.crops[ci];
         const long long local = g - c.block0;
         const int hs = c.hs, vs = c.vs, per_mcu = c.per_mcu, luma = hs * vs;
         const unsigned m = unsigned(local) / unsigned(per_mcu);           // (a crop has at most 2^21 blocks)
@@ -60,7 +67,14 @@ __global__ __launch_bounds__(COEF_BLOCKS * 8) __attribute__((amdgpu_waves_per_eu
         const int W = c.width, H = c.height;
         quant = d.quant + c.table * 128;
         real = mdj_enc_block_real(c, m, k);
-        if (k < luma) {
+        keep = d.source != nullptr && !mdj_keep_changed(d.rects, d.rect0[ci], d.rect0[ci + 1], mx, my, hs, vs);
+        if (keep) {                                                       // row r of the source's block, as it is (dummy blocks too)
+            const uint4 row = *reinterpret_cast<const uint4*>(d.source[ci] + mdj_keep_source_offset(c, mx, my, k) + r * 8);
+            lds[lb][r][0] = int(row.x & 0xffffu), lds[lb][r][1] = int(row.x >> 16);
+            lds[lb][r][2] = int(row.y & 0xffffu), lds[lb][r][3] = int(row.y >> 16);
+            lds[lb][r][4] = int(row.z & 0xffffu), lds[lb][r][5] = int(row.z >> 16);
+            lds[lb][r][6] = int(row.w & 0xffffu), lds[lb][r][7] = int(row.w >> 16);
+        } else if (k < luma) {
             if (real) {                                                   // row r of a luma block
                 const int kx = hs == 2 ? k & 1 : 0, ky = hs == 2 ? k >> 1 : k;
                 const int sy = min((my * vs + ky) * 8 + r, H - 1);
@@ -112,7 +126,7 @@ __global__ __launch_bounds__(COEF_BLOCKS * 8) __attribute__((amdgpu_waves_per_eu
                 v[i] = int(unsigned(s + bias) >> 2) - 128;
             }
         }
-        if (real) {
+        if (real && !keep) {
             fdct_1d<true>(v, ws);
 #pragma unroll
             for (int i = 0; i < 8; ++i) lds[lb][r][i] = ws[i];
@@ -121,7 +135,12 @@ __global__ __launch_bounds__(COEF_BLOCKS * 8) __attribute__((amdgpu_waves_per_eu
     __syncthreads();
     if (!active) return;
     uint4 o = {0u, 0u, 0u, 0u};
-    if (real) {
+    if (keep) {                                                           // column r of the source's block: 16-bit halves
+        o.x = unsigned(lds[lb][0][r]) | (unsigned(lds[lb][1][r]) << 16);
+        o.y = unsigned(lds[lb][2][r]) | (unsigned(lds[lb][3][r]) << 16);
+        o.z = unsigned(lds[lb][4][r]) | (unsigned(lds[lb][5][r]) << 16);
+        o.w = unsigned(lds[lb][6][r]) | (unsigned(lds[lb][7][r]) << 16);
+    } else if (real) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] = lds[lb][i][r];                 // column r of the workspace
         fdct_1d<false>(v, ws);                                            // coefficients (i, r), scaled by 8
@@ -170,12 +189,17 @@ __global__ __launch_bounds__(LANES) void jpeg_enc_write_kernel(const JpegEncDev 
 __global__ __launch_bounds__(LANES) void jpeg_enc_count_kernel(const JpegEncDev d) {
     const long long q = (long long)blockIdx.x * LANES + threadIdx.x;
     if (q >= d.chunks) return;
+    if (d.source && d.status[mdj_enc_locate<&MdjEncCrop::chunk0>(d.crops, d.n, q)]) {   // a flagged window of encode_kept: no scan
+        d.count[q] = 0;
+        return;
+    }
     d.count[q] = mdj_enc_lane_count(d.crops, d.n, d.off, d.bitbuf, d.chunk_bytes, q);
 }
 
 __global__ __launch_bounds__(LANES) void jpeg_enc_stuff_kernel(const JpegEncDev d) {
     const long long q = (long long)blockIdx.x * LANES + threadIdx.x;
     if (q >= d.chunks) return;
+    if (d.source && d.status[mdj_enc_locate<&MdjEncCrop::chunk0>(d.crops, d.n, q)]) return;
     mdj_enc_lane_stuff(d.crops, d.n, d.off, d.bitbuf, d.chunk_bytes, d.start, d.out, d.capacity, q);
 }
 

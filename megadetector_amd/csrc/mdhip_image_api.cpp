@@ -17,6 +17,7 @@
 #include "mdhip_ctx.h"
 #include "jpeg_subseq.h"
 #include "jpeg_encode.h"
+#include "jpeg_keep.h"
 #include "blur_box.h"
 #include "resample.h"
 
@@ -440,12 +441,29 @@ long long mdhip_jpeg_encode_sampled_bound(int width, int height, int sampling) {
 
 namespace {
 
-// mdhip_jpeg_encode and mdhip_jpeg_encode_sampled.  samplings NULL: h2v2 for every window; quant: n_tables pairs
-// [luma 64][chroma 64], window i takes pair i when there are n of them and pair 0 when there is one.
+// what mdhip_jpeg_encode_kept adds to a call
+struct JpegKeepArgs {
+    const mdhip_jpeg_source* sources;
+    const int32_t* rect_image;
+    const int32_t* rects;
+    int n_rects;
+    int32_t* status;
+};
+
+// mdhip_jpeg_encode, mdhip_jpeg_encode_sampled and mdhip_jpeg_encode_kept.  samplings NULL: h2v2 for every window; quant:
+// n_tables pairs [luma 64][chroma 64], window i takes pair i when there are n of them and pair 0 when there is one; keep
+// NULL: every block comes from the pixels.
 int jpeg_encode_windows(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
                         const int64_t* pitches, const int32_t* samplings, int n, const uint16_t* quant, int n_tables, uint8_t* out,
-                        int64_t capacity, int64_t* offsets, int64_t* sizes, int64_t* needed, void* hip_stream) {
+                        int64_t capacity, int64_t* offsets, int64_t* sizes, int64_t* needed, void* hip_stream,
+                        const JpegKeepArgs* keep = nullptr) {
     if (n < 1) return fail(ctx, MDHIP_EINVAL, "n = %d", n);
+    if (keep) {
+        if (keep->n_rects < 0) return fail(ctx, MDHIP_EINVAL, "n_rects = %d", keep->n_rects);
+        for (int i = 0; i < keep->n_rects; ++i)
+            if (keep->rect_image[i] < 0 || keep->rect_image[i] >= n)
+                return fail(ctx, MDHIP_EINVAL, "rectangle %d: window %d of %d", i, keep->rect_image[i], n);
+    }
     if (capacity < 0 || (capacity > 0 && !out)) return fail(ctx, MDHIP_EINVAL, "capacity %lld with out %p", (long long)capacity, (void*)out);
     for (int t = 0; t < n_tables; ++t)
         if (int rc = check_quant_tables(ctx, quant + 128 * (size_t)t, quant + 128 * (size_t)t + 64)) return rc;
@@ -476,6 +494,15 @@ int jpeg_encode_windows(mdhip_ctx* ctx, const uint8_t* const* windows, const int
         c.pitch = pitches[i];
         mdj_enc_set_layout(c, w, h, sampling);
         c.table = n_tables == 1 ? 0 : i;
+        if (keep) {                                                     // the source's planes: the window's whole MCUs, on the device
+            const mdhip_jpeg_source& src = keep->sources[i];
+            for (int p = 0; p < 3; ++p)
+                if (src.blocks_w[p] != c.mcus_x * (p == 0 ? c.hs : 1) || src.blocks_h[p] != c.mcus_y * (p == 0 ? c.vs : 1))
+                    return fail(ctx, MDHIP_EINVAL, "window %d: plane %d of the source is %d x %d blocks, the window's MCUs make it %d x %d", i,
+                                p, src.blocks_w[p], src.blocks_h[p], c.mcus_x * (p == 0 ? c.hs : 1), c.mcus_y * (p == 0 ? c.vs : 1));
+            if (!src.coef || (reinterpret_cast<uintptr_t>(src.coef) & 15) || !is_device_ptr(src.coef))
+                return fail(ctx, MDHIP_EINVAL, "window %d: the source's planes are NULL, not 16-byte aligned or a host pointer", i);
+        }
         blocks += nb;
         words += mdj_enc_region_words(nb);
         chunks += mdj_enc_region_chunks(nb, chunk_bytes);
@@ -485,6 +512,26 @@ int jpeg_encode_windows(mdhip_ctx* ctx, const uint8_t* const* windows, const int
     const size_t o_crops = lay.take(sizeof(MdjEncCrop) * ((size_t)n + 1));
     const size_t o_tables = lay.take(sizeof(MdjEncTables));
     const size_t o_quant = lay.take(256 * (size_t)n_tables);
+    // mdhip_jpeg_encode_kept: the rectangles clipped to their windows, window by window in the order of the list
+    std::vector<MdjKeepRect> kept_rects;
+    std::vector<int32_t> rect0;
+    if (keep) {
+        rect0.assign((size_t)n + 1, 0);
+        std::vector<std::vector<MdjKeepRect>> per((size_t)n);
+        for (int i = 0; i < keep->n_rects; ++i) {
+            const int w = keep->rect_image[i];
+            MdjKeepRect q;
+            if (mdj_keep_clip(keep->rects + 4 * (size_t)i, widths[w], heights[w], &q)) per[(size_t)w].push_back(q);
+        }
+        for (int i = 0; i < n; ++i) {
+            rect0[(size_t)i] = (int32_t)kept_rects.size();
+            kept_rects.insert(kept_rects.end(), per[(size_t)i].begin(), per[(size_t)i].end());
+        }
+        rect0[(size_t)n] = (int32_t)kept_rects.size();
+    }
+    const size_t o_source = lay.take(keep ? sizeof(const int16_t*) * (size_t)n : 0);
+    const size_t o_rect0 = lay.take(keep ? 4 * ((size_t)n + 1) : 0);
+    const size_t o_rects = lay.take(sizeof(MdjKeepRect) * kept_rects.size());
     const size_t upload_bytes = lay.size;
     const size_t o_status = lay.take(4 * (size_t)n);
     const size_t o_bitbuf = lay.take(4 * (size_t)words);
@@ -504,6 +551,11 @@ int jpeg_encode_windows(mdhip_ctx* ctx, const uint8_t* const* windows, const int
     mdj_enc_build_tables(tables);
     memcpy(up.data() + o_tables, &tables, sizeof(tables));
     memcpy(up.data() + o_quant, quant, 256 * (size_t)n_tables);
+    if (keep) {
+        for (int i = 0; i < n; ++i) memcpy(up.data() + o_source + sizeof(const int16_t*) * (size_t)i, &keep->sources[i].coef, sizeof(const int16_t*));
+        memcpy(up.data() + o_rect0, rect0.data(), 4 * rect0.size());
+        if (!kept_rects.empty()) memcpy(up.data() + o_rects, kept_rects.data(), sizeof(MdjKeepRect) * kept_rects.size());
+    }
     // (the upload is from pageable memory: the copy has left `up` when the call returns)
     HIP_TRY(ctx, hipMemcpyAsync(base, up.data(), upload_bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemsetAsync(base + o_status, 0, zero_bytes, s));
@@ -526,6 +578,9 @@ int jpeg_encode_windows(mdhip_ctx* ctx, const uint8_t* const* windows, const int
     d.chunks = chunks;
     d.n = n;
     d.chunk_bytes = chunk_bytes;
+    d.source = keep ? (const int16_t* const*)(base + o_source) : nullptr;
+    d.rects = (const MdjKeepRect*)(base + o_rects);
+    d.rect0 = (const int32_t*)(base + o_rect0);
     HIP_TRY(ctx, launch_jpeg_encode(d, s));
     std::vector<long long> result(2 * (size_t)n + 1);
     std::vector<uint32_t> status((size_t)n);
@@ -537,7 +592,9 @@ int jpeg_encode_windows(mdhip_ctx* ctx, const uint8_t* const* windows, const int
         sizes[i] = result[(size_t)n + i];
     }
     *needed = result[2 * (size_t)n];
-    for (int i = 0; i < n; ++i)
+    if (keep)                                                           // a flagged window has no scan; the others are whole
+        for (int i = 0; i < n; ++i) keep->status[i] = status[i] ? 1 : 0;
+    for (int i = 0; i < n && !keep; ++i)
         if (status[i]) return fail(ctx, MDHIP_EINVAL, "window %d: a coefficient no baseline JPEG can hold (status %u)", i, status[i]);
     if (*needed > capacity)
         return fail(ctx, MDHIP_ECAPACITY, "the scans take %lld bytes, the output buffer has %lld", (long long)*needed, (long long)capacity);
@@ -565,6 +622,19 @@ int mdhip_jpeg_encode_sampled(mdhip_ctx* ctx, const uint8_t* const* windows, con
     if (!windows || !widths || !heights || !pitches || !samplings || !quant || !offsets || !sizes || !needed)
         return fail(ctx, MDHIP_EINVAL, "windows/widths/heights/pitches/samplings/quant/offsets/sizes/needed is NULL");
     return jpeg_encode_windows(ctx, windows, widths, heights, pitches, samplings, n, quant, n, out, capacity, offsets, sizes, needed, hip_stream);
+}
+
+int mdhip_jpeg_encode_kept(mdhip_ctx* ctx, const uint8_t* const* windows, const int32_t* widths, const int32_t* heights,
+                           const int64_t* pitches, const int32_t* samplings, int n, const uint16_t* quant,
+                           const mdhip_jpeg_source* sources, const int32_t* rect_image, const int32_t* rects, int n_rects, uint8_t* out,
+                           int64_t capacity, int64_t* offsets, int64_t* sizes, int64_t* needed, int32_t* status, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!windows || !widths || !heights || !pitches || !samplings || !quant || !sources || !offsets || !sizes || !needed || !status ||
+        (n_rects > 0 && (!rect_image || !rects)))
+        return fail(ctx, MDHIP_EINVAL, "windows/widths/heights/pitches/samplings/quant/sources/rect_image/rects/offsets/sizes/needed/status is NULL");
+    const JpegKeepArgs keep = {sources, rect_image, rects, n_rects, status};
+    return jpeg_encode_windows(ctx, windows, widths, heights, pitches, samplings, n, quant, n, out, capacity, offsets, sizes, needed, hip_stream,
+                               &keep);
 }
 
 int mdhip_blur_regions(mdhip_ctx* ctx, uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches,

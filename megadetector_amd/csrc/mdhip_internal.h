@@ -12,6 +12,7 @@ struct MdClassifyCrop;             // resample.h: the record of a crop of mdhip_
 struct MdjImage;
 struct MdjEncCrop;
 struct MdjEncTables;
+struct MdjKeepRect;
 
 namespace mdhip {
 
@@ -592,6 +593,10 @@ struct JpegEncDev {
     long long capacity;
     long long blocks, chunks;
     int n, chunk_bytes;
+    // mdhip_jpeg_encode_kept (jpeg_keep.h); source NULL: every block comes from the pixels
+    const int16_t* const* source; // [n] each crop's source planes, or NULL
+    const ::MdjKeepRect*  rects;  // the changed rectangles, clipped, crop by crop
+    const int32_t*        rect0;  // [n + 1] crop c's rectangles are rects[rect0[c] .. rect0[c + 1])
 };
 hipError_t launch_jpeg_encode(const JpegEncDev& d, hipStream_t s);
 long long jpeg_encode_scan_tiles(long long n);

@@ -31,11 +31,13 @@ def probe(path, keep_data=False):
     return out
 
 
-def decode_chunk(ctx, torch, device, image_base, files, probes, counts, via_pil=None):
+def decode_chunk(ctx, torch, device, image_base, files, probes, counts, via_pil=None, coefficients=None):
     """file -> flat uint8 device tensor of its RGB pixels, each file decoded once: the JPEGs the decoder takes through
     mdhip_jpeg_entropy_decode and mdhip_jpeg_reconstruct (one call each for the chunk), every other file -- and a JPEG the
     decoder flags -- through PIL and an upload.  files are relative to image_base; probes: file -> probe(); counts gets
-    'files_decoded_gpu' and 'files_decoded_pil' added to; via_pil: a set that receives the files PIL decoded.
+    'files_decoded_gpu' and 'files_decoded_pil' added to; via_pil: a set that receives the files PIL decoded; coefficients: a
+    dict that receives, per file the GPU decoded, (device pointer to its quantised planes in the layout of mdjpeg_decode, the
+    tensor that holds them) -- the planes live as long as the caller keeps the entry; None: they are freed with the call.
     -> (pixels, the files PIL could not decode either)"""
     import numpy as np
     from .feed import load_image
@@ -62,6 +64,8 @@ def decode_chunk(ctx, torch, device, image_base, files, probes, counts, via_pil=
                                  [t.data_ptr() for t in outs])
             for k, t in zip(clean, outs):
                 pixels[scans[k]] = t
+                if coefficients is not None:
+                    coefficients[scans[k]] = (coefs.data_ptr() + 2 * coef_offs[k], coefs)
             counts['files_decoded_gpu'] += len(clean)
     for f in files:
         if f not in pixels:

@@ -414,6 +414,48 @@ class HipContext:
             self._check(rc, 'mdhip_jpeg_encode_sampled')
         return rc == 0, np.array(offs[:n], dtype=np.int64), np.array(lens[:n], dtype=np.int64), int(need.value)
 
+    def jpeg_encode_kept(self, ptrs, sizes, pitches, samplings, quants, source_ptrs, rect_image, rects, out_ptr, capacity, stream=0):
+        """
+        jpeg_encode_sampled for copies in which only rectangles changed (include/mdhip.h: mdhip_jpeg_encode_kept): the blocks
+        of every MCU that no rectangle touches are the source file's own coefficients.
+        source_ptrs: per window the integer device pointer (16-byte aligned) to the source's quantised planes in the layout of
+                     jpeg_host.decode / jpeg_entropy_decode for the window's size and sampling (whole MCUs)
+        rect_image, rects: per changed rectangle the index of its window and (left, top, right, bottom), right / bottom
+                     exclusive; clipped to the window by the call
+        Everything else as for jpeg_encode_sampled.  Returns (fits, offsets, sizes, needed, status): status 1 marks a window
+        whose merged blocks no baseline scan holds; its scan has size 0 and the caller re-encodes it whole.
+        """
+        n, m = len(ptrs), len(rects)
+        if not (len(sizes) == len(pitches) == len(samplings) == len(quants) == len(source_ptrs) == n) or len(rect_image) != m:
+            raise ValueError('one entry per window is needed in every list, and one window index per rectangle')
+        p, ws, hs, pt = _window_arrays(ptrs, sizes, pitches)
+        ss = (C.c_int32 * max(n, 1))(*[int(v) for v in samplings])
+        packed = np.zeros((max(n, 1), 2, 64), dtype=np.uint16)
+        for i, pair in enumerate(quants):
+            for k in (0, 1):
+                table = np.asarray(pair[k]).reshape(-1)
+                if table.size != 64 or table.min() < 0 or table.max() > 65535:
+                    raise ValueError('window {}: a quantisation table has 64 entries'.format(i))
+                packed[i, k] = table
+        sources = (_lib.mdhip_jpeg_source * max(n, 1))()
+        for i, ((w, h), sampling) in enumerate(zip(sizes, samplings)):
+            fh, fv = {0: (1, 1), 1: (2, 1), 2: (2, 2)}.get(int(sampling), (1, 1))      # (the call refuses any other sampling)
+            mx, my = (int(w) + 8 * fh - 1) // (8 * fh), (int(h) + 8 * fv - 1) // (8 * fv)
+            sources[i].coef = int(source_ptrs[i])
+            sources[i].blocks_w[:] = [mx * fh, mx, mx]
+            sources[i].blocks_h[:] = [my * fv, my, my]
+        ri = (C.c_int32 * max(m, 1))(*[int(v) for v in rect_image])
+        rc4 = (C.c_int32 * max(4 * m, 1))(*[int(v) for q in rects for v in q])
+        offs, lens, need = (C.c_int64 * max(n, 1))(), (C.c_int64 * max(n, 1))(), C.c_int64(0)
+        status = (C.c_int32 * max(n, 1))()
+        rc = self.lib.mdhip_jpeg_encode_kept(self.h, p, ws, hs, pt, ss, n, packed.ctypes.data_as(C.POINTER(C.c_uint16)), sources, ri, rc4, m,
+                                             C.c_void_p(int(out_ptr) if capacity else 0), int(capacity), offs, lens, C.byref(need),
+                                             status, C.c_void_p(stream))
+        if rc != _lib.MDHIP_ECAPACITY:
+            self._check(rc, 'mdhip_jpeg_encode_kept')
+        return (rc == 0, np.array(offs[:n], dtype=np.int64), np.array(lens[:n], dtype=np.int64), int(need.value),
+                np.array(status[:n], dtype=np.int32))
+
     @staticmethod
     def jpeg_encode_sampled_bound(width, height, sampling):
         """bytes the scan of a width x height window can take at the very most at that sampling (mdhip_jpeg_encode_sampled_bound)"""

@@ -61,6 +61,8 @@ SYMBOLS = {
                                                      C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]),
     'mdjpeg_encode_sampled_bound': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    'mdjpeg_keep_merge': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int,
+                                    C.POINTER(C.c_int32)]),
     'mdjpeg_blur_regions': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_float]),
     'mdjpeg_blur_regions_chunked': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int,
                                               C.c_float, C.c_int]),
@@ -461,6 +463,33 @@ def encode_subsequences(coefs, sizes, chunk_bytes=64, capacity=None, samplings=N
         raise AssertionError('mdjpeg_encode_subsequences wrote beyond its capacity')
     scans = [buf[offs[i]:offs[i] + lens[i]].tobytes() for i in range(n)] if rc == MDJPEG_OK else None
     return rc, scans, int(need.value), buf[:capacity]
+
+
+def keep_merge(planes, source, size, sampling, rects):
+    """
+    The host model of mdhip_jpeg_encode_kept's merge for one window (mdjpeg_keep_merge).  planes: the re-encoded coefficients,
+    a flat int16 array in the layout of decode() for `sampling`, changed IN PLACE; source: the source file's in the same
+    layout; size: (width, height); rects: (left, top, right, bottom), right and bottom exclusive.  Every block of an MCU that
+    no rectangle touches becomes the source's.  Returns the status: 1 when the merged planes hold a DC difference or an AC
+    value no baseline scan codes (encode_subsequences refuses them), else 0.
+    """
+    if planes.dtype != np.int16 or not planes.flags.c_contiguous or not planes.flags.writeable:
+        raise ValueError('planes must be a writeable contiguous int16 array')
+    source = np.ascontiguousarray(source, dtype=np.int16)
+    width, height = int(size[0]), int(size[1])
+    if sampling not in SAMPLING_FACTORS:
+        raise ValueError('sampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0), got {!r}'.format(sampling))
+    hs, vs = SAMPLING_FACTORS[sampling]
+    values = ((width + 8 * hs - 1) // (8 * hs)) * ((height + 8 * vs - 1) // (8 * vs)) * (hs * vs + 2) * 64
+    if planes.size != values or source.size != values:
+        raise ValueError('planes and source hold {} values each for {} x {} at sampling {}'.format(values, width, height, sampling))
+    flat = np.ascontiguousarray(np.asarray(rects, dtype=np.int32).reshape(-1, 4))
+    status = C.c_int32(0)
+    rc = load().mdjpeg_keep_merge(planes.ctypes.data, source.ctypes.data, width, height, int(sampling),
+                                  flat.ctypes.data_as(C.POINTER(C.c_int32)), len(flat), C.byref(status))
+    if rc != MDJPEG_OK:
+        raise ValueError('mdjpeg_keep_merge failed ({})'.format(rc))
+    return int(status.value)
 
 
 def blur_regions(rgb, rects, radius, lds_bytes=None):

@@ -25,10 +25,16 @@ though its saved form would be the quality-85 one), when its name is not a JPEG'
 two 8-bit tables, a sampling other than 4:4:4 / 4:2:2 / 4:2:0, a box thinner than its outline, classification labels on the
 boxes) or when its rendering fails on the device.
 
+keep_source_blocks (not in the reference, off by default): a manipulated copy of a plain RGB JPEG keeps the SOURCE file's
+quantised coefficients in every MCU that no blur rectangle and no drawing operation touches, and only the touched MCUs are
+re-encoded (mdhip_jpeg_encode_kept on the device leg, jpeg_host.keep_merge on the host leg: the same bytes).  Every other copy,
+and one whose merged blocks no baseline scan holds, is written exactly as without the option; the counts say how many of each
+('kept', 'kept_refused').
+
 Not restated: nothing of run_detector_batch changes, there is no multi-GPU sharding, and n_threads applies to the host leg.
 
 Command line:  python -m megadetector_amd.separate_detections RESULTS INPUT_DIR OUTPUT_DIR [the reference's flags]
-               [--backend gpu|host] [--device 0]
+               [--backend gpu|host] [--device 0] [--keep_source_blocks]
 """
 
 import argparse
@@ -82,6 +88,7 @@ class SeparateDetectionsIntoFoldersOptions:
         self.category_names_to_blur = None               #: a list, or 'person,vehicle'
         self.remove_empty_folders = False
         self.verbose = False
+        self.keep_source_blocks = False                  #: (not the reference's) manipulated copies keep the source's JPEG blocks
 
 
 def _path_is_abs(p):
@@ -414,10 +421,110 @@ def exif_preserving_save(pil_image, output_file, quality='keep', default_quality
         pil_image.save(output_file)
 
 
+class _HostLeg(Exception):
+    """this copy is not one the device restates"""
+
+
+def changed_rectangles(blur_rects, ops):
+    """What a copy's plan changes, as (left, top, right, bottom) with right and bottom exclusive: the blur rectangles as they
+    are, a solid rectangle x0 .. x1, y0 .. y1 (inclusive) as (x0, y0, x1 + 1, y1 + 1), a pasted patch as (x, y, x + w, y + h).
+    Not clipped: mdhip_jpeg_encode_kept and jpeg_host.keep_merge clip to the image."""
+    out = [tuple(int(v) for v in r) for r in blur_rects]
+    for op in ops:
+        if op[0] == PV.OP_PATCH:
+            out.append((op[1], op[2], op[1] + op[3], op[2] + op[4]))
+        else:
+            out.append((op[1], op[2], op[3] + 1, op[4] + 1))
+    return out
+
+
+def _plan_ops(detections, categories_above_threshold, options, width, height):
+    """the drawing operations of a copy and their patches (preview.render_plan of every category pass); raises _HostLeg"""
+    ops, patches = [], []
+    try:
+        for category_detections, o, label_map, labels in category_passes(detections, categories_above_threshold, options):
+            plan = PV.render_plan(category_detections, width, height, o, label_map, labels)
+            for op in plan.ops:
+                if op[0] == PV.OP_PATCH:
+                    patches.append(bytes(plan.patches[op[5]:op[5] + op[3] * op[4] * 3]))
+                    op = op[:5] + [len(patches) - 1] + op[6:]
+                ops.append(op)
+    except (PV.HostLeg, PV.RenderFailure) as e:
+        raise _HostLeg(str(e))
+    return ops, patches
+
+
+def keep_source_record(source_path, target_path):
+    """What the host leg needs of a source file to keep its blocks in a copy -- {'src': jpeg_host.keep_source's record, 'coef':
+    its quantised planes (jpeg_host.decode), 'size'} -- or None when a copy of it at target_path is not eligible: the name is
+    no JPEG's, the source is not an RGB JPEG that open_image returns as it is with two 8-bit tables at 4:4:4 / 4:2:2 / 4:2:0,
+    or the coefficient decoder does not take it."""
+    from PIL import Image
+    from . import jpeg_host
+    if Image.registered_extensions().get(os.path.splitext(target_path)[1].lower()) != 'JPEG':
+        return None
+    try:
+        with open(source_path, 'rb') as f:
+            data = f.read()
+        src = jpeg_host.keep_source(source_path, data)
+        if not src['keep'] or src['quant'] is None or len(src['exif']) > 65533 or len(src['comment'] or b'') > 65533:
+            return None
+        rc, _, coef = jpeg_host.decode(data)
+    except Exception:
+        return None
+    if rc != jpeg_host.MDJPEG_OK or max(src['size']) > 65535:
+        return None
+    return {'src': src, 'coef': coef, 'size': tuple(src['size'])}
+
+
+def _keep_plan_host(source_path, target_path, detections, categories_above_threshold, options):
+    """keep_source_record with 'changed', the rectangles the copy's plan changes; None also when its drawing is not one the
+    plan restates (the device leg sends such a copy to the host leg as a whole)"""
+    keep = keep_source_record(source_path, target_path)
+    if keep is None:
+        return None
+    width, height = keep['size']
+    try:
+        ops, _ = _plan_ops(detections, categories_above_threshold, options, width, height)
+    except Exception:
+        return None
+    rects = [blur_rectangle(d['bbox'], width, height) for d in detections_to_blur(detections, options)]
+    keep['changed'] = changed_rectangles([r for r in rects if r is not None], ops)
+    return keep
+
+
+def save_kept_host(pil_image, target_path, keep):
+    """The host leg of a kept copy: Pillow encodes the modified pixels in memory with the source's tables and sampling, and the
+    file gets Pillow's blocks in every MCU a rectangle of keep['changed'] touches and the source's elsewhere.  -> 'kept', or
+    'kept_refused' when no baseline scan holds the merged blocks (nothing is written; the caller saves the copy as without
+    the option)"""
+    import io
+    from . import jpeg_host
+    src, (width, height) = keep['src'], keep['size']
+    ql, qc = src['quant']
+    bio = io.BytesIO()
+    pil_image.save(bio, 'JPEG', qtables=[[int(v) for v in ql], [int(v) for v in qc]], subsampling=src['sampling'])
+    rc, _, planes = jpeg_host.decode(bio.getvalue())
+    if rc != jpeg_host.MDJPEG_OK or planes.size != keep['coef'].size:
+        return 'kept_refused'
+    if jpeg_host.keep_merge(planes, keep['coef'], (width, height), src['sampling'], keep['changed']):
+        return 'kept_refused'
+    rc, scans, _, _ = jpeg_host.encode_subsequences([planes], [(width, height)], samplings=[src['sampling']])
+    if rc != jpeg_host.MDJPEG_OK:
+        return 'kept_refused'
+    with open(target_path, 'wb') as f:
+        f.write(jpeg_host.sampled_file(width, height, ql, qc, src['sampling'], scans[0], src['exif'], src['comment']))
+    return 'kept'
+
+
 def render_host(source_path, target_path, detections, categories_above_threshold, options):
-    """:432-500 by the reference's own PIL calls: the host leg of one manipulated copy"""
+    """:432-500 by the reference's own PIL calls: the host leg of one manipulated copy.  -> None, or with keep_source_blocks
+    'kept' / 'kept_refused' for an eligible copy"""
     from PIL import ImageFilter
     from .feed import load_image
+    keep = None
+    if getattr(options, 'keep_source_blocks', False):
+        keep = _keep_plan_host(source_path, target_path, detections, categories_above_threshold, options)
     pil_image = load_image(source_path)
     for d in detections_to_blur(detections, options):                     # visualization_utils.blur_detections :509-531
         rect = blur_rectangle(d['bbox'], pil_image.size[0], pil_image.size[1])
@@ -431,7 +538,10 @@ def render_host(source_path, target_path, detections, categories_above_threshold
             _render_classified_with_pil(pil_image, category_detections, o, label_map, classification_label_map)
         else:
             PV.render_with_pil(pil_image, category_detections, o, label_map=label_map, labels=labels)
-    exif_preserving_save(pil_image, target_path)
+    kept = save_kept_host(pil_image, target_path, keep) if keep is not None else None
+    if kept != 'kept':
+        exif_preserving_save(pil_image, target_path)
+    return kept
 
 
 # ---- file handling ---------------------------------------------------------------------------------------------------------------
@@ -487,18 +597,17 @@ def _map(function, items, options):
 
 
 def _dispose_host(im, options):
-    return _dispose(im, options)
+    """-> (what _dispose did, what render_host returned for a manipulated copy)"""
+    kept = []
+    done = _dispose(im, options, manipulate=lambda *args: kept.append(render_host(*args)))
+    return done, (kept[0] if kept else None)
 
 
 def _render_job_host(job, options):
-    render_host(job['source'], job['target'], job['detections'], job['categories'], options)
+    return render_host(job['source'], job['target'], job['detections'], job['categories'], options)
 
 
 # ---- the device leg ----------------------------------------------------------------------------------------------------------------
-
-class _HostLeg(Exception):
-    """this copy is not one the device restates"""
-
 
 def _plan_job(job, options):
     """What the device needs for one manipulated copy, before any pixel is decoded; raises _HostLeg (or whatever opening the
@@ -527,18 +636,11 @@ def _plan_job(job, options):
     job['exif'], job['comment'], job['size'], job['probe'] = src['exif'], src['comment'], (width, height), p
     rects = [blur_rectangle(d['bbox'], width, height) for d in detections_to_blur(job['detections'], options)]
     job['rects'] = [r for r in rects if r is not None]
-    ops, patches = [], []
-    try:
-        for category_detections, o, label_map, labels in category_passes(job['detections'], job['categories'], options):
-            plan = PV.render_plan(category_detections, width, height, o, label_map, labels)
-            for op in plan.ops:
-                if op[0] == PV.OP_PATCH:
-                    patches.append(bytes(plan.patches[op[5]:op[5] + op[3] * op[4] * 3]))
-                    op = op[:5] + [len(patches) - 1] + op[6:]
-                ops.append(op)
-    except (PV.HostLeg, PV.RenderFailure) as e:
-        raise _HostLeg(str(e))
-    job['ops'], job['patches'] = ops, patches
+    job['ops'], job['patches'] = _plan_ops(job['detections'], job['categories'], options, width, height)
+    # eligible for keep_source_blocks: an RGB JPEG saved with its own tables and sampling (the decoder's verdict comes with the chunk)
+    job['keep'] = bool(getattr(options, 'keep_source_blocks', False) and src['keep'])
+    if job['keep']:
+        job['changed'] = changed_rectangles(job['rects'], job['ops'])
 
 
 def _encode_sampled(ctx, torch, device, tensors, jobs):
@@ -560,6 +662,29 @@ def _encode_sampled(ctx, torch, device, tensors, jobs):
     raise RuntimeError('mdhip_jpeg_encode_sampled asked for {} bytes and refused a buffer of that size'.format(needed))
 
 
+def _encode_kept(ctx, torch, device, tensors, jobs, coefficients):
+    """ONE mdhip_jpeg_encode_kept call for the chunk's eligible copies (and a second one when the guess at the output was too
+    small).  -> the files; None for a copy the call flagged"""
+    from . import jpeg_host
+    sizes = [j['size'] for j in jobs]
+    capacity = sum(w * h * 3 // 2 + 64 * ((w + 7) // 8) * ((h + 7) // 8) + 64 for w, h in sizes)
+    rect_image = [k for k, j in enumerate(jobs) for _ in j['changed']]
+    rects = [r for j in jobs for r in j['changed']]
+    for _ in range(2):
+        out = torch.empty(capacity, dtype=torch.uint8, device=device)
+        fits, offs, lens, needed, status = ctx.jpeg_encode_kept([t.data_ptr() for t in tensors], sizes, [w * 3 for w, _ in sizes],
+                                                                [j['sampling'] for j in jobs], [j['quant'] for j in jobs],
+                                                                [coefficients[j['file']][0] for j in jobs], rect_image, rects,
+                                                                out.data_ptr(), capacity)
+        if fits:
+            host = out[:max(needed, 1)].cpu().numpy()
+            return [None if st else jpeg_host.sampled_file(w, h, j['quant'][0], j['quant'][1], j['sampling'], host[o:o + n].tobytes(),
+                                                           j['exif'], j['comment'])
+                    for (w, h), j, o, n, st in zip(sizes, jobs, offs, lens, status)]
+        capacity = needed
+    raise RuntimeError('mdhip_jpeg_encode_kept asked for {} bytes and refused a buffer of that size'.format(needed))
+
+
 def _render_chunk_device(ctx, torch, device, jobs, options, counts, clock):
     """The manipulated copies of one chunk.  -> the jobs the host leg has to make"""
     import numpy as np
@@ -567,8 +692,9 @@ def _render_chunk_device(ctx, torch, device, jobs, options, counts, clock):
     names = [j['file'] for j in jobs]
     probes = {j['file']: j['probe'] for j in jobs}
     via_pil = set()
+    coefficients = {} if any(j['keep'] for j in jobs) else None           # the sources' planes stay until the chunk is written
     with clock('decode'):
-        pixels, failed = decode_chunk(ctx, torch, device, options.base_input_folder, names, probes, counts, via_pil)
+        pixels, failed = decode_chunk(ctx, torch, device, options.base_input_folder, names, probes, counts, via_pil, coefficients)
     refused = [j for j in jobs if j['file'] in failed or j['file'] in via_pil]      # the device did not decode it
     jobs = [j for j in jobs if j['file'] in pixels and j['file'] not in via_pil]
     if not jobs:
@@ -596,9 +722,21 @@ def _render_chunk_device(ctx, torch, device, jobs, options, counts, clock):
         with clock('draw'):
             patches = torch.from_numpy(np.frombuffer(bytes(packed) or b'\0', np.uint8).copy()).to(device)
             ctx.draw_ops(ptrs, sizes, pitches, op_image, ops, patches.data_ptr(), len(packed))
-    with clock('encode'):
-        files = _encode_sampled(ctx, torch, device, tensors, jobs)
-    counts['encode_calls'] += 1
+    files = [None] * len(jobs)
+    kept = [k for k, j in enumerate(jobs) if j['keep'] and j['file'] in coefficients]
+    if kept:
+        with clock('encode_kept'):
+            for k, data in zip(kept, _encode_kept(ctx, torch, device, [tensors[k] for k in kept], [jobs[k] for k in kept], coefficients)):
+                files[k] = data
+        counts['encode_calls'] += 1
+        counts['kept'] += sum(files[k] is not None for k in kept)
+        counts['kept_refused'] += sum(files[k] is None for k in kept)
+    rest = [k for k in range(len(jobs)) if files[k] is None]              # (a copy the kept call flagged is re-encoded whole)
+    if rest:
+        with clock('encode'):
+            for k, data in zip(rest, _encode_sampled(ctx, torch, device, [tensors[k] for k in rest], [jobs[k] for k in rest])):
+                files[k] = data
+        counts['encode_calls'] += 1
     for j, data in zip(jobs, files):
         with open(j['target'], 'wb') as f:
             f.write(data)
@@ -635,6 +773,8 @@ def _render_device(jobs, options, ctx, counts, profile):
     chunks, room, seen = [[]], DECODE_CHUNK_BYTES, set()
     for job in planned:
         size = job['size'][0] * job['size'][1] * 3
+        if job['keep']:                                                   # its coefficients stay on the device with its pixels
+            size += 2 * int(job['probe']['scan'].coef_count)
         if chunks[-1] and (size > room or job['file'] in seen):           # (a file twice in the results: its copies in two chunks)
             chunks.append([])
             room, seen = DECODE_CHUNK_BYTES, set()
@@ -664,7 +804,9 @@ def separate_detections_into_folders(options, backend='gpu', device=0, ctx=None,
     category_names_to_blur nothing touches a GPU whatever the backend.  profile: also counts['ms'], the milliseconds around
     the decode, blur, draw and encode calls (the device is waited for around each: slower).
     Returns counts: 'images', and of these 'missing', 'exists', 'skipped', 'copied', 'moved' and 'rendered'; of the rendered
-    ones those made on the 'gpu' and by the 'host' leg; 'files_decoded_gpu', 'files_decoded_pil', 'decode_chunks', 'encode_calls'.
+    ones those made on the 'gpu' and by the 'host' leg; 'files_decoded_gpu', 'files_decoded_pil', 'decode_chunks', 'encode_calls';
+    with options.keep_source_blocks 'kept', the eligible copies that kept their source's blocks, and 'kept_refused', those the
+    merge refused and that were written as without the option (both 0 without it).
     """
     if backend not in ('gpu', 'host'):
         raise ValueError("backend must be 'gpu' or 'host', not {!r}".format(backend))
@@ -686,14 +828,16 @@ def separate_detections_into_folders(options, backend='gpu', device=0, ctx=None,
         print('Debug: clipping list to {} images'.format(options.debug_max_images))
         images = images[0:options.debug_max_images]
     counts = {k: 0 for k in ('missing', 'exists', 'skipped', 'copied', 'moved', 'rendered', 'gpu', 'host', 'files_decoded_gpu',
-                             'files_decoded_pil', 'decode_chunks', 'encode_calls')}
+                             'files_decoded_pil', 'decode_chunks', 'encode_calls', 'kept', 'kept_refused')}
     counts['images'] = len(images)
     if profile:
         counts['ms'] = {}
     manipulating = options.render_boxes or (options.category_names_to_blur is not None)
     if backend == 'host' or not manipulating:
-        for done in _map(partial(_dispose_host, options=options), images, options):
+        for done, kept in _map(partial(_dispose_host, options=options), images, options):
             counts[done] += 1
+            if kept:
+                counts[kept] += 1
         counts['host'] = counts['rendered']
     else:
         jobs = []
@@ -714,7 +858,9 @@ def separate_detections_into_folders(options, backend='gpu', device=0, ctx=None,
             finally:
                 if own:
                     ctx.close()
-            _map(partial(_render_job_host, options=options), host, options)
+            for kept in _map(partial(_render_job_host, options=options), host, options):
+                if kept:
+                    counts[kept] += 1
             counts['host'] = len(host)
     if options.remove_empty_folders:
         print('Removing empty folders from {}'.format(options.base_output_folder))
@@ -752,6 +898,8 @@ def main(argv=None):
     parser.add_argument('--remove_empty_folders', action='store_true', help='Remove all empty folders from the target folder at the end')
     parser.add_argument('--backend', choices=('host', 'gpu'), default='gpu', help="'host': the reference's PIL calls, no GPU needed")
     parser.add_argument('--device', type=int, default=0, help='HIP device of the gpu backend')
+    parser.add_argument('--keep_source_blocks', action='store_true',
+                        help="Manipulated copies of RGB JPEGs keep the source file's JPEG blocks outside the boxes (not in the reference)")
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) == 0:
         parser.print_help()
@@ -760,7 +908,7 @@ def main(argv=None):
     options = SeparateDetectionsIntoFoldersOptions()
     for name in ('results_file', 'base_input_folder', 'base_output_folder', 'threshold', 'classification_thresholds', 'n_threads',
                  'allow_existing_directory', 'skip_empty_images', 'move_images', 'render_boxes', 'line_thickness', 'box_expansion',
-                 'category_names_to_blur', 'remove_empty_folders'):
+                 'category_names_to_blur', 'remove_empty_folders', 'keep_source_blocks'):
         setattr(options, name, getattr(args, name))
 
     def validate_threshold(v, name):
