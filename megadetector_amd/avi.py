@@ -1,5 +1,6 @@
 """
-A reader for Motion-JPEG video in an AVI (RIFF) container: where each frame's JPEG lies in the file, and nothing else.
+A reader for Motion-JPEG video in an AVI (RIFF) container: where each frame's JPEG lies in the file, and nothing else --
+and a writer of the plainest such file (write_mjpeg_avi, at the end).
 
 Plain Python (struct only, no cv2, no numpy).  The frame list is built by walking chunk headers -- seek, read 8 bytes --
 through `LIST movi` of `RIFF 'AVI '` and of every `RIFF 'AVIX'` segment that follows (OpenDML); the `idx1` index is not
@@ -176,3 +177,97 @@ class AviFile:
 
     def __exit__(self, *exc):
         self.close()
+
+
+# ---- the writer ------------------------------------------------------------------------------------------------------
+RIFF_SIZE_LIMIT = (1 << 31) - 1                           # the size field of RIFF 'AVI ' in an AVI 1.0 file (no OpenDML)
+_HEADER_BYTES = 12 + (12 + (8 + 56) + (12 + (8 + 56) + (8 + 40))) + 12      # RIFF 'AVI ', LIST hdrl, the head of LIST movi
+
+
+def frame_rate_fraction(fps):
+    """(dwRate, dwScale) of a stream header for `fps` frames a second: round(fps * 1000) over 1000, in lowest terms -- exact
+    for every rate with at most three decimals (30 -> 30 / 1, 12.5 -> 25 / 2, 29.97 -> 2997 / 100)"""
+    from math import gcd
+    rate = int(round(float(fps) * 1000))
+    if rate <= 0:
+        raise AviError('a frame rate of {!r} cannot be written'.format(fps))
+    g = gcd(rate, 1000)
+    return rate // g, 1000 // g
+
+
+def riff_size(frame_lengths):
+    """the size field of RIFF 'AVI ' for frames of these lengths, as write_mjpeg_avi lays the file out"""
+    n = movi = 0
+    for ln in frame_lengths:
+        movi += 8 + ln + (ln & 1)
+        n += 1
+    return _HEADER_BYTES + movi + 8 + 16 * n - 8
+
+
+def _headers(n, fps, width, height, largest, movi_bytes):
+    rate, scale = frame_rate_fraction(fps)
+    avih = struct.pack('<14I', int(round(1e6 / float(fps))), 0, 0, 0x10, n, 0, 1, largest, width, height, 0, 0, 0, 0)
+    strh = struct.pack('<4s4sIHHIIIIIIII4H', b'vids', b'MJPG', 0, 0, 0, 0, scale, rate, 0, n, largest, 0xFFFFFFFF, 0, 0, 0, width, height)
+    strf = struct.pack('<IiiHH4sIiiII', 40, width, height, 1, 24, b'MJPG', width * height * 3, 0, 0, 0, 0)
+    strl = b'LIST' + struct.pack('<I', 4 + 8 + len(strh) + 8 + len(strf)) + b'strl' + b'strh' + struct.pack('<I', len(strh)) + strh \
+        + b'strf' + struct.pack('<I', len(strf)) + strf
+    hdrl = b'LIST' + struct.pack('<I', 4 + 8 + len(avih) + len(strl)) + b'hdrl' + b'avih' + struct.pack('<I', len(avih)) + avih + strl
+    head = b'RIFF' + struct.pack('<I', _HEADER_BYTES + movi_bytes + 8 + 16 * n - 8) + b'AVI ' + hdrl \
+        + b'LIST' + struct.pack('<I', 4 + movi_bytes) + b'movi'
+    assert len(head) == _HEADER_BYTES
+    return head
+
+
+def write_mjpeg_avi(path, frames, fps, width, height):
+    """
+    Writes an AVI 1.0 file with one Motion-JPEG video stream.  frames: an iterable of complete JPEG files as bytes, in order
+    (b'' is a dropped frame: a chunk of size 0); every frame is written as it is, as one `00dc` chunk.  Returns the number of
+    frames.
+
+        RIFF 'AVI '   LIST hdrl   avih, LIST strl (strh 'vids' / 'MJPG', strf BITMAPINFOHEADER 'MJPG', 24 bits)
+                      LIST movi   00dc ...          a chunk of odd size is followed by one pad byte
+                      idx1        per frame '00dc', AVIIF_KEYFRAME, the offset of the chunk's header from the 'movi' tag, its size
+
+    dwMicroSecPerFrame is round(1e6 / fps); strh's dwRate / dwScale is frame_rate_fraction(fps).  dwTotalFrames, dwLength and
+    dwSuggestedBufferSize (the largest chunk) are filled in when the last frame is written: the frames are streamed into
+    `path + '.part'`, only the 16 index bytes of each stay in memory, and the finished file is renamed to `path`.  A file whose
+    RIFF size would pass 2^31 - 1 bytes raises AviError and leaves nothing at `path`: for a sequence (something with len())
+    the lengths are added up before the first byte is written; for an iterator the frame that would pass the limit ends the
+    writing, and the partial file is removed.  OpenDML is not written.
+    """
+    width, height = int(width), int(height)
+    if not (1 <= width <= 65535 and 1 <= height <= 65535):
+        raise AviError('a frame of {} x {} pixels cannot be written'.format(width, height))
+    frame_rate_fraction(fps)
+    if hasattr(frames, '__len__'):
+        size = riff_size(len(f) for f in frames)
+        if size > RIFF_SIZE_LIMIT:
+            raise AviError('the file would take {} bytes: more than an AVI 1.0 file holds'.format(size + 8))
+    part = path + '.part'
+    n = largest = movi = 0
+    index = []
+    try:
+        with open(part, 'wb') as f:
+            f.write(b'\0' * _HEADER_BYTES)
+            for data in frames:
+                ln = len(data)
+                if _HEADER_BYTES + movi + 8 + ln + (ln & 1) + 8 + 16 * (n + 1) - 8 > RIFF_SIZE_LIMIT:
+                    raise AviError('frame {} would take the file past what an AVI 1.0 file holds'.format(n))
+                index.append(struct.pack('<4sIII', b'00dc', 0x10, 4 + movi, ln))
+                f.write(b'00dc' + struct.pack('<I', ln))
+                f.write(data)
+                if ln & 1:
+                    f.write(b'\0')
+                movi += 8 + ln + (ln & 1)
+                largest = max(largest, ln)
+                n += 1
+            f.write(b'idx1' + struct.pack('<I', 16 * n))
+            f.write(b''.join(index))
+            f.seek(0)
+            f.write(_headers(n, fps, width, height, largest, movi))
+    except BaseException:
+        if os.path.exists(part):
+            os.remove(part)
+        raise
+    os.replace(part, path)
+    return n

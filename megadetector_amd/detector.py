@@ -127,6 +127,7 @@ class HIPDetector:
         self.jpeg_images_entropy_decoded = 0    # of those: images whose scan was Huffman-decoded on the device too
         self.crop_counts = {'gpu': 0, 'host': 0, 'skipped': 0}      # crops= : encoded on the device / saved by PIL / without area
         self.blur_counts = {'gpu': 0, 'host': 0}                    # blur= : copies encoded on the device / saved by PIL
+        self.render_counts = {'gpu': 0}                             # render= : video frames made on the device
         self.preview_counts = {'gpu': 0, 'host': 0, 'skipped': 0}   # preview= : encoded on the device / rendered or saved by PIL / no file
         self.classify_counts = {'gpu': 0, 'host': 0, 'skipped': 0}  # classify= : crops made by the kernel / by PIL / without a crop
         self.jpeg_entropy_fallbacks = 0         # scans the device flagged: decoded with PIL from the file's bytes instead
@@ -258,7 +259,7 @@ class HIPDetector:
 
     def generate_detections_one_batch(self, img_original, image_id=None, detection_threshold=0.00001,
                                       image_size=None, augment=False, verbose=False, crops=None, blur=None, preview=None,
-                                      classify=None):
+                                      classify=None, render=None):
         """reference pytorch_detector.py:1124-1252.  crops (a crops.CropOptions, default None = off): every result dict gains
         'crops', a list of (crop_id, crop_filename_relative, bytes) -- the files create_crop_folder.py writes for the
         image's detections, encoded on the device from the pixels that are resident there (mdhip_jpeg_encode).
@@ -297,12 +298,15 @@ class HIPDetector:
                     raise ValueError('Mixed input types in batch: item {} is a dict, but item 0 is not a dict'.format(i_img))
         # one group in flight at a time: each chunk is collected before the next is enqueued, the last one here
         return self.finish_batch(self.start_batch(img_original, image_id, detection_threshold, image_size, augment, verbose,
-                                                  crops=crops, blur=blur, preview=preview, classify=classify))
+                                                  crops=crops, blur=blur, preview=preview, classify=classify, render=render))
 
-    def _products(self, crops, blur, preview, classify=None):
+    def _products(self, crops, blur, preview, classify=None, render=None):
         """the products asked for (crops.Product), in the order their kernels are enqueued"""
         asked = ((CropProduct, crops, self.crop_counts), (ClassifyProduct, classify, self.classify_counts),
                  (BlurProduct, blur, self.blur_counts), (PreviewProduct, preview, self.preview_counts))
+        if render is not None:                             # (process_video's annotated videos: visualize_video_output.py)
+            from .visualize_video_output import RenderProduct
+            asked += ((RenderProduct, render, self.render_counts),)
         return [product(options, counts) for product, options, counts in asked if options is not None]
 
     @staticmethod
@@ -332,7 +336,9 @@ class HIPDetector:
                 else:
                     r[product.key] = product.of_host_image(np.asarray(info['img_original']), current_id, r['detections'])
                     continue
-                entries.append((t, ww, hh, current_id, r['detections']))
+                entry = (t, ww, hh, current_id, r['detections'])
+                # a product that wants it also gets the image as it came: a DeviceCoefficientImage's planes are still on the device
+                entries.append(entry + (info['img_original'],) if getattr(product, 'wants_source', False) else entry)
                 where.append(original_idx)
             if entries:
                 for original_idx, value in zip(where, product.of_device_images(self._ctx, entries, stream)):
@@ -693,7 +699,7 @@ class HIPDetector:
                     handle['staged'].products_made(handle, product_s)
 
     def start_batch(self, img_original, image_id, detection_threshold=0.00001, image_size=None, augment=False,
-                    verbose=False, crops=None, blur=None, preview=None, classify=None):
+                    verbose=False, crops=None, blur=None, preview=None, classify=None, render=None):
         """Enqueues a batch; returns a ticket for finish_batch(), and every ticket must be finished.  At most two tickets may
         be outstanding, and at most four groups can be in flight: every shape group of at most max_batch images takes one of
         the four NMS result slots until it is collected, and so does every chunk of the other calls.  All groups of a batch
@@ -705,7 +711,7 @@ class HIPDetector:
         self._check_augment(augment)
         if detection_threshold is None:
             detection_threshold = 0.0
-        products = self._products(crops, blur, preview, classify)
+        products = self._products(crops, blur, preview, classify, render)
         img_original = self.decode_scans(img_original)
         results, shape_groups = self._prepare_batch(img_original, image_id, image_size, verbose)
         chunks = []
@@ -748,14 +754,14 @@ class HIPDetector:
     # -----------------------------------------------------------------------------------
     def generate_detections_one_image(self, img_original, image_id='unknown', detection_threshold=0.00001,
                                       image_size=None, augment=False, verbose=False, crops=None, blur=None, preview=None,
-                                      classify=None):
+                                      classify=None, render=None):
         """reference pytorch_detector.py:1428-1478"""
         if isinstance(img_original, dict):
             res = self.generate_detections_one_batch([img_original], None, detection_threshold,
-                                                     image_size, augment, verbose, crops=crops, blur=blur, preview=preview, classify=classify)
+                                                     image_size, augment, verbose, crops=crops, blur=blur, preview=preview, classify=classify, render=render)
         else:
             res = self.generate_detections_one_batch([img_original], [image_id], detection_threshold,
-                                                     image_size, augment, verbose, crops=crops, blur=blur, preview=preview, classify=classify)
+                                                     image_size, augment, verbose, crops=crops, blur=blur, preview=preview, classify=classify, render=render)
         return res[0]
 
 

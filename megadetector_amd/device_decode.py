@@ -31,9 +31,43 @@ def probe(path, keep_data=False):
     return out
 
 
+def decode_scans(ctx, torch, device, images, keep_coefficients=False):
+    """jpeg_host.ScanImage objects -> their RGB pixels in device memory: ONE mdhip_jpeg_entropy_decode call and ONE
+    mdhip_jpeg_reconstruct call for all of them, whatever their sizes, samplings and tables.  -> (pixels, coefficients): per
+    image a flat uint8 device tensor, None for an image the decoder flags; per image None or, with keep_coefficients and for a
+    decoded image, (device pointer to its quantised planes in the layout of mdjpeg_decode, the tensor that holds them) -- the
+    planes live as long as the caller keeps the entry."""
+    import numpy as np
+    pixels, coefficients = [None] * len(images), [None] * len(images)
+    if not images:
+        return pixels, coefficients
+    scan_offs, coef_offs, nbytes, nvals = [], [], 0, 0
+    for im in images:
+        scan_offs.append(nbytes)
+        nbytes += (im.nbytes + 255) // 256 * 256 + 256
+        coef_offs.append(nvals)
+        nvals += (im.coef_count + 127) // 128 * 128
+    host = np.zeros(nbytes, dtype=np.uint8)
+    for im, off in zip(images, scan_offs):
+        host[off:off + im.nbytes] = im.scan_bytes
+    compressed = torch.from_numpy(host).to(device)
+    coefs = torch.empty(max(nvals, 1), dtype=torch.int16, device=device)
+    status = ctx.jpeg_entropy_decode(images, [compressed.data_ptr() + o for o in scan_offs], [coefs.data_ptr() + 2 * o for o in coef_offs])
+    clean = [k for k, st in enumerate(status) if st == 0]
+    if clean:
+        outs = [torch.empty(int(np.prod(images[k].shape)), dtype=torch.uint8, device=device) for k in clean]
+        ctx.jpeg_reconstruct([images[k].coefficient_image() for k in clean], [coefs.data_ptr() + 2 * coef_offs[k] for k in clean],
+                             [t.data_ptr() for t in outs])
+        for k, t in zip(clean, outs):
+            pixels[k] = t
+            if keep_coefficients:
+                coefficients[k] = (coefs.data_ptr() + 2 * coef_offs[k], coefs)
+    return pixels, coefficients
+
+
 def decode_chunk(ctx, torch, device, image_base, files, probes, counts, via_pil=None, coefficients=None):
     """file -> flat uint8 device tensor of its RGB pixels, each file decoded once: the JPEGs the decoder takes through
-    mdhip_jpeg_entropy_decode and mdhip_jpeg_reconstruct (one call each for the chunk), every other file -- and a JPEG the
+    decode_scans (one entropy-decode and one reconstruct call for the chunk), every other file -- and a JPEG the
     decoder flags -- through PIL and an upload.  files are relative to image_base; probes: file -> probe(); counts gets
     'files_decoded_gpu' and 'files_decoded_pil' added to; via_pil: a set that receives the files PIL decoded; coefficients: a
     dict that receives, per file the GPU decoded, (device pointer to its quantised planes in the layout of mdjpeg_decode, the
@@ -43,30 +77,13 @@ def decode_chunk(ctx, torch, device, image_base, files, probes, counts, via_pil=
     from .feed import load_image
     pixels, failed = {}, set()
     scans = [f for f in files if probes[f]['scan'] is not None]
-    if scans:
-        images = [probes[f]['scan'] for f in scans]
-        scan_offs, coef_offs, nbytes, nvals = [], [], 0, 0
-        for im in images:
-            scan_offs.append(nbytes)
-            nbytes += (im.nbytes + 255) // 256 * 256 + 256
-            coef_offs.append(nvals)
-            nvals += (im.coef_count + 127) // 128 * 128
-        host = np.zeros(nbytes, dtype=np.uint8)
-        for im, off in zip(images, scan_offs):
-            host[off:off + im.nbytes] = im.scan_bytes
-        compressed = torch.from_numpy(host).to(device)
-        coefs = torch.empty(max(nvals, 1), dtype=torch.int16, device=device)
-        status = ctx.jpeg_entropy_decode(images, [compressed.data_ptr() + o for o in scan_offs], [coefs.data_ptr() + 2 * o for o in coef_offs])
-        clean = [k for k, st in enumerate(status) if st == 0]
-        if clean:
-            outs = [torch.empty(int(np.prod(images[k].shape)), dtype=torch.uint8, device=device) for k in clean]
-            ctx.jpeg_reconstruct([images[k].coefficient_image() for k in clean], [coefs.data_ptr() + 2 * coef_offs[k] for k in clean],
-                                 [t.data_ptr() for t in outs])
-            for k, t in zip(clean, outs):
-                pixels[scans[k]] = t
-                if coefficients is not None:
-                    coefficients[scans[k]] = (coefs.data_ptr() + 2 * coef_offs[k], coefs)
-            counts['files_decoded_gpu'] += len(clean)
+    decoded, planes = decode_scans(ctx, torch, device, [probes[f]['scan'] for f in scans], coefficients is not None)
+    for f, t, c in zip(scans, decoded, planes):
+        if t is not None:
+            pixels[f] = t
+            counts['files_decoded_gpu'] += 1
+            if coefficients is not None:
+                coefficients[f] = c
     for f in files:
         if f not in pixels:
             try:

@@ -19,6 +19,9 @@ and needs `opencv-python`, which this image does not have; `ArrayFrameSource` se
 reader (avi.py) and hands each sampled frame's JPEG to the device's decoder (`mjpeg='gpu'`) or to Pillow (`mjpeg='host'`).
 A source may yield lazy frame handles (objects with `materialise()`): only a frame that is sampled is materialised.
 
+With render_folder the pass also writes every Motion-JPEG AVI with its detections drawn (visualize_video_output.InPassRenderer),
+from the frames it decoded.
+
 Command line: python -m megadetector_amd.process_video MODEL INPUT [options]; see main().
 """
 
@@ -137,6 +140,7 @@ class MJPEGAVIFrameSource:
         self.frame_rate = float(self.avi.frame_rate)
         self.n_frames = self.avi.n_frames
         self.frames_read = 0
+        self.remember = None                  #: a dict that receives frame name -> the stored JPEG with its tables written in
 
     def __iter__(self):
         return (LazyFrame(self, i) for i in range(self.n_frames))
@@ -145,6 +149,8 @@ class MJPEGAVIFrameSource:
         from . import feed, jpeg_host
         data = jpeg_host.with_standard_tables(self.avi.read_frame(i))
         self.frames_read += 1
+        if self.remember is not None:
+            self.remember[frame_number_to_filename(i)] = data
         try:
             if self.device:
                 # the header half of load_image: its mode check and the EXIF rotation it would apply; no pixel is decoded
@@ -208,12 +214,14 @@ def _frame_interval(every_n_frames, frame_rate):
 
 def run_detector_on_frames(detector, source, every_n_frames=None, frames_to_process=None, batch_size=8,
                            detection_threshold=DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD, image_size=None,
-                           allow_empty_videos=False, verbose=False):
+                           allow_empty_videos=False, verbose=False, renderer=None):
     """
     The batched equivalent of reference `run_callback_on_frames` (video_utils.py:332-470) with the detector
     as the callback.  Returns {'frame_filenames', 'frame_rate', 'results'}; `results[i]` is what
     `detector.generate_detections_one_image(frame, 'frameNNNNNN.jpg', detection_threshold=...)` returns for
-    the i-th sampled frame.
+    the i-th sampled frame.  renderer (a visualize_video_output.InPassRenderer, begun for this source): makes the output
+    frame of every sampled frame as its result arrives -- on the device leg the detector makes it from the image it decoded
+    (render=) -- and the results come back without it.
     """
     if isinstance(frames_to_process, int):
         frames_to_process = [frames_to_process]
@@ -228,27 +236,32 @@ def run_detector_on_frames(detector, source, every_n_frames=None, frames_to_proc
     pipelined = hasattr(detector, 'start_batch') and hasattr(detector, 'finish_batch') and batch_size > 1
 
     frame_filenames, results, inflight = [], [], []
+    extra = {'render': renderer} if renderer is not None and renderer.on_device else {}
+
+    def add(new):
+        if renderer is not None:
+            renderer.take(new)
+        results.extend(new)
 
     def finish_oldest():
         ticket, frames = inflight.pop(0)
-        results.extend(detector.finish_batch(ticket))
+        add(detector.finish_batch(ticket))
         del frames
 
     def flush(frames, ids):
         if not frames:
             return
         if batch_size == 1:
-            results.append(detector.generate_detections_one_image(frames[0], ids[0], detection_threshold=detection_threshold,
-                                                                  image_size=image_size, verbose=verbose))
+            add([detector.generate_detections_one_image(frames[0], ids[0], detection_threshold=detection_threshold,
+                                                        image_size=image_size, verbose=verbose, **extra)])
         elif pipelined:
             inflight.append((detector.start_batch(list(frames), list(ids), detection_threshold=detection_threshold,
-                                                  image_size=image_size, verbose=verbose), list(frames)))
+                                                  image_size=image_size, verbose=verbose, **extra), list(frames)))
             while len(inflight) >= 2:
                 finish_oldest()
         else:
-            results.extend(detector.generate_detections_one_batch(list(frames), list(ids),
-                                                                  detection_threshold=detection_threshold,
-                                                                  image_size=image_size, verbose=verbose))
+            add(detector.generate_detections_one_batch(list(frames), list(ids), detection_threshold=detection_threshold,
+                                                       image_size=image_size, verbose=verbose, **extra))
 
     frames, ids = [], []
     for frame_number, image in enumerate(source):
@@ -283,26 +296,42 @@ def run_detector_on_frames(detector, source, every_n_frames=None, frames_to_proc
 # --------------------------------------------------------------------------------------------
 # many videos -> MegaDetector video results
 # --------------------------------------------------------------------------------------------
-def run_detector_on_videos(detector, videos, open_source=OpenCVFrameSource, error_on_empty_video=False, **kwargs):
+def run_detector_on_videos(detector, videos, open_source=OpenCVFrameSource, error_on_empty_video=False, render=None, **kwargs):
     """
     videos: list of (relative_name, thing handed to open_source).  Same return value as the reference's
     `run_callback_on_frames_for_folder` (video_utils.py:473-583): failed videos get frame rate -1 and a
-    {'failure': ...} dict instead of a result list.
+    {'failure': ...} dict instead of a result list.  render: (folder, a visualize_video_output.VideoVisualizationOptions or
+    None) -- the annotated video of every Motion-JPEG AVI is written below the folder when the video ends, from the frames
+    this pass decoded (InPassRenderer); ret['render_results'] gets the result dict of every video.
     """
     ret = {'video_filenames': [], 'frame_rates': [], 'results': []}
+    renderer = None
+    if render is not None:
+        from .visualize_video_output import InPassRenderer
+        renderer = InPassRenderer(render[0], render[1])
+        ret['render_results'] = renderer.results
+
+    def rendered(rate, res, source):
+        if renderer is not None:
+            md = {'video_filenames': [rel], 'frame_rates': [rate], 'results': [res]}
+            renderer.end_video(video_results_to_md_format(md)[0], what, source)
+
     for rel, what in videos:
         rel = rel.replace('\\', '/')
         ret['video_filenames'].append(rel)
         source = None
         try:
             source = open_source(what)
-            r = run_detector_on_frames(detector, source, **kwargs)
+            if renderer is not None:
+                renderer.begin_video(source)
+            r = run_detector_on_frames(detector, source, renderer=renderer, **kwargs)
         except Exception as e:
             if error_on_empty_video:
                 raise
             print('Warning: error processing video {}: {}'.format(rel, str(e)))
             ret['frame_rates'].append(-1.0)
             ret['results'].append({'failure': 'Failure processing video: {}'.format(str(e))})
+            rendered(-1.0, ret['results'][-1], source)
             continue
         finally:
             if source is not None:
@@ -312,6 +341,7 @@ def run_detector_on_videos(detector, videos, open_source=OpenCVFrameSource, erro
             assert x['file'].startswith('frame')
             x['file'] = rel + '/' + x['file']
         ret['results'].append(r['results'])
+        rendered(r['frame_rate'], r['results'], source)
     return ret
 
 
@@ -426,7 +456,7 @@ def run_detector_on_videos_sharded(model_file, videos, n_gpus, detector_options=
 def process_videos(model_file, input_video_file, output_json_file=None, frame_sample=None, time_sample=None,
                    json_confidence_threshold=DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD, image_size=None, recursive=True,
                    batch_size=8, detector_options=None, detector=None, exit_on_empty_video=False, verbose=False,
-                   n_gpus=1, videos=None, open_source=None, shard_worker=None, mjpeg='off'):
+                   n_gpus=1, videos=None, open_source=None, shard_worker=None, mjpeg='off', render_folder=None, render_options=None, render_results=None):
     """
     reference process_video.py:123-272 (the options that touch this path).  n_gpus > 1 (BASELINE.json configs[3],
     reference notebooks/manage_video_batch.py:51-67,201-218 does it out of process): the video list is sharded over
@@ -434,6 +464,13 @@ def process_videos(model_file, input_video_file, output_json_file=None, frame_sa
     `open_source` replace the folder scan and the cv2 decoder (tests, frames decoded elsewhere).
     mjpeg: 'off' | 'host' | 'gpu' (open_video_source): with 'host' or 'gpu' Motion-JPEG AVI files are read without cv2, and
     with 'gpu' their sampled frames are decoded on the device -- the same pixels, hence the same JSON.
+    render_folder (off by default; only with mjpeg 'gpu' or 'host'): the annotated video of every Motion-JPEG AVI is written
+    below it in the same pass, from the frames the pass decoded -- with 'gpu' from the device images and, for
+    keep_source_blocks, the coefficient planes the entropy decoder left there; the file is not read a second time.  The
+    files are byte for byte those visualize_video_output writes from the JSON of this run with render_options (a
+    VideoVisualizationOptions; None: its defaults), and the JSON is that of a run without the folder.  A video's finished
+    frames are held until it ends.  With n_gpus > 1 every shard writes the videos it processed.  render_results: a list that
+    receives the tool's result dict of every video (one process only).
     """
     if mjpeg not in MJPEG_MODES:
         raise ValueError('mjpeg must be one of {}, got {!r}'.format(MJPEG_MODES, mjpeg))
@@ -443,6 +480,14 @@ def process_videos(model_file, input_video_file, output_json_file=None, frame_sa
         raise ValueError("mjpeg='gpu' needs a detector that decodes JPEG scans on the device (HIPDetector.decode_scans)")
     if frame_sample is not None and time_sample is not None:
         raise ValueError('frame_sample and time_sample are mutually exclusive')
+    if render_folder is None and render_options is not None:
+        raise ValueError('render_options needs render_folder')
+    if render_folder is not None:
+        if mjpeg == 'off':
+            raise ValueError("render_folder needs mjpeg='gpu' or mjpeg='host': only Motion-JPEG AVI files are rendered")
+        from .visualize_video_output import check_options, VideoVisualizationOptions
+        render_options = VideoVisualizationOptions() if render_options is None else render_options
+        check_options(render_options)
     if output_json_file is None:
         v = input_video_file.replace('\\', '/')
         output_json_file = (v[:-1] if v.endswith('/') else v) + '.json'
@@ -467,6 +512,8 @@ def process_videos(model_file, input_video_file, output_json_file=None, frame_sa
         open_source = functools.partial(open_video_source, mjpeg=mjpeg)
     if open_source is not None:
         run_kwargs['open_source'] = open_source
+    if render_folder is not None:
+        run_kwargs['render'] = (render_folder, render_options)
     if n_gpus > 1 and len(videos) > 1:
         assert detector is None, 'a detector object cannot be shared between GPU processes: pass the model file'
         md = run_detector_on_videos_sharded(model_file, videos, min(n_gpus, len(videos)), detector_options=opts,
@@ -479,6 +526,8 @@ def process_videos(model_file, input_video_file, output_json_file=None, frame_sa
         gc.freeze()              # see run_detector_batch.load_and_run_detector_batch
         md = run_detector_on_videos(detector, videos, **run_kwargs)
     print('Finished running MD on videos')
+    if render_results is not None:
+        render_results.extend(md.get('render_results', []))
     images = video_results_to_md_format(md)
     run_detector_batch.write_results_to_file(images, output_json_file, relative_path_base=None, detector_file=model_file)
     return images
@@ -513,7 +562,25 @@ def main(argv=None, detector=None):
     ap.add_argument('--mjpeg', choices=MJPEG_MODES, default='off',
                     help="read Motion-JPEG AVI files without OpenCV: 'host' decodes their frames with Pillow, 'gpu' on the "
                          "device (same pixels); every other file goes to OpenCV as with 'off' (default)")
+    ap.add_argument('--render_folder', type=str, default=None,
+                    help='also write every Motion-JPEG AVI with its detections drawn below this folder, from the frames this pass '
+                         'decoded (needs --mjpeg gpu or host; off by default)')
+    ap.add_argument('--render_confidence_threshold', type=float, default=0.15, help='draw detections at or above this confidence')
+    ap.add_argument('--render_blur_categories', type=str, default=None, help='comma-separated categories to blur in the videos, e.g. person')
+    ap.add_argument('--render_quality', default='keep', help="'keep' (the stored frames' tables and sampling) or 1 .. 95")
+    ap.add_argument('--render_keep_source_blocks', action='store_true',
+                    help="with --render_quality keep: untouched MCUs keep the stored frame's JPEG blocks")
     args = ap.parse_args(argv)
+    render_options = None
+    if args.render_folder is not None:
+        if args.mjpeg == 'off':
+            ap.error('--render_folder needs --mjpeg gpu or --mjpeg host')
+        from .visualize_video_output import VideoVisualizationOptions
+        render_options = VideoVisualizationOptions()
+        render_options.confidence_threshold = args.render_confidence_threshold
+        render_options.blur_category_names = args.render_blur_categories
+        render_options.quality = args.render_quality if args.render_quality == 'keep' else int(args.render_quality)
+        render_options.keep_source_blocks = args.render_keep_source_blocks
     if args.frame_sample is not None and args.time_sample is not None:
         ap.error('--frame_sample and --time_sample are mutually exclusive')
     if not os.path.exists(args.input_video_file):
@@ -523,7 +590,8 @@ def main(argv=None, detector=None):
                    json_confidence_threshold=args.json_confidence_threshold, image_size=args.image_size,
                    recursive=args.recursive, batch_size=args.batch_size,
                    detector_options=run_detector_batch.parse_kvp_list(args.detector_options), detector=detector,
-                   exit_on_empty_video=args.exit_on_empty_video, verbose=args.verbose, n_gpus=args.n_gpus, mjpeg=args.mjpeg)
+                   exit_on_empty_video=args.exit_on_empty_video, verbose=args.verbose, n_gpus=args.n_gpus, mjpeg=args.mjpeg,
+                   render_folder=args.render_folder, render_options=render_options)
     return 0
 
 

@@ -339,57 +339,76 @@ def _classified(detections, o):
     return any('classifications' in d and len(d['classifications']) > 0 for d in PV.drawn_detections(detections, o))
 
 
-def _render_classified_with_pil(image, detections, o, label_map, classification_label_map):
+def classified_label_lines(det, label_map, classification_label_map, classification_confidence_threshold=CLASSIFICATION_CONFIDENCE_THRESHOLD):
+    """render_detection_bounding_boxes :691-769 for one drawn detection: (its label lines -- the detection's, then one per
+    classification at or above the threshold, at most MAX_CLASSIFICATIONS looked at --, the class its colour is of: the
+    detection's category, or NUM_DETECTOR_CATEGORIES + the best classification's)"""
+    clss = det['category']
+    label = label_map[clss] if clss in label_map else clss
+    strings = ['{}: {}%'.format(label, round(100 * det['conf'])) if det['conf'] is not None else '{}'.format(label)]
+    if ('classifications' in det) and len(det['classifications']) > 0:
+        classifications = det['classifications']
+        if len(classifications) > MAX_CLASSIFICATIONS:
+            classifications = classifications[0:MAX_CLASSIFICATIONS]
+        max_category, max_conf = 0, -100
+        if classification_label_map is not None:
+            for class_key, conf in (c[:2] for c in classifications):
+                if conf is None or conf < classification_confidence_threshold:
+                    continue
+                if conf > max_conf:
+                    max_conf, max_category = conf, int(class_key)
+                if class_key in classification_label_map:
+                    class_name = classification_label_map[class_key]
+                elif str(class_key) in classification_label_map:
+                    class_name = classification_label_map[str(class_key)]
+                else:
+                    class_name = str(class_key)
+                strings += ['{}: {}%'.format(class_name.lower(), str(round(100.0 * conf, 1)))]
+        clss = NUM_DETECTOR_CATEGORIES + max_category
+    return strings, clss
+
+
+def stacked_labels(font, strings, left, top, bottom, height):
+    """draw_bounding_box_on_image :1052-1131 for the label lines of one box, left- and top-aligned, in the order they are drawn:
+    the last line first, at the bottom, every further line int(text_height + 2 * margin) higher -- above the box, below it when
+    that leaves the image at the top, inside it when below leaves the image too.  Yields (the padded string, its margin, the
+    corners (x0, y0), (x1, y1) of its filled rectangle, where its text goes)."""
+    import numpy as np
+    total_height = (1 + 2 * 0.05) * sum(PV.text_size(font, s)[1] for s in strings)
+    for i_str, s in enumerate(strings[::-1]):
+        if len(s) == 0:
+            continue
+        s = ' ' + s + ' '
+        text_width, text_height = PV.text_size(font, s)
+        margin = int(np.ceil(0.05 * text_height))
+        text_bottom = top
+        if (text_bottom - total_height) < 0:
+            text_bottom = bottom + total_height
+            if text_bottom > height:
+                text_bottom = top + total_height
+        text_bottom = int(text_bottom) - i_str * (int(text_height + (2 * margin)))
+        text_left = int(left)
+        yield (s, margin, (text_left, (text_bottom - text_height) - (2 * margin)), (text_left + text_width, text_bottom),
+               (text_left + margin, text_bottom - text_height - margin))
+
+
+def _render_classified_with_pil(image, detections, o, label_map, classification_label_map,
+                                classification_confidence_threshold=CLASSIFICATION_CONFIDENCE_THRESHOLD):
     """render_detection_bounding_boxes :673-796 and draw_bounding_box_on_image :990-1137 for detections that carry
     classifications: several label lines per box, stacked from the bottom up, and the colour of the best classification"""
-    import numpy as np
     from PIL import ImageDraw
     width, height = image.size
     thickness, expansion, font_size = PV.resolve_sizes(o, width)
     for det in PV.drawn_detections(detections, o):
-        clss = det['category']
-        label = label_map[clss] if clss in label_map else clss
-        strings = ['{}: {}%'.format(label, round(100 * det['conf'])) if det['conf'] is not None else '{}'.format(label)]
-        if ('classifications' in det) and len(det['classifications']) > 0:
-            classifications = det['classifications']
-            if len(classifications) > MAX_CLASSIFICATIONS:
-                classifications = classifications[0:MAX_CLASSIFICATIONS]
-            max_category, max_conf = 0, -100
-            if classification_label_map is not None:
-                for class_key, conf in (c[:2] for c in classifications):
-                    if conf is None or conf < CLASSIFICATION_CONFIDENCE_THRESHOLD:
-                        continue
-                    if conf > max_conf:
-                        max_conf, max_category = conf, int(class_key)
-                    if class_key in classification_label_map:
-                        class_name = classification_label_map[class_key]
-                    elif str(class_key) in classification_label_map:
-                        class_name = classification_label_map[str(class_key)]
-                    else:
-                        class_name = str(class_key)
-                    strings += ['{}: {}%'.format(class_name.lower(), str(round(100.0 * conf, 1)))]
-            clss = NUM_DETECTOR_CATEGORIES + max_category
+        strings, clss = classified_label_lines(det, label_map, classification_label_map, classification_confidence_threshold)
         color = PV.PREVIEW_COLORS[int(clss) % len(PV.PREVIEW_COLORS)]
         draw = ImageDraw.Draw(image)
         left, top, right, bottom = PV.box_edges(det['bbox'], width, height, expansion)
         draw.rectangle([(left, top), (right, bottom)], outline=color, width=thickness)
         font = PV.load_font(o.label_font, font_size)
-        total_height = (1 + 2 * 0.05) * sum(PV.text_size(font, s)[1] for s in strings)
-        for i_str, s in enumerate(strings[::-1]):
-            if len(s) == 0:
-                continue
-            s = ' ' + s + ' '
-            text_width, text_height = PV.text_size(font, s)
-            margin = int(np.ceil(0.05 * text_height))
-            text_bottom = top
-            if (text_bottom - total_height) < 0:
-                text_bottom = bottom + total_height
-                if text_bottom > height:
-                    text_bottom = top + total_height
-            text_bottom = int(text_bottom) - i_str * (int(text_height + (2 * margin)))
-            text_left = int(left)
-            draw.rectangle([(text_left, (text_bottom - text_height) - (2 * margin)), (text_left + text_width, text_bottom)], fill=color)
-            draw.text((text_left + margin, text_bottom - text_height - margin), s, fill='black', font=font)
+        for s, _, corner0, corner1, text_at in stacked_labels(font, strings, left, top, bottom, height):
+            draw.rectangle([corner0, corner1], fill=color)
+            draw.text(text_at, s, fill='black', font=font)
 
 
 def exif_preserving_save(pil_image, output_file, quality='keep', default_quality=DEFAULT_BLUR_QUALITY):
@@ -498,6 +517,16 @@ def save_kept_host(pil_image, target_path, keep):
     file gets Pillow's blocks in every MCU a rectangle of keep['changed'] touches and the source's elsewhere.  -> 'kept', or
     'kept_refused' when no baseline scan holds the merged blocks (nothing is written; the caller saves the copy as without
     the option)"""
+    data = kept_file_host(pil_image, keep, keep['src']['exif'])
+    if data is None:
+        return 'kept_refused'
+    with open(target_path, 'wb') as f:
+        f.write(data)
+    return 'kept'
+
+
+def kept_file_host(pil_image, keep, exif=b''):
+    """save_kept_host's file as bytes, with `exif` as its APP1 block (none when empty); None where that says 'kept_refused'"""
     import io
     from . import jpeg_host
     src, (width, height) = keep['src'], keep['size']
@@ -506,15 +535,13 @@ def save_kept_host(pil_image, target_path, keep):
     pil_image.save(bio, 'JPEG', qtables=[[int(v) for v in ql], [int(v) for v in qc]], subsampling=src['sampling'])
     rc, _, planes = jpeg_host.decode(bio.getvalue())
     if rc != jpeg_host.MDJPEG_OK or planes.size != keep['coef'].size:
-        return 'kept_refused'
+        return None
     if jpeg_host.keep_merge(planes, keep['coef'], (width, height), src['sampling'], keep['changed']):
-        return 'kept_refused'
+        return None
     rc, scans, _, _ = jpeg_host.encode_subsequences([planes], [(width, height)], samplings=[src['sampling']])
     if rc != jpeg_host.MDJPEG_OK:
-        return 'kept_refused'
-    with open(target_path, 'wb') as f:
-        f.write(jpeg_host.sampled_file(width, height, ql, qc, src['sampling'], scans[0], src['exif'], src['comment']))
-    return 'kept'
+        return None
+    return jpeg_host.sampled_file(width, height, ql, qc, src['sampling'], scans[0], exif, src['comment'])
 
 
 def render_host(source_path, target_path, detections, categories_above_threshold, options):
@@ -643,7 +670,7 @@ def _plan_job(job, options):
         job['changed'] = changed_rectangles(job['rects'], job['ops'])
 
 
-def _encode_sampled(ctx, torch, device, tensors, jobs):
+def _encode_sampled(ctx, torch, device, tensors, jobs, stream=0):
     """ONE mdhip_jpeg_encode_sampled call for the chunk, and a second one with the size the first asked for when the guess at
     the output was too small.  -> the files"""
     from . import jpeg_host
@@ -653,7 +680,7 @@ def _encode_sampled(ctx, torch, device, tensors, jobs):
         out = torch.empty(capacity, dtype=torch.uint8, device=device)
         fits, offs, lens, needed = ctx.jpeg_encode_sampled([t.data_ptr() for t in tensors], sizes, [w * 3 for w, _ in sizes],
                                                            [j['sampling'] for j in jobs], [j['quant'] for j in jobs],
-                                                           out.data_ptr(), capacity)
+                                                           out.data_ptr(), capacity, stream)
         if fits:
             host = out[:max(needed, 1)].cpu().numpy()
             return [jpeg_host.sampled_file(w, h, j['quant'][0], j['quant'][1], j['sampling'], host[o:o + n].tobytes(), j['exif'], j['comment'])
@@ -662,7 +689,7 @@ def _encode_sampled(ctx, torch, device, tensors, jobs):
     raise RuntimeError('mdhip_jpeg_encode_sampled asked for {} bytes and refused a buffer of that size'.format(needed))
 
 
-def _encode_kept(ctx, torch, device, tensors, jobs, coefficients):
+def _encode_kept(ctx, torch, device, tensors, jobs, coefficients, stream=0):
     """ONE mdhip_jpeg_encode_kept call for the chunk's eligible copies (and a second one when the guess at the output was too
     small).  -> the files; None for a copy the call flagged"""
     from . import jpeg_host
@@ -675,7 +702,7 @@ def _encode_kept(ctx, torch, device, tensors, jobs, coefficients):
         fits, offs, lens, needed, status = ctx.jpeg_encode_kept([t.data_ptr() for t in tensors], sizes, [w * 3 for w, _ in sizes],
                                                                 [j['sampling'] for j in jobs], [j['quant'] for j in jobs],
                                                                 [coefficients[j['file']][0] for j in jobs], rect_image, rects,
-                                                                out.data_ptr(), capacity)
+                                                                out.data_ptr(), capacity, stream)
         if fits:
             host = out[:max(needed, 1)].cpu().numpy()
             return [None if st else jpeg_host.sampled_file(w, h, j['quant'][0], j['quant'][1], j['sampling'], host[o:o + n].tobytes(),
@@ -685,28 +712,18 @@ def _encode_kept(ctx, torch, device, tensors, jobs, coefficients):
     raise RuntimeError('mdhip_jpeg_encode_kept asked for {} bytes and refused a buffer of that size'.format(needed))
 
 
-def _render_chunk_device(ctx, torch, device, jobs, options, counts, clock):
-    """The manipulated copies of one chunk.  -> the jobs the host leg has to make"""
+def blur_and_draw(ctx, torch, device, tensors, jobs, clock, radius=DEFAULT_BLUR_RADIUS, stream=0):
+    """ONE mdhip_blur_regions call and then ONE mdhip_draw_ops call for the images `tensors` (flat uint8 device tensors, changed
+    in place) of `jobs`: of each job its 'size', its 'rects' to blur and its 'ops' with their 'patches' (_plan_ops); a patch
+    that several images share is uploaded once.  stream: the raw stream the calls go on (the caller makes it torch's current one)"""
     import numpy as np
-    from .device_decode import decode_chunk
-    names = [j['file'] for j in jobs]
-    probes = {j['file']: j['probe'] for j in jobs}
-    via_pil = set()
-    coefficients = {} if any(j['keep'] for j in jobs) else None           # the sources' planes stay until the chunk is written
-    with clock('decode'):
-        pixels, failed = decode_chunk(ctx, torch, device, options.base_input_folder, names, probes, counts, via_pil, coefficients)
-    refused = [j for j in jobs if j['file'] in failed or j['file'] in via_pil]      # the device did not decode it
-    jobs = [j for j in jobs if j['file'] in pixels and j['file'] not in via_pil]
-    if not jobs:
-        return refused
-    tensors = [pixels[j['file']] for j in jobs]
     sizes = [j['size'] for j in jobs]
     pitches = [w * 3 for w, _ in sizes]
     ptrs = [t.data_ptr() for t in tensors]
     rect_image = [k for k, j in enumerate(jobs) for _ in j['rects']]
     if rect_image:
         with clock('blur'):
-            ctx.blur_regions(ptrs, sizes, pitches, rect_image, [r for j in jobs for r in j['rects']], DEFAULT_BLUR_RADIUS)
+            ctx.blur_regions(ptrs, sizes, pitches, rect_image, [r for j in jobs for r in j['rects']], radius, stream)
     packed, where, op_image, ops = bytearray(), {}, [], []
     for k, j in enumerate(jobs):
         for op in j['ops']:
@@ -721,7 +738,24 @@ def _render_chunk_device(ctx, torch, device, jobs, options, counts, clock):
     if ops:
         with clock('draw'):
             patches = torch.from_numpy(np.frombuffer(bytes(packed) or b'\0', np.uint8).copy()).to(device)
-            ctx.draw_ops(ptrs, sizes, pitches, op_image, ops, patches.data_ptr(), len(packed))
+            ctx.draw_ops(ptrs, sizes, pitches, op_image, ops, patches.data_ptr(), len(packed), stream)
+
+
+def _render_chunk_device(ctx, torch, device, jobs, options, counts, clock):
+    """The manipulated copies of one chunk.  -> the jobs the host leg has to make"""
+    from .device_decode import decode_chunk
+    names = [j['file'] for j in jobs]
+    probes = {j['file']: j['probe'] for j in jobs}
+    via_pil = set()
+    coefficients = {} if any(j['keep'] for j in jobs) else None           # the sources' planes stay until the chunk is written
+    with clock('decode'):
+        pixels, failed = decode_chunk(ctx, torch, device, options.base_input_folder, names, probes, counts, via_pil, coefficients)
+    refused = [j for j in jobs if j['file'] in failed or j['file'] in via_pil]      # the device did not decode it
+    jobs = [j for j in jobs if j['file'] in pixels and j['file'] not in via_pil]
+    if not jobs:
+        return refused
+    tensors = [pixels[j['file']] for j in jobs]
+    blur_and_draw(ctx, torch, device, tensors, jobs, clock)
     files = [None] * len(jobs)
     kept = [k for k, j in enumerate(jobs) if j['keep'] and j['file'] in coefficients]
     if kept:
