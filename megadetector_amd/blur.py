@@ -116,6 +116,7 @@ def blurred_of_device_images(ctx, entries, options, category_ids, stream=0):
     pixels are copied back and PIL saves them in the format of the name (counts['host']).
     """
     import torch
+    from .device_render import blur_rects
     counts = {'gpu': 0, 'host': 0}
     out = [None] * len(entries)
     jobs = []                                                    # (entry, rectangles)
@@ -129,8 +130,7 @@ def blurred_of_device_images(ctx, entries, options, category_ids, stream=0):
     with torch.cuda.stream(ext):
         copies = [entries[e][0].clone() for e, _ in jobs]
     sizes = [(entries[e][1], entries[e][2]) for e, _ in jobs]
-    ctx.blur_regions([c.data_ptr() for c in copies], sizes, [w * 3 for w, _ in sizes], [k for k, (_, rects) in enumerate(jobs) for _ in rects],
-                     [r for _, rects in jobs for r in rects], options.radius, stream=ext.cuda_stream)
+    blur_rects(ctx, [c.data_ptr() for c in copies], sizes, [rects for _, rects in jobs], options.radius, ext.cuda_stream)
     files = files_of_device_images(ctx, [(c, w, h, entries[e][3]) for c, (w, h), (e, _) in zip(copies, sizes, jobs)], options.quality, ext)
     for (e, _), (data, leg) in zip(jobs, files):
         out[e] = data

@@ -116,21 +116,17 @@ def encode_windows(ctx, ptrs, pitches, rects, quality, stream=0):
     pitches[i] its bytes a row.  ONE call of the encoder for all of them and one read-back; a second call with the size
     the first reported when the guess at the output was too small.
     """
-    import torch
+    from .device_render import read_encoded
     if not rects:
         return []
     wins = [int(p) + y0 * pitch + x0 * 3 for p, pitch, (x0, y0, _, _) in zip(ptrs, pitches, rects)]
     sizes = [(x1 - x0, y1 - y0) for x0, y0, x1, y1 in rects]
-    # a guess far below the bound (ctx.jpeg_encode_bound): half a byte a sample and the blocks' fixed cost
+    # a guess far below the bound (ctx.jpeg_encode_bound): half a byte a sample and the 16 x 16 blocks' fixed cost
     capacity = sum(w * h * 3 // 2 + 64 * ((w + 15) // 16) * ((h + 15) // 16) + 64 for w, h in sizes)
-    for _ in range(2):
-        out = torch.empty(capacity, dtype=torch.uint8, device='cuda:{}'.format(ctx.device))
-        fits, offs, lens, needed = ctx.jpeg_encode(wins, sizes, list(pitches), quality, out.data_ptr(), capacity, stream)
-        if fits:
-            host = out[:max(needed, 1)].cpu().numpy()
-            return [jpeg_host.jfif_file(w, h, quality, host[o:o + n].tobytes()) for (w, h), o, n in zip(sizes, offs, lens)]
-        capacity = needed
-    raise RuntimeError('mdhip_jpeg_encode asked for {} bytes and refused a buffer of that size'.format(needed))
+    host, offs, lens, _ = read_encoded(
+        lambda out_ptr, capacity: ctx.jpeg_encode(wins, sizes, list(pitches), quality, out_ptr, capacity, stream),
+        capacity, 'cuda:{}'.format(ctx.device), 'mdhip_jpeg_encode')
+    return [jpeg_host.jfif_file(w, h, quality, host[o:o + n].tobytes()) for (w, h), o, n in zip(sizes, offs, lens)]
 
 
 def _pick(image_file, width, height, detections, options, category_ids, warn):

@@ -1,6 +1,7 @@
 """
-Files of a folder as RGB pixels in device memory, each decoded once: what the tools that work on written results files share
-(rde_review.py, separate_detections.py).  A baseline JPEG the GPU's decoder takes goes through mdhip_jpeg_entropy_decode and
+Files of a folder, and the stored frames of videos, as RGB pixels in device memory, each decoded once: what the tools that work
+on written results files share (rde_review.py, separate_detections.py, visualize_video_output.py).  What follows the decode --
+blur, draw, encode -- is device_render.py.  A baseline JPEG the GPU's decoder takes goes through mdhip_jpeg_entropy_decode and
 mdhip_jpeg_reconstruct on a context that needs no model -- one call each for a whole chunk of files -- and comes out as the
 pixels the reference's load_image gives, EXIF rotation included; every other file, and a JPEG the decoder flags, is decoded
 by PIL and uploaded.

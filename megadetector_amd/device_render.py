@@ -1,0 +1,218 @@
+"""
+The device render path: what follows the decode for images that lie in device memory, shared by the preview folder (preview.py),
+the blurred copies (blur.py), the crops (crops.py), the RDE review sheets (rde_review.py), separate_detections.py and
+visualize_video_output.py.  device_decode.py brings files into device memory; this module changes and encodes them:
+
+  blur_rects      ONE mdhip_blur_regions call for the rectangles of a batch of images
+  draw_plans      ONE mdhip_draw_ops call for the preview.RenderPlan of each image, the label patches of all of them uploaded
+                  once in one buffer (pack_ops)
+  blur_and_draw   the two for a chunk of jobs
+  read_encoded    an encoder call into a guessed buffer, once more with the size the call asked for, and the read-back
+  encode_sampled  ONE mdhip_jpeg_encode_sampled call, jpeg_host.sampled_file around each scan
+  encode_kept     ONE mdhip_jpeg_encode_kept call for the copies that keep their source's JPEG blocks
+
+and, for the host leg that writes the same bytes, blur_with_pil and kept_file_host.  chunked and DECODE_CHUNK_BYTES cut a run
+into decode chunks; Clock times the kinds of device call of a profiled run.  Nothing here synchronises the device unless a
+Clock was given a dict to fill.
+"""
+
+import datetime
+from contextlib import contextmanager, nullcontext
+
+from .blur import DEFAULT_BLUR_RADIUS
+from .preview import OP_PATCH
+
+DECODE_CHUNK_BYTES = 256 << 20                   # decoded pixels of one decode chunk: 28 files at 3 MP, 97 frames of 1280 x 720
+
+
+def chunked(items, size_of, limit, also_break=None):
+    """items in their order as a list of chunks, greedily: an item starts a new chunk when its size_of(item) bytes no longer
+    fit under `limit` beside the chunk's, or when also_break(chunk, item) says so.  An item above the limit gets a chunk of
+    its own; no chunk is empty."""
+    chunks, room = [], 0
+    for item in items:
+        size = size_of(item)
+        if not chunks or size > room or (also_break is not None and also_break(chunks[-1], item)):
+            chunks.append([])
+            room = limit
+        chunks[-1].append(item)
+        room -= size
+    return chunks
+
+
+class Clock:
+    """`with clock('decode'):` adds the milliseconds of the block to ms['decode'], the device waited for before and after, so a
+    profiled run is slower than a plain one; with ms None the block just runs and neither torch nor the device is touched"""
+
+    def __init__(self, torch, device, ms):
+        self.torch, self.device, self.ms = torch, device, ms
+
+    @contextmanager
+    def __call__(self, key):
+        if self.ms is None:
+            yield
+            return
+        self.torch.cuda.synchronize(self.device)
+        t0 = datetime.datetime.now()
+        yield
+        self.torch.cuda.synchronize(self.device)
+        self.ms[key] = self.ms.get(key, 0.0) + (datetime.datetime.now() - t0).total_seconds() * 1e3
+
+
+# ---- blur and draw -------------------------------------------------------------------------------------------------------------
+
+def blur_rects(ctx, ptrs, sizes, rects_per_image, radius, stream=0):
+    """ONE mdhip_blur_regions call for images in device memory (ptrs, sizes (width, height), rows of 3 * width bytes), changed
+    in place: rects_per_image[k] the (left, top, right, bottom) rectangles of image k, applied in their order.  No call when
+    no image has a rectangle.  -> whether the call was made"""
+    rect_image = [k for k, rects in enumerate(rects_per_image) for _ in rects]
+    if not rect_image:
+        return False
+    ctx.blur_regions(ptrs, sizes, [w * 3 for w, _ in sizes], rect_image, [r for rects in rects_per_image for r in rects], radius,
+                     stream=stream)
+    return True
+
+
+def pack_ops(plans):
+    """The preview.RenderPlan of each image of a batch as the arguments of one mdhip_draw_ops call: -> (op_image, ops, packed) --
+    the image of every row, the rows in the order of the plans, and all label patches in one buffer, a patch that several
+    images share or one image repeats stored once.  RECT rows are the plans' own; PATCH rows get their offset into `packed`."""
+    packed, where, op_image, ops = bytearray(), {}, [], []
+    for k, plan in enumerate(plans):
+        for op in plan.ops:
+            if op[0] == OP_PATCH:
+                data = plan.patch_of(op)
+                if data not in where:
+                    where[data] = len(packed)
+                    packed += data
+                op = op[:5] + [where[data]] + op[6:]
+            op_image.append(k)
+            ops.append(op)
+    return op_image, ops, packed
+
+
+def draw_plans(ctx, ptrs, sizes, plans, device, stream=0, clock=None):
+    """ONE mdhip_draw_ops call that draws plans[k] on image k (in place), after ONE upload of the packed patches on torch's
+    current stream (the caller makes `stream` that one).  No call when the plans hold no operation.  clock: a Clock that
+    times the upload and the call as 'draw' (not the packing, which is host work).  -> whether the call was made"""
+    import numpy as np
+    import torch
+    op_image, ops, packed = pack_ops(plans)
+    if not ops:
+        return False
+    with clock('draw') if clock is not None else nullcontext():
+        patches = torch.from_numpy(np.frombuffer(bytes(packed) or b'\0', np.uint8).copy()).to(device)
+        ctx.draw_ops(ptrs, sizes, [w * 3 for w, _ in sizes], op_image, ops, patches.data_ptr(), len(packed), stream=stream)
+    return True
+
+
+def blur_and_draw(ctx, device, tensors, jobs, clock, radius=DEFAULT_BLUR_RADIUS, stream=0):
+    """blur_rects and then draw_plans for the images `tensors` (flat uint8 device tensors, changed in place) of `jobs`: of each
+    job its 'size', its 'rects' to blur and its 'plan'.  stream: the raw stream the calls go on (the caller makes it torch's
+    current one).  -> (whether it blurred, whether it drew)"""
+    sizes = [j['size'] for j in jobs]
+    ptrs = [t.data_ptr() for t in tensors]
+    blurred = False
+    if any(j['rects'] for j in jobs):
+        with clock('blur'):
+            blurred = blur_rects(ctx, ptrs, sizes, [j['rects'] for j in jobs], radius, stream)
+    return blurred, draw_plans(ctx, ptrs, sizes, [j['plan'] for j in jobs], device, stream, clock)
+
+
+def changed_rectangles(blur_rects, ops):
+    """What a copy's plan changes, as (left, top, right, bottom) with right and bottom exclusive: the blur rectangles as they
+    are, a solid rectangle x0 .. x1, y0 .. y1 (inclusive) of the plan's `ops` as (x0, y0, x1 + 1, y1 + 1), a pasted patch as
+    (x, y, x + w, y + h).  Not clipped: mdhip_jpeg_encode_kept and jpeg_host.keep_merge clip to the image."""
+    out = [tuple(int(v) for v in r) for r in blur_rects]
+    for op in ops:
+        if op[0] == OP_PATCH:
+            out.append((op[1], op[2], op[1] + op[3], op[2] + op[4]))
+        else:
+            out.append((op[1], op[2], op[3] + 1, op[4] + 1))
+    return out
+
+
+# ---- the encoders --------------------------------------------------------------------------------------------------------------
+
+def read_encoded(call, capacity, device, what):
+    """An encoder call into a buffer of `capacity` bytes on `device`, the caller's guess at the output, and a second call with
+    the size the first asked for when the guess was too small.  call(out_ptr, capacity) -> (fits, offsets, sizes, needed,
+    *rest).  -> (the output as a host uint8 array, offsets, sizes, rest)"""
+    import torch
+    for _ in range(2):
+        out = torch.empty(capacity, dtype=torch.uint8, device=device)
+        fits, offs, lens, needed, *rest = call(out.data_ptr(), capacity)
+        if fits:
+            return out[:max(needed, 1)].cpu().numpy(), offs, lens, rest
+        capacity = needed
+    raise RuntimeError('{} asked for {} bytes and refused a buffer of that size'.format(what, needed))
+
+
+def _sampled_guess(sizes):
+    # far below the bound (ctx.jpeg_encode_sampled_bound): half a byte a sample and the 8 x 8 blocks' fixed cost
+    return sum(w * h * 3 // 2 + 64 * ((w + 7) // 8) * ((h + 7) // 8) + 64 for w, h in sizes)
+
+
+def _sampled_file(job, scan):
+    from . import jpeg_host
+    (w, h), (ql, qc) = job['size'], job['quant']
+    return jpeg_host.sampled_file(w, h, ql, qc, job['sampling'], scan, job['exif'], job['comment'])
+
+
+def encode_sampled(ctx, device, tensors, jobs, stream=0):
+    """ONE mdhip_jpeg_encode_sampled call (read_encoded) for the images `tensors` of `jobs`: each with its job's 'size',
+    'sampling' and 'quant' tables, the file written with its 'exif' and 'comment'.  -> the files"""
+    sizes = [j['size'] for j in jobs]
+    host, offs, lens, _ = read_encoded(
+        lambda out_ptr, capacity: ctx.jpeg_encode_sampled([t.data_ptr() for t in tensors], sizes, [w * 3 for w, _ in sizes],
+                                                          [j['sampling'] for j in jobs], [j['quant'] for j in jobs],
+                                                          out_ptr, capacity, stream),
+        _sampled_guess(sizes), device, 'mdhip_jpeg_encode_sampled')
+    return [_sampled_file(j, host[o:o + n].tobytes()) for j, o, n in zip(jobs, offs, lens)]
+
+
+def encode_kept(ctx, device, tensors, jobs, source_ptrs, stream=0):
+    """ONE mdhip_jpeg_encode_kept call (read_encoded) for copies that keep their source's blocks outside their job's 'changed'
+    rectangles; source_ptrs: per job the device pointer to its source's quantised planes.  -> the files; None for a copy the
+    call flagged"""
+    sizes = [j['size'] for j in jobs]
+    rect_image = [k for k, j in enumerate(jobs) for _ in j['changed']]
+    rects = [r for j in jobs for r in j['changed']]
+    host, offs, lens, (status,) = read_encoded(
+        lambda out_ptr, capacity: ctx.jpeg_encode_kept([t.data_ptr() for t in tensors], sizes, [w * 3 for w, _ in sizes],
+                                                       [j['sampling'] for j in jobs], [j['quant'] for j in jobs], source_ptrs,
+                                                       rect_image, rects, out_ptr, capacity, stream),
+        _sampled_guess(sizes), device, 'mdhip_jpeg_encode_kept')
+    return [None if st else _sampled_file(j, host[o:o + n].tobytes()) for j, o, n, st in zip(jobs, offs, lens, status)]
+
+
+# ---- the host leg's share ------------------------------------------------------------------------------------------------------
+
+def blur_with_pil(image, rects, radius=DEFAULT_BLUR_RADIUS):
+    """visualization_utils.blur_detections :509-531 for rectangles with area (blur.blur_rectangle), IN PLACE on a PIL image"""
+    from PIL import ImageFilter
+    for rect in rects:
+        region = image.crop(rect)
+        image.paste(region.filter(ImageFilter.GaussianBlur(radius=radius)), (rect[0], rect[1]))
+
+
+def kept_file_host(pil_image, keep, exif=b''):
+    """The host leg of a copy that keeps its source's blocks: Pillow encodes the modified pixels in memory with the source's
+    tables and sampling, and the file gets Pillow's blocks in every MCU a rectangle of keep['changed'] touches and the source's
+    (keep['coef']) elsewhere, with `exif` as its APP1 block (none when empty).  keep['src']: jpeg_host.keep_source's record.
+    -> the file, or None when no baseline scan holds the merged blocks"""
+    import io
+    from . import jpeg_host
+    src, (width, height) = keep['src'], keep['size']
+    ql, qc = src['quant']
+    bio = io.BytesIO()
+    pil_image.save(bio, 'JPEG', qtables=[[int(v) for v in ql], [int(v) for v in qc]], subsampling=src['sampling'])
+    rc, _, planes = jpeg_host.decode(bio.getvalue())
+    if rc != jpeg_host.MDJPEG_OK or planes.size != keep['coef'].size:
+        return None
+    if jpeg_host.keep_merge(planes, keep['coef'], (width, height), src['sampling'], keep['changed']):
+        return None
+    rc, scans, _, _ = jpeg_host.encode_subsequences([planes], [(width, height)], samplings=[src['sampling']])
+    if rc != jpeg_host.MDJPEG_OK:
+        return None
+    return jpeg_host.sampled_file(width, height, ql, qc, src['sampling'], scans[0], exif, src['comment'])

@@ -44,6 +44,10 @@ PREVIEW_COLORS = (
     'SaddleBrown Green SandyBrown SeaGreen SeaShell Sienna Silver SkyBlue SlateBlue SlateGray SlateGrey Snow SpringGreen '
     'SteelBlue GreenYellow Teal Thistle Tomato Turquoise Violet Wheat White WhiteSmoke Yellow YellowGreen').split()
 
+NUM_DETECTOR_CATEGORIES = 3                     # data_management/annotation_constants.py: animal, person, vehicle
+DEFAULT_CLASSIFICATION_CONFIDENCE_THRESHOLD = 0.3       # render_detection_bounding_boxes' defaults
+MAX_CLASSIFICATIONS = 3
+
 OP_RECT, OP_PATCH = 0, 1                        # csrc/resample.h MD_DRAW_RECT / MD_DRAW_PATCH
 _COORD_LIMIT = 1 << 30                          # operations carry int32 coordinates
 
@@ -243,25 +247,64 @@ def box_edges(bbox, width, height, expansion):
     return left, top, right, bottom
 
 
-def label_box(font, s, left, top, bottom, im_height):
-    """
-    draw_bounding_box_on_image :1052-1131 for ONE label, left- and top-aligned: the padded string, its margin and the filled
-    rectangle (x0, y0, x1, y1 inclusive) the text is drawn into at (x0 + margin, y0 + margin).  Above the box; below it when
-    that leaves the image at the top; inside it when below leaves the image too.
-    """
+def classified_label_lines(det, label_map, classification_label_map,
+                           classification_confidence_threshold=DEFAULT_CLASSIFICATION_CONFIDENCE_THRESHOLD):
+    """render_detection_bounding_boxes :691-769 for one drawn detection: (its label lines -- the detection's, then one per
+    classification at or above the threshold, at most MAX_CLASSIFICATIONS looked at --, the class its colour is of: the
+    detection's category, or NUM_DETECTOR_CATEGORIES + the best classification's)"""
+    clss = det['category']
+    strings = [label_string(det, label_map)]
+    if ('classifications' in det) and len(det['classifications']) > 0:
+        classifications = det['classifications']
+        if len(classifications) > MAX_CLASSIFICATIONS:
+            classifications = classifications[0:MAX_CLASSIFICATIONS]
+        max_category, max_conf = 0, -100
+        if classification_label_map is not None:
+            for class_key, conf in (c[:2] for c in classifications):
+                if conf is None or conf < classification_confidence_threshold:
+                    continue
+                if conf > max_conf:
+                    max_conf, max_category = conf, int(class_key)
+                if class_key in classification_label_map:
+                    class_name = classification_label_map[class_key]
+                elif str(class_key) in classification_label_map:
+                    class_name = classification_label_map[str(class_key)]
+                else:
+                    class_name = str(class_key)
+                strings += ['{}: {}%'.format(class_name.lower(), str(round(100.0 * conf, 1)))]
+        clss = NUM_DETECTOR_CATEGORIES + max_category
+    return strings, clss
+
+
+def stacked_labels(font, strings, left, top, bottom, im_height):
+    """draw_bounding_box_on_image :1052-1131 for the label lines of one box, left- and top-aligned, in the order they are drawn:
+    the last line first, at the bottom, every further line int(text_height + 2 * margin) higher -- above the box, below it when
+    that leaves the image at the top, inside it when below leaves the image too.  Yields (the padded string, its margin, the
+    corners (x0, y0), (x1, y1) of its filled rectangle (inclusive), where its text goes)."""
     import numpy as np
-    total_height = (1 + 2 * 0.05) * text_size(font, s)[1]           # :1055 (of the string WITHOUT its padding)
-    padded = ' ' + s + ' '
-    text_width, text_height = text_size(font, padded)
-    margin = int(np.ceil(0.05 * text_height))
-    text_bottom = top
-    if (text_bottom - total_height) < 0:
-        text_bottom = bottom + total_height
-        if text_bottom > im_height:
-            text_bottom = top + total_height
-    text_bottom = int(text_bottom)
-    text_left = int(left)
-    return padded, margin, (text_left, (text_bottom - text_height) - (2 * margin), text_left + text_width, text_bottom)
+    total_height = (1 + 2 * 0.05) * sum(text_size(font, s)[1] for s in strings)     # :1055 (of the strings WITHOUT their padding)
+    for i_str, s in enumerate(strings[::-1]):
+        if len(s) == 0:                                                              # :1061
+            continue
+        s = ' ' + s + ' '
+        text_width, text_height = text_size(font, s)
+        margin = int(np.ceil(0.05 * text_height))
+        text_bottom = top
+        if (text_bottom - total_height) < 0:
+            text_bottom = bottom + total_height
+            if text_bottom > im_height:
+                text_bottom = top + total_height
+        text_bottom = int(text_bottom) - i_str * (int(text_height + (2 * margin)))
+        text_left = int(left)
+        yield (s, margin, (text_left, (text_bottom - text_height) - (2 * margin)), (text_left + text_width, text_bottom),
+               (text_left + margin, text_bottom - text_height - margin))
+
+
+def label_box(font, s, left, top, bottom, im_height):
+    """stacked_labels for ONE label that is not empty: the padded string, its margin and the filled rectangle (x0, y0, x1, y1
+    inclusive) the text is drawn into at (x0 + margin, y0 + margin)"""
+    padded, margin, (x0, y0), (x1, y1), _ = next(stacked_labels(font, [s], left, top, bottom, im_height))
+    return padded, margin, (x0, y0, x1, y1)
 
 
 class HostLeg(Exception):
@@ -330,12 +373,41 @@ class RenderPlan:
             self.patches += data
         return self._offsets[data]
 
+    def patch_of(self, op):
+        """the pixels a PATCH row pastes"""
+        return bytes(self.patches[op[5]:op[5] + op[3] * op[4] * 3])
 
-def render_plan(detections, width, height, options, label_map=None, labels=True):
+    def extend(self, other):
+        """appends what another plan draws (for the same image) behind what this one draws; a patch both hold is kept once"""
+        for op in other.ops:
+            if op[0] == OP_PATCH:
+                op = op[:5] + [self.add_patch(other.patch_of(op))] + op[6:]
+            self.ops.append(op)
+        self.labels += other.labels
+        self.order += other.order
+        return self
+
+
+def _label_lines(det, label_map, classification_label_map, classification_confidence_threshold):
+    """(the label lines of one drawn detection, the class its colour is of); None for a detection with classifications when
+    they are not asked for (no threshold) or cannot be labelled (no label map)"""
+    if classification_confidence_threshold is None or label_map is None:
+        if 'classifications' in det and len(det['classifications']) > 0:
+            return None
+        return [label_string(det, label_map)], det['category']
+    return classified_label_lines(det, label_map, classification_label_map, classification_confidence_threshold)
+
+
+def render_plan(detections, width, height, options, label_map=None, labels=True, classification_label_map=None,
+                classification_confidence_threshold=None):
     """
     render_detection_bounding_boxes(detections, image, label_map=..., confidence_threshold, thickness, expansion,
-    label_font_size, label_font, box_sort_order) for an image of width x height (the RESIZED size) as a RenderPlan.
-    labels False: label_map=None of the reference (boxes only).  Raises HostLeg or RenderFailure.
+    label_font_size, label_font, box_sort_order) for an image of width x height (the RESIZED size) as a RenderPlan: per box
+    outline_ops, then one patch per label line in the order PIL draws them (stacked_labels).
+    labels False: label_map=None of the reference (boxes only).  classification_confidence_threshold None: a box that carries
+    classifications is a HostLeg; a number: its classification_label_map=, classification_confidence_threshold= are the
+    reference's, and such a box gets a label line per classification and the colour of the best one (classified_label_lines).
+    Raises HostLeg or RenderFailure.
     """
     thickness, expansion, font_size = resolve_sizes(options, width)
     label_map = _label_map(label_map) if labels else None
@@ -345,57 +417,61 @@ def render_plan(detections, width, height, options, label_map=None, labels=True)
     for det in drawn_detections(detections, options):
         if det['conf'] is None:
             raise HostLeg('a detection without a confidence')
-        if 'classifications' in det and len(det['classifications']) > 0:
-            raise HostLeg('classification labels')
         try:
-            color_name, rgb = box_color(det['category'])
+            lines = _label_lines(det, label_map, classification_label_map, classification_confidence_threshold)
+            if lines is None:
+                raise HostLeg('classification labels')
+            strings, clss = lines
+            color_name, rgb = box_color(clss)
         except (TypeError, ValueError) as e:
             raise RenderFailure(str(e))
         left, top, right, bottom = box_edges(det['bbox'], width, height, expansion)
         plan.ops += outline_ops(left, top, right, bottom, thickness, rgb)
-        s = label_string(det, label_map)
-        plan.labels.append(s)
+        plan.labels.append(strings[0])
         plan.order.append(next(i for i, d in enumerate(listed) if d is det))
-        if len(s) == 0:                                                          # :1061
+        if not any(strings):                                                     # :1061
             continue
         if font is None:
             font = load_font(options.label_font, font_size)
-        padded, margin, (x0, y0, x1, y1) = label_box(font, s, left, top, bottom, height)
-        bbox = font.getbbox(padded)
-        if bbox[0] < 0 or bbox[1] < 0:
-            raise HostLeg('ink of {!r} may leave its label'.format(padded))
-        if not all(isinstance(v, int) or float(v).is_integer() for v in (x0, y0, x1, y1)):
-            raise HostLeg('a label of a fractional size')
-        x0, y0, x1, y1 = int(x0), int(y0), int(x1), int(y1)
-        w, h = x1 - x0 + 1, y1 - y0 + 1
-        if w < 1 or h < 1 or w > 32767 or h > 32767:
-            raise HostLeg('a label of {} x {} pixels'.format(w, h))
-        data = label_patch(font, (options.label_font, font_size), padded, margin, (w, h), color_name)
-        plan.ops.append([OP_PATCH, x0, y0, w, h, plan.add_patch(data), 0, 0])
+        for padded, margin, (x0, y0), (x1, y1), _ in stacked_labels(font, strings, left, top, bottom, height):
+            bbox = font.getbbox(padded)
+            if bbox[0] < 0 or bbox[1] < 0:
+                raise HostLeg('ink of {!r} may leave its label'.format(padded))
+            if not all(isinstance(v, int) or float(v).is_integer() for v in (x0, y0, x1, y1)):
+                raise HostLeg('a label of a fractional size')
+            x0, y0, x1, y1 = int(x0), int(y0), int(x1), int(y1)
+            w, h = x1 - x0 + 1, y1 - y0 + 1
+            if w < 1 or h < 1 or w > 32767 or h > 32767:
+                raise HostLeg('a label of {} x {} pixels'.format(w, h))
+            data = label_patch(font, (options.label_font, font_size), padded, margin, (w, h), color_name)
+            plan.ops.append([OP_PATCH, x0, y0, w, h, plan.add_patch(data), 0, 0])
     return plan
 
 
-def render_with_pil(image, detections, options, label_map=None, labels=True):
-    """the same drawing by PIL's own calls in the reference's order (draw_bounding_box_on_image :990-1137), IN PLACE on a
-    PIL image of the resized size: the host leg.  Raises what PIL raises."""
+def render_with_pil(image, detections, options, label_map=None, labels=True, classification_label_map=None,
+                    classification_confidence_threshold=None):
+    """the same drawing by PIL's own calls in the reference's order (render_detection_bounding_boxes :673-796,
+    draw_bounding_box_on_image :990-1137), IN PLACE on a PIL image of the resized size: the host leg.  The arguments are
+    render_plan's; a box with classifications that are not asked for is NotImplementedError.  Raises what PIL raises."""
     from PIL import ImageDraw
     width, height = image.size
     thickness, expansion, font_size = resolve_sizes(options, width)
     label_map = _label_map(label_map) if labels else None
     for det in drawn_detections(detections, options):
-        if 'classifications' in det and len(det['classifications']) > 0:
+        lines = _label_lines(det, label_map, classification_label_map, classification_confidence_threshold)
+        if lines is None:
             raise NotImplementedError('classification labels are not rendered')
-        color_name, _ = box_color(det['category'])
+        strings, clss = lines
+        color_name, _ = box_color(clss)
         draw = ImageDraw.Draw(image)
         left, top, right, bottom = box_edges(det['bbox'], width, height, expansion)
         draw.rectangle([(left, top), (right, bottom)], outline=color_name, width=thickness)
         font = load_font(options.label_font, font_size)
-        s = label_string(det, label_map)
-        if len(s) == 0:
+        if not any(strings):
             continue
-        padded, margin, (x0, y0, x1, y1) = label_box(font, s, left, top, bottom, height)
-        draw.rectangle([(x0, y0), (x1, y1)], fill=color_name)
-        draw.text((x0 + margin, y0 + margin), padded, fill='black', font=font)
+        for padded, _, corner0, corner1, text_at in stacked_labels(font, strings, left, top, bottom, height):
+            draw.rectangle([corner0, corner1], fill=color_name)
+            draw.text(text_at, padded, fill='black', font=font)
     return image
 
 
@@ -443,8 +519,8 @@ def previews_of_device_images(ctx, entries, options, label_map=None, stream=0):
     copied back and PIL saves them (counts['host']).  An image the plan hands to the host leg is copied back as it is and
     PIL renders it (counts['host'] too); one without a file counts as 'skipped'.
     """
-    import numpy as np
     import torch
+    from .device_render import blur_rects, draw_plans
     counts = {'gpu': 0, 'host': 0, 'skipped': 0}
     out = [(None, 'skipped')] * len(entries)
     labels = label_map != NO_LABELS
@@ -479,10 +555,8 @@ def previews_of_device_images(ctx, entries, options, label_map=None, stream=0):
             # a copy only where the source would be changed: something to blur, or nothing to resize (drawn in place)
             sources = [entries[e][0].clone() if rects or size == sizes[k] else entries[e][0] for k, (e, size, _, rects) in enumerate(jobs)]
         blurred = [k for k, job in enumerate(jobs) if job[3]]
-        if blurred:
-            ctx.blur_regions([sources[k].data_ptr() for k in blurred], [sizes[k] for k in blurred], [sizes[k][0] * 3 for k in blurred],
-                             [i for i, k in enumerate(blurred) for _ in jobs[k][3]], [r for k in blurred for r in jobs[k][3]], 40,
-                             stream=ext.cuda_stream)
+        blur_rects(ctx, [sources[k].data_ptr() for k in blurred], [sizes[k] for k in blurred], [jobs[k][3] for k in blurred], 40,
+                   ext.cuda_stream)
         with torch.cuda.stream(ext):
             rendered = [sources[k] if size == sizes[k] else torch.empty(size[0] * size[1] * 3, dtype=torch.uint8, device=device)
                         for k, (_, size, _, _) in enumerate(jobs)]
@@ -491,23 +565,8 @@ def previews_of_device_images(ctx, entries, options, label_map=None, stream=0):
             ctx.resample_lanczos([sources[k].data_ptr() for k in resized], [sizes[k] for k in resized], [sizes[k][0] * 3 for k in resized],
                                  [rendered[k].data_ptr() for k in resized], [jobs[k][1] for k in resized], [jobs[k][1][0] * 3 for k in resized],
                                  stream=ext.cuda_stream)
-        # all patches of the batch in one buffer, a patch once
-        packed, where, op_image, ops = bytearray(), {}, [], []
-        for k, (_, _, plan, _) in enumerate(jobs):
-            for op in plan.ops:
-                if op[0] == OP_PATCH:
-                    data = bytes(plan.patches[op[5]:op[5] + op[3] * op[4] * 3])
-                    if data not in where:
-                        where[data] = len(packed)
-                        packed += data
-                    op = op[:5] + [where[data]] + op[6:]
-                op_image.append(k)
-                ops.append(op)
-        if ops:
-            with torch.cuda.stream(ext):
-                patches = torch.from_numpy(np.frombuffer(bytes(packed) or b'\0', np.uint8).copy()).to(device)
-            ctx.draw_ops([t.data_ptr() for t in rendered], [job[1] for job in jobs], [job[1][0] * 3 for job in jobs], op_image, ops,
-                         patches.data_ptr(), len(packed), stream=ext.cuda_stream)
+        with torch.cuda.stream(ext):
+            draw_plans(ctx, [t.data_ptr() for t in rendered], [job[1] for job in jobs], [job[2] for job in jobs], device, ext.cuda_stream)
         files = files_of_device_images(ctx, [(t, size[0], size[1], entries[e][3]) for t, (e, size, _, _) in zip(rendered, jobs)],
                                        options.quality, ext)
         for (e, _, _, _), pair in zip(jobs, files):
@@ -547,6 +606,7 @@ class PreviewProduct(Product):
         return previews_of_device_images(ctx, entries, self.options, stream=stream)
 
 
-__all__ = ['HostLeg', 'NO_LABELS', 'PreviewOptions', 'RenderFailure', 'RenderPlan', 'box_edges', 'drawn_detections', 'is_rendered',
-           'label_box', 'label_string', 'output_name', 'outline_ops', 'preview_file_of_host_image', 'previews_of_device_images',
-           'rectangles_to_blur', 'render_plan', 'render_with_pil', 'resolve_sizes', 'target_size', 'write_preview']
+__all__ = ['HostLeg', 'NO_LABELS', 'PreviewOptions', 'RenderFailure', 'RenderPlan', 'box_edges', 'classified_label_lines',
+           'drawn_detections', 'is_rendered', 'label_box', 'label_string', 'output_name', 'outline_ops', 'preview_file_of_host_image',
+           'previews_of_device_images', 'rectangles_to_blur', 'render_plan', 'render_with_pil', 'resolve_sizes', 'stacked_labels',
+           'target_size', 'write_preview']

@@ -38,6 +38,7 @@ import traceback
 from . import preview as PV
 from . import repeat_detections as RD
 from .device_decode import decode_chunk, probe
+from .device_render import DECODE_CHUNK_BYTES, Clock, chunked, draw_plans
 
 INDEX_NAME = 'detectionIndex.json'           # reference detection_index_file_name_base
 
@@ -46,8 +47,6 @@ INDEX_NAME = 'detectionIndex.json'           # reference detection_index_file_na
 # resize); 1 GiB is some 25 such sheets -- enough that the one encoder call and the once-per-group decode of a camera's files
 # amortise, small beside the 288 GB of the device and beside a detector that may share it.
 GROUP_DEVICE_BYTES = 1 << 30
-# Decoded pixels of one decode chunk: 256 MiB is 28 files at 3 MP, the size of a detector batch.
-DECODE_CHUNK_BYTES = 256 << 20
 BICUBIC = 0                                  # Image.resize without a filter, for RGB (csrc/resample.h MD_FILTER_BICUBIC)
 SAMPLE_QUALITY = 75                          # Image.save(path) of a JPEG: Pillow's default
 
@@ -275,31 +274,13 @@ def render_sample_host(location, filtering_dir, options):
 
 # ---- the device leg ----------------------------------------------------------------------------------------------------------
 
-class _Clock:
-    """milliseconds per kind of call into counts['ms'], when write_review_folder(profile=True) put that dict there: the device
-    is waited for before and after the timed calls, so a profiled run is slower than a plain one"""
-
-    def __init__(self, torch, device, counts, key):
-        self.sync = (lambda: torch.cuda.synchronize(device)) if 'ms' in counts else None
-        self.ms, self.key = counts.get('ms'), key
-
-    def __enter__(self):
-        if self.sync:
-            self.sync()
-            self.t0 = datetime.datetime.now()
-
-    def __exit__(self, *exc):
-        if self.sync:
-            self.sync()
-            self.ms[self.key] = self.ms.get(self.key, 0.0) + (datetime.datetime.now() - self.t0).total_seconds() * 1e3
-
-
 def _render_group_device(ctx, torch, device, group, probes, filtering_dir, options, counts):
     """The sheets of one group (plans of sample_plan with their RenderPlan under 'draw'): their files decoded once in chunks, per
     chunk one mdhip_thumbnails call and the primaries' calls, one encoder call for the group.  Returns the plans it could not
-    make (MDHIP_EUNSUPPORTED): the host leg makes them."""
-    import numpy as np
+    make (MDHIP_EUNSUPPORTED): the host leg makes them.  With counts['ms'] (write_review_folder(profile=True)) the kinds of
+    call are timed into it (device_render.Clock)."""
     from .crops import encode_windows
+    clock = Clock(torch, device, counts.get('ms'))
     # the sheets (black) and, without tiles, nothing yet: the drawn primary is the image
     sheets = {}
     for p in group:
@@ -311,18 +292,10 @@ def _render_group_device(ctx, torch, device, group, probes, filtering_dir, optio
         for f in [p['file']] + [t[0] for t in p['tiles']]:
             if f not in needed:
                 needed.append(f)
-    chunks, room = [[]], DECODE_CHUNK_BYTES
-    for f in needed:
-        size = probes[f]['size'][0] * probes[f]['size'][1] * 3
-        if chunks[-1] and size > room:
-            chunks.append([])
-            room = DECODE_CHUNK_BYTES
-        chunks[-1].append(f)
-        room -= size
     refused = set()
-    for files in chunks:
+    for files in chunked(needed, lambda f: probes[f]['size'][0] * probes[f]['size'][1] * 3, DECODE_CHUNK_BYTES):
         counts['decode_chunks'] += 1
-        with _Clock(torch, device, counts, 'decode'):
+        with clock('decode'):
             pixels, failed = decode_chunk(ctx, torch, device, options.imageBase, files, probes, counts)
         refused.update(p['name'] for p in group if p['file'] in failed or any(t[0] in failed for t in p['tiles']))
         tiles = []
@@ -342,7 +315,7 @@ def _render_group_device(ctx, torch, device, group, probes, filtering_dir, optio
                                           sheets[p['name']].data_ptr() + (y * sheet_w + x) * 3, sheet_w * 3)))
         tiles = [t for t in tiles if t[0] not in refused]
         while tiles:
-            with _Clock(torch, device, counts, 'thumbnails'):
+            with clock('thumbnails'):
                 ok = ctx.thumbnails([t[1] for t in tiles[:65535]], BICUBIC)
             if ok:
                 counts['tile_calls'] += 1
@@ -361,20 +334,7 @@ def _render_group_device(ctx, torch, device, group, probes, filtering_dir, optio
             continue
         drawn = [pixels[p['file']].clone() for p in prim]
         sizes = [p['image'] for p in prim]
-        packed, where, op_image, ops = bytearray(), {}, [], []
-        for k, p in enumerate(prim):
-            for op in p['draw'].ops:
-                if op[0] == PV.OP_PATCH:
-                    data = bytes(p['draw'].patches[op[5]:op[5] + op[3] * op[4] * 3])
-                    if data not in where:
-                        where[data] = len(packed)
-                        packed += data
-                    op = op[:5] + [where[data]] + op[6:]
-                op_image.append(k)
-                ops.append(op)
-        if ops:
-            patches = torch.from_numpy(np.frombuffer(bytes(packed) or b'\0', np.uint8).copy()).to(device)
-            ctx.draw_ops([t.data_ptr() for t in drawn], sizes, [s[0] * 3 for s in sizes], op_image, ops, patches.data_ptr(), len(packed))
+        draw_plans(ctx, [t.data_ptr() for t in drawn], sizes, [p['draw'] for p in prim], device)
         tiled = [k for k, p in enumerate(prim) if p['layout'] is not None]
         for k, p in enumerate(prim):
             if p['layout'] is None:
@@ -400,7 +360,7 @@ def _render_group_device(ctx, torch, device, group, probes, filtering_dir, optio
     made = [p for p in group if p['name'] not in refused]
     if made:
         dims = [p['layout']['sheet'] if p['layout'] is not None else p['image'] for p in made]
-        with _Clock(torch, device, counts, 'encode'):
+        with clock('encode'):
             files = encode_windows(ctx, [sheets[p['name']].data_ptr() for p in made], [d[0] * 3 for d in dims],
                                    [(0, 0, d[0], d[1]) for d in dims], SAMPLE_QUALITY)
         counts['encode_calls'] += 1

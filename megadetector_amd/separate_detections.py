@@ -11,8 +11,9 @@ file handling (_dispose).  What a manipulated copy is has two legs that write th
 
   backend='host'   exactly the reference's PIL calls: load_image, blur_detections, one render_detection_bounding_boxes per
                    category above threshold in sorted name order, exif_preserving_save(quality='keep').
-  backend='gpu'    per chunk of images: every file decoded once on the device (device_decode), ONE mdhip_blur_regions call, ONE
-                   mdhip_draw_ops call with the concatenated preview.render_plan of the categories, ONE
+  backend='gpu'    the device render path (device_render.py; DESIGN.md, "the device render path"), per chunk of images: every
+                   file decoded once on the device (device_decode), ONE mdhip_blur_regions call, ONE mdhip_draw_ops call with
+                   the preview.render_plan of the categories one behind the other (RenderPlan.extend), ONE
                    mdhip_jpeg_encode_sampled call for all images of the chunk -- each with the sampling and the quantisation
                    tables Pillow's quality='keep' takes from its source file -- and jpeg_host.sampled_file around each scan.
 
@@ -27,9 +28,9 @@ boxes) or when its rendering fails on the device.
 
 keep_source_blocks (not in the reference, off by default): a manipulated copy of a plain RGB JPEG keeps the SOURCE file's
 quantised coefficients in every MCU that no blur rectangle and no drawing operation touches, and only the touched MCUs are
-re-encoded (mdhip_jpeg_encode_kept on the device leg, jpeg_host.keep_merge on the host leg: the same bytes).  Every other copy,
-and one whose merged blocks no baseline scan holds, is written exactly as without the option; the counts say how many of each
-('kept', 'kept_refused').
+re-encoded (device_render.encode_kept on the device leg, device_render.kept_file_host on the host leg: the same bytes).  Every
+other copy, and one whose merged blocks no baseline scan holds, is written exactly as without the option; the counts say how
+many of each ('kept', 'kept_refused').
 
 Not restated: nothing of run_detector_batch changes, there is no multi-GPU sharding, and n_threads applies to the host leg.
 
@@ -45,17 +46,14 @@ import shutil
 import sys
 from functools import partial
 
+from . import device_render as DR
 from . import preview as PV
-from .blur import DEFAULT_BLUR_QUALITY, DEFAULT_BLUR_RADIUS, blur_rectangle
+from .blur import DEFAULT_BLUR_QUALITY, blur_rectangle
 
 friendly_folder_names = {'animal': 'animals', 'person': 'people', 'vehicle': 'vehicles'}
 default_line_thickness = 8
 default_box_expansion = 3
 fallback_detection_threshold = 0.2               # detection/run_detector.py:83
-NUM_DETECTOR_CATEGORIES = 3                      # data_management/annotation_constants.py: animal, person, vehicle
-CLASSIFICATION_CONFIDENCE_THRESHOLD = 0.3        # render_detection_bounding_boxes' defaults
-MAX_CLASSIFICATIONS = 3
-DECODE_CHUNK_BYTES = 256 << 20                   # decoded pixels of one chunk: 28 files at 3 MP
 
 
 class SeparateDetectionsIntoFoldersOptions:
@@ -335,82 +333,6 @@ def category_passes(detections, categories_above_threshold, options):
     return passes
 
 
-def _classified(detections, o):
-    return any('classifications' in d and len(d['classifications']) > 0 for d in PV.drawn_detections(detections, o))
-
-
-def classified_label_lines(det, label_map, classification_label_map, classification_confidence_threshold=CLASSIFICATION_CONFIDENCE_THRESHOLD):
-    """render_detection_bounding_boxes :691-769 for one drawn detection: (its label lines -- the detection's, then one per
-    classification at or above the threshold, at most MAX_CLASSIFICATIONS looked at --, the class its colour is of: the
-    detection's category, or NUM_DETECTOR_CATEGORIES + the best classification's)"""
-    clss = det['category']
-    label = label_map[clss] if clss in label_map else clss
-    strings = ['{}: {}%'.format(label, round(100 * det['conf'])) if det['conf'] is not None else '{}'.format(label)]
-    if ('classifications' in det) and len(det['classifications']) > 0:
-        classifications = det['classifications']
-        if len(classifications) > MAX_CLASSIFICATIONS:
-            classifications = classifications[0:MAX_CLASSIFICATIONS]
-        max_category, max_conf = 0, -100
-        if classification_label_map is not None:
-            for class_key, conf in (c[:2] for c in classifications):
-                if conf is None or conf < classification_confidence_threshold:
-                    continue
-                if conf > max_conf:
-                    max_conf, max_category = conf, int(class_key)
-                if class_key in classification_label_map:
-                    class_name = classification_label_map[class_key]
-                elif str(class_key) in classification_label_map:
-                    class_name = classification_label_map[str(class_key)]
-                else:
-                    class_name = str(class_key)
-                strings += ['{}: {}%'.format(class_name.lower(), str(round(100.0 * conf, 1)))]
-        clss = NUM_DETECTOR_CATEGORIES + max_category
-    return strings, clss
-
-
-def stacked_labels(font, strings, left, top, bottom, height):
-    """draw_bounding_box_on_image :1052-1131 for the label lines of one box, left- and top-aligned, in the order they are drawn:
-    the last line first, at the bottom, every further line int(text_height + 2 * margin) higher -- above the box, below it when
-    that leaves the image at the top, inside it when below leaves the image too.  Yields (the padded string, its margin, the
-    corners (x0, y0), (x1, y1) of its filled rectangle, where its text goes)."""
-    import numpy as np
-    total_height = (1 + 2 * 0.05) * sum(PV.text_size(font, s)[1] for s in strings)
-    for i_str, s in enumerate(strings[::-1]):
-        if len(s) == 0:
-            continue
-        s = ' ' + s + ' '
-        text_width, text_height = PV.text_size(font, s)
-        margin = int(np.ceil(0.05 * text_height))
-        text_bottom = top
-        if (text_bottom - total_height) < 0:
-            text_bottom = bottom + total_height
-            if text_bottom > height:
-                text_bottom = top + total_height
-        text_bottom = int(text_bottom) - i_str * (int(text_height + (2 * margin)))
-        text_left = int(left)
-        yield (s, margin, (text_left, (text_bottom - text_height) - (2 * margin)), (text_left + text_width, text_bottom),
-               (text_left + margin, text_bottom - text_height - margin))
-
-
-def _render_classified_with_pil(image, detections, o, label_map, classification_label_map,
-                                classification_confidence_threshold=CLASSIFICATION_CONFIDENCE_THRESHOLD):
-    """render_detection_bounding_boxes :673-796 and draw_bounding_box_on_image :990-1137 for detections that carry
-    classifications: several label lines per box, stacked from the bottom up, and the colour of the best classification"""
-    from PIL import ImageDraw
-    width, height = image.size
-    thickness, expansion, font_size = PV.resolve_sizes(o, width)
-    for det in PV.drawn_detections(detections, o):
-        strings, clss = classified_label_lines(det, label_map, classification_label_map, classification_confidence_threshold)
-        color = PV.PREVIEW_COLORS[int(clss) % len(PV.PREVIEW_COLORS)]
-        draw = ImageDraw.Draw(image)
-        left, top, right, bottom = PV.box_edges(det['bbox'], width, height, expansion)
-        draw.rectangle([(left, top), (right, bottom)], outline=color, width=thickness)
-        font = PV.load_font(o.label_font, font_size)
-        for s, _, corner0, corner1, text_at in stacked_labels(font, strings, left, top, bottom, height):
-            draw.rectangle([corner0, corner1], fill=color)
-            draw.text(text_at, s, fill='black', font=font)
-
-
 def exif_preserving_save(pil_image, output_file, quality='keep', default_quality=DEFAULT_BLUR_QUALITY):
     """visualization_utils.py:196-301 with its default arguments: EXIF kept, the quality 'kept' only for a JPEG source; once
     more without the quality, then without the EXIF block"""
@@ -440,37 +362,22 @@ def exif_preserving_save(pil_image, output_file, quality='keep', default_quality
         pil_image.save(output_file)
 
 
-class _HostLeg(Exception):
-    """this copy is not one the device restates"""
+def rectangles_to_blur(detections, options, width, height):
+    """the rectangles with area of detections_to_blur, in the order they are applied"""
+    rects = [blur_rectangle(d['bbox'], width, height) for d in detections_to_blur(detections, options)]
+    return [r for r in rects if r is not None]
 
 
-def changed_rectangles(blur_rects, ops):
-    """What a copy's plan changes, as (left, top, right, bottom) with right and bottom exclusive: the blur rectangles as they
-    are, a solid rectangle x0 .. x1, y0 .. y1 (inclusive) as (x0, y0, x1 + 1, y1 + 1), a pasted patch as (x, y, x + w, y + h).
-    Not clipped: mdhip_jpeg_encode_kept and jpeg_host.keep_merge clip to the image."""
-    out = [tuple(int(v) for v in r) for r in blur_rects]
-    for op in ops:
-        if op[0] == PV.OP_PATCH:
-            out.append((op[1], op[2], op[1] + op[3], op[2] + op[4]))
-        else:
-            out.append((op[1], op[2], op[3] + 1, op[4] + 1))
-    return out
-
-
-def _plan_ops(detections, categories_above_threshold, options, width, height):
-    """the drawing operations of a copy and their patches (preview.render_plan of every category pass); raises _HostLeg"""
-    ops, patches = [], []
+def _plan(detections, categories_above_threshold, options, width, height):
+    """what is drawn on a copy as ONE preview.RenderPlan: the render_plan of every category pass, one behind the other.  Raises
+    preview.HostLeg, also where the reference's own drawing raises (the host leg then raises it as the reference does)."""
+    plan = PV.RenderPlan()
     try:
         for category_detections, o, label_map, labels in category_passes(detections, categories_above_threshold, options):
-            plan = PV.render_plan(category_detections, width, height, o, label_map, labels)
-            for op in plan.ops:
-                if op[0] == PV.OP_PATCH:
-                    patches.append(bytes(plan.patches[op[5]:op[5] + op[3] * op[4] * 3]))
-                    op = op[:5] + [len(patches) - 1] + op[6:]
-                ops.append(op)
-    except (PV.HostLeg, PV.RenderFailure) as e:
-        raise _HostLeg(str(e))
-    return ops, patches
+            plan.extend(PV.render_plan(category_detections, width, height, o, label_map, labels))
+    except PV.RenderFailure as e:
+        raise PV.HostLeg(str(e))
+    return plan
 
 
 def keep_source_record(source_path, target_path):
@@ -504,20 +411,17 @@ def _keep_plan_host(source_path, target_path, detections, categories_above_thres
         return None
     width, height = keep['size']
     try:
-        ops, _ = _plan_ops(detections, categories_above_threshold, options, width, height)
+        plan = _plan(detections, categories_above_threshold, options, width, height)
     except Exception:
         return None
-    rects = [blur_rectangle(d['bbox'], width, height) for d in detections_to_blur(detections, options)]
-    keep['changed'] = changed_rectangles([r for r in rects if r is not None], ops)
+    keep['changed'] = DR.changed_rectangles(rectangles_to_blur(detections, options, width, height), plan.ops)
     return keep
 
 
 def save_kept_host(pil_image, target_path, keep):
-    """The host leg of a kept copy: Pillow encodes the modified pixels in memory with the source's tables and sampling, and the
-    file gets Pillow's blocks in every MCU a rectangle of keep['changed'] touches and the source's elsewhere.  -> 'kept', or
-    'kept_refused' when no baseline scan holds the merged blocks (nothing is written; the caller saves the copy as without
-    the option)"""
-    data = kept_file_host(pil_image, keep, keep['src']['exif'])
+    """The host leg of a kept copy (device_render.kept_file_host, with the source's EXIF block).  -> 'kept', or 'kept_refused'
+    when no baseline scan holds the merged blocks (nothing is written; the caller saves the copy as without the option)"""
+    data = DR.kept_file_host(pil_image, keep, keep['src']['exif'])
     if data is None:
         return 'kept_refused'
     with open(target_path, 'wb') as f:
@@ -525,46 +429,21 @@ def save_kept_host(pil_image, target_path, keep):
     return 'kept'
 
 
-def kept_file_host(pil_image, keep, exif=b''):
-    """save_kept_host's file as bytes, with `exif` as its APP1 block (none when empty); None where that says 'kept_refused'"""
-    import io
-    from . import jpeg_host
-    src, (width, height) = keep['src'], keep['size']
-    ql, qc = src['quant']
-    bio = io.BytesIO()
-    pil_image.save(bio, 'JPEG', qtables=[[int(v) for v in ql], [int(v) for v in qc]], subsampling=src['sampling'])
-    rc, _, planes = jpeg_host.decode(bio.getvalue())
-    if rc != jpeg_host.MDJPEG_OK or planes.size != keep['coef'].size:
-        return None
-    if jpeg_host.keep_merge(planes, keep['coef'], (width, height), src['sampling'], keep['changed']):
-        return None
-    rc, scans, _, _ = jpeg_host.encode_subsequences([planes], [(width, height)], samplings=[src['sampling']])
-    if rc != jpeg_host.MDJPEG_OK:
-        return None
-    return jpeg_host.sampled_file(width, height, ql, qc, src['sampling'], scans[0], exif, src['comment'])
-
-
 def render_host(source_path, target_path, detections, categories_above_threshold, options):
     """:432-500 by the reference's own PIL calls: the host leg of one manipulated copy.  -> None, or with keep_source_blocks
     'kept' / 'kept_refused' for an eligible copy"""
-    from PIL import ImageFilter
     from .feed import load_image
     keep = None
     if getattr(options, 'keep_source_blocks', False):
         keep = _keep_plan_host(source_path, target_path, detections, categories_above_threshold, options)
     pil_image = load_image(source_path)
-    for d in detections_to_blur(detections, options):                     # visualization_utils.blur_detections :509-531
-        rect = blur_rectangle(d['bbox'], pil_image.size[0], pil_image.size[1])
-        if rect is None:
-            continue
-        region = pil_image.crop(rect)
-        pil_image.paste(region.filter(ImageFilter.GaussianBlur(radius=DEFAULT_BLUR_RADIUS)), (rect[0], rect[1]))
+    DR.blur_with_pil(pil_image, rectangles_to_blur(detections, options, pil_image.size[0], pil_image.size[1]))
+    # (the classifications are on the boxes only with classification folders and show_box_labels: category_passes)
     classification_label_map = options.classification_categories if using_classification_folders(options) else None
     for category_detections, o, label_map, labels in category_passes(detections, categories_above_threshold, options):
-        if labels and _classified(category_detections, o):
-            _render_classified_with_pil(pil_image, category_detections, o, label_map, classification_label_map)
-        else:
-            PV.render_with_pil(pil_image, category_detections, o, label_map=label_map, labels=labels)
+        PV.render_with_pil(pil_image, category_detections, o, label_map=label_map, labels=labels,
+                           classification_label_map=classification_label_map,
+                           classification_confidence_threshold=PV.DEFAULT_CLASSIFICATION_CONFIDENCE_THRESHOLD)
     kept = save_kept_host(pil_image, target_path, keep) if keep is not None else None
     if kept != 'kept':
         exif_preserving_save(pil_image, target_path)
@@ -637,112 +516,46 @@ def _render_job_host(job, options):
 # ---- the device leg ----------------------------------------------------------------------------------------------------------------
 
 def _plan_job(job, options):
-    """What the device needs for one manipulated copy, before any pixel is decoded; raises _HostLeg (or whatever opening the
-    file raises: the host leg then raises it as the reference does)."""
+    """What the device needs for one manipulated copy, before any pixel is decoded; raises preview.HostLeg (or whatever opening
+    the file raises: the host leg then raises it as the reference does)."""
     from PIL import Image
     from . import jpeg_host
     from .device_decode import probe
     ext = os.path.splitext(job['target'])[1].lower()
     if Image.registered_extensions().get(ext) != 'JPEG':
-        raise _HostLeg('not a JPEG name')
+        raise PV.HostLeg('not a JPEG name')
     p = probe(job['source'], keep_data=True)
     if p['scan'] is None:
-        raise _HostLeg('a file the device does not decode')
+        raise PV.HostLeg('a file the device does not decode')
     src = jpeg_host.keep_source(job['source'], p['data'])
     if src['keep'] and src['quant'] is None:
-        raise _HostLeg('tables or a sampling the device does not restate')
+        raise PV.HostLeg('tables or a sampling the device does not restate')
     if len(src['exif']) > 65533 or len(src['comment'] or b'') > 65533:
-        raise _HostLeg('an EXIF block or a comment Pillow refuses')
+        raise PV.HostLeg('an EXIF block or a comment Pillow refuses')
     if max(p['size']) > 65535:
-        raise _HostLeg('a side above 65535 pixels')
+        raise PV.HostLeg('a side above 65535 pixels')
     width, height = p['size']
     if src['keep']:
         job['sampling'], job['quant'] = src['sampling'], src['quant']
     else:
         job['sampling'], job['quant'] = 2, list(jpeg_host.quant_tables(DEFAULT_BLUR_QUALITY))
     job['exif'], job['comment'], job['size'], job['probe'] = src['exif'], src['comment'], (width, height), p
-    rects = [blur_rectangle(d['bbox'], width, height) for d in detections_to_blur(job['detections'], options)]
-    job['rects'] = [r for r in rects if r is not None]
-    job['ops'], job['patches'] = _plan_ops(job['detections'], job['categories'], options, width, height)
+    job['rects'] = rectangles_to_blur(job['detections'], options, width, height)
+    job['plan'] = _plan(job['detections'], job['categories'], options, width, height)
     # eligible for keep_source_blocks: an RGB JPEG saved with its own tables and sampling (the decoder's verdict comes with the chunk)
     job['keep'] = bool(getattr(options, 'keep_source_blocks', False) and src['keep'])
     if job['keep']:
-        job['changed'] = changed_rectangles(job['rects'], job['ops'])
+        job['changed'] = DR.changed_rectangles(job['rects'], job['plan'].ops)
 
 
-def _encode_sampled(ctx, torch, device, tensors, jobs, stream=0):
-    """ONE mdhip_jpeg_encode_sampled call for the chunk, and a second one with the size the first asked for when the guess at
-    the output was too small.  -> the files"""
-    from . import jpeg_host
-    sizes = [j['size'] for j in jobs]
-    capacity = sum(w * h * 3 // 2 + 64 * ((w + 7) // 8) * ((h + 7) // 8) + 64 for w, h in sizes)
-    for _ in range(2):
-        out = torch.empty(capacity, dtype=torch.uint8, device=device)
-        fits, offs, lens, needed = ctx.jpeg_encode_sampled([t.data_ptr() for t in tensors], sizes, [w * 3 for w, _ in sizes],
-                                                           [j['sampling'] for j in jobs], [j['quant'] for j in jobs],
-                                                           out.data_ptr(), capacity, stream)
-        if fits:
-            host = out[:max(needed, 1)].cpu().numpy()
-            return [jpeg_host.sampled_file(w, h, j['quant'][0], j['quant'][1], j['sampling'], host[o:o + n].tobytes(), j['exif'], j['comment'])
-                    for (w, h), j, o, n in zip(sizes, jobs, offs, lens)]
-        capacity = needed
-    raise RuntimeError('mdhip_jpeg_encode_sampled asked for {} bytes and refused a buffer of that size'.format(needed))
-
-
-def _encode_kept(ctx, torch, device, tensors, jobs, coefficients, stream=0):
-    """ONE mdhip_jpeg_encode_kept call for the chunk's eligible copies (and a second one when the guess at the output was too
-    small).  -> the files; None for a copy the call flagged"""
-    from . import jpeg_host
-    sizes = [j['size'] for j in jobs]
-    capacity = sum(w * h * 3 // 2 + 64 * ((w + 7) // 8) * ((h + 7) // 8) + 64 for w, h in sizes)
-    rect_image = [k for k, j in enumerate(jobs) for _ in j['changed']]
-    rects = [r for j in jobs for r in j['changed']]
-    for _ in range(2):
-        out = torch.empty(capacity, dtype=torch.uint8, device=device)
-        fits, offs, lens, needed, status = ctx.jpeg_encode_kept([t.data_ptr() for t in tensors], sizes, [w * 3 for w, _ in sizes],
-                                                                [j['sampling'] for j in jobs], [j['quant'] for j in jobs],
-                                                                [coefficients[j['file']][0] for j in jobs], rect_image, rects,
-                                                                out.data_ptr(), capacity, stream)
-        if fits:
-            host = out[:max(needed, 1)].cpu().numpy()
-            return [None if st else jpeg_host.sampled_file(w, h, j['quant'][0], j['quant'][1], j['sampling'], host[o:o + n].tobytes(),
-                                                           j['exif'], j['comment'])
-                    for (w, h), j, o, n, st in zip(sizes, jobs, offs, lens, status)]
-        capacity = needed
-    raise RuntimeError('mdhip_jpeg_encode_kept asked for {} bytes and refused a buffer of that size'.format(needed))
-
-
-def blur_and_draw(ctx, torch, device, tensors, jobs, clock, radius=DEFAULT_BLUR_RADIUS, stream=0):
-    """ONE mdhip_blur_regions call and then ONE mdhip_draw_ops call for the images `tensors` (flat uint8 device tensors, changed
-    in place) of `jobs`: of each job its 'size', its 'rects' to blur and its 'ops' with their 'patches' (_plan_ops); a patch
-    that several images share is uploaded once.  stream: the raw stream the calls go on (the caller makes it torch's current one)"""
-    import numpy as np
-    sizes = [j['size'] for j in jobs]
-    pitches = [w * 3 for w, _ in sizes]
-    ptrs = [t.data_ptr() for t in tensors]
-    rect_image = [k for k, j in enumerate(jobs) for _ in j['rects']]
-    if rect_image:
-        with clock('blur'):
-            ctx.blur_regions(ptrs, sizes, pitches, rect_image, [r for j in jobs for r in j['rects']], radius, stream)
-    packed, where, op_image, ops = bytearray(), {}, [], []
-    for k, j in enumerate(jobs):
-        for op in j['ops']:
-            if op[0] == PV.OP_PATCH:
-                data = j['patches'][op[5]]
-                if data not in where:
-                    where[data] = len(packed)
-                    packed += data
-                op = op[:5] + [where[data]] + op[6:]
-            op_image.append(k)
-            ops.append(op)
-    if ops:
-        with clock('draw'):
-            patches = torch.from_numpy(np.frombuffer(bytes(packed) or b'\0', np.uint8).copy()).to(device)
-            ctx.draw_ops(ptrs, sizes, pitches, op_image, ops, patches.data_ptr(), len(packed), stream)
+def _job_bytes(job):
+    """device bytes of a planned copy in its decode chunk: its pixels and, when it keeps its source's blocks, the coefficients
+    that stay on the device with them"""
+    return job['size'][0] * job['size'][1] * 3 + (2 * int(job['probe']['scan'].coef_count) if job['keep'] else 0)
 
 
 def _render_chunk_device(ctx, torch, device, jobs, options, counts, clock):
-    """The manipulated copies of one chunk.  -> the jobs the host leg has to make"""
+    """The manipulated copies of one chunk, by the device render path (device_render).  -> the jobs the host leg has to make"""
     from .device_decode import decode_chunk
     names = [j['file'] for j in jobs]
     probes = {j['file']: j['probe'] for j in jobs}
@@ -755,21 +568,24 @@ def _render_chunk_device(ctx, torch, device, jobs, options, counts, clock):
     if not jobs:
         return refused
     tensors = [pixels[j['file']] for j in jobs]
-    blur_and_draw(ctx, torch, device, tensors, jobs, clock)
+    DR.blur_and_draw(ctx, device, tensors, jobs, clock)
     files = [None] * len(jobs)
     kept = [k for k, j in enumerate(jobs) if j['keep'] and j['file'] in coefficients]
     if kept:
         with clock('encode_kept'):
-            for k, data in zip(kept, _encode_kept(ctx, torch, device, [tensors[k] for k in kept], [jobs[k] for k in kept], coefficients)):
-                files[k] = data
+            made = DR.encode_kept(ctx, device, [tensors[k] for k in kept], [jobs[k] for k in kept],
+                                  [coefficients[jobs[k]['file']][0] for k in kept])
+        for k, data in zip(kept, made):
+            files[k] = data
         counts['encode_calls'] += 1
         counts['kept'] += sum(files[k] is not None for k in kept)
         counts['kept_refused'] += sum(files[k] is None for k in kept)
     rest = [k for k in range(len(jobs)) if files[k] is None]              # (a copy the kept call flagged is re-encoded whole)
     if rest:
         with clock('encode'):
-            for k, data in zip(rest, _encode_sampled(ctx, torch, device, [tensors[k] for k in rest], [jobs[k] for k in rest])):
-                files[k] = data
+            made = DR.encode_sampled(ctx, device, [tensors[k] for k in rest], [jobs[k] for k in rest])
+        for k, data in zip(rest, made):
+            files[k] = data
         counts['encode_calls'] += 1
     for j, data in zip(jobs, files):
         with open(j['target'], 'wb') as f:
@@ -780,23 +596,10 @@ def _render_chunk_device(ctx, torch, device, jobs, options, counts, clock):
 
 def _render_device(jobs, options, ctx, counts, profile):
     """-> the jobs that go to the host leg"""
-    import datetime
     import torch
-    from contextlib import contextmanager
     from ._lib import HipError
     device = torch.device('cuda:{}'.format(ctx.device))
-
-    @contextmanager
-    def clock(key):
-        if not profile:
-            yield
-            return
-        torch.cuda.synchronize(device)
-        t0 = datetime.datetime.now()
-        yield
-        torch.cuda.synchronize(device)
-        counts['ms'][key] = counts['ms'].get(key, 0.0) + (datetime.datetime.now() - t0).total_seconds() * 1e3
-
+    clock = DR.Clock(torch, device, counts['ms'] if profile else None)
     host, planned = [], []
     for job in jobs:
         try:
@@ -804,21 +607,10 @@ def _render_device(jobs, options, ctx, counts, profile):
             planned.append(job)
         except Exception:
             host.append(job)                                              # (what the reference raises, the host leg raises)
-    chunks, room, seen = [[]], DECODE_CHUNK_BYTES, set()
-    for job in planned:
-        size = job['size'][0] * job['size'][1] * 3
-        if job['keep']:                                                   # its coefficients stay on the device with its pixels
-            size += 2 * int(job['probe']['scan'].coef_count)
-        if chunks[-1] and (size > room or job['file'] in seen):           # (a file twice in the results: its copies in two chunks)
-            chunks.append([])
-            room, seen = DECODE_CHUNK_BYTES, set()
-        chunks[-1].append(job)
-        seen.add(job['file'])
-        room -= size
+    # (a file twice in the results: its copies in two chunks)
+    chunks = DR.chunked(planned, _job_bytes, DR.DECODE_CHUNK_BYTES, lambda chunk, job: any(j['file'] == job['file'] for j in chunk))
     with torch.cuda.device(device):
         for chunk in chunks:
-            if not chunk:
-                continue
             counts['decode_chunks'] += 1
             try:
                 host += _render_chunk_device(ctx, torch, device, chunk, options, counts, clock)

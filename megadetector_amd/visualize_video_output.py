@@ -27,8 +27,9 @@ standard Huffman tables written in where it implies them (jpeg_host.with_standar
 A frame has two legs that write the same bytes:
   backend='host'   Pillow: feed.load_image of the stored JPEG, blur_detections, the reference's drawing, Image.save with
                    qtables= / subsampling= or quality=.
-  backend='gpu'    per chunk of frames -- of one video or of several, each with its own size, sampling and tables -- on a
-                   context without a model: the frames decoded once (device_decode.decode_scans), ONE mdhip_blur_regions call,
+  backend='gpu'    the device render path (device_render.py; DESIGN.md, "the device render path"), per chunk of frames -- of
+                   one video or of several, each with its own size, sampling and tables -- on a context without a model: the
+                   frames decoded once (device_decode.decode_scans), ONE mdhip_blur_regions call,
                    ONE mdhip_draw_ops call, ONE mdhip_jpeg_encode_kept and ONE mdhip_jpeg_encode_sampled call, and
                    jpeg_host.sampled_file around each scan.  A frame the device does not restate -- a box thinner than its
                    outline, a stored frame the decoder does not take or flags, tables or a sampling sampled_file does not
@@ -54,8 +55,8 @@ import random
 import sys
 import unicodedata
 
+from . import device_render as DR
 from . import preview as PV
-from . import separate_detections as SD
 from .avi import AviError, AviFile, write_mjpeg_avi
 from .blur import DEFAULT_BLUR_RADIUS, BlurOptions, blur_rectangle, select_detections
 from .constants import DEFAULT_DETECTOR_LABEL_MAP
@@ -68,7 +69,6 @@ SKIPPED_STRING = 'Skipped'
 NOT_MJPEG_STRING = 'not a Motion-JPEG AVI'
 VIDEO_EXTENSIONS = ('.mp4', '.avi', '.mpeg', '.mpg', '.mov', '.mkv', '.flv')        # detection/video_utils.py:35
 DEFAULT_HOST_QUALITY = 85                                 # exif_preserving_save's default_quality: a frame that is no RGB JPEG
-DECODE_CHUNK_BYTES = 256 << 20                            # decoded pixels of one chunk: 97 frames of 1280 x 720
 _VALID_FILENAME_CHARS = '~-_.() abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789'       # utils/path_utils.py:46
 
 
@@ -372,68 +372,26 @@ class FramePlanner:
         """whether anything is drawn on or blurred in a frame of this size with these detections"""
         return len(PV.drawn_detections(detections, self.draw)) > 0 or len(self.rectangles(detections, width, height)) > 0
 
-    def lines(self, det):
-        """(the label lines of one drawn detection, the class its colour is of): separate_detections.classified_label_lines
-        with the tool's classification_confidence_threshold"""
-        return SD.classified_label_lines(det, self.label_map, self.classification_label_map,
-                                         self.options.classification_confidence_threshold)
-
-    def classified(self, detections):
-        return any('classifications' in d and len(d['classifications']) > 0 for d in PV.drawn_detections(detections, self.draw))
-
     def draw_with_pil(self, image, detections):
         """render_detection_bounding_boxes(detections, image, detector_label_map, classification_label_map,
-        classification_confidence_threshold=...) by PIL's own calls in the reference's order, IN PLACE: the restatement
-        separate_detections keeps, with the tool's threshold"""
-        SD._render_classified_with_pil(image, detections, self.draw, self.label_map, self.classification_label_map,
-                                       self.options.classification_confidence_threshold)
+        classification_confidence_threshold=...) by PIL's own calls in the reference's order, IN PLACE"""
+        PV.render_with_pil(image, detections, self.draw, self.label_map, classification_label_map=self.classification_label_map,
+                           classification_confidence_threshold=self.options.classification_confidence_threshold)
 
-    def plan_classified(self, detections, width, height):
-        """draw_with_pil as a preview.RenderPlan, for a frame whose boxes carry classifications: per box preview.outline_ops,
-        then one patch per label line in the order PIL draws them (separate_detections.stacked_labels).  Raises
-        preview.HostLeg or preview.RenderFailure."""
-        o = self.draw
-        thickness, expansion, font_size = PV.resolve_sizes(o, width)
-        font = PV.load_font(o.label_font, font_size)
-        plan = PV.RenderPlan()
-        for det in PV.drawn_detections(detections, o):
-            if det['conf'] is None:
-                raise PV.HostLeg('a detection without a confidence')
-            try:
-                strings, clss = self.lines(det)
-                color_name, rgb = PV.box_color(clss)
-            except (TypeError, ValueError) as e:
-                raise PV.RenderFailure(str(e))
-            left, top, right, bottom = PV.box_edges(det['bbox'], width, height, expansion)
-            plan.ops += PV.outline_ops(left, top, right, bottom, thickness, rgb)
-            for padded, margin, (x0, y0), (x1, y1), _ in SD.stacked_labels(font, strings, left, top, bottom, height):
-                bbox = font.getbbox(padded)
-                if bbox[0] < 0 or bbox[1] < 0:
-                    raise PV.HostLeg('ink of {!r} may leave its label'.format(padded))
-                if not all(isinstance(v, int) or float(v).is_integer() for v in (x0, y0, x1, y1)):
-                    raise PV.HostLeg('a label of a fractional size')
-                x0, y0, x1, y1 = int(x0), int(y0), int(x1), int(y1)
-                w, h = x1 - x0 + 1, y1 - y0 + 1
-                if w < 1 or h < 1 or w > 32767 or h > 32767:
-                    raise PV.HostLeg('a label of {} x {} pixels'.format(w, h))
-                data = PV.label_patch(font, (o.label_font, font_size), padded, margin, (w, h), color_name)
-                plan.ops.append([PV.OP_PATCH, x0, y0, w, h, plan.add_patch(data), 0, 0])
-        return plan
+    def plan(self, detections, width, height):
+        """draw_with_pil as a preview.RenderPlan, what device_render.blur_and_draw draws.  Raises preview.HostLeg or
+        preview.RenderFailure."""
+        return PV.render_plan(detections, width, height, self.draw, self.label_map,
+                              classification_label_map=self.classification_label_map,
+                              classification_confidence_threshold=self.options.classification_confidence_threshold)
 
     def ops(self, detections, width, height):
-        """the drawing operations of a frame and their patches, as separate_detections.blur_and_draw takes them: the plan of
-        preview.render_plan, or plan_classified where a drawn box carries classifications"""
-        if self.classified(detections):
-            plan = self.plan_classified(detections, width, height)
-        else:
-            plan = PV.render_plan(detections, width, height, self.draw, self.label_map, True)
-        ops, patches = [], []
-        for op in plan.ops:
-            if op[0] == PV.OP_PATCH:
-                patches.append(bytes(plan.patches[op[5]:op[5] + op[3] * op[4] * 3]))
-                op = op[:5] + [len(patches) - 1] + op[6:]
-            ops.append(op)
-        return ops, patches
+        """plan() for a caller that wants the rows and the patches apart: (the rows, a PATCH row's column 5 the index of its
+        patch; the patches as a list of bytes).  The device leg takes the plan itself."""
+        plan = self.plan(detections, width, height)
+        patches = [plan.patch_of(op) for op in plan.ops if op[0] == PV.OP_PATCH]
+        at = iter(range(len(patches)))
+        return [op[:5] + [next(at)] + op[6:] if op[0] == PV.OP_PATCH else op for op in plan.ops], patches
 
 
 # ---- one frame -------------------------------------------------------------------------------------------------------------------
@@ -464,7 +422,6 @@ def passes_through(data, detections, planner):
 def render_frame_host(data, detections, planner):
     """The host leg of one frame that does not pass through: `data` is jpeg_host.with_standard_tables(the stored frame).
     -> the JPEG file of the output frame.  Raises what Pillow raises."""
-    from PIL import ImageFilter
     from . import jpeg_host
     from .feed import load_image
     options = planner.options
@@ -476,19 +433,17 @@ def render_frame_host(data, detections, planner):
         src = _keep_source(data)
         if options.keep_source_blocks and src['quant'] is not None:
             try:
-                ops, _ = planner.ops(detections, width, height)
+                changed = DR.changed_rectangles(rects, planner.plan(detections, width, height).ops)
                 rc, _, coef = jpeg_host.decode(data)
                 if rc == jpeg_host.MDJPEG_OK:
-                    keep = {'src': src, 'coef': coef, 'size': (width, height), 'changed': SD.changed_rectangles(rects, ops)}
+                    keep = {'src': src, 'coef': coef, 'size': (width, height), 'changed': changed}
             except Exception:
                 keep = None                              # (a drawing the plan does not restate: the frame is encoded whole)
-    for rect in rects:                                   # visualization_utils.blur_detections :509-531
-        region = pil_image.crop(rect)
-        pil_image.paste(region.filter(ImageFilter.GaussianBlur(radius=options.blur_radius)), (rect[0], rect[1]))
+    DR.blur_with_pil(pil_image, rects, options.blur_radius)
     if detections:
         planner.draw_with_pil(pil_image, detections)
     if keep is not None:
-        kept = SD.kept_file_host(pil_image, keep)
+        kept = DR.kept_file_host(pil_image, keep)
         if kept is not None:
             return kept
     out = io.BytesIO()
@@ -504,50 +459,47 @@ def render_frame_host(data, detections, planner):
     return out.getvalue()
 
 
-class _HostLeg(Exception):
-    """this frame is not one the device restates"""
-
-
 def plan_frame_device(data, detections, planner):
     """What the device needs for one frame that does not pass through, before any pixel is decoded: a job for
-    separate_detections.blur_and_draw and its encoders.  Raises _HostLeg."""
+    device_render.blur_and_draw and its encoders.  Raises preview.HostLeg, also where the reference's own drawing raises (the
+    host leg then raises it as the reference does)."""
     from . import jpeg_host
     from .feed import open_for_coefficients
     options = planner.options
     try:
         image, rotation = open_for_coefficients(io.BytesIO(data))
     except Exception as e:
-        raise _HostLeg(str(e))
+        raise PV.HostLeg(str(e))
     if image.format != 'JPEG' or image.mode != 'RGB' or rotation != 0:
-        raise _HostLeg('not a plain RGB JPEG')
+        raise PV.HostLeg('not a plain RGB JPEG')
     rc, scan, reason = jpeg_host.ScanImage.from_bytes(data, 0)
     if rc != jpeg_host.MDJPEG_OK:
-        raise _HostLeg('a frame the device does not decode: {}'.format(reason))
+        raise PV.HostLeg('a frame the device does not decode: {}'.format(reason))
     width, height = image.size
     job = {'size': (width, height), 'scan': scan, 'exif': b'', 'keep': False}
     if options.quality == 'keep':
         src = _keep_source(data)
         if src['quant'] is None:
-            raise _HostLeg('tables or a sampling the device does not restate')
+            raise PV.HostLeg('tables or a sampling the device does not restate')
         job['sampling'], job['quant'], job['comment'] = src['sampling'], src['quant'], src['comment']
     else:
         comment = image.info.get('comment')
         if len(comment or b'') > 65533 or max(width, height) > 65535:
-            raise _HostLeg('a comment or a size Pillow refuses')
+            raise PV.HostLeg('a comment or a size Pillow refuses')
         job['sampling'], job['quant'], job['comment'] = 2, list(jpeg_host.quant_tables(options.quality)), comment
     job['rects'] = planner.rectangles(detections, width, height)
     try:
-        job['ops'], job['patches'] = planner.ops(detections, width, height)
-    except (PV.HostLeg, PV.RenderFailure) as e:
-        raise _HostLeg(str(e))
+        job['plan'] = planner.plan(detections, width, height)
+    except PV.RenderFailure as e:
+        raise PV.HostLeg(str(e))
     if options.quality == 'keep' and options.keep_source_blocks:
-        job['keep'], job['changed'] = True, SD.changed_rectangles(job['rects'], job['ops'])
+        job['keep'], job['changed'] = True, DR.changed_rectangles(job['rects'], job['plan'].ops)
     return job
 
 
-def render_decoded(ctx, torch, device, pixels, planes, jobs, planner, profile, clock, stream=0):
-    """What follows the decode, for frames whose pixels lie in device memory: ONE mdhip_blur_regions call, ONE mdhip_draw_ops
-    call and ONE call of each encoder the jobs need.  pixels: per job a flat uint8 device tensor (changed in place) or None
+def render_decoded(ctx, device, pixels, planes, jobs, planner, profile, clock, stream=0):
+    """What follows the decode, for frames whose pixels lie in device memory (device_render): ONE mdhip_blur_regions call, ONE
+    mdhip_draw_ops call and ONE call of each encoder the jobs need.  pixels: per job a flat uint8 device tensor (changed in place) or None
     for a frame the decoder flagged; planes: per job None or (device pointer to its quantised planes, what holds them).
     stream: the raw stream of the calls (the caller makes it torch's current one).  -> per job the JPEG file of its output
     frame, None for a frame the host leg has to make (flagged, or no baseline scan holds its merged blocks)"""
@@ -555,22 +507,21 @@ def render_decoded(ctx, torch, device, pixels, planes, jobs, planner, profile, c
     live = [k for k in range(len(jobs)) if pixels[k] is not None]
     if not live:
         return files
-    for k in live:
-        jobs[k]['file'] = k
-    SD.blur_and_draw(ctx, torch, device, [pixels[k] for k in live], [jobs[k] for k in live], clock, planner.options.blur_radius, stream)
-    profile['blur_calls'] += any(jobs[k]['rects'] for k in live)
-    profile['draw_calls'] += any(jobs[k]['ops'] for k in live)
+    blurred, drawn = DR.blur_and_draw(ctx, device, [pixels[k] for k in live], [jobs[k] for k in live], clock,
+                                      planner.options.blur_radius, stream)
+    profile['blur_calls'] += blurred
+    profile['draw_calls'] += drawn
     kept = [k for k in live if jobs[k]['keep'] and planes[k] is not None]
     if kept:
         with clock('encode_kept'):
-            made = SD._encode_kept(ctx, torch, device, [pixels[k] for k in kept], [jobs[k] for k in kept], dict(enumerate(planes)), stream)
+            made = DR.encode_kept(ctx, device, [pixels[k] for k in kept], [jobs[k] for k in kept], [planes[k][0] for k in kept], stream)
         for k, data in zip(kept, made):
             files[k] = data
         profile['encode_calls'] += 1
     rest = [k for k in live if not jobs[k]['keep']]
     if rest:
         with clock('encode'):
-            made = SD._encode_sampled(ctx, torch, device, [pixels[k] for k in rest], [jobs[k] for k in rest], stream)
+            made = DR.encode_sampled(ctx, device, [pixels[k] for k in rest], [jobs[k] for k in rest], stream)
         for k, data in zip(rest, made):
             files[k] = data
         profile['encode_calls'] += 1
@@ -583,7 +534,7 @@ def render_chunk_device(ctx, torch, device, jobs, planner, profile, clock):
     with clock('decode'):
         pixels, planes = decode_scans(ctx, torch, device, [j['scan'] for j in jobs], any(j['keep'] for j in jobs))
     profile['decode_calls'] += 1
-    return render_decoded(ctx, torch, device, pixels, planes, jobs, planner, profile, clock)
+    return render_decoded(ctx, device, pixels, planes, jobs, planner, profile, clock)
 
 
 # ---- the videos of a run ---------------------------------------------------------------------------------------------------------
@@ -712,24 +663,12 @@ def _run_host(video_entries, planner, classification_label_map, options, video_d
 
 
 def _run_device(video_entries, planner, classification_label_map, options, video_dir, out_dir, ctx, profile):
-    import datetime
     import torch
-    from contextlib import contextmanager
     from ._lib import HipError
     device = torch.device('cuda:{}'.format(ctx.device))
-
-    @contextmanager
-    def clock(key):
-        if 'ms' not in profile:
-            yield
-            return
-        torch.cuda.synchronize(device)
-        t0 = datetime.datetime.now()
-        yield
-        torch.cuda.synchronize(device)
-        profile['ms'][key] = profile['ms'].get(key, 0.0) + (datetime.datetime.now() - t0).total_seconds() * 1e3
-
-    results, chunk, room, device_off = [], [], [DECODE_CHUNK_BYTES], []
+    clock = DR.Clock(torch, device, profile.get('ms'))
+    # (not device_render.chunked: a chunk is rendered as soon as it is full, while the videos are still being read)
+    results, chunk, room, device_off = [], [], [DR.DECODE_CHUNK_BYTES], []
 
     def host_frame(video, slot, data, detections):
         try:
@@ -761,7 +700,7 @@ def _run_device(video_entries, planner, classification_label_map, options, video
             if video.pending == 0 and video.enumerated:
                 video.finish()
         del chunk[:]
-        room[0] = DECODE_CHUNK_BYTES
+        room[0] = DR.DECODE_CHUNK_BYTES
 
     with torch.cuda.device(device):
         for video_entry in video_entries:
@@ -780,9 +719,9 @@ def _run_device(video_entries, planner, classification_label_map, options, video
                     slot = len(video.frames) - 1
                     try:
                         if device_off:
-                            raise _HostLeg('the device leg has ended')
+                            raise PV.HostLeg('the device leg has ended')
                         job = plan_frame_device(data, detections, planner)
-                    except _HostLeg:
+                    except PV.HostLeg:
                         host_frame(video, slot, data, detections)
                         continue
                     size = job['size'][0] * job['size'][1] * 3 + (2 * int(job['scan'].coef_count) if job['keep'] else 0)
@@ -857,7 +796,6 @@ class InPassRenderer:
         """entries: [(tensor, width, height, frame name, detections, the detector's image)], the tensors NOT changed.  ONE blur,
         ONE draw and ONE call of each encoder for the frames of the batch that are rendered on the device."""
         import torch
-        from contextlib import contextmanager
         from .crops import device_stream
         from .jpeg_host import DeviceCoefficientImage
         out, jobs, where = [None] * len(entries), [], []
@@ -879,17 +817,12 @@ class InPassRenderer:
             where.append(e)
         if not jobs:
             return out, {'gpu': 0}
-
-        @contextmanager
-        def clock(key):
-            yield
-
         device = entries[0][0].device
         ext = device_stream(stream, device)
         with torch.cuda.stream(ext):
             pixels = [entries[e][0].clone() for e in where]
-            files = render_decoded(ctx, torch, device, pixels, [j['planes'] for j in jobs], jobs, self.planner, self.profile, clock,
-                                   ext.cuda_stream)
+            files = render_decoded(ctx, device, pixels, [j['planes'] for j in jobs], jobs, self.planner, self.profile,
+                                   DR.Clock(torch, device, None), ext.cuda_stream)
         for e, data in zip(where, files):
             out[e] = data
         return out, {'gpu': sum(f is not None for f in files)}

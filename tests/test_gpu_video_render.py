@@ -13,6 +13,7 @@ import os
 import pytest
 
 import video_render_scene as S
+from megadetector_amd import device_render as DR
 from megadetector_amd import visualize_video_output as V
 from test_video_render_cpu import MODES, host_run, quiet
 
@@ -68,7 +69,7 @@ def test_small_chunks_give_the_same_files(tmp_path_factory, tmp_path, monkeypatc
     """a chunk limit of two 70 x 50 frames: a video's frames arrive over several chunks, and chunks end inside a video"""
     together = host_run(tmp_path_factory, 'q75', True, False, backend='gpu', profile={})
     video_dir, results_file, _ = S.build_small(str(tmp_path), classified=False, thin=True)
-    monkeypatch.setattr(V, 'DECODE_CHUNK_BYTES', 2 * 70 * 50 * 3)
+    monkeypatch.setattr(DR, 'DECODE_CHUNK_BYTES', 2 * 70 * 50 * 3)
     profile = {}
     out_dir = str(tmp_path / 'out')
     quiet(V.visualize_video_output, results_file, out_dir, video_dir, together['options'], backend='gpu', profile=profile)

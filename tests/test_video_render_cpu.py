@@ -16,9 +16,9 @@ from PIL import Image, ImageFilter, JpegImagePlugin
 
 import video_render_scene as S
 from megadetector_amd import avi
+from megadetector_amd import device_render as DR
 from megadetector_amd import jpeg_host as J
 from megadetector_amd import preview as PV
-from megadetector_amd import separate_detections as SD
 from megadetector_amd import visualize_video_output as V
 from test_keep_blocks_cpu import _block_mask, changed_mcus
 
@@ -298,7 +298,8 @@ def pillow_pixels(data, dets, blur, classified):
             image.paste(image.crop(rect).filter(ImageFilter.GaussianBlur(radius=6)), rect[:2])
     o = PV.PreviewOptions(confidence_threshold=0, output_image_width=None)
     if classified and any('classifications' in d for d in dets):
-        SD._render_classified_with_pil(image, dets, o, S.DETECTION_CATEGORIES, S.CLASSIFICATION_CATEGORIES)
+        PV.render_with_pil(image, dets, o, S.DETECTION_CATEGORIES, classification_label_map=S.CLASSIFICATION_CATEGORIES,
+                           classification_confidence_threshold=PV.DEFAULT_CLASSIFICATION_CONFIDENCE_THRESHOLD)
     else:
         PV.render_with_pil(image, dets, o, label_map=S.DETECTION_CATEGORIES)
     return image
@@ -356,10 +357,12 @@ def test_classification_threshold_reaches_the_labels(tmp_path_factory):
     options.classification_confidence_threshold = 0.5
     planner = V.FramePlanner(S.DETECTION_CATEGORIES, S.CLASSIFICATION_CATEGORIES, options)
     assert V.render_frame_host(data, dets, planner) != run['out']['v422.avi'][4]
-    assert [planner.lines(d)[0] for d in dets if d['category'] == '1'] == [['animal: 40%']]
+    lines = lambda d: PV.classified_label_lines(d, planner.label_map, planner.classification_label_map,
+                                                options.classification_confidence_threshold)
+    assert [lines(d)[0] for d in dets if d['category'] == '1'] == [['animal: 40%']]
     options.classification_confidence_threshold = 0.3
     assert V.render_frame_host(data, dets, planner) == run['out']['v422.avi'][4]
-    assert [planner.lines(d) for d in dets if d['category'] == '1'] == [(['animal: 40%', 'red fox: 45.0%'], 3 + 1)]
+    assert [lines(d) for d in dets if d['category'] == '1'] == [(['animal: 40%', 'red fox: 45.0%'], 3 + 1)]
 
 
 @pytest.mark.parametrize('classified', [False, True])
@@ -422,7 +425,7 @@ def test_keep_source_blocks_on_the_host_leg(tmp_path_factory, blur):
                 continue
             rects = planner.rectangles(dets, w, h)
             ops, _ = planner.ops(dets, w, h)
-            changed = changed_mcus(w, h, s, SD.changed_rectangles(rects, ops))
+            changed = changed_mcus(w, h, s, DR.changed_rectangles(rects, ops))
             assert changed.any()
             image = pillow_pixels(data, dets, blur, False)
             before = np.asarray(Image.open(io.BytesIO(data)).convert('RGB')).astype(int)
