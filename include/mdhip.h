@@ -207,6 +207,10 @@ int mdhip_forward(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream);
  * libmdjpeg.so, include/mdjpeg.h): rebuilds from the QUANTISED DCT coefficients of a baseline JPEG the RGB pixels that
  * Pillow / libjpeg-turbo produce, bit for bit -- de-quantisation, the "islow" integer inverse DCT, "fancy" chroma
  * upsampling, fixed-point YCbCr -> RGB, and the EXIF rotation -- into device memory that mdhip_preprocess then reads.
+ * The inverse DCT's results are SATURATED to 0 .. 255, as libjpeg-turbo's SIMD code packs them; libjpeg's C code indexes a
+ * range-limit table with (sample - 128) & 1023 instead, which wraps around for samples outside [-512, 511].  Planes that
+ * mdjpeg_decode accepts can hold such samples (its energy bound admits a block whose whole norm sits in one sample), and
+ * for them the pixels are those of a Pillow whose libjpeg saturates.  quant entries may use all 16 bits.
  *   coef        DEVICE pointer, 16-byte aligned: the planes of Y[, Cb, Cr] one behind the other exactly as mdjpeg_decode
  *               writes them (plane c: [blocks_h[c]][blocks_w[c]][64], natural order within a block)
  *   width, height   of the image before rotation;  components 1 (grayscale: R = G = B = Y) or 3

@@ -420,8 +420,11 @@ int mdjpeg_decode(const uint8_t* data, size_t size, mdjpeg_info* info, int16_t* 
     }
     const int nc = info->components;
     // Parseval: the coefficients of 64 samples in [-128, 127] have a 2-norm of at most 8 * 128; quantisation moves every
-    // coefficient by at most half its step.  A block beyond that was not made from 8-bit samples; it is also the bound
-    // that keeps 16-bit and 32-bit implementations of the inverse DCT in agreement.
+    // coefficient by at most half its step.  A block beyond that was not made from 8-bit samples.  The cap of 2800 keeps
+    // the 16-bit workspace of a SIMD inverse DCT from saturating (4 * sqrt(8) * 2800 < 32768), so that such a decoder and a
+    // 32-bit one agree BEFORE the range limit.  The bound does not keep samples inside [-512, 511], where libjpeg's
+    // range-limit table and saturation part: a block's whole norm can sit in one sample.  The reconstruction saturates,
+    // as libjpeg-turbo's SIMD code and so Pillow do ("Foreign files and the range limit").
     int64_t emax[3];
     for (int c = 0; c < nc; ++c) {
         double qn = 0;

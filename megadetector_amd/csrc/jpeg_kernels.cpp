@@ -2,7 +2,7 @@
 // produce, bit for bit.  Integer arithmetic only; restates tests/jpeg_ref.py, which is pinned against Pillow.
 //
 //   jpeg_idct_kernel      de-quantise + libjpeg's "islow" inverse DCT (jidctint: 13-bit constants, columns then rows,
-//                         rounding shifts by 11 and 18, range-limit table indexed with value & 1023) -> u8 component planes
+//                         rounding shifts by 11 and 18, results saturated to 0 .. 255) -> u8 component planes
 //   jpeg_colour_kernel    "fancy" (triangle) chroma upsampling, 16-bit fixed-point YCbCr -> RGB, EXIF rotation as an index
 //                         permutation; one thread writes four neighbouring OUTPUT pixels (12 bytes, three dwords when aligned)
 //
@@ -76,10 +76,11 @@ __device__ __forceinline__ void idct_1d(const int* d, int* o, int shift) {
     o[4] = descale(tmp13 - tmp0, shift);
 }
 
-// libjpeg's post-IDCT range-limit table, indexed with (x & 1023), x = sample - 128
+// post-IDCT range limit, x = sample - 128: saturation, as libjpeg-turbo's SIMD inverse DCT packs its results (and so
+// Pillow's pixels).  libjpeg's C code indexes a table with (x & 1023) instead, which is the same inside [-512, 511] and
+// wraps around outside it; a block within the energy bound of the entropy decoders can leave that range.
 __device__ __forceinline__ unsigned range_limit(int x) {
-    const int i = x & 1023;
-    return i < 128 ? unsigned(i + 128) : i < 512 ? 255u : i < 896 ? 0u : unsigned(i - 896);
+    return unsigned(x < -128 ? 0 : (x > 127 ? 255 : x + 128));
 }
 
 __global__ __launch_bounds__(IDCT_BLOCKS * 8) void jpeg_idct_kernel(const JpegDev d) {

@@ -6,8 +6,10 @@ Input: the quantised coefficient planes of megadetector_amd.jpeg_host.decode.  O
 np.asarray(feed.load_image(file)).  Integer arithmetic throughout (int64 here; nothing leaves 32 bits on legal data):
 
   * IDCT: libjpeg's jidctint "islow" -- de-quantise, columns then rows with 13-bit constants, rounding right shifts by
-    11 and 18, and the range-limit TABLE indexed with (value & 1023): a clamp of value + 128 for values in [-512, 511],
-    and the table's wrap-around outside it;
+    11 and 18, and SATURATION of value + 128 to 0 .. 255.  libjpeg's C code indexes a range-limit table with
+    (value & 1023) instead: the same for values in [-512, 511], a wrap-around outside.  libjpeg-turbo's SIMD inverse
+    DCT packs with saturation, and that is what Pillow's pixels show; a block inside the energy bound of mdjpeg_decode
+    can reach +-2800, so the two differ on files the decoders accept (tests/test_jpeg_foreign_cpu.py has the probe);
   * chroma: "fancy" triangle upsampling (h2v1 / h2v2) over the component's downsampled width and height -- not over the
     block-padded plane -- with the nearest real row repeated above the first and below the last; components of at most
     two columns are replicated instead (libjpeg's rule);
@@ -23,17 +25,21 @@ F_0_899976223, F_1_175875602, F_1_501321110, F_1_847759065 = 7373, 9633, 12299, 
 F_1_961570560, F_2_053119869, F_2_562915447, F_3_072711026 = 16069, 16819, 20995, 25172
 
 
-def _range_limit_table():
-    """libjpeg's post-IDCT table (jdmaster.c prepare_range_limit_table), indexed by (x & 1023), x = sample - 128"""
+def range_limit(x):
+    """post-IDCT range limit, x = sample - 128: saturation (see the module's text)"""
+    return np.clip(x + 128, 0, 255)
+
+
+def range_limit_table(x):
+    """libjpeg's C form, which this project does NOT follow: its table (jdmaster.c prepare_range_limit_table) indexed by
+    (x & 1023).  Equal to range_limit inside [-512, 511], wrapping around outside.  Kept for the probe test that states
+    which of the two the installed Pillow shows."""
     t = np.zeros(1024, dtype=np.int64)
     t[0:128] = np.arange(128, 256)
     t[128:512] = 255
     t[512:896] = 0
     t[896:1024] = np.arange(0, 128)
-    return t
-
-
-RANGE_LIMIT = _range_limit_table()
+    return t[x & 1023]
 
 
 def _descale(x, n):
@@ -70,14 +76,14 @@ def _pass(d, shift):
                      _descale(tmp11 - tmp2, shift), _descale(tmp10 - tmp3, shift)])
 
 
-def idct_plane(plane, quant):
+def idct_plane(plane, quant, limit=range_limit):
     """plane: [bh][bw][64] int16 quantised, quant: [64] -> [bh * 8][bw * 8] samples (int64 in 0 .. 255)"""
     bh, bw = plane.shape[:2]
     d = plane.astype(np.int64) * quant.astype(np.int64)[None, None, :]
     d = d.reshape(bh, bw, 8, 8)                                       # [.., row v, column u]
     ws = _pass(np.moveaxis(d, 2, 0), CONST_BITS - PASS1_BITS)         # columns: over v -> [y][bh][bw][u]
     out = _pass(np.moveaxis(ws, 3, 0), CONST_BITS + PASS1_BITS + 3)   # rows: over u -> [x][y][bh][bw]
-    out = RANGE_LIMIT[out & 1023]
+    out = limit(out)
     return out.transpose(2, 1, 3, 0).reshape(bh * 8, bw * 8)
 
 
