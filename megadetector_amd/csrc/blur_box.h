@@ -1,5 +1,5 @@
 // Pillow's Gaussian blur, shared by the GPU kernels (blur_kernels.cpp) and their host model (mdjpeg_blur_regions in
-// jpeg_entropy.cpp): ONE computation of the weights, ONE pass along a line, ONE plan for the row stage, compiled by both, so
+// image_host.cpp): ONE computation of the weights, ONE pass along a line, ONE plan for the row stage, compiled by both, so
 // that the CPU suite and the host sanitizers exercise the very statements the lanes run (the arrangement of jpeg_subseq.h
 // and jpeg_encode.h).
 //

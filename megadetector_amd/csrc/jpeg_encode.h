@@ -1,5 +1,5 @@
 // The baseline Huffman ENCODER of a crop, shared by the GPU kernels (jpeg_encode.cpp) and their host model
-// (mdjpeg_encode_subsequences in jpeg_entropy.cpp): ONE encoder of a block, ONE rule for where a block's bits go, ONE
+// (mdjpeg_encode_subsequences in jpeg_encode_host.cpp): ONE encoder of a block, ONE rule for where a block's bits go, ONE
 // stuffing chunk, compiled by both, so that the CPU suite and the host sanitizers exercise the very code the lanes run
 // (the arrangement of jpeg_subseq.h for the decoder).
 //

@@ -1,6 +1,6 @@
 // Keeping the source's blocks (mdhip_jpeg_encode_kept, mdjpeg_keep_merge): which MCUs of a window a list of changed
 // rectangles touches, and where the blocks of an MCU lie in the source's coefficient planes.  ONE predicate and ONE
-// addressing rule, compiled by the coefficient kernel (jpeg_encode.cpp) and by the host model (jpeg_entropy.cpp), the
+// addressing rule, compiled by the coefficient kernel (jpeg_encode.cpp) and by the host model (jpeg_encode_host.cpp), the
 // arrangement of jpeg_encode.h, blur_box.h and resample.h.
 //
 // A rectangle is left, top, right, bottom in pixels of its window, right and bottom exclusive (mdhip_blur_regions'

@@ -1,7 +1,7 @@
 // Pillow's resize (LANCZOS for the annotated previews; bicubic, bilinear and LANCZOS for the classifier input and the
 // thumbnails of the RDE review folder, at the end of this file), and the drawing of the previews, shared by the GPU kernels
 // (preview_kernels.cpp, classify_kernels.cpp) and their host models (mdjpeg_resample, mdjpeg_draw, mdjpeg_classifier_input,
-// mdjpeg_thumbnails in jpeg_entropy.cpp): ONE computation of the coefficient tables, ONE weighted
+// mdjpeg_thumbnails in image_host.cpp): ONE computation of the coefficient tables, ONE weighted
 // sum of a run of samples, ONE walk of a pixel through its image's drawing operations, compiled by both, so that the CPU
 // suite and the host sanitizers exercise the very statements the lanes run (the arrangement of blur_box.h).
 //

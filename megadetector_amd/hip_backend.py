@@ -151,6 +151,18 @@ def _window_arrays(ptrs, sizes, pitches):
             (C.c_int32 * n)(*[int(v[1]) for v in sizes]), (C.c_int64 * n)(*[int(v) for v in pitches]))
 
 
+def _quant_array(quants, n):
+    """per window (luma, chroma), 64 entries each -> the uint16 [n][2][64] array the sampled encoders take"""
+    packed = np.zeros((max(n, 1), 2, 64), dtype=np.uint16)
+    for i, pair in enumerate(quants):
+        for k in (0, 1):
+            table = np.asarray(pair[k]).reshape(-1)
+            if table.size != 64 or table.min() < 0 or table.max() > 65535:
+                raise ValueError('window {}: a quantisation table has 64 entries'.format(i))
+            packed[i, k] = table
+    return packed
+
+
 def _letterbox_array(geoms):
     """[(src_h, src_w, resized_h, resized_w, top, left[, interp])] -> mdhip_letterbox array"""
     g = (_lib.mdhip_letterbox * len(geoms))()
@@ -375,14 +387,20 @@ class HipContext:
         if not (len(sizes) == len(pitches) == n):
             raise ValueError('ptrs, sizes and pitches must have one entry per window')
         ql, qc = quant_tables(quality)
-        p, ws, hs, pt = _window_arrays(ptrs, sizes, pitches)
+        return self._jpeg_encode('mdhip_jpeg_encode', _window_arrays(ptrs, sizes, pitches), n,
+                                 (ql.ctypes.data_as(C.POINTER(C.c_uint16)), qc.ctypes.data_as(C.POINTER(C.c_uint16))), out_ptr, capacity, stream)
+
+    def _jpeg_encode(self, name, windows, n, tables, out_ptr, capacity, stream, status=None):
+        """
+        What the three encode calls share.  name: the C function; windows: its arguments in front of `n` (the window arrays and,
+        where it takes them, the samplings); tables: those between `n` and `out` (tables, sources, rectangles); status: the
+        per-window array jpeg_encode_kept has behind `needed`.  MDHIP_ECAPACITY is a result (fits False), any other code raises.
+        """
         offs, lens, need = (C.c_int64 * max(n, 1))(), (C.c_int64 * max(n, 1))(), C.c_int64(0)
-        rc = self.lib.mdhip_jpeg_encode(self.h, p, ws, hs, pt, n,
-                                        ql.ctypes.data_as(C.POINTER(C.c_uint16)), qc.ctypes.data_as(C.POINTER(C.c_uint16)),
-                                        C.c_void_p(int(out_ptr) if capacity else 0), int(capacity), offs, lens, C.byref(need),
-                                        C.c_void_p(stream))
+        rc = getattr(self.lib, name)(self.h, *windows, n, *tables, C.c_void_p(int(out_ptr) if capacity else 0), int(capacity), offs, lens,
+                                     C.byref(need), *(() if status is None else (status,)), C.c_void_p(stream))
         if rc != _lib.MDHIP_ECAPACITY:
-            self._check(rc, 'mdhip_jpeg_encode')
+            self._check(rc, name)
         return rc == 0, np.array(offs[:n], dtype=np.int64), np.array(lens[:n], dtype=np.int64), int(need.value)
 
     def jpeg_encode_sampled(self, ptrs, sizes, pitches, samplings, quants, out_ptr, capacity, stream=0):
@@ -397,22 +415,9 @@ class HipContext:
         n = len(ptrs)
         if not (len(sizes) == len(pitches) == len(samplings) == len(quants) == n):
             raise ValueError('ptrs, sizes, pitches, samplings and quants must have one entry per window')
-        p, ws, hs, pt = _window_arrays(ptrs, sizes, pitches)
-        ss = (C.c_int32 * max(n, 1))(*[int(v) for v in samplings])
-        packed = np.zeros((max(n, 1), 2, 64), dtype=np.uint16)
-        for i, pair in enumerate(quants):
-            for k in (0, 1):
-                table = np.asarray(pair[k]).reshape(-1)
-                if table.size != 64 or table.min() < 0 or table.max() > 65535:
-                    raise ValueError('window {}: a quantisation table has 64 entries'.format(i))
-                packed[i, k] = table
-        offs, lens, need = (C.c_int64 * max(n, 1))(), (C.c_int64 * max(n, 1))(), C.c_int64(0)
-        rc = self.lib.mdhip_jpeg_encode_sampled(self.h, p, ws, hs, pt, ss, n, packed.ctypes.data_as(C.POINTER(C.c_uint16)),
-                                                C.c_void_p(int(out_ptr) if capacity else 0), int(capacity), offs, lens, C.byref(need),
-                                                C.c_void_p(stream))
-        if rc != _lib.MDHIP_ECAPACITY:
-            self._check(rc, 'mdhip_jpeg_encode_sampled')
-        return rc == 0, np.array(offs[:n], dtype=np.int64), np.array(lens[:n], dtype=np.int64), int(need.value)
+        windows = _window_arrays(ptrs, sizes, pitches) + ((C.c_int32 * max(n, 1))(*[int(v) for v in samplings]),)
+        packed = _quant_array(quants, n)
+        return self._jpeg_encode('mdhip_jpeg_encode_sampled', windows, n, (packed.ctypes.data_as(C.POINTER(C.c_uint16)),), out_ptr, capacity, stream)
 
     def jpeg_encode_kept(self, ptrs, sizes, pitches, samplings, quants, source_ptrs, rect_image, rects, out_ptr, capacity, stream=0):
         """
@@ -428,15 +433,8 @@ class HipContext:
         n, m = len(ptrs), len(rects)
         if not (len(sizes) == len(pitches) == len(samplings) == len(quants) == len(source_ptrs) == n) or len(rect_image) != m:
             raise ValueError('one entry per window is needed in every list, and one window index per rectangle')
-        p, ws, hs, pt = _window_arrays(ptrs, sizes, pitches)
-        ss = (C.c_int32 * max(n, 1))(*[int(v) for v in samplings])
-        packed = np.zeros((max(n, 1), 2, 64), dtype=np.uint16)
-        for i, pair in enumerate(quants):
-            for k in (0, 1):
-                table = np.asarray(pair[k]).reshape(-1)
-                if table.size != 64 or table.min() < 0 or table.max() > 65535:
-                    raise ValueError('window {}: a quantisation table has 64 entries'.format(i))
-                packed[i, k] = table
+        windows = _window_arrays(ptrs, sizes, pitches) + ((C.c_int32 * max(n, 1))(*[int(v) for v in samplings]),)
+        packed = _quant_array(quants, n)
         sources = (_lib.mdhip_jpeg_source * max(n, 1))()
         for i, ((w, h), sampling) in enumerate(zip(sizes, samplings)):
             fh, fv = {0: (1, 1), 1: (2, 1), 2: (2, 2)}.get(int(sampling), (1, 1))      # (the call refuses any other sampling)
@@ -446,15 +444,10 @@ class HipContext:
             sources[i].blocks_h[:] = [my * fv, my, my]
         ri = (C.c_int32 * max(m, 1))(*[int(v) for v in rect_image])
         rc4 = (C.c_int32 * max(4 * m, 1))(*[int(v) for q in rects for v in q])
-        offs, lens, need = (C.c_int64 * max(n, 1))(), (C.c_int64 * max(n, 1))(), C.c_int64(0)
         status = (C.c_int32 * max(n, 1))()
-        rc = self.lib.mdhip_jpeg_encode_kept(self.h, p, ws, hs, pt, ss, n, packed.ctypes.data_as(C.POINTER(C.c_uint16)), sources, ri, rc4, m,
-                                             C.c_void_p(int(out_ptr) if capacity else 0), int(capacity), offs, lens, C.byref(need),
-                                             status, C.c_void_p(stream))
-        if rc != _lib.MDHIP_ECAPACITY:
-            self._check(rc, 'mdhip_jpeg_encode_kept')
-        return (rc == 0, np.array(offs[:n], dtype=np.int64), np.array(lens[:n], dtype=np.int64), int(need.value),
-                np.array(status[:n], dtype=np.int32))
+        result = self._jpeg_encode('mdhip_jpeg_encode_kept', windows, n, (packed.ctypes.data_as(C.POINTER(C.c_uint16)), sources, ri, rc4, m),
+                                   out_ptr, capacity, stream, status)
+        return result + (np.array(status[:n], dtype=np.int32),)
 
     @staticmethod
     def jpeg_encode_sampled_bound(width, height, sampling):

@@ -1,5 +1,8 @@
 """
-ctypes binding of libmdjpeg.so (C ABI: include/mdjpeg.h): the host half of the GPU JPEG feed.
+ctypes binding of libmdjpeg.so (C ABI: include/mdjpeg.h): the host half of the GPU JPEG feed -- header parser, entropy decoder
+and scan descriptor (csrc/jpeg_entropy.cpp) -- and the host models the CPU suite holds the image kernels to: the entropy
+encoder and the kept-block merge (csrc/jpeg_encode_host.cpp), blur, resample, drawing, classifier input and thumbnails
+(csrc/image_host.cpp), repeat-detection elimination (csrc/rde_host.cpp).
 
 parse() / decode() turn the bytes of a baseline JPEG into quantised DCT coefficients; the GPU rebuilds the pixels
 (hip_backend.HipContext.jpeg_reconstruct).  Whatever the decoder does not take cleanly is reported, never guessed at: the

@@ -1,5 +1,6 @@
 """CPU-side checks of the drop-in boundary: the shared library builds, loads and exports every
-symbol include/mdhip.h declares; without a GPU the product path fails loudly (no fallback)."""
+symbol include/mdhip.h declares, and the host library every symbol include/mdjpeg.h declares; without a GPU the
+product path fails loudly (no fallback)."""
 
 import os
 import re
@@ -10,10 +11,10 @@ import pytest
 from conftest import REPO
 
 
-def _header_symbols():
-    text = open(os.path.join(REPO, 'include', 'mdhip.h')).read()
+def _header_symbols(header='mdhip.h', prefix='mdhip_'):
+    text = open(os.path.join(REPO, 'include', header)).read()
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b(mdhip_[a-z_0-9]+)\s*\(', text)))
+    return sorted(set(re.findall(r'\b(' + prefix + r'[a-z_0-9]+)\s*\(', text)))
 
 
 def test_library_exports_every_declared_symbol():
@@ -27,6 +28,23 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), 'libmdhip.so does not export {}'.format(name)
     assert sorted(_lib.SYMBOLS) == declared, 'ctypes table and header disagree'
     assert b'gfx950' in lib.mdhip_version()
+
+
+def test_host_library_exports_every_declared_symbol():
+    """the same for libmdjpeg.so, whose sources are one file per subject: every function include/mdjpeg.h declares is
+    exported by the built library (looked up in a handle of its own, not through the binding's table), and
+    jpeg_host.SYMBOLS names exactly those"""
+    import ctypes
+    import __graft_entry__ as G
+    G.build()
+    from megadetector_amd import jpeg_host
+    lib = ctypes.CDLL(jpeg_host.LIB_PATH)
+    declared = _header_symbols('mdjpeg.h', 'mdjpeg_')
+    assert len(declared) >= 19, 'functions parsed from include/mdjpeg.h: {}'.format(declared)
+    for name in declared:
+        assert hasattr(lib, name), 'libmdjpeg.so does not export {}'.format(name)
+    assert sorted(jpeg_host.SYMBOLS) == declared, 'ctypes table and header disagree'
+    assert jpeg_host.load().mdjpeg_version() == b'mdjpeg 7'
 
 
 def test_product_path_fails_loudly_without_gpu():

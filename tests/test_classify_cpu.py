@@ -259,8 +259,8 @@ def test_batch_driver_with_a_stub_detector(tmp_path):
 # ---- sanitizers ----------------------------------------------------------------------------------------------------------------
 
 def test_host_model_under_sanitizers(tmp_path):
-    """mdjpeg_classifier_input in a stand-alone build of jpeg_entropy.cpp with AddressSanitizer + UBSan (host code; `make
-    asan-jpeg`, its --classify mode): sources of their exact sizes at every alignment, outputs of exactly 3 S S floats, tiles
+    """mdjpeg_classifier_input in a stand-alone build of image_host.cpp with AddressSanitizer + UBSan (host code; `make
+    asan-jpeg`, the --classify mode of host_asan_main.cpp): sources of their exact sizes at every alignment, outputs of exactly 3 S S floats, tiles
     of exactly the planned size -- any access outside them, and any undefined arithmetic, ends the run"""
     cxx = shutil.which('g++')
     if cxx is None:

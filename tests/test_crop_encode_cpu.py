@@ -160,8 +160,8 @@ def test_bad_arguments():
 
 
 def test_host_model_under_sanitizers(tmp_path):
-    """the encoder's host model in the AddressSanitizer + UBSan build of jpeg_entropy.cpp (`make asan-jpeg`): its program
-    encodes every 4:2:0 file it decoded, at three chunk sizes, into buffers of exactly the size the call asked for"""
+    """the encoder's host model, jpeg_encode_host.cpp, in the AddressSanitizer + UBSan build (`make asan-jpeg`): its program,
+    host_asan_main.cpp, encodes every 4:2:0 file it decoded, at three chunk sizes, into buffers of exactly the size the call asked for"""
     cxx = shutil.which('g++')
     if cxx is None:
         pytest.skip('no g++')

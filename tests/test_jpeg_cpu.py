@@ -218,8 +218,8 @@ def test_damaged_files_error_or_equal_pillow(J, tmp_path):
 
 
 def test_damaged_files_under_sanitizers(J, tmp_path):
-    """the same files through a build of jpeg_entropy.cpp with AddressSanitizer + UBSan (host code; `make asan-jpeg`): the
-    buffers have their exact sizes there, so any read or write outside them, and any undefined arithmetic, ends the run"""
+    """the same files through host_asan_main.cpp, a program around jpeg_entropy.cpp (and the library's other sources) built with
+    AddressSanitizer + UBSan (host code; `make asan-jpeg`): the buffers have their exact sizes there, so any read or write outside them, and any undefined arithmetic, ends the run"""
     cxx = shutil.which('g++')
     if cxx is None:
         pytest.skip('no g++')

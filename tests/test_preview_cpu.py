@@ -524,8 +524,8 @@ def test_the_new_symbols_are_declared_exported_and_bound():
 
 
 def test_host_models_under_sanitizers(tmp_path):
-    """mdjpeg_resample and mdjpeg_draw in a build of jpeg_entropy.cpp with AddressSanitizer + UBSan (host code; `make asan-jpeg`,
-    its --preview mode): images of their exact sizes at every alignment, a pitch above 3 x width, operations that leave the
+    """mdjpeg_resample and mdjpeg_draw in a build of image_host.cpp with AddressSanitizer + UBSan (host code; `make asan-jpeg`,
+    the --preview mode of host_asan_main.cpp): images of their exact sizes at every alignment, a pitch above 3 x width, operations that leave the
     image -- any access outside an image, and any undefined arithmetic, ends the run"""
     cxx = shutil.which('g++')
     if cxx is None:

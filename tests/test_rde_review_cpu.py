@@ -294,8 +294,8 @@ def test_run_detector_batch_writes_the_review_folder(tmp_path, monkeypatch):
 
 
 def test_host_model_under_sanitizers(tmp_path):
-    """mdjpeg_thumbnails in a stand-alone build of jpeg_entropy.cpp with AddressSanitizer + UBSan (host code; `make asan-jpeg`,
-    its --thumbnails mode): sources and sheets of their exact sizes at every alignment, LDS tiles of exactly the planned size --
+    """mdjpeg_thumbnails in a stand-alone build of image_host.cpp with AddressSanitizer + UBSan (host code; `make asan-jpeg`,
+    the --thumbnails mode of host_asan_main.cpp): sources and sheets of their exact sizes at every alignment, LDS tiles of exactly the planned size --
     any access outside them, and any undefined arithmetic, ends the run"""
     import shutil
     import subprocess
