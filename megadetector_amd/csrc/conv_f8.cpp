@@ -21,26 +21,17 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "mdhip_internal.h"
+#include "conv_device.h"
 
 namespace mdhip {
 namespace MDHIP_ST {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
-typedef __attribute__((address_space(3))) char lds_char;
 
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;
-[[maybe_unused]] constexpr int kNumRecords = 0x7fffffff;
 [[maybe_unused]] constexpr int kUnitScale = 0x7f7f7f7f;          // E8M0 127 = 2^0 in every byte (tools/probe_fp8.cpp)
-
-__device__ __forceinline__ float silu_f32(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-}
 
 constexpr int f8_run_pieces(int bm) { return (bm + 2 + 7) / 8; }
 // 2 run buffers + 2 weight stages + 2 KiB: the row of zeros, the staged bias and the staged scales
@@ -57,8 +48,6 @@ constexpr int f8_waves_per_simd(int bm, int bn, int nw) {
 
 }  // namespace
 
-#define MDHIP_DMA16(rsrc, lptr, voff, soff) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (lptr), 16, (voff), (soff), 0, 0)
 // The builtin form (__builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4) has no accumulate-in-place variant in this
 // compiler: destination and C operand get different registers, the accumulators ping-pong between two register sets
 // and the kernel spills (measured: 310 spilled VGPRs for the 128x160 tile).  The instruction is therefore written out
@@ -127,7 +116,7 @@ conv_f8_kernel(const ConvArgs p) {
     const int lr = lane >> 3;
     const int jj = (lane & 7) ^ lr;
     const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.wgt8 + (size_t)n0 * p.k_pad8), 0, kNumRecords, 0x00020000);
+        (void*)(p.wgt8 + (size_t)n0 * p.k_pad8), 0, kNumRecords, kRsrcFlags);
     unsigned b_off[B_PER];
 #pragma unroll
     for (int i = 0; i < B_PER; ++i) {
@@ -149,7 +138,7 @@ conv_f8_kernel(const ConvArgs p) {
     // check zeroes the pixels outside the batch; the channel test stays -- an e4m3 MFMA reads all 128 channels of a group, and
     // what lies behind the last channel must be zeros, not the next pixel)
     const __amdgpu_buffer_rsrc_t a_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc((void*)in8, 0, (int)((unsigned)p.M * (unsigned)p.ld_in), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc((void*)in8, 0, (int)((unsigned)p.M * (unsigned)p.ld_in), kRsrcFlags);
     unsigned q_off[A_PER];
 #pragma unroll
     for (int i = 0; i < A_PER; ++i) {
@@ -249,21 +238,19 @@ conv_f8_kernel(const ConvArgs p) {
         // Outputs and the residual go through buffer instructions (conv_v5.cpp): one 32-bit offset register per lane and
         // tensor instead of 64-bit address pairs, which were spilled and reloaded -- with an s_waitcnt vmcnt(0) each --
         // in front of every store; rows past the tensor's end are dropped / read as zeros by the range check.
-        typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-        typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
         const int npair0 = n0 + wn * TN + q4 * 8;
         const int nlast = nbase + (FN - 1) * 16;
         // (descriptors start at the tile's first pixel: offsets stay small whatever the tensor's size)
         const long long rows_left = (long long)p.M - (long long)tile_m * BM;
         const int ml = wm * TM + (lane_e & 15);
         const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)((uint16_t*)p.out + (size_t)tile_m * BM * p.ld_out), 0, (int)min(rows_left * p.ld_out * 2, 0x7fffffffLL), 0x00020000);
+            (void*)((uint16_t*)p.out + (size_t)tile_m * BM * p.ld_out), 0, (int)min(rows_left * p.ld_out * 2, 0x7fffffffLL), kRsrcFlags);
         const unsigned o_pair = ((unsigned)ml * (unsigned)p.ld_out + (unsigned)npair0) * 2u;
         const unsigned o_last = ((unsigned)ml * (unsigned)p.ld_out + (unsigned)nlast) * 2u;
         const unsigned o_step = 16u * (unsigned)p.ld_out * 2u;
         const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
             (void*)(p.res + (HAS_RES ? (size_t)tile_m * BM * p.ld_res : 0)), 0,
-            HAS_RES ? (int)min(rows_left * p.ld_res * 2, 0x7fffffffLL) : 0, 0x00020000);
+            HAS_RES ? (int)min(rows_left * p.ld_res * 2, 0x7fffffffLL) : 0, kRsrcFlags);
         const unsigned r_col = ((unsigned)ml * (unsigned)p.ld_res + (unsigned)nbase) * 2u;
         const unsigned r_step = 16u * (unsigned)p.ld_res * 2u;
         uint2 rrow[2][FN];
@@ -306,6 +293,7 @@ conv_f8_kernel(const ConvArgs p) {
             } else {
 #pragma unroll
                 for (int j = 0; j + 1 < FN; j += 2) {
+                    // (written out, not conv_pack_pair of conv_device.h: with the helper this unit's code comes out in another order)
                     unsigned a0 = st_pack2(v[j][0], v[j][1]), a1 = st_pack2(v[j][2], v[j][3]);
                     unsigned b0 = st_pack2(v[j + 1][0], v[j + 1][1]), b1 = st_pack2(v[j + 1][2], v[j + 1][3]);
                     auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
@@ -369,7 +357,6 @@ conv_f8_kernel(const ConvArgs p) {
         }
     };
     if constexpr ((PROF & 1) != 0) t_prev = __builtin_amdgcn_s_memtime();
-#define MDHIP_FENCE() __builtin_amdgcn_sched_barrier(0)
     constexpr int FN2 = FN - FN1;
     constexpr int DMA_MAX = B_PER + A_H0, DMA_PER_G = (DMA_MAX + FN2 - 1) / FN2;
     // reads of the second half: FM activation fragments of the next step + FN1 weight columns, spread over its columns
@@ -456,7 +443,6 @@ conv_f8_kernel(const ConvArgs p) {
         run_body(std::integral_constant<int, 1>{});
     }
     if (run < total_runs) run_body(std::integral_constant<int, 0>{});
-#undef MDHIP_FENCE
     if constexpr ((PROF & 1) != 0) {
         if (lane == 0 && p.dbg) {
             unsigned long long* d = (unsigned long long*)p.dbg + ((size_t)blockIdx.x * NW + wave) * 8;
@@ -501,15 +487,13 @@ constexpr int kNumCfgs8 = 0 MDHIP_CONV8_CFGS(MDHIP_COUNT_ROW);
 constexpr int kNumProf8 = 0 MDHIP_CONV8_PROF(MDHIP_COUNT_ROW);          // developer variants, behind the configurations
 
 namespace {
-hipError_t conv8_init() {
-    hipError_t e = hipSuccess;
-#define X(id, bm, bn, wm, wn, prof)                                                              \
-    if (e == hipSuccess)                                                                       \
-        e = hipFuncSetAttribute((const void*)conv_f8_kernel<bm, bn, wm, wn, prof>,                \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_cfgs8[id].lds_bytes);
-    MDHIP_CONV8_CFGS(X) MDHIP_CONV8_PROF(X)
+ConvInstTable conv8_insts() {
+    static const ConvInst t[] = {
+#define X(id, bm, bn, wm, wn, prof) MDHIP_INST(id, 0, (wm) * (wn) * 64, f8_lds_bytes(bm, bn), conv_f8_kernel<bm, bn, wm, wn, prof>)
+        MDHIP_CONV8_CFGS(X) MDHIP_CONV8_PROF(X)
 #undef X
-    return e;
+    };
+    return {t, (int)(sizeof(t) / sizeof(t[0]))};
 }
 
 bool conv8_supports(int cfg, const ConvArgs& a) {
@@ -521,22 +505,13 @@ bool conv8_supports(int cfg, const ConvArgs& a) {
 
 hipError_t conv8_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     if (!conv8_supports(cfg, a)) return hipErrorInvalidValue;
-    const ConvCfg& c = g_cfgs8[cfg];
     ConvArgs p = a;
-    const dim3 grid = conv_tile_grid(p, c);
-    switch (cfg) {
-#define X(id, bm, bn, wm, wn, prof)                                                               \
-    case id:                                                                                    \
-        hipLaunchKernelGGL((conv_f8_kernel<bm, bn, wm, wn, prof>), grid, dim3((wm) * (wn) * 64), c.lds_bytes, s, p); \
-        break;
-        MDHIP_CONV8_CFGS(X) MDHIP_CONV8_PROF(X)
-#undef X
-    }
-    return hipGetLastError();
+    const dim3 grid = conv_tile_grid(p, g_cfgs8[cfg]);
+    return conv_launch_inst(conv_find_inst(conv8_insts(), cfg, 0), grid, p, s);
 }
 }  // namespace
 
-MDHIP_CONV_FAMILY(conv_f8, CONV_F8, g_cfgs8, kNumCfgs8, kNumProf8, false, true, false, conv8_supports, conv8_launch, conv8_init, nullptr)
+MDHIP_CONV_FAMILY(conv_f8, CONV_F8, g_cfgs8, kNumCfgs8, kNumProf8, false, true, false, conv8_supports, conv8_launch, conv8_insts)
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

@@ -32,33 +32,12 @@
 //   and the weight panel) are placed on the same XCD/L2.
 
 #include <algorithm>
+#include <vector>
 
-#include "mdhip_internal.h"
+#include "conv_device.h"
 
 namespace mdhip {
 namespace MDHIP_ST {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-typedef __attribute__((address_space(3))) char lds_char;
-
-// 16 bytes per lane, HBM/L2 -> LDS directly: LDS address = m0-base (wave-uniform) + lane*16;
-// source = descriptor base + voff (per lane) + soff (wave-uniform SGPR).  A lane whose voff is
-// >= num_records reads zeros: that is how conv padding, K padding and ragged tiles are done.
-#define MDHIP_BLDS16(rsrc, lptr, voff, soff) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (lptr), 16, (voff), (soff), 0, 0)
-
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;        // >= every descriptor's num_records
-[[maybe_unused]] constexpr int kNumRecords = 0x7fffffff;
-
-
-// SiLU = x * sigmoid(x): v_mul, v_exp, v_add, v_rcp, v_mul (each <= 1 ulp: far inside the bf16
-// rounding that follows)
-__device__ __forceinline__ float silu_f32(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-}
-
-// two fp32 -> packed bf16, round-to-nearest-even in hardware (v_cvt_pk_bf16_f32)
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
@@ -138,7 +117,7 @@ conv_igemm_kernel(const ConvArgs p) {
     const int lr = lane >> 3;              // row inside an 8-row load instruction (== row & 7)
     const int jj = (lane & 7) ^ lr;        // swizzled source chunk inside the 128-byte K slab
     const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.wgt + (size_t)n0 * p.k_pad), 0, kNumRecords, 0x00020000);
+        (void*)(p.wgt + (size_t)n0 * p.k_pad), 0, kNumRecords, kRsrcFlags);
     unsigned b_off[B_PER];                 // byte offset of (row, chunk jj); the slab adds kt*128 as SGPR offset
 #pragma unroll
     for (int i = 0; i < B_PER; ++i) {
@@ -163,7 +142,7 @@ conv_igemm_kernel(const ConvArgs p) {
     auto init_loader_tile = [&](int tile_m) {
         const int m0 = tile_m * BM;
         if (pointwise) {                                                            // wave-uniform
-            a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + (long long)m0 * p.ld_in), 0, kNumRecords, 0x00020000);
+            a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + (long long)m0 * p.ld_in), 0, kNumRecords, kRsrcFlags);
 #pragma unroll
             for (int i = 0; i < A_PER; ++i) {
                 const int row = (i * NW + wave) * 8 + lr;
@@ -180,7 +159,7 @@ conv_igemm_kernel(const ConvArgs p) {
         const int oy0 = conv_udiv(rem0, p.Wo, p.rcp_wo);
         const int ox0 = rem0 - oy0 * p.Wo;
         const long long base_px = (long long)(b0 * p.H + oy0 * p.stride - p.pad) * p.W + (ox0 * p.stride - p.pad);
-        a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + base_px * p.ld_in), 0, kNumRecords, 0x00020000);
+        a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + base_px * p.ld_in), 0, kNumRecords, kRsrcFlags);
 #pragma unroll
         for (int i = 0; i < A_PER; ++i) {
             const int row = (i * NW + wave) * 8 + lr;
@@ -229,14 +208,14 @@ conv_igemm_kernel(const ConvArgs p) {
 #pragma unroll
         for (int i = 0; i < A_PER; ++i) {
             const unsigned voff = (a_mask[i] & bit) ? a_off[i] + tapoff : kOOB;
-            MDHIP_BLDS16(a_rsrc, sA + (i * NW + wave) * 1024, voff, 0);
+            MDHIP_DMA16(a_rsrc, sA + (i * NW + wave) * 1024, voff, 0);
         }
         const int soff = l_kt * 128;
 #pragma unroll
         for (int i = 0; i < B_PER; ++i) {
             const int instr = i * NW + wave;
             lds_char* dst = (instr < B_INSTR) ? sB + instr * 1024 : smem + DUMP_OFF;
-            MDHIP_BLDS16(b_rsrc, dst, b_off[i], soff);
+            MDHIP_DMA16(b_rsrc, dst, b_off[i], soff);
         }
         c8 += 8;                           // advance this lane's K position by one slab
         while (c8 >= p.C8) {
@@ -336,15 +315,10 @@ conv_igemm_kernel(const ConvArgs p) {
                 uint16_t* orow = (uint16_t*)p.out + (size_t)m * p.ld_out;
 #pragma unroll
                 for (int j = 0; j + 1 < FN; j += 2) {
-                    const unsigned a0 = st_pack2(v[j][0], v[j][1]), a1 = st_pack2(v[j][2], v[j][3]);
-                    const unsigned b0 = st_pack2(v[j + 1][0], v[j + 1][1]), b1 = st_pack2(v[j + 1][2], v[j + 1][3]);
-                    const auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-                    const auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-                    const auto t0 = __builtin_amdgcn_permlane16_swap(s0[0], s0[1], false, false);
-                    const auto t1 = __builtin_amdgcn_permlane16_swap(s1[0], s1[1], false, false);
+                    const u32x4 d = conv_pack_pair(v[j], v[j + 1]);
                     // row q of the wave now holds channels q*8 .. q*8+7 of this pair's 32 channels
                     const int n = n0 + wn * TN + j * 16 + q4 * 8;
-                    if (m_ok && n < p.N) *(uint4*)(orow + n) = make_uint4(t0[0], t1[0], t0[1], t1[1]);
+                    if (m_ok && n < p.N) *(uint4*)(orow + n) = make_uint4(d[0], d[1], d[2], d[3]);
                 }
                 if (FN & 1) {
                     const int j = FN - 1;
@@ -481,60 +455,38 @@ static const ConvCfg g_cfgs[] = {
 constexpr int kNumV1 = (int)(sizeof(g_cfgs) / sizeof(g_cfgs[0]));
 
 namespace {
-// the configurations that exist in a decoding instantiation (DEC): the narrow tiles a 24-channel op is given
-constexpr bool v1_decodes(int bn) { return bn <= 80; }
+// a configuration's rows: the kernel, and for the narrow tiles a 24-channel op is given the instantiation that decodes (DEC)
 template <int BM, int BN, int WM, int WN, int NS, int FP>
-hipError_t v1_set_lds(int lds) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_igemm_kernel<BM, BN, WM, WN, NS, FP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if constexpr (v1_decodes(BN)) {
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)conv_igemm_kernel<BM, BN, WM, WN, NS, FP, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    }
-    return e;
+void v1_rows(int id, std::vector<ConvInst>& t) {
+    t.push_back({(const void*)conv_igemm_kernel<BM, BN, WM, WN, NS, FP>, id, 0, WM * WN * 64, (size_t)conv_lds_bytes(BM, BN, NS)});
+    if constexpr (BN <= 80)
+        t.push_back({(const void*)conv_igemm_kernel<BM, BN, WM, WN, NS, FP, 1>, id, CONV_KEY_DEC, WM * WN * 64, (size_t)conv_lds_bytes(BM, BN, NS)});
 }
-template <int BM, int BN, int WM, int WN, int NS, int FP>
-hipError_t v1_launch(const ConvArgs& p, dim3 grid, size_t lds, hipStream_t s) {
-    if (p.dec_pred) {
-        if constexpr (v1_decodes(BN)) {
-            hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, NS, FP, 1>), grid, dim3(WM * WN * 64), lds, s, p);
-            return hipGetLastError();
-        }
-        return hipErrorInvalidValue;
-    }
-    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, NS, FP>), grid, dim3(WM * WN * 64), lds, s, p);
-    return hipGetLastError();
-}
-
-bool igemm_decodes(int cfg) { return v1_decodes(g_cfgs[cfg].bn); }
-bool igemm_supports(int, const ConvArgs&) { return true; }             // this kernel takes every 16-bit op
-
-hipError_t igemm_init() {
-    hipError_t e = hipSuccess;
-#define X(id, bm, bn, wm, wn, ns, fp, prior) \
-    if (e == hipSuccess) e = v1_set_lds<bm, bn, wm, wn, ns, fp>((int)g_cfgs[id].lds_bytes);
-    MDHIP_CONV_CFGS(X)
+ConvInstTable igemm_insts() {
+    static const std::vector<ConvInst> t = [] {
+        std::vector<ConvInst> v;
+#define X(id, bm, bn, wm, wn, ns, fp, prior) v1_rows<bm, bn, wm, wn, ns, fp>(id, v);
+        MDHIP_CONV_CFGS(X)
 #undef X
-    return e;
+        return v;
+    }();
+    return {t.data(), (int)t.size()};
 }
+
+bool igemm_supports(int, const ConvArgs&) { return true; }             // this kernel takes every 16-bit op
 
 hipError_t igemm_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     if (cfg < 0 || cfg >= kNumV1 || a.in_f8) return hipErrorInvalidValue;
-    const ConvCfg& c = g_cfgs[cfg];
     ConvArgs p = a;
     conv_set_rcp(p);
-    const dim3 grid = conv_tile_grid(p, c);
-    if (!conv_decode_ok(igemm_decodes(cfg), p)) return hipErrorInvalidValue;
-    switch (cfg) {
-#define X(id, bm, bn, wm, wn, ns, fp, prior) \
-    case id: return v1_launch<bm, bn, wm, wn, ns, fp>(p, grid, c.lds_bytes, s);
-        MDHIP_CONV_CFGS(X)
-#undef X
-    }
-    return hipErrorInvalidValue;
+    const dim3 grid = conv_tile_grid(p, g_cfgs[cfg]);
+    const ConvInst* inst = conv_find_inst(igemm_insts(), cfg, p.dec_pred ? CONV_KEY_DEC : 0);
+    if (!conv_decode_ok(inst != nullptr, p)) return hipErrorInvalidValue;
+    return conv_launch_inst(inst, grid, p, s);
 }
 }  // namespace
 
-MDHIP_CONV_FAMILY(conv_igemm, CONV_IGEMM, g_cfgs, kNumV1, 0, true, false, true, igemm_supports, igemm_launch, igemm_init, igemm_decodes)
+MDHIP_CONV_FAMILY(conv_igemm, CONV_IGEMM, g_cfgs, kNumV1, 0, true, false, true, igemm_supports, igemm_launch, igemm_insts)
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

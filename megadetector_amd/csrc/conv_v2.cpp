@@ -28,23 +28,12 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "mdhip_internal.h"
+#include "conv_device.h"
 
 namespace mdhip {
 namespace MDHIP_ST {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(3))) char lds_char;
-
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;        // >= every descriptor's num_records: the lane reads zeros
-[[maybe_unused]] constexpr int kNumRecords = 0x7fffffff;
-
-__device__ __forceinline__ float silu_f32(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-}
 
 constexpr int v2_lds_bytes(int bm, int bn) { return 2 * (bm + bn) * 128; }
 constexpr int v2_ring_lds_bytes(int bm, int bn) { return (3 * bm + 2 * bn) * 128; }
@@ -60,9 +49,6 @@ constexpr int v2_waves_per_simd(int bm, int bn, int nw) {
 }
 
 }  // namespace
-
-#define MDHIP_DMA16(rsrc, lptr, voff, soff) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (lptr), 16, (voff), (soff), 0, 0)
 
 // PROF = 1: timing-only instrumentation (s_memtime at the phase boundaries of every step, summed per
 // wave and written to p.dbg); used by tools/convbench.cpp, never by the product path
@@ -120,7 +106,7 @@ conv_v2_kernel(const ConvArgs p) {
     const int lr = lane >> 3;
     const int jj = (lane & 7) ^ lr;        // swizzled source chunk inside the 128-byte K slab
     const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.wgt + (size_t)n0 * p.k_pad), 0, kNumRecords, 0x00020000);
+        (void*)(p.wgt + (size_t)n0 * p.k_pad), 0, kNumRecords, kRsrcFlags);
     unsigned b_off[B_PER];
 #pragma unroll
     for (int i = 0; i < B_PER; ++i) {
@@ -135,7 +121,7 @@ conv_v2_kernel(const ConvArgs p) {
     // nearest-neighbour upsample read in place (1x1 convs only): the slabs [0, up_slabs) of K come from the low-resolution
     // producer of the concatenated input's first part, at this lane's pixel halved
     const int up_slabs = UP ? p.up_slabs : 0;
-    [[maybe_unused]] const __amdgpu_buffer_rsrc_t u_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(UP ? p.in_up : p.in), 0, kNumRecords, 0x00020000);
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t u_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(UP ? p.in_up : p.in), 0, kNumRecords, kRsrcFlags);
     [[maybe_unused]] unsigned u_off[UP ? A_PER : 1];
     // position of this lane's 16-byte chunk inside K (valid for C8 >= 8: at most one tap wrap per slab)
     int c8 = 0, ts = 0;
@@ -162,7 +148,7 @@ conv_v2_kernel(const ConvArgs p) {
             const int m0 = tile_m * BM;
             const long long left = ((long long)p.M - m0) * p.ld_in * 2;
             a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + (long long)m0 * p.ld_in), 0,
-                                                       (int)(left > 0x7fffffffLL ? 0x7fffffffLL : left), 0x00020000);
+                                                       (int)(left > 0x7fffffffLL ? 0x7fffffffLL : left), kRsrcFlags);
 #pragma unroll
             for (int i = 0; i < A_PER; ++i) {
                 const int row = (i * NW + wave) * 8 + lr;
@@ -178,7 +164,7 @@ conv_v2_kernel(const ConvArgs p) {
         const int oy0 = conv_udiv(rem0, p.Wo, p.rcp_wo);
         const int ox0 = rem0 - oy0 * p.Wo;
         const long long base_px = (long long)(b0 * p.H + oy0 * p.stride - p.pad) * p.W + (ox0 * p.stride - p.pad);
-        a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + base_px * p.ld_in), 0, kNumRecords, 0x00020000);
+        a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + base_px * p.ld_in), 0, kNumRecords, kRsrcFlags);
 #pragma unroll
         for (int i = 0; i < A_PER; ++i) {
             const int row = (i * NW + wave) * 8 + lr;
@@ -321,8 +307,6 @@ conv_v2_kernel(const ConvArgs p) {
         // and tensor, tile-relative descriptors, rows past the end dropped / read as zeros by the range check -- no
         // 64-bit address arithmetic and no branch around every store.  The offsets come from an opaque copy of the lane
         // id so that they are computed here and not kept alive across the main loop.
-        typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-        typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
         int lane_e = lane;
         asm volatile("" : "+v"(lane_e));
         float neg_log2e = kNegLog2e;                             // (opaque: not a register pair kept across the main loop)
@@ -334,17 +318,15 @@ conv_v2_kernel(const ConvArgs p) {
         const long long rows_left = (long long)p.M - (long long)tile_m * BM;
         const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc(
             (void*)((uint16_t*)p.out + (size_t)tile_m * BM * p.ld_out), 0,
-            (OUT_F32 || OUT_F8) ? 0 : (int)min(rows_left * p.ld_out * 2, 0x7fffffffLL), 0x00020000);
+            (OUT_F32 || OUT_F8) ? 0 : (int)min(rows_left * p.ld_out * 2, 0x7fffffffLL), kRsrcFlags);
         const unsigned o_pair = ((unsigned)ml * (unsigned)p.ld_out + (unsigned)npair0) * 2u;
         const unsigned o_last = ((unsigned)ml * (unsigned)p.ld_out + (unsigned)nlast) * 2u;
         const unsigned o_step = 16u * (unsigned)p.ld_out * 2u;
         const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
             (void*)(p.res + (HAS_RES ? (size_t)tile_m * BM * p.ld_res : 0)), 0,
-            HAS_RES ? (int)min(rows_left * p.ld_res * 2, 0x7fffffffLL) : 0, 0x00020000);
+            HAS_RES ? (int)min(rows_left * p.ld_res * 2, 0x7fffffffLL) : 0, kRsrcFlags);
         const unsigned r_col = ((unsigned)ml * (unsigned)p.ld_res + (unsigned)(n0 + wn * TN + qe * 4)) * 2u;
         const unsigned r_step = 16u * (unsigned)p.ld_res * 2u;
-        // bias of all fragment columns first (scalar loads), then pixel-row by pixel-row so that the
-        // stores that complete one cache line are issued back to back
         // bias of all fragment columns first (scalar loads), then pixel-row by pixel-row so that the
         // stores that complete one cache line are issued back to back
         // (round 3, measured and not kept: the five columns as vector loads issued together -- the compiler's vmcnt wait
@@ -436,7 +418,7 @@ conv_v2_kernel(const ConvArgs p) {
                 // e4m3 output (MDHIP_DTYPE_FP8: the hidden tensor of a bottleneck): 4 channels = 4 bytes per lane and
                 // fragment; the same exchange as the 16-bit path leaves 8 consecutive channels = 8 bytes per lane
                 const __amdgpu_buffer_rsrc_t o8_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                    (void*)((uint8_t*)p.out + (size_t)tile_m * BM * p.ld_out), 0, (int)min(rows_left * p.ld_out, 0x7fffffffLL), 0x00020000);
+                    (void*)((uint8_t*)p.out + (size_t)tile_m * BM * p.ld_out), 0, (int)min(rows_left * p.ld_out, 0x7fffffffLL), kRsrcFlags);
                 const unsigned row8 = (unsigned)(ml + i * 16) * (unsigned)p.ld_out;
 #pragma unroll
                 for (int j = 0; j + 1 < FN; j += 2) {
@@ -458,6 +440,7 @@ conv_v2_kernel(const ConvArgs p) {
                 // = 16 bytes, and one store covers 64 contiguous bytes per pixel instead of 32
 #pragma unroll
                 for (int j = 0; j + 1 < FN; j += 2) {
+                    // (written out, not conv_pack_pair of conv_device.h: with the helper this unit's code comes out in another order)
                     unsigned a0 = st_pack2(v[j][0], v[j][1]), a1 = st_pack2(v[j][2], v[j][3]);
                     unsigned b0 = st_pack2(v[j + 1][0], v[j + 1][1]), b1 = st_pack2(v[j + 1][2], v[j + 1][3]);
                     auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
@@ -651,7 +634,7 @@ conv_v2_kernel(const ConvArgs p) {
     X(10, 64, 160, 1, 2)    \
     X(11, 320, 160, 4, 2)   \
     X(12, 256, 160, 4, 2)
-// the configurations that also exist as a decoding instantiation (DEC = 1; conv2_cfg_decodes): id, BM, BN, WM, WN
+// the configurations that also exist as a decoding instantiation (DEC = 1; pointwise, whole 64-channel slabs -- the tiles the tables give the 24-channel Detect convs): id, BM, BN, WM, WN
 #define MDHIP_CONV2_DEC(X) \
     X(0, 160, 160, 2, 2)   \
     X(2, 160, 80, 2, 1)    \
@@ -697,62 +680,52 @@ constexpr int kNumCfgs2 = kNumPlain2 MDHIP_CONV2_RING(MDHIP_COUNT_ROW);
 constexpr int kNumProf = 0 MDHIP_CONV2_PROF(MDHIP_COUNT_ROW) MDHIP_CONV2_PROFRING(MDHIP_COUNT_ROW);   // trailing instrumented entries: developer variants
 
 namespace {
-hipError_t conv2_init() {
-    hipError_t e = hipSuccess;
-#define X(id, bm, bn, wm, wn)                                                                        \
-    if (e == hipSuccess)                                                                           \
-        e = hipFuncSetAttribute((const void*)conv_v2_kernel<bm, bn, wm, wn>,                          \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_cfgs2[id].lds_bytes); \
-    if (e == hipSuccess)                                                                           \
-        e = hipFuncSetAttribute((const void*)conv_v2_kernel<bm, bn, wm, wn, 0, false, 1>,             \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_cfgs2[id].lds_bytes); \
-    if (e == hipSuccess)                                                                           \
-        e = hipFuncSetAttribute((const void*)conv_v2_kernel<bm, bn, wm, wn, 0, false, 2>,             \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_cfgs2[id].lds_bytes);
-    MDHIP_CONV2_CFGS(X)
+// keys: PW 0 / 1 / 2 of the configurations, the upsample read in place (UP), the one instantiation of a developer variant --
+// for the ring ones a pointwise instantiation
+enum { V2_PLAIN = 0, V2_PW1, V2_PW2, V2_UP, V2_DEV, V2_DEV_PW };
+ConvInstTable conv2_insts() {
+    static const ConvInst t[] = {
+#define X(id, bm, bn, wm, wn)                                                                                         \
+    MDHIP_INST(id, V2_PLAIN, (wm) * (wn) * 64, v2_lds_bytes(bm, bn), conv_v2_kernel<bm, bn, wm, wn>)                  \
+    MDHIP_INST(id, V2_PW1, (wm) * (wn) * 64, v2_lds_bytes(bm, bn), conv_v2_kernel<bm, bn, wm, wn, 0, false, 1>)       \
+    MDHIP_INST(id, V2_PW2, (wm) * (wn) * 64, v2_lds_bytes(bm, bn), conv_v2_kernel<bm, bn, wm, wn, 0, false, 2>)
+        MDHIP_CONV2_CFGS(X)
 #undef X
-#define X(id, bm, bn, wm, wn)                                                                        \
-    if (e == hipSuccess)                                                                           \
-        e = hipFuncSetAttribute((const void*)conv_v2_kernel<bm, bn, wm, wn, 0, false, 1, 3>,          \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_cfgs2[id].lds_bytes); \
-    if (e == hipSuccess)                                                                           \
-        e = hipFuncSetAttribute((const void*)conv_v2_kernel<bm, bn, wm, wn, 0, false, 2, 3>,          \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_cfgs2[id].lds_bytes);
-    MDHIP_CONV2_RING(X)
+#define X(id, bm, bn, wm, wn)                                                                                         \
+    MDHIP_INST(id, V2_PW1, (wm) * (wn) * 64, v2_ring_lds_bytes(bm, bn), conv_v2_kernel<bm, bn, wm, wn, 0, false, 1, 3>) \
+    MDHIP_INST(id, V2_PW2, (wm) * (wn) * 64, v2_ring_lds_bytes(bm, bn), conv_v2_kernel<bm, bn, wm, wn, 0, false, 2, 3>)
+        MDHIP_CONV2_RING(X)
 #undef X
-#define X(id, bm, bn, wm, wn, prof)                                                                  \
-    if (e == hipSuccess)                                                                           \
-        e = hipFuncSetAttribute((const void*)conv_v2_kernel<bm, bn, wm, wn, prof>,                       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_cfgs2[id].lds_bytes);
-    MDHIP_CONV2_PROF(X)
+#define X(id, bm, bn, wm, wn, prof) MDHIP_INST(id, V2_DEV, (wm) * (wn) * 64, v2_lds_bytes(bm, bn), conv_v2_kernel<bm, bn, wm, wn, prof>)
+        MDHIP_CONV2_PROF(X)
 #undef X
-#define X(id, bm, bn, wm, wn, prof)                                                                  \
-    if (e == hipSuccess)                                                                           \
-        e = hipFuncSetAttribute((const void*)conv_v2_kernel<bm, bn, wm, wn, prof, false, 1, 3>,       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_cfgs2[id].lds_bytes);
-    MDHIP_CONV2_PROFRING(X)
+#define X(id, bm, bn, wm, wn, prof) MDHIP_INST(id, V2_DEV_PW, (wm) * (wn) * 64, v2_ring_lds_bytes(bm, bn), conv_v2_kernel<bm, bn, wm, wn, prof, false, 1, 3>)
+        MDHIP_CONV2_PROFRING(X)
 #undef X
-#define X(id, bm, bn, wm, wn)                                                                        \
-    if (e == hipSuccess)                                                                           \
-        e = hipFuncSetAttribute((const void*)conv_v2_kernel<bm, bn, wm, wn, 0, false, 1, 2, 1>,       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_cfgs2[id].lds_bytes);
-    MDHIP_CONV2_DEC(X)
+#define X(id, bm, bn, wm, wn) MDHIP_INST(id, CONV_KEY_DEC, (wm) * (wn) * 64, v2_lds_bytes(bm, bn), conv_v2_kernel<bm, bn, wm, wn, 0, false, 1, 2, 1>)
+        MDHIP_CONV2_DEC(X)
 #undef X
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv_v2_kernel<160, 160, 2, 2, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)g_cfgs2[0].lds_bytes);
-    return e;
+        MDHIP_INST(0, V2_UP, 256, v2_lds_bytes(160, 160), conv_v2_kernel<160, 160, 2, 2, 0, true>)
+    };
+    return {t, (int)(sizeof(t) / sizeof(t[0]))};
+}
+const ConvInst* conv2_pick(int cfg, const ConvArgs& a) {
+    const ConvInstTable t = conv2_insts();
+    if (a.in_up) return a.dec_pred ? nullptr : conv_find_inst(t, cfg, V2_UP);       // upsample read in place: 160x160 only
+    // 1x1 / stride 1 / unpadded: the instantiations whose tile set-up needs no divisions (same loads, same results), PW 1 on
+    // whole 64-channel slabs; the ring configurations and the decoding instantiations exist as such only
+    const bool pw = a.ntaps == 1 && a.stride == 1 && a.pad == 0 && a.H == a.Ho && a.W == a.Wo, whole = (a.C8 & 7) == 0;
+    if (a.dec_pred) return pw && whole && a.out_f32 ? conv_find_inst(t, cfg, CONV_KEY_DEC) : nullptr;   // Detect conv that decodes in its epilogue
+    if (cfg >= kNumCfgs2) {
+        const ConvInst* dev = conv_find_inst(t, cfg, V2_DEV);
+        return dev || !(pw && whole) ? dev : conv_find_inst(t, cfg, V2_DEV_PW);
+    }
+    return conv_find_inst(t, cfg, !pw ? V2_PLAIN : whole ? V2_PW1 : V2_PW2);
 }
 
-// (the configurations with a three-stage activation ring: 1x1 / stride 1 / unpadded launches only, at least three K slabs)
+// (the configurations with a three-stage activation ring: pointwise instantiations only, and at least three K slabs)
 bool conv2_cfg_is_ring(int cfg) { return cfg >= kNumPlain2 && cfg < kNumCfgs2; }
-// the configurations with a decoding instantiation (pointwise, channel count a multiple of 64): the tiles the tables give the
-// 24-channel Detect convs
-bool conv2_cfg_decodes(int cfg) { return cfg == 0 || cfg == 2 || cfg == 3 || cfg == 8; }
-bool conv2_is_pointwise(const ConvArgs& a) {
-    return a.ntaps == 1 && a.stride == 1 && a.pad == 0 && a.H == a.Ho && a.W == a.Wo && a.in_up == nullptr;
-}
-// what every launch needs of an op (conv2_launch checks no more than this)
+// what every launch needs of an op
 bool conv2_shape_ok(const ConvArgs& a) {
     // the branch-free K walk needs at least one whole slab per tap; the epilogue stores 4 channels
     if (a.in_up && !(a.ntaps == 1 && a.stride == 1 && (a.H % 2) == 0 && (a.W % 2) == 0 && a.up_slabs > 0 &&
@@ -762,70 +735,20 @@ bool conv2_shape_ok(const ConvArgs& a) {
 }
 bool conv2_supports(int cfg, const ConvArgs& a) {
     if (cfg < 0 || cfg >= kNumCfgs2 + kNumProf) return false;
-    if (conv2_cfg_is_ring(cfg) && !(conv2_is_pointwise(a) && a.k_pad >= 3 * 64)) return false;
-    return conv2_shape_ok(a) && (a.in_up == nullptr || cfg == 0);                   // in_up: 160x160 only
+    if (conv2_cfg_is_ring(cfg) && a.k_pad < 3 * 64) return false;
+    return conv2_shape_ok(a) && conv2_pick(cfg, a) != nullptr;
 }
 
 hipError_t conv2_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     if (cfg < 0 || cfg >= kNumCfgs2 + kNumProf || !conv2_shape_ok(a)) return hipErrorInvalidValue;
-    const ConvCfg& c = g_cfgs2[cfg];
     ConvArgs p = a;
     conv_set_rcp(p);
-    const dim3 grid = conv_tile_grid(p, c);
-    if (a.in_up) {                                     // upsample read in place: configuration 0 (160x160) only
-        hipLaunchKernelGGL((conv_v2_kernel<160, 160, 2, 2, 0, true>), grid, dim3(256), c.lds_bytes, s, p);
-        return hipGetLastError();
-    }
-    // 1x1 / stride 1 / unpadded: the instantiation whose tile set-up needs no divisions (same loads, same results)
-    const bool pw = a.ntaps == 1 && a.stride == 1 && a.pad == 0 && a.H == a.Ho && a.W == a.Wo;
-    if (a.dec_pred) {                                  // Detect conv that decodes in its epilogue
-        if (!pw || (a.C8 & 7) != 0 || !a.out_f32 || !conv2_cfg_decodes(cfg)) return hipErrorInvalidValue;
-        switch (cfg) {
-#define X(id, bm, bn, wm, wn)                                                                        \
-    case id:                                                                                       \
-        hipLaunchKernelGGL((conv_v2_kernel<bm, bn, wm, wn, 0, false, 1, 2, 1>), grid, dim3((wm) * (wn) * 64), c.lds_bytes, s, p); \
-        break;
-            MDHIP_CONV2_DEC(X)
-#undef X
-        }
-        return hipGetLastError();
-    }
-    switch (cfg) {
-#define X(id, bm, bn, wm, wn)                                                                        \
-    case id:                                                                                       \
-        if (pw && (a.C8 & 7) == 0) hipLaunchKernelGGL((conv_v2_kernel<bm, bn, wm, wn, 0, false, 1>), grid, dim3((wm) * (wn) * 64), c.lds_bytes, s, p); \
-        else if (pw) hipLaunchKernelGGL((conv_v2_kernel<bm, bn, wm, wn, 0, false, 2>), grid, dim3((wm) * (wn) * 64), c.lds_bytes, s, p); \
-        else hipLaunchKernelGGL((conv_v2_kernel<bm, bn, wm, wn>), grid, dim3((wm) * (wn) * 64), c.lds_bytes, s, p); \
-        break;
-        MDHIP_CONV2_CFGS(X)
-#undef X
-#define X(id, bm, bn, wm, wn)                                                                        \
-    case id:                                                                                       \
-        if (!pw) return hipErrorInvalidValue;                                                      \
-        if ((a.C8 & 7) == 0) hipLaunchKernelGGL((conv_v2_kernel<bm, bn, wm, wn, 0, false, 1, 3>), grid, dim3((wm) * (wn) * 64), c.lds_bytes, s, p); \
-        else hipLaunchKernelGGL((conv_v2_kernel<bm, bn, wm, wn, 0, false, 2, 3>), grid, dim3((wm) * (wn) * 64), c.lds_bytes, s, p); \
-        break;
-        MDHIP_CONV2_RING(X)
-#undef X
-#define X(id, bm, bn, wm, wn, prof)                                                                  \
-    case id:                                                                                       \
-        hipLaunchKernelGGL((conv_v2_kernel<bm, bn, wm, wn, prof>), grid, dim3((wm) * (wn) * 64), c.lds_bytes, s, p); \
-        break;
-        MDHIP_CONV2_PROF(X)
-#undef X
-#define X(id, bm, bn, wm, wn, prof)                                                                  \
-    case id:                                                                                       \
-        if (!pw || (a.C8 & 7) != 0) return hipErrorInvalidValue;                                   \
-        hipLaunchKernelGGL((conv_v2_kernel<bm, bn, wm, wn, prof, false, 1, 3>), grid, dim3((wm) * (wn) * 64), c.lds_bytes, s, p); \
-        break;
-        MDHIP_CONV2_PROFRING(X)
-#undef X
-    }
-    return hipGetLastError();
+    const dim3 grid = conv_tile_grid(p, g_cfgs2[cfg]);
+    return conv_launch_inst(conv2_pick(cfg, a), grid, p, s);
 }
 }  // namespace
 
-MDHIP_CONV_FAMILY(conv_v2, CONV_V2, g_cfgs2, kNumCfgs2, kNumProf, true, false, true, conv2_supports, conv2_launch, conv2_init, conv2_cfg_decodes)
+MDHIP_CONV_FAMILY(conv_v2, CONV_V2, g_cfgs2, kNumCfgs2, kNumProf, true, false, true, conv2_supports, conv2_launch, conv2_insts)
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

@@ -37,25 +37,14 @@
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
+#include <vector>
 
-#include "mdhip_internal.h"
+#include "conv_device.h"
 
 namespace mdhip {
 namespace MDHIP_ST {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(3))) char lds_char;
-
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;
-[[maybe_unused]] constexpr int kNumRecords = 0x7fffffff;
-
-__device__ __forceinline__ float silu_f32(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-}
-typedef mdhip_f32x2 f32x2;
 
 constexpr int v5_run_pieces(int bm) { return (bm + 2 + 7) / 8; }
 // the row of zeros (256 bytes) and, behind it, the staged bias of the workgroup's BN channels: whole KiB
@@ -76,9 +65,6 @@ constexpr int v5_waves_per_simd(int bm, int bn, int nw) {
 }
 
 }  // namespace
-
-#define MDHIP_DMA16(rsrc, lptr, voff, soff) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (lptr), 16, (voff), (soff), 0, 0)
 
 // PROF bits (developer builds only): 1 = s_memtime stamps, 2 = no stores, 4 = no SiLU, 16 = no DMA in the steady state,
 // 32 = no tap-validity selects (timing experiment: wrong at image borders), 64 = no paired / short last group
@@ -165,7 +151,7 @@ conv_v5_kernel(const ConvArgs p) {
     const int jj = (lane & 7) ^ lr;
     const int w_kpad = pair ? p.k_pad4p : p.k_pad4;
     const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((pair ? p.wgt4p : p.wgt4) + (size_t)n0 * w_kpad), 0, kNumRecords, 0x00020000);
+        (void*)((pair ? p.wgt4p : p.wgt4) + (size_t)n0 * w_kpad), 0, kNumRecords, kRsrcFlags);
     // LEAN (the 8-wave tiles, which have no register to spare): one offset register for the wave's first piece, the
     // others are that + i * NW * 8 rows; needs every row of the tile to exist (conv5_supports: n_rows % BN == 0)
     constexpr bool LEAN = FM == 5 && FN == 5;
@@ -210,7 +196,7 @@ conv_v5_kernel(const ConvArgs p) {
     // are inside the batch but outside the image for some tap are dealt with at the fragment read.
     // (conv5_supports: the tensor is smaller than 4 GiB)
     const __amdgpu_buffer_rsrc_t a_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, (int)((unsigned)p.M * (unsigned)p.ld_in * 2u), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, (int)((unsigned)p.M * (unsigned)p.ld_in * 2u), kRsrcFlags);
     unsigned q_off[LEAN ? 1 : A_PER];              // byte offset of this lane's pixel + chunk from the run's first pixel
 #pragma unroll
     for (int i = 0; i < (LEAN ? 1 : A_PER); ++i) {
@@ -407,14 +393,12 @@ conv_v5_kernel(const ConvArgs p) {
         // check.  With 64-bit global addresses the compiler kept an address pair per column alive across the tile's main
         // loop, spilled them, and reloaded one before every store -- each reload an s_waitcnt vmcnt(0), i.e. a full
         // write round trip per store and no residual row ever in flight behind the one being finished.
-        typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-        typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
         const int npair0 = n0 + wn * TN + lq * 8;                      // first of this lane's 8 channels of column pair 0
         // (descriptors start at the tile's first pixel: offsets stay small whatever the tensor's size)
         const long long rows_left = (long long)p.M - (long long)tile_m * BM;
         const int ml = wm * TM + lp;                                    // this lane's pixel inside the tile (+ 16 per row i)
         const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)((uint16_t*)p.out + (size_t)tile_m * BM * p.ld_out), 0, (int)min(rows_left * p.ld_out * 2, 0x7fffffffLL), 0x00020000);
+            (void*)((uint16_t*)p.out + (size_t)tile_m * BM * p.ld_out), 0, (int)min(rows_left * p.ld_out * 2, 0x7fffffffLL), kRsrcFlags);
         const unsigned o_pair = ((unsigned)ml * (unsigned)p.ld_out + (unsigned)npair0) * 2u;
         const unsigned o_last = ((unsigned)ml * (unsigned)p.ld_out + (unsigned)nlast) * 2u;
         const unsigned o_step = 16u * (unsigned)p.ld_out * 2u;
@@ -444,7 +428,7 @@ conv_v5_kernel(const ConvArgs p) {
         uint2 rlast[RS];
         const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
             (void*)(p.res + (HAS_RES ? (size_t)tile_m * BM * p.ld_res : 0)), 0,
-            HAS_RES ? (int)min(rows_left * p.ld_res * 2, 0x7fffffffLL) : 0, 0x00020000);
+            HAS_RES ? (int)min(rows_left * p.ld_res * 2, 0x7fffffffLL) : 0, kRsrcFlags);
         const unsigned r_pair = ((unsigned)ml * (unsigned)p.ld_res + (unsigned)npair0) * 2u;
         const unsigned r_last = ((unsigned)ml * (unsigned)p.ld_res + (unsigned)nlast) * 2u;
         const unsigned r_step = 16u * (unsigned)p.ld_res * 2u;
@@ -520,15 +504,9 @@ conv_v5_kernel(const ConvArgs p) {
             } else {
 #pragma unroll
                 for (int j = 0; j + 1 < FN; j += 2) {
-                    unsigned a0 = st_pack2(v[j][0], v[j][1]), a1 = st_pack2(v[j][2], v[j][3]);
-                    unsigned b0 = st_pack2(v[j + 1][0], v[j + 1][1]), b1 = st_pack2(v[j + 1][2], v[j + 1][3]);
-                    auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-                    auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-                    auto t0 = __builtin_amdgcn_permlane16_swap(s0[0], s0[1], false, false);
-                    auto t1 = __builtin_amdgcn_permlane16_swap(s1[0], s1[1], false, false);
-                    const uint4 o = make_uint4(t0[0], t1[0], t0[1], t1[1]);
+                    const u32x4 d = conv_pack_pair(v[j], v[j + 1]);
                     const unsigned off = o_pair + (unsigned)i * o_step + (unsigned)(j * 32);
-                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{o.x, o.y, o.z, o.w}, o_rsrc,
+                    __builtin_amdgcn_raw_buffer_store_b128(d, o_rsrc,
                                                            (int)(n_ok(npair0 + j * 16) ? off : kOOB), 0, 0);
                 }
                 if (FN & 1) {
@@ -595,7 +573,6 @@ conv_v5_kernel(const ConvArgs p) {
     int c_r = 0, c_cg = 0, c_tile = first_tile, pa = 0, step = 0;
     [[maybe_unused]] bool after_epilogue = false;
     if constexpr ((PROF & 1) != 0) t_prev = __builtin_amdgcn_s_memtime();
-#define MDHIP_FENCE() __builtin_amdgcn_sched_barrier(0)
     // a half-full last channel group (C_in mod 64 <= 32) has nothing in k 32..63: its second-half MFMAs are skipped
     const bool tail_short = RT ? ((PROF & 64) == 0 && (p.C8 & 7) != 0 && (p.C8 & 7) <= 4) : TAIL >= 1;
     // DMA slots behind the MFMA chunks of a second half: the weight pieces of step + 2, then this step's share of the NEXT
@@ -719,7 +696,6 @@ conv_v5_kernel(const ConvArgs p) {
         }
         stamp(5);
     }
-#undef MDHIP_FENCE
     if constexpr ((PROF & 1) != 0) {
         if (lane == 0 && p.dbg) {
             unsigned long long* d = (unsigned long long*)p.dbg + ((size_t)blockIdx.x * NW + wave) * 8;
@@ -775,33 +751,45 @@ constexpr int kNumMain5 = 0 MDHIP_CONV5_CFGS(MDHIP_COUNT_ROW);
 constexpr int kNumProf5 = 0 MDHIP_CONV5_PROF(MDHIP_COUNT_ROW);          // developer variants, behind the configurations
 
 namespace {
-hipError_t conv5_init() {
-    hipError_t e = hipSuccess;
-#define X(id, bm, bn, wm, wn, prof)                                                              \
-    if (e == hipSuccess)                                                                       \
-        e = hipFuncSetAttribute((const void*)conv_v5_kernel<bm, bn, wm, wn, prof>,                \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_cfgs5[id].lds_bytes);
-    MDHIP_CONV5_PROF(X)
+// keys: TAIL 0 / 1 / 2 (the last channel group, see the kernel), + V5_KEY_AL for the aligned mode of the 8-wave tiles (AL);
+// a developer variant is one instantiation (TAIL decided inside the kernel)
+enum { V5_KEY_AL = 3, V5_KEY_DEV = 6 };
+template <int BM, int BN, int WM, int WN, int PROF>
+void v5_rows(int id, std::vector<ConvInst>& t) {
+    constexpr int threads = WM * WN * 64;
+    constexpr size_t lds = v5_lds_bytes(BM, BN), al_lds = lds + v5_al_extra_lds;
+    if constexpr (v5_is_lean(BM, BN, WM, WN)) {
+        t.push_back({(const void*)conv_v5_kernel<BM, BN, WM, WN, PROF, 0, true>, id, V5_KEY_AL + 0, threads, al_lds});
+        t.push_back({(const void*)conv_v5_kernel<BM, BN, WM, WN, PROF, 1, true>, id, V5_KEY_AL + 1, threads, al_lds});
+        t.push_back({(const void*)conv_v5_kernel<BM, BN, WM, WN, PROF, 2, true>, id, V5_KEY_AL + 2, threads, al_lds});
+    }
+    t.push_back({(const void*)conv_v5_kernel<BM, BN, WM, WN, PROF, 0>, id, 0, threads, lds});
+    t.push_back({(const void*)conv_v5_kernel<BM, BN, WM, WN, PROF, 1>, id, 1, threads, lds});
+    t.push_back({(const void*)conv_v5_kernel<BM, BN, WM, WN, PROF, 2>, id, 2, threads, lds});
+}
+ConvInstTable conv5_insts() {
+    static const std::vector<ConvInst> t = [] {
+        std::vector<ConvInst> v;
+#define X(id, bm, bn, wm, wn, prof) v.push_back({(const void*)conv_v5_kernel<bm, bn, wm, wn, prof>, id, V5_KEY_DEV, (wm) * (wn) * 64, (size_t)v5_lds_bytes(bm, bn)});
+        MDHIP_CONV5_PROF(X)
 #undef X
-#define X(id, bm, bn, wm, wn, prof)                                                              \
-    if constexpr ((bm) * (bn) == 320 * 160 && (wm) * (wn) == 8) {                                   \
-        const int al_lds = (int)g_cfgs5[id].lds_bytes + v5_al_extra_lds;                          \
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv_v5_kernel<bm, bn, wm, wn, prof, 0, v5_is_lean(bm, bn, wm, wn)>, hipFuncAttributeMaxDynamicSharedMemorySize, al_lds); \
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv_v5_kernel<bm, bn, wm, wn, prof, 1, v5_is_lean(bm, bn, wm, wn)>, hipFuncAttributeMaxDynamicSharedMemorySize, al_lds); \
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv_v5_kernel<bm, bn, wm, wn, prof, 2, v5_is_lean(bm, bn, wm, wn)>, hipFuncAttributeMaxDynamicSharedMemorySize, al_lds); \
-    }                                                                                          \
-    if (e == hipSuccess)                                                                       \
-        e = hipFuncSetAttribute((const void*)conv_v5_kernel<bm, bn, wm, wn, prof, 0>,             \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_cfgs5[id].lds_bytes); \
-    if (e == hipSuccess)                                                                       \
-        e = hipFuncSetAttribute((const void*)conv_v5_kernel<bm, bn, wm, wn, prof, 1>,             \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_cfgs5[id].lds_bytes); \
-    if (e == hipSuccess)                                                                       \
-        e = hipFuncSetAttribute((const void*)conv_v5_kernel<bm, bn, wm, wn, prof, 2>,             \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_cfgs5[id].lds_bytes);
-    MDHIP_CONV5_CFGS(X)
+#define X(id, bm, bn, wm, wn, prof) v5_rows<bm, bn, wm, wn, prof>(id, v);
+        MDHIP_CONV5_CFGS(X)
 #undef X
-    return e;
+        return v;
+    }();
+    return {t.data(), (int)t.size()};
+}
+const ConvInst* conv5_pick(int cfg, const ConvArgs& a) {
+    const ConvInstTable t = conv5_insts();
+    if (cfg >= kNumMain5) return conv_find_inst(t, cfg, V5_KEY_DEV);
+    // the last channel group (see TAIL): at most half full -> its k 32..63 MFMAs are skipped; with the paired packing two taps a step
+    const bool tail_short = (a.C8 & 7) != 0 && (a.C8 & 7) <= 4;
+    const int tail = !tail_short ? 0 : (a.wgt4p != nullptr ? 2 : 1);
+    // the 8-wave tiles' aligned mode (conv_v5_kernel AL): a wave's 80 pixels inside one image row; same results
+    const bool aligned = (a.W % 80) == 0 && a.dev_param != 77;
+    const ConvInst* al = aligned ? conv_find_inst(t, cfg, V5_KEY_AL + tail) : nullptr;      // (only those tiles have such rows)
+    return al ? al : conv_find_inst(t, cfg, tail);
 }
 
 bool conv5_supports(int cfg, const ConvArgs& a) {
@@ -820,42 +808,13 @@ bool conv5_supports(int cfg, const ConvArgs& a) {
 
 hipError_t conv5_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     if (!conv5_supports(cfg, a)) return hipErrorInvalidValue;
-    const ConvCfg& c = g_cfgs5[cfg];
     ConvArgs p = a;
-    const dim3 grid = conv_tile_grid(p, c);
-    // the last channel group (see TAIL): at most half full -> its k 32..63 MFMAs are skipped; with the paired packing two taps a step
-    const bool tail_short = (a.C8 & 7) != 0 && (a.C8 & 7) <= 4;
-    const int tail = !tail_short ? 0 : (a.wgt4p != nullptr ? 2 : 1);
-    // the 8-wave tiles' aligned mode (conv_v5_kernel AL): a wave's 80 pixels inside one image row; same results
-    const bool aligned = (a.W % 80) == 0 && a.dev_param != 77;
-    switch (cfg) {
-#define X(id, bm, bn, wm, wn, prof)                                                               \
-    case id:                                                                                    \
-        if (v5_is_lean(bm, bn, wm, wn) && aligned) {                                            \
-            const size_t al_lds = c.lds_bytes + v5_al_extra_lds;                                  \
-            if (tail == 0) hipLaunchKernelGGL((conv_v5_kernel<bm, bn, wm, wn, prof, 0, v5_is_lean(bm, bn, wm, wn)>), grid, dim3((wm) * (wn) * 64), al_lds, s, p); \
-            else if (tail == 1) hipLaunchKernelGGL((conv_v5_kernel<bm, bn, wm, wn, prof, 1, v5_is_lean(bm, bn, wm, wn)>), grid, dim3((wm) * (wn) * 64), al_lds, s, p); \
-            else hipLaunchKernelGGL((conv_v5_kernel<bm, bn, wm, wn, prof, 2, v5_is_lean(bm, bn, wm, wn)>), grid, dim3((wm) * (wn) * 64), al_lds, s, p); \
-            break;                                                                              \
-        }                                                                                       \
-        if (tail == 0) hipLaunchKernelGGL((conv_v5_kernel<bm, bn, wm, wn, prof, 0>), grid, dim3((wm) * (wn) * 64), c.lds_bytes, s, p); \
-        else if (tail == 1) hipLaunchKernelGGL((conv_v5_kernel<bm, bn, wm, wn, prof, 1>), grid, dim3((wm) * (wn) * 64), c.lds_bytes, s, p); \
-        else hipLaunchKernelGGL((conv_v5_kernel<bm, bn, wm, wn, prof, 2>), grid, dim3((wm) * (wn) * 64), c.lds_bytes, s, p); \
-        break;
-        MDHIP_CONV5_CFGS(X)
-#undef X
-#define X(id, bm, bn, wm, wn, prof)                                                               \
-    case id:                                                                                    \
-        hipLaunchKernelGGL((conv_v5_kernel<bm, bn, wm, wn, prof>), grid, dim3((wm) * (wn) * 64), c.lds_bytes, s, p); \
-        break;
-        MDHIP_CONV5_PROF(X)
-#undef X
-    }
-    return hipGetLastError();
+    const dim3 grid = conv_tile_grid(p, g_cfgs5[cfg]);
+    return conv_launch_inst(conv5_pick(cfg, a), grid, p, s);
 }
 }  // namespace
 
-MDHIP_CONV_FAMILY(conv_v5, CONV_V5_RUN, g_cfgs5, kNumMain5, kNumProf5, false, false, false, conv5_supports, conv5_launch, conv5_init, nullptr)
+MDHIP_CONV_FAMILY(conv_v5, CONV_V5_RUN, g_cfgs5, kNumMain5, kNumProf5, false, false, false, conv5_supports, conv5_launch, conv5_insts)
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

@@ -31,22 +31,12 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "mdhip_internal.h"
+#include "conv_device.h"
 
 namespace mdhip {
 namespace MDHIP_ST {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) char lds_char;
-
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;
-[[maybe_unused]] constexpr int kNumRecords = 0x7fffffff;
-
-__device__ __forceinline__ float silu_f32(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-}
 
 constexpr int kPixB = 160;                                     // bytes per pixel (80 channels)
 constexpr int c80_run_bytes(int bm) { return ((bm + 2) * kPixB + 1023) & ~1023; }
@@ -58,9 +48,6 @@ constexpr int c80f_lds_bytes(int bm, int wm) { return c80_lds_bytes(bm, wm) + 80
 constexpr int c80_blocks(int bm, int wm) { return 163840 / c80_lds_bytes(bm, wm) >= 2 && wm == 1 ? 2 : 1; }
 
 }  // namespace
-
-#define MDHIP_DMA16(rsrc, lptr, voff, soff) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (lptr), 16, (voff), (soff), 0, 0)
 
 // ConvArgs as set by the launcher: tiles_n = column strips per image row, tiles_per_xcd = row segments per strip,
 // m_streams = rows per segment, tiles_m = units = images x segments x strips
@@ -157,10 +144,10 @@ conv_c80_kernel(const ConvArgs p) {
         const int sg = t2 % segs, b = t2 / segs;
         x0 = xs * BM;
         const int y_lo = sg * seg_rows, y_hi = min(y_lo + seg_rows, p.H);
-        in_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + (size_t)b * p.HoWo * p.ld_in), 0, img_in_bytes, 0x00020000);
-        out_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)p.out + (size_t)b * img_out_bytes), 0, img_out_bytes, 0x00020000);
+        in_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + (size_t)b * p.HoWo * p.ld_in), 0, img_in_bytes, kRsrcFlags);
+        out_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)p.out + (size_t)b * img_out_bytes), 0, img_out_bytes, kRsrcFlags);
         if (p.res)
-            res_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.res + (size_t)b * p.HoWo * p.ld_res), 0, img_res_bytes, 0x00020000);
+            res_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.res + (size_t)b * p.HoWo * p.ld_res), 0, img_res_bytes, kRsrcFlags);
         // every wave is past its fragment reads of the previous unit before the ring is refilled
         if (!first) __builtin_amdgcn_s_barrier();
         issue_row(y_lo - 1);
@@ -175,7 +162,6 @@ conv_c80_kernel(const ConvArgs p) {
             __builtin_amdgcn_s_barrier();
             if (y + 1 < y_hi) issue_row(y + 2);                               // into the slot row y - 2 has left
             // residual of this tile (8 bytes per lane and fragment row), long before the epilogue needs it
-            typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
             u32x2 rres[FM];
             if (p.res) {
 #pragma unroll
@@ -380,10 +366,10 @@ conv_c80f_kernel(const ConvArgs p) {
         const int sg = t2 % segs, b = t2 / segs;
         x0 = xs * BM;
         const int y_lo = sg * seg_rows, y_hi = min(y_lo + seg_rows, p.H);
-        in_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + (size_t)b * p.HoWo * p.ld_in), 0, img_in_bytes, 0x00020000);
-        out_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)p.out + (size_t)b * img_out_bytes), 0, img_out_bytes, 0x00020000);
+        in_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + (size_t)b * p.HoWo * p.ld_in), 0, img_in_bytes, kRsrcFlags);
+        out_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)p.out + (size_t)b * img_out_bytes), 0, img_out_bytes, kRsrcFlags);
         if (p.res)
-            res_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.res + (size_t)b * p.HoWo * p.ld_res), 0, img_res_bytes, 0x00020000);
+            res_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.res + (size_t)b * p.HoWo * p.ld_res), 0, img_res_bytes, kRsrcFlags);
         // ring slot of T row iy: (iy - y_lo + 1) % 3.  The unit's first three T rows: staged and converted one by one
         // (the previous unit's fragment reads are over: barrier)
         for (int k = 0; k < 3; ++k) {
@@ -400,7 +386,6 @@ conv_c80f_kernel(const ConvArgs p) {
         const int xw = x0 + wm * (BM / WM) + m15;
         int s0 = 0;                                                             // ring slot of T row y - 1
         for (int y = y_lo; y < y_hi; ++y) {
-            typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
             u32x2 rres[FM];
             if (p.res) {
 #pragma unroll
@@ -664,12 +649,12 @@ conv_c80d_kernel(const ConvArgs p) {
         const int sg = t2 % segs, b = t2 / segs;
         x0 = xs * BM;
         const int y_lo = sg * seg_rows, y_hi = min(y_lo + seg_rows, p.H);
-        in_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + (size_t)b * p.HoWo * p.ld_in), 0, img_in_bytes, 0x00020000);
-        out_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)p.out + (size_t)b * img_out_bytes), 0, img_out_bytes, 0x00020000);
+        in_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + (size_t)b * p.HoWo * p.ld_in), 0, img_in_bytes, kRsrcFlags);
+        out_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)p.out + (size_t)b * img_out_bytes), 0, img_out_bytes, kRsrcFlags);
         // (no residual: an empty descriptor -- the loads below are issued either way and return zeros: a branch around them inside
         // the unrolled step loop made the compiler duplicate the rest of the loop and keep the fragment buffers in scratch)
         res_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.res ? p.res + (size_t)b * p.HoWo * p.ld_res : p.in), 0,
-                                                     p.res ? img_res_bytes : 0, 0x00020000);
+                                                     p.res ? img_res_bytes : 0, kRsrcFlags);
         // ---- the unit's first RW + 2 T rows (y_lo - 1 .. y_lo + RW): RW staged and converted, then two more; ring slot of
         //      T row q of the unit: (q - y_lo + 1) mod NRING ----------------------------------------------------------------
         if (first) {                                                              // (the zeroing above is complete in every wave)
@@ -698,7 +683,6 @@ conv_c80d_kernel(const ConvArgs p) {
         int s0 = 0;                                                               // ring slot of T row y - 1
         stamp(5);
         for (int y = y_lo; y < y_hi; y += RW) {
-            typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
             u32x2 rres[RW][FMW];
             ++n_tiles;
             // The loop runs T row by T row: step st < NS1 = (T row qi, tap shift s, k half kk) of the 64-channel group (pass 1),
@@ -859,41 +843,41 @@ conv_c80d_kernel(const ConvArgs p) {
     X(1, 128, 2)
 // id 2: the four-row fused bottleneck (conv_c80d_kernel); as a plain 3x3 (fusion off) it launches id 0's strip kernel -- same bits
 constexpr int kCfgR4 = 2;
+// its developer variants (phase stamps; run only with ConvArgs::dbg set: tools/convbench), ids kCfgR4 + 1 + k: k, PROF, NB, RL
+#define MDHIP_C80D_VARIANTS(X) X(0, 1, 2, 4) X(1, 1, 2, 3) X(2, 1, 2, 5) X(3, 1, 3, 3) X(4, 1, 4, 3)
 
 static const ConvCfg g_cfgs5c[] = {
 #define X(id, bm, wm) {bm, 80, (wm) * 5 * 64, (size_t)c80_lds_bytes(bm, wm), c80_blocks(bm, wm), "v5:strip" #bm "x80/" #wm "x5"},
     MDHIP_CONV5C_CFGS(X)
 #undef X
     {kD_BM, 80, 640, (size_t)kD_LDS, 1, "v5:strip64x80/2x5/r4"},
-    // (phase stamps; run only with ConvArgs::dbg set: tools/convbench)
-    {kD_BM, 80, 640, (size_t)kD_LDS, 1, "dev:strip64x80/2x5/r4/nb2rl4"},
-    {kD_BM, 80, 640, (size_t)kD_LDS, 1, "dev:strip64x80/2x5/r4/nb2rl3"},
-    {kD_BM, 80, 640, (size_t)kD_LDS, 1, "dev:strip64x80/2x5/r4/nb2rl5"},
-    {kD_BM, 80, 640, (size_t)kD_LDS, 1, "dev:strip64x80/2x5/r4/nb3rl3"},
-    {kD_BM, 80, 640, (size_t)kD_LDS, 1, "dev:strip64x80/2x5/r4/nb4rl3"},
+#define X(k, prof, nb, rl) {kD_BM, 80, 640, (size_t)kD_LDS, 1, "dev:strip64x80/2x5/r4/nb" #nb "rl" #rl},
+    MDHIP_C80D_VARIANTS(X)
+#undef X
 };
 constexpr int kNumCfgs5c = (int)(sizeof(g_cfgs5c) / sizeof(g_cfgs5c[0]));
 
 namespace {
-hipError_t conv5c_init() {
-    hipError_t e = hipSuccess;
-#define X(id, bm, wm)                                                                            \
-    if (e == hipSuccess)                                                                         \
-        e = hipFuncSetAttribute((const void*)conv_c80_kernel<bm, wm>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)g_cfgs5c[id].lds_bytes);                                       \
-    if (e == hipSuccess)                                                                         \
-        e = hipFuncSetAttribute((const void*)conv_c80f_kernel<bm, wm>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                c80f_lds_bytes(bm, wm));
-
-    MDHIP_CONV5C_CFGS(X)
+// keys: the strip kernel, the fused bottleneck on the same tiles, the four-row fused bottleneck
+enum { C80_STRIP = 0, C80_FUSED, C80_ROWS4 };
+ConvInstTable conv5c_insts() {
+    static const ConvInst t[] = {
+#define X(id, bm, wm)                                                                             \
+    MDHIP_INST(id, C80_STRIP, (wm) * 5 * 64, c80_lds_bytes(bm, wm), conv_c80_kernel<bm, wm>)      \
+    MDHIP_INST(id, C80_FUSED, (wm) * 5 * 64, c80f_lds_bytes(bm, wm), conv_c80f_kernel<bm, wm>)
+        MDHIP_CONV5C_CFGS(X)
 #undef X
-#define MDHIP_C80D_VARIANTS(X) X(0, 1, 2, 4) X(1, 1, 2, 3) X(2, 1, 2, 5) X(3, 1, 3, 3) X(4, 1, 4, 3)
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv_c80d_kernel<0, kD_NB, kD_RL>, hipFuncAttributeMaxDynamicSharedMemorySize, kD_LDS);
-#define X(id, prof, nb, rl) \
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv_c80d_kernel<prof, nb, rl>, hipFuncAttributeMaxDynamicSharedMemorySize, kD_LDS);
-    MDHIP_C80D_VARIANTS(X)
+        MDHIP_INST(kCfgR4, C80_ROWS4, 640, kD_LDS, conv_c80d_kernel<0, kD_NB, kD_RL>)
+#define X(k, prof, nb, rl) MDHIP_INST(kCfgR4 + 1 + k, C80_ROWS4, 640, kD_LDS, conv_c80d_kernel<prof, nb, rl>)
+        MDHIP_C80D_VARIANTS(X)
 #undef X
-    return e;
+    };
+    return {t, (int)(sizeof(t) / sizeof(t[0]))};
+}
+const ConvInst* conv5c_pick(int cfg, const ConvArgs& a) {
+    if (cfg >= kCfgR4 && a.wgt_pre) return conv_find_inst(conv5c_insts(), cfg, C80_ROWS4);
+    // (the four-row configuration on a plain 3x3, fusion off: configuration 0's strip kernel -- same family, same bits)
+    return conv_find_inst(conv5c_insts(), cfg == kCfgR4 ? 0 : cfg, a.wgt_pre ? C80_FUSED : C80_STRIP);
 }
 
 // (a.wgt_pre != nullptr: the fused bottleneck -- in and out must be different tensors, the 1x1 has 80 input channels)
@@ -908,14 +892,11 @@ bool conv5c_supports(int cfg, const ConvArgs& a) {
 }
 
 hipError_t conv5c_launch(int cfg, const ConvArgs& a, hipStream_t s) {
-    if (!conv5c_supports(cfg, a)) return hipErrorInvalidValue;
-    const int dev = cfg > kCfgR4 ? cfg - kCfgR4 - 1 : -1;
-    if (dev >= 0) cfg = kCfgR4;
-    if (cfg == kCfgR4 && !a.wgt_pre) cfg = 0;                   // (not fused: the strip kernel, same family)
-    const ConvCfg& c = g_cfgs5c[cfg];
+    const ConvInst* inst = conv5c_supports(cfg, a) ? conv5c_pick(cfg, a) : nullptr;
+    if (!inst) return hipErrorInvalidValue;
     ConvArgs p = a;
     const int n_img = a.M / a.HoWo;
-    if (cfg == kCfgR4) {
+    if (inst->key == C80_ROWS4) {
         // units = (image, row segment, 64-pixel column strip); rows per segment: the multiple of four that minimises
         // (units per workgroup, rounded up) x (rows + the unit's start-up, ~ 3 rows' worth)
         const int strips = (a.W + kD_BM - 1) / kD_BM;
@@ -932,14 +913,9 @@ hipError_t conv5c_launch(int cfg, const ConvArgs& a, hipStream_t s) {
         p.tiles_m = n_img * p.tiles_per_xcd * strips;
         const int slots = std::max(1, std::min(32, (p.tiles_m + 7) / 8));
         const dim3 grid_d((unsigned)(8 * slots));
-        switch (dev) {
-#define X(id, prof, nb, rl) case id: hipLaunchKernelGGL((conv_c80d_kernel<prof, nb, rl>), grid_d, dim3(640), kD_LDS, s, p); break;
-            MDHIP_C80D_VARIANTS(X)
-#undef X
-            default: hipLaunchKernelGGL((conv_c80d_kernel<0, kD_NB, kD_RL>), grid_d, dim3(640), kD_LDS, s, p); break;
-        }
-        return hipGetLastError();
+        return conv_launch_inst(inst, grid_d, p, s);
     }
+    const ConvCfg& c = g_cfgs5c[inst->local];
     const int strips = (a.W + c.bm - 1) / c.bm;
     const int wgs = 256 * c.blocks_per_cu;
     // rows per segment: ~4 units per workgroup when the batch allows it (the first tile of a unit waits for three row
@@ -953,20 +929,11 @@ hipError_t conv5c_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     p.tiles_m = n_img * segs * strips;
     const int slots = std::max(1, std::min(32 * c.blocks_per_cu, (p.tiles_m + 7) / 8));
     const dim3 grid((unsigned)(8 * slots));
-    switch (cfg) {
-#define X(id, bm, wm)                                                                             \
-    case id:                                                                                      \
-        if (a.wgt_pre) hipLaunchKernelGGL((conv_c80f_kernel<bm, wm>), grid, dim3((wm) * 5 * 64), c80f_lds_bytes(bm, wm), s, p); \
-        else hipLaunchKernelGGL((conv_c80_kernel<bm, wm>), grid, dim3((wm) * 5 * 64), c.lds_bytes, s, p); \
-        break;
-        MDHIP_CONV5C_CFGS(X)
-#undef X
-    }
-    return hipGetLastError();
+    return conv_launch_inst(inst, grid, p, s);
 }
 }  // namespace
 
-MDHIP_CONV_FAMILY(conv_v5c, CONV_V5_STRIP, g_cfgs5c, kNumCfgs5c, 0, false, false, false, conv5c_supports, conv5c_launch, conv5c_init, nullptr)
+MDHIP_CONV_FAMILY(conv_v5c, CONV_V5_STRIP, g_cfgs5c, kNumCfgs5c, 0, false, false, false, conv5c_supports, conv5c_launch, conv5c_insts)
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

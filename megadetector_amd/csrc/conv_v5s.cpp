@@ -24,22 +24,12 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "mdhip_internal.h"
+#include "conv_device.h"
 
 namespace mdhip {
 namespace MDHIP_ST {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) char lds_char;
-
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;
-[[maybe_unused]] constexpr int kNumRecords = 0x7fffffff;
-
-__device__ __forceinline__ float silu_f32(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-}
 
 constexpr int v5s_run_pieces(int bm) { return (bm + 2 + 7) / 8; }
 constexpr int v5s_stage_bytes(int bm, int bn, int nw) {
@@ -58,9 +48,6 @@ constexpr int v5s_waves_per_simd(int bm, int bn, int nw, int ns) {
 }
 
 }  // namespace
-
-#define MDHIP_DMA16(rsrc, lptr, voff, soff) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (lptr), 16, (voff), (soff), 0, 0)
 
 template <int BM, int BN, int WM, int WN, int NS, int PD>
 __global__ void __launch_bounds__(WM * WN * 64, v5s_waves_per_simd(BM, BN, WM * WN, NS))
@@ -119,7 +106,7 @@ conv_v5s_kernel(const ConvArgs p) {
     const int lr = lane >> 3;
     const int jj = (lane & 7) ^ lr;
     const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.wgt4 + (size_t)n0 * p.k_pad4), 0, kNumRecords, 0x00020000);
+        (void*)(p.wgt4 + (size_t)n0 * p.k_pad4), 0, kNumRecords, kRsrcFlags);
     unsigned b_off[B_PER];
 #pragma unroll
     for (int i = 0; i < B_PER; ++i) {
@@ -139,7 +126,7 @@ conv_v5s_kernel(const ConvArgs p) {
     unsigned lg_soff = 0;
     auto run_tile = [&](int t) __attribute__((always_inline)) {
         const long long origin = (long long)t * BM - p.W - 1;          // first pixel of the r = 0 run
-        a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + origin * p.ld_in), 0, kNumRecords, 0x00020000);
+        a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + origin * p.ld_in), 0, kNumRecords, kRsrcFlags);
     };
     auto run_setup = [&]() __attribute__((always_inline)) {
         lg_first = lg_tile * BM + (lg_r - 1) * p.W - 1;
@@ -281,14 +268,9 @@ conv_v5s_kernel(const ConvArgs p) {
             uint16_t* orow = (uint16_t*)p.out + (size_t)m * p.ld_out;
 #pragma unroll
             for (int j = 0; j + 1 < FN; j += 2) {
-                unsigned a0 = st_pack2(v[j][0], v[j][1]), a1 = st_pack2(v[j][2], v[j][3]);
-                unsigned b0 = st_pack2(v[j + 1][0], v[j + 1][1]), b1 = st_pack2(v[j + 1][2], v[j + 1][3]);
-                auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-                auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-                auto t0 = __builtin_amdgcn_permlane16_swap(s0[0], s0[1], false, false);
-                auto t1 = __builtin_amdgcn_permlane16_swap(s1[0], s1[1], false, false);
+                const u32x4 d = conv_pack_pair(v[j], v[j + 1]);
                 const int n = n0 + wn * TN + j * 16 + q4 * 8;
-                if (m < p.M && n < p.N) *(uint4*)(orow + n) = make_uint4(t0[0], t1[0], t0[1], t1[1]);
+                if (m < p.M && n < p.N) *(uint4*)(orow + n) = make_uint4(d[0], d[1], d[2], d[3]);
             }
             if (FN & 1) {
                 const int j = FN - 1;
@@ -381,15 +363,13 @@ static const ConvCfg g_cfgs5s[] = {
 constexpr int kNumCfgs5s = (int)(sizeof(g_cfgs5s) / sizeof(g_cfgs5s[0]));
 
 namespace {
-hipError_t conv5s_init() {
-    hipError_t e = hipSuccess;
-#define X(id, bm, bn, wm, wn, ns, pd)                                                          \
-    if (e == hipSuccess)                                                                       \
-        e = hipFuncSetAttribute((const void*)conv_v5s_kernel<bm, bn, wm, wn, ns, pd>,             \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_cfgs5s[id].lds_bytes);
-    MDHIP_CONV5S_CFGS(X)
+ConvInstTable conv5s_insts() {
+    static const ConvInst t[] = {
+#define X(id, bm, bn, wm, wn, ns, pd) MDHIP_INST(id, 0, (wm) * (wn) * 64, v5s_lds_bytes(bm, bn, (wm) * (wn), ns), conv_v5s_kernel<bm, bn, wm, wn, ns, pd>)
+        MDHIP_CONV5S_CFGS(X)
 #undef X
-    return e;
+    };
+    return {t, (int)(sizeof(t) / sizeof(t[0]))};
 }
 
 bool conv5s_supports(int cfg, const ConvArgs& a) {
@@ -398,22 +378,13 @@ bool conv5s_supports(int cfg, const ConvArgs& a) {
 
 hipError_t conv5s_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     if (!conv5s_supports(cfg, a)) return hipErrorInvalidValue;
-    const ConvCfg& c = g_cfgs5s[cfg];
     ConvArgs p = a;
-    const dim3 grid = conv_tile_grid(p, c);
-    switch (cfg) {
-#define X(id, bm, bn, wm, wn, ns, pd)                                                              \
-    case id:                                                                                    \
-        hipLaunchKernelGGL((conv_v5s_kernel<bm, bn, wm, wn, ns, pd>), grid, dim3((wm) * (wn) * 64), c.lds_bytes, s, p); \
-        break;
-        MDHIP_CONV5S_CFGS(X)
-#undef X
-    }
-    return hipGetLastError();
+    const dim3 grid = conv_tile_grid(p, g_cfgs5s[cfg]);
+    return conv_launch_inst(conv_find_inst(conv5s_insts(), cfg, 0), grid, p, s);
 }
 }  // namespace
 
-MDHIP_CONV_FAMILY(conv_v5s, CONV_V5_SMALL, g_cfgs5s, kNumCfgs5s, 0, false, false, false, conv5s_supports, conv5s_launch, conv5s_init, nullptr)
+MDHIP_CONV_FAMILY(conv_v5s, CONV_V5_SMALL, g_cfgs5s, kNumCfgs5s, 0, false, false, false, conv5s_supports, conv5s_launch, conv5s_insts)
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

@@ -17,22 +17,12 @@
 
 #include <algorithm>
 
-#include "mdhip_internal.h"
+#include "conv_device.h"
 
 namespace mdhip {
 namespace MDHIP_ST {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) char lds_char;
-
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;
-[[maybe_unused]] constexpr int kNumRecords = 0x7fffffff;
-
-__device__ __forceinline__ float silu_f32(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-}
 
 [[maybe_unused]] constexpr int kBM = 128;                    // output pixels per tile (one image row segment)
 constexpr int kNW = 4;                      // waves; each owns 32 pixels x 80 channels
@@ -44,9 +34,6 @@ constexpr int kBiasOff = 2 * kBufBytes;
 constexpr int kStemLds = kBiasOff + 80 * 4;
 
 }  // namespace
-
-#define MDHIP_DMA16(rsrc, lptr, voff, soff) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (lptr), 16, (voff), (soff), 0, 0)
 
 __global__ void __launch_bounds__(kNW * 64, 2)
 conv_stem_kernel(const ConvArgs p) {
@@ -96,7 +83,7 @@ conv_stem_kernel(const ConvArgs p) {
         const int y = yb % p.H, b = yb / p.H;
         const int x0 = xt * kBM;
         const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(p.in + (size_t)b * p.HoWo * p.ld_in), 0, kNumRecords, 0x00020000);
+            (void*)(p.in + (size_t)b * p.HoWo * p.ld_in), 0, kNumRecords, kRsrcFlags);
 #pragma unroll
         for (int k = 0; k < (3 * kRunPieces + kNW - 1) / kNW; ++k) {
             const int pc = k * kNW + wave;
@@ -147,7 +134,7 @@ conv_stem_kernel(const ConvArgs p) {
         const int yb = tile / tiles_x;
         const int y_img = yb % p.H, b_img = yb / p.H;
         const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)((char*)p.out + (size_t)b_img * img_out_bytes), 0, img_out_bytes, 0x00020000);
+            (void*)((char*)p.out + (size_t)b_img * img_out_bytes), 0, img_out_bytes, kRsrcFlags);
         const int x0 = xt * kBM + wave * 32 + m15;
 #pragma unroll
         for (int i = 0; i < kFM; ++i) {
@@ -164,19 +151,11 @@ conv_stem_kernel(const ConvArgs p) {
             }
 #pragma unroll
             for (int j = 0; j + 1 < kFN; j += 2) {
-                unsigned a0 = st_pack2(v[j][0], v[j][1]), a1 = st_pack2(v[j][2], v[j][3]);
-                unsigned b0 = st_pack2(v[j + 1][0], v[j + 1][1]), b1 = st_pack2(v[j + 1][2], v[j + 1][3]);
-                auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-                auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-                auto t0 = __builtin_amdgcn_permlane16_swap(s0[0], s0[1], false, false);
-                auto t1 = __builtin_amdgcn_permlane16_swap(s1[0], s1[1], false, false);
-                typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-                const u32x4 d = {t0[0], t1[0], t0[1], t1[1]};
+                const u32x4 d = conv_pack_pair(v[j], v[j + 1]);
                 __builtin_amdgcn_raw_buffer_store_b128(d, o_rsrc, ok ? row_off + (unsigned)((j * 16 + q4 * 8) * 2) : kOOB, 0, 0);
             }
             {
                 constexpr int j = kFN - 1;
-                typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
                 const u32x2 d = {st_pack2(v[j][0], v[j][1]), st_pack2(v[j][2], v[j][3])};
                 __builtin_amdgcn_raw_buffer_store_b64(d, o_rsrc, ok ? row_off + (unsigned)((j * 16 + q4 * 4) * 2) : kOOB, 0, 0);
             }
@@ -192,8 +171,9 @@ conv_stem_kernel(const ConvArgs p) {
 [[maybe_unused]] static const ConvCfg g_cfg6 = {kBM, 80, kNW * 64, (size_t)kStemLds, 2, "stem:row128x80/4x1"};
 
 namespace {
-hipError_t conv6_init() {
-    return hipFuncSetAttribute((const void*)conv_stem_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kStemLds);
+ConvInstTable conv6_insts() {
+    static const ConvInst t[] = {MDHIP_INST(0, 0, kNW * 64, kStemLds, conv_stem_kernel)};
+    return {t, 1};
 }
 
 bool conv6_supports(int cfg, const ConvArgs& a) {
@@ -210,12 +190,11 @@ hipError_t conv6_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     const int tiles_x = (a.W + kBM - 1) / kBM;
     const long long total = (long long)(a.M / a.HoWo) * a.H * tiles_x;
     const int slots = (int)std::max(1LL, std::min<long long>(64, (total + 7) / 8));      // 2 workgroups on each of 32 CUs per XCD
-    hipLaunchKernelGGL(conv_stem_kernel, dim3((unsigned)(8 * slots)), dim3(kNW * 64), kStemLds, s, a);
-    return hipGetLastError();
+    return conv_launch_inst(conv_find_inst(conv6_insts(), cfg, 0), dim3((unsigned)(8 * slots)), a, s);
 }
 }  // namespace
 
-MDHIP_CONV_FAMILY(conv_v6, CONV_STEM, &g_cfg6, 1, 0, true, false, false, conv6_supports, conv6_launch, conv6_init, nullptr)   // same K order as the implicit GEMM
+MDHIP_CONV_FAMILY(conv_v6, CONV_STEM, &g_cfg6, 1, 0, true, false, false, conv6_supports, conv6_launch, conv6_insts)   // same K order as the implicit GEMM
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

@@ -37,19 +37,12 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "mdhip_internal.h"
+#include "conv_device.h"
 
 namespace mdhip {
 namespace MDHIP_ST {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) char lds_char;
-typedef mdhip_f32x2 f32x2;
-
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;
-[[maybe_unused]] constexpr int kNumRecords = 0x7fffffff;
 
 constexpr int kBM7 = 320, kBN7 = 160, kWM7 = 4, kWN7 = 2, kNW7 = kWM7 * kWN7;
 constexpr int kSub7 = kBM7 * 128;                                   // one sub-buffer: 320 entries x 128 bytes
@@ -59,9 +52,6 @@ constexpr int kLds7 = 2 * kSub7 + 2 * kStage7 + kZero7;             // 123 904 b
 constexpr int kAlExtra7 = 4 * 2048;                                 // aligned mode: zero rows at ZERO_OFF + i * 2048, i = 1..4
 
 }  // namespace
-
-#define MDHIP_DMA16(rsrc, lptr, voff, soff) \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (lptr), 16, (voff), (soff), 0, 0)
 
 // TAIL: 0 = the channel count is a multiple of 64 (no partly full last group: its tests are compiled out), 1 = it is not.
 // AL: a wave's 80 output pixels lie inside one output row (Wo a multiple of 80): tap validity from three per-wave flags --
@@ -132,7 +122,7 @@ conv_v7_kernel(const ConvArgs p) {
     const int lr = lane >> 3;
     const int jj = (lane & 7) ^ lr;
     const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.wgt4 + (size_t)n0 * p.k_pad4), 0, kNumRecords, 0x00020000);
+        (void*)(p.wgt4 + (size_t)n0 * p.k_pad4), 0, kNumRecords, kRsrcFlags);
     const unsigned b_off = (unsigned)((wave * 8 + lr) * p.k_pad4 + jj * 8) * 2u;
     const unsigned b_stride = (unsigned)(NW * 8 * p.k_pad4) * 2u;
     int l_base = 0, l_j = 0;                       // the loader's slab: l_base = 9 * group + 3 * (kernel row), l_j = 0 / 1 / 2 -> tap 0 / 2 / 1
@@ -188,7 +178,7 @@ conv_v7_kernel(const ConvArgs p) {
         const int b0 = conv_udiv(m_t, p.HoWo, p.rcp_howo);
         const long long left = (long long)(n_img - b0) * img_bytes;
         lg_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.in + (long long)b0 * img_bytes), 0,
-                                                    (int)(left > 0x7fffff00LL ? 0x7fffff00LL : left), 0x00020000);
+                                                    (int)(left > 0x7fffff00LL ? 0x7fffff00LL : left), kRsrcFlags);
         const int m_w = lg_tile * BM + 40 * wave;                          // first output pixel of the wave's block (wave-uniform)
         lg_ok = m_w < p.M;
         const int b = conv_udiv(min(m_w, p.M - 1), p.HoWo, p.rcp_howo);
@@ -325,14 +315,12 @@ conv_v7_kernel(const ConvArgs p) {
         asm volatile("" : "+v"(lane_e));
         const int lp = lane_e & 15;
         const int lq = lane_e >> 4;
-        typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-        typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
         const int npair0 = n0 + wn * TN + lq * 8;
         const int nlast = n0 + wn * TN + (FN - 1) * 16 + lq * 4;
         const long long rows_left = (long long)p.M - (long long)tile_m * BM;
         const int ml = wm * TM + lp;
         const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)((uint16_t*)p.out + (size_t)tile_m * BM * p.ld_out), 0, (int)min(rows_left * p.ld_out * 2, 0x7fffffffLL), 0x00020000);
+            (void*)((uint16_t*)p.out + (size_t)tile_m * BM * p.ld_out), 0, (int)min(rows_left * p.ld_out * 2, 0x7fffffffLL), kRsrcFlags);
         const unsigned o_pair = ((unsigned)ml * (unsigned)p.ld_out + (unsigned)npair0) * 2u;
         const unsigned o_last = ((unsigned)ml * (unsigned)p.ld_out + (unsigned)nlast) * 2u;
         const unsigned o_step = 16u * (unsigned)p.ld_out * 2u;
@@ -356,14 +344,9 @@ conv_v7_kernel(const ConvArgs p) {
             }
 #pragma unroll
             for (int j = 0; j + 1 < FN; j += 2) {
-                unsigned a0 = st_pack2(v[j][0], v[j][1]), a1 = st_pack2(v[j][2], v[j][3]);
-                unsigned b0 = st_pack2(v[j + 1][0], v[j + 1][1]), b1 = st_pack2(v[j + 1][2], v[j + 1][3]);
-                auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-                auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-                auto t0 = __builtin_amdgcn_permlane16_swap(s0[0], s0[1], false, false);
-                auto t1 = __builtin_amdgcn_permlane16_swap(s1[0], s1[1], false, false);
+                const u32x4 d = conv_pack_pair(v[j], v[j + 1]);
                 const unsigned off = o_pair + (unsigned)i * o_step + (unsigned)(j * 32);
-                __builtin_amdgcn_raw_buffer_store_b128(u32x4{t0[0], t1[0], t0[1], t1[1]}, o_rsrc, (int)off, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(d, o_rsrc, (int)off, 0, 0);
             }
             {
                 constexpr int j = FN - 1;
@@ -409,7 +392,6 @@ conv_v7_kernel(const ConvArgs p) {
     for (int j = 0; j < FN; ++j) wa[j] = read_w(0, 0, j);
 
     int c_r = 0, c_cg = 0, c_tile = first_tile, step = 0;
-#define MDHIP_FENCE() __builtin_amdgcn_sched_barrier(0)
     // a last channel group of at most 32 channels has nothing in k 32..63: its second-half MFMAs are skipped
     const bool tail_short = TAIL != 0 && (p.C8 & 7) != 0 && (p.C8 & 7) <= 4;
     constexpr int DMA_MAX = B_PER + A_PER, DMA_PER_G = (DMA_MAX + FN - 1) / FN;
@@ -491,7 +473,6 @@ conv_v7_kernel(const ConvArgs p) {
             c_tile += tile_step;
         }
     }
-#undef MDHIP_FENCE
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
@@ -501,12 +482,21 @@ conv_v7_kernel(const ConvArgs p) {
 [[maybe_unused]] static const ConvCfg g_cfg7 = {kBM7, kBN7, kNW7 * 64, (size_t)kLds7, 1, "v7:s2run320x160/4x2"};
 
 namespace {
-hipError_t conv7_init() {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_v7_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds7);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv_v7_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds7);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv_v7_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds7 + kAlExtra7);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv_v7_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds7 + kAlExtra7);
-    return e;
+// key = TAIL + 2 * AL
+ConvInstTable conv7_insts() {
+    static const ConvInst t[] = {
+        MDHIP_INST(0, 0, kNW7 * 64, kLds7, conv_v7_kernel<0, false>)
+        MDHIP_INST(0, 1, kNW7 * 64, kLds7, conv_v7_kernel<1, false>)
+        MDHIP_INST(0, 2, kNW7 * 64, kLds7 + kAlExtra7, conv_v7_kernel<0, true>)
+        MDHIP_INST(0, 3, kNW7 * 64, kLds7 + kAlExtra7, conv_v7_kernel<1, true>)
+    };
+    return {t, (int)(sizeof(t) / sizeof(t[0]))};
+}
+// same results from every instantiation: what the last channel group looks like, and whether a wave's 80 output pixels lie
+// inside one output row
+const ConvInst* conv7_pick(int cfg, const ConvArgs& a) {
+    const bool tail = (a.C8 & 7) != 0, aligned = (a.Wo % 80) == 0 && a.dev_param != 77;
+    return conv_find_inst(conv7_insts(), cfg, (tail ? 1 : 0) + (aligned ? 2 : 0));
 }
 
 bool conv7_supports(int cfg, const ConvArgs& a) {
@@ -530,21 +520,11 @@ hipError_t conv7_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     p.tiles_per_xcd = (p.tiles_m + 7) / 8;
     p.m_streams = std::max(1, std::min(p.tiles_per_xcd, 32 / p.tiles_n));
     const dim3 grid((unsigned)(8 * p.tiles_n * p.m_streams));
-    // same results from every instantiation: what the last channel group looks like, and whether a wave's 80 output pixels lie
-    // inside one output row
-    const bool tail = (a.C8 & 7) != 0, aligned = (a.Wo % 80) == 0 && a.dev_param != 77;
-    if (aligned) {
-        if (tail) hipLaunchKernelGGL((conv_v7_kernel<1, true>), grid, dim3(kNW7 * 64), kLds7 + kAlExtra7, s, p);
-        else hipLaunchKernelGGL((conv_v7_kernel<0, true>), grid, dim3(kNW7 * 64), kLds7 + kAlExtra7, s, p);
-    } else {
-        if (tail) hipLaunchKernelGGL((conv_v7_kernel<1, false>), grid, dim3(kNW7 * 64), kLds7, s, p);
-        else hipLaunchKernelGGL((conv_v7_kernel<0, false>), grid, dim3(kNW7 * 64), kLds7, s, p);
-    }
-    return hipGetLastError();
+    return conv_launch_inst(conv7_pick(cfg, a), grid, p, s);
 }
 }  // namespace
 
-MDHIP_CONV_FAMILY(conv_v7, CONV_V7, &g_cfg7, 1, 0, false, false, false, conv7_supports, conv7_launch, conv7_init, nullptr)   // a K order of its own
+MDHIP_CONV_FAMILY(conv_v7, CONV_V7, &g_cfg7, 1, 0, false, false, false, conv7_supports, conv7_launch, conv7_insts)   // a K order of its own
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

@@ -243,15 +243,15 @@ int level_offset(const mdhip_ctx* ctx, int level, int h, int w, int per_cell) {
     return off;
 }
 
-// Detect decode in this conv's epilogue (mdhip_decode_store): the plain forward of a head with 8 outputs per anchor, on the
-// two kernel families that take 1x1 / fp32-output ops (pointwise with whole 64-channel slabs: what the decoding
-// instantiations of conv_v2.cpp take); the augmented forward (anchors kept / de-scaled / flipped per pass) and every other
-// head keep the separate decode launch.  Settles the conv's record and the one of its decode op, the next op.
+// Detect decode in this conv's epilogue (mdhip_decode_store): the plain forward of a head with 8 outputs per anchor, on a
+// tile that takes the op as a decoding one (the two kernel families that take 1x1 / fp32-output ops have such
+// instantiations); the augmented forward (anchors kept / de-scaled / flipped per pass) and every other head keep the
+// separate decode launch.  Settles the conv's record and the one of its decode op, the next op.
 void resolve_decode(const mdhip_ctx* ctx, Resolved& r, size_t conv) {
     Launch& L = r.ops[conv];
     const Op& dec = ctx->ops[conv + 1];
     L.decodes = ctx->fuse_decode && !ctx->fuse_suspended && ctx->no == 8 && plain_pass(ctx->cur_tta) && !ctx->calibrating &&
-                conv_api(ctx).cfg_decodes(L.cfg) && (conv_api(ctx).family(L.cfg) == CONV_IGEMM || (L.a.C8 & 7) == 0);
+                conv_api(ctx).supports_decoding(L.cfg, L.a);
     L.a.dec_anchors = (const float*)(ctx->warena + ctx->anchors_off) + dec.level * ctx->na * 2;
     L.a.dec_stride = ctx->strides[dec.level];
     L.a.dec_level_off = level_offset(ctx, dec.level, r.h, r.w, ctx->na);

@@ -86,57 +86,14 @@ __host__ __device__ inline uint16_t f32_to_st(float f, int f16) { return f16 ? f
 __host__ __device__ inline float st_to_f32(uint16_t h, int f16) { return f16 ? f16_to_f32(h) : bf16_to_f32(h); }
 
 // The convolution translation units are compiled twice: as is (bf16, namespace mdhip::st_bf16) and with
-// -DMDHIP_ST_F16 (fp16, namespace mdhip::st_f16).  Inside them MDHIP_ST is that namespace, frag8_t the MFMA
-// operand type, MDHIP_MFMA the 16x16x32 instruction, st_pack2 / st_unpack the epilogue conversions.
+// -DMDHIP_ST_F16 (fp16, namespace mdhip::st_f16).  Inside them MDHIP_ST is that namespace; conv_device.h holds what
+// their kernels share.
 #if defined(MDHIP_ST_F16)
 #define MDHIP_ST st_f16
 #define MDHIP_ST_LABEL "fp16"
 #else
 #define MDHIP_ST st_bf16
 #define MDHIP_ST_LABEL "bf16"
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
-#if defined(MDHIP_ST_F16)
-typedef _Float16 frag8_t __attribute__((ext_vector_type(8)));
-#define MDHIP_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-__device__ __forceinline__ uint32_t st_pack2(float a, float b) {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    const f2 v = {a, b};
-    const h2 r = __builtin_convertvector(v, h2);
-    return *(const uint32_t*)&r;
-}
-__device__ __forceinline__ float st_unpack(uint16_t h) { return f16_to_f32(h); }
-#else
-typedef short frag8_t __attribute__((ext_vector_type(8)));
-#define MDHIP_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
-__device__ __forceinline__ uint32_t st_pack2(float a, float b) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    const f2 v = {a, b};
-    const b2 r = __builtin_convertvector(v, b2);
-    return *(const uint32_t*)&r;
-}
-__device__ __forceinline__ float st_unpack(uint16_t h) { return bf16_to_f32(h); }
-#endif
-// four fp32 values -> four e4m3 bytes (RNE, saturating at +-448): the out_f8 epilogue of the 16-bit kernels
-__device__ __forceinline__ uint32_t pack_e4m3x4(float a, float b, float c, float d, float qscale) {
-    a = __builtin_fminf(__builtin_fmaxf(a * qscale, -448.0f), 448.0f);
-    b = __builtin_fminf(__builtin_fmaxf(b * qscale, -448.0f), 448.0f);
-    c = __builtin_fminf(__builtin_fmaxf(c * qscale, -448.0f), 448.0f);
-    d = __builtin_fminf(__builtin_fmaxf(d * qscale, -448.0f), 448.0f);
-    int r = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-    r = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, r, true);
-    return (uint32_t)r;
-}
-// a fragment that is not read from LDS (ablation variants of the kernels only)
-__device__ __forceinline__ frag8_t frag_dummy(int v) {
-    frag8_t z;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) z[k] = (__typeof__(z[0]))(v + k);
-    asm volatile("" : "+v"(z));
-    return z;
-}
 #endif
 
 // ---------------------------------------------------------------------------------------
@@ -205,35 +162,9 @@ struct ConvArgs {
 inline unsigned conv_rcp32(int d) { return d <= 1 ? 0xffffffffu : (unsigned)(0x100000000ull / (unsigned)d); }
 inline void conv_set_rcp(ConvArgs& p) { p.rcp_howo = conv_rcp32(p.HoWo); p.rcp_wo = conv_rcp32(p.Wo); }
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
-// m / d for 0 <= m < 2^31, d >= 1, rcp = floor(2^32 / d): the estimate mulhi(m, rcp) is the quotient or one below it
-// (m * (2^32 / d - rcp) / 2^32 < 1), one compare fixes it -- 5 instructions instead of the ~30 of a run-time division
-__device__ __forceinline__ int conv_udiv(int m, int d, unsigned rcp) {
-    unsigned q = __umulhi((unsigned)m, rcp);
-    const unsigned r = (unsigned)m - q * (unsigned)d;
-    return (int)(r >= (unsigned)d ? q + 1u : q);
-}
-// SiLU of two values at a time: the same operations and roundings as the scalar  x * rcp(1 + exp(-x))  of every kernel
-// family (x * -log2(e), v_exp_f32, 1 + e, v_rcp_f32, x * r), with the four full-rate ones as packed fp32 instructions.
-// The two transcendentals are quarter rate: for 1x1 convs with K <= 640 the activation is more VALU time than the
-// layer's MFMAs are matrix time, so the epilogues are written around it.  (neg_log2e: -0x1.715476p+0f, passed in so that
-// register-tight kernels can keep it out of the main loop.)
-typedef __attribute__((ext_vector_type(2))) float mdhip_f32x2;
-constexpr float kNegLog2e = -0x1.715476p+0f;
-__device__ __forceinline__ mdhip_f32x2 silu_f32x2(mdhip_f32x2 x, float neg_log2e = kNegLog2e) {
-    const mdhip_f32x2 u = x * mdhip_f32x2{neg_log2e, neg_log2e};
-    const mdhip_f32x2 e = mdhip_f32x2{__builtin_amdgcn_exp2f(u[0]), __builtin_amdgcn_exp2f(u[1])} + mdhip_f32x2{1.0f, 1.0f};
-    return x * mdhip_f32x2{__builtin_amdgcn_rcpf(e[0]), __builtin_amdgcn_rcpf(e[1])};
-}
-// v[0..3] = a[0..3] + b[0..3] (packed), the first half of every epilogue; the activation follows under one uniform branch
-// per pixel row (mdhip_silu4), not as a select per value
-template <typename A, typename B>
-__device__ __forceinline__ void mdhip_bias4(const A& a, const B& b, float (&v)[4]) {
-    const mdhip_f32x2 t0 = mdhip_f32x2{a[0], a[1]} + mdhip_f32x2{b[0], b[1]};
-    const mdhip_f32x2 t1 = mdhip_f32x2{a[2], a[3]} + mdhip_f32x2{b[2], b[3]};
-    v[0] = t0[0]; v[1] = t0[1]; v[2] = t1[0]; v[3] = t1[1];
-}
 // Detect decode (yolov5 Detect.forward, inference): ONE definition for detect_decode_kernel
-// (misc_kernels.cpp) and for the conv epilogues that decode in place -- same statements, no contraction: same bits
+// (misc_kernels.cpp) and for the conv epilogues that decode in place (conv_device.h: mdhip_decode_store) -- same statements,
+// no contraction: same bits
 __device__ __forceinline__ float mdhip_sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ void mdhip_decode_box(float l0, float l1, float l2, float l3, int x, int y, float stride, float aw, float ah,
                                                  float& cx, float& cy, float& bw, float& bh) {
@@ -245,26 +176,6 @@ __device__ __forceinline__ void mdhip_decode_box(float l0, float l1, float l2, f
     const float w2 = s2 * 2.0f, h2 = s3 * 2.0f;
     bw = (w2 * w2) * aw;
     bh = (h2 * h2) * ah;
-}
-// a lane's four consecutive logits (channels n .. n + 3 of output pixel m, n a multiple of 4, 8 outputs per anchor) -> its
-// half of the prediction row of anchor n / 8: the box (n mod 8 == 0) or objectness + classes (n mod 8 == 4)
-__device__ __forceinline__ void mdhip_decode_store(const ConvArgs& p, int m, int n, const float (&v)[4]) {
-#pragma clang fp contract(off)
-    const int b = conv_udiv(m, p.HoWo, p.rcp_howo);
-    const int rem = m - b * p.HoWo;
-    const int y = conv_udiv(rem, p.Wo, p.rcp_wo);
-    const int x = rem - y * p.Wo;
-    const int a = n >> 3;
-    const int idx = p.dec_level_off + (a * p.Ho + y) * p.Wo + x;
-    float* o = p.dec_pred + ((size_t)b * p.dec_n_anchors + idx) * 8 + (n & 4);
-    float4 r;
-    if ((n & 4) == 0) mdhip_decode_box(v[0], v[1], v[2], v[3], x, y, p.dec_stride, p.dec_anchors[a * 2 + 0], p.dec_anchors[a * 2 + 1], r.x, r.y, r.z, r.w);
-    else r = make_float4(mdhip_sigmoid_exact(v[0]), mdhip_sigmoid_exact(v[1]), mdhip_sigmoid_exact(v[2]), mdhip_sigmoid_exact(v[3]));
-    *(float4*)o = r;
-}
-__device__ __forceinline__ void mdhip_silu4(float (&v)[4], float neg_log2e = kNegLog2e) {
-    const mdhip_f32x2 t0 = silu_f32x2(mdhip_f32x2{v[0], v[1]}, neg_log2e), t1 = silu_f32x2(mdhip_f32x2{v[2], v[3]}, neg_log2e);
-    v[0] = t0[0]; v[1] = t0[1]; v[2] = t1[0]; v[3] = t1[1];
 }
 #endif
 
@@ -303,6 +214,34 @@ inline dim3 conv_tile_grid(ConvArgs& p, const ConvCfg& c) {
 //   CONV_F8       : conv_v5's structure on e4m3 operands with the block-scaled K = 128 MFMA (conv_f8.cpp)
 //   CONV_V7       : 3x3 / STRIDE 2 with row-run reuse (odd / even input columns in two sub-buffers; conv_v7.cpp)
 enum ConvFamilyId { CONV_IGEMM = 0, CONV_V2, CONV_V5_RUN, CONV_V5_SMALL, CONV_V5_STRIP, CONV_STEM, CONV_F8, CONV_V7, CONV_NUM_FAMILIES };
+
+// One compiled kernel: configuration `local` of its family in the variant `key`, the family's own code for what its pick()
+// chooses between at run time (conv_v2.cpp: plain / pointwise / upsample read in place ...; conv_v5.cpp: the last channel
+// group x aligned rows).  One key is common to the families, CONV_KEY_DEC: the instantiation that decodes in its epilogue.
+// Block size and LDS belong to the instantiation -- some kernels need more LDS than their configuration's ConvCfg says.
+// A family's table of these (ConvFamily::insts) is the ONE list of the kernels it has: the registry raises the LDS limit
+// of every row, a launch goes through a row, and a configuration decodes when it has a CONV_KEY_DEC row.
+struct ConvInst {
+    const void* fn;
+    int local, key, threads;
+    size_t lds_bytes;
+};
+struct ConvInstTable { const ConvInst* rows; int n; };
+constexpr int CONV_KEY_DEC = 100;
+// a row of a table:  MDHIP_INST(local, key, threads, lds_bytes, kernel<template arguments>)
+#define MDHIP_INST(local, key, threads, lds, ...) {(const void*)(__VA_ARGS__), (local), (key), (threads), (size_t)(lds)},
+inline const ConvInst* conv_find_inst(ConvInstTable t, int local, int key) {
+    for (int i = 0; i < t.n; ++i)
+        if (t.rows[i].local == local && t.rows[i].key == key) return &t.rows[i];
+    return nullptr;
+}
+// every conv launch: the instantiation a family's pick() chose (nullptr: it has none for this op) on the family's own grid
+inline hipError_t conv_launch_inst(const ConvInst* inst, dim3 grid, const ConvArgs& p, hipStream_t s) {
+    if (!inst) return hipErrorInvalidValue;
+    void* args[] = {(void*)&p};
+    return hipLaunchKernel(inst->fn, grid, dim3((unsigned)inst->threads), args, inst->lds_bytes, s);
+}
+
 struct ConvFamily {
     ConvFamilyId id;
     const ConvCfg* cfgs;    // n_cfgs public configurations, then n_dev developer variants (tools/convbench.cpp: launch_dev)
@@ -312,11 +251,11 @@ struct ConvFamily {
     bool f8_out;            // its epilogue can write e4m3 (ConvArgs::out_f8)
     bool (*supports)(int local, const ConvArgs& a);
     hipError_t (*launch)(int local, const ConvArgs& a, hipStream_t s);   // hipSuccess or the launch error
-    hipError_t (*init)();                                                // raises the dynamic-LDS limits (one-off)
-    bool (*decodes)(int local);   // the configuration has an instantiation that decodes in its epilogue; nullptr: none has
+    ConvInstTable (*insts)();
 };
-// MDHIP_CONV_FAMILY(name, id, cfgs, n_cfgs, n_dev, bitwise, f8_in, f8_out, supports, launch, init, decodes) defines a translation
-// unit's family object.  It is host data: the device pass must not emit a copy into the code object
+// MDHIP_CONV_FAMILY(name, id, cfgs, n_cfgs, n_dev, bitwise, f8_in, f8_out, supports, launch, insts) defines a translation
+// unit's family object.  It is host data: the device pass must not emit a copy into the code object (a family's table is a
+// function-local static of its insts() for the same reason: that names -- and so instantiates -- the kernels in both passes)
 #if defined(__HIP_DEVICE_COMPILE__)
 #define MDHIP_CONV_FAMILY(name, ...)
 #else
@@ -367,15 +306,23 @@ struct ConvRegistry {
         const ConvFamily* f = find(cfg, &l);
         return f ? f->bitwise : true;
     }
+    // the configuration has an instantiation that decodes in its epilogue
     bool cfg_decodes(int cfg) const {
         int l = 0;
         const ConvFamily* f = find(cfg, &l);
-        return f && f->decodes && f->decodes(l);
+        return f && conv_find_inst(f->insts(), l, CONV_KEY_DEC) != nullptr;
     }
     bool supports(int cfg, const ConvArgs& a) const {
         int l = 0;
         const ConvFamily* f = find(cfg, &l);
-        return f && conv_decode_ok(f->decodes && f->decodes(l), a) && conv_family_takes(*f, a) && f->supports(l, a);
+        return f && (!a.dec_pred || conv_decode_ok(cfg_decodes(cfg), a)) && conv_family_takes(*f, a) && f->supports(l, a);
+    }
+    // the configuration takes the op as one that decodes in its epilogue (of a.dec_pred only "is set" is ever read)
+    bool supports_decoding(int cfg, const ConvArgs& a) const {
+        float none = 0.f;
+        ConvArgs d = a;
+        if (!d.dec_pred) d.dec_pred = &none;
+        return supports(cfg, d);
     }
     hipError_t launch(int cfg, const ConvArgs& a, hipStream_t s) const {
         int l = 0;
@@ -387,10 +334,14 @@ struct ConvRegistry {
         const ConvFamily* f = fam[family];
         return k >= 0 && k < f->n_dev ? f->launch(f->n_cfgs + k, a, s) : hipErrorInvalidValue;
     }
+    // raises the dynamic-LDS limit of every instantiation (one-off)
     hipError_t init() const {
         hipError_t e = hipSuccess;
-        for (const ConvFamily* f : fam)
-            if (e == hipSuccess) e = f->init();
+        for (const ConvFamily* f : fam) {
+            const ConvInstTable t = f->insts();
+            for (int i = 0; i < t.n && e == hipSuccess; ++i)
+                e = hipFuncSetAttribute(t.rows[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.rows[i].lds_bytes);
+        }
         return e;
     }
 };
