@@ -161,7 +161,7 @@ int mdhip_create(const mdhip_model* model, int device, int dtype,
                  int max_batch, int max_h, int max_w, mdhip_ctx** out);
 /* A context WITHOUT a model, for work that only touches images (marking a results file and writing its review folder load no
  * detector): every image entry point works on it -- mdhip_jpeg_*, mdhip_blur_regions, mdhip_resample_lanczos, mdhip_draw_ops,
- * mdhip_classifier_input, mdhip_thumbnails -- and every entry point that needs the plan or the weights (mdhip_preprocess*,
+ * mdhip_classifier_input, mdhip_thumbnails, mdhip_change_detect (and its hook mdhip_label_regions_on) -- and every entry point that needs the plan or the weights (mdhip_preprocess*,
  * the forwards, mdhip_nms*, mdhip_read_*, mdhip_calibrate and the fp8 calls, the op / cfg / tuned / fuse / option / graph /
  * timing calls, the mdhip_*_on kernel hooks) returns MDHIP_EINVAL with a text in mdhip_last_error.  It owns nothing on the
  * device until a call needs scratch.  mdhip_destroy frees it. */
@@ -538,6 +538,34 @@ int mdhip_repeat_detections(int device, const mdhip_rde_box* boxes, int64_t n, d
  * candidates (all chunks), ms[1] counting the instances, ms[2] writing the pairs (0 when none were written); uploads and
  * read-backs are in none of them (tools/rde_bench.py) */
 int mdhip_repeat_detections_times(float ms[3]);
+
+/* Change detection between images that lie in device memory: what the reference's detection/change_detection.py detect_motion
+ * (FRAME_DIFF) computes per pair of consecutive images -- gray, region of interest, Gaussian blur, absolute difference,
+ * threshold (GLOBAL or OTSU), dilation, connected regions -- with the arithmetic csrc/change_detect.h defines in integers (it is
+ * the project's restatement: not verified against OpenCV, and regions are measured by pixel count and listed by label, which
+ * cv2.contourArea and cv2.findContours do not do).  The host model is mdjpeg_change_detect (include/mdjpeg.h), whose comment
+ * describes every argument; here
+ *   ctx                       any context, one of mdhip_create_images included
+ *   images, blurred, masks    point to DEVICE memory; every other array is HOST memory, inputs and results alike
+ *   blurred, blurred_ready    a caller keeps the plane of a camera's last image and hands it in, ready, with the next call: every
+ *                             image is converted and blurred once, not once as "current" and once as "previous"
+ * One launch per stage for all images (gray + blur along x, blur along y) and for all pairs of a group (histogram for OTSU,
+ * threshold + count, dilation with fused iterations, label init / merge / sums, selection in three launches), pairs of any sizes
+ * side by side; a group is as many pairs as fit 1 GiB of scratch (26 bytes a pixel), which belongs to the context and grows on
+ * demand.  OTSU's threshold is chosen on the host from the histogram (one extra synchronisation a group).  The call returns when
+ * the results are in host memory.  MDHIP_EINVAL as mdjpeg_change_detect, and for a host pointer where device memory is due, more
+ * than 65535 images or pairs; nothing is launched then. */
+typedef mdjpeg_change_options mdhip_change_options;
+int mdhip_change_detect(mdhip_ctx* ctx, const uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
+                        int n_images, uint8_t* const* blurred, const uint8_t* blurred_ready, const int32_t* pairs, int n_pairs,
+                        const mdhip_change_options* opt, int64_t* counts, uint32_t* hist, int32_t* thresholds, int32_t* n_regions,
+                        int32_t* regions, uint8_t* overflow, uint8_t* const* masks, void* hip_stream);
+/* The region stage of mdhip_change_detect in isolation (tests; host buffers, any context): the 8-connected components of the
+ * non-zero pixels of mask (w x h bytes) -> labels (w x h; the smallest raster index of the pixel's component, -1 for
+ * background), *n_regions (components with more than min_area pixels), the first `cap` of them by ascending label as
+ * x, y, w, h, area in regions, *overflow (1: more than cap). */
+int mdhip_label_regions_on(mdhip_ctx* ctx, const uint8_t* mask, int w, int h, int min_area, int cap, int32_t* labels, int32_t* n_regions,
+                           int32_t* regions, uint8_t* overflow, void* hip_stream);
 
 /* Test-time augmentation: replaces mdhip_forward for `model(batch, augment=True)` (reference
  * pytorch_detector.py:1313 -> yolov5 _forward_augment): three passes over the batch that mdhip_preprocess

@@ -205,6 +205,42 @@ int mdjpeg_repeat_detections(const mdjpeg_rde_box* boxes, int64_t n, double iou_
                              int32_t occurrence_threshold, int32_t chunk, uint8_t* is_candidate, int32_t* n_instances,
                              int64_t* pairs, int64_t capacity, int64_t* needed);
 
+/* ---- change detection between images (GPU: mdhip_change_detect, include/mdhip.h) ----------------------------------------- */
+/* The host model of the GPU call, compiled from the header the kernels are compiled from (csrc/change_detect.h, which defines
+ * every step: gray, region of interest, blur, difference, threshold, dilation, regions).  Arguments and results are those of
+ * mdhip_change_detect without the context and the stream, and every pointer is host memory:
+ *   images, widths, heights, pitches, n_images   RGB images, 8 bits a sample, `pitches[i]` bytes a row; sides 1 .. 32767.
+ *   blurred, blurred_ready      per image a plane of widths[i] x heights[i] bytes, dense: the blurred gray image.  ready 0: the
+ *                               call computes it from images[i] and writes it there; ready 1: it holds the plane already (of an
+ *                               earlier call with the same options) and images[i] is not read and may be NULL.
+ *   pairs, n_pairs              n_pairs x 2 image indices (previous, current); both images of a pair have one size
+ *   opt                         the options: see csrc/change_detect.h for their ranges
+ *   counts                      per pair the number of non-zero pixels of the thresholded mask (after the region of interest)
+ *   hist                        per pair the 256-bin histogram of the difference for threshold_type 1 (OTSU), else zeros
+ *   thresholds                  per pair the threshold that was applied
+ *   n_regions                   per pair the number of significant regions (area > min_area), whatever the cap
+ *   regions                     per pair opt->region_cap x 5 values: x, y, w, h, area of the first region_cap significant
+ *                               regions by ascending label
+ *   overflow                    per pair 1 when n_regions is above region_cap (the list is cut), else 0
+ *   masks                       NULL, or per pair NULL or a widths x heights plane that receives the dilated mask (0 / 255)
+ * MDJPEG_EINVAL, and nothing is written, for a NULL pointer, an option or a size outside its range, a pitch below its row, a
+ * pair that names an image outside 0 .. n_images - 1 or two images of different sizes, an image that is neither given nor ready. */
+typedef struct {
+    int32_t blur_kernel_size;    /* odd, 1 .. 127                                   */
+    int32_t threshold_type;      /* 0 GLOBAL, 1 OTSU                                */
+    int32_t threshold;           /* GLOBAL: 0 .. 255                                */
+    int32_t dilate_kernel_size;  /* 1 .. 33                                         */
+    int32_t dilate_iterations;   /* 0 .. 64                                         */
+    int32_t min_area;            /* >= 0                                            */
+    int32_t has_ignore;          /* 0: ignore_fraction is None                      */
+    int32_t region_cap;          /* 0 .. 65536                                      */
+    double  ignore_fraction;     /* -1 .. 1                                         */
+} mdjpeg_change_options;
+int mdjpeg_change_detect(const uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches, int n_images,
+                         uint8_t* const* blurred, const uint8_t* blurred_ready, const int32_t* pairs, int n_pairs,
+                         const mdjpeg_change_options* opt, int64_t* counts, uint32_t* hist, int32_t* thresholds, int32_t* n_regions,
+                         int32_t* regions, uint8_t* overflow, uint8_t* const* masks);
+
 const char* mdjpeg_version(void);
 
 #ifdef __cplusplus

@@ -10,6 +10,8 @@ import os
 
 import numpy as np
 
+from .jpeg_host import mdjpeg_change_options
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libmdhip.so')
 
@@ -78,6 +80,9 @@ class mdhip_rde_box(C.Structure):
                 ('group', C.c_int32), ('category', C.c_int32)]
 
 
+mdhip_change_options = mdjpeg_change_options      # the header's typedef
+
+
 class mdhip_op_info(C.Structure):
     _fields_ = [('name', C.c_char * 48), ('kind', C.c_int32), ('layer', C.c_int32),
                 ('m', C.c_int32), ('n', C.c_int32), ('k', C.c_int32),
@@ -130,6 +135,9 @@ SYMBOLS = {
     'mdhip_repeat_detections': (C.c_int, [C.c_int, _P, C.c_int64, C.c_double, C.c_int, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64,
                                           C.POINTER(C.c_int64)]),
     'mdhip_repeat_detections_times': (C.c_int, [C.POINTER(C.c_float)]),
+    'mdhip_change_detect': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.POINTER(mdhip_change_options), _P, _P, _P, _P, _P,
+                                      _P, _P, _P]),
+    'mdhip_label_regions_on': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     'mdhip_forward_tta': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_last_num_anchors': (C.c_int, [_P]),
     'mdhip_calibrate': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),

@@ -1,6 +1,6 @@
 // The image entry points of the C ABI (include/mdhip.h): letterbox (mdhip_preprocess*), JPEG (mdhip_jpeg_*), mdhip_blur_regions,
 // the previews (mdhip_resample_lanczos, mdhip_draw_ops), the classifier input (mdhip_classifier_input), the thumbnails
-// (mdhip_thumbnails).
+// (mdhip_thumbnails), change detection (mdhip_change_detect).
 // None of them looks at the model: they check their arguments, lay out scratch in one of the context's growable buffers
 // (mdhip_ctx.h DevBuffer) and launch.  What their checks have in common is written once, below; where two entry points
 // apply the same checks in a different order, each keeps its own order (the first failing check is what a caller sees).
@@ -20,6 +20,7 @@
 #include "jpeg_keep.h"
 #include "blur_box.h"
 #include "resample.h"
+#include "change_detect.h"
 
 namespace {
 
@@ -1016,6 +1017,130 @@ int mdhip_thumbnails(mdhip_ctx* ctx, const mdhip_thumbnail* tiles, int n, int fi
     HIP_TRY(ctx, hipMemcpyAsync(base + o_recs, recs.data(), recs.size() * sizeof(MdClassifyCrop), hipMemcpyHostToDevice, s));
     if (!table.empty()) HIP_TRY(ctx, hipMemcpyAsync(base + o_table, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, launch_thumbnails((const MdClassifyCrop*)(base + o_recs), n, max_blocks, (const int32_t*)(base + o_table), s));
+    return MDHIP_OK;
+}
+
+int mdhip_change_detect(mdhip_ctx* ctx, const uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
+                        int n_images, uint8_t* const* blurred, const uint8_t* blurred_ready, const int32_t* pairs, int n_pairs,
+                        const mdhip_change_options* opt, int64_t* counts, uint32_t* hist, int32_t* thresholds, int32_t* n_regions,
+                        int32_t* regions, uint8_t* overflow, uint8_t* const* masks, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!opt || !chg_options_ok(opt->blur_kernel_size, opt->threshold_type, opt->threshold, opt->dilate_kernel_size, opt->dilate_iterations,
+                                opt->min_area, opt->has_ignore, opt->ignore_fraction, opt->region_cap))
+        return fail(ctx, MDHIP_EINVAL, "options: NULL, or a value outside its range (csrc/change_detect.h)");
+    if (n_images > 65535 || n_pairs > 65535 ||
+        !chg_args_ok(images, widths, heights, pitches, n_images, blurred, blurred_ready, pairs, n_pairs, counts, hist, thresholds, n_regions,
+                     regions, overflow, opt->region_cap))
+        return fail(ctx, MDHIP_EINVAL, "a NULL pointer, a size or pitch outside its range, an image neither given nor ready, or a pair that "
+                    "names no image or two images of different sizes (%d images, %d pairs)", n_images, n_pairs);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    for (int i = 0; i < n_images; ++i)
+        if (!is_device_ptr(blurred[i]) || (!blurred_ready[i] && !is_device_ptr(images[i])))
+            return fail(ctx, MDHIP_EINVAL, "image %d: the pixels and the blurred plane must be device memory", i);
+    for (int p = 0; masks && p < n_pairs; ++p)
+        if (masks[p] && !is_device_ptr(masks[p])) return fail(ctx, MDHIP_EINVAL, "pair %d: the mask must be device memory", p);
+    const size_t budget = (size_t)1 << 30;              // scratch planes of one group of images or pairs (one that needs more is a group)
+    ChgWeights wt;
+    chg_blur_weights(opt->blur_kernel_size, &wt);
+
+    // ---- gray and blur, once per image that does not come with its plane
+    for (int first = 0; first < n_images;) {
+        ScratchLayout lay;
+        std::vector<ChgImage> recs;
+        std::vector<size_t> o_first;
+        int max_w = 1, max_h = 1, last = first;
+        lay.take(sizeof(ChgImage) * (size_t)(n_images - first));        // (at offset 0; room for every image that is left)
+        for (; last < n_images && (recs.empty() || lay.size < budget); ++last) {
+            if (blurred_ready[last]) continue;
+            ChgImage d{};
+            d.rgb = images[last], d.pitch = pitches[last], d.out = blurred[last], d.w = widths[last], d.h = heights[last];
+            chg_roi_rows(opt->has_ignore, opt->ignore_fraction, d.h, &d.y0, &d.y1);
+            o_first.push_back(lay.take(2 * (size_t)d.w * d.h));
+            max_w = std::max(max_w, d.w), max_h = std::max(max_h, d.h);
+            recs.push_back(d);
+        }
+        first = last;
+        if (recs.empty()) continue;
+        if (int rc = ctx->change.reserve(ctx, lay.size, &s)) return rc;
+        for (size_t k = 0; k < recs.size(); ++k) recs[k].first = (uint16_t*)(ctx->change.p + o_first[k]);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->change.p, recs.data(), sizeof(ChgImage) * recs.size(), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, launch_chg_blur((const ChgImage*)ctx->change.p, (int)recs.size(), max_w, max_h, wt, s));
+    }
+
+    // ---- the pairs, in groups
+    const int cap = opt->region_cap;
+    for (int first = 0; first < n_pairs;) {
+        struct Off { size_t m0, m1, label, stat, blocks; };
+        ScratchLayout lay;
+        std::vector<Off> offs;
+        int last = first, max_w = 1, max_h = 1;
+        long long max_px = 1;
+        const size_t room = (size_t)(n_pairs - first);
+        lay.take(sizeof(ChgPair) * room);                               // (at offset 0)
+        const size_t o_thr = lay.take(4 * room), o_count = lay.take(8 * room), o_nreg = lay.take(4 * room);
+        const size_t o_hist = lay.take(1024 * room), o_regions = lay.take(20 * (size_t)cap * room);
+        const size_t o_planes = lay.size;
+        for (; last < n_pairs && (offs.empty() || lay.size - o_planes < budget); ++last) {
+            const size_t px = (size_t)widths[pairs[2 * last]] * heights[pairs[2 * last]], nb = (px + 255) / 256;
+            Off o;
+            o.m0 = lay.take(px), o.m1 = lay.take(px), o.label = lay.take(4 * px), o.stat = lay.take(20 * px), o.blocks = lay.take(8 * nb);
+            offs.push_back(o);
+        }
+        const int n = last - first;
+        if (int rc = ctx->change.reserve(ctx, lay.size, &s)) return rc;
+        char* base = ctx->change.p;
+        std::vector<ChgPair> recs((size_t)n);
+        for (int k = 0; k < n; ++k) {
+            const int p = first + k, a = pairs[2 * p], b = pairs[2 * p + 1];
+            ChgPair& d = recs[(size_t)k];
+            d.a = blurred[a], d.b = blurred[b];
+            d.m[0] = (uint8_t*)(base + offs[k].m0), d.m[1] = (uint8_t*)(base + offs[k].m1);
+            d.label = (uint32_t*)(base + offs[k].label), d.stat = (uint32_t*)(base + offs[k].stat);
+            d.block_count = (uint32_t*)(base + offs[k].blocks);
+            d.hist = (uint32_t*)(base + o_hist) + 256 * (size_t)k;
+            d.count = (unsigned long long*)(base + o_count) + k;
+            d.n_regions = (int32_t*)(base + o_nreg) + k;
+            d.regions = (int32_t*)(base + o_regions) + 5 * (size_t)cap * k;
+            d.label_out = nullptr;
+            d.w = widths[a], d.h = heights[a];
+            chg_roi_rows(opt->has_ignore, opt->ignore_fraction, d.h, &d.y0, &d.y1);
+            max_w = std::max(max_w, d.w), max_h = std::max(max_h, d.h);
+            max_px = std::max(max_px, (long long)d.w * d.h);
+        }
+        const ChgPair* dev = (const ChgPair*)base;
+        HIP_TRY(ctx, hipMemcpyAsync(base, recs.data(), sizeof(ChgPair) * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemsetAsync(base + o_thr, 0, o_planes - o_thr, s));            // thresholds, counts, histograms, regions
+        std::vector<int32_t> thr((size_t)n, opt->threshold);
+        if (opt->threshold_type == 1) {
+            // the histogram comes to the host, where chg_otsu chooses the threshold for both legs
+            HIP_TRY(ctx, launch_chg_diff(dev, n, max_px, 0, nullptr, s));
+            HIP_TRY(ctx, hipMemcpyAsync(hist + 256 * (size_t)first, base + o_hist, 1024 * (size_t)n, hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, hipStreamSynchronize(s));
+            for (int k = 0; k < n; ++k) thr[(size_t)k] = chg_otsu(hist + 256 * (size_t)(first + k));
+        } else {
+            memset(hist + 256 * (size_t)first, 0, 1024 * (size_t)n);
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_thr, thr.data(), 4 * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, launch_chg_diff(dev, n, max_px, 1, (const int32_t*)(base + o_thr), s));
+        int sel = 0;
+        HIP_TRY(ctx, launch_chg_dilate(dev, n, max_w, max_h, opt->dilate_kernel_size, opt->dilate_iterations, &sel, s));
+        HIP_TRY(ctx, launch_chg_regions(dev, n, max_w, max_h, sel, opt->min_area, cap, s));
+        for (int k = 0; masks && k < n; ++k)
+            if (masks[first + k])
+                HIP_TRY(ctx, hipMemcpyAsync(masks[first + k], recs[(size_t)k].m[sel], (size_t)recs[(size_t)k].w * recs[(size_t)k].h,
+                                            hipMemcpyDeviceToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(counts + first, base + o_count, 8 * (size_t)n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipMemcpyAsync(n_regions + first, base + o_nreg, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
+        if (cap)
+            HIP_TRY(ctx, hipMemcpyAsync(regions + 5 * (size_t)cap * first, base + o_regions, 20 * (size_t)cap * n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        for (int k = 0; k < n; ++k) {
+            thresholds[first + k] = thr[(size_t)k];
+            overflow[first + k] = n_regions[first + k] > cap ? 1 : 0;
+        }
+        first = last;
+    }
     return MDHIP_OK;
 }
 

@@ -9,6 +9,7 @@
 
 struct MdClassifyCrop;             // resample.h: the record of a crop of mdhip_classifier_input
 
+struct ChgWeights;                 // change_detect.h: the blur's taps
 struct MdjImage;
 struct MdjEncCrop;
 struct MdjEncTables;
@@ -610,5 +611,42 @@ hipError_t launch_classifier_input(const MdClassifyCrop* crops, int n, int max_b
                                    hipStream_t s);
 // Thumbnails (the same kernel body, bytes stored interleaved at each record's dst): n tiles, one launch
 hipError_t launch_thumbnails(const MdClassifyCrop* tiles, int n, int max_blocks, const int32_t* table, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------
+// Change detection (change_kernels.cpp; the arithmetic is change_detect.h's): one record per image of the blur launches and
+// one per pair of the others, read by the workgroups of a launch (blockIdx.z, or blockIdx.y of the one-dimensional kernels)
+// ---------------------------------------------------------------------------------------
+struct ChgImage {
+    const uint8_t* rgb;                // the image, `pitch` bytes a row
+    long long pitch;
+    uint16_t* first;                   // w x h: the blur's first pass (along x), 16-bit sums
+    uint8_t*  out;                     // w x h: the blurred gray image
+    int w, h;
+    int y0, y1;                        // rows the region of interest keeps: [y0, y1)
+};
+struct ChgPair {
+    const uint8_t* a;                  // the two blurred gray images, w x h
+    const uint8_t* b;
+    uint8_t*  m[2];                    // w x h each: the thresholded mask (m[0]) and the dilation's other buffer
+    uint32_t* label;                   // w x h: the parent links of the label merge (0xffffffff: background)
+    uint32_t* stat;                    // 5 planes of w x h, read at a component's label: pixel count, xmin, ymin, xmax, ymax
+    uint32_t* block_count;             // per 256 pixels the significant labels among them, and (behind them) the offset of the first
+    uint32_t* hist;                    // 256
+    unsigned long long* count;         // non-zero pixels of the thresholded mask
+    int32_t*  n_regions;
+    int32_t*  regions;                 // cap x 5
+    int32_t*  label_out;               // nullptr, or w x h: every pixel's label (-1: background)
+    int w, h;
+    int y0, y1;
+};
+constexpr int CHG_DILATE_HALO = 32;    // reach of one dilation launch to either side, in pixels
+hipError_t launch_chg_blur(const ChgImage* images, int n, int max_w, int max_h, const ChgWeights& wt, hipStream_t s);
+// mode 0: the histogram of |a - b| (added to hist); mode 1: the thresholded mask m[0] with pair p's threshold thr[p], and its count
+hipError_t launch_chg_diff(const ChgPair* pairs, int n, long long max_px, int mode, const int32_t* thr, hipStream_t s);
+// `iterations` dilations with the k x k square, as many of them fused per launch as the halo allows; *sel: in, the buffer that
+// holds the mask; out, the one that holds the result
+hipError_t launch_chg_dilate(const ChgPair* pairs, int n, int max_w, int max_h, int k, int iterations, int* sel, hipStream_t s);
+// the regions of m[sel]: labels, per-label sums, the significant ones (count > min_area) in ascending order, at most cap written
+hipError_t launch_chg_regions(const ChgPair* pairs, int n, int max_w, int max_h, int sel, int min_area, int cap, hipStream_t s);
 
 }  // namespace mdhip

@@ -1,10 +1,12 @@
-// The YOLO11 / YOLOv9 kernels in isolation (tests): the mdhip_*_on hooks of include/mdhip.h.
+// The YOLO11 / YOLOv9 kernels and the region stage of the change detection in isolation (tests): the mdhip_*_on hooks of
+// include/mdhip.h.
 // host buffers in / out; scratch device memory is allocated per call (not for the product path)
 
 #include <algorithm>
 #include <vector>
 
 #include "mdhip_ctx.h"
+#include "change_detect.h"
 
 namespace {
 struct DevBufs {
@@ -145,6 +147,43 @@ int mdhip_cbfuse_on(mdhip_ctx* ctx, const uint16_t* const* src, const int32_t* f
     HIP_TRY(ctx, launch_cbfuse(a, ctx->dtype == MDHIP_DTYPE_FP16, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     HIP_TRY(ctx, hipMemcpy(out, dout, px * c * 2, hipMemcpyDeviceToHost));
+    return MDHIP_OK;
+}
+
+// (reads no model: a context of mdhip_create_images serves)
+int mdhip_label_regions_on(mdhip_ctx* ctx, const uint8_t* mask, int w, int h, int min_area, int cap, int32_t* labels, int32_t* n_regions,
+                           int32_t* regions, uint8_t* overflow, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (!mask || !labels || !n_regions || !overflow || w < 1 || h < 1 || w > CHG_MAX_SIDE || h > CHG_MAX_SIDE ||
+        (long long)w * h > CHG_MAX_PIXELS || min_area < 0 || cap < 0 || cap > 65536 || (cap && !regions))
+        return fail(ctx, MDHIP_EINVAL, "a NULL pointer, or %dx%d, min_area %d, cap %d outside their ranges", w, h, min_area, cap);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)w * h, nb = (px + 255) / 256;
+    DevBufs d;
+    void *dm, *dlabel, *dstat, *dblocks, *dn, *dregions, *dout, *drec;
+    HIP_TRY(ctx, d.get(px, &dm));
+    HIP_TRY(ctx, d.get(4 * px, &dlabel));
+    HIP_TRY(ctx, d.get(20 * px, &dstat));
+    HIP_TRY(ctx, d.get(8 * nb, &dblocks));
+    HIP_TRY(ctx, d.get(4, &dn));
+    HIP_TRY(ctx, d.get(20 * (size_t)cap, &dregions));
+    HIP_TRY(ctx, d.get(4 * px, &dout));
+    HIP_TRY(ctx, d.get(sizeof(ChgPair), &drec));
+    ChgPair rec{};
+    rec.m[0] = (uint8_t*)dm, rec.m[1] = nullptr;
+    rec.label = (uint32_t*)dlabel, rec.stat = (uint32_t*)dstat, rec.block_count = (uint32_t*)dblocks;
+    rec.n_regions = (int32_t*)dn, rec.regions = (int32_t*)dregions, rec.label_out = (int32_t*)dout;
+    rec.w = w, rec.h = h, rec.y0 = 0, rec.y1 = h;
+    HIP_TRY(ctx, hipMemcpy(dm, mask, px, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(drec, &rec, sizeof(rec), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemset(dregions, 0, std::max<size_t>(20 * (size_t)cap, 16)));
+    HIP_TRY(ctx, launch_chg_regions((const ChgPair*)drec, 1, w, h, 0, min_area, cap, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipMemcpy(labels, dout, 4 * px, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(n_regions, dn, 4, hipMemcpyDeviceToHost));
+    if (cap) HIP_TRY(ctx, hipMemcpy(regions, dregions, 20 * (size_t)cap, hipMemcpyDeviceToHost));
+    *overflow = *n_regions > cap ? 1 : 0;
     return MDHIP_OK;
 }
 

@@ -510,6 +510,41 @@ class HipContext:
         self._check(self.lib.mdhip_draw_ops(self.h, p, ws, hs, pt, n, oi, flat, m,
                                             C.c_void_p(int(patches_ptr) or None), int(patch_bytes), C.c_void_p(stream)), 'mdhip_draw_ops')
 
+    def change_detect(self, ptrs, sizes, blurred_ptrs, ready, pairs, options, mask_ptrs=None, stream=0):
+        """
+        Change detection between device images (include/mdhip.h: mdhip_change_detect).
+        ptrs, sizes:   per image the device address of its dense RGB pixels (0 where its plane is ready) and (width, height)
+        blurred_ptrs:  per image the device address of its width x height blurred gray plane; ready[i]: it is filled already
+        pairs:         (previous, current) indices; options: jpeg_host.change_options()
+        mask_ptrs:     None, or per pair 0 or the device address that receives the dilated mask
+        Returns jpeg_host.ChangeArrays.result(): host arrays; the call has completed.
+        """
+        from . import jpeg_host
+        n, m = len(ptrs), len(pairs)
+        if not (len(sizes) == len(blurred_ptrs) == len(ready) == n):
+            raise ValueError('ptrs, sizes, blurred_ptrs and ready must have one entry per image')
+        p, ws, hs, pt = _window_arrays(ptrs, sizes, [3 * s[0] for s in sizes])
+        bl = C.cast((C.c_void_p * max(n, 1))(*[int(v) for v in blurred_ptrs]), C.c_void_p)
+        rd = (C.c_uint8 * max(n, 1))(*[1 if v else 0 for v in ready])
+        pr = (C.c_int32 * max(2 * m, 1))(*[int(v) for q in pairs for v in q])
+        mk = None if mask_ptrs is None else C.cast((C.c_void_p * max(m, 1))(*[int(v) or None for v in mask_ptrs]), C.c_void_p)
+        out = jpeg_host.ChangeArrays(m, options.region_cap)
+        self._check(self.lib.mdhip_change_detect(self.h, p, ws, hs, pt, n, bl, rd, pr, m, C.byref(options), *out.pointers(), mk,
+                                                 C.c_void_p(stream)), 'mdhip_change_detect')
+        return out.result(m, options.region_cap)
+
+    def label_regions_on(self, mask, min_area=0, cap=256, stream=0):
+        """the region stage of change_detect on a host mask (h, w) (include/mdhip.h: mdhip_label_regions_on) -> (labels (h, w)
+        int32, n_regions, regions (min(n_regions, cap), 5), overflow)"""
+        mask = np.ascontiguousarray(mask, np.uint8)
+        h, w = mask.shape
+        labels, n_regions, overflow = np.zeros((h, w), np.int32), C.c_int32(0), C.c_uint8(0)
+        regions = np.zeros((max(cap, 1), 5), np.int32)
+        self._check(self.lib.mdhip_label_regions_on(self.h, mask.ctypes.data, w, h, int(min_area), int(cap), labels.ctypes.data,
+                                                    C.addressof(n_regions), regions.ctypes.data, C.addressof(overflow), C.c_void_p(stream)),
+                    'mdhip_label_regions_on')
+        return labels, n_regions.value, regions[:min(n_regions.value, cap)], overflow.value
+
     def classifier_input(self, crops, size, out_ptr, filter=0, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), stream=0):
         """
         The input tensor of a classifier for crops of device images, in one launch (include/mdhip.h: mdhip_classifier_input).

@@ -50,6 +50,12 @@ class mdjpeg_thumbnail(C.Structure):
                 ('out_w', C.c_int32), ('out_h', C.c_int32), ('dst', C.c_void_p), ('dst_pitch', C.c_int64)]
 
 
+class mdjpeg_change_options(C.Structure):
+    _fields_ = [('blur_kernel_size', C.c_int32), ('threshold_type', C.c_int32), ('threshold', C.c_int32),
+                ('dilate_kernel_size', C.c_int32), ('dilate_iterations', C.c_int32), ('min_area', C.c_int32),
+                ('has_ignore', C.c_int32), ('region_cap', C.c_int32), ('ignore_fraction', C.c_double)]
+
+
 #: every symbol include/mdjpeg.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     'mdjpeg_parse': (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(mdjpeg_info)]),
@@ -78,6 +84,8 @@ SYMBOLS = {
     'mdjpeg_thumbnails': (C.c_int, [C.POINTER(mdjpeg_thumbnail), C.c_int, C.c_int32]),
     'mdjpeg_repeat_detections': (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    'mdjpeg_change_detect': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'mdjpeg_version': (C.c_char_p, []),
 }
 
@@ -595,6 +603,74 @@ def thumbnails(tiles, filter=0):
     if rc != MDJPEG_OK:
         raise ValueError('mdjpeg_thumbnails returned {}'.format(rc))
     return True
+
+
+def change_options(blur_kernel_size=21, threshold_type=0, threshold=25, dilate_kernel_size=5, dilate_iterations=2, min_area=500,
+                   ignore_fraction=None, region_cap=256):
+    """the option record of mdjpeg_change_detect / mdhip_change_detect (threshold_type: 0 GLOBAL, 1 OTSU)"""
+    return mdjpeg_change_options(int(blur_kernel_size), int(threshold_type), int(threshold), int(dilate_kernel_size), int(dilate_iterations),
+                                 int(min_area), 0 if ignore_fraction is None else 1, int(region_cap),
+                                 0.0 if ignore_fraction is None else float(ignore_fraction))
+
+
+class ChangeArrays:
+    """the host arrays both change-detection calls fill, and what is read out of them: per pair `counts`, `hist` (256),
+    `thresholds`, `n_regions`, `regions` (cap x 5: x, y, w, h, area), `overflow`"""
+
+    def __init__(self, n_pairs, cap):
+        n = max(int(n_pairs), 1)
+        self.counts = np.zeros(n, np.int64)
+        self.hist = np.zeros((n, 256), np.uint32)
+        self.thresholds = np.zeros(n, np.int32)
+        self.n_regions = np.zeros(n, np.int32)
+        self.regions = np.zeros((n, max(int(cap), 1), 5), np.int32)
+        self.overflow = np.zeros(n, np.uint8)
+
+    def pointers(self):
+        return [a.ctypes.data for a in (self.counts, self.hist, self.thresholds, self.n_regions, self.regions, self.overflow)]
+
+    def result(self, n_pairs, cap):
+        return {'counts': self.counts[:n_pairs], 'hist': self.hist[:n_pairs], 'thresholds': self.thresholds[:n_pairs],
+                'n_regions': self.n_regions[:n_pairs], 'regions': self.regions[:n_pairs, :cap], 'overflow': self.overflow[:n_pairs]}
+
+
+def change_detect(images, pairs, options, blurred=None, want_masks=False):
+    """mdjpeg_change_detect: images: per image an (h, w, 3) uint8 array, or None where blurred[i] is given; pairs: (previous,
+    current) indices; options: change_options(); blurred: None, or per image None or its (h, w) uint8 blurred gray plane of an
+    earlier call.  -> the ChangeArrays result plus 'blurred' (per image its plane) and 'masks' (per pair the dilated mask, or
+    None).  ValueError for what the call refuses."""
+    n, m = len(images), len(pairs)
+    blurred = list(blurred) if blurred is not None else [None] * n
+    ready = np.array([b is not None for b in blurred], np.uint8)
+    rgb, sizes = [], []
+    for i in range(n):
+        if ready[i]:
+            blurred[i] = np.ascontiguousarray(blurred[i], np.uint8)
+            rgb.append(None)
+            sizes.append((blurred[i].shape[1], blurred[i].shape[0]))
+        else:
+            a = np.ascontiguousarray(images[i], np.uint8)
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError('image {}: an (h, w, 3) array is needed'.format(i))
+            rgb.append(a)
+            sizes.append((a.shape[1], a.shape[0]))
+            blurred[i] = np.zeros((a.shape[0], a.shape[1]), np.uint8)
+    pair_arr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+    for a, b in pair_arr:
+        if not (0 <= a < n and 0 <= b < n) or sizes[a] != sizes[b]:
+            raise ValueError('a pair names no image, or two images of different sizes')
+    masks = [np.zeros((sizes[a][1], sizes[a][0]), np.uint8) for a, _ in pair_arr] if want_masks else None
+    out = ChangeArrays(m, options.region_cap)
+    rc = load().mdjpeg_change_detect(
+        (C.c_void_p * max(n, 1))(*[None if a is None else a.ctypes.data for a in rgb]), (C.c_int32 * max(n, 1))(*[s[0] for s in sizes]),
+        (C.c_int32 * max(n, 1))(*[s[1] for s in sizes]), (C.c_int64 * max(n, 1))(*[3 * s[0] for s in sizes]), n,
+        (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in blurred]), ready.ctypes.data, pair_arr.ctypes.data, m, C.addressof(options),
+        *out.pointers(), (C.c_void_p * max(m, 1))(*[k.ctypes.data for k in masks]) if want_masks else None)
+    if rc != MDJPEG_OK:
+        raise ValueError('mdjpeg_change_detect refused its arguments ({})'.format(rc))
+    res = out.result(m, options.region_cap)
+    res['blurred'], res['masks'] = blurred, masks
+    return res
 
 
 def classifier_plan(canvas_w, canvas_h, size, filter=0, lds_bytes=0):
