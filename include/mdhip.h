@@ -638,6 +638,21 @@ int mdhip_read_input(mdhip_ctx* ctx, int n, int h, int w, float* out, void* hip_
  * c,h,w through the out-params; out may be NULL to query the shape only */
 int mdhip_read_layer(mdhip_ctx* ctx, int layer, int n, float* out, int* c, int* h, int* w,
                      void* hip_stream);
+/* A forward op by op (tests/op_step.py; ops are numbered as mdhip_get_op_info and mdhip_plan_describe number them).
+ * mdhip_run_ops: the checks of mdhip_forward_timed, then ONE isolated pass (every op its own launch, as mdhip_time_op runs one:
+ *   no fused bottleneck, no upsample read in place, no decode in a conv's epilogue; never a replayed graph) over ops
+ *   [first, first + count) of a forward of n images of h x w, then a wait for the stream.  first == 0 begins a pass as
+ *   mdhip_forward does (the other prediction buffer); a range that reaches the last op finishes it: from then on mdhip_read_layer
+ *   and mdhip_read_predictions describe the stepped pass.  A range outside [0, mdhip_num_ops] is MDHIP_EINVAL.
+ * mdhip_read_op_tensor: a view of op `op` exactly as stored, as NCHW fp32 at the size of the pass being stepped (of the last
+ *   forward when none is): which = 0 in, 1 out, 2 res, 3 out2, 4..6 fsrc[0..2]; out may be NULL to query the shape only.  The
+ *   fp32 logits of a Detect conv for its `out`; the stem's `in` as mdhip_read_input returns the network input.  MDHIP_EINVAL for
+ *   a view the op does not have, for an e4m3 tensor (fp8 contexts) and for the decode ops.
+ * mdhip_read_op_weights: what a conv or depthwise op multiplies, read back from the device: its 16-bit weights unpacked to
+ *   w [c_out][c_in][kh][kw] fp32 (the stem: its 6x6 taps) and its fp32 bias b [c_out]; NULL buffers query the shape only. */
+int mdhip_run_ops(mdhip_ctx* ctx, int n, int h, int w, int first, int count, void* hip_stream);
+int mdhip_read_op_tensor(mdhip_ctx* ctx, int op, int which, int n, float* out, int* c, int* h, int* w, void* hip_stream);
+int mdhip_read_op_weights(mdhip_ctx* ctx, int op, float* w, float* b, int* c_out, int* c_in, int* kh, int* kw);
 
 /* the YOLO11 kernels in isolation (tests; host buffers, scratch device memory allocated per call), in the context's
  * 16-bit storage type (bf16 or fp16 bits):

@@ -154,6 +154,10 @@ SYMBOLS = {
     'mdhip_read_predictions': (C.c_int, [_P, C.c_int, _P, _P]),
     'mdhip_read_input': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
     'mdhip_read_layer': (C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
+    'mdhip_run_ops': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    'mdhip_read_op_tensor': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
+    'mdhip_read_op_weights': (C.c_int, [_P, C.c_int, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int)]),
     'mdhip_dwconv3x3_on': (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.c_int, _P]),
     'mdhip_attention_on': (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),

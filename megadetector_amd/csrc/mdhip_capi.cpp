@@ -118,6 +118,7 @@ struct Pass {
         ctx->last_n = n; ctx->last_h = h; ctx->last_w = w;
         ctx->last_A = ctx->cur_A;
         ctx->last_ran = ran;
+        ctx->step_n = ctx->step_h = ctx->step_w = 0;
     }
 };
 
@@ -737,6 +738,115 @@ int mdhip_read_layer(mdhip_ctx* ctx, int layer, int n, float* out, int* c, int* 
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(tmp);
     HIP_TRY(ctx, e);
+    return MDHIP_OK;
+}
+
+// ---- a forward op by op (tests/op_step.py): run a range of ops, read what an op reads and writes, read what it multiplies ----
+
+int mdhip_run_ops(mdhip_ctx* ctx, int n, int h, int w, int first, int count, void* hip_stream) {
+    NEED_MODEL(ctx);
+    if (int rc = check_shape(ctx, n, h, w)) return rc;
+    if (int rc = check_calibrated(ctx)) return rc;
+    const int n_ops = (int)ctx->ops.size();
+    if (first < 0 || count < 0 || first > n_ops || count > n_ops - first)
+        return fail(ctx, MDHIP_EINVAL, "mdhip_run_ops: ops [%d,%d) outside [0,%d]", first, first + count, n_ops);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // every op as its own launch, as mdhip_time_op runs one
+    Pass pass(ctx, s, num_anchors_for(ctx, h, w), true);
+    if (first == 0)
+        if (int rc = pass.flip_prediction()) return rc;
+    if (int rc = pass.run(n, h, w, s, (size_t)first, (size_t)count)) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    if (first + count == n_ops) {
+        (void)pass.input_done(true);
+        pass.finish(n, h, w);
+    } else {
+        ctx->last_ran = pass.ran;          // (mdhip_get_op_info: the tiles of the pass that is being stepped)
+        ctx->step_n = n; ctx->step_h = h; ctx->step_w = w;
+    }
+    return MDHIP_OK;
+}
+
+int mdhip_read_op_tensor(mdhip_ctx* ctx, int op, int which, int n, float* out, int* c, int* h, int* w, void* hip_stream) {
+    NEED_MODEL(ctx);
+    if (op < 0 || op >= (int)ctx->ops.size()) return fail(ctx, MDHIP_EINVAL, "mdhip_read_op_tensor: op %d outside [0,%d)", op, (int)ctx->ops.size());
+    if (which < 0 || which > 6) return fail(ctx, MDHIP_EINVAL, "mdhip_read_op_tensor: which %d outside [0,6]", which);
+    const Op& o = ctx->ops[op];
+    if (o.kind == OP_DECODE || o.kind == OP_DFL)
+        return fail(ctx, MDHIP_EINVAL, "mdhip_read_op_tensor: op %d (%s) is a decode: read the conv in front and mdhip_read_predictions", op, o.name.c_str());
+    const bool f32 = which == 1 && o.kind == OP_CONV && o.out_f32;
+    const Tensor& t = which == 0 ? o.in : which == 1 ? o.out : which == 2 ? o.res : which == 3 ? o.out2 : o.fsrc[which - 4];
+    if (!t.valid || (which == 2 && !o.has_res) || (which >= 4 && which - 4 >= o.n_fsrc))
+        return fail(ctx, MDHIP_EINVAL, "mdhip_read_op_tensor: op %d (%s) has no tensor %d", op, o.name.c_str(), which);
+    if (ctx->dtype == MDHIP_DTYPE_FP8 && ((which == 0 && o.f8_in) || (which == 1 && o.f8_out)))
+        return fail(ctx, MDHIP_EINVAL, "mdhip_read_op_tensor: tensor %d of op %d (%s) is e4m3", which, op, o.name.c_str());
+    const int ph = ctx->step_h ? ctx->step_h : ctx->last_h, pw = ctx->step_h ? ctx->step_w : ctx->last_w;
+    const int pn = ctx->step_h ? ctx->step_n : ctx->last_n;
+    if (ph == 0) return fail(ctx, MDHIP_EINVAL, "mdhip_read_op_tensor before mdhip_run_ops or mdhip_forward");
+    const bool net_input = t.off == ctx->input.off;      // space-to-depth: returned as mdhip_read_input returns it
+    const int H = net_input ? ph : ph / t.div, W = net_input ? pw : pw / t.div, C = net_input ? 3 : t.c;
+    if (c) *c = C;
+    if (h) *h = H;
+    if (w) *w = W;
+    if (!out) return MDHIP_OK;
+    if (n < 1 || n > pn) return fail(ctx, MDHIP_EINVAL, "n=%d outside the last pass's batch %d", n, pn);
+    if (net_input) return mdhip_read_input(ctx, n, ph, pw, out, hip_stream);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (f32) {                       // fp32 logits [pixel][f32_ld]: transposed on the host
+        const size_t px = (size_t)n * H * W;
+        std::vector<float> host(px * o.f32_ld);
+        HIP_TRY(ctx, hipMemcpyAsync(host.data(), ctx->arena + o.f32_off, host.size() * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        for (int b = 0; b < n; ++b)
+            for (int ch = 0; ch < C; ++ch)
+                for (int p = 0; p < H * W; ++p) out[((size_t)b * C + ch) * H * W + p] = host[((size_t)b * H * W + p) * o.f32_ld + ch];
+        return MDHIP_OK;
+    }
+    float* tmp = nullptr;
+    const size_t bytes = (size_t)n * C * H * W * 4;
+    HIP_TRY(ctx, hipMalloc((void**)&tmp, bytes));
+    hipError_t e = launch_nhwc_to_nchw_f32((const uint16_t*)(ctx->arena + t.off), t.ld, tmp, n, C, H, W, ctx->dtype == MDHIP_DTYPE_FP16, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, tmp, bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(tmp);
+    HIP_TRY(ctx, e);
+    return MDHIP_OK;
+}
+
+int mdhip_read_op_weights(mdhip_ctx* ctx, int op, float* w, float* b, int* c_out, int* c_in, int* kh, int* kw) {
+    NEED_MODEL(ctx);
+    if (op < 0 || op >= (int)ctx->ops.size()) return fail(ctx, MDHIP_EINVAL, "mdhip_read_op_weights: op %d outside [0,%d)", op, (int)ctx->ops.size());
+    const Op& o = ctx->ops[op];
+    if ((o.kind != OP_CONV && o.kind != OP_DW) || o.pc < 0)
+        return fail(ctx, MDHIP_EINVAL, "mdhip_read_op_weights: op %d (%s) is neither a conv nor a depthwise conv", op, o.name.c_str());
+    const PackedConv& pc = ctx->packed[o.pc];
+    const bool stem = o.kind == OP_CONV && o.in.off == ctx->input.off;       // 6x6 taps over the space-to-depth cells
+    const bool dw = o.kind == OP_DW;
+    const int KH = stem ? 6 : pc.kh, KW = stem ? 6 : pc.kw, CI = stem ? 3 : dw ? 1 : pc.k_real / (pc.kh * pc.kw), CO = pc.c_out;
+    if (c_out) *c_out = CO;
+    if (c_in) *c_in = CI;
+    if (kh) *kh = KH;
+    if (kw) *kw = KW;
+    if (!w && !b) return MDHIP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    const int f16 = ctx->dtype == MDHIP_DTYPE_FP16;
+    if (b) HIP_TRY(ctx, hipMemcpy(b, ctx->warena + pc.b_off, (size_t)CO * 4, hipMemcpyDeviceToHost));
+    if (!w) return MDHIP_OK;
+    std::vector<uint16_t> p((size_t)pc.n_rows * pc.k_pad);
+    HIP_TRY(ctx, hipMemcpy(p.data(), ctx->warena + pc.w_off, p.size() * 2, hipMemcpyDeviceToHost));
+    for (int oc = 0; oc < CO; ++oc)
+        for (int ci = 0; ci < CI; ++ci)
+            for (int r = 0; r < KH; ++r)
+                for (int q = 0; q < KW; ++q) {
+                    size_t k;
+                    if (dw) k = (size_t)(r * 3 + q) * CO + oc;                     // [9][C]
+                    else if (stem) k = (size_t)oc * pc.k_pad + ((r >> 1) * 3 + (q >> 1)) * 16 + ((r & 1) * 2 + (q & 1)) * 3 + ci;
+                    else k = (size_t)oc * pc.k_pad + (r * KW + q) * pc.cin_pad + ci;
+                    w[(((size_t)oc * CI + ci) * KH + r) * KW + q] = st_to_f32(p[k], f16);
+                }
     return MDHIP_OK;
 }
 

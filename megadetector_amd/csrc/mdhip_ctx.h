@@ -228,6 +228,7 @@ struct mdhip_ctx {
     DevBuffer change;             // mdhip_change_detect: records, results, first-pass planes, masks, labels and sums of a group of pairs
     long long jpeg_entropy_stats[4] = {0, 0, 0, 0};   // of the last call: lanes, lanes decoded again, pass-2 launches, images
     int last_n = 0, last_h = 0, last_w = 0;
+    int step_n = 0, step_h = 0, step_w = 0;   // of a pass that mdhip_run_ops has begun and not finished (0: none)
     std::string err;
     // fp8 mode: until every e4m3 tensor has a scale (mdhip_calibrate / mdhip_fp8_set_scales) the forward refuses
     // to run; `calibrating` (the pass of mdhip_calibrate) runs every op in 16 bits and records the range of the tensors

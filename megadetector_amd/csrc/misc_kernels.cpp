@@ -670,8 +670,8 @@ hipError_t launch_sppf_pool(uint16_t* buf, int ld, int c, int n, int h, int w, i
                                buf, ld, c / 8, h, w, k / 2, f16);
             return hipGetLastError();
         }
-        const int threads = h * w * 4 >= 1024 ? 1024 : 256;
-        hipLaunchKernelGGL(sppf_pool_lds_kernel<4>, dim3((unsigned)(n * ((c / 8 + 3) / 4))), dim3(threads), per_chunk * 4, s,
+        // (here h * w < 256: fewer than 1024 (pixel, chunk) items)
+        hipLaunchKernelGGL(sppf_pool_lds_kernel<4>, dim3((unsigned)(n * ((c / 8 + 3) / 4))), dim3(256), per_chunk * 4, s,
                            buf, ld, c / 8, h, w, k / 2, f16);
         return hipGetLastError();
     }

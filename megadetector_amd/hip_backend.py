@@ -674,6 +674,29 @@ class HipContext:
                                               C.byref(w), C.c_void_p(stream)), 'mdhip_read_layer')
         return out
 
+    def run_ops(self, n, h, w, first, count, stream=0):
+        """ops [first, first + count) of a forward of n images of h x w, each as its own launch (mdhip_run_ops)"""
+        self._check(self.lib.mdhip_run_ops(self.h, int(n), int(h), int(w), int(first), int(count), C.c_void_p(stream)), 'mdhip_run_ops')
+
+    def read_op_tensor(self, op, which, n, stream=0):
+        """a view of an op as stored, NCHW float32: which = 0 in, 1 out, 2 res, 3 out2, 4..6 fsrc (mdhip_read_op_tensor)"""
+        c, h, w = C.c_int(), C.c_int(), C.c_int()
+        args = (C.byref(c), C.byref(h), C.byref(w), C.c_void_p(stream))
+        self._check(self.lib.mdhip_read_op_tensor(self.h, int(op), int(which), int(n), None, *args), 'mdhip_read_op_tensor')
+        out = np.empty((n, c.value, h.value, w.value), dtype=np.float32)
+        self._check(self.lib.mdhip_read_op_tensor(self.h, int(op), int(which), int(n), _lib.np_ptr(out), *args), 'mdhip_read_op_tensor')
+        return out
+
+    def read_op_weights(self, op):
+        """(weights [c_out][c_in][kh][kw], bias [c_out]) of a conv or depthwise op as the device holds them (mdhip_read_op_weights)"""
+        dims = [C.c_int() for _ in range(4)]
+        refs = [C.byref(d) for d in dims]
+        self._check(self.lib.mdhip_read_op_weights(self.h, int(op), None, None, *refs), 'mdhip_read_op_weights')
+        w = np.empty(tuple(d.value for d in dims), dtype=np.float32)
+        b = np.empty((dims[0].value,), dtype=np.float32)
+        self._check(self.lib.mdhip_read_op_weights(self.h, int(op), _lib.np_ptr(w), _lib.np_ptr(b), *refs), 'mdhip_read_op_weights')
+        return w, b
+
     def num_ops(self):
         return self.lib.mdhip_num_ops(self.h)
 

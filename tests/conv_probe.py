@@ -154,8 +154,13 @@ def accumulation_bound(S, K):
     return (K + 4) * U32 * S
 
 
+def conv_error(y, z, S, K):
+    """E of the docstring: the fp32 value in front of the rounding to storage against y"""
+    return 1.1 * accumulation_bound(S, K) + (8 + 2 * np.abs(z)) * U32 * np.abs(y)
+
+
 def conv_tolerance(y, z, S, K, dtype):
-    E = 1.1 * accumulation_bound(S, K) + (8 + 2 * np.abs(z)) * U32 * np.abs(y)
+    E = conv_error(y, z, S, K)
     return E + 0.5 * ulp_storage(np.abs(y) + E, dtype)
 
 
