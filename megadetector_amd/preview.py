@@ -210,14 +210,23 @@ def box_color(category):
     return name, ImageColor.getrgb(name)[:3]
 
 
-def drawn_detections(detections, options):
+def drawn_detections(detections, options, category_thresholds=None):
     """render_detection_bounding_boxes :664-684: the order the boxes are drawn in -- ascending confidence, so that the most
     confident box lands on top (a stable sort: equal confidences keep the file's order) -- and only those at or above the
-    threshold (a confidence of None is always drawn)"""
+    threshold (a confidence of None is always drawn).  category_thresholds: None, or the reference's confidence_threshold as
+    a dict (:677-680) -- category id -> threshold, consulted instead of options.confidence_threshold; a category it lacks is
+    KeyError as there, and a threshold of None draws every box of the category"""
     dets = list(file_detections(detections, options))
     if options.box_sort_order is not None:
         dets = sorted(dets, key=lambda d: (d['conf'] is not None, d['conf']), reverse=options.box_sort_order == 'reverse_confidence')
-    return [d for d in dets if d['conf'] is None or d['conf'] >= options.confidence_threshold]
+    if category_thresholds is None:
+        return [d for d in dets if d['conf'] is None or d['conf'] >= options.confidence_threshold]
+    drawn = []
+    for d in dets:
+        threshold = category_thresholds[d['category']]
+        if d['conf'] is None or threshold is None or d['conf'] >= threshold:
+            drawn.append(d)
+    return drawn
 
 
 def label_string(det, label_map):
@@ -399,7 +408,7 @@ def _label_lines(det, label_map, classification_label_map, classification_confid
 
 
 def render_plan(detections, width, height, options, label_map=None, labels=True, classification_label_map=None,
-                classification_confidence_threshold=None):
+                classification_confidence_threshold=None, category_thresholds=None):
     """
     render_detection_bounding_boxes(detections, image, label_map=..., confidence_threshold, thickness, expansion,
     label_font_size, label_font, box_sort_order) for an image of width x height (the RESIZED size) as a RenderPlan: per box
@@ -407,6 +416,7 @@ def render_plan(detections, width, height, options, label_map=None, labels=True,
     labels False: label_map=None of the reference (boxes only).  classification_confidence_threshold None: a box that carries
     classifications is a HostLeg; a number: its classification_label_map=, classification_confidence_threshold= are the
     reference's, and such a box gets a label line per classification and the colour of the best one (classified_label_lines).
+    category_thresholds: drawn_detections' (the reference's confidence_threshold as a dict by category id).
     Raises HostLeg or RenderFailure.
     """
     thickness, expansion, font_size = resolve_sizes(options, width)
@@ -414,7 +424,7 @@ def render_plan(detections, width, height, options, label_map=None, labels=True,
     font = None
     plan = RenderPlan()
     listed = file_detections(detections, options)
-    for det in drawn_detections(detections, options):
+    for det in drawn_detections(detections, options, category_thresholds):
         if det['conf'] is None:
             raise HostLeg('a detection without a confidence')
         try:
@@ -449,7 +459,7 @@ def render_plan(detections, width, height, options, label_map=None, labels=True,
 
 
 def render_with_pil(image, detections, options, label_map=None, labels=True, classification_label_map=None,
-                    classification_confidence_threshold=None):
+                    classification_confidence_threshold=None, category_thresholds=None):
     """the same drawing by PIL's own calls in the reference's order (render_detection_bounding_boxes :673-796,
     draw_bounding_box_on_image :990-1137), IN PLACE on a PIL image of the resized size: the host leg.  The arguments are
     render_plan's; a box with classifications that are not asked for is NotImplementedError.  Raises what PIL raises."""
@@ -457,7 +467,7 @@ def render_with_pil(image, detections, options, label_map=None, labels=True, cla
     width, height = image.size
     thickness, expansion, font_size = resolve_sizes(options, width)
     label_map = _label_map(label_map) if labels else None
-    for det in drawn_detections(detections, options):
+    for det in drawn_detections(detections, options, category_thresholds):
         lines = _label_lines(det, label_map, classification_label_map, classification_confidence_threshold)
         if lines is None:
             raise NotImplementedError('classification labels are not rendered')
