@@ -161,7 +161,7 @@ int mdhip_create(const mdhip_model* model, int device, int dtype,
                  int max_batch, int max_h, int max_w, mdhip_ctx** out);
 /* A context WITHOUT a model, for work that only touches images (marking a results file and writing its review folder load no
  * detector): every image entry point works on it -- mdhip_jpeg_*, mdhip_blur_regions, mdhip_resample_lanczos, mdhip_draw_ops,
- * mdhip_classifier_input, mdhip_thumbnails, mdhip_change_detect (and its hook mdhip_label_regions_on) -- and every entry point that needs the plan or the weights (mdhip_preprocess*,
+ * mdhip_draw_ops_from, mdhip_classifier_input, mdhip_thumbnails, mdhip_change_detect (and its hook mdhip_label_regions_on) -- and every entry point that needs the plan or the weights (mdhip_preprocess*,
  * the forwards, mdhip_nms*, mdhip_read_*, mdhip_calibrate and the fp8 calls, the op / cfg / tuned / fuse / option / graph /
  * timing calls, the mdhip_*_on kernel hooks) returns MDHIP_EINVAL with a text in mdhip_last_error.  It owns nothing on the
  * device until a call needs scratch.  mdhip_destroy frees it. */
@@ -435,6 +435,23 @@ int mdhip_resample_lanczos(mdhip_ctx* ctx, const uint8_t* const* src, const int3
 int mdhip_draw_ops(mdhip_ctx* ctx, uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
                    int n_images, const int32_t* op_image, const int32_t* ops, int n_ops, const uint8_t* patches, int64_t patch_bytes,
                    void* hip_stream);
+
+/* mdhip_draw_ops_from is the fan-out form of mdhip_draw_ops: it MAKES n_dst destination images out of n_src source images,
+ * in one launch, and leaves the sources as they are -- for a source that several renderings draw on (compare_batch_results:
+ * one decoded and resampled file, one rendering per comparison).  A pixel of a destination takes the value of the LAST
+ * operation of the destination's list that covers it, or else its source's pixel (the host model: mdjpeg_draw_from).
+ *   src, widths, heights, pitches    n_src DEVICE images as above; only read
+ *   dst, dst_src, dst_pitches        n_dst DEVICE images: destination i has the size of source dst_src[i] (many destinations
+ *                                    may name one source) and dst_pitches[i] bytes a row (>= 3 * width, any value).  Exactly
+ *                                    the 3 * width bytes of each of its rows are written.  A destination without an
+ *                                    operation is a copy of its source.
+ *   op_image, ops, n_ops, patches, patch_bytes   as for mdhip_draw_ops; op_image[i] names a DESTINATION
+ * MDHIP_EINVAL, with nothing launched and nothing written, for what mdhip_draw_ops refuses, for a dst_src[i] outside
+ * 0 .. n_src - 1, and for a destination that shares a byte (from its first pixel to the end of its last row) with a source or
+ * with another destination.  The call only enqueues; its scratch is that of mdhip_draw_ops: same stream. */
+int mdhip_draw_ops_from(mdhip_ctx* ctx, const uint8_t* const* src, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
+                        int n_src, uint8_t* const* dst, const int32_t* dst_src, const int64_t* dst_pitches, int n_dst, const int32_t* op_image,
+                        const int32_t* ops, int n_ops, const uint8_t* patches, int64_t patch_bytes, void* hip_stream);
 
 /* The input of a species classifier for n detections of a batch, from the images that are in device memory already (the
  * reference: classification/crop_detections.py save_crop writes a crop file per detection, classification/run_classifier.py

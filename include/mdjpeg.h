@@ -155,6 +155,14 @@ int mdjpeg_resample(const uint8_t* src, int32_t width, int32_t height, int64_t p
                     int64_t dst_pitch);
 int mdjpeg_draw(uint8_t* rgb, int32_t width, int32_t height, int64_t pitch, const int32_t* ops, int n_ops, const uint8_t* patches,
                 int64_t patch_bytes);
+/* mdjpeg_draw_from: the host model of mdhip_draw_ops_from, with the same arguments on host memory -- destination i is made
+ * from source dst_src[i] (same size, dst_pitches[i] bytes a row): a pixel is the last operation of the destination's list that
+ * covers it, or else the source's pixel; op_image[i] names a destination.  Only the 3 * width bytes of a destination's rows
+ * are written and no source is.  MDJPEG_EINVAL, and nothing is written, for what mdjpeg_draw refuses, a dst_src[i] or
+ * op_image[i] out of range, and a destination that overlaps a source or another destination. */
+int mdjpeg_draw_from(const uint8_t* const* src, const int32_t* widths, const int32_t* heights, const int64_t* pitches, int n_src,
+                     uint8_t* const* dst, const int32_t* dst_src, const int64_t* dst_pitches, int n_dst, const int32_t* op_image,
+                     const int32_t* ops, int n_ops, const uint8_t* patches, int64_t patch_bytes);
 
 /* ---- classifier input (GPU: mdhip_classifier_input, include/mdhip.h) ---------------------------------------------------- */
 /* The host model of the GPU call for ONE crop, compiled from the header the kernel is compiled from (csrc/resample.h): the

@@ -129,6 +129,9 @@ SYMBOLS = {
                                          C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), _P]),
     'mdhip_draw_ops': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int,
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, _P, C.c_int64, _P]),
+    'mdhip_draw_ops_from': (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int,
+                                      C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int,
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, _P, C.c_int64, _P]),
     'mdhip_classifier_input': (C.c_int, [_P, C.POINTER(mdhip_classifier_crop), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
                                          C.POINTER(C.c_float), _P, _P]),
     'mdhip_thumbnails': (C.c_int, [_P, C.POINTER(mdhip_thumbnail), C.c_int, C.c_int, _P]),

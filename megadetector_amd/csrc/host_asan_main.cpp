@@ -96,6 +96,80 @@ static int preview_matrix() {
     return 0;
 }
 
+// `--draw-from`: mdjpeg_draw_from on heap images of exactly pitch x (height - 1) + 3 x width bytes against a copy followed by
+// mdjpeg_draw -- the sizes whose rows are 3, 15, 21, 99 and 393 bytes, both pitches, a destination 0 .. 3 bytes off its
+// source's alignment, three destinations on one source (one without an operation), a second source of another size in the
+// same call, operations that hang over every edge, lie outside and cover the whole image -- and what it refuses.
+static int draw_from_matrix() {
+    const int sizes[][2] = {{1, 1}, {5, 3}, {7, 5}, {33, 17}, {131, 67}};
+    const int pw = 9, ph = 4;
+    const int64_t patch_bytes = int64_t(pw) * ph * 3 + 7;
+    uint8_t* patch = new uint8_t[size_t(patch_bytes)];
+    for (int64_t i = 0; i < patch_bytes; ++i) patch[i] = uint8_t(200 + i);
+    int runs = 0;
+    for (const auto& sz : sizes)
+        for (int pad : {0, 5})
+            for (int shift = 0; shift < 4; ++shift) {
+                const int W = sz[0], H = sz[1], W2 = 6, H2 = 2;
+                const int64_t pitch = int64_t(W) * 3 + pad, dpitch = int64_t(W) * 3 + (pad ? 5 : 0), pitch2 = int64_t(W2) * 3;
+                const size_t bytes = size_t(pitch) * (H - 1) + size_t(W) * 3, dbytes = size_t(dpitch) * (H - 1) + size_t(W) * 3;
+                const size_t bytes2 = size_t(pitch2) * (H2 - 1) + size_t(W2) * 3;
+                uint8_t* s0 = new uint8_t[bytes];
+                uint8_t* s1 = new uint8_t[bytes2];
+                uint32_t seed = 31u + uint32_t(runs);
+                for (size_t i = 0; i < bytes; ++i) s0[i] = uint8_t((seed = seed * 1664525u + 1013904223u) >> 24);
+                for (size_t i = 0; i < bytes2; ++i) s1[i] = uint8_t((seed = seed * 1664525u + 1013904223u) >> 24);
+                uint8_t* d[4];
+                uint8_t* want[4];
+                for (int m = 0; m < 3; ++m) d[m] = new uint8_t[dbytes + shift], want[m] = new uint8_t[dbytes];
+                d[3] = new uint8_t[bytes2 + shift], want[3] = new uint8_t[bytes2];
+                // destination 0: overlapping rectangles and patches, over every edge; 1: nothing; 2: the whole image, then a patch;
+                // 3 (of the second source): a rectangle wholly outside and one inside
+                const int32_t ops[] = {0, -3, -2, W / 2, H / 2, 0x0000ff, 0, 0,       0, W / 3, H / 3, W + 4, H + 9, 0x00ff00, 0, 0,
+                                       1, -4, H - 2, pw, ph, 7, 0, 0,                 1, W - 2, -1, pw, ph, 0, 0, 0,
+                                       0, W / 2, 0, W / 2, H - 1, 0x123456, 0, 0,     1, W + 1, H + 1, pw, ph, 0, 0, 0,
+                                       0, -100, -100, 100000, 100000, 0xabcdef, 0, 0, 1, 0, 0, pw, ph, 3, 0, 0,
+                                       0, W2, 0, W2 + 5, 3, 0x111111, 0, 0,           0, 1, 1, 3, 1, 0x222222, 0, 0};
+                const int32_t op_image[] = {0, 0, 0, 0, 0, 0, 2, 2, 3, 3};
+                const int first[] = {0, 6, 6, 8}, count[] = {6, 0, 2, 2};
+                const uint8_t* src[2] = {s0, s1};
+                const int32_t ws[2] = {W, W2}, hs[2] = {H, H2};
+                const int64_t ps[2] = {pitch, pitch2};
+                uint8_t* dst[4] = {d[0] + shift, d[1] + shift, d[2] + shift, d[3] + shift};
+                const int32_t dst_src[4] = {0, 0, 0, 1};
+                const int64_t dps[4] = {dpitch, dpitch, dpitch, pitch2};
+                const int rc = mdjpeg_draw_from(src, ws, hs, ps, 2, dst, dst_src, dps, 4, op_image, ops, 10, patch, patch_bytes);
+                bool same = rc == MDJPEG_OK;
+                for (int m = 0; m < 4 && same; ++m) {
+                    const int k = dst_src[m];
+                    for (int y = 0; y < hs[k]; ++y) memcpy(want[m] + size_t(dps[m]) * y, src[k] + size_t(ps[k]) * y, size_t(ws[k]) * 3);
+                    if (mdjpeg_draw(want[m], ws[k], hs[k], dps[m], ops + first[m] * MD_DRAW_OP_WORDS, count[m], patch, patch_bytes) != MDJPEG_OK) same = false;
+                    for (int y = 0; y < hs[k] && same; ++y)
+                        same = memcmp(want[m] + size_t(dps[m]) * y, dst[m] + size_t(dps[m]) * y, size_t(ws[k]) * 3) == 0;
+                }
+                // refused: a destination on its source, a source index and an operation's destination out of range, a patch beyond the buffer
+                uint8_t* on_source[4] = {dst[0], const_cast<uint8_t*>(s0), dst[2], dst[3]};
+                const int64_t on_pitch[4] = {dpitch, pitch, dpitch, pitch2};
+                const int32_t bad_src[4] = {0, 2, 0, 1}, bad_image[] = {0, 0, 0, 0, 0, 0, 2, 4, 3, 3};
+                const int r1 = mdjpeg_draw_from(src, ws, hs, ps, 2, on_source, dst_src, on_pitch, 4, op_image, ops, 10, patch, patch_bytes);
+                const int r2 = mdjpeg_draw_from(src, ws, hs, ps, 2, dst, bad_src, dps, 4, op_image, ops, 10, patch, patch_bytes);
+                const int r3 = mdjpeg_draw_from(src, ws, hs, ps, 2, dst, dst_src, dps, 4, bad_image, ops, 10, patch, patch_bytes);
+                const int r4 = mdjpeg_draw_from(src, ws, hs, ps, 2, dst, dst_src, dps, 4, op_image, ops, 10, patch, int64_t(pw) * ph * 3 + 6);
+                delete[] s0;
+                delete[] s1;
+                for (int m = 0; m < 4; ++m) { delete[] d[m]; delete[] want[m]; }
+                if (!same || r1 != MDJPEG_EINVAL || r2 != MDJPEG_EINVAL || r3 != MDJPEG_EINVAL || r4 != MDJPEG_EINVAL) {
+                    printf("draw-from: %dx%d pad %d shift %d: %d %d %d %d %d %d\n", W, H, pad, shift, rc, int(same), r1, r2, r3, r4);
+                    delete[] patch;
+                    return 9;
+                }
+                ++runs;
+            }
+    delete[] patch;
+    printf("draw-from: %d runs\n", runs);
+    return 0;
+}
+
 // `--classify`: mdjpeg_classifier_input on heap images of exactly pitch x (src_h - 1) + 3 x src_w bytes and an output of
 // exactly 3 x size x size floats -- reducing, enlarging, a single column, an unchanged size, more than one strip, canvases
 // with zeros on every side, the three filters -- so that the sanitizers see any access outside a rectangle or the tensor.
@@ -181,6 +255,7 @@ int main(int argc, char** argv) {
     if (argc == 2 && !strcmp(argv[1], "--thumbnails")) return thumbnails_matrix();
     if (argc == 2 && !strcmp(argv[1], "--classify")) return classify_matrix();
     if (argc == 2 && !strcmp(argv[1], "--preview")) return preview_matrix();
+    if (argc == 2 && !strcmp(argv[1], "--draw-from")) return draw_from_matrix();
     if (argc == 2 && !strcmp(argv[1], "--blur")) return blur_matrix();
     for (int i = 1; i < argc; ++i) {
         FILE* f = fopen(argv[i], "rb");

@@ -160,6 +160,58 @@ int mdjpeg_draw(uint8_t* rgb, int32_t width, int32_t height, int64_t pitch, cons
     return MDJPEG_OK;
 }
 
+// the host model of mdhip_draw_ops_from: every pixel of a destination takes the value of the last operation of the
+// destination's list that covers it, or else its source's pixel; everything is checked before a byte is written
+int mdjpeg_draw_from(const uint8_t* const* src, const int32_t* widths, const int32_t* heights, const int64_t* pitches, int n_src,
+                     uint8_t* const* dst, const int32_t* dst_src, const int64_t* dst_pitches, int n_dst, const int32_t* op_image,
+                     const int32_t* ops, int n_ops, const uint8_t* patches, int64_t patch_bytes) {
+    if (n_dst == 0 && n_ops == 0) return MDJPEG_OK;
+    if (!src || !widths || !heights || !pitches || !dst || !dst_src || !dst_pitches || n_src < 1 || n_dst < 1 || n_ops < 0 ||
+        (n_ops && (!op_image || !ops)) || patch_bytes < 0)
+        return MDJPEG_EINVAL;
+    std::vector<std::vector<int32_t>> lists;
+    lists.resize(size_t(n_dst));
+    for (int i = 0; i < n_ops; ++i) {
+        const int32_t* op = ops + size_t(i) * MD_DRAW_OP_WORDS;
+        if (op_image[i] < 0 || op_image[i] >= n_dst || md_draw_op_bad(op, patch_bytes)) return MDJPEG_EINVAL;
+        if (op[0] == MD_DRAW_PATCH && op[3] > 0 && op[4] > 0 && !patches) return MDJPEG_EINVAL;
+        lists[size_t(op_image[i])].insert(lists[size_t(op_image[i])].end(), op, op + MD_DRAW_OP_WORDS);
+    }
+    const size_t n_win = size_t(n_src) + size_t(n_dst);
+    std::vector<uintptr_t> start(n_win), end(n_win);
+    std::vector<uint8_t> is_dst(n_win);
+    std::vector<int> order(n_win);
+    for (int i = 0; i < n_src; ++i) {
+        if (!src[i] || widths[i] < 1 || heights[i] < 1 || pitches[i] < int64_t(widths[i]) * 3) return MDJPEG_EINVAL;
+        start[size_t(i)] = uintptr_t(src[i]);
+        end[size_t(i)] = start[size_t(i)] + uintptr_t(pitches[i] * (heights[i] - 1) + int64_t(widths[i]) * 3);
+    }
+    for (int m = 0; m < n_dst; ++m) {
+        const int k = dst_src[m];
+        if (k < 0 || k >= n_src || !dst[m] || dst_pitches[m] < int64_t(widths[k]) * 3) return MDJPEG_EINVAL;
+        const size_t j = size_t(n_src) + size_t(m);
+        start[j] = uintptr_t(dst[m]);
+        end[j] = start[j] + uintptr_t(dst_pitches[m] * (heights[k] - 1) + int64_t(widths[k]) * 3);
+        is_dst[j] = 1;
+    }
+    if (md_draw_from_overlap(start.data(), end.data(), is_dst.data(), int(n_win), order.data())) return MDJPEG_EINVAL;
+    for (int m = 0; m < n_dst; ++m) {
+        const int k = dst_src[m];
+        const std::vector<int32_t>& list = lists[size_t(m)];
+        const int n = int(list.size() / MD_DRAW_OP_WORDS);
+        for (int y = 0; y < heights[k]; ++y) {
+            const uint8_t* p = src[k] + int64_t(y) * pitches[k];
+            uint8_t* q = dst[m] + int64_t(y) * dst_pitches[m];
+            for (int x = 0; x < widths[k]; ++x) {
+                uint8_t v[3] = {p[3 * x], p[3 * x + 1], p[3 * x + 2]};
+                md_draw_pixel(list.data(), n, patches, x, y, v);
+                q[3 * x] = v[0], q[3 * x + 1] = v[1], q[3 * x + 2] = v[2];
+            }
+        }
+    }
+    return MDJPEG_OK;
+}
+
 // The host model of mdhip_classifier_input for one crop: tile by tile as the workgroups run it -- the horizontal pass of the
 // canvas rows a tile's vertical taps cover into an 8-bit tile of exactly that size, then the vertical pass and the lookup.
 int mdjpeg_classifier_input(const uint8_t* src, int64_t pitch, int32_t src_w, int32_t src_h, int32_t canvas_w, int32_t canvas_h,

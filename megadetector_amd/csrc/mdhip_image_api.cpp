@@ -905,6 +905,92 @@ int mdhip_draw_ops(mdhip_ctx* ctx, uint8_t* const* images, const int32_t* widths
     return MDHIP_OK;
 }
 
+int mdhip_draw_ops_from(mdhip_ctx* ctx, const uint8_t* const* src, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
+                        int n_src, uint8_t* const* dst, const int32_t* dst_src, const int64_t* dst_pitches, int n_dst, const int32_t* op_image,
+                        const int32_t* ops, int n_ops, const uint8_t* patches, int64_t patch_bytes, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    if (n_dst == 0 && n_ops == 0) return MDHIP_OK;
+    if (!src || !widths || !heights || !pitches || !dst || !dst_src || !dst_pitches || (n_ops && (!op_image || !ops)))
+        return fail(ctx, MDHIP_EINVAL, "src/widths/heights/pitches/dst/dst_src/dst_pitches/op_image/ops is NULL");
+    if (n_src < 1 || n_src > 65535 || n_dst < 1 || n_dst > 65535 || n_ops < 0 || patch_bytes < 0 || patch_bytes > 0x7fff0000LL)
+        return fail(ctx, MDHIP_EINVAL, "n_src = %d, n_dst = %d, n_ops = %d, patch_bytes = %lld", n_src, n_dst, n_ops, (long long)patch_bytes);
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // everything is checked before anything is launched: the operations as mdhip_draw_ops checks them, then the windows
+    std::vector<int> count((size_t)n_dst, 0);
+    bool any_patch = false;
+    for (int i = 0; i < n_ops; ++i) {
+        const int m = op_image[i];
+        if (m < 0 || m >= n_dst) return fail(ctx, MDHIP_EINVAL, "operation %d: destination %d of %d", i, m, n_dst);
+        const int32_t* op = ops + (size_t)i * MD_DRAW_OP_WORDS;
+        if (md_draw_op_bad(op, patch_bytes))
+            return fail(ctx, MDHIP_EINVAL, "operation %d: kind %d, or a patch of %dx%d pixels at byte %d of %lld", i, op[0], op[3], op[4], op[5],
+                        (long long)patch_bytes);
+        any_patch |= op[0] == MD_DRAW_PATCH && op[3] > 0 && op[4] > 0;
+        ++count[m];
+    }
+    if (any_patch && (!patches || !is_device_ptr(patches))) return fail(ctx, MDHIP_EINVAL, "patches: NULL or a host pointer");
+    const size_t n_win = (size_t)n_src + (size_t)n_dst;
+    std::vector<uintptr_t> start(n_win), end(n_win);
+    std::vector<uint8_t> is_dst(n_win);
+    std::vector<int> order(n_win);
+    for (int i = 0; i < n_src; ++i) {
+        long long extent = 0;
+        if (int rc = check_window(ctx, "source", i, widths[i], heights[i], pitches[i], 65535, &extent)) return rc;
+        if (!src[i] || !is_device_ptr(src[i])) return fail(ctx, MDHIP_EINVAL, "source %d: NULL or a host pointer -- images must be device memory", i);
+        start[(size_t)i] = (uintptr_t)src[i], end[(size_t)i] = (uintptr_t)src[i] + (uintptr_t)extent, is_dst[(size_t)i] = 0;
+    }
+    std::vector<DrawFrom> recs((size_t)n_dst);
+    int first = 0, max_row_bytes = 0, max_h = 0;
+    for (int m = 0; m < n_dst; ++m) {
+        const int k = dst_src[m];
+        if (k < 0 || k >= n_src) return fail(ctx, MDHIP_EINVAL, "destination %d: source %d of %d", m, k, n_src);
+        long long extent = 0;
+        if (int rc = check_window(ctx, "destination", m, widths[k], heights[k], dst_pitches[m], 65535, &extent)) return rc;
+        if (!dst[m] || !is_device_ptr(dst[m]))
+            return fail(ctx, MDHIP_EINVAL, "destination %d: NULL or a host pointer -- images must be device memory", m);
+        const size_t j = (size_t)n_src + (size_t)m;
+        start[j] = (uintptr_t)dst[m], end[j] = (uintptr_t)dst[m] + (uintptr_t)extent, is_dst[j] = 1;
+        DrawFrom& d = recs[(size_t)m];
+        memset(&d, 0, sizeof(d));
+        d.src = src[k], d.dst = dst[m], d.src_pitch = pitches[k], d.dst_pitch = dst_pitches[m];
+        d.row_bytes = widths[k] * 3, d.height = heights[k];
+        d.x0 = widths[k], d.y0 = heights[k], d.x1 = -1, d.y1 = -1;
+        d.op_first = first, d.op_count = count[m];
+        first += count[m];
+        max_row_bytes = std::max(max_row_bytes, d.row_bytes);
+        max_h = std::max(max_h, d.height);
+    }
+    if (md_draw_from_overlap(start.data(), end.data(), is_dst.data(), (int)n_win, order.data()))
+        return fail(ctx, MDHIP_EINVAL, "a destination overlaps a source or another destination");
+    std::vector<int32_t> sorted((size_t)n_ops * MD_DRAW_OP_WORDS);
+    std::vector<int> fill((size_t)n_dst, 0);
+    for (int i = 0; i < n_ops; ++i) {
+        const int m = op_image[i];
+        DrawFrom& d = recs[(size_t)m];
+        const int32_t* op = ops + (size_t)i * MD_DRAW_OP_WORDS;
+        memcpy(sorted.data() + (size_t)(d.op_first + fill[m]++) * MD_DRAW_OP_WORDS, op, sizeof(int32_t) * MD_DRAW_OP_WORDS);
+        // what the operation covers, clipped to the image (64-bit: a corner plus a size may pass 2^31)
+        const long long w = d.row_bytes / 3, h = d.height;
+        long long a = op[1], b = op[2], c = op[3], e = op[4];
+        if (op[0] == MD_DRAW_PATCH) c = a + c - 1, e = b + e - 1;
+        a = std::max(a, 0LL), b = std::max(b, 0LL);
+        c = std::min(c, w - 1), e = std::min(e, h - 1);
+        if (c < a || e < b) continue;
+        d.x0 = std::min(d.x0, (int)a), d.y0 = std::min(d.y0, (int)b), d.x1 = std::max(d.x1, (int)c), d.y1 = std::max(d.y1, (int)e);
+    }
+    ScratchLayout lay;
+    const size_t o_recs = lay.take(recs.size() * sizeof(DrawFrom));
+    const size_t o_ops = lay.take(std::max(sorted.size(), (size_t)1) * sizeof(int32_t));
+    if (int rc = ctx->draw.reserve(ctx, lay.size)) return rc;
+    uint8_t* base = (uint8_t*)ctx->draw.p;
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_recs, recs.data(), recs.size() * sizeof(DrawFrom), hipMemcpyHostToDevice, s));
+    if (!sorted.empty())
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_ops, sorted.data(), sorted.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, launch_draw_ops_from((const DrawFrom*)(base + o_recs), n_dst, max_row_bytes, max_h, (const int32_t*)(base + o_ops), patches, s));
+    return MDHIP_OK;
+}
+
 int mdhip_classifier_input(mdhip_ctx* ctx, const mdhip_classifier_crop* crops, int n, int size, int filter, const float mean[3],
                            const float std[3], float* out, void* hip_stream) {
     if (!ctx) return MDHIP_EINVAL;

@@ -602,6 +602,17 @@ struct DrawImage {
 hipError_t launch_resample_rows(const ResampleRows* descs, int n, int max_blocks, const int32_t* table, hipStream_t s);
 hipError_t launch_resample_columns(const ResampleColumns* descs, int n, int max_row_bytes, int max_out_h, const int32_t* table, hipStream_t s);
 hipError_t launch_draw_ops(const DrawImage* images, int n, int max_w, int max_h, const int32_t* ops, const uint8_t* patches, hipStream_t s);
+// The fan-out draw: a destination is its source's pixels under the destination's operations; the source is only read
+struct DrawFrom {
+    const uint8_t* src;
+    uint8_t*  dst;
+    long long src_pitch, dst_pitch;
+    int row_bytes, height;             // 3 * width, and the rows
+    int x0, y0, x1, y1;                // what the operations cover, clipped to the image; inclusive; x1 < x0: nothing
+    int op_first, op_count;
+};
+hipError_t launch_draw_ops_from(const DrawFrom* images, int n, int max_row_bytes, int max_h, const int32_t* ops, const uint8_t* patches,
+                                hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
 // Classifier input (classify_kernels.cpp): n crops -> fp32 [n][3][S][S], one record per crop (blockIdx.y), one launch.

@@ -17,6 +17,10 @@
 //                            row); the weights are the same for the whole workgroup, so they come through the scalar cache.
 //   draw_ops_kernel          a lane owns one pixel of the rectangle its image's operations cover and takes the value of
 //                            the last operation that covers it (md_draw_pixel): order-exact without launch rounds.
+//   draw_ops_from_kernel     the fan-out draw (mdhip_draw_ops_from) moves every byte of every destination: a lane owns the
+//                            16 bytes of a destination row that share an aligned 16-byte line -- one dwordx4 load (of any
+//                            alignment) and one aligned dwordx4 store; the runs at a row's two ends go byte by byte -- and
+//                            walks the operations only for the pixels of its run inside the operations' bounding box.
 
 #include <hip/hip_runtime.h>
 
@@ -29,6 +33,8 @@ namespace {
 
 constexpr int LANES = 256;
 constexpr int DRAW_X = 64, DRAW_Y = LANES / DRAW_X;
+constexpr int FROM_RUN = 16;                                             // bytes of a destination row a lane moves
+constexpr int FROM_X = 64, FROM_Y = LANES / FROM_X;                      // a wave moves 1 KiB of one row
 
 static_assert(MD_RESAMPLE_LDS_BYTES <= 64 * 1024, "static LDS of a workgroup");
 
@@ -115,6 +121,70 @@ __global__ __launch_bounds__(LANES) void draw_ops_kernel(const DrawImage* __rest
     p[0] = rgb[0], p[1] = rgb[1], p[2] = rgb[2];
 }
 
+struct __attribute__((packed, aligned(1))) FromRun { uint32_t w0, w1, w2, w3; };  // 16 bytes of a row wherever they lie
+
+// byte k (0 .. 15) of a run held in four named dwords (an array indexed by k would live in scratch memory)
+__device__ __forceinline__ void from_put(uint32_t& w0, uint32_t& w1, uint32_t& w2, uint32_t& w3, int k, uint32_t v) {
+    if (k < 0 || k >= FROM_RUN) return;
+    const int sh = (k & 3) * 8, i = k >> 2;
+    const uint32_t keep = ~(0xffu << sh), bits = v << sh;
+    w0 = i == 0 ? (w0 & keep) | bits : w0;
+    w1 = i == 1 ? (w1 & keep) | bits : w1;
+    w2 = i == 2 ? (w2 & keep) | bits : w2;
+    w3 = i == 3 ? (w3 & keep) | bits : w3;
+}
+
+// the bytes first .. first + 3 of a run that lie in lo .. hi - 1 of the row, loaded into / stored from one dword
+__device__ __forceinline__ uint32_t from_load4(const uint8_t* row, int first, int lo, int hi) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (first + j >= lo && first + j < hi) w |= (uint32_t)row[first + j] << (8 * j);
+    return w;
+}
+
+__device__ __forceinline__ void from_store4(uint8_t* row, int first, int lo, int hi, uint32_t w) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (first + j >= lo && first + j < hi) row[first + j] = (uint8_t)(w >> (8 * j));
+}
+
+__global__ __launch_bounds__(LANES) void draw_ops_from_kernel(const DrawFrom* __restrict__ images, const int32_t* __restrict__ ops,
+                                                              const uint8_t* __restrict__ patches) {
+    const DrawFrom d = images[blockIdx.z];
+    const int y = (int)blockIdx.y * FROM_Y + (int)(threadIdx.x / FROM_X);
+    if (y >= d.height) return;
+    const uint8_t* p = d.src + (long long)y * d.src_pitch;
+    uint8_t* q = d.dst + (long long)y * d.dst_pitch;
+    // run c holds bytes 16 c - lead .. 16 c - lead + 15 of the row, so that a whole run is one aligned 16-byte store
+    const int lead = (int)((uintptr_t)q & (FROM_RUN - 1));
+    const int b0 = ((int)blockIdx.x * FROM_X + (int)(threadIdx.x % FROM_X)) * FROM_RUN - lead;
+    if (b0 >= d.row_bytes) return;
+    const int lo = max(b0, 0), hi = min(b0 + FROM_RUN, d.row_bytes);     // the run's bytes of the row: lo .. hi - 1
+    const bool whole = hi - lo == FROM_RUN;
+    uint32_t w0, w1, w2, w3;
+    if (whole) {
+        const FromRun v = *reinterpret_cast<const FromRun*>(p + b0);     // (all 16 bytes belong to the row; any alignment)
+        w0 = v.w0, w1 = v.w1, w2 = v.w2, w3 = v.w3;
+    } else {
+        w0 = from_load4(p, b0, lo, hi), w1 = from_load4(p, b0 + 4, lo, hi), w2 = from_load4(p, b0 + 8, lo, hi), w3 = from_load4(p, b0 + 12, lo, hi);
+    }
+    if (d.x1 >= d.x0 && y >= d.y0 && y <= d.y1) {                        // the operations are looked at inside their box only
+        const int xa = max(lo / 3, d.x0), xb = min((hi - 1) / 3, d.x1);
+        for (int x = xa; x <= xb; ++x) {
+            uint8_t rgb[3];
+            if (!md_draw_pixel(ops + (long long)d.op_first * MD_DRAW_OP_WORDS, d.op_count, patches, x, y, rgb)) continue;
+            const int k = x * 3 - b0;                                    // (a pixel may begin before the run or end behind it)
+            from_put(w0, w1, w2, w3, k, rgb[0]), from_put(w0, w1, w2, w3, k + 1, rgb[1]), from_put(w0, w1, w2, w3, k + 2, rgb[2]);
+        }
+    }
+    if (whole) {
+        *reinterpret_cast<uint4*>(q + b0) = make_uint4(w0, w1, w2, w3);
+    } else {
+        from_store4(q, b0, lo, hi, w0), from_store4(q, b0 + 4, lo, hi, w1), from_store4(q, b0 + 8, lo, hi, w2), from_store4(q, b0 + 12, lo, hi, w3);
+    }
+}
+
 }  // namespace
 
 hipError_t launch_resample_rows(const ResampleRows* descs, int n, int max_blocks, const int32_t* table, hipStream_t s) {
@@ -133,6 +203,16 @@ hipError_t launch_resample_columns(const ResampleColumns* descs, int n, int max_
 hipError_t launch_draw_ops(const DrawImage* images, int n, int max_w, int max_h, const int32_t* ops, const uint8_t* patches, hipStream_t s) {
     if (n < 1 || max_w < 1 || max_h < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(draw_ops_kernel, dim3((unsigned)(max_w + DRAW_X - 1) / DRAW_X, (unsigned)(max_h + DRAW_Y - 1) / DRAW_Y, (unsigned)n),
+                       dim3(LANES), 0, s, images, ops, patches);
+    return hipGetLastError();
+}
+
+hipError_t launch_draw_ops_from(const DrawFrom* images, int n, int max_row_bytes, int max_h, const int32_t* ops, const uint8_t* patches,
+                                hipStream_t s) {
+    if (n < 1 || max_row_bytes < 1 || max_h < 1) return hipErrorInvalidValue;
+    // a row of b bytes that begins `lead` (0 .. 15) bytes into a 16-byte line spans (lead + b + 15) / 16 runs
+    const unsigned runs = ((unsigned)max_row_bytes + 2 * FROM_RUN - 2) / FROM_RUN;
+    hipLaunchKernelGGL(draw_ops_from_kernel, dim3((runs + FROM_X - 1) / FROM_X, (unsigned)(max_h + FROM_Y - 1) / FROM_Y, (unsigned)n),
                        dim3(LANES), 0, s, images, ops, patches);
     return hipGetLastError();
 }

@@ -25,6 +25,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <vector>
 
 #if defined(__HIPCC__)
@@ -195,6 +196,23 @@ MDR_HD static inline int md_draw_pixel(const int32_t* ops, int n, const uint8_t*
         const uint8_t* p = patches + op[5] + (dy * op[3] + dx) * 3;
         rgb[0] = p[0], rgb[1] = p[1], rgb[2] = p[2];
         return 1;
+    }
+    return 0;
+}
+
+// The fan-out draw (mdhip_draw_ops_from / mdjpeg_draw_from): destinations are made from sources that stay as they are, so
+// no destination may share a byte with a source or with another destination.  start[i] .. end[i] (exclusive) are the bytes
+// of window i from its first pixel to the end of its last row, is_dst[i] whether it is written.  order: scratch of n ints.
+// 1 when a destination overlaps any other window; sources may overlap each other.
+static inline int md_draw_from_overlap(const uintptr_t* start, const uintptr_t* end, const uint8_t* is_dst, int n, int* order) {
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::sort(order, order + n, [start](int a, int b) { return start[a] < start[b]; });
+    uintptr_t end_any = 0, end_dst = 0;                                   // the furthest end of the windows / destinations so far
+    for (int k = 0; k < n; ++k) {
+        const int i = order[k];
+        if (start[i] < (is_dst[i] ? end_any : end_dst)) return 1;
+        if (end[i] > end_any) end_any = end[i];
+        if (is_dst[i] && end[i] > end_dst) end_dst = end[i];
     }
     return 0;
 }

@@ -6,6 +6,7 @@ visualize_video_output.py.  device_decode.py brings files into device memory; th
   blur_rects      ONE mdhip_blur_regions call for the rectangles of a batch of images
   draw_plans      ONE mdhip_draw_ops call for the preview.RenderPlan of each image, the label patches of all of them uploaded
                   once in one buffer (pack_ops)
+  draw_plans_from ONE mdhip_draw_ops_from call that makes every rendering of a chunk from the shared images they draw on
   blur_and_draw   the two for a chunk of jobs
   read_encoded    an encoder call into a guessed buffer, once more with the size the call asked for, and the read-back
   encode_sampled  ONE mdhip_jpeg_encode_sampled call, jpeg_host.sampled_file around each scan
@@ -103,6 +104,24 @@ def draw_plans(ctx, ptrs, sizes, plans, device, stream=0, clock=None):
     with clock('draw') if clock is not None else nullcontext():
         patches = torch.from_numpy(np.frombuffer(bytes(packed) or b'\0', np.uint8).copy()).to(device)
         ctx.draw_ops(ptrs, sizes, [w * 3 for w, _ in sizes], op_image, ops, patches.data_ptr(), len(packed), stream=stream)
+    return True
+
+
+def draw_plans_from(ctx, src_ptrs, sizes, dst_ptrs, dst_src, plans, device, stream=0, clock=None):
+    """ONE mdhip_draw_ops_from call that MAKES destination k (rows of 3 * width bytes at dst_ptrs[k]) from source dst_src[k]
+    (src_ptrs, sizes (width, height), rows of 3 * width bytes; only read) under plans[k], after ONE upload of the packed
+    patches on torch's current stream (the caller makes `stream` that one): the fan-out of a source that several renderings
+    draw on.  A destination whose plan holds no operation is a copy.  No call without destinations.  clock: a Clock that times
+    the upload and the call as 'draw'.  -> whether the call was made"""
+    import numpy as np
+    import torch
+    if not dst_ptrs:
+        return False
+    op_image, ops, packed = pack_ops(plans)
+    with clock('draw') if clock is not None else nullcontext():
+        patches = torch.from_numpy(np.frombuffer(bytes(packed) or b'\0', np.uint8).copy()).to(device)
+        ctx.draw_ops_from(src_ptrs, sizes, [w * 3 for w, _ in sizes], dst_ptrs, dst_src, [sizes[k][0] * 3 for k in dst_src], op_image, ops,
+                          patches.data_ptr(), len(packed), stream=stream)
     return True
 
 

@@ -510,6 +510,31 @@ class HipContext:
         self._check(self.lib.mdhip_draw_ops(self.h, p, ws, hs, pt, n, oi, flat, m,
                                             C.c_void_p(int(patches_ptr) or None), int(patch_bytes), C.c_void_p(stream)), 'mdhip_draw_ops')
 
+    def draw_ops_from(self, src_ptrs, sizes, src_pitches, dst_ptrs, dst_src, dst_pitches, op_image, ops, patches_ptr=0, patch_bytes=0,
+                      stream=0, check=True):
+        """
+        The fan-out draw (include/mdhip.h: mdhip_draw_ops_from): destination i becomes the pixels of source dst_src[i] under
+        the operations whose op_image names i, in one launch for all destinations; the sources are only read and a
+        destination without operations is a copy.  ops, patches_ptr, patch_bytes: as for draw_ops.  Only enqueues.
+        check=False returns the library's code instead of raising.
+        """
+        n, k, m = len(src_ptrs), len(dst_ptrs), len(ops)
+        if not (len(sizes) == len(src_pitches) == n) or not (len(dst_src) == len(dst_pitches) == k) or len(op_image) != m:
+            raise ValueError('one entry per source, per destination and per operation is needed in their lists')
+        if k == 0 and m == 0:
+            return 0
+        p, ws, hs, pt = _window_arrays(src_ptrs, sizes, src_pitches)
+        dp = C.cast((C.c_void_p * max(k, 1))(*[int(v) for v in dst_ptrs]), C.POINTER(C.c_void_p))
+        ds = (C.c_int32 * max(k, 1))(*[int(v) for v in dst_src])
+        dpt = (C.c_int64 * max(k, 1))(*[int(v) for v in dst_pitches])
+        oi = (C.c_int32 * max(m, 1))(*[int(v) for v in op_image])
+        flat = (C.c_int32 * max(8 * m, 1))(*[int(v) for q in ops for v in q])
+        rc = self.lib.mdhip_draw_ops_from(self.h, p, ws, hs, pt, n, dp, ds, dpt, k, oi, flat, m,
+                                          C.c_void_p(int(patches_ptr) or None), int(patch_bytes), C.c_void_p(stream))
+        if check:
+            self._check(rc, 'mdhip_draw_ops_from')
+        return rc
+
     def change_detect(self, ptrs, sizes, blurred_ptrs, ready, pairs, options, mask_ptrs=None, stream=0):
         """
         Change detection between device images (include/mdhip.h: mdhip_change_detect).

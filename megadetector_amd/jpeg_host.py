@@ -78,6 +78,9 @@ SYMBOLS = {
     'mdjpeg_blur_weights': (C.c_int, [C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     'mdjpeg_resample': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64]),
     'mdjpeg_draw': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int64]),
+    'mdjpeg_draw_from': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int,
+                                   C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int,
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int64]),
     'mdjpeg_classifier_input': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p]),
     'mdjpeg_classifier_plan': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
@@ -558,6 +561,28 @@ def draw_ops(rgb, ops, patches=b''):
     pbuf = np.frombuffer(bytes(patches), np.uint8) if not isinstance(patches, np.ndarray) else np.ascontiguousarray(patches, np.uint8)
     return load().mdjpeg_draw(rgb.ctypes.data, w, h, pitch, flat.ctypes.data_as(C.POINTER(C.c_int32)), len(flat),
                               pbuf.ctypes.data if pbuf.size else None, pbuf.size)
+
+
+def draw_ops_from(src_ptrs, sizes, src_pitches, dst_ptrs, dst_src, dst_pitches, op_image, ops, patches=b''):
+    """
+    The fan-out draw on host memory (mdjpeg_draw_from: the host model of mdhip_draw_ops_from), with the arguments of
+    hip_backend's draw_ops_from: ADDRESSES of the sources (with their (width, height) and bytes a row) and of the destinations
+    (each with the index of its source and its bytes a row), the destination of every operation and the operations' rows
+    of 8 int32.  The caller keeps the memory alive.  patches: the bytes the patch operations point into.  Returns the
+    library's code.
+    """
+    n, k = len(src_ptrs), len(dst_ptrs)
+    flat = np.ascontiguousarray(np.asarray(ops, dtype=np.int32).reshape(-1, 8))
+    oi = np.ascontiguousarray(np.asarray(op_image, dtype=np.int32).reshape(-1))
+    if not (len(sizes) == len(src_pitches) == n) or not (len(dst_src) == len(dst_pitches) == k) or len(oi) != len(flat):
+        raise ValueError('one entry per source, per destination and per operation is needed in their lists')
+    pbuf = np.frombuffer(bytes(patches), np.uint8) if not isinstance(patches, np.ndarray) else np.ascontiguousarray(patches, np.uint8)
+    i32 = C.POINTER(C.c_int32)
+    return load().mdjpeg_draw_from((C.c_void_p * max(n, 1))(*[int(v) for v in src_ptrs]), (C.c_int32 * max(n, 1))(*[int(s[0]) for s in sizes]),
+                                   (C.c_int32 * max(n, 1))(*[int(s[1]) for s in sizes]), (C.c_int64 * max(n, 1))(*[int(v) for v in src_pitches]), n,
+                                   (C.c_void_p * max(k, 1))(*[int(v) for v in dst_ptrs]), (C.c_int32 * max(k, 1))(*[int(v) for v in dst_src]),
+                                   (C.c_int64 * max(k, 1))(*[int(v) for v in dst_pitches]), k, oi.ctypes.data_as(i32), flat.ctypes.data_as(i32),
+                                   len(flat), pbuf.ctypes.data if pbuf.size else None, pbuf.size)
 
 
 def classifier_input(rgb, canvas, size, filter=0, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):

@@ -203,10 +203,12 @@ def text_size(font, s):
     return w, h
 
 
-def box_color(category):
-    """visualization_utils.py:984-988 (name, (r, g, b))"""
+def box_color(category, colormap=None):
+    """visualization_utils.py:978-988 (name, (r, g, b)); colormap: None for DEFAULT_COLORS, or a list of colour names -- the
+    class index is taken % len(colormap), and a class of None takes colormap[1] as there (IndexError for a list of one)"""
     from PIL import ImageColor
-    name = PREVIEW_COLORS[1] if category is None else PREVIEW_COLORS[int(category) % len(PREVIEW_COLORS)]
+    colors = PREVIEW_COLORS if colormap is None else colormap
+    name = colors[1] if category is None else colors[int(category) % len(colors)]
     return name, ImageColor.getrgb(name)[:3]
 
 
@@ -216,16 +218,22 @@ def drawn_detections(detections, options, category_thresholds=None):
     threshold (a confidence of None is always drawn).  category_thresholds: None, or the reference's confidence_threshold as
     a dict (:677-680) -- category id -> threshold, consulted instead of options.confidence_threshold; a category it lacks is
     KeyError as there, and a threshold of None draws every box of the category"""
+    return [d for _, d in _drawn_with_positions(detections, options, category_thresholds)]
+
+
+def _drawn_with_positions(detections, options, category_thresholds=None):
+    """drawn_detections with, for every drawn detection, the reference's i_detection (:673): its position in the list the
+    loop runs over, which is the SORTED list when there is a sort order"""
     dets = list(file_detections(detections, options))
     if options.box_sort_order is not None:
         dets = sorted(dets, key=lambda d: (d['conf'] is not None, d['conf']), reverse=options.box_sort_order == 'reverse_confidence')
     if category_thresholds is None:
-        return [d for d in dets if d['conf'] is None or d['conf'] >= options.confidence_threshold]
+        return [(i, d) for i, d in enumerate(dets) if d['conf'] is None or d['conf'] >= options.confidence_threshold]
     drawn = []
-    for d in dets:
+    for i, d in enumerate(dets):
         threshold = category_thresholds[d['category']]
         if d['conf'] is None or threshold is None or d['conf'] >= threshold:
-            drawn.append(d)
+            drawn.append((i, d))
     return drawn
 
 
@@ -285,12 +293,16 @@ def classified_label_lines(det, label_map, classification_label_map,
     return strings, clss
 
 
-def stacked_labels(font, strings, left, top, bottom, im_height):
-    """draw_bounding_box_on_image :1052-1131 for the label lines of one box, left- and top-aligned, in the order they are drawn:
-    the last line first, at the bottom, every further line int(text_height + 2 * margin) higher -- above the box, below it when
-    that leaves the image at the top, inside it when below leaves the image too.  Yields (the padded string, its margin, the
-    corners (x0, y0), (x1, y1) of its filled rectangle (inclusive), where its text goes)."""
+def stacked_labels(font, strings, left, top, bottom, im_height, vtextalign='top'):
+    """draw_bounding_box_on_image :1052-1131 for the label lines of one box, left-aligned, in the order they are drawn:
+    the last line first, at the bottom, every further line int(text_height + 2 * margin) higher.  vtextalign 'top'
+    (VTEXTALIGN_TOP): above the box, below it when that leaves the image at the top, inside it at the top when below leaves
+    the image too.  'bottom' (VTEXTALIGN_BOTTOM, :1112-1116): below the box, above it when that leaves the image at the
+    bottom, inside it at the bottom when above leaves the image too.  Yields (the padded string, its margin, the corners
+    (x0, y0), (x1, y1) of its filled rectangle (inclusive), where its text goes)."""
     import numpy as np
+    if vtextalign not in ('top', 'bottom'):
+        raise ValueError('Unrecognized vertical text alignment {}'.format(vtextalign))
     total_height = (1 + 2 * 0.05) * sum(text_size(font, s)[1] for s in strings)     # :1055 (of the strings WITHOUT their padding)
     for i_str, s in enumerate(strings[::-1]):
         if len(s) == 0:                                                              # :1061
@@ -298,11 +310,18 @@ def stacked_labels(font, strings, left, top, bottom, im_height):
         s = ' ' + s + ' '
         text_width, text_height = text_size(font, s)
         margin = int(np.ceil(0.05 * text_height))
-        text_bottom = top
-        if (text_bottom - total_height) < 0:
+        if vtextalign == 'top':
+            text_bottom = top
+            if (text_bottom - total_height) < 0:
+                text_bottom = bottom + total_height
+                if text_bottom > im_height:
+                    text_bottom = top + total_height
+        else:
             text_bottom = bottom + total_height
             if text_bottom > im_height:
-                text_bottom = top + total_height
+                text_bottom = top
+                if (text_bottom - total_height) < 0:
+                    text_bottom = bottom
         text_bottom = int(text_bottom) - i_str * (int(text_height + (2 * margin)))
         text_left = int(left)
         yield (s, margin, (text_left, (text_bottom - text_height) - (2 * margin)), (text_left + text_width, text_bottom),
@@ -397,18 +416,34 @@ class RenderPlan:
         return self
 
 
-def _label_lines(det, label_map, classification_label_map, classification_confidence_threshold):
+def _label_lines(det, label_map, classification_label_map, classification_confidence_threshold, custom_string=None,
+                 unlabelled_classifications=False):
     """(the label lines of one drawn detection, the class its colour is of); None for a detection with classifications when
-    they are not asked for (no threshold) or cannot be labelled (no label map)"""
-    if classification_confidence_threshold is None or label_map is None:
+    they are not asked for (no threshold) or cannot be labelled (no label map) -- unless unlabelled_classifications, which
+    then does what the reference does without a label map: no classification line, and the colour of the best
+    classification it looked at.  custom_string: render_detection_bounding_boxes :705-709, appended to the first line with
+    a blank when it is not empty"""
+    if classification_confidence_threshold is None or (label_map is None and not unlabelled_classifications):
         if 'classifications' in det and len(det['classifications']) > 0:
             return None
-        return [label_string(det, label_map)], det['category']
-    return classified_label_lines(det, label_map, classification_label_map, classification_confidence_threshold)
+        strings, clss = [label_string(det, label_map)], det['category']
+    else:
+        strings, clss = classified_label_lines(det, label_map, classification_label_map, classification_confidence_threshold)
+    if custom_string is not None and len(custom_string) > 0:
+        strings[0] += ' ' + custom_string
+    return strings, clss
+
+
+def _check_custom_strings(custom_strings, listed):
+    # render_detection_bounding_boxes :651-654
+    if custom_strings is not None:
+        assert len(custom_strings) == len(listed), \
+            '{} custom strings provided for {} detections'.format(len(custom_strings), len(listed))
 
 
 def render_plan(detections, width, height, options, label_map=None, labels=True, classification_label_map=None,
-                classification_confidence_threshold=None, category_thresholds=None):
+                classification_confidence_threshold=None, *, colormap=None, vtextalign='top', custom_strings=None,
+                unlabelled_classifications=False, category_thresholds=None):
     """
     render_detection_bounding_boxes(detections, image, label_map=..., confidence_threshold, thickness, expansion,
     label_font_size, label_font, box_sort_order) for an image of width x height (the RESIZED size) as a RenderPlan: per box
@@ -417,6 +452,10 @@ def render_plan(detections, width, height, options, label_map=None, labels=True,
     classifications is a HostLeg; a number: its classification_label_map=, classification_confidence_threshold= are the
     reference's, and such a box gets a label line per classification and the colour of the best one (classified_label_lines).
     category_thresholds: drawn_detections' (the reference's confidence_threshold as a dict by category id).
+    colormap: box_color's; vtextalign: stacked_labels'; custom_strings: None, or one string per detection of the list, indexed
+    as the reference indexes it -- by the position in the list its loop runs over, which is the list sorted by confidence
+    when there is a sort order, not the file's; unlabelled_classifications: _label_lines'.  What follows
+    classification_confidence_threshold is given by name (category_thresholds stays the last argument).
     Raises HostLeg or RenderFailure.
     """
     thickness, expansion, font_size = resolve_sizes(options, width)
@@ -424,15 +463,17 @@ def render_plan(detections, width, height, options, label_map=None, labels=True,
     font = None
     plan = RenderPlan()
     listed = file_detections(detections, options)
-    for det in drawn_detections(detections, options, category_thresholds):
+    _check_custom_strings(custom_strings, listed)
+    for position, det in _drawn_with_positions(detections, options, category_thresholds):
         if det['conf'] is None:
             raise HostLeg('a detection without a confidence')
         try:
-            lines = _label_lines(det, label_map, classification_label_map, classification_confidence_threshold)
+            lines = _label_lines(det, label_map, classification_label_map, classification_confidence_threshold,
+                                 None if custom_strings is None else custom_strings[position], unlabelled_classifications)
             if lines is None:
                 raise HostLeg('classification labels')
             strings, clss = lines
-            color_name, rgb = box_color(clss)
+            color_name, rgb = box_color(clss, colormap)
         except (TypeError, ValueError) as e:
             raise RenderFailure(str(e))
         left, top, right, bottom = box_edges(det['bbox'], width, height, expansion)
@@ -443,7 +484,7 @@ def render_plan(detections, width, height, options, label_map=None, labels=True,
             continue
         if font is None:
             font = load_font(options.label_font, font_size)
-        for padded, margin, (x0, y0), (x1, y1), _ in stacked_labels(font, strings, left, top, bottom, height):
+        for padded, margin, (x0, y0), (x1, y1), _ in stacked_labels(font, strings, left, top, bottom, height, vtextalign):
             bbox = font.getbbox(padded)
             if bbox[0] < 0 or bbox[1] < 0:
                 raise HostLeg('ink of {!r} may leave its label'.format(padded))
@@ -459,7 +500,8 @@ def render_plan(detections, width, height, options, label_map=None, labels=True,
 
 
 def render_with_pil(image, detections, options, label_map=None, labels=True, classification_label_map=None,
-                    classification_confidence_threshold=None, category_thresholds=None):
+                    classification_confidence_threshold=None, *, colormap=None, vtextalign='top', custom_strings=None,
+                    unlabelled_classifications=False, category_thresholds=None):
     """the same drawing by PIL's own calls in the reference's order (render_detection_bounding_boxes :673-796,
     draw_bounding_box_on_image :990-1137), IN PLACE on a PIL image of the resized size: the host leg.  The arguments are
     render_plan's; a box with classifications that are not asked for is NotImplementedError.  Raises what PIL raises."""
@@ -467,19 +509,21 @@ def render_with_pil(image, detections, options, label_map=None, labels=True, cla
     width, height = image.size
     thickness, expansion, font_size = resolve_sizes(options, width)
     label_map = _label_map(label_map) if labels else None
-    for det in drawn_detections(detections, options, category_thresholds):
-        lines = _label_lines(det, label_map, classification_label_map, classification_confidence_threshold)
+    _check_custom_strings(custom_strings, file_detections(detections, options))
+    for position, det in _drawn_with_positions(detections, options, category_thresholds):
+        lines = _label_lines(det, label_map, classification_label_map, classification_confidence_threshold,
+                             None if custom_strings is None else custom_strings[position], unlabelled_classifications)
         if lines is None:
             raise NotImplementedError('classification labels are not rendered')
         strings, clss = lines
-        color_name, _ = box_color(clss)
+        color_name, _ = box_color(clss, colormap)
         draw = ImageDraw.Draw(image)
         left, top, right, bottom = box_edges(det['bbox'], width, height, expansion)
         draw.rectangle([(left, top), (right, bottom)], outline=color_name, width=thickness)
         font = load_font(options.label_font, font_size)
         if not any(strings):
             continue
-        for padded, _, corner0, corner1, text_at in stacked_labels(font, strings, left, top, bottom, height):
+        for padded, _, corner0, corner1, text_at in stacked_labels(font, strings, left, top, bottom, height, vtextalign):
             draw.rectangle([corner0, corner1], fill=color_name)
             draw.text(text_at, padded, fill='black', font=font)
     return image
