@@ -12,8 +12,8 @@ of jobs; then
 
   backend='host'   makes the reference's PIL calls per job (open_image, resize_image, render_detection_bounding_boxes twice,
                    Image.save), on its pool of n_rendering_workers threads or processes;
-  backend='gpu'    groups the jobs by source file and renders a decode chunk (device_render.chunked) with ONE decode of each
-                   file (device_decode.decode_chunk), ONE mdhip_resample_lanczos call that makes one resampled image per
+  backend='gpu'    groups the jobs by source file and renders a decode chunk (device_render.run_chunks) with ONE decode of each
+                   file (device_decode.decode_stage), ONE mdhip_resample_lanczos call that makes one resampled image per
                    distinct file, ONE mdhip_draw_ops_from call that makes every job's image from its file's shared image
                    (the plan is A's preview.render_plan, then B's), and ONE mdhip_jpeg_encode call.  A job without any
                    operation needs no image of its own: the encoder reads the shared one.  The host leg takes, per job and
@@ -40,10 +40,11 @@ import re
 import sys
 import textwrap
 import urllib.parse
+from functools import partial
 
 from . import device_render as DR
 from . import preview as PV
-from .crops import encode_windows, is_jpeg_name
+from .crops import encode_windows
 from .postprocess_batch_results import SAVE_QUALITY, flatten_path, open_image, resized_size, write_html_image_list
 
 THICKNESS_A, THICKNESS_B = 4, 2                  # _render_image_pair: thickness=4 for A, 2 for B
@@ -420,14 +421,7 @@ def _render_host(jobs, options, threads_only=False):
     """the reference's loop over the images of a category, for all jobs: serial, or its pool of threads or processes"""
     if options.n_rendering_workers <= 1 or not jobs:
         return [render_job_host(job) for job in jobs]
-    from multiprocessing.pool import Pool, ThreadPool
-    threads = options.parallelize_rendering_with_threads or threads_only
-    pool = ThreadPool(options.n_rendering_workers) if threads else Pool(options.n_rendering_workers)
-    try:
-        return list(pool.imap(render_job_host, jobs))
-    finally:
-        pool.close()
-        pool.join()
+    return DR.pool_map(render_job_host, jobs, options.n_rendering_workers, options.parallelize_rendering_with_threads or threads_only)
 
 
 # ---- rendering: the device leg ----------------------------------------------------------------------------------------------------
@@ -447,39 +441,22 @@ def plan_device_jobs(jobs, probes=None):
     """Which jobs the device leg renders, decided before any pixel is decoded.  -> (planned, host, undecodable): the jobs
     with their 'probe', 'source_size', 'size' and 'plan'; the jobs the host leg takes, in their order; the distinct files
     among those that the device does not decode.  A missing file is the reference's AssertionError.  probes: a dict that
-    keeps device_decode.probe per file (a file is probed once however many jobs draw on it)."""
-    from .device_decode import probe
+    keeps device_decode.plan_source's probe per input path (a file is probed once however many jobs draw on it)."""
+    from .device_decode import plan_source
     probes = {} if probes is None else probes
     planned, host, undecodable = [], [], []
     for job in jobs:
         assert os.path.isfile(job['input_path']), 'Image {} does not exist'.format(job['input_path'])
         try:
-            if job['file'] not in probes:
-                try:
-                    probes[job['file']] = probe(job['input_path'])
-                except Exception as e:
-                    probes[job['file']] = e
-            p = probes[job['file']]
-            if isinstance(p, Exception):
-                raise PV.HostLeg('a file that does not open: PIL raises what the reference raises')
-            if p['scan'] is None:
-                if job['file'] not in undecodable:
-                    undecodable.append(job['file'])
-                raise PV.HostLeg('a file the device does not decode')
-            if not is_jpeg_name(job['output_path']):
-                raise PV.HostLeg('not a JPEG name')
-            width, height = p['size']
-            size = (width, height) if job['target_width'] is None else resized_size(width, height, job['target_width'])
-            if max(width, height, size[0], size[1]) > 65535:
-                raise PV.HostLeg('a side above 65535 pixels')
+            p, size = plan_source(job['input_path'], job['output_path'], job['target_width'], probes=probes)
             plan = job_plan(job, size)
-        except PV.HostLeg:
+        except Exception:                                            # (not a HostLeg: the host leg raises it as the reference does)
             host.append(job)
+            probed = probes[job['input_path']]                       # (what plan_source kept: the file is counted whatever fails after it)
+            if isinstance(probed, dict) and probed['scan'] is None and job['file'] not in undecodable:
+                undecodable.append(job['file'])
             continue
-        except Exception:
-            host.append(job)                                         # (the host leg raises it as the reference does)
-            continue
-        planned.append(dict(job, probe=p, source_size=(width, height), size=size, plan=plan))
+        planned.append(dict(job, probe=p, source_size=p['size'], size=size, plan=plan))
     return planned, host, undecodable
 
 
@@ -498,30 +475,20 @@ def group_bytes(group):
     return w * h * 3 + (tw * th * 3 if (tw, th) != (w, h) else 0) + tw * th * 3 * sum(1 for j in group if j['plan'].ops)
 
 
-def _render_chunk_device(ctx, torch, device, groups, options, counts, clock):
+def _render_chunk_device(ctx, torch, device, groups, clock, options, counts):
     """The jobs of one chunk of files, by the device render path.  -> the jobs the host leg has to make"""
-    from .device_decode import decode_chunk
-    files = [g[0]['file'] for g in groups]
-    probes = {g[0]['file']: g[0]['probe'] for g in groups}
-    via_pil = set()
-    with clock('decode'):
-        pixels, failed = decode_chunk(ctx, torch, device, options.image_folder, files, probes, counts, via_pil)
-    refused = [j for g in groups for j in g if j['file'] in failed or j['file'] in via_pil]      # the device did not decode it
-    groups = [g for g in groups if g[0]['file'] in pixels and g[0]['file'] not in via_pil]
+    from .device_decode import decode_stage
+    pixels, refused, _ = decode_stage(ctx, torch, device, options.image_folder, [g[0]['file'] for g in groups],
+                                      {g[0]['file']: g[0]['probe'] for g in groups}, counts, clock)
+    host = [j for g in groups for j in g if j['file'] in refused]    # the device did not decode it
+    groups = [g for g in groups if g[0]['file'] not in refused]
     if not groups:
-        return refused
+        return host
     # ONE shared image per distinct file: its decoded pixels, or their resampled form
-    sources = [pixels[g[0]['file']] for g in groups]
-    source_sizes, sizes = [g[0]['source_size'] for g in groups], [g[0]['size'] for g in groups]
-    shared = [s if size == source_size else torch.empty(size[0] * size[1] * 3, dtype=torch.uint8, device=device)
-              for s, size, source_size in zip(sources, sizes, source_sizes)]
-    resized = [k for k in range(len(groups)) if sizes[k] != source_sizes[k]]
-    if resized:
-        with clock('resample'):
-            ctx.resample_lanczos([sources[k].data_ptr() for k in resized], [source_sizes[k] for k in resized],
-                                 [source_sizes[k][0] * 3 for k in resized], [shared[k].data_ptr() for k in resized],
-                                 [sizes[k] for k in resized], [sizes[k][0] * 3 for k in resized])
-        counts['resample_calls'] += 1
+    sizes = [g[0]['size'] for g in groups]
+    shared, resampled = DR.resample_stage(ctx, torch, device, [pixels[g[0]['file']] for g in groups],
+                                          [g[0]['source_size'] for g in groups], sizes, clock)
+    counts['resample_calls'] += resampled
     # ONE fan-out draw: every job that draws anything gets an image of its own, made from its file's shared image
     jobs = [(k, j) for k, g in enumerate(groups) for j in g]
     drawn = [(k, j) for k, j in jobs if j['plan'].ops]
@@ -539,30 +506,17 @@ def _render_chunk_device(ctx, torch, device, groups, options, counts, clock):
         with open(j['output_path'], 'wb') as f:
             f.write(file_bytes)
     counts['gpu'] += len(jobs)
-    return refused
+    return host
 
 
 def _render_device(jobs, options, ctx, counts, profile):
     """-> the jobs that go to the host leg, in their order"""
     import torch
-    from ._lib import HipError
-    device = torch.device('cuda:{}'.format(ctx.device))
-    clock = DR.Clock(torch, device, counts['ms'] if profile else None)
     planned, host, undecodable = plan_device_jobs(jobs)
     counts['files_decoded_pil'] += len(undecodable)
-    chunks = DR.chunked(group_by_file(planned), group_bytes, DR.DECODE_CHUNK_BYTES)
-    with torch.cuda.device(device):
-        for chunk in chunks:
-            counts['decode_chunks'] += 1
-            try:
-                host += _render_chunk_device(ctx, torch, device, chunk, options, counts, clock)
-            except HipError as e:
-                n = sum(len(g) for g in chunk)
-                print('Warning: rendering {} images on the device failed ({}); PIL renders them'.format(n, e))
-                host += [j for g in chunk for j in g]                # (a chunk's files are written after its last device call)
-        torch.cuda.synchronize(device)
-    order = {(j['comparison'], j['category'], j['file']): i for i, j in enumerate(jobs)}
-    return sorted(host, key=lambda j: order[(j['comparison'], j['category'], j['file'])])
+    place = {(j['comparison'], j['category'], j['file']): i for i, j in enumerate(jobs)}
+    return DR.run_chunks(ctx, torch, group_by_file(planned), group_bytes, partial(_render_chunk_device, options=options, counts=counts),
+                         counts, profile, host, jobs_of=list, order=lambda j: place[(j['comparison'], j['category'], j['file'])])
 
 
 # ---- the pages --------------------------------------------------------------------------------------------------------------------
@@ -735,11 +689,8 @@ def compare_batch_results(options, backend='gpu', device=0, profile=False):
     host = jobs
     if backend == 'gpu' and jobs:
         from .hip_backend import HipContext
-        ctx = HipContext.for_images(device)
-        try:
+        with HipContext.images_or(None, device) as ctx:
             host = _render_device(jobs, options, ctx, counts, profile)
-        finally:
-            ctx.close()
     _render_host(host, options, threads_only=backend == 'gpu')
     counts['host'] = len(host)
 

@@ -1,6 +1,7 @@
 """
 Files of a folder, and the stored frames of videos, as RGB pixels in device memory, each decoded once: what the tools that work
-on written results files share (rde_review.py, separate_detections.py, visualize_video_output.py).  What follows the decode --
+on written results files share (rde_review.py, separate_detections.py, postprocess_batch_results.py, compare_batch_results.py,
+visualize_video_output.py), with what they check of a file before they decode it (plan_source).  What follows the decode --
 blur, draw, encode -- is device_render.py.  A baseline JPEG the GPU's decoder takes goes through mdhip_jpeg_entropy_decode and
 mdhip_jpeg_reconstruct on a context that needs no model -- one call each for a whole chunk of files -- and comes out as the
 pixels the reference's load_image gives, EXIF rotation included; every other file, and a JPEG the decoder flags, is decoded
@@ -30,6 +31,35 @@ def probe(path, keep_data=False):
     if keep_data:
         out['data'] = data
     return out
+
+
+def plan_source(path, output_name, target_width=None, keep_data=False, probes=None):
+    """What every results-file tool checks of a job before any pixel is decoded: -> (probe(path, keep_data), the size the image
+    is rendered at: resize_image's for target_width, its own for None).  Raises preview.HostLeg, the checks in this order: a
+    file that does not open, a file the device does not decode, an output name Pillow does not save as JPEG, a side above
+    65535 pixels; a target that is not positive is the reference's AssertionError.  probes: a dict that keeps what probe gave
+    or raised per path, so a file is probed once however many jobs draw on it."""
+    from .crops import is_jpeg_name
+    from .preview import HostLeg, resized_size
+    p = None if probes is None else probes.get(path)
+    if p is None:
+        try:
+            p = probe(path, keep_data)
+        except Exception as e:
+            p = e
+        if probes is not None:
+            probes[path] = p
+    if isinstance(p, Exception):
+        raise HostLeg('a file that does not open: PIL raises what the reference raises')
+    if p['scan'] is None:
+        raise HostLeg('a file the device does not decode')
+    if not is_jpeg_name(output_name):
+        raise HostLeg('not a JPEG name')
+    width, height = p['size']
+    size = resized_size(width, height, target_width)
+    if max(width, height, size[0], size[1]) > 65535:
+        raise HostLeg('a side above 65535 pixels')
+    return p, size
 
 
 def decode_scans(ctx, torch, device, images, keep_coefficients=False):
@@ -97,3 +127,15 @@ def decode_chunk(ctx, torch, device, image_base, files, probes, counts, via_pil=
             if via_pil is not None:
                 via_pil.add(f)
     return pixels, failed
+
+
+def decode_stage(ctx, torch, device, image_base, files, probes, counts, clock, keep_coefficients=False):
+    """The decode of one chunk of a results-file tool, timed as 'decode' by `clock` (a device_render.Clock): decode_chunk for
+    `files`, of which the tool renders only what the GPU's decoder took.  -> (pixels: file -> flat uint8 device tensor, the
+    refused files -- those PIL decoded or could not decode either: their jobs go to the host leg --, coefficients: None, or
+    with keep_coefficients decode_chunk's dict, which keeps the sources' planes until the caller drops it)"""
+    via_pil = set()
+    coefficients = {} if keep_coefficients else None
+    with clock('decode'):
+        pixels, failed = decode_chunk(ctx, torch, device, image_base, files, probes, counts, via_pil, coefficients)
+    return pixels, failed | via_pil, coefficients

@@ -1,9 +1,13 @@
 """
 The device render path: what follows the decode for images that lie in device memory, shared by the preview folder (preview.py),
-the blurred copies (blur.py), the crops (crops.py), the RDE review sheets (rde_review.py), separate_detections.py and
-visualize_video_output.py.  device_decode.py brings files into device memory; this module changes and encodes them:
+the blurred copies (blur.py), the crops (crops.py), the RDE review sheets (rde_review.py), separate_detections.py,
+postprocess_batch_results.py, compare_batch_results.py and visualize_video_output.py.  device_decode.py brings files into
+device memory; this module changes and encodes them:
 
-  blur_rects      ONE mdhip_blur_regions call for the rectangles of a batch of images
+  run_chunks      the device leg of a results-file tool: its planned jobs in decode chunks, a chunk that fails handed to the
+                  host leg, the host leg's jobs in their order
+  resample_stage  ONE mdhip_resample_lanczos call for the images of a chunk whose size changes
+  blur_rects     ONE mdhip_blur_regions call for the rectangles of a batch of images
   draw_plans      ONE mdhip_draw_ops call for the preview.RenderPlan of each image, the label patches of all of them uploaded
                   once in one buffer (pack_ops)
   draw_plans_from ONE mdhip_draw_ops_from call that makes every rendering of a chunk from the shared images they draw on
@@ -11,10 +15,11 @@ visualize_video_output.py.  device_decode.py brings files into device memory; th
   read_encoded    an encoder call into a guessed buffer, once more with the size the call asked for, and the read-back
   encode_sampled  ONE mdhip_jpeg_encode_sampled call, jpeg_host.sampled_file around each scan
   encode_kept     ONE mdhip_jpeg_encode_kept call for the copies that keep their source's JPEG blocks
+  encode_copies   the two for a chunk of copies, some of which keep their source's blocks
 
-and, for the host leg that writes the same bytes, blur_with_pil and kept_file_host.  chunked and DECODE_CHUNK_BYTES cut a run
-into decode chunks; Clock times the kinds of device call of a profiled run.  Nothing here synchronises the device unless a
-Clock was given a dict to fill.
+and, for the host leg that writes the same bytes, blur_with_pil, kept_file_host and pool_map, the reference's pool.  chunked,
+DECODE_CHUNK_BYTES and file_twice cut a run into decode chunks; Clock times the kinds of device call of a profiled run.
+Apart from run_chunks' wait at its end, nothing here synchronises the device unless a Clock was given a dict to fill.
 """
 
 import datetime
@@ -58,6 +63,52 @@ class Clock:
         yield
         self.torch.cuda.synchronize(self.device)
         self.ms[key] = self.ms.get(key, 0.0) + (datetime.datetime.now() - t0).total_seconds() * 1e3
+
+
+def file_twice(chunk, job):
+    """chunked's also_break of the tools whose jobs are files: a file that is listed twice has its jobs in two chunks"""
+    return any(j['file'] == job['file'] for j in chunk)
+
+
+def run_chunks(ctx, torch, items, size_of, render_chunk, counts, profile, host=(), also_break=None, jobs_of=None, order=None):
+    """The device leg of a results-file tool around its planned `items`: cuts them into decode chunks (chunked, under
+    DECODE_CHUNK_BYTES), calls render_chunk(ctx, torch, device, chunk, clock) for each -- it returns the jobs of the chunk
+    that the host leg has to make, and writes a chunk's files after its last device call -- and waits for the device at the
+    end.  A chunk whose rendering raises HipError goes to the host leg as a whole, with a warning; anything else propagates.
+    counts: gets 'decode_chunks' added to and, with profile, its 'ms' filled by the Clock the chunks are given.  host: the
+    jobs that could not be planned.  jobs_of(item): the host leg's jobs of an item that is not one itself.  order: job ->
+    its place in the tool's input.  -> the jobs of the host leg: in that order, or without one `host` and then what the
+    chunks gave back."""
+    from ._lib import HipError
+    device = torch.device('cuda:{}'.format(ctx.device))
+    clock = Clock(torch, device, counts['ms'] if profile else None)
+    host = list(host)
+    with torch.cuda.device(device):
+        for chunk in chunked(items, size_of, DECODE_CHUNK_BYTES, also_break):
+            counts['decode_chunks'] += 1
+            try:
+                host += render_chunk(ctx, torch, device, chunk, clock)
+            except HipError as e:
+                jobs = chunk if jobs_of is None else [j for item in chunk for j in jobs_of(item)]
+                print('Warning: rendering {} images on the device failed ({}); PIL renders them'.format(len(jobs), e))
+                host += jobs
+        torch.cuda.synchronize(device)
+    return host if order is None else sorted(host, key=order)
+
+
+def resample_stage(ctx, torch, device, sources, source_sizes, sizes, clock):
+    """sources (flat uint8 device tensors of source_sizes (width, height)) at `sizes`: -> (per image the source itself where
+    the size stays, else a new tensor, whether the call was made) -- the new ones filled by ONE mdhip_resample_lanczos
+    call, timed as 'resample'"""
+    out = [s if size == source_size else torch.empty(size[0] * size[1] * 3, dtype=torch.uint8, device=device)
+           for s, source_size, size in zip(sources, source_sizes, sizes)]
+    resized = [k for k in range(len(sources)) if sizes[k] != source_sizes[k]]
+    if resized:
+        with clock('resample'):
+            ctx.resample_lanczos([sources[k].data_ptr() for k in resized], [source_sizes[k] for k in resized],
+                                 [source_sizes[k][0] * 3 for k in resized], [out[k].data_ptr() for k in resized],
+                                 [sizes[k] for k in resized], [sizes[k][0] * 3 for k in resized])
+    return out, bool(resized)
 
 
 # ---- blur and draw -------------------------------------------------------------------------------------------------------------
@@ -205,7 +256,45 @@ def encode_kept(ctx, device, tensors, jobs, source_ptrs, stream=0):
     return [None if st else _sampled_file(j, host[o:o + n].tobytes()) for j, o, n, st in zip(jobs, offs, lens, status)]
 
 
+def encode_copies(ctx, device, tensors, jobs, source_ptrs, clock, reencode_flagged, stream=0):
+    """The files of a chunk's copies: ONE encode_kept call ('encode_kept' on the clock) for the jobs with 'keep' whose
+    source's planes are on the device (source_ptrs: per job the pointer, or None), then ONE encode_sampled call ('encode')
+    for the jobs without 'keep' -- and, with reencode_flagged, in the same call for every copy that has no file yet, so one
+    the kept call flagged is encoded whole.  Neither call is made without a copy for it.
+    -> (the files, None for a copy left to the host leg; the encoder calls made; the copies the kept call flagged)"""
+    files, calls = [None] * len(jobs), 0
+    kept = [k for k, j in enumerate(jobs) if j['keep'] and source_ptrs[k] is not None]
+    if kept:
+        with clock('encode_kept'):
+            made = encode_kept(ctx, device, [tensors[k] for k in kept], [jobs[k] for k in kept], [source_ptrs[k] for k in kept], stream)
+        for k, data in zip(kept, made):
+            files[k] = data
+        calls += 1
+    flagged = sum(files[k] is None for k in kept)
+    rest = [k for k, j in enumerate(jobs) if (files[k] is None if reencode_flagged else not j['keep'])]
+    if rest:
+        with clock('encode'):
+            made = encode_sampled(ctx, device, [tensors[k] for k in rest], [jobs[k] for k in rest], stream)
+        for k, data in zip(rest, made):
+            files[k] = data
+        calls += 1
+    return files, calls, flagged
+
+
 # ---- the host leg's share ------------------------------------------------------------------------------------------------------
+
+def pool_map(function, items, n, threads):
+    """[function(item) for item in items] on the reference's pool of n threads or processes (None: the pool's default
+    size), the results in the order of the items"""
+    from multiprocessing.pool import Pool, ThreadPool
+    kind = ThreadPool if threads else Pool
+    pool = kind() if n is None else kind(n)
+    try:
+        return list(pool.imap(function, items))
+    finally:
+        pool.close()
+        pool.join()
+
 
 def blur_with_pil(image, rects, radius=DEFAULT_BLUR_RADIUS):
     """visualization_utils.blur_detections :509-531 for rectangles with area (blur.blur_rectangle), IN PLACE on a PIL image"""

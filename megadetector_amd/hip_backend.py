@@ -7,6 +7,7 @@ All arithmetic happens in libmdhip.so (hand-written HIP); nothing here computes.
 import ctypes as C
 import json
 import os
+from contextlib import contextmanager
 
 import numpy as np
 
@@ -219,6 +220,18 @@ class HipContext:
         self.has_detect = False
         self.max_stride = 0
         return self
+
+    @classmethod
+    @contextmanager
+    def images_or(cls, ctx, device=0):
+        """`with HipContext.images_or(ctx, device) as ctx:` -- the caller's context, left open, or for None a for_images(device)
+        made for the block and closed after it"""
+        own = cls.for_images(device) if ctx is None else None
+        try:
+            yield ctx if own is None else own
+        finally:
+            if own is not None:
+                own.close()
 
     TUNED_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tuned_cfgs.json')
 

@@ -18,8 +18,8 @@ What rendering one image is has two legs that write the same bytes:
                    render_detection_bounding_boxes, Image.save; parallelize_rendering, parallelize_rendering_n_cores and
                    parallelize_rendering_with_threads size its pool.
   backend='gpu'    the device render path (device_render.py) on a context without a model: the sampled images that are not
-                   bypassed, in order, cut into decode chunks; per chunk every file decoded once on the device
-                   (device_decode.decode_chunk), ONE mdhip_resample_lanczos call, ONE mdhip_draw_ops call with the
+                   bypassed, in order, cut into decode chunks (device_render.run_chunks); per chunk every file decoded once
+                   on the device (device_decode.decode_stage), ONE mdhip_resample_lanczos call, ONE mdhip_draw_ops call with the
                    preview.render_plan of every image, ONE mdhip_jpeg_encode call (Pillow's quality 75 with 4:2:0) and
                    jpeg_host.jfif_file around each scan.
 
@@ -57,7 +57,8 @@ import numpy as np
 
 from . import device_render as DR
 from . import preview as PV
-from .crops import encode_windows, is_jpeg_name
+from .crops import encode_windows
+from .preview import resized_size
 from .separate_detections import get_typical_confidence_threshold_from_results
 
 DEFAULT_NEGATIVE_CLASSES = ['empty']
@@ -490,14 +491,6 @@ def open_image(input_file):
     return image
 
 
-def resized_size(width, height, target_width):
-    """the size resize_image(image, target_width) gives (preview.target_size); the reference's assertion for a target that
-    is not positive"""
-    size = PV.target_size(width, height, target_width)
-    assert size is not None, 'Invalid image resize target {},{}'.format(target_width, int(target_width / (width / height)))
-    return size
-
-
 def draw_arguments(decision, detection_categories, classification_categories):
     """What render_detection_bounding_boxes is called with at :540-547, as preview.render_plan and preview.render_with_pil
     take it: -> (PreviewOptions, keyword arguments)"""
@@ -556,43 +549,28 @@ def _map(function, items, options, threads_only=False):
     """the reference's loop :1785-1825: serial, or its pool of threads or processes"""
     if not options.parallelize_rendering:
         return [function(item) for item in items]
-    from multiprocessing.pool import Pool, ThreadPool
     threads = options.parallelize_rendering_with_threads or threads_only
     n = options.parallelize_rendering_n_cores
-    pool = (ThreadPool() if threads else Pool()) if n is None else (ThreadPool(n) if threads else Pool(n))
     if n is not None:
         print('Rendering images with {} {}'.format(n, 'threads' if threads else 'processes'))
-    try:
-        return list(pool.imap(function, items))
-    finally:
-        pool.close()
-        pool.join()
+    return DR.pool_map(function, items, n, threads)
 
 
 # ---- rendering: the device leg -----------------------------------------------------------------------------------------------------
 
 def _plan_job(decision, detection_categories, classification_categories, options):
     """What the device needs for one image before any pixel is decoded: -> the job; raises preview.HostLeg, or whatever
-    opening or planning raises (the host leg then does what the reference does with it)."""
-    from .device_decode import probe
+    planning raises (the host leg then does what the reference does with it)."""
+    from .device_decode import plan_source
     sample_name = sample_name_of(decision)
-    if not is_jpeg_name(sample_name):
-        raise PV.HostLeg('not a JPEG name')
-    p = probe(os.path.join(options.image_base_dir, decision['file']))
-    if p['scan'] is None:
-        raise PV.HostLeg('a file the device does not decode')
-    width, height = p['size']
-    target = (width, height)
-    if decision['rendering_options'].viz_target_width is not None:
-        target = resized_size(width, height, decision['rendering_options'].viz_target_width)
-    if max(width, height, target[0], target[1]) > 65535:
-        raise PV.HostLeg('a side above 65535 pixels')
+    p, target = plan_source(os.path.join(options.image_base_dir, decision['file']), sample_name,
+                            decision['rendering_options'].viz_target_width)
     o, kw = draw_arguments(decision, detection_categories, classification_categories)
     try:
         plan = PV.render_plan(decision['detections'], target[0], target[1], o, **kw)
     except PV.RenderFailure as e:
         raise PV.HostLeg(str(e))
-    return {'decision': decision, 'file': decision['file'], 'sample_name': sample_name, 'probe': p, 'source_size': (width, height),
+    return {'decision': decision, 'file': decision['file'], 'sample_name': sample_name, 'probe': p, 'source_size': p['size'],
             'size': target, 'plan': plan}
 
 
@@ -602,29 +580,19 @@ def _job_bytes(job):
     return w * h * 3 + (tw * th * 3 if (tw, th) != (w, h) else 0)
 
 
-def _render_chunk_device(ctx, torch, device, jobs, options, counts, clock):
-    """The images of one chunk, by the device render path.  -> the jobs the host leg has to make"""
-    from .device_decode import decode_chunk
-    names = [j['file'] for j in jobs]
-    probes = {j['file']: j['probe'] for j in jobs}
-    via_pil = set()
-    with clock('decode'):
-        pixels, failed = decode_chunk(ctx, torch, device, options.image_base_dir, names, probes, counts, via_pil)
-    refused = [j for j in jobs if j['file'] in failed or j['file'] in via_pil]          # the device did not decode it
-    jobs = [j for j in jobs if j['file'] in pixels and j['file'] not in via_pil]
+def _render_chunk_device(ctx, torch, device, jobs, clock, options, counts):
+    """The images of one chunk, by the device render path.  -> the decisions the host leg has to render"""
+    from .device_decode import decode_stage
+    pixels, refused, _ = decode_stage(ctx, torch, device, options.image_base_dir, [j['file'] for j in jobs],
+                                      {j['file']: j['probe'] for j in jobs}, counts, clock)
+    host = [j['decision'] for j in jobs if j['file'] in refused]          # the device did not decode it
+    jobs = [j for j in jobs if j['file'] not in refused]
     if not jobs:
-        return refused
-    sources = [pixels[j['file']] for j in jobs]
-    rendered = [s if j['size'] == j['source_size'] else torch.empty(j['size'][0] * j['size'][1] * 3, dtype=torch.uint8, device=device)
-                for s, j in zip(sources, jobs)]
-    resized = [k for k, j in enumerate(jobs) if j['size'] != j['source_size']]
-    if resized:
-        with clock('resample'):
-            ctx.resample_lanczos([sources[k].data_ptr() for k in resized], [jobs[k]['source_size'] for k in resized],
-                                 [jobs[k]['source_size'][0] * 3 for k in resized], [rendered[k].data_ptr() for k in resized],
-                                 [jobs[k]['size'] for k in resized], [jobs[k]['size'][0] * 3 for k in resized])
-        counts['resample_calls'] += 1
+        return host
     sizes = [j['size'] for j in jobs]
+    rendered, resampled = DR.resample_stage(ctx, torch, device, [pixels[j['file']] for j in jobs], [j['source_size'] for j in jobs],
+                                            sizes, clock)
+    counts['resample_calls'] += resampled
     if DR.draw_plans(ctx, [t.data_ptr() for t in rendered], sizes, [j['plan'] for j in jobs], device, clock=clock):
         counts['draw_calls'] += 1
     with clock('encode'):
@@ -637,34 +605,21 @@ def _render_chunk_device(ctx, torch, device, jobs, options, counts, clock):
                 f.write(data)
         j['decision']['sample_name'] = _save(save, options.output_dir, j['decision']['category_string'], j['sample_name'])
     counts['gpu'] += len(jobs)
-    return refused
+    return host
 
 
 def _render_device(decisions, detection_categories, classification_categories, options, ctx, counts, profile):
     """-> the decisions that go to the host leg, in their order"""
     import torch
-    from ._lib import HipError
-    device = torch.device('cuda:{}'.format(ctx.device))
-    clock = DR.Clock(torch, device, counts['ms'] if profile else None)
     host, planned = [], []
     for decision in decisions:
         try:
             planned.append(_plan_job(decision, detection_categories, classification_categories, options))
         except Exception:
             host.append(decision)
-    # (a file twice in the sample: its images in two chunks)
-    chunks = DR.chunked(planned, _job_bytes, DR.DECODE_CHUNK_BYTES, lambda chunk, job: any(j['file'] == job['file'] for j in chunk))
-    with torch.cuda.device(device):
-        for chunk in chunks:
-            counts['decode_chunks'] += 1
-            try:
-                host += [j['decision'] for j in _render_chunk_device(ctx, torch, device, chunk, options, counts, clock)]
-            except HipError as e:
-                print('Warning: rendering {} images on the device failed ({}); PIL renders them'.format(len(chunk), e))
-                host += [j['decision'] for j in chunk]               # (a chunk's files are written after its last device call)
-        torch.cuda.synchronize(device)
-    order = {id(d): i for i, d in enumerate(decisions)}
-    return sorted(host, key=lambda d: order[id(d)])
+    place = {id(d): i for i, d in enumerate(decisions)}
+    return DR.run_chunks(ctx, torch, planned, _job_bytes, partial(_render_chunk_device, options=options, counts=counts), counts,
+                         profile, host, DR.file_twice, lambda job: [job['decision']], lambda d: place[id(d)])
 
 
 # ---- the HTML ----------------------------------------------------------------------------------------------------------------------
@@ -1050,11 +1005,8 @@ def process_batch_results(options, backend='gpu', device=0, profile=False):
     host = to_render
     if backend == 'gpu' and to_render:
         from .hip_backend import HipContext
-        ctx = HipContext.for_images(device)
-        try:
+        with HipContext.images_or(None, device) as ctx:
             host = _render_device(to_render, detection_categories, classification_categories, options, ctx, counts, profile)
-        finally:
-            ctx.close()
     render = partial(render_host, detection_categories=detection_categories,
                      classification_categories=classification_categories, options=options)
     for decision, (sample_name, opened) in zip(host, _map(render, host, options, threads_only=backend == 'gpu')):

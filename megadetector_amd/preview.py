@@ -120,6 +120,14 @@ def target_size(width, height, target_width):
     return target_width, target_height
 
 
+def resized_size(width, height, target_width):
+    """the size resize_image(image, target_width) gives (target_size); the reference's assertion for a target that is not
+    positive"""
+    size = target_size(width, height, target_width)
+    assert size is not None, 'Invalid image resize target {},{}'.format(target_width, int(target_width / (width / height)))
+    return size
+
+
 def output_name(image_file, options):
     """visualize_detector_output.py:150-156: the path below the output folder; image_file is relative to the image folder"""
     if options.preserve_path_structure:

@@ -497,15 +497,9 @@ def write_review_folder(rde_results, review_options, backend='gpu', device=0, ct
             render_sample_host(location, folder, review_options)
         counts['host'] = len(flat)
     elif flat:
-        own = ctx is None
-        if own:
-            from .hip_backend import HipContext
-            ctx = HipContext.for_images(device)
-        try:
+        from .hip_backend import HipContext
+        with HipContext.images_or(ctx, device) as ctx:
             _render_device(flat, folder, review_options, ctx, ctx.device, counts)
-        finally:
-            if own:
-                ctx.close()
     RD._write_json(os.path.join(folder, INDEX_NAME), index_for_folder(rde_results, rde_options, review_options))
     counts['folder'] = folder
     return counts

@@ -11,11 +11,12 @@ file handling (_dispose).  What a manipulated copy is has two legs that write th
 
   backend='host'   exactly the reference's PIL calls: load_image, blur_detections, one render_detection_bounding_boxes per
                    category above threshold in sorted name order, exif_preserving_save(quality='keep').
-  backend='gpu'    the device render path (device_render.py; DESIGN.md, "the device render path"), per chunk of images: every
-                   file decoded once on the device (device_decode), ONE mdhip_blur_regions call, ONE mdhip_draw_ops call with
-                   the preview.render_plan of the categories one behind the other (RenderPlan.extend), ONE
-                   mdhip_jpeg_encode_sampled call for all images of the chunk -- each with the sampling and the quantisation
-                   tables Pillow's quality='keep' takes from its source file -- and jpeg_host.sampled_file around each scan.
+  backend='gpu'    the device render path (device_render.py; DESIGN.md, "the device render path"), per chunk of images
+                   (device_render.run_chunks): every file decoded once on the device (device_decode.decode_stage), ONE
+                   mdhip_blur_regions call, ONE mdhip_draw_ops call with the preview.render_plan of the categories one behind
+                   the other (RenderPlan.extend), ONE mdhip_jpeg_encode_sampled call for all images of the chunk -- each
+                   with the sampling and the quantisation tables Pillow's quality='keep' takes from its source file
+                   (device_render.encode_copies) -- and jpeg_host.sampled_file around each scan.
 
 For a plain RGB JPEG, which is what a camera trap writes, quality='keep' re-encodes with the SOURCE file's quantisation tables
 and chroma sampling and writes an EXIF APP1 segment and the source's COM segment.  A file open_image makes a new image of (an
@@ -493,13 +494,7 @@ def _map(function, items, options):
     """the reference's loop: serial, or its pool of threads or processes"""
     if options.n_threads <= 1:
         return [function(item) for item in items]
-    from multiprocessing.pool import Pool, ThreadPool
-    pool = ThreadPool(options.n_threads) if options.rendering_pool_type == 'threads' else Pool(options.n_threads)
-    try:
-        return list(pool.imap(function, items))
-    finally:
-        pool.close()
-        pool.join()
+    return DR.pool_map(function, items, options.n_threads, options.rendering_pool_type == 'threads')
 
 
 def _dispose_host(im, options):
@@ -516,25 +511,16 @@ def _render_job_host(job, options):
 # ---- the device leg ----------------------------------------------------------------------------------------------------------------
 
 def _plan_job(job, options):
-    """What the device needs for one manipulated copy, before any pixel is decoded; raises preview.HostLeg (or whatever opening
-    the file raises: the host leg then raises it as the reference does)."""
-    from PIL import Image
+    """What the device needs for one manipulated copy, before any pixel is decoded; raises preview.HostLeg (the host leg then
+    raises what the reference raises)."""
     from . import jpeg_host
-    from .device_decode import probe
-    ext = os.path.splitext(job['target'])[1].lower()
-    if Image.registered_extensions().get(ext) != 'JPEG':
-        raise PV.HostLeg('not a JPEG name')
-    p = probe(job['source'], keep_data=True)
-    if p['scan'] is None:
-        raise PV.HostLeg('a file the device does not decode')
+    from .device_decode import plan_source
+    p, (width, height) = plan_source(job['source'], job['target'], keep_data=True)
     src = jpeg_host.keep_source(job['source'], p['data'])
     if src['keep'] and src['quant'] is None:
         raise PV.HostLeg('tables or a sampling the device does not restate')
     if len(src['exif']) > 65533 or len(src['comment'] or b'') > 65533:
         raise PV.HostLeg('an EXIF block or a comment Pillow refuses')
-    if max(p['size']) > 65535:
-        raise PV.HostLeg('a side above 65535 pixels')
-    width, height = p['size']
     if src['keep']:
         job['sampling'], job['quant'] = src['sampling'], src['quant']
     else:
@@ -554,52 +540,35 @@ def _job_bytes(job):
     return job['size'][0] * job['size'][1] * 3 + (2 * int(job['probe']['scan'].coef_count) if job['keep'] else 0)
 
 
-def _render_chunk_device(ctx, torch, device, jobs, options, counts, clock):
+def _render_chunk_device(ctx, torch, device, jobs, clock, options, counts):
     """The manipulated copies of one chunk, by the device render path (device_render).  -> the jobs the host leg has to make"""
-    from .device_decode import decode_chunk
-    names = [j['file'] for j in jobs]
-    probes = {j['file']: j['probe'] for j in jobs}
-    via_pil = set()
-    coefficients = {} if any(j['keep'] for j in jobs) else None           # the sources' planes stay until the chunk is written
-    with clock('decode'):
-        pixels, failed = decode_chunk(ctx, torch, device, options.base_input_folder, names, probes, counts, via_pil, coefficients)
-    refused = [j for j in jobs if j['file'] in failed or j['file'] in via_pil]      # the device did not decode it
-    jobs = [j for j in jobs if j['file'] in pixels and j['file'] not in via_pil]
+    from .device_decode import decode_stage
+    # (with copies that keep their blocks the sources' planes stay until the chunk is written)
+    pixels, refused, coefficients = decode_stage(ctx, torch, device, options.base_input_folder, [j['file'] for j in jobs],
+                                                 {j['file']: j['probe'] for j in jobs}, counts, clock, any(j['keep'] for j in jobs))
+    host = [j for j in jobs if j['file'] in refused]                      # the device did not decode it
+    jobs = [j for j in jobs if j['file'] not in refused]
     if not jobs:
-        return refused
+        return host
     tensors = [pixels[j['file']] for j in jobs]
     DR.blur_and_draw(ctx, device, tensors, jobs, clock)
-    files = [None] * len(jobs)
-    kept = [k for k, j in enumerate(jobs) if j['keep'] and j['file'] in coefficients]
-    if kept:
-        with clock('encode_kept'):
-            made = DR.encode_kept(ctx, device, [tensors[k] for k in kept], [jobs[k] for k in kept],
-                                  [coefficients[jobs[k]['file']][0] for k in kept])
-        for k, data in zip(kept, made):
-            files[k] = data
-        counts['encode_calls'] += 1
-        counts['kept'] += sum(files[k] is not None for k in kept)
-        counts['kept_refused'] += sum(files[k] is None for k in kept)
-    rest = [k for k in range(len(jobs)) if files[k] is None]              # (a copy the kept call flagged is re-encoded whole)
-    if rest:
-        with clock('encode'):
-            made = DR.encode_sampled(ctx, device, [tensors[k] for k in rest], [jobs[k] for k in rest])
-        for k, data in zip(rest, made):
-            files[k] = data
-        counts['encode_calls'] += 1
+    # (a copy the kept call flagged is re-encoded whole)
+    files, calls, flagged = DR.encode_copies(ctx, device, tensors, jobs, [coefficients[j['file']][0] if j['keep'] else None for j in jobs],
+                                             clock, True)
+    counts['encode_calls'] += calls
+    counts['kept'] += sum(j['keep'] for j in jobs) - flagged
+    counts['kept_refused'] += flagged
     for j, data in zip(jobs, files):
         with open(j['target'], 'wb') as f:
             f.write(data)
     counts['gpu'] += len(jobs)
-    return refused
+    return host
 
 
 def _render_device(jobs, options, ctx, counts, profile):
-    """-> the jobs that go to the host leg"""
+    """-> the jobs that go to the host leg: those that could not be planned, then those the chunks gave back (run_chunks
+    without an order)"""
     import torch
-    from ._lib import HipError
-    device = torch.device('cuda:{}'.format(ctx.device))
-    clock = DR.Clock(torch, device, counts['ms'] if profile else None)
     host, planned = [], []
     for job in jobs:
         try:
@@ -607,18 +576,8 @@ def _render_device(jobs, options, ctx, counts, profile):
             planned.append(job)
         except Exception:
             host.append(job)                                              # (what the reference raises, the host leg raises)
-    # (a file twice in the results: its copies in two chunks)
-    chunks = DR.chunked(planned, _job_bytes, DR.DECODE_CHUNK_BYTES, lambda chunk, job: any(j['file'] == job['file'] for j in chunk))
-    with torch.cuda.device(device):
-        for chunk in chunks:
-            counts['decode_chunks'] += 1
-            try:
-                host += _render_chunk_device(ctx, torch, device, chunk, options, counts, clock)
-            except HipError as e:
-                print('Warning: rendering {} images on the device failed ({}); PIL renders them'.format(len(chunk), e))
-                host += chunk                                             # (a chunk's files are written after its last device call)
-        torch.cuda.synchronize(device)
-    return host
+    return DR.run_chunks(ctx, torch, planned, _job_bytes, partial(_render_chunk_device, options=options, counts=counts), counts,
+                         profile, host, DR.file_twice)
 
 
 # ---- the entry function ------------------------------------------------------------------------------------------------------------
@@ -675,15 +634,9 @@ def separate_detections_into_folders(options, backend='gpu', device=0, ctx=None,
         for im in images:
             counts[_dispose(im, options, manipulate=queue)] += 1
         if jobs:
-            own = ctx is None
-            if own:
-                from .hip_backend import HipContext
-                ctx = HipContext.for_images(device)
-            try:
+            from .hip_backend import HipContext
+            with HipContext.images_or(ctx, device) as ctx:
                 host = _render_device(jobs, options, ctx, counts, profile)
-            finally:
-                if own:
-                    ctx.close()
             for kept in _map(partial(_render_job_host, options=options), host, options):
                 if kept:
                     counts[kept] += 1

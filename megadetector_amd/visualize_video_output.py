@@ -507,24 +507,15 @@ def render_decoded(ctx, device, pixels, planes, jobs, planner, profile, clock, s
     live = [k for k in range(len(jobs)) if pixels[k] is not None]
     if not live:
         return files
-    blurred, drawn = DR.blur_and_draw(ctx, device, [pixels[k] for k in live], [jobs[k] for k in live], clock,
-                                      planner.options.blur_radius, stream)
+    tensors, live_jobs = [pixels[k] for k in live], [jobs[k] for k in live]
+    blurred, drawn = DR.blur_and_draw(ctx, device, tensors, live_jobs, clock, planner.options.blur_radius, stream)
     profile['blur_calls'] += blurred
     profile['draw_calls'] += drawn
-    kept = [k for k in live if jobs[k]['keep'] and planes[k] is not None]
-    if kept:
-        with clock('encode_kept'):
-            made = DR.encode_kept(ctx, device, [pixels[k] for k in kept], [jobs[k] for k in kept], [planes[k][0] for k in kept], stream)
-        for k, data in zip(kept, made):
-            files[k] = data
-        profile['encode_calls'] += 1
-    rest = [k for k in live if not jobs[k]['keep']]
-    if rest:
-        with clock('encode'):
-            made = DR.encode_sampled(ctx, device, [pixels[k] for k in rest], [jobs[k] for k in rest], stream)
-        for k, data in zip(rest, made):
-            files[k] = data
-        profile['encode_calls'] += 1
+    # (a frame the kept call flagged is the host leg's)
+    made, calls, _ = DR.encode_copies(ctx, device, tensors, live_jobs, [planes[k] and planes[k][0] for k in live], clock, False, stream)
+    profile['encode_calls'] += calls
+    for k, data in zip(live, made):
+        files[k] = data
     return files
 
 
@@ -919,15 +910,9 @@ def visualize_video_output(detector_output_path, out_dir, video_dir, options=Non
     if backend == 'host':
         results = _run_host(video_entries, planner, classification_label_map, options, video_dir, out_dir)
     else:
-        own = ctx is None
-        if own:
-            from .hip_backend import HipContext
-            ctx = HipContext.for_images(device)
-        try:
+        from .hip_backend import HipContext
+        with HipContext.images_or(ctx, device) as ctx:
             results = _run_device(video_entries, planner, classification_label_map, options, video_dir, out_dir, ctx, profile)
-        finally:
-            if own:
-                ctx.close()
     for r in results:
         for key in ('frames_copied', 'frames_rendered', 'frames_host'):
             r.setdefault(key, 0)

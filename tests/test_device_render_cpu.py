@@ -1,22 +1,27 @@
 """
 device_render without a GPU: the pure parts of the shared device render path -- the packing of the label patches of a batch,
 RenderPlan.extend, the encoder's two-try loop (on a CPU tensor with a stand-in for the encoder), the greedy chunker against the
-chunk lists the loops it replaced cut the test scenes into (tests/golden/device_render_chunks.json), the profiling clock -- and
-preview.stacked_labels for one string against the single-label arithmetic it replaced.
+chunk lists the loops it replaced cut the test scenes into (tests/golden/device_render_chunks.json), the profiling clock, the
+chunk driver of the results-file tools, its resample stage and its encode tail on stand-ins for torch, the context and the
+encoders, the host leg's pool, device_decode.plan_source on files Pillow writes -- and preview.stacked_labels for one string
+against the single-label arithmetic it replaced.
 """
 
 import ctypes
 import json
 import os
+from contextlib import contextmanager
 
 import numpy as np
 import pytest
 
 import rde_review_scene as RS
 import separate_scene as SS
+from megadetector_amd import device_decode as DD
 from megadetector_amd import device_render as DR
 from megadetector_amd import jpeg_host as J
 from megadetector_amd import preview as PV
+from megadetector_amd._lib import HipError
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 with open(os.path.join(HERE, 'golden', 'device_render_chunks.json')) as _f:
@@ -217,6 +222,270 @@ def test_clock_adds_to_its_key_and_waits_for_the_device_around_the_block():
         pass
     assert torch.synced == ['cuda:1'] * 6
     assert first >= 0.0 and ms['decode'] >= first and ms['draw'] >= 1.0 and set(ms) == {'decode', 'draw'}
+
+
+# ---- run_chunks -------------------------------------------------------------------------------------------------------------------
+
+class _Cuda:
+    def __init__(self):
+        self.synced, self.entered = [], []
+
+    def synchronize(self, device):
+        self.synced.append(device)
+
+    @contextmanager
+    def device(self, device):
+        self.entered.append(device)
+        yield
+
+
+class _Tensor:
+    def __init__(self, n, ptr):
+        self.n, self.ptr = n, ptr
+
+    def data_ptr(self):
+        return self.ptr
+
+
+class _DeviceTorch:
+    """what run_chunks and resample_stage touch of torch: device, empty, cuda.device and cuda.synchronize"""
+    uint8 = 'uint8'
+
+    def __init__(self):
+        self.cuda, self.made = _Cuda(), []
+
+    def device(self, name):
+        return name
+
+    def empty(self, n, dtype, device):
+        assert dtype == self.uint8
+        self.made.append(_Tensor(n, 0x1000 * (len(self.made) + 1)))
+        return self.made[-1]
+
+
+class _Context:
+    device = 1
+
+    def __init__(self):
+        self.resample_calls = []
+
+    def resample_lanczos(self, *args):
+        self.resample_calls.append(args)
+
+
+MB = 1 << 20
+JOBS = [{'file': f, 'bytes': n * MB} for f, n in (('a', 100), ('b', 100), ('c', 100), ('a', 1), ('d', 300), ('e', 1))]
+JOB_CHUNKS = [['a', 'b'], ['c', 'a'], ['d'], ['e']]                      # under 256 MiB; the second 'a' would break the first chunk anyway
+
+
+def _drive(render_chunk, profile=False, items=JOBS, **kw):
+    torch, ctx, counts = _DeviceTorch(), _Context(), {'decode_chunks': 0, 'ms': {}}
+    seen = []
+
+    def wrapped(*args):
+        seen.append(args)
+        return render_chunk(args[3])
+
+    try:
+        host = DR.run_chunks(ctx, torch, items, lambda j: j['bytes'], wrapped, counts, profile, **kw)
+    finally:
+        counts['seen'], counts['torch'], counts['ctx'] = seen, torch, ctx
+    return host, counts
+
+
+def test_run_chunks_renders_each_chunk_of_chunked_once():
+    assert [[j['file'] for j in c] for c in DR.chunked(JOBS, lambda j: j['bytes'], DR.DECODE_CHUNK_BYTES, DR.file_twice)] == JOB_CHUNKS
+    for profile in (False, True):
+        host, counts = _drive(lambda chunk: [], profile, also_break=DR.file_twice)
+        assert host == [] and counts['decode_chunks'] == len(JOB_CHUNKS) == len(counts['seen'])
+        assert [c for _, _, _, c, _ in counts['seen']] == DR.chunked(JOBS, lambda j: j['bytes'], DR.DECODE_CHUNK_BYTES, DR.file_twice)
+        for ctx, torch, device, _, clock in counts['seen']:
+            assert ctx is counts['ctx'] and torch is counts['torch'] and device == 'cuda:1'
+            assert isinstance(clock, DR.Clock) and clock.device == 'cuda:1' and clock.ms is (counts['ms'] if profile else None)
+        assert counts['torch'].cuda.entered == ['cuda:1'] and counts['torch'].cuda.synced == ['cuda:1']
+    # without the rule for a file listed twice only the bytes cut
+    _, counts = _drive(lambda chunk: [])
+    assert [[j['file'] for j in c] for _, _, _, c, _ in counts['seen']] == [['a', 'b'], ['c', 'a'], ['d'], ['e']]
+    _, counts = _drive(lambda chunk: [], items=JOBS[:2] + JOBS[3:4])
+    assert [[j['file'] for j in c] for _, _, _, c, _ in counts['seen']] == [['a', 'b', 'a']]
+    host, counts = _drive(lambda chunk: [], items=[])
+    assert host == [] and counts['decode_chunks'] == 0 and counts['torch'].cuda.synced == ['cuda:1']
+
+
+def test_run_chunks_gives_the_refused_jobs_back_in_the_order_of_the_input():
+    unplanned = [{'file': 'x', 'place': 2.5}, {'file': 'y', 'place': 9}]
+    for k, job in enumerate(JOBS):
+        job['place'] = k
+    refuse = lambda chunk: [j for j in reversed(chunk) if j['file'] in ('a', 'd')]
+    host, _ = _drive(refuse, host=unplanned, also_break=DR.file_twice, order=lambda j: j['place'])
+    assert [(j['file'], j['place']) for j in host] == [('a', 0), ('x', 2.5), ('a', 3), ('d', 4), ('y', 9)]
+    # without an order: what could not be planned, then what each chunk gave back, as it gave it back
+    host, _ = _drive(refuse, host=unplanned, also_break=DR.file_twice)
+    assert [(j['file'], j['place']) for j in host] == [('x', 2.5), ('y', 9), ('a', 0), ('a', 3), ('d', 4)]
+    assert unplanned == [{'file': 'x', 'place': 2.5}, {'file': 'y', 'place': 9}]         # (the caller's list is not changed)
+
+
+def test_run_chunks_hands_a_chunk_that_fails_on_the_device_to_the_host_leg(capsys):
+    def render(chunk):
+        if chunk[0]['file'] == 'c':
+            raise HipError('mdhip_draw_ops failed (7)')
+        return [j for j in chunk if j['file'] == 'e']
+
+    host, counts = _drive(render, also_break=DR.file_twice)
+    assert [j['file'] for j in host] == ['c', 'a', 'e'] and host[0] is JOBS[2] and host[1] is JOBS[3]
+    assert capsys.readouterr().out == 'Warning: rendering 2 images on the device failed (mdhip_draw_ops failed (7)); PIL renders them\n'
+    assert counts['decode_chunks'] == 4 and [c[0]['file'] for _, _, _, c, _ in counts['seen']] == ['a', 'c', 'd', 'e']
+    assert counts['torch'].cuda.synced == ['cuda:1']                     # the wait at the end, once, failed chunk or not
+
+
+def test_run_chunks_counts_and_flattens_the_jobs_of_grouped_items(capsys):
+    groups = [[{'file': 'a', 'n': 0}, {'file': 'a', 'n': 1}, {'file': 'a', 'n': 2}], [{'file': 'b', 'n': 3}], [{'file': 'c', 'n': 4}]]
+
+    def render(chunk):
+        if len(chunk) == 2:
+            raise HipError('out of memory')
+        return []
+
+    torch, counts = _DeviceTorch(), {'decode_chunks': 0}
+    host = DR.run_chunks(_Context(), torch, groups, lambda g: (100 if g[0]['file'] != 'c' else 200) * MB,
+                         lambda ctx, torch, device, chunk, clock: render(chunk), counts, False, [{'file': 'z', 'n': 2.5}], jobs_of=list,
+                         order=lambda j: j['n'])
+    assert [j['n'] for j in host] == [0, 1, 2, 2.5, 3] and counts['decode_chunks'] == 2
+    assert capsys.readouterr().out == 'Warning: rendering 4 images on the device failed (out of memory); PIL renders them\n'
+
+
+def test_run_chunks_lets_every_other_exception_through():
+    def render(chunk):
+        if chunk[0]['file'] == 'c':
+            raise ValueError('not the device')
+        return []
+
+    with pytest.raises(ValueError, match='^not the device$'):
+        _drive(render)
+
+
+# ---- resample_stage ---------------------------------------------------------------------------------------------------------------
+
+def test_resample_stage_returns_the_sources_themselves_where_no_size_changes():
+    torch, ctx, clock = _DeviceTorch(), _Context(), DR.Clock(_NoTorch(), 'cuda:1', None)
+    sources = [_Tensor(12 * 8 * 3, 0x10), _Tensor(5 * 7 * 3, 0x20)]
+    out, made = DR.resample_stage(ctx, torch, 'cuda:1', sources, [(12, 8), (5, 7)], [(12, 8), (5, 7)], clock)
+    assert made is False and len(out) == 2 and all(o is s for o, s in zip(out, sources))
+    assert ctx.resample_calls == [] and torch.made == []
+    assert DR.resample_stage(ctx, torch, 'cuda:1', [], [], [], clock) == ([], False)
+
+
+def test_resample_stage_makes_one_call_for_the_images_whose_size_changes():
+    torch, ctx, ms = _DeviceTorch(), _Context(), {}
+    clock = DR.Clock(_Torch(), 'cuda:1', ms)
+    sources = [_Tensor(12 * 8 * 3, 0x10), _Tensor(5 * 7 * 3, 0x20), _Tensor(9 * 9 * 3, 0x30), _Tensor(4 * 2 * 3, 0x40)]
+    source_sizes, sizes = [(12, 8), (5, 7), (9, 9), (4, 2)], [(6, 4), (5, 7), (9, 9), (40, 20)]
+    out, made = DR.resample_stage(ctx, torch, 'cuda:1', sources, source_sizes, sizes, clock)
+    assert made is True and out[1] is sources[1] and out[2] is sources[2]
+    assert [t.n for t in torch.made] == [6 * 4 * 3, 40 * 20 * 3] and out[0] is torch.made[0] and out[3] is torch.made[1]
+    assert ctx.resample_calls == [([0x10, 0x40], [(12, 8), (4, 2)], [36, 12], [0x1000, 0x2000], [(6, 4), (40, 20)], [18, 120])]
+    assert set(ms) == {'resample'}
+
+
+# ---- encode_copies ----------------------------------------------------------------------------------------------------------------
+
+def _encoders(monkeypatch, flag):
+    """encode_kept and encode_sampled stood in for: -> the calls, as (encoder, the jobs' names); the kept call flags `flag`"""
+    calls = []
+
+    def kept(ctx, device, tensors, jobs, source_ptrs, stream=0):
+        assert source_ptrs == [j['ptr'] for j in jobs] and tensors == [j['name'].upper() for j in jobs]
+        calls.append(('kept', [j['name'] for j in jobs]))
+        return [None if j['name'] in flag else 'kept ' + j['name'] for j in jobs]
+
+    def sampled(ctx, device, tensors, jobs, stream=0):
+        assert tensors == [j['name'].upper() for j in jobs]
+        calls.append(('sampled', [j['name'] for j in jobs]))
+        return ['sampled ' + j['name'] for j in jobs]
+
+    monkeypatch.setattr(DR, 'encode_kept', kept)
+    monkeypatch.setattr(DR, 'encode_sampled', sampled)
+    return calls
+
+
+@pytest.mark.parametrize('reencode_flagged', [True, False])
+def test_encode_copies_makes_one_call_of_each_encoder_the_jobs_need(monkeypatch, reencode_flagged):
+    """separate_detections (reencode_flagged) encodes a copy the kept call flagged whole, in the SAME sampled call as the copies
+    without 'keep'; visualize_video_output leaves it to the host leg.  Either way at most one call of each encoder per chunk."""
+    clock = DR.Clock(_NoTorch(), 'cuda:0', None)
+    jobs = [{'name': n, 'keep': k, 'ptr': p} for n, k, p in (('a', True, 1), ('b', False, None), ('c', True, 3), ('d', False, None))]
+
+    def run(jobs, flag=()):
+        calls = _encoders(monkeypatch, flag)
+        return DR.encode_copies(None, 'cuda:0', [j['name'].upper() for j in jobs], jobs, [j['ptr'] for j in jobs], clock, reencode_flagged), calls
+
+    (files, n, flagged), calls = run(jobs)
+    assert files == ['kept a', 'sampled b', 'kept c', 'sampled d'] and (n, flagged) == (2, 0)
+    assert calls == [('kept', ['a', 'c']), ('sampled', ['b', 'd'])]
+    (files, n, flagged), calls = run(jobs, flag=('c',))
+    assert (n, flagged) == (2, 1)
+    if reencode_flagged:
+        assert files == ['kept a', 'sampled b', 'sampled c', 'sampled d'] and calls == [('kept', ['a', 'c']), ('sampled', ['b', 'c', 'd'])]
+    else:
+        assert files == ['kept a', 'sampled b', None, 'sampled d'] and calls == [('kept', ['a', 'c']), ('sampled', ['b', 'd'])]
+    # only copies that keep their blocks: a second call only for a flagged one that is encoded whole
+    (files, n, flagged), calls = run(jobs[0::2], flag=('a',))
+    assert (files, n, flagged) == ((['sampled a', 'kept c'], 2, 1) if reencode_flagged else ([None, 'kept c'], 1, 1))
+    (files, n, flagged), calls = run(jobs[0::2])
+    assert (files, n, flagged) == (['kept a', 'kept c'], 1, 0) and calls == [('kept', ['a', 'c'])]
+    (files, n, flagged), calls = run(jobs[1::2])
+    assert (files, n, flagged) == (['sampled b', 'sampled d'], 1, 0) and calls == [('sampled', ['b', 'd'])]
+    assert run([]) == (([], 0, 0), [])
+
+
+# ---- pool_map ---------------------------------------------------------------------------------------------------------------------
+
+def test_pool_map_keeps_the_order_of_the_items():
+    assert DR.pool_map(abs, [-3, 2, -1, 0], 2, True) == [3, 2, 1, 0]
+    assert DR.pool_map(abs, [-3, 2], None, True) == [3, 2] and DR.pool_map(abs, [], 3, True) == []
+
+
+# ---- device_decode.plan_source ----------------------------------------------------------------------------------------------------
+
+def test_plan_source_raises_each_message_for_its_condition(tmp_path, monkeypatch):
+    from PIL import Image
+    rng = np.random.default_rng(5)
+    image = Image.fromarray(rng.integers(0, 255, (8, 16, 3), dtype=np.uint8))
+    baseline, png, progressive, gone = (str(tmp_path / n) for n in ('base.jpg', 'image.png', 'prog.jpg', 'gone.jpg'))
+    image.save(baseline)
+    image.save(png)
+    image.save(progressive, progressive=True)
+    probed = []
+    real = DD.probe
+    monkeypatch.setattr(DD, 'probe', lambda path, keep_data=False: probed.append(path) or real(path, keep_data))
+
+    def message(*args, **kw):
+        with pytest.raises(PV.HostLeg) as e:
+            DD.plan_source(*args, **kw)
+        return str(e.value)
+
+    p, size = DD.plan_source(baseline, 'out/copy.JPG')
+    assert p['size'] == size == (16, 8) and p['scan'] is not None and 'data' not in p
+    p, size = DD.plan_source(baseline, 'copy.jpeg', 40, keep_data=True)
+    assert size == (40, 20) and p['size'] == (16, 8) and p['data'] == open(baseline, 'rb').read()
+    assert DD.plan_source(baseline, 'copy.jpg', 16)[1] == DD.plan_source(baseline, 'copy.jpg', -1)[1] == (16, 8)
+    assert message(png, 'copy.jpg') == message(progressive, 'copy.jpg') == 'a file the device does not decode'
+    assert message(png, 'copy.png') == 'a file the device does not decode'             # (the file is looked at before the name)
+    assert message(baseline, 'copy.png') == message(baseline, 'copy') == 'not a JPEG name'
+    assert message(baseline, 'copy.jpg', 65536) == message(baseline, 'copy.jpg', 131072) == 'a side above 65535 pixels'
+    assert DD.plan_source(baseline, 'copy.jpg', 65535)[1] == (65535, 32767)
+    assert message(gone, 'copy.jpg') == 'a file that does not open: PIL raises what the reference raises'
+    with pytest.raises(AssertionError, match='^Invalid image resize target 0,0$'):
+        DD.plan_source(baseline, 'copy.jpg', 0)
+    # a dict of probes: every file is probed once, whatever it gave
+    del probed[:]
+    probes = {}
+    for _ in range(2):
+        assert DD.plan_source(baseline, 'copy.jpg', 40, probes=probes)[1] == (40, 20)
+        assert message(png, 'copy.jpg', probes=probes) == 'a file the device does not decode'
+        assert message(gone, 'copy.jpg', probes=probes) == 'a file that does not open: PIL raises what the reference raises'
+    assert probed == [baseline, png, gone] and set(probes) == {baseline, png, gone}
+    assert probes[png]['scan'] is None and isinstance(probes[gone], Exception)
 
 
 # ---- stacked_labels ---------------------------------------------------------------------------------------------------------------
