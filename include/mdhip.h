@@ -705,6 +705,10 @@ typedef struct {
     int32_t cfg;            /* tile configuration chosen (a decode op: -2 = done in
                              * the epilogue of the conv in front, -1 = own launch) */
     int32_t ntaps, stride, has_res;   /* conv: kh*kw of the packed kernel, stride, residual added */
+    int32_t variant;        /* a conv with its own launch: which of the tile's compiled bodies ran, a number of the tile's
+                             * kernel family (conv_v2: 0 general, 1 / 2 pointwise, 3 upsample read in place, 6 the streaming
+                             * body of "pw_stream", 100 decoding), -1 where the family does not tell; never part of
+                             * mdhip_launches_describe */
 } mdhip_op_info;
 
 /* What mdhip_create would plan for this model, dtype and capacity, as text, without touching a device: the context's sizes and
@@ -772,6 +776,12 @@ int mdhip_set_graph(mdhip_ctx* ctx, int mode, int max_n);
  *                               epilogue of each level's 1x1 conv -- no fp32 logits tensor, four launches fewer -- for heads
  *                               with 8 outputs per anchor (MDv5: nc = 3) in the plain forward; the augmented forward and
  *                               other heads always use the separate decode kernel.  Same statements, bit-identical.
+ *   "pw_stream"         1 | 0 | 2   1x1 / stride 1 convs with 160 input and 160 output channels, SiLU and a 16-bit output that
+ *                               does not overlap their input have a second body that keeps the weights in registers and streams
+ *                               pixels past them, under the tile configuration the op has anyway (the tile's name,
+ *                               mdhip_launches_describe and mdhip_op_info::cfg do not change; mdhip_op_info::variant tells):
+ *                               1 (default) = it runs them from the pixel count on at which it is the faster one, 0 = never,
+ *                               2 = always (tests).  Same MFMA chain and epilogue per output: bit-identical.
  * Replaces nothing in the reference; the switches exist for measurements and tests. */
 int mdhip_set_option(mdhip_ctx* ctx, const char* name, int value);
 /* time one op in isolation: `iters` back-to-back launches bracketed by events */
@@ -791,6 +801,7 @@ int mdhip_time_op(mdhip_ctx* ctx, int op, int n, int h, int w, int iters, float*
 #define MDHIP_LAUNCHES_ISOLATED 8         /* one op on its own, as mdhip_time_op runs it */
 #define MDHIP_LAUNCHES_CALIBRATING 16     /* the 16-bit forward of mdhip_calibrate (fp8 contexts) */
 #define MDHIP_LAUNCHES_AUGMENTED 32       /* a pass of mdhip_forward_tta, h x w being the size of that pass */
+#define MDHIP_LAUNCHES_NO_PW_STREAM 128    /* mdhip_set_option(ctx, "pw_stream", 0): the text does not depend on it */
 #define MDHIP_LAUNCHES_AFTER_OTHERS 64    /* test hook: other shapes, passes and settings are resolved on the context first and
                                              every setting is flipped and flipped back; the text must not depend on it */
 long long mdhip_launches_describe(const mdhip_model* model, int dtype, int max_batch, int max_h, int max_w, const mdhip_tuned* tuned,

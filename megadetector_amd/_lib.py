@@ -24,7 +24,7 @@ MDHIP_DTYPE_FP8 = 1
 MDHIP_DTYPE_FP16 = 2
 #: flags of mdhip_launches_describe
 MDHIP_LAUNCHES_NO_FUSE, MDHIP_LAUNCHES_NO_FUSE_DECODE, MDHIP_LAUNCHES_NO_PAIR, MDHIP_LAUNCHES_ISOLATED = 1, 2, 4, 8
-MDHIP_LAUNCHES_CALIBRATING, MDHIP_LAUNCHES_AUGMENTED, MDHIP_LAUNCHES_AFTER_OTHERS = 16, 32, 64
+MDHIP_LAUNCHES_CALIBRATING, MDHIP_LAUNCHES_AUGMENTED, MDHIP_LAUNCHES_AFTER_OTHERS, MDHIP_LAUNCHES_NO_PW_STREAM = 16, 32, 64, 128
 
 
 class mdhip_conv(C.Structure):
@@ -87,7 +87,7 @@ class mdhip_op_info(C.Structure):
     _fields_ = [('name', C.c_char * 48), ('kind', C.c_int32), ('layer', C.c_int32),
                 ('m', C.c_int32), ('n', C.c_int32), ('k', C.c_int32),
                 ('flops', C.c_double), ('bytes', C.c_double), ('cfg', C.c_int32),
-                ('ntaps', C.c_int32), ('stride', C.c_int32), ('has_res', C.c_int32)]
+                ('ntaps', C.c_int32), ('stride', C.c_int32), ('has_res', C.c_int32), ('variant', C.c_int32)]
 
 
 class mdhip_tuned(C.Structure):

@@ -614,6 +614,8 @@ conv_v2_kernel(const ConvArgs p) {
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
+#include "conv_v2_stream.h"
+
 // ---------------------------------------------------------------------------------------
 // configuration table
 // ---------------------------------------------------------------------------------------
@@ -682,7 +684,13 @@ constexpr int kNumProf = 0 MDHIP_CONV2_PROF(MDHIP_COUNT_ROW) MDHIP_CONV2_PROFRIN
 namespace {
 // keys: PW 0 / 1 / 2 of the configurations, the upsample read in place (UP), the one instantiation of a developer variant --
 // for the ring ones a pointwise instantiation
-enum { V2_PLAIN = 0, V2_PW1, V2_PW2, V2_UP, V2_DEV, V2_DEV_PW };
+// V2_STREAM: the streaming body (conv_v2_stream.h), which has no tile shape: one row (local id 0) serves every public configuration
+enum { V2_PLAIN = 0, V2_PW1, V2_PW2, V2_UP, V2_DEV, V2_DEV_PW, V2_STREAM };
+// ConvArgs::pw_stream 1 takes the streaming body from this many pixels on (2: from one pixel on).  Measured against the tiles
+// the table gives these ops (profiles/pw_stream.txt): 25 600 .. 102 400 pixels 57 .. 8 % slower (a wave's 61 KB of weights
+// for a handful of groups), 204 800 even with the 128-row tile and 15 % faster than the 320-row one, 307 200 and up 6 .. 15 %
+// faster than either.  The bits do not depend on it, so an image's result does not depend on its batch.
+constexpr int kStreamMinM = 307200;
 ConvInstTable conv2_insts() {
     static const ConvInst t[] = {
 #define X(id, bm, bn, wm, wn)                                                                                         \
@@ -706,8 +714,24 @@ ConvInstTable conv2_insts() {
         MDHIP_CONV2_DEC(X)
 #undef X
         MDHIP_INST(0, V2_UP, 256, v2_lds_bytes(160, 160), conv_v2_kernel<160, 160, 2, 2, 0, true>)
+        MDHIP_INST(0, V2_STREAM, 256, 0, conv_v2_stream_kernel)
     };
     return {t, (int)(sizeof(t) / sizeof(t[0]))};
+}
+// the op is one the streaming body computes: 160 -> 160 channels, SiLU, 16-bit output, nothing else attached; and no byte of the
+// output is a byte of the input (groups are in flight while others are stored)
+bool conv2_streams(const ConvArgs& a, bool pw) {
+    if (a.pw_stream <= 0 || (a.pw_stream == 1 && a.M < kStreamMinM) || !pw || a.k_pad != 192 || a.C8 != 20 || a.n_rows != 160 || a.N != 160 ||
+        a.act != 1 || a.out_f32 || a.res || a.in_up || a.in_f8 || a.out_f8 || a.dec_pred || a.M <= 0 || (a.ld_in % 8) != 0 ||
+        (a.ld_out % 8) != 0 || a.ld_in < 160 || a.ld_out < 160 || ((uintptr_t)a.in % 16) != 0 || ((uintptr_t)a.out % 16) != 0)
+        return false;
+    const long long in0 = (long long)(uintptr_t)a.in, out0 = (long long)(uintptr_t)a.out;
+    const long long in1 = in0 + ((long long)(a.M - 1) * a.ld_in + 160) * 2, out1 = out0 + ((long long)(a.M - 1) * a.ld_out + 160) * 2;
+    if (in1 <= out0 || out1 <= in0) return true;
+    // channel slices of one buffer: the same pitch, and the two column ranges apart in every row
+    if (a.ld_in != a.ld_out) return false;
+    const long long pitch = (long long)a.ld_in * 2, r = (((out0 - in0) % pitch) + pitch) % pitch;
+    return r >= 320 && r + 320 <= pitch;
 }
 const ConvInst* conv2_pick(int cfg, const ConvArgs& a) {
     const ConvInstTable t = conv2_insts();
@@ -720,6 +744,7 @@ const ConvInst* conv2_pick(int cfg, const ConvArgs& a) {
         const ConvInst* dev = conv_find_inst(t, cfg, V2_DEV);
         return dev || !(pw && whole) ? dev : conv_find_inst(t, cfg, V2_DEV_PW);
     }
+    if (cfg >= 0 && conv2_streams(a, pw)) return conv_find_inst(t, 0, V2_STREAM);
     return conv_find_inst(t, cfg, !pw ? V2_PLAIN : whole ? V2_PW1 : V2_PW2);
 }
 
@@ -743,12 +768,25 @@ hipError_t conv2_launch(int cfg, const ConvArgs& a, hipStream_t s) {
     if (cfg < 0 || cfg >= kNumCfgs2 + kNumProf || !conv2_shape_ok(a)) return hipErrorInvalidValue;
     ConvArgs p = a;
     conv_set_rcp(p);
-    const dim3 grid = conv_tile_grid(p, g_cfgs2[cfg]);
-    return conv_launch_inst(conv2_pick(cfg, a), grid, p, s);
+    dim3 grid = conv_tile_grid(p, g_cfgs2[cfg]);
+    const ConvInst* inst = conv2_pick(cfg, a);
+    if (inst && inst->key == V2_STREAM) {
+        // a persistent grid of pixel streams, one resident wave each: 256 CUs x 4 SIMDs of them at most, and no more than leave
+        // a stream two groups of 16 pixels for the weights it loads
+        const int streams = std::max(1, std::min(1024, (p.M + 15) / 16 / 2));
+        grid = dim3((unsigned)((streams + 3) / 4));
+    }
+    return conv_launch_inst(inst, grid, p, s);
+}
+// what pick chose, for mdhip_op_info::variant
+int conv2_variant(int cfg, const ConvArgs& a) {
+    if (cfg < 0 || cfg >= kNumCfgs2 + kNumProf || !conv2_shape_ok(a)) return -1;
+    const ConvInst* inst = conv2_pick(cfg, a);
+    return inst ? inst->key : -1;
 }
 }  // namespace
 
-MDHIP_CONV_FAMILY(conv_v2, CONV_V2, g_cfgs2, kNumCfgs2, kNumProf, true, false, true, conv2_supports, conv2_launch, conv2_insts)
+MDHIP_CONV_FAMILY(conv_v2, CONV_V2, g_cfgs2, kNumCfgs2, kNumProf, true, false, true, conv2_supports, conv2_launch, conv2_insts, conv2_variant)
 
 }  // namespace MDHIP_ST
 }  // namespace mdhip

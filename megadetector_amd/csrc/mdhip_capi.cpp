@@ -288,6 +288,7 @@ long long mdhip_launches_describe(const mdhip_model* model, int dtype, int max_b
     const bool fuse = !(flags & MDHIP_LAUNCHES_NO_FUSE), fuse_decode = !(flags & MDHIP_LAUNCHES_NO_FUSE_DECODE);
     (void)mdhip_set_fuse(&ctx, fuse);
     (void)mdhip_set_option(&ctx, "fuse_decode", fuse_decode);
+    (void)mdhip_set_option(&ctx, "pw_stream", !(flags & MDHIP_LAUNCHES_NO_PW_STREAM));
     // the pass as one of the forward-like calls would set it up (an augmented pass: any placement but the plain one)
     auto resolve_as = [&](unsigned kind, int rn, int rh, int rw) {
         Pass pass(&ctx, nullptr, num_anchors_for(&ctx, rh, rw), (kind & MDHIP_LAUNCHES_ISOLATED) != 0, (kind & MDHIP_LAUNCHES_CALIBRATING) != 0);
@@ -869,6 +870,13 @@ int mdhip_get_op_info(mdhip_ctx* ctx, int op, mdhip_op_info* out) {
     out->bytes = L.bytes;
     // a conv with its own launch: its tile; -2 = a decode folded into the conv in front; -1 = anything else
     out->cfg = L.how == RUN_IN_FRONT ? -2 : (o.kind == OP_CONV && L.how == RUN_LAUNCH) ? L.cfg : -1;
+    out->variant = -1;
+    if (o.kind == OP_CONV && L.how == RUN_LAUNCH) {          // (the arguments as launch_op passes them on)
+        ConvArgs a = L.a;
+        float none = 0.f;
+        a.dec_pred = L.decodes ? &none : nullptr;
+        out->variant = conv_api(ctx).variant(L.cfg, a);
+    }
     if (o.kind == OP_CONV || o.kind == OP_DW) {
         const PackedConv& pc = ctx->packed[o.pc];
         out->ntaps = pc.kh * pc.kw;
@@ -917,6 +925,7 @@ int mdhip_set_option(mdhip_ctx* ctx, const char* name, int value) {
     if (!ctx || !name) return MDHIP_EINVAL;
     if (!strcmp(name, "letterbox_general")) ctx->letterbox_general = value != 0;
     else if (!strcmp(name, "fuse_decode")) ctx->fuse_decode = value != 0;
+    else if (!strcmp(name, "pw_stream")) ctx->pw_stream = value <= 0 ? 0 : value >= 2 ? 2 : 1;
     else return fail(ctx, MDHIP_EINVAL, "unknown option '%s'", name);
     launches_changed(ctx);
     return MDHIP_OK;

@@ -239,6 +239,7 @@ struct mdhip_ctx {
     bool fuse_enabled = true, fuse_suspended = false;
     bool pair_enabled = true;         // paired taps of a half-full last channel group (conv_v5.cpp); MDHIP_PAIR=0 at create: off
     bool fuse_decode = true;          // Detect decode in the epilogue of the Detect 1x1 convs (mdhip_set_option "fuse_decode")
+    int pw_stream = 1;                // streaming body for the 160 -> 160 channel 1x1 convs: ConvArgs::pw_stream (mdhip_set_option "pw_stream")
     bool letterbox_general = false;   // MDHIP_LETTERBOX_GENERAL at create: never take the streaming-copy letterbox (A/B, tests)
     std::vector<hipEvent_t> events;
     std::vector<mdhip_tuned> tuned;   // measured tile choices (tools/autotune.py)

@@ -93,6 +93,7 @@ void conv_args(const mdhip_ctx* ctx, const Op& op, int n, int h, int w, ConvArgs
     a.groups = pc.groups;
     a.wgt4p = (pc.w4p_off && ctx->pair_enabled) ? (const uint16_t*)(ctx->warena + pc.w4p_off) : nullptr;
     a.k_pad4p = pc.k_pad4p;
+    a.pw_stream = ctx->pw_stream;
     if (ctx->dtype == MDHIP_DTYPE_FP8 && !ctx->calibrating) {
         if (op.f8_in) {
             // the e4m3 tensor lives in the 16-bit tensor's allocation: same pixel pitch, counted in bytes

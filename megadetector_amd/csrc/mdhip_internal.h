@@ -159,6 +159,10 @@ struct ConvArgs {
     // splits an output pixel index into (image, row, column) with conv_udiv() instead of two run-time integer
     // divisions per row; filled by the launch functions that need them (conv_set_rcp), callers leave them alone
     unsigned rcp_howo, rcp_wo;
+    // conv_v2.cpp, 1x1 convs whose weights fit a wave's registers (C_in = N = 160): the streaming body (conv_v2_stream.h: same
+    // MFMA chain and epilogue per output, same bits) runs them 0 = never, 1 = from the pixel count on at which it is the faster
+    // one, 2 = always (mdhip_set_option "pw_stream")
+    int pw_stream;
 };
 inline unsigned conv_rcp32(int d) { return d <= 1 ? 0xffffffffu : (unsigned)(0x100000000ull / (unsigned)d); }
 inline void conv_set_rcp(ConvArgs& p) { p.rcp_howo = conv_rcp32(p.HoWo); p.rcp_wo = conv_rcp32(p.Wo); }
@@ -253,8 +257,11 @@ struct ConvFamily {
     bool (*supports)(int local, const ConvArgs& a);
     hipError_t (*launch)(int local, const ConvArgs& a, hipStream_t s);   // hipSuccess or the launch error
     ConvInstTable (*insts)();
+    // the key of the instantiation (ConvInst::key) the family's pick() chooses for this op, -1 for none; nullptr: the family
+    // does not tell (mdhip_op_info::variant then reports -1)
+    int (*variant)(int local, const ConvArgs& a);
 };
-// MDHIP_CONV_FAMILY(name, id, cfgs, n_cfgs, n_dev, bitwise, f8_in, f8_out, supports, launch, insts) defines a translation
+// MDHIP_CONV_FAMILY(name, id, cfgs, n_cfgs, n_dev, bitwise, f8_in, f8_out, supports, launch, insts[, variant]) defines a translation
 // unit's family object.  It is host data: the device pass must not emit a copy into the code object (a family's table is a
 // function-local static of its insts() for the same reason: that names -- and so instantiates -- the kernels in both passes)
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -329,6 +336,11 @@ struct ConvRegistry {
         int l = 0;
         const ConvFamily* f = find(cfg, &l);
         return f && conv_family_takes(*f, a) ? f->launch(l, a, s) : hipErrorInvalidValue;
+    }
+    int variant(int cfg, const ConvArgs& a) const {
+        int l = 0;
+        const ConvFamily* f = find(cfg, &l);
+        return f && f->variant && conv_family_takes(*f, a) ? f->variant(l, a) : -1;
     }
     // developer variant k of a family (tools/convbench.cpp)
     hipError_t launch_dev(ConvFamilyId family, int k, const ConvArgs& a, hipStream_t s) const {

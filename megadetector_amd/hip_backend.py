@@ -115,7 +115,7 @@ def describe_plan(weights, dtype='bf16', max_batch=32, max_h=1280, max_w=1280):
 
 
 def describe_launches(weights, dtype, capacity, tuned_entries, n, h, w, fuse=True, fuse_decode=True, pair=True, isolated=False,
-                      calibrating=False, augmented=False, forced=None, after_others=False):
+                      calibrating=False, augmented=False, forced=None, after_others=False, pw_stream=True):
     """
     What a forward of n images of h x w launches on a context of these weights, storage type and capacity (max_batch, max_h,
     max_w) with this tile table (the entries of tuned_cfgs*.json; None = none) and these settings, as text
@@ -127,7 +127,7 @@ def describe_launches(weights, dtype, capacity, tuned_entries, n, h, w, fuse=Tru
     flags = ((not fuse) * _lib.MDHIP_LAUNCHES_NO_FUSE | (not fuse_decode) * _lib.MDHIP_LAUNCHES_NO_FUSE_DECODE |
              (not pair) * _lib.MDHIP_LAUNCHES_NO_PAIR | bool(isolated) * _lib.MDHIP_LAUNCHES_ISOLATED |
              bool(calibrating) * _lib.MDHIP_LAUNCHES_CALIBRATING | bool(augmented) * _lib.MDHIP_LAUNCHES_AUGMENTED |
-             bool(after_others) * _lib.MDHIP_LAUNCHES_AFTER_OTHERS)
+             bool(after_others) * _lib.MDHIP_LAUNCHES_AFTER_OTHERS | (not pw_stream) * _lib.MDHIP_LAUNCHES_NO_PW_STREAM)
     by_name = {lib.mdhip_conv_cfg_name(i).decode(): i for i in range(lib.mdhip_num_conv_cfgs())}
     pairs = [v for op, cfg in sorted((forced or {}).items()) for v in (int(op), by_name[cfg] if isinstance(cfg, str) else int(cfg))]
     farr = (C.c_int32 * max(1, len(pairs)))(*pairs)
@@ -745,7 +745,7 @@ class HipContext:
             self._check(self.lib.mdhip_get_op_info(self.h, i, C.byref(info)), 'mdhip_get_op_info')
             res.append(dict(op=i, name=info.name.decode(), kind=info.kind, layer=info.layer, m=info.m,
                             n=info.n, k=info.k, flops=info.flops, bytes=info.bytes, cfg=info.cfg,
-                            ntaps=info.ntaps, stride=info.stride, has_res=info.has_res))
+                            ntaps=info.ntaps, stride=info.stride, has_res=info.has_res, variant=info.variant))
         return res
 
     def forward_timed(self, n, h, w, stream=0):

@@ -93,6 +93,7 @@ static const Shape kShapes[] = {
     {"odd", 3, 19, 37, 96, 200, 3, 1, true},            // nothing divides anything: masks, ragged M and N
     {"q320", 3, 11, 23, 96, 320, 3, 1, true},           // 8-wave tiles (N % 320 == 0): ragged M, masks, 64 + 32 channels
     {"q160", 3, 11, 23, 160, 160, 3, 1, true},
+    {"pw160", 3, 11, 23, 160, 160, 1, 1, false},        // the streaming 1x1 body: 759 pixels, a ragged last group of 16
     {"small", 2, 24, 40, 64, 96, 3, 1, true},
     {"small1", 2, 24, 40, 64, 96, 1, 1, false},
     {"smalls2", 2, 24, 40, 64, 96, 3, 2, false},
@@ -342,6 +343,9 @@ int main(int argc, char** argv) {
     CK(hipMemset(d_dbg, 0, dbg_words * 8));
     a.dbg = d_dbg;
     a.dev_param = getenv("MDHIP_DEV_PARAM") ? atoi(getenv("MDHIP_DEV_PARAM")) : 0;
+    // CONVBENCH_PW_STREAM (ConvArgs::pw_stream): 0 = the tiled instantiation for the 160 -> 160 channel 1x1 shapes, 1 (default) = the
+    // streaming body where the library would take it, 2 = always; the `bits` of a line must not depend on it
+    a.pw_stream = getenv("CONVBENCH_PW_STREAM") ? atoi(getenv("CONVBENCH_PW_STREAM")) : 1;
 
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
@@ -374,6 +378,8 @@ int main(int argc, char** argv) {
             if (d > max_err || d != d) max_err = d;
             if (fabs(r) > max_ref) max_ref = fabs(r);
         }
+        unsigned long long bits = 1469598103934665603ull;                // FNV-1a of the output: equal bits, equal number
+        for (size_t i = 0; i < out_elems; ++i) bits = (bits ^ h_out[i]) * 1099511628211ull;
         float best = 1e30f, tot = 0;
         const int reps = 3;
         for (int r = 0; r < reps; ++r) {
@@ -387,8 +393,8 @@ int main(int argc, char** argv) {
             tot += ms;
             if (ms < best) best = ms;
         }
-        printf("  cfg %2d %-22s %8.4f ms (best %8.4f)  %7.1f TF/s   max|err| %.3g (max|ref| %.3g) bad %zu%s\n", cfg,
-               name, tot / reps, best, flops / (tot / reps * 1e-3) / 1e12, max_err, max_ref, bad,
+        printf("  cfg %2d %-22s %8.4f ms (best %8.4f)  %7.1f TF/s   max|err| %.3g (max|ref| %.3g) bad %zu bits %016llx%s\n", cfg,
+               name, tot / reps, best, flops / (tot / reps * 1e-3) / 1e12, max_err, max_ref, bad, bits,
                bad ? "  <-- MISMATCH" : "");
         if (!dev && !strncmp(name, "dev:strip", 9)) {
             // the stamped four-row fused bottleneck: cycles per tile and wave by phase

@@ -1,5 +1,6 @@
 // Measured peaks of the box next to the vendor figures: an HBM stream test
-// (copy and read-only, 16 bytes per lane, grid-stride) and a register-only MFMA loop
+// (copy and read-only, 16 bytes per lane, grid-stride; the copy also with U independent loads in flight per lane, which is
+// the figure a streaming kernel is priced against -- the plain loop has one) and a register-only MFMA loop
 // (v_mfma_f32_16x16x32_bf16, independent accumulators, no memory traffic).
 //
 // Build:  bash tools/build_convbench.sh   (builds build/peaks as well)
@@ -24,6 +25,21 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 __global__ void __launch_bounds__(256) copy_kernel(const uint4* __restrict__ in, uint4* __restrict__ out, size_t n) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = in[i];
+}
+
+// the copy with U independent 16-byte loads per lane in flight before the first store: a workgroup moves U runs of 4 KiB per
+// round, the grid walks the buffer front to back
+template <int U>
+__global__ void __launch_bounds__(256) copy_shaped_kernel(const uint4* __restrict__ in, uint4* __restrict__ out, size_t n) {
+    const size_t stride = (size_t)gridDim.x * 256 * U;
+    for (size_t base = (size_t)blockIdx.x * 256 * U + threadIdx.x; base < n; base += stride) {
+        uint4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = base + (size_t)u * 256 < n ? in[base + (size_t)u * 256] : make_uint4(0, 0, 0, 0);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (base + (size_t)u * 256 < n) out[base + (size_t)u * 256] = v[u];
+    }
 }
 
 __global__ void __launch_bounds__(256) read_kernel(const uint4* __restrict__ in, unsigned* __restrict__ out, size_t n) {
@@ -99,6 +115,10 @@ int main() {
     const int grid = prop.multiProcessorCount * 16;
     float ms = time_ms([&] { hipLaunchKernelGGL(copy_kernel, dim3(grid), dim3(256), 0, 0, a, b, n); }, 5);
     printf("HBM copy  (read + write): %7.1f GB/s  (%.2f ms for 2 x %.1f GiB)\n", 2.0 * bytes / ms / 1e6, ms, bytes / 1073741824.0);
+    ms = time_ms([&] { hipLaunchKernelGGL(copy_shaped_kernel<4>, dim3(prop.multiProcessorCount * 8), dim3(256), 0, 0, a, b, n); }, 5);
+    printf("HBM copy, 4 loads in flight per lane: %7.1f GB/s  (%.2f ms)\n", 2.0 * bytes / ms / 1e6, ms);
+    ms = time_ms([&] { hipLaunchKernelGGL(copy_shaped_kernel<8>, dim3(prop.multiProcessorCount * 8), dim3(256), 0, 0, a, b, n); }, 5);
+    printf("HBM copy, 8 loads in flight per lane: %7.1f GB/s  (%.2f ms)\n", 2.0 * bytes / ms / 1e6, ms);
     ms = time_ms([&] { hipLaunchKernelGGL(read_kernel, dim3(grid), dim3(256), 0, 0, a, flag, n); }, 5);
     printf("HBM read  only          : %7.1f GB/s  (%.2f ms)\n", 1.0 * bytes / ms / 1e6, ms);
     ms = time_ms([&] { hipLaunchKernelGGL(write_kernel, dim3(grid), dim3(256), 0, 0, b, n); }, 5);
