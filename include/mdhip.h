@@ -161,7 +161,7 @@ int mdhip_create(const mdhip_model* model, int device, int dtype,
                  int max_batch, int max_h, int max_w, mdhip_ctx** out);
 /* A context WITHOUT a model, for work that only touches images (marking a results file and writing its review folder load no
  * detector): every image entry point works on it -- mdhip_jpeg_*, mdhip_blur_regions, mdhip_resample_lanczos, mdhip_draw_ops,
- * mdhip_draw_ops_from, mdhip_classifier_input, mdhip_thumbnails, mdhip_change_detect (and its hook mdhip_label_regions_on) -- and every entry point that needs the plan or the weights (mdhip_preprocess*,
+ * mdhip_draw_ops_from, mdhip_classifier_input, mdhip_thumbnails, mdhip_change_detect (and its hook mdhip_label_regions_on), mdhip_gray_count -- and every entry point that needs the plan or the weights (mdhip_preprocess*,
  * the forwards, mdhip_nms*, mdhip_read_*, mdhip_calibrate and the fp8 calls, the op / cfg / tuned / fuse / option / graph /
  * timing calls, the mdhip_*_on kernel hooks) returns MDHIP_EINVAL with a text in mdhip_last_error.  It owns nothing on the
  * device until a call needs scratch.  mdhip_destroy frees it. */
@@ -583,6 +583,27 @@ int mdhip_change_detect(mdhip_ctx* ctx, const uint8_t* const* images, const int3
  * x, y, w, h, area in regions, *overflow (1: more than cap). */
 int mdhip_label_regions_on(mdhip_ctx* ctx, const uint8_t* mask, int w, int h, int min_area, int cap, int32_t* labels, int32_t* n_regions,
                            int32_t* regions, uint8_t* overflow, void* hip_stream);
+
+/* The number of gray pixels (R == G and R == B) inside a rectangle of each of n images that lie in device memory: the numerator
+ * of the reference's visualization_utils.gray_scale_fraction, np.logical_and(r == g, r == b).sum(), for a whole chunk of decoded
+ * files at once.  The statement and the walk of a row are csrc/gray_count.h's; the host model is mdjpeg_gray_count
+ * (include/mdjpeg.h).
+ *   ctx                       any context, one of mdhip_create_images included
+ *   images                    per image the DEVICE address of its first pixel: RGB, 8 bits a sample, pitches[i] bytes a row, at
+ *                             any alignment; widths, heights 1 .. 65535
+ *   windows                   n x 4 values x, y, w, h: the rectangle that is counted, at least one pixel, inside its image (a
+ *                             device image holds the pixels after the EXIF rotation, so the reference's band of rows, taken in
+ *                             the stored orientation, may be a band of columns here)
+ *   counts                    HOST memory, n values: per image the exact count
+ * Every other array is host memory.  ONE launch for all images; only the 3 * w bytes of the h rows of a window are read.  Lane
+ * counts are summed per wave and per workgroup, and each workgroup adds once, with a 64-bit atomicAdd, to its image's counter
+ * in the context's scratch, which the call zeroes on the same stream first; the sums are integers, so the result does not depend
+ * on the order.  The call returns when the counts are in host memory.  MDHIP_EINVAL, with nothing launched and counts left as
+ * it is: a NULL pointer, n outside 1 .. 65535, a side outside 1 .. 65535, a pitch below 3 * width, an image whose last byte lies
+ * 0x7fff0000 bytes or more behind its first (the limit of every image entry point), a window that is empty or leaves its
+ * image, a host pointer among the images. */
+int mdhip_gray_count(mdhip_ctx* ctx, const uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
+                     const int32_t* windows, int n, uint64_t* counts, void* hip_stream);
 
 /* Test-time augmentation: replaces mdhip_forward for `model(batch, augment=True)` (reference
  * pytorch_detector.py:1313 -> yolov5 _forward_augment): three passes over the batch that mdhip_preprocess

@@ -249,6 +249,21 @@ int mdjpeg_change_detect(const uint8_t* const* images, const int32_t* widths, co
                          const mdjpeg_change_options* opt, int64_t* counts, uint32_t* hist, int32_t* thresholds, int32_t* n_regions,
                          int32_t* regions, uint8_t* overflow, uint8_t* const* masks);
 
+/* ---- gray pixels of a rectangle (GPU: mdhip_gray_count, include/mdhip.h) ---------------------------------------------------- */
+/* The host model of the GPU call, compiled from the header the kernel is compiled from (csrc/gray_count.h): per image the number
+ * of pixels with R == G and R == B inside its window.  Arguments as mdhip_gray_count without the context and the stream, every
+ * pointer host memory: images (RGB, 8 bits a sample, pitches[i] bytes a row, any alignment), widths, heights (1 .. 65535),
+ * windows (n x 4: x, y, w, h; at least one pixel, inside the image), counts (n values).  mdjpeg_gray_count asks every pixel of
+ * the window in turn; mdjpeg_gray_count_walk takes the kernel's walk of a row (head pixels byte by byte up to an aligned
+ * address, four pixels at a time as three 32-bit words, the tail byte by byte) and must give the same counts.  Neither reads a
+ * byte outside the 3 * w bytes of the window's rows.  MDJPEG_EINVAL, and nothing is written, for a NULL pointer, n outside
+ * 1 .. 65535, a side outside 1 .. 65535, a pitch below 3 * width, an image whose last byte lies 0x7fff0000 bytes or more
+ * behind its first (the GPU call's limit, kept so that both refuse the same), a window that is empty or leaves its image. */
+int mdjpeg_gray_count(const uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
+                      const int32_t* windows, int n, uint64_t* counts);
+int mdjpeg_gray_count_walk(const uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
+                           const int32_t* windows, int n, uint64_t* counts);
+
 const char* mdjpeg_version(void);
 
 #ifdef __cplusplus

@@ -141,6 +141,7 @@ SYMBOLS = {
     'mdhip_change_detect': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.POINTER(mdhip_change_options), _P, _P, _P, _P, _P,
                                       _P, _P, _P]),
     'mdhip_label_regions_on': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    'mdhip_gray_count': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
     'mdhip_forward_tta': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_last_num_anchors': (C.c_int, [_P]),
     'mdhip_calibrate': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),

@@ -320,7 +320,7 @@ void mdhip_destroy(mdhip_ctx* ctx) {
             if (ctx->fwd_ev[i][k]) (void)hipEventDestroy(ctx->fwd_ev[i][k]);
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->warena) (void)hipFree(ctx->warena);
-    for (DevBuffer* b : {&ctx->stage, &ctx->jpeg_planes, &ctx->jpeg_entropy, &ctx->jpeg_encode, &ctx->blur, &ctx->resample, &ctx->draw, &ctx->classify, &ctx->change}) b->release();
+    for (DevBuffer* b : {&ctx->stage, &ctx->jpeg_planes, &ctx->jpeg_entropy, &ctx->jpeg_encode, &ctx->blur, &ctx->resample, &ctx->draw, &ctx->classify, &ctx->change, &ctx->gray}) b->release();
     if (ctx->geom_host) (void)hipHostFree(ctx->geom_host);
     for (int i = 0; i < 4; ++i) if (ctx->geom_ev[i]) (void)hipEventDestroy(ctx->geom_ev[i]);
     if (ctx->input_free) (void)hipEventDestroy(ctx->input_free);

@@ -225,6 +225,7 @@ struct mdhip_ctx {
     DevBuffer resample;           // mdhip_resample_lanczos: coefficient tables, records, the images between the two passes
     DevBuffer draw;               // mdhip_draw_ops: the images' records and the operations
     DevBuffer classify;           // mdhip_classifier_input: the float table, the crops' records, the coefficient tables
+    DevBuffer gray;               // mdhip_gray_count: the windows' records and their counters
     DevBuffer change;             // mdhip_change_detect: records, results, first-pass planes, masks, labels and sums of a group of pairs
     long long jpeg_entropy_stats[4] = {0, 0, 0, 0};   // of the last call: lanes, lanes decoded again, pass-2 launches, images
     int last_n = 0, last_h = 0, last_w = 0;

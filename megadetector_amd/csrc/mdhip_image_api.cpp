@@ -1,6 +1,6 @@
 // The image entry points of the C ABI (include/mdhip.h): letterbox (mdhip_preprocess*), JPEG (mdhip_jpeg_*), mdhip_blur_regions,
 // the previews (mdhip_resample_lanczos, mdhip_draw_ops), the classifier input (mdhip_classifier_input), the thumbnails
-// (mdhip_thumbnails), change detection (mdhip_change_detect).
+// (mdhip_thumbnails), change detection (mdhip_change_detect), the gray pixels of a rectangle (mdhip_gray_count).
 // None of them looks at the model: they check their arguments, lay out scratch in one of the context's growable buffers
 // (mdhip_ctx.h DevBuffer) and launch.  What their checks have in common is written once, below; where two entry points
 // apply the same checks in a different order, each keeps its own order (the first failing check is what a caller sees).
@@ -21,6 +21,7 @@
 #include "blur_box.h"
 #include "resample.h"
 #include "change_detect.h"
+#include "gray_count.h"
 
 namespace {
 
@@ -1227,6 +1228,46 @@ int mdhip_change_detect(mdhip_ctx* ctx, const uint8_t* const* images, const int3
         }
         first = last;
     }
+    return MDHIP_OK;
+}
+
+int mdhip_gray_count(mdhip_ctx* ctx, const uint8_t* const* images, const int32_t* widths, const int32_t* heights, const int64_t* pitches,
+                     const int32_t* windows, int n, uint64_t* counts, void* hip_stream) {
+    if (!ctx) return MDHIP_EINVAL;
+    int bad;
+    if (!gc_args_ok(images, widths, heights, pitches, windows, n, counts, &bad)) {
+        if (bad < 0) return fail(ctx, MDHIP_EINVAL, "images/widths/heights/pitches/windows/counts is NULL, or n = %d outside 1 .. %d", n, GC_MAX_IMAGES);
+        return fail(ctx, MDHIP_EINVAL, "image %d: NULL, %dx%d at pitch %lld (sides 1 .. 65535, pitch >= 3 * width, under 0x7fff0000 bytes in all), or its window (%d, %d, %d, %d) is empty or leaves it", bad, widths[bad],
+                    heights[bad], (long long)pitches[bad], windows[4 * bad], windows[4 * bad + 1], windows[4 * bad + 2], windows[4 * bad + 3]);
+    }
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    for (int i = 0; i < n; ++i)
+        if (!is_device_ptr(images[i])) return fail(ctx, MDHIP_EINVAL, "image %d: a host pointer -- images must be device memory", i);
+    // the scratch: [records][counters]
+    ScratchLayout lay;
+    lay.take(sizeof(GrayWindow) * (size_t)n);                           // (at offset 0)
+    const size_t o_counts = lay.take(8 * (size_t)n);
+    if (int rc = ctx->gray.reserve(ctx, lay.size, &s)) return rc;
+    std::vector<GrayWindow> recs((size_t)n);
+    long long max_groups = 1;
+    for (int i = 0; i < n; ++i) {
+        const int32_t* q = windows + 4 * (size_t)i;
+        GrayWindow& d = recs[(size_t)i];
+        d.origin = images[i] + (long long)q[1] * pitches[i] + 3LL * q[0];
+        d.pitch = pitches[i];
+        d.count = (unsigned long long*)(ctx->gray.p + o_counts) + i;
+        d.w = q[2], d.h = q[3];
+        max_groups = std::max(max_groups, (long long)gc_groups(d.w) * d.h);
+    }
+    // (the upload is from pageable memory: the copy has left `recs` when the call returns)
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->gray.p, recs.data(), sizeof(GrayWindow) * (size_t)n, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->gray.p + o_counts, 0, 8 * (size_t)n, s));
+    HIP_TRY(ctx, launch_gray_count((const GrayWindow*)ctx->gray.p, n, max_groups, s));
+    std::vector<uint64_t> got((size_t)n);                               // the caller's array stays as it is unless all of it arrives
+    HIP_TRY(ctx, hipMemcpyAsync(got.data(), ctx->gray.p + o_counts, 8 * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    memcpy(counts, got.data(), 8 * (size_t)n);
     return MDHIP_OK;
 }
 

@@ -672,4 +672,17 @@ hipError_t launch_chg_dilate(const ChgPair* pairs, int n, int max_w, int max_h, 
 // the regions of m[sel]: labels, per-label sums, the significant ones (count > min_area) in ascending order, at most cap written
 hipError_t launch_chg_regions(const ChgPair* pairs, int n, int max_w, int max_h, int sel, int min_area, int cap, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------
+// Gray pixels of a rectangle (gray_kernels.cpp; the statement is gray_count.h's): one record per image, read by the workgroups
+// of blockIdx.y
+// ---------------------------------------------------------------------------------------
+struct GrayWindow {
+    const uint8_t* origin;             // the window's first pixel, `pitch` bytes a row
+    long long pitch;
+    unsigned long long* count;         // the image's counter, zero before the launch
+    int w, h;                          // of the window
+};
+// max_groups: the largest rows x gc_groups(width) of the n windows
+hipError_t launch_gray_count(const GrayWindow* windows, int n, long long max_groups, hipStream_t s);
+
 }  // namespace mdhip

@@ -200,7 +200,7 @@ class HipContext:
     def for_images(cls, device=0):
         """
         A context without a model (include/mdhip.h: mdhip_create_images): the image calls work on it -- jpeg_*, blur_regions,
-        resample_lanczos, draw_ops, classifier_input, thumbnails -- and every call that needs the plan or the weights
+        resample_lanczos, draw_ops, classifier_input, thumbnails, change_detect, gray_count -- and every call that needs the plan or the weights
         (preprocess, forward, nms, read_*, ...) raises HipError (MDHIP_EINVAL).
         """
         self = cls.__new__(cls)
@@ -582,6 +582,30 @@ class HipContext:
                                                     C.addressof(n_regions), regions.ctypes.data, C.addressof(overflow), C.c_void_p(stream)),
                     'mdhip_label_regions_on')
         return labels, n_regions.value, regions[:min(n_regions.value, cap)], overflow.value
+
+    def gray_count(self, ptrs, sizes, pitches, windows, counts=None, stream=0):
+        """
+        The gray pixels (R == G and R == B) inside a rectangle of each device image, in one launch (include/mdhip.h:
+        mdhip_gray_count).
+        ptrs, sizes, pitches: per image the device address of an RGB uint8 image, its (width, height) and its bytes a row
+        windows:              per image (x, y, w, h), inside the image
+        counts:               None, or the uint64 array the call fills (it stays as it is when the call refuses its arguments)
+        Returns the counts as Python ints; the call has completed.
+        """
+        n = len(ptrs)
+        if not (len(sizes) == len(pitches) == len(windows) == n):
+            raise ValueError('ptrs, sizes, pitches and windows must have one entry per image')
+        if counts is None:
+            counts = np.zeros(max(n, 1), np.uint64)
+        if counts.dtype != np.uint64 or not counts.flags['C_CONTIGUOUS'] or counts.size < n:
+            raise ValueError('counts: a contiguous uint64 array with one entry per image is needed')
+        m = max(n, 1)
+        p = C.cast((C.c_void_p * m)(*[int(v) or None for v in ptrs]), C.c_void_p)
+        ws, hs = (C.c_int32 * m)(*[int(v[0]) for v in sizes]), (C.c_int32 * m)(*[int(v[1]) for v in sizes])
+        pt = (C.c_int64 * m)(*[int(v) for v in pitches])
+        win = (C.c_int32 * (4 * m))(*[int(v) for q in windows for v in q])
+        self._check(self.lib.mdhip_gray_count(self.h, p, ws, hs, pt, win, n, counts.ctypes.data, C.c_void_p(stream)), 'mdhip_gray_count')
+        return [int(v) for v in counts[:n]]
 
     def classifier_input(self, crops, size, out_ptr, filter=0, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), stream=0):
         """

@@ -89,6 +89,8 @@ SYMBOLS = {
                                            C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     'mdjpeg_change_detect': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'mdjpeg_gray_count': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'mdjpeg_gray_count_walk': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'mdjpeg_version': (C.c_char_p, []),
 }
 
@@ -696,6 +698,31 @@ def change_detect(images, pairs, options, blurred=None, want_masks=False):
     res = out.result(m, options.region_cap)
     res['blurred'], res['masks'] = blurred, masks
     return res
+
+
+def gray_count(images, windows=None, walk=False):
+    """mdjpeg_gray_count (walk: mdjpeg_gray_count_walk, the kernel's walk of a row): images: per image an (h, w, 3) uint8 array whose
+    pixels are 3 adjacent bytes -- any base address, any bytes a row (a view with strides (pitch, 3, 1) is taken as it lies);
+    windows: None for the whole images, or per image (x, y, w, h).  -> per image the number of pixels of its window with
+    R == G and R == B, as Python ints.  ValueError for what the call refuses."""
+    n = len(images)
+    for i, a in enumerate(images):
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.strides[1:] != (3, 1) or (a.shape[0] > 1 and a.strides[0] < 3 * a.shape[1]):
+            raise ValueError('image {}: an (h, w, 3) uint8 array with 3 adjacent bytes a pixel is needed'.format(i))
+    if windows is None:
+        windows = [(0, 0, a.shape[1], a.shape[0]) for a in images]
+    if len(windows) != n:
+        raise ValueError('one window per image is needed')
+    win = np.ascontiguousarray(np.asarray(windows, np.int32).reshape(-1, 4))
+    counts = np.zeros(max(n, 1), np.uint64)
+    call = load().mdjpeg_gray_count_walk if walk else load().mdjpeg_gray_count
+    rc = call((C.c_void_p * max(n, 1))(*[a.ctypes.data for a in images]), (C.c_int32 * max(n, 1))(*[a.shape[1] for a in images]),
+              (C.c_int32 * max(n, 1))(*[a.shape[0] for a in images]),
+              (C.c_int64 * max(n, 1))(*[a.strides[0] if a.shape[0] > 1 else 3 * a.shape[1] for a in images]), win.ctypes.data, n,
+              counts.ctypes.data)
+    if rc != MDJPEG_OK:
+        raise ValueError('mdjpeg_gray_count refused its arguments ({})'.format(rc))
+    return [int(v) for v in counts[:n]]
 
 
 def classifier_plan(canvas_w, canvas_h, size, filter=0, lds_bytes=0):
