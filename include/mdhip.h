@@ -714,6 +714,14 @@ int mdhip_adown_pool_on(mdhip_ctx* ctx, const uint16_t* in, uint16_t* a, uint16_
 int mdhip_cbfuse_on(mdhip_ctx* ctx, const uint16_t* const* src, const int32_t* factor, int n_src, const uint16_t* last,
                     uint16_t* out, int n, int h, int w, int c, void* hip_stream);
 
+/* the network input of a scaled pass of mdhip_forward_tta in isolation (tests): pass 1 (scale 0.83, left-right flipped) or 2
+ * (scale 0.67) of the batch of n images of h x w that mdhip_preprocess left in the context, computed as mdhip_forward_tta computes
+ * it (the same launch, the same scratch copy of the batch, the pass geometry from the same function) and copied to host as
+ * [n][3][*oh][*ow] fp32, exactly the stored values.  out may be NULL to query *oh and *ow only.  The context's input holds the
+ * batch again when the call returns, and no forward state changes.  MDHIP_EUNSUPPORTED for anchor-free models, MDHIP_EINVAL for
+ * another pass or without a preprocess of that batch. */
+int mdhip_tta_input_on(mdhip_ctx* ctx, int n, int h, int w, int pass, float* out, int* oh, int* ow, void* hip_stream);
+
 typedef struct {
     char    name[48];       /* e.g. "L6.m3.cv2 3x3"                           */
     int32_t kind;           /* 0 conv (implicit GEMM), 1 pool, 2 upsample, 3 decode (YOLOv5 Detect decode, or the DFL

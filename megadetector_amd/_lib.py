@@ -168,6 +168,7 @@ SYMBOLS = {
     'mdhip_dfl_decode_on': (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P]),
     'mdhip_adown_pool_on': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     'mdhip_cbfuse_on': (C.c_int, [_P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    'mdhip_tta_input_on': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
     'mdhip_plan_describe': (C.c_longlong, [C.POINTER(mdhip_model), C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     'mdhip_launches_describe': (C.c_longlong, [C.POINTER(mdhip_model), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(mdhip_tuned),
                                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_int32), C.c_int,

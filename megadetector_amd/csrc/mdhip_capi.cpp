@@ -46,6 +46,21 @@ int mdhip::need_model(mdhip_ctx* ctx, const char* call) {
     return fail(ctx, MDHIP_EINVAL, "%s: this context has no model (mdhip_create_images): only the image entry points work on it", call);
 }
 
+TtaPass mdhip::tta_pass(const mdhip_ctx* ctx, int h, int w, int k) {
+    static const float scales[3] = {1.0f, 0.83f, 0.67f};
+    static const double scales_d[3] = {1.0, 0.83, 0.67};
+    static const int flips[3] = {0, 1, 0};
+    const int gs = ctx->max_stride;
+    TtaPass p;
+    p.sh = k ? (int)(h * scales_d[k]) : h;
+    p.sw = k ? (int)(w * scales_d[k]) : w;
+    p.oh = k ? (int)std::ceil(h * scales_d[k] / gs) * gs : h;
+    p.ow = k ? (int)std::ceil(w * scales_d[k] / gs) * gs : w;
+    p.flip = flips[k];
+    p.scale = scales[k];
+    return p;
+}
+
 namespace {
 
 // the captured graphs go (after the device has finished with them: an executable may still be in flight on the caller's stream)
@@ -414,17 +429,11 @@ int mdhip_forward_tta(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
     if (int rc = check_calibrated(ctx)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const float scales[3] = {1.0f, 0.83f, 0.67f};
-    const double scales_d[3] = {1.0, 0.83, 0.67};
-    const int flips[3] = {0, 1, 0};
-    const int gs = ctx->max_stride;
-    int sh[3], sw[3], oh[3], ow[3], A[3];
+    TtaPass g3[3];
+    int A[3];
     for (int k = 0; k < 3; ++k) {
-        sh[k] = k ? (int)(h * scales_d[k]) : h;
-        sw[k] = k ? (int)(w * scales_d[k]) : w;
-        oh[k] = k ? (int)std::ceil(h * scales_d[k] / gs) * gs : h;
-        ow[k] = k ? (int)std::ceil(w * scales_d[k] / gs) * gs : w;
-        A[k] = num_anchors_for(ctx, oh[k], ow[k]);
+        g3[k] = tta_pass(ctx, h, w, k);
+        A[k] = num_anchors_for(ctx, g3[k].oh, g3[k].ow);
     }
     long long g = 0, p4 = 1;
     for (int l = 0; l < ctx->nl; ++l) { g += p4; if (l + 1 < ctx->nl) p4 *= 4; }      // p4 = 4^(nl-1)
@@ -441,16 +450,17 @@ int mdhip_forward_tta(mdhip_ctx* ctx, int n, int h, int w, void* hip_stream) {
     if (int rc = pass.flip_prediction()) return rc;
     int out_off = 0;
     for (int k = 0; k < 3; ++k) {
-        if (k) HIP_TRY(ctx, launch_tta_scale(orig, in, n, h, w, sh[k], sw[k], oh[k], ow[k], flips[k], f16, s));
+        const TtaPass& tp = g3[k];
+        if (k) HIP_TRY(ctx, launch_tta_scale(orig, in, n, h, w, tp.sh, tp.sw, tp.oh, tp.ow, tp.flip, f16, s));
         DecodeTta t;
         t.keep_from = k == 2 ? i3 : 0;
         t.keep_to = k == 0 ? A[0] - i1 : A[k];
         t.out_off = out_off;
-        t.scale = scales[k];
-        t.flip_lr = flips[k];
+        t.scale = tp.scale;
+        t.flip_lr = tp.flip;
         t.img_w = (float)w;
         ctx->cur_tta = t;
-        if (int rc = pass.run(n, oh[k], ow[k], s)) return rc;
+        if (int rc = pass.run(n, tp.oh, tp.ow, s)) return rc;
         out_off += t.keep_to - t.keep_from;
     }
     HIP_TRY(ctx, hipMemcpyAsync(in, orig, in_bytes, hipMemcpyDeviceToDevice, s));       // `input` holds the batch again

@@ -33,6 +33,12 @@ inline int round_up(int x, int a) { return (x + a - 1) / a * a; }
 // batch and input size against what the context was planned for
 int check_shape(mdhip_ctx* ctx, int n, int h, int w);
 
+// Pass k (0, 1, 2) of the augmented forward on an h x w input (mdhip_capi.cpp; yolov5 _forward_augment / scale_img): the batch,
+// left-right flipped when `flip`, is resized to sh x sw and padded with 0.447 to oh x ow, the next multiple of the model stride.
+// mdhip_forward_tta and the test hook mdhip_tta_input_on both take the geometry from here.
+struct TtaPass { int sh, sw, oh, ow, flip; float scale; };
+TtaPass tta_pass(const mdhip_ctx* ctx, int h, int w, int k);
+
 // A context of mdhip_create_images has no plan, no weights and no arena: every entry point that reads one of them starts with
 // NEED_MODEL, which refuses such a context (MDHIP_EINVAL, the call's name in mdhip_last_error) -- and a NULL one
 int need_model(mdhip_ctx* ctx, const char* call);

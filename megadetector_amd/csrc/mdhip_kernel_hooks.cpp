@@ -1,6 +1,7 @@
 // The YOLO11 / YOLOv9 kernels and the region stage of the change detection in isolation (tests): the mdhip_*_on hooks of
 // include/mdhip.h.
 // host buffers in / out; scratch device memory is allocated per call (not for the product path)
+// mdhip_tta_input_on is the one hook that works on the context's own buffers: the scaled input of an augmented pass.
 
 #include <algorithm>
 #include <vector>
@@ -147,6 +148,42 @@ int mdhip_cbfuse_on(mdhip_ctx* ctx, const uint16_t* const* src, const int32_t* f
     HIP_TRY(ctx, launch_cbfuse(a, ctx->dtype == MDHIP_DTYPE_FP16, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     HIP_TRY(ctx, hipMemcpy(out, dout, px * c * 2, hipMemcpyDeviceToHost));
+    return MDHIP_OK;
+}
+
+int mdhip_tta_input_on(mdhip_ctx* ctx, int n, int h, int w, int pass, float* out, int* oh, int* ow, void* hip_stream) {
+    NEED_MODEL(ctx);
+    if (ctx->anchor_free)
+        return fail(ctx, MDHIP_EUNSUPPORTED, "mdhip_tta_input_on: augmented inference is implemented for YOLOv5 (anchor-based) "
+                                             "models only, not for anchor-free (YOLO11) models");
+    if (pass != 1 && pass != 2) return fail(ctx, MDHIP_EINVAL, "mdhip_tta_input_on: pass %d is not a scaled pass (1 or 2)", pass);
+    if (int rc = check_shape(ctx, n, h, w)) return rc;
+    if (ctx->last_n < n || ctx->last_h != h || ctx->last_w != w)
+        return fail(ctx, MDHIP_EINVAL, "mdhip_tta_input_on needs mdhip_preprocess of the same batch first");
+    const TtaPass tp = tta_pass(ctx, h, w, pass);
+    if (oh) *oh = tp.oh;
+    if (ow) *ow = tp.ow;
+    if (!out) return MDHIP_OK;
+    hipStream_t s = (hipStream_t)hip_stream;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int f16 = ctx->dtype == MDHIP_DTYPE_FP16;
+    const size_t in_bytes = (size_t)n * (h / 2) * (w / 2) * 16 * 2, out_bytes = (size_t)n * 3 * tp.oh * tp.ow * 4;
+    uint16_t* in = (uint16_t*)(ctx->arena + ctx->input.off);
+    uint16_t* orig = (uint16_t*)(ctx->arena + ctx->input_orig.off);
+    DevBufs d;
+    void* tmp;
+    HIP_TRY(ctx, d.get(out_bytes, &tmp));
+    // as a scaled pass of mdhip_forward_tta: the batch goes to the scratch copy, the scaled input is written over `input`
+    HIP_TRY(ctx, hipMemcpyAsync(orig, in, in_bytes, hipMemcpyDeviceToDevice, s));
+    hipError_t e = launch_tta_scale(orig, in, n, h, w, tp.sh, tp.sw, tp.oh, tp.ow, tp.flip, f16, s);
+    if (e == hipSuccess) e = launch_s2d_to_nchw_f32(in, (float*)tmp, n, tp.oh, tp.ow, f16, s);
+    // `input` holds the batch again, whatever became of the launches
+    hipError_t back = hipMemcpyAsync(in, orig, in_bytes, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = back;
+    if (e == hipSuccess) e = hipMemcpyAsync(out, tmp, out_bytes, hipMemcpyDeviceToHost, s);
+    hipError_t done = hipStreamSynchronize(s);
+    HIP_TRY(ctx, e);
+    HIP_TRY(ctx, done);
     return MDHIP_OK;
 }
 

@@ -653,6 +653,17 @@ class HipContext:
         """augmented inference (yolov5 _forward_augment) on the batch left by preprocess()"""
         self._check(self.lib.mdhip_forward_tta(self.h, int(n), int(h), int(w), C.c_void_p(stream)), 'mdhip_forward_tta')
 
+    def tta_input_on(self, n, h, w, tta_pass, stream=0):
+        """the network input of scaled pass 1 or 2 of forward_tta on the batch left by preprocess(), as (n, 3, oh, ow) float32 of
+        the stored values (tests; include/mdhip.h: mdhip_tta_input_on).  The context's input holds the batch again afterwards."""
+        oh, ow = C.c_int(), C.c_int()
+        self._check(self.lib.mdhip_tta_input_on(self.h, int(n), int(h), int(w), int(tta_pass), None, C.byref(oh), C.byref(ow),
+                                                C.c_void_p(stream)), 'mdhip_tta_input_on')
+        out = np.empty((n, 3, oh.value, ow.value), dtype=np.float32)
+        self._check(self.lib.mdhip_tta_input_on(self.h, int(n), int(h), int(w), int(tta_pass), _lib.np_ptr(out), C.byref(oh),
+                                                C.byref(ow), C.c_void_p(stream)), 'mdhip_tta_input_on')
+        return out
+
     def last_num_anchors(self):
         return self.lib.mdhip_last_num_anchors(self.h)
 

@@ -16,8 +16,10 @@ compares:
     upsample, copy       repeat 2 x 2, identity; bit for bit
     Detect decode        the fp32 logits of the conv in front decoded in float64 (decode_interval) against the predictions
     DFL decode           yolo11_ref.dfl_decode of the box and class logits, bit for bit (test_dfl_decode_bit_exact)
-    depthwise 3x3        the float32 grouped conv of test_dwconv3x3_kernel, max |d| / max |ref| < its _unit_tol
-    attention            yolo11_ref attention_core, the two figures of test_attention_kernel
+    depthwise 3x3        kernel_elements.depthwise_reference: float64 on the channels the plan's mapping gathers, conv_tolerance,
+                         with a residual the E_res form above; every element
+    attention            kernel_elements.AttentionReference: float64 softmax(q k^T scale) v on the view read in place, every
+                         element against the bound derived there
     ADown pools, CBFuse  yolov9_ref.adown_pool / cbfuse, bit for bit
 
 For YOLOv5 models the weights read back are also pinned against the model: the rows of an op must be round_storage of the convs
@@ -36,6 +38,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_probe as P
+import kernel_elements as KE
 from conv_probe import Verdict, round_storage, ulp_storage, ulp_f32, conv_reference, conv_tolerance, conv_error, U32
 
 # OpKind of mdhip_ctx.h, as mdhip_plan_describe writes it
@@ -234,10 +237,6 @@ def _nchw(x):
     return np.ascontiguousarray(np.transpose(x, (0, 3, 1, 2)))
 
 
-def _unit_tol(dtype):                       # of tests/test_gpu_yolo11.py
-    return 4e-3 if dtype == 'fp16' else 2e-2
-
-
 class Result:
     def __init__(self, num_ops):
         self.num_ops = num_ops
@@ -306,28 +305,22 @@ class StepChecker:
         return out
 
     def depthwise(self, op, a, r, got, w, b, what):
+        assert P.is_storage(w, self.dtype), (op['name'], 'weights read back that are not of the storage type')
         grp, grp_stride, grp_off = op['dw']
-        o = np.arange(w.shape[0])
-        x = torch.from_numpy(np.ascontiguousarray(a[:, (o // grp) * grp_stride + grp_off + o % grp]))
-        ref = F.conv2d(x, torch.from_numpy(w), torch.from_numpy(b), padding=1, groups=w.shape[0])
-        if op['act']:
-            ref = F.silu(ref)
-        ref = ref.numpy().astype(np.float64) + (0 if r is None else np.asarray(r, dtype=np.float64))
-        v = Verdict(what, 9, got, ref, np.full(ref.shape, _unit_tol(self.dtype) * max(np.abs(ref).max(), 1e-30)))
+        v = KE.depthwise_verdict(what, got, a, w, b, r, grp, grp_stride, grp_off, bool(op['act']), self.dtype)
         v.kind = 'depthwise'
         return v
 
     def attention(self, op, a, got, what):
-        import yolo11_ref as R11
-        ref, _ = R11.Forward.attention_core(None, torch.from_numpy(a), op['heads'])
-        ref = ref.numpy().astype(np.float64)
-        tol = _unit_tol(self.dtype)
-        v = Verdict(what, 32, got, ref, np.full(ref.shape, 2 * tol * max(np.abs(ref).max(), 1e-30)))
+        n, c, H, Wd = a.shape
+        heads = op['heads']
+        assert c == heads * KE.HEAD_CH and got.shape == (n, heads * KE.HD, H, Wd), (op['name'], a.shape, got.shape)
+        ref = KE.AttentionReference(_nhwc(a).reshape(n, H * Wd, c), heads, self.dtype)
+
+        def maps(t):                                            # (n, tokens, channels) -> NCHW, as `got` is
+            return _nchw(t.reshape(n, H, Wd, heads * KE.HD))
+        v = Verdict(what, KE.KD, got, maps(ref.y), maps(ref.tol))
         v.kind = 'attention'
-        emean = float(np.abs(got - ref).mean() / max(np.abs(ref).mean(), 1e-30))
-        if not emean < tol / 4:                                 # the second figure of test_attention_kernel
-            v.over = max(v.over, 1)
-            v.what += ' (mean |d| / mean |ref| {:.3e} >= {:.3e})'.format(emean, tol / 4)
         return v
 
     # -- the walk -------------------------------------------------------------------------------------------------------------
