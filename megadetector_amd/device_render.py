@@ -1,7 +1,7 @@
 """
 The device render path: what follows the decode for images that lie in device memory, shared by the preview folder (preview.py),
 the blurred copies (blur.py), the crops (crops.py), the RDE review sheets (rde_review.py), separate_detections.py,
-postprocess_batch_results.py, compare_batch_results.py and visualize_video_output.py.  device_decode.py brings files into
+postprocess_batch_results.py, compare_batch_results.py, visualize_video_output.py and visualize_db.py.  device_decode.py brings files into
 device memory; this module changes and encodes them:
 
   run_chunks      the device leg of a results-file tool: its planned jobs in decode chunks, a chunk that fails handed to the

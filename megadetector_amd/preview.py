@@ -10,7 +10,8 @@ What the reference draws is restated here as a PLAN (render_plan): an ordered li
 patches that PIL rasterises on the host, once per distinct label.  Whatever the plan does not restate -- a box thinner than
 its own outline, ink that may leave a label's patch, a confidence of None -- sends the image to the HOST LEG
 (preview_file_of_host_image), which draws with PIL's own calls in the reference's order, so a run writes the same files
-either way.
+either way.  A caller that asks by name (render_plan(thin_outlines=True): visualize_db.py, whose ground-truth boxes are often
+tiny) keeps a box thinner than its outline on the device: thin_outline_ops takes its pixels from Pillow, once per box size.
 
 Two deliberate differences from the reference script: the HTML index is not written, and an image whose resize target is not
 positive is skipped and counted (the reference asserts, which its caller reports as a rendering failure of that image: no
@@ -260,6 +261,11 @@ def box_edges(bbox, width, height, expansion):
     and, only then, clamped to the image"""
     x1, y1, w_box, h_box = bbox
     ymin, xmin, ymax, xmax = y1, x1, y1 + h_box, x1 + w_box          # render_detection_bounding_boxes :686-687
+    return corner_edges(ymin, xmin, ymax, xmax, width, height, expansion)
+
+
+def corner_edges(ymin, xmin, ymax, xmax, width, height, expansion):
+    """box_edges for a box that is given as draw_bounding_box_on_image takes it: normalised (ymin, xmin, ymax, xmax)"""
     left, right, top, bottom = xmin * width, xmax * width, ymin * height, ymax * height
     if expansion > 0:
         left -= expansion
@@ -378,6 +384,58 @@ def outline_ops(left, top, right, bottom, thickness, rgb):
             [OP_RECT, x0, y0 + t, x0 + t - 1, y1 - t, c, 0, 0], [OP_RECT, x1 - t + 1, y0 + t, x1, y1 - t, c, 0, 0]]
 
 
+def is_thin(left, top, right, bottom, thickness):
+    """whether outline_ops hands this box over: narrower or lower than twice its outline"""
+    return int(right) - int(left) + 1 < 2 * thickness or int(bottom) - int(top) + 1 < 2 * thickness
+
+
+_THIN_OUTLINES = {}
+
+
+def _thin_outline_rectangles(width, height, thickness):
+    """What ImageDraw.rectangle(outline=, width=thickness) sets for a box of width x height pixels, rasterised by Pillow once on
+    a scratch canvas with room for what spills (its bars are as long as the outline is thick, whatever the box): ->
+    [(dx0, dy0, dx1, dy1)] inclusive, relative to the box's top left corner -- the runs of every row, equal runs of consecutive
+    rows as one rectangle"""
+    key = (width, height, thickness)
+    if key not in _THIN_OUTLINES:
+        import numpy as np
+        from PIL import Image, ImageDraw
+        if len(_THIN_OUTLINES) > 4096:
+            _THIN_OUTLINES.clear()
+        m = 2 * thickness + 2
+        canvas = Image.new('L', (width + 2 * m, height + 2 * m), 0)
+        ImageDraw.Draw(canvas).rectangle([(m, m), (m + width - 1, m + height - 1)], outline=255, width=thickness)
+        ink = np.asarray(canvas) != 0
+        assert not (ink[0].any() or ink[-1].any() or ink[:, 0].any() or ink[:, -1].any()), 'the outline reaches the scratch canvas edge'
+        rectangles, open_runs = [], {}                                    # (x0, x1) -> the row the rectangle began in
+        for y in range(ink.shape[0] + 1):
+            runs = []
+            if y < ink.shape[0] and ink[y].any():
+                steps = np.diff(np.concatenate(([0], ink[y].astype(np.int8), [0])))
+                runs = list(zip(np.flatnonzero(steps == 1).tolist(), (np.flatnonzero(steps == -1) - 1).tolist()))
+            for run in [r for r in open_runs if r not in runs]:
+                rectangles.append((run[0] - m, open_runs.pop(run) - m, run[1] - m, y - 1 - m))
+            for run in runs:
+                open_runs.setdefault(run, y)
+        _THIN_OUTLINES[key] = sorted(rectangles, key=lambda r: (r[1], r[0]))
+    return _THIN_OUTLINES[key]
+
+
+def thin_outline_ops(left, top, right, bottom, thickness, rgb):
+    """
+    ImageDraw.rectangle([(left, top), (right, bottom)], outline=color, width=thickness) for a box outline_ops hands over, one
+    narrower or lower than 2 * thickness pixels: there Pillow's bars overlap, are not solid and leave the box, so the pixels
+    are Pillow's own -- rasterised once per (width, height, thickness) and kept, as label_patch keeps its labels -- as solid
+    rectangles offset to int(left), int(top).  Pinned against Pillow for thicknesses 1 .. 8, in the image and across its edge
+    (tests/test_visualize_db_cpu.py).  Any box is drawn right; only a thin one is worth a scratch canvas.
+    """
+    _check_rectangle(left, top, right, bottom)
+    x0, y0, x1, y1 = int(left), int(top), int(right), int(bottom)
+    c = rgb[0] | rgb[1] << 8 | rgb[2] << 16
+    return [[OP_RECT, x0 + a, y0 + b, x0 + p, y0 + q, c, 0, 0] for a, b, p, q in _thin_outline_rectangles(x1 - x0 + 1, y1 - y0 + 1, thickness)]
+
+
 _PATCHES = {}
 
 
@@ -424,6 +482,32 @@ class RenderPlan:
         return self
 
 
+def box_outline_ops(left, top, right, bottom, thickness, rgb, thin_outlines=False):
+    """outline_ops, and with thin_outlines thin_outline_ops for the boxes outline_ops hands over"""
+    if thin_outlines:
+        _check_rectangle(left, top, right, bottom)
+        if is_thin(left, top, right, bottom, thickness):
+            return thin_outline_ops(left, top, right, bottom, thickness, rgb)
+    return outline_ops(left, top, right, bottom, thickness, rgb)
+
+
+def add_label_ops(plan, font, font_key, strings, left, top, bottom, height, vtextalign, color_name):
+    """appends to `plan` one patch per label line of a box in the order PIL draws them (stacked_labels); raises HostLeg for a
+    label the patches do not restate"""
+    for padded, margin, (x0, y0), (x1, y1), _ in stacked_labels(font, strings, left, top, bottom, height, vtextalign):
+        bbox = font.getbbox(padded)
+        if bbox[0] < 0 or bbox[1] < 0:
+            raise HostLeg('ink of {!r} may leave its label'.format(padded))
+        if not all(isinstance(v, int) or float(v).is_integer() for v in (x0, y0, x1, y1)):
+            raise HostLeg('a label of a fractional size')
+        x0, y0, x1, y1 = int(x0), int(y0), int(x1), int(y1)
+        w, h = x1 - x0 + 1, y1 - y0 + 1
+        if w < 1 or h < 1 or w > 32767 or h > 32767:
+            raise HostLeg('a label of {} x {} pixels'.format(w, h))
+        data = label_patch(font, font_key, padded, margin, (w, h), color_name)
+        plan.ops.append([OP_PATCH, x0, y0, w, h, plan.add_patch(data), 0, 0])
+
+
 def _label_lines(det, label_map, classification_label_map, classification_confidence_threshold, custom_string=None,
                  unlabelled_classifications=False):
     """(the label lines of one drawn detection, the class its colour is of); None for a detection with classifications when
@@ -451,7 +535,7 @@ def _check_custom_strings(custom_strings, listed):
 
 def render_plan(detections, width, height, options, label_map=None, labels=True, classification_label_map=None,
                 classification_confidence_threshold=None, *, colormap=None, vtextalign='top', custom_strings=None,
-                unlabelled_classifications=False, category_thresholds=None):
+                unlabelled_classifications=False, thin_outlines=False, category_thresholds=None):
     """
     render_detection_bounding_boxes(detections, image, label_map=..., confidence_threshold, thickness, expansion,
     label_font_size, label_font, box_sort_order) for an image of width x height (the RESIZED size) as a RenderPlan: per box
@@ -463,7 +547,8 @@ def render_plan(detections, width, height, options, label_map=None, labels=True,
     colormap: box_color's; vtextalign: stacked_labels'; custom_strings: None, or one string per detection of the list, indexed
     as the reference indexes it -- by the position in the list its loop runs over, which is the list sorted by confidence
     when there is a sort order, not the file's; unlabelled_classifications: _label_lines'.  What follows
-    classification_confidence_threshold is given by name (category_thresholds stays the last argument).
+    classification_confidence_threshold is given by name (category_thresholds stays the last argument).  thin_outlines: a box
+    thinner than twice its outline is drawn by thin_outline_ops; without it such a box is a HostLeg.
     Raises HostLeg or RenderFailure.
     """
     thickness, expansion, font_size = resolve_sizes(options, width)
@@ -485,25 +570,14 @@ def render_plan(detections, width, height, options, label_map=None, labels=True,
         except (TypeError, ValueError) as e:
             raise RenderFailure(str(e))
         left, top, right, bottom = box_edges(det['bbox'], width, height, expansion)
-        plan.ops += outline_ops(left, top, right, bottom, thickness, rgb)
+        plan.ops += box_outline_ops(left, top, right, bottom, thickness, rgb, thin_outlines)
         plan.labels.append(strings[0])
         plan.order.append(next(i for i, d in enumerate(listed) if d is det))
         if not any(strings):                                                     # :1061
             continue
         if font is None:
             font = load_font(options.label_font, font_size)
-        for padded, margin, (x0, y0), (x1, y1), _ in stacked_labels(font, strings, left, top, bottom, height, vtextalign):
-            bbox = font.getbbox(padded)
-            if bbox[0] < 0 or bbox[1] < 0:
-                raise HostLeg('ink of {!r} may leave its label'.format(padded))
-            if not all(isinstance(v, int) or float(v).is_integer() for v in (x0, y0, x1, y1)):
-                raise HostLeg('a label of a fractional size')
-            x0, y0, x1, y1 = int(x0), int(y0), int(x1), int(y1)
-            w, h = x1 - x0 + 1, y1 - y0 + 1
-            if w < 1 or h < 1 or w > 32767 or h > 32767:
-                raise HostLeg('a label of {} x {} pixels'.format(w, h))
-            data = label_patch(font, (options.label_font, font_size), padded, margin, (w, h), color_name)
-            plan.ops.append([OP_PATCH, x0, y0, w, h, plan.add_patch(data), 0, 0])
+        add_label_ops(plan, font, (options.label_font, font_size), strings, left, top, bottom, height, vtextalign, color_name)
     return plan
 
 
@@ -669,6 +743,6 @@ class PreviewProduct(Product):
 
 
 __all__ = ['HostLeg', 'NO_LABELS', 'PreviewOptions', 'RenderFailure', 'RenderPlan', 'box_edges', 'classified_label_lines',
-           'drawn_detections', 'is_rendered', 'label_box', 'label_string', 'output_name', 'outline_ops', 'preview_file_of_host_image',
-           'previews_of_device_images', 'rectangles_to_blur', 'render_plan', 'render_with_pil', 'resolve_sizes', 'stacked_labels',
-           'target_size', 'write_preview']
+           'corner_edges', 'drawn_detections', 'is_rendered', 'label_box', 'label_string', 'output_name', 'outline_ops',
+           'preview_file_of_host_image', 'previews_of_device_images', 'rectangles_to_blur', 'render_plan', 'render_with_pil',
+           'resolve_sizes', 'stacked_labels', 'target_size', 'thin_outline_ops', 'write_preview']
