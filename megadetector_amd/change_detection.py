@@ -33,7 +33,6 @@ host model and counted in 'host_pairs'.
 
 import argparse
 import csv
-import glob
 import io
 import os
 import random
@@ -43,8 +42,8 @@ from enum import Enum, auto
 from pathlib import Path
 from typing import Optional
 
-#: reference path_utils.IMG_EXTENSIONS
-IMG_EXTENSIONS = ('.jpg', '.jpeg', '.gif', '.png', '.tif', '.tiff', '.bmp', '.webp', '.avif')
+from .ref_utils import find_images
+
 #: significant regions a pair's device result has room for; a pair with more goes to the host model
 REGION_CAP = 256
 COLUMNS = ('camera', 'image', 'prev_image', 'motion_detected', 'diff_percentage', 'num_regions', 'regions')
@@ -112,14 +111,6 @@ def check_options(options, backend='host'):
         raise ValueError('ignore_fraction must be between -1.0 and 1.0')
     return jpeg_host.change_options(k, 1 if options.threshold_type == ThresholdType.OTSU else 0, options.threshold, d,
                                     options.dilate_iterations, options.min_area, options.ignore_fraction, REGION_CAP)
-
-
-def find_images(folder_path):
-    """path_utils.find_images(folder, recursive=True, return_relative_paths=False)"""
-    assert os.path.isdir(folder_path), '{} is not a folder'.format(folder_path)
-    strings = glob.glob(os.path.join(folder_path, '**', '*.*'), recursive=True)
-    image_files = sorted(s for s in strings if os.path.splitext(s)[1].lower() in IMG_EXTENSIONS)
-    return [fn.replace('\\', '/') for fn in image_files]
 
 
 def empty_result():
@@ -217,7 +208,7 @@ def result_row(camera_name, prev_image, curr_image, motion_result):
 def _camera_images(folder_path):
     folder_path = Path(folder_path)
     camera_name = folder_path.name
-    image_files = find_images(folder_path)
+    image_files = find_images(folder_path, recursive=True)
     if len(image_files) == 0:
         print('No images found in {}'.format(folder_path))
     else:

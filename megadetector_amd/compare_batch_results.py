@@ -44,7 +44,6 @@ from functools import partial
 
 from . import device_render as DR
 from . import preview as PV
-from .crops import encode_windows
 from .postprocess_batch_results import SAVE_QUALITY, flatten_path, open_image, resized_size, write_html_image_list
 
 THICKNESS_A, THICKNESS_B = 4, 2                  # _render_image_pair: thickness=4 for A, 2 for B
@@ -477,35 +476,26 @@ def group_bytes(group):
 
 def _render_chunk_device(ctx, torch, device, groups, clock, options, counts):
     """The jobs of one chunk of files, by the device render path.  -> the jobs the host leg has to make"""
-    from .device_decode import decode_stage
-    pixels, refused, _ = decode_stage(ctx, torch, device, options.image_folder, [g[0]['file'] for g in groups],
-                                      {g[0]['file']: g[0]['probe'] for g in groups}, counts, clock)
+    heads, pixels, refused, _ = DR.decode_front(ctx, torch, device, [g[0] for g in groups], options.image_folder, counts, clock)
+    refused = {j['file'] for j in refused}
     host = [j for g in groups for j in g if j['file'] in refused]    # the device did not decode it
     groups = [g for g in groups if g[0]['file'] not in refused]
     if not groups:
         return host
     # ONE shared image per distinct file: its decoded pixels, or their resampled form
-    sizes = [g[0]['size'] for g in groups]
-    shared, resampled = DR.resample_stage(ctx, torch, device, [pixels[g[0]['file']] for g in groups],
-                                          [g[0]['source_size'] for g in groups], sizes, clock)
-    counts['resample_calls'] += resampled
+    sizes = [j['size'] for j in heads]
+    shared = DR.resample_jobs(ctx, torch, device, heads, pixels, counts, clock)
+    jobs = [j for g in groups for j in g]
     # ONE fan-out draw: every job that draws anything gets an image of its own, made from its file's shared image
-    jobs = [(k, j) for k, g in enumerate(groups) for j in g]
-    drawn = [(k, j) for k, j in jobs if j['plan'].ops]
+    drawn = [(k, j) for k, g in enumerate(groups) for j in g if j['plan'].ops]
     dests = [torch.empty(sizes[k][0] * sizes[k][1] * 3, dtype=torch.uint8, device=device) for k, _ in drawn]
     if DR.draw_plans_from(ctx, [t.data_ptr() for t in shared], sizes, [t.data_ptr() for t in dests], [k for k, _ in drawn],
                           [j['plan'] for _, j in drawn], device, clock=clock):
         counts['draw_calls'] += 1
     image_of = {id(j): t for (_, j), t in zip(drawn, dests)}
-    rendered = [image_of.get(id(j), shared[k]) for k, j in jobs]      # (a job without an operation: the shared image itself)
-    with clock('encode'):
-        data = encode_windows(ctx, [t.data_ptr() for t in rendered], [sizes[k][0] * 3 for k, _ in jobs],
-                              [(0, 0, sizes[k][0], sizes[k][1]) for k, _ in jobs], SAVE_QUALITY)
-    counts['encode_calls'] += 1
-    for (_, j), file_bytes in zip(jobs, data):
-        with open(j['output_path'], 'wb') as f:
-            f.write(file_bytes)
-    counts['gpu'] += len(jobs)
+    rendered = [image_of.get(id(j), shared[k]) for k, g in enumerate(groups) for j in g]      # (no operation: the shared image itself)
+    DR.encode_and_write(jobs, rendered, counts, partial(DR.encode_whole, ctx, clock, SAVE_QUALITY),
+                        lambda job, data: DR.write_bytes(job['output_path'], data))
     return host
 
 

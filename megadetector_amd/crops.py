@@ -110,11 +110,12 @@ def is_jpeg_name(name):
     return os.path.splitext(name)[1].lower() in _JPEG_EXTENSIONS
 
 
-def encode_windows(ctx, ptrs, pitches, rects, quality, stream=0):
+def encode_windows(ctx, ptrs, pitches, rects, quality, stream=0, comments=None):
     """
     JPEG files of windows of device images: ptrs[i] the first pixel of the image rects[i] (from crop_rectangle) lies in,
     pitches[i] its bytes a row.  ONE call of the encoder for all of them and one read-back; a second call with the size
-    the first reported when the guess at the output was too small.
+    the first reported when the guess at the output was too small.  comments: per window None or the bytes of the COM
+    segment Pillow carries over from a source; a window with one is written by jpeg_host.sampled_file, not jfif_file.
     """
     from .device_render import read_encoded
     if not rects:
@@ -126,7 +127,12 @@ def encode_windows(ctx, ptrs, pitches, rects, quality, stream=0):
     host, offs, lens, _ = read_encoded(
         lambda out_ptr, capacity: ctx.jpeg_encode(wins, sizes, list(pitches), quality, out_ptr, capacity, stream),
         capacity, 'cuda:{}'.format(ctx.device), 'mdhip_jpeg_encode')
-    return [jpeg_host.jfif_file(w, h, quality, host[o:o + n].tobytes()) for (w, h), o, n in zip(sizes, offs, lens)]
+    scans = [host[o:o + n].tobytes() for o, n in zip(offs, lens)]
+    if not comments or not any(comments):
+        return [jpeg_host.jfif_file(w, h, quality, scan) for (w, h), scan in zip(sizes, scans)]
+    ql, qc = jpeg_host.quant_tables(quality)
+    return [jpeg_host.sampled_file(w, h, ql, qc, 2, scan, b'', comment) if comment else jpeg_host.jfif_file(w, h, quality, scan)
+            for (w, h), scan, comment in zip(sizes, scans, comments)]
 
 
 def _pick(image_file, width, height, detections, options, category_ids, warn):

@@ -1,11 +1,19 @@
 """
 The device render path: what follows the decode for images that lie in device memory, shared by the preview folder (preview.py),
 the blurred copies (blur.py), the crops (crops.py), the RDE review sheets (rde_review.py), separate_detections.py,
-postprocess_batch_results.py, compare_batch_results.py, visualize_video_output.py and visualize_db.py.  device_decode.py brings files into
-device memory; this module changes and encodes them:
+postprocess_batch_results.py, compare_batch_results.py, visualize_video_output.py, visualize_db.py, resize_images.py and
+resize_coco_dataset.py.  device_decode.py brings files into device memory; this module changes and encodes them:
 
   run_chunks      the device leg of a results-file tool: its planned jobs in decode chunks, a chunk that fails handed to the
                   host leg, the host leg's jobs in their order
+  plan_each       the planning loop in front of it: plan(item), or the host leg for an item whose planning raises
+  job_bytes       the device bytes of a planned image in its decode chunk
+  decode_front    the front of a chunk: ONE device_decode.decode_stage for its distinct files; the jobs of a refused file are
+                  the host leg's
+  render_jobs     the tail of a chunk: resample_jobs, draw_plans, encode_and_write
+  resample_jobs   resample_stage for the jobs whose 'size' is not their 'source_size', counted
+  encode_and_write  the tool's encoder call or calls, then -- after this last device call of the chunk -- its files, counted
+  encode_whole    the encoder of the tools that save as Image.save does: ONE crops.encode_windows call for whole images
   resample_stage  ONE mdhip_resample_lanczos call for the images of a chunk whose size changes
   blur_rects     ONE mdhip_blur_regions call for the rectangles of a batch of images
   draw_plans      ONE mdhip_draw_ops call for the preview.RenderPlan of each image, the label patches of all of them uploaded
@@ -109,6 +117,71 @@ def resample_stage(ctx, torch, device, sources, source_sizes, sizes, clock):
                                  [source_sizes[k][0] * 3 for k in resized], [out[k].data_ptr() for k in resized],
                                  [sizes[k] for k in resized], [sizes[k][0] * 3 for k in resized])
     return out, bool(resized)
+
+
+def plan_each(items, plan):
+    """The planning loop of a device leg, before any pixel is decoded: -> (plan(item) of every item, the items whose
+    planning raised anything -- the host leg's, which then raises what the reference raises), both in the items' order"""
+    planned, host = [], []
+    for item in items:
+        try:
+            planned.append(plan(item))
+        except Exception:
+            host.append(item)
+    return planned, host
+
+
+def job_bytes(job):
+    """device bytes of a planned image in its decode chunk: its decoded pixels and its resized ones"""
+    (w, h), (tw, th) = job['source_size'], job['size']
+    return w * h * 3 + (tw * th * 3 if (tw, th) != (w, h) else 0)
+
+
+def decode_front(ctx, torch, device, jobs, image_base, counts, clock, keep_coefficients=False):
+    """The front of a chunk: ONE device_decode.decode_stage for the distinct files (relative to image_base) of `jobs`, each a
+    dict with its 'file' and that file's 'probe'.  -> (the jobs whose file the GPU's decoder took, their pixel tensors -- jobs
+    of one file share one --, the jobs of the refused files in their order: the host leg's, decode_stage's coefficients, which
+    with keep_coefficients keep the sources' planes alive as long as the caller holds them)"""
+    from .device_decode import decode_stage
+    probes = {j['file']: j['probe'] for j in jobs}
+    pixels, refused, coefficients = decode_stage(ctx, torch, device, image_base, list(probes), probes, counts, clock, keep_coefficients)
+    taken = [j for j in jobs if j['file'] not in refused]
+    return taken, [pixels[j['file']] for j in taken], [j for j in jobs if j['file'] in refused], coefficients
+
+
+def resample_jobs(ctx, torch, device, jobs, tensors, counts, clock):
+    """resample_stage for `tensors`, the pixels of `jobs` at their 'source_size': -> the images at the jobs' 'size', the tensor
+    itself where the size stays; counts['resample_calls'] moves when the call was made"""
+    out, called = resample_stage(ctx, torch, device, tensors, [j['source_size'] for j in jobs], [j['size'] for j in jobs], clock)
+    counts['resample_calls'] += called
+    return out
+
+
+def write_bytes(path, data):
+    with open(path, 'wb') as f:
+        f.write(data)
+
+
+def encode_and_write(jobs, tensors, counts, encode, write):
+    """The end of a chunk: encode(tensors, jobs) -> (the files, the encoder calls made) makes the tool's encoder call or calls
+    under its own clock keys; then, after this last device call of the chunk, write(job, file) for each job in order"""
+    files, calls = encode(tensors, jobs)
+    counts['encode_calls'] += calls
+    for job, data in zip(jobs, files):
+        write(job, data)
+    counts['gpu'] += len(jobs)
+
+
+def render_jobs(ctx, torch, device, jobs, tensors, counts, clock, encode, write, draw=True):
+    """The tail of a chunk for `jobs` (not empty) with their decoded `tensors`: resample_jobs, with `draw` ONE draw_plans
+    call for the jobs' 'plan' in place on the result (counts['draw_calls'] moves when the call was made), then
+    encode_and_write.  separate_detections, whose copies are never resized and are blurred first, calls blur_and_draw and
+    encode_and_write itself."""
+    tensors = resample_jobs(ctx, torch, device, jobs, tensors, counts, clock)
+    if draw:
+        counts['draw_calls'] += draw_plans(ctx, [t.data_ptr() for t in tensors], [j['size'] for j in jobs], [j['plan'] for j in jobs], device,
+                                           clock=clock)
+    encode_and_write(jobs, tensors, counts, encode, write)
 
 
 # ---- blur and draw -------------------------------------------------------------------------------------------------------------
@@ -254,6 +327,17 @@ def encode_kept(ctx, device, tensors, jobs, source_ptrs, stream=0):
                                                        rect_image, rects, out_ptr, capacity, stream),
         _sampled_guess(sizes), device, 'mdhip_jpeg_encode_kept')
     return [None if st else _sampled_file(j, host[o:o + n].tobytes()) for j, o, n, st in zip(jobs, offs, lens, status)]
+
+
+def encode_whole(ctx, clock, quality, tensors, jobs):
+    """encode_and_write's encoder of the tools whose reference saves with Image.save: ONE crops.encode_windows call ('encode'
+    on the clock) for the whole images `tensors` of the jobs' 'size' at `quality`, with a job's 'comment' where it has one"""
+    from .crops import encode_windows
+    sizes = [j['size'] for j in jobs]
+    with clock('encode'):
+        files = encode_windows(ctx, [t.data_ptr() for t in tensors], [w * 3 for w, _ in sizes], [(0, 0, w, h) for w, h in sizes], quality,
+                               comments=[j.get('comment') for j in jobs])
+    return files, 1
 
 
 def encode_copies(ctx, device, tensors, jobs, source_ptrs, clock, reencode_flagged, stream=0):

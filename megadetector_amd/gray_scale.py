@@ -237,7 +237,7 @@ def _device_leg(jobs, out, device, ctx, counts, profile):
 
 
 def main(argv=None):
-    from .change_detection import find_images
+    from .ref_utils import find_images
     parser = argparse.ArgumentParser(description='The fraction of gray pixels (R == G == B) of every image of a folder, as CSV')
     parser.add_argument('folder')
     parser.add_argument('--output_csv', default=None, help='the file the rows go to (default: standard output)')
@@ -246,7 +246,7 @@ def main(argv=None):
     parser.add_argument('--backend', choices=('gpu', 'host'), default='gpu')
     parser.add_argument('--device', type=int, default=0)
     args = parser.parse_args(argv)
-    files = find_images(args.folder)
+    files = find_images(args.folder, recursive=True)
     counts = {}
     fractions = gray_scale_fractions(files, (args.crop_top, args.crop_bottom), backend=args.backend, device=args.device, counts=counts)
     lines = ['image,gray_scale_fraction']

@@ -45,9 +45,7 @@ import json
 import math
 import os
 import random
-import re
 import sys
-import unicodedata
 import urllib.parse
 import uuid
 from collections import defaultdict
@@ -57,8 +55,8 @@ import numpy as np
 
 from . import device_render as DR
 from . import preview as PV
-from .crops import encode_windows
 from .preview import resized_size
+from .ref_utils import clean_filename, flatten_path, insert_before_extension, open_image  # noqa: F401  (compare_batch_results' too)
 from .separate_detections import get_typical_confidence_threshold_from_results
 
 DEFAULT_NEGATIVE_CLASSES = ['empty']
@@ -126,42 +124,6 @@ DS_NEGATIVE, DS_POSITIVE, DS_ALMOST = 0, 1, 5                    # DetectionStat
 
 
 # ---- the reference's small helpers -----------------------------------------------------------------------------------------------
-
-VALID_FILENAME_CHARS = '~-_.() abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789'      # utils/path_utils.py:46
-SEPARATOR_CHARS = ':\\/'
-CHAR_LIMIT = 255
-
-
-def clean_filename(filename, allow_list=VALID_FILENAME_CHARS, char_limit=CHAR_LIMIT, replace_whitespace=None):
-    """utils/path_utils.py clean_filename with the arguments it is given here"""
-    separator = '/'
-    if '\\' in filename:
-        separator = '\\'
-    filename = filename.replace('\\', '/')
-    filename = separator.join([c.strip() for c in filename.split('/')])
-    if separator == '\\':
-        filename = filename.replace('/', '\\')
-    cleaned = unicodedata.normalize('NFKD', filename).encode('ASCII', 'ignore').decode()
-    cleaned = ''.join([c for c in cleaned if c in allow_list])
-    if char_limit is not None:
-        cleaned = cleaned[:char_limit]
-    if replace_whitespace is not None:
-        cleaned = re.sub(r'\s+', replace_whitespace, cleaned)
-    return cleaned
-
-
-def flatten_path(pathname):
-    """utils/path_utils.py flatten_path: clean_path, then every separator becomes '~'"""
-    s = clean_filename(pathname, allow_list=VALID_FILENAME_CHARS + SEPARATOR_CHARS)
-    for c in SEPARATOR_CHARS:
-        s = s.replace(c, '~')
-    return s
-
-
-def insert_before_extension(filename, s, separator='.'):
-    name, ext = os.path.splitext(filename)
-    return '{}{}{}{}'.format(name, separator, s, ext)
-
 
 def get_max_conf(im):
     """utils/ct_utils.py get_max_conf"""
@@ -471,26 +433,6 @@ def html_info(decision, sample_name, options):
 
 # ---- rendering: the host leg -------------------------------------------------------------------------------------------------------
 
-def open_image(input_file):
-    """visualization_utils.open_image :103-176 for a local file: lazy, as there (a truncated file raises where it is resized)"""
-    from PIL import Image
-    from .feed import EXIF_IMAGE_ROTATIONS
-    image = Image.open(input_file)
-    if image.mode not in ('RGBA', 'RGB', 'L', 'I;16'):
-        raise AttributeError('Image {} uses unsupported mode {}'.format(input_file, image.mode))
-    if image.mode == 'RGBA' or image.mode == 'L':
-        image = image.convert(mode='RGB')
-    try:
-        exif = image._getexif()
-        orientation = exif.get(274, None)
-        if (orientation is not None) and (orientation != 1):
-            assert orientation in EXIF_IMAGE_ROTATIONS, 'Mirrored rotations are not supported'
-            image = image.rotate(EXIF_IMAGE_ROTATIONS[orientation], expand=True)
-    except Exception:
-        pass
-    return image
-
-
 def draw_arguments(decision, detection_categories, classification_categories):
     """What render_detection_bounding_boxes is called with at :540-547, as preview.render_plan and preview.render_with_pil
     take it: -> (PreviewOptions, keyword arguments)"""
@@ -574,51 +516,25 @@ def _plan_job(decision, detection_categories, classification_categories, options
             'size': target, 'plan': plan}
 
 
-def _job_bytes(job):
-    """device bytes of a planned image in its decode chunk: its decoded pixels and its resized ones"""
-    (w, h), (tw, th) = job['source_size'], job['size']
-    return w * h * 3 + (tw * th * 3 if (tw, th) != (w, h) else 0)
-
-
 def _render_chunk_device(ctx, torch, device, jobs, clock, options, counts):
     """The images of one chunk, by the device render path.  -> the decisions the host leg has to render"""
-    from .device_decode import decode_stage
-    pixels, refused, _ = decode_stage(ctx, torch, device, options.image_base_dir, [j['file'] for j in jobs],
-                                      {j['file']: j['probe'] for j in jobs}, counts, clock)
-    host = [j['decision'] for j in jobs if j['file'] in refused]          # the device did not decode it
-    jobs = [j for j in jobs if j['file'] not in refused]
-    if not jobs:
-        return host
-    sizes = [j['size'] for j in jobs]
-    rendered, resampled = DR.resample_stage(ctx, torch, device, [pixels[j['file']] for j in jobs], [j['source_size'] for j in jobs],
-                                            sizes, clock)
-    counts['resample_calls'] += resampled
-    if DR.draw_plans(ctx, [t.data_ptr() for t in rendered], sizes, [j['plan'] for j in jobs], device, clock=clock):
-        counts['draw_calls'] += 1
-    with clock('encode'):
-        files = encode_windows(ctx, [t.data_ptr() for t in rendered], [w * 3 for w, _ in sizes], [(0, 0, w, h) for w, h in sizes],
-                               SAVE_QUALITY)
-    counts['encode_calls'] += 1
-    for j, data in zip(jobs, files):
-        def save(path, data=data):
-            with open(path, 'wb') as f:
-                f.write(data)
-        j['decision']['sample_name'] = _save(save, options.output_dir, j['decision']['category_string'], j['sample_name'])
-    counts['gpu'] += len(jobs)
-    return host
+    jobs, tensors, host, _ = DR.decode_front(ctx, torch, device, jobs, options.image_base_dir, counts, clock)
+
+    def write(job, data):
+        decision = job['decision']
+        decision['sample_name'] = _save(partial(DR.write_bytes, data=data), options.output_dir, decision['category_string'], job['sample_name'])
+
+    if jobs:
+        DR.render_jobs(ctx, torch, device, jobs, tensors, counts, clock, partial(DR.encode_whole, ctx, clock, SAVE_QUALITY), write)
+    return [j['decision'] for j in host]
 
 
 def _render_device(decisions, detection_categories, classification_categories, options, ctx, counts, profile):
     """-> the decisions that go to the host leg, in their order"""
     import torch
-    host, planned = [], []
-    for decision in decisions:
-        try:
-            planned.append(_plan_job(decision, detection_categories, classification_categories, options))
-        except Exception:
-            host.append(decision)
+    planned, host = DR.plan_each(decisions, lambda d: _plan_job(d, detection_categories, classification_categories, options))
     place = {id(d): i for i, d in enumerate(decisions)}
-    return DR.run_chunks(ctx, torch, planned, _job_bytes, partial(_render_chunk_device, options=options, counts=counts), counts,
+    return DR.run_chunks(ctx, torch, planned, DR.job_bytes, partial(_render_chunk_device, options=options, counts=counts), counts,
                          profile, host, DR.file_twice, lambda job: [job['decision']], lambda d: place[id(d)])
 
 

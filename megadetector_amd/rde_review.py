@@ -500,7 +500,7 @@ def write_review_folder(rde_results, review_options, backend='gpu', device=0, ct
         from .hip_backend import HipContext
         with HipContext.images_or(ctx, device) as ctx:
             _render_device(flat, folder, review_options, ctx, ctx.device, counts)
-    RD._write_json(os.path.join(folder, INDEX_NAME), index_for_folder(rde_results, rde_options, review_options))
+    RD.write_json(os.path.join(folder, INDEX_NAME), index_for_folder(rde_results, rde_options, review_options), force_str=True)
     counts['folder'] = folder
     return counts
 
@@ -575,7 +575,7 @@ def remove_repeat_detections(input_file, output_file, filtering_dir_or_index, fi
     out.suspicious_detections = suspicious
     out.n_bbox_changes = n_bbox_changes
     if output_file:
-        RD._write_json(output_file, RD.results_for_file(results))
+        RD.write_json(output_file, RD.results_for_file(results), force_str=True)
     return out
 
 

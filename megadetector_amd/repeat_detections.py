@@ -37,8 +37,7 @@ import sys
 
 import numpy as np
 
-#: reference path_utils.IMG_EXTENSIONS
-IMG_EXTENSIONS = ('.jpg', '.jpeg', '.gif', '.png', '.tif', '.tiff', '.bmp', '.webp', '.avif')
+from .ref_utils import IMG_EXTENSIONS, write_json
 
 #: layout of mdhip_rde_box / mdjpeg_rde_box
 BOX_DTYPE = np.dtype([('x', '<f8'), ('y', '<f8'), ('w', '<f8'), ('h', '<f8'), ('group', '<i4'), ('category', '<i4')])
@@ -329,14 +328,6 @@ def mark_repeat_detections(results, options=None, backend='gpu', device=0):
     return out
 
 
-def _write_json(path, content):
-    parent = os.path.dirname(path)
-    if parent:
-        os.makedirs(parent, exist_ok=True)
-    with open(path, 'w', newline='\n', encoding='utf-8') as f:
-        json.dump(content, f, indent=1, default=str, ensure_ascii=True)
-
-
 def results_for_file(results):
     """what the reference's write_api_results writes of marked results -- without its rounding and without the keys its table
     adds: 'failure' dropped where it is None, format_version a string, max_detection_conf dropped for format >= 1.3"""
@@ -372,8 +363,8 @@ def index_for_file(rde_results, options):
 
 
 def write_outputs(rde_results, options, output_file_name):
-    _write_json(output_file_name, results_for_file(rde_results.detectionResults))
-    _write_json(output_file_name + '.rde_index.json', index_for_file(rde_results, options))
+    write_json(output_file_name, results_for_file(rde_results.detectionResults), force_str=True)
+    write_json(output_file_name + '.rde_index.json', index_for_file(rde_results, options), force_str=True)
 
 
 def find_repeat_detections(input_filename, output_file_name=None, options=None, backend='gpu', device=0):

@@ -35,64 +35,13 @@ from collections import defaultdict
 from functools import partial
 
 from . import device_render as DR
-from .blur import DEFAULT_BLUR_QUALITY as DEFAULT_QUALITY
-from .feed import EXIF_IMAGE_ROTATIONS
 from .gray_scale import _reference_truncation_rule
 from .preview import HostLeg
+from .ref_utils import DEFAULT_SAVE_QUALITY as DEFAULT_QUALITY
+from .ref_utils import ORIENTATION, exif_preserving_save, exif_without, open_image, write_json
 from .resize_images import _resize_image, render_chunk, resize_target
 
 COUNT_KEYS = ('files', 'omitted', 'gpu', 'host', 'files_decoded_gpu', 'decode_chunks', 'resample_calls', 'encode_calls')
-ORIENTATION = 274               # the id of 'Orientation' in PIL.ExifTags: what _remove_exif_tags pops
-
-
-def open_image(input_file):
-    """visualization_utils.open_image for a file: feed.load_image without the load -- the mode check, 'RGBA' / 'L' converted,
-    the EXIF rotation; no pixel is decoded unless one of the two made a new image"""
-    from PIL import Image
-    image = Image.open(input_file)
-    if image.mode not in ('RGBA', 'RGB', 'L', 'I;16'):
-        raise AttributeError('Image {} uses unsupported mode {}'.format(input_file, image.mode))
-    if image.mode in ('RGBA', 'L'):
-        image = image.convert(mode='RGB')
-    try:
-        exif = image._getexif()
-        orientation = exif.get(ORIENTATION, None)
-        if orientation is not None and orientation != 1:
-            assert orientation in EXIF_IMAGE_ROTATIONS, 'Mirrored rotations are not supported'
-            image = image.rotate(EXIF_IMAGE_ROTATIONS[orientation], expand=True)
-    except Exception:
-        pass
-    return image
-
-
-def exif_without(pil_image, tag_ids):
-    """_remove_exif_tags: the image's getexif() with the tags popped"""
-    exif = pil_image.getexif()
-    if exif is not None:
-        for tag in tag_ids:
-            exif.pop(tag, None)
-    return exif
-
-
-def exif_preserving_save(pil_image, output_file, quality='keep', default_quality=DEFAULT_QUALITY, tags_to_exclude=None):
-    """visualization_utils.exif_preserving_save with tags_to_exclude (a tuple of tag ids here): the EXIF block without them,
-    the quality 'kept' only for a JPEG source; once more without the quality, then without the EXIF block"""
-    exif = pil_image.getexif()
-    if (exif is not None) and (tags_to_exclude is not None):
-        exif = exif_without(pil_image, tags_to_exclude)
-    if pil_image.format != 'JPEG':
-        if quality == 'keep':
-            quality = default_quality
-    for kwargs in ({'quality': quality}, {}):
-        try:
-            if exif is not None:
-                pil_image.save(output_file, exif=exif, **kwargs)
-            else:
-                pil_image.save(output_file, **kwargs)
-            return
-        except Exception:
-            pass
-    pil_image.save(output_file)
 
 
 def finish_image(im, annotations_this_image, input_size, output_size):
@@ -214,6 +163,7 @@ def plan_job(job, target_size, correct_size_image_handling, no_enlarge_width):
         job['sampling'], job['quant'] = 2, list(jpeg_host.quant_tables(DEFAULT_QUALITY))
     job['probe'], job['source_size'], job['size'], job['resized'] = p, tuple(source_size), (width, height), resized
     job['exif'], job['comment'] = exif, src['comment']
+    return job
 
 
 def _light_job(index, image_data, input_folder, output_folder):
@@ -305,15 +255,6 @@ def resize_coco_dataset(input_folder, input_filename, output_folder, output_file
     if output_filename is not None:
         write_json(output_filename, d)
     return d
-
-
-def write_json(path, content):
-    """ct_utils.write_json with its defaults"""
-    parent_dir = os.path.dirname(path)
-    if len(parent_dir) > 0:
-        os.makedirs(parent_dir, exist_ok=True)
-    with open(path, 'w', newline='\n', encoding='utf-8') as f:
-        json.dump(content, f, indent=1, default=None, ensure_ascii=True)
 
 
 def main(argv=None):

@@ -7,7 +7,7 @@ as -1, the three ways to "no resize" ((-1, -1), no_enlarge_width, already that s
 assertion `Invalid image resize target`, which becomes that file's 'error', 'skipped' for an existing target without
 overwrite, os.makedirs of the target's folder, the enumeration of path_utils.find_images (recursive glob of *.*, the
 reference's extension list, sorted, relative, forward slashes), output_folder None as resizing in place, the assertion on
-pool_type, and exif_preserving_save with its quirks (separate_detections.exif_preserving_save): a resized, rotated or
+pool_type, and exif_preserving_save with its quirks (ref_utils.exif_preserving_save): a resized, rotated or
 converted image has no format, so quality 'keep' becomes 85 at 4:2:0 and an integer quality is passed through; an unresized
 plain RGB JPEG keeps its format, so 'keep' re-encodes it with the source's own tables and sampling; the EXIF block is the
 image's getexif() as Pillow serialises it, the Orientation tag of a file load_image turned included.  The reference loads
@@ -32,7 +32,6 @@ CLI: python -m megadetector_amd.resize_images INPUT_FOLDER [OUTPUT_FOLDER] --tar
 """
 
 import argparse
-import glob
 import os
 import sys
 from functools import partial
@@ -40,25 +39,14 @@ from functools import partial
 from . import device_render as DR
 from .gray_scale import _reference_truncation_rule
 from .preview import HostLeg
-from .separate_detections import DEFAULT_BLUR_QUALITY as DEFAULT_QUALITY
-from .separate_detections import exif_preserving_save
+from .ref_utils import DEFAULT_SAVE_QUALITY as DEFAULT_QUALITY
+from .ref_utils import exif_preserving_save, quality_argument
+from .ref_utils import find_images as _find_images
 
-#: reference path_utils.IMG_EXTENSIONS
-IMG_EXTENSIONS = ('.jpg', '.jpeg', '.gif', '.png', '.tif', '.tiff', '.bmp', '.webp', '.avif')
+#: path_utils.find_images(dirname, recursive, return_relative_paths=True, convert_slashes=True)
+find_images = partial(_find_images, return_relative_paths=True)
 COUNT_KEYS = ('files', 'resized', 'unresized', 'skipped', 'errors', 'gpu', 'host', 'files_decoded_gpu', 'files_decoded_pil',
               'decode_chunks', 'resample_calls', 'encode_calls')
-
-
-def find_images(dirname, recursive=False):
-    """path_utils.find_images(dirname, recursive, return_relative_paths=True, convert_slashes=True)"""
-    assert os.path.isdir(dirname), '{} is not a folder'.format(dirname)
-    if recursive:
-        strings = glob.glob(os.path.join(dirname, '**', '*.*'), recursive=True)
-    else:
-        strings = glob.glob(os.path.join(dirname, '*.*'))
-    image_files = [s for s in strings if os.path.splitext(s)[1].lower() in IMG_EXTENSIONS]
-    image_files = sorted(os.path.relpath(fn, dirname) for fn in image_files)
-    return [fn.replace('\\', '/') for fn in image_files]
 
 
 def resize_target(size, target_width=-1, target_height=-1, no_enlarge_width=False):
@@ -152,7 +140,7 @@ def _count_result(counts, result, resized):
 
 def plan_job(job, target_width, target_height, no_enlarge_width, quality):
     """What the device needs for one file, before any pixel is decoded: fills job['probe', 'source_size', 'size', 'resized',
-    'sampling', 'quant', 'exif', 'comment'].  Raises preview.HostLeg, and whatever else the planning raises also sends the file
+    'sampling', 'quant', 'exif', 'comment'] and returns the job.  Raises preview.HostLeg, and whatever else the planning raises also sends the file
     to the host leg, which then raises what the reference raises."""
     from . import jpeg_host
     from .device_decode import plan_source
@@ -180,20 +168,15 @@ def plan_job(job, target_width, target_height, no_enlarge_width, quality):
             raise HostLeg('a quality whose tables quant_tables does not give')
     job['probe'], job['source_size'], job['size'], job['resized'] = p, tuple(source_size), (width, height), resized
     job['exif'], job['comment'] = src['exif'], src['comment']
+    return job
 
 
 def render_chunk(ctx, torch, device, chunk, clock, plan, counts, done):
-    """One decode chunk of a resize tool: every file planned and read (plan(job) fills the job as plan_job does, or raises),
-    then decoded, ONE resample call, ONE encode call, then the files written and done(job) called for each.
-    -> the jobs the host leg has to make"""
+    """One decode chunk of a resize tool: every file planned and read (plan(job) fills the job as plan_job does and returns
+    it, or raises), then decoded by the GPU's decoder alone (a file it flags is the host leg's as it is), ONE resample call,
+    ONE encode call, then the files written and done(job) called for each.  -> the jobs the host leg has to make"""
     from .device_decode import decode_scans
-    host, jobs = [], []
-    for job in chunk:
-        try:
-            plan(job)
-            jobs.append(job)
-        except Exception:
-            host.append(job)
+    jobs, host = DR.plan_each(chunk, plan)
     if not jobs:
         return host
     with clock('decode'):
@@ -202,18 +185,17 @@ def render_chunk(ctx, torch, device, chunk, clock, plan, counts, done):
     tensors = [t for t in decoded if t is not None]
     jobs = [j for j, t in zip(jobs, decoded) if t is not None]
     counts['files_decoded_gpu'] += len(jobs)
-    if not jobs:
-        return host
-    tensors, called = DR.resample_stage(ctx, torch, device, tensors, [j['source_size'] for j in jobs], [j['size'] for j in jobs], clock)
-    counts['resample_calls'] += called
-    with clock('encode'):
-        files = DR.encode_sampled(ctx, device, tensors, jobs)
-    counts['encode_calls'] += 1
-    for j, data in zip(jobs, files):
-        with open(j['output'], 'wb') as f:
-            f.write(data)
-        done(j)
-    counts['gpu'] += len(jobs)
+
+    def encode(tensors, jobs):
+        with clock('encode'):
+            return DR.encode_sampled(ctx, device, tensors, jobs), 1
+
+    def write(job, data):
+        DR.write_bytes(job['output'], data)
+        done(job)
+
+    if jobs:
+        DR.render_jobs(ctx, torch, device, jobs, tensors, counts, clock, encode, write, draw=False)
     return host
 
 
@@ -313,10 +295,6 @@ def resize_image_folder(input_folder, output_folder=None, target_width=-1, targe
                          overwrite=overwrite, backend=backend, device=device, ctx=ctx, profile=profile, counts=counts)
 
 
-def _quality(s):
-    return s if s == 'keep' else int(s)
-
-
 def main(argv=None):
     parser = argparse.ArgumentParser(description='Resize every image of a folder (in place without an output folder)')
     parser.add_argument('input_folder')
@@ -324,7 +302,7 @@ def main(argv=None):
     parser.add_argument('--target_width', type=int, default=-1)
     parser.add_argument('--target_height', type=int, default=-1)
     parser.add_argument('--no_enlarge_width', action='store_true')
-    parser.add_argument('--quality', type=_quality, default='keep', help="'keep' or an integer JPEG quality")
+    parser.add_argument('--quality', type=quality_argument, default='keep', help="'keep' or an integer JPEG quality")
     parser.add_argument('--no_recursive', action='store_true')
     parser.add_argument('--no_overwrite', action='store_true')
     parser.add_argument('--n_workers', type=int, default=10, help='size of the host leg\'s pool')

@@ -33,6 +33,7 @@ import sys
 import threading
 import time
 from datetime import datetime
+from functools import partial
 
 import numpy as np
 
@@ -45,6 +46,7 @@ from . import crops as crops_mod
 from . import blur as blur_mod
 from . import preview as preview_mod
 from .jpeg_host import ScanFailure
+from .ref_utils import write_json as _write_json
 
 # reference run_detector_batch.py:86-119
 default_loaders = 4
@@ -89,13 +91,7 @@ def parse_kvp_list(items, kv_separator='='):
     return d
 
 
-def write_json(path, content, indent=1):
-    """reference ct_utils.py:210-251 (force_str=True)"""
-    parent = os.path.dirname(path)
-    if parent:
-        os.makedirs(parent, exist_ok=True)
-    with open(path, 'w', newline='\n', encoding='utf-8') as f:
-        json.dump(content, f, indent=indent, default=str, ensure_ascii=True)
+write_json = partial(_write_json, force_str=True)               # reference ct_utils.py:210-251 with force_str=True
 
 
 def _sort_by_key(items, key, reverse=False):

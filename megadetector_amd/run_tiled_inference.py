@@ -31,10 +31,8 @@ Multi-GPU sharding by image is not implemented here.
 import argparse
 import json
 import os
-import string
 import sys
 import tempfile
-import unicodedata
 import uuid
 from concurrent.futures import ThreadPoolExecutor
 
@@ -44,6 +42,7 @@ from . import run_detector
 from .constants import CONF_DIGITS, COORD_DIGITS, DEFAULT_OUTPUT_CONFIDENCE_THRESHOLD
 from .feed import load_image
 from .jpeg_host import check_quality
+from .ref_utils import clean_filename
 from .run_detector_batch import (default_loaders, find_images, load_checkpoint, parse_kvp_list, write_checkpoint,
                                  write_json, write_results_to_file)
 
@@ -52,20 +51,6 @@ nms_iou_threshold = 0.45            # de-duplication of detections from overlapp
 default_tile_size = [1280, 1280]
 default_n_patch_extraction_workers = 1
 default_pool_type = 'thread'
-
-_VALID_FILENAME_CHARS = '~-_.() ' + string.ascii_letters + string.digits
-
-
-def clean_filename(filename, char_limit=255, force_lower=False):
-    """reference path_utils.clean_filename: strip path components, keep ASCII file-name characters only"""
-    separator = '\\' if '\\' in filename else '/'
-    filename = separator.join(c.strip() for c in filename.replace('\\', '/').split('/'))
-    cleaned = unicodedata.normalize('NFKD', filename).encode('ASCII', 'ignore').decode()
-    cleaned = ''.join(c for c in cleaned if c in _VALID_FILENAME_CHARS)
-    if char_limit is not None:
-        cleaned = cleaned[:char_limit]
-    return cleaned.lower() if force_lower else cleaned
-
 
 def get_patch_boundaries(image_size, patch_size, patch_stride=None):
     """

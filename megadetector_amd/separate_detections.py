@@ -50,6 +50,7 @@ from functools import partial
 from . import device_render as DR
 from . import preview as PV
 from .blur import DEFAULT_BLUR_QUALITY, blur_rectangle
+from .ref_utils import exif_preserving_save, path_is_abs
 
 friendly_folder_names = {'animal': 'animals', 'person': 'people', 'vehicle': 'vehicles'}
 default_line_thickness = 8
@@ -88,10 +89,6 @@ class SeparateDetectionsIntoFoldersOptions:
         self.remove_empty_folders = False
         self.verbose = False
         self.keep_source_blocks = False                  #: (not the reference's) manipulated copies keep the source's JPEG blocks
-
-
-def _path_is_abs(p):
-    return (len(p) > 1) and (p[0] == '/' or p[1] == ':')
 
 
 def is_float(s):
@@ -169,7 +166,7 @@ def resolve_options(options, results):
     """
     images = results['images']
     for im in images:
-        assert not _path_is_abs(im['file']), 'Cannot process results with absolute image paths'
+        assert not path_is_abs(im['file'], leading_backslash=False), 'Cannot process results with absolute image paths'
     default_threshold = options.threshold
     if default_threshold is None:
         default_threshold = get_typical_confidence_threshold_from_results(results)
@@ -334,35 +331,6 @@ def category_passes(detections, categories_above_threshold, options):
     return passes
 
 
-def exif_preserving_save(pil_image, output_file, quality='keep', default_quality=DEFAULT_BLUR_QUALITY):
-    """visualization_utils.py:196-301 with its default arguments: EXIF kept, the quality 'kept' only for a JPEG source; once
-    more without the quality, then without the EXIF block"""
-    exif = pil_image.getexif()
-    if pil_image.format != 'JPEG':
-        if quality == 'keep':
-            quality = default_quality
-    successful_write = False
-    try:
-        if exif is not None:
-            pil_image.save(output_file, exif=exif, quality=quality)
-        else:
-            pil_image.save(output_file, quality=quality)
-        successful_write = True
-    except Exception:
-        pass
-    if not successful_write:
-        try:
-            if exif is not None:
-                pil_image.save(output_file, exif=exif)
-            else:
-                pil_image.save(output_file)
-            successful_write = True
-        except Exception:
-            pass
-    if not successful_write:
-        pil_image.save(output_file)
-
-
 def rectangles_to_blur(detections, options, width, height):
     """the rectangles with area of detections_to_blur, in the order they are applied"""
     rects = [blur_rectangle(d['bbox'], width, height) for d in detections_to_blur(detections, options)]
@@ -511,8 +479,8 @@ def _render_job_host(job, options):
 # ---- the device leg ----------------------------------------------------------------------------------------------------------------
 
 def _plan_job(job, options):
-    """What the device needs for one manipulated copy, before any pixel is decoded; raises preview.HostLeg (the host leg then
-    raises what the reference raises)."""
+    """What the device needs for one manipulated copy, before any pixel is decoded: fills the job and returns it; raises
+    preview.HostLeg (the host leg then raises what the reference raises)."""
     from . import jpeg_host
     from .device_decode import plan_source
     p, (width, height) = plan_source(job['source'], job['target'], keep_data=True)
@@ -532,6 +500,7 @@ def _plan_job(job, options):
     job['keep'] = bool(getattr(options, 'keep_source_blocks', False) and src['keep'])
     if job['keep']:
         job['changed'] = DR.changed_rectangles(job['rects'], job['plan'].ops)
+    return job
 
 
 def _job_bytes(job):
@@ -542,26 +511,21 @@ def _job_bytes(job):
 
 def _render_chunk_device(ctx, torch, device, jobs, clock, options, counts):
     """The manipulated copies of one chunk, by the device render path (device_render).  -> the jobs the host leg has to make"""
-    from .device_decode import decode_stage
     # (with copies that keep their blocks the sources' planes stay until the chunk is written)
-    pixels, refused, coefficients = decode_stage(ctx, torch, device, options.base_input_folder, [j['file'] for j in jobs],
-                                                 {j['file']: j['probe'] for j in jobs}, counts, clock, any(j['keep'] for j in jobs))
-    host = [j for j in jobs if j['file'] in refused]                      # the device did not decode it
-    jobs = [j for j in jobs if j['file'] not in refused]
-    if not jobs:
-        return host
-    tensors = [pixels[j['file']] for j in jobs]
-    DR.blur_and_draw(ctx, device, tensors, jobs, clock)
-    # (a copy the kept call flagged is re-encoded whole)
-    files, calls, flagged = DR.encode_copies(ctx, device, tensors, jobs, [coefficients[j['file']][0] if j['keep'] else None for j in jobs],
-                                             clock, True)
-    counts['encode_calls'] += calls
-    counts['kept'] += sum(j['keep'] for j in jobs) - flagged
-    counts['kept_refused'] += flagged
-    for j, data in zip(jobs, files):
-        with open(j['target'], 'wb') as f:
-            f.write(data)
-    counts['gpu'] += len(jobs)
+    jobs, tensors, host, coefficients = DR.decode_front(ctx, torch, device, jobs, options.base_input_folder, counts, clock,
+                                                        any(j['keep'] for j in jobs))
+
+    def encode(tensors, jobs):
+        # (a copy the kept call flagged is re-encoded whole)
+        files, calls, flagged = DR.encode_copies(ctx, device, tensors, jobs, [coefficients[j['file']][0] if j['keep'] else None for j in jobs],
+                                                 clock, True)
+        counts['kept'] += sum(j['keep'] for j in jobs) - flagged
+        counts['kept_refused'] += flagged
+        return files, calls
+
+    if jobs:                                                              # (a copy is never resized: no resample_jobs)
+        DR.blur_and_draw(ctx, device, tensors, jobs, clock)
+        DR.encode_and_write(jobs, tensors, counts, encode, lambda job, data: DR.write_bytes(job['target'], data))
     return host
 
 
@@ -569,13 +533,7 @@ def _render_device(jobs, options, ctx, counts, profile):
     """-> the jobs that go to the host leg: those that could not be planned, then those the chunks gave back (run_chunks
     without an order)"""
     import torch
-    host, planned = [], []
-    for job in jobs:
-        try:
-            _plan_job(job, options)
-            planned.append(job)
-        except Exception:
-            host.append(job)                                              # (what the reference raises, the host leg raises)
+    planned, host = DR.plan_each(jobs, partial(_plan_job, options=options))
     return DR.run_chunks(ctx, torch, planned, _job_bytes, partial(_render_chunk_device, options=options, counts=counts), counts,
                          profile, host, DR.file_twice)
 

@@ -44,7 +44,6 @@ import json
 import math
 import os
 import random
-import re
 import sys
 from collections import defaultdict
 from copy import deepcopy
@@ -54,6 +53,7 @@ from types import SimpleNamespace
 
 from . import device_render as DR
 from . import preview as PV
+from .ref_utils import clean_filename, open_image
 from .resize_images import resize_target
 
 COUNT_KEYS = ('sampled', 'rendered', 'skipped', 'unopened', 'gpu', 'host', 'files_decoded_gpu', 'files_decoded_pil', 'decode_chunks',
@@ -128,8 +128,7 @@ def classes_for_image(image, image_id_to_annotations, cat_id_to_name):
 
 def category_page_name(category_name):
     """clean_filename(category_name, force_lower=True, replace_whitespace='_') + '.html'"""
-    from .postprocess_batch_results import clean_filename
-    return re.sub(r'\s+', '_', clean_filename(category_name).lower()) + '.html'
+    return clean_filename(category_name, force_lower=True, replace_whitespace='_') + '.html'
 
 
 def check_restated(options, image_base_dir):
@@ -450,7 +449,6 @@ def render_host(info, output_dir, options, label_map):
     """_render_image_info :589-660 by the reference's own PIL calls.  -> RENDERED, SKIPPED (an existing file without
     force_rendering) or UNOPENED (no file)"""
     from PIL import Image
-    from .postprocess_batch_results import open_image
     img_path = info['img_path']
     output_full_path = _output_path(info, output_dir)
     if (os.path.isfile(output_full_path)) and (not options.force_rendering):
@@ -513,63 +511,21 @@ def plan_job(info, options, label_map, thin_outlines=True):
             'quality': quality, 'comment': comment}
 
 
-def _job_bytes(job):
-    """device bytes of a planned image in its decode chunk: its decoded pixels and its resized ones"""
-    (w, h), (tw, th) = job['source_size'], job['size']
-    return w * h * 3 + (tw * th * 3 if (tw, th) != (w, h) else 0)
-
-
-def encode_files(ctx, device, tensors, jobs, quality, stream=0):
-    """ONE mdhip_jpeg_encode call (device_render.read_encoded) for the rendered images of a chunk: -> the files Image.save
-    writes at `quality`, a job's 'comment' where Pillow puts the COM segment it carries from the source"""
-    from . import jpeg_host
-    sizes = [j['size'] for j in jobs]
-    capacity = sum(w * h * 3 // 2 + 64 * ((w + 15) // 16) * ((h + 15) // 16) + 64 for w, h in sizes)
-    host, offs, lens, _ = DR.read_encoded(
-        lambda out_ptr, capacity: ctx.jpeg_encode([t.data_ptr() for t in tensors], sizes, [w * 3 for w, _ in sizes], quality, out_ptr,
-                                                  capacity, stream),
-        capacity, device, 'mdhip_jpeg_encode')
-    ql, qc = jpeg_host.quant_tables(quality)
-    return [jpeg_host.sampled_file(w, h, ql, qc, 2, host[o:o + n].tobytes(), b'', j['comment']) if j['comment']
-            else jpeg_host.jfif_file(w, h, quality, host[o:o + n].tobytes()) for j, (w, h), o, n in zip(jobs, sizes, offs, lens)]
-
-
 def _render_chunk_device(ctx, torch, device, jobs, clock, output_dir, counts):
-    """The images of one chunk, by the device render path.  -> the jobs the host leg has to render"""
-    from .device_decode import decode_stage
-    pixels, refused, _ = decode_stage(ctx, torch, device, '', [j['file'] for j in jobs], {j['file']: j['probe'] for j in jobs},
-                                      counts, clock)
-    host = [j for j in jobs if j['file'] in refused]                       # the device did not decode it
-    jobs = [j for j in jobs if j['file'] not in refused]
-    if not jobs:
-        return host
-    sizes = [j['size'] for j in jobs]
-    rendered, resampled = DR.resample_stage(ctx, torch, device, [pixels[j['file']] for j in jobs], [j['source_size'] for j in jobs],
-                                            sizes, clock)
-    counts['resample_calls'] += resampled
-    if DR.draw_plans(ctx, [t.data_ptr() for t in rendered], sizes, [j['plan'] for j in jobs], device, clock=clock):
-        counts['draw_calls'] += 1
-    with clock('encode'):
-        files = encode_files(ctx, device, rendered, jobs, jobs[0]['quality'])
-    counts['encode_calls'] += 1
-    for j, data in zip(jobs, files):
-        with open(_output_path(j['info'], output_dir), 'wb') as f:
-            f.write(data)
-    counts['gpu'] += len(jobs)
-    return host
+    """The images of one chunk, by the device render path.  -> the entries the host leg has to render"""
+    jobs, tensors, host, _ = DR.decode_front(ctx, torch, device, jobs, '', counts, clock)
+    if jobs:
+        DR.render_jobs(ctx, torch, device, jobs, tensors, counts, clock, partial(DR.encode_whole, ctx, clock, jobs[0]['quality']),
+                       lambda job, data: DR.write_bytes(_output_path(job['info'], output_dir), data))
+    return [j['info'] for j in host]
 
 
 def _render_device(to_render, output_dir, options, label_map, ctx, counts, profile, thin_outlines):
     """-> the entries of to_render that go to the host leg, in their order"""
     import torch
-    host, planned = [], []
-    for info in to_render:
-        try:
-            planned.append(plan_job(info, options, label_map, thin_outlines))
-        except Exception:
-            host.append(info)
+    planned, host = DR.plan_each(to_render, lambda info: plan_job(info, options, label_map, thin_outlines))
     place = {id(info): i for i, info in enumerate(to_render)}
-    return DR.run_chunks(ctx, torch, planned, _job_bytes, partial(_render_chunk_device, output_dir=output_dir, counts=counts), counts,
+    return DR.run_chunks(ctx, torch, planned, DR.job_bytes, partial(_render_chunk_device, output_dir=output_dir, counts=counts), counts,
                          profile, host, DR.file_twice, lambda job: [job['info']], lambda info: place[id(info)])
 
 

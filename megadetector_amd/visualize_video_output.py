@@ -53,7 +53,6 @@ import json
 import os
 import random
 import sys
-import unicodedata
 
 from . import device_render as DR
 from . import preview as PV
@@ -61,6 +60,7 @@ from .avi import AviError, AviFile, write_mjpeg_avi
 from .blur import DEFAULT_BLUR_RADIUS, BlurOptions, blur_rectangle, select_detections
 from .constants import DEFAULT_DETECTOR_LABEL_MAP
 from .crops import Product
+from .ref_utils import clean_filename, insert_before_extension, path_is_abs, quality_argument
 
 DEFAULT_CLASSIFICATION_THRESHOLD = 0.4
 DEFAULT_DETECTION_THRESHOLD = 0.15
@@ -69,7 +69,6 @@ SKIPPED_STRING = 'Skipped'
 NOT_MJPEG_STRING = 'not a Motion-JPEG AVI'
 VIDEO_EXTENSIONS = ('.mp4', '.avi', '.mpeg', '.mpg', '.mov', '.mkv', '.flv')        # detection/video_utils.py:35
 DEFAULT_HOST_QUALITY = 85                                 # exif_preserving_save's default_quality: a frame that is no RGB JPEG
-_VALID_FILENAME_CHARS = '~-_.() abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789'       # utils/path_utils.py:46
 
 
 class VideoVisualizationOptions:
@@ -102,36 +101,6 @@ class VideoVisualizationOptions:
 
 
 # ---- the reference's support functions -----------------------------------------------------------------------------------------
-
-def path_is_abs(p):
-    """utils/path_utils.py:334"""
-    return (len(p) > 1) and (p[0] == '/' or p[1] == ':' or p[0] == '\\')
-
-
-def clean_filename(filename, force_lower=False):
-    """utils/path_utils.py:568 with its default arguments"""
-    separator = '/'
-    if '\\' in filename:
-        separator = '\\'
-    filename = filename.replace('\\', '/')
-    filename = separator.join([c.strip() for c in filename.split('/')])
-    if separator == '\\':
-        filename = filename.replace('/', '\\')
-    cleaned = unicodedata.normalize('NFKD', filename).encode('ASCII', 'ignore').decode()
-    cleaned = ''.join([c for c in cleaned if c in _VALID_FILENAME_CHARS])[:255]
-    if force_lower:
-        cleaned = cleaned.lower()
-    return cleaned
-
-
-def insert_before_extension(filename, s):
-    """utils/path_utils.py:254 for a string that is not empty"""
-    assert len(filename) > 0
-    name, ext = os.path.splitext(filename)
-    output_string = '{}.{}{}'.format(name, s, ext)
-    assert output_string != filename, 'Input and output filenames are identical'
-    return output_string
-
 
 def is_video_file(s):
     return os.path.splitext(s)[1].lower() in VIDEO_EXTENSIONS
@@ -306,7 +275,7 @@ def plan_video(video_entry, classification_label_map, options, video_dir, out_di
         if options.include_category_names_in_filenames == 'start':
             output_fn_relative = category_names + '_' + output_fn_relative
         else:
-            output_fn_relative = insert_before_extension(output_fn_relative, category_names)
+            output_fn_relative = insert_before_extension(output_fn_relative, category_names, check=True)
     output_fn_abs = os.path.join(out_dir, output_fn_relative)
     parent_dir = os.path.dirname(output_fn_abs)
     if len(parent_dir) > 0:
@@ -941,10 +910,6 @@ def visualize_video_output(detector_output_path, out_dir, video_dir, options=Non
 
 # ---- command line ----------------------------------------------------------------------------------------------------------------
 
-def _quality(s):
-    return s if s == 'keep' else int(s)
-
-
 def main(argv=None):
     parser = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                                      description='Render videos with bounding boxes predicted by a detector above a confidence '
@@ -969,7 +934,7 @@ def main(argv=None):
     parser.add_argument('--blur_category_names', type=str, default=None,
                         help='Comma-separated detection category names to blur before drawing, e.g. "person" (not in the reference)')
     parser.add_argument('--blur_radius', type=float, default=DEFAULT_BLUR_RADIUS, help='Radius of the blur (not in the reference)')
-    parser.add_argument('--quality', type=_quality, default='keep',
+    parser.add_argument('--quality', type=quality_argument, default='keep',
                         help="'keep': re-encode a touched frame with the stored frame's tables and sampling; 1 .. 95: Pillow's "
                              "quality, 4:2:0 (not in the reference)")
     parser.add_argument('--keep_source_blocks', action='store_true',

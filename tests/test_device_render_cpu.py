@@ -438,6 +438,328 @@ def test_encode_copies_makes_one_call_of_each_encoder_the_jobs_need(monkeypatch,
     assert run([]) == (([], 0, 0), [])
 
 
+# ---- the chunk body: plan_each, decode_front, render_jobs ----------------------------------------------------------------------------
+
+def test_plan_each_sends_what_raises_to_the_host_leg_in_order():
+    def plan(item):
+        if item % 3 == 0:
+            raise PV.HostLeg('a file the device does not decode') if item else ZeroDivisionError()
+        return {'item': item}
+
+    assert DR.plan_each(range(8), plan) == ([{'item': k} for k in (1, 2, 4, 5, 7)], [0, 3, 6])
+    assert DR.plan_each([], plan) == ([], [])
+    with pytest.raises(KeyboardInterrupt):                                 # (not an Exception: not the host leg's)
+        DR.plan_each([1], lambda item: (_ for _ in ()).throw(KeyboardInterrupt()))
+
+
+def test_job_bytes_counts_the_resized_pixels_only_where_the_size_changes():
+    assert DR.job_bytes({'source_size': (12, 8), 'size': (12, 8)}) == 12 * 8 * 3
+    assert DR.job_bytes({'source_size': (12, 8), 'size': (6, 4)}) == 12 * 8 * 3 + 6 * 4 * 3
+
+
+class _Chunk:
+    """One chunk on stand-ins: decode_stage refuses `refused` and gives every other file one _Tensor, under clock('decode');
+    draw_plans, draw_plans_from and blur_rects record instead of calling the device; `log` holds every call in its order."""
+
+    def __init__(self, monkeypatch, refused=(), profile=True):
+        self.torch, self.ctx, self.log, self.ms = _DeviceTorch(), _Context(), [], ({} if profile else None)
+        self.clock = DR.Clock(_Torch(), 'cuda:1', self.ms)
+        self.counts = {k: 0 for k in ('gpu', 'files_decoded_gpu', 'files_decoded_pil', 'resample_calls', 'draw_calls', 'encode_calls')}
+        self.pixels = {}
+        self.ctx.resample_lanczos = lambda *args: self.log.append(('resample', list(args[0]), list(args[4])))
+
+        def decode_stage(ctx, torch, device, image_base, files, probes, counts, clock, keep_coefficients=False):
+            assert ctx is self.ctx and torch is self.torch and device == 'cuda:1' and counts is self.counts
+            assert list(probes) == list(files) and all(probes[f] == 'probe of ' + f for f in files)
+            self.log.append(('decode', image_base, list(files), keep_coefficients))
+            with clock('decode'):
+                for k, f in enumerate(f for f in files if f not in refused):
+                    self.pixels[f] = _Tensor(0, 0x10 * (k + 1))
+            counts['files_decoded_gpu'] += len(self.pixels)
+            return dict(self.pixels), set(refused), ({f: (7, None) for f in self.pixels} if keep_coefficients else None)
+
+        def draw_plans(ctx, ptrs, sizes, plans, device, stream=0, clock=None):
+            if not any(p.ops for p in plans):
+                return False
+            with clock('draw'):
+                self.log.append(('draw', list(ptrs), list(sizes)))
+            return True
+
+        def draw_plans_from(ctx, src_ptrs, sizes, dst_ptrs, dst_src, plans, device, stream=0, clock=None):
+            with clock('draw'):
+                self.log.append(('draw', list(dst_ptrs), [sizes[k] for k in dst_src]))
+            return True
+
+        def blur_rects(ctx, ptrs, sizes, rects_per_image, radius, stream=0):
+            self.log.append(('blur', list(ptrs), [list(r) for r in rects_per_image]))
+            return True
+
+        monkeypatch.setattr(DD, 'decode_stage', decode_stage)
+        monkeypatch.setattr(DR, 'draw_plans', draw_plans)
+        monkeypatch.setattr(DR, 'draw_plans_from', draw_plans_from)
+        monkeypatch.setattr(DR, 'blur_rects', blur_rects)
+
+    def args(self):
+        return self.ctx, self.torch, 'cuda:1'
+
+    def encode(self, tensors, jobs):
+        with self.clock('encode'):
+            self.log.append(('encode', [t.data_ptr() for t in tensors], [j['name'] for j in jobs]))
+        return ['file of ' + j['name'] for j in jobs], 1
+
+    def write(self, job, data):
+        self.log.append(('write', job['name'], data))
+
+    def kinds(self):
+        return [entry[0] for entry in self.log]
+
+
+def _job(name, file, source_size=(12, 8), size=None, ops=True, **more):
+    plan = _plan([('rect', 1, 2, 3, 4, 0x0000FF)]) if ops else PV.RenderPlan()
+    return dict({'name': name, 'file': file, 'probe': 'probe of ' + file, 'source_size': source_size, 'size': size or source_size,
+                 'plan': plan}, **more)
+
+
+def test_decode_front_decodes_each_distinct_file_once_and_gives_the_jobs_of_a_refused_file_to_the_host(monkeypatch):
+    """one file refused, two jobs on one file (compare_batch_results): the file is decoded once, its jobs share the tensor, and
+    all jobs of the refused file come back for the host leg, in their order"""
+    chunk = _Chunk(monkeypatch, refused={'b.jpg'})
+    jobs = [_job('a1', 'a.jpg'), _job('b1', 'b.jpg'), _job('c1', 'c.jpg'), _job('a2', 'a.jpg'), _job('b2', 'b.jpg')]
+    taken, tensors, host, coefficients = DR.decode_front(*chunk.args(), jobs, 'base', chunk.counts, chunk.clock)
+    assert chunk.log == [('decode', 'base', ['a.jpg', 'b.jpg', 'c.jpg'], False)] and coefficients is None
+    assert [j['name'] for j in taken] == ['a1', 'c1', 'a2'] and [j['name'] for j in host] == ['b1', 'b2']
+    assert all(t is j for t, j in zip(taken + host, [jobs[0], jobs[2], jobs[3], jobs[1], jobs[4]]))
+    assert tensors[0] is tensors[2] is chunk.pixels['a.jpg'] and tensors[1] is chunk.pixels['c.jpg']
+    assert set(chunk.ms) == {'decode'} and chunk.counts['files_decoded_gpu'] == 2
+    # the sources' planes are asked for, and handed on, only on request (separate_detections with keep_source_blocks)
+    chunk = _Chunk(monkeypatch)
+    taken, _, host, coefficients = DR.decode_front(*chunk.args(), jobs[:1], '', chunk.counts, chunk.clock, True)
+    assert chunk.log == [('decode', '', ['a.jpg'], True)] and coefficients == {'a.jpg': (7, None)} and host == []
+
+
+def test_render_jobs_resamples_draws_encodes_and_only_then_writes(monkeypatch):
+    """sizes that change for some jobs and not for others: ONE resample call, the source tensors reused where the size stays;
+    ONE draw call on the images at their final sizes; ONE encoder call; every file written after it, in the jobs' order"""
+    chunk = _Chunk(monkeypatch)
+    jobs = [_job('a', 'a.jpg', (12, 8), (6, 4)), _job('b', 'b.jpg', (5, 7)), _job('c', 'c.jpg', (9, 9), (18, 18), ops=False), _job('d', 'd.jpg')]
+    jobs, tensors, host, _ = DR.decode_front(*chunk.args(), jobs, '', chunk.counts, chunk.clock)
+    DR.render_jobs(*chunk.args(), jobs, tensors, chunk.counts, chunk.clock, chunk.encode, chunk.write)
+    a, b, c, d = (t.data_ptr() for t in tensors)
+    new_a, new_c = (t.data_ptr() for t in chunk.torch.made)
+    assert [t.n for t in chunk.torch.made] == [6 * 4 * 3, 18 * 18 * 3] and host == []
+    assert chunk.log[1:] == [('resample', [a, c], [(6, 4), (18, 18)]),
+                             ('draw', [new_a, b, new_c, d], [(6, 4), (5, 7), (18, 18), (12, 8)]),
+                             ('encode', [new_a, b, new_c, d], ['a', 'b', 'c', 'd']),
+                             ('write', 'a', 'file of a'), ('write', 'b', 'file of b'), ('write', 'c', 'file of c'), ('write', 'd', 'file of d')]
+    assert chunk.counts == {'gpu': 4, 'files_decoded_gpu': 4, 'files_decoded_pil': 0, 'resample_calls': 1, 'draw_calls': 1, 'encode_calls': 1}
+    assert set(chunk.ms) == {'decode', 'resample', 'draw', 'encode'}       # postprocess_batch_results, visualize_db
+
+
+def test_render_jobs_makes_no_draw_call_for_plans_without_operations(monkeypatch):
+    chunk = _Chunk(monkeypatch)
+    jobs = [_job('a', 'a.jpg', ops=False), _job('b', 'b.jpg', ops=False)]
+    jobs, tensors, _, _ = DR.decode_front(*chunk.args(), jobs, '', chunk.counts, chunk.clock)
+    DR.render_jobs(*chunk.args(), jobs, tensors, chunk.counts, chunk.clock, chunk.encode, chunk.write)
+    assert chunk.kinds() == ['decode', 'encode', 'write', 'write'] and chunk.torch.made == []
+    assert chunk.counts['draw_calls'] == 0 and chunk.counts['resample_calls'] == 0 and chunk.counts['encode_calls'] == 1
+    assert set(chunk.ms) == {'decode', 'encode'}
+    # and none at all, whatever the plans hold, for a tool that does not draw (the resize tools)
+    chunk = _Chunk(monkeypatch)
+    jobs = [_job('a', 'a.jpg', (12, 8), (6, 4))]
+    del jobs[0]['plan']
+    jobs, tensors, _, _ = DR.decode_front(*chunk.args(), jobs, '', chunk.counts, chunk.clock)
+    DR.render_jobs(*chunk.args(), jobs, tensors, chunk.counts, chunk.clock, chunk.encode, chunk.write, draw=False)
+    assert chunk.kinds() == ['decode', 'resample', 'encode', 'write'] and set(chunk.ms) == {'decode', 'resample', 'encode'}
+
+
+def test_render_jobs_needs_every_counter_it_moves(monkeypatch):
+    """a counter the tool's counts lack is an error, not a silent miss (separate_detections, which counts neither resample nor
+    draw calls, does not go through render_jobs)"""
+    for missing in ('resample_calls', 'draw_calls', 'encode_calls', 'gpu'):
+        chunk = _Chunk(monkeypatch)
+        del chunk.counts[missing]
+        jobs, tensors, _, _ = DR.decode_front(*chunk.args(), [_job('a', 'a.jpg', (12, 8), (6, 4))], '', chunk.counts, chunk.clock)
+        with pytest.raises(KeyError, match=missing):
+            DR.render_jobs(*chunk.args(), jobs, tensors, chunk.counts, chunk.clock, chunk.encode, chunk.write)
+
+
+def _tool_chunks(monkeypatch, tmp_path, chunk):
+    """the chunk bodies of the five tools on the stand-ins of `chunk`, each writing below tmp_path: name -> (run(jobs) -> what
+    the body returns for the host leg, the jobs of a chunk over a.jpg, b.jpg and c.jpg)"""
+    from types import SimpleNamespace
+    from megadetector_amd import compare_batch_results as C
+    from megadetector_amd import crops
+    from megadetector_amd import postprocess_batch_results as PB
+    from megadetector_amd import resize_images as R
+    from megadetector_amd import separate_detections as SD
+    from megadetector_amd import visualize_db as VD
+
+    def encode_windows(ctx, ptrs, pitches, rects, quality, stream=0, comments=None):
+        chunk.log.append(('encode', list(ptrs), quality))
+        return [b'window %d' % k for k in range(len(ptrs))]
+
+    def encode_copies(ctx, device, tensors, jobs, source_ptrs, clock, reencode_flagged, stream=0):
+        with clock('encode_kept'):
+            chunk.log.append(('encode', [t.data_ptr() for t in tensors], source_ptrs))
+        return [b'copy'] * len(jobs), 1, 1
+
+    def encode_sampled(ctx, device, tensors, jobs, stream=0):
+        chunk.log.append(('encode', [t.data_ptr() for t in tensors], 'sampled'))
+        return [b'sampled'] * len(jobs)
+
+    def decode_scans(ctx, torch, device, scans, keep_coefficients=False):
+        chunk.log.append(('decode', list(scans)))
+        return [None if s == 'scan of b.jpg' else _Tensor(0, 0x10 * (k + 1)) for k, s in enumerate(scans)], [None] * len(scans)
+
+    monkeypatch.setattr(crops, 'encode_windows', encode_windows)
+    monkeypatch.setattr(DR, 'encode_copies', encode_copies)
+    monkeypatch.setattr(DR, 'encode_sampled', encode_sampled)
+    monkeypatch.setattr(DD, 'decode_scans', decode_scans)
+    out = str(tmp_path)
+    os.makedirs(os.path.join(out, 'rendered_images'))
+    os.makedirs(os.path.join(out, 'detections'))
+    chunk.counts.update(kept=0, kept_refused=0)
+    files = ('a.jpg', 'b.jpg', 'c.jpg')
+    path = lambda tool, f: os.path.join(out, tool + '_' + f)
+    plain = lambda tool, **more: [_job(f[0], f, (12, 8), (6, 4) if f == 'c.jpg' else None, **dict({k: v(f) for k, v in more.items()})) for f in files]
+    options = SimpleNamespace(image_base_dir='base', output_dir=out, base_input_folder='base', image_folder='base')
+    args, done = chunk.args() + (None, chunk.clock), []
+    return {
+        'postprocess': (lambda jobs: PB._render_chunk_device(*args[:3], jobs, chunk.clock, options, chunk.counts),
+                        plain('postprocess', decision=lambda f: {'category_string': 'detections', 'file': f}, sample_name=lambda f: 'detections_' + f)),
+        'visualize_db': (lambda jobs: VD._render_chunk_device(*args[:3], jobs, chunk.clock, out, chunk.counts),
+                         plain('visualize_db', info=lambda f: {'output_file_name': 'visualize_db_' + f}, quality=lambda f: 75, comment=lambda f: None)),
+        'separate': (lambda jobs: SD._render_chunk_device(*args[:3], jobs, chunk.clock, options, chunk.counts),
+                     [dict(j, size=j['source_size']) for j in plain('separate', target=lambda f: path('separate', f), rects=lambda f: [(0, 0, 2, 2)],
+                                                                   keep=lambda f: f == 'a.jpg')]),
+        'compare': (lambda jobs: C._render_chunk_device(*args[:3], C.group_by_file(jobs), chunk.clock, options, chunk.counts),
+                    plain('compare', output_path=lambda f: path('compare', f)) + [_job('a2', 'a.jpg', ops=False, output_path=path('compare', 'a2.jpg'))]),
+        'resize': (lambda jobs: R.render_chunk(*args[:3], jobs, chunk.clock, lambda j: dict(j, probe={'scan': 'scan of ' + j['file']}), chunk.counts,
+                                               done.append),
+                   plain('resize', output=lambda f: path('resize', f))),
+    }
+
+
+CLOCK_KEYS = {'postprocess': {'decode', 'resample', 'draw', 'encode'}, 'visualize_db': {'decode', 'resample', 'draw', 'encode'},
+              'compare': {'decode', 'resample', 'draw', 'encode'}, 'separate': {'decode', 'blur', 'draw', 'encode_kept'},
+              'resize': {'decode', 'resample', 'encode'}}
+
+
+@pytest.mark.parametrize('tool', sorted(CLOCK_KEYS))
+def test_the_tools_chunk_bodies_refuse_one_file_and_render_the_rest(monkeypatch, tmp_path, tool):
+    """b.jpg is refused by the decoder: its jobs come back for the host leg, a.jpg and c.jpg (which is resized, except by
+    separate_detections) are rendered in ONE call of each kind under the clock keys the tool has always had, and their files
+    are on disk only after the encoder call"""
+    chunk = _Chunk(monkeypatch, refused={'b.jpg'})
+    run, jobs = _tool_chunks(monkeypatch, tmp_path, chunk)[tool]
+    if tool == 'separate':                                                # (it keeps neither counter)
+        del chunk.counts['resample_calls'], chunk.counts['draw_calls']
+    written = lambda: sorted(n for _, _, names in os.walk(str(tmp_path)) for n in names)
+    real = chunk.log.append
+    seen = []
+    chunk.log = type('Log', (list,), {'append': lambda self, entry: (seen.append((entry[0], written())), real(entry), list.append(self, entry))})()
+    host = run(jobs)
+    b = [j for j in jobs if j['file'] == 'b.jpg']
+    # what the host leg gets is what the tool's run_chunks orders and its host leg renders: the decision, the entry, else the job
+    assert len(host) == len(b) == 1
+    if tool in ('postprocess', 'visualize_db'):
+        assert host[0] is b[0]['decision' if tool == 'postprocess' else 'info']
+    elif tool == 'resize':                                                # (its plan stand-in returns a copy of the job)
+        assert host[0]['name'] == 'b' and host[0]['output'] == b[0]['output']
+    else:
+        assert host[0] is b[0]
+    kinds = [k for k, _ in seen]
+    assert kinds == {'separate': ['decode', 'blur', 'draw', 'encode'], 'resize': ['decode', 'resample', 'encode']}.get(
+        tool, ['decode', 'resample', 'draw', 'encode'])
+    assert all(files == [] for _, files in seen)                           # nothing is written before the last device call returned
+    n = 3 if tool == 'compare' else 2
+    assert len(written()) == n and chunk.counts['gpu'] == n and chunk.counts['encode_calls'] == 1
+    assert chunk.counts.get('resample_calls') == (None if tool == 'separate' else 1)
+    assert chunk.counts.get('draw_calls') == {'separate': None, 'resize': 0}.get(tool, 1)
+    assert set(chunk.ms) == CLOCK_KEYS[tool]
+    if tool == 'separate':
+        assert (chunk.counts['kept'], chunk.counts['kept_refused']) == (0, 1)          # one copy keeps, and the stand-in flags one
+        assert [e for e in chunk.log if e[0] == 'decode'][0][3] is True and chunk.log[-1][2] == [7, None]
+    if tool == 'compare':                                                 # a.jpg decoded once; its job without operations is the shared image
+        assert [e for e in chunk.log if e[0] == 'decode'][0][2] == ['a.jpg', 'b.jpg', 'c.jpg']
+        a, c = chunk.pixels['a.jpg'].data_ptr(), chunk.pixels['c.jpg'].data_ptr()
+        assert [e for e in chunk.log if e[0] == 'resample'] == [('resample', [c], [(6, 4)])]
+        ptrs = chunk.log[-1][1]                                           # the jobs by file: a, a2, c
+        assert ptrs[1] == a and a not in (ptrs[0], ptrs[2]) and c not in ptrs
+
+
+def test_visualize_db_gives_the_entry_of_a_refused_file_to_the_host_leg_in_its_place(monkeypatch, tmp_path):
+    """the whole device leg (_render_device, run_chunks with the tool's order) around a file the decoder refuses: the entries
+    come back -- not the jobs, which the order does not know -- in the order of to_render, after the entry that was not planned"""
+    from megadetector_amd import crops
+    from megadetector_amd import visualize_db as VD
+    chunk = _Chunk(monkeypatch, refused={'b.jpg'})
+    monkeypatch.setattr(crops, 'encode_windows', lambda ctx, ptrs, *args, **kw: [b'window'] * len(ptrs))
+    os.makedirs(str(tmp_path / 'rendered_images'))
+    infos = [{'img_path': f, 'output_file_name': f} for f in ('x.png', 'a.jpg', 'b.jpg', 'c.jpg')]
+
+    def plan_job(info, options, label_map, thin_outlines):
+        if info['img_path'] == 'x.png':
+            raise PV.HostLeg('a file the device does not decode')
+        return _job(info['img_path'][0], info['img_path'], info=info, quality=75, comment=None)
+
+    monkeypatch.setattr(VD, 'plan_job', plan_job)
+    monkeypatch.setitem(__import__('sys').modules, 'torch', chunk.torch)   # (_render_device imports it for run_chunks)
+    chunk.counts['decode_chunks'] = 0
+    host = VD._render_device(list(reversed(infos)), str(tmp_path), None, None, chunk.ctx, chunk.counts, False, True)
+    assert len(host) == 2 and host[0] is infos[2] and host[1] is infos[0]
+    assert sorted(os.listdir(str(tmp_path / 'rendered_images'))) == ['a.jpg', 'c.jpg'] and chunk.counts['gpu'] == 2
+
+
+@pytest.mark.parametrize('tool', sorted(CLOCK_KEYS))
+def test_the_tools_chunk_bodies_stop_after_the_decode_when_every_file_is_refused(monkeypatch, tmp_path, tool):
+    chunk = _Chunk(monkeypatch, refused={'a.jpg', 'b.jpg', 'c.jpg'})
+    run, jobs = _tool_chunks(monkeypatch, tmp_path, chunk)[tool]
+    if tool == 'resize':                                                  # (its decoder stand-in flags b.jpg only)
+        jobs = [j for j in jobs if j['file'] == 'b.jpg']
+    before = dict(chunk.counts)
+    host = run(jobs)
+    assert len(host) == len(jobs) and chunk.kinds() == ['decode'] and chunk.torch.made == []
+    assert chunk.counts == before and chunk.counts['gpu'] == 0
+    assert [n for _, _, names in os.walk(str(tmp_path)) for n in names] == []
+
+
+def test_encode_windows_writes_a_window_with_a_comment_through_sampled_file(monkeypatch):
+    """visualize_db: Pillow carries a source's COM segment into the file it saves, so such a window is written by sampled_file
+    with the quality's standard tables at 4:2:0 (sampling 2) around the same scan; every other window by jfif_file"""
+    from types import SimpleNamespace
+    from megadetector_amd import crops
+    scans = [bytes([k]) * (k + 3) for k in range(3)]
+    calls = []
+
+    def read_encoded(call, capacity, device, what):
+        assert what == 'mdhip_jpeg_encode' and device == 'cuda:1'
+        blob = b''.join(scans)
+        offs = [0, len(scans[0]), len(scans[0]) + len(scans[1])]
+        return np.frombuffer(blob, np.uint8), offs, [len(s) for s in scans], []
+
+    monkeypatch.setattr(DR, 'read_encoded', read_encoded)
+    for name in ('sampled_file', 'jfif_file'):
+        real = getattr(J, name)
+        monkeypatch.setattr(J, name, lambda *args, name=name, real=real: calls.append((name, args)) or real(*args))
+    ctx = SimpleNamespace(device=1)
+    rects, comments = [(0, 0, 16, 8), (2, 1, 10, 9), (0, 0, 24, 16)], [None, b'a comment', b'']
+    files = crops.encode_windows(ctx, [0x100, 0x200, 0x300], [48, 48, 72], rects, 60, comments=comments)
+    ql, qc = J.quant_tables(60)
+    assert [name for name, _ in calls] == ['jfif_file', 'sampled_file', 'jfif_file']
+    assert calls[0][1] == (16, 8, 60, scans[0]) and calls[2][1] == (24, 16, 60, scans[2])
+    w, h, got_ql, got_qc, sampling, scan, exif, comment = calls[1][1]
+    assert (w, h, sampling, scan, exif, comment) == (8, 8, 2, scans[1], b'', b'a comment')
+    assert np.array_equal(got_ql, ql) and np.array_equal(got_qc, qc)
+    assert files == [J.jfif_file(16, 8, 60, scans[0]), J.sampled_file(8, 8, ql, qc, 2, scans[1], b'', b'a comment'), J.jfif_file(24, 16, 60, scans[2])]
+    assert b'a comment' in files[1] and files[1] != J.jfif_file(8, 8, 60, scans[1])
+    # without comments: as it always was
+    del calls[:]
+    assert crops.encode_windows(ctx, [0x100, 0x200, 0x300], [48, 48, 72], rects, 60) == [J.jfif_file(w, h, 60, s) for (w, h), s in
+                                                                                         zip([(16, 8), (8, 8), (24, 16)], scans)]
+    assert [name for name, _ in calls] == ['jfif_file'] * 6
+
+
 # ---- pool_map ---------------------------------------------------------------------------------------------------------------------
 
 def test_pool_map_keeps_the_order_of_the_items():
