@@ -233,36 +233,19 @@ def run_detector_on_frames(detector, source, every_n_frames=None, frames_to_proc
     wanted = set(frames_to_process) if frames_to_process is not None else None
     last_wanted = max(wanted) if wanted else None
     batch_size = max(1, int(batch_size))
-    pipelined = hasattr(detector, 'start_batch') and hasattr(detector, 'finish_batch') and batch_size > 1
 
-    frame_filenames, results, inflight = [], [], []
-    extra = {'render': renderer} if renderer is not None and renderer.on_device else {}
+    frame_filenames, results = [], []
+    kw = dict(detection_threshold=detection_threshold, image_size=image_size, verbose=verbose)
+    if renderer is not None and renderer.on_device:
+        kw['render'] = renderer
 
-    def add(new):
+    def add(_, new, error, entry):
         if renderer is not None:
             renderer.take(new)
         results.extend(new)
 
-    def finish_oldest():
-        ticket, frames = inflight.pop(0)
-        add(detector.finish_batch(ticket))
-        del frames
-
-    def flush(frames, ids):
-        if not frames:
-            return
-        if batch_size == 1:
-            add([detector.generate_detections_one_image(frames[0], ids[0], detection_threshold=detection_threshold,
-                                                        image_size=image_size, verbose=verbose, **extra)])
-        elif pipelined:
-            inflight.append((detector.start_batch(list(frames), list(ids), detection_threshold=detection_threshold,
-                                                  image_size=image_size, verbose=verbose, **extra), list(frames)))
-            while len(inflight) >= 2:
-                finish_oldest()
-        else:
-            add(detector.generate_detections_one_batch(list(frames), list(ids), detection_threshold=detection_threshold,
-                                                       image_size=image_size, verbose=verbose, **extra))
-
+    # (nothing is caught: an exception of the detector ends the video, the caller makes it the video's failure)
+    window = run_detector_batch.DetectorWindow(detector, batch_size, True, kw, kw, add)
     frames, ids = [], []
     for frame_number, image in enumerate(source):
         if frame_number >= source.n_frames:
@@ -279,11 +262,11 @@ def run_detector_on_frames(detector, source, every_n_frames=None, frames_to_proc
         frames.append(image.materialise() if hasattr(image, 'materialise') else np.ascontiguousarray(image))
         ids.append(name)
         if len(frames) >= batch_size:
-            flush(frames, ids)
+            window.submit(frames, ids)
             frames, ids = [], []
-    flush(frames, ids)
-    while inflight:
-        finish_oldest()
+    if frames:
+        window.submit(frames, ids)
+    window.drain()
     if len(frame_filenames) == 0:
         if allow_empty_videos:
             print('Warning: found no frames')

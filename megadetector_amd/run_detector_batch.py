@@ -4,11 +4,13 @@ top of the HIP detector, emitting the same MegaDetector JSON.
 
 Mirrored entry points (same names, argument meaning and failure conventions):
   load_and_run_detector_batch   reference :1062-1439
-  _process_batch                reference :680-831   (batched path; threshold applied afterwards :766)
-  _process_image                reference :937-1056  (per-image path; threshold forwarded :988-994)
   write_checkpoint / load_checkpoint   reference :1465 / :1497
   write_results_to_file         reference :1546-1662
   main (CLI)                    reference :1763-2186 (the options that touch this path)
+The reference's loop bodies -- per image (:937-1056: threshold, image_size and augment forwarded :988-994), batched (:680-831:
+none of them forwarded, the threshold applied afterwards :766) and the queue consumer (:203-455) -- are one loop here: a feed per way images arrive (_inline_feed, _thread_feed, _ring_feed) delivers groups
+of loaded images and load failures, _BatchDriver does everything else with a group, and DetectorWindow holds every detector
+call, for this file and for process_video.
 New here (spec = reference notebooks/manage_local_batch.py:496-964):
   run_sharded                   one spawned worker process per GPU, balanced `i % G` sharding of the
                                 image list, host-side merge with duplicate/missing checks -- no
@@ -24,6 +26,7 @@ plain loop.
 """
 
 import argparse
+import contextlib
 import copy
 import json
 import os
@@ -341,137 +344,153 @@ def write_crop_result_files(final_output, options, base, crop_results_file=None,
         write_json(crops_output_file, per_crop)
 
 
-class _BatchPipeline:
+class DetectorWindow:
     """
-    Feeds batches of (file, image, meta_image, release) to the detector.  With a detector that has
-    start_batch / finish_batch (HIPDetector) two batches are kept in flight; otherwise every batch is
-    processed synchronously.  `release` (or None) is called once the detector no longer reads the pixels.
+    Every call of the detector, for this driver and for process_video.run_detector_on_frames: which entry point a batch
+    goes through, and the window of batches in flight.
+      batch size 1                          generate_detections_one_image with image_kw
+      pipelined, a detector with the pair   start_batch with batch_kw at once; finish_batch of its ticket when a second ticket
+                                            is outstanding, oldest first, and at drain(): the GPU works on one batch while
+                                            the host formats the one before it and assembles the next
+      otherwise                             generate_detections_one_batch with batch_kw
+    deliver(context, results, error, entry) gets what every call returned, `entry` naming the call.  The caller says what an
+    exception means: one of the classes in `catch` is delivered as `error` with no results -- from start_batch at once, ahead of
+    the ticket in flight -- and any other leaves submit() or drain().
     """
 
-    def __init__(self, detector, confidence_threshold, include_image_size, include_image_timestamp, on_results,
-                 depth=2, writers=()):
-        self.writers = writers
-        self.det = detector
-        self.thr = confidence_threshold
-        self.inc_size, self.inc_time = include_image_size, include_image_timestamp
-        self.on_results = on_results
-        self.async_ok = hasattr(detector, 'start_batch') and hasattr(detector, 'finish_batch')
-        self.depth = depth
+    def __init__(self, detector, batch_size, pipelined, image_kw, batch_kw, deliver, catch=()):
+        self.det, self.image_kw, self.batch_kw, self.deliver, self.catch = detector, image_kw, batch_kw, deliver, catch
+        if batch_size == 1:
+            self.entry = 'one_image'
+        elif pipelined and hasattr(detector, 'start_batch') and hasattr(detector, 'finish_batch'):
+            self.entry = 'start_batch'
+        else:
+            self.entry = 'one_batch'
         self.inflight = []
 
-    def submit(self, items):
-        if not items:
-            return
-        names = [it[0] for it in items]
-        images = [it[1] for it in items]
-        metas = [it[2] if it[2] is not None else it[1] for it in items]
-        releases = [it[3] for it in items if it[3] is not None]
-        if not self.async_ok:
-            try:
-                dets = self.det.generate_detections_one_batch(images, names, verbose=verbose, **_detector_kw(self.writers, self.det))
-                res = _filter_batch_output(dets, names, metas, self.thr, self.inc_size, self.inc_time)
-            except Exception as e:
-                print('Batch processing failure for {} images: {}'.format(len(images), str(e)))
-                res = [{'file': n, 'failure': FAILURE_INFER} for n in names]
-            _write_products(self.writers, res, images)
-            for r in releases:
-                r()
-            self.on_results(res)
-            return
+    def _awaited(self, entry, context, call):
+        results = error = None
         try:
-            ticket = self.det.start_batch(images, names, verbose=verbose, **_detector_kw(self.writers, self.det))
-        except Exception as e:
-            print('Batch processing failure for {} images: {}'.format(len(images), str(e)))
-            for r in releases:
-                r()
-            self.on_results([{'file': n, 'failure': FAILURE_INFER} for n in names])
-            return
-        self.inflight.append((ticket, names, metas, releases, images))
-        while len(self.inflight) >= self.depth:
-            self._finish_oldest()
+            results = call()
+        except self.catch as e:
+            error = e
+        self.deliver(context, results, error, entry)
+
+    def submit(self, images, names, context=None):
+        if self.entry == 'one_image':
+            self._awaited('one_image', context,
+                          lambda: [self.det.generate_detections_one_image(images[0], names[0], **self.image_kw)])
+        elif self.entry == 'one_batch':
+            self._awaited('one_batch', context, lambda: self.det.generate_detections_one_batch(images, names, **self.batch_kw))
+        else:
+            try:
+                ticket = self.det.start_batch(images, names, **self.batch_kw)
+            except self.catch as e:
+                self.deliver(context, None, e, 'start_batch')
+                return
+            self.inflight.append((ticket, context, images))         # (the pixels stay alive until finish_batch has read them)
+            while len(self.inflight) >= 2:
+                self._finish_oldest()
 
     def _finish_oldest(self):
-        ticket, names, metas, releases, images = self.inflight.pop(0)
-        try:
-            dets = self.det.finish_batch(ticket)
-            res = _filter_batch_output(dets, names, metas, self.thr, self.inc_size, self.inc_time)
-        except Exception as e:
-            print('Batch processing failure for {} images: {}'.format(len(names), str(e)))
-            res = [{'file': n, 'failure': FAILURE_INFER} for n in names]
-        _write_products(self.writers, res, images)
-        for r in releases:
-            r()
-        self.on_results(res)
+        ticket, context, _ = self.inflight.pop(0)
+        self._awaited('finish_batch', context, lambda: self.det.finish_batch(ticket))
 
     def drain(self):
         while self.inflight:
             self._finish_oldest()
 
 
-def _process_batch(image_items_batch, detector, confidence_threshold, quiet=False, image_size=None,
-                   include_image_size=False, include_image_timestamp=False, include_exif_tags=None,
-                   augment=False, writers=()):
+class _BatchDriver:
     """
-    reference :680-831.  Items are file names or (file, image, producer_id) tuples.  As in the
-    reference, the batched detector call receives neither the threshold nor image_size/augment
-    (:751-754); the confidence threshold is applied to its output (:766-767).
+    The loop body, once, for every feed.  A group is (items, failures): an item is (file, image, meta, release) -- meta the
+    object its size and timestamp are read from (None: the image), release (or None) frees what holds the pixels -- and a
+    failure a finished {'file', 'failure'} record.  A group's images go to the detector through one DetectorWindow; an
+    exception becomes FAILURE_INFER records; the batched call gets no threshold, it is applied to its output (reference
+    :751-767), the per-image call gets threshold, image_size and augment (:988-994); then metadata, the written products, the
+    releases -- after the call that read the pixels has returned, also when it raised -- and on_results, the group's failures
+    in front.  fed: the queue modes, whose batches go through the ticket pair.
     """
-    valid_images, valid_names, batch_results = [], [], []
-    for item in image_items_batch:
-        if isinstance(item, str):
+
+    def __init__(self, detector, batch_size, fed, confidence_threshold, quiet, image_size, include_image_size,
+                 include_image_timestamp, augment, writers, on_results):
+        self.batch_size, self.thr, self.quiet = batch_size, confidence_threshold, quiet
+        self.inc_size, self.inc_time = include_image_size, include_image_timestamp
+        self.writers, self.on_results = writers, on_results
+        products = _detector_kw(writers, detector)
+        self.window = DetectorWindow(
+            detector, batch_size, fed,
+            dict(detection_threshold=confidence_threshold, image_size=image_size, augment=augment, verbose=verbose, **products),
+            dict(verbose=verbose, **products), self._deliver, catch=Exception)
+        self.drain = self.window.drain
+
+    def submit(self, group):
+        items, failures = group
+        if not items:
+            self.on_results(failures)
+            return
+        if self.batch_size == 1 and not self.quiet:
+            print('Processing image {}'.format(items[0][0]))
+        self.window.submit([it[1] for it in items], [it[0] for it in items], group)
+
+    def _deliver(self, group, results, error, entry):
+        items, failures = group
+        names, images = [it[0] for it in items], [it[1] for it in items]
+        metas = [it[1] if it[2] is None else it[2] for it in items]
+        if error is None and entry == 'one_image':
+            if results[0].get('failure') is None:
+                _add_image_metadata(results[0], metas[0], self.inc_size, self.inc_time)
+        elif error is None:
             try:
-                image = load_image(item)
+                results = _filter_batch_output(results, names, metas, self.thr, self.inc_size, self.inc_time)
             except Exception as e:
-                print('Image {} cannot be loaded: {}'.format(item, str(e)))
-                batch_results.append({'file': item, 'failure': FAILURE_IMAGE_OPEN})
-                continue
-            name = item
-        else:
-            assert len(item) == 3
-            name, image, _ = item
-        valid_images.append(image)
-        valid_names.append(name)
-
-    valid_results = []
-    if valid_images:
-        try:
-            dets = detector.generate_detections_one_batch(valid_images, valid_names, verbose=verbose,
-                                                          **_detector_kw(writers, detector))
-            valid_results = _filter_batch_output(dets, valid_names, valid_images, confidence_threshold,
-                                                 include_image_size, include_image_timestamp)
-        except Exception as e:
-            print('Batch processing failure for {} images: {}'.format(len(valid_images), str(e)))
-            valid_results = [{'file': n, 'failure': FAILURE_INFER} for n in valid_names]
-        _write_products(writers, valid_results, valid_images)
-    batch_results.extend(valid_results)
-    return batch_results
+                error = e
+        if error is not None:
+            if entry != 'one_image':
+                print('Batch processing failure for {} images: {}'.format(len(names), str(error)))
+            elif not self.quiet:
+                print('Image {} cannot be processed: {}'.format(names[0], str(error)))
+            results = [{'file': n, 'failure': FAILURE_INFER} for n in names]
+        if error is None or entry in ('one_batch', 'finish_batch'):
+            # (outside the try blocks: a folder that cannot be written ends the run, it is no inference failure)
+            _write_products(self.writers, results, images)
+        for it in items:
+            if it[3] is not None:
+                it[3]()
+        self.on_results(failures + results)
 
 
-def _process_image(im_file, detector, confidence_threshold, image=None, quiet=False, image_size=None,
-                   include_image_size=False, include_image_timestamp=False, include_exif_tags=None,
-                   augment=False, writers=()):
-    """reference :937-1056 (the un-batched path: threshold, image_size and augment ARE forwarded)"""
-    if not quiet:
-        print('Processing image {}'.format(im_file))
-    if image is None:
-        try:
-            image = load_image(im_file)
-        except Exception as e:
-            if not quiet:
-                print('Image {} cannot be loaded: {}'.format(im_file, str(e)))
-            return {'file': im_file, 'failure': FAILURE_IMAGE_OPEN}
-    try:
-        result = detector.generate_detections_one_image(image, im_file, detection_threshold=confidence_threshold,
-                                                        image_size=image_size, augment=augment, verbose=verbose,
-                                                        **_detector_kw(writers, detector))
-    except Exception as e:
-        if not quiet:
-            print('Image {} cannot be processed: {}'.format(im_file, str(e)))
-        return {'file': im_file, 'failure': FAILURE_INFER}
-    _write_products(writers, [result], [image])
-    if 'failure' not in result or result.get('failure') is None:
-        _add_image_metadata(result, image, include_image_size, include_image_timestamp)
-    return result
+def _inline_feed(image_files, batch_size, quiet):
+    """the files grouped before they are loaded (reference :1297): a file that cannot be loaded takes its place in its group"""
+    for group in _group_into_batches(image_files, batch_size):
+        items, failures = [], []
+        for im_file in group:
+            try:
+                items.append((im_file, load_image(im_file), None, None))
+            except Exception as e:
+                if batch_size == 1 and not quiet:           # (the per-image path announces a file before it loads it)
+                    print('Processing image {}'.format(im_file))
+                if batch_size > 1 or not quiet:
+                    print('Image {} cannot be loaded: {}'.format(im_file, str(e)))
+                failures.append({'file': im_file, 'failure': FAILURE_IMAGE_OPEN})
+        yield items, failures
+
+
+def _accumulate(arrivals, batch_size, groups_of=None):
+    """the fed modes: valid items up to the batch size; a failure record travels as a group of its own the moment it arrives.
+    groups_of(items): the groups a full batch becomes (default: itself)"""
+    groups_of = groups_of or (lambda items: [(items, [])])
+    pending = []
+    for arrival in arrivals:
+        if isinstance(arrival, dict):
+            yield [], [arrival]
+            continue
+        pending.append(arrival)
+        if len(pending) >= batch_size:
+            yield from groups_of(pending)
+            pending = []
+    if pending:
+        yield from groups_of(pending)
 
 
 # --------------------------------------------------------------------------------------------
@@ -535,10 +554,8 @@ def _make_preprocessor(detector, detector_options):
     return pre
 
 
-def _run_detector_with_image_queue(image_files, detector, confidence_threshold, quiet, image_size,
-                                   include_image_size, include_image_timestamp, augment, loader_workers,
-                                   preprocess_on_image_queue, batch_size, on_results, detector_options=None,
-                                   writers=()):
+def _thread_feed(image_files, detector, image_size, loader_workers, batch_size, preprocess_on_image_queue=False,
+                 detector_options=None):
     q = queue.Queue(max_queue_size)
     file_q = queue.Queue()
     for f in image_files:
@@ -553,36 +570,19 @@ def _run_detector_with_image_queue(image_files, detector, confidence_threshold, 
                for i in range(n_workers)]
     for t in threads:
         t.start()
-    finished = 0
-    pending = []
-    pipe = _BatchPipeline(detector, confidence_threshold, include_image_size, include_image_timestamp, on_results,
-                          writers=writers)
 
-    def flush():
-        if pending:
-            if batch_size > 1:
-                pipe.submit([(f, im, None, None) for f, im, _ in pending])
+    def arrivals():
+        finished = 0
+        while finished < n_workers:
+            item = q.get()
+            if item is None:
+                finished += 1
+            elif isinstance(item[1], str):
+                yield {'file': item[0], 'failure': item[1]}
             else:
-                on_results([_process_image(f, detector, confidence_threshold, image=im, quiet=quiet,
-                                           image_size=image_size, include_image_size=include_image_size,
-                                           include_image_timestamp=include_image_timestamp, augment=augment,
-                                           writers=writers)
-                            for f, im, _ in pending])
-            pending.clear()
+                yield item[0], item[1], None, None
 
-    while finished < n_workers:
-        item = q.get()
-        if item is None:
-            finished += 1
-            continue
-        if isinstance(item[1], str):
-            on_results([{'file': item[0], 'failure': item[1]}])
-            continue
-        pending.append(item)
-        if len(pending) >= max(1, batch_size):
-            flush()
-    flush()
-    pipe.drain()
+    yield from _accumulate(arrivals(), batch_size)
     for t in threads:
         t.join()
 
@@ -597,12 +597,11 @@ ring_slots_per_batch_image = 3                  # one batch being filled, two in
 last_feed_counts = {}
 
 
-def _run_detector_with_shared_ring(image_files, detector, confidence_threshold, quiet, image_size,
-                                   include_image_size, include_image_timestamp, augment, loader_workers,
-                                   batch_size, on_results, gpu_jpeg=False, writers=()):
+@contextlib.contextmanager
+def _ring_feed(image_files, detector, image_size, want_meta, loader_workers, batch_size, gpu_jpeg=False):
     """
-    SURVEY.md 8(f) N1 (feed.py): spawned loader processes decode into a page-locked shared-memory ring,
-    the batches go through the detector's pipelined interface.  Same results as every other mode.
+    SURVEY.md 8(f) N1 (feed.py): spawned loader processes decode into a page-locked shared-memory ring.  A context: the
+    groups inside it, the ring open until the last batch in flight has been finished and its slots released.
     gpu_jpeg: the loaders only entropy-decode baseline JPEGs and the detector rebuilds their pixels on the GPU
     (feed.py decode='coefficients'); needs a detector that takes coefficient images (HIPDetector).
     gpu_jpeg='entropy': the loaders only parse the headers and the GPU Huffman-decodes too (feed.py decode='scan',
@@ -619,87 +618,55 @@ def _run_detector_with_shared_ring(image_files, detector, confidence_threshold, 
     entropy = gpu_jpeg == 'entropy'
     if entropy:
         last_feed_counts['scan'] = 0
-    bs = max(1, batch_size)
     n_workers = max(1, min(loader_workers, len(image_files)))
-    n_slots = ring_slots_per_batch_image * bs + n_workers
+    n_slots = ring_slots_per_batch_image * batch_size + n_workers
     try:
-        loader = feed.ProcessLoader(image_files, n_workers, n_slots, ring_slot_bytes,
-                                    want_meta=include_image_size or include_image_timestamp,
+        loader = feed.ProcessLoader(image_files, n_workers, n_slots, ring_slot_bytes, want_meta=want_meta,
                                     decode='scan' if entropy else 'coefficients' if gpu_jpeg else 'pixels')
     except (OSError, MemoryError) as e:
         # e.g. a container whose /dev/shm is smaller than the ring: the thread queue needs no shared memory
         print('Warning: cannot create the shared-memory ring ({} slots of {} MB: {}); using loader threads'.format(
             n_slots, ring_slot_bytes >> 20, str(e)))
-        return _run_detector_with_image_queue(image_files, detector, confidence_threshold, quiet, image_size,
-                                              include_image_size, include_image_timestamp, augment, loader_workers,
-                                              False, batch_size, on_results, writers=writers)
+        loader = None
+    if loader is None:
+        yield _thread_feed(image_files, detector, image_size, loader_workers, batch_size)
+        return
     ring = loader.ring
+    in_slot = {'slot': ring.view, 'jpeg': partial(feed.coefficient_image, ring), 'scan': partial(feed.scan_image, ring)}
+
+    def arrivals():
+        for kind, im_file, payload, shape, meta in loader:
+            last_feed_counts[kind] = last_feed_counts.get(kind, 0) + 1
+            meta_img = feed.ImageMeta(meta) if meta is not None else None
+            if kind == 'fail':
+                yield {'file': im_file, 'failure': FAILURE_IMAGE_OPEN}
+            elif kind in in_slot:
+                yield im_file, in_slot[kind](payload, shape), meta_img, partial(ring.release, payload)
+            else:
+                yield im_file, payload, meta_img, None
+
+    def decoded(pending):
+        """gpu_jpeg='entropy': the batch's scans become device coefficient images, or what PIL makes of a flagged file --
+        pixels, or the failure the loader would have reported, which goes ahead of the batch"""
+        kept = []
+        for (f, _, meta_img, release), im in zip(pending, detector.decode_scans([it[1] for it in pending])):
+            if isinstance(im, ScanFailure):
+                print('Image {} cannot be loaded:\n{}'.format(f, str(im.error)))
+                if release is not None:
+                    release()
+                yield [], [{'file': f, 'failure': FAILURE_IMAGE_OPEN}]
+            elif isinstance(im, np.ndarray) and release is not None:
+                release()                                # PIL's pixels are an array of this process: the slot is free
+                kept.append((f, im, meta_img, None))
+            else:
+                kept.append((f, im, meta_img, release))
+        if kept:
+            yield kept, []
+
     try:
         if hasattr(detector, 'start_batch'):
             ring.pin()
-        pipe = _BatchPipeline(detector, confidence_threshold, include_image_size, include_image_timestamp, on_results,
-                              writers=writers)
-        pending = []
-
-        def decode_scans():
-            """gpu_jpeg='entropy': the batch's scans become device coefficient images, or what PIL makes of a flagged file --
-            pixels, or the failure the loader would have reported"""
-            images = detector.decode_scans([it[1] for it in pending])
-            kept = []
-            for (f, _, meta_img, release), im in zip(pending, images):
-                if isinstance(im, ScanFailure):
-                    print('Image {} cannot be loaded:\n{}'.format(f, str(im.error)))
-                    if release is not None:
-                        release()
-                    on_results([{'file': f, 'failure': FAILURE_IMAGE_OPEN}])
-                elif isinstance(im, np.ndarray) and release is not None:
-                    release()                                # PIL's pixels are an array of this process: the slot is free
-                    kept.append((f, im, meta_img, None))
-                else:
-                    kept.append((f, im, meta_img, release))
-            pending[:] = kept
-
-        def flush():
-            if pending and entropy:
-                decode_scans()
-            if not pending:
-                return
-            if bs > 1:
-                pipe.submit(list(pending))
-            else:
-                for f, im, meta_img, release in pending:
-                    r = _process_image(f, detector, confidence_threshold, image=im, quiet=quiet,
-                                       image_size=image_size, include_image_size=False,
-                                       include_image_timestamp=False, augment=augment, writers=writers)
-                    if r.get('failure') is None and meta_img is not None:
-                        _add_image_metadata(r, meta_img, include_image_size, include_image_timestamp)
-                    if release is not None:
-                        release()
-                    on_results([r])
-            pending.clear()
-
-        for kind, im_file, payload, shape, meta in loader:
-            last_feed_counts[kind] = last_feed_counts.get(kind, 0) + 1
-            if kind == 'fail':
-                on_results([{'file': im_file, 'failure': FAILURE_IMAGE_OPEN}])
-                continue
-            meta_img = feed.ImageMeta(meta) if meta is not None else None
-            if kind == 'slot':
-                slot = payload
-                pending.append((im_file, ring.view(slot, shape), meta_img, (lambda s=slot: ring.release(s))))
-            elif kind == 'jpeg':
-                slot = payload
-                pending.append((im_file, feed.coefficient_image(ring, slot, shape), meta_img,
-                                (lambda s=slot: ring.release(s))))
-            elif kind == 'scan':
-                slot = payload
-                pending.append((im_file, feed.scan_image(ring, slot, shape), meta_img, (lambda s=slot: ring.release(s))))
-            else:
-                pending.append((im_file, payload, meta_img, None))
-            if len(pending) >= bs:
-                flush()
-        flush()
-        pipe.drain()
+        yield _accumulate(arrivals(), batch_size, decoded if entropy else None)
     finally:
         loader.close()
 
@@ -846,10 +813,9 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
     counts = {'images': 0, 'last_checkpoint': 0}
     crossing_rule = bool(use_image_queue)
 
-    def on_results(new_results, n_images=None):
+    def on_results(new_results):
         results.extend(new_results)
-        before = counts['images']
-        counts['images'] = before + (len(new_results) if n_images is None else n_images)
+        counts['images'] += len(new_results)
         if checkpoint_path is None or checkpoint_frequency is None or checkpoint_frequency <= 0:
             return
         if crossing_rule:
@@ -865,26 +831,20 @@ def load_and_run_detector_batch(model_file, image_file_names, checkpoint_path=No
     if gpu_jpeg and not (use_image_queue and not use_threads_for_queue):
         print('gpu_jpeg is ignored: it takes effect with --use_image_queue and loader processes only')
     if use_image_queue and not use_threads_for_queue and len(image_files) > 0:
-        _run_detector_with_shared_ring(image_files, detector, confidence_threshold, quiet, image_size,
-                                       include_image_size, include_image_timestamp, augment, loader_workers,
-                                       batch_size, on_results, gpu_jpeg='entropy' if gpu_jpeg == 'entropy' else bool(gpu_jpeg),
-                                       writers=writers)
+        groups_in = _ring_feed(image_files, detector, image_size, include_image_size or include_image_timestamp, loader_workers,
+                               batch_size, gpu_jpeg='entropy' if gpu_jpeg == 'entropy' else bool(gpu_jpeg))
     elif use_image_queue:
-        _run_detector_with_image_queue(image_files, detector, confidence_threshold, quiet, image_size,
-                                       include_image_size, include_image_timestamp, augment, loader_workers,
-                                       preprocess_on_image_queue, batch_size, on_results,
-                                       detector_options=detector_options, writers=writers)
-    elif batch_size > 1:
-        for batch in _group_into_batches(image_files, batch_size):
-            on_results(_process_batch(batch, detector, confidence_threshold, quiet, image_size,
-                                      include_image_size, include_image_timestamp, None, augment, writers=writers),
-                       len(batch))
+        groups_in = contextlib.nullcontext(_thread_feed(image_files, detector, image_size, loader_workers, batch_size,
+                                                        preprocess_on_image_queue, detector_options))
     else:
-        for im_file in image_files:
-            on_results([_process_image(im_file, detector, confidence_threshold, quiet=quiet, image_size=image_size,
-                                       include_image_size=include_image_size,
-                                       include_image_timestamp=include_image_timestamp, augment=augment,
-                                       writers=writers)])
+        groups_in = contextlib.nullcontext(_inline_feed(image_files, batch_size, quiet))
+    driver = _BatchDriver(detector, batch_size, bool(use_image_queue), confidence_threshold, quiet, image_size, include_image_size,
+                          include_image_timestamp, augment, writers, on_results)
+    with groups_in as groups:
+        for group in groups:
+            driver.submit(group)
+            del group                   # (its images go before the feed loads the next group's)
+        driver.drain()
     # a loader process that died mid-list, or a result dropped anywhere above, must not pass silently
     have = set(r['file'] for r in results)
     missing = [f for f in image_files if f not in have]
